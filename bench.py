@@ -22,6 +22,9 @@ with respect to `value`):
                 256^3 grid (throughput reported, parity in tests/)
   parity        voxels that differ from the reference algorithm (oracle) on 128^3 samples
   cpu_baseline  the oracle timed on this host
+
+`--dump-outputs DIR` (N = 1) writes what the last timed step returned to its caller -- the fp32 field (whole up to 4 Mvoxel,
+else a fixed seeded sample with its voxel indices) and the fp64 extrema -- as DIR/*.npy, so two builds can be compared.
 """
 import argparse
 import json
@@ -80,7 +83,14 @@ def parse_args():
     ap.add_argument("--no-profile", action="store_true", help="do not record per-stage HIP events in the timed region")
     ap.add_argument("--force-slab", action="store_true", help="run the multi-GPU slab builder even at N = 1")
     ap.add_argument("--opt", action="append", default=[], help="library option name=value (sdfgpu_set_option)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (field, or a fixed seeded sample of it, and extrema) as DIR/*.npy")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.gpus > 1 or args.force_slab):
+        ap.error("--dump-outputs covers the single-GPU path (--gpus 1 without --force-slab)")
+    return args
 
 
 def relaunch_as_ranks(n):
@@ -234,6 +244,28 @@ def roofline_of(stage, ms, n_total, plane16, traffic_table=None, info=None):
                       "note": "SURVEY 8(d) bytes of the three materialised sweeps attributed to this kernel; a fused / "
                               "bit-parallel kernel moves fewer bytes, so this is an equivalence figure, not a hardware fraction"}
     return r
+
+
+DUMP_FULL_MAX_VOXELS = 1 << 22      # fields up to 16 MB are written whole; larger ones as a seeded sample of this many draws
+
+
+def dump_outputs(d, out, extrema):
+    """--dump-outputs: the device field `out` and the build's (max, min) as .npy files under `d` (64 MB at most in all).
+    Large fields are sampled at voxel indices drawn with a fixed seed (sorted, duplicates dropped), so two runs with the
+    same arguments -- or two builds of the project -- write the same voxels; the indices are written beside the values."""
+    import numpy as np
+    import torch
+
+    os.makedirs(d, exist_ok=True)
+    n_total = out.numel()
+    if n_total <= DUMP_FULL_MAX_VOXELS:
+        np.save(os.path.join(d, "sdf.npy"), out.cpu().numpy().astype(np.float32))
+    else:
+        idx = np.unique(np.random.default_rng(0).integers(0, n_total, size=DUMP_FULL_MAX_VOXELS, dtype=np.int64))
+        vals = out.reshape(-1)[torch.from_numpy(idx).to(out.device)].cpu().numpy()
+        np.save(os.path.join(d, "sdf_sample.npy"), vals.astype(np.float32))
+        np.save(os.path.join(d, "sdf_sample_index.npy"), idx.astype(np.float64))     # flat x*ny*nz + y*nz + z, exact below 2^53
+    np.save(os.path.join(d, "extrema.npy"), np.asarray(extrema, dtype=np.float64))
 
 
 def timed_loop(step, steps, fence):
@@ -558,6 +590,8 @@ def main():
             dominant_only = False
         ctx.set_profiling(0 if args.no_profile else (3 if dominant_only else 1))
     dt = timed_loop(step, args.steps, fence)
+    if args.dump_outputs:           # before any later loop touches `out`: the last timed step's field and extrema
+        dump_outputs(args.dump_outputs, out, ctx.get_extrema())
     per_rank_ms = [dt / args.steps * 1e3]
     if world > 1:
         mine = torch.tensor([dt, float(rank)], dtype=torch.float64, device=dev)

@@ -12,6 +12,7 @@
 
 int main(int argc, char** argv) {
     const bool compile_only_smoke = argc > 1 && std::string(argv[1]) == "--no-gpu";
+    const std::string sdf_path = argc > 1 && !compile_only_smoke ? argv[1] : "/tmp/tutorial.sdf";     // file round trip target
     const double resolution = 0.25;
     Eigen::Isometry3d origin_transform = Eigen::Isometry3d::Identity();
 #if SDF_TOOLS_HAVE_EIGEN
@@ -81,8 +82,8 @@ int main(int argc, char** argv) {
         ok = ok && same;
     }
     // file round trip (SDFZ)
-    sdf_tools::SignedDistanceField::SaveToFile(sdf, "/tmp/tutorial.sdf", true);
-    const sdf_tools::SignedDistanceField back = sdf_tools::SignedDistanceField::LoadFromFile("/tmp/tutorial.sdf");
+    sdf_tools::SignedDistanceField::SaveToFile(sdf, sdf_path, true);
+    const sdf_tools::SignedDistanceField back = sdf_tools::SignedDistanceField::LoadFromFile(sdf_path);
     ok = ok && back.GetImmutableRawData() == sdf.GetImmutableRawData() && back.GetFrame() == frame;
     // tagged-object map (reference tagged_object_collision_map.hpp): object 1 = the same box, object 2 = one far cell,
     // and one occupied cell without an object id

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Writes tests/golden/collision_map_serialized.hex: the bytes CollisionMapGrid::SerializeSelf produces (through pysdf_tools)
 for a small fixed grid.  A SELF-golden: it pins this repository's own wire format against accidental change (field order of
-/root/reference/src/sdf_tools/collision_map.cpp:21-62 over the in-tree arc_utilities primitives); it says nothing about
+the reference's src/sdf_tools/collision_map.cpp:21-62 over the in-tree arc_utilities primitives); it says nothing about
 byte interoperability with the reference, whose arc_utilities dependency is not vendored."""
 import os
 import sys

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Writes tests/golden/tagged_map_serialized.hex: the bytes TaggedObjectCollisionMapGrid::SerializeSelf produces (through
 pysdf_tools) for a small fixed grid.  A SELF-golden like collision_map_serialized.hex: it pins this repository's own wire
-format against accidental change (field order of /root/reference/src/sdf_tools/tagged_object_collision_map.cpp:23-75 over
+format against accidental change (field order of the reference's src/sdf_tools/tagged_object_collision_map.cpp:23-75 over
 the in-tree arc_utilities primitives); it says nothing about byte interoperability with the reference, whose
 arc_utilities dependency is not vendored -- wire-format parity stays unpinned."""
 import os

@@ -32,9 +32,9 @@ def test_cpp_client_compiles_links_and_refuses_without_gpu():
 
 
 @pytest.mark.gpu
-def test_cpp_client_reproduces_tutorial_scene():
+def test_cpp_client_reproduces_tutorial_scene(tmp_path):
     exe = _build()
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([exe, str(tmp_path / "tutorial.sdf")], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "tutorial scene OK" in r.stdout
 

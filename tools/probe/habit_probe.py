@@ -1,5 +1,5 @@
 import sys, os
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
 from sdf_tools_amd import capi, synth
 n=512; dev=torch.device("cuda",0)

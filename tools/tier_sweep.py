@@ -1,5 +1,5 @@
 import json, os, sys, time
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from sdf_tools_amd import capi, synth
 n = 512; shape = (n, n, n); dev = torch.device("cuda", 0)
