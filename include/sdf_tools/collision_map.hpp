@@ -1,8 +1,10 @@
 // CollisionMapGrid -- dense occupancy grid, API-compatible with the subset of
 // sdf_tools::CollisionMapGrid (reference include/sdf_tools/collision_map.hpp) on the SDF path:
 // COLLISION_CELL (:20-32), the constructors (:215-270), SetValue (:405-420) and
-// ExtractSignedDistanceField (:680-712).  Connected components, topology and RViz export are out
-// of scope.  Wire formats (N3): SerializeSelf / DeserializeSelf, SaveToFile /
+// ExtractSignedDistanceField (:680-712), and the connected components (UpdateConnectedComponents :564-618,
+// ExtractConnectedComponents :757-778, GetNumConnectedComponents hpp :503) computed on the GPU by sdfgpu_components_cells.
+// Topology (hole / void counting), component surfaces, convex segments and RViz export are out of scope (SURVEY.md
+// section 2, rows 2/8).  Wire formats (N3): SerializeSelf / DeserializeSelf, SaveToFile /
 // LoadFromFile ("CMGZ" / "CMGR") and the CollisionMap message pair in the field order of
 // src/sdf_tools/collision_map.cpp:21-62, :205-283, :285-315.  The byte layout of the primitives
 // (arc_utilities::SerializeFixedSizePOD / SerializeEigen / SerializeVector / SerializeString) is the in-tree
@@ -74,6 +76,9 @@ public:
     std::string GetFrame() const { return frame_; }
     void SetFrame(const std::string& f) { frame_ = f; }
     bool AreComponentsValid() const { return components_valid_; }
+    // For callers that write cells through GetMutableRawData() (SetValue does this itself): the stored components no longer
+    // describe the grid, so the next UpdateConnectedComponents() recomputes them.
+    void InvalidateConnectedComponents() { components_valid_ = false; }
 
     bool SetValue(const int64_t x, const int64_t y, const int64_t z, const COLLISION_CELL& value) override {
         if (!IndexInBounds(x, y, z)) return false;
@@ -105,6 +110,43 @@ public:
         return sdf_generation::ExtractSignedDistanceFieldDeviceFromCells(
             GetOriginTransform(), GetCellSizes(), GetNumXCells(), GetNumYCells(), GetNumZCells(), data_.data(),
             sizeof(COLLISION_CELL), offsetof(COLLISION_CELL, occupancy), unknown_is_filled, oob_value, GetFrame(), add_virtual_border);
+    }
+
+    // ---- connected components (reference collision_map.cpp:564-618, :757-778) ---------------------------------------------
+    // Two classes, occupancy > 0.5 and the rest (unknown and NaN join free space); 6-connectivity; components numbered 1..K in
+    // the order of the x -> y -> z scan.  Labels are written into every cell's `component`; an early-out when the stored ones are
+    // valid (also after deserialising a grid that carries them), as in the reference.
+    uint32_t UpdateConnectedComponents() {
+        if (components_valid_) return number_of_components_;
+        uint32_t count = 0;
+        if (!data_.empty()) {
+            const std::shared_ptr<sdf_generation::SharedGpuContext> ctx = sdf_generation::GpuContext::Shared();
+            const std::lock_guard<std::mutex> lock(ctx->mutex);
+            sdf_generation::ThrowOnStatus(
+                ctx->handle, sdfgpu_components_cells(ctx->handle, data_.data(), sizeof(COLLISION_CELL), offsetof(COLLISION_CELL, occupancy),
+                                                     offsetof(COLLISION_CELL, component), GetNumXCells(), GetNumYCells(),
+                                                     GetNumZCells(), &count));
+        }
+        number_of_components_ = count;
+        components_valid_ = true;
+        return number_of_components_;
+    }
+
+    std::pair<uint32_t, bool> GetNumConnectedComponents() const { return std::make_pair(number_of_components_, components_valid_); }
+
+    // Indices of each component, in scan order inside each (one counting pass, then one placement pass over the labels).
+    std::vector<std::vector<GRID_INDEX>> ExtractConnectedComponents() {
+        if (!components_valid_) UpdateConnectedComponents();
+        std::vector<size_t> sizes(number_of_components_, 0);
+        for (const COLLISION_CELL& cell : data_) sizes.at(cell.component - 1) += 1;
+        std::vector<std::vector<GRID_INDEX>> components(number_of_components_);
+        for (size_t c = 0; c < components.size(); ++c) components[c].reserve(sizes[c]);
+        const int64_t nx = GetNumXCells(), ny = GetNumYCells(), nz = GetNumZCells();
+        size_t i = 0;
+        for (int64_t x = 0; x < nx; ++x)
+            for (int64_t y = 0; y < ny; ++y)
+                for (int64_t z = 0; z < nz; ++z, ++i) components[data_[i].component - 1].emplace_back(x, y, z);
+        return components;
     }
 
     // ---- wire formats: collision_map.cpp:21-62 (fields), :205-283 (files), :285-315 (messages) ------------------------

@@ -7,8 +7,9 @@
 // (src/sdf_tools/tagged_object_collision_map.cpp:23-75, :77-240), TCMZ / TCMR files (:242-307) and the
 // TaggedObjectCollisionMap message pair (:309-339, msg/TaggedObjectCollisionMap.msg) -- byte format of the un-vendored
 // arc_utilities serialisers: "wire-format parity unpinned", like the other two containers.
-// Connected components, convex segmentation, topology and RViz export are out of scope (SURVEY.md section 2,
-// rows 7/8).  Every SDF is built on the GPU through sdfgpu_build_tagged_cells (device-side predicate).
+// The connected components (UpdateConnectedComponents, tagged_object_collision_map.cpp:340-380, same connectivity rule as
+// CollisionMapGrid's) are computed on the GPU by sdfgpu_components_cells.  Convex segmentation, topology and RViz export are
+// out of scope.  Every SDF is built on the GPU through sdfgpu_build_tagged_cells (device-side predicate).
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -111,6 +112,27 @@ public:
         return true;
     }
     bool SetValue(const GRID_INDEX& i, const TAGGED_OBJECT_COLLISION_CELL& v) override { return SetValue(i.x, i.y, i.z, v); }
+
+    // ---- connected components (reference tagged_object_collision_map.cpp:340-380): occupancy > 0.5 against the rest, whatever
+    // the object id; 6-connectivity; numbered 1..K in x -> y -> z scan order, written into every cell's `component`.
+    uint32_t UpdateConnectedComponents() {
+        if (components_valid_) return number_of_components_;
+        uint32_t count = 0;
+        if (!data_.empty()) {
+            const std::shared_ptr<sdf_generation::SharedGpuContext> ctx = sdf_generation::GpuContext::Shared();
+            const std::lock_guard<std::mutex> lock(ctx->mutex);
+            sdf_generation::ThrowOnStatus(
+                ctx->handle, sdfgpu_components_cells(ctx->handle, data_.data(), sizeof(TAGGED_OBJECT_COLLISION_CELL),
+                                                     offsetof(TAGGED_OBJECT_COLLISION_CELL, occupancy),
+                                                     offsetof(TAGGED_OBJECT_COLLISION_CELL, component), GetNumXCells(),
+                                                     GetNumYCells(), GetNumZCells(), &count));
+        }
+        number_of_components_ = count;
+        components_valid_ = true;
+        return number_of_components_;
+    }
+
+    std::pair<uint32_t, bool> GetNumConnectedComponents() const { return std::make_pair(number_of_components_, components_valid_); }
 
     // ---- wire formats: tagged_object_collision_map.cpp:23-75 (fields), :242-307 (files), :309-339 (messages) ------------
     using CellSerializer = std::function<uint64_t(const TAGGED_OBJECT_COLLISION_CELL&, std::vector<uint8_t>&)>;

@@ -365,6 +365,33 @@ int sdfgpu_voxelize_points_bits_device(sdfgpu_handle h, const float* d_points, i
                                        int64_t nx, int64_t ny, int64_t nz,
                                        uint32_t* d_bits, int clear_first, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Connected components of a two-class grid: CollisionMapGrid::UpdateConnectedComponents
+ * (reference src/sdf_tools/collision_map.cpp:564-618, topology_computation.hpp:25-150) on the GPU.
+ *   - a voxel is filled iff its bit is set (the bit field of sdfgpu_build_bits_device), its mask byte is nonzero, or its
+ *     cell's occupancy > 0.5f -- unknown (0.5) and NaN voxels are free; there is no unknown_is_filled here
+ *   - two voxels are in one component iff a path of face neighbours (6-connectivity) of their class joins them
+ *   - components are numbered 1 .. K in the order the reference's x -> y -> z scan meets them, i.e. by each component's
+ *     minimum linear index; the labels are therefore fully determined (bit-equal to the reference's) and every voxel gets
+ *     one >= 1.  K goes to *out_count.
+ *   - a grid of more than 2^32 - 1 voxels is refused (SDFGPU_ERR_INVALID_ARGUMENT): labels are uint32
+ * All three are synchronous: they return when the labels are written (the device form synchronises `stream` to read K).
+ * They use scratch of their own: the handle's SDF scratch, status block and learnt policy are left as they were.
+ *
+ *   sdfgpu_components_bits_device: d_bits (ceil(n / 32) words, 4-byte aligned) -> d_labels (n uint32, [nx][ny][nz]); a streaming
+ *       frame goes point cloud -> bits -> labels with sdfgpu_voxelize_points_bits_device in front.
+ *   sdfgpu_components: host mask (n bytes) -> host labels (n uint32).
+ *   sdfgpu_components_cells: raw cell records of `cell_stride` bytes (COLLISION_CELL: 8, 0, 4; TAGGED_OBJECT_COLLISION_CELL:
+ *       16, 0, 4), classified on the host into 1 bit per voxel while the pinned staging chunks fill; the labels come back
+ *       through the staging chunks and are written IN PLACE into each record's uint32 at component_offset.
+ * ------------------------------------------------------------------------- */
+int sdfgpu_components_bits_device(sdfgpu_handle h, const uint32_t* d_bits, int64_t nx, int64_t ny, int64_t nz,
+                                  uint32_t* d_labels, uint32_t* out_count, void* stream);
+int sdfgpu_components(sdfgpu_handle h, const uint8_t* filled, int64_t nx, int64_t ny, int64_t nz,
+                      uint32_t* out_labels, uint32_t* out_count);
+int sdfgpu_components_cells(sdfgpu_handle h, void* cells, size_t cell_stride, size_t occupancy_offset, size_t component_offset,
+                            int64_t nx, int64_t ny, int64_t nz, uint32_t* out_count);
+
 /* Red zones (round 6).  With SDFGPU_REDZONE=1 in the environment when sdfgpu_create runs -- or after
  * sdfgpu_set_option(h, "redzone", 1) -- every device allocation of the library (scratch fields, status block, extrema slots,
  * staging buffers, sdfgpu_device_malloc memory) carries 4 KiB of canary bytes in front and behind, and every entry point that

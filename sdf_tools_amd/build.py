@@ -33,8 +33,9 @@ def _hipcc():
 
 
 def build_libsdfgpu(force=False, verbose=False, out=None):
-    """Three translation units -> objects (compiled side by side) -> libsdfgpu.so: sdfgpu.hip (C ABI, host orchestration, most
-    kernels), sdfgpu_envelope_tu.hip (the far-field kernel's instantiations) and sdfgpu_dense6_tu.hip (the shell pass).  Each object is rebuilt when its
+    """Four translation units -> objects (compiled side by side) -> libsdfgpu.so: sdfgpu.hip (C ABI, host orchestration, most
+    kernels), sdfgpu_envelope_tu.hip (the far-field kernel's instantiations), sdfgpu_dense6_tu.hip (the shell pass) and
+    sdfgpu_components.hip (connected components).  Each object is rebuilt when its
     source or ANY header it can include is newer (a stale library after a header-only edit is the kind of bug that
     invalidates measurements without failing anything)."""
     from concurrent.futures import ThreadPoolExecutor
@@ -43,7 +44,8 @@ def build_libsdfgpu(force=False, verbose=False, out=None):
     env_hdrs = [os.path.join(CSRC, f) for f in ("sdfgpu_envelope_dc.hpp", "sdfgpu_kernels.hpp", "sdfgpu_sweep_x16.hpp")]
     d6_hdrs = [os.path.join(CSRC, f) for f in ("sdfgpu_dense6.hpp", "sdfgpu_dense3.hpp", "sdfgpu_dense.hpp", "sdfgpu_kernels.hpp")]
     units = [(os.path.join(CSRC, "sdfgpu.hip"), hdrs), (os.path.join(CSRC, "sdfgpu_envelope_tu.hip"), env_hdrs),
-             (os.path.join(CSRC, "sdfgpu_dense6_tu.hip"), d6_hdrs)]
+             (os.path.join(CSRC, "sdfgpu_dense6_tu.hip"), d6_hdrs),
+             (os.path.join(CSRC, "sdfgpu_components.hip"), [os.path.join(CSRC, "sdfgpu_components.hpp")])]
     extra = os.environ.get("SDFGPU_EXTRA_FLAGS", "").split()
     objdir = os.path.join(CSRC, ".obj" + ("_" + "".join(c for c in "".join(extra) if c.isalnum()) if extra else ""))
     os.makedirs(objdir, exist_ok=True)
@@ -60,7 +62,7 @@ def build_libsdfgpu(force=False, verbose=False, out=None):
     if verbose:
         for cmd in todo:
             print(" ".join(cmd))
-    with ThreadPoolExecutor(max_workers=3) as pool:
+    with ThreadPoolExecutor(max_workers=4) as pool:
         list(pool.map(subprocess.check_call, todo))
     cmd = [_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-pthread"] + objs + ["-o", lib]
     if verbose:

@@ -27,6 +27,7 @@ EXPORTS = [
     "sdfgpu_copy_to_host", "sdfgpu_copy_from_host", "sdfgpu_query_points", "sdfgpu_device_malloc", "sdfgpu_device_free",
     "sdfgpu_build_to_device", "sdfgpu_build_cells_to_device", "sdfgpu_upload_classified",
     "sdfgpu_build_bits_device", "sdfgpu_build_bits", "sdfgpu_voxelize_points_bits_device", "sdfgpu_debug_finish_table", "sdfgpu_redzone_check",
+    "sdfgpu_components_bits_device", "sdfgpu_components", "sdfgpu_components_cells",
 ]
 
 
@@ -106,6 +107,9 @@ def load_library():
     L.sdfgpu_copy_from_host.argtypes = [vp, vp, vp, ctypes.c_size_t, vp]
     L.sdfgpu_upload_classified.argtypes = [vp, vp, vp, sz, sz, ci, i64, vp, vp]
     L.sdfgpu_get_stage_times.argtypes = [vp, vp, vp]
+    L.sdfgpu_components_bits_device.argtypes = [vp, vp, i64, i64, i64, vp, vp, vp]
+    L.sdfgpu_components.argtypes = [vp, vp, i64, i64, i64, vp, vp]
+    L.sdfgpu_components_cells.argtypes = [vp, vp, sz, sz, sz, i64, i64, i64, vp]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is ctypes.c_int or name not in ("sdfgpu_version", "sdfgpu_last_error"):
@@ -286,6 +290,38 @@ class SdfGpu:
                                                 int(bool(add_virtual_border)), out.ctypes.data,
                                                 ctypes.byref(ext, 0), ctypes.byref(ext, 8)))
         return out, (float(ext[0]), float(ext[1]))
+
+    # ---- connected components (CollisionMapGrid::UpdateConnectedComponents, include/sdfgpu.h) -------------
+    def components(self, filled):
+        """filled: uint8/bool [nx,ny,nz].  Returns (labels uint32 [nx,ny,nz], K): 6-connected components of the filled and the
+        free voxels, numbered 1..K in x -> y -> z scan order."""
+        m = np.ascontiguousarray(filled, dtype=np.uint8)
+        if m.ndim != 3:
+            raise ValueError("mask must be [nx, ny, nz]")
+        out = np.empty(m.shape, dtype=np.uint32)
+        k = ctypes.c_uint32(0)
+        self._check(self._lib.sdfgpu_components(self._h, m.ctypes.data, *m.shape, out.ctypes.data, ctypes.byref(k)))
+        return out, int(k.value)
+
+    def components_bits_device(self, d_bits, shape, d_labels, stream=0):
+        """d_bits: device bit field (ceil(n / 32) words), d_labels: device uint32 [n].  Returns K (synchronises `stream`)."""
+        nx, ny, nz = (int(s) for s in shape)
+        k = ctypes.c_uint32(0)
+        self._check(self._lib.sdfgpu_components_bits_device(self._h, d_bits, nx, ny, nz, d_labels, ctypes.byref(k), stream or None))
+        return int(k.value)
+
+    def components_cells(self, cells, shape, cell_stride=8, occupancy_offset=0, component_offset=4):
+        """cells: writable contiguous records (COLLISION_CELL: 8, 0, 4; TAGGED_OBJECT_COLLISION_CELL: 16, 0, 4); the labels are
+        written into them in place.  Returns K."""
+        nx, ny, nz = (int(s) for s in shape)
+        if not (isinstance(cells, np.ndarray) and cells.flags.c_contiguous and cells.flags.writeable):
+            raise ValueError("cells must be a writable C-contiguous numpy array")
+        if cells.nbytes != nx * ny * nz * cell_stride:
+            raise ValueError("cells buffer size does not match shape * cell_stride")
+        k = ctypes.c_uint32(0)
+        self._check(self._lib.sdfgpu_components_cells(self._h, cells.ctypes.data, cell_stride, occupancy_offset, component_offset,
+                                                      nx, ny, nz, ctypes.byref(k)))
+        return int(k.value)
 
     def voxelize_points_bits_device(self, d_points, n_points, origin, resolution, shape, d_bits, clear_first=True, stream=0):
         nx, ny, nz = (int(s) for s in shape)

@@ -2,7 +2,7 @@
 // (module name, class names, method names and positional argument orders, :15-106), bound to the
 // in-tree mirror classes whose SDF build runs on the MI355X through the C ABI (libsdfgpu.so).
 // Extras beside (not instead of) the reference-shaped methods: numpy fast paths
-// (SetOccupancyFromNumpy / GetRawDataNumpy / GetFullGradientNumpy) that avoid per-voxel Python calls,
+// (SetOccupancyFromNumpy / GetRawDataNumpy / GetFullGradientNumpy / GetComponentsNumpy) that avoid per-voxel Python calls,
 // and the GIL is released for the duration of ExtractSignedDistanceField.
 #include <pybind11/functional.h>
 #include <pybind11/numpy.h>
@@ -91,6 +91,8 @@ PYBIND11_MODULE(pysdf_tools, m) {
         .def(py::init<Isometry3d const&, std::string, double, int64_t, int64_t, int64_t, TAGGED_OBJECT_COLLISION_CELL const&>())
         .def(py::init<>())
         .def("SetValue", [](TaggedObjectCollisionMapGrid& g, int64_t x, int64_t y, int64_t z, const TAGGED_OBJECT_COLLISION_CELL& c) { return g.SetValue(x, y, z, c); })
+        .def("UpdateConnectedComponents", &TaggedObjectCollisionMapGrid::UpdateConnectedComponents, py::call_guard<py::gil_scoped_release>())
+        .def("GetNumConnectedComponents", &TaggedObjectCollisionMapGrid::GetNumConnectedComponents)
         .def("GetValueByIndex", [](const TaggedObjectCollisionMapGrid& g, int64_t x, int64_t y, int64_t z) { const auto q = g.GetImmutable(x, y, z); return std::make_pair(q.first, q.second); })
         .def("GetNumXCells", &TaggedObjectCollisionMapGrid::GetNumXCells)
         .def("GetNumYCells", &TaggedObjectCollisionMapGrid::GetNumYCells)
@@ -239,7 +241,19 @@ PYBIND11_MODULE(pysdf_tools, m) {
             const float* p = occ.data();
             auto& cells = g.GetMutableRawData();
             for (size_t i = 0; i < cells.size(); i++) cells[i] = COLLISION_CELL(p[i]);
-        });
+            g.InvalidateConnectedComponents();                      // (the cells' labels were just reset, as SetValue would)
+        })
+        // connected components on the GPU (collision_map.cpp:564-618); ExtractConnectedComponents stays C++-only: a list of
+        // GRID_INDEX lists per component is not a usable Python value at 512^3 -- GetComponentsNumpy is the bulk accessor
+        .def("UpdateConnectedComponents", &CollisionMapGrid::UpdateConnectedComponents, py::call_guard<py::gil_scoped_release>())
+        .def("GetNumConnectedComponents", &CollisionMapGrid::GetNumConnectedComponents)
+        .def("GetComponentsNumpy", [](const CollisionMapGrid& g) {
+            py::array_t<uint32_t> out({(py::ssize_t)g.GetNumXCells(), (py::ssize_t)g.GetNumYCells(), (py::ssize_t)g.GetNumZCells()});
+            uint32_t* o = out.mutable_data();
+            const auto& cells = g.GetImmutableRawData();
+            for (size_t i = 0; i < cells.size(); i++) o[i] = cells[i].component;
+            return out;
+        }, "the cells' component labels as uint32 [nx, ny, nz] (0 until UpdateConnectedComponents has run)");
 
     m.def("DecompressBytes", &ZlibHelpers::DecompressBytes);
     m.def("DeserializeFixedSizePODFloat", &arc_utilities::DeserializeFixedSizePOD<float>);

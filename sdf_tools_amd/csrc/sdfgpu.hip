@@ -11,6 +11,7 @@
 #include "sdfgpu_envelope_dc.hpp"
 #include "sdfgpu_policy.hpp"
 #include "sdfgpu_hostteam.hpp"
+#include "sdfgpu_components.hpp"
 
 #include <sys/mman.h>
 #if defined(__SSE2__)
@@ -66,6 +67,7 @@ struct sdfgpu_context {
                              // caller's mask / cells and classify on the device, as rounds 1 - 4 did)
     DeviceBuffer stage_out;  // host-API staging: sdf
     DeviceBuffer query_stage;   // host-API staging of sdfgpu_query_points: points | distance | gradient | flags
+    DeviceBuffer cc_scratch;    // sdfgpu_components*: root flags, ranks, chunk counts, K (sdfgpu_components.hpp)
     size_t tag_cached_bytes = 0;            // stage_in holds the tagged cell records of the last sdfgpu_build_tagged_cells call
     void* pin[2] = {nullptr, nullptr};      // pinned host staging of copy_to_host (two chunks in flight)
     // Red zones (round 6, VERDICT r5 "next round" 2): with SDFGPU_REDZONE=1 in the environment of sdfgpu_create (or option
@@ -1367,22 +1369,26 @@ int build_device_impl(sdfgpu_handle h, const uint8_t* d_filled, const void* d_ce
 constexpr size_t kPinChunk = (size_t)32 << 20;
 constexpr size_t kPinMin = (size_t)4 << 20;      // below this a plain (runtime-staged) copy is as fast as the team
 
-int copy_to_host(sdfgpu_handle h, void* dst, const void* d_src, size_t bytes, hipStream_t st = nullptr) {
+// `drain(src, offset_in_download, len)` consumes bytes [offset, offset + len) of the download from pinned (or, for transfers
+// below kPinMin, temporary) host memory: a memcpy for copy_to_host, the scatter of labels into cell records for
+// sdfgpu_components_cells.
+template <class Drain>
+int staged_download_hip(sdfgpu_handle h, const void* d_src, size_t bytes, hipStream_t st, Drain drain) {
     if (bytes == 0) return SDFGPU_OK;
     for (int i = 0; i < 2 && bytes >= kPinMin; ++i) {
         if (!h->pin[i] && hipHostMalloc(&h->pin[i], kPinChunk, hipHostMallocDefault) != hipSuccess) h->pin[i] = nullptr;
         if (h->pin[i] && !h->pin_ev[i] && hipEventCreateWithFlags(&h->pin_ev[i], hipEventDisableTiming) != hipSuccess) h->pin_ev[i] = nullptr;
     }
     if (bytes < kPinMin || !h->pin[0] || !h->pin[1] || !h->pin_ev[0] || !h->pin_ev[1]) {
-        HIP_TRY(h, hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(h, hipStreamSynchronize(st));
+        (void)hipGetLastError();
+        std::vector<char> tmp(std::min(bytes, kPinChunk));
+        for (size_t o = 0; o < bytes; o += tmp.size()) {
+            const size_t len = std::min(tmp.size(), bytes - o);
+            HIP_TRY(h, hipMemcpyAsync(tmp.data(), static_cast<const char*>(d_src) + o, len, hipMemcpyDeviceToHost, st));
+            HIP_TRY(h, hipStreamSynchronize(st));
+            drain(tmp.data(), o, len);
+        }
         return SDFGPU_OK;
-    }
-    {   // huge pages on the 2 MiB-aligned interior, where the kernel grants them: one fault then maps 512 small pages' worth
-        constexpr uintptr_t kHuge = (uintptr_t)2 << 20;
-        const uintptr_t lo = (reinterpret_cast<uintptr_t>(dst) + kHuge - 1) & ~(kHuge - 1);
-        const uintptr_t hi = (reinterpret_cast<uintptr_t>(dst) + bytes) & ~(kHuge - 1);
-        if (hi > lo) (void)madvise(reinterpret_cast<void*>(lo), hi - lo, MADV_HUGEPAGE);
     }
     if (!h->team) h->team = new (std::nothrow) HostTeam();
     if (!h->team) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "out of host memory");
@@ -1396,12 +1402,28 @@ int copy_to_host(sdfgpu_handle h, void* dst, const void* d_src, size_t bytes, hi
             return herr == hipSuccess ? 0 : 1;
         },
         [&](int buf) -> int { herr = hipEventSynchronize(h->pin_ev[buf]); return herr == hipSuccess ? 0 : 1; },
-        [&](int buf, size_t off, size_t goff, size_t len) { memcpy(static_cast<char*>(dst) + goff, static_cast<const char*>(h->pin[buf]) + off, len); });
+        [&](int buf, size_t off, size_t goff, size_t len) { drain(static_cast<const char*>(h->pin[buf]) + off, goff, len); });
     if (rc != 0) {
         (void)hipDeviceSynchronize();
         return fail(h, SDFGPU_ERR_HIP, "HIP error %d (%s) in the device-to-host copy", (int)herr, hipGetErrorString(herr));
     }
     return SDFGPU_OK;
+}
+
+int copy_to_host(sdfgpu_handle h, void* dst, const void* d_src, size_t bytes, hipStream_t st = nullptr) {
+    if (bytes == 0) return SDFGPU_OK;
+    if (bytes < kPinMin) {
+        HIP_TRY(h, hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(h, hipStreamSynchronize(st));
+        return SDFGPU_OK;
+    }
+    {   // huge pages on the 2 MiB-aligned interior, where the kernel grants them: one fault then maps 512 small pages' worth
+        constexpr uintptr_t kHuge = (uintptr_t)2 << 20;
+        const uintptr_t lo = (reinterpret_cast<uintptr_t>(dst) + kHuge - 1) & ~(kHuge - 1);
+        const uintptr_t hi = (reinterpret_cast<uintptr_t>(dst) + bytes) & ~(kHuge - 1);
+        if (hi > lo) (void)madvise(reinterpret_cast<void*>(lo), hi - lo, MADV_HUGEPAGE);
+    }
+    return staged_download_hip(h, d_src, bytes, st, [dst](const char* src, size_t goff, size_t len) { memcpy(static_cast<char*>(dst) + goff, src, len); });
 }
 
 // Pageable host -> device, the mirror image of copy_to_host: a synchronous hipMemcpy from pageable memory goes through
@@ -1607,6 +1629,41 @@ int build_host_impl(sdfgpu_handle h, const uint8_t* filled, const void* cells, s
     return SDFGPU_OK;
 }
 
+// ---- connected components (sdfgpu_components.hpp) ------------------------------------------------------------------------------
+// Uses only cc_scratch (and, in the host forms, the bit / output staging and the pinned chunks, which every host-buffer call
+// owns while it runs): the SDF builds' scratch, status block and policy are not touched.
+int check_components_dims(sdfgpu_handle h, int64_t nx, int64_t ny, int64_t nz) {
+    if (nx <= 0 || ny <= 0 || nz <= 0)
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "grid dimensions must be positive (got %lld x %lld x %lld)",
+                    (long long)nx, (long long)ny, (long long)nz);
+    if ((unsigned __int128)nx * (unsigned __int128)ny * (unsigned __int128)nz > (unsigned __int128)0xFFFFFFFFu)
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "grid %lld x %lld x %lld has more than 2^32 - 1 voxels: uint32 component labels cannot number it",
+                    (long long)nx, (long long)ny, (long long)nz);
+    return SDFGPU_OK;
+}
+
+// bits (device) -> labels (device), K -> *out_count; synchronises `st` (K is read back)
+int components_impl(sdfgpu_handle h, const uint32_t* d_bits, int64_t nx, int64_t ny, int64_t nz, uint32_t* d_labels, uint32_t* out_count,
+                    hipStream_t st) {
+    const CcPlan plan = cc_plan(nx, ny, nz);
+    if (int rc = ensure(h, h->cc_scratch, plan.scratch_bytes, "components scratch")) return rc;
+    HIP_TRY(h, cc_launch(plan, d_bits, d_labels, h->cc_scratch.ptr, st));
+    uint32_t k = 0;
+    HIP_TRY(h, hipMemcpyAsync(&k, cc_count_word(plan, h->cc_scratch.ptr), 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    if (out_count) *out_count = k;
+    return SDFGPU_OK;
+}
+
+// host mask / cell records -> bits (host team, 1 bit per voxel over PCIe) -> labels in the output staging
+int components_host(sdfgpu_handle h, const uint8_t* filled, const void* cells, size_t stride, size_t occ_off, int64_t nx, int64_t ny,
+                    int64_t nz, uint32_t* out_count) {
+    const int64_t n = nx * ny * nz;
+    if (int rc = upload_packed(h, filled, cells, stride, occ_off, 0, n, nullptr, nullptr)) return rc;
+    if (int rc = ensure(h, h->stage_out, (size_t)n * 4, "output staging")) return rc;
+    return components_impl(h, (const uint32_t*)h->stage_bits.ptr, nx, ny, nz, (uint32_t*)h->stage_out.ptr, out_count, nullptr);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1672,7 +1729,7 @@ int sdfgpu_destroy(sdfgpu_handle h) {
     if (!h) return SDFGPU_OK;
     (void)hipSetDevice(h->device);
     for (DeviceBuffer* b : {&h->zfield, &h->yzfield, &h->plane16, &h->bits, &h->unc, &h->tileflag, &h->fix_order, &h->tagmask, &h->tagids, &h->stage_in,
-                            &h->stage_bits, &h->stage_out, &h->query_stage, &h->planebits})
+                            &h->stage_bits, &h->stage_out, &h->query_stage, &h->planebits, &h->cc_scratch})
         if (b->ptr) (void)rz_free(h, b->ptr);
     if (h->d_small) (void)rz_free(h, h->d_small);
     if (h->d_slots) (void)rz_free(h, h->d_slots);
@@ -2610,6 +2667,58 @@ int sdfgpu_set_tuning(sdfgpu_handle h, int rows_per_chunk_y, int rows_per_chunk_
     h->tune_ty = rows_per_chunk_y;
     h->tune_tx = rows_per_chunk_x;
     return SDFGPU_OK;
+}
+
+static int sdfgpu_components_bits_device_body(sdfgpu_handle h, const uint32_t* d_bits, int64_t nx, int64_t ny, int64_t nz,
+                                              uint32_t* d_labels, uint32_t* out_count, void* stream) {
+    if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
+    if (!d_bits || !d_labels || !out_count) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
+    if ((reinterpret_cast<uintptr_t>(d_bits) | reinterpret_cast<uintptr_t>(d_labels)) & 3)
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "d_bits and d_labels must be 4-byte aligned");
+    if (int rc = check_components_dims(h, nx, ny, nz)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    return components_impl(h, d_bits, nx, ny, nz, d_labels, out_count, (hipStream_t)stream);
+}
+int sdfgpu_components_bits_device(sdfgpu_handle h, const uint32_t* d_bits, int64_t nx, int64_t ny, int64_t nz, uint32_t* d_labels,
+                                  uint32_t* out_count, void* stream) {
+    return rz_wrap(h, stream, [&]() -> int { return sdfgpu_components_bits_device_body(h, d_bits, nx, ny, nz, d_labels, out_count, stream); });
+}
+
+static int sdfgpu_components_body(sdfgpu_handle h, const uint8_t* filled, int64_t nx, int64_t ny, int64_t nz, uint32_t* out_labels,
+                                  uint32_t* out_count) {
+    if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
+    if (!filled || !out_labels || !out_count) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
+    if (int rc = check_components_dims(h, nx, ny, nz)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (int rc = components_host(h, filled, nullptr, 0, 0, nx, ny, nz, out_count)) return rc;
+    return copy_to_host(h, out_labels, h->stage_out.ptr, (size_t)(nx * ny * nz) * 4);
+}
+int sdfgpu_components(sdfgpu_handle h, const uint8_t* filled, int64_t nx, int64_t ny, int64_t nz, uint32_t* out_labels, uint32_t* out_count) {
+    return rz_wrap(h, nullptr, [&]() -> int { return sdfgpu_components_body(h, filled, nx, ny, nz, out_labels, out_count); });
+}
+
+static int sdfgpu_components_cells_body(sdfgpu_handle h, void* cells, size_t cell_stride, size_t occupancy_offset, size_t component_offset,
+                                        int64_t nx, int64_t ny, int64_t nz, uint32_t* out_count) {
+    if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
+    if (!cells || !out_count) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
+    if (cell_stride < 8 || (cell_stride % 4) || (occupancy_offset % 4) || (component_offset % 4) || occupancy_offset + 4 > cell_stride ||
+        component_offset + 4 > cell_stride || occupancy_offset == component_offset)
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cell_stride / occupancy_offset / component_offset must be 4-byte aligned, in range and distinct");
+    if (int rc = check_components_dims(h, nx, ny, nz)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (int rc = components_host(h, nullptr, cells, cell_stride, occupancy_offset, nx, ny, nz, out_count)) return rc;
+    char* const rec = static_cast<char*>(cells) + component_offset;
+    // the drain team writes each label into its record (download offsets are multiples of 4: whole labels)
+    return staged_download_hip(h, h->stage_out.ptr, (size_t)(nx * ny * nz) * 4, nullptr, [=](const char* src, size_t goff, size_t len) {
+        char* dst = rec + (goff / 4) * cell_stride;
+        for (size_t o = 0; o < len; o += 4, dst += cell_stride) memcpy(dst, src + o, 4);
+    });
+}
+int sdfgpu_components_cells(sdfgpu_handle h, void* cells, size_t cell_stride, size_t occupancy_offset, size_t component_offset,
+                            int64_t nx, int64_t ny, int64_t nz, uint32_t* out_count) {
+    return rz_wrap(h, nullptr, [&]() -> int {
+        return sdfgpu_components_cells_body(h, cells, cell_stride, occupancy_offset, component_offset, nx, ny, nz, out_count);
+    });
 }
 
 }  // extern "C"

@@ -1,0 +1,350 @@
+// sdfgpu_components.hip -- the connected-components kernels (sdfgpu_components.hpp) and their launcher.  Compiled beside
+// sdfgpu.hip and linked into the same libsdfgpu.so (sdf_tools_amd/build.py); the C ABI entry points live in sdfgpu.hip.
+//
+// Union-find invariant, relied on by every find below: a label word only ever DECREASES, and it never holds a value above its
+// own index (a provisional label is the index of a tile-local root <= the voxel; a link stores a smaller root into a larger
+// one with atomicMin).  Every parent chain is therefore strictly decreasing until it meets a self-loop, so every find ends,
+// and the root of a component is its minimum linear index -- the voxel at which the reference's x -> y -> z scan starts it.
+#include "sdfgpu_components.hpp"
+
+#include <algorithm>
+
+namespace sdfgpu {
+
+namespace {
+
+constexpr int kLocalThreads = 1024;
+constexpr int kMergeThreads = 256;
+constexpr int kScanThreads = 1024;
+constexpr int kRelabelPerThread = 4;
+
+__device__ __forceinline__ uint32_t bit_at(const uint32_t* __restrict__ bits, uint64_t g) {
+    return (bits[g >> 5] >> (g & 31)) & 1u;
+}
+
+// ---- LDS union-find (one workgroup) ------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t lds_find(volatile uint32_t* l, uint32_t a) {
+    uint32_t p = l[a];
+    while (p != a) { a = p; p = l[a]; }
+    return a;
+}
+
+__device__ __forceinline__ void lds_union(uint32_t* l, uint32_t a, uint32_t b) {
+    for (;;) {
+        a = lds_find(l, a);
+        b = lds_find(l, b);
+        if (a == b) return;
+        if (a < b) { const uint32_t t = a; a = b; b = t; }
+        const uint32_t old = atomicMin(&l[a], b);    // a was a root: it now hangs under b; else retry from what a had become
+        if (old == a) return;
+        a = old;
+    }
+}
+
+// ---- global union-find (k_cc_merge) -------------------------------------------------------------------------------------------
+// Other workgroups, on other XCDs, link roots while this one walks: every read of a label word is an agent-scope load (sc1, past
+// this CU's L1 and never a stale line of this XCD's L2 for words another XCD's atomic wrote) and every write an agent-scope atomic.
+// A stale read would still be safe (it returns an older, larger ancestor), but nothing here depends on that.
+__device__ __forceinline__ uint32_t ld_agent(uint32_t* p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ uint32_t min_agent(uint32_t* p, uint32_t v) {
+    return __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// find with path halving: a hop whose grandparent differs is shortened with atomicMin (monotone, stays in the component)
+__device__ __forceinline__ uint32_t g_find(uint32_t* L, uint32_t a) {
+    for (;;) {
+        const uint32_t p = ld_agent(&L[a]);
+        if (p == a) return a;
+        const uint32_t gp = ld_agent(&L[p]);
+        if (gp == p) return p;
+        (void)min_agent(&L[a], gp);
+        a = gp;
+    }
+}
+
+__device__ __forceinline__ void g_union(uint32_t* L, uint32_t a, uint32_t b) {
+    for (;;) {
+        a = g_find(L, a);
+        b = g_find(L, b);
+        if (a == b) return;
+        if (a < b) { const uint32_t t = a; a = b; b = t; }
+        const uint32_t old = min_agent(&L[a], b);
+        if (old == a) return;
+        a = old;                                      // a had been linked meanwhile (old < a): join its new root instead
+    }
+}
+
+struct CcArgs {
+    const uint32_t* bits;
+    uint32_t* L;
+    int64_t nx, ny, nz;
+    int tx, ty, tz;
+    int64_t nty, ntz;
+    uint64_t nwords;                // ceil(n / 32)
+};
+
+__device__ __forceinline__ void tile_origin(const CcArgs& a, uint64_t b, int64_t& x0, int64_t& y0, int64_t& z0,
+                                            bool& lo_x, bool& lo_y, bool& lo_z) {
+    const int64_t tzi = (int64_t)(b % (uint64_t)a.ntz);
+    const int64_t r = (int64_t)(b / (uint64_t)a.ntz);
+    const int64_t tyi = r % a.nty, txi = r / a.nty;
+    x0 = txi * a.tx; y0 = tyi * a.ty; z0 = tzi * a.tz;
+    lo_x = txi > 0; lo_y = tyi > 0; lo_z = tzi > 0;
+}
+
+// ---- k_cc_local ---------------------------------------------------------------------------------------------------------------
+// Local index i = (ix * ty + iy) * tz + iz is increasing in the same order as the global index of the voxel, so the tile-local
+// minimum IS the global minimum of the tile's part of the component.
+__global__ __launch_bounds__(kLocalThreads) void k_cc_local(const CcArgs a) {
+    __shared__ uint32_t lab[kCcTileVoxels];
+    __shared__ uint32_t cls[kCcTileVoxels / 32];
+    int64_t x0, y0, z0;
+    bool lx, ly, lz;
+    tile_origin(a, blockIdx.x, x0, y0, z0, lx, ly, lz);
+    const int tz = a.tz, ty = a.ty, wz = tz >> 5, rows = a.tx * ty, nv = rows * tz;
+
+    // class words of the tile's rows: 32 voxels from an arbitrary bit offset (rows share words when nz % 32 != 0)
+    for (int w = threadIdx.x; w < rows * wz; w += kLocalThreads) {
+        const int row = w / wz, k = w - row * wz;
+        const int64_t x = x0 + row / ty, y = y0 + row % ty, z = z0 + 32 * k;
+        uint32_t word = 0;
+        if (x < a.nx && y < a.ny && z < a.nz) {
+            const uint64_t g = ((uint64_t)x * (uint64_t)a.ny + (uint64_t)y) * (uint64_t)a.nz + (uint64_t)z;
+            const uint64_t q = g >> 5;
+            const uint32_t s = (uint32_t)(g & 31);
+            const uint32_t lo = a.bits[q];
+            const uint32_t hi = (s && q + 1 < a.nwords) ? a.bits[q + 1] : 0u;
+            word = s ? (lo >> s) | (hi << (32 - s)) : lo;
+            const int64_t rem = a.nz - z;
+            if (rem < 32) word &= (1u << rem) - 1u;
+        }
+        cls[w] = word;
+    }
+    __syncthreads();
+
+    // z runs: every voxel starts under the first voxel of its run inside the tile row
+    for (int i = threadIdx.x; i < nv; i += kLocalThreads) {
+        const int row = i / tz, iz = i - row * tz;
+        const int64_t x = x0 + row / ty, y = y0 + row % ty, z = z0 + iz;
+        if (x >= a.nx || y >= a.ny || z >= a.nz) { lab[i] = (uint32_t)i; continue; }
+        const uint32_t* cw = cls + row * wz;
+        int k = iz >> 5;
+        const uint32_t c = (cw[k] >> (iz & 31)) & 1u;
+        uint32_t d = (c ? ~cw[k] : cw[k]) & ((1u << (iz & 31)) - 1u);   // voxels of the other class below iz in this word
+        while (!d && k > 0) { --k; d = c ? ~cw[k] : cw[k]; }
+        lab[i] = (uint32_t)(row * tz + (d ? 32 * k + (31 - __clz(d)) + 1 : 0));
+    }
+    __syncthreads();
+
+    // y and x faces inside the tile.  A pair whose z predecessors are a same-class pair too is already joined through them.
+    for (int i = threadIdx.x; i < nv; i += kLocalThreads) {
+        const int row = i / tz, iz = i - row * tz, ix = row / ty, iy = row - ix * ty;
+        if (x0 + ix >= a.nx || y0 + iy >= a.ny || z0 + iz >= a.nz) continue;
+        const int k = iz >> 5, s = iz & 31;
+        const uint32_t c = (cls[row * wz + k] >> s) & 1u;
+        const bool zp = iz > 0 && ((cls[row * wz + ((iz - 1) >> 5)] >> ((iz - 1) & 31)) & 1u) == c;
+        if (iy > 0) {
+            const int r2 = row - 1;
+            if (((cls[r2 * wz + k] >> s) & 1u) == c &&
+                !(zp && ((cls[r2 * wz + ((iz - 1) >> 5)] >> ((iz - 1) & 31)) & 1u) == c))
+                lds_union(lab, (uint32_t)i, (uint32_t)(i - tz));
+        }
+        if (ix > 0) {
+            const int r2 = row - ty;
+            if (((cls[r2 * wz + k] >> s) & 1u) == c &&
+                !(zp && ((cls[r2 * wz + ((iz - 1) >> 5)] >> ((iz - 1) & 31)) & 1u) == c))
+                lds_union(lab, (uint32_t)i, (uint32_t)(i - ty * tz));
+        }
+    }
+    __syncthreads();
+
+    for (int i = threadIdx.x; i < nv; i += kLocalThreads) {
+        const int row = i / tz, iz = i - row * tz;
+        const int64_t x = x0 + row / ty, y = y0 + row % ty, z = z0 + iz;
+        if (x >= a.nx || y >= a.ny || z >= a.nz) continue;
+        const uint32_t r = lds_find(lab, (uint32_t)i);
+        const int rrow = (int)r / tz, riz = (int)r - rrow * tz;
+        const uint64_t gr = ((uint64_t)(x0 + rrow / ty) * (uint64_t)a.ny + (uint64_t)(y0 + rrow % ty)) * (uint64_t)a.nz + (uint64_t)(z0 + riz);
+        const uint64_t g = ((uint64_t)x * (uint64_t)a.ny + (uint64_t)y) * (uint64_t)a.nz + (uint64_t)z;
+        a.L[g] = (uint32_t)gr;
+    }
+}
+
+// ---- k_cc_merge ---------------------------------------------------------------------------------------------------------------
+// One workgroup per tile joins each voxel of the tile's low x / y / z faces with its neighbour in the previous tile.
+__global__ __launch_bounds__(kMergeThreads) void k_cc_merge(const CcArgs a) {
+    int64_t x0, y0, z0;
+    bool lx, ly, lz;
+    tile_origin(a, blockIdx.x, x0, y0, z0, lx, ly, lz);
+    const uint64_t ny = (uint64_t)a.ny, nz = (uint64_t)a.nz, plane = ny * nz;
+    auto gidx = [&](int64_t x, int64_t y, int64_t z) { return ((uint64_t)x * ny + (uint64_t)y) * nz + (uint64_t)z; };
+    if (lx) {                               // neighbour (x0 - 1, y, z); skip when (z - 1) pairs up the same way
+        for (int idx = threadIdx.x; idx < a.ty * a.tz; idx += kMergeThreads) {
+            const int iy = idx / a.tz, iz = idx - iy * a.tz;
+            const int64_t y = y0 + iy, z = z0 + iz;
+            if (x0 >= a.nx || y >= a.ny || z >= a.nz) continue;
+            const uint64_t v = gidx(x0, y, z), u = v - plane;
+            const uint32_t c = bit_at(a.bits, v);
+            if (bit_at(a.bits, u) != c) continue;
+            if (iz > 0 && bit_at(a.bits, v - 1) == c && bit_at(a.bits, u - 1) == c) continue;
+            g_union(a.L, (uint32_t)v, (uint32_t)u);
+        }
+    }
+    if (ly) {                               // neighbour (x, y0 - 1, z)
+        for (int idx = threadIdx.x; idx < a.tx * a.tz; idx += kMergeThreads) {
+            const int ix = idx / a.tz, iz = idx - ix * a.tz;
+            const int64_t x = x0 + ix, z = z0 + iz;
+            if (x >= a.nx || y0 >= a.ny || z >= a.nz) continue;
+            const uint64_t v = gidx(x, y0, z), u = v - nz;
+            const uint32_t c = bit_at(a.bits, v);
+            if (bit_at(a.bits, u) != c) continue;
+            if (iz > 0 && bit_at(a.bits, v - 1) == c && bit_at(a.bits, u - 1) == c) continue;
+            g_union(a.L, (uint32_t)v, (uint32_t)u);
+        }
+    }
+    if (lz) {                               // neighbour (x, y, z0 - 1); skip when (y - 1) pairs up the same way
+        for (int idx = threadIdx.x; idx < a.tx * a.ty; idx += kMergeThreads) {
+            const int ix = idx / a.ty, iy = idx - ix * a.ty;
+            const int64_t x = x0 + ix, y = y0 + iy;
+            if (x >= a.nx || y >= a.ny || z0 >= a.nz) continue;
+            const uint64_t v = gidx(x, y, z0), u = v - 1;
+            const uint32_t c = bit_at(a.bits, v);
+            if (bit_at(a.bits, u) != c) continue;
+            if (iy > 0 && bit_at(a.bits, v - nz) == c && bit_at(a.bits, u - nz) == c) continue;
+            g_union(a.L, (uint32_t)v, (uint32_t)u);
+        }
+    }
+}
+
+// ---- k_cc_flatten -------------------------------------------------------------------------------------------------------------
+// After k_cc_merge (stream order: its atomics are visible).  Writes inside this launch only replace a label by its root, so any
+// value a plain load sees is an ancestor of the voxel.  rb[w]: root flags of voxels 32 w .. 32 w + 31; wr[w]: roots in the
+// chunk's words before w; cc[chunk]: roots in the chunk.
+__global__ __launch_bounds__(256) void k_cc_flatten(uint32_t* __restrict__ L, uint64_t n, uint32_t* __restrict__ rb,
+                                                    uint32_t* __restrict__ wr, uint32_t* __restrict__ cc) {
+    __shared__ uint32_t wc[kCcChunk / 32];
+    const uint64_t base = (uint64_t)blockIdx.x * kCcChunk;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int j = 0; j < kCcChunk / 256; ++j) {
+        const uint64_t v = base + (uint64_t)j * 256 + threadIdx.x;
+        bool root = false;
+        if (v < n) {
+            const uint32_t r = L[v];
+            if (r == (uint32_t)v) {
+                root = true;
+            } else {
+                uint32_t q = r, p = L[q];
+                while (p != q) { q = p; p = L[q]; }
+                if (q != r) L[v] = q;
+            }
+        }
+        const uint64_t m = __ballot(root);
+        if (lane == 0) {
+            const int w = j * 8 + 2 * wave;
+            rb[base / 32 + w] = (uint32_t)m;
+            rb[base / 32 + w + 1] = (uint32_t)(m >> 32);
+            wc[w] = __popc((uint32_t)m);
+            wc[w + 1] = __popc((uint32_t)(m >> 32));
+        }
+    }
+    __syncthreads();
+    const int t = threadIdx.x;
+    const uint32_t own = wc[t];
+    for (int d = 1; d < 256; d <<= 1) {     // inclusive scan of the 256 word counts
+        const uint32_t add = t >= d ? wc[t - d] : 0u;
+        __syncthreads();
+        wc[t] += add;
+        __syncthreads();
+    }
+    wr[base / 32 + t] = wc[t] - own;
+    if (t == 255) cc[blockIdx.x] = wc[255];
+}
+
+// ---- k_cc_scan: one workgroup, exclusive scan of the chunk counts, K -----------------------------------------------------------
+__global__ __launch_bounds__(kScanThreads) void k_cc_scan(const uint32_t* __restrict__ cc, uint32_t* __restrict__ co, uint64_t chunks,
+                                                          uint32_t* __restrict__ count) {
+    __shared__ uint32_t s[kScanThreads];
+    const int t = threadIdx.x;
+    const uint64_t per = (chunks + kScanThreads - 1) / kScanThreads;
+    const uint64_t lo = std::min<uint64_t>(chunks, per * t), hi = std::min<uint64_t>(chunks, lo + per);
+    uint32_t sum = 0;
+    for (uint64_t i = lo; i < hi; ++i) sum += cc[i];
+    s[t] = sum;
+    __syncthreads();
+    for (int d = 1; d < kScanThreads; d <<= 1) {
+        const uint32_t add = t >= d ? s[t - d] : 0u;
+        __syncthreads();
+        s[t] += add;
+        __syncthreads();
+    }
+    uint32_t run = s[t] - sum;
+    for (uint64_t i = lo; i < hi; ++i) { const uint32_t c = cc[i]; co[i] = run; run += c; }
+    if (t == kScanThreads - 1) *count = s[t];
+}
+
+// ---- k_cc_relabel -------------------------------------------------------------------------------------------------------------
+// Reads only the voxel's own label (its root r) and the rank tables, so rewriting labels in place races with nothing.
+__global__ __launch_bounds__(256) void k_cc_relabel(uint32_t* __restrict__ L, uint64_t n, const uint32_t* __restrict__ rb,
+                                                    const uint32_t* __restrict__ wr, const uint32_t* __restrict__ co) {
+    const uint64_t base = (uint64_t)blockIdx.x * (256 * kRelabelPerThread) + threadIdx.x;
+#pragma unroll
+    for (int j = 0; j < kRelabelPerThread; ++j) {
+        const uint64_t v = base + (uint64_t)j * 256;
+        if (v >= n) return;
+        const uint32_t r = L[v], w = r >> 5;
+        L[v] = co[w / (kCcChunk / 32)] + wr[w] + (uint32_t)__popc(rb[w] & ((1u << (r & 31)) - 1u)) + 1u;
+    }
+}
+
+}  // namespace
+
+CcPlan cc_plan(int64_t nx, int64_t ny, int64_t nz) {
+    CcPlan p;
+    // singleton axes to the front (index = x * ny * nz + y * nz + z is unchanged, and a singleton axis has no neighbours)
+    if (nz == 1) { nz = ny; ny = nx; nx = 1; }
+    if (nz == 1) { nz = ny; ny = nx; nx = 1; }
+    if (ny == 1) { ny = nx; nx = 1; }
+    p.nx = nx; p.ny = ny; p.nz = nz;
+    p.tz = nz <= 32 ? 32 : 64;
+    p.ty = (int)std::min<int64_t>(ny, 16);
+    p.tx = (int)std::min<int64_t>(nx, kCcTileVoxels / (p.tz * p.ty));
+    if (p.tx == nx) {                       // thin grids: spend the rest of the tile on z
+        const int cap = (kCcTileVoxels / (p.tx * p.ty)) & ~31;
+        const int64_t nz32 = (nz + 31) & ~(int64_t)31;
+        p.tz = (int)std::min<int64_t>(nz32, std::max(p.tz, cap));
+    }
+    p.ntx = (nx + p.tx - 1) / p.tx;
+    p.nty = (ny + p.ty - 1) / p.ty;
+    p.ntz = (nz + p.tz - 1) / p.tz;
+    p.n = (uint64_t)nx * (uint64_t)ny * (uint64_t)nz;
+    p.chunks = (p.n + kCcChunk - 1) / kCcChunk;
+    p.scratch_bytes = (size_t)(2 * p.chunks * (kCcChunk / 32) + 2 * p.chunks + 4) * 4;
+    return p;
+}
+
+hipError_t cc_launch(const CcPlan& p, const uint32_t* d_bits, uint32_t* d_labels, void* d_scratch, hipStream_t s) {
+    CcArgs a;
+    a.bits = d_bits;
+    a.L = d_labels;
+    a.nx = p.nx; a.ny = p.ny; a.nz = p.nz;
+    a.tx = p.tx; a.ty = p.ty; a.tz = p.tz;
+    a.nty = p.nty; a.ntz = p.ntz;
+    a.nwords = (p.n + 31) / 32;
+    const uint64_t tiles = (uint64_t)p.ntx * (uint64_t)p.nty * (uint64_t)p.ntz;
+    uint32_t* rb = static_cast<uint32_t*>(d_scratch);
+    uint32_t* wr = rb + p.chunks * (kCcChunk / 32);
+    uint32_t* cc = wr + p.chunks * (kCcChunk / 32);
+    uint32_t* co = cc + p.chunks;
+    hipLaunchKernelGGL(k_cc_local, dim3((unsigned)tiles), dim3(kLocalThreads), 0, s, a);
+    if (tiles > 1) hipLaunchKernelGGL(k_cc_merge, dim3((unsigned)tiles), dim3(kMergeThreads), 0, s, a);
+    hipLaunchKernelGGL(k_cc_flatten, dim3((unsigned)p.chunks), dim3(256), 0, s, d_labels, p.n, rb, wr, cc);
+    hipLaunchKernelGGL(k_cc_scan, dim3(1), dim3(kScanThreads), 0, s, (const uint32_t*)cc, co, p.chunks, cc_count_word(p, d_scratch));
+    const uint64_t rblocks = (p.n + 256 * kRelabelPerThread - 1) / (256 * kRelabelPerThread);
+    hipLaunchKernelGGL(k_cc_relabel, dim3((unsigned)rblocks), dim3(256), 0, s, d_labels, p.n, (const uint32_t*)rb,
+                       (const uint32_t*)wr, (const uint32_t*)co);
+    return hipGetLastError();
+}
+
+}  // namespace sdfgpu
