@@ -431,8 +431,8 @@ int sdfgpu_get_stage_times(sdfgpu_handle h, double* out_ms_sum, int64_t* out_bui
 
 /* Named integer options.  EVERY option leaves the results exact: they move work between kernels, switch a measured optimisation
  * off for an A/B, or put the handle's policy into a state a test needs.  Unknown names return SDFGPU_ERR_INVALID_ARGUMENT.
- * Switches that SKIP work for profiling ("dc_debug", "dc_debug_stage", "ball_variant") exist only in libraries built with
- * -DSDFGPU_DEBUG_HOOKS (tools/probe/libsdfgpu_hooks.so) and are rejected by the shipped one.
+ * No option skips work: the profiling builds whose switches did were removed after commit 4eb6a2c, and the names of those
+ * switches are unknown names here.
  * [T] = test / fuzz only (forces a state the policy reaches by itself), [AB] = A/B switch of a measured optimisation (default = the
  * faster setting; DESIGN.md / LAB_NOTES.md hold the measurement), [U] = for users.
  *

@@ -32,7 +32,7 @@ def _hipcc():
             return c
 
 
-def build_libsdfgpu(force=False, verbose=False, out=None):
+def build_libsdfgpu(force=False, verbose=False):
     """Four translation units -> objects (compiled side by side) -> libsdfgpu.so: sdfgpu.hip (C ABI, host orchestration, most
     kernels), sdfgpu_envelope_tu.hip (the far-field kernel's instantiations), sdfgpu_dense6_tu.hip (the shell pass) and
     sdfgpu_components.hip (connected components).  Each object is rebuilt when its
@@ -46,8 +46,7 @@ def build_libsdfgpu(force=False, verbose=False, out=None):
     units = [(os.path.join(CSRC, "sdfgpu.hip"), hdrs), (os.path.join(CSRC, "sdfgpu_envelope_tu.hip"), env_hdrs),
              (os.path.join(CSRC, "sdfgpu_dense6_tu.hip"), d6_hdrs),
              (os.path.join(CSRC, "sdfgpu_components.hip"), [os.path.join(CSRC, "sdfgpu_components.hpp")])]
-    extra = os.environ.get("SDFGPU_EXTRA_FLAGS", "").split()
-    objdir = os.path.join(CSRC, ".obj" + ("_" + "".join(c for c in "".join(extra) if c.isalnum()) if extra else ""))
+    objdir = os.path.join(CSRC, ".obj")
     os.makedirs(objdir, exist_ok=True)
     todo, objs = [], []
     for src, deps in units:
@@ -55,36 +54,19 @@ def build_libsdfgpu(force=False, verbose=False, out=None):
         objs.append(obj)
         if force or _newer(obj, [src] + deps):
             todo.append([_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-pthread", "-I", INCLUDE, "-c", src,
-                         "-o", obj] + extra)
-    lib = out or LIB
-    if not todo and not _newer(lib, objs):
-        return lib
+                         "-o", obj])
+    if not todo and not _newer(LIB, objs):
+        return LIB
     if verbose:
         for cmd in todo:
             print(" ".join(cmd))
     with ThreadPoolExecutor(max_workers=4) as pool:
         list(pool.map(subprocess.check_call, todo))
-    cmd = [_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-pthread"] + objs + ["-o", lib]
+    cmd = [_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-pthread"] + objs + ["-o", LIB]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)
-    return lib
-
-
-def build_profiling_variant(name, flags, verbose=False):
-    """A profiling build of the same library (never the shipped one): tools/probe/libsdfgpu_<name>.so compiled with extra
-    flags -- "hooks": -DSDFGPU_DEBUG_HOOKS (switches that skip work; results are then wrong), "trips":
-    -DSDFGPU_PHASE_CLOCKS -DSDFGPU_TRIP_COUNTS.  Selected with SDFGPU_LIB=<path> by the tools/ scripts."""
-    out = os.path.join(ROOT, "tools", "probe", "libsdfgpu_%s.so" % name)
-    old = os.environ.get("SDFGPU_EXTRA_FLAGS")
-    os.environ["SDFGPU_EXTRA_FLAGS"] = flags
-    try:
-        return build_libsdfgpu(False, verbose, out)
-    finally:
-        if old is None:
-            del os.environ["SDFGPU_EXTRA_FLAGS"]
-        else:
-            os.environ["SDFGPU_EXTRA_FLAGS"] = old
+    return LIB
 
 
 def build_libsdfgpu_multi(force=False, verbose=False):

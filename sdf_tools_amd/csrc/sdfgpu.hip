@@ -113,7 +113,6 @@ struct sdfgpu_context {
     uint32_t* unc_override = nullptr;   // set around the staged KD3 launch: undecided bits in the z field's storage
     size_t unc_override_bytes = 0;
     int defer_fold = 0;           // stage entry points leave their maxima in the slot array until sdfgpu_fold_extrema_device
-    int ball_variant = 0;         // debugging: bit0 = bounds-checked expansion, bit1 = generic (non-ZINV) expansion
     int nt_store = 0;               // measured: non-temporal output stores slow the next build's pack (0.03 -> 0.08 ms)
     bool envelope_on = true;         // bound the outward scans and redo far-field sweeps with the envelope kernels
     bool envelope_dc = true;         // use the divide-and-conquer envelope kernel (sdfgpu_envelope_dc.hpp) when the shape allows
@@ -151,9 +150,6 @@ struct sdfgpu_context {
     int standby_grid = 1024;         // workgroups of the stand-by launches (LOOP form; option "standby_grid"): 4 per CU = all resident at once
     bool dc_attr_set[16] = {};   // MaxDynamicSharedMemorySize raised, per far-field kernel instantiation
     int k1_resident = 0;             // workgroups of k_sweep_z_vec16 the device holds at once (persistent grid size)
-    unsigned long long* d_clocks = nullptr;   // SDFGPU_PHASE_CLOCKS builds: phase clocks of the far-field kernels
-    int dc_debug = 0;                // profiling aid: skips phases of k_envelope_dc (results are then wrong)
-    int dc_debug_stage = 0;          // ... of this stage only (2 / 3; 0 = both)
     uint32_t* far_y = nullptr;       // set while a build enqueues a bounded K2 / K3
     int scan_y = kScanExpectNear, scan_x = kScanExpectNear;   // outward-scan bounds of the marching kernels
     bool fused_always = false;
@@ -681,13 +677,6 @@ int launch_envelope(sdfgpu_handle h, int stage, const int16_t* d_in16, const int
         }
         const bool loop = ex && ex->loop && !probe_out;
         a.maxdsq = h->d_slots; a.guard = guard; a.guard_invert = guard_invert;
-#ifdef SDFGPU_DEBUG_HOOKS
-        a.dbg = (h->dc_debug_stage == 0 || h->dc_debug_stage == stage) ? h->dc_debug : 0;    // (an ablated y sweep hands garbage to the x sweep: ablate one stage at a time)
-#endif
-#ifdef SDFGPU_PHASE_CLOCKS
-        if (!h->d_clocks) { HIP_TRY(h, hipMalloc((void**)&h->d_clocks, 16 * 8)); HIP_TRY(h, hipMemset(h->d_clocks, 0, 16 * 8)); }
-        a.clocks = h->d_clocks;
-#endif
         if (ntiles > 0x7fffffffLL) return fail(h, SDFGPU_ERR_UNSUPPORTED_SIZE, "envelope grid too large");
         const int64_t all = ntiles;
         if (probe_out && dec && h->probe_window) {
@@ -739,11 +728,7 @@ int launch_envelope(sdfgpu_handle h, int stage, const int16_t* d_in16, const int
         // vector loads: 4 consecutive lines per load, whole tiles, aligned rows
         auto al = [](const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) % n) == 0; };
         const bool vec = !a.bits && (nz % 4) == 0 && (a.group_lines % NL) == 0 && al(d_in16, 8) && al(d_side_in, 16) && al(a.in_i32, 16);
-#ifdef SDFGPU_DEBUG_HOOKS
-        const size_t lds = envelope_dc_lds_bytes(a.L, NL) + (size_t)(h->dc_debug >> 8) * 1024;  // profiling builds: LDS padding = lower occupancy
-#else
         const size_t lds = envelope_dc_lds_bytes(a.L, NL);
-#endif
         // (the kernel is a template over lines per tile and lanes; measured at 512^3: 8-line tiles -- 20 KB of LDS, 7 - 8
         //  workgroups per CU -- with 128 or 256 lanes are 12 - 25 % slower than 16 lines x 256 lanes, 16 lines x 512 lanes
         //  +-5 %, 32 lines x 512 lanes +-3 %; 2 instead of 4 workgroups per CU is 1.55x slower)
@@ -914,8 +899,7 @@ int launch_ball_dense(sdfgpu_handle h, const uint32_t* d_bits, float* d_out, int
         }
         a.unc = h->unc_override ? h->unc_override : (uint32_t*)h->unc.ptr; a.tileflag = tileflag; a.fix_needed = d_fix_needed;
     }
-    const bool zinv = nz <= (int64_t)bd * 4 && !(h->ball_variant & 2);   // an expansion pass covers whole z-rows
-    a.checked = h->ball_variant & 1;
+    const bool zinv = nz <= (int64_t)bd * 4;   // an expansion pass covers whole z-rows
     if (radius == 3) {
         if (bd != 256 || vb) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "KD3: 256-lane tiles without virtual border only (internal)");
         // nz = 512 (16 words per row, 4 x 4-row tiles): the instance with compile-time row pitch and halo width (option "dense3_fixed")
@@ -1748,137 +1732,114 @@ int sdfgpu_destroy(sdfgpu_handle h) {
 
 const char* sdfgpu_last_error(sdfgpu_handle h) { return h ? h->error.c_str() : g_create_error.c_str(); }
 
-static int sdfgpu_build_body(sdfgpu_handle h, const uint8_t* filled, int64_t nx, int64_t ny, int64_t nz, double resolution,
-                 int add_virtual_border, float* out_sdf, double* out_max, double* out_min) {
-    return build_host_impl(h, filled, nullptr, 0, 0, 0, nx, ny, nz, resolution, add_virtual_border, out_sdf,
-                           out_max, out_min);
-}
 int sdfgpu_build(sdfgpu_handle h, const uint8_t* filled, int64_t nx, int64_t ny, int64_t nz, double resolution,
                  int add_virtual_border, float* out_sdf, double* out_max, double* out_min) {
-    return rz_wrap(h, nullptr, [&]() -> int { return sdfgpu_build_body(h, filled, nx, ny, nz, resolution, add_virtual_border, out_sdf, out_max, out_min); });
+    return rz_wrap(h, nullptr, [&]() -> int {
+        return build_host_impl(h, filled, nullptr, 0, 0, 0, nx, ny, nz, resolution, add_virtual_border, out_sdf,
+                               out_max, out_min);
+    });
 }
 
-static int sdfgpu_build_cells_body(sdfgpu_handle h, const void* cells, size_t cell_stride, size_t occupancy_offset,
-                       int unknown_is_filled, int64_t nx, int64_t ny, int64_t nz, double resolution,
-                       int add_virtual_border, float* out_sdf, double* out_max, double* out_min) {
-    if (h && !cells) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cells is null");
-    if (h && (cell_stride < 4 || (cell_stride % 4) || (occupancy_offset % 4) || occupancy_offset + 4 > cell_stride))
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cell_stride/occupancy_offset must be 4-byte aligned and in range");
-    return build_host_impl(h, nullptr, cells, cell_stride, occupancy_offset, unknown_is_filled, nx, ny, nz,
-                           resolution, add_virtual_border, out_sdf, out_max, out_min);
-}
 int sdfgpu_build_cells(sdfgpu_handle h, const void* cells, size_t cell_stride, size_t occupancy_offset,
                        int unknown_is_filled, int64_t nx, int64_t ny, int64_t nz, double resolution,
                        int add_virtual_border, float* out_sdf, double* out_max, double* out_min) {
-    return rz_wrap(h, nullptr, [&]() -> int { return sdfgpu_build_cells_body(h, cells, cell_stride, occupancy_offset, unknown_is_filled, nx, ny, nz, resolution, add_virtual_border, out_sdf, out_max, out_min); });
+    return rz_wrap(h, nullptr, [&]() -> int {
+        if (h && !cells) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cells is null");
+        if (h && (cell_stride < 4 || (cell_stride % 4) || (occupancy_offset % 4) || occupancy_offset + 4 > cell_stride))
+            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cell_stride/occupancy_offset must be 4-byte aligned and in range");
+        return build_host_impl(h, nullptr, cells, cell_stride, occupancy_offset, unknown_is_filled, nx, ny, nz,
+                               resolution, add_virtual_border, out_sdf, out_max, out_min);
+    });
 }
 
-static int sdfgpu_build_to_device_body(sdfgpu_handle h, const uint8_t* filled, int64_t nx, int64_t ny, int64_t nz, double resolution,
-                           int add_virtual_border, float* d_out_sdf, double* out_max, double* out_min) {
-    if (h && !d_out_sdf) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "d_out_sdf is null");
-    return build_host_impl(h, filled, nullptr, 0, 0, 0, nx, ny, nz, resolution, add_virtual_border, nullptr, out_max, out_min,
-                           d_out_sdf);
-}
 int sdfgpu_build_to_device(sdfgpu_handle h, const uint8_t* filled, int64_t nx, int64_t ny, int64_t nz, double resolution,
                            int add_virtual_border, float* d_out_sdf, double* out_max, double* out_min) {
-    return rz_wrap(h, nullptr, [&]() -> int { return sdfgpu_build_to_device_body(h, filled, nx, ny, nz, resolution, add_virtual_border, d_out_sdf, out_max, out_min); });
+    return rz_wrap(h, nullptr, [&]() -> int {
+        if (h && !d_out_sdf) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "d_out_sdf is null");
+        return build_host_impl(h, filled, nullptr, 0, 0, 0, nx, ny, nz, resolution, add_virtual_border, nullptr, out_max, out_min,
+                               d_out_sdf);
+    });
 }
 
-static int sdfgpu_build_cells_to_device_body(sdfgpu_handle h, const void* cells, size_t cell_stride, size_t occupancy_offset,
-                                 int unknown_is_filled, int64_t nx, int64_t ny, int64_t nz, double resolution,
-                                 int add_virtual_border, float* d_out_sdf, double* out_max, double* out_min) {
-    if (h && !cells) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cells is null");
-    if (h && !d_out_sdf) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "d_out_sdf is null");
-    if (h && (cell_stride < 4 || (cell_stride % 4) || (occupancy_offset % 4) || occupancy_offset + 4 > cell_stride))
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cell_stride/occupancy_offset must be 4-byte aligned and in range");
-    return build_host_impl(h, nullptr, cells, cell_stride, occupancy_offset, unknown_is_filled, nx, ny, nz, resolution,
-                           add_virtual_border, nullptr, out_max, out_min, d_out_sdf);
-}
 int sdfgpu_build_cells_to_device(sdfgpu_handle h, const void* cells, size_t cell_stride, size_t occupancy_offset,
                                  int unknown_is_filled, int64_t nx, int64_t ny, int64_t nz, double resolution,
                                  int add_virtual_border, float* d_out_sdf, double* out_max, double* out_min) {
-    return rz_wrap(h, nullptr, [&]() -> int { return sdfgpu_build_cells_to_device_body(h, cells, cell_stride, occupancy_offset, unknown_is_filled, nx, ny, nz, resolution, add_virtual_border, d_out_sdf, out_max, out_min); });
+    return rz_wrap(h, nullptr, [&]() -> int {
+        if (h && !cells) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cells is null");
+        if (h && !d_out_sdf) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "d_out_sdf is null");
+        if (h && (cell_stride < 4 || (cell_stride % 4) || (occupancy_offset % 4) || occupancy_offset + 4 > cell_stride))
+            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cell_stride/occupancy_offset must be 4-byte aligned and in range");
+        return build_host_impl(h, nullptr, cells, cell_stride, occupancy_offset, unknown_is_filled, nx, ny, nz, resolution,
+                               add_virtual_border, nullptr, out_max, out_min, d_out_sdf);
+    });
 }
 
-static int sdfgpu_build_device_body(sdfgpu_handle h, const uint8_t* d_filled, int64_t nx, int64_t ny, int64_t nz,
-                        double resolution, int add_virtual_border, float* d_out_sdf, void* stream) {
-    if (h && !d_filled) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "d_filled is null");
-    return build_device_impl(h, d_filled, nullptr, 0, 0, 0, nx, ny, nz, resolution, add_virtual_border, d_out_sdf,
-                             (hipStream_t)stream);
-}
 int sdfgpu_build_device(sdfgpu_handle h, const uint8_t* d_filled, int64_t nx, int64_t ny, int64_t nz,
                         double resolution, int add_virtual_border, float* d_out_sdf, void* stream) {
-    return rz_wrap(h, stream, [&]() -> int { return sdfgpu_build_device_body(h, d_filled, nx, ny, nz, resolution, add_virtual_border, d_out_sdf, stream); });
+    return rz_wrap(h, stream, [&]() -> int {
+        if (h && !d_filled) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "d_filled is null");
+        return build_device_impl(h, d_filled, nullptr, 0, 0, 0, nx, ny, nz, resolution, add_virtual_border, d_out_sdf,
+                                 (hipStream_t)stream);
+    });
 }
 
-static int sdfgpu_build_cells_device_body(sdfgpu_handle h, const void* d_cells, size_t cell_stride, size_t occupancy_offset,
-                              int unknown_is_filled, int64_t nx, int64_t ny, int64_t nz, double resolution,
-                              int add_virtual_border, float* d_out_sdf, void* stream) {
-    if (h && !d_cells) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "d_cells is null");
-    return build_device_impl(h, nullptr, d_cells, cell_stride, occupancy_offset, unknown_is_filled, nx, ny, nz,
-                             resolution, add_virtual_border, d_out_sdf, (hipStream_t)stream);
-}
 int sdfgpu_build_cells_device(sdfgpu_handle h, const void* d_cells, size_t cell_stride, size_t occupancy_offset,
                               int unknown_is_filled, int64_t nx, int64_t ny, int64_t nz, double resolution,
                               int add_virtual_border, float* d_out_sdf, void* stream) {
-    return rz_wrap(h, stream, [&]() -> int { return sdfgpu_build_cells_device_body(h, d_cells, cell_stride, occupancy_offset, unknown_is_filled, nx, ny, nz, resolution, add_virtual_border, d_out_sdf, stream); });
+    return rz_wrap(h, stream, [&]() -> int {
+        if (h && !d_cells) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "d_cells is null");
+        return build_device_impl(h, nullptr, d_cells, cell_stride, occupancy_offset, unknown_is_filled, nx, ny, nz,
+                                 resolution, add_virtual_border, d_out_sdf, (hipStream_t)stream);
+    });
 }
 
-static int sdfgpu_build_bits_device_body(sdfgpu_handle h, const uint32_t* d_bits, int64_t nx, int64_t ny, int64_t nz,
-                             double resolution, int add_virtual_border, float* d_out_sdf, void* stream) {
-    if (h && !d_bits) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "d_bits is null");
-    return build_device_impl(h, nullptr, nullptr, 0, 0, 0, nx, ny, nz, resolution, add_virtual_border, d_out_sdf,
-                             (hipStream_t)stream, d_bits);
-}
 int sdfgpu_build_bits_device(sdfgpu_handle h, const uint32_t* d_bits, int64_t nx, int64_t ny, int64_t nz,
                              double resolution, int add_virtual_border, float* d_out_sdf, void* stream) {
-    return rz_wrap(h, stream, [&]() -> int { return sdfgpu_build_bits_device_body(h, d_bits, nx, ny, nz, resolution, add_virtual_border, d_out_sdf, stream); });
+    return rz_wrap(h, stream, [&]() -> int {
+        if (h && !d_bits) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "d_bits is null");
+        return build_device_impl(h, nullptr, nullptr, 0, 0, 0, nx, ny, nz, resolution, add_virtual_border, d_out_sdf,
+                                 (hipStream_t)stream, d_bits);
+    });
 }
 
-static int sdfgpu_build_bits_body(sdfgpu_handle h, const uint32_t* bits, int64_t nx, int64_t ny, int64_t nz, double resolution,
-                      int add_virtual_border, float* out_sdf, double* out_max, double* out_min) {
-    if (h && !bits) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "bits is null");
-    return build_host_impl(h, nullptr, nullptr, 0, 0, 0, nx, ny, nz, resolution, add_virtual_border, out_sdf, out_max, out_min,
-                           nullptr, bits);
-}
 int sdfgpu_build_bits(sdfgpu_handle h, const uint32_t* bits, int64_t nx, int64_t ny, int64_t nz, double resolution,
                       int add_virtual_border, float* out_sdf, double* out_max, double* out_min) {
-    return rz_wrap(h, nullptr, [&]() -> int { return sdfgpu_build_bits_body(h, bits, nx, ny, nz, resolution, add_virtual_border, out_sdf, out_max, out_min); });
+    return rz_wrap(h, nullptr, [&]() -> int {
+        if (h && !bits) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "bits is null");
+        return build_host_impl(h, nullptr, nullptr, 0, 0, 0, nx, ny, nz, resolution, add_virtual_border, out_sdf, out_max, out_min,
+                               nullptr, bits);
+    });
 }
 
-static int sdfgpu_copy_to_host_body(sdfgpu_handle h, void* dst, const void* d_src, size_t bytes, void* stream) {
-    if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-    if (bytes > 0 && (!dst || !d_src)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
-    HIP_TRY(h, hipSetDevice(h->device));
-    return copy_to_host(h, dst, d_src, bytes, (hipStream_t)stream);
-}
 int sdfgpu_copy_to_host(sdfgpu_handle h, void* dst, const void* d_src, size_t bytes, void* stream) {
-    return rz_wrap(h, stream, [&]() -> int { return sdfgpu_copy_to_host_body(h, dst, d_src, bytes, stream); });
+    return rz_wrap(h, stream, [&]() -> int {
+        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
+        if (bytes > 0 && (!dst || !d_src)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
+        HIP_TRY(h, hipSetDevice(h->device));
+        return copy_to_host(h, dst, d_src, bytes, (hipStream_t)stream);
+    });
 }
 
-static int sdfgpu_copy_from_host_body(sdfgpu_handle h, void* d_dst, const void* src, size_t bytes, void* stream) {
-    if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-    if (bytes > 0 && (!d_dst || !src)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
-    HIP_TRY(h, hipSetDevice(h->device));
-    return copy_from_host(h, d_dst, src, bytes, (hipStream_t)stream);
-}
 int sdfgpu_copy_from_host(sdfgpu_handle h, void* d_dst, const void* src, size_t bytes, void* stream) {
-    return rz_wrap(h, stream, [&]() -> int { return sdfgpu_copy_from_host_body(h, d_dst, src, bytes, stream); });
+    return rz_wrap(h, stream, [&]() -> int {
+        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
+        if (bytes > 0 && (!d_dst || !src)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
+        HIP_TRY(h, hipSetDevice(h->device));
+        return copy_from_host(h, d_dst, src, bytes, (hipStream_t)stream);
+    });
 }
 
-static int sdfgpu_upload_classified_body(sdfgpu_handle h, const uint8_t* filled, const void* cells, size_t cell_stride, size_t occupancy_offset,
-                             int unknown_is_filled, int64_t n, uint8_t* d_mask, void* stream) {
-    if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-    if ((!filled && !cells) || !d_mask) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
-    if (n <= 0) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "voxel count must be positive");
-    if (cells && (cell_stride < 4 || (cell_stride % 4) || (occupancy_offset % 4) || occupancy_offset + 4 > cell_stride))
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cell_stride/occupancy_offset must be 4-byte aligned and in range");
-    HIP_TRY(h, hipSetDevice(h->device));
-    return upload_packed(h, cells ? nullptr : filled, cells, cell_stride, occupancy_offset, unknown_is_filled, n, d_mask, (hipStream_t)stream);
-}
 int sdfgpu_upload_classified(sdfgpu_handle h, const uint8_t* filled, const void* cells, size_t cell_stride, size_t occupancy_offset,
                              int unknown_is_filled, int64_t n, uint8_t* d_mask, void* stream) {
-    return rz_wrap(h, stream, [&]() -> int { return sdfgpu_upload_classified_body(h, filled, cells, cell_stride, occupancy_offset, unknown_is_filled, n, d_mask, stream); });
+    return rz_wrap(h, stream, [&]() -> int {
+        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
+        if ((!filled && !cells) || !d_mask) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
+        if (n <= 0) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "voxel count must be positive");
+        if (cells && (cell_stride < 4 || (cell_stride % 4) || (occupancy_offset % 4) || occupancy_offset + 4 > cell_stride))
+            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cell_stride/occupancy_offset must be 4-byte aligned and in range");
+        HIP_TRY(h, hipSetDevice(h->device));
+        return upload_packed(h, cells ? nullptr : filled, cells, cell_stride, occupancy_offset, unknown_is_filled, n, d_mask, (hipStream_t)stream);
+    });
 }
 
 int sdfgpu_extrema_from_dsq(uint32_t max_dsq_free, uint32_t max_dsq_filled, double resolution, double* out_max,
@@ -1910,172 +1871,156 @@ int sdfgpu_get_extrema(sdfgpu_handle h, double* out_max, double* out_min) {
     return sdfgpu_extrema_from_dsq(v[0], v[1], h->last_resolution, out_max, out_min);
 }
 
-static int sdfgpu_sweep_zy_tiered_device_body(sdfgpu_handle h, const uint8_t* d_filled, int64_t nxs, int64_t ny, int64_t nz,
-                                  int32_t* d_plane_dsq, uint32_t* d_far, void* stream) {
-    if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-    h->guard = nullptr;
-    h->far_y = nullptr;
-    if (!d_filled || !d_plane_dsq) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null device pointer");
-    if (int rc = check_dims(h, nxs, ny, nz)) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    const int64_t n = nxs * ny * nz;
-    hipStream_t s = (hipStream_t)stream;
-    // (this call uses the handle's status block and scratch fields like a whole build does: it takes part in the same
-    //  cross-stream ordering -- waits for the handle's previous work when that ran on another stream, and is waited for)
-    if (h->order_valid && s != h->order_stream) HIP_TRY(h, hipStreamWaitEvent(s, h->build_done_ev, 0));
-    struct OrderEnd { sdfgpu_handle h; hipStream_t s; ~OrderEnd() { if (hipEventRecord(h->build_done_ev, s) == hipSuccess) { h->order_valid = true; h->order_stream = s; } } } order_end{h, s};
-    const bool tiered = h->envelope_on && far_geometry_ok(h, 2, nxs, ny, nz) &&
-                        (nz % 4) == 0 && (reinterpret_cast<uintptr_t>(d_plane_dsq) % 16) == 0;
-    if (!tiered) {
-        if (fused_zy_eligible(h, d_filled, d_plane_dsq, nz)) return launch_sweep_zy_fused(h, d_filled, d_plane_dsq, nullptr, nxs, ny, nz, s);
-        if (int rc = ensure(h, h->zfield, (size_t)n * 2, "z field")) return rc;
-        if (int rc = launch_sweep_z(h, d_filled, nullptr, 0, 0, 0, nxs, ny, nz, (int16_t*)h->zfield.ptr, s)) return rc;
-        return launch_sweep_y(h, (const int16_t*)h->zfield.ptr, d_plane_dsq, nullptr, nxs, ny, nz, s);
-    }
-    // K1, then the y sweep picked on the device: probe -> decide -> marching (bounded scan) / envelope, int32 output
-    if (int rc = ensure(h, h->zfield, (size_t)n * 2, "z field")) return rc;
-    HIP_TRY(h, hipMemsetAsync(h->d_small, 0, 128, s));
-    h->small_clean = false;
-    if (int rc = launch_sweep_z(h, d_filled, nullptr, 0, 0, 0, nxs, ny, nz, (int16_t*)h->zfield.ptr, s)) return rc;
-    DcExtra ex;
-    ex.out_i32 = d_plane_dsq;
-    DcDecide dy; dy.stage = 0;
-    if (h->force_env < 0) {
-        if (int rc = launch_envelope(h, 2, (const int16_t*)h->zfield.ptr, nullptr, nullptr, nullptr, nxs, ny, nz, 1.0, 0,
-                                     h->d_small, nullptr, s, 0, h->d_small + 12, &ex, &dy)) return rc;
-    } else if (int rc = launch_decide(h, 0, false, s)) return rc;
-    h->guard = h->d_small + 8;
-    h->far_y = h->d_small + 4;
-    h->scan_y = kScanExpectNear;
-    int rc = launch_sweep_y(h, (const int16_t*)h->zfield.ptr, d_plane_dsq, nullptr, nxs, ny, nz, s);
-    h->guard = nullptr;
-    h->far_y = nullptr;
-    if (rc) return rc;
-    if (int rc2 = launch_envelope(h, 2, (const int16_t*)h->zfield.ptr, nullptr, nullptr, nullptr, nxs, ny, nz, 1.0, 0,
-                                  h->d_small, h->d_small + 4, s, 0, nullptr, &ex)) return rc2;
-    if (d_far) HIP_TRY(h, hipMemcpyAsync(d_far, h->d_small + 4, 4, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(h, hipMemsetAsync(h->d_small, 0, 128, s));
-    h->small_clean = true;
-    return SDFGPU_OK;
-}
 int sdfgpu_sweep_zy_tiered_device(sdfgpu_handle h, const uint8_t* d_filled, int64_t nxs, int64_t ny, int64_t nz,
                                   int32_t* d_plane_dsq, uint32_t* d_far, void* stream) {
-    return rz_wrap(h, stream, [&]() -> int { return sdfgpu_sweep_zy_tiered_device_body(h, d_filled, nxs, ny, nz, d_plane_dsq, d_far, stream); });
+    return rz_wrap(h, stream, [&]() -> int {
+        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
+        h->guard = nullptr;
+        h->far_y = nullptr;
+        if (!d_filled || !d_plane_dsq) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null device pointer");
+        if (int rc = check_dims(h, nxs, ny, nz)) return rc;
+        HIP_TRY(h, hipSetDevice(h->device));
+        const int64_t n = nxs * ny * nz;
+        hipStream_t s = (hipStream_t)stream;
+        // (this call uses the handle's status block and scratch fields like a whole build does: it takes part in the same
+        //  cross-stream ordering -- waits for the handle's previous work when that ran on another stream, and is waited for)
+        if (h->order_valid && s != h->order_stream) HIP_TRY(h, hipStreamWaitEvent(s, h->build_done_ev, 0));
+        struct OrderEnd { sdfgpu_handle h; hipStream_t s; ~OrderEnd() { if (hipEventRecord(h->build_done_ev, s) == hipSuccess) { h->order_valid = true; h->order_stream = s; } } } order_end{h, s};
+        const bool tiered = h->envelope_on && far_geometry_ok(h, 2, nxs, ny, nz) &&
+                            (nz % 4) == 0 && (reinterpret_cast<uintptr_t>(d_plane_dsq) % 16) == 0;
+        if (!tiered) {
+            if (fused_zy_eligible(h, d_filled, d_plane_dsq, nz)) return launch_sweep_zy_fused(h, d_filled, d_plane_dsq, nullptr, nxs, ny, nz, s);
+            if (int rc = ensure(h, h->zfield, (size_t)n * 2, "z field")) return rc;
+            if (int rc = launch_sweep_z(h, d_filled, nullptr, 0, 0, 0, nxs, ny, nz, (int16_t*)h->zfield.ptr, s)) return rc;
+            return launch_sweep_y(h, (const int16_t*)h->zfield.ptr, d_plane_dsq, nullptr, nxs, ny, nz, s);
+        }
+        // K1, then the y sweep picked on the device: probe -> decide -> marching (bounded scan) / envelope, int32 output
+        if (int rc = ensure(h, h->zfield, (size_t)n * 2, "z field")) return rc;
+        HIP_TRY(h, hipMemsetAsync(h->d_small, 0, 128, s));
+        h->small_clean = false;
+        if (int rc = launch_sweep_z(h, d_filled, nullptr, 0, 0, 0, nxs, ny, nz, (int16_t*)h->zfield.ptr, s)) return rc;
+        DcExtra ex;
+        ex.out_i32 = d_plane_dsq;
+        DcDecide dy; dy.stage = 0;
+        if (h->force_env < 0) {
+            if (int rc = launch_envelope(h, 2, (const int16_t*)h->zfield.ptr, nullptr, nullptr, nullptr, nxs, ny, nz, 1.0, 0,
+                                         h->d_small, nullptr, s, 0, h->d_small + 12, &ex, &dy)) return rc;
+        } else if (int rc = launch_decide(h, 0, false, s)) return rc;
+        h->guard = h->d_small + 8;
+        h->far_y = h->d_small + 4;
+        h->scan_y = kScanExpectNear;
+        int rc = launch_sweep_y(h, (const int16_t*)h->zfield.ptr, d_plane_dsq, nullptr, nxs, ny, nz, s);
+        h->guard = nullptr;
+        h->far_y = nullptr;
+        if (rc) return rc;
+        if (int rc2 = launch_envelope(h, 2, (const int16_t*)h->zfield.ptr, nullptr, nullptr, nullptr, nxs, ny, nz, 1.0, 0,
+                                      h->d_small, h->d_small + 4, s, 0, nullptr, &ex)) return rc2;
+        if (d_far) HIP_TRY(h, hipMemcpyAsync(d_far, h->d_small + 4, 4, hipMemcpyDeviceToDevice, s));
+        HIP_TRY(h, hipMemsetAsync(h->d_small, 0, 128, s));
+        h->small_clean = true;
+        return SDFGPU_OK;
+    });
 }
 
-static int sdfgpu_sweep_zy_device_body(sdfgpu_handle h, const uint8_t* d_filled, int64_t nxs, int64_t ny, int64_t nz,
-                           int32_t* d_plane_dsq, void* stream) {
-    return sdfgpu_sweep_zy_tiered_device(h, d_filled, nxs, ny, nz, d_plane_dsq, nullptr, stream);
-}
 int sdfgpu_sweep_zy_device(sdfgpu_handle h, const uint8_t* d_filled, int64_t nxs, int64_t ny, int64_t nz,
                            int32_t* d_plane_dsq, void* stream) {
-    return rz_wrap(h, stream, [&]() -> int { return sdfgpu_sweep_zy_device_body(h, d_filled, nxs, ny, nz, d_plane_dsq, stream); });
+    return rz_wrap(h, stream, [&]() -> int {
+        return sdfgpu_sweep_zy_tiered_device(h, d_filled, nxs, ny, nz, d_plane_dsq, nullptr, stream);
+    });
 }
 
-static int sdfgpu_sweep_x_lines_device_body(sdfgpu_handle h, const int32_t* d_plane_dsq, int64_t nx, int64_t nys, int64_t nz,
-                                int64_t y_global, int64_t ny_global, double resolution, int add_virtual_border,
-                                float* d_out_sdf, uint32_t* d_maxdsq, void* stream) {
-    if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-    if (!d_plane_dsq || !d_out_sdf || !d_maxdsq) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null device pointer");
-    if (y_global < 0 || y_global + nys > ny_global) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "inconsistent slab geometry");
-    if (int rc = check_dims(h, nx, nys, nz)) return rc;
-    if (int rc = check_dims(h, nx, ny_global, nz)) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    h->guard = nullptr;
-    h->far_y = nullptr;
-    if (h->order_valid && s != h->order_stream) HIP_TRY(h, hipStreamWaitEvent(s, h->build_done_ev, 0));
-    struct OrderEnd { sdfgpu_handle h; hipStream_t s; ~OrderEnd() { if (hipEventRecord(h->build_done_ev, s) == hipSuccess) { h->order_valid = true; h->order_stream = s; } } } order_end{h, s};
-    const bool tiered = h->envelope_on && far_geometry_ok(h, 3, nx, nys, nz, ny_global) &&
-                        (reinterpret_cast<uintptr_t>(d_plane_dsq) % 16) == 0;
-    if (!tiered) {
-        if (int rc = launch_sweep_x(h, d_plane_dsq, d_out_sdf, 0, nx, 0, nys, nz, 0, 0, 0, nx, resolution, add_virtual_border,
-                                    d_maxdsq, nullptr, s, y_global, ny_global)) return rc;
-        return h->defer_fold ? SDFGPU_OK : fold_slots(h, d_maxdsq, s);
-    }
-    HIP_TRY(h, hipMemsetAsync(h->d_small, 0, 128, s));
-    h->small_clean = false;
-    DcExtra ex;
-    ex.in_i32 = d_plane_dsq; ex.y_off = y_global; ex.ny_glob = ny_global;
-    DcDecide dx; dx.stage = 1;
-    if (h->force_env < 0) {
-        if (int rc = launch_envelope(h, 3, nullptr, nullptr, d_out_sdf, nullptr, nx, nys, nz, resolution, add_virtual_border,
-                                     h->d_small, nullptr, s, 0, h->d_small + 12, &ex, &dx)) return rc;
-    } else if (int rc = launch_decide(h, 1, false, s)) return rc;
-    h->guard = h->d_small + 10;
-    int rc = launch_sweep_x(h, d_plane_dsq, d_out_sdf, 0, nx, 0, nys, nz, 0, 0, 0, nx, resolution, add_virtual_border,
-                            d_maxdsq, nullptr, s, y_global, ny_global, kScanExpectNear, h->d_small + 5);
-    h->guard = nullptr;
-    if (rc) return rc;
-    if (int rc2 = launch_envelope(h, 3, nullptr, nullptr, d_out_sdf, nullptr, nx, nys, nz, resolution, add_virtual_border,
-                                  h->d_small, h->d_small + 5, s, 0, nullptr, &ex)) return rc2;
-    if (!h->defer_fold) if (int rc3 = fold_slots(h, d_maxdsq, s)) return rc3;
-    HIP_TRY(h, hipMemsetAsync(h->d_small, 0, 128, s));
-    h->small_clean = true;
-    return SDFGPU_OK;
-}
 int sdfgpu_sweep_x_lines_device(sdfgpu_handle h, const int32_t* d_plane_dsq, int64_t nx, int64_t nys, int64_t nz,
                                 int64_t y_global, int64_t ny_global, double resolution, int add_virtual_border,
                                 float* d_out_sdf, uint32_t* d_maxdsq, void* stream) {
-    return rz_wrap(h, stream, [&]() -> int { return sdfgpu_sweep_x_lines_device_body(h, d_plane_dsq, nx, nys, nz, y_global, ny_global, resolution, add_virtual_border, d_out_sdf, d_maxdsq, stream); });
+    return rz_wrap(h, stream, [&]() -> int {
+        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
+        if (!d_plane_dsq || !d_out_sdf || !d_maxdsq) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null device pointer");
+        if (y_global < 0 || y_global + nys > ny_global) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "inconsistent slab geometry");
+        if (int rc = check_dims(h, nx, nys, nz)) return rc;
+        if (int rc = check_dims(h, nx, ny_global, nz)) return rc;
+        HIP_TRY(h, hipSetDevice(h->device));
+        hipStream_t s = (hipStream_t)stream;
+        h->guard = nullptr;
+        h->far_y = nullptr;
+        if (h->order_valid && s != h->order_stream) HIP_TRY(h, hipStreamWaitEvent(s, h->build_done_ev, 0));
+        struct OrderEnd { sdfgpu_handle h; hipStream_t s; ~OrderEnd() { if (hipEventRecord(h->build_done_ev, s) == hipSuccess) { h->order_valid = true; h->order_stream = s; } } } order_end{h, s};
+        const bool tiered = h->envelope_on && far_geometry_ok(h, 3, nx, nys, nz, ny_global) &&
+                            (reinterpret_cast<uintptr_t>(d_plane_dsq) % 16) == 0;
+        if (!tiered) {
+            if (int rc = launch_sweep_x(h, d_plane_dsq, d_out_sdf, 0, nx, 0, nys, nz, 0, 0, 0, nx, resolution, add_virtual_border,
+                                        d_maxdsq, nullptr, s, y_global, ny_global)) return rc;
+            return h->defer_fold ? SDFGPU_OK : fold_slots(h, d_maxdsq, s);
+        }
+        HIP_TRY(h, hipMemsetAsync(h->d_small, 0, 128, s));
+        h->small_clean = false;
+        DcExtra ex;
+        ex.in_i32 = d_plane_dsq; ex.y_off = y_global; ex.ny_glob = ny_global;
+        DcDecide dx; dx.stage = 1;
+        if (h->force_env < 0) {
+            if (int rc = launch_envelope(h, 3, nullptr, nullptr, d_out_sdf, nullptr, nx, nys, nz, resolution, add_virtual_border,
+                                         h->d_small, nullptr, s, 0, h->d_small + 12, &ex, &dx)) return rc;
+        } else if (int rc = launch_decide(h, 1, false, s)) return rc;
+        h->guard = h->d_small + 10;
+        int rc = launch_sweep_x(h, d_plane_dsq, d_out_sdf, 0, nx, 0, nys, nz, 0, 0, 0, nx, resolution, add_virtual_border,
+                                d_maxdsq, nullptr, s, y_global, ny_global, kScanExpectNear, h->d_small + 5);
+        h->guard = nullptr;
+        if (rc) return rc;
+        if (int rc2 = launch_envelope(h, 3, nullptr, nullptr, d_out_sdf, nullptr, nx, nys, nz, resolution, add_virtual_border,
+                                      h->d_small, h->d_small + 5, s, 0, nullptr, &ex)) return rc2;
+        if (!h->defer_fold) if (int rc3 = fold_slots(h, d_maxdsq, s)) return rc3;
+        HIP_TRY(h, hipMemsetAsync(h->d_small, 0, 128, s));
+        h->small_clean = true;
+        return SDFGPU_OK;
+    });
 }
 
-static int sdfgpu_sweep_x_device_body(sdfgpu_handle h, const int32_t* d_plane_dsq, int64_t halo_lo, int64_t nxs,
-                          int64_t halo_hi, int64_t ny, int64_t nz, int lo_truncated, int hi_truncated,
-                          int64_t x_global, int64_t nx_global, double resolution, int add_virtual_border,
-                          float* d_out_sdf, uint32_t* d_maxdsq, uint32_t* d_status, void* stream) {
-    if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-    if (!d_plane_dsq || !d_out_sdf || !d_maxdsq)
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null device pointer");
-    if (halo_lo < 0 || halo_hi < 0 || x_global < 0 || x_global + nxs > nx_global)
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "inconsistent slab geometry");
-    h->guard = nullptr;
-    h->far_y = nullptr;
-    if (int rc = check_dims(h, halo_lo + nxs + halo_hi, ny, nz)) return rc;
-    if (int rc = check_dims(h, nx_global, ny, nz)) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (int rc = launch_sweep_x(h, d_plane_dsq, d_out_sdf, halo_lo, nxs, halo_hi, ny, nz, lo_truncated, hi_truncated,
-                                x_global, nx_global, resolution, add_virtual_border, d_maxdsq, d_status,
-                                (hipStream_t)stream)) return rc;
-    return h->defer_fold ? SDFGPU_OK : fold_slots(h, d_maxdsq, (hipStream_t)stream);
-}
 int sdfgpu_sweep_x_device(sdfgpu_handle h, const int32_t* d_plane_dsq, int64_t halo_lo, int64_t nxs,
                           int64_t halo_hi, int64_t ny, int64_t nz, int lo_truncated, int hi_truncated,
                           int64_t x_global, int64_t nx_global, double resolution, int add_virtual_border,
                           float* d_out_sdf, uint32_t* d_maxdsq, uint32_t* d_status, void* stream) {
-    return rz_wrap(h, stream, [&]() -> int { return sdfgpu_sweep_x_device_body(h, d_plane_dsq, halo_lo, nxs, halo_hi, ny, nz, lo_truncated, hi_truncated, x_global, nx_global, resolution, add_virtual_border, d_out_sdf, d_maxdsq, d_status, stream); });
+    return rz_wrap(h, stream, [&]() -> int {
+        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
+        if (!d_plane_dsq || !d_out_sdf || !d_maxdsq)
+            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null device pointer");
+        if (halo_lo < 0 || halo_hi < 0 || x_global < 0 || x_global + nxs > nx_global)
+            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "inconsistent slab geometry");
+        h->guard = nullptr;
+        h->far_y = nullptr;
+        if (int rc = check_dims(h, halo_lo + nxs + halo_hi, ny, nz)) return rc;
+        if (int rc = check_dims(h, nx_global, ny, nz)) return rc;
+        HIP_TRY(h, hipSetDevice(h->device));
+        if (int rc = launch_sweep_x(h, d_plane_dsq, d_out_sdf, halo_lo, nxs, halo_hi, ny, nz, lo_truncated, hi_truncated,
+                                    x_global, nx_global, resolution, add_virtual_border, d_maxdsq, d_status,
+                                    (hipStream_t)stream)) return rc;
+        return h->defer_fold ? SDFGPU_OK : fold_slots(h, d_maxdsq, (hipStream_t)stream);
+    });
 }
 
-static int sdfgpu_pack_bits_device_body(sdfgpu_handle h, const uint8_t* d_filled, int64_t n_rows, int64_t nz, uint32_t* d_bits,
-                            void* stream) {
-    if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-    if (!d_filled || !d_bits) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null device pointer");
-    if (n_rows <= 0 || nz <= 0 || (nz % 32) != 0) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "pack_bits needs nz % 32 == 0");
-    HIP_TRY(h, hipSetDevice(h->device));
-    return launch_pack_bits(h, d_filled, nullptr, 0, 0, 0, n_rows * nz, d_bits, (hipStream_t)stream);
-}
 int sdfgpu_pack_bits_device(sdfgpu_handle h, const uint8_t* d_filled, int64_t n_rows, int64_t nz, uint32_t* d_bits,
                             void* stream) {
-    return rz_wrap(h, stream, [&]() -> int { return sdfgpu_pack_bits_device_body(h, d_filled, n_rows, nz, d_bits, stream); });
+    return rz_wrap(h, stream, [&]() -> int {
+        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
+        if (!d_filled || !d_bits) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null device pointer");
+        if (n_rows <= 0 || nz <= 0 || (nz % 32) != 0) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "pack_bits needs nz % 32 == 0");
+        HIP_TRY(h, hipSetDevice(h->device));
+        return launch_pack_bits(h, d_filled, nullptr, 0, 0, 0, n_rows * nz, d_bits, (hipStream_t)stream);
+    });
 }
 
-static int sdfgpu_dense_ball_device_body(sdfgpu_handle h, const uint32_t* d_bits, int64_t rows_x, int64_t out_lo, int64_t out_hi,
-                             int64_t ny, int64_t nz, double resolution, float* d_out_sdf, uint32_t* d_maxdsq,
-                             uint32_t* d_uncertified, void* stream) {
-    if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-    if (!d_bits || !d_out_sdf || !d_maxdsq || !d_uncertified) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null device pointer");
-    if (out_lo < 0 || out_hi <= out_lo || out_hi > rows_x) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "inconsistent slab geometry");
-    if (int rc = check_dims(h, rows_x, ny, nz)) return rc;
-    if (!dense_eligible(h, nz, 0)) return fail(h, SDFGPU_ERR_UNSUPPORTED_SIZE, "dense kernel needs nz = 32 * 2^k <= 2048");
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (int rc = launch_ball_dense(h, d_bits, d_out_sdf, rows_x, out_lo, out_hi, ny, nz, resolution, d_maxdsq,
-                                   d_uncertified, (hipStream_t)stream)) return rc;
-    return h->defer_fold ? SDFGPU_OK : fold_slots(h, d_maxdsq, (hipStream_t)stream);
-}
 int sdfgpu_dense_ball_device(sdfgpu_handle h, const uint32_t* d_bits, int64_t rows_x, int64_t out_lo, int64_t out_hi,
                              int64_t ny, int64_t nz, double resolution, float* d_out_sdf, uint32_t* d_maxdsq,
                              uint32_t* d_uncertified, void* stream) {
-    return rz_wrap(h, stream, [&]() -> int { return sdfgpu_dense_ball_device_body(h, d_bits, rows_x, out_lo, out_hi, ny, nz, resolution, d_out_sdf, d_maxdsq, d_uncertified, stream); });
+    return rz_wrap(h, stream, [&]() -> int {
+        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
+        if (!d_bits || !d_out_sdf || !d_maxdsq || !d_uncertified) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null device pointer");
+        if (out_lo < 0 || out_hi <= out_lo || out_hi > rows_x) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "inconsistent slab geometry");
+        if (int rc = check_dims(h, rows_x, ny, nz)) return rc;
+        if (!dense_eligible(h, nz, 0)) return fail(h, SDFGPU_ERR_UNSUPPORTED_SIZE, "dense kernel needs nz = 32 * 2^k <= 2048");
+        HIP_TRY(h, hipSetDevice(h->device));
+        if (int rc = launch_ball_dense(h, d_bits, d_out_sdf, rows_x, out_lo, out_hi, ny, nz, resolution, d_maxdsq,
+                                       d_uncertified, (hipStream_t)stream)) return rc;
+        return h->defer_fold ? SDFGPU_OK : fold_slots(h, d_maxdsq, (hipStream_t)stream);
+    });
 }
 
 // One x slab of the dense path in three host calls instead of ten (the per-call cost of the Python binding is what
@@ -2084,299 +2029,274 @@ int sdfgpu_dense_ball_device(sdfgpu_handle h, const uint32_t* d_bits, int64_t ro
 // (10 / 11 = only the first / second half of that), phase 2 = ball kernel on the border planes + fold of the maxima
 // (after the exchange has been waited for).  Without neighbours, or for slabs too thin to split, phase 0 packs
 // everything, phase 1 does nothing and phase 2 runs the ball kernel on the whole slab.
-static int sdfgpu_slab_dense_phase_body(sdfgpu_handle h, int phase, const uint8_t* d_mask_slab, int64_t nxs, int64_t ny, int64_t nz,
-                            uint32_t* d_bits_ext, int64_t halo_lo, int64_t halo_hi, double resolution, float* d_out,
-                            uint32_t* d_small, void* stream) {
-    if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-    if (!d_mask_slab || !d_bits_ext || !d_out || !d_small) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null device pointer");
-    const int64_t hb = kBallR;
-    if (nxs <= 0 || (halo_lo != 0 && halo_lo != hb) || (halo_hi != 0 && halo_hi != hb))
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "inconsistent slab geometry");
-    if (int rc = check_dims(h, halo_lo + nxs + halo_hi, ny, nz)) return rc;
-    if (!dense_eligible(h, nz, 0)) return fail(h, SDFGPU_ERR_UNSUPPORTED_SIZE, "dense kernel needs nz = 32 * 2^k <= 2048");
-    HIP_TRY(h, hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t plane = ny * nz, wplane = ny * (nz / 32), rows_x = halo_lo + nxs + halo_hi;
-    uint32_t* own = d_bits_ext + halo_lo * wplane;
-    const bool split = (halo_lo || halo_hi) && 4 * hb < nxs;
-    const int64_t i_lo = (split && halo_lo) ? hb : 0, i_hi = (split && halo_hi) ? nxs - hb : nxs;
-    auto pack = [&](int64_t p0, int64_t p1) -> int {
-        if (p1 <= p0) return SDFGPU_OK;
-        return launch_pack_bits(h, d_mask_slab + p0 * plane, nullptr, 0, 0, 0, (p1 - p0) * plane, own + p0 * wplane, s);
-    };
-    auto ball = [&](int64_t p0, int64_t p1) -> int {
-        if (p1 <= p0) return SDFGPU_OK;
-        return launch_ball_dense(h, d_bits_ext, d_out + p0 * plane, rows_x, halo_lo + p0, halo_lo + p1, ny, nz, resolution,
-                                 d_small, d_small + 3, s);
-    };
-    switch (phase) {
-    case 0:
-        HIP_TRY(h, hipMemsetAsync(d_small, 0, 16, s));
-        if (!split) return pack(0, nxs);
-        if (int rc = pack(0, hb)) return rc;
-        return pack(nxs - hb, nxs);
-    case 1:
-    case 10:
-    case 11:
-        if (!split) return SDFGPU_OK;
-        if (phase != 11) if (int rc = pack(hb, nxs - hb)) return rc;
-        if (phase != 10) if (int rc = ball(i_lo, i_hi)) return rc;
-        return SDFGPU_OK;
-    case 2:
-        if (!split) {
-            if (int rc = ball(0, nxs)) return rc;
-        } else {
-            if (int rc = ball(0, i_lo)) return rc;
-            if (int rc = ball(i_hi, nxs)) return rc;
-        }
-        return fold_slots(h, d_small, s);
-    default:
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "unknown phase %d", phase);
-    }
-}
 int sdfgpu_slab_dense_phase(sdfgpu_handle h, int phase, const uint8_t* d_mask_slab, int64_t nxs, int64_t ny, int64_t nz,
                             uint32_t* d_bits_ext, int64_t halo_lo, int64_t halo_hi, double resolution, float* d_out,
                             uint32_t* d_small, void* stream) {
-    return rz_wrap(h, stream, [&]() -> int { return sdfgpu_slab_dense_phase_body(h, phase, d_mask_slab, nxs, ny, nz, d_bits_ext, halo_lo, halo_hi, resolution, d_out, d_small, stream); });
+    return rz_wrap(h, stream, [&]() -> int {
+        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
+        if (!d_mask_slab || !d_bits_ext || !d_out || !d_small) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null device pointer");
+        const int64_t hb = kBallR;
+        if (nxs <= 0 || (halo_lo != 0 && halo_lo != hb) || (halo_hi != 0 && halo_hi != hb))
+            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "inconsistent slab geometry");
+        if (int rc = check_dims(h, halo_lo + nxs + halo_hi, ny, nz)) return rc;
+        if (!dense_eligible(h, nz, 0)) return fail(h, SDFGPU_ERR_UNSUPPORTED_SIZE, "dense kernel needs nz = 32 * 2^k <= 2048");
+        HIP_TRY(h, hipSetDevice(h->device));
+        hipStream_t s = (hipStream_t)stream;
+        const int64_t plane = ny * nz, wplane = ny * (nz / 32), rows_x = halo_lo + nxs + halo_hi;
+        uint32_t* own = d_bits_ext + halo_lo * wplane;
+        const bool split = (halo_lo || halo_hi) && 4 * hb < nxs;
+        const int64_t i_lo = (split && halo_lo) ? hb : 0, i_hi = (split && halo_hi) ? nxs - hb : nxs;
+        auto pack = [&](int64_t p0, int64_t p1) -> int {
+            if (p1 <= p0) return SDFGPU_OK;
+            return launch_pack_bits(h, d_mask_slab + p0 * plane, nullptr, 0, 0, 0, (p1 - p0) * plane, own + p0 * wplane, s);
+        };
+        auto ball = [&](int64_t p0, int64_t p1) -> int {
+            if (p1 <= p0) return SDFGPU_OK;
+            return launch_ball_dense(h, d_bits_ext, d_out + p0 * plane, rows_x, halo_lo + p0, halo_lo + p1, ny, nz, resolution,
+                                     d_small, d_small + 3, s);
+        };
+        switch (phase) {
+        case 0:
+            HIP_TRY(h, hipMemsetAsync(d_small, 0, 16, s));
+            if (!split) return pack(0, nxs);
+            if (int rc = pack(0, hb)) return rc;
+            return pack(nxs - hb, nxs);
+        case 1:
+        case 10:
+        case 11:
+            if (!split) return SDFGPU_OK;
+            if (phase != 11) if (int rc = pack(hb, nxs - hb)) return rc;
+            if (phase != 10) if (int rc = ball(i_lo, i_hi)) return rc;
+            return SDFGPU_OK;
+        case 2:
+            if (!split) {
+                if (int rc = ball(0, nxs)) return rc;
+            } else {
+                if (int rc = ball(0, i_lo)) return rc;
+                if (int rc = ball(i_hi, nxs)) return rc;
+            }
+            return fold_slots(h, d_small, s);
+        default:
+            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "unknown phase %d", phase);
+        }
+    });
 }
 
-static int sdfgpu_fold_extrema_device_body(sdfgpu_handle h, uint32_t* d_maxdsq, void* stream) {
-    if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-    if (!d_maxdsq) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null device pointer");
-    HIP_TRY(h, hipSetDevice(h->device));
-    return fold_slots(h, d_maxdsq, (hipStream_t)stream);
-}
 int sdfgpu_fold_extrema_device(sdfgpu_handle h, uint32_t* d_maxdsq, void* stream) {
-    return rz_wrap(h, stream, [&]() -> int { return sdfgpu_fold_extrema_device_body(h, d_maxdsq, stream); });
+    return rz_wrap(h, stream, [&]() -> int {
+        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
+        if (!d_maxdsq) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null device pointer");
+        HIP_TRY(h, hipSetDevice(h->device));
+        return fold_slots(h, d_maxdsq, (hipStream_t)stream);
+    });
 }
 
-static int sdfgpu_build_tagged_cells_body(sdfgpu_handle h, const void* cells, size_t cell_stride, size_t occupancy_offset,
-                              size_t object_id_offset, int object_mode, const uint32_t* object_ids, int64_t n_object_ids,
-                              int unknown_is_filled, int64_t nx, int64_t ny, int64_t nz, double resolution,
-                              int add_virtual_border, float* out_sdf, double* out_max, double* out_min) {
-    if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-    if (!out_sdf) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null host pointer");
-    if (cell_stride < 8 || (cell_stride % 4) || (occupancy_offset % 4) || (object_id_offset % 4) ||
-        occupancy_offset + 4 > cell_stride || object_id_offset + 4 > cell_stride)
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cell layout must be 4-byte aligned and in range");
-    if (object_mode < 0 || object_mode > 2 || n_object_ids < 0 || n_object_ids > 0x7fffffffLL ||
-        (object_mode == 2 && n_object_ids > 0 && !object_ids))
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "bad object filter");
-    if (object_mode == 2 && n_object_ids == 0) object_mode = 0;       // "no objects supplied" = any object (:826)
-    if (int rc = check_dims(h, nx, ny, nz)) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    const int64_t n = nx * ny * nz;
-    if (!cells) {                                  // the records of the previous call on this handle, still on the device
-        if (h->tag_cached_bytes == 0 || h->tag_cached_bytes != (size_t)n * cell_stride)
-            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cells is null and the handle holds no cell records of this size");
-    } else {
-        h->tag_cached_bytes = 0;
-        if (int rc = ensure(h, h->stage_in, (size_t)n * cell_stride, "input staging")) return rc;
-    }
-    if (int rc = ensure(h, h->stage_out, (size_t)n * 4, "output staging")) return rc;
-    if (int rc = ensure(h, h->tagmask, (size_t)n, "tagged-object mask")) return rc;
-    if (int rc = ensure(h, h->tagids, (size_t)std::max<int64_t>(n_object_ids, 1) * 4, "object id list")) return rc;
-    if (cells) {
-        if (int rc0 = copy_from_host(h, h->stage_in.ptr, cells, (size_t)n * cell_stride)) return rc0;
-        h->tag_cached_bytes = (size_t)n * cell_stride;
-    }
-    if (n_object_ids > 0) {                        // sorted copy: the classify kernel binary-searches it
-        std::vector<uint32_t> sorted_ids(object_ids, object_ids + n_object_ids);
-        std::sort(sorted_ids.begin(), sorted_ids.end());
-        HIP_TRY(h, hipMemcpy(h->tagids.ptr, sorted_ids.data(), (size_t)n_object_ids * 4, hipMemcpyHostToDevice));
-    }
-    hipLaunchKernelGGL(k_classify_tagged, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, nullptr,
-                       (const char*)h->stage_in.ptr, (int64_t)cell_stride, (int64_t)occupancy_offset, (int64_t)object_id_offset,
-                       unknown_is_filled, object_mode, (const uint32_t*)h->tagids.ptr, (int)n_object_ids, n,
-                       (uint8_t*)h->tagmask.ptr);
-    HIP_TRY(h, hipGetLastError());
-    int rc = build_device_impl(h, (const uint8_t*)h->tagmask.ptr, nullptr, 0, 0, 0, nx, ny, nz, resolution, add_virtual_border,
-                               (float*)h->stage_out.ptr, nullptr);
-    if (rc) return rc;
-    if (int rc2 = copy_to_host(h, out_sdf, h->stage_out.ptr, (size_t)n * 4)) return rc2;
-    double mx, mn;
-    rc = sdfgpu_get_extrema(h, &mx, &mn);
-    if (rc) return rc;
-    if (out_max) *out_max = mx;
-    if (out_min) *out_min = mn;
-    return SDFGPU_OK;
-}
 int sdfgpu_build_tagged_cells(sdfgpu_handle h, const void* cells, size_t cell_stride, size_t occupancy_offset,
                               size_t object_id_offset, int object_mode, const uint32_t* object_ids, int64_t n_object_ids,
                               int unknown_is_filled, int64_t nx, int64_t ny, int64_t nz, double resolution,
                               int add_virtual_border, float* out_sdf, double* out_max, double* out_min) {
-    return rz_wrap(h, nullptr, [&]() -> int { return sdfgpu_build_tagged_cells_body(h, cells, cell_stride, occupancy_offset, object_id_offset, object_mode, object_ids, n_object_ids, unknown_is_filled, nx, ny, nz, resolution, add_virtual_border, out_sdf, out_max, out_min); });
+    return rz_wrap(h, nullptr, [&]() -> int {
+        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
+        if (!out_sdf) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null host pointer");
+        if (cell_stride < 8 || (cell_stride % 4) || (occupancy_offset % 4) || (object_id_offset % 4) ||
+            occupancy_offset + 4 > cell_stride || object_id_offset + 4 > cell_stride)
+            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cell layout must be 4-byte aligned and in range");
+        if (object_mode < 0 || object_mode > 2 || n_object_ids < 0 || n_object_ids > 0x7fffffffLL ||
+            (object_mode == 2 && n_object_ids > 0 && !object_ids))
+            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "bad object filter");
+        if (object_mode == 2 && n_object_ids == 0) object_mode = 0;       // "no objects supplied" = any object (:826)
+        if (int rc = check_dims(h, nx, ny, nz)) return rc;
+        HIP_TRY(h, hipSetDevice(h->device));
+        const int64_t n = nx * ny * nz;
+        if (!cells) {                                  // the records of the previous call on this handle, still on the device
+            if (h->tag_cached_bytes == 0 || h->tag_cached_bytes != (size_t)n * cell_stride)
+                return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cells is null and the handle holds no cell records of this size");
+        } else {
+            h->tag_cached_bytes = 0;
+            if (int rc = ensure(h, h->stage_in, (size_t)n * cell_stride, "input staging")) return rc;
+        }
+        if (int rc = ensure(h, h->stage_out, (size_t)n * 4, "output staging")) return rc;
+        if (int rc = ensure(h, h->tagmask, (size_t)n, "tagged-object mask")) return rc;
+        if (int rc = ensure(h, h->tagids, (size_t)std::max<int64_t>(n_object_ids, 1) * 4, "object id list")) return rc;
+        if (cells) {
+            if (int rc0 = copy_from_host(h, h->stage_in.ptr, cells, (size_t)n * cell_stride)) return rc0;
+            h->tag_cached_bytes = (size_t)n * cell_stride;
+        }
+        if (n_object_ids > 0) {                        // sorted copy: the classify kernel binary-searches it
+            std::vector<uint32_t> sorted_ids(object_ids, object_ids + n_object_ids);
+            std::sort(sorted_ids.begin(), sorted_ids.end());
+            HIP_TRY(h, hipMemcpy(h->tagids.ptr, sorted_ids.data(), (size_t)n_object_ids * 4, hipMemcpyHostToDevice));
+        }
+        hipLaunchKernelGGL(k_classify_tagged, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, nullptr,
+                           (const char*)h->stage_in.ptr, (int64_t)cell_stride, (int64_t)occupancy_offset, (int64_t)object_id_offset,
+                           unknown_is_filled, object_mode, (const uint32_t*)h->tagids.ptr, (int)n_object_ids, n,
+                           (uint8_t*)h->tagmask.ptr);
+        HIP_TRY(h, hipGetLastError());
+        int rc = build_device_impl(h, (const uint8_t*)h->tagmask.ptr, nullptr, 0, 0, 0, nx, ny, nz, resolution, add_virtual_border,
+                                   (float*)h->stage_out.ptr, nullptr);
+        if (rc) return rc;
+        if (int rc2 = copy_to_host(h, out_sdf, h->stage_out.ptr, (size_t)n * 4)) return rc2;
+        double mx, mn;
+        rc = sdfgpu_get_extrema(h, &mx, &mn);
+        if (rc) return rc;
+        if (out_max) *out_max = mx;
+        if (out_min) *out_min = mn;
+        return SDFGPU_OK;
+    });
 }
 
-static int sdfgpu_classify_cells_device_body(sdfgpu_handle h, const void* d_cells, size_t cell_stride, size_t occupancy_offset,
-                                 int unknown_is_filled, int64_t n_cells, uint8_t* d_mask, void* stream) {
-    if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-    if (!d_cells || !d_mask || n_cells < 0) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "bad classify arguments");
-    if (cell_stride < 4 || (cell_stride % 4) || (occupancy_offset % 4) || occupancy_offset + 4 > cell_stride)
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cell_stride/occupancy_offset must be 4-byte aligned and in range");
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (n_cells == 0) return SDFGPU_OK;
-    CellLoader ld{reinterpret_cast<const char*>(d_cells), (int64_t)cell_stride, (int64_t)occupancy_offset, unknown_is_filled};
-    hipLaunchKernelGGL(k_classify_cells, dim3((unsigned)((n_cells + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream,
-                       ld, n_cells, d_mask);
-    HIP_TRY(h, hipGetLastError());
-    return SDFGPU_OK;
-}
 int sdfgpu_classify_cells_device(sdfgpu_handle h, const void* d_cells, size_t cell_stride, size_t occupancy_offset,
                                  int unknown_is_filled, int64_t n_cells, uint8_t* d_mask, void* stream) {
-    return rz_wrap(h, stream, [&]() -> int { return sdfgpu_classify_cells_device_body(h, d_cells, cell_stride, occupancy_offset, unknown_is_filled, n_cells, d_mask, stream); });
+    return rz_wrap(h, stream, [&]() -> int {
+        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
+        if (!d_cells || !d_mask || n_cells < 0) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "bad classify arguments");
+        if (cell_stride < 4 || (cell_stride % 4) || (occupancy_offset % 4) || occupancy_offset + 4 > cell_stride)
+            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cell_stride/occupancy_offset must be 4-byte aligned and in range");
+        HIP_TRY(h, hipSetDevice(h->device));
+        if (n_cells == 0) return SDFGPU_OK;
+        CellLoader ld{reinterpret_cast<const char*>(d_cells), (int64_t)cell_stride, (int64_t)occupancy_offset, unknown_is_filled};
+        hipLaunchKernelGGL(k_classify_cells, dim3((unsigned)((n_cells + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream,
+                           ld, n_cells, d_mask);
+        HIP_TRY(h, hipGetLastError());
+        return SDFGPU_OK;
+    });
 }
 
-static int sdfgpu_voxelize_points_device_body(sdfgpu_handle h, const float* d_points, int64_t n_points, const double* origin,
-                                  double resolution, int64_t nx, int64_t ny, int64_t nz, uint8_t* d_mask, int clear_first,
-                                  void* stream) {
-    if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-    if (!d_mask || !origin || (n_points > 0 && !d_points) || n_points < 0 || !(resolution > 0.0))
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "bad voxelize arguments");
-    if (int rc = check_dims(h, nx, ny, nz)) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    if (clear_first) HIP_TRY(h, hipMemsetAsync(d_mask, 0, (size_t)(nx * ny * nz), s));
-    if (n_points > 0) {
-        hipLaunchKernelGGL(k_voxelize_points, dim3((unsigned)((n_points + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, d_points,
-                           n_points, origin[0], origin[1], origin[2], resolution, nx, ny, nz, d_mask);
-        HIP_TRY(h, hipGetLastError());
-    }
-    return SDFGPU_OK;
-}
 int sdfgpu_voxelize_points_device(sdfgpu_handle h, const float* d_points, int64_t n_points, const double* origin,
                                   double resolution, int64_t nx, int64_t ny, int64_t nz, uint8_t* d_mask, int clear_first,
                                   void* stream) {
-    return rz_wrap(h, stream, [&]() -> int { return sdfgpu_voxelize_points_device_body(h, d_points, n_points, origin, resolution, nx, ny, nz, d_mask, clear_first, stream); });
+    return rz_wrap(h, stream, [&]() -> int {
+        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
+        if (!d_mask || !origin || (n_points > 0 && !d_points) || n_points < 0 || !(resolution > 0.0))
+            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "bad voxelize arguments");
+        if (int rc = check_dims(h, nx, ny, nz)) return rc;
+        HIP_TRY(h, hipSetDevice(h->device));
+        hipStream_t s = (hipStream_t)stream;
+        if (clear_first) HIP_TRY(h, hipMemsetAsync(d_mask, 0, (size_t)(nx * ny * nz), s));
+        if (n_points > 0) {
+            hipLaunchKernelGGL(k_voxelize_points, dim3((unsigned)((n_points + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, d_points,
+                               n_points, origin[0], origin[1], origin[2], resolution, nx, ny, nz, d_mask);
+            HIP_TRY(h, hipGetLastError());
+        }
+        return SDFGPU_OK;
+    });
 }
 
-static int sdfgpu_voxelize_points_bits_device_body(sdfgpu_handle h, const float* d_points, int64_t n_points, const double* origin,
-                                       double resolution, int64_t nx, int64_t ny, int64_t nz, uint32_t* d_bits, int clear_first,
-                                       void* stream) {
-    if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-    if (!d_bits || !origin || (n_points > 0 && !d_points) || n_points < 0 || !(resolution > 0.0))
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "bad voxelize arguments");
-    if (int rc = check_dims(h, nx, ny, nz)) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    if (clear_first) HIP_TRY(h, hipMemsetAsync(d_bits, 0, (((size_t)(nx * ny * nz) + 31) / 32) * 4, s));
-    if (n_points > 0) {
-        hipLaunchKernelGGL(k_voxelize_points_bits, dim3((unsigned)((n_points + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, d_points,
-                           n_points, origin[0], origin[1], origin[2], resolution, nx, ny, nz, d_bits);
-        HIP_TRY(h, hipGetLastError());
-    }
-    return SDFGPU_OK;
-}
 int sdfgpu_voxelize_points_bits_device(sdfgpu_handle h, const float* d_points, int64_t n_points, const double* origin,
                                        double resolution, int64_t nx, int64_t ny, int64_t nz, uint32_t* d_bits, int clear_first,
                                        void* stream) {
-    return rz_wrap(h, stream, [&]() -> int { return sdfgpu_voxelize_points_bits_device_body(h, d_points, n_points, origin, resolution, nx, ny, nz, d_bits, clear_first, stream); });
+    return rz_wrap(h, stream, [&]() -> int {
+        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
+        if (!d_bits || !origin || (n_points > 0 && !d_points) || n_points < 0 || !(resolution > 0.0))
+            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "bad voxelize arguments");
+        if (int rc = check_dims(h, nx, ny, nz)) return rc;
+        HIP_TRY(h, hipSetDevice(h->device));
+        hipStream_t s = (hipStream_t)stream;
+        if (clear_first) HIP_TRY(h, hipMemsetAsync(d_bits, 0, (((size_t)(nx * ny * nz) + 31) / 32) * 4, s));
+        if (n_points > 0) {
+            hipLaunchKernelGGL(k_voxelize_points_bits, dim3((unsigned)((n_points + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, d_points,
+                               n_points, origin[0], origin[1], origin[2], resolution, nx, ny, nz, d_bits);
+            HIP_TRY(h, hipGetLastError());
+        }
+        return SDFGPU_OK;
+    });
 }
 
-static int sdfgpu_gradient_device_body(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t ny, int64_t nz,
-                           double resolution, int enable_edge_gradients, void* d_out_grad, int out_is_f64,
-                           void* stream) {
-    if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-    if (!d_sdf || !d_out_grad) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null device pointer");
-    if (int rc = check_dims(h, nx, ny, nz)) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    const int64_t n = nx * ny * nz;
-    dim3 grid((unsigned)((n + kBlock - 1) / kBlock)), block(kBlock);
-    hipStream_t s = (hipStream_t)stream;
-    // the reference's reciprocals, computed once with its own double operations (sdf.hpp:447 and :464-512)
-    GradScale sc{};
-    sc.inv2 = 1.0 / (2.0 * resolution);
-    sc.inv_w1 = 1.0 / ((double)1 * resolution);
-    sc.inv_w2 = 1.0 / ((double)2 * resolution);
-    sc.inv2f = (float)sc.inv2;
-    if (out_is_f64)
-        hipLaunchKernelGGL(k_gradient<double>, grid, block, 0, s, d_sdf, (double*)d_out_grad, nx, ny, nz, sc, enable_edge_gradients);
-    else if ((nz % 4) == 0 && ny * (nz / 4) < ((int64_t)1 << 31) - kBlock &&
-             (reinterpret_cast<uintptr_t>(d_sdf) % 16) == 0 && (reinterpret_cast<uintptr_t>(d_out_grad) % 16) == 0) {
-        const bool f32scale = (double)sc.inv2f == sc.inv2 && std::isfinite(sc.inv2) && std::fabs(sc.inv2) < 1e30 && std::fabs(sc.inv2) > 1e-30;
-        const int64_t per_plane = ny * (nz / 4);                                  // groups of 4 voxels per x plane
-        const dim3 g4((unsigned)((per_plane + kBlock - 1) / kBlock), (unsigned)std::min<int64_t>(nx, 65535));
-        int gshift = -1;                                                           // log2(nz / 4) when that is a power of two
-        for (int b = 0; b < 31; ++b) if (((int64_t)1 << b) == nz / 4) gshift = b;
-        if (f32scale) hipLaunchKernelGGL(k_gradient_f32x4<true>, g4, block, 0, s, d_sdf, (float*)d_out_grad, nx, ny, nz, sc, enable_edge_gradients, gshift);
-        else hipLaunchKernelGGL(k_gradient_f32x4<false>, g4, block, 0, s, d_sdf, (float*)d_out_grad, nx, ny, nz, sc, enable_edge_gradients, gshift);
-    } else
-        hipLaunchKernelGGL(k_gradient<float>, grid, block, 0, s, d_sdf, (float*)d_out_grad, nx, ny, nz, sc, enable_edge_gradients);
-    HIP_TRY(h, hipGetLastError());
-    return SDFGPU_OK;
-}
 int sdfgpu_gradient_device(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t ny, int64_t nz,
                            double resolution, int enable_edge_gradients, void* d_out_grad, int out_is_f64,
                            void* stream) {
-    return rz_wrap(h, stream, [&]() -> int { return sdfgpu_gradient_device_body(h, d_sdf, nx, ny, nz, resolution, enable_edge_gradients, d_out_grad, out_is_f64, stream); });
+    return rz_wrap(h, stream, [&]() -> int {
+        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
+        if (!d_sdf || !d_out_grad) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null device pointer");
+        if (int rc = check_dims(h, nx, ny, nz)) return rc;
+        HIP_TRY(h, hipSetDevice(h->device));
+        const int64_t n = nx * ny * nz;
+        dim3 grid((unsigned)((n + kBlock - 1) / kBlock)), block(kBlock);
+        hipStream_t s = (hipStream_t)stream;
+        // the reference's reciprocals, computed once with its own double operations (sdf.hpp:447 and :464-512)
+        GradScale sc{};
+        sc.inv2 = 1.0 / (2.0 * resolution);
+        sc.inv_w1 = 1.0 / ((double)1 * resolution);
+        sc.inv_w2 = 1.0 / ((double)2 * resolution);
+        sc.inv2f = (float)sc.inv2;
+        if (out_is_f64)
+            hipLaunchKernelGGL(k_gradient<double>, grid, block, 0, s, d_sdf, (double*)d_out_grad, nx, ny, nz, sc, enable_edge_gradients);
+        else if ((nz % 4) == 0 && ny * (nz / 4) < ((int64_t)1 << 31) - kBlock &&
+                 (reinterpret_cast<uintptr_t>(d_sdf) % 16) == 0 && (reinterpret_cast<uintptr_t>(d_out_grad) % 16) == 0) {
+            const bool f32scale = (double)sc.inv2f == sc.inv2 && std::isfinite(sc.inv2) && std::fabs(sc.inv2) < 1e30 && std::fabs(sc.inv2) > 1e-30;
+            const int64_t per_plane = ny * (nz / 4);                                  // groups of 4 voxels per x plane
+            const dim3 g4((unsigned)((per_plane + kBlock - 1) / kBlock), (unsigned)std::min<int64_t>(nx, 65535));
+            int gshift = -1;                                                           // log2(nz / 4) when that is a power of two
+            for (int b = 0; b < 31; ++b) if (((int64_t)1 << b) == nz / 4) gshift = b;
+            if (f32scale) hipLaunchKernelGGL(k_gradient_f32x4<true>, g4, block, 0, s, d_sdf, (float*)d_out_grad, nx, ny, nz, sc, enable_edge_gradients, gshift);
+            else hipLaunchKernelGGL(k_gradient_f32x4<false>, g4, block, 0, s, d_sdf, (float*)d_out_grad, nx, ny, nz, sc, enable_edge_gradients, gshift);
+        } else
+            hipLaunchKernelGGL(k_gradient<float>, grid, block, 0, s, d_sdf, (float*)d_out_grad, nx, ny, nz, sc, enable_edge_gradients);
+        HIP_TRY(h, hipGetLastError());
+        return SDFGPU_OK;
+    });
 }
 
 // Host-buffer form of the full-grid gradient (what SignedDistanceField::GetFullGradient / pysdf_tools'
 // GetFullGradientNumpy call instead of N host GetGradient calls): upload the field, one kernel, download.
-static int sdfgpu_gradient_body(sdfgpu_handle h, const float* sdf, int64_t nx, int64_t ny, int64_t nz, double resolution,
-                    int enable_edge_gradients, void* out_grad, int out_is_f64) {
-    if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-    if (!sdf || !out_grad) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null host pointer");
-    if (int rc = check_dims(h, nx, ny, nz)) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    const size_t n = (size_t)(nx * ny * nz), esz = out_is_f64 ? 8 : 4;
-    // the x axis is cut into chunks (+1 plane of context each side) so that the staging stays <= ~1.5 GiB even
-    // for the 24 B/voxel double output of a 512^3 field
-    const int64_t plane = ny * nz;
-    const int64_t max_rows = std::max<int64_t>(1, ((int64_t)1 << 26) / std::max<int64_t>(plane, 1));   // <= 64 Mi voxels per chunk
-    const int64_t rows = std::min<int64_t>(nx, max_rows);
-    h->tag_cached_bytes = 0;
-    if (int rc = ensure(h, h->stage_in, (size_t)(rows + 2) * plane * 4, "input staging")) return rc;
-    if (int rc = ensure(h, h->stage_out, (size_t)(rows + 2) * plane * 3 * esz, "output staging")) return rc;
-    (void)n;
-    for (int64_t x0 = 0; x0 < nx; x0 += rows) {
-        const int64_t x1 = std::min(nx, x0 + rows);
-        const int64_t lo = std::max<int64_t>(0, x0 - 1), hi = std::min(nx, x1 + 1);     // context planes
-        if (int rc0 = copy_from_host(h, h->stage_in.ptr, sdf + lo * plane, (size_t)(hi - lo) * plane * 4)) return rc0;
-        // the kernel treats the chunk as a grid of its own: its first / last plane would take the one-sided boundary
-        // formula, so those planes are computed only when they ARE grid faces and are otherwise context that is skipped
-        if (int rc = sdfgpu_gradient_device(h, (const float*)h->stage_in.ptr, hi - lo, ny, nz, resolution, enable_edge_gradients,
-                                            h->stage_out.ptr, out_is_f64, nullptr)) return rc;
-        if (int rc = copy_to_host(h, (char*)out_grad + (size_t)x0 * plane * 3 * esz,
-                                  (const char*)h->stage_out.ptr + (size_t)(x0 - lo) * plane * 3 * esz,
-                                  (size_t)(x1 - x0) * plane * 3 * esz)) return rc;
-    }
-    return SDFGPU_OK;
-}
 int sdfgpu_gradient(sdfgpu_handle h, const float* sdf, int64_t nx, int64_t ny, int64_t nz, double resolution,
                     int enable_edge_gradients, void* out_grad, int out_is_f64) {
-    return rz_wrap(h, nullptr, [&]() -> int { return sdfgpu_gradient_body(h, sdf, nx, ny, nz, resolution, enable_edge_gradients, out_grad, out_is_f64); });
+    return rz_wrap(h, nullptr, [&]() -> int {
+        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
+        if (!sdf || !out_grad) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null host pointer");
+        if (int rc = check_dims(h, nx, ny, nz)) return rc;
+        HIP_TRY(h, hipSetDevice(h->device));
+        const size_t n = (size_t)(nx * ny * nz), esz = out_is_f64 ? 8 : 4;
+        // the x axis is cut into chunks (+1 plane of context each side) so that the staging stays <= ~1.5 GiB even
+        // for the 24 B/voxel double output of a 512^3 field
+        const int64_t plane = ny * nz;
+        const int64_t max_rows = std::max<int64_t>(1, ((int64_t)1 << 26) / std::max<int64_t>(plane, 1));   // <= 64 Mi voxels per chunk
+        const int64_t rows = std::min<int64_t>(nx, max_rows);
+        h->tag_cached_bytes = 0;
+        if (int rc = ensure(h, h->stage_in, (size_t)(rows + 2) * plane * 4, "input staging")) return rc;
+        if (int rc = ensure(h, h->stage_out, (size_t)(rows + 2) * plane * 3 * esz, "output staging")) return rc;
+        (void)n;
+        for (int64_t x0 = 0; x0 < nx; x0 += rows) {
+            const int64_t x1 = std::min(nx, x0 + rows);
+            const int64_t lo = std::max<int64_t>(0, x0 - 1), hi = std::min(nx, x1 + 1);     // context planes
+            if (int rc0 = copy_from_host(h, h->stage_in.ptr, sdf + lo * plane, (size_t)(hi - lo) * plane * 4)) return rc0;
+            // the kernel treats the chunk as a grid of its own: its first / last plane would take the one-sided boundary
+            // formula, so those planes are computed only when they ARE grid faces and are otherwise context that is skipped
+            if (int rc = sdfgpu_gradient_device(h, (const float*)h->stage_in.ptr, hi - lo, ny, nz, resolution, enable_edge_gradients,
+                                                h->stage_out.ptr, out_is_f64, nullptr)) return rc;
+            if (int rc = copy_to_host(h, (char*)out_grad + (size_t)x0 * plane * 3 * esz,
+                                      (const char*)h->stage_out.ptr + (size_t)(x0 - lo) * plane * 3 * esz,
+                                      (size_t)(x1 - x0) * plane * 3 * esz)) return rc;
+        }
+        return SDFGPU_OK;
+    });
 }
 
-static int sdfgpu_query_points_device_body(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t ny, int64_t nz, double resolution,
-                               const double* world_to_grid, const double* grid_to_world_rotation, float oob_value,
-                               const double* d_points, int64_t n_points, int enable_edge_gradients, double* d_distance,
-                               double* d_gradient, uint8_t* d_flags, void* stream) {
-    if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-    if (!d_sdf || (n_points > 0 && !d_points)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null device pointer");
-    if (n_points < 0 || !(resolution > 0.0)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "bad point count or resolution");
-    if (int rc = check_dims(h, nx, ny, nz)) return rc;
-    if (n_points == 0 || (!d_distance && !d_gradient && !d_flags)) return SDFGPU_OK;
-    HIP_TRY(h, hipSetDevice(h->device));
-    QueryArgs a{};
-    a.sdf = d_sdf; a.points = d_points; a.distance = d_distance; a.gradient = d_gradient; a.flags = d_flags;
-    a.n = n_points; a.nx = nx; a.ny = ny; a.nz = nz;
-    a.res = resolution; a.inv_res = 1.0 / resolution; a.oob = (double)oob_value;
-    static const double ident34[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-    static const double ident33[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    for (int i = 0; i < 12; ++i) a.w2g[i] = world_to_grid ? world_to_grid[i] : ident34[i];
-    for (int i = 0; i < 9; ++i) a.rot[i] = grid_to_world_rotation ? grid_to_world_rotation[i] : ident33[i];
-    a.edge = enable_edge_gradients;
-    hipLaunchKernelGGL(k_query_points, dim3((unsigned)((n_points + kBlock - 1) / kBlock)), dim3(kBlock), 0,
-                       (hipStream_t)stream, a);
-    HIP_TRY(h, hipGetLastError());
-    return SDFGPU_OK;
-}
 int sdfgpu_query_points_device(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t ny, int64_t nz, double resolution,
                                const double* world_to_grid, const double* grid_to_world_rotation, float oob_value,
                                const double* d_points, int64_t n_points, int enable_edge_gradients, double* d_distance,
                                double* d_gradient, uint8_t* d_flags, void* stream) {
-    return rz_wrap(h, stream, [&]() -> int { return sdfgpu_query_points_device_body(h, d_sdf, nx, ny, nz, resolution, world_to_grid, grid_to_world_rotation, oob_value, d_points, n_points, enable_edge_gradients, d_distance, d_gradient, d_flags, stream); });
+    return rz_wrap(h, stream, [&]() -> int {
+        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
+        if (!d_sdf || (n_points > 0 && !d_points)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null device pointer");
+        if (n_points < 0 || !(resolution > 0.0)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "bad point count or resolution");
+        if (int rc = check_dims(h, nx, ny, nz)) return rc;
+        if (n_points == 0 || (!d_distance && !d_gradient && !d_flags)) return SDFGPU_OK;
+        HIP_TRY(h, hipSetDevice(h->device));
+        QueryArgs a{};
+        a.sdf = d_sdf; a.points = d_points; a.distance = d_distance; a.gradient = d_gradient; a.flags = d_flags;
+        a.n = n_points; a.nx = nx; a.ny = ny; a.nz = nz;
+        a.res = resolution; a.inv_res = 1.0 / resolution; a.oob = (double)oob_value;
+        static const double ident34[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+        static const double ident33[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+        for (int i = 0; i < 12; ++i) a.w2g[i] = world_to_grid ? world_to_grid[i] : ident34[i];
+        for (int i = 0; i < 9; ++i) a.rot[i] = grid_to_world_rotation ? grid_to_world_rotation[i] : ident33[i];
+        a.edge = enable_edge_gradients;
+        hipLaunchKernelGGL(k_query_points, dim3((unsigned)((n_points + kBlock - 1) / kBlock)), dim3(kBlock), 0,
+                           (hipStream_t)stream, a);
+        HIP_TRY(h, hipGetLastError());
+        return SDFGPU_OK;
+    });
 }
 
 int sdfgpu_device_malloc(sdfgpu_handle h, size_t bytes, void** out_ptr) {
@@ -2395,62 +2315,57 @@ int sdfgpu_device_free(sdfgpu_handle h, void* ptr) {
     return rz_free(h, ptr);
 }
 
-static int sdfgpu_query_points_body(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t ny, int64_t nz, double resolution,
-                        const double* world_to_grid, const double* grid_to_world_rotation, float oob_value,
-                        const double* points, int64_t n_points, int enable_edge_gradients, double* out_distance,
-                        double* out_gradient, uint8_t* out_flags) {
-    if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-    if (!d_sdf || (n_points > 0 && !points)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
-    if (n_points < 0 || !(resolution > 0.0)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "bad point count or resolution");
-    if (int rc = check_dims(h, nx, ny, nz)) return rc;
-    if (n_points == 0 || (!out_distance && !out_gradient && !out_flags)) return SDFGPU_OK;
-    HIP_TRY(h, hipSetDevice(h->device));
-    // staging in the context (grown on demand, re-used by the next call): points | distance | gradient | flags
-    const size_t n = (size_t)n_points;
-    const size_t o_d = n * 24, o_g = o_d + n * 8, o_f = o_g + n * 24, total = o_f + ((n + 255) & ~(size_t)255);
-    if (int rc = ensure(h, h->query_stage, total, "query staging")) return rc;
-    char* base = (char*)h->query_stage.ptr;
-    // Round 5: the null stream of the context's device, ordered behind this handle's last build by its event --
-    // not h->last_stream, which is a handle of the CALLER's (an earlier *_device build's stream may have been destroyed since).
-    // A field produced ELSEWHERE (another handle, a caller's kernel) is ordered by the null stream's implicit synchronisation only
-    // when its stream is a blocking one: producers on hipStreamNonBlocking streams (PyTorch's are) must be synchronised by the caller
-    // before this call -- include/sdfgpu.h says so.
-    hipStream_t s = nullptr;
-    if (h->order_valid && h->order_stream != nullptr) HIP_TRY(h, hipStreamWaitEvent(s, h->build_done_ev, 0));
-    if (int rc = copy_from_host(h, base, points, n * 24, s)) return rc;
-    if (int rc = sdfgpu_query_points_device(h, d_sdf, nx, ny, nz, resolution, world_to_grid, grid_to_world_rotation, oob_value,
-                                            (const double*)base, n_points, enable_edge_gradients,
-                                            out_distance ? (double*)(base + o_d) : nullptr,
-                                            out_gradient ? (double*)(base + o_g) : nullptr,
-                                            out_flags ? (uint8_t*)(base + o_f) : nullptr, s)) return rc;
-    if (out_distance) if (int rc = copy_to_host(h, out_distance, base + o_d, n * 8, s)) return rc;
-    if (out_gradient) if (int rc = copy_to_host(h, out_gradient, base + o_g, n * 24, s)) return rc;
-    if (out_flags) if (int rc = copy_to_host(h, out_flags, base + o_f, n, s)) return rc;
-    return SDFGPU_OK;
-}
 int sdfgpu_query_points(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t ny, int64_t nz, double resolution,
                         const double* world_to_grid, const double* grid_to_world_rotation, float oob_value,
                         const double* points, int64_t n_points, int enable_edge_gradients, double* out_distance,
                         double* out_gradient, uint8_t* out_flags) {
-    return rz_wrap(h, nullptr, [&]() -> int { return sdfgpu_query_points_body(h, d_sdf, nx, ny, nz, resolution, world_to_grid, grid_to_world_rotation, oob_value, points, n_points, enable_edge_gradients, out_distance, out_gradient, out_flags); });
+    return rz_wrap(h, nullptr, [&]() -> int {
+        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
+        if (!d_sdf || (n_points > 0 && !points)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
+        if (n_points < 0 || !(resolution > 0.0)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "bad point count or resolution");
+        if (int rc = check_dims(h, nx, ny, nz)) return rc;
+        if (n_points == 0 || (!out_distance && !out_gradient && !out_flags)) return SDFGPU_OK;
+        HIP_TRY(h, hipSetDevice(h->device));
+        // staging in the context (grown on demand, re-used by the next call): points | distance | gradient | flags
+        const size_t n = (size_t)n_points;
+        const size_t o_d = n * 24, o_g = o_d + n * 8, o_f = o_g + n * 24, total = o_f + ((n + 255) & ~(size_t)255);
+        if (int rc = ensure(h, h->query_stage, total, "query staging")) return rc;
+        char* base = (char*)h->query_stage.ptr;
+        // Round 5: the null stream of the context's device, ordered behind this handle's last build by its event --
+        // not h->last_stream, which is a handle of the CALLER's (an earlier *_device build's stream may have been destroyed since).
+        // A field produced ELSEWHERE (another handle, a caller's kernel) is ordered by the null stream's implicit synchronisation only
+        // when its stream is a blocking one: producers on hipStreamNonBlocking streams (PyTorch's are) must be synchronised by the caller
+        // before this call -- include/sdfgpu.h says so.
+        hipStream_t s = nullptr;
+        if (h->order_valid && h->order_stream != nullptr) HIP_TRY(h, hipStreamWaitEvent(s, h->build_done_ev, 0));
+        if (int rc = copy_from_host(h, base, points, n * 24, s)) return rc;
+        if (int rc = sdfgpu_query_points_device(h, d_sdf, nx, ny, nz, resolution, world_to_grid, grid_to_world_rotation, oob_value,
+                                                (const double*)base, n_points, enable_edge_gradients,
+                                                out_distance ? (double*)(base + o_d) : nullptr,
+                                                out_gradient ? (double*)(base + o_g) : nullptr,
+                                                out_flags ? (uint8_t*)(base + o_f) : nullptr, s)) return rc;
+        if (out_distance) if (int rc = copy_to_host(h, out_distance, base + o_d, n * 8, s)) return rc;
+        if (out_gradient) if (int rc = copy_to_host(h, out_gradient, base + o_g, n * 24, s)) return rc;
+        if (out_flags) if (int rc = copy_to_host(h, out_flags, base + o_f, n, s)) return rc;
+        return SDFGPU_OK;
+    });
 }
 
-static int sdfgpu_debug_finish_table_body(sdfgpu_handle h, float* d_out, int64_t n, double resolution, int fast, uint32_t* out_slow_lanes) {
-    if (!h || !d_out || n <= 0 || n > (1ll << 24)) return SDFGPU_ERR_INVALID_ARGUMENT;
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (int rc = ensure(h, h->tagids, 4, "object id list")) return rc;
-    h->tag_cached_bytes = 0;
-    HIP_TRY(h, hipMemset(h->tagids.ptr, 0, 4));
-    const FinishFast fin = make_finish_fast(resolution, (uint64_t)n, fast != 0);
-    hipLaunchKernelGGL(k_finish_table, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, d_out, n, resolution, fin, (uint32_t*)h->tagids.ptr);
-    HIP_TRY(h, hipGetLastError());
-    uint32_t c = 0;
-    HIP_TRY(h, hipMemcpy(&c, h->tagids.ptr, 4, hipMemcpyDeviceToHost));
-    if (out_slow_lanes) *out_slow_lanes = c;
-    return SDFGPU_OK;
-}
 int sdfgpu_debug_finish_table(sdfgpu_handle h, float* d_out, int64_t n, double resolution, int fast, uint32_t* out_slow_lanes) {
-    return rz_wrap(h, nullptr, [&]() -> int { return sdfgpu_debug_finish_table_body(h, d_out, n, resolution, fast, out_slow_lanes); });
+    return rz_wrap(h, nullptr, [&]() -> int {
+        if (!h || !d_out || n <= 0 || n > (1ll << 24)) return SDFGPU_ERR_INVALID_ARGUMENT;
+        HIP_TRY(h, hipSetDevice(h->device));
+        if (int rc = ensure(h, h->tagids, 4, "object id list")) return rc;
+        h->tag_cached_bytes = 0;
+        HIP_TRY(h, hipMemset(h->tagids.ptr, 0, 4));
+        const FinishFast fin = make_finish_fast(resolution, (uint64_t)n, fast != 0);
+        hipLaunchKernelGGL(k_finish_table, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, d_out, n, resolution, fin, (uint32_t*)h->tagids.ptr);
+        HIP_TRY(h, hipGetLastError());
+        uint32_t c = 0;
+        HIP_TRY(h, hipMemcpy(&c, h->tagids.ptr, 4, hipMemcpyDeviceToHost));
+        if (out_slow_lanes) *out_slow_lanes = c;
+        return SDFGPU_OK;
+    });
 }
 
 int sdfgpu_redzone_check(sdfgpu_handle h, void* stream) {
@@ -2534,19 +2449,6 @@ int sdfgpu_get_stage_times(sdfgpu_handle h, double* out_ms_sum, int64_t* out_bui
     return SDFGPU_OK;
 }
 
-#ifdef SDFGPU_PHASE_CLOCKS
-// profiling builds only: read (and clear) the phase clocks of the far-field kernels, [2][8] shader-clock sums over waves
-extern "C" int sdfgpu_debug_read_clocks(sdfgpu_handle h, unsigned long long* out16) {
-    if (!h || !out16) return SDFGPU_ERR_INVALID_ARGUMENT;
-    for (int i = 0; i < 16; ++i) out16[i] = 0;
-    if (!h->d_clocks) return SDFGPU_OK;
-    HIP_TRY(h, hipDeviceSynchronize());
-    HIP_TRY(h, hipMemcpy(out16, h->d_clocks, 16 * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(h, hipMemset(h->d_clocks, 0, 16 * 8));
-    return SDFGPU_OK;
-}
-#endif
-
 int sdfgpu_set_option(sdfgpu_handle h, const char* name, int value) {
     if (!h || !name) return SDFGPU_ERR_INVALID_ARGUMENT;
     const std::string n(name);
@@ -2563,11 +2465,6 @@ int sdfgpu_set_option(sdfgpu_handle h, const char* name, int value) {
     else if (n == "dense_generic") h->dense_generic_on = value != 0;
     else if (n == "envelope") h->envelope_on = value != 0;
     else if (n == "envelope_dc") h->envelope_dc = value != 0;
-#ifdef SDFGPU_DEBUG_HOOKS
-    else if (n == "dc_debug_stage") h->dc_debug_stage = value;
-    else if (n == "dc_debug") h->dc_debug = value;              // profiling builds only: these skip work, results are then wrong
-    else if (n == "ball_variant") h->ball_variant = value;
-#endif
     else if (n == "i32_handoff") h->i32_handoff = value != 0;
     else if (n == "standby_far") h->standby_far = value != 0;
     else if (n == "host_pack") h->host_pack = (value >= 0 && value <= 2) ? value : 1;
@@ -2669,55 +2566,47 @@ int sdfgpu_set_tuning(sdfgpu_handle h, int rows_per_chunk_y, int rows_per_chunk_
     return SDFGPU_OK;
 }
 
-static int sdfgpu_components_bits_device_body(sdfgpu_handle h, const uint32_t* d_bits, int64_t nx, int64_t ny, int64_t nz,
-                                              uint32_t* d_labels, uint32_t* out_count, void* stream) {
-    if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-    if (!d_bits || !d_labels || !out_count) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
-    if ((reinterpret_cast<uintptr_t>(d_bits) | reinterpret_cast<uintptr_t>(d_labels)) & 3)
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "d_bits and d_labels must be 4-byte aligned");
-    if (int rc = check_components_dims(h, nx, ny, nz)) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    return components_impl(h, d_bits, nx, ny, nz, d_labels, out_count, (hipStream_t)stream);
-}
 int sdfgpu_components_bits_device(sdfgpu_handle h, const uint32_t* d_bits, int64_t nx, int64_t ny, int64_t nz, uint32_t* d_labels,
                                   uint32_t* out_count, void* stream) {
-    return rz_wrap(h, stream, [&]() -> int { return sdfgpu_components_bits_device_body(h, d_bits, nx, ny, nz, d_labels, out_count, stream); });
-}
-
-static int sdfgpu_components_body(sdfgpu_handle h, const uint8_t* filled, int64_t nx, int64_t ny, int64_t nz, uint32_t* out_labels,
-                                  uint32_t* out_count) {
-    if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-    if (!filled || !out_labels || !out_count) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
-    if (int rc = check_components_dims(h, nx, ny, nz)) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (int rc = components_host(h, filled, nullptr, 0, 0, nx, ny, nz, out_count)) return rc;
-    return copy_to_host(h, out_labels, h->stage_out.ptr, (size_t)(nx * ny * nz) * 4);
-}
-int sdfgpu_components(sdfgpu_handle h, const uint8_t* filled, int64_t nx, int64_t ny, int64_t nz, uint32_t* out_labels, uint32_t* out_count) {
-    return rz_wrap(h, nullptr, [&]() -> int { return sdfgpu_components_body(h, filled, nx, ny, nz, out_labels, out_count); });
-}
-
-static int sdfgpu_components_cells_body(sdfgpu_handle h, void* cells, size_t cell_stride, size_t occupancy_offset, size_t component_offset,
-                                        int64_t nx, int64_t ny, int64_t nz, uint32_t* out_count) {
-    if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-    if (!cells || !out_count) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
-    if (cell_stride < 8 || (cell_stride % 4) || (occupancy_offset % 4) || (component_offset % 4) || occupancy_offset + 4 > cell_stride ||
-        component_offset + 4 > cell_stride || occupancy_offset == component_offset)
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cell_stride / occupancy_offset / component_offset must be 4-byte aligned, in range and distinct");
-    if (int rc = check_components_dims(h, nx, ny, nz)) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (int rc = components_host(h, nullptr, cells, cell_stride, occupancy_offset, nx, ny, nz, out_count)) return rc;
-    char* const rec = static_cast<char*>(cells) + component_offset;
-    // the drain team writes each label into its record (download offsets are multiples of 4: whole labels)
-    return staged_download_hip(h, h->stage_out.ptr, (size_t)(nx * ny * nz) * 4, nullptr, [=](const char* src, size_t goff, size_t len) {
-        char* dst = rec + (goff / 4) * cell_stride;
-        for (size_t o = 0; o < len; o += 4, dst += cell_stride) memcpy(dst, src + o, 4);
+    return rz_wrap(h, stream, [&]() -> int {
+        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
+        if (!d_bits || !d_labels || !out_count) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
+        if ((reinterpret_cast<uintptr_t>(d_bits) | reinterpret_cast<uintptr_t>(d_labels)) & 3)
+            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "d_bits and d_labels must be 4-byte aligned");
+        if (int rc = check_components_dims(h, nx, ny, nz)) return rc;
+        HIP_TRY(h, hipSetDevice(h->device));
+        return components_impl(h, d_bits, nx, ny, nz, d_labels, out_count, (hipStream_t)stream);
     });
 }
+
+int sdfgpu_components(sdfgpu_handle h, const uint8_t* filled, int64_t nx, int64_t ny, int64_t nz, uint32_t* out_labels, uint32_t* out_count) {
+    return rz_wrap(h, nullptr, [&]() -> int {
+        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
+        if (!filled || !out_labels || !out_count) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
+        if (int rc = check_components_dims(h, nx, ny, nz)) return rc;
+        HIP_TRY(h, hipSetDevice(h->device));
+        if (int rc = components_host(h, filled, nullptr, 0, 0, nx, ny, nz, out_count)) return rc;
+        return copy_to_host(h, out_labels, h->stage_out.ptr, (size_t)(nx * ny * nz) * 4);
+    });
+}
+
 int sdfgpu_components_cells(sdfgpu_handle h, void* cells, size_t cell_stride, size_t occupancy_offset, size_t component_offset,
                             int64_t nx, int64_t ny, int64_t nz, uint32_t* out_count) {
     return rz_wrap(h, nullptr, [&]() -> int {
-        return sdfgpu_components_cells_body(h, cells, cell_stride, occupancy_offset, component_offset, nx, ny, nz, out_count);
+        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
+        if (!cells || !out_count) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
+        if (cell_stride < 8 || (cell_stride % 4) || (occupancy_offset % 4) || (component_offset % 4) || occupancy_offset + 4 > cell_stride ||
+            component_offset + 4 > cell_stride || occupancy_offset == component_offset)
+            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cell_stride / occupancy_offset / component_offset must be 4-byte aligned, in range and distinct");
+        if (int rc = check_components_dims(h, nx, ny, nz)) return rc;
+        HIP_TRY(h, hipSetDevice(h->device));
+        if (int rc = components_host(h, nullptr, cells, cell_stride, occupancy_offset, nx, ny, nz, out_count)) return rc;
+        char* const rec = static_cast<char*>(cells) + component_offset;
+        // the drain team writes each label into its record (download offsets are multiples of 4: whole labels)
+        return staged_download_hip(h, h->stage_out.ptr, (size_t)(nx * ny * nz) * 4, nullptr, [=](const char* src, size_t goff, size_t len) {
+            char* dst = rec + (goff / 4) * cell_stride;
+            for (size_t o = 0; o < len; o += 4, dst += cell_stride) memcpy(dst, src + o, 4);
+        });
     });
 }
 

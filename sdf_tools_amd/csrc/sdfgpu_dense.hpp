@@ -134,7 +134,6 @@ struct DenseArgs {
     // axes with more than one cell): inside the ball only b = 1 and b = 2 can bind, folded into levels 0 and 3
     int vb;
     int nx_glob;            // x extent of the whole grid (buffer plane 0 = grid plane 0 in this mode)
-    int checked;            // debugging: take the bounds-checked expansion even for interior tiles
     int nt_store;           // write the output with non-temporal stores (it is never re-read here)
     const uint32_t* guard;  // KD3 only: non-null = run iff *guard != 0 (the staged fix-up stage behind KD in the same build)
     uint32_t* und_sample;   // KD3 only: nullptr, or the slot array: every 16th wave adds its undecided voxels to word 2 of a slot -- a 1 / 16
@@ -396,7 +395,7 @@ __global__ __launch_bounds__(BD) void k_ball_dense(const DenseArgs a) {
             }
         }
     };
-    if (!(a.checked & 1) && (x0 + a.tx <= a.out_hi) && (y0 + a.ty <= a.ny)) expand(std::true_type{});
+    if ((x0 + a.tx <= a.out_hi) && (y0 + a.ty <= a.ny)) expand(std::true_type{});
     else expand(std::false_type{});
 
 #pragma unroll

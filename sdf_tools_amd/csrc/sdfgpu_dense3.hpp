@@ -288,7 +288,7 @@ __global__ __launch_bounds__(BD) void k_ball_dense3(const DenseArgs a) {
             }
         }
     };
-    if (!(a.checked & 1) && (x0 + a_tx <= a.out_hi) && (y0 + a_ty <= a.ny)) expand(std::true_type{});
+    if ((x0 + a_tx <= a.out_hi) && (y0 + a_ty <= a.ny)) expand(std::true_type{});
     else expand(std::false_type{});
 
 #pragma unroll

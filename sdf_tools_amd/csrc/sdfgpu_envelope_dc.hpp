@@ -31,8 +31,8 @@
 //     see nearly the same sites (in the first pass exactly the same: a row / plane either holds a filled voxel or not).
 //   * Any line count: tiles that stick out of their line group replicate the last line on load and mask the stores;
 //     shapes without 4-element alignment use scalar loads (template parameter VEC).
-// Measured and not kept (512^3, two-box scene and Bernoulli 1 % .. 0.01 %; tools/ff_check.sh, profiling builds with
-// -DSDFGPU_DEBUG_HOOKS / -DSDFGPU_PHASE_CLOCKS):
+// Measured and not kept (512^3, two-box scene and Bernoulli 1 % .. 0.01 %; profiles/r04_ke_ablation.txt,
+// profiles/r04_tile_pattern_probe.txt, profiles/r06_x_sweep_floor_decomposition.txt):
 //   * 512 lanes per tile inside 64 VGPRs (8 waves per SIMD): +-5 % either way; 8-line tiles (20 KB of LDS, 7 - 8 workgroups
 //     per CU) with 128 or 256 lanes: 12 - 25 % slower; padding the LDS so that only 2 workgroups fit a CU: 1.55x slower --
 //     4 workgroups of 4 waves per CU is a plateau;
@@ -105,10 +105,6 @@ struct EnvDcArgs {
     const uint32_t* i32_flag;
     int h;                    // centre of the key coordinates, ceil(L / 2)
     int64_t group_lines;      // lines per outer unit (tiles that stick out replicate the last line)
-    unsigned long long* clocks;   // SDFGPU_PHASE_CLOCKS builds only: per-phase shader-clock sums over waves ([stage - 2][8])
-    int dbg;                  // SDFGPU_DEBUG_HOOKS builds only (wrong results): bit0 no search, bit1 no fp64 finish, bit2 no stores, bit3 no level-C scans, bit4 no level-B scans (with bit3)
-                              // bit5 the y sweep's stores to one block per tile, bit6 no local-search rounds; two-valued tiles: bit7 path off (results stay right),
-                              // bit8 no distance chains, bit9 no nearest-site scans, bit10 no classification
     int64_t ntiles;           // LOOP form: tiles of the whole launch (a workgroup takes tiles blockIdx.x, + gridDim.x, ...)
     const uint32_t* bits;     // STAGE 2, scalar (VEC = false) form only: the dense tier's bit field ([x][y][nzw] words, bit i of word w =
     int nzw;                  // voxel z = 32 w + i is filled) INSTEAD of the z field: the stand-by behind a trusted dense tier computes
@@ -347,23 +343,6 @@ __device__ __forceinline__ uint32_t umax(uint32_t a, uint32_t b) { return a > b 
 __device__ __forceinline__ int imin(int a, int b) { return a < b ? a : b; }
 __device__ __forceinline__ int imax(int a, int b) { return a > b ? a : b; }
 
-// Profiling builds (-DSDFGPU_PHASE_CLOCKS, never the shipped library): shader-clock time per phase, summed over waves.
-// With -DSDFGPU_TRIP_COUNTS on top, the same eight slots count trips of the scan loops instead: [2 l] = trips issued by the
-// waves (the slowest lane's), [2 l + 1] = trips the lanes needed, summed, for level l = 0 (A), 1 (B), 2 (C).
-#if defined(SDFGPU_PHASE_CLOCKS) && defined(SDFGPU_TRIP_COUNTS)
-#define DC_TRIP ++dbgt
-#define DC_STAMP(k) do { int mx_ = dbgt, sm_ = dbgt; \
-        for (int off_ = 32; off_ >= 1; off_ >>= 1) { mx_ = max(mx_, __shfl_xor(mx_, off_)); sm_ += __shfl_xor(sm_, off_); } \
-        if ((k) >= 1 && (k) <= 3) { clk[2 * ((k) - 1)] += (unsigned long long)mx_; clk[2 * ((k) - 1) + 1] += (unsigned long long)sm_; } \
-        dbgt = 0; (void)tprev; } while (0)
-#elif defined(SDFGPU_PHASE_CLOCKS)
-#define DC_TRIP do {} while (0)
-#define DC_STAMP(k) do { const unsigned long long now_ = __builtin_readcyclecounter(); clk[k] += now_ - tprev; tprev = now_; } while (0)
-#else
-#define DC_TRIP do {} while (0)
-#define DC_STAMP(k) do {} while (0)
-#endif
-
 // Device-side tier selection for one axis (stage 0 = y, 1 = x), one thread.  small = the context's status block:
 // [3] uncertified (dense tier could not decide the scene), [4] / [5] "y / x sweep belongs to the far-field kernel" (also
 // raised by a marching sweep that hits its scan bound), [8 + 2 stage] guard word of the marching sweep, [12] / [13] the
@@ -566,11 +545,6 @@ __global__ __launch_bounds__(NT, WPS) void k_envelope_dc(const EnvDcArgs a) {
     uint32_t* const fl_mx = misc + 64;                          // [16] ... largest entry
     uint32_t* const flist = misc + kDcMisc;                         // [kDcLocalFilled] filled voxels of pass 0: line << 28 | p << 12 | min(S, kDcLocalSat)
     const int t = threadIdx.x;
-#ifdef SDFGPU_PHASE_CLOCKS
-    unsigned long long clk[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tprev = __builtin_readcyclecounter();
-    int dbgt = 0;
-    (void)dbgt;
-#endif
     if (a.ran_flag && blockIdx.x == 0 && t == 0) *a.ran_flag = 1u;
     int mxF = 0, mxQ = 0;
     const uint32_t nblk = LOOP ? (uint32_t)a.ntiles : gridDim.x;          // "virtual" workgroups = tiles
@@ -710,7 +684,6 @@ __global__ __launch_bounds__(NT, WPS) void k_envelope_dc(const EnvDcArgs a) {
             for (int k = 0; k < 8; ++k) best[k] = umin(best[k], umin(mad_i24(qc, nc[k], kk.x), mad_i24(qc1, nc[k], kk.y)));
             kp += step;
             qc += step;
-            DC_TRIP;
         }
     };
 
@@ -738,7 +711,6 @@ __global__ __launch_bounds__(NT, WPS) void k_envelope_dc(const EnvDcArgs a) {
                 for (int k = 0; k < 8; ++k) best[k] = umin(best[k], umin(mad_i24(qc, nc[k], kk.x), mad_i24(qc1, nc[k], kk.y)));
                 kp += step;
                 qc += step;
-                DC_TRIP;
             }
             const uint64_t act = __ballot(q <= qe);             // (wave-uniform from here)
             if (act == 0ull) return;
@@ -839,9 +811,6 @@ __global__ __launch_bounds__(NT, WPS) void k_envelope_dc(const EnvDcArgs a) {
                     // DPP quad (sub = t & 3) and the tile's 16 lines lie in ONE word of the bit row (c0 is a multiple of 16)
                     static_assert(LPR == 4 && NL == 16, "the lanes of a tile row must be one DPP quad");
                     static_assert(NT % 64 == 0, "zrow_scan_quad's quad permutes need whole waves");
-#ifdef SDFGPU_DEBUG_HOOKS
-                    if (__builtin_amdgcn_read_exec() != ~0ull) __builtin_trap();     // (a partial wave would read zeros from its inactive lanes)
-#endif
                     const int prow = (pb + PP * it + r < L) ? pb + PP * it + r : L - 1;
                     const int w0 = (int)(c0 >> 5);
                     const ZRowBits zr = zrow_scan_quad(a.bits + (o * a.ny + prow) * a.nzw, a.nzw, w0, sub);
@@ -969,16 +938,11 @@ __global__ __launch_bounds__(NT, WPS) void k_envelope_dc(const EnvDcArgs a) {
             keys[line * pitch + q] = ((finf + (uint32_t)(qc * qc) + (uint32_t)(h * h)) << B) | ((uint32_t)q & mask);
         }
         __syncthreads();
-        DC_STAMP(0);
         int lo_t = 0x7fffffff, hi_t = -1;
         uint32_t mt_t = 0xFFFFFFFFu;
 #pragma unroll
         for (int w = 0; w < NW; ++w) { lo_t = imin(lo_t, (int)misc[w]); hi_t = imax(hi_t, (int)misc[8 + w]); mt_t = umin(mt_t, misc[16 + w]); }
-#ifdef SDFGPU_DEBUG_HOOKS
-        const bool act = lo_t <= hi_t && !(a.dbg & 1);          // profiling builds: dbg bit 0 = no search (wrong results), bit 1 = no fp64 finish, bit 2 = no stores
-#else
         const bool act = lo_t <= hi_t;                          // the tile holds a site (block-uniform)
-#endif
         // Two-valued tiles.  Every lane classifies the positions of its chunks against its line's smallest non-zero entry mn and
         // largest entry mx: zero site, mn site, mx site -- or something else, and then the tile is searched as usual (the keys
         // are untouched until the verdict; tracking + classification cost a searched tile ~15 %: hence the habit, EnvDcArgs::flat_score).
@@ -995,9 +959,6 @@ __global__ __launch_bounds__(NT, WPS) void k_envelope_dc(const EnvDcArgs a) {
             for (int l = 0; l < NL; ++l) { const uint32_t a1 = fl_mn[l] + 1u, b1 = fl_mx[l]; two = two || (b1 != 0u && a1 != b1); }
             bool other = false;
             int n = 0;
-#ifdef SDFGPU_DEBUG_HOOKS
-            if (a.dbg & 1024) {} else                   // profiling builds: bit 10 = no classification (wrong results)
-#endif
             if (!two) {
                 for (int i0 = 0; i0 < M; i0 += S, ++n) {
                     const int i = i0 + slotT;
@@ -1085,10 +1046,6 @@ __global__ __launch_bounds__(NT, WPS) void k_envelope_dc(const EnvDcArgs a) {
             flat = __syncthreads_and(other ? 0 : 1) != 0;      // (block-uniform; everybody has read its keys)
             if (a.flat_on == 1 && (flat_hash >> 28) == 0u && t == 0)     // this tile's vote (every 16th, and every one of the 64th that try with the gate down)
                 (void)__hip_atomic_fetch_add(reinterpret_cast<int*>(a.flat_score), flat ? -3 : 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            DC_STAMP(1);
-#ifdef SDFGPU_DEBUG_HOOKS
-            if (a.dbg & 128) flat = false;
-#endif
         }
 
         if (flat) {
@@ -1111,9 +1068,6 @@ __global__ __launch_bounds__(NT, WPS) void k_envelope_dc(const EnvDcArgs a) {
             }
             __syncthreads();
             // per line, 16 lanes, each with a run of chunks: exclusive prefix maximum of "last" / suffix minimum of "first" over the chunks
-#ifdef SDFGPU_DEBUG_HOOKS
-            if (a.dbg & 512) {} else                    // profiling builds: bit 9 = no nearest-site scans (wrong results)
-#endif
             if (t < 16 * NL) {
                 const int line2 = t >> 4, j = t & 15;
                 const int CP = (M + 15) >> 4, cb = j * CP, ce = imin(cb + CP, M);
@@ -1147,7 +1101,6 @@ __global__ __launch_bounds__(NT, WPS) void k_envelope_dc(const EnvDcArgs a) {
                 if (two) nearest(cl0, nll, nlr);
             }
             __syncthreads();
-            DC_STAMP(2);
         } else if (act) {
             // ---- level A: positions 64 i ---------------------------------------------------------------------------------------
             // Two forms, chosen per wave (= 64 / S whole lines): (a) one position per lane group over a range clipped by the
@@ -1193,7 +1146,6 @@ __global__ __launch_bounds__(NT, WPS) void k_envelope_dc(const EnvDcArgs a) {
                             best = umin(best, umin(mad_i24(qc, nc1, kk.x), mad_i24(qc + 1, nc1, kk.y)));
                             kp += 2 * G;
                             qc += 2 * G;
-                            DC_TRIP;
                         }
                         atomicMin(&args[(8 * i1) * NL + lineA], best);
                     }
@@ -1214,7 +1166,6 @@ __global__ __launch_bounds__(NT, WPS) void k_envelope_dc(const EnvDcArgs a) {
                 }
             }
             __syncthreads();
-            DC_STAMP(1);
             if (probe) {
                 // the probe's statistic from the coarse positions alone (64 i of every line: an unbiased sample of the voxels)
                 if (slotT < imin(MA, S)) {
@@ -1250,9 +1201,6 @@ __global__ __launch_bounds__(NT, WPS) void k_envelope_dc(const EnvDcArgs a) {
                         nc[k] = ncof(64 * i + 8 * k);
                         best[k] = 0xFFFFFFFFu;
                     }
-#ifdef SDFGPU_DEBUG_HOOKS
-                    if (a.dbg & 16) continue;
-#endif
                     if (coop && __ballot(hi - lo >= 108) != 0ull) {             // (an interval's range without a jump: <= 64 + noise)
                         int q = (lo & ~1) + 2 * u;
                         if (Hs == 1) {                          // (block-uniform)
@@ -1272,7 +1220,6 @@ __global__ __launch_bounds__(NT, WPS) void k_envelope_dc(const EnvDcArgs a) {
                 }
             }
             __syncthreads();
-            DC_STAMP(2);
         }
 
         if (probe) {                            // (a tile without sites: every sampled voxel is at "infinity")
@@ -1301,12 +1248,6 @@ __global__ __launch_bounds__(NT, WPS) void k_envelope_dc(const EnvDcArgs a) {
                     if (two) { ll = (int)keys[(4 * NL + lineT) * MP + ic]; rl = (int)keys[(5 * NL + lineT) * MP + ic]; }
                     // (a chunk-level shortcut -- no site inside, the nearest ones too far to matter: one value for all eight positions,
                     //  decided per wave -- was measured: y sweep +2 ... 3 %; the wall at low y reaches half of the room's chunks)
-#ifdef SDFGPU_DEBUG_HOOKS
-                    if (a.dbg & 256) {                          // profiling builds: bit 8 = no distance chains (wrong results)
-#pragma unroll
-                        for (int k = 0; k < 8; ++k) D[k] = mx >= finf ? kInf32 : (int)mx;
-                    } else
-#endif
                     if (!two) {                                 // (block-uniform) one value per line
                         int dz[8];
 #pragma unroll
@@ -1342,7 +1283,6 @@ __global__ __launch_bounds__(NT, WPS) void k_envelope_dc(const EnvDcArgs a) {
                         D[k] = d >= finf ? kInf32 : (int)d;
                     }
                     }
-                    DC_STAMP(3);
                 } else if (act) {
                     const int ic = imin(i, M - 1);
                     const int a0 = (int)(args[ic * NL + lineT] & mask);
@@ -1354,11 +1294,6 @@ __global__ __launch_bounds__(NT, WPS) void k_envelope_dc(const EnvDcArgs a) {
                         nc[k] = ncof(p0 + k);
                         best[k] = 0xFFFFFFFFu;
                     }
-                    DC_STAMP(4);
-#ifdef SDFGPU_DEBUG_HOOKS
-                    if (a.dbg & 8) {}                           // profiling builds: bit 3 = no level-C scan, bit 4 = no level-B scan (use with bit 3)
-                    else
-#endif
                     if (NL == 16 && __ballot(a8 - a0 >= 34) != 0ull) {          // (a chunk's range without a jump: <= 8 + noise)
                         int q = a0 & ~1;
                         scan8_calm(kl, q, a8, 2, nc, best, std::integral_constant<int, 1>{}, 2);
@@ -1366,7 +1301,6 @@ __global__ __launch_bounds__(NT, WPS) void k_envelope_dc(const EnvDcArgs a) {
                     } else {
                         scan8(kl, a0 & ~1, a8, 2, nc, best);
                     }
-                    DC_STAMP(3);
                     // D = (best >> B) - (h^2 - p'^2), h^2 - p'^2 = p (2 h - p): a running value, + (2 h - 2 p - 1) per position
                     uint32_t hp = __umul24((uint32_t)p0, (uint32_t)(2 * h - p0));
                     const uint32_t c1 = (uint32_t)(2 * h - 2 * p0);
@@ -1402,18 +1336,8 @@ __global__ __launch_bounds__(NT, WPS) void k_envelope_dc(const EnvDcArgs a) {
                     if (out32) {
                         char* op = reinterpret_cast<char*>(a.out_i32 + base);      // (uniform base + 32-bit byte offset)
                         uint32_t bo = ob * 4u, bstep = 4u * ls;
-#ifdef SDFGPU_DEBUG_HOOKS
-                        if (a.dbg & 32) {                       // profiling builds: bit 5 = the tile's stores to ONE contiguous 16 x L block (wrong results)
-                            op = reinterpret_cast<char*>(a.out_i32 + ((((c0 >> 4) * a.nx + o) * (int64_t)L) << 4));
-                            bo = ((uint32_t)lineT + (uint32_t)p0 * 16u) * 4u;
-                            bstep = 64u;
-                        }
-#endif
 #pragma unroll
                         for (int k = 0; k < 8; ++k) {
-#ifdef SDFGPU_DEBUG_HOOKS
-                            if ((a.dbg & 4) && (k || slotT)) { bo += bstep; continue; }
-#endif
                             if (D[k] != 0) *reinterpret_cast<int32_t*>(op + bo) = cls == 1 ? -D[k] : D[k];
                             bo += bstep;
                         }
@@ -1459,12 +1383,7 @@ __global__ __launch_bounds__(NT, WPS) void k_envelope_dc(const EnvDcArgs a) {
                         mx = imax(mx, D[k]);
                         // (round 6 built an fp64-free form of this finish -- sdfgpu_finish.hpp: exact, and 2.4 % SLOWER here: on this chip
                         //  v_fma_f64 issues at the fp32 rate, and the fp32 form with its exactness test is the longer sequence)
-#ifdef SDFGPU_DEBUG_HOOKS
-                        float f = (a.dbg & 2) ? (float)D[k] : (float)(sqrt_exact_pos((double)D[k]) * a.resolution);
-                        if ((a.dbg & 4) && (k || slotT)) { bo += 4u * ls; continue; }
-#else
                         float f = (float)(sqrt_exact_pos((double)D[k]) * a.resolution);                 // (D = 0: not stored)
-#endif
                         f = D[k] >= kInf32 ? __builtin_inff() : f;
                         if (D[k] != 0) *reinterpret_cast<float*>(op + bo) = cls == 1 ? -f : f;
                         bo += 4u * ls;
@@ -1472,7 +1391,6 @@ __global__ __launch_bounds__(NT, WPS) void k_envelope_dc(const EnvDcArgs a) {
                     if (cls == 1) mxQ = imax(mxQ, mx); else mxF = imax(mxF, mx);
                 }
             }
-            DC_STAMP(4);
             // Pass 0 finishes the tile's filled voxels itself when they are few and shallow (thin surfaces): one lane per
             // listed voxel, exact local search along its line.  Deep or numerous filled voxels raise misc[25] and the second
             // pass does the class properly.
@@ -1488,9 +1406,6 @@ __global__ __launch_bounds__(NT, WPS) void k_envelope_dc(const EnvDcArgs a) {
                         // offsets in rounds of 4 (8 loads in flight; D1 <= 1023: at most 8 rounds).  (Round 6 measured rounds of 8 in the y sweep: slower
                         // on every scene -- room y sweep +3 %, two-box +5 %.)  A candidate beyond the bound that
                         // rides along in a round is still a candidate: harmless.
-#ifdef SDFGPU_DEBUG_HOOKS
-                        if (a.dbg & 64) D1 = 1;                 // profiling builds: bit 6 = no local-search rounds (wrong results)
-#endif
                         for (int d0 = 1; (int)__umul24(d0, d0) < D1; d0 += 4) {
                             int v[8];
 #pragma unroll
@@ -1508,9 +1423,7 @@ __global__ __launch_bounds__(NT, WPS) void k_envelope_dc(const EnvDcArgs a) {
                 }
             }
         }
-        DC_STAMP(5);
         __syncthreads();                        // keys / args are rebuilt by the next class; misc[25] is complete
-        DC_STAMP(6);
     };
 
     run_pass(std::integral_constant<int, 0>{});
@@ -1521,16 +1434,6 @@ __global__ __launch_bounds__(NT, WPS) void k_envelope_dc(const EnvDcArgs a) {
     if constexpr (LOOP) __syncthreads();            // (the next tile's first pass clears misc: everybody has read it)
     if (second) run_pass(std::integral_constant<int, 1>{});
 
-#ifdef SDFGPU_PHASE_CLOCKS
-#ifdef SDFGPU_TRIP_COUNTS
-    if (a.clocks && (t & 63) == 0 && !probe) {
-#else
-    if (a.clocks && (t & 63) == 0 && !probe && ((blockIdx.x * 2654435761u) >> 27) == 5u) {     // a sample (hashed: consecutive workgroups are consecutive tiles of a row): same-address atomics serialise
-#endif
-#pragma unroll
-        for (int k = 0; k < 8; ++k) atomicAdd(a.clocks + (STAGE - 2) * 8 + k, clk[k]);
-    }
-#endif
     if (probe) {
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) {

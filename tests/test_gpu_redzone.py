@@ -1,7 +1,7 @@
 """GPU: red zones (round 6, VERDICT r5 "next round" 2).  With option "redzone" (or SDFGPU_REDZONE=1 at sdfgpu_create) every device
 allocation of the library carries canaries and every entry point ends with a check: a store outside a buffer fails the call
-that made it and names the buffer.  The whole `-m gpu` suite and the fuzz are also run with SDFGPU_REDZONE=1 (tools/r06_redzone.sh,
-log under profiles/)."""
+that made it and names the buffer.  The whole `-m gpu` suite and the fuzz are also run with SDFGPU_REDZONE=1 (a script removed
+after commit 4eb6a2c, tools/r06_redzone.sh; its log is profiles/r06_redzone_suite_and_fuzz.txt)."""
 import numpy as np
 import pytest
 

@@ -7,7 +7,8 @@ positions of levels A / B / C, the trips every lane of levels B and C needs, and
   coop     : wave-uniform blocks 4, 8, 16, ... and the hand-over of long ranges to the wave's four rows (round 4; gate, block size,
              calm rule and the cost of a hand-over as in sdfgpu_envelope_dc.hpp),
   sorted   : level C only -- the tile's 64 (chunk x 16 lines) units dealt to the waves in order of their longest range.
-The thresholds of scan8_calm / coop8 were chosen with this; the kernel's trip counters (tools/trip_counts.py on a GPU) read
+The thresholds of scan8_calm / coop8 were chosen with this; the kernel's trip counters (tools/trip_counts.py with a profiling
+build, both removed after commit 4eb6a2c; profiles/r04_trip_counts.jsonl) read
 10.0 / 13.4 / 21.5 issued and 9.6 / 9.6 / 13.1 needed trips per wave for levels A / B / C of the two-box x sweep.
 
 usage: ke_schedule_sim.py <box|room|bernoulli p> <x|y> [tiles = 200]
