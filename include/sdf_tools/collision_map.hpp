@@ -2,9 +2,10 @@
 // sdf_tools::CollisionMapGrid (reference include/sdf_tools/collision_map.hpp) on the SDF path:
 // COLLISION_CELL (:20-32), the constructors (:215-270), SetValue (:405-420) and
 // ExtractSignedDistanceField (:680-712), and the connected components (UpdateConnectedComponents :564-618,
-// ExtractConnectedComponents :757-778, GetNumConnectedComponents hpp :503) computed on the GPU by sdfgpu_components_cells.
-// Topology (hole / void counting), component surfaces, convex segments and RViz export are out of scope (SURVEY.md
-// section 2, rows 2/8).  Wire formats (N3): SerializeSelf / DeserializeSelf, SaveToFile /
+// ExtractConnectedComponents :757-778, GetNumConnectedComponents hpp :503) computed on the GPU by sdfgpu_components_cells,
+// and their topology (ComputeComponentTopology :620-671, holes and voids per component) by sdfgpu_component_topology_cells.
+// Component surfaces (ExtractComponentSurfaces), convex segments and RViz export are out of scope (SURVEY.md section 2,
+// rows 2/8).  Wire formats (N3): SerializeSelf / DeserializeSelf, SaveToFile /
 // LoadFromFile ("CMGZ" / "CMGR") and the CollisionMap message pair in the field order of
 // src/sdf_tools/collision_map.cpp:21-62, :205-283, :285-315.  The byte layout of the primitives
 // (arc_utilities::SerializeFixedSizePOD / SerializeEigen / SerializeVector / SerializeString) is the in-tree
@@ -24,6 +25,7 @@
 #include "arc_utilities/serialization.hpp"
 #include "arc_utilities/voxel_grid.hpp"
 #include "arc_utilities/zlib_helpers.hpp"
+#include "sdf_tools/component_topology.hpp"
 #include "sdf_tools/sdf.hpp"
 #include "sdf_tools/sdf_generation.hpp"
 
@@ -52,6 +54,8 @@ protected:
     bool components_valid_;
 
 public:
+    enum COMPONENT_TYPES : uint8_t { FILLED_COMPONENTS = 0x01, EMPTY_COMPONENTS = 0x02, UNKNOWN_COMPONENTS = 0x04 };
+
     EIGEN_MAKE_ALIGNED_OPERATOR_NEW
     using Base = ::VoxelGrid::VoxelGrid<COLLISION_CELL>;
 
@@ -133,6 +137,26 @@ public:
     }
 
     std::pair<uint32_t, bool> GetNumConnectedComponents() const { return std::make_pair(number_of_components_, components_valid_); }
+
+    // ---- component topology (reference collision_map.cpp:620-671) ------------------------------------------------------------
+    // {component: (holes, voids)} of the filled components (ignore_empty_components) or of every component, computed on the GPU
+    // (include/sdfgpu.h "Component topology": the contract and its two deviations from the reference as written).  Labels are
+    // recomputed first when asked (an early-out when the stored ones are valid); stored labels that are not valid are used as
+    // they are, up to the largest of them.  Refusals throw std::invalid_argument, HIP failures std::runtime_error.
+    std::map<uint32_t, std::pair<int32_t, int32_t>> ComputeComponentTopology(const bool ignore_empty_components,
+                                                                             const bool recompute_connected_components,
+                                                                             const bool verbose) {
+        if (recompute_connected_components) UpdateConnectedComponents();
+        uint32_t max_label = number_of_components_;
+        if (!components_valid_) {
+            max_label = 0;
+            for (const COLLISION_CELL& cell : data_) max_label = cell.component > max_label ? cell.component : max_label;
+        }
+        return ComputeComponentTopologyFromCells(data_.data(), sizeof(COLLISION_CELL), offsetof(COLLISION_CELL, occupancy),
+                                                 offsetof(COLLISION_CELL, component), GetNumXCells(), GetNumYCells(), GetNumZCells(),
+                                                 ignore_empty_components ? FILLED_COMPONENTS : (FILLED_COMPONENTS | EMPTY_COMPONENTS | UNKNOWN_COMPONENTS),
+                                                 max_label, verbose);
+    }
 
     // Indices of each component, in scan order inside each (one counting pass, then one placement pass over the labels).
     std::vector<std::vector<GRID_INDEX>> ExtractConnectedComponents() {

@@ -8,8 +8,9 @@
 // TaggedObjectCollisionMap message pair (:309-339, msg/TaggedObjectCollisionMap.msg) -- byte format of the un-vendored
 // arc_utilities serialisers: "wire-format parity unpinned", like the other two containers.
 // The connected components (UpdateConnectedComponents, tagged_object_collision_map.cpp:340-380, same connectivity rule as
-// CollisionMapGrid's) are computed on the GPU by sdfgpu_components_cells.  Convex segmentation, topology and RViz export are
-// out of scope.  Every SDF is built on the GPU through sdfgpu_build_tagged_cells (device-side predicate).
+// CollisionMapGrid's) are computed on the GPU by sdfgpu_components_cells, and their topology (ComputeComponentTopology,
+// :424-490) by sdfgpu_component_topology_cells.  Convex segmentation, component surfaces and RViz export are out of scope
+// (SURVEY.md section 2, rows 7/8).  Every SDF is built on the GPU through sdfgpu_build_tagged_cells (device-side predicate).
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -25,6 +26,7 @@
 #include "arc_utilities/serialization.hpp"
 #include "arc_utilities/voxel_grid.hpp"
 #include "arc_utilities/zlib_helpers.hpp"
+#include "sdf_tools/component_topology.hpp"
 #include "sdf_tools/sdf.hpp"
 #include "sdf_tools/sdf_generation.hpp"
 
@@ -83,6 +85,8 @@ protected:
     }
 
 public:
+    enum COMPONENT_TYPES : uint8_t { FILLED_COMPONENTS = 0x01, EMPTY_COMPONENTS = 0x02, UNKNOWN_COMPONENTS = 0x04 };
+
     EIGEN_MAKE_ALIGNED_OPERATOR_NEW
     using Base = ::VoxelGrid::VoxelGrid<TAGGED_OBJECT_COLLISION_CELL>;
 
@@ -133,6 +137,26 @@ public:
     }
 
     std::pair<uint32_t, bool> GetNumConnectedComponents() const { return std::make_pair(number_of_components_, components_valid_); }
+
+    // ---- component topology (reference tagged_object_collision_map.cpp:424-490) ---------------------------------------------
+    // {component: (holes, voids)} of the components whose voxels are in component_types_to_use: FILLED (occupancy > 0.5), EMPTY
+    // (< 0.5), UNKNOWN (the rest, NaN included), computed on the GPU (include/sdfgpu.h "Component topology").  Free space is one
+    // class for the components, so a free component holding both empty and unknown voxels under a mask that takes one of them
+    // and not the other is refused (std::invalid_argument).  Labels as in CollisionMapGrid::ComputeComponentTopology.
+    std::map<uint32_t, std::pair<int32_t, int32_t>> ComputeComponentTopology(const COMPONENT_TYPES component_types_to_use,
+                                                                             const bool recompute_connected_components,
+                                                                             const bool verbose) {
+        if (recompute_connected_components) UpdateConnectedComponents();
+        uint32_t max_label = number_of_components_;
+        if (!components_valid_) {
+            max_label = 0;
+            for (const TAGGED_OBJECT_COLLISION_CELL& cell : data_) max_label = cell.component > max_label ? cell.component : max_label;
+        }
+        return ComputeComponentTopologyFromCells(data_.data(), sizeof(TAGGED_OBJECT_COLLISION_CELL),
+                                                 offsetof(TAGGED_OBJECT_COLLISION_CELL, occupancy),
+                                                 offsetof(TAGGED_OBJECT_COLLISION_CELL, component), GetNumXCells(), GetNumYCells(),
+                                                 GetNumZCells(), (int)component_types_to_use, max_label, verbose);
+    }
 
     // ---- wire formats: tagged_object_collision_map.cpp:23-75 (fields), :242-307 (files), :309-339 (messages) ------------
     using CellSerializer = std::function<uint64_t(const TAGGED_OBJECT_COLLISION_CELL&, std::vector<uint8_t>&)>;

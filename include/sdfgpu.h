@@ -392,6 +392,47 @@ int sdfgpu_components(sdfgpu_handle h, const uint8_t* filled, int64_t nx, int64_
 int sdfgpu_components_cells(sdfgpu_handle h, void* cells, size_t cell_stride, size_t occupancy_offset, size_t component_offset,
                             int64_t nx, int64_t ny, int64_t nz, uint32_t* out_count);
 
+/* ---------------------------------------------------------------------------
+ * Component topology: CollisionMapGrid / TaggedObjectCollisionMapGrid::ComputeComponentTopology (reference
+ * src/sdf_tools/collision_map.cpp:620-671, tagged_object_collision_map.cpp:424-490, topology_computation.hpp:297-672) on the GPU.
+ * Indices: voxel (x, y, z) is (x ny + y) nz + z.  Vertex (i, j, k), 0 <= i <= nx, 0 <= j <= ny, 0 <= k <= nz, is the corner of
+ * the eight voxels (i-1..i, j-1..j, k-1..k), its cube.  An out-of-grid voxel is component -1.
+ * Inputs: one uint32 label per voxel (normally sdfgpu_components' output) and optionally a selection, one bit per voxel in the
+ * library's bit-field layout (ignore_empty_components = occupancy > 0.5; the tagged COMPONENT_TYPES mask).
+ *   - (v, c) is a SURFACE VERTEX of c iff v's cube holds a selected voxel s of label c and a face neighbour of s inside the
+ *     cube has another label.  With no selection (or each label wholly selected or wholly unselected) this is: the cube holds
+ *     c and something else.
+ *   - its edge mask has the reference's 6 bits (z-, z+, y-, y+, x-, x+); an edge is exposed iff the 4 voxels around it hold c
+ *     and something else; e = number of exposed edges; M3 / M5 / M6 = surface vertices of c with e = 3 / 5 / 6
+ *   - surfaces_c = connected components of c's surface vertices joined by exposed edges (each ends in a surface vertex of c)
+ *   - per component (int32, C truncation): raw = 1 + (M5 + 2 M6 - M3) / 8, voids = surfaces - 1, holes = raw + voids; the
+ *     map holds exactly the components with at least one surface vertex (with sdfgpu_components labels: every selected one)
+ * out_counts: (max_label + 1) x 5 int64, row c = surface vertices, M3, M5, M6, surfaces of label c (rows of absent labels are 0).
+ * Deviations from the literal reference:
+ *   1. the "+z" face neighbour is read at z + 1 (topology_computation.hpp:383-386 reads z - 1, after which the reference throws
+ *      std::out_of_range on almost every grid: the vertices of an upper-z face never enter the vertex set its search reaches);
+ *   2. out-of-grid voxels are component -1 everywhere (the reference's surface-voxel test alone compares against the OOB cell's
+ *      component, and misses z == nz - 1 as an edge voxel, collision_map.hpp:108); these differ only when the OOB cell carries
+ *      a label in use.
+ * Refused (SDFGPU_ERR_INVALID_ARGUMENT, with a message): a selection under which some label has both selected and unselected
+ * voxels (e.g. stale labels; even the corrected reference can throw there); a label above max_label; max_label = 2^32 - 1;
+ * more than 2^32 - 1 voxels; more than 2^32 - 1 surface-vertex nodes (the union-find's node ids are 32-bit: Bernoulli noise has
+ * about 2.1 - 2.3 nodes per vertex, so noise grids beyond about 1250^3 exceed it; structured scenes have orders of magnitude fewer).
+ * All three are synchronous and, like the components, use scratch of their own (the SDF scratch, status block and policy
+ * are left as they were).  Counts are integers: results are bit-reproducible.
+ *
+ *   sdfgpu_component_topology_device: d_labels (n uint32), d_select_bits (ceil(n / 32) words, NULL = every voxel), 4-byte aligned.
+ *   sdfgpu_component_topology: host labels (n uint32) and host select_mask (n bytes, nonzero = selected; NULL = every voxel).
+ *   sdfgpu_component_topology_cells: labels from each record's uint32 at component_offset, selection from its occupancy float
+ *       by class_mask = FILLED (1, > 0.5) | EMPTY (2, < 0.5) | UNKNOWN (4, the rest, NaN included); 7 = every voxel.
+ * ------------------------------------------------------------------------- */
+int sdfgpu_component_topology_device(sdfgpu_handle h, const uint32_t* d_labels, const uint32_t* d_select_bits, int64_t nx, int64_t ny,
+                                     int64_t nz, uint32_t max_label, int64_t* out_counts, void* stream);
+int sdfgpu_component_topology(sdfgpu_handle h, const uint32_t* labels, const uint8_t* select_mask, int64_t nx, int64_t ny, int64_t nz,
+                              uint32_t max_label, int64_t* out_counts);
+int sdfgpu_component_topology_cells(sdfgpu_handle h, const void* cells, size_t cell_stride, size_t occupancy_offset, size_t component_offset,
+                                    int64_t nx, int64_t ny, int64_t nz, int class_mask, uint32_t max_label, int64_t* out_counts);
+
 /* Red zones (round 6).  With SDFGPU_REDZONE=1 in the environment when sdfgpu_create runs -- or after
  * sdfgpu_set_option(h, "redzone", 1) -- every device allocation of the library (scratch fields, status block, extrema slots,
  * staging buffers, sdfgpu_device_malloc memory) carries 4 KiB of canary bytes in front and behind, and every entry point that

@@ -28,6 +28,7 @@ EXPORTS = [
     "sdfgpu_build_to_device", "sdfgpu_build_cells_to_device", "sdfgpu_upload_classified",
     "sdfgpu_build_bits_device", "sdfgpu_build_bits", "sdfgpu_voxelize_points_bits_device", "sdfgpu_debug_finish_table", "sdfgpu_redzone_check",
     "sdfgpu_components_bits_device", "sdfgpu_components", "sdfgpu_components_cells",
+    "sdfgpu_component_topology_device", "sdfgpu_component_topology", "sdfgpu_component_topology_cells",
 ]
 
 
@@ -110,6 +111,9 @@ def load_library():
     L.sdfgpu_components_bits_device.argtypes = [vp, vp, i64, i64, i64, vp, vp, vp]
     L.sdfgpu_components.argtypes = [vp, vp, i64, i64, i64, vp, vp]
     L.sdfgpu_components_cells.argtypes = [vp, vp, sz, sz, sz, i64, i64, i64, vp]
+    L.sdfgpu_component_topology_device.argtypes = [vp, vp, vp, i64, i64, i64, u32, vp, vp]
+    L.sdfgpu_component_topology.argtypes = [vp, vp, vp, i64, i64, i64, u32, vp]
+    L.sdfgpu_component_topology_cells.argtypes = [vp, vp, sz, sz, sz, i64, i64, i64, ci, u32, vp]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is ctypes.c_int or name not in ("sdfgpu_version", "sdfgpu_last_error"):
@@ -125,6 +129,23 @@ def pack_bits_host(filled):
     b = np.packbits(m, bitorder="little")
     b = np.concatenate([b, np.zeros((-b.size) % 4, np.uint8)])
     return b.view("<u4").astype(np.uint32, copy=False)
+
+
+TOPOLOGY_FILLED, TOPOLOGY_EMPTY, TOPOLOGY_UNKNOWN = 1, 2, 4       # class_mask of SdfGpu.component_topology_cells
+
+
+def topology_holes_voids(counts):
+    """component_topology* counters int64 [L, 5] (surface vertices, M3, M5, M6, surfaces) -> {component: (holes, voids)} for every
+    component with a surface vertex, in the reference's int32 arithmetic: raw = 1 + (M5 + 2 M6 - M3) / 8 with C truncation
+    (math.trunc, not //), voids = surfaces - 1, holes = raw + voids."""
+    out = {}
+    counts = np.asarray(counts)
+    for c in np.nonzero(counts[:, 0])[0]:
+        _, m3, m5, m6, surfaces = (int(v) for v in counts[c])
+        num = m5 + 2 * m6 - m3
+        raw = 1 + (abs(num) // 8) * (1 if num >= 0 else -1)
+        out[int(c)] = (raw + surfaces - 1, surfaces - 1)
+    return out
 
 
 def device_count():
@@ -322,6 +343,48 @@ class SdfGpu:
         self._check(self._lib.sdfgpu_components_cells(self._h, cells.ctypes.data, cell_stride, occupancy_offset, component_offset,
                                                       nx, ny, nz, ctypes.byref(k)))
         return int(k.value)
+
+    # ---- component topology (CollisionMapGrid::ComputeComponentTopology, include/sdfgpu.h) -----------------
+    def component_topology(self, labels, select=None, max_label=None):
+        """labels: uint32 [nx, ny, nz]; select: bool/uint8 [nx, ny, nz] or None (every voxel).  Returns int64 [max_label + 1, 5]:
+        surface vertices, M3, M5, M6, surfaces per label (topology_holes_voids turns it into {c: (holes, voids)}).  max_label
+        defaults to the largest label."""
+        lab = np.ascontiguousarray(labels, dtype=np.uint32)
+        if lab.ndim != 3:
+            raise ValueError("labels must be [nx, ny, nz]")
+        if max_label is None:
+            max_label = int(lab.max()) if lab.size else 0
+        sel = None
+        if select is not None:
+            sel = np.ascontiguousarray(np.asarray(select) != 0, dtype=np.uint8)
+            if sel.shape != lab.shape:
+                raise ValueError("select must have the labels' shape")
+        out = np.zeros((int(max_label) + 1, 5), np.int64)
+        self._check(self._lib.sdfgpu_component_topology(self._h, lab.ctypes.data, None if sel is None else sel.ctypes.data, *lab.shape,
+                                                         int(max_label), out.ctypes.data))
+        return out
+
+    def component_topology_device(self, d_labels, shape, max_label, d_select_bits=None, stream=0):
+        """d_labels: device uint32 [n]; d_select_bits: device bit field (ceil(n / 32) words) or None.  Returns int64
+        [max_label + 1, 5] (synchronises `stream`)."""
+        nx, ny, nz = (int(s) for s in shape)
+        out = np.zeros((int(max_label) + 1, 5), np.int64)
+        self._check(self._lib.sdfgpu_component_topology_device(self._h, d_labels, d_select_bits or None, nx, ny, nz, int(max_label),
+                                                                out.ctypes.data, stream or None))
+        return out
+
+    def component_topology_cells(self, cells, shape, class_mask, max_label, cell_stride=8, occupancy_offset=0, component_offset=4):
+        """cells: contiguous records (COLLISION_CELL: 8, 0, 4; TAGGED_OBJECT_COLLISION_CELL: 16, 0, 4) holding labels;
+        class_mask: TOPOLOGY_FILLED | TOPOLOGY_EMPTY | TOPOLOGY_UNKNOWN (7 = every voxel).  Returns int64 [max_label + 1, 5]."""
+        nx, ny, nz = (int(s) for s in shape)
+        if not (isinstance(cells, np.ndarray) and cells.flags.c_contiguous):
+            raise ValueError("cells must be a C-contiguous numpy array")
+        if cells.nbytes != nx * ny * nz * cell_stride:
+            raise ValueError("cells buffer size does not match shape * cell_stride")
+        out = np.zeros((int(max_label) + 1, 5), np.int64)
+        self._check(self._lib.sdfgpu_component_topology_cells(self._h, cells.ctypes.data, cell_stride, occupancy_offset, component_offset,
+                                                               nx, ny, nz, int(class_mask), int(max_label), out.ctypes.data))
+        return out
 
     def voxelize_points_bits_device(self, d_points, n_points, origin, resolution, shape, d_bits, clear_first=True, stream=0):
         nx, ny, nz = (int(s) for s in shape)

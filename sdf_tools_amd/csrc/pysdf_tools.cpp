@@ -247,6 +247,9 @@ PYBIND11_MODULE(pysdf_tools, m) {
         // GRID_INDEX lists per component is not a usable Python value at 512^3 -- GetComponentsNumpy is the bulk accessor
         .def("UpdateConnectedComponents", &CollisionMapGrid::UpdateConnectedComponents, py::call_guard<py::gil_scoped_release>())
         .def("GetNumConnectedComponents", &CollisionMapGrid::GetNumConnectedComponents)
+        .def("ComputeComponentTopology", &CollisionMapGrid::ComputeComponentTopology, py::arg("ignore_empty_components") = true,
+             py::arg("recompute_connected_components") = true, py::arg("verbose") = false, py::call_guard<py::gil_scoped_release>(),
+             "{component: (holes, voids)} on the GPU (collision_map.cpp:620-671; include/sdfgpu.h \"Component topology\")")
         .def("GetComponentsNumpy", [](const CollisionMapGrid& g) {
             py::array_t<uint32_t> out({(py::ssize_t)g.GetNumXCells(), (py::ssize_t)g.GetNumYCells(), (py::ssize_t)g.GetNumZCells()});
             uint32_t* o = out.mutable_data();

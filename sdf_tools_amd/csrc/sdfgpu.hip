@@ -12,6 +12,7 @@
 #include "sdfgpu_policy.hpp"
 #include "sdfgpu_hostteam.hpp"
 #include "sdfgpu_components.hpp"
+#include "sdfgpu_topology.hpp"
 
 #include <sys/mman.h>
 #if defined(__SSE2__)
@@ -68,6 +69,8 @@ struct sdfgpu_context {
     DeviceBuffer stage_out;  // host-API staging: sdf
     DeviceBuffer query_stage;   // host-API staging of sdfgpu_query_points: points | distance | gradient | flags
     DeviceBuffer cc_scratch;    // sdfgpu_components*: root flags, ranks, chunk counts, K (sdfgpu_components.hpp)
+    DeviceBuffer tp_scratch;    // sdfgpu_component_topology*: counters, status, node bytes, node offsets (sdfgpu_topology.hpp)
+    DeviceBuffer tp_nodes;      // sdfgpu_component_topology*: one union-find word per surface-vertex node
     size_t tag_cached_bytes = 0;            // stage_in holds the tagged cell records of the last sdfgpu_build_tagged_cells call
     void* pin[2] = {nullptr, nullptr};      // pinned host staging of copy_to_host (two chunks in flight)
     // Red zones (round 6, VERDICT r5 "next round" 2): with SDFGPU_REDZONE=1 in the environment of sdfgpu_create (or option
@@ -1648,6 +1651,92 @@ int components_host(sdfgpu_handle h, const uint8_t* filled, const void* cells, s
     return components_impl(h, (const uint32_t*)h->stage_bits.ptr, nx, ny, nz, (uint32_t*)h->stage_out.ptr, out_count, nullptr);
 }
 
+// ---- component topology (sdfgpu_topology.hpp) ----------------------------------------------------------------------------------
+// Like the components: only tp_scratch and tp_nodes (and, in the host forms, the label / bit staging and the pinned chunks) are
+// used; the SDF builds' scratch, status block and policy are not touched.
+int check_topology_args(sdfgpu_handle h, int64_t nx, int64_t ny, int64_t nz, uint32_t max_label, const int64_t* out_counts) {
+    if (!out_counts) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
+    if (int rc = check_components_dims(h, nx, ny, nz)) return rc;
+    if (max_label == 0xFFFFFFFFu) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "max_label must be below 2^32 - 1");
+    return SDFGPU_OK;
+}
+
+// labels (device) + selection bits (device or null) -> (max_label + 1) x 5 counters (host); synchronises `st`
+int topology_impl(sdfgpu_handle h, const uint32_t* d_labels, const uint32_t* d_select, int64_t nx, int64_t ny, int64_t nz, uint32_t max_label,
+                  int64_t* out_counts, hipStream_t st) {
+    const TpPlan plan = tp_plan(nx, ny, nz, max_label, d_select != nullptr);
+    if (int rc = ensure(h, h->tp_scratch, plan.scratch_bytes, "topology scratch")) return rc;
+    HIP_TRY(h, tp_launch_count(plan, d_labels, d_select, h->tp_scratch.ptr, st));
+    TpStatus status;
+    HIP_TRY(h, hipMemcpyAsync(&status, static_cast<char*>(h->tp_scratch.ptr) + plan.off_status, sizeof status, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    if (status.err & kTpErrLabel)
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "label %u exceeds max_label %u", status.label_over, max_label);
+    if (status.err & kTpErrMixed)
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT,
+                    "label %u has both selected and unselected voxels: its surface is undefined under this selection "
+                    "(labels must come from the connected components of the same occupancy)", status.label_mixed);
+    if (status.nodes > 0xFFFFFFFFull)
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT,
+                    "%llu surface-vertex nodes: more than the 2^32 - 1 that the union-find's 32-bit node ids can number",
+                    (unsigned long long)status.nodes);
+    if (int rc = ensure(h, h->tp_nodes, (size_t)std::max<uint64_t>(status.nodes, 1) * 4, "topology nodes")) return rc;
+    HIP_TRY(h, tp_launch_surfaces(plan, d_labels, h->tp_scratch.ptr, (uint32_t*)h->tp_nodes.ptr, status.nodes, st));
+    // (uint64 counters, read as int64: every count is below 2^32)
+    return copy_to_host(h, out_counts, h->tp_scratch.ptr, ((size_t)max_label + 1) * kTpCounters * 8, st);
+}
+
+// Bit (v & 7) of byte (v >> 3) = voxel v's occupancy class is in class_mask: FILLED (1) occupancy > 0.5f, EMPTY (2) < 0.5f,
+// UNKNOWN (4) the rest (0.5 and NaN), as the reference's tagged is_surface_index_fn branches (tagged_object_collision_map.cpp:448-481).
+void pack_cells_class_bits(const char* cells, size_t stride, size_t off, int class_mask, int64_t n, size_t ob, size_t len, uint8_t* out) {
+    int64_t v = (int64_t)ob * 8;
+    for (size_t o = 0; o < len; ++o) {
+        uint32_t b = 0;
+        for (int k = 0; k < 8; ++k, ++v) {
+            if (v >= n) continue;
+            float occ;
+            memcpy(&occ, cells + (size_t)v * stride + off, 4);
+            const int cls = occ > 0.5f ? 1 : occ < 0.5f ? 2 : 4;
+            if (cls & class_mask) b |= 1u << k;
+        }
+        out[o] = (uint8_t)b;
+    }
+}
+
+// host labels / cell records -> stage_out (labels) and, unless select_all, stage_bits (selection) -> counters
+int topology_host(sdfgpu_handle h, const uint32_t* labels, const uint8_t* select, const void* cells, size_t stride, size_t occ_off,
+                  size_t comp_off, int class_mask, int64_t nx, int64_t ny, int64_t nz, uint32_t max_label, int64_t* out_counts) {
+    const int64_t n = nx * ny * nz;
+    if (int rc = ensure(h, h->stage_out, (size_t)n * 4, "output staging")) return rc;
+    if (labels) {
+        if (int rc = copy_from_host(h, h->stage_out.ptr, labels, (size_t)n * 4)) return rc;
+    } else {
+        const char* const rec = static_cast<const char*>(cells) + comp_off;
+        if (int rc = staged_upload_hip(h, h->stage_out.ptr, (size_t)n * 4, nullptr, 32, [=](char* dst, size_t o, size_t len) {
+                const char* src = rec + (o / 4) * stride;
+                for (size_t q = 0; q < len; q += 4, src += stride) memcpy(dst + q, src, 4);
+            }))
+            return rc;
+    }
+    const bool selected = labels ? select != nullptr : (class_mask & 7) != 7;
+    if (selected) {
+        if (labels || class_mask == 1) {                       // a byte mask, or FILLED: the build's packers (occupancy > 0.5f)
+            if (int rc = upload_packed(h, labels ? select : nullptr, labels ? nullptr : cells, stride, occ_off, 0, n, nullptr, nullptr)) return rc;
+        } else {
+            const size_t nbytes = ((size_t)n + 7) / 8, padded = (nbytes + 3) & ~(size_t)3;
+            if (int rc = ensure(h, h->stage_bits, padded, "bit staging")) return rc;
+            if (int rc = staged_upload_hip(h, h->stage_bits.ptr, padded, nullptr, 32, [=](char* dst, size_t o, size_t len) {
+                    const size_t real = o >= nbytes ? 0 : std::min(len, nbytes - o);
+                    if (real) pack_cells_class_bits(static_cast<const char*>(cells), stride, occ_off, class_mask, n, o, real, reinterpret_cast<uint8_t*>(dst));
+                    if (real < len) memset(dst + real, 0, len - real);
+                }))
+                return rc;
+        }
+    }
+    return topology_impl(h, (const uint32_t*)h->stage_out.ptr, selected ? (const uint32_t*)h->stage_bits.ptr : nullptr, nx, ny, nz,
+                         max_label, out_counts, nullptr);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1713,7 +1802,8 @@ int sdfgpu_destroy(sdfgpu_handle h) {
     if (!h) return SDFGPU_OK;
     (void)hipSetDevice(h->device);
     for (DeviceBuffer* b : {&h->zfield, &h->yzfield, &h->plane16, &h->bits, &h->unc, &h->tileflag, &h->fix_order, &h->tagmask, &h->tagids, &h->stage_in,
-                            &h->stage_bits, &h->stage_out, &h->query_stage, &h->planebits, &h->cc_scratch})
+                            &h->stage_bits, &h->stage_out, &h->query_stage, &h->planebits, &h->cc_scratch,
+                            &h->tp_scratch, &h->tp_nodes})
         if (b->ptr) (void)rz_free(h, b->ptr);
     if (h->d_small) (void)rz_free(h, h->d_small);
     if (h->d_slots) (void)rz_free(h, h->d_slots);
@@ -2607,6 +2697,47 @@ int sdfgpu_components_cells(sdfgpu_handle h, void* cells, size_t cell_stride, si
             char* dst = rec + (goff / 4) * cell_stride;
             for (size_t o = 0; o < len; o += 4, dst += cell_stride) memcpy(dst, src + o, 4);
         });
+    });
+}
+
+int sdfgpu_component_topology_device(sdfgpu_handle h, const uint32_t* d_labels, const uint32_t* d_select_bits, int64_t nx, int64_t ny,
+                                     int64_t nz, uint32_t max_label, int64_t* out_counts, void* stream) {
+    return rz_wrap(h, stream, [&]() -> int {
+        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
+        if (!d_labels) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
+        if ((reinterpret_cast<uintptr_t>(d_labels) | reinterpret_cast<uintptr_t>(d_select_bits)) & 3)
+            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "d_labels and d_select_bits must be 4-byte aligned");
+        if (int rc = check_topology_args(h, nx, ny, nz, max_label, out_counts)) return rc;
+        HIP_TRY(h, hipSetDevice(h->device));
+        return topology_impl(h, d_labels, d_select_bits, nx, ny, nz, max_label, out_counts, (hipStream_t)stream);
+    });
+}
+
+int sdfgpu_component_topology(sdfgpu_handle h, const uint32_t* labels, const uint8_t* select_mask, int64_t nx, int64_t ny, int64_t nz,
+                              uint32_t max_label, int64_t* out_counts) {
+    return rz_wrap(h, nullptr, [&]() -> int {
+        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
+        if (!labels) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
+        if (int rc = check_topology_args(h, nx, ny, nz, max_label, out_counts)) return rc;
+        HIP_TRY(h, hipSetDevice(h->device));
+        return topology_host(h, labels, select_mask, nullptr, 0, 0, 0, 7, nx, ny, nz, max_label, out_counts);
+    });
+}
+
+int sdfgpu_component_topology_cells(sdfgpu_handle h, const void* cells, size_t cell_stride, size_t occupancy_offset, size_t component_offset,
+                                    int64_t nx, int64_t ny, int64_t nz, int class_mask, uint32_t max_label, int64_t* out_counts) {
+    return rz_wrap(h, nullptr, [&]() -> int {
+        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
+        if (!cells) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
+        if (cell_stride < 8 || (cell_stride % 4) || (occupancy_offset % 4) || (component_offset % 4) || occupancy_offset + 4 > cell_stride ||
+            component_offset + 4 > cell_stride || occupancy_offset == component_offset)
+            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cell_stride / occupancy_offset / component_offset must be 4-byte aligned, in range and distinct");
+        if (class_mask < 1 || class_mask > 7)
+            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "class_mask must be a nonzero combination of FILLED (1), EMPTY (2) and UNKNOWN (4)");
+        if (int rc = check_topology_args(h, nx, ny, nz, max_label, out_counts)) return rc;
+        HIP_TRY(h, hipSetDevice(h->device));
+        return topology_host(h, nullptr, nullptr, cells, cell_stride, occupancy_offset, component_offset, class_mask, nx, ny, nz, max_label,
+                             out_counts);
     });
 }
 
