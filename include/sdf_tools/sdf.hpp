@@ -2,14 +2,15 @@
 // of sdf_tools::SignedDistanceField (reference include/sdf_tools/sdf.hpp) that the hot path and the
 // pysdf_tools surface use: constructors (:34-81), lock-guarded SetValue (:236-264), GetGradient /
 // GetGridAlignedGradient / GetFullGradient (:341-526), EstimateDistance (:699-961), serialisation
-// and file / message forms (src/sdf_tools/sdf.cpp:213-502).  Out of scope here:
-// local-extrema maps, projection out of collision, AutoDiff gradients, RViz export.
+// and file / message forms (src/sdf_tools/sdf.cpp:213-502), and the local extrema map (sdf.cpp:23-207, on the GPU).  Out of
+// scope here: projection out of collision, AutoDiff gradients, RViz export.
 #pragma once
 #include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <fstream>
 #include <functional>
+#include <limits>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -227,6 +228,41 @@ public:
                 for (int64_t z = 0; z < GetNumZCells(); ++z)
                     grid.SetValue(x, y, z, gradient_function(x, y, z, enable_edge_gradients));
         return grid;
+    }
+
+    // ---- local extrema map (reference src/sdf_tools/sdf.cpp:23-207, sdf.hpp:1202-1218) ----------------------------
+    // For every cell, the extremum its gradient walk reaches (include/sdfgpu.h "Local extrema and convex segments", DESIGN.md
+    // section 15), computed on the GPU: the index of the fixed point, or of the cycle node the scan enters first, or 0xFFFFFFFF
+    // where the walk leaves the grid.  4 B per cell, for callers that do not need the reference's 24.
+    std::vector<uint32_t> ComputeLocalExtremaIndices() const {
+        const int64_t nx = GetNumXCells(), ny = GetNumYCells(), nz = GetNumZCells();
+        std::vector<uint32_t> idx((size_t)(nx * ny * nz));
+        if (idx.empty()) return idx;
+        const Eigen::Quaterniond q(origin_transform_.rotation());
+        const Eigen::Quaterniond qi = q.inverse();
+        const double q_and_qinv[8] = {q.w(), q.x(), q.y(), q.z(), qi.w(), qi.x(), qi.y(), qi.z()};
+        const std::shared_ptr<sdf_generation::SharedGpuContext> ctx = sdf_generation::GpuContext::Shared();
+        const std::lock_guard<std::mutex> lock(ctx->mutex);
+        sdf_generation::ThrowOnStatus(ctx->handle, sdfgpu_local_extrema(ctx->handle, data_.data(), nx, ny, nz, GetResolution(), q_and_qinv,
+                                                                        idx.data()));
+        return idx;
+    }
+
+    // The reference's map: grid-frame cell centre of each cell's extremum, (+inf, +inf, +inf) where the walk leaves the grid.
+    ::VoxelGrid::VoxelGrid<Eigen::Vector3d> ComputeLocalExtremaMap() const {
+        const double ninf = -std::numeric_limits<double>::infinity(), inf = std::numeric_limits<double>::infinity();
+        ::VoxelGrid::VoxelGrid<Eigen::Vector3d> map(origin_transform_, GetResolution(), GetNumXCells(), GetNumYCells(), GetNumZCells(),
+                                                   Eigen::Vector3d(ninf, ninf, ninf));
+        const std::vector<uint32_t> idx = ComputeLocalExtremaIndices();
+        const int64_t ny = GetNumYCells(), nz = GetNumZCells();
+        std::vector<Eigen::Vector3d>& out = map.GetMutableRawData();
+        for (size_t i = 0; i < idx.size(); ++i) {
+            const uint32_t e = idx[i];
+            if (e == 0xFFFFFFFFu) { out[i] = Eigen::Vector3d(inf, inf, inf); continue; }
+            const Eigen::Vector4d l = GridIndexToLocationGridFrame((int64_t)e / (ny * nz), ((int64_t)e / nz) % ny, (int64_t)e % nz);
+            out[i] = Eigen::Vector3d(l(0), l(1), l(2));
+        }
+        return map;
     }
 
     // ---- trilinear distance estimate (:699-961) ----------------------------------------------

@@ -9,8 +9,9 @@
 // arc_utilities serialisers: "wire-format parity unpinned", like the other two containers.
 // The connected components (UpdateConnectedComponents, tagged_object_collision_map.cpp:340-380, same connectivity rule as
 // CollisionMapGrid's) are computed on the GPU by sdfgpu_components_cells, and their topology (ComputeComponentTopology,
-// :424-490) by sdfgpu_component_topology_cells.  Convex segmentation, component surfaces and RViz export are out of scope
-// (SURVEY.md section 2, rows 7/8).  Every SDF is built on the GPU through sdfgpu_build_tagged_cells (device-side predicate).
+// :424-490) by sdfgpu_component_topology_cells, and the convex segments (UpdateConvexSegments, :552-654) by
+// sdfgpu_convex_segments_cells.  Component surfaces and RViz export are out of scope.
+// Every SDF is built on the GPU through sdfgpu_build_tagged_cells (device-side predicate).
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -157,6 +158,40 @@ public:
                                                  offsetof(TAGGED_OBJECT_COLLISION_CELL, component), GetNumXCells(), GetNumYCells(),
                                                  GetNumZCells(), (int)component_types_to_use, max_label, verbose);
     }
+
+    // ---- convex segments (reference tagged_object_collision_map.cpp:552-654) ---------------------------------------------------
+    // The SDF (virtual border: every filled cell; otherwise free space outside, named objects inside) -> its local extrema map ->
+    // segments: face neighbours that take part (occupancy < 0.5 or a named object, and an extremum inside the grid), carry the
+    // same object id and whose extrema lie closer than connected_threshold are joined; numbered 1..K in x -> y -> z scan order,
+    // 0 for every other cell, written into every cell's `convex_segment` (include/sdfgpu.h "Local extrema and convex segments").
+    // One GPU call: the cells travel once, the SDF and the extrema never leave the device.  Unlike the reference, which writes
+    // the labels through SetValue, the connected components stay valid: occupancy and object ids are not touched.
+    uint32_t UpdateConvexSegments(const double connected_threshold, const bool add_virtual_border) {
+        const Eigen::Vector3d cell_sizes = GetCellSizes();
+        if ((cell_sizes.x() != cell_sizes.y()) || (cell_sizes.x() != cell_sizes.z()))
+            throw std::invalid_argument("Grid must have uniform resolution");
+        uint32_t count = 0;
+        if (!data_.empty()) {
+            const Eigen::Quaterniond q(GetOriginTransform().rotation());
+            const Eigen::Quaterniond qi = q.inverse();
+            const double q_and_qinv[8] = {q.w(), q.x(), q.y(), q.z(), qi.w(), qi.x(), qi.y(), qi.z()};
+            const std::shared_ptr<sdf_generation::SharedGpuContext> ctx = sdf_generation::GpuContext::Shared();
+            const std::lock_guard<std::mutex> lock(ctx->mutex);
+            sdf_generation::ThrowOnStatus(
+                ctx->handle, sdfgpu_convex_segments_cells(ctx->handle, data_.data(), sizeof(TAGGED_OBJECT_COLLISION_CELL),
+                                                          offsetof(TAGGED_OBJECT_COLLISION_CELL, occupancy),
+                                                          offsetof(TAGGED_OBJECT_COLLISION_CELL, object_id),
+                                                          offsetof(TAGGED_OBJECT_COLLISION_CELL, convex_segment), GetNumXCells(),
+                                                          GetNumYCells(), GetNumZCells(), cell_sizes.x(), q_and_qinv, connected_threshold,
+                                                          add_virtual_border ? 1 : 0, &count));
+        }
+        number_of_convex_segments_ = count;
+        convex_segments_valid_ = true;
+        return number_of_convex_segments_;
+    }
+
+    std::pair<uint32_t, bool> GetNumConvexSegments() const { return std::make_pair(number_of_convex_segments_, convex_segments_valid_); }
+    bool AreConvexSegmentsValid() const { return convex_segments_valid_; }
 
     // ---- wire formats: tagged_object_collision_map.cpp:23-75 (fields), :242-307 (files), :309-339 (messages) ------------
     using CellSerializer = std::function<uint64_t(const TAGGED_OBJECT_COLLISION_CELL&, std::vector<uint8_t>&)>;

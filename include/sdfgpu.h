@@ -433,6 +433,53 @@ int sdfgpu_component_topology(sdfgpu_handle h, const uint32_t* labels, const uin
 int sdfgpu_component_topology_cells(sdfgpu_handle h, const void* cells, size_t cell_stride, size_t occupancy_offset, size_t component_offset,
                                     int64_t nx, int64_t ny, int64_t nz, int class_mask, uint32_t max_label, int64_t* out_counts);
 
+/* -------------------------------------------------------------------------
+ * Local extrema and convex segments: SignedDistanceField::ComputeLocalExtremaMap (reference src/sdf_tools/sdf.cpp:23-207) and
+ * TaggedObjectCollisionMapGrid::UpdateConvexSegments (tagged_object_collision_map.cpp:552-654) on the GPU.  DESIGN.md section 15.
+ * Indices: voxel (x, y, z) is (x ny + y) nz + z; loc(i) = (res (x + 0.5), res (y + 0.5), res (z + 0.5)) in the grid frame.
+ * Local extrema of an SDF f (float [nx][ny][nz]) with cell size res and origin rotation q:
+ *   - g(v) = GetGradient(v, enable_edge_gradients = true): central differences inside the grid, clamped one-sided differences on
+ *     the boundary shell, rotated as q * ((0, g) * q^-1) with eigen_lite's Quaterniond arithmetic (no fused multiply-add).
+ *   - next(v): w = f(v) < 0 ? -g : g; per axis +1 if w > s, -1 if w < -s, else 0, s = res * 0.06125.  next(v) == v exactly when
+ *     the reference's GradientIsEffectiveFlat holds or no axis steps because of a NaN; the reference stops at v in both cases.
+ *     A step out of the grid goes to the sink OFF.
+ *   - the extremum e(v) of v's forward orbit: a fixed point t -> loc(t); OFF -> (+inf, +inf, +inf); a cycle C (length >= 2) ->
+ *     loc(entry), entry = the first node of C on the orbit of the minimum-index voxel of C's basin (the voxels whose orbit ends
+ *     in C).  That voxel's walk is the first of the basin in the reference's x -> y -> z scan and fixes the value for the whole
+ *     basin: two voxels either side of a ridge whose maximum lies between them point at each other, and the one the scan
+ *     enters first is the extremum of both.
+ *   As indices: out_extremum[v] = t, entry, or 0xFFFFFFFF for OFF (4 B per voxel; the reference's map holds 24).
+ *   q_and_qinv: (w, x, y, z) of q, then of q.inverse() as eigen_lite computes it (identity: 1 0 0 0 1 -0 -0 -0).
+ * Convex segments of tagged cell records (float occupancy, uint32 object id, uint32 segment):
+ *   - the SDF is ExtractSignedDistanceField(+inf, {}, unknown_is_filled = true, true) with add_virtual_border, otherwise
+ *     ExtractFreeAndNamedObjectsSignedDistanceField(+inf, true) (free-space SDF outside, named-object SDF inside, 0 else);
+ *   - a cell takes part iff (occupancy < 0.5f || object_id > 0) (NaN occupancy with object 0 does not) and e(cell) is not OFF;
+ *   - two face neighbours that take part are joined iff their object ids are equal and
+ *     sqrt(((0 + dx dx) + dy dy) + dz dz) < connected_threshold in double, d = loc(e(a)) - loc(e(b)) (correctly rounded sqrt);
+ *   - segments are numbered 1..K by minimum index; every other cell gets 0.  Every record's segment word is overwritten; the
+ *     other fields are not touched.  *out_count = K.
+ * Refused (SDFGPU_ERR_INVALID_ARGUMENT): 2^32 - 1 voxels or more (indices and the OFF sentinel are uint32); res <= 0 or not finite.
+ * The SDF of sdfgpu_convex_segments_cells is an ordinary tagged build on the handle; the extrema and segment stages use scratch
+ * of their own (the SDF scratch, status block and policy are left as they were).  All results are bit-reproducible.
+ *
+ *   sdfgpu_local_extrema_device: d_sdf (n floats) -> d_extremum (n uint32), enqueued on `stream`; synchronises it once per
+ *       doubling round (the host reads the count of unresolved voxels).
+ *   sdfgpu_local_extrema: host field in, host indices out.
+ *   sdfgpu_convex_segments_cells: synchronous, in place; the records are uploaded once and the SDF, extrema and labels stay on
+ *       the device until the labels are scattered into each record's uint32 at segment_offset.
+ *   sdfgpu_convex_last_info: the last extrema computation on this handle: doubling rounds used, cycles (length >= 2), the
+ *       longest cycle and the longest basin-minimum -> cycle walk (diagnostics, the benchmarks report them).
+ * ------------------------------------------------------------------------- */
+int sdfgpu_local_extrema_device(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                                const double q_and_qinv[8], uint32_t* d_extremum, void* stream);
+int sdfgpu_local_extrema(sdfgpu_handle h, const float* sdf, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                         const double q_and_qinv[8], uint32_t* out_extremum);
+int sdfgpu_convex_segments_cells(sdfgpu_handle h, void* cells, size_t cell_stride, size_t occupancy_offset, size_t object_id_offset,
+                                 size_t segment_offset, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                                 const double q_and_qinv[8], double connected_threshold, int add_virtual_border, uint32_t* out_count);
+int sdfgpu_convex_last_info(sdfgpu_handle h, int* out_rounds, uint32_t* out_cycles, uint32_t* out_longest_cycle,
+                            uint32_t* out_longest_entry);
+
 /* Red zones (round 6).  With SDFGPU_REDZONE=1 in the environment when sdfgpu_create runs -- or after
  * sdfgpu_set_option(h, "redzone", 1) -- every device allocation of the library (scratch fields, status block, extrema slots,
  * staging buffers, sdfgpu_device_malloc memory) carries 4 KiB of canary bytes in front and behind, and every entry point that

@@ -6,6 +6,7 @@ there is deliberately no CPU fallback (the CPU oracle lives in oracle/ and is
 test infrastructure only).
 """
 import ctypes
+import math
 import os
 
 import numpy as np
@@ -29,6 +30,7 @@ EXPORTS = [
     "sdfgpu_build_bits_device", "sdfgpu_build_bits", "sdfgpu_voxelize_points_bits_device", "sdfgpu_debug_finish_table", "sdfgpu_redzone_check",
     "sdfgpu_components_bits_device", "sdfgpu_components", "sdfgpu_components_cells",
     "sdfgpu_component_topology_device", "sdfgpu_component_topology", "sdfgpu_component_topology_cells",
+    "sdfgpu_local_extrema_device", "sdfgpu_local_extrema", "sdfgpu_convex_segments_cells", "sdfgpu_convex_last_info",
 ]
 
 
@@ -114,6 +116,10 @@ def load_library():
     L.sdfgpu_component_topology_device.argtypes = [vp, vp, vp, i64, i64, i64, u32, vp, vp]
     L.sdfgpu_component_topology.argtypes = [vp, vp, vp, i64, i64, i64, u32, vp]
     L.sdfgpu_component_topology_cells.argtypes = [vp, vp, sz, sz, sz, i64, i64, i64, ci, u32, vp]
+    L.sdfgpu_local_extrema_device.argtypes = [vp, vp, i64, i64, i64, dbl, vp, vp, vp]
+    L.sdfgpu_local_extrema.argtypes = [vp, vp, i64, i64, i64, dbl, vp, vp]
+    L.sdfgpu_convex_segments_cells.argtypes = [vp, vp, sz, sz, sz, sz, i64, i64, i64, dbl, vp, dbl, ci, vp]
+    L.sdfgpu_convex_last_info.argtypes = [vp, vp, vp, vp, vp]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is ctypes.c_int or name not in ("sdfgpu_version", "sdfgpu_last_error"):
@@ -146,6 +152,51 @@ def topology_holes_voids(counts):
         raw = 1 + (abs(num) // 8) * (1 if num >= 0 else -1)
         out[int(c)] = (raw + surfaces - 1, surfaces - 1)
     return out
+
+
+EXTREMUM_OFF = 0xFFFFFFFF          # local_extrema*: the voxel's gradient walk leaves the grid
+
+
+def quaternion_and_inverse(q=(1.0, 0.0, 0.0, 0.0)):
+    """(w, x, y, z) -> the 8 doubles of sdfgpu_local_extrema*'s q_and_qinv: q, then q.inverse() with eigen_lite's arithmetic
+    (n = w w + x x + y y + z z, left to right; (w / n, -x / n, -y / n, -z / n))."""
+    w, x, y, z = (float(v) for v in q)
+    n = w * w + x * x + y * y + z * z
+    return (w, x, y, z, w / n, -x / n, -y / n, -z / n)
+
+
+def quaternion_from_matrix(R):
+    """3x3 rotation -> (w, x, y, z) by eigen_lite's Quaterniond(Matrix3d) (Shepperd's method, same branches and operations): the
+    quaternion the C++ classes derive from their origin transform."""
+    R = [[float(R[i][j]) for j in range(3)] for i in range(3)]
+    t = R[0][0] + R[1][1] + R[2][2]
+    if t > 0:
+        s = math.sqrt(t + 1.0) * 2
+        return (0.25 * s, (R[2][1] - R[1][2]) / s, (R[0][2] - R[2][0]) / s, (R[1][0] - R[0][1]) / s)
+    if R[0][0] > R[1][1] and R[0][0] > R[2][2]:
+        s = math.sqrt(1.0 + R[0][0] - R[1][1] - R[2][2]) * 2
+        return ((R[2][1] - R[1][2]) / s, 0.25 * s, (R[0][1] + R[1][0]) / s, (R[0][2] + R[2][0]) / s)
+    if R[1][1] > R[2][2]:
+        s = math.sqrt(1.0 + R[1][1] - R[0][0] - R[2][2]) * 2
+        return ((R[0][2] - R[2][0]) / s, (R[0][1] + R[1][0]) / s, 0.25 * s, (R[1][2] + R[2][1]) / s)
+    s = math.sqrt(1.0 + R[2][2] - R[0][0] - R[1][1]) * 2
+    return ((R[1][0] - R[0][1]) / s, (R[0][2] + R[2][0]) / s, (R[1][2] + R[2][1]) / s, 0.25 * s)
+
+
+def extremum_locations(indices, shape, resolution):
+    """uint32 extremum indices [nx, ny, nz] -> the reference's local extrema map, float64 [nx, ny, nz, 3]: grid-frame cell centres
+    res * (i + 0.5), (+inf, +inf, +inf) for EXTREMUM_OFF."""
+    nx, ny, nz = (int(s) for s in shape)
+    idx = np.asarray(indices, np.uint32).reshape(-1).astype(np.int64)
+    off = idx == EXTREMUM_OFF
+    idx = np.where(off, 0, idx)
+    res = float(resolution)
+    out = np.empty((idx.size, 3), np.float64)
+    out[:, 0] = res * ((idx // (ny * nz)).astype(np.float64) + 0.5)
+    out[:, 1] = res * (((idx // nz) % ny).astype(np.float64) + 0.5)
+    out[:, 2] = res * ((idx % nz).astype(np.float64) + 0.5)
+    out[off] = np.inf
+    return out.reshape(nx, ny, nz, 3)
 
 
 def device_count():
@@ -385,6 +436,45 @@ class SdfGpu:
         self._check(self._lib.sdfgpu_component_topology_cells(self._h, cells.ctypes.data, cell_stride, occupancy_offset, component_offset,
                                                                nx, ny, nz, int(class_mask), int(max_label), out.ctypes.data))
         return out
+
+    # ---- local extrema and convex segments (ComputeLocalExtremaMap / UpdateConvexSegments, include/sdfgpu.h) -----------------
+    def local_extrema(self, sdf, resolution, q=(1.0, 0.0, 0.0, 0.0)):
+        """sdf: float32 [nx, ny, nz]; q: (w, x, y, z) of the origin rotation.  Returns the extremum indices, uint32 [nx, ny, nz]
+        (EXTREMUM_OFF where the walk leaves the grid; extremum_locations() gives the reference's map)."""
+        f = np.ascontiguousarray(sdf, dtype=np.float32)
+        if f.ndim != 3:
+            raise ValueError("sdf must be [nx, ny, nz]")
+        out = np.empty(f.shape, np.uint32)
+        qq = (ctypes.c_double * 8)(*quaternion_and_inverse(q))
+        self._check(self._lib.sdfgpu_local_extrema(self._h, f.ctypes.data, *f.shape, float(resolution), qq, out.ctypes.data))
+        return out
+
+    def local_extrema_device(self, d_sdf, shape, resolution, d_extremum, q=(1.0, 0.0, 0.0, 0.0), stream=0):
+        nx, ny, nz = (int(s) for s in shape)
+        qq = (ctypes.c_double * 8)(*quaternion_and_inverse(q))
+        self._check(self._lib.sdfgpu_local_extrema_device(self._h, d_sdf, nx, ny, nz, float(resolution), qq, d_extremum, stream or None))
+
+    def convex_segments_cells(self, cells, shape, resolution, connected_threshold, add_virtual_border, q=(1.0, 0.0, 0.0, 0.0),
+                              cell_stride=16, occupancy_offset=0, object_id_offset=8, segment_offset=12):
+        """cells: writable contiguous records (TAGGED_OBJECT_COLLISION_CELL: 16 bytes, occupancy 0, object id 8, segment 12); the
+        segment labels are written into them in place.  Returns K."""
+        nx, ny, nz = (int(s) for s in shape)
+        if not (isinstance(cells, np.ndarray) and cells.flags.c_contiguous and cells.flags.writeable):
+            raise ValueError("cells must be a writable C-contiguous numpy array")
+        if cells.nbytes != nx * ny * nz * cell_stride:
+            raise ValueError("cells buffer size does not match shape * cell_stride")
+        k = ctypes.c_uint32(0)
+        qq = (ctypes.c_double * 8)(*quaternion_and_inverse(q))
+        self._check(self._lib.sdfgpu_convex_segments_cells(self._h, cells.ctypes.data, cell_stride, occupancy_offset, object_id_offset,
+                                                           segment_offset, nx, ny, nz, float(resolution), qq, float(connected_threshold),
+                                                           int(bool(add_virtual_border)), ctypes.byref(k)))
+        return int(k.value)
+
+    def convex_last_info(self):
+        """The last extrema computation on this handle: {rounds, cycles, longest_cycle, longest_entry}."""
+        r, c, lc, le = ctypes.c_int(0), ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_uint32(0)
+        self._check(self._lib.sdfgpu_convex_last_info(self._h, ctypes.byref(r), ctypes.byref(c), ctypes.byref(lc), ctypes.byref(le)))
+        return {"rounds": r.value, "cycles": c.value, "longest_cycle": lc.value, "longest_entry": le.value}
 
     def voxelize_points_bits_device(self, d_points, n_points, origin, resolution, shape, d_bits, clear_first=True, stream=0):
         nx, ny, nz = (int(s) for s in shape)

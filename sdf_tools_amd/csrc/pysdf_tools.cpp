@@ -105,6 +105,18 @@ PYBIND11_MODULE(pysdf_tools, m) {
         .def_static("LoadFromFile", &TaggedObjectCollisionMapGrid::LoadFromFile)
         .def("GetMessageRepresentation", [](const TaggedObjectCollisionMapGrid& g) { return TaggedObjectCollisionMapGrid::GetMessageRepresentation(g); })
         .def_static("LoadFromMessageRepresentation", &TaggedObjectCollisionMapGrid::LoadFromMessageRepresentation)
+        .def("UpdateConvexSegments", &TaggedObjectCollisionMapGrid::UpdateConvexSegments, py::arg("connected_threshold"),
+             py::arg("add_virtual_border"), py::call_guard<py::gil_scoped_release>(),
+             "convex segments on the GPU (tagged_object_collision_map.cpp:552-654; include/sdfgpu.h \"Local extrema and convex segments\")")
+        .def("GetNumConvexSegments", &TaggedObjectCollisionMapGrid::GetNumConvexSegments)
+        .def("AreConvexSegmentsValid", &TaggedObjectCollisionMapGrid::AreConvexSegmentsValid)
+        .def("GetConvexSegmentsNumpy", [](const TaggedObjectCollisionMapGrid& g) {
+            py::array_t<uint32_t> out({(py::ssize_t)g.GetNumXCells(), (py::ssize_t)g.GetNumYCells(), (py::ssize_t)g.GetNumZCells()});
+            uint32_t* o = out.mutable_data();
+            const auto& cells = g.GetImmutableRawData();
+            for (size_t i = 0; i < cells.size(); i++) o[i] = cells[i].convex_segment;
+            return out;
+        }, "the cells' convex segment labels as uint32 [nx, ny, nz] (0 until UpdateConvexSegments has run)")
         .def("ExtractSignedDistanceField", [](const TaggedObjectCollisionMapGrid& g, float oob_value, const std::vector<uint32_t>& objects_to_use,
                                                bool unknown_is_filled, bool add_virtual_border) {
             return g.ExtractSignedDistanceField(oob_value, objects_to_use, unknown_is_filled, add_virtual_border);
@@ -159,6 +171,29 @@ PYBIND11_MODULE(pysdf_tools, m) {
             std::memcpy(out.mutable_data(), g.data(), g.size() * sizeof(double));
             return out;
         }, py::arg("enable_edge_gradients") = true)
+        .def("ComputeLocalExtremaMapNumpy", [](const SignedDistanceField& s) {
+            const int64_t nx = s.GetNumXCells(), ny = s.GetNumYCells(), nz = s.GetNumZCells();
+            ::VoxelGrid::VoxelGrid<Eigen::Vector3d> map;
+            {
+                py::gil_scoped_release release;
+                map = s.ComputeLocalExtremaMap();
+            }
+            py::array_t<double> out({nx, ny, nz, (int64_t)3});
+            double* o = out.mutable_data();
+            for (const Eigen::Vector3d& e : map.GetImmutableRawData()) { *o++ = e.x(); *o++ = e.y(); *o++ = e.z(); }
+            return out;
+        }, "ComputeLocalExtremaMap (sdf.cpp:23-207, on the GPU) as float64 [nx, ny, nz, 3]: grid-frame extremum of each cell's "
+           "gradient walk, +inf where it leaves the grid")
+        .def("ComputeLocalExtremaIndicesNumpy", [](const SignedDistanceField& s) {
+            std::vector<uint32_t> idx;
+            {
+                py::gil_scoped_release release;
+                idx = s.ComputeLocalExtremaIndices();
+            }
+            py::array_t<uint32_t> out({(py::ssize_t)s.GetNumXCells(), (py::ssize_t)s.GetNumYCells(), (py::ssize_t)s.GetNumZCells()});
+            std::memcpy(out.mutable_data(), idx.data(), idx.size() * sizeof(uint32_t));
+            return out;
+        }, "the extremum of each cell as a linear index, uint32 [nx, ny, nz]; 0xFFFFFFFF where the walk leaves the grid")
         .def("GetFullGradientNumpyHost", [](const SignedDistanceField& s, bool enable_edge_gradients) {
             // the reference's per-voxel loop (sdf.hpp:341-358) on one host core: kept as the checker of the GPU path
             const int64_t nx = s.GetNumXCells(), ny = s.GetNumYCells(), nz = s.GetNumZCells();

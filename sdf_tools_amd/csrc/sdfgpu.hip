@@ -13,6 +13,7 @@
 #include "sdfgpu_hostteam.hpp"
 #include "sdfgpu_components.hpp"
 #include "sdfgpu_topology.hpp"
+#include "sdfgpu_convex.hpp"
 
 #include <sys/mman.h>
 #if defined(__SSE2__)
@@ -71,6 +72,10 @@ struct sdfgpu_context {
     DeviceBuffer cc_scratch;    // sdfgpu_components*: root flags, ranks, chunk counts, K (sdfgpu_components.hpp)
     DeviceBuffer tp_scratch;    // sdfgpu_component_topology*: counters, status, node bytes, node offsets (sdfgpu_topology.hpp)
     DeviceBuffer tp_nodes;      // sdfgpu_component_topology*: one union-find word per surface-vertex node
+    DeviceBuffer cx_scratch;    // sdfgpu_local_extrema* / sdfgpu_convex_segments_cells: doubling state, next, stats, ranks (sdfgpu_convex.hpp)
+    DeviceBuffer cx_field;      // sdfgpu_local_extrema: the field; sdfgpu_convex_segments_cells: the named-object SDF, then the extrema
+    size_t cx_stats_off = 0;    // where the last extrema call left its CxStats in cx_scratch (0 = no call yet)
+    int cx_rounds = 0;          // doubling rounds of that call
     size_t tag_cached_bytes = 0;            // stage_in holds the tagged cell records of the last sdfgpu_build_tagged_cells call
     void* pin[2] = {nullptr, nullptr};      // pinned host staging of copy_to_host (two chunks in flight)
     // Red zones (round 6, VERDICT r5 "next round" 2): with SDFGPU_REDZONE=1 in the environment of sdfgpu_create (or option
@@ -1737,6 +1742,65 @@ int topology_host(sdfgpu_handle h, const uint32_t* labels, const uint8_t* select
                          max_label, out_counts, nullptr);
 }
 
+// ---- local extrema and convex segments (sdfgpu_convex.hpp) ---------------------------------------------------------------------
+// The extrema and segment stages use only cx_scratch and cx_field (and, in the host forms, the staging buffers and the pinned
+// chunks); the SDF scratch, status block and policy are left as they were.  sdfgpu_convex_segments_cells builds its SDF with the
+// ordinary tagged build.
+int check_convex_args(sdfgpu_handle h, int64_t nx, int64_t ny, int64_t nz, double resolution, const double* q_and_qinv) {
+    if (!q_and_qinv) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
+    if (nx <= 0 || ny <= 0 || nz <= 0)
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "grid dimensions must be positive (got %lld x %lld x %lld)",
+                    (long long)nx, (long long)ny, (long long)nz);
+    if ((unsigned __int128)nx * (unsigned __int128)ny * (unsigned __int128)nz >= (unsigned __int128)0xFFFFFFFFu)
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT,
+                    "grid %lld x %lld x %lld has 2^32 - 1 voxels or more: uint32 indices and the OFF sentinel cannot number it",
+                    (long long)nx, (long long)ny, (long long)nz);
+    if (!(resolution > 0.0) || !std::isfinite(resolution))
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "resolution must be positive and finite (got %g)", resolution);
+    return SDFGPU_OK;
+}
+
+// d_sdf (device) -> d_ext (device); synchronises `st` once per doubling round
+int extrema_impl(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t ny, int64_t nz, double resolution, const double* q_and_qinv,
+                 uint32_t* d_ext, hipStream_t st) {
+    const CxPlan plan = cx_plan(nx, ny, nz);
+    if (int rc = ensure(h, h->cx_scratch, plan.scratch_bytes, "convex scratch")) return rc;
+    CxRot rot;
+    for (int i = 0; i < 4; ++i) { rot.q[i] = q_and_qinv[i]; rot.qi[i] = q_and_qinv[4 + i]; }
+    int rounds = 0;
+    h->cx_stats_off = 0;
+    HIP_TRY(h, cx_extrema(plan, d_sdf, resolution, rot, d_ext, h->cx_scratch.ptr, st, &rounds));
+    h->cx_stats_off = plan.off_stats;
+    h->cx_rounds = rounds;
+    return SDFGPU_OK;
+}
+
+// records in stage_in -> SDF in stage_out (float), the virtual-border or the free-and-named-objects form
+int convex_sdf(sdfgpu_handle h, size_t stride, size_t occ_off, size_t obj_off, int64_t nx, int64_t ny, int64_t nz, double resolution,
+               int add_virtual_border) {
+    const int64_t n = nx * ny * nz;
+    auto classify = [&](int mode) {
+        hipLaunchKernelGGL(k_classify_tagged, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, nullptr,
+                           (const char*)h->stage_in.ptr, (int64_t)stride, (int64_t)occ_off, (int64_t)obj_off, 1, mode,
+                           (const uint32_t*)h->tagids.ptr, 0, n, (uint8_t*)h->tagmask.ptr);
+        return hipGetLastError();
+    };
+    // ExtractSignedDistanceField(+inf, {}, true, true): every filled cell (an empty id list is "any object", :826)
+    HIP_TRY(h, classify(0));
+    if (int rc = build_device_impl(h, (const uint8_t*)h->tagmask.ptr, nullptr, 0, 0, 0, nx, ny, nz, resolution, add_virtual_border ? 1 : 0,
+                                   (float*)h->stage_out.ptr, nullptr))
+        return rc;
+    if (add_virtual_border) return SDFGPU_OK;
+    // ExtractFreeAndNamedObjectsSignedDistanceField(+inf, true): the free-space SDF above, the named-object SDF, combined as the
+    // host does it (tagged_object_collision_map.hpp)
+    HIP_TRY(h, classify(1));
+    if (int rc = build_device_impl(h, (const uint8_t*)h->tagmask.ptr, nullptr, 0, 0, 0, nx, ny, nz, resolution, 0, (float*)h->cx_field.ptr,
+                                   nullptr))
+        return rc;
+    HIP_TRY(h, cx_combine((float*)h->stage_out.ptr, (const float*)h->cx_field.ptr, (uint64_t)n, nullptr));
+    return SDFGPU_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1803,7 +1867,7 @@ int sdfgpu_destroy(sdfgpu_handle h) {
     (void)hipSetDevice(h->device);
     for (DeviceBuffer* b : {&h->zfield, &h->yzfield, &h->plane16, &h->bits, &h->unc, &h->tileflag, &h->fix_order, &h->tagmask, &h->tagids, &h->stage_in,
                             &h->stage_bits, &h->stage_out, &h->query_stage, &h->planebits, &h->cc_scratch,
-                            &h->tp_scratch, &h->tp_nodes})
+                            &h->tp_scratch, &h->tp_nodes, &h->cx_scratch, &h->cx_field})
         if (b->ptr) (void)rz_free(h, b->ptr);
     if (h->d_small) (void)rz_free(h, h->d_small);
     if (h->d_slots) (void)rz_free(h, h->d_slots);
@@ -2739,6 +2803,96 @@ int sdfgpu_component_topology_cells(sdfgpu_handle h, const void* cells, size_t c
         return topology_host(h, nullptr, nullptr, cells, cell_stride, occupancy_offset, component_offset, class_mask, nx, ny, nz, max_label,
                              out_counts);
     });
+}
+
+int sdfgpu_local_extrema_device(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                                const double q_and_qinv[8], uint32_t* d_extremum, void* stream) {
+    return rz_wrap(h, stream, [&]() -> int {
+        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
+        if (!d_sdf || !d_extremum) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
+        if ((reinterpret_cast<uintptr_t>(d_sdf) | reinterpret_cast<uintptr_t>(d_extremum)) & 3)
+            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "d_sdf and d_extremum must be 4-byte aligned");
+        if (int rc = check_convex_args(h, nx, ny, nz, resolution, q_and_qinv)) return rc;
+        HIP_TRY(h, hipSetDevice(h->device));
+        return extrema_impl(h, d_sdf, nx, ny, nz, resolution, q_and_qinv, d_extremum, (hipStream_t)stream);
+    });
+}
+
+int sdfgpu_local_extrema(sdfgpu_handle h, const float* sdf, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                         const double q_and_qinv[8], uint32_t* out_extremum) {
+    return rz_wrap(h, nullptr, [&]() -> int {
+        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
+        if (!sdf || !out_extremum) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
+        if (int rc = check_convex_args(h, nx, ny, nz, resolution, q_and_qinv)) return rc;
+        HIP_TRY(h, hipSetDevice(h->device));
+        const size_t n = (size_t)(nx * ny * nz);
+        if (int rc = ensure(h, h->cx_field, n * 4, "convex field")) return rc;
+        if (int rc = ensure(h, h->stage_out, n * 4, "output staging")) return rc;
+        if (int rc = copy_from_host(h, h->cx_field.ptr, sdf, n * 4)) return rc;
+        if (int rc = extrema_impl(h, (const float*)h->cx_field.ptr, nx, ny, nz, resolution, q_and_qinv, (uint32_t*)h->stage_out.ptr, nullptr))
+            return rc;
+        return copy_to_host(h, out_extremum, h->stage_out.ptr, n * 4);
+    });
+}
+
+int sdfgpu_convex_segments_cells(sdfgpu_handle h, void* cells, size_t cell_stride, size_t occupancy_offset, size_t object_id_offset,
+                                 size_t segment_offset, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                                 const double q_and_qinv[8], double connected_threshold, int add_virtual_border, uint32_t* out_count) {
+    return rz_wrap(h, nullptr, [&]() -> int {
+        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
+        if (!cells || !out_count) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
+        if (cell_stride < 12 || (cell_stride % 4) || (occupancy_offset % 4) || (object_id_offset % 4) || (segment_offset % 4) ||
+            occupancy_offset + 4 > cell_stride || object_id_offset + 4 > cell_stride || segment_offset + 4 > cell_stride ||
+            occupancy_offset == object_id_offset || segment_offset == occupancy_offset || segment_offset == object_id_offset)
+            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT,
+                        "cell_stride / occupancy_offset / object_id_offset / segment_offset must be 4-byte aligned, in range and distinct");
+        if (int rc = check_convex_args(h, nx, ny, nz, resolution, q_and_qinv)) return rc;
+        if (int rc = check_dims(h, nx, ny, nz)) return rc;                     // (the SDF build's own limits)
+        HIP_TRY(h, hipSetDevice(h->device));
+        const int64_t n = nx * ny * nz;
+        const CxPlan plan = cx_plan(nx, ny, nz);
+        h->tag_cached_bytes = 0;
+        if (int rc = ensure(h, h->stage_in, (size_t)n * cell_stride, "input staging")) return rc;
+        if (int rc = ensure(h, h->stage_out, (size_t)n * 4, "output staging")) return rc;
+        if (int rc = ensure(h, h->tagmask, (size_t)n, "tagged-object mask")) return rc;
+        if (int rc = ensure(h, h->tagids, 4, "object id list")) return rc;
+        if (int rc = ensure(h, h->cx_field, (size_t)n * 4, "convex field")) return rc;
+        if (int rc = ensure(h, h->cx_scratch, plan.scratch_bytes, "convex scratch")) return rc;
+        if (int rc = copy_from_host(h, h->stage_in.ptr, cells, (size_t)n * cell_stride)) return rc;
+        if (int rc = convex_sdf(h, cell_stride, occupancy_offset, object_id_offset, nx, ny, nz, resolution, add_virtual_border)) return rc;
+        uint32_t* d_ext = (uint32_t*)h->cx_field.ptr;                          // (the named-object SDF is consumed by now)
+        if (int rc = extrema_impl(h, (const float*)h->stage_out.ptr, nx, ny, nz, resolution, q_and_qinv, d_ext, nullptr)) return rc;
+        uint32_t* d_labels = (uint32_t*)h->stage_out.ptr;                      // (the SDF is consumed by the extrema)
+        HIP_TRY(h, cx_segments(plan, d_ext, (const char*)h->stage_in.ptr, cell_stride, occupancy_offset, object_id_offset, resolution,
+                               connected_threshold, d_labels, h->cx_scratch.ptr, nullptr));
+        uint32_t count = 0;
+        HIP_TRY(h, hipMemcpyAsync(&count, static_cast<char*>(h->cx_scratch.ptr) + plan.off_stats + offsetof(CxStats, count), 4,
+                                  hipMemcpyDeviceToHost, nullptr));
+        HIP_TRY(h, hipStreamSynchronize(nullptr));
+        char* const rec = static_cast<char*>(cells) + segment_offset;
+        if (int rc = staged_download_hip(h, d_labels, (size_t)n * 4, nullptr, [=](const char* src, size_t goff, size_t len) {
+                char* dst = rec + (goff / 4) * cell_stride;
+                for (size_t o = 0; o < len; o += 4, dst += cell_stride) memcpy(dst, src + o, 4);
+            }))
+            return rc;
+        *out_count = count;
+        return SDFGPU_OK;
+    });
+}
+
+int sdfgpu_convex_last_info(sdfgpu_handle h, int* out_rounds, uint32_t* out_cycles, uint32_t* out_longest_cycle,
+                            uint32_t* out_longest_entry) {
+    if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
+    if (h->cx_stats_off == 0 || !h->cx_scratch.ptr) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "no local extrema computed on this handle");
+    HIP_TRY(h, hipSetDevice(h->device));
+    static thread_local CxStats st;                            // (336 KiB: not on the stack)
+    HIP_TRY(h, hipDeviceSynchronize());
+    HIP_TRY(h, hipMemcpy(&st, static_cast<char*>(h->cx_scratch.ptr) + h->cx_stats_off, sizeof st, hipMemcpyDeviceToHost));
+    if (out_rounds) *out_rounds = h->cx_rounds;
+    if (out_cycles) *out_cycles = cx_row_sum(st.cycles);
+    if (out_longest_cycle) *out_longest_cycle = st.longest_cycle[0];
+    if (out_longest_entry) *out_longest_entry = st.longest_entry[0];
+    return SDFGPU_OK;
 }
 
 }  // extern "C"
