@@ -629,7 +629,9 @@ struct DcExtra {                 // int32 plane fields instead of p16 + side tab
 struct DcDecide {                // a probe launch turns its counters into the tier decision itself (last workgroup)
     int stage = 0; bool dense_tried = false, handoff = false, window_choice = false;
 };
-// Longer lines, larger grids (L > 2048, finf + (L + 2)^2 >= 2^(32 - B), 2^31 voxels or more): the marching sweeps with unbounded scans.
+// Shapes refused here (keys wider than 32 bits: finf + (L + 2)^2 >= 2^(32 - B); 2^31 voxels or more) take the marching sweeps
+// with unbounded scans.  In practice the key gate decides for every line longer than 1024: from L = 1025 on, B = 11 and
+// (L - 1)^2 + (L + 2)^2 alone exceed 2^21, so the L > 2048, 24-bit and LDS tests below never turn a shape away by themselves.
 DcGeometry envelope_dc_geometry(const sdfgpu_context* h, int stage, int64_t nx, int64_t ny, int64_t nz, int64_t ny_full = -1) {
     DcGeometry g{};
     if (ny_full < 0) ny_full = ny;
