@@ -458,7 +458,8 @@ int sdfgpu_component_topology_cells(sdfgpu_handle h, const void* cells, size_t c
  *     sqrt(((0 + dx dx) + dy dy) + dz dz) < connected_threshold in double, d = loc(e(a)) - loc(e(b)) (correctly rounded sqrt);
  *   - segments are numbered 1..K by minimum index; every other cell gets 0.  Every record's segment word is overwritten; the
  *     other fields are not touched.  *out_count = K.
- * Refused (SDFGPU_ERR_INVALID_ARGUMENT): 2^32 - 1 voxels or more (indices and the OFF sentinel are uint32); res <= 0 or not finite.
+ * Refused (SDFGPU_ERR_INVALID_ARGUMENT): 2^32 - 2 voxels or more (indices share the uint32 space with the OFF sentinel 2^32 - 1
+ * and the doubling markers 2^32 - 1, 2^32 - 2, 2^32 - 3: at most 2^32 - 3 voxels); res <= 0 or not finite.
  * The SDF of sdfgpu_convex_segments_cells is an ordinary tagged build on the handle; the extrema and segment stages use scratch
  * of their own (the SDF scratch, status block and policy are left as they were).  All results are bit-reproducible.
  *

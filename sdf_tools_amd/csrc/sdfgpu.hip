@@ -1753,9 +1753,12 @@ int check_convex_args(sdfgpu_handle h, int64_t nx, int64_t ny, int64_t nz, doubl
     if (nx <= 0 || ny <= 0 || nz <= 0)
         return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "grid dimensions must be positive (got %lld x %lld x %lld)",
                     (long long)nx, (long long)ny, (long long)nz);
-    if ((unsigned __int128)nx * (unsigned __int128)ny * (unsigned __int128)nz >= (unsigned __int128)0xFFFFFFFFu)
+    // Indices, kCxOff and the doubling markers share one uint32 space (sdfgpu_convex.hip): the markers are 2^32 - 1 (= kCxOff),
+    // 2^32 - 2 and 2^32 - 3, so every index must stay below 2^32 - 3 and n may be at most 2^32 - 3.
+    if ((unsigned __int128)nx * (unsigned __int128)ny * (unsigned __int128)nz >= (unsigned __int128)0xFFFFFFFEu)
         return fail(h, SDFGPU_ERR_INVALID_ARGUMENT,
-                    "grid %lld x %lld x %lld has 2^32 - 1 voxels or more: uint32 indices and the OFF sentinel cannot number it",
+                    "grid %lld x %lld x %lld has 2^32 - 2 voxels or more: uint32 indices share their space with the OFF sentinel and "
+                    "the doubling markers 2^32 - 1, 2^32 - 2, 2^32 - 3, so at most 2^32 - 3 voxels can be numbered",
                     (long long)nx, (long long)ny, (long long)nz);
     if (!(resolution > 0.0) || !std::isfinite(resolution))
         return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "resolution must be positive and finite (got %g)", resolution);

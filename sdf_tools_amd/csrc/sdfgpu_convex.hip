@@ -16,7 +16,8 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kScanThreads = 1024;
-// The doubling state of an unresolved node is (p_k(v) << 32) | m_k(v), m_k(v) < n <= 2^32 - 2.  A resolved node's low word is
+// The doubling state of an unresolved node is (p_k(v) << 32) | m_k(v), m_k(v) < n <= 2^32 - 3 (check_convex_args): an index must
+// never equal one of the three markers below, or an open state would read as resolved.  A resolved node's low word is
 // a marker, its high word the answer: kResTerm -> the terminal (a fixed point, or kCxOff), kResCycle -> the cycle's minimum index;
 // k_cx_entry turns the marker of every cycle node into kOnCycle.
 constexpr uint32_t kResTerm = 0xFFFFFFFFu;
@@ -27,6 +28,14 @@ __device__ __forceinline__ uint64_t pack(uint32_t hi, uint32_t lo) { return ((ui
 __device__ __forceinline__ uint32_t hi32(uint64_t s) { return (uint32_t)(s >> 32); }
 __device__ __forceinline__ uint32_t lo32(uint64_t s) { return (uint32_t)s; }
 __device__ __forceinline__ bool resolved(uint64_t s) { return lo32(s) >= kOnCycle; }
+
+// One lane per voxel.  A launch of 2^32 work-items or more along one axis is refused by the runtime, and n > 2^32 - 256 takes
+// 2^24 workgroups of 256, so the workgroups are numbered over a 2-D grid, x fastest: workgroup b = blockIdx.y gridDim.x +
+// blockIdx.x holds indices [256 b, 256 b + 256), dispatched in the order of a 1-D grid.
+constexpr unsigned kGridX = 1u << 16;
+__device__ __forceinline__ uint64_t lane_index() {
+    return ((uint64_t)blockIdx.y * gridDim.x + blockIdx.x) * kThreads + threadIdx.x;
+}
 
 // Sum (and maxima) of a per-lane value over the workgroup; the result is valid in thread 0.  Every thread must call these.
 __device__ __forceinline__ uint32_t wave_max(uint32_t x) {
@@ -60,7 +69,7 @@ __device__ __forceinline__ Q4 qmul(const Q4& a, const Q4& o) {
 __global__ __launch_bounds__(kThreads) void k_cx_next(const float* __restrict__ f, int64_t nx, int64_t ny, int64_t nz, uint64_t n,
                                                       const GradScale sc, double step, const CxRot rot, uint32_t* __restrict__ nxt,
                                                       uint64_t* __restrict__ A, uint64_t* __restrict__ B) {
-    const uint64_t v = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+    const uint64_t v = lane_index();
     if (v >= n) return;
     const int64_t z = (int64_t)(v % (uint64_t)nz), r = (int64_t)(v / (uint64_t)nz), y = r % ny, x = r / ny;
     double g[3];
@@ -105,7 +114,7 @@ __global__ __launch_bounds__(kThreads) void k_cx_next(const float* __restrict__ 
 // The nodes left open are counted per workgroup into one of the spread slots of round k.
 __global__ __launch_bounds__(kThreads) void k_cx_round(uint64_t* __restrict__ in, uint64_t* __restrict__ out,
                                                        const uint32_t* __restrict__ nxt, uint64_t n, CxStats* __restrict__ st, int k) {
-    const uint64_t v = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+    const uint64_t v = lane_index();
     bool open = false;
     if (v < n) {
         const uint64_t s = in[v];
@@ -142,7 +151,7 @@ __global__ __launch_bounds__(kThreads) void k_cx_round(uint64_t* __restrict__ in
 // ---- k_cx_basin: slot[c] = min index of the voxels whose orbit ends in the cycle c ---------------------------------------------
 // A basin is usually one cycle for a whole wave (a room's free space drains into a handful): one atomic per wave then.
 __global__ __launch_bounds__(kThreads) void k_cx_basin(const uint64_t* __restrict__ A, uint64_t n, uint32_t* __restrict__ slot) {
-    const uint64_t v = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+    const uint64_t v = lane_index();
     uint32_t c = kCxOff;
     if (v < n) {
         const uint64_t s = A[v];
@@ -168,7 +177,7 @@ __global__ __launch_bounds__(kThreads) void k_cx_basin(const uint64_t* __restric
 // lane touches only its own basin's nodes; all walks together are at most n steps.
 __global__ __launch_bounds__(kThreads) void k_cx_entry(uint64_t* __restrict__ A, const uint32_t* __restrict__ nxt, uint64_t n,
                                                        uint32_t* __restrict__ slot, CxStats* __restrict__ st) {
-    const uint64_t v = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+    const uint64_t v = lane_index();
     uint32_t len = 0, steps = 0;
     if (v < n) {
         const uint64_t s = A[v];
@@ -195,7 +204,7 @@ __global__ __launch_bounds__(kThreads) void k_cx_entry(uint64_t* __restrict__ A,
 
 __global__ __launch_bounds__(kThreads) void k_cx_final(const uint64_t* __restrict__ A, const uint32_t* __restrict__ slot, uint64_t n,
                                                        uint32_t* __restrict__ ext) {
-    const uint64_t v = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+    const uint64_t v = lane_index();
     if (v >= n) return;
     const uint64_t s = A[v];
     ext[v] = lo32(s) == kResTerm ? hi32(s) : slot[hi32(s)];
@@ -206,7 +215,7 @@ __global__ __launch_bounds__(kThreads) void k_cx_final(const uint64_t* __restric
 // (NaN occupancy with object 0 included), or its walk leaves the grid.
 __global__ __launch_bounds__(kThreads) void k_cx_key(const uint32_t* __restrict__ ext, const char* __restrict__ cells, uint64_t stride,
                                                      uint64_t occ_off, uint64_t obj_off, uint64_t n, uint64_t* __restrict__ key) {
-    const uint64_t v = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+    const uint64_t v = lane_index();
     if (v >= n) return;
     const char* rec = cells + v * stride;
     const float occ = *reinterpret_cast<const float*>(rec + occ_off);
@@ -269,7 +278,7 @@ __device__ __forceinline__ void g_union(uint32_t* L, uint32_t a, uint32_t b) {
 // L[v] = the first voxel of v's run of joined z neighbours inside v's wave (64 consecutive indices): chains of depth <= 1
 __global__ __launch_bounds__(kThreads) void k_cx_uf_init(const uint64_t* __restrict__ key, uint64_t n, const SegGeom g,
                                                          uint32_t* __restrict__ L) {
-    const uint64_t v = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+    const uint64_t v = lane_index();
     const int lane = threadIdx.x & 63;
     bool j = false;
     if (v < n && v % (uint64_t)g.nz != 0) j = joined(key[v], key[v - 1], g);
@@ -283,7 +292,7 @@ __global__ __launch_bounds__(kThreads) void k_cx_uf_init(const uint64_t* __restr
 // The remaining pairs: z across wave boundaries; y and x unless the square through the z predecessors already joins them
 __global__ __launch_bounds__(kThreads) void k_cx_uf_link(const uint64_t* __restrict__ key, uint64_t n, const SegGeom g,
                                                          uint32_t* __restrict__ L) {
-    const uint64_t v = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+    const uint64_t v = lane_index();
     if (v >= n) return;
     const uint64_t kv = key[v];
     if (lo32(kv) == kCxOff) return;
@@ -375,7 +384,7 @@ __global__ __launch_bounds__(kScanThreads) void k_cx_scan(const uint32_t* __rest
 __global__ __launch_bounds__(256) void k_cx_relabel(uint32_t* __restrict__ L, const uint64_t* __restrict__ key, uint64_t n,
                                                     const uint32_t* __restrict__ rb, const uint32_t* __restrict__ wr,
                                                     const uint32_t* __restrict__ co) {
-    const uint64_t v = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    const uint64_t v = lane_index();
     if (v >= n) return;
     if (lo32(key[v]) == kCxOff) { L[v] = 0u; return; }
     const uint32_t r = L[v], w = r >> 5;
@@ -383,13 +392,16 @@ __global__ __launch_bounds__(256) void k_cx_relabel(uint32_t* __restrict__ L, co
 }
 
 __global__ __launch_bounds__(kThreads) void k_cx_combine(float* __restrict__ fr, const float* __restrict__ nm, uint64_t n) {
-    const uint64_t v = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+    const uint64_t v = lane_index();
     if (v >= n) return;
     const float a = fr[v], b = nm[v];
     fr[v] = a >= 0.0f ? a : (b <= -0.0f ? b : 0.0f);
 }
 
-unsigned blocks(uint64_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
+dim3 lanes(uint64_t n) {
+    const uint64_t b = (n + kThreads - 1) / kThreads;
+    return b <= kGridX ? dim3((unsigned)b) : dim3(kGridX, (unsigned)((b + kGridX - 1) / kGridX));
+}
 
 }  // namespace
 
@@ -425,15 +437,15 @@ hipError_t cx_extrema(const CxPlan& p, const float* d_sdf, double res, const CxR
     sc.inv_w2 = 1.0 / ((double)2 * res);
     sc.inv2f = (float)sc.inv2;
     const double step = res * 0.06125;
-    const unsigned nb = blocks(p.n);
-    hipLaunchKernelGGL(k_cx_next, dim3(nb), dim3(kThreads), 0, s, d_sdf, p.nx, p.ny, p.nz, p.n, sc, step, rot, nxt, A, B);
+    const dim3 nb = lanes(p.n);
+    hipLaunchKernelGGL(k_cx_next, nb, dim3(kThreads), 0, s, d_sdf, p.nx, p.ny, p.nz, p.n, sc, step, rot, nxt, A, B);
     // doubling: one launch per round; the host reads the round's count of open nodes
     int used = 0;
     for (int k = 0;; ++k) {
         if (k >= kCxMaxRounds) return hipErrorUnknown;           // (unreachable: ceil(log2 n) + 1 rounds resolve every node)
         uint64_t* in = (k & 1) ? B : A;
         uint64_t* out = (k & 1) ? A : B;
-        hipLaunchKernelGGL(k_cx_round, dim3(nb), dim3(kThreads), 0, s, in, out, (const uint32_t*)nxt, p.n, st, k);
+        hipLaunchKernelGGL(k_cx_round, nb, dim3(kThreads), 0, s, in, out, (const uint32_t*)nxt, p.n, st, k);
         static thread_local uint32_t row[kCxSpread * kCxLine];
         if ((e = hipMemcpyAsync(row, st->open[k], sizeof row, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
         if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
@@ -443,9 +455,9 @@ hipError_t cx_extrema(const CxPlan& p, const float* d_sdf, double res, const CxR
     // every resolved node holds its marker in A and in B: B's words become the per-cycle slots
     uint32_t* slot = reinterpret_cast<uint32_t*>(B);
     if ((e = hipMemsetAsync(slot, 0xFF, p.n * 4, s)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_cx_basin, dim3(nb), dim3(kThreads), 0, s, (const uint64_t*)A, p.n, slot);
-    hipLaunchKernelGGL(k_cx_entry, dim3(nb), dim3(kThreads), 0, s, A, (const uint32_t*)nxt, p.n, slot, st);
-    hipLaunchKernelGGL(k_cx_final, dim3(nb), dim3(kThreads), 0, s, (const uint64_t*)A, (const uint32_t*)slot, p.n, d_ext);
+    hipLaunchKernelGGL(k_cx_basin, nb, dim3(kThreads), 0, s, (const uint64_t*)A, p.n, slot);
+    hipLaunchKernelGGL(k_cx_entry, nb, dim3(kThreads), 0, s, A, (const uint32_t*)nxt, p.n, slot, st);
+    hipLaunchKernelGGL(k_cx_final, nb, dim3(kThreads), 0, s, (const uint64_t*)A, (const uint32_t*)slot, p.n, d_ext);
     return hipGetLastError();
 }
 
@@ -458,21 +470,21 @@ hipError_t cx_segments(const CxPlan& p, const uint32_t* d_ext, const char* d_cel
     uint32_t* wr = reinterpret_cast<uint32_t*>(base + p.off_wr);
     uint32_t* cc = reinterpret_cast<uint32_t*>(base + p.off_cc);
     uint32_t* co = reinterpret_cast<uint32_t*>(base + p.off_co);
-    const unsigned nb = blocks(p.n);
+    const dim3 nb = lanes(p.n);
     SegGeom g{p.ny, p.nz, res, threshold};
-    hipLaunchKernelGGL(k_cx_key, dim3(nb), dim3(kThreads), 0, s, d_ext, d_cells, (uint64_t)stride, (uint64_t)occ_off, (uint64_t)obj_off,
+    hipLaunchKernelGGL(k_cx_key, nb, dim3(kThreads), 0, s, d_ext, d_cells, (uint64_t)stride, (uint64_t)occ_off, (uint64_t)obj_off,
                        p.n, key);
-    hipLaunchKernelGGL(k_cx_uf_init, dim3(nb), dim3(kThreads), 0, s, (const uint64_t*)key, p.n, g, d_labels);
-    hipLaunchKernelGGL(k_cx_uf_link, dim3(nb), dim3(kThreads), 0, s, (const uint64_t*)key, p.n, g, d_labels);
+    hipLaunchKernelGGL(k_cx_uf_init, nb, dim3(kThreads), 0, s, (const uint64_t*)key, p.n, g, d_labels);
+    hipLaunchKernelGGL(k_cx_uf_link, nb, dim3(kThreads), 0, s, (const uint64_t*)key, p.n, g, d_labels);
     hipLaunchKernelGGL(k_cx_flatten, dim3((unsigned)p.chunks), dim3(256), 0, s, d_labels, (const uint64_t*)key, p.n, rb, wr, cc);
     hipLaunchKernelGGL(k_cx_scan, dim3(1), dim3(kScanThreads), 0, s, (const uint32_t*)cc, co, p.chunks, st->count);
-    hipLaunchKernelGGL(k_cx_relabel, dim3(nb), dim3(256), 0, s, d_labels, (const uint64_t*)key, p.n, (const uint32_t*)rb,
+    hipLaunchKernelGGL(k_cx_relabel, nb, dim3(256), 0, s, d_labels, (const uint64_t*)key, p.n, (const uint32_t*)rb,
                        (const uint32_t*)wr, (const uint32_t*)co);
     return hipGetLastError();
 }
 
 hipError_t cx_combine(float* free_sdf, const float* named_sdf, uint64_t n, hipStream_t s) {
-    hipLaunchKernelGGL(k_cx_combine, dim3(blocks(n)), dim3(kThreads), 0, s, free_sdf, named_sdf, n);
+    hipLaunchKernelGGL(k_cx_combine, lanes(n), dim3(kThreads), 0, s, free_sdf, named_sdf, n);
     return hipGetLastError();
 }
 

@@ -53,7 +53,7 @@ inline uint32_t cx_row_sum(const uint32_t* row) {
 
 struct CxPlan {
     int64_t nx = 0, ny = 0, nz = 0;
-    uint64_t n = 0;                            // voxels (< 2^32 - 1)
+    uint64_t n = 0;                            // voxels (<= 2^32 - 3: indices stay below the doubling markers)
     uint64_t chunks = 0;                       // ceil(n / kCxChunk)
     // scratch layout (bytes): A u64 [n] | B u64 [n] | next u32 [n] | pad | stats | root bits u32 [chunks * 256] | word ranks
     // u32 [chunks * 256] | chunk counts u32 [chunks] | chunk offsets u32 [chunks]
@@ -61,7 +61,7 @@ struct CxPlan {
     size_t scratch_bytes = 0;
 };
 
-// nx, ny, nz positive, nx * ny * nz < 2^32 - 1 (checked by the caller)
+// nx, ny, nz positive, nx * ny * nz <= 2^32 - 3 (checked by the caller)
 CxPlan cx_plan(int64_t nx, int64_t ny, int64_t nz);
 
 // d_sdf: n floats [nx][ny][nz]; d_ext: n uint32 out.  Enqueued on `s`, with one synchronisation per doubling round (the host

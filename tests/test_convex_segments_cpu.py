@@ -1,7 +1,8 @@
 """Local extrema and convex segments without a GPU: the C++ restatement of the reference's ComputeLocalExtremaMap and
 UpdateConvexSegments (tests/convex_segments_restated.cpp) pinned to hand-derived answers, and a model of the GPU's scheme (pointer
 doubling with the cycle test, then the basin-minimum entry walk) checked against a literal memoised walk on random functional
-graphs.  tests/test_gpu_convex_segments.py compares the GPU with the same restatement."""
+graphs, once with tagged tuples for states and once word by word, markers and all, up to the largest grid the library accepts.
+tests/test_gpu_convex_segments.py compares the GPU with the same restatement."""
 import ctypes
 import math
 import os
@@ -212,6 +213,136 @@ def doubling_model(nxt):
     return [S[v][1] if S[v][0] == "T" else entry[S[v][1]] for v in range(n)], rounds
 
 
+# ---- the five extrema kernels restated on W-bit words ------------------------------------------------------------------------------
+# The accepted grid size, in one place: check_convex_args (sdfgpu.hip) refuses n >= 2^32 - 2, so the largest grid it accepts has
+# n = 2^32 - 3 voxels.  At word width W that is n = 2^W - CX_N_MARGIN; indices then stay below the three markers.
+CX_N_MARGIN = 3
+
+
+def cx_max_accepted_n(W):
+    return (1 << W) - CX_N_MARGIN
+
+
+def word_model(nxt, W, seed=0):
+    """k_cx_next, k_cx_round, k_cx_basin, k_cx_entry and k_cx_final (sdfgpu_convex.hip) on W-bit words: a state packs the high
+    word over the low one, kCxOff = kResTerm = 2^W - 1, kResCycle = 2^W - 2, kOnCycle = 2^W - 3, and `resolved` compares the low
+    word with kOnCycle, as the kernels do.  nxt[v] = v at a terminal, -1 for OFF.  Each round's lanes run one after another in a
+    seeded random order, with the in-place marker writes the kernel makes (one of the interleavings the device may take).  Every
+    index a kernel reads is checked against n, every walk against n steps.  Returns (extremum per node, -1 = OFF; rounds)."""
+    n = len(nxt)
+    assert n <= (1 << W) - 1
+    off = term = (1 << W) - 1
+    cyc, onc = (1 << W) - 2, (1 << W) - 3
+    mask = (1 << W) - 1
+
+    def pack(hi, lo):
+        return (hi << W) | lo
+
+    def hi(s):
+        return s >> W
+
+    def lo(s):
+        return s & mask
+
+    def resolved(s):
+        return lo(s) >= onc
+
+    def rd(buf, i):
+        assert 0 <= i < n, "read at %d, n = %d" % (i, n)
+        assert buf[i] is not None, "read of an unwritten word at %d" % i
+        return buf[i]
+
+    rng = random.Random(seed)
+    # k_cx_next
+    nx_w = [off if t == -1 else t for t in nxt]
+    A, B = [None] * n, [None] * n
+    for v in range(n):
+        t = nxt[v]
+        s = pack(v, term) if t == v else (pack(off, term) if t == -1 else pack(t, v))
+        A[v] = s
+        if resolved(s):
+            B[v] = s
+    # k_cx_round
+    rounds = 0
+    for k in range(W + 8):
+        src, dst = (B, A) if k & 1 else (A, B)
+        order = list(range(n))
+        rng.shuffle(order)
+        open_ = 0
+        for v in order:
+            s = rd(src, v)
+            if resolved(s):
+                continue
+            p = hi(s)
+            r, done = pack(off, term), True
+            if p != off:
+                sp = rd(src, p)
+                if resolved(sp):
+                    r = sp
+                else:
+                    c = lo(sp)
+                    d = nx_w[c] if 0 <= c < n else None
+                    assert d is not None, "next read at %d, n = %d" % (c, n)
+                    if d != off:
+                        sd = rd(src, d)
+                        if resolved(sd):
+                            r = sd
+                        elif lo(sd) == c:
+                            r = pack(c, cyc)
+                        else:
+                            done = False
+                            dst[v] = pack(hi(sp), min(lo(s), c))
+            if done:
+                dst[v] = r
+                src[v] = r
+            else:
+                open_ += 1
+        if open_ == 0:
+            rounds = k + 1
+            break
+    else:
+        raise AssertionError("no round left every node resolved")
+    # k_cx_basin (slot: B's words, all ones)
+    slot = [off] * n
+    for v in range(n):
+        s = A[v]
+        if lo(s) == cyc:
+            c = hi(s)
+            assert c < n
+            slot[c] = min(slot[c], v)
+    # k_cx_entry
+    for v in range(n):
+        s = A[v]
+        if lo(s) == cyc and hi(s) == v:
+            u, steps = v, 0
+            while True:
+                A[u] = pack(v, onc)
+                u = nx_w[u]
+                steps += 1
+                assert 0 <= u < n and steps <= n, "cycle walk from %d left the graph" % v
+                if u == v:
+                    break
+            w, steps = slot[v], 0
+            while True:
+                assert 0 <= w < n and steps <= n, "entry walk of cycle %d at %d" % (v, w)
+                if lo(A[w]) == onc:
+                    break
+                w = nx_w[w]
+                steps += 1
+            slot[v] = w
+    # k_cx_final
+    ext = []
+    for v in range(n):
+        s = A[v]
+        if lo(s) == term:
+            e = hi(s)
+        else:
+            assert hi(s) < n, "slot read at %d, n = %d" % (hi(s), n)
+            e = slot[hi(s)]
+        ext.append(-1 if e == off else e)
+    return ext, rounds
+
+
 def random_functional_graph(rng, n):
     kind = rng.random()
     out = []
@@ -253,6 +384,66 @@ def test_doubling_model_on_long_cycles_and_paths():
     path = [v + 1 for v in range(n - 1)] + [n - 1]
     got, rounds = doubling_model(path)
     assert got == [n - 1] * n and rounds <= 11
+
+
+def _last_steps_inward(rng, n):
+    """A random functional graph whose last node steps to another node of the graph (not a terminal, not OFF)."""
+    g = random_functional_graph(rng, n)
+    if n > 1:
+        g[n - 1] = rng.randrange(n - 1)
+    return g
+
+
+def _word_graphs(rng, W, n, count):
+    """Random graphs at n, half of them with a last node that steps inward, plus a path and a two-cycle through the last node."""
+    out = [_last_steps_inward(rng, n) if i % 2 else random_functional_graph(rng, n) for i in range(count)]
+    if n < 4:
+        return out
+    out.append([v + 1 for v in range(n - 1)] + [n - 2])                       # a path ending in the 2-cycle {n-2, n-1}
+    out.append([min(v + 1, n - 3) if v < n - 3 else (v + 1 if v < n - 1 else n - 3) for v in range(n)])   # ... {n-3, n-2, n-1}
+    return out
+
+
+@pytest.mark.parametrize("W", [6, 7, 8])
+def test_word_model_matches_the_memoised_walk_up_to_the_accepted_bound(W):
+    """The kernels' word arithmetic at every n up to the largest grid check_convex_args accepts, scaled to W bits: the same answer
+    as the literal walk, every read in bounds, every walk ended."""
+    rng = random.Random(1000 + W)
+    top = cx_max_accepted_n(W)
+    for n in [1, 2, 3, top - 2, top - 1, top] + [rng.randint(4, top) for _ in range(6)]:
+        for trial, nxt in enumerate(_word_graphs(rng, W, n, 100 if n == top else 6)):
+            got, rounds = word_model(nxt, W, seed=trial)
+            assert got == literal_walk(nxt), (W, n, trial, nxt)
+            assert rounds <= max(1, math.ceil(math.log2(max(n, 2)))) + 1, (W, n, rounds)
+
+
+@pytest.mark.parametrize("W", [6, 7, 8])
+def test_word_model_sees_the_marker_collision_one_past_the_bound(W):
+    """One voxel more than the bound: the last index equals kOnCycle, its round-0 state reads as resolved, and graphs whose last
+    node steps inward come back wrong -- the case the bound exists for (the tuple model above cannot see it)."""
+    rng = random.Random(2000 + W)
+    n = cx_max_accepted_n(W) + 1
+    assert n - 1 == (1 << W) - 3
+    wrong = 0
+    for trial in range(40):
+        nxt = _last_steps_inward(rng, n)
+        got, _ = word_model(nxt, W, seed=trial)
+        want = literal_walk(nxt)
+        if got != want:
+            wrong += 1
+            assert got[n - 1] != want[n - 1]                                   # the last node itself is always among them
+    assert wrong > 0
+    path = [v + 1 for v in range(n - 1)] + [n - 2]                             # (every node's orbit passes the last one)
+    got, _ = word_model(path, W)
+    assert got[n - 1] == -1 and literal_walk(path)[n - 1] == n - 2
+
+
+def test_word_model_agrees_with_the_tuple_model_on_small_graphs():
+    rng = random.Random(77)
+    for trial in range(400):
+        n = rng.randint(1, 40)
+        nxt = random_functional_graph(rng, n)
+        assert word_model(nxt, 8, seed=trial)[0] == doubling_model(nxt)[0] == literal_walk(nxt), (trial, nxt)
 
 
 # ---- the restatement on hand-derived fields -------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 """Local extrema and convex segments on the MI355X (sdfgpu_local_extrema*, sdfgpu_convex_segments_cells, SignedDistanceField::
 ComputeLocalExtremaMap, TaggedObjectCollisionMapGrid::UpdateConvexSegments): extremum triples, labels and K bit-equal to the C++
 restatement of the reference (tests/convex_segments_restated.cpp), through every entry point."""
+import ctypes
 import math
 
 import numpy as np
@@ -225,10 +226,15 @@ def test_refusals_allocate_nothing(gpu):
         with pytest.raises(capi.SdfGpuError) as ei:
             gpu.local_extrema(f, res)
         assert ei.value.code == -1
-    for shape in ((65535, 65537, 1), (1 << 16, 1 << 8, 1 << 8)):        # (2^32 - 1 and 2^32 voxels)
+    # 2^32 - 1 and 2^32 voxels; 2^32 - 2 = 2 (2^31 - 1), where the last index would equal the kOnCycle marker
+    qq = (ctypes.c_double * 8)(*capi.quaternion_and_inverse((1.0, 0.0, 0.0, 0.0)))
+    for shape in ((65535, 65537, 1), (1 << 16, 1 << 8, 1 << 8), (1, 2, 2147483647), (2147483647, 2, 1)):
         with pytest.raises(capi.SdfGpuError) as ei:
             gpu.local_extrema_device(1 << 20, shape, 1.0, 1 << 20)
         assert ei.value.code == -1
+        # the host entry point, with stand-in buffers: the size is refused before either is touched
+        assert gpu._lib.sdfgpu_local_extrema(gpu._h, 1 << 20, *shape, 1.0, qq, 1 << 20) == -1, shape
+        assert "2^32 - 2 voxels or more" in gpu._lib.sdfgpu_last_error(gpu._h).decode(), shape
     cells = _cells(np.zeros((2, 2, 2), np.float32), np.zeros((2, 2, 2), np.uint32))
     with pytest.raises(capi.SdfGpuError) as ei:
         gpu.convex_segments_cells(cells, (2, 2, 2), 0.0, 1.0, True)

@@ -5,11 +5,16 @@
   is admitted and must not run where it is not;
 * 1024^3, inside the gate, and 1024 x 1024 x 1025, one plane past it;
 * lines of 1025 .. 16384 voxels (never far-field) and the size refusal at 16385;
-* grids of more than 2^31 voxels (linear indices past 2^31) for the SDF and the connected components.
+* grids of more than 2^31 voxels (linear indices past 2^31) for the SDF and the connected components;
+* component topology past 2^31 node ids (512 slabs at 3072 x 1024 x 1024), past 2^32 vertices (one box of 2^32 - 2^17 voxels,
+  with and without a selection) and its refusal of more than 2^32 - 1 nodes (the all-even lattice: nothing allocated for them);
+* local extrema at n = 2^32 - 3, the largest grid check_convex_args accepts (its last index one below the kOnCycle marker), with
+  a basin and doubling windows across index 2^31.
 
 Every reference is independent of the library: the oracle's exact EDT, or a closed form in int64 whose float32 values come
-from a table computed on the host like the oracle computes them (sqrt and multiply in float64, one cast).  Each closed form
-is first checked against the oracle on a small grid of the same pattern.  All comparisons are bit for bit."""
+from a table computed on the host like the oracle computes them (sqrt and multiply in float64, one cast), or a closed form
+in int64 of the topology counters and extremum indices.  Each closed form is first checked against the oracle (or the C++
+restatements of the reference's topology and extrema) on a small grid of the same pattern.  All comparisons are bit for bit."""
 import math
 import time
 from concurrent.futures import ThreadPoolExecutor
@@ -683,3 +688,350 @@ def test_components_past_2_31_voxels(big):
     del bits, labels
     torch.cuda.empty_cache()
     print("\n[size-limits] components %s: %.3f s, K = %d; device memory in use %.2f GB" % ("x".join(map(str, shape)), dt, k, peak / 1e9))
+
+
+# ---- 5. component topology past 2^31 node ids and 2^32 vertices ------------------------------------------------------------------
+def _layer_labels(shape, device):
+    """Labels z // 2 (the slabs of a grid filled iff z mod 4 < 2, two voxels thick, alternately filled and free)."""
+    import torch
+    nx, ny, nz = shape
+    lz = (torch.arange(nz, dtype=torch.int32, device=device) // 2).view(1, 1, nz)
+    return lz.expand(nx, ny, nz).contiguous()
+
+
+def _layer_counts(shape):
+    """Closed form of the counters of _layer_labels (nz a multiple of 4): every label is a slab spanning x and y with another label
+    (or the outside) on each side -- nodes at its two z faces and at the x / y rim of its middle vertex plane; M3 = its 8 corners;
+    every other node has 4 exposed edges; one surface."""
+    nx, ny, nz = shape
+    assert nz % 4 == 0
+    per = [2 * (nx + 1) * (ny + 1) + 2 * (nx + ny), 8, 0, 0, 1]
+    return np.array([per] * (nz // 2), np.int64)
+
+
+def _box_counts(shape):
+    """Closed form of the counters of one label over the whole grid (label 1; row 0 empty): the boundary vertices, 8 corners."""
+    nx, ny, nz = shape
+    nodes = (nx + 1) * (ny + 1) * (nz + 1) - (nx - 1) * (ny - 1) * (nz - 1)
+    return np.array([[0] * 5, [nodes, 8, 0, 0, 1]], np.int64)
+
+
+def _even_lattice_nodes(shape):
+    """Closed form of the surface-vertex nodes of _even_lattice_labels: 8 per lattice voxel (each is a component of its own), and
+    one of the free component at every vertex except those whose in-grid cube is a lone lattice voxel (a corner of the vertex grid
+    on each axis that starts or, for an odd extent, ends with a lattice coordinate)."""
+    lattice = math.prod((n + 1) // 2 for n in shape)
+    lone = math.prod(1 + n % 2 for n in shape)
+    return 8 * lattice + math.prod(n + 1 for n in shape) - lone
+
+
+def _numpy_nodes(labels):
+    """Node count by the header's definition, independent of both restatements: (vertex, c) is a node iff the vertex's cube holds
+    a voxel of c with a face neighbour inside the cube whose label is not c (the outside is -1)."""
+    lab = np.pad(np.asarray(labels, np.int64), 1, constant_values=-1)
+    nx, ny, nz = labels.shape
+    cube = [lab[dx:dx + nx + 1, dy:dy + ny + 1, dz:dz + nz + 1] for dx in (0, 1) for dy in (0, 1) for dz in (0, 1)]
+    surface = []
+    for s in range(8):
+        nb = [cube[s ^ b] for b in (1, 2, 4)]
+        surface.append((cube[s] >= 0) & ((nb[0] != cube[s]) | (nb[1] != cube[s]) | (nb[2] != cube[s])))
+    total = 0
+    for s in range(8):
+        first = surface[s].copy()
+        for t in range(s):
+            first &= ~(surface[t] & (cube[t] == cube[s]))
+        total += int(first.sum())
+    return total
+
+
+def _tp_scratch_bytes(shape, max_label, select):
+    """tp_plan's scratch_bytes (sdfgpu_topology.hip), restated."""
+    nx, ny, nz = shape
+    chunk, align8 = 8192, (lambda b: (b + 7) & ~7)
+    nv = (nx + 1) * (ny + 1) * (nz + 1)
+    chunks = (nv + chunk - 1) // chunk
+    labels = max_label + 1
+    off_flags = align8(labels * 5 * 8) + 24                               # counters | TpStatus (24 bytes)
+    off_nm = align8(off_flags + (labels * 4 if select else 0))
+    return off_nm + chunks * chunk + chunks * (chunk // 8) * 4 + chunks * 4 * 2
+
+
+def test_topology_closed_forms_match_the_restatement():
+    """The three closed forms on small grids of the same patterns (odd and even extents, thin ones): every counter against
+    restated_counts, the node totals against a numpy count by the header's definition."""
+    from test_topology_cpu import holes_voids, restated_counts
+    for shape in ((5, 3, 8), (2, 7, 12), (1, 1, 4), (6, 4, 16), (3, 1, 8)):
+        lab = _layer_labels(shape, "cpu").numpy().view(np.uint32)
+        want = _layer_counts(shape)
+        assert np.array_equal(restated_counts(lab, max_label=shape[2] // 2 - 1), want), shape
+        assert _numpy_nodes(lab) == int(want[:, 0].sum()), shape
+        assert holes_voids(want) == {c: (0, 0) for c in range(shape[2] // 2)}
+    for shape in ((4, 8, 7), (1, 3, 4), (2, 2, 2), (4, 5, 6), (1, 1, 1)):
+        lab = np.ones(shape, np.uint32)
+        want = _box_counts(shape)
+        assert np.array_equal(restated_counts(lab, max_label=1), want), shape
+        assert _numpy_nodes(lab) == int(want[1, 0]), shape
+        assert holes_voids(want) == {1: (0, 0)}
+    for shape in ((6, 4, 8), (5, 3, 7), (4, 5, 2), (1, 3, 9), (7, 6, 5)):
+        lab = _even_lattice_labels(shape, 0, shape[0], "cpu").numpy().astype(np.uint32)
+        counts = restated_counts(lab)
+        assert int(counts[:, 0].sum()) == _even_lattice_nodes(shape) == _numpy_nodes(lab), shape
+    assert _even_lattice_nodes(BIG) == 8 * 3 * 2 ** 27 + 3073 * 1025 * 1025 - 1
+
+
+def _counts_device(ctx, labels, shape, max_label, select=None):
+    import torch
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    got = ctx.component_topology_device(labels.data_ptr(), shape, max_label, None if select is None else select.data_ptr(),
+                                        torch.cuda.current_stream().cuda_stream)
+    return got, time.perf_counter() - t0
+
+
+def test_topology_refuses_more_than_2_32_nodes(big):
+    """The all-even lattice at 3072 x 1024 x 1024 has about 6.4e9 surface-vertex nodes: refused with -1 after the counting pass,
+    the count in the message equal to the closed form, the node buffer never allocated (device memory grows by the scratch at
+    most).  The same handle then answers a small scene exactly."""
+    import torch
+    from test_components_cpu import restated_labels
+    from test_topology_cpu import SHAPES, restated_counts
+    from sdf_tools_amd.capi import SdfGpuError
+    shape = BIG
+    nx = shape[0]
+    dev = torch.device("cuda", 0)
+    torch.cuda.empty_cache()
+    labels = torch.empty(shape, dtype=torch.int32, device=dev)
+    for x0 in range(0, nx, 128):
+        labels[x0:x0 + 128] = _even_lattice_labels(shape, x0, min(nx, x0 + 128), dev).to(torch.int32)
+    max_label = 3 * 2 ** 27 + 1
+    nodes = _even_lattice_nodes(shape)
+    assert nodes > 2 ** 32 - 1
+    scratch = _tp_scratch_bytes(shape, max_label, False)
+    torch.cuda.synchronize()
+    base = _used_device_bytes()
+    t0 = time.perf_counter()
+    with pytest.raises(SdfGpuError) as ei:
+        big.component_topology_device(labels.data_ptr(), shape, max_label, None, torch.cuda.current_stream().cuda_stream)
+    dt = time.perf_counter() - t0
+    grew = _used_device_bytes() - base
+    msg = str(ei.value)
+    assert ei.value.code == -1, msg
+    assert ("%d surface-vertex nodes" % nodes) in msg, (nodes, msg)
+    assert grew <= scratch + (64 << 20), (grew, scratch, nodes * 4)
+    del labels
+    torch.cuda.empty_cache()
+    m = SHAPES["cube_two_cavities"]()
+    lab, k = restated_labels(m)
+    d = torch.from_numpy(lab.astype(np.int32)).to(dev)
+    got, _ = _counts_device(big, d, m.shape, k)
+    assert np.array_equal(got, restated_counts(lab, max_label=k))
+    print("\n[size-limits] topology refusal %s: %d nodes, %.3f s, device memory grew %.2f GB (scratch %.2f GB)" % (
+        "x".join(map(str, shape)), nodes, dt, grew / 1e9, scratch / 1e9))
+
+
+def test_topology_layers_past_2_31_node_ids(big):
+    """3072 x 1024 x 1024 labelled z // 2: 512 slabs whose surfaces span the whole vertex range, about 3.23e9 nodes, so the
+    union-find joins node ids above 2^31 with ids below it.  Every counter against the closed form; (holes, voids) = (0, 0)."""
+    import torch
+    from test_topology_cpu import holes_voids
+    shape = BIG
+    dev = torch.device("cuda", 0)
+    torch.cuda.empty_cache()
+    base = _used_device_bytes()
+    labels = _layer_labels(shape, dev)
+    want = _layer_counts(shape)
+    nodes = int(want[:, 0].sum())
+    assert 2 ** 31 < nodes < 2 ** 32 - 1, nodes
+    got, dt = _counts_device(big, labels, shape, shape[2] // 2 - 1)
+    peak = _used_device_bytes() - base
+    assert np.array_equal(got, want), (got[:3], want[:3], np.argwhere(got != want)[:5])
+    assert holes_voids(got) == {c: (0, 0) for c in range(shape[2] // 2)}
+    del labels
+    torch.cuda.empty_cache()
+    print("\n[size-limits] topology layers %s: %d nodes, %.3f s; device memory in use %.2f GB" % (
+        "x".join(map(str, shape)), nodes, dt, peak / 1e9))
+
+
+def test_topology_one_box_past_2_32_vertices(big):
+    """(4, 32768, 32767): n = 2^32 - 2^17 voxels, 5.37e9 vertices (the 64-bit branch of vertex_of, vertex ids past 2^32), one
+    label from the components of an all-filled bit field (K = 1) and 2,147,942,394 nodes on one surface.  Without a selection
+    and with an all-ones one: the same counters, equal to the closed form."""
+    import torch
+    from test_topology_cpu import holes_voids
+    shape = (4, 32768, 32767)
+    n = math.prod(shape)
+    assert n == 2 ** 32 - 2 ** 17 and math.prod(s + 1 for s in shape) > 2 ** 32
+    dev = torch.device("cuda", 0)
+    torch.cuda.empty_cache()
+    base = _used_device_bytes()
+    bits = torch.full(((n + 31) // 32,), -1, dtype=torch.int32, device=dev)
+    labels = torch.zeros(n, dtype=torch.int32, device=dev)
+    t0 = time.perf_counter()
+    k = big.components_bits_device(bits.data_ptr(), shape, labels.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    t_cc = time.perf_counter() - t0
+    assert k == 1, k
+    assert bool((labels == 1).all())
+    want = _box_counts(shape)
+    assert int(want[1, 0]) == 2147942394
+    got, t_all = _counts_device(big, labels, shape, 1)
+    assert np.array_equal(got, want), (got, want)
+    sel, t_sel = _counts_device(big, labels, shape, 1, bits)
+    assert np.array_equal(sel, got), (sel, got)
+    assert holes_voids(got) == {1: (0, 0)}
+    peak = _used_device_bytes() - base
+    del bits, labels
+    torch.cuda.empty_cache()
+    print("\n[size-limits] topology box %s: components %.3f s; %d nodes, %.3f s, selected %.3f s; device memory in use %.2f GB" % (
+        "x".join(map(str, shape)), t_cc, int(want[1, 0]), t_all, t_sel, peak / 1e9))
+
+
+# ---- 6. local extrema at the largest grid check_convex_args accepts -----------------------------------------------------------------
+CX_BIG = (9241, 464773, 1)                 # n = 2^32 - 3; index 2^31 is (4620, 232388, 0)
+CX_RAMP = (4620, 4100, 1101)               # (split, left, right) of cx_profile
+
+
+def cx_profile(nx, split, left, right):
+    """An x profile (integers >= 0, exact in float32): blocks 0 1 1 0 from x = 0 up to a = split - left, each block a 2-cycle
+    entered from its first voxel; a ramp rising over `left` steps from a to the 2-cycle {split - 1, split}; a ramp falling over
+    `right` steps after it; blocks 0 1 1 0 anchored at the last x, so that the last plane steps to x - 1 into its block's 2-cycle."""
+    a, b = split - left, split + right
+    assert a % 4 == 0 and (nx - 1 - b) % 4 == 3 and right <= left
+    x = np.arange(nx)
+    blk = np.array([0, 1, 1, 0])
+    f = np.empty(nx, np.int64)
+    f[:a] = blk[x[:a] % 4]
+    f[a:split] = left + 1 - (split - 1 - x[a:split])
+    f[split:b] = left + 1 - (x[split:b] - split)
+    f[b:] = blk[(nx - 1 - x[b:]) % 4]
+    return f.astype(np.float32)
+
+
+def _profile_next(f):
+    """next() along x of a field that depends on x alone: the sign of f(x + 1) - f(x - 1), one-sided at both ends."""
+    fi = f.astype(np.int64)
+    nx = len(f)
+    out = []
+    for x in range(nx):
+        d = fi[min(nx - 1, x + 1)] - fi[max(0, x - 1)]
+        out.append(x + 1 if d > 0 else (x - 1 if d < 0 else x))
+    return out
+
+
+def _cx_scratch_bytes(n):
+    """cx_plan's scratch_bytes (sdfgpu_convex.hip), restated: A, B (u64), next (u32), CxStats, root bits, word ranks, chunk
+    counts and offsets."""
+    chunks = (n + 8191) // 8192
+    stats = (40 * 64 * 32 + 64 * 32 + 3 * 32) * 4
+    off_stats = (20 * n + 7) & ~7
+    return off_stats + ((stats + 7) & ~7) + 2 * chunks * 256 * 4 + 2 * chunks * 4
+
+
+def cx_profile_walk(f):
+    """The literal walk along the profile (every step an integer difference of at least 1, far above the step threshold at
+    res = 1) and, per cycle, the steps from its basin minimum to its entry: (extremum x or -1 per x, cycles, longest entry walk)."""
+    from test_convex_segments_cpu import literal_walk
+    nx = len(f)
+    nxt = _profile_next(f)
+    E = literal_walk(nxt)
+    cycles, longest = 0, 0
+    for x in range(nx):
+        if nxt[x] != x and nxt[nxt[x]] == x and x < nxt[x]:
+            cycles += 1
+            b = min(u for u in range(nx) if E[u] in (x, nxt[x]))
+            steps, u = 0, b
+            while u not in (x, nxt[x]):
+                u, steps = nxt[u], steps + 1
+            longest = max(longest, steps)
+    return np.array(E, np.int64), cycles, longest
+
+
+def cx_expected(E, ny, x0, x1, device):
+    """Closed form of the extremum indices of x planes [x0, x1): E[x] ny + y (int64; every walk stays in its row)."""
+    import torch
+    e = torch.as_tensor(E[x0:x1], device=device).view(-1, 1)
+    return torch.where(e < 0, torch.full_like(e, 0xFFFFFFFF), e * ny + torch.arange(ny, dtype=torch.int64, device=device).view(1, -1))
+
+
+def test_extrema_profile_closed_form_matches_the_restatement():
+    """The profile's closed form on small grids whose x pattern matches CX_BIG's at both ends (blocks from x = 0, the two ramps,
+    blocks ending at the last plane): the extremum locations against restated_extrema, the cycles and the longest entry walk
+    against the walk of the grid's own next()."""
+    from test_convex_segments_cpu import _cycles, cx_max_accepted_n, literal_walk, next_map, restated_extrema
+    assert math.prod(CX_BIG) == cx_max_accepted_n(32) == 2 ** 32 - 3
+    assert 4620 * CX_BIG[1] + 232388 == 2 ** 31
+    for nx, ny, ramp in ((37, 5, (24, 12, 9)), (45, 3, (24, 12, 9)), (41, 1, (20, 12, 9)), (61, 4, (32, 16, 13))):
+        f = cx_profile(nx, *ramp)
+        field = np.broadcast_to(f.reshape(nx, 1, 1), (nx, ny, 1)).copy()
+        E, cycles, longest = cx_profile_walk(f)
+        idx = cx_expected(E, ny, 0, nx, "cpu").numpy().reshape(nx, ny, 1)
+        got = restated_extrema(field, 1.0)
+        assert np.array_equal(capi.extremum_locations(idx.astype(np.uint32), field.shape, 1.0), got), (nx, ny, ramp)
+        nxt = next_map(field, 1.0)
+        assert nxt[-1] == (nx - 2) * ny + ny - 1                            # the last voxel steps to x - 1
+        assert len(_cycles(nxt)) == cycles * ny == (ramp[0] - ramp[1]) // 4 * ny + (nx - ramp[0] - ramp[2]) // 4 * ny + ny
+        assert longest == ramp[1]
+        assert np.array_equal(np.array(literal_walk(nxt)).reshape(nx, ny, 1), idx)
+    f = cx_profile(CX_BIG[0], *CX_RAMP)
+    assert f.min() >= 0 and f.max() < 2 ** 24
+    E, cycles, longest = cx_profile_walk(f)
+    ny = CX_BIG[1]
+    assert E[4620] == E[4617] == 4619 and E[519] == 4619 and E[4620 + 1100] == 4619        # one basin across index 2^31
+    assert E[-1] == CX_BIG[0] - 3 and E[-1] * ny + ny - 1 < 2 ** 32 - 3
+    assert cycles == 1011 and longest == 4100
+
+
+def test_extrema_at_the_largest_accepted_grid(big):
+    """n = 2^32 - 3, the largest grid check_convex_args accepts: the last index, 2^32 - 4, is one below kOnCycle, and the last voxel
+    steps inward.  A basin of 5202 x planes around index 2^31 (entered at x = 4619 from its minimum at x = 519; a signed minimum
+    would pick x = 4620 or 4621 and enter at x = 4620), reached over up to 4100 steps (at least 10 doubling rounds whose windows
+    span both sides), blocks with 2-cycles elsewhere.  Past n = 2^32 - 256 a 1-D launch of one lane per voxel would need 2^32
+    work-items, which the runtime refuses: the kernels' 2-D grid is exercised here too.  All 4.29e9 extremum indices against the
+    closed form, bit for bit, and the doubling statistics."""
+    import torch
+    from test_convex_segments_cpu import word_model
+    shape, res = CX_BIG, 1.0
+    nx, ny, _ = shape
+    n = math.prod(shape)
+    f = cx_profile(nx, *CX_RAMP)
+    E, cycles, longest = cx_profile_walk(f)
+    dev = torch.device("cuda", 0)
+    torch.cuda.empty_cache()
+    need = 8 * n + _cx_scratch_bytes(n) + (4 << 30)                        # field, indices, scratch, the comparison's chunks
+    free, _ = torch.cuda.mem_get_info()
+    assert free >= need, "local extrema at 2^32 - 3 voxels needs about %.1f GB of device memory, %.1f GB are free" % (need / 1e9, free / 1e9)
+    base = _used_device_bytes()
+    field = torch.empty(shape, dtype=torch.float32, device=dev)
+    ft = torch.from_numpy(f).to(dev)
+    for x0 in range(0, nx, 512):
+        field[x0:x0 + 512] = ft[x0:x0 + 512].view(-1, 1, 1).expand(-1, ny, 1)
+    ext = torch.empty(shape, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    big.local_extrema_device(field.data_ptr(), shape, res, ext.data_ptr(), stream=torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    peak = _used_device_bytes() - base
+    info = big.convex_last_info()
+    del field
+    for x0 in range(0, nx, 128):
+        x1 = min(nx, x0 + 128)
+        want = cx_expected(E, ny, x0, x1, dev)
+        got = ext[x0:x1, :, 0].to(torch.int64) & 0xFFFFFFFF
+        eq = got == want
+        if not bool(eq.all()):
+            bad = (~eq).nonzero()[:3].tolist()
+            raise AssertionError("x chunk %d: %d extrema differ, first %s got %s want %s" % (
+                x0, int((~eq).sum()), [[b[0] + x0, b[1]] for b in bad], [int(got[tuple(b)]) for b in bad],
+                [int(want[tuple(b)]) for b in bad]))
+        del want, got, eq
+    del ext
+    torch.cuda.empty_cache()
+    line_rounds = word_model([int(v) for v in _profile_next(f)], 32)[1]
+    assert info["cycles"] == cycles * ny, (info, cycles * ny)
+    assert info["longest_cycle"] == 2 and info["longest_entry"] == longest, info
+    assert 10 <= info["rounds"] <= math.ceil(math.log2(n)) + 1, info
+    print("\n[size-limits] extrema %s (n = 2^32 - 3): %.3f s, %d rounds (one row alone in the word model: %d), %d cycles, "
+          "longest entry %d; device memory in use %.2f GB" % ("x".join(map(str, shape)), dt, info["rounds"], line_rounds,
+                                                               info["cycles"], info["longest_entry"], peak / 1e9))
+
