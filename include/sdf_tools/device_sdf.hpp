@@ -6,7 +6,8 @@
 // sdfgpu_build (~10 ms of PCIe against 0.14 - 1.5 ms of kernels) before the first query.  This class is the other
 // shape of the same API: ExtractSignedDistanceFieldDevice (sdf_generation.hpp / CollisionMapGrid) leaves the field on the
 // MI355X, EstimateDistanceBatch / GetGradientBatch answer n points with ONE kernel (sdfgpu_query_points: one lane per
-// point, the reference's double arithmetic), and Host() downloads the field lazily, once, for callers that do want the
+// point, the reference's double arithmetic), ProjectBatch walks n points out of collision in one kernel (sdfgpu_project_points),
+// and Host() downloads the field lazily, once, for callers that do want the
 // reference's container (GetValue*, serialisation, per-point calls).
 //
 // Ownership (round 5): the device memory belongs to the libsdfgpu context of the thread that built the field,
@@ -125,6 +126,48 @@ public:
         for (size_t i = 0; i < out.size(); ++i)
             if (flags[i] & 2u) out[i] = std::vector<double>{grad[3 * i], grad[3 * i + 1], grad[3 * i + 2]};
         return out;
+    }
+
+    // n world-frame points (n x 3 doubles) -> what n calls of SignedDistanceField::ProjectCounted4d return (the counted form of
+    // ProjectOutOfCollisionToMinimumDistance3d, or of ProjectIntoValidVolumeToMinimumDistance3d with into_valid_volume_only), from
+    // one kernel (sdfgpu_project_points, include/sdfgpu.h "Projection"):
+    //   out_points[3 n]  world-frame results (a failed walk keeps the last location it reached; a refused point its input)
+    //   out_status[n]    SDFGPU_PROJECT_*
+    //   out_steps[n]     steps taken
+    // out_status and out_steps may be null.  max_steps = 0: the library default (sdfgpu_project_step_limit).
+    void ProjectBatch(const double* points_xyz, const int64_t n, const double minimum_distance, const double stepsize_multiplier,
+                      const bool into_valid_volume_only, const int max_steps, double* out_points, uint8_t* out_status,
+                      int32_t* out_steps) const {
+        if (!d_sdf_) throw std::runtime_error("DeviceSignedDistanceField is not initialized");
+        double w2g[12], g2w[12];
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 4; ++c) { w2g[r * 4 + c] = inverse_origin_.matrix()(r, c); g2w[r * 4 + c] = origin_.matrix()(r, c); }
+        const std::lock_guard<std::mutex> lock(ctx_->mutex);
+        sdf_generation::ThrowOnStatus(handle_, sdfgpu_project_points(handle_, d_sdf_, nx_, ny_, nz_, resolution_, w2g, g2w, minimum_distance,
+                                                                     stepsize_multiplier, max_steps,
+                                                                     into_valid_volume_only ? SDFGPU_PROJECT_INTO_VALID_VOLUME
+                                                                                            : SDFGPU_PROJECT_OUT_OF_COLLISION,
+                                                                     points_xyz, n, out_points, out_status, out_steps));
+    }
+    // Reference-shaped: one location per input like ProjectOutOfCollisionToMinimumDistance3d, plus the statuses (a location
+    // is the reference's answer only where its status is SDFGPU_PROJECT_CONVERGED; elsewhere the reference throws).
+    std::vector<Eigen::Vector3d> ProjectOutOfCollisionToMinimumDistanceBatch(const std::vector<Eigen::Vector3d>& locations,
+                                                                             const double minimum_distance,
+                                                                             std::vector<uint8_t>* statuses = nullptr,
+                                                                             const double stepsize_multiplier = 1.0 / 8.0) const {
+        const std::vector<double> pts = Flatten(locations);
+        std::vector<double> out(pts.size());
+        std::vector<uint8_t> st(locations.size());
+        ProjectBatch(pts.data(), (int64_t)locations.size(), minimum_distance, stepsize_multiplier, false, 0, out.data(), st.data(), nullptr);
+        std::vector<Eigen::Vector3d> r(locations.size());
+        for (size_t i = 0; i < r.size(); ++i) r[i] = Eigen::Vector3d(out[3 * i], out[3 * i + 1], out[3 * i + 2]);
+        if (statuses) *statuses = std::move(st);
+        return r;
+    }
+    std::vector<Eigen::Vector3d> ProjectOutOfCollisionBatch(const std::vector<Eigen::Vector3d>& locations,
+                                                            std::vector<uint8_t>* statuses = nullptr,
+                                                            const double stepsize_multiplier = 1.0 / 8.0) const {
+        return ProjectOutOfCollisionToMinimumDistanceBatch(locations, 0.0, statuses, stepsize_multiplier);
     }
 
     // The reference's container, downloaded on first use (and again after DevicePointer() handed out write access).

@@ -33,6 +33,15 @@ public:
     VecNd operator*(double s) const { VecNd r; for (int i = 0; i < N; i++) r.v_[i] = v_[i] * s; return r; }
     double dot(const VecNd& o) const { double s = 0; for (int i = 0; i < N; i++) s += v_[i] * o.v_[i]; return s; }
     double norm() const { return std::sqrt(dot(*this)); }
+    // Eigen's MatrixBase::normalized(): each component divided by the norm (a division, not a product with its inverse); a
+    // vector whose squared norm is not positive comes back unchanged.
+    VecNd normalized() const {
+        const double z = dot(*this);
+        if (!(z > 0.0)) return *this;
+        const double n = std::sqrt(z);
+        VecNd r; for (int i = 0; i < N; i++) r.v_[i] = v_[i] / n; return r;
+    }
+    VecNd& operator+=(const VecNd& o) { for (int i = 0; i < N; i++) v_[i] = v_[i] + o.v_[i]; return *this; }
     const double* data() const { return v_.data(); }
 private:
     std::array<double, N> v_;

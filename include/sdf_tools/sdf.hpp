@@ -2,8 +2,9 @@
 // of sdf_tools::SignedDistanceField (reference include/sdf_tools/sdf.hpp) that the hot path and the
 // pysdf_tools surface use: constructors (:34-81), lock-guarded SetValue (:236-264), GetGradient /
 // GetGridAlignedGradient / GetFullGradient (:341-526), EstimateDistance (:699-961), serialisation
-// and file / message forms (src/sdf_tools/sdf.cpp:213-502), and the local extrema map (sdf.cpp:23-207, on the GPU).  Out of
-// scope here: projection out of collision, AutoDiff gradients, RViz export.
+// and file / message forms (src/sdf_tools/sdf.cpp:213-502), the local extrema map (sdf.cpp:23-207, on the GPU) and projection
+// out of collision / into the valid volume (:996-1190; batched on the GPU through DeviceSignedDistanceField::ProjectBatch).  Out
+// of scope here: AutoDiff gradients, RViz export.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -317,6 +318,158 @@ public:
     std::pair<double, bool> EstimateDistance(const double x, const double y, const double z) const {
         return EstimateDistance4d(Eigen::Vector4d(x, y, z, 1.0));
     }
+
+    // ---- projection out of collision / into the valid volume (:996-1190) ----------------------------------------------------
+    // One counted walk is the core of every member below and the yardstick of the GPU (sdfgpu_project_points, include/sdfgpu.h
+    // "Projection"): its arithmetic order IS the specification -- eigen_lite's left-to-right sums, no fused multiply-add (the
+    // in-tree builds pass -ffp-contract=off or target no FMA).  Byte equality with real Eigen is UNVERIFIED: Eigen is not
+    // installed here and its vectorised norm() may sum in another order.
+    // Two deviations from the reference, which loops without a bound and casts NaN coordinates to int64:
+    //   - a walk stops after `max_steps` steps (0 = the library default, sdfgpu_project_step_limit): the reference-named members
+    //     throw std::runtime_error naming the limit, the counted walk reports SDFGPU_PROJECT_STEP_LIMIT;
+    //   - a NaN or infinite coordinate is refused: std::invalid_argument, or SDFGPU_PROJECT_NON_FINITE.
+    struct ProjectionResult {
+        Eigen::Vector4d location;                                // world frame (grid frame from the GridFrame core)
+        uint8_t status;                                          // SDFGPU_PROJECT_*
+        int32_t steps;
+    };
+
+    // The step limit a walk with these arguments uses; std::invalid_argument for a step that is not positive and finite or a
+    // negative max_steps.
+    int ProjectionStepLimit(const double stepsize_multiplier, const int max_steps = 0) const {
+        int limit = 0;
+        if (sdfgpu_project_step_limit(GetNumXCells(), GetNumYCells(), GetNumZCells(), stepsize_multiplier, max_steps, &limit) != SDFGPU_OK)
+            throw std::invalid_argument("projection: stepsize_multiplier must be positive and finite and max_steps >= 0");
+        return limit;
+    }
+
+    // ProjectOutOfCollisionToMinimumDistanceGridFrame (:1071-1122) with the walk counted and bounded.  A failed walk keeps the
+    // last location it reached.
+    ProjectionResult ProjectOutOfCollisionToMinimumDistanceGridFrameCounted(const Eigen::Vector4d& grid_frame_location,
+                                                                           const double minimum_distance,
+                                                                           const double stepsize_multiplier, const int step_limit) const {
+        ProjectionResult r{grid_frame_location, (uint8_t)SDFGPU_PROJECT_CONVERGED, 0};
+        Eigen::Vector4d& p = r.location;
+        const double minimum_distance_with_margin = minimum_distance + GetResolution() * stepsize_multiplier * 1e-4;
+        const double max_stepsize = GetResolution() * stepsize_multiplier;
+        GRID_INDEX index;
+        if (!GridFrameCell(p, index)) { r.status = SDFGPU_PROJECT_LEFT_GRID; return r; }
+        double sdf_dist = EstimateFromNeighborsGridFrame(p, index.x, index.y, index.z);
+        while (sdf_dist <= minimum_distance) {
+            if (r.steps >= step_limit) { r.status = SDFGPU_PROJECT_STEP_LIMIT; return r; }
+            const std::vector<double> gradient = GetGridAlignedGradient(index.x, index.y, index.z, true);
+            if (gradient.size() != 3) { r.status = SDFGPU_PROJECT_NO_GRADIENT; return r; }
+            const Eigen::Vector4d grad_vector(gradient[0], gradient[1], gradient[2], 0.0);
+            if (!(grad_vector.norm() > GetResolution() * 0.25)) { r.status = SDFGPU_PROJECT_FLAT_GRADIENT; return r; }
+            const double step_distance = std::min(max_stepsize, minimum_distance_with_margin - sdf_dist);
+            p += grad_vector.normalized() * step_distance;
+            r.steps++;
+            if (!GridFrameCell(p, index)) { r.status = SDFGPU_PROJECT_LEFT_GRID; return r; }
+            sdf_dist = EstimateFromNeighborsGridFrame(p, index.x, index.y, index.z);
+        }
+        return r;
+    }
+
+    // The whole world-frame call, counted: ProjectOutOfCollisionToMinimumDistance4d (:1041-1069) or, with
+    // into_valid_volume_only, ProjectIntoValidVolumeToMinimumDistance4d (:1158-1190).  Never throws for a point; throws
+    // std::invalid_argument for bad arguments (ProjectionStepLimit).
+    ProjectionResult ProjectCounted4d(const Eigen::Vector4d& location, const double minimum_distance, const double stepsize_multiplier,
+                                      const bool into_valid_volume_only, const int max_steps = 0) const {
+        const int step_limit = ProjectionStepLimit(stepsize_multiplier, max_steps);
+        if (!std::isfinite(location(0)) || !std::isfinite(location(1)) || !std::isfinite(location(2)))
+            return ProjectionResult{location, (uint8_t)SDFGPU_PROJECT_NON_FINITE, 0};
+        if (into_valid_volume_only)
+            return ProjectionResult{ClampIntoValidVolume(location, minimum_distance), (uint8_t)SDFGPU_PROJECT_CONVERGED, 0};
+        GRID_INDEX index;
+        const Eigen::Vector4d start = GridFrameCell(inverse_origin_transform_ * location, index) ? location
+                                                                                               : ClampIntoValidVolume(location, 0.0);
+        ProjectionResult r = ProjectOutOfCollisionToMinimumDistanceGridFrameCounted(inverse_origin_transform_ * start, minimum_distance,
+                                                                                   stepsize_multiplier, step_limit);
+        r.location = GetOriginTransform() * r.location;
+        return r;
+    }
+
+    // reference-named members (:996-1190); max_steps is an addition with a default (see above)
+    Eigen::Vector4d ProjectOutOfCollisionToMinimumDistance4d(const Eigen::Vector4d& location, const double minimum_distance,
+                                                             const double stepsize_multiplier = 1.0 / 8.0, const int max_steps = 0) const {
+        return ThrowOnProjectionStatus(ProjectCounted4d(location, minimum_distance, stepsize_multiplier, false, max_steps));
+    }
+    Eigen::Vector3d ProjectOutOfCollisionToMinimumDistance(const double x, const double y, const double z, const double minimum_distance,
+                                                           const double stepsize_multiplier = 1.0 / 8.0, const int max_steps = 0) const {
+        return Head3(ProjectOutOfCollisionToMinimumDistance4d(Eigen::Vector4d(x, y, z, 1.0), minimum_distance, stepsize_multiplier, max_steps));
+    }
+    Eigen::Vector3d ProjectOutOfCollisionToMinimumDistance3d(const Eigen::Vector3d& location, const double minimum_distance,
+                                                             const double stepsize_multiplier = 1.0 / 8.0, const int max_steps = 0) const {
+        return ProjectOutOfCollisionToMinimumDistance(location.x(), location.y(), location.z(), minimum_distance, stepsize_multiplier, max_steps);
+    }
+    Eigen::Vector4d ProjectOutOfCollision4d(const Eigen::Vector4d& location, const double stepsize_multiplier = 1.0 / 8.0,
+                                            const int max_steps = 0) const {
+        return ProjectOutOfCollisionToMinimumDistance4d(location, 0.0, stepsize_multiplier, max_steps);
+    }
+    Eigen::Vector3d ProjectOutOfCollision(const double x, const double y, const double z, const double stepsize_multiplier = 1.0 / 8.0,
+                                          const int max_steps = 0) const {
+        return Head3(ProjectOutOfCollision4d(Eigen::Vector4d(x, y, z, 1.0), stepsize_multiplier, max_steps));
+    }
+    Eigen::Vector3d ProjectOutOfCollision3d(const Eigen::Vector3d& location, const double stepsize_multiplier = 1.0 / 8.0,
+                                            const int max_steps = 0) const {
+        return ProjectOutOfCollision(location.x(), location.y(), location.z(), stepsize_multiplier, max_steps);
+    }
+    Eigen::Vector4d ProjectIntoValidVolumeToMinimumDistance4d(const Eigen::Vector4d& location, const double minimum_distance) const {
+        if (!std::isfinite(location(0)) || !std::isfinite(location(1)) || !std::isfinite(location(2)))
+            throw std::invalid_argument("Cannot project a non-finite location");
+        return ClampIntoValidVolume(location, minimum_distance);
+    }
+    Eigen::Vector4d ProjectIntoValidVolume4d(const Eigen::Vector4d& location) const {
+        return ProjectIntoValidVolumeToMinimumDistance4d(location, 0.0);
+    }
+    Eigen::Vector3d ProjectIntoValidVolumeToMinimumDistance(const double x, const double y, const double z, const double minimum_distance) const {
+        return Head3(ProjectIntoValidVolumeToMinimumDistance4d(Eigen::Vector4d(x, y, z, 1.0), minimum_distance));
+    }
+    Eigen::Vector3d ProjectIntoValidVolumeToMinimumDistance3d(const Eigen::Vector3d& location, const double minimum_distance) const {
+        return ProjectIntoValidVolumeToMinimumDistance(location.x(), location.y(), location.z(), minimum_distance);
+    }
+    Eigen::Vector3d ProjectIntoValidVolume(const double x, const double y, const double z) const {
+        return Head3(ProjectIntoValidVolume4d(Eigen::Vector4d(x, y, z, 1.0)));
+    }
+    Eigen::Vector3d ProjectIntoValidVolume3d(const Eigen::Vector3d& location) const {
+        return ProjectIntoValidVolume(location.x(), location.y(), location.z());
+    }
+
+protected:
+    static Eigen::Vector3d Head3(const Eigen::Vector4d& v) { return Eigen::Vector3d(v(0), v(1), v(2)); }
+    // PointInFrameToGridIndex4d + IndexInBounds, decided on the floored doubles before any cast to int64 (the reference casts
+    // first, which is undefined for coordinates beyond int64; for every other input the answer is the same).
+    bool GridFrameCell(const Eigen::Vector4d& p, GRID_INDEX& index) const {
+        const double fx = std::floor(p(0) * inv_cell_x_size_), fy = std::floor(p(1) * inv_cell_y_size_),
+                     fz = std::floor(p(2) * inv_cell_z_size_);
+        if (!(fx >= 0.0 && fy >= 0.0 && fz >= 0.0 && fx < (double)GetNumXCells() && fy < (double)GetNumYCells() && fz < (double)GetNumZCells()))
+            return false;
+        index = GRID_INDEX((int64_t)fx, (int64_t)fy, (int64_t)fz);
+        return true;
+    }
+    // ProjectIntoValidVolumeToMinimumDistance4d's body (:1158-1190): the input itself when no coordinate moves
+    Eigen::Vector4d ClampIntoValidVolume(const Eigen::Vector4d& location, const double minimum_distance) const {
+        const Eigen::Vector4d g = inverse_origin_transform_ * location;
+        const double dist_margin = minimum_distance + GetResolution() * 1e-4;
+        const double x = std::min(x_size_ - dist_margin, std::max(dist_margin, g(0)));
+        const double y = std::min(y_size_ - dist_margin, std::max(dist_margin, g(1)));
+        const double z = std::min(z_size_ - dist_margin, std::max(dist_margin, g(2)));
+        if (x != g(0) || y != g(1) || z != g(2)) return GetOriginTransform() * Eigen::Vector4d(x, y, z, 1.0);
+        return location;
+    }
+    Eigen::Vector4d ThrowOnProjectionStatus(const ProjectionResult& r) const {
+        switch (r.status) {
+            case SDFGPU_PROJECT_CONVERGED: return r.location;
+            case SDFGPU_PROJECT_FLAT_GRADIENT: throw std::runtime_error("Encountered flat gradient - stuck");
+            case SDFGPU_PROJECT_NO_GRADIENT: throw std::runtime_error("Failed to compute gradient - out of SDF?");
+            case SDFGPU_PROJECT_LEFT_GRID: throw std::invalid_argument("Index out of bounds");
+            case SDFGPU_PROJECT_NON_FINITE: throw std::invalid_argument("Cannot project a non-finite location");
+            default:
+                throw std::runtime_error("Projection did not converge within the step limit of " + std::to_string(r.steps) + " steps");
+        }
+    }
+
+public:
 
     // ---- serialisation (src/sdf_tools/sdf.cpp:213-502) ------------------------------------------
     using FloatSerializer = std::function<uint64_t(const float&, std::vector<uint8_t>&)>;

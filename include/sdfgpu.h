@@ -481,6 +481,62 @@ int sdfgpu_convex_segments_cells(sdfgpu_handle h, void* cells, size_t cell_strid
 int sdfgpu_convex_last_info(sdfgpu_handle h, int* out_rounds, uint32_t* out_cycles, uint32_t* out_longest_cycle,
                             uint32_t* out_longest_entry);
 
+/* -------------------------------------------------------------------------
+ * Projection out of collision / into the valid volume (SignedDistanceField::ProjectOutOfCollision*,
+ * ProjectOutOfCollisionToMinimumDistance*, ProjectIntoValidVolume*, ProjectIntoValidVolumeToMinimumDistance*; reference
+ * include/sdf_tools/sdf.hpp:996-1190), one lane per point, all arithmetic in double without fused multiply-add.
+ * For a world-frame point p, with res the cell size, W the world -> grid transform and G the grid -> world transform
+ * (each 12 host doubles, row-major 3x4, the full transform including the translation; both are required):
+ *   mode SDFGPU_PROJECT_OUT_OF_COLLISION:
+ *     1. if floor((W p) * (1 / res)) is outside the grid on some axis, clamp each grid coordinate c of W p into [m, size - m]
+ *        (m = res * 1e-4, size = cells * res, as min(size - m, max(m, c))); if any coordinate changed, p = G (clamped);
+ *     2. q = W p;  margin = minimum_distance + res * stepsize_multiplier * 1e-4;  max_step = res * stepsize_multiplier;
+ *     3. d = the trilinear estimate at q (sdfgpu_query_points' EstimateDistance) in the cell floor(q * (1 / res)); while
+ *        d <= minimum_distance: g = the grid-aligned gradient of that cell with edge gradients on; if |g| <= res * 0.25
+ *        (NaN included) the point is stuck (FLAT_GRADIENT); else q += (g / |g|) * min(max_step, margin - d) and d is
+ *        re-estimated; a cell outside the grid ends the walk (LEFT_GRID);
+ *     4. the result is G q -- also for a point that took no step (it comes back through both transforms).
+ *   mode SDFGPU_PROJECT_INTO_VALID_VOLUME: step 1 alone, always applied, with m = minimum_distance + res * 1e-4; a point
+ *     that no clamp changes comes back as the input bits.
+ *   Sums are evaluated left to right ((a + b) + c) + d as eigen_lite.hpp does; |g| = sqrt(((0 + gx gx) + gy gy) + gz gz).
+ * Two deviations from the reference (which has no bound and casts NaN coordinates to int64):
+ *   - every walk stops after max_steps steps (status STEP_LIMIT, the location reached so far is kept); max_steps = 0 takes the
+ *     library default 4 * ceil(sqrt(nx^2 + ny^2 + nz^2) / stepsize_multiplier) + 64, at most SDFGPU_PROJECT_MAX_STEPS_CEILING
+ *     (sdfgpu_project_step_limit computes it, for the host walk as well);
+ *   - a point with a NaN or infinite coordinate is refused (status NON_FINITE, the input is returned unchanged, 0 steps).
+ * Per point: d_out_points[3i..3i+2] the world-frame result (a failed walk keeps the last location it reached), d_out_status[i]
+ * one of SDFGPU_PROJECT_* below, d_out_steps[i] the steps taken.  status and steps may be NULL.  n = 0 is a no-op.
+ * Refused (SDFGPU_ERR_INVALID_ARGUMENT, with a message): null field, points or out_points (n > 0); non-positive dims; cells
+ * overflowing int64; resolution or stepsize_multiplier not positive and finite; max_steps < 0; an unknown mode; null W or G.
+ * Cell indices are int64 throughout (fields past 2^31 cells).
+ *   sdfgpu_project_points_device: device points and outputs, enqueued on `stream`.
+ *   sdfgpu_project_points: host points and outputs against a field in HBM; synchronous, on the device's null stream behind this
+ *       handle's last build (the threading note of sdfgpu_query_points applies: a field written by another producer on a
+ *       non-blocking stream must be complete before the call).
+ *   sdfgpu_project_step_limit: the step limit a call with these arguments uses (*out_limit).
+ * ------------------------------------------------------------------------- */
+#define SDFGPU_PROJECT_OUT_OF_COLLISION 0
+#define SDFGPU_PROJECT_INTO_VALID_VOLUME 1
+
+#define SDFGPU_PROJECT_CONVERGED 0      /* d > minimum_distance reached (or no walk asked for)                         */
+#define SDFGPU_PROJECT_FLAT_GRADIENT 1  /* |g| <= res / 4 or NaN: "Encountered flat gradient - stuck"                  */
+#define SDFGPU_PROJECT_NO_GRADIENT 2    /* the gradient was empty: "Failed to compute gradient - out of SDF?"          */
+#define SDFGPU_PROJECT_LEFT_GRID 3      /* the walk reached a cell outside the grid: "Index out of bounds"             */
+#define SDFGPU_PROJECT_STEP_LIMIT 4     /* max_steps steps taken without converging                                    */
+#define SDFGPU_PROJECT_NON_FINITE 5     /* a NaN or infinite input coordinate                                          */
+
+#define SDFGPU_PROJECT_MAX_STEPS_CEILING 1048576
+
+int sdfgpu_project_step_limit(int64_t nx, int64_t ny, int64_t nz, double stepsize_multiplier, int max_steps, int* out_limit);
+int sdfgpu_project_points_device(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                                 const double world_to_grid[12], const double grid_to_world[12], double minimum_distance,
+                                 double stepsize_multiplier, int max_steps, int mode, const double* d_points, int64_t n_points,
+                                 double* d_out_points, uint8_t* d_out_status, int32_t* d_out_steps, void* stream);
+int sdfgpu_project_points(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                          const double world_to_grid[12], const double grid_to_world[12], double minimum_distance,
+                          double stepsize_multiplier, int max_steps, int mode, const double* points, int64_t n_points,
+                          double* out_points, uint8_t* out_status, int32_t* out_steps);
+
 /* Red zones (round 6).  With SDFGPU_REDZONE=1 in the environment when sdfgpu_create runs -- or after
  * sdfgpu_set_option(h, "redzone", 1) -- every device allocation of the library (scratch fields, status block, extrema slots,
  * staging buffers, sdfgpu_device_malloc memory) carries 4 KiB of canary bytes in front and behind, and every entry point that

@@ -31,7 +31,13 @@ EXPORTS = [
     "sdfgpu_components_bits_device", "sdfgpu_components", "sdfgpu_components_cells",
     "sdfgpu_component_topology_device", "sdfgpu_component_topology", "sdfgpu_component_topology_cells",
     "sdfgpu_local_extrema_device", "sdfgpu_local_extrema", "sdfgpu_convex_segments_cells", "sdfgpu_convex_last_info",
+    "sdfgpu_project_step_limit", "sdfgpu_project_points_device", "sdfgpu_project_points",
 ]
+
+# include/sdfgpu.h "Projection": modes and per-point statuses
+PROJECT_OUT_OF_COLLISION, PROJECT_INTO_VALID_VOLUME = 0, 1
+PROJECT_CONVERGED, PROJECT_FLAT_GRADIENT, PROJECT_NO_GRADIENT, PROJECT_LEFT_GRID, PROJECT_STEP_LIMIT, PROJECT_NON_FINITE = range(6)
+PROJECT_MAX_STEPS_CEILING = 1048576
 
 
 class SdfGpuError(RuntimeError):
@@ -120,6 +126,9 @@ def load_library():
     L.sdfgpu_local_extrema.argtypes = [vp, vp, i64, i64, i64, dbl, vp, vp]
     L.sdfgpu_convex_segments_cells.argtypes = [vp, vp, sz, sz, sz, sz, i64, i64, i64, dbl, vp, dbl, ci, vp]
     L.sdfgpu_convex_last_info.argtypes = [vp, vp, vp, vp, vp]
+    L.sdfgpu_project_step_limit.argtypes = [i64, i64, i64, dbl, ci, vp]
+    L.sdfgpu_project_points_device.argtypes = [vp, vp, i64, i64, i64, dbl, vp, vp, dbl, dbl, ci, ci, vp, i64, vp, vp, vp, vp]
+    L.sdfgpu_project_points.argtypes = [vp, vp, i64, i64, i64, dbl, vp, vp, dbl, dbl, ci, ci, vp, i64, vp, vp, vp]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is ctypes.c_int or name not in ("sdfgpu_version", "sdfgpu_last_error"):
@@ -197,6 +206,25 @@ def extremum_locations(indices, shape, resolution):
     out[:, 2] = res * ((idx % nz).astype(np.float64) + 0.5)
     out[off] = np.inf
     return out.reshape(nx, ny, nz, 3)
+
+
+def _transform12(t):
+    """3x4 or 4x4 transform -> the 12 row-major doubles of the C ABI (None stays None)"""
+    if t is None:
+        return None
+    a = np.asarray(t, np.float64)
+    return (ctypes.c_double * 12)(*a.reshape(-1, 4)[:3].reshape(-1))
+
+
+def project_step_limit(shape, stepsize_multiplier=1.0 / 8.0, max_steps=0):
+    """The step limit a projection with these arguments uses (sdfgpu_project_step_limit; no GPU needed)."""
+    L = load_library()
+    out = ctypes.c_int()
+    nx, ny, nz = (int(v) for v in shape)
+    rc = L.sdfgpu_project_step_limit(nx, ny, nz, float(stepsize_multiplier), int(max_steps), ctypes.byref(out))
+    if rc != 0:
+        raise SdfGpuError(rc, "stepsize_multiplier must be positive and finite, max_steps >= 0, dims positive")
+    return out.value
 
 
 def device_count():
@@ -469,6 +497,35 @@ class SdfGpu:
                                                            segment_offset, nx, ny, nz, float(resolution), qq, float(connected_threshold),
                                                            int(bool(add_virtual_border)), ctypes.byref(k)))
         return int(k.value)
+
+    def project_points(self, d_sdf, shape, resolution, points, world_to_grid, grid_to_world, minimum_distance=0.0,
+                       stepsize_multiplier=1.0 / 8.0, max_steps=0, into_valid_volume_only=False):
+        """Projection out of collision (or into the valid volume) of host points [n, 3] float64 against a field in HBM (d_sdf:
+        device address).  world_to_grid / grid_to_world: 3x4 (or 4x4) transforms.  Returns (points [n, 3], status uint8 [n],
+        steps int32 [n])."""
+        nx, ny, nz = (int(v) for v in shape)
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        n = pts.shape[0]
+        out, status, steps = np.empty((n, 3), np.float64), np.empty(n, np.uint8), np.empty(n, np.int32)
+        w, g = _transform12(world_to_grid), _transform12(grid_to_world)
+        mode = PROJECT_INTO_VALID_VOLUME if into_valid_volume_only else PROJECT_OUT_OF_COLLISION
+        self._check(self._lib.sdfgpu_project_points(self._h, ctypes.c_void_p(int(d_sdf)), nx, ny, nz, float(resolution), w, g,
+                                                    float(minimum_distance), float(stepsize_multiplier), int(max_steps), mode,
+                                                    pts.ctypes.data, n, out.ctypes.data, status.ctypes.data, steps.ctypes.data))
+        return out, status, steps
+
+    def project_points_device(self, d_sdf, shape, resolution, d_points, n_points, d_out_points, world_to_grid, grid_to_world,
+                              minimum_distance=0.0, stepsize_multiplier=1.0 / 8.0, max_steps=0, into_valid_volume_only=False,
+                              d_status=0, d_steps=0, stream=0, mode=None):
+        """Device form of project_points (device addresses as ints; d_status / d_steps may be 0), enqueued on `stream`."""
+        nx, ny, nz = (int(v) for v in shape)
+        w, g = _transform12(world_to_grid), _transform12(grid_to_world)
+        if mode is None:
+            mode = PROJECT_INTO_VALID_VOLUME if into_valid_volume_only else PROJECT_OUT_OF_COLLISION
+        self._check(self._lib.sdfgpu_project_points_device(
+            self._h, d_sdf or None, nx, ny, nz, float(resolution), w, g, float(minimum_distance), float(stepsize_multiplier),
+            int(max_steps), int(mode), d_points or None, int(n_points), d_out_points or None, d_status or None, d_steps or None,
+            stream or None))
 
     def convex_last_info(self):
         """The last extrema computation on this handle: {rounds, cycles, longest_cycle, longest_entry}."""

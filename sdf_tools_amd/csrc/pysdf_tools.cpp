@@ -31,6 +31,8 @@ Isometry3d IsometryFromArray(const py::array_t<double, py::array::c_style | py::
     return t;
 }
 
+py::tuple ToTuple(const Eigen::Vector3d& v) { return py::make_tuple(v.x(), v.y(), v.z()); }
+
 py::array_t<double> MatrixToArray(const Isometry3d& t) {
     py::array_t<double> out({4, 4});
     auto a = out.mutable_unchecked<2>();
@@ -205,7 +207,52 @@ PYBIND11_MODULE(pysdf_tools, m) {
                 for (int k = 0; k < 3; k++) *p++ = g.size() == 3 ? g[(size_t)k] : oob;
             }
             return out;
-        }, py::arg("enable_edge_gradients") = true);
+        }, py::arg("enable_edge_gradients") = true)
+        // projection (reference sdf.hpp:996-1190): reference-named members, (x, y, z) forms; they raise what the reference throws
+        // (RuntimeError for a flat / missing gradient and for the step limit, ValueError for "Index out of bounds" and NaN input)
+        .def("ProjectOutOfCollision", [](const SignedDistanceField& s, double x, double y, double z, double stepsize_multiplier) {
+            return ToTuple(s.ProjectOutOfCollision(x, y, z, stepsize_multiplier));
+        }, py::arg("x"), py::arg("y"), py::arg("z"), py::arg("stepsize_multiplier") = 1.0 / 8.0)
+        .def("ProjectOutOfCollisionToMinimumDistance", [](const SignedDistanceField& s, double x, double y, double z, double minimum_distance,
+                                                          double stepsize_multiplier) {
+            return ToTuple(s.ProjectOutOfCollisionToMinimumDistance(x, y, z, minimum_distance, stepsize_multiplier));
+        }, py::arg("x"), py::arg("y"), py::arg("z"), py::arg("minimum_distance"), py::arg("stepsize_multiplier") = 1.0 / 8.0)
+        .def("ProjectIntoValidVolume", [](const SignedDistanceField& s, double x, double y, double z) {
+            return ToTuple(s.ProjectIntoValidVolume(x, y, z));
+        }, py::arg("x"), py::arg("y"), py::arg("z"))
+        .def("ProjectIntoValidVolumeToMinimumDistance", [](const SignedDistanceField& s, double x, double y, double z, double minimum_distance) {
+            return ToTuple(s.ProjectIntoValidVolumeToMinimumDistance(x, y, z, minimum_distance));
+        }, py::arg("x"), py::arg("y"), py::arg("z"), py::arg("minimum_distance"))
+        .def("ProjectOutOfCollisionNumpyHost", [](const SignedDistanceField& s, const py::array_t<double, py::array::c_style | py::array::forcecast>& points,
+                                                  double minimum_distance, double stepsize_multiplier, int max_steps, bool into_valid_volume_only) {
+            // the counted host walk (SignedDistanceField::ProjectCounted4d) over [n, 3] points on one host core: the checker of
+            // DeviceSignedDistanceField.ProjectBatch
+            if (points.ndim() != 2 || points.shape(1) != 3) throw std::invalid_argument("points must be [n, 3] float64 (world frame)");
+            const int64_t n = points.shape(0);
+            (void)s.ProjectionStepLimit(stepsize_multiplier, max_steps);            // (argument check, also for n = 0)
+            py::array_t<double> out({n, (int64_t)3});
+            py::array_t<uint8_t> status({n});
+            py::array_t<int32_t> steps({n});
+            {
+                py::gil_scoped_release release;
+                const double* p = points.data();
+                double* o = out.mutable_data();
+                uint8_t* st = status.mutable_data();
+                int32_t* sp = steps.mutable_data();
+                for (int64_t i = 0; i < n; ++i) {
+                    const SignedDistanceField::ProjectionResult r = s.ProjectCounted4d(Eigen::Vector4d(p[3 * i], p[3 * i + 1], p[3 * i + 2], 1.0),
+                                                                                      minimum_distance, stepsize_multiplier, into_valid_volume_only,
+                                                                                      max_steps);
+                    o[3 * i] = r.location(0); o[3 * i + 1] = r.location(1); o[3 * i + 2] = r.location(2);
+                    st[i] = r.status;
+                    sp[i] = r.steps;
+                }
+            }
+            return py::make_tuple(out, status, steps);
+        }, py::arg("points"), py::arg("minimum_distance") = 0.0, py::arg("stepsize_multiplier") = 1.0 / 8.0, py::arg("max_steps") = 0,
+           py::arg("into_valid_volume_only") = false,
+           "n x ProjectOutOfCollisionToMinimumDistance3d (or ProjectIntoValidVolumeToMinimumDistance3d) counted, on one host core: "
+           "(points [n, 3], status uint8 [n]: SDFGPU_PROJECT_*, steps int32 [n])");
 
     // the field left in HBM (include/sdf_tools/device_sdf.hpp): batched queries without the download.  A pybind thread is the
     // thread that owns the libsdfgpu context, so build, query and drop the object from the same Python thread.
@@ -219,7 +266,26 @@ PYBIND11_MODULE(pysdf_tools, m) {
         .def("HostCopyExists", &sdf_tools::DeviceSignedDistanceField::HostCopyExists)
         .def("DevicePointer", [](sdf_tools::DeviceSignedDistanceField& d) { return (uintptr_t)d.DevicePointer(); },
              "address of the [x][y][z] fp32 field in HBM (e.g. for torch / the *_device ABI)")
+        .def(py::init<const Isometry3d&, const std::string&, double, int64_t, int64_t, int64_t, float>(), py::arg("origin_transform"),
+             py::arg("frame"), py::arg("resolution"), py::arg("x_cells"), py::arg("y_cells"), py::arg("z_cells"), py::arg("oob_value"),
+             "an empty field of this geometry in HBM (contents undefined until written through DevicePointer())")
         .def("Host", [](const sdf_tools::DeviceSignedDistanceField& d) { return d.Host(); }, "the reference's container (downloads once)")
+        .def("ProjectBatch", [](const sdf_tools::DeviceSignedDistanceField& d, const py::array_t<double, py::array::c_style | py::array::forcecast>& points,
+                                double minimum_distance, double stepsize_multiplier, int max_steps, bool into_valid_volume_only) {
+            if (points.ndim() != 2 || points.shape(1) != 3) throw std::invalid_argument("points must be [n, 3] float64 (world frame)");
+            const int64_t n = points.shape(0);
+            py::array_t<double> out({n, (int64_t)3});
+            py::array_t<uint8_t> status({n});
+            py::array_t<int32_t> steps({n});
+            {
+                py::gil_scoped_release release;
+                d.ProjectBatch(points.data(), n, minimum_distance, stepsize_multiplier, into_valid_volume_only, max_steps, out.mutable_data(),
+                               status.mutable_data(), steps.mutable_data());
+            }
+            return py::make_tuple(out, status, steps);
+        }, py::arg("points"), py::arg("minimum_distance") = 0.0, py::arg("stepsize_multiplier") = 1.0 / 8.0, py::arg("max_steps") = 0,
+           py::arg("into_valid_volume_only") = false,
+           "ProjectOutOfCollisionNumpyHost's walk for n points in one kernel (sdfgpu_project_points): (points [n, 3], status [n], steps [n])")
         .def("QueryBatch", [](const sdf_tools::DeviceSignedDistanceField& d,
                               const py::array_t<double, py::array::c_style | py::array::forcecast>& points, bool enable_edge_gradients) {
             if (points.ndim() != 2 || points.shape(1) != 3) throw std::invalid_argument("points must be [n, 3] float64 (world frame)");

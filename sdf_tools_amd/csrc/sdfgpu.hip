@@ -14,6 +14,7 @@
 #include "sdfgpu_components.hpp"
 #include "sdfgpu_topology.hpp"
 #include "sdfgpu_convex.hpp"
+#include "sdfgpu_project.hpp"
 
 #include <sys/mman.h>
 #if defined(__SSE2__)
@@ -2898,6 +2899,87 @@ int sdfgpu_convex_last_info(sdfgpu_handle h, int* out_rounds, uint32_t* out_cycl
     if (out_longest_cycle) *out_longest_cycle = st.longest_cycle[0];
     if (out_longest_entry) *out_longest_entry = st.longest_entry[0];
     return SDFGPU_OK;
+}
+
+int sdfgpu_project_step_limit(int64_t nx, int64_t ny, int64_t nz, double stepsize_multiplier, int max_steps, int* out_limit) {
+    if (!out_limit || nx <= 0 || ny <= 0 || nz <= 0) return SDFGPU_ERR_INVALID_ARGUMENT;
+    const int limit = project_step_limit(nx, ny, nz, stepsize_multiplier, max_steps);
+    if (limit < 0) return SDFGPU_ERR_INVALID_ARGUMENT;
+    *out_limit = limit;
+    return SDFGPU_OK;
+}
+
+namespace {
+int check_project_args(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                       const double* world_to_grid, const double* grid_to_world, double stepsize_multiplier, int max_steps, int mode,
+                       const double* points, int64_t n_points, const double* out_points, ProjectArgs& a) {
+    if (!d_sdf) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "projection: null field pointer");
+    if (n_points < 0 || n_points > ((int64_t)1 << 40)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "projection: point count %lld out of range [0, 2^40]", (long long)n_points);
+    if (n_points > 0 && (!points || !out_points)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "projection: null points or out_points");
+    if (!world_to_grid || !grid_to_world) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "projection: world_to_grid and grid_to_world are required");
+    if (nx <= 0 || ny <= 0 || nz <= 0 || nx > INT64_MAX / ny || nx * ny > INT64_MAX / nz)
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "projection: unsupported grid %lld x %lld x %lld", (long long)nx, (long long)ny, (long long)nz);
+    if (!(resolution > 0.0) || !std::isfinite(resolution)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "projection: resolution must be positive and finite");
+    if (mode != SDFGPU_PROJECT_OUT_OF_COLLISION && mode != SDFGPU_PROJECT_INTO_VALID_VOLUME)
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "projection: unknown mode %d", mode);
+    const int limit = project_step_limit(nx, ny, nz, stepsize_multiplier, max_steps);
+    if (limit < 0) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "projection: stepsize_multiplier must be positive and finite and max_steps >= 0");
+    a = ProjectArgs{};
+    a.sdf = d_sdf; a.n = n_points; a.nx = nx; a.ny = ny; a.nz = nz;
+    a.step_limit = limit; a.mode = mode;
+    for (int i = 0; i < 12; ++i) { a.w2g[i] = world_to_grid[i]; a.g2w[i] = grid_to_world[i]; }
+    return SDFGPU_OK;
+}
+}  // namespace
+
+int sdfgpu_project_points_device(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                                 const double world_to_grid[12], const double grid_to_world[12], double minimum_distance,
+                                 double stepsize_multiplier, int max_steps, int mode, const double* d_points, int64_t n_points,
+                                 double* d_out_points, uint8_t* d_out_status, int32_t* d_out_steps, void* stream) {
+    return rz_wrap(h, stream, [&]() -> int {
+        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
+        ProjectArgs a;
+        if (int rc = check_project_args(h, d_sdf, nx, ny, nz, resolution, world_to_grid, grid_to_world, stepsize_multiplier, max_steps,
+                                        mode, d_points, n_points, d_out_points, a)) return rc;
+        if (n_points == 0) return SDFGPU_OK;
+        HIP_TRY(h, hipSetDevice(h->device));
+        a.points = d_points; a.out = d_out_points; a.status = d_out_status; a.steps = d_out_steps;
+        project_prepare(a, resolution, minimum_distance, stepsize_multiplier);
+        HIP_TRY(h, project_launch(a, (hipStream_t)stream));
+        return SDFGPU_OK;
+    });
+}
+
+int sdfgpu_project_points(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                          const double world_to_grid[12], const double grid_to_world[12], double minimum_distance,
+                          double stepsize_multiplier, int max_steps, int mode, const double* points, int64_t n_points,
+                          double* out_points, uint8_t* out_status, int32_t* out_steps) {
+    return rz_wrap(h, nullptr, [&]() -> int {
+        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
+        ProjectArgs a;
+        if (int rc = check_project_args(h, d_sdf, nx, ny, nz, resolution, world_to_grid, grid_to_world, stepsize_multiplier, max_steps,
+                                        mode, points, n_points, out_points, a)) return rc;
+        if (n_points == 0) return SDFGPU_OK;
+        HIP_TRY(h, hipSetDevice(h->device));
+        // staging in the context (shared with sdfgpu_query_points): points | out points | steps | status
+        const size_t n = (size_t)n_points;
+        const size_t o_o = n * 24, o_s = o_o + n * 24, o_t = o_s + n * 4, total = o_t + ((n + 255) & ~(size_t)255);
+        if (int rc = ensure(h, h->query_stage, total, "query staging")) return rc;
+        char* base = (char*)h->query_stage.ptr;
+        // the ordering of sdfgpu_query_points: the null stream, behind this handle's last build
+        hipStream_t s = nullptr;
+        if (h->order_valid && h->order_stream != nullptr) HIP_TRY(h, hipStreamWaitEvent(s, h->build_done_ev, 0));
+        if (int rc = copy_from_host(h, base, points, n * 24, s)) return rc;
+        a.points = (const double*)base; a.out = (double*)(base + o_o);
+        a.steps = out_steps ? (int32_t*)(base + o_s) : nullptr;
+        a.status = out_status ? (uint8_t*)(base + o_t) : nullptr;
+        project_prepare(a, resolution, minimum_distance, stepsize_multiplier);
+        HIP_TRY(h, project_launch(a, s));
+        if (int rc = copy_to_host(h, out_points, base + o_o, n * 24, s)) return rc;
+        if (out_steps) if (int rc = copy_to_host(h, out_steps, base + o_s, n * 4, s)) return rc;
+        if (out_status) if (int rc = copy_to_host(h, out_status, base + o_t, n, s)) return rc;
+        return SDFGPU_OK;
+    });
 }
 
 }  // extern "C"

@@ -1,0 +1,342 @@
+"""Projection out of collision / into the valid volume without a GPU: SignedDistanceField's host members (include/sdf_tools/sdf.hpp,
+reference include/sdf_tools/sdf.hpp:996-1190) pinned to hand-derived answers through tests/projection_harness.cpp.  The host walk is
+the yardstick of the GPU kernel (tests/test_gpu_projection.py compares the two bit for bit).
+
+The test fields are slabs along x, constant in y and z: cells 10 .. 30 of 41 are filled, f(i) = -min(i - 9, 31 - i) * res inside
+and max(10 - i, i - 30) * res outside.  Near the surface at x = 10 (grid frame, in cells) the trilinear estimate of the
+half-cell-corrected values is exactly (10 - x) * res, and the central difference of cell 20 (the medial plane) is exactly 0."""
+import ctypes
+import math
+import os
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+_LIB = []
+
+CONVERGED, FLAT, NO_GRADIENT, LEFT_GRID, STEP_LIMIT, NON_FINITE = range(6)
+NX, NY, NZ = 41, 6, 5
+
+
+def _harness():
+    if not _LIB:
+        from sdf_tools_amd import build as b
+        b.build_libsdfgpu()
+        lib = os.path.join(ROOT, "sdf_tools_amd")
+        out = os.path.join(tempfile.mkdtemp(prefix="projection_harness_"), "projection_harness.so")
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-ffp-contract=off", "-fPIC", "-shared",
+                               "-I", os.path.join(ROOT, "include"), os.path.join(HERE, "projection_harness.cpp"), "-o", out,
+                               "-L", lib, "-lsdfgpu", "-Wl,-rpath," + lib, "-lz"])
+        L = ctypes.CDLL(out)
+        d, i64, vp, ci = ctypes.c_double, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int
+        L.ph_create.restype = vp
+        L.ph_create.argtypes = [i64, i64, i64, d, vp, vp, ctypes.c_float]
+        L.ph_destroy.argtypes = [vp]
+        L.ph_counted.restype = ci
+        L.ph_counted.argtypes = [vp, d, d, d, d, d, ci, ci, vp, vp, ctypes.c_char_p, ci]
+        L.ph_member.restype = ci
+        L.ph_member.argtypes = [vp, ci, ci, d, d, d, d, d, ci, vp, ctypes.c_char_p, ci]
+        L.ph_estimate.restype = ci
+        L.ph_estimate.argtypes = [vp, d, d, d, vp]
+        L.ph_step_limit.restype = ci
+        L.ph_step_limit.argtypes = [vp, d, ci]
+        _LIB.append(L)
+    return _LIB[0]
+
+
+class Field:
+    def __init__(self, data, res, origin=None):
+        self.L = _harness()
+        self.data = np.ascontiguousarray(data, np.float32)
+        self.res = res
+        self.origin = np.eye(4) if origin is None else np.asarray(origin, np.float64)
+        o = np.ascontiguousarray(self.origin, np.float64)
+        self.h = self.L.ph_create(*self.data.shape, res, o.ctypes.data, self.data.ctypes.data, math.inf)
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            self.L.ph_destroy(self.h)
+
+    def counted(self, p, minimum_distance=0.0, stepsize_multiplier=0.125, valid_only=False, max_steps=0):
+        out = (ctypes.c_double * 4)()
+        steps = ctypes.c_int(-1)
+        msg = ctypes.create_string_buffer(256)
+        st = self.L.ph_counted(self.h, *map(float, p), minimum_distance, stepsize_multiplier, int(valid_only), max_steps, out,
+                               ctypes.byref(steps), msg, 256)
+        return st, (out[0], out[1], out[2]), steps.value
+
+    def member(self, kind, form, p, minimum_distance=0.0, stepsize_multiplier=0.125, max_steps=-1):
+        out = (ctypes.c_double * 4)()
+        msg = ctypes.create_string_buffer(256)
+        rc = self.L.ph_member(self.h, kind, form, *map(float, p), minimum_distance, stepsize_multiplier, max_steps, out, msg, 256)
+        return rc, (out[0], out[1], out[2]), msg.value.decode()
+
+    def estimate(self, p):
+        d = ctypes.c_double()
+        inside = self.L.ph_estimate(self.h, *map(float, p), ctypes.byref(d))
+        return d.value, bool(inside)
+
+
+def slab(res, nx=NX):
+    f = np.empty((nx, NY, NZ), np.float32)
+    for i in range(nx):
+        v = -min(i - 9, 31 - i) if 10 <= i <= 30 else max(10 - i, i - 30)
+        f[i] = v * res
+    return f
+
+
+# eigen_lite arithmetic, restated in Python (IEEE double, no fused multiply-add, left-to-right sums)
+def rigid(angle, t):
+    c, s = math.cos(angle), math.sin(angle)
+    m = np.eye(4)
+    m[:3, :3] = [[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]]
+    m[:3, 3] = t
+    return m
+
+
+def inverse(m):
+    r = np.eye(4)
+    for i in range(3):
+        for j in range(3):
+            r[i, j] = m[j, i]
+    for i in range(3):
+        r[i, 3] = -(r[i, 0] * m[0, 3] + r[i, 1] * m[1, 3] + r[i, 2] * m[2, 3])
+    return r
+
+
+def apply(m, p):
+    v = (float(p[0]), float(p[1]), float(p[2]), 1.0)
+    return tuple(float(m[i, 0]) * v[0] + float(m[i, 1]) * v[1] + float(m[i, 2]) * v[2] + float(m[i, 3]) * v[3] for i in range(3))
+
+
+def bits(t):
+    return tuple(np.float64(v).view(np.uint64) for v in t)
+
+
+ALL_MEMBERS = [(k, f) for k in range(4) for f in range(3)]
+
+
+# ---- a point already free --------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("res", [1.0, 0.05])
+def test_free_point_takes_no_step_and_comes_back_through_both_transforms(res):
+    origin = rigid(0.3, (1.5, -2.0, 0.25))
+    f = Field(slab(res), res, origin)
+    g = (5.2 * res, 2.3 * res, 1.7 * res)                        # grid frame, d = 4.8 res
+    p = apply(origin, g)
+    st, out, steps = f.counted(p)
+    assert (st, steps) == (CONVERGED, 0)
+    want = apply(origin, apply(inverse(origin), p))
+    assert bits(out) == bits(want)
+    for form in range(3):
+        rc, got, _ = f.member(0, form, p)
+        assert rc == 0 and bits(got) == bits(want)
+    fi = Field(slab(res), res)                                   # identity origin: the input bits themselves
+    st, out, steps = fi.counted(g)
+    assert (st, steps) == (CONVERGED, 0) and bits(out) == bits(g)
+
+
+# ---- a point inside a thick slab ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("minimum_distance_cells", [0.0, 1.5])
+@pytest.mark.parametrize("stepsize_multiplier", [0.125, 0.5])
+@pytest.mark.parametrize("res", [1.0, 0.25])
+def test_deep_point_walks_out_to_just_past_the_minimum_distance(minimum_distance_cells, stepsize_multiplier, res):
+    f = Field(slab(res), res)
+    md = minimum_distance_cells * res
+    p = (14.3 * res, 4.1 * res, 3.7 * res)
+    d0, inside = f.estimate(p)
+    assert inside and abs(d0 - (10.0 - 14.3) * res) < 1e-9 * max(res, 1.0)
+    st, out, steps = f.counted(p, md, stepsize_multiplier)
+    assert st == CONVERGED
+    max_step = res * stepsize_multiplier
+    margin = md + res * stepsize_multiplier * 1e-4
+    d, inside = f.estimate(out)
+    assert inside and d > md
+    assert d <= margin + max_step + 1e-9 * res                   # the last step is at most max_step, from a d <= md
+    assert out[1] == p[1] and out[2] == p[2]                     # the gradient has no y, z component: exactly no motion there
+    assert out[0] < p[0]                                         # toward the nearer surface, x = 10
+    need = (md - d0) / max_step                                  # d rises by exactly the step: about this many full steps
+    assert math.floor(need) <= steps <= math.ceil(need) + 1
+    for form in range(3):                                        # the reference-named members return the same location
+        rc, got, _ = f.member(1, form, p, md, stepsize_multiplier)
+        assert rc == 0 and bits(got) == bits(out)
+    if md == 0.0:
+        rc, got, _ = f.member(0, 0, p, 0.0, stepsize_multiplier)
+        assert rc == 0 and bits(got) == bits(out)
+
+
+def test_medial_plane_is_a_flat_gradient():
+    f = Field(slab(1.0), 1.0)
+    p = (20.5, 3.3, 2.2)                                         # cell 20: f(21) - f(19) == 0 exactly
+    st, out, steps = f.counted(p)
+    assert (st, steps) == (FLAT, 0) and bits(out) == bits(p)
+    for kind, form in [(0, 0), (0, 1), (0, 2), (1, 0), (1, 1), (1, 2)]:
+        rc, _, msg = f.member(kind, form, p, 0.0)
+        assert rc == 1 and msg == "Encountered flat gradient - stuck"
+
+
+def test_minimum_distance_beyond_the_field_leaves_the_grid():
+    f = Field(slab(1.0), 1.0)
+    p = (14.3, 4.1, 3.7)
+    st, out, steps = f.counted(p, 100.0)
+    assert st == LEFT_GRID
+    assert out[0] < 0.0 and out[1] == p[1] and out[2] == p[2]   # the last location reached: just past the x = 0 face
+    assert 14.3 / 0.125 - 2 <= steps <= 14.3 / 0.125 + 2
+    rc, _, msg = f.member(1, 0, p, 100.0)
+    assert rc == 2 and msg == "Index out of bounds"
+
+
+# ---- outside points, the valid volume -------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("res", [1.0, 0.5])
+def test_outside_points_are_clamped_first(res):
+    f = Field(slab(res), res)
+    m = res * 1e-4
+    sx, sy, sz = NX * res, NY * res, NZ * res
+    cases = [((50.0 * res, 2.5 * res, 1.5 * res), (sx - m, 2.5 * res, 1.5 * res)),
+             ((-3.0 * res, 2.5 * res, -7.0 * res), (m, 2.5 * res, m)),
+             ((38.0 * res, 99.0 * res, sz), (38.0 * res, sy - m, sz - m))]
+    for p, clamped in cases:
+        # free where they land: no step, the clamped point itself (identity origin: origin * (x, y, z, 1) is exact)
+        st, out, steps = f.counted(p)
+        assert (st, steps) == (CONVERGED, 0) and bits(out) == bits(clamped), (p, out, clamped)
+        for form in range(3):
+            rc, got, _ = f.member(2, form, p)
+            assert rc == 0 and bits(got) == bits(clamped)
+        st, out, steps = f.counted(p, 0.0, 0.125, valid_only=True)
+        assert (st, steps) == (CONVERGED, 0) and bits(out) == bits(clamped)
+    # with a minimum distance the margin grows
+    md = 2.0 * res
+    rc, got, _ = f.member(3, 0, (50.0 * res, 2.5 * res, 1.5 * res), md)
+    assert rc == 0 and bits(got) == bits((sx - (md + m), 2.5 * res, md + m))
+
+
+def test_inside_points_come_back_from_the_valid_volume_bit_identical():
+    origin = rigid(-1.1, (0.3, 0.7, -4.0))
+    f = Field(slab(0.5), 0.5, origin)
+    rng = np.random.default_rng(3)
+    for _ in range(50):
+        g = (rng.uniform(0.01, NX * 0.5 - 0.01), rng.uniform(0.01, NY * 0.5 - 0.01), rng.uniform(0.01, NZ * 0.5 - 0.01))
+        p = apply(origin, g)
+        if any(not (0.5e-4 + 1e-9 < c < s * 0.5 - 0.5e-4 - 1e-9) for c, s in zip(apply(inverse(origin), p), (NX, NY, NZ))):
+            continue
+        for form in range(3):
+            rc, got, _ = f.member(2, form, p)
+            assert rc == 0 and bits(got) == bits(p)
+        st, out, steps = f.counted(p, 0.0, 0.125, valid_only=True)
+        assert (st, steps) == (CONVERGED, 0) and bits(out) == bits(p)
+
+
+# ---- a rotated and shifted origin ---------------------------------------------------------------------------------------------------
+def test_rotated_and_shifted_origin():
+    origin = rigid(0.7, (-3.25, 1.5, 2.0))
+    inv = inverse(origin)
+    f = Field(slab(0.1), 0.1, origin)
+    g = (1.43, 0.41, 0.37)                                       # grid frame, 4.3 cells deep
+    p = apply(origin, g)
+    st, out, steps = f.counted(p, 0.15, 0.125)
+    assert st == CONVERGED and steps > 0
+    d, inside = f.estimate(out)
+    assert inside and 0.15 < d <= 0.15 + 0.1 * 0.125 * (1 + 1e-4) + 1e-9
+    back = apply(inv, out)
+    assert abs(back[1] - g[1]) < 1e-12 and abs(back[2] - g[2]) < 1e-12 and back[0] < 1.0 - 0.15
+    # outside in the world frame: clamped in the grid frame, then walked
+    p = apply(origin, (-0.5, 0.31, 0.22))
+    st, out, steps = f.counted(p)
+    assert st == CONVERGED and steps == 0
+    assert bits(out) == bits(apply(origin, (0.1 * 1e-4, 0.31, 0.22))) or bits(out) == bits(apply(origin, apply(inv, apply(origin, (0.1 * 1e-4, 0.31, 0.22)))))
+
+
+# ---- infinite fields ------------------------------------------------------------------------------------------------------------------
+def test_all_filled_and_all_free_fields_take_no_step():
+    """An all-filled field (-inf everywhere) does not report a flat gradient, although its gradient is NaN: the estimate is NaN
+    first -- the z slope is (pz - mz) = (-inf) - (-inf) -- so `d <= minimum_distance` is false and the reference's loop is never
+    entered; the point comes back after 0 steps.  An all-free field (+inf) estimates +inf or NaN: 0 steps as well."""
+    for value in (-np.inf, np.inf):
+        f = Field(np.full((7, 6, 5), value, np.float32), 1.0)
+        for p in [(3.3, 2.6, 2.2), (3.5, 2.5, 2.5), (0.01, 5.99, 4.99)]:
+            d, inside = f.estimate(p)
+            assert inside and (math.isnan(d) or d == math.inf)
+            st, out, steps = f.counted(p, 1.0)
+            assert (st, steps) == (CONVERGED, 0) and bits(out) == bits(p)
+            rc, got, _ = f.member(1, 0, p, 1.0)
+            assert rc == 0 and bits(got) == bits(p)
+
+
+def test_nan_gradient_fails_the_flat_test():
+    """The flat test is !(|g| > res / 4), so a NaN norm fails it.  NaN sits in the plane z = 4 only: the gradient of a z = 3 cell
+    reads it, the estimate of a point in the lower half of that cell (planes z = 2 and 3) does not."""
+    f = np.full((7, 6, 6), -2.0, np.float32)
+    f[:, :, 4] = np.nan
+    fld = Field(f, 1.0)
+    p = (3.6, 2.6, 3.3)
+    d, inside = fld.estimate(p)
+    assert inside and d == -1.5
+    st, out, steps = fld.counted(p)
+    assert (st, steps) == (FLAT, 0) and bits(out) == bits(p)
+    rc, _, msg = fld.member(0, 1, p)
+    assert rc == 1 and msg == "Encountered flat gradient - stuck"
+
+
+# ---- the two deviations: the step limit and non-finite input ---------------------------------------------------------------------
+def test_step_limit():
+    f = Field(slab(1.0), 1.0)
+    p = (14.3, 4.1, 3.7)
+    st, out, steps = f.counted(p, 0.0, 0.125, max_steps=1)
+    assert (st, steps) == (STEP_LIMIT, 1) and out[0] == p[0] - 0.125 and out[1:] == p[1:]
+    rc, _, msg = f.member(0, 2, p, 0.0, 0.125, max_steps=1)
+    assert rc == 1 and "step limit of 1 steps" in msg
+    st, _, steps = f.counted(p, 0.0, 0.125, max_steps=40)        # 35 steps are needed
+    assert (st, steps) == (CONVERGED, 35)
+    st, _, steps = f.counted(p, 0.0, 0.125, max_steps=34)
+    assert (st, steps) == (STEP_LIMIT, 34)
+    # the default: 4 * ceil(diagonal / stepsize_multiplier) + 64, at most 2^20
+    diag = math.sqrt(NX * NX + NY * NY + NZ * NZ)
+    assert f.L.ph_step_limit(f.h, 0.125, 0) == 4 * math.ceil(diag / 0.125) + 64
+    assert f.L.ph_step_limit(f.h, 0.5, 0) == 4 * math.ceil(diag / 0.5) + 64
+    assert f.L.ph_step_limit(f.h, 1e-6, 0) == 1 << 20
+    assert f.L.ph_step_limit(f.h, 0.125, 7) == 7
+    for bad in [(0.0, 0), (-0.125, 0), (math.nan, 0), (math.inf, 0), (0.125, -1)]:
+        assert f.L.ph_step_limit(f.h, *bad) == -1
+        assert f.counted(p, 0.0, bad[0], max_steps=bad[1])[0] == -2
+    from sdf_tools_amd import capi
+    assert capi.project_step_limit((NX, NY, NZ), 0.125) == 4 * math.ceil(diag / 0.125) + 64
+    assert capi.project_step_limit((512, 512, 512), 0.125) == 4 * math.ceil(math.sqrt(3 * 512 * 512) / 0.125) + 64
+    with pytest.raises(capi.SdfGpuError):
+        capi.project_step_limit((NX, NY, NZ), 0.0)
+
+
+@pytest.mark.parametrize("bad", [(math.nan, 1.0, 1.0), (1.0, math.inf, 1.0), (1.0, 1.0, -math.inf), (math.nan,) * 3])
+def test_non_finite_input_is_refused(bad):
+    f = Field(slab(1.0), 1.0)
+    st, out, steps = f.counted(bad)
+    assert (st, steps) == (NON_FINITE, 0)
+    assert all((math.isnan(a) and math.isnan(b)) or a == b for a, b in zip(out, bad))
+    st, _, _ = f.counted(bad, 0.0, 0.125, valid_only=True)
+    assert st == NON_FINITE
+    for kind, form in ALL_MEMBERS:
+        rc, _, msg = f.member(kind, form, bad)
+        assert rc == 2 and msg == "Cannot project a non-finite location"
+
+
+def test_normalized_is_division_by_the_norm():
+    """eigen_lite's normalized(): a component-wise division (not a product with 1 / norm), the vector itself when the norm is 0;
+    checked through one step along a diagonal gradient, whose location the test restates."""
+    res = 1.0
+    f = np.empty((9, 9, 9), np.float32)
+    for i in range(9):
+        for j in range(9):
+            for k in range(9):
+                f[i, j, k] = 3.0 * i + 1.0 * j - 20.0                # gradient (3, 1, 0) everywhere inside
+    fld = Field(f, res)
+    p = (4.3, 4.6, 4.2)
+    st, out, steps = fld.counted(p, 0.0, 0.125, max_steps=1)
+    assert steps == 1
+    g0, g1, g2 = 3.0, 1.0, 0.0
+    n = math.sqrt(((0.0 + g0 * g0) + g1 * g1) + g2 * g2)
+    d, _ = fld.estimate(p)
+    step = min(0.125, (0.0 + res * 0.125 * 1e-4) - d)
+    want = (p[0] + (g0 / n) * step, p[1] + (g1 / n) * step, p[2] + (g2 / n) * step)
+    assert bits(out) == bits(want)
