@@ -14,14 +14,19 @@ generated directly in HBM before the timed region; the steps rotate over three d
           `python bench.py --gpus N` launches its own N ranks (re-exec through
           torch.distributed.run on 127.0.0.1); under an existing torchrun it uses the ranks it is given.
 
-Prints ONE JSON line on rank 0.  Besides the contract fields it carries (N = 1 only, all untimed
-with respect to `value`):
+A plain run sets up, warms up, times the K steps, writes --dump-outputs if asked and prints ONE JSON line on
+rank 0: the contract fields, the workload, the step against the compulsory bytes, the last step's extrema (N = 1)
+and the ranks' self-check (N > 1).  Everything else runs only with `--full`, after the timed steps and untimed with
+respect to `value`; the full detail is then printed first, as a `BENCH_FULL {...}` line.  At N = 1:
   roofline      dominant kernel of the timed steps: HIP-event duration, compulsory bytes, PMC traffic
+  value_without_stage_events, value_repeats, bits_entry   the timed loop again: no events, five repeats, bits input
   legs          the other tiers at the same 512^3 size: general (separable sweeps) tier on the headline
                 input, a sparse Bernoulli grid, the streaming two-box point cloud; and BASELINE configs[1], the
-                256^3 grid (throughput reported, parity in tests/)
+                256^3 grid (throughput reported, parity in tests/)  [--no-legs drops them and parity]
   parity        voxels that differ from the reference algorithm (oracle) on 128^3 samples
-  cpu_baseline  the oracle timed on this host
+  host_api, cpu_baseline   host-buffer calls of the library; the oracle timed on this host  [--no-cpu-baseline]
+and with the slab builder: the roofline of its ball kernel, `vs_1gpu_same_grid` (the same grid on one GPU) and, at
+N = 1 (--force-slab), `multi_native_on_one_gpu`.
 
 `--dump-outputs DIR` (N = 1) writes what the last timed step returned to its caller -- the fp32 field (whole up to 4 Mvoxel,
 else a fixed seeded sample with its voxel indices) and the fp64 extrema -- as DIR/*.npy, so two builds can be compared.
@@ -75,10 +80,13 @@ def parse_args():
     ap.add_argument("--resolution", type=float, default=0.01)
     ap.add_argument("--halo", type=int, default=3)
     ap.add_argument("--masks", type=int, default=3, help="distinct input grids the steps rotate over")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-legs", action="store_true", help="skip the extra (untimed) tier legs and the parity counts")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check what the headline figure does not need: roofline, "
+                         "repeats, bits entry, tier legs, parity, host calls, CPU baseline, slab comparisons")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the host-buffer calls and the CPU baseline")
+    ap.add_argument("--no-legs", action="store_true", help="with --full: skip the extra (untimed) tier legs and the parity counts")
     ap.add_argument("--cpu-sample", type=int, default=0,
-                    help="edge of the cube timed on the CPU oracle (0 = 512 if the host has the memory, else 320)")
+                    help="with --full: edge of the cube timed on the CPU oracle (0 = 512 if the host has the memory, else 320)")
     ap.add_argument("--tune", type=int, nargs=2, default=None, help="rows per chunk: y x")
     ap.add_argument("--no-profile", action="store_true", help="do not record per-stage HIP events in the timed region")
     ap.add_argument("--force-slab", action="store_true", help="run the multi-GPU slab builder even at N = 1")
@@ -471,21 +479,24 @@ def summary_line(result):
     if h:
         out["host_api_ms"] = {"sdfgpu_build": h.get("ms"), "to_device": (h.get("device_resident") or {}).get("build_ms"),
                               "class_seam_cpp": (h.get("class_seam") or {}).get("cpp_ms"), "class_seam_pybind": (h.get("class_seam") or {}).get("pybind_ms")}
-    out["full_detail"] = "the line above (BENCH_FULL ...) and gpurun_out/bench_full.json"
     return out
 
 
 def emit(result):
+    """--full: the whole result as a `BENCH_FULL {...}` line (also written to a file), then the summary line."""
     full = json.dumps(result)
     print("BENCH_FULL " + full, flush=True)
+    line = summary_line(result)
+    line["full_detail"] = "the line above (BENCH_FULL ...)"
     try:
         d = os.path.join(ROOT, "gpurun_out")
         os.makedirs(d, exist_ok=True)
         with open(os.path.join(d, "bench_full.json"), "w") as f:
             f.write(full + "\n")
+        line["full_detail"] += " and " + os.path.relpath(f.name, ROOT)
     except Exception:
         pass
-    print(json.dumps(summary_line(result)), flush=True)
+    print(json.dumps(line), flush=True)
 
 
 def main():
@@ -626,7 +637,7 @@ def main():
                                "ms_per_step_by_rank": [round(v, 4) for v in per_rank_ms],
                                "general_path_builds": builder.general_builds, "whole_line_sweeps": builder.fallbacks,
                                "general_path_host_reads": builder.host_reads, "general_path_mispredictions": builder.mispredictions}
-    if use_slab:
+    if use_slab and args.full:
         # (also at world = 1 with --force-slab: the same code path runs on a one-GPU box every round)
         # BASELINE.md section 3's target is ">= 6x at 8 GPUs ON 1024^3": the denominator is the SAME grid on ONE GPU, not the
         # 512^3 N = 1 line.  Rank 0 builds the whole grid of this run through the single-GPU ABI (same masks' seeds, same
@@ -667,7 +678,9 @@ def main():
                       "ratio_to_peak": round(n_total * B_ALG_TOTAL / (dt / args.steps) / 1e9 / HBM_PEAK_GBPS / world, 4)},
     }
 
-    if not use_slab:
+    if not use_slab and not args.full:
+        result["extrema"] = list(ctx.get_extrema())
+    elif not use_slab:
         ms_sum, builds = ctx.get_stage_times()
         ctx.set_profiling(False)
         if not args.no_profile and dominant_only:
@@ -736,7 +749,7 @@ def main():
             result["roofline"] = r
     else:
         launches, ms_total, vox = builder.pop_ball_timings()
-        if launches and rank == 0:
+        if launches and rank == 0 and args.full:
             avg_ms = ms_total / launches
             traffic = load_traffic()
             per_voxel = ((traffic or {}).get("dense_ball") or 0) / float(512 ** 3)
@@ -753,7 +766,7 @@ def main():
         result["config"]["whole_line_fallbacks"] = builder.fallbacks
         result["config"]["general_exchange"] = getattr(builder, "general_exchange", None)
 
-    if args.force_slab and world == 1:
+    if args.force_slab and world == 1 and args.full:
         # VERDICT r3 "next round" 5: what the HOST costs a multi-rank build.  libsdfgpu_multi with 1 / 2 / 8 logical ranks on
         # this one GPU (the messages travel as device-to-device copies) against the single-GPU ABI on the same scenes:
         # wall time per synchronous build, its host round trips, and the difference to the single-GPU build = host calls +
@@ -812,7 +825,7 @@ def main():
             result["multi_native_on_one_gpu"] = {"error": repr(e)}
 
     single = rank == 0 and world == 1 and not args.force_slab
-    if single and not args.no_legs:
+    if single and args.full and not args.no_legs:
         legs = {}
         leg_steps = max(10, min(50, args.steps))
         try:
@@ -880,7 +893,7 @@ def main():
             result["parity"] = parity_counts(ctx, res)
         except Exception as e:
             result["parity"] = {"error": repr(e)}
-    if single and not args.no_cpu_baseline:
+    if single and args.full and not args.no_cpu_baseline:
         # what a caller of the reference's C++ API sees: host mask -> host SDF through sdfgpu_build (PCIe both ways,
         # fresh output buffer).  Reported for context only -- never `value`.
         host_mask = masks[0].cpu().numpy()
@@ -927,8 +940,10 @@ def main():
         except Exception as e:
             result["host_api"]["class_seam"] = {"error": repr(e)}
         result["cpu_baseline"] = cpu_baseline(args.cpu_sample, args.p, res)
-    if rank == 0:
+    if rank == 0 and args.full:
         emit(result)
+    elif rank == 0:
+        print(json.dumps(summary_line(result)), flush=True)
     if world > 1:
         dist.destroy_process_group()
 
