@@ -7,7 +7,8 @@
 // shape of the same API: ExtractSignedDistanceFieldDevice (sdf_generation.hpp / CollisionMapGrid) leaves the field on the
 // MI355X, EstimateDistanceBatch / GetGradientBatch answer n points with ONE kernel (sdfgpu_query_points: one lane per
 // point, the reference's double arithmetic), ProjectBatch walks n points out of collision in one kernel (sdfgpu_project_points),
-// and Host() downloads the field lazily, once, for callers that do want the
+// QueryGradientsBatch answers GetAutoDiffGradient / GetSmoothGradient / DistanceToBoundary for n points in one kernel
+// (sdfgpu_query_gradients), and Host() downloads the field lazily, once, for callers that do want the
 // reference's container (GetValue*, serialisation, per-point calls).
 //
 // Ownership (round 5): the device memory belongs to the libsdfgpu context of the thread that built the field,
@@ -170,6 +171,46 @@ public:
         return ProjectOutOfCollisionToMinimumDistanceBatch(locations, 0.0, statuses, stepsize_multiplier);
     }
 
+    // n world-frame points (n x 3 doubles) -> what n calls of SignedDistanceField::QueryGradient4d return for `kind`
+    // (SDFGPU_QUERY_SMOOTH_GRADIENT with `window`, SDFGPU_QUERY_AUTODIFF_GRADIENT, SDFGPU_QUERY_DISTANCE_TO_BOUNDARY), from one
+    // kernel (sdfgpu_query_gradients, include/sdfgpu.h "Interpolated gradients"):
+    //   out_value[n]       the estimate (OOB value outside), or the signed displacement to the nearest face
+    //   out_gradient[3 n]  world frame; NaN where GetSmoothGradient / GetAutoDiffGradient return an empty vector or throw
+    //   out_status[n]      SDFGPU_QUERY_*
+    // Any output may be null.
+    void QueryGradientsBatch(const double* points_xyz, const int64_t n, const int kind, const double window, double* out_value,
+                             double* out_gradient, uint8_t* out_status) const {
+        if (!d_sdf_) throw std::runtime_error("DeviceSignedDistanceField is not initialized");
+        double w2g[12];
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 4; ++c) w2g[r * 4 + c] = inverse_origin_.matrix()(r, c);
+        const std::lock_guard<std::mutex> lock(ctx_->mutex);
+        sdf_generation::ThrowOnStatus(handle_, sdfgpu_query_gradients(handle_, d_sdf_, nx_, ny_, nz_, resolution_, w2g, oob_, kind, window,
+                                                                      points_xyz, n, out_value, out_gradient, out_status));
+    }
+    // Reference-shaped: one std::vector<double> per location like GetAutoDiffGradient3d (3 components, or empty outside the grid
+    // or for a non-finite location); the estimates (EstimateDistance3d's .first) in *values when asked.
+    std::vector<std::vector<double>> GetAutoDiffGradientBatch(const std::vector<Eigen::Vector3d>& locations,
+                                                              std::vector<double>* values = nullptr,
+                                                              std::vector<uint8_t>* statuses = nullptr) const {
+        return GradientBatch(locations, SDFGPU_QUERY_AUTODIFF_GRADIENT, 0.0, values, statuses);
+    }
+    // ... like GetSmoothGradient3d (empty where the reference returns empty or throws; *statuses tells which)
+    std::vector<std::vector<double>> GetSmoothGradientBatch(const std::vector<Eigen::Vector3d>& locations, const double nominal_window_size,
+                                                            std::vector<uint8_t>* statuses = nullptr) const {
+        return GradientBatch(locations, SDFGPU_QUERY_SMOOTH_GRADIENT, nominal_window_size, nullptr, statuses);
+    }
+    // ... like DistanceToBoundary3d
+    std::vector<std::pair<double, bool>> DistanceToBoundaryBatch(const std::vector<Eigen::Vector3d>& locations) const {
+        const std::vector<double> pts = Flatten(locations);
+        std::vector<double> value(locations.size());
+        std::vector<uint8_t> st(locations.size());
+        QueryGradientsBatch(pts.data(), (int64_t)locations.size(), SDFGPU_QUERY_DISTANCE_TO_BOUNDARY, 0.0, value.data(), nullptr, st.data());
+        std::vector<std::pair<double, bool>> out(locations.size());
+        for (size_t i = 0; i < out.size(); ++i) out[i] = std::make_pair(value[i], st[i] == SDFGPU_QUERY_OK);
+        return out;
+    }
+
     // The reference's container, downloaded on first use (and again after DevicePointer() handed out write access).
     const SignedDistanceField& Host() const {
         if (!host_) {
@@ -185,6 +226,19 @@ public:
     bool HostCopyExists() const { return (bool)host_; }
 
 private:
+    std::vector<std::vector<double>> GradientBatch(const std::vector<Eigen::Vector3d>& locations, const int kind, const double window,
+                                                   std::vector<double>* values, std::vector<uint8_t>* statuses) const {
+        const std::vector<double> pts = Flatten(locations);
+        std::vector<double> value(locations.size()), grad(locations.size() * 3);
+        std::vector<uint8_t> st(locations.size());
+        QueryGradientsBatch(pts.data(), (int64_t)locations.size(), kind, window, value.data(), grad.data(), st.data());
+        std::vector<std::vector<double>> out(locations.size());
+        for (size_t i = 0; i < out.size(); ++i)
+            if (st[i] == SDFGPU_QUERY_OK) out[i] = std::vector<double>{grad[3 * i], grad[3 * i + 1], grad[3 * i + 2]};
+        if (values) *values = std::move(value);
+        if (statuses) *statuses = std::move(st);
+        return out;
+    }
     static std::vector<double> Flatten(const std::vector<Eigen::Vector3d>& locations) {
         std::vector<double> pts(locations.size() * 3);
         for (size_t i = 0; i < locations.size(); ++i) { pts[3 * i] = locations[i].x(); pts[3 * i + 1] = locations[i].y(); pts[3 * i + 2] = locations[i].z(); }

@@ -3,8 +3,9 @@
 // pysdf_tools surface use: constructors (:34-81), lock-guarded SetValue (:236-264), GetGradient /
 // GetGridAlignedGradient / GetFullGradient (:341-526), EstimateDistance (:699-961), serialisation
 // and file / message forms (src/sdf_tools/sdf.cpp:213-502), the local extrema map (sdf.cpp:23-207, on the GPU) and projection
-// out of collision / into the valid volume (:996-1190; batched on the GPU through DeviceSignedDistanceField::ProjectBatch).  Out
-// of scope here: AutoDiff gradients, RViz export.
+// out of collision / into the valid volume (:996-1190; batched on the GPU through DeviceSignedDistanceField::ProjectBatch), and
+// the smooth and autodiff gradients and DistanceToBoundary (:528-653, :963-988; batched on the GPU through
+// DeviceSignedDistanceField::QueryGradientsBatch).  Out of scope here: RViz export.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -21,6 +22,7 @@
 #include "arc_utilities/serialization.hpp"
 #include "arc_utilities/voxel_grid.hpp"
 #include "arc_utilities/zlib_helpers.hpp"
+#include "sdf_tools/autodiff.hpp"
 #include "sdf_tools/eigen_lite.hpp"
 #include "sdf_tools/gpu_context.hpp"
 
@@ -287,25 +289,25 @@ protected:
     }
     static double Bilinear(double l1, double h1, double l2, double h2, double q1, double q2, double ll, double lh, double hl, double hh) {
         // (multiplier * [h1-q1, q1-l1]) * [[ll, lh], [hl, hh]] * [h2-q2, q2-l2]^T, evaluated left to right (:699-727)
-        const double multiplier = 1.0 / ((h1 - l1) * (h2 - l2));
-        const double a0 = multiplier * (h1 - q1), a1 = multiplier * (q1 - l1);
-        const double r0 = a0 * ll + a1 * hl, r1 = a0 * lh + a1 * hh;
-        return r0 * (h2 - q2) + r1 * (q2 - l2);
+        return BilinearT<double>(l1, h1, l2, h2, q1, q2, ll, lh, hl, hh);
+    }
+    // EstimateDistanceInterpolateFromNeighborsGridFrame (:836-915) over T = double or AutoDiff3 (autodiff.hpp): the cell (x, y,
+    // z) is inside the grid; the corners are chosen from the value of q.
+    template <typename T>
+    T EstimateFromNeighborsGridFrameT(const T& q0, const T& q1, const T& q2, const int64_t x, const int64_t y, const int64_t z) const {
+        const Eigen::Vector4d c = GridIndexToLocationGridFrame(x, y, z);
+        const auto xi = AxisInterpolationIndices(x, GetNumXCells(), ValueOf(q0) - c(0));
+        const auto yi = AxisInterpolationIndices(y, GetNumYCells(), ValueOf(q1) - c(1));
+        const auto zi = AxisInterpolationIndices(z, GetNumZCells(), ValueOf(q2) - c(2));
+        const Eigen::Vector4d lo = GridIndexToLocationGridFrame(xi.first, yi.first, zi.first);
+        auto D = [&](int64_t a, int64_t b, int64_t cc) { return CorrectedCenterDistance(a, b, cc); };
+        return TrilinearT<T>(lo(0), lo(1), lo(2), GetResolution(), q0, q1, q2, D(xi.first, yi.first, zi.first),
+                             D(xi.first, yi.first, zi.second), D(xi.first, yi.second, zi.first), D(xi.first, yi.second, zi.second),
+                             D(xi.second, yi.first, zi.first), D(xi.second, yi.first, zi.second), D(xi.second, yi.second, zi.first),
+                             D(xi.second, yi.second, zi.second));            // (slope (pz - mz) * (1 / res), :745-771)
     }
     double EstimateFromNeighborsGridFrame(const Eigen::Vector4d& q, const int64_t x, const int64_t y, const int64_t z) const {
-        const Eigen::Vector4d c = GridIndexToLocationGridFrame(x, y, z);
-        const auto xi = AxisInterpolationIndices(x, GetNumXCells(), q(0) - c(0));
-        const auto yi = AxisInterpolationIndices(y, GetNumYCells(), q(1) - c(1));
-        const auto zi = AxisInterpolationIndices(z, GetNumZCells(), q(2) - c(2));
-        const Eigen::Vector4d lo = GridIndexToLocationGridFrame(xi.first, yi.first, zi.first);
-        const double res = GetResolution();
-        auto D = [&](int64_t a, int64_t b, int64_t cc) { return CorrectedCenterDistance(a, b, cc); };
-        const double mz = Bilinear(lo(0), lo(0) + res, lo(1), lo(1) + res, q(0), q(1), D(xi.first, yi.first, zi.first),
-                                   D(xi.first, yi.second, zi.first), D(xi.second, yi.first, zi.first), D(xi.second, yi.second, zi.first));
-        const double pz = Bilinear(lo(0), lo(0) + res, lo(1), lo(1) + res, q(0), q(1), D(xi.first, yi.first, zi.second),
-                                   D(xi.first, yi.second, zi.second), D(xi.second, yi.first, zi.second), D(xi.second, yi.second, zi.second));
-        const double slope = (pz - mz) * (1.0 / res);            // (:745-771)
-        return mz + ((q(2) - lo(2)) * slope);
+        return EstimateFromNeighborsGridFrameT<double>(q(0), q(1), q(2), x, y, z);
     }
 
 public:
@@ -318,6 +320,147 @@ public:
     std::pair<double, bool> EstimateDistance(const double x, const double y, const double z) const {
         return EstimateDistance4d(Eigen::Vector4d(x, y, z, 1.0));
     }
+
+    // ---- smooth and autodiff gradients, DistanceToBoundary (:528-653, :963-988) -----------------------------------------------
+    // One core, QueryGradient4d, answers all three kinds without throwing for a point, and is the yardstick of the GPU
+    // (sdfgpu_query_gradients, include/sdfgpu.h "Interpolated gradients"): its arithmetic order IS the specification --
+    // eigen_lite's left-to-right sums, no fused multiply-add, the operators of AutoDiff3 (autodiff.hpp).  Byte equality with real
+    // Eigen (AutoDiffScalar, its matrix products and Transform * vector) is UNVERIFIED: Eigen is not installed here.
+    //   SDFGPU_QUERY_AUTODIFF_GRADIENT: the location (x, y, z, 1) seeded with Unit(0..2) goes through W = inverse_origin_transform_
+    //     and the trilinear estimate as AutoDiff3; value = EstimateDistance4d's bits, gradient = the derivatives (world frame).
+    //   SDFGPU_QUERY_SMOOTH_GRADIENT: w = |window|; the seven EstimateDistance calls at p and p -+ w along each world axis, then
+    //     per axis (d+ - d-) / ((a + w) - (a - w)), else (d - d-) / (a - (a - w)), else (d+ - d) / ((a + w) - a), as
+    //     ComputeAxisSmoothGradient (:656-697) decides; value = the estimate at p.  A window of 0 gives 0 / 0 = NaN.
+    //   SDFGPU_QUERY_DISTANCE_TO_BOUNDARY: (a, b, c) = W (p, 1); each displacement std::min(a, size - a) (size = cells * res);
+    //     inside when all are >= 0; value = the displacement with the first least |displacement| (strict <, as minCoeff).
+    // A window end or point "in the grid" is decided on the floored doubles (GridFrameCell), never by an int64 cast.
+    // Two deviations from the reference (the precedent is the projection members): a NaN or infinite coordinate passed to a
+    // smooth or autodiff member throws std::invalid_argument (the reference casts NaN to int64), and so does a non-finite
+    // window.  The core reports the former as SDFGPU_QUERY_NON_FINITE (value and gradient NaN) and throws for the latter.
+    struct GradientQueryResult {
+        double value;                                            // estimate (oob outside), or the boundary displacement
+        double gradient[3];                                      // world frame; NaN where the reference returns no vector
+        uint8_t status;                                          // SDFGPU_QUERY_*
+    };
+
+    GradientQueryResult QueryGradient4d(const Eigen::Vector4d& location, const int kind, const double window = 0.0) const {
+        const double nan = std::numeric_limits<double>::quiet_NaN();
+        GradientQueryResult r{nan, {nan, nan, nan}, (uint8_t)SDFGPU_QUERY_OK};
+        const double x = location(0), y = location(1), z = location(2);
+        if (kind == SDFGPU_QUERY_DISTANCE_TO_BOUNDARY) {
+            const std::pair<double, bool> b = DistanceToBoundary4d(location);
+            r.value = b.first;
+            r.status = b.second ? (uint8_t)SDFGPU_QUERY_OK : (uint8_t)SDFGPU_QUERY_OUTSIDE;
+            return r;
+        }
+        if (kind != SDFGPU_QUERY_SMOOTH_GRADIENT && kind != SDFGPU_QUERY_AUTODIFF_GRADIENT)
+            throw std::invalid_argument("QueryGradient4d: unknown kind " + std::to_string(kind));
+        if (!std::isfinite(window)) throw std::invalid_argument("GetSmoothGradient: the window size must be finite");
+        if (!std::isfinite(x) || !std::isfinite(y) || !std::isfinite(z)) { r.status = SDFGPU_QUERY_NON_FINITE; return r; }
+        const Eigen::Vector4d q = inverse_origin_transform_ * Eigen::Vector4d(x, y, z, 1.0);
+        GRID_INDEX index;
+        if (!GridFrameCell(q, index)) { r.value = (double)GetOOBValue(); r.status = SDFGPU_QUERY_OUTSIDE; return r; }
+        if (kind == SDFGPU_QUERY_AUTODIFF_GRADIENT) {
+            const AutoDiff3 p0 = AutoDiff3::Seed(x, 0), p1 = AutoDiff3::Seed(y, 1), p2 = AutoDiff3::Seed(z, 2);
+            double w2g[12];
+            for (int row = 0; row < 3; ++row)
+                for (int col = 0; col < 4; ++col) w2g[row * 4 + col] = inverse_origin_transform_.matrix()(row, col);
+            const AutoDiff3 g0 = TransformRowT(w2g, p0, p1, p2), g1 = TransformRowT(w2g + 4, p0, p1, p2), g2 = TransformRowT(w2g + 8, p0, p1, p2);
+            const AutoDiff3 d = EstimateFromNeighborsGridFrameT<AutoDiff3>(g0, g1, g2, index.x, index.y, index.z);
+            r.value = d.v;
+            r.gradient[0] = d.d[0]; r.gradient[1] = d.d[1]; r.gradient[2] = d.d[2];
+            return r;
+        }
+        const double w = std::abs(window);
+        const std::pair<double, bool> c = EstimateInGrid(x, y, z);
+        r.value = c.first;
+        const double p[3] = {x, y, z};
+        for (int axis = 0; axis < 3; ++axis) {
+            double lo[3] = {x, y, z}, hi[3] = {x, y, z};
+            lo[axis] = p[axis] - w;
+            hi[axis] = p[axis] + w;
+            const std::pair<double, bool> m = EstimateInGrid(lo[0], lo[1], lo[2]), pl = EstimateInGrid(hi[0], hi[1], hi[2]);
+            // ComputeAxisSmoothGradient (:656-697); the query point is available here
+            if (m.second && pl.second) r.gradient[axis] = (pl.first - m.first) / (hi[axis] - lo[axis]);
+            else if (m.second) r.gradient[axis] = (c.first - m.first) / (p[axis] - lo[axis]);
+            else if (pl.second) r.gradient[axis] = (pl.first - c.first) / (hi[axis] - p[axis]);
+            else {
+                r.gradient[0] = r.gradient[1] = r.gradient[2] = nan;
+                r.status = SDFGPU_QUERY_WINDOW_TOO_LARGE;
+                return r;
+            }
+        }
+        return r;
+    }
+
+    // reference-named members
+    std::vector<double> GetSmoothGradient(const double x, const double y, const double z, const double nominal_window_size) const {
+        return GradientVector(QueryGradient4d(Eigen::Vector4d(x, y, z, 1.0), SDFGPU_QUERY_SMOOTH_GRADIENT, nominal_window_size));
+    }
+    std::vector<double> GetSmoothGradient3d(const Eigen::Vector3d& location, const double nominal_window_size) const {
+        return GetSmoothGradient(location.x(), location.y(), location.z(), nominal_window_size);
+    }
+    std::vector<double> GetSmoothGradient4d(const Eigen::Vector4d& location, const double nominal_window_size) const {
+        return GetSmoothGradient(location(0), location(1), location(2), nominal_window_size);
+    }
+    std::vector<double> GetSmoothGradient(const GRID_INDEX& index, const double nominal_window_size) const {
+        return GetSmoothGradient4d(GridIndexToLocation(index), nominal_window_size);
+    }
+    std::vector<double> GetSmoothGradient(const int64_t x_index, const int64_t y_index, const int64_t z_index,
+                                          const double nominal_window_size) const {
+        return GetSmoothGradient4d(GridIndexToLocation(x_index, y_index, z_index), nominal_window_size);
+    }
+    // (the reference notes "TODO: this does not work if you query at cell centers!": there the corners switch sides, and the
+    // derivative is the one-sided one of the corners chosen -- kept as is)
+    std::vector<double> GetAutoDiffGradient(const double x, const double y, const double z) const {
+        return GradientVector(QueryGradient4d(Eigen::Vector4d(x, y, z, 1.0), SDFGPU_QUERY_AUTODIFF_GRADIENT));
+    }
+    std::vector<double> GetAutoDiffGradient3d(const Eigen::Vector3d& location) const {
+        return GetAutoDiffGradient(location.x(), location.y(), location.z());
+    }
+    std::vector<double> GetAutoDiffGradient4d(const Eigen::Vector4d& location) const {
+        return GetAutoDiffGradient(location(0), location(1), location(2));
+    }
+    std::vector<double> GetAutoDiffGradient(const GRID_INDEX& index) const { return GetAutoDiffGradient4d(GridIndexToLocation(index)); }
+    std::vector<double> GetAutoDiffGradient(const int64_t x_index, const int64_t y_index, const int64_t z_index) const {
+        return GetAutoDiffGradient4d(GridIndexToLocation(x_index, y_index, z_index));
+    }
+
+    std::pair<double, bool> DistanceToBoundary(const double x, const double y, const double z) const {
+        return DistanceToBoundary4d(Eigen::Vector4d(x, y, z, 1.0));
+    }
+    std::pair<double, bool> DistanceToBoundary3d(const Eigen::Vector3d& location) const {
+        return DistanceToBoundary(location.x(), location.y(), location.z());
+    }
+    std::pair<double, bool> DistanceToBoundary4d(const Eigen::Vector4d& location) const {
+        const Eigen::Vector4d a = inverse_origin_transform_ * location;
+        const double displacements[3] = {std::min(a(0), x_size_ - a(0)), std::min(a(1), y_size_ - a(1)), std::min(a(2), z_size_ - a(2))};
+        const bool point_inside = displacements[0] >= 0.0 && displacements[1] >= 0.0 && displacements[2] >= 0.0;
+        int min_index = 0;                                       // Eigen's minCoeff(&i): the first least, strict <
+        double least = std::abs(displacements[0]);
+        for (int i = 1; i < 3; ++i)
+            if (std::abs(displacements[i]) < least) { least = std::abs(displacements[i]); min_index = i; }
+        return {displacements[min_index], point_inside};
+    }
+
+protected:
+    // EstimateDistance(x, y, z) with the cell decided on the floored doubles
+    std::pair<double, bool> EstimateInGrid(const double x, const double y, const double z) const {
+        const Eigen::Vector4d q = inverse_origin_transform_ * Eigen::Vector4d(x, y, z, 1.0);
+        GRID_INDEX index;
+        if (!GridFrameCell(q, index)) return std::make_pair((double)GetOOBValue(), false);
+        return std::make_pair(EstimateFromNeighborsGridFrame(q, index.x, index.y, index.z), true);
+    }
+    static std::vector<double> GradientVector(const GradientQueryResult& r) {
+        switch (r.status) {
+            case SDFGPU_QUERY_OK: return std::vector<double>{r.gradient[0], r.gradient[1], r.gradient[2]};
+            case SDFGPU_QUERY_OUTSIDE: return std::vector<double>();
+            case SDFGPU_QUERY_WINDOW_TOO_LARGE: throw std::runtime_error("Window size for GetSmoothGradient is too large for SDF");
+            default: throw std::invalid_argument("Cannot compute a gradient at a non-finite location");
+        }
+    }
+
+public:
 
     // ---- projection out of collision / into the valid volume (:996-1190) ----------------------------------------------------
     // One counted walk is the core of every member below and the yardstick of the GPU (sdfgpu_project_points, include/sdfgpu.h

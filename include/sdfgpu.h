@@ -537,6 +537,43 @@ int sdfgpu_project_points(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64
                           double stepsize_multiplier, int max_steps, int mode, const double* points, int64_t n_points,
                           double* out_points, uint8_t* out_status, int32_t* out_steps);
 
+/* -------------------------------------------------------------------------
+ * Interpolated gradients (SignedDistanceField::GetSmoothGradient*, GetAutoDiffGradient*, DistanceToBoundary*; reference
+ * include/sdf_tools/sdf.hpp:528-653, 963-988), one lane per point, all arithmetic in double without fused multiply-add, bit-equal
+ * to the host core SignedDistanceField::QueryGradient4d (include/sdf_tools/sdf.hpp, whose comment states the arithmetic).
+ * For a world-frame point p, with res the cell size and W the world -> grid transform (12 host doubles, row-major 3x4):
+ *   kind SDFGPU_QUERY_AUTODIFF_GRADIENT: the exact derivative of the trilinear estimate (sdfgpu_query_points' distance) with
+ *     respect to p, by forward-mode dual numbers through W and the estimate; value = that estimate, bit for bit.
+ *   kind SDFGPU_QUERY_SMOOTH_GRADIENT: central differences of the estimate over p -+ |window| along each world axis, one-sided
+ *     where one end's cell is outside the grid; value = the estimate at p.  window = 0 gives a NaN (0 / 0) gradient.
+ *   kind SDFGPU_QUERY_DISTANCE_TO_BOUNDARY: (a, b, c) = W p; per axis min(a, size - a) (size = cells * res); value = the one
+ *     with the first least magnitude; status OK when all three are >= 0.  The gradient is not computed (NaN).  Non-finite points
+ *     are not refused for this kind: they give what that arithmetic gives.
+ * Per point: d_value[i], d_gradient[3i..3i+2] (world frame; NaN where the reference returns an empty vector or throws),
+ * d_status[i] one of SDFGPU_QUERY_* below.  Any output may be NULL.  n = 0 is a no-op.  A point or window end is inside the grid
+ * when floor(q * (1 / res)) is, decided on the doubles.  Outside (status OUTSIDE), value = oob_value for the two gradient kinds.
+ * A NaN or infinite coordinate (smooth, autodiff): status NON_FINITE, value NaN -- a deviation, the reference casts NaN to int64.
+ * Refused (SDFGPU_ERR_INVALID_ARGUMENT, with a message): null field, or null points with n > 0; non-positive dims; cells
+ * overflowing int64; resolution not positive and finite; a non-finite window; an unknown kind; null W.  Cell indices are int64.
+ *   sdfgpu_query_gradients_device: device points and outputs, enqueued on `stream`.
+ *   sdfgpu_query_gradients: host points and outputs against a field in HBM; synchronous, ordered as sdfgpu_query_points.
+ * ------------------------------------------------------------------------- */
+#define SDFGPU_QUERY_SMOOTH_GRADIENT 0
+#define SDFGPU_QUERY_AUTODIFF_GRADIENT 1
+#define SDFGPU_QUERY_DISTANCE_TO_BOUNDARY 2
+
+#define SDFGPU_QUERY_OK 0                /* gradient computed / point inside the volume                                     */
+#define SDFGPU_QUERY_OUTSIDE 1           /* reference returns an empty vector / point_inside == false                       */
+#define SDFGPU_QUERY_WINDOW_TOO_LARGE 2  /* reference throws "Window size for GetSmoothGradient is too large for SDF"       */
+#define SDFGPU_QUERY_NON_FINITE 3        /* NaN / inf coordinate (smooth, autodiff)                                          */
+
+int sdfgpu_query_gradients_device(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                                  const double world_to_grid[12], float oob_value, int kind, double window, const double* d_points,
+                                  int64_t n_points, double* d_value, double* d_gradient, uint8_t* d_status, void* stream);
+int sdfgpu_query_gradients(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                           const double world_to_grid[12], float oob_value, int kind, double window, const double* points,
+                           int64_t n_points, double* out_value, double* out_gradient, uint8_t* out_status);
+
 /* Red zones (round 6).  With SDFGPU_REDZONE=1 in the environment when sdfgpu_create runs -- or after
  * sdfgpu_set_option(h, "redzone", 1) -- every device allocation of the library (scratch fields, status block, extrema slots,
  * staging buffers, sdfgpu_device_malloc memory) carries 4 KiB of canary bytes in front and behind, and every entry point that

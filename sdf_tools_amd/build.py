@@ -33,10 +33,11 @@ def _hipcc():
 
 
 def build_libsdfgpu(force=False, verbose=False):
-    """Seven translation units -> objects (compiled side by side) -> libsdfgpu.so: sdfgpu.hip (C ABI, host orchestration, most
+    """Eight translation units -> objects (compiled side by side) -> libsdfgpu.so: sdfgpu.hip (C ABI, host orchestration, most
     kernels), sdfgpu_envelope_tu.hip (the far-field kernel's instantiations), sdfgpu_dense6_tu.hip (the shell pass),
     sdfgpu_components.hip (connected components), sdfgpu_topology.hip (component topology), sdfgpu_convex.hip (local extrema
-    and convex segments) and sdfgpu_project.hip (projection out of collision).  Each object is rebuilt when its
+    and convex segments), sdfgpu_project.hip (projection out of collision) and sdfgpu_query.hip (smooth and autodiff gradients,
+    distance to the boundary).  Each object is rebuilt when its
     source or ANY header it can include is newer (a stale library after a header-only edit is the kind of bug that
     invalidates measurements without failing anything)."""
     from concurrent.futures import ThreadPoolExecutor
@@ -50,7 +51,9 @@ def build_libsdfgpu(force=False, verbose=False):
              (os.path.join(CSRC, "sdfgpu_topology.hip"), [os.path.join(CSRC, "sdfgpu_topology.hpp")]),
              (os.path.join(CSRC, "sdfgpu_convex.hip"), [os.path.join(CSRC, f) for f in ("sdfgpu_convex.hpp", "sdfgpu_kernels.hpp")]),
              (os.path.join(CSRC, "sdfgpu_project.hip"), [os.path.join(CSRC, f) for f in ("sdfgpu_project.hpp", "sdfgpu_kernels.hpp")] +
-              [os.path.join(INCLUDE, "sdfgpu.h")])]
+              [os.path.join(INCLUDE, "sdfgpu.h")]),
+             (os.path.join(CSRC, "sdfgpu_query.hip"), [os.path.join(CSRC, f) for f in ("sdfgpu_query.hpp", "sdfgpu_kernels.hpp")] +
+              [os.path.join(INCLUDE, "sdfgpu.h"), os.path.join(INCLUDE, "sdf_tools", "autodiff.hpp")])]
     objdir = os.path.join(CSRC, ".obj")
     os.makedirs(objdir, exist_ok=True)
     todo, objs = [], []
@@ -65,7 +68,7 @@ def build_libsdfgpu(force=False, verbose=False):
     if verbose:
         for cmd in todo:
             print(" ".join(cmd))
-    with ThreadPoolExecutor(max_workers=7) as pool:
+    with ThreadPoolExecutor(max_workers=8) as pool:
         list(pool.map(subprocess.check_call, todo))
     cmd = [_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-pthread"] + objs + ["-o", LIB]
     if verbose:

@@ -32,12 +32,17 @@ EXPORTS = [
     "sdfgpu_component_topology_device", "sdfgpu_component_topology", "sdfgpu_component_topology_cells",
     "sdfgpu_local_extrema_device", "sdfgpu_local_extrema", "sdfgpu_convex_segments_cells", "sdfgpu_convex_last_info",
     "sdfgpu_project_step_limit", "sdfgpu_project_points_device", "sdfgpu_project_points",
+    "sdfgpu_query_gradients_device", "sdfgpu_query_gradients",
 ]
 
 # include/sdfgpu.h "Projection": modes and per-point statuses
 PROJECT_OUT_OF_COLLISION, PROJECT_INTO_VALID_VOLUME = 0, 1
 PROJECT_CONVERGED, PROJECT_FLAT_GRADIENT, PROJECT_NO_GRADIENT, PROJECT_LEFT_GRID, PROJECT_STEP_LIMIT, PROJECT_NON_FINITE = range(6)
 PROJECT_MAX_STEPS_CEILING = 1048576
+
+# include/sdfgpu.h "Interpolated gradients": kinds and per-point statuses
+QUERY_SMOOTH_GRADIENT, QUERY_AUTODIFF_GRADIENT, QUERY_DISTANCE_TO_BOUNDARY = 0, 1, 2
+QUERY_OK, QUERY_OUTSIDE, QUERY_WINDOW_TOO_LARGE, QUERY_NON_FINITE = range(4)
 
 
 class SdfGpuError(RuntimeError):
@@ -129,6 +134,8 @@ def load_library():
     L.sdfgpu_project_step_limit.argtypes = [i64, i64, i64, dbl, ci, vp]
     L.sdfgpu_project_points_device.argtypes = [vp, vp, i64, i64, i64, dbl, vp, vp, dbl, dbl, ci, ci, vp, i64, vp, vp, vp, vp]
     L.sdfgpu_project_points.argtypes = [vp, vp, i64, i64, i64, dbl, vp, vp, dbl, dbl, ci, ci, vp, i64, vp, vp, vp]
+    L.sdfgpu_query_gradients_device.argtypes = [vp, vp, i64, i64, i64, dbl, vp, ctypes.c_float, ci, dbl, vp, i64, vp, vp, vp, vp]
+    L.sdfgpu_query_gradients.argtypes = [vp, vp, i64, i64, i64, dbl, vp, ctypes.c_float, ci, dbl, vp, i64, vp, vp, vp]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is ctypes.c_int or name not in ("sdfgpu_version", "sdfgpu_last_error"):
@@ -526,6 +533,28 @@ class SdfGpu:
             self._h, d_sdf or None, nx, ny, nz, float(resolution), w, g, float(minimum_distance), float(stepsize_multiplier),
             int(max_steps), int(mode), d_points or None, int(n_points), d_out_points or None, d_status or None, d_steps or None,
             stream or None))
+
+    def query_gradients(self, d_sdf, shape, resolution, points, world_to_grid, kind, window=0.0, oob_value=math.inf, outputs=True):
+        """Smooth / autodiff gradients or distances to the boundary (kind QUERY_*) of host points [n, 3] float64 against a field in
+        HBM (d_sdf: device address).  world_to_grid: 3x4 (or 4x4).  Returns (value [n], gradient [n, 3], status uint8 [n]);
+        outputs=False passes NULL for all three (and returns None)."""
+        nx, ny, nz = (int(v) for v in shape)
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        n = pts.shape[0]
+        value, grad, status = np.empty(n, np.float64), np.empty((n, 3), np.float64), np.empty(n, np.uint8)
+        self._check(self._lib.sdfgpu_query_gradients(self._h, ctypes.c_void_p(int(d_sdf)), nx, ny, nz, float(resolution),
+                                                     _transform12(world_to_grid), float(oob_value), int(kind), float(window),
+                                                     pts.ctypes.data if n else None, n, value.ctypes.data if outputs else None,
+                                                     grad.ctypes.data if outputs else None, status.ctypes.data if outputs else None))
+        return (value, grad, status) if outputs else None
+
+    def query_gradients_device(self, d_sdf, shape, resolution, d_points, n_points, world_to_grid, kind, window=0.0,
+                               oob_value=math.inf, d_value=0, d_gradient=0, d_status=0, stream=0):
+        """Device form of query_gradients (device addresses as ints; any output may be 0), enqueued on `stream`."""
+        nx, ny, nz = (int(v) for v in shape)
+        self._check(self._lib.sdfgpu_query_gradients_device(
+            self._h, d_sdf or None, nx, ny, nz, float(resolution), _transform12(world_to_grid), float(oob_value), int(kind),
+            float(window), d_points or None, int(n_points), d_value or None, d_gradient or None, d_status or None, stream or None))
 
     def convex_last_info(self):
         """The last extrema computation on this handle: {rounds, cycles, longest_cycle, longest_entry}."""

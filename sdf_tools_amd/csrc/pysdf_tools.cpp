@@ -252,7 +252,56 @@ PYBIND11_MODULE(pysdf_tools, m) {
         }, py::arg("points"), py::arg("minimum_distance") = 0.0, py::arg("stepsize_multiplier") = 1.0 / 8.0, py::arg("max_steps") = 0,
            py::arg("into_valid_volume_only") = false,
            "n x ProjectOutOfCollisionToMinimumDistance3d (or ProjectIntoValidVolumeToMinimumDistance3d) counted, on one host core: "
-           "(points [n, 3], status uint8 [n]: SDFGPU_PROJECT_*, steps int32 [n])");
+           "(points [n, 3], status uint8 [n]: SDFGPU_PROJECT_*, steps int32 [n])") 
+        // smooth and autodiff gradients, DistanceToBoundary (reference sdf.hpp:528-653, 963-988): (x, y, z) forms with the
+        // reference's results (an empty list outside the grid) and exceptions (RuntimeError for a window too large for the field,
+        // ValueError for a non-finite location or window)
+        .def("GetSmoothGradient", [](const SignedDistanceField& s, double x, double y, double z, double nominal_window_size) {
+            return s.GetSmoothGradient(x, y, z, nominal_window_size);
+        }, py::arg("x"), py::arg("y"), py::arg("z"), py::arg("nominal_window_size"))
+        .def("GetAutoDiffGradient", [](const SignedDistanceField& s, double x, double y, double z) { return s.GetAutoDiffGradient(x, y, z); },
+             py::arg("x"), py::arg("y"), py::arg("z"))
+        .def("DistanceToBoundary", [](const SignedDistanceField& s, double x, double y, double z) { return s.DistanceToBoundary(x, y, z); },
+             py::arg("x"), py::arg("y"), py::arg("z"))
+        .def("QueryGradientsNumpyHost", [](const SignedDistanceField& s, const py::array_t<double, py::array::c_style | py::array::forcecast>& points,
+                                           int kind, double window) {
+            // the host core (SignedDistanceField::QueryGradient4d) over [n, 3] points on one host core: the checker of
+            // DeviceSignedDistanceField.QueryGradientsBatch
+            if (points.ndim() != 2 || points.shape(1) != 3) throw std::invalid_argument("points must be [n, 3] float64 (world frame)");
+            if (kind != SDFGPU_QUERY_DISTANCE_TO_BOUNDARY) (void)s.QueryGradient4d(Eigen::Vector4d(0.0, 0.0, 0.0, 1.0), kind, window);  // (argument check, also for n = 0)
+            const int64_t n = points.shape(0);
+            py::array_t<double> value({n});
+            py::array_t<double> gradient({n, (int64_t)3});
+            py::array_t<uint8_t> status({n});
+            {
+                py::gil_scoped_release release;
+                const double* p = points.data();
+                double* v = value.mutable_data();
+                double* g = gradient.mutable_data();
+                uint8_t* st = status.mutable_data();
+                for (int64_t i = 0; i < n; ++i) {
+                    const SignedDistanceField::GradientQueryResult r = s.QueryGradient4d(Eigen::Vector4d(p[3 * i], p[3 * i + 1], p[3 * i + 2], 1.0),
+                                                                                          kind, window);
+                    v[i] = r.value;
+                    g[3 * i] = r.gradient[0]; g[3 * i + 1] = r.gradient[1]; g[3 * i + 2] = r.gradient[2];
+                    st[i] = r.status;
+                }
+            }
+            return py::make_tuple(value, gradient, status);
+        }, py::arg("points"), py::arg("kind"), py::arg("window") = 0.0,
+           "n x QueryGradient4d on one host core (kind SDFGPU_QUERY_*: 0 smooth with `window`, 1 autodiff, 2 distance to boundary): "
+           "(value [n], gradient [n, 3], status uint8 [n]: SDFGPU_QUERY_*)")
+        .def(py::init<const Isometry3d&, const std::string&, double, int64_t, int64_t, int64_t, float>(), py::arg("origin_transform"),
+             py::arg("frame"), py::arg("resolution"), py::arg("x_cells"), py::arg("y_cells"), py::arg("z_cells"), py::arg("oob_value"),
+             "a field of this geometry on the host, every cell oob_value")
+        .def("SetRawDataNumpy", [](SignedDistanceField& s, const py::array_t<float, py::array::c_style | py::array::forcecast>& data) {
+            // the whole [x][y][z] field at once (refused while locked)
+            if (data.ndim() != 3 || data.shape(0) != s.GetNumXCells() || data.shape(1) != s.GetNumYCells() || data.shape(2) != s.GetNumZCells())
+                throw std::invalid_argument("data must be float32 [x_cells, y_cells, z_cells]");
+            float* dst = s.MutableDataForBuild();
+            if (!dst) throw std::runtime_error("the field is locked");
+            std::memcpy(dst, data.data(), (size_t)data.size() * sizeof(float));
+        }, py::arg("data"));
 
     // the field left in HBM (include/sdf_tools/device_sdf.hpp): batched queries without the download.  A pybind thread is the
     // thread that owns the libsdfgpu context, so build, query and drop the object from the same Python thread.
@@ -286,6 +335,20 @@ PYBIND11_MODULE(pysdf_tools, m) {
         }, py::arg("points"), py::arg("minimum_distance") = 0.0, py::arg("stepsize_multiplier") = 1.0 / 8.0, py::arg("max_steps") = 0,
            py::arg("into_valid_volume_only") = false,
            "ProjectOutOfCollisionNumpyHost's walk for n points in one kernel (sdfgpu_project_points): (points [n, 3], status [n], steps [n])")
+        .def("QueryGradientsBatch", [](const sdf_tools::DeviceSignedDistanceField& d, const py::array_t<double, py::array::c_style | py::array::forcecast>& points,
+                                       int kind, double window) {
+            if (points.ndim() != 2 || points.shape(1) != 3) throw std::invalid_argument("points must be [n, 3] float64 (world frame)");
+            const int64_t n = points.shape(0);
+            py::array_t<double> value({n});
+            py::array_t<double> gradient({n, (int64_t)3});
+            py::array_t<uint8_t> status({n});
+            {
+                py::gil_scoped_release release;
+                d.QueryGradientsBatch(points.data(), n, kind, window, value.mutable_data(), gradient.mutable_data(), status.mutable_data());
+            }
+            return py::make_tuple(value, gradient, status);
+        }, py::arg("points"), py::arg("kind"), py::arg("window") = 0.0,
+           "QueryGradientsNumpyHost's answers for n points in one kernel (sdfgpu_query_gradients): (value [n], gradient [n, 3], status [n])")
         .def("QueryBatch", [](const sdf_tools::DeviceSignedDistanceField& d,
                               const py::array_t<double, py::array::c_style | py::array::forcecast>& points, bool enable_edge_gradients) {
             if (points.ndim() != 2 || points.shape(1) != 3) throw std::invalid_argument("points must be [n, 3] float64 (world frame)");

@@ -15,6 +15,7 @@
 #include "sdfgpu_topology.hpp"
 #include "sdfgpu_convex.hpp"
 #include "sdfgpu_project.hpp"
+#include "sdfgpu_query.hpp"
 
 #include <sys/mman.h>
 #if defined(__SSE2__)
@@ -2978,6 +2979,74 @@ int sdfgpu_project_points(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64
         if (int rc = copy_to_host(h, out_points, base + o_o, n * 24, s)) return rc;
         if (out_steps) if (int rc = copy_to_host(h, out_steps, base + o_s, n * 4, s)) return rc;
         if (out_status) if (int rc = copy_to_host(h, out_status, base + o_t, n, s)) return rc;
+        return SDFGPU_OK;
+    });
+}
+
+namespace {
+int check_query_gradients_args(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                               const double* world_to_grid, int kind, double window, const double* points, int64_t n_points,
+                               GradientQueryArgs& a) {
+    if (!d_sdf) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "gradient query: null field pointer");
+    if (n_points < 0 || n_points > ((int64_t)1 << 40)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "gradient query: point count %lld out of range [0, 2^40]", (long long)n_points);
+    if (n_points > 0 && !points) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "gradient query: null points");
+    if (!world_to_grid) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "gradient query: world_to_grid is required");
+    if (nx <= 0 || ny <= 0 || nz <= 0 || nx > INT64_MAX / ny || nx * ny > INT64_MAX / nz)
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "gradient query: unsupported grid %lld x %lld x %lld", (long long)nx, (long long)ny, (long long)nz);
+    if (!(resolution > 0.0) || !std::isfinite(resolution)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "gradient query: resolution must be positive and finite");
+    if (kind != SDFGPU_QUERY_SMOOTH_GRADIENT && kind != SDFGPU_QUERY_AUTODIFF_GRADIENT && kind != SDFGPU_QUERY_DISTANCE_TO_BOUNDARY)
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "gradient query: unknown kind %d", kind);
+    if (!std::isfinite(window)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "gradient query: the window must be finite");
+    a = GradientQueryArgs{};
+    a.sdf = d_sdf; a.n = n_points; a.nx = nx; a.ny = ny; a.nz = nz; a.kind = kind;
+    for (int i = 0; i < 12; ++i) a.w2g[i] = world_to_grid[i];
+    return SDFGPU_OK;
+}
+}  // namespace
+
+int sdfgpu_query_gradients_device(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                                  const double world_to_grid[12], float oob_value, int kind, double window, const double* d_points,
+                                  int64_t n_points, double* d_value, double* d_gradient, uint8_t* d_status, void* stream) {
+    return rz_wrap(h, stream, [&]() -> int {
+        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
+        GradientQueryArgs a;
+        if (int rc = check_query_gradients_args(h, d_sdf, nx, ny, nz, resolution, world_to_grid, kind, window, d_points, n_points, a)) return rc;
+        if (n_points == 0 || (!d_value && !d_gradient && !d_status)) return SDFGPU_OK;
+        HIP_TRY(h, hipSetDevice(h->device));
+        a.points = d_points; a.value = d_value; a.gradient = d_gradient; a.status = d_status;
+        query_gradients_prepare(a, resolution, window, oob_value);
+        HIP_TRY(h, query_gradients_launch(a, (hipStream_t)stream));
+        return SDFGPU_OK;
+    });
+}
+
+int sdfgpu_query_gradients(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                           const double world_to_grid[12], float oob_value, int kind, double window, const double* points,
+                           int64_t n_points, double* out_value, double* out_gradient, uint8_t* out_status) {
+    return rz_wrap(h, nullptr, [&]() -> int {
+        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
+        GradientQueryArgs a;
+        if (int rc = check_query_gradients_args(h, d_sdf, nx, ny, nz, resolution, world_to_grid, kind, window, points, n_points, a)) return rc;
+        if (n_points == 0 || (!out_value && !out_gradient && !out_status)) return SDFGPU_OK;
+        HIP_TRY(h, hipSetDevice(h->device));
+        // staging in the context (shared with sdfgpu_query_points): points | gradient | value | status
+        const size_t n = (size_t)n_points;
+        const size_t o_g = n * 24, o_v = o_g + n * 24, o_s = o_v + n * 8, total = o_s + ((n + 255) & ~(size_t)255);
+        if (int rc = ensure(h, h->query_stage, total, "query staging")) return rc;
+        char* base = (char*)h->query_stage.ptr;
+        // the ordering of sdfgpu_query_points: the null stream, behind this handle's last build
+        hipStream_t s = nullptr;
+        if (h->order_valid && h->order_stream != nullptr) HIP_TRY(h, hipStreamWaitEvent(s, h->build_done_ev, 0));
+        if (int rc = copy_from_host(h, base, points, n * 24, s)) return rc;
+        a.points = (const double*)base;
+        a.gradient = out_gradient ? (double*)(base + o_g) : nullptr;
+        a.value = out_value ? (double*)(base + o_v) : nullptr;
+        a.status = out_status ? (uint8_t*)(base + o_s) : nullptr;
+        query_gradients_prepare(a, resolution, window, oob_value);
+        HIP_TRY(h, query_gradients_launch(a, s));
+        if (out_gradient) if (int rc = copy_to_host(h, out_gradient, base + o_g, n * 24, s)) return rc;
+        if (out_value) if (int rc = copy_to_host(h, out_value, base + o_v, n * 8, s)) return rc;
+        if (out_status) if (int rc = copy_to_host(h, out_status, base + o_s, n, s)) return rc;
         return SDFGPU_OK;
     });
 }
