@@ -121,7 +121,9 @@ int staged_upload(HostTeam& team_pool, size_t bytes, size_t chunk, int team, Fil
     auto chunk_bytes = [&](int64_t i) { return std::min(chunk, bytes - (size_t)i * chunk); };
     auto slice = [&](int64_t i, int w) {
         const size_t len = chunk_bytes(i);
-        const size_t per = ((len / (size_t)team) + 4095) & ~(size_t)4095;
+        // (ceil(len / team) rounded up to 4096: with len / team rounded down, a chunk shorter than the team -- or one just past a
+        // multiple of 4096 team -- had slices that covered none or not all of it, and its staging buffer went up unfilled)
+        const size_t per = ((len + (size_t)team - 1) / (size_t)team + 4095) & ~(size_t)4095;
         const size_t b = std::min(len, (size_t)w * per), e = std::min(len, b + per);
         if (e > b) fill((int)(i & 1), b, (size_t)i * chunk + b, e - b);
         if (kPerChunkCounters) filled[(size_t)i].fetch_add(1, std::memory_order_release);
@@ -203,7 +205,7 @@ int staged_drain(HostTeam& team_pool, size_t bytes, size_t chunk, int team, Issu
                     std::this_thread::yield();
                 }
                 const size_t len = chunk_bytes(i);
-                const size_t per = ((len / (size_t)team) + 4095) & ~(size_t)4095;
+                const size_t per = ((len + (size_t)team - 1) / (size_t)team + 4095) & ~(size_t)4095;     // (as in staged_upload)
                 const size_t b = std::min(len, (size_t)s * per), e = std::min(len, b + per);
                 if (e > b) drain((int)(i & 1), b, (size_t)i * chunk + b, e - b);
                 copied[(size_t)i].fetch_add(1, std::memory_order_release);

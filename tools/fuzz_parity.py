@@ -14,6 +14,9 @@ import numpy as np  # noqa: E402
 from oracle import oracle as O  # noqa: E402
 from sdf_tools_amd import capi, synth  # noqa: E402
 
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+import analysis_scenes as AS  # noqa: E402
+
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
 seed = int(sys.argv[2]) if len(sys.argv) > 2 else 0
 rng = np.random.default_rng(seed)
@@ -152,6 +155,7 @@ while time.time() - t0 < budget:
     # SDFGPU_REDZONE=1 every buffer the library owns -- the ranks' slabs and exchange buffers included -- and every
     # sdfgpu_device_malloc buffer used here carries canaries that each call checks.
     mode = str(rng.choice(["host", "guard", "guard", "bits", "multi", "rz_out"]))
+    values_bad = None                                   # rz_out: what the gradient / query value check found
     if os.environ.get("FUZZ_GUARD") and mode == "host":
         mode = "guard"
     if mode == "multi" and (shape[0] < 4 or vb and rng.random() < 0.5):
@@ -175,15 +179,29 @@ while time.time() - t0 < budget:
         ctx.build_device(d_in, shape, d_out, res, vb, 0)
         ext = ctx.get_extrema()
         got = ctx.copy_to_host(np.empty(shape, np.float32), d_out)
-        if rng.random() < 0.3:                      # the gradient and query kernels on the fresh field, exact-size outputs (values: tests/)
+        if rng.random() < 0.3:                      # the gradient and query kernels on the fresh field, exact-size outputs
             d_g = ctx.device_malloc(nvox * 12)
             ctx.gradient_device(d_out, shape, d_g, res, True, False, 0)
             npts = 257
             pts = (rng.random((npts, 3)) * (np.asarray(shape) * res * 1.2) - 0.1 * res).astype(np.float64)
             d_p, d_d, d_gr, d_f = ctx.device_malloc(npts * 24), ctx.device_malloc(npts * 8), ctx.device_malloc(npts * 24), ctx.device_malloc(npts)
             ctx.copy_from_host(d_p, pts)
-            ctx.query_points_device(d_out, shape, res, d_p, npts, d_d, d_gr, d_f, enable_edge_gradients=bool(rng.integers(0, 2)))
+            q_edge = bool(rng.integers(0, 2))
+            ctx.query_points_device(d_out, shape, res, d_p, npts, d_d, d_gr, d_f, enable_edge_gradients=q_edge)
             ctx.redzone_check()
+            # their values against the numpy restatements (tests/analysis_scenes.py): the field itself is checked below
+            g32 = ctx.copy_to_host(np.empty(shape + (3,), np.float32), d_g)
+            q_d, q_g, q_f = (ctx.copy_to_host(np.empty(npts, np.float64), d_d), ctx.copy_to_host(np.empty((npts, 3), np.float64), d_gr),
+                             ctx.copy_to_host(np.empty(npts, np.uint8), d_f))
+            w_d, w_g, w_f = AS.query_points(got, res, pts, np.inf, q_edge)
+            w32 = AS.grid_gradient(got, res, True).astype(np.float32)
+            same_g = np.all((g32.view(np.uint32) == w32.view(np.uint32)) | (np.isnan(g32) & np.isnan(w32)))
+            same_q = np.array_equal(q_f, w_f) and np.all((q_g.view(np.uint64) == w_g.view(np.uint64)) | (np.isnan(q_g) & np.isnan(w_g)))
+            with np.errstate(invalid="ignore"):             # (the query distance kernel may fuse products with sums: 1e-9)
+                near = np.isclose(q_d, w_d, rtol=1e-9, atol=1e-9) | (np.isnan(q_d) & np.isnan(w_d)) | ((q_d == w_d) & np.isinf(w_d))
+            if not (same_g and same_q and near.all()):      # (reported with the field's own check below, which saves the scene)
+                values_bad = "gradient / query values differ: gradient %s query %s distance %d" % (bool(same_g), bool(same_q),
+                                                                                                   int((~near).sum()))
             for ptr in (d_g, d_p, d_d, d_gr, d_f):
                 ctx.device_free(ptr)
         ctx.device_free(d_in)
@@ -226,11 +244,11 @@ while time.time() - t0 < budget:
     else:
         got, ext = ctx.build(m, res, vb)
     want, want_ext, _ = O.exact_sdf(m, res, vb)
-    if not np.array_equal(got.view(np.uint32), want.view(np.uint32)) or tuple(ext) != tuple(float(v) for v in want_ext):
+    if not np.array_equal(got.view(np.uint32), want.view(np.uint32)) or tuple(ext) != tuple(float(v) for v in want_ext) or values_bad:
         bad = np.argwhere(got.view(np.uint32) != want.view(np.uint32))
         os.makedirs("gpurun_out", exist_ok=True)
         np.save("gpurun_out/fuzz_fail_mask.npy", m)
-        print("MISMATCH shape", shape, "kind", kind, "res", res, "vb", vb, "bad", len(bad), bad[:3].tolist(), ext, want_ext)
+        print("MISMATCH shape", shape, "kind", kind, "res", res, "vb", vb, "bad", len(bad), bad[:3].tolist(), ext, want_ext, values_bad or "")
         sys.exit(1)
     n += 1
     MODES[mode] = MODES.get(mode, 0) + 1
