@@ -138,6 +138,14 @@ struct sdfgpu_context {
     bool last_plane_skip = false;    // the last build used it (sdfgpu_debug_copy_yzsweep fills the skipped planes in)
     int64_t last_dims[3] = {0, 0, 0};
     bool dense3_fixed = true;        // KD3's nz = 512 instance (option "dense3_fixed")
+    // Serpentine tile order (option "ball_serpentine"): a whole build that writes the buffer the handle's last KD launch wrote, at
+    // the same size, walks KD's tiles in the opposite order -- it starts on the lines the last one finished with, which are
+    // the ones the Infinity Cache still holds; walked the same way round every time, an LRU-like cache has evicted each
+    // line just before it is reached.  Speed only: the field, the maxima and the flags do not depend on the order.
+    bool ball_serpentine = true;
+    const float* serp_out = nullptr; // output buffer and voxel count of the last whole-build KD launch, and its direction
+    int64_t serp_n = 0;
+    int serp_flip = 0;
     int shell_min_words = kShellMinWords;   // option "shell_min_words"
     int shell_budget_den = 8;        // ... for scenes with at most 1 / 8 of their voxels undecided behind KD3 (option "shell_budget_den"): Bernoulli
                                      // p = 0.01 leaves 8 % (0.78 ms against the far-field pair's 0.96), p = 0.007 17 % (1.07 ms against 0.97)
@@ -846,7 +854,7 @@ int fold_slots(sdfgpu_handle h, uint32_t* d_maxdsq, hipStream_t s, uint32_t* res
 int launch_ball_dense(sdfgpu_handle h, const uint32_t* d_bits, float* d_out, int64_t rows_x, int64_t out_lo, int64_t out_hi,
                       int64_t ny, int64_t nz, double resolution, uint32_t* d_maxdsq, uint32_t* d_uncert, hipStream_t s,
                       uint32_t* d_fix_needed = nullptr, bool early_out = false, int vb = 0, int64_t nx_glob = 0, int radius = 2,
-                      const uint32_t* d_guard = nullptr) {
+                      const uint32_t* d_guard = nullptr, int flip = 0) {
     const int R = radius == 3 ? kBall3R : kBallR;                   // 3: KD3 (sdfgpu_dense3.hpp; whole-grid builds without virtual border only)
     DenseArgs a{};
     a.early_out = early_out ? 1 : 0;
@@ -878,6 +886,7 @@ int launch_ball_dense(sdfgpu_handle h, const uint32_t* d_bits, float* d_out, int
     a.slots = h->d_slots; a.uncertified = d_uncert;
     a.reason = early_out ? h->d_small + 21 : nullptr;                // (whole builds: the context's status block; stage calls have none)
     a.nt_store = h->nt_store;
+    a.flip = radius == 3 ? 0 : flip;
     a.guard = d_guard;
     // KD3 gives up at once when a wave holds more undecided voxels than the stage behind it takes: KF's per-tile cap -- or, with
     // the shell pass in between (which turns words, not voxels, around and leaves KF what lies beyond d^2 = 36), three quarters
@@ -1143,9 +1152,14 @@ int build_device_impl(sdfgpu_handle h, const uint8_t* d_filled, const void* d_ce
         const bool fix = plan.fix;
         cur_dense3 = plan.dense3;
         cur_staged = plan.staged;
+        int flip = 0;
+        if (!cur_dense3) {                                      // (KD; see ball_serpentine)
+            flip = (h->ball_serpentine && d_out == h->serp_out && n == h->serp_n) ? !h->serp_flip : 0;
+            h->serp_out = d_out; h->serp_n = n; h->serp_flip = flip;
+        }
         if (int rc = launch_ball_dense(h, dense_bits, d_out, nx, 0, nx, ny, nz, resolution, h->d_small,
                                        cur_staged ? h->d_small + 20 : h->d_small + 3, s,
-                                       (fix || cur_dense3) ? h->d_small + 6 : nullptr, true, vb, nx, cur_dense3 ? 3 : 2)) return rc;
+                                       (fix || cur_dense3) ? h->d_small + 6 : nullptr, true, vb, nx, cur_dense3 ? 3 : 2, nullptr, flip)) return rc;
         if (cur_staged) {
             h->unc_override = (!fused && h->zfield.ptr && h->zfield.bytes >= (size_t)n / 8) ? (uint32_t*)h->zfield.ptr : nullptr;
             h->unc_override_bytes = h->unc_override ? h->zfield.bytes : 0;
@@ -2668,6 +2682,7 @@ int sdfgpu_set_option(sdfgpu_handle h, const char* name, int value) {
         h->flags_pending = h->far_pending = false;
     }
     else if (n == "dense3_fixed") h->dense3_fixed = value != 0;
+    else if (n == "ball_serpentine") h->ball_serpentine = value != 0;
     else if (n == "shell_min_words") h->shell_min_words = value >= 0 ? value : kShellMinWords;
     else if (n == "shell_budget_den") h->shell_budget_den = value >= 1 ? value : 8;
     else if (n == "dense3_staged") h->pol.dense3_staged = value != 0;

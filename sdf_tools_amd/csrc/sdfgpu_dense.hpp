@@ -135,6 +135,7 @@ struct DenseArgs {
     int vb;
     int nx_glob;            // x extent of the whole grid (buffer plane 0 = grid plane 0 in this mode)
     int nt_store;           // write the output with non-temporal stores (it is never re-read here)
+    int flip;               // KD only: walk the tiles in the opposite order (whole builds that rewrite the previous build's buffer)
     const uint32_t* guard;  // KD3 only: non-null = run iff *guard != 0 (the staged fix-up stage behind KD in the same build)
     uint32_t* und_sample;   // KD3 only: nullptr, or the slot array: every 16th wave adds its undecided voxels to word 2 of a slot -- a 1 / 16
                             // sample of the scene's total, which k_shell_budget folds and holds against the shell pass's budget
@@ -218,8 +219,15 @@ __global__ __launch_bounds__(BD) void k_ball_dense(const DenseArgs a) {
         magl[t] = m;
     }
 
-    const int x0 = a.out_lo + (int)blockIdx.y * a.tx;         // first tile plane (buffer coordinates)
-    const int y0 = (int)blockIdx.x * a.ty;
+    // Logical tile coordinates.  flip = the launch walks the tiles in the opposite order (serpentine: a build that rewrites
+    // the buffer of the build before it starts on the lines that one wrote last, which the Infinity Cache still holds).
+    // Nothing depends on the order: a tile's result is a function of its logical coordinates only, the early out only
+    // ever skips work that the stage behind redoes, the maxima slots are max-folded and the flags only ever rise.  x0, y0
+    // AND tile_id (slot index, tile flag: KF and the shell pass address tiles by logical coordinates) come from bx, by.
+    const uint32_t bx = a.flip ? gridDim.x - 1u - blockIdx.x : blockIdx.x;
+    const uint32_t by = a.flip ? gridDim.y - 1u - blockIdx.y : blockIdx.y;
+    const int x0 = a.out_lo + (int)by * a.tx;                 // first tile plane (buffer coordinates)
+    const int y0 = (int)bx * a.ty;
     // stage the bit-rows of the tile + halo; rows outside the buffer / grid replicate the nearest row
     if (nzw >= 4) {
         // one 16-byte load per lane and staged quarter-row: (hx*hy rows) x (nzw/4 quads); all loads of a
@@ -410,7 +418,7 @@ __global__ __launch_bounds__(BD) void k_ball_dense(const DenseArgs a) {
             a.unc[((int64_t)(x0 + tx_ - a.out_lo) * a.ny + (y0 + ty_)) * nzw + w] = ~acc[6];
     }
     if ((t & 63) == 0) {
-        const uint32_t tile_id = (uint32_t)blockIdx.y * gridDim.x + blockIdx.x;
+        const uint32_t tile_id = by * gridDim.x + bx;
         // The early-out test at the top is per wave: if the flag rises between the loads of two waves of one workgroup, some
         // waves leave and the others run on over a partly staged tile -- what they find is garbage.  The field is rewritten
         // by the stage behind (the flag is up), but maxima are max-folded: they must not leave this wave.  A wave that can
