@@ -14,6 +14,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 #include <fstream>
 #include <functional>
 #include <iterator>
@@ -249,5 +250,48 @@ public:
         return sdf_generation::ExtractSignedDistanceField(*this, is_filled_fn, oob_value, GetFrame(), add_virtual_border);
     }
 };
+
+// A batch of maps of ONE shape in one launch sequence (sdfgpu_build_batch): what a caller with many small environments uses in
+// place of a loop over CollisionMapGrid::ExtractSignedDistanceField.  Each result carries its own map's origin, frame and
+// resolution and equals that map's single call.  std::invalid_argument when the shapes differ or a map has non-uniform cells.
+inline std::vector<std::pair<SignedDistanceField, std::pair<double, double>>> ExtractSignedDistanceFieldBatch(
+    const std::vector<const CollisionMapGrid*>& maps, const float oob_value, const bool unknown_is_filled, const bool add_virtual_border) {
+    std::vector<std::pair<SignedDistanceField, std::pair<double, double>>> results;
+    if (maps.empty()) return results;
+    const int64_t nx = maps[0]->GetNumXCells(), ny = maps[0]->GetNumYCells(), nz = maps[0]->GetNumZCells();
+    const size_t n = (size_t)(nx * ny * nz), batch = maps.size();
+    std::vector<double> resolutions(batch);
+    std::vector<uint8_t> filled(batch * n);
+    for (size_t b = 0; b < batch; ++b) {
+        const CollisionMapGrid& map = *maps[b];
+        if (map.GetNumXCells() != nx || map.GetNumYCells() != ny || map.GetNumZCells() != nz)
+            throw std::invalid_argument("All grids of a batch must have the same shape");
+        const Eigen::Vector3d cell_sizes = map.GetCellSizes();
+        if ((cell_sizes.x() != cell_sizes.y()) || (cell_sizes.x() != cell_sizes.z()))
+            throw std::invalid_argument("Grid must have uniform resolution");
+        resolutions[b] = cell_sizes.x();
+        const std::vector<COLLISION_CELL>& cells = map.GetImmutableRawData();       // the predicate of :689-704
+        for (size_t i = 0; i < n; ++i)
+            filled[b * n + i] = ((cells[i].occupancy > 0.5f) || (unknown_is_filled && (cells[i].occupancy == 0.5f))) ? 1 : 0;
+    }
+    if (n == 0) throw std::invalid_argument("Grid must not be empty");
+    std::vector<float> fields(batch * n);
+    std::vector<double> mx(batch), mn(batch);
+    {
+        const std::shared_ptr<sdf_generation::SharedGpuContext> ctx = sdf_generation::GpuContext::Shared();
+        const std::lock_guard<std::mutex> lock(ctx->mutex);
+        sdf_generation::ThrowOnStatus(ctx->handle, sdfgpu_build_batch(ctx->handle, filled.data(), (int64_t)batch, nx, ny, nz, resolutions[0],
+                                                                      resolutions.data(), add_virtual_border ? 1 : 0, fields.data(),
+                                                                      mx.data(), mn.data()));
+    }
+    results.reserve(batch);
+    for (size_t b = 0; b < batch; ++b) {
+        SignedDistanceField new_sdf(SignedDistanceField::ForBuild{}, maps[b]->GetOriginTransform(), maps[b]->GetFrame(), resolutions[b], nx,
+                                    ny, nz, oob_value);
+        std::memcpy(new_sdf.MutableDataForBuild(), fields.data() + b * n, n * sizeof(float));
+        results.emplace_back(std::move(new_sdf), std::make_pair(mx[b], mn[b]));
+    }
+    return results;
+}
 
 }  // namespace sdf_tools

@@ -19,6 +19,7 @@
 #include <functional>
 #include <iterator>
 #include <limits>
+#include <cstring>
 #include <map>
 #include <string>
 #include <utility>
@@ -289,16 +290,33 @@ public:
         return std::make_pair(combined_sdf, std::make_pair(free_sdf_result.second.first, named_objects_sdf_result.second.second));
     }
 
-    // One SDF per object id, built with oob = +inf like the reference (:875-891).
+    // One SDF per object id, built with oob = +inf like the reference (:875-891).  ONE call for all ids: the cell records travel
+    // once and the batch kernels classify them per id (sdfgpu_build_tagged_objects), no host round trip between objects.
     std::map<uint32_t, SignedDistanceField> MakeObjectSDFs(const std::vector<uint32_t>& object_ids, const bool unknown_is_filled,
                                                            const bool add_virtual_border) const {
         std::map<uint32_t, SignedDistanceField> per_object_sdfs;
-        bool uploaded = false;                  // the cell records travel once; every further object re-uses the device copy
-        for (const uint32_t object_id : object_ids) {
-            per_object_sdfs[object_id] = BuildWithFilter(std::numeric_limits<float>::infinity(), 2,
-                                                         std::vector<uint32_t>{object_id}, unknown_is_filled,
-                                                         add_virtual_border, uploaded).first;
-            uploaded = true;
+        if (object_ids.empty()) return per_object_sdfs;
+        const Eigen::Vector3d cell_sizes = GetCellSizes();
+        if ((cell_sizes.x() != cell_sizes.y()) || (cell_sizes.x() != cell_sizes.z()))
+            throw std::invalid_argument("Grid must have uniform resolution");
+        const size_t n = data_.size();
+        std::vector<float> fields(object_ids.size() * n);
+        {
+            const std::shared_ptr<sdf_generation::SharedGpuContext> ctx = sdf_generation::GpuContext::Shared();
+            const std::lock_guard<std::mutex> lock(ctx->mutex);
+            sdfgpu_handle h = ctx->handle;
+            sdf_generation::ThrowOnStatus(
+                h, sdfgpu_build_tagged_objects(h, data_.data(), sizeof(TAGGED_OBJECT_COLLISION_CELL),
+                                               offsetof(TAGGED_OBJECT_COLLISION_CELL, occupancy),
+                                               offsetof(TAGGED_OBJECT_COLLISION_CELL, object_id), object_ids.data(),
+                                               (int64_t)object_ids.size(), unknown_is_filled ? 1 : 0, GetNumXCells(), GetNumYCells(),
+                                               GetNumZCells(), cell_sizes.x(), add_virtual_border ? 1 : 0, fields.data(), nullptr, nullptr));
+        }
+        for (size_t b = 0; b < object_ids.size(); ++b) {
+            SignedDistanceField new_sdf(SignedDistanceField::ForBuild{}, GetOriginTransform(), frame_, cell_sizes.x(), GetNumXCells(),
+                                        GetNumYCells(), GetNumZCells(), std::numeric_limits<float>::infinity());
+            std::memcpy(new_sdf.MutableDataForBuild(), fields.data() + b * n, n * sizeof(float));
+            per_object_sdfs[object_ids[b]] = std::move(new_sdf);
         }
         return per_object_sdfs;
     }

@@ -574,6 +574,53 @@ int sdfgpu_query_gradients(sdfgpu_handle h, const float* d_sdf, int64_t nx, int6
                            const double world_to_grid[12], float oob_value, int kind, double window, const double* points,
                            int64_t n_points, double* out_value, double* out_gradient, uint8_t* out_status);
 
+/* ---------------------------------------------------------------------------
+ * Batches of same-shape grids: B grids of one shape (nx, ny, nz) in one launch sequence.  Grid b lies at offset b * nx * ny * nz
+ * of the input and of the output, each in the layout above (z fastest).  Every grid comes out bit-equal to its single build
+ * (sdfgpu_build_device with resolutions[b], or `resolution` for every grid when resolutions == NULL) and so do its extrema.
+ * What callers with many small fields use in place of a host loop over the one-grid calls: a batch of environments
+ * (reference src/sdf_tools/utils_3d_tensorflow.py:6-15), one field per object id (tagged_object_collision_map.hpp:875-891).
+ *   - fast path: a shape whose three axes are all <= 128 (after singleton axes are moved to the front) is built by an exact
+ *     min-plus over whole lines in TWO launches for the whole batch (sdf_tools_amd/csrc/sdfgpu_batch.hip), whatever the scenes
+ *     are: no tier, probe or guard is involved.  It uses scratch of its own.
+ *   - any other shape: the single build is enqueued once per grid on `stream`, without a host synchronisation between grids.
+ *     sdfgpu_last_batch_info reports which of the two ran (*out_fast_path 1 / 0) and the launches of the fast path
+ *     (*out_launches: 2; -1 on the other path, which does not count them).
+ *   - `resolutions` (host, batch entries) is read before the call returns; the caller may free it.
+ *   - a batch build and a single build on one handle do not affect each other's results: sdfgpu_get_extrema keeps answering
+ *     for the last SINGLE build, sdfgpu_get_extrema_batch (it waits for the batch) for the last batch build, whose batch it
+ *     must be given.  Batch calls take part in the handle's ordering of builds across streams.  The debug hooks and the learnt
+ *     tier policy see the single builds of the second path like any other single build.
+ * INVALID_ARGUMENT: null pointers, batch < 1 (or > 2^24), non-positive dimensions, a resolution that is not positive (NaN
+ * included), a misaligned cell layout.
+ *   sdfgpu_build_batch_device: device pointers, asynchronous on `stream`.
+ *   sdfgpu_build_batch: host masks in, host fields and batch (max, min) pairs out (out_max / out_min may be NULL).
+ *   sdfgpu_build_tagged_objects: one field per object id from ONE grid of tagged cell records: grid b is filled where the
+ *       occupancy says so AND object_id == object_ids[b] (sdfgpu_build_tagged_cells' object_mode 2 with that single id).  The ids
+ *       may come in any order, repeat, or be absent from the grid (such a field is all +inf).  The records are uploaded once and
+ *       classified inside the batch's first kernel for every id: no per-id mask exists and no per-id classify launch runs (fast
+ *       path).  cells == NULL re-uses the records of the previous tagged call, under the rule of sdfgpu_build_tagged_cells.
+ *       out_sdf: n_object_ids fields.
+ *   sdfgpu_gradient_batch_device: the definition of sdfgpu_gradient_device on every grid of a batch (any shape), one launch;
+ *       d_out: [batch][nx,ny,nz,3] float64 (f64 != 0) or float32, bit-equal to the single call per grid.
+ * ------------------------------------------------------------------------- */
+int sdfgpu_build_batch_device(sdfgpu_handle h, const uint8_t* d_filled, int64_t batch,
+                              int64_t nx, int64_t ny, int64_t nz,
+                              double resolution, const double* resolutions,
+                              int add_virtual_border, float* d_out_sdf, void* stream);
+int sdfgpu_get_extrema_batch(sdfgpu_handle h, int64_t batch, double* out_max, double* out_min);
+int sdfgpu_build_batch(sdfgpu_handle h, const uint8_t* filled, int64_t batch, int64_t nx, int64_t ny, int64_t nz,
+                       double resolution, const double* resolutions, int add_virtual_border,
+                       float* out_sdf, double* out_max, double* out_min);
+int sdfgpu_build_tagged_objects(sdfgpu_handle h, const void* cells, size_t cell_stride, size_t occupancy_offset,
+                                size_t object_id_offset, const uint32_t* object_ids, int64_t n_object_ids,
+                                int unknown_is_filled, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                                int add_virtual_border, float* out_sdf, double* out_max, double* out_min);
+int sdfgpu_gradient_batch_device(sdfgpu_handle h, const float* d_sdf, int64_t batch, int64_t nx, int64_t ny, int64_t nz,
+                                 double resolution, const double* resolutions, int enable_edge_gradients, int f64,
+                                 void* d_out, void* stream);
+int sdfgpu_last_batch_info(sdfgpu_handle h, int* out_fast_path, int* out_launches);
+
 /* Red zones (round 6).  With SDFGPU_REDZONE=1 in the environment when sdfgpu_create runs -- or after
  * sdfgpu_set_option(h, "redzone", 1) -- every device allocation of the library (scratch fields, status block, extrema slots,
  * staging buffers, sdfgpu_device_malloc memory) carries 4 KiB of canary bytes in front and behind, and every entry point that

@@ -33,6 +33,8 @@ EXPORTS = [
     "sdfgpu_local_extrema_device", "sdfgpu_local_extrema", "sdfgpu_convex_segments_cells", "sdfgpu_convex_last_info",
     "sdfgpu_project_step_limit", "sdfgpu_project_points_device", "sdfgpu_project_points",
     "sdfgpu_query_gradients_device", "sdfgpu_query_gradients",
+    "sdfgpu_build_batch_device", "sdfgpu_get_extrema_batch", "sdfgpu_build_batch", "sdfgpu_build_tagged_objects",
+    "sdfgpu_gradient_batch_device", "sdfgpu_last_batch_info",
 ]
 
 # include/sdfgpu.h "Projection": modes and per-point statuses
@@ -136,6 +138,12 @@ def load_library():
     L.sdfgpu_project_points.argtypes = [vp, vp, i64, i64, i64, dbl, vp, vp, dbl, dbl, ci, ci, vp, i64, vp, vp, vp]
     L.sdfgpu_query_gradients_device.argtypes = [vp, vp, i64, i64, i64, dbl, vp, ctypes.c_float, ci, dbl, vp, i64, vp, vp, vp, vp]
     L.sdfgpu_query_gradients.argtypes = [vp, vp, i64, i64, i64, dbl, vp, ctypes.c_float, ci, dbl, vp, i64, vp, vp, vp]
+    L.sdfgpu_build_batch_device.argtypes = [vp, vp, i64, i64, i64, i64, dbl, vp, ci, vp, vp]
+    L.sdfgpu_get_extrema_batch.argtypes = [vp, i64, vp, vp]
+    L.sdfgpu_build_batch.argtypes = [vp, vp, i64, i64, i64, i64, dbl, vp, ci, vp, vp, vp]
+    L.sdfgpu_build_tagged_objects.argtypes = [vp, vp, sz, sz, sz, vp, i64, ci, i64, i64, i64, dbl, ci, vp, vp, vp]
+    L.sdfgpu_gradient_batch_device.argtypes = [vp, vp, i64, i64, i64, i64, dbl, vp, ci, ci, vp, vp]
+    L.sdfgpu_last_batch_info.argtypes = [vp, vp, vp]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is ctypes.c_int or name not in ("sdfgpu_version", "sdfgpu_last_error"):
@@ -575,6 +583,77 @@ class SdfGpu:
                                                         int(bool(unknown_is_filled)), nx, ny, nz,
                                                         float(resolution), int(bool(add_virtual_border)),
                                                         d_out, stream or None))
+
+    # ---- batches of same-shape grids (include/sdfgpu.h "Batches of same-shape grids") ----
+    @staticmethod
+    def _batch_resolutions(resolution, batch):
+        """(scalar, array or None): one resolution for every grid, or one per grid."""
+        if np.ndim(resolution) == 0:
+            return float(resolution), None
+        r = np.ascontiguousarray(resolution, dtype=np.float64)
+        if r.shape != (batch,):
+            raise ValueError("resolutions must hold one entry per grid")
+        return float(r[0]), r
+
+    def build_batch(self, filled, resolution=1.0, add_virtual_border=False):
+        """filled: uint8/bool [B,nx,ny,nz]; resolution: a scalar or B values.  Returns (sdf float32 [B,nx,ny,nz], [(max, min)] * B)."""
+        m = np.ascontiguousarray(filled, dtype=np.uint8)
+        if m.ndim != 4:
+            raise ValueError("masks must be [B, nx, ny, nz]")
+        res, arr = self._batch_resolutions(resolution, m.shape[0])
+        out = np.empty(m.shape, dtype=np.float32)
+        mx = np.empty(m.shape[0], np.float64)
+        mn = np.empty(m.shape[0], np.float64)
+        self._check(self._lib.sdfgpu_build_batch(self._h, m.ctypes.data, *m.shape, res, arr.ctypes.data if arr is not None else None,
+                                                 int(bool(add_virtual_border)), out.ctypes.data, mx.ctypes.data, mn.ctypes.data))
+        return out, [(float(a), float(b)) for a, b in zip(mx, mn)]
+
+    def build_batch_device(self, d_filled, batch, shape, d_out, resolution=1.0, add_virtual_border=False, stream=0):
+        nx, ny, nz = (int(s) for s in shape)
+        res, arr = self._batch_resolutions(resolution, int(batch))
+        self._check(self._lib.sdfgpu_build_batch_device(self._h, d_filled, int(batch), nx, ny, nz, res,
+                                                        arr.ctypes.data if arr is not None else None,
+                                                        int(bool(add_virtual_border)), d_out, stream or None))
+
+    def get_extrema_batch(self, batch):
+        mx = np.empty(int(batch), np.float64)
+        mn = np.empty(int(batch), np.float64)
+        self._check(self._lib.sdfgpu_get_extrema_batch(self._h, int(batch), mx.ctypes.data, mn.ctypes.data))
+        return [(float(a), float(b)) for a, b in zip(mx, mn)]
+
+    def build_tagged_objects(self, cells, shape, object_ids, unknown_is_filled=False, resolution=1.0, add_virtual_border=False,
+                             cell_stride=16, occupancy_offset=0, object_id_offset=8):
+        """One field per object id from one grid of raw TAGGED_OBJECT_COLLISION_CELL records (cells=None: the records of the
+        previous tagged call).  Returns (sdf float32 [len(object_ids),nx,ny,nz], [(max, min)] per id)."""
+        nx, ny, nz = (int(s) for s in shape)
+        c = None
+        if cells is not None:
+            c = np.ascontiguousarray(cells)
+            if c.nbytes != nx * ny * nz * cell_stride:
+                raise ValueError("cells buffer size does not match shape * cell_stride")
+        ids = np.ascontiguousarray(np.asarray(object_ids, dtype=np.uint32))
+        out = np.empty((ids.size, nx, ny, nz), dtype=np.float32)
+        mx = np.empty(ids.size, np.float64)
+        mn = np.empty(ids.size, np.float64)
+        self._check(self._lib.sdfgpu_build_tagged_objects(
+            self._h, c.ctypes.data if c is not None else None, cell_stride, occupancy_offset, object_id_offset,
+            ids.ctypes.data if ids.size else None, int(ids.size), int(bool(unknown_is_filled)), nx, ny, nz, float(resolution),
+            int(bool(add_virtual_border)), out.ctypes.data, mx.ctypes.data, mn.ctypes.data))
+        return out, [(float(a), float(b)) for a, b in zip(mx, mn)]
+
+    def gradient_batch_device(self, d_sdf, batch, shape, d_out, resolution=1.0, enable_edge_gradients=True, f64=True, stream=0):
+        nx, ny, nz = (int(s) for s in shape)
+        res, arr = self._batch_resolutions(resolution, int(batch))
+        self._check(self._lib.sdfgpu_gradient_batch_device(self._h, d_sdf, int(batch), nx, ny, nz, res,
+                                                           arr.ctypes.data if arr is not None else None,
+                                                           int(bool(enable_edge_gradients)), int(bool(f64)), d_out, stream or None))
+
+    def last_batch_info(self):
+        """(fast_path, launches) of the last batch build: launches is 2 on the fast path, -1 (not counted) otherwise."""
+        f = ctypes.c_int(0)
+        n = ctypes.c_int(0)
+        self._check(self._lib.sdfgpu_last_batch_info(self._h, ctypes.byref(f), ctypes.byref(n)))
+        return bool(f.value), int(n.value)
 
     def get_extrema(self):
         ext = (ctypes.c_double * 2)()

@@ -122,7 +122,12 @@ PYBIND11_MODULE(pysdf_tools, m) {
         .def("ExtractSignedDistanceField", [](const TaggedObjectCollisionMapGrid& g, float oob_value, const std::vector<uint32_t>& objects_to_use,
                                                bool unknown_is_filled, bool add_virtual_border) {
             return g.ExtractSignedDistanceField(oob_value, objects_to_use, unknown_is_filled, add_virtual_border);
-        }, py::call_guard<py::gil_scoped_release>());
+        }, py::call_guard<py::gil_scoped_release>())
+        .def("MakeObjectSDFs", &TaggedObjectCollisionMapGrid::MakeObjectSDFs, py::arg("object_ids"), py::arg("unknown_is_filled"),
+             py::arg("add_virtual_border"), py::call_guard<py::gil_scoped_release>(),
+             "{object id: SignedDistanceField}, OOB value +inf, all ids in one batched build (sdfgpu_build_tagged_objects)")
+        .def("MakeAllObjectSDFs", &TaggedObjectCollisionMapGrid::MakeAllObjectSDFs, py::arg("unknown_is_filled"), py::arg("add_virtual_border"),
+             py::call_guard<py::gil_scoped_release>(), "... for every object id > 0 present in the grid");
 
     using VoxelGridVecd = VoxelGrid::VoxelGrid<std::vector<double>>;
 
@@ -443,4 +448,9 @@ PYBIND11_MODULE(pysdf_tools, m) {
         .def("DeserializeSelf", [](VoxelGridVecd& g, const std::vector<uint8_t>& buffer, uint64_t current, py::object) {
             return g.DeserializeSelf(buffer, current, arc_utilities::DeserializeVectorOfDoubles); },
              "deserialize", py::arg("buffer"), py::arg("current"), py::arg("value_deserializer") = py::none());
+    m.def("ExtractSignedDistanceFieldBatch", [](const std::vector<const CollisionMapGrid*>& maps, float oob_value, bool unknown_is_filled,
+                                                bool add_virtual_border) {
+        return sdf_tools::ExtractSignedDistanceFieldBatch(maps, oob_value, unknown_is_filled, add_virtual_border);
+    }, py::arg("maps"), py::arg("oob_value"), py::arg("unknown_is_filled"), py::arg("add_virtual_border"), py::call_guard<py::gil_scoped_release>(),
+          "[(SignedDistanceField, (max, min))] of CollisionMapGrids of one shape in one batched build (sdfgpu_build_batch)");
 }
