@@ -2912,9 +2912,11 @@ int sdfgpu_set_option(sdfgpu_handle h, const char* name, int value) {
         HIP_TRY(h, hipSetDevice(h->device));
         HIP_TRY(h, hipDeviceSynchronize());
         for (DeviceBuffer* b : {&h->zfield, &h->yzfield, &h->plane16, &h->bits, &h->unc, &h->tileflag, &h->fix_order, &h->tagmask, &h->tagids, &h->stage_in,
-                                &h->stage_bits, &h->stage_out, &h->query_stage, &h->planebits})
+                                &h->stage_bits, &h->stage_out, &h->query_stage, &h->planebits, &h->batch_field, &h->batch_ext, &h->batch_res,
+                                &h->batch_gscale})
             if (b->ptr) { (void)rz_free(h, b->ptr); b->ptr = nullptr; b->bytes = 0; }
         h->tag_cached_bytes = 0;
+        h->batch_valid = false;                         // (the batch's extrema words went with batch_ext)
         (void)rz_free(h, h->d_small);
         (void)rz_free(h, h->d_slots);
         h->d_small = h->d_slots = nullptr;

@@ -23,6 +23,16 @@ namespace {
 
 constexpr int kBatchBlock = 256;
 constexpr int kNone16 = 0x7FFF;        // LDS / scratch magnitude of "no opposite voxel in this row / plane"
+// One dimension of a HIP launch takes fewer than 2^32 threads (a larger one is not refused: its size wraps and most workgroups
+// never run), so more than kBatchGridX workgroups go over two grid dimensions and a workgroup's number is y * gridDim.x + x.
+constexpr int64_t kBatchGridX = (int64_t)1 << 22;
+
+dim3 batch_grid(int64_t workgroups) {
+    if (workgroups <= kBatchGridX) return dim3((unsigned)workgroups);
+    return dim3((unsigned)kBatchGridX, (unsigned)((workgroups + kBatchGridX - 1) / kBatchGridX));
+}
+
+__device__ __forceinline__ int64_t batch_workgroup() { return (int64_t)blockIdx.y * gridDim.x + blockIdx.x; }
 
 __device__ __forceinline__ int mag16(int v) { return v >= kNone16 ? kInf32 : v; }
 
@@ -32,13 +42,15 @@ __global__ __launch_bounds__(kBatchBlock) void k_batch_zy(const BatchArgs a, con
     const int t = threadIdx.x, lane = t & 63;
     const int nz = a.nz, ny = a.ny, plane = ny * nz;
     const int64_t planes_total = (int64_t)a.batch * a.nx;
-    const int64_t gp0 = (int64_t)blockIdx.x * P;
+    const int64_t wg = batch_workgroup();
+    const int64_t gp0 = wg * P;
+    if (gp0 >= planes_total) return;                                          // (the last row of a two-dimensional launch)
     const int np = (int)min((int64_t)P, planes_total - gp0);
     const int nvox = np * plane, rows = np * ny;
     uint32_t* bm = reinterpret_cast<uint32_t*>(smem);                         // [P * ny][4] row bitmaps (nz <= 128)
     uint16_t* g = reinterpret_cast<uint16_t*>(smem + (size_t)P * ny * 16);    // [P * plane] bit 15 = class, bits 0..14 = dz^2
 
-    if (blockIdx.x == 0)             // the x pass's per-grid maxima start at 0
+    if (wg == 0)                     // the x pass's per-grid maxima start at 0
         for (int i = t; i < 2 * a.batch; i += kBatchBlock) a.ext[i] = 0u;
     for (int i = t; i < rows * 4; i += kBatchBlock) bm[i] = 0u;
     __syncthreads();
@@ -130,7 +142,9 @@ __global__ __launch_bounds__(kBatchBlock) void k_batch_x_finish(const BatchArgs 
     int16_t* col = reinterpret_cast<int16_t*>(smem);          // [nx][TC]
     const int t = threadIdx.x;
     const int nx = a.nx, ny = a.ny, nz = a.nz, plane = ny * nz;
-    const int b = blockIdx.x / tiles, tile = blockIdx.x - b * tiles;
+    const int64_t wg = batch_workgroup();
+    if (wg >= (int64_t)a.batch * tiles) return;
+    const int b = (int)(wg / tiles), tile = (int)(wg - (int64_t)b * tiles);
     const int c0 = tile * TC, nc = min(TC, plane - c0);
     const int64_t base = (int64_t)b * nx * plane;
     const double res = a.res ? a.res[b] : a.res_uniform;
@@ -219,16 +233,16 @@ hipError_t batch_launch(const BatchArgs& a, hipStream_t s, int* launches) {
     // 128 x 128 plane takes
     const int P = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(1024 / plane, 8), planes_total));
     const size_t lds_zy = (size_t)P * a.ny * 16 + (size_t)P * plane * 2;
-    const unsigned grid_zy = (unsigned)((planes_total + P - 1) / P);
+    const dim3 grid_zy = batch_grid((planes_total + P - 1) / P);
     if (a.mask)
-        hipLaunchKernelGGL(k_batch_zy<false>, dim3(grid_zy), dim3(kBatchBlock), lds_zy, s, a, P);
+        hipLaunchKernelGGL(k_batch_zy<false>, grid_zy, dim3(kBatchBlock), lds_zy, s, a, P);
     else
-        hipLaunchKernelGGL(k_batch_zy<true>, dim3(grid_zy), dim3(kBatchBlock), lds_zy, s, a, P);
+        hipLaunchKernelGGL(k_batch_zy<true>, grid_zy, dim3(kBatchBlock), lds_zy, s, a, P);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     const int tiles = (plane + kBatchTileCols - 1) / kBatchTileCols;
     const size_t lds_x = (size_t)a.nx * kBatchTileCols * 2;
-    hipLaunchKernelGGL(k_batch_x_finish, dim3((unsigned)((int64_t)a.batch * tiles)), dim3(kBatchBlock), lds_x, s, a, tiles);
+    hipLaunchKernelGGL(k_batch_x_finish, batch_grid((int64_t)a.batch * tiles), dim3(kBatchBlock), lds_x, s, a, tiles);
     if (launches) *launches = 2;
     return hipGetLastError();
 }
