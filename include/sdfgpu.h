@@ -303,7 +303,11 @@ int sdfgpu_gradient(sdfgpu_handle h, const float* sdf,
  * points (d_points: n x 3 doubles).  world_to_grid: 12 host doubles, row-major 3x4 = inverse origin
  * transform (NULL = identity); grid_to_world_rotation: 9 host doubles, row-major (NULL = identity).
  * Outputs (device, any may be NULL):
- *   d_distance[n]  the estimate, or oob_value where the point is outside the grid
+ *   d_distance[n]  the estimate, or oob_value where the point is outside the grid; every product and sum is rounded on its own
+ *                  (no fused multiply-add).  With world_to_grid = NULL (the identity) or a pure translation (rotation part the
+ *                  identity: 1 x + 0 y + 0 z + t is x + t, one rounding) it is bit-equal to the host's EstimateDistance4d; the
+ *                  tests pin these two cases.  With a rotation the grid coordinates are the four-term sums above, which the
+ *                  host's transform need not round the same way: no bit-level claim is made there
  *   d_gradient[3n] world-frame gradient of the cell holding the point; NaN where the reference returns
  *                  an empty vector (outside, or boundary shell without enable_edge_gradients)
  *   d_flags[n]     bit0 = point inside the grid, bit1 = gradient available */

@@ -584,6 +584,11 @@ class SdfGpu:
                                                         float(resolution), int(bool(add_virtual_border)),
                                                         d_out, stream or None))
 
+    def classify_cells_device(self, d_cells, n_cells, d_mask, cell_stride=8, occupancy_offset=0, unknown_is_filled=False, stream=0):
+        """The CollisionMapGrid predicate on n_cells raw device records -> device byte mask (1 = filled)."""
+        self._check(self._lib.sdfgpu_classify_cells_device(self._h, d_cells, cell_stride, occupancy_offset,
+                                                           int(bool(unknown_is_filled)), int(n_cells), d_mask, stream or None))
+
     # ---- batches of same-shape grids (include/sdfgpu.h "Batches of same-shape grids") ----
     @staticmethod
     def _batch_resolutions(resolution, batch):

@@ -1092,6 +1092,7 @@ __device__ __forceinline__ void query_axis_pair(int64_t i, int64_t n, double off
 
 __device__ __forceinline__ double query_bilinear(double l1, double h1, double l2, double h2, double q1, double q2,
                                                  double ll, double lh, double hl, double hh) {
+#pragma clang fp contract(off)                                       // (see k_query_points)
     const double multiplier = 1.0 / ((h1 - l1) * (h2 - l2));
     const double a0 = multiplier * (h1 - q1), a1 = multiplier * (q1 - l1);
     const double r0 = a0 * ll + a1 * hl, r1 = a0 * lh + a1 * hh;
@@ -1099,6 +1100,10 @@ __device__ __forceinline__ double query_bilinear(double l1, double h1, double l2
 }
 
 SDFGPU_KERNEL __launch_bounds__(kBlock) void k_query_points(const QueryArgs a) {
+    // The estimate is the reference's sequence of double products and sums, each rounded: hipcc contracts a product and a sum into
+    // an FMA by default, which moved distances by an ulp or two against the host's EstimateDistance and could pick the other
+    // neighbour pair at an exact cell centre.  No contraction here or in query_bilinear, like sdfgpu_query.hip and sdfgpu_project.hip.
+#pragma clang fp contract(off)
     const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (t >= a.n) return;
     const double px = a.points[3 * t], py = a.points[3 * t + 1], pz = a.points[3 * t + 2];

@@ -11,6 +11,13 @@
 * local extrema at n = 2^32 - 3, the largest grid check_convex_args accepts (its last index one below the kOnCycle marker), with
   a basin and doubling windows across index 2^31.
 
+The byte-mask build above runs the point lattice (distances of at most 5 voxels) and Bernoulli(0.5) past 2^31 voxels; the batched
+build's launch of 2^32 threads is in test_gpu_batch_edges.py, the projection and gradient-query kernels' 1300 x 1300 x 1272 fields in
+test_gpu_projection.py and test_gpu_query_gradients.py.  The other entry points at these sizes -- a far-field scene on the marching
+sweeps, bits in, cells in, voxelisation, the full-field gradient, point queries, a host-to-host build -- are in
+test_gpu_size_limits_entry_points.py, which imports this module's closed forms.  The closed-form pins of this module carry the gpu
+marker with the rest of it (they need no GPU); those of the sibling module do not.
+
 Every reference is independent of the library: the oracle's exact EDT, or a closed form in int64 whose float32 values come
 from a table computed on the host like the oracle computes them (sqrt and multiply in float64, one cast), or a closed form
 in int64 of the topology counters and extremum indices.  Each closed form is first checked against the oracle (or the C++

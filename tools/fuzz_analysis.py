@@ -9,7 +9,7 @@ output compared bit for bit with its restatement (the checkers of tests/, import
   segments          sdfgpu_convex_segments_cells                                        restated_segments
   projection        sdfgpu_project_points, _device, DeviceSignedDistanceField           the host walk (ProjectCounted4d)
   query_gradients   sdfgpu_query_gradients, _device, DeviceSignedDistanceField          the host core (QueryGradient4d)
-  query_points      sdfgpu_query_points (distance within 1e-9: that kernel may fuse)    analysis_scenes.query_points
+  query_points      sdfgpu_query_points (bit-equal, distance included)                  analysis_scenes.query_points
   gradient          sdfgpu_gradient_device, fp32 and fp64, aligned or not               analysis_scenes.grid_gradient
 
 The operations that use atomics (components, topology, segments) run twice on the same input; both results must match.
@@ -229,12 +229,9 @@ def op_query_gradients(ctx, rng, mask, res):
 
 
 def _near(a, b):
-    """the query_points distance: that kernel's file lets hipcc fuse products with sums, so 1e-9 (relative above 1) is the bar"""
-    both_nan = np.isnan(a) & np.isnan(b)
-    inf_same = np.isinf(a) & (a == b)
-    with np.errstate(invalid="ignore"):
-        close = np.abs(a - b) <= 1e-9 * np.maximum(1.0, np.abs(b))
-    return bool(np.all(both_nan | inf_same | close))
+    """the query_points distance: bit-equal (two NaNs are equal) -- k_query_points rounds every product and sum on its own, and the
+    grid coordinates of op_query_points are exact (see there)"""
+    return _same(a, b)
 
 
 def op_query_points(ctx, rng, mask, res):
