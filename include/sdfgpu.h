@@ -72,6 +72,16 @@ int sdfgpu_destroy(sdfgpu_handle h);
 const char* sdfgpu_last_error(sdfgpu_handle h);
 
 /* ---------------------------------------------------------------------------
+ * Resolutions.  Every entry point that takes a `resolution` (or an array of them)
+ * accepts exactly the positive finite doubles -- subnormal and huge finite values
+ * included: the field then underflows to signed zeros or overflows to +/-inf as
+ * float(sqrt((double)D) * resolution) does.  NaN, 0, negative and infinite values
+ * are refused with SDFGPU_ERR_INVALID_ARGUMENT before anything is enqueued or
+ * written; sdfgpu_last_error names the value.  (sdfgpu_extrema_from_dsq has no
+ * handle: it returns the code and leaves its outputs untouched.)
+ * ------------------------------------------------------------------------- */
+
+/* ---------------------------------------------------------------------------
  * Whole-path entry points, host buffers.
  * Replaces sdf_generation::ExtractSignedDistanceField (sdf_generation.hpp:273-420)
  * once the caller has evaluated its predicate into `filled` (nonzero = filled),
@@ -595,8 +605,8 @@ int sdfgpu_query_gradients(sdfgpu_handle h, const float* d_sdf, int64_t nx, int6
  *     for the last SINGLE build, sdfgpu_get_extrema_batch (it waits for the batch) for the last batch build, whose batch it
  *     must be given.  Batch calls take part in the handle's ordering of builds across streams.  The debug hooks and the learnt
  *     tier policy see the single builds of the second path like any other single build.
- * INVALID_ARGUMENT: null pointers, batch < 1 (or > 2^24), non-positive dimensions, a resolution that is not positive (NaN
- * included), a misaligned cell layout.
+ * INVALID_ARGUMENT: null pointers, batch < 1 (or > 2^24), non-positive dimensions, a resolution that is not positive and
+ * finite ("Resolutions" above), a misaligned cell layout.
  *   sdfgpu_build_batch_device: device pointers, asynchronous on `stream`.
  *   sdfgpu_build_batch: host masks in, host fields and batch (max, min) pairs out (out_max / out_min may be NULL).
  *   sdfgpu_build_tagged_objects: one field per object id from ONE grid of tagged cell records: grid b is filled where the
@@ -728,7 +738,12 @@ int sdfgpu_set_option(sdfgpu_handle h, const char* name, int value);
  * dense stage was its wide form (KD3 + fix-up kernel in KD's place), bit 5 = that form was enqueued BEHIND KD, guarded on
  * KD's verdict (a build that had no reason to expect that KD decides the scene), bit 6 = the far-field pair was enqueued
  * without probes and marching launches because the handle's recent builds were far-field on both axes (option
- * "far_predict": 0 never, 1 learnt -- the default --, 2 every build; exact either way, every 16th build probes again). */
+ * "far_predict": 0 never, 1 learnt -- the default --, 2 every build; exact either way, every 16th build probes again).
+ * Also answers for the last sdfgpu_sweep_x_lines_device call: bit 7 = that call chose its tier on the device (the far-field
+ * kernel enqueued behind the marching sweep; 0: the marching sweep alone, unbounded).  Bits 8..12 = 1 + the instance of the
+ * far-field kernel that the last build or lines call enqueued for its x sweep (0: none): + 1 stage 3, + 2 vector loads, + 4 the
+ * looping stand-by form, + 8 512 lanes (lines above 512); 13 / 15 = the instances with a 512- / 1024-voxel line as compile-time
+ * constants.  (Enqueued, not necessarily run: whether a guarded launch did work is sdfgpu_last_dense_certified's far flags.) */
 int sdfgpu_last_build_info(sdfgpu_handle h, int* out_fused_zy);
 
 /* Which path did the work of the last build (synchronises): bit 0 = the dense kernel decided every voxel

@@ -44,7 +44,9 @@ int sdfgpu_multi_ranks(sdfgpu_multi_handle h);
 /* x range [*x0, *x1) of `rank` for a grid with nx planes (balanced contiguous slabs). */
 int sdfgpu_multi_slab_range(sdfgpu_multi_handle h, int64_t nx, int rank, int64_t* x0, int64_t* x1);
 
-/* Whole-path entry points, host buffers holding the WHOLE grid (same contract as sdfgpu_build / sdfgpu_build_cells). */
+/* Whole-path entry points, host buffers holding the WHOLE grid (same contract as sdfgpu_build / sdfgpu_build_cells).
+ * The resolution rule of include/sdfgpu.h ("Resolutions") holds for the three build calls below: a resolution that is not
+ * positive and finite is refused with SDFGPU_ERR_INVALID_ARGUMENT before anything is uploaded, enqueued or written on any rank. */
 int sdfgpu_multi_build(sdfgpu_multi_handle h, const uint8_t* filled,
                        int64_t nx, int64_t ny, int64_t nz,
                        double resolution, int add_virtual_border,

@@ -249,8 +249,10 @@ def device_count():
 def extrema_from_dsq(max_dsq_free, max_dsq_filled, resolution):
     """Host helper (no GPU needed): (max, min) from the integer maxima, as sdf_generation.hpp:246-269."""
     out = (ctypes.c_double * 2)()
-    load_library().sdfgpu_extrema_from_dsq(int(max_dsq_free), int(max_dsq_filled), float(resolution),
-                                           ctypes.byref(out, 0), ctypes.byref(out, 8))
+    rc = load_library().sdfgpu_extrema_from_dsq(int(max_dsq_free), int(max_dsq_filled), float(resolution),
+                                                ctypes.byref(out, 0), ctypes.byref(out, 8))
+    if rc != 0:
+        raise SdfGpuError(rc, "resolution must be positive and finite")
     return float(out[0]), float(out[1])
 
 
@@ -779,7 +781,8 @@ class SdfGpu:
         self._check(self._lib.sdfgpu_last_build_info(self._h, ctypes.byref(v)))
         return {"fused_zy": bool(v.value & 1), "plane16": bool(v.value & 2), "dense": bool(v.value & 4),
                 "standby_far": bool(v.value & 8), "dense3": bool(v.value & 16), "dense3_staged": bool(v.value & 32),
-                "far_predicted": bool(v.value & 64)}
+                "far_predicted": bool(v.value & 64), "lines_tiered": bool(v.value & 128),
+                "far_x_instance": ((v.value >> 8) & 31) - 1}
 
     def last_path(self):
         """{'dense_certified', 'far_y', 'far_x'} of the last build (synchronises)."""

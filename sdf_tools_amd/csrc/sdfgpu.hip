@@ -114,6 +114,8 @@ struct sdfgpu_context {
     int64_t last_n = 0;
     bool have_result = false;
     bool last_fused = false;
+    bool last_lines_tiered = false;  // the last sdfgpu_sweep_x_lines_device call chose its tier on the device (probe / forced tier + far-field kernel behind the marching sweep)
+    int last_dc_x = 0;               // 1 + the far-field kernel instance (launch_envelope's `which`) of the last x sweep launched through it; 0: none since the last build / lines call began
     bool last_predicted = false;     // the last build took the far-field pair on the strength of the handle's recent builds: no probes, no marching launches
     // "this handle's scene is a far-field scene on both axes": learnt from the status blocks that come back (never a wait).  Such a
     // build skips the two probes and the three guarded marching launches (35 us of a 0.8 - 1.4 ms build) and enqueues KE2 -> KE3
@@ -367,6 +369,13 @@ int check_dims(sdfgpu_handle h, int64_t nx, int64_t ny, int64_t nz) {
         return fail(h, SDFGPU_ERR_UNSUPPORTED_SIZE,
                     "grid %lld x %lld x %lld exceeds the supported extent (dims <= 16384, nx^2+ny^2+nz^2 < 2^30)",
                     (long long)nx, (long long)ny, (long long)nz);
+    return SDFGPU_OK;
+}
+
+// include/sdfgpu.h "Resolutions": positive and finite (subnormal and huge finite values included), refused before anything is enqueued
+int check_resolution(sdfgpu_handle h, double resolution) {
+    if (!(resolution > 0.0) || !std::isfinite(resolution))
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "resolution must be positive and finite (got %g)", resolution);
     return SDFGPU_OK;
 }
 
@@ -779,6 +788,7 @@ int launch_envelope(sdfgpu_handle h, int stage, const int16_t* d_in16, const int
         const bool fixed1024 = h->dc_fixed && a.L == 1024 && vec && big && a.B == 10 && a.pitch == 1026 && a.M == 128 && a.h == 512;
         const int which = fixed512 ? 12 + (stage == 3 ? 1 : 0) : fixed1024 ? 14 + (stage == 3 ? 1 : 0) :
                           (stage == 3 ? 1 : 0) + (vec ? 2 : 0) + (loop ? 4 : 0) + (big ? 8 : 0);
+        if (stage == 3 && !probe_out) h->last_dc_x = which + 1;
         auto launch = [&](auto kern) -> int {
             // (the attribute is per kernel: raised once per instantiation, not on every launch -- ADVICE r3)
             if (lds > 64 * 1024 && !h->dc_attr_set[which]) {
@@ -1030,11 +1040,14 @@ int build_device_impl(sdfgpu_handle h, const uint8_t* d_filled, const void* d_ce
     if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
     if ((!d_filled && !d_cells && !d_bits_in) || !d_out) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null device pointer");
     if (d_bits_in && (reinterpret_cast<uintptr_t>(d_bits_in) % 4) != 0) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "the bit field must be 4-byte aligned");
+    if (int rc = check_resolution(h, resolution)) return rc;
     if (int rc = check_dims(h, nx, ny, nz)) return rc;
     if (d_cells && (stride < 4 || (stride % 4) || (off % 4) || off + 4 > stride))
         return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cell_stride/occupancy_offset must be 4-byte aligned and in range");
     HIP_TRY(h, hipSetDevice(h->device));
     canonical_dims(nx, ny, nz);
+    h->last_dc_x = 0;
+    h->last_lines_tiered = false;
     const int64_t n = nx * ny * nz;
     const bool p16 = plane16_eligible(h, ny, nz);
     if (int rc = ensure(h, h->yzfield, (size_t)n * 4, "int32 plane field / side table")) return rc;          // int32 plane field / side table
@@ -1612,6 +1625,7 @@ int build_host_impl(sdfgpu_handle h, const uint8_t* filled, const void* cells, s
                     double* out_max, double* out_min, float* d_out_user = nullptr, const uint32_t* bits_in = nullptr) {
     if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
     if ((!filled && !cells && !bits_in) || (!out_sdf && !d_out_user)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
+    if (int rc = check_resolution(h, resolution)) return rc;                  // (before the upload: nothing is enqueued for a refused call)
     if (int rc = check_dims(h, nx, ny, nz)) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     const int64_t n = nx * ny * nz;
@@ -2033,6 +2047,7 @@ int sdfgpu_upload_classified(sdfgpu_handle h, const uint8_t* filled, const void*
 
 int sdfgpu_extrema_from_dsq(uint32_t max_dsq_free, uint32_t max_dsq_filled, double resolution, double* out_max,
                             double* out_min) {
+    if (!(resolution > 0.0) || !std::isfinite(resolution)) return SDFGPU_ERR_INVALID_ARGUMENT;     // (no handle: the code only; outputs untouched)
     const double inf = std::numeric_limits<double>::infinity();
     // sdf_generation.hpp:246-269: max is attained on a free voxel, min on a filled one;
     // an absent class leaves the running value at its -inf / +inf start or at the
@@ -2125,6 +2140,7 @@ int sdfgpu_sweep_x_lines_device(sdfgpu_handle h, const int32_t* d_plane_dsq, int
         if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
         if (!d_plane_dsq || !d_out_sdf || !d_maxdsq) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null device pointer");
         if (y_global < 0 || y_global + nys > ny_global) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "inconsistent slab geometry");
+        if (int rc = check_resolution(h, resolution)) return rc;
         if (int rc = check_dims(h, nx, nys, nz)) return rc;
         if (int rc = check_dims(h, nx, ny_global, nz)) return rc;
         HIP_TRY(h, hipSetDevice(h->device));
@@ -2135,6 +2151,8 @@ int sdfgpu_sweep_x_lines_device(sdfgpu_handle h, const int32_t* d_plane_dsq, int
         struct OrderEnd { sdfgpu_handle h; hipStream_t s; ~OrderEnd() { if (hipEventRecord(h->build_done_ev, s) == hipSuccess) { h->order_valid = true; h->order_stream = s; } } } order_end{h, s};
         const bool tiered = h->envelope_on && far_geometry_ok(h, 3, nx, nys, nz, ny_global) &&
                             (reinterpret_cast<uintptr_t>(d_plane_dsq) % 16) == 0;
+        h->last_dc_x = 0;
+        h->last_lines_tiered = tiered;
         if (!tiered) {
             if (int rc = launch_sweep_x(h, d_plane_dsq, d_out_sdf, 0, nx, 0, nys, nz, 0, 0, 0, nx, resolution, add_virtual_border,
                                         d_maxdsq, nullptr, s, y_global, ny_global)) return rc;
@@ -2173,6 +2191,7 @@ int sdfgpu_sweep_x_device(sdfgpu_handle h, const int32_t* d_plane_dsq, int64_t h
             return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null device pointer");
         if (halo_lo < 0 || halo_hi < 0 || x_global < 0 || x_global + nxs > nx_global)
             return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "inconsistent slab geometry");
+        if (int rc = check_resolution(h, resolution)) return rc;
         h->guard = nullptr;
         h->far_y = nullptr;
         if (int rc = check_dims(h, halo_lo + nxs + halo_hi, ny, nz)) return rc;
@@ -2203,6 +2222,7 @@ int sdfgpu_dense_ball_device(sdfgpu_handle h, const uint32_t* d_bits, int64_t ro
         if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
         if (!d_bits || !d_out_sdf || !d_maxdsq || !d_uncertified) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null device pointer");
         if (out_lo < 0 || out_hi <= out_lo || out_hi > rows_x) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "inconsistent slab geometry");
+        if (int rc = check_resolution(h, resolution)) return rc;
         if (int rc = check_dims(h, rows_x, ny, nz)) return rc;
         if (!dense_eligible(h, nz, 0)) return fail(h, SDFGPU_ERR_UNSUPPORTED_SIZE, "dense kernel needs nz = 32 * 2^k <= 2048");
         HIP_TRY(h, hipSetDevice(h->device));
@@ -2227,6 +2247,7 @@ int sdfgpu_slab_dense_phase(sdfgpu_handle h, int phase, const uint8_t* d_mask_sl
         const int64_t hb = kBallR;
         if (nxs <= 0 || (halo_lo != 0 && halo_lo != hb) || (halo_hi != 0 && halo_hi != hb))
             return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "inconsistent slab geometry");
+        if (int rc = check_resolution(h, resolution)) return rc;
         if (int rc = check_dims(h, halo_lo + nxs + halo_hi, ny, nz)) return rc;
         if (!dense_eligible(h, nz, 0)) return fail(h, SDFGPU_ERR_UNSUPPORTED_SIZE, "dense kernel needs nz = 32 * 2^k <= 2048");
         HIP_TRY(h, hipSetDevice(h->device));
@@ -2294,6 +2315,7 @@ int sdfgpu_build_tagged_cells(sdfgpu_handle h, const void* cells, size_t cell_st
             (object_mode == 2 && n_object_ids > 0 && !object_ids))
             return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "bad object filter");
         if (object_mode == 2 && n_object_ids == 0) object_mode = 0;       // "no objects supplied" = any object (:826)
+        if (int rc = check_resolution(h, resolution)) return rc;
         if (int rc = check_dims(h, nx, ny, nz)) return rc;
         HIP_TRY(h, hipSetDevice(h->device));
         const int64_t n = nx * ny * nz;
@@ -2367,7 +2389,7 @@ int check_batch_args(sdfgpu_handle h, int64_t batch, int64_t nx, int64_t ny, int
     if (nx * ny * nz > (((int64_t)1 << 62) / batch) / 16) return fail(h, SDFGPU_ERR_UNSUPPORTED_SIZE, "batch * nx * ny * nz overflows");
     for (int64_t b = 0; b < (resolutions ? batch : 1); ++b) {
         const double r = resolutions ? resolutions[b] : resolution;
-        if (!(r > 0.0)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "resolution must be positive and not NaN (grid %lld)", (long long)b);
+        if (!(r > 0.0) || !std::isfinite(r)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "resolution must be positive and finite (grid %lld: %g)", (long long)b, r);
     }
     return SDFGPU_OK;
 }
@@ -2524,6 +2546,8 @@ int sdfgpu_gradient_batch_device(sdfgpu_handle h, const float* d_sdf, int64_t ba
         if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
         if (!d_sdf || !d_out) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null device pointer");
         if (batch < 1 || batch > ((int64_t)1 << 24)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "batch must be in 1 .. 2^24 (got %lld)", (long long)batch);
+        for (int64_t b = 0; b < (resolutions ? batch : 1); ++b)
+            if (int rc = check_resolution(h, resolutions ? resolutions[b] : resolution)) return rc;
         if (int rc = check_dims(h, nx, ny, nz)) return rc;
         HIP_TRY(h, hipSetDevice(h->device));
         hipStream_t s = (hipStream_t)stream;
@@ -2589,8 +2613,9 @@ int sdfgpu_voxelize_points_device(sdfgpu_handle h, const float* d_points, int64_
                                   void* stream) {
     return rz_wrap(h, stream, [&]() -> int {
         if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-        if (!d_mask || !origin || (n_points > 0 && !d_points) || n_points < 0 || !(resolution > 0.0))
+        if (!d_mask || !origin || (n_points > 0 && !d_points) || n_points < 0)
             return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "bad voxelize arguments");
+        if (int rc = check_resolution(h, resolution)) return rc;
         if (int rc = check_dims(h, nx, ny, nz)) return rc;
         HIP_TRY(h, hipSetDevice(h->device));
         hipStream_t s = (hipStream_t)stream;
@@ -2609,8 +2634,9 @@ int sdfgpu_voxelize_points_bits_device(sdfgpu_handle h, const float* d_points, i
                                        void* stream) {
     return rz_wrap(h, stream, [&]() -> int {
         if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-        if (!d_bits || !origin || (n_points > 0 && !d_points) || n_points < 0 || !(resolution > 0.0))
+        if (!d_bits || !origin || (n_points > 0 && !d_points) || n_points < 0)
             return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "bad voxelize arguments");
+        if (int rc = check_resolution(h, resolution)) return rc;
         if (int rc = check_dims(h, nx, ny, nz)) return rc;
         HIP_TRY(h, hipSetDevice(h->device));
         hipStream_t s = (hipStream_t)stream;
@@ -2630,6 +2656,7 @@ int sdfgpu_gradient_device(sdfgpu_handle h, const float* d_sdf, int64_t nx, int6
     return rz_wrap(h, stream, [&]() -> int {
         if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
         if (!d_sdf || !d_out_grad) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null device pointer");
+        if (int rc = check_resolution(h, resolution)) return rc;
         if (int rc = check_dims(h, nx, ny, nz)) return rc;
         HIP_TRY(h, hipSetDevice(h->device));
         const int64_t n = nx * ny * nz;
@@ -2666,6 +2693,7 @@ int sdfgpu_gradient(sdfgpu_handle h, const float* sdf, int64_t nx, int64_t ny, i
     return rz_wrap(h, nullptr, [&]() -> int {
         if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
         if (!sdf || !out_grad) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null host pointer");
+        if (int rc = check_resolution(h, resolution)) return rc;
         if (int rc = check_dims(h, nx, ny, nz)) return rc;
         HIP_TRY(h, hipSetDevice(h->device));
         const size_t n = (size_t)(nx * ny * nz), esz = out_is_f64 ? 8 : 4;
@@ -2701,7 +2729,8 @@ int sdfgpu_query_points_device(sdfgpu_handle h, const float* d_sdf, int64_t nx, 
     return rz_wrap(h, stream, [&]() -> int {
         if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
         if (!d_sdf || (n_points > 0 && !d_points)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null device pointer");
-        if (n_points < 0 || !(resolution > 0.0)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "bad point count or resolution");
+        if (n_points < 0) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "bad point count");
+        if (int rc = check_resolution(h, resolution)) return rc;
         if (int rc = check_dims(h, nx, ny, nz)) return rc;
         if (n_points == 0 || (!d_distance && !d_gradient && !d_flags)) return SDFGPU_OK;
         HIP_TRY(h, hipSetDevice(h->device));
@@ -2744,7 +2773,8 @@ int sdfgpu_query_points(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t
     return rz_wrap(h, nullptr, [&]() -> int {
         if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
         if (!d_sdf || (n_points > 0 && !points)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
-        if (n_points < 0 || !(resolution > 0.0)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "bad point count or resolution");
+        if (n_points < 0) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "bad point count");
+        if (int rc = check_resolution(h, resolution)) return rc;
         if (int rc = check_dims(h, nx, ny, nz)) return rc;
         if (n_points == 0 || (!out_distance && !out_gradient && !out_flags)) return SDFGPU_OK;
         HIP_TRY(h, hipSetDevice(h->device));
@@ -2954,7 +2984,8 @@ int sdfgpu_set_option(sdfgpu_handle h, const char* name, int value) {
 int sdfgpu_last_build_info(sdfgpu_handle h, int* out_fused_zy) {
     if (!h || !out_fused_zy) return SDFGPU_ERR_INVALID_ARGUMENT;
     *out_fused_zy = (h->last_fused ? 1 : 0) | (h->last_plane16 ? 2 : 0) | (h->last_dense ? 4 : 0) | (h->last_standby ? 8 : 0) |
-                    (h->last_dense3 ? 16 : 0) | (h->last_staged ? 32 : 0) | (h->last_predicted ? 64 : 0);
+                    (h->last_dense3 ? 16 : 0) | (h->last_staged ? 32 : 0) | (h->last_predicted ? 64 : 0) |
+                    (h->last_lines_tiered ? 128 : 0) | ((h->last_dc_x & 31) << 8);
     return SDFGPU_OK;
 }
 

@@ -13,6 +13,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstdarg>
 #include <cstdio>
@@ -256,8 +257,15 @@ int wait_rank(sdfgpu_multi_handle h, int q) {
 
 // The limits of sdfgpu_build* (check_dims in sdfgpu.hip), applied before anything is allocated or uploaded: an oversized
 // or malformed request must come back as UNSUPPORTED_SIZE / INVALID_ARGUMENT, not as a hipMalloc failure half-way.
-int check_request(sdfgpu_multi_handle h, int64_t nx, int64_t ny, int64_t nz, const void* cells, size_t stride, size_t off) {
+// (the resolution: include/sdfgpu.h "Resolutions" -- positive and finite, or nothing is uploaded, enqueued or written)
+int check_resolution(sdfgpu_multi_handle h, double res) {
+    if (!(res > 0.0) || !std::isfinite(res)) return mfail(h, SDFGPU_ERR_INVALID_ARGUMENT, "resolution must be positive and finite (got %g)", res);
+    return SDFGPU_OK;
+}
+
+int check_request(sdfgpu_multi_handle h, int64_t nx, int64_t ny, int64_t nz, double res, const void* cells, size_t stride, size_t off) {
     const int G = (int)h->r.size();
+    if (int rc = check_resolution(h, res)) return rc;
     if (nx <= 0 || ny <= 0 || nz <= 0) return mfail(h, SDFGPU_ERR_INVALID_ARGUMENT, "grid dimensions must be positive");
     constexpr int64_t kMaxDim = 16384;
     if (nx > kMaxDim || ny > kMaxDim || nz > kMaxDim || nx * nx + ny * ny + nz * nz >= (1ll << 30))
@@ -273,7 +281,7 @@ int build_device(sdfgpu_multi_handle h, const uint8_t* const* d_mask, int64_t nx
                  float* const* d_out, double* out_max, double* out_min) {
     const int G = (int)h->r.size();
     if (h->rccl_dead) return mfail(h, SDFGPU_ERR_HIP, "this context's RCCL communicators were aborted after a rank failed mid-exchange; destroy it and create a new one");
-    if (int rc = check_request(h, nx, ny, nz, nullptr, 0, 0)) return rc;
+    if (int rc = check_request(h, nx, ny, nz, res, nullptr, 0, 0)) return rc;
     const int64_t plane = ny * nz;
     int64_t min_slab = nx;
     for (int q = 0; q < G; ++q) {
@@ -551,7 +559,7 @@ int build_host(sdfgpu_multi_handle h, const uint8_t* filled, const void* cells, 
     if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
     if ((!filled && !cells) || !out) return mfail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null host pointer");
     const int G = (int)h->r.size();
-    if (int rc = check_request(h, nx, ny, nz, cells, stride, off)) return rc;
+    if (int rc = check_request(h, nx, ny, nz, res, cells, stride, off)) return rc;
     const int64_t plane = ny * nz;
     std::vector<const uint8_t*> dm((size_t)G);
     std::vector<float*> dout((size_t)G);
@@ -719,6 +727,7 @@ int sdfgpu_multi_build_device(sdfgpu_multi_handle h, const uint8_t* const* d_mas
                               double* out_min) {
     if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
     if (!d_mask_slabs || !d_out_slabs) return mfail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer array");
+    if (int rc = check_resolution(h, resolution)) return rc;
     // the caller's buffers may have been produced on other streams: settle them first
     for (Rank& k : h->r) {
         M_HIP(h, hipSetDevice(k.dev));
