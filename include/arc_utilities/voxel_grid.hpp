@@ -13,6 +13,7 @@
 #include <cmath>
 #include <cstdint>
 #include <functional>
+#include <initializer_list>
 #include <stdexcept>
 #include <utility>
 #include <vector>
@@ -30,6 +31,22 @@ struct GRID_INDEX {
     GRID_INDEX(const int64_t in_x, const int64_t in_y, const int64_t in_z) : x(in_x), y(in_y), z(in_z) {}
     bool operator==(const GRID_INDEX& o) const { return x == o.x && y == o.y && z == o.z; }
 };
+
+}  // namespace VoxelGrid
+
+namespace std {
+// keys of the reference's std::unordered_map<GRID_INDEX, ...> (component surfaces): the three coordinates combined in turn
+template <>
+struct hash<VoxelGrid::GRID_INDEX> {
+    size_t operator()(const VoxelGrid::GRID_INDEX& index) const {
+        size_t seed = 0;
+        for (const int64_t v : {index.x, index.y, index.z}) seed ^= std::hash<int64_t>()(v) + 0x9e3779b97f4a7c15ull + (seed << 6) + (seed >> 2);
+        return seed;
+    }
+};
+}  // namespace std
+
+namespace VoxelGrid {
 
 template <typename T, typename BackingStore = std::vector<T>>
 class VoxelGrid {

@@ -4,8 +4,9 @@
 // ExtractSignedDistanceField (:680-712), and the connected components (UpdateConnectedComponents :564-618,
 // ExtractConnectedComponents :757-778, GetNumConnectedComponents hpp :503) computed on the GPU by sdfgpu_components_cells,
 // and their topology (ComputeComponentTopology :620-671, holes and voids per component) by sdfgpu_component_topology_cells.
-// Component surfaces (ExtractComponentSurfaces), convex segments and RViz export are out of scope (SURVEY.md section 2,
-// rows 2/8).  Wire formats (N3): SerializeSelf / DeserializeSelf, SaveToFile /
+// and the surface voxels of each component (ExtractComponentSurfaces :697-754 and its wrappers) by
+// sdfgpu_component_surfaces_cells; CheckIfCandidateCorner (hpp :508-619) is a host query on the stored labels.
+// Convex segments and RViz export are out of scope.  Wire formats (N3): SerializeSelf / DeserializeSelf, SaveToFile /
 // LoadFromFile ("CMGZ" / "CMGR") and the CollisionMap message pair in the field order of
 // src/sdf_tools/collision_map.cpp:21-62, :205-283, :285-315.  The byte layout of the primitives
 // (arc_utilities::SerializeFixedSizePOD / SerializeEigen / SerializeVector / SerializeString) is the in-tree
@@ -26,6 +27,7 @@
 #include "arc_utilities/serialization.hpp"
 #include "arc_utilities/voxel_grid.hpp"
 #include "arc_utilities/zlib_helpers.hpp"
+#include "sdf_tools/component_surfaces.hpp"
 #include "sdf_tools/component_topology.hpp"
 #include "sdf_tools/sdf.hpp"
 #include "sdf_tools/sdf_generation.hpp"
@@ -157,6 +159,47 @@ public:
                                                  offsetof(COLLISION_CELL, component), GetNumXCells(), GetNumYCells(), GetNumZCells(),
                                                  ignore_empty_components ? FILLED_COMPONENTS : (FILLED_COMPONENTS | EMPTY_COMPONENTS | UNKNOWN_COMPONENTS),
                                                  max_label, verbose);
+    }
+
+    // ---- component surfaces (reference collision_map.cpp:697-754, collision_map.hpp:651-671) ---------------------------------------------------------------
+    // {component: {index: 1}} of the surface voxels -- a voxel with a face neighbour of another component, the outside of the
+    // grid being component -1 -- whose occupancy class is in component_types_to_extract, found on the GPU from the STORED
+    // labels (include/sdfgpu.h "Component surfaces": every class is tested at (x, y, z), and the z = nz - 1 face is a grid face
+    // like the other five).  Components are not recomputed, as in the reference.
+    std::map<uint32_t, std::unordered_map<GRID_INDEX, uint8_t>> ExtractComponentSurfaces(const COMPONENT_TYPES component_types_to_extract) const {
+        return ComponentSurfacesToMap(ExtractComponentSurfaceIndices(component_types_to_extract), GetNumYCells(), GetNumZCells());
+    }
+    std::map<uint32_t, std::unordered_map<GRID_INDEX, uint8_t>> ExtractFilledComponentSurfaces() const { return ExtractComponentSurfaces(FILLED_COMPONENTS); }
+    std::map<uint32_t, std::unordered_map<GRID_INDEX, uint8_t>> ExtractUnknownComponentSurfaces() const { return ExtractComponentSurfaces(UNKNOWN_COMPONENTS); }
+    std::map<uint32_t, std::unordered_map<GRID_INDEX, uint8_t>> ExtractEmptyComponentSurfaces() const { return ExtractComponentSurfaces(EMPTY_COMPONENTS); }
+
+    // The fast form: offsets per component and ascending uint32 linear indices, no hash maps (component_surfaces.hpp).
+    ComponentSurfaceIndices ExtractComponentSurfaceIndices(const COMPONENT_TYPES component_types_to_extract) const {
+        uint32_t max_label = number_of_components_;
+        if (!components_valid_) {
+            max_label = 0;
+            for (const COLLISION_CELL& cell : data_) max_label = cell.component > max_label ? cell.component : max_label;
+        }
+        return ExtractComponentSurfaceIndicesFromCells(data_.data(), sizeof(COLLISION_CELL), offsetof(COLLISION_CELL, occupancy),
+                                                       offsetof(COLLISION_CELL, component), GetNumXCells(), GetNumYCells(), GetNumZCells(),
+                                                       (int)component_types_to_extract, max_label);
+    }
+
+    // ---- candidate corners (reference collision_map.hpp:508-619): (two or more in-grid face neighbours of another component, index in the grid)
+    std::pair<bool, bool> CheckIfCandidateCorner3d(const Eigen::Vector3d& location) const {
+        const GRID_INDEX index = LocationToGridIndex3d(location);
+        return IndexInBounds(index) ? CheckIfCandidateCorner(index) : std::pair<bool, bool>(false, false);
+    }
+    std::pair<bool, bool> CheckIfCandidateCorner4d(const Eigen::Vector4d& location) const {
+        const GRID_INDEX index = LocationToGridIndex4d(location);
+        return IndexInBounds(index) ? CheckIfCandidateCorner(index) : std::pair<bool, bool>(false, false);
+    }
+    std::pair<bool, bool> CheckIfCandidateCorner(const double x, const double y, const double z) const {
+        return CheckIfCandidateCorner4d(Eigen::Vector4d(x, y, z, 1.0));
+    }
+    std::pair<bool, bool> CheckIfCandidateCorner(const GRID_INDEX& index) const { return CheckIfCandidateCorner(index.x, index.y, index.z); }
+    std::pair<bool, bool> CheckIfCandidateCorner(const int64_t x_index, const int64_t y_index, const int64_t z_index) const {
+        return CheckIfCandidateCornerOnGrid(*this, x_index, y_index, z_index);
     }
 
     // Indices of each component, in scan order inside each (one counting pass, then one placement pass over the labels).

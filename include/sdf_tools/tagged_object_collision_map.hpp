@@ -10,7 +10,8 @@
 // The connected components (UpdateConnectedComponents, tagged_object_collision_map.cpp:340-380, same connectivity rule as
 // CollisionMapGrid's) are computed on the GPU by sdfgpu_components_cells, and their topology (ComputeComponentTopology,
 // :424-490) by sdfgpu_component_topology_cells, and the convex segments (UpdateConvexSegments, :552-654) by
-// sdfgpu_convex_segments_cells.  Component surfaces and RViz export are out of scope.
+// sdfgpu_convex_segments_cells, and the surface voxels of each component (ExtractComponentSurfaces, :492-550) by
+// sdfgpu_component_surfaces_cells.  RViz export is out of scope.
 // Every SDF is built on the GPU through sdfgpu_build_tagged_cells (device-side predicate).
 #pragma once
 #include <cstddef>
@@ -28,6 +29,7 @@
 #include "arc_utilities/serialization.hpp"
 #include "arc_utilities/voxel_grid.hpp"
 #include "arc_utilities/zlib_helpers.hpp"
+#include "sdf_tools/component_surfaces.hpp"
 #include "sdf_tools/component_topology.hpp"
 #include "sdf_tools/sdf.hpp"
 #include "sdf_tools/sdf_generation.hpp"
@@ -158,6 +160,47 @@ public:
                                                  offsetof(TAGGED_OBJECT_COLLISION_CELL, occupancy),
                                                  offsetof(TAGGED_OBJECT_COLLISION_CELL, component), GetNumXCells(), GetNumYCells(),
                                                  GetNumZCells(), (int)component_types_to_use, max_label, verbose);
+    }
+
+    // ---- component surfaces (reference tagged_object_collision_map.cpp:492-550, tagged_object_collision_map.hpp:703-723) ---------------------------------------------------------------
+    // {component: {index: 1}} of the surface voxels -- a voxel with a face neighbour of another component, the outside of the
+    // grid being component -1 -- whose occupancy class is in component_types_to_extract, found on the GPU from the STORED
+    // labels (include/sdfgpu.h "Component surfaces": every class is tested at (x, y, z), and the z = nz - 1 face is a grid face
+    // like the other five).  Components are not recomputed, as in the reference.
+    std::map<uint32_t, std::unordered_map<GRID_INDEX, uint8_t>> ExtractComponentSurfaces(const COMPONENT_TYPES component_types_to_extract) const {
+        return ComponentSurfacesToMap(ExtractComponentSurfaceIndices(component_types_to_extract), GetNumYCells(), GetNumZCells());
+    }
+    std::map<uint32_t, std::unordered_map<GRID_INDEX, uint8_t>> ExtractFilledComponentSurfaces() const { return ExtractComponentSurfaces(FILLED_COMPONENTS); }
+    std::map<uint32_t, std::unordered_map<GRID_INDEX, uint8_t>> ExtractUnknownComponentSurfaces() const { return ExtractComponentSurfaces(UNKNOWN_COMPONENTS); }
+    std::map<uint32_t, std::unordered_map<GRID_INDEX, uint8_t>> ExtractEmptyComponentSurfaces() const { return ExtractComponentSurfaces(EMPTY_COMPONENTS); }
+
+    // The fast form: offsets per component and ascending uint32 linear indices, no hash maps (component_surfaces.hpp).
+    ComponentSurfaceIndices ExtractComponentSurfaceIndices(const COMPONENT_TYPES component_types_to_extract) const {
+        uint32_t max_label = number_of_components_;
+        if (!components_valid_) {
+            max_label = 0;
+            for (const TAGGED_OBJECT_COLLISION_CELL& cell : data_) max_label = cell.component > max_label ? cell.component : max_label;
+        }
+        return ExtractComponentSurfaceIndicesFromCells(data_.data(), sizeof(TAGGED_OBJECT_COLLISION_CELL), offsetof(TAGGED_OBJECT_COLLISION_CELL, occupancy),
+                                                       offsetof(TAGGED_OBJECT_COLLISION_CELL, component), GetNumXCells(), GetNumYCells(), GetNumZCells(),
+                                                       (int)component_types_to_extract, max_label);
+    }
+
+    // ---- candidate corners (reference tagged_object_collision_map.hpp:558-669): (two or more in-grid face neighbours of another component, index in the grid)
+    std::pair<bool, bool> CheckIfCandidateCorner3d(const Eigen::Vector3d& location) const {
+        const GRID_INDEX index = LocationToGridIndex3d(location);
+        return IndexInBounds(index) ? CheckIfCandidateCorner(index) : std::pair<bool, bool>(false, false);
+    }
+    std::pair<bool, bool> CheckIfCandidateCorner4d(const Eigen::Vector4d& location) const {
+        const GRID_INDEX index = LocationToGridIndex4d(location);
+        return IndexInBounds(index) ? CheckIfCandidateCorner(index) : std::pair<bool, bool>(false, false);
+    }
+    std::pair<bool, bool> CheckIfCandidateCorner(const double x, const double y, const double z) const {
+        return CheckIfCandidateCorner4d(Eigen::Vector4d(x, y, z, 1.0));
+    }
+    std::pair<bool, bool> CheckIfCandidateCorner(const GRID_INDEX& index) const { return CheckIfCandidateCorner(index.x, index.y, index.z); }
+    std::pair<bool, bool> CheckIfCandidateCorner(const int64_t x_index, const int64_t y_index, const int64_t z_index) const {
+        return CheckIfCandidateCornerOnGrid(*this, x_index, y_index, z_index);
     }
 
     // ---- convex segments (reference tagged_object_collision_map.cpp:552-654) ---------------------------------------------------

@@ -447,6 +447,52 @@ int sdfgpu_component_topology(sdfgpu_handle h, const uint32_t* labels, const uin
 int sdfgpu_component_topology_cells(sdfgpu_handle h, const void* cells, size_t cell_stride, size_t occupancy_offset, size_t component_offset,
                                     int64_t nx, int64_t ny, int64_t nz, int class_mask, uint32_t max_label, int64_t* out_counts);
 
+/* ---------------------------------------------------------------------------
+ * Component surfaces: CollisionMapGrid / TaggedObjectCollisionMapGrid::ExtractComponentSurfaces and its Filled / Unknown / Empty
+ * wrappers (reference src/sdf_tools/collision_map.cpp:697-754, tagged_object_collision_map.cpp:492-550,
+ * topology_computation.hpp:297-330) on the GPU.  DESIGN.md section 19.
+ * Indices: voxel (x, y, z) is (x ny + y) nz + z.  An out-of-grid voxel is component -1 (as in "Component topology", deviation 2).
+ * Inputs: one uint32 label per voxel (normally sdfgpu_components' output) and optionally a selection, one bit per voxel in the
+ * library's bit-field layout (for cell records: the class mask FILLED 1, occupancy > 0.5; EMPTY 2, < 0.5; UNKNOWN 4, the rest,
+ * NaN included).
+ *   - a voxel v of label c is a SURFACE VOXEL iff at least one of its six face neighbours has a label other than c; an
+ *     out-of-grid neighbour counts as different, so every voxel on a grid face is a surface voxel;
+ *   - v is REPORTED iff it is selected and a surface voxel.  The neighbour comparison does not look at the selection, and no
+ *     label is refused for being partly selected: each voxel stands alone.
+ * Results:
+ *   out_counts: max_label + 1 int64, entry c = reported voxels of label c (0 for absent labels);
+ *   indices: the linear indices of all reported voxels as uint32, grouped by label in ascending label order and ascending
+ *     inside each group -- the order in which the reference's x -> y -> z loop inserts them.  Group c starts at the sum of
+ *     out_counts[0 .. c - 1].  *out_total = their number.  Fully determined, so results are bit-reproducible.
+ *   d_surface_bits (device form, optional): ceil(n / 32) words, bit v set iff voxel v is reported.
+ * A NULL index buffer asks for the counts (and the total, and the bits) only.
+ * Deviations from the literal reference:
+ *   1. every occupancy class is tested at (x, y, z) (collision_map.cpp:723 tests filled voxels at (x, y, y) and :743 unknown
+ *      ones at (x, z, z); tagged_object_collision_map.cpp:519 and :539 do the same);
+ *   2. out-of-grid voxels are component -1 everywhere (collision_map.hpp:108 compares z_index == GetNumZCells(), so the
+ *      z = nz - 1 face is missed, and interior comparisons against the edge read the OOB cell's component).
+ * Refused (SDFGPU_ERR_INVALID_ARGUMENT, with a message): a label above max_label; max_label = 2^32 - 1; more than 2^32 - 1
+ * voxels (by shape alone, before anything is allocated); an index buffer whose capacity is below the total -- out_counts and
+ * *out_total are valid then, so the caller can size the buffer and call again, and nothing is written past the capacity.
+ * All three are synchronous and use scratch of their own from the library's allocator (the SDF scratch, status block and
+ * policy are left as they were).
+ *
+ *   sdfgpu_component_surfaces_device: d_labels (n uint32), d_select_bits (ceil(n / 32) words, NULL = every voxel), d_indices
+ *       (capacity uint32, NULL = counts only), d_surface_bits (NULL = not wanted): device pointers, 4-byte aligned.
+ *   sdfgpu_component_surfaces: host labels (n uint32), host select_mask (n bytes, nonzero = selected; NULL = every voxel), host
+ *       out_indices (capacity uint32, NULL = counts only).
+ *   sdfgpu_component_surfaces_cells: labels from each record's uint32 at component_offset, selection from its occupancy float
+ *       by class_mask (7 = every voxel), packed on the host like sdfgpu_component_topology_cells' selection.
+ * ------------------------------------------------------------------------- */
+int sdfgpu_component_surfaces_device(sdfgpu_handle h, const uint32_t* d_labels, const uint32_t* d_select_bits, int64_t nx, int64_t ny,
+                                     int64_t nz, uint32_t max_label, int64_t* out_counts, uint32_t* d_indices, int64_t capacity,
+                                     int64_t* out_total, uint32_t* d_surface_bits, void* stream);
+int sdfgpu_component_surfaces(sdfgpu_handle h, const uint32_t* labels, const uint8_t* select_mask, int64_t nx, int64_t ny, int64_t nz,
+                              uint32_t max_label, int64_t* out_counts, uint32_t* out_indices, int64_t capacity, int64_t* out_total);
+int sdfgpu_component_surfaces_cells(sdfgpu_handle h, const void* cells, size_t cell_stride, size_t occupancy_offset, size_t component_offset,
+                                    int64_t nx, int64_t ny, int64_t nz, int class_mask, uint32_t max_label, int64_t* out_counts,
+                                    uint32_t* out_indices, int64_t capacity, int64_t* out_total);
+
 /* -------------------------------------------------------------------------
  * Local extrema and convex segments: SignedDistanceField::ComputeLocalExtremaMap (reference src/sdf_tools/sdf.cpp:23-207) and
  * TaggedObjectCollisionMapGrid::UpdateConvexSegments (tagged_object_collision_map.cpp:552-654) on the GPU.  DESIGN.md section 15.

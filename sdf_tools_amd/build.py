@@ -33,9 +33,9 @@ def _hipcc():
 
 
 def build_libsdfgpu(force=False, verbose=False):
-    """Nine translation units -> objects (compiled side by side) -> libsdfgpu.so: sdfgpu.hip (C ABI, host orchestration, most
+    """Ten translation units -> objects (compiled side by side) -> libsdfgpu.so: sdfgpu.hip (C ABI, host orchestration, most
     kernels), sdfgpu_envelope_tu.hip (the far-field kernel's instantiations), sdfgpu_dense6_tu.hip (the shell pass),
-    sdfgpu_components.hip (connected components), sdfgpu_topology.hip (component topology), sdfgpu_convex.hip (local extrema
+    sdfgpu_components.hip (connected components), sdfgpu_topology.hip (component topology), sdfgpu_surfaces.hip (component surfaces), sdfgpu_convex.hip (local extrema
     and convex segments), sdfgpu_project.hip (projection out of collision) sdfgpu_query.hip (smooth and autodiff gradients,
     distance to the boundary) and sdfgpu_batch.hip (batches of small same-shape grids).  Each object is rebuilt when its
     source or ANY header it can include is newer (a stale library after a header-only edit is the kind of bug that
@@ -49,6 +49,7 @@ def build_libsdfgpu(force=False, verbose=False):
              (os.path.join(CSRC, "sdfgpu_dense6_tu.hip"), d6_hdrs),
              (os.path.join(CSRC, "sdfgpu_components.hip"), [os.path.join(CSRC, "sdfgpu_components.hpp")]),
              (os.path.join(CSRC, "sdfgpu_topology.hip"), [os.path.join(CSRC, "sdfgpu_topology.hpp")]),
+             (os.path.join(CSRC, "sdfgpu_surfaces.hip"), [os.path.join(CSRC, "sdfgpu_surfaces.hpp")]),
              (os.path.join(CSRC, "sdfgpu_convex.hip"), [os.path.join(CSRC, f) for f in ("sdfgpu_convex.hpp", "sdfgpu_kernels.hpp")]),
              (os.path.join(CSRC, "sdfgpu_project.hip"), [os.path.join(CSRC, f) for f in ("sdfgpu_project.hpp", "sdfgpu_kernels.hpp")] +
               [os.path.join(INCLUDE, "sdfgpu.h")]),

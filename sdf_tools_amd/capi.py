@@ -30,6 +30,7 @@ EXPORTS = [
     "sdfgpu_build_bits_device", "sdfgpu_build_bits", "sdfgpu_voxelize_points_bits_device", "sdfgpu_debug_finish_table", "sdfgpu_redzone_check",
     "sdfgpu_components_bits_device", "sdfgpu_components", "sdfgpu_components_cells",
     "sdfgpu_component_topology_device", "sdfgpu_component_topology", "sdfgpu_component_topology_cells",
+    "sdfgpu_component_surfaces_device", "sdfgpu_component_surfaces", "sdfgpu_component_surfaces_cells",
     "sdfgpu_local_extrema_device", "sdfgpu_local_extrema", "sdfgpu_convex_segments_cells", "sdfgpu_convex_last_info",
     "sdfgpu_project_step_limit", "sdfgpu_project_points_device", "sdfgpu_project_points",
     "sdfgpu_query_gradients_device", "sdfgpu_query_gradients",
@@ -129,6 +130,9 @@ def load_library():
     L.sdfgpu_component_topology_device.argtypes = [vp, vp, vp, i64, i64, i64, u32, vp, vp]
     L.sdfgpu_component_topology.argtypes = [vp, vp, vp, i64, i64, i64, u32, vp]
     L.sdfgpu_component_topology_cells.argtypes = [vp, vp, sz, sz, sz, i64, i64, i64, ci, u32, vp]
+    L.sdfgpu_component_surfaces_device.argtypes = [vp, vp, vp, i64, i64, i64, u32, vp, vp, i64, vp, vp, vp]
+    L.sdfgpu_component_surfaces.argtypes = [vp, vp, vp, i64, i64, i64, u32, vp, vp, i64, vp]
+    L.sdfgpu_component_surfaces_cells.argtypes = [vp, vp, sz, sz, sz, i64, i64, i64, ci, u32, vp, vp, i64, vp]
     L.sdfgpu_local_extrema_device.argtypes = [vp, vp, i64, i64, i64, dbl, vp, vp, vp]
     L.sdfgpu_local_extrema.argtypes = [vp, vp, i64, i64, i64, dbl, vp, vp]
     L.sdfgpu_convex_segments_cells.argtypes = [vp, vp, sz, sz, sz, sz, i64, i64, i64, dbl, vp, dbl, ci, vp]
@@ -481,6 +485,79 @@ class SdfGpu:
         self._check(self._lib.sdfgpu_component_topology_cells(self._h, cells.ctypes.data, cell_stride, occupancy_offset, component_offset,
                                                                nx, ny, nz, int(class_mask), int(max_label), out.ctypes.data))
         return out
+
+    # ---- component surfaces (CollisionMapGrid::ExtractComponentSurfaces, include/sdfgpu.h) -----------------
+    def component_surfaces(self, labels, select=None, max_label=None):
+        """labels: uint32 [nx, ny, nz]; select: bool/uint8 [nx, ny, nz] or None (every voxel).  Returns (counts int64
+        [max_label + 1], indices uint32 [total]): the selected surface voxels grouped by ascending label, ascending inside each
+        group (group c starts at counts[:c].sum()).  max_label defaults to the largest label."""
+        lab = np.ascontiguousarray(labels, dtype=np.uint32)
+        if lab.ndim != 3:
+            raise ValueError("labels must be [nx, ny, nz]")
+        if max_label is None:
+            max_label = int(lab.max()) if lab.size else 0
+        sel = None
+        if select is not None:
+            sel = np.ascontiguousarray(np.asarray(select) != 0, dtype=np.uint8)
+            if sel.shape != lab.shape:
+                raise ValueError("select must have the labels' shape")
+        counts = np.zeros(int(max_label) + 1, np.int64)
+        idx = np.empty(max(lab.size, 1), np.uint32)           # (every voxel can be a surface voxel)
+        total = ctypes.c_int64(0)
+        self._check(self._lib.sdfgpu_component_surfaces(self._h, lab.ctypes.data, None if sel is None else sel.ctypes.data, *lab.shape,
+                                                         int(max_label), counts.ctypes.data, idx.ctypes.data, lab.size, ctypes.byref(total)))
+        return counts, idx[:total.value].copy()
+
+    def component_surfaces_device(self, d_labels, shape, max_label, d_select_bits=None, d_indices=None, capacity=0, d_surface_bits=None,
+                                  stream=0, counts_only=False):
+        """d_labels: device uint32 [n]; d_select_bits: device bit field (ceil(n / 32) words) or None; d_surface_bits: device bit
+        field to receive the reported voxels, or None.  With d_indices (device uint32 [capacity]) the indices stay on the device
+        and the call returns (counts, total); a capacity below the total raises SdfGpuError, whose `total` attribute then holds
+        the number needed.  With counts_only it returns (counts, total) and sorts nothing.  Otherwise the indices are fetched:
+        (counts int64 [max_label + 1], indices uint32 [total]).  Synchronises `stream`."""
+        nx, ny, nz = (int(s) for s in shape)
+        counts = np.zeros(int(max_label) + 1, np.int64)
+        total = ctypes.c_int64(-1)
+
+        def call(d_idx, cap):
+            try:
+                self._check(self._lib.sdfgpu_component_surfaces_device(self._h, d_labels, d_select_bits or None, nx, ny, nz, int(max_label),
+                                                                        counts.ctypes.data, d_idx or None, int(cap), ctypes.byref(total),
+                                                                        d_surface_bits or None, stream or None))
+            except SdfGpuError as e:
+                e.total = int(total.value)
+                raise
+        if d_indices or counts_only:
+            call(d_indices, capacity)
+            return counts, int(total.value)
+        call(None, 0)
+        n_idx = int(total.value)
+        idx = np.empty(n_idx, np.uint32)
+        if n_idx:
+            d_idx = self.device_malloc(n_idx * 4)
+            try:
+                call(d_idx, n_idx)
+                self.copy_to_host(idx, d_idx, stream)
+            finally:
+                self.device_free(d_idx)
+        return counts, idx
+
+    def component_surfaces_cells(self, cells, shape, class_mask, max_label, cell_stride=8, occupancy_offset=0, component_offset=4):
+        """cells: contiguous records (COLLISION_CELL: 8, 0, 4; TAGGED_OBJECT_COLLISION_CELL: 16, 0, 4) holding labels;
+        class_mask: TOPOLOGY_FILLED | TOPOLOGY_EMPTY | TOPOLOGY_UNKNOWN (7 = every voxel).  Returns (counts int64 [max_label + 1],
+        indices uint32 [total])."""
+        nx, ny, nz = (int(s) for s in shape)
+        if not (isinstance(cells, np.ndarray) and cells.flags.c_contiguous):
+            raise ValueError("cells must be a C-contiguous numpy array")
+        if cells.nbytes != nx * ny * nz * cell_stride:
+            raise ValueError("cells buffer size does not match shape * cell_stride")
+        counts = np.zeros(int(max_label) + 1, np.int64)
+        idx = np.empty(max(nx * ny * nz, 1), np.uint32)
+        total = ctypes.c_int64(0)
+        self._check(self._lib.sdfgpu_component_surfaces_cells(self._h, cells.ctypes.data, cell_stride, occupancy_offset, component_offset,
+                                                               nx, ny, nz, int(class_mask), int(max_label), counts.ctypes.data,
+                                                               idx.ctypes.data, nx * ny * nz, ctypes.byref(total)))
+        return counts, idx[:total.value].copy()
 
     # ---- local extrema and convex segments (ComputeLocalExtremaMap / UpdateConvexSegments, include/sdfgpu.h) -----------------
     def local_extrema(self, sdf, resolution, q=(1.0, 0.0, 0.0, 0.0)):

@@ -42,6 +42,58 @@ py::array_t<double> MatrixToArray(const Isometry3d& t) {
 
 }  // namespace
 
+// ExtractComponentSurfaces for Python: {component: {(x, y, z): 1}}, and the bulk form (offsets int64 [max_label + 2], indices uint32)
+template <typename Grid>
+py::dict SurfacesDict(const Grid& g, int types) {
+    sdf_tools::ComponentSurfaceIndices s;
+    {
+        py::gil_scoped_release release;
+        s = g.ExtractComponentSurfaceIndices((typename Grid::COMPONENT_TYPES)types);
+    }
+    const int64_t ny = g.GetNumYCells(), nz = g.GetNumZCells();
+    py::dict out;
+    for (size_t c = 0; c + 1 < s.offsets.size(); ++c) {
+        if (s.offsets[c + 1] == s.offsets[c]) continue;
+        py::dict cells;
+        for (uint64_t i = s.offsets[c]; i < s.offsets[c + 1]; ++i) {
+            const int64_t v = (int64_t)s.indices[(size_t)i], t = v / nz;
+            cells[py::make_tuple(t / ny, t % ny, v % nz)] = 1;
+        }
+        out[py::int_(c)] = cells;
+    }
+    return out;
+}
+
+template <typename Grid>
+py::tuple SurfacesNumpy(const Grid& g, int types) {
+    sdf_tools::ComponentSurfaceIndices s;
+    {
+        py::gil_scoped_release release;
+        s = g.ExtractComponentSurfaceIndices((typename Grid::COMPONENT_TYPES)types);
+    }
+    py::array_t<int64_t> offsets((py::ssize_t)s.offsets.size());
+    for (size_t c = 0; c < s.offsets.size(); ++c) offsets.mutable_data()[c] = (int64_t)s.offsets[c];
+    py::array_t<uint32_t> indices((py::ssize_t)s.indices.size());
+    if (!s.indices.empty()) std::memcpy(indices.mutable_data(), s.indices.data(), s.indices.size() * sizeof(uint32_t));
+    return py::make_tuple(offsets, indices);
+}
+
+template <typename Grid, typename Class>
+void DefSurfaces(Class& cls) {
+    cls.def("ExtractComponentSurfaces", [](const Grid& g, int types) { return SurfacesDict(g, types); }, py::arg("component_types_to_extract"),
+            "{component: {(x, y, z): 1}} of the surface voxels whose class is in FILLED_COMPONENTS | EMPTY_COMPONENTS | UNKNOWN_COMPONENTS, "
+            "from the stored components, on the GPU (include/sdfgpu.h \"Component surfaces\")")
+        .def("ExtractFilledComponentSurfaces", [](const Grid& g) { return SurfacesDict(g, 1); })
+        .def("ExtractEmptyComponentSurfaces", [](const Grid& g) { return SurfacesDict(g, 2); })
+        .def("ExtractUnknownComponentSurfaces", [](const Grid& g) { return SurfacesDict(g, 4); })
+        .def("ExtractComponentSurfaceIndicesNumpy", [](const Grid& g, int types) { return SurfacesNumpy(g, types); },
+             py::arg("component_types_to_extract"),
+             "(offsets int64 [max_label + 2], indices uint32): component c's surface voxels are indices[offsets[c]:offsets[c + 1]], ascending");
+    cls.attr("FILLED_COMPONENTS") = py::int_(1);
+    cls.attr("EMPTY_COMPONENTS") = py::int_(2);
+    cls.attr("UNKNOWN_COMPONENTS") = py::int_(4);
+}
+
 PYBIND11_MODULE(pysdf_tools, m) {
     m.doc() = "MI355X-native drop-in for sdf_tools' pysdf_tools (SDF build on the GPU via libsdfgpu.so)";
 
@@ -89,7 +141,9 @@ PYBIND11_MODULE(pysdf_tools, m) {
         .def_readwrite("is_compressed", &TaggedObjectCollisionMap::is_compressed)
         .def_property("frame_id", [](const TaggedObjectCollisionMap& s) { return s.header.frame_id; },
                       [](TaggedObjectCollisionMap& s, const std::string& f) { s.header.frame_id = f; });
-    py::class_<TaggedObjectCollisionMapGrid>(m, "TaggedObjectCollisionMapGrid")
+    py::class_<TaggedObjectCollisionMapGrid> tagged_grid(m, "TaggedObjectCollisionMapGrid");
+    DefSurfaces<TaggedObjectCollisionMapGrid>(tagged_grid);
+    tagged_grid
         .def(py::init<Isometry3d const&, std::string, double, int64_t, int64_t, int64_t, TAGGED_OBJECT_COLLISION_CELL const&>())
         .def(py::init<>())
         .def("SetValue", [](TaggedObjectCollisionMapGrid& g, int64_t x, int64_t y, int64_t z, const TAGGED_OBJECT_COLLISION_CELL& c) { return g.SetValue(x, y, z, c); })
@@ -369,7 +423,9 @@ PYBIND11_MODULE(pysdf_tools, m) {
            "n x EstimateDistance3d + GetGradient3d (sdf.hpp:947-953, :395-403) in one kernel: (distance [n], gradient [n, 3], flags [n]: "
            "bit 0 inside the grid, bit 1 gradient available)");
 
-    py::class_<CollisionMapGrid>(m, "CollisionMapGrid")
+    py::class_<CollisionMapGrid> collision_grid(m, "CollisionMapGrid");
+    DefSurfaces<CollisionMapGrid>(collision_grid);
+    collision_grid
         .def(py::init<Isometry3d const&, std::string, double, int64_t, int64_t, int64_t, COLLISION_CELL const&>())
         .def("SetValue", [](CollisionMapGrid& g, int64_t x, int64_t y, int64_t z, const COLLISION_CELL& c) { return g.SetValue(x, y, z, c); })
         .def("SetValueByCoordinates", [](CollisionMapGrid& g, double x, double y, double z, const COLLISION_CELL& c) { return g.SetValue(x, y, z, c); })

@@ -13,6 +13,7 @@
 #include "sdfgpu_hostteam.hpp"
 #include "sdfgpu_components.hpp"
 #include "sdfgpu_topology.hpp"
+#include "sdfgpu_surfaces.hpp"
 #include "sdfgpu_convex.hpp"
 #include "sdfgpu_project.hpp"
 #include "sdfgpu_query.hpp"
@@ -75,6 +76,9 @@ struct sdfgpu_context {
     DeviceBuffer cc_scratch;    // sdfgpu_components*: root flags, ranks, chunk counts, K (sdfgpu_components.hpp)
     DeviceBuffer tp_scratch;    // sdfgpu_component_topology*: counters, status, node bytes, node offsets (sdfgpu_topology.hpp)
     DeviceBuffer tp_nodes;      // sdfgpu_component_topology*: one union-find word per surface-vertex node
+    DeviceBuffer sf_scratch;    // sdfgpu_component_surfaces*: per-label counts, status, surface bit words (sdfgpu_surfaces.hpp)
+    DeviceBuffer sf_sort;       // sdfgpu_component_surfaces*: the sort's pair buffers and histogram table
+    DeviceBuffer sf_indices;    // sdfgpu_component_surfaces / _cells: the indices on their way to the caller's host buffer
     DeviceBuffer cx_scratch;    // sdfgpu_local_extrema* / sdfgpu_convex_segments_cells: doubling state, next, stats, ranks (sdfgpu_convex.hpp)
     DeviceBuffer cx_field;      // sdfgpu_local_extrema: the field; sdfgpu_convex_segments_cells: the named-object SDF, then the extrema
     size_t cx_stats_off = 0;    // where the last extrema call left its CxStats in cx_scratch (0 = no call yet)
@@ -1752,10 +1756,10 @@ void pack_cells_class_bits(const char* cells, size_t stride, size_t off, int cla
     }
 }
 
-// host labels / cell records -> stage_out (labels) and, unless select_all, stage_bits (selection) -> counters
-int topology_host(sdfgpu_handle h, const uint32_t* labels, const uint8_t* select, const void* cells, size_t stride, size_t occ_off,
-                  size_t comp_off, int class_mask, int64_t nx, int64_t ny, int64_t nz, uint32_t max_label, int64_t* out_counts) {
-    const int64_t n = nx * ny * nz;
+// host labels / cell records -> stage_out (labels) and, unless every voxel is selected, stage_bits (selection); *out_selected
+// says which
+int stage_labels_selection(sdfgpu_handle h, const uint32_t* labels, const uint8_t* select, const void* cells, size_t stride, size_t occ_off,
+                           size_t comp_off, int class_mask, int64_t n, bool* out_selected) {
     if (int rc = ensure(h, h->stage_out, (size_t)n * 4, "output staging")) return rc;
     if (labels) {
         if (int rc = copy_from_host(h, h->stage_out.ptr, labels, (size_t)n * 4)) return rc;
@@ -1782,8 +1786,74 @@ int topology_host(sdfgpu_handle h, const uint32_t* labels, const uint8_t* select
                 return rc;
         }
     }
+    *out_selected = selected;
+    return SDFGPU_OK;
+}
+
+// host labels / cell records -> counters
+int topology_host(sdfgpu_handle h, const uint32_t* labels, const uint8_t* select, const void* cells, size_t stride, size_t occ_off,
+                  size_t comp_off, int class_mask, int64_t nx, int64_t ny, int64_t nz, uint32_t max_label, int64_t* out_counts) {
+    bool selected = false;
+    if (int rc = stage_labels_selection(h, labels, select, cells, stride, occ_off, comp_off, class_mask, nx * ny * nz, &selected)) return rc;
     return topology_impl(h, (const uint32_t*)h->stage_out.ptr, selected ? (const uint32_t*)h->stage_bits.ptr : nullptr, nx, ny, nz,
                          max_label, out_counts, nullptr);
+}
+
+// ---- component surfaces (sdfgpu_surfaces.hpp) -----------------------------------------------------------------------------------
+// Like the topology: only sf_scratch, sf_sort and sf_indices (and, in the host forms, the label / bit staging and the pinned
+// chunks) are used; the SDF builds' scratch, status block and policy are not touched.
+int check_surfaces_args(sdfgpu_handle h, int64_t nx, int64_t ny, int64_t nz, uint32_t max_label, const int64_t* out_counts, bool want_indices,
+                        int64_t capacity, const int64_t* out_total) {
+    if (!out_counts || !out_total) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
+    if (int rc = check_components_dims(h, nx, ny, nz)) return rc;
+    if (max_label == 0xFFFFFFFFu) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "max_label must be below 2^32 - 1");
+    if (want_indices && capacity < 0) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "capacity must not be negative (got %lld)", (long long)capacity);
+    return SDFGPU_OK;
+}
+
+// labels (device) + selection bits (device or null) -> counts (host) and, when asked, the grouped indices: into d_indices
+// (device) or, through sf_indices, into host_indices.  Synchronises `st`.
+int surfaces_impl(sdfgpu_handle h, const uint32_t* d_labels, const uint32_t* d_select, int64_t nx, int64_t ny, int64_t nz, uint32_t max_label,
+                  int64_t* out_counts, uint32_t* d_indices, uint32_t* host_indices, int64_t capacity, int64_t* out_total,
+                  uint32_t* d_surface_bits, hipStream_t st) {
+    const SfPlan plan = sf_plan(nx, ny, nz, max_label);
+    if (int rc = ensure(h, h->sf_scratch, plan.scratch_bytes, "surfaces scratch")) return rc;
+    HIP_TRY(h, sf_launch_flag(plan, d_labels, d_select, d_surface_bits, h->sf_scratch.ptr, st));
+    SfStatus status;
+    HIP_TRY(h, hipMemcpyAsync(&status, static_cast<char*>(h->sf_scratch.ptr) + plan.off_status, sizeof status, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    if (status.err & kSfErrLabel)
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "label %u exceeds max_label %u", status.label_over, max_label);
+    *out_total = (int64_t)status.total;
+    {                                                           // (uint32 counters, widened: every count is below 2^32)
+        std::vector<uint32_t> c32((size_t)max_label + 1);
+        if (int rc = copy_to_host(h, c32.data(), h->sf_scratch.ptr, c32.size() * 4, st)) return rc;
+        for (size_t c = 0; c < c32.size(); ++c) out_counts[c] = (int64_t)c32[c];
+    }
+    if (!d_indices && !host_indices) return SDFGPU_OK;          // counts only
+    if ((uint64_t)capacity < status.total)
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "the index buffer holds %lld indices, the surfaces have %llu (counts and total are valid)",
+                    (long long)capacity, (unsigned long long)status.total);
+    if (status.total == 0) return SDFGPU_OK;
+    if (host_indices) {
+        if (int rc = ensure(h, h->sf_indices, (size_t)status.total * 4, "surfaces indices")) return rc;
+        d_indices = (uint32_t*)h->sf_indices.ptr;
+    }
+    const SfSortPlan sp = sf_sort_plan(plan, status.total);
+    if (int rc = ensure(h, h->sf_sort, sp.bytes, "surfaces sort scratch")) return rc;
+    HIP_TRY(h, sf_launch_sort(plan, sp, d_labels, h->sf_scratch.ptr, h->sf_sort.ptr, d_indices, st));
+    if (host_indices) return copy_to_host(h, host_indices, d_indices, (size_t)status.total * 4, st);
+    HIP_TRY(h, hipStreamSynchronize(st));
+    return SDFGPU_OK;
+}
+
+int surfaces_host(sdfgpu_handle h, const uint32_t* labels, const uint8_t* select, const void* cells, size_t stride, size_t occ_off,
+                  size_t comp_off, int class_mask, int64_t nx, int64_t ny, int64_t nz, uint32_t max_label, int64_t* out_counts,
+                  uint32_t* out_indices, int64_t capacity, int64_t* out_total) {
+    bool selected = false;
+    if (int rc = stage_labels_selection(h, labels, select, cells, stride, occ_off, comp_off, class_mask, nx * ny * nz, &selected)) return rc;
+    return surfaces_impl(h, (const uint32_t*)h->stage_out.ptr, selected ? (const uint32_t*)h->stage_bits.ptr : nullptr, nx, ny, nz,
+                         max_label, out_counts, nullptr, out_indices, capacity, out_total, nullptr, nullptr);
 }
 
 // ---- local extrema and convex segments (sdfgpu_convex.hpp) ---------------------------------------------------------------------
@@ -1914,7 +1984,7 @@ int sdfgpu_destroy(sdfgpu_handle h) {
     (void)hipSetDevice(h->device);
     for (DeviceBuffer* b : {&h->zfield, &h->yzfield, &h->plane16, &h->bits, &h->unc, &h->tileflag, &h->fix_order, &h->tagmask, &h->tagids, &h->stage_in,
                             &h->stage_bits, &h->stage_out, &h->query_stage, &h->planebits, &h->cc_scratch,
-                            &h->tp_scratch, &h->tp_nodes, &h->cx_scratch, &h->cx_field, &h->batch_field, &h->batch_ext, &h->batch_res,
+                            &h->tp_scratch, &h->tp_nodes, &h->sf_scratch, &h->sf_sort, &h->sf_indices, &h->cx_scratch, &h->cx_field, &h->batch_field, &h->batch_ext, &h->batch_res,
                             &h->batch_gscale})
         if (b->ptr) (void)rz_free(h, b->ptr);
     if (h->d_small) (void)rz_free(h, h->d_small);
@@ -3104,6 +3174,51 @@ int sdfgpu_component_topology_cells(sdfgpu_handle h, const void* cells, size_t c
         HIP_TRY(h, hipSetDevice(h->device));
         return topology_host(h, nullptr, nullptr, cells, cell_stride, occupancy_offset, component_offset, class_mask, nx, ny, nz, max_label,
                              out_counts);
+    });
+}
+
+int sdfgpu_component_surfaces_device(sdfgpu_handle h, const uint32_t* d_labels, const uint32_t* d_select_bits, int64_t nx, int64_t ny,
+                                     int64_t nz, uint32_t max_label, int64_t* out_counts, uint32_t* d_indices, int64_t capacity,
+                                     int64_t* out_total, uint32_t* d_surface_bits, void* stream) {
+    return rz_wrap(h, stream, [&]() -> int {
+        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
+        if (!d_labels) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
+        if ((reinterpret_cast<uintptr_t>(d_labels) | reinterpret_cast<uintptr_t>(d_select_bits) | reinterpret_cast<uintptr_t>(d_indices) |
+             reinterpret_cast<uintptr_t>(d_surface_bits)) & 3)
+            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "d_labels, d_select_bits, d_indices and d_surface_bits must be 4-byte aligned");
+        if (int rc = check_surfaces_args(h, nx, ny, nz, max_label, out_counts, d_indices != nullptr, capacity, out_total)) return rc;
+        HIP_TRY(h, hipSetDevice(h->device));
+        return surfaces_impl(h, d_labels, d_select_bits, nx, ny, nz, max_label, out_counts, d_indices, nullptr, capacity, out_total,
+                             d_surface_bits, (hipStream_t)stream);
+    });
+}
+
+int sdfgpu_component_surfaces(sdfgpu_handle h, const uint32_t* labels, const uint8_t* select_mask, int64_t nx, int64_t ny, int64_t nz,
+                              uint32_t max_label, int64_t* out_counts, uint32_t* out_indices, int64_t capacity, int64_t* out_total) {
+    return rz_wrap(h, nullptr, [&]() -> int {
+        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
+        if (!labels) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
+        if (int rc = check_surfaces_args(h, nx, ny, nz, max_label, out_counts, out_indices != nullptr, capacity, out_total)) return rc;
+        HIP_TRY(h, hipSetDevice(h->device));
+        return surfaces_host(h, labels, select_mask, nullptr, 0, 0, 0, 7, nx, ny, nz, max_label, out_counts, out_indices, capacity, out_total);
+    });
+}
+
+int sdfgpu_component_surfaces_cells(sdfgpu_handle h, const void* cells, size_t cell_stride, size_t occupancy_offset, size_t component_offset,
+                                    int64_t nx, int64_t ny, int64_t nz, int class_mask, uint32_t max_label, int64_t* out_counts,
+                                    uint32_t* out_indices, int64_t capacity, int64_t* out_total) {
+    return rz_wrap(h, nullptr, [&]() -> int {
+        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
+        if (!cells) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
+        if (cell_stride < 8 || (cell_stride % 4) || (occupancy_offset % 4) || (component_offset % 4) || occupancy_offset + 4 > cell_stride ||
+            component_offset + 4 > cell_stride || occupancy_offset == component_offset)
+            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cell_stride / occupancy_offset / component_offset must be 4-byte aligned, in range and distinct");
+        if (class_mask < 1 || class_mask > 7)
+            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "class_mask must be a nonzero combination of FILLED (1), EMPTY (2) and UNKNOWN (4)");
+        if (int rc = check_surfaces_args(h, nx, ny, nz, max_label, out_counts, out_indices != nullptr, capacity, out_total)) return rc;
+        HIP_TRY(h, hipSetDevice(h->device));
+        return surfaces_host(h, nullptr, nullptr, cells, cell_stride, occupancy_offset, component_offset, class_mask, nx, ny, nz, max_label,
+                             out_counts, out_indices, capacity, out_total);
     });
 }
 
