@@ -524,7 +524,9 @@ int sdfgpu_component_surfaces_cells(sdfgpu_handle h, const void* cells, size_t c
  * of their own (the SDF scratch, status block and policy are left as they were).  All results are bit-reproducible.
  *
  *   sdfgpu_local_extrema_device: d_sdf (n floats) -> d_extremum (n uint32), enqueued on `stream`; synchronises it once per
- *       doubling round (the host reads the count of unresolved voxels).
+ *       doubling round (the host reads the count of unresolved voxels) and returns with its last three kernels pending there:
+ *       read d_extremum on `stream` or after synchronising it.  Calls on one handle from different streams are ordered by the
+ *       library (a call first waits, on the device, for the previous call's last kernel), as builds are.
  *   sdfgpu_local_extrema: host field in, host indices out.
  *   sdfgpu_convex_segments_cells: synchronous, in place; the records are uploaded once and the SDF, extrema and labels stay on
  *       the device until the labels are scattered into each record's uint32 at segment_offset.

@@ -200,6 +200,10 @@ struct sdfgpu_context {
                                           // work on another stream waits for it first
     bool order_valid = false;             // build_done_ev has been recorded on order_stream
     hipStream_t order_stream = nullptr;
+    hipEvent_t cx_done_ev = nullptr;      // recorded behind every local-extrema computation, whose last three kernels are still
+                                          // pending on its stream when the call returns: one on another stream waits for it first
+    bool cx_order_valid = false;          // cx_done_ev has been recorded on cx_stream
+    hipStream_t cx_stream = nullptr;
     bool last_dense = false;
     const uint32_t* guard = nullptr; // set while a build enqueues the flag-guarded general pipeline
     bool plane16_on = true;          // use the int16 plane field + side table when the shape allows
@@ -1881,12 +1885,19 @@ int check_convex_args(sdfgpu_handle h, int64_t nx, int64_t ny, int64_t nz, doubl
 int extrema_impl(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t ny, int64_t nz, double resolution, const double* q_and_qinv,
                  uint32_t* d_ext, hipStream_t st) {
     const CxPlan plan = cx_plan(nx, ny, nz);
+    // cx_extrema returns with its basin / entry / final kernels still pending on `st`, and they read and write cx_scratch: a
+    // computation on another stream is ordered behind them, as the builds are ordered by build_done_ev.  (ensure() below may
+    // free the scratch: hipFree waits for the device.)
+    if (!h->cx_done_ev) HIP_TRY(h, hipEventCreateWithFlags(&h->cx_done_ev, hipEventDisableTiming));
+    if (h->cx_order_valid && st != h->cx_stream) HIP_TRY(h, hipStreamWaitEvent(st, h->cx_done_ev, 0));
     if (int rc = ensure(h, h->cx_scratch, plan.scratch_bytes, "convex scratch")) return rc;
     CxRot rot;
     for (int i = 0; i < 4; ++i) { rot.q[i] = q_and_qinv[i]; rot.qi[i] = q_and_qinv[4 + i]; }
     int rounds = 0;
     h->cx_stats_off = 0;
-    HIP_TRY(h, cx_extrema(plan, d_sdf, resolution, rot, d_ext, h->cx_scratch.ptr, st, &rounds));
+    const hipError_t ce = cx_extrema(plan, d_sdf, resolution, rot, d_ext, h->cx_scratch.ptr, st, &rounds);
+    if (hipEventRecord(h->cx_done_ev, st) == hipSuccess) { h->cx_order_valid = true; h->cx_stream = st; }
+    HIP_TRY(h, ce);
     h->cx_stats_off = plan.off_stats;
     h->cx_rounds = rounds;
     return SDFGPU_OK;
@@ -1994,6 +2005,7 @@ int sdfgpu_destroy(sdfgpu_handle h) {
     if (h->h_flags) { (void)hipHostFree(h->h_flags); (void)hipEventDestroy(h->flags_ev); }
     if (h->far_ev) (void)hipEventDestroy(h->far_ev);
     if (h->build_done_ev) (void)hipEventDestroy(h->build_done_ev);
+    if (h->cx_done_ev) (void)hipEventDestroy(h->cx_done_ev);
     for (int i = 0; i < 2; ++i) { if (h->pin[i]) (void)hipHostFree(h->pin[i]); if (h->pin_ev[i]) (void)hipEventDestroy(h->pin_ev[i]); }
     for (size_t i = 0; i < h->events.size(); ++i)
         if (i % 8 == 0 || h->events[i] != h->events[i - 1]) (void)hipEventDestroy(h->events[i]);
