@@ -29,6 +29,7 @@
 #include "arc_utilities/zlib_helpers.hpp"
 #include "sdf_tools/component_surfaces.hpp"
 #include "sdf_tools/component_topology.hpp"
+#include "sdf_tools/resample.hpp"
 #include "sdf_tools/sdf.hpp"
 #include "sdf_tools/sdf_generation.hpp"
 
@@ -118,6 +119,13 @@ public:
             GetOriginTransform(), GetCellSizes(), GetNumXCells(), GetNumYCells(), GetNumZCells(), data_.data(),
             sizeof(COLLISION_CELL), offsetof(COLLISION_CELL, occupancy), unknown_is_filled, oob_value, GetFrame(), add_virtual_border);
     }
+
+    // ---- Resample (reference collision_map.cpp:673-695) -------------------------------------------------------------------------
+    // A grid over the same volume at new_resolution: every cell, in x -> y -> z order, overwrites the result cell that holds its
+    // centre (GPU: include/sdfgpu.h "Resample", bit for bit the host arithmetic).  Coarsening keeps the last such cell of the scan;
+    // refining leaves the result cells that hold no source centre at the OOB value -- the reference's holes, kept.  The result's
+    // components are invalid.  Throws std::invalid_argument when new_resolution is not positive and finite.
+    CollisionMapGrid Resample(const double new_resolution) const { return ResampleGridFromCells(*this, new_resolution); }
 
     // ---- connected components (reference collision_map.cpp:564-618, :757-778) ---------------------------------------------
     // Two classes, occupancy > 0.5 and the rest (unknown and NaN join free space); 6-connectivity; components numbered 1..K in

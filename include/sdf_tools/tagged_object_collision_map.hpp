@@ -23,6 +23,7 @@
 #include <cstring>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -31,6 +32,7 @@
 #include "arc_utilities/zlib_helpers.hpp"
 #include "sdf_tools/component_surfaces.hpp"
 #include "sdf_tools/component_topology.hpp"
+#include "sdf_tools/resample.hpp"
 #include "sdf_tools/sdf.hpp"
 #include "sdf_tools/sdf_generation.hpp"
 
@@ -103,6 +105,14 @@ public:
                                  const int64_t z_cells, const TAGGED_OBJECT_COLLISION_CELL& oob_default_value)
         : Base(resolution, x_cells, y_cells, z_cells, oob_default_value), number_of_components_(0u),
           number_of_convex_segments_(0u), frame_(frame), components_valid_(false), convex_segments_valid_(false) {}
+    // metric sizes (the reference's second constructor; Resample builds its result with it).  Only floating-point sizes select it, so
+    // that integer literals keep meaning cell counts, as they did before this constructor existed.
+    template <typename Size, typename = typename std::enable_if<std::is_floating_point<Size>::value>::type>
+    TaggedObjectCollisionMapGrid(const Eigen::Isometry3d& origin_transform, const std::string& frame, const double resolution,
+                                 const Size x_size, const Size y_size, const Size z_size,
+                                 const TAGGED_OBJECT_COLLISION_CELL& oob_default_value)
+        : Base(origin_transform, resolution, (double)x_size, (double)y_size, (double)z_size, oob_default_value), number_of_components_(0u),
+          number_of_convex_segments_(0u), frame_(frame), components_valid_(false), convex_segments_valid_(false) {}
     TaggedObjectCollisionMapGrid()
         : Base(), number_of_components_(0u), number_of_convex_segments_(0u), frame_(""), components_valid_(false),
           convex_segments_valid_(false) {}
@@ -120,6 +130,11 @@ public:
         return true;
     }
     bool SetValue(const GRID_INDEX& i, const TAGGED_OBJECT_COLLISION_CELL& v) override { return SetValue(i.x, i.y, i.z, v); }
+
+    // ---- Resample (reference tagged_object_collision_map.cpp:399-422): as CollisionMapGrid::Resample -- whole 16-byte records move
+    // (occupancy, component, object id, convex segment); the result's components and convex segments are invalid; result cells
+    // that hold no source centre keep the OOB value.
+    TaggedObjectCollisionMapGrid Resample(const double new_resolution) const { return ResampleGridFromCells(*this, new_resolution); }
 
     // ---- connected components (reference tagged_object_collision_map.cpp:340-380): occupancy > 0.5 against the rest, whatever
     // the object id; 6-connectivity; numbered 1..K in x -> y -> z scan order, written into every cell's `component`.

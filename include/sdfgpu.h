@@ -683,6 +683,47 @@ int sdfgpu_gradient_batch_device(sdfgpu_handle h, const float* d_sdf, int64_t ba
                                  void* d_out, void* stream);
 int sdfgpu_last_batch_info(sdfgpu_handle h, int* out_fast_path, int* out_launches);
 
+/* ---------------------------------------------------------------------------
+ * Resample: CollisionMapGrid / TaggedObjectCollisionMapGrid::Resample(new_resolution) (reference src/sdf_tools/collision_map.cpp:673-695,
+ * tagged_object_collision_map.cpp:399-422) on the GPU.  DESIGN.md section 21.
+ * The caller builds the result grid (the classes do it with VoxelGrid's metric-size constructor: the source's origin transform,
+ * ceil(size / new_resolution) cells per axis) and passes both geometries; the library moves the cell records.
+ * Indices: cell (x, y, z) of a grid of nx x ny x nz is record (x ny + y) nz + z; records are cell_bytes = 4, 8 or 16 bytes and are
+ * copied whole (occupancy bit pattern, component, object id, convex segment: no field is interpreted).  Matrices are row-major
+ * 4 x 4, as in the projection entry points (all 16 entries are used, as Isometry3d * Vector4d uses them).
+ * Every source cell (x, y, z), in x -> y -> z order:
+ *   loc = origin * (src_cell[0] (x + 0.5), src_cell[1] (y + 0.5), src_cell[2] (z + 0.5), 1)
+ *   p   = dst_inverse_origin * loc
+ *   idx = floor(p[a] * dst_inv_cell[a]) per axis a            (dst_inv_cell = 1.0 / the result's cell sizes: a product, not a division)
+ *   idx inside mx x my x mz: the source record overwrites result record idx; otherwise the cell is dropped.
+ * So, of the source cells that land in one result cell, the one with the LARGEST source index stays, and a result cell on which no
+ * source cell lands holds fill_cell (any upsampling leaves such holes: the reference's behaviour, kept).
+ * Arithmetic: double precision, each row as ((m0 v0 + m1 v1) + m2 v2) + m3 v3 with separate products and sums (no FMA): bit for bit
+ * what VoxelGrid::GridIndexToLocation and LocationToGridIndex4d compute on the host.  The bounds test is made on the double
+ * (v >= 0 && v < n) before it is converted, which for finite values is the host's floor-then-compare; a p that is not finite is
+ * dropped.
+ * *out_cells_written (optional) = result cells that received a source cell.
+ * Refused (SDFGPU_ERR_INVALID_ARGUMENT, with a message, nothing written): cell_bytes not 4, 8 or 16; a dimension that is not
+ * positive; a null pointer (out_cells_written excepted); src == dst; device pointers that are not 4-byte aligned.
+ *
+ *   sdfgpu_resample_cells_device: d_src, d_dst device pointers (4-byte aligned; wider accesses are used when both are 8- or
+ *       16-byte aligned), fill_cell a host record.  A memset and two kernels on `stream`, nothing on another stream; returns with
+ *       them pending, unless out_cells_written is asked for: then it synchronises `stream`.  The winner words (4 bytes per result
+ *       cell, 8 when the source has 2^32 - 1 cells or more) are scratch of the handle: a call on another stream is ordered behind
+ *       the last one on the device.
+ *   sdfgpu_resample_cells: host src and dst, through the handle's staging buffers on the null stream; synchronous.
+ * ------------------------------------------------------------------------- */
+int sdfgpu_resample_cells_device(sdfgpu_handle h, const void* d_src, size_t cell_bytes, int64_t nx, int64_t ny, int64_t nz,
+                                 const double src_cell[3], const double origin[16], const double dst_inverse_origin[16],
+                                 const double dst_inv_cell[3], void* d_dst, int64_t mx, int64_t my, int64_t mz, const void* fill_cell,
+                                 uint64_t* out_cells_written, void* stream);
+int sdfgpu_resample_cells(sdfgpu_handle h, const void* src, size_t cell_bytes, int64_t nx, int64_t ny, int64_t nz, const double src_cell[3],
+                          const double origin[16], const double dst_inverse_origin[16], const double dst_inv_cell[3], void* dst, int64_t mx,
+                          int64_t my, int64_t mz, const void* fill_cell, uint64_t* out_cells_written);
+/* After sdfgpu_set_option(h, "resample_timing", 1): the device time of the last resample call's memset + winner kernel and of its
+ * gather kernel, in milliseconds, from HIP events on its stream (synchronises with them; tools/resample_bench.py). */
+int sdfgpu_debug_resample_times(sdfgpu_handle h, double* out_winner_ms, double* out_gather_ms);
+
 /* Red zones (round 6).  With SDFGPU_REDZONE=1 in the environment when sdfgpu_create runs -- or after
  * sdfgpu_set_option(h, "redzone", 1) -- every device allocation of the library (scratch fields, status block, extrema slots,
  * staging buffers, sdfgpu_device_malloc memory) carries 4 KiB of canary bytes in front and behind, and every entry point that
@@ -777,7 +818,10 @@ int sdfgpu_get_stage_times(sdfgpu_handle h, double* out_ms_sum, int64_t* out_bui
  *  "host_pack"               [U]      1        host-buffer builds classify on the host and upload 1 bit / voxel (0: upload + classify on
  *                                              the device; 2: whatever the size)
  *  "defer_fold"              [U]      0        stage entry points leave their maxima in the slots until sdfgpu_fold_extrema_device
- *  "redzone"                 [U]      0        canaries around every device allocation, checked at the end of every call (see above) */
+ *  "redzone"                 [U]      0        canaries around every device allocation, checked at the end of every call (see above)
+ *  "resample_plain_atomics"  [AB]     0        sdfgpu_resample_cells*: one atomic per source cell instead of one per run of neighbouring
+ *                                              lanes with the same result cell (DESIGN.md section 21 holds the measurement)
+ *  "resample_timing"         [U]      0        HIP events around the two Resample kernels (sdfgpu_debug_resample_times) */
 int sdfgpu_set_option(sdfgpu_handle h, const char* name, int value);
 
 /* Which kernels the most recent sdfgpu_build*_device call used: bit 0 = fused z+y kernel (K12),

@@ -36,6 +36,7 @@ EXPORTS = [
     "sdfgpu_query_gradients_device", "sdfgpu_query_gradients",
     "sdfgpu_build_batch_device", "sdfgpu_get_extrema_batch", "sdfgpu_build_batch", "sdfgpu_build_tagged_objects",
     "sdfgpu_gradient_batch_device", "sdfgpu_last_batch_info",
+    "sdfgpu_resample_cells_device", "sdfgpu_resample_cells", "sdfgpu_debug_resample_times",
 ]
 
 # include/sdfgpu.h "Projection": modes and per-point statuses
@@ -142,6 +143,9 @@ def load_library():
     L.sdfgpu_project_points.argtypes = [vp, vp, i64, i64, i64, dbl, vp, vp, dbl, dbl, ci, ci, vp, i64, vp, vp, vp]
     L.sdfgpu_query_gradients_device.argtypes = [vp, vp, i64, i64, i64, dbl, vp, ctypes.c_float, ci, dbl, vp, i64, vp, vp, vp, vp]
     L.sdfgpu_query_gradients.argtypes = [vp, vp, i64, i64, i64, dbl, vp, ctypes.c_float, ci, dbl, vp, i64, vp, vp, vp]
+    L.sdfgpu_resample_cells_device.argtypes = [vp, vp, sz, i64, i64, i64, vp, vp, vp, vp, vp, i64, i64, i64, vp, vp, vp]
+    L.sdfgpu_resample_cells.argtypes = [vp, vp, sz, i64, i64, i64, vp, vp, vp, vp, vp, i64, i64, i64, vp, vp]
+    L.sdfgpu_debug_resample_times.argtypes = [vp, vp, vp]
     L.sdfgpu_build_batch_device.argtypes = [vp, vp, i64, i64, i64, i64, dbl, vp, ci, vp, vp]
     L.sdfgpu_get_extrema_batch.argtypes = [vp, i64, vp, vp]
     L.sdfgpu_build_batch.argtypes = [vp, vp, i64, i64, i64, i64, dbl, vp, ci, vp, vp, vp]
@@ -233,6 +237,16 @@ def _transform12(t):
         return None
     a = np.asarray(t, np.float64)
     return (ctypes.c_double * 12)(*a.reshape(-1, 4)[:3].reshape(-1))
+
+
+def _doubles(v, n):
+    """scalar or sequence -> n C doubles (a scalar is repeated; a matrix is taken row-major)"""
+    a = np.asarray(v, np.float64).reshape(-1)
+    if a.size == 1:
+        a = np.repeat(a, n)
+    if a.size != n:
+        raise ValueError("expected %d values, got %d" % (n, a.size))
+    return (ctypes.c_double * n)(*a)
 
 
 def project_step_limit(shape, stepsize_multiplier=1.0 / 8.0, max_steps=0):
@@ -642,6 +656,49 @@ class SdfGpu:
         self._check(self._lib.sdfgpu_query_gradients_device(
             self._h, d_sdf or None, nx, ny, nz, float(resolution), _transform12(world_to_grid), float(oob_value), int(kind),
             float(window), d_points or None, int(n_points), d_value or None, d_gradient or None, d_status or None, stream or None))
+
+    # ---- Resample (CollisionMapGrid / TaggedObjectCollisionMapGrid::Resample, include/sdfgpu.h) -----------------
+    def _resample_geometry(self, shape, src_cell, origin, dst_inverse_origin, dst_inv_cell, dst_shape, fill_cell, cell_bytes):
+        fill = np.ascontiguousarray(fill_cell).view(np.uint8).reshape(-1)
+        if fill.size != cell_bytes:
+            raise ValueError("fill_cell must hold cell_bytes bytes")
+        return ([int(v) for v in shape], _doubles(src_cell, 3), _doubles(origin, 16), _doubles(dst_inverse_origin, 16),
+                _doubles(dst_inv_cell, 3), [int(v) for v in dst_shape], fill)
+
+    def resample_cells(self, cells, shape, src_cell, origin, dst_inverse_origin, dst_inv_cell, dst_shape, fill_cell, cell_bytes=8):
+        """cells: contiguous records (COLLISION_CELL 8 bytes, TAGGED_OBJECT_COLLISION_CELL 16, or 4) of a grid `shape` with cell
+        sizes src_cell and the 4 x 4 origin transform; the result grid has dst_shape cells, the 4 x 4 inverse origin transform
+        dst_inverse_origin and cell sizes 1 / dst_inv_cell.  Returns (records uint8 [mx, my, mz, cell_bytes], result cells
+        written): each result cell holds the source cell of the largest linear index that lands in it, or fill_cell."""
+        if not (isinstance(cells, np.ndarray) and cells.flags.c_contiguous):
+            raise ValueError("cells must be a C-contiguous numpy array")
+        (nx, ny, nz), c, o, inv, ic, (mx, my, mz), fill = self._resample_geometry(shape, src_cell, origin, dst_inverse_origin,
+                                                                                dst_inv_cell, dst_shape, fill_cell, cell_bytes)
+        if cells.nbytes != nx * ny * nz * cell_bytes:
+            raise ValueError("cells buffer size does not match shape * cell_bytes")
+        out = np.empty((mx, my, mz, cell_bytes), np.uint8)
+        written = ctypes.c_uint64(0)
+        self._check(self._lib.sdfgpu_resample_cells(self._h, cells.ctypes.data, cell_bytes, nx, ny, nz, c, o, inv, ic, out.ctypes.data,
+                                                    mx, my, mz, fill.ctypes.data, ctypes.byref(written)))
+        return out, int(written.value)
+
+    def resample_cells_device(self, d_src, shape, src_cell, origin, dst_inverse_origin, dst_inv_cell, d_dst, dst_shape, fill_cell,
+                              cell_bytes=8, count=False, stream=0):
+        """Device form of resample_cells (device addresses as ints), enqueued on `stream`.  count: return the number of result
+        cells written (synchronises `stream`); otherwise the call returns None with its work pending."""
+        (nx, ny, nz), c, o, inv, ic, (mx, my, mz), fill = self._resample_geometry(shape, src_cell, origin, dst_inverse_origin,
+                                                                                dst_inv_cell, dst_shape, fill_cell, cell_bytes)
+        written = ctypes.c_uint64(0)
+        self._check(self._lib.sdfgpu_resample_cells_device(self._h, d_src or None, cell_bytes, nx, ny, nz, c, o, inv, ic, d_dst or None,
+                                                           mx, my, mz, fill.ctypes.data, ctypes.byref(written) if count else None,
+                                                           stream or None))
+        return int(written.value) if count else None
+
+    def debug_resample_times(self):
+        """(memset + winner kernel, gather kernel) of the last resample call in ms, after set_option("resample_timing", 1)"""
+        a, b = ctypes.c_double(), ctypes.c_double()
+        self._check(self._lib.sdfgpu_debug_resample_times(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return float(a.value), float(b.value)
 
     def convex_last_info(self):
         """The last extrema computation on this handle: {rounds, cycles, longest_cycle, longest_entry}."""

@@ -11,6 +11,8 @@
 
 #include <cstdint>
 #include <cstring>
+#include <type_traits>
+#include <utility>
 
 #include "arc_utilities/zlib_helpers.hpp"
 #include "sdf_tools/collision_map.hpp"
@@ -94,6 +96,29 @@ void DefSurfaces(Class& cls) {
     cls.attr("UNKNOWN_COMPONENTS") = py::int_(4);
 }
 
+// Resample, and the cell records in bulk (uint8 [nx, ny, nz, sizeof(cell)]) so that whole grids go in and out without per-cell calls
+template <typename Grid, typename Class>
+void DefResample(Class& cls) {
+    using Cell = typename std::remove_cv<typename std::remove_reference<decltype(std::declval<Grid>().GetOOBValue())>::type>::type;
+    cls.def("Resample", [](const Grid& g, double new_resolution) { return g.Resample(new_resolution); }, py::arg("new_resolution"),
+            py::call_guard<py::gil_scoped_release>(),
+            "a grid over the same volume at new_resolution, on the GPU (include/sdfgpu.h \"Resample\"): each cell overwrites the result cell "
+            "that holds its centre, in x -> y -> z order; result cells that hold no source centre keep the OOB value")
+        .def("SetRawCellsNumpy", [](Grid& g, const py::array_t<uint8_t, py::array::c_style>& raw) {
+            auto& cells = g.GetMutableRawData();
+            if ((size_t)raw.size() != cells.size() * sizeof(Cell)) throw std::invalid_argument("records array must hold nx * ny * nz cells");
+            // (through SetValue for the first cell: the grid's stored components and segments no longer describe it)
+            std::memcpy(static_cast<void*>(cells.data()), raw.data(), (size_t)raw.size());
+            if (!cells.empty()) { const Cell first = cells[0]; g.SetValue((int64_t)0, (int64_t)0, (int64_t)0, first); }
+        }, "overwrite every cell record from uint8 [nx, ny, nz, cell bytes]; stored components become invalid")
+        .def("GetRawCellsNumpy", [](const Grid& g) {
+            py::array_t<uint8_t> out({(py::ssize_t)g.GetNumXCells(), (py::ssize_t)g.GetNumYCells(), (py::ssize_t)g.GetNumZCells(), (py::ssize_t)sizeof(Cell)});
+            const auto& cells = g.GetImmutableRawData();
+            std::memcpy(out.mutable_data(), static_cast<const void*>(cells.data()), cells.size() * sizeof(Cell));
+            return out;
+        }, "the cell records as uint8 [nx, ny, nz, cell bytes]");
+}
+
 PYBIND11_MODULE(pysdf_tools, m) {
     m.doc() = "MI355X-native drop-in for sdf_tools' pysdf_tools (SDF build on the GPU via libsdfgpu.so)";
 
@@ -143,6 +168,7 @@ PYBIND11_MODULE(pysdf_tools, m) {
                       [](TaggedObjectCollisionMap& s, const std::string& f) { s.header.frame_id = f; });
     py::class_<TaggedObjectCollisionMapGrid> tagged_grid(m, "TaggedObjectCollisionMapGrid");
     DefSurfaces<TaggedObjectCollisionMapGrid>(tagged_grid);
+    DefResample<TaggedObjectCollisionMapGrid>(tagged_grid);
     tagged_grid
         .def(py::init<Isometry3d const&, std::string, double, int64_t, int64_t, int64_t, TAGGED_OBJECT_COLLISION_CELL const&>())
         .def(py::init<>())
@@ -425,6 +451,7 @@ PYBIND11_MODULE(pysdf_tools, m) {
 
     py::class_<CollisionMapGrid> collision_grid(m, "CollisionMapGrid");
     DefSurfaces<CollisionMapGrid>(collision_grid);
+    DefResample<CollisionMapGrid>(collision_grid);
     collision_grid
         .def(py::init<Isometry3d const&, std::string, double, int64_t, int64_t, int64_t, COLLISION_CELL const&>())
         .def("SetValue", [](CollisionMapGrid& g, int64_t x, int64_t y, int64_t z, const COLLISION_CELL& c) { return g.SetValue(x, y, z, c); })

@@ -18,6 +18,7 @@
 #include "sdfgpu_project.hpp"
 #include "sdfgpu_query.hpp"
 #include "sdfgpu_batch.hpp"
+#include "sdfgpu_resample.hpp"
 
 #include <sys/mman.h>
 #if defined(__SSE2__)
@@ -204,6 +205,15 @@ struct sdfgpu_context {
                                           // pending on its stream when the call returns: one on another stream waits for it first
     bool cx_order_valid = false;          // cx_done_ev has been recorded on cx_stream
     hipStream_t cx_stream = nullptr;
+    DeviceBuffer rs_scratch;              // sdfgpu_resample_cells*: one winner word per result cell, the counter (sdfgpu_resample.hpp)
+    hipEvent_t rs_done_ev = nullptr;      // recorded behind every resample, which may return with its kernels pending on its
+                                          // stream: one on another stream waits for it before it clears the winner words
+    bool rs_order_valid = false;          // rs_done_ev has been recorded on rs_stream
+    hipStream_t rs_stream = nullptr;
+    bool rs_plain_atomics = false;        // option "resample_plain_atomics": one atomic per lane (tools/resample_bench.py)
+    bool rs_timing = false;               // option "resample_timing": events around the two kernels (sdfgpu_debug_resample_times)
+    hipEvent_t rs_time_ev[3] = {nullptr, nullptr, nullptr};
+    bool rs_timed = false;
     bool last_dense = false;
     const uint32_t* guard = nullptr; // set while a build enqueues the flag-guarded general pipeline
     bool plane16_on = true;          // use the int16 plane field + side table when the shape allows
@@ -1860,6 +1870,61 @@ int surfaces_host(sdfgpu_handle h, const uint32_t* labels, const uint8_t* select
                          max_label, out_counts, nullptr, out_indices, capacity, out_total, nullptr, nullptr);
 }
 
+// ---- resample (sdfgpu_resample.hpp) ------------------------------------------------------------------------------------------------
+// Only rs_scratch (and, in the host form, the cell and field staging and the pinned chunks) is used.
+int check_resample_args(sdfgpu_handle h, const void* src, size_t cell_bytes, int64_t nx, int64_t ny, int64_t nz, const double* src_cell,
+                        const double* origin, const double* dst_inverse_origin, const double* dst_inv_cell, const void* dst, int64_t mx,
+                        int64_t my, int64_t mz, const void* fill_cell, ResampleArgs& a) {
+    if (!src || !dst || !src_cell || !origin || !dst_inverse_origin || !dst_inv_cell || !fill_cell)
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "resample: null pointer");
+    if (cell_bytes != 4 && cell_bytes != 8 && cell_bytes != 16)
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "resample: cell_bytes must be 4, 8 or 16 (got %zu)", cell_bytes);
+    if (src == dst) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "resample: the source and the result must be different buffers");
+    const int64_t kMaxCells = INT64_MAX / 16;
+    if (nx <= 0 || ny <= 0 || nz <= 0 || nx > kMaxCells / ny || nx * ny > kMaxCells / nz)
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "resample: unsupported source grid %lld x %lld x %lld", (long long)nx, (long long)ny, (long long)nz);
+    if (mx <= 0 || my <= 0 || mz <= 0 || mx > kMaxCells / my || mx * my > kMaxCells / mz)
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "resample: unsupported result grid %lld x %lld x %lld", (long long)mx, (long long)my, (long long)mz);
+    a = ResampleArgs{};
+    a.nx = nx; a.ny = ny; a.nz = nz; a.mx = mx; a.my = my; a.mz = mz;
+    a.n_src = nx * ny * nz; a.n_dst = mx * my * mz;
+    for (int i = 0; i < 3; ++i) { a.cell[i] = src_cell[i]; a.inv_cell[i] = dst_inv_cell[i]; }
+    for (int i = 0; i < 16; ++i) { a.origin[i] = origin[i]; a.inverse[i] = dst_inverse_origin[i]; }
+    memcpy(a.fill, fill_cell, cell_bytes);
+    a.cell_bytes = (int)cell_bytes;
+    a.winner_bytes = resample_winner_bytes(a.n_src);
+    a.plain_atomics = h->rs_plain_atomics;
+    return SDFGPU_OK;
+}
+
+// a.src -> a.dst (device) on `st`; synchronises `st` only when out_written is asked for
+int resample_impl(sdfgpu_handle h, ResampleArgs& a, uint64_t* out_written, hipStream_t st) {
+    // the winner words belong to the handle and the call may return with its kernels pending: a call on another stream waits for
+    // them on the device first, as the local extrema do (ensure() below may free the scratch: hipFree waits for the device)
+    if (!h->rs_done_ev) HIP_TRY(h, hipEventCreateWithFlags(&h->rs_done_ev, hipEventDisableTiming));
+    if (h->rs_order_valid && st != h->rs_stream) HIP_TRY(h, hipStreamWaitEvent(st, h->rs_done_ev, 0));
+    if (int rc = ensure(h, h->rs_scratch, resample_scratch_bytes(a.n_dst, a.winner_bytes), "resample winners")) return rc;
+    a.winner = h->rs_scratch.ptr;
+    unsigned long long* const counter =
+        reinterpret_cast<unsigned long long*>(static_cast<char*>(h->rs_scratch.ptr) + resample_counter_offset(a.n_dst, a.winner_bytes));
+    a.written = out_written ? counter : nullptr;
+    if (h->rs_timing) {
+        for (hipEvent_t& e : h->rs_time_ev) if (!e) HIP_TRY(h, hipEventCreate(&e));
+        HIP_TRY(h, hipEventRecord(h->rs_time_ev[0], st));
+    }
+    const hipError_t le = resample_launch(a, st, h->rs_timing ? h->rs_time_ev[1] : nullptr);
+    if (h->rs_timing) h->rs_timed = le == hipSuccess && hipEventRecord(h->rs_time_ev[2], st) == hipSuccess;
+    if (hipEventRecord(h->rs_done_ev, st) == hipSuccess) { h->rs_order_valid = true; h->rs_stream = st; }
+    HIP_TRY(h, le);
+    if (out_written) {
+        unsigned long long count = 0;
+        HIP_TRY(h, hipMemcpyAsync(&count, counter, sizeof count, hipMemcpyDeviceToHost, st));
+        HIP_TRY(h, hipStreamSynchronize(st));
+        *out_written = (uint64_t)count;
+    }
+    return SDFGPU_OK;
+}
+
 // ---- local extrema and convex segments (sdfgpu_convex.hpp) ---------------------------------------------------------------------
 // The extrema and segment stages use only cx_scratch and cx_field (and, in the host forms, the staging buffers and the pinned
 // chunks); the SDF scratch, status block and policy are left as they were.  sdfgpu_convex_segments_cells builds its SDF with the
@@ -1996,7 +2061,7 @@ int sdfgpu_destroy(sdfgpu_handle h) {
     for (DeviceBuffer* b : {&h->zfield, &h->yzfield, &h->plane16, &h->bits, &h->unc, &h->tileflag, &h->fix_order, &h->tagmask, &h->tagids, &h->stage_in,
                             &h->stage_bits, &h->stage_out, &h->query_stage, &h->planebits, &h->cc_scratch,
                             &h->tp_scratch, &h->tp_nodes, &h->sf_scratch, &h->sf_sort, &h->sf_indices, &h->cx_scratch, &h->cx_field, &h->batch_field, &h->batch_ext, &h->batch_res,
-                            &h->batch_gscale})
+                            &h->batch_gscale, &h->rs_scratch})
         if (b->ptr) (void)rz_free(h, b->ptr);
     if (h->d_small) (void)rz_free(h, h->d_small);
     if (h->d_slots) (void)rz_free(h, h->d_slots);
@@ -2006,6 +2071,8 @@ int sdfgpu_destroy(sdfgpu_handle h) {
     if (h->far_ev) (void)hipEventDestroy(h->far_ev);
     if (h->build_done_ev) (void)hipEventDestroy(h->build_done_ev);
     if (h->cx_done_ev) (void)hipEventDestroy(h->cx_done_ev);
+    if (h->rs_done_ev) (void)hipEventDestroy(h->rs_done_ev);
+    for (hipEvent_t e : h->rs_time_ev) if (e) (void)hipEventDestroy(e);
     for (int i = 0; i < 2; ++i) { if (h->pin[i]) (void)hipHostFree(h->pin[i]); if (h->pin_ev[i]) (void)hipEventDestroy(h->pin_ev[i]); }
     for (size_t i = 0; i < h->events.size(); ++i)
         if (i % 8 == 0 || h->events[i] != h->events[i - 1]) (void)hipEventDestroy(h->events[i]);
@@ -3025,7 +3092,7 @@ int sdfgpu_set_option(sdfgpu_handle h, const char* name, int value) {
         HIP_TRY(h, hipDeviceSynchronize());
         for (DeviceBuffer* b : {&h->zfield, &h->yzfield, &h->plane16, &h->bits, &h->unc, &h->tileflag, &h->fix_order, &h->tagmask, &h->tagids, &h->stage_in,
                                 &h->stage_bits, &h->stage_out, &h->query_stage, &h->planebits, &h->batch_field, &h->batch_ext, &h->batch_res,
-                                &h->batch_gscale})
+                                &h->batch_gscale, &h->rs_scratch})
             if (b->ptr) { (void)rz_free(h, b->ptr); b->ptr = nullptr; b->bytes = 0; }
         h->tag_cached_bytes = 0;
         h->batch_valid = false;                         // (the batch's extrema words went with batch_ext)
@@ -3043,6 +3110,8 @@ int sdfgpu_set_option(sdfgpu_handle h, const char* name, int value) {
         h->flags_pending = h->far_pending = false;
     }
     else if (n == "dense3_fixed") h->dense3_fixed = value != 0;
+    else if (n == "resample_plain_atomics") h->rs_plain_atomics = value != 0;
+    else if (n == "resample_timing") { h->rs_timing = value != 0; h->rs_timed = false; }
     else if (n == "ball_serpentine") h->ball_serpentine = value != 0;
     else if (n == "shell_min_words") h->shell_min_words = value >= 0 ? value : kShellMinWords;
     else if (n == "shell_budget_den") h->shell_budget_den = value >= 1 ? value : 8;
@@ -3470,6 +3539,58 @@ int sdfgpu_query_gradients(sdfgpu_handle h, const float* d_sdf, int64_t nx, int6
         if (out_value) if (int rc = copy_to_host(h, out_value, base + o_v, n * 8, s)) return rc;
         if (out_status) if (int rc = copy_to_host(h, out_status, base + o_s, n, s)) return rc;
         return SDFGPU_OK;
+    });
+}
+
+int sdfgpu_resample_cells_device(sdfgpu_handle h, const void* d_src, size_t cell_bytes, int64_t nx, int64_t ny, int64_t nz,
+                                 const double src_cell[3], const double origin[16], const double dst_inverse_origin[16],
+                                 const double dst_inv_cell[3], void* d_dst, int64_t mx, int64_t my, int64_t mz, const void* fill_cell,
+                                 uint64_t* out_cells_written, void* stream) {
+    return rz_wrap(h, stream, [&]() -> int {
+        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
+        ResampleArgs a;
+        if (int rc = check_resample_args(h, d_src, cell_bytes, nx, ny, nz, src_cell, origin, dst_inverse_origin, dst_inv_cell, d_dst, mx, my,
+                                         mz, fill_cell, a)) return rc;
+        if ((reinterpret_cast<uintptr_t>(d_src) | reinterpret_cast<uintptr_t>(d_dst)) & 3)
+            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "resample: d_src and d_dst must be 4-byte aligned");
+        HIP_TRY(h, hipSetDevice(h->device));
+        a.src = d_src; a.dst = d_dst;
+        return resample_impl(h, a, out_cells_written, (hipStream_t)stream);
+    });
+}
+
+int sdfgpu_debug_resample_times(sdfgpu_handle h, double* out_winner_ms, double* out_gather_ms) {
+    if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
+    if (!out_winner_ms || !out_gather_ms) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
+    if (!h->rs_timed) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "no resample timed on this handle (option \"resample_timing\")");
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipEventSynchronize(h->rs_time_ev[2]));
+    float a = 0.0f, b = 0.0f;
+    HIP_TRY(h, hipEventElapsedTime(&a, h->rs_time_ev[0], h->rs_time_ev[1]));
+    HIP_TRY(h, hipEventElapsedTime(&b, h->rs_time_ev[1], h->rs_time_ev[2]));
+    *out_winner_ms = (double)a;
+    *out_gather_ms = (double)b;
+    return SDFGPU_OK;
+}
+
+int sdfgpu_resample_cells(sdfgpu_handle h, const void* src, size_t cell_bytes, int64_t nx, int64_t ny, int64_t nz, const double src_cell[3],
+                          const double origin[16], const double dst_inverse_origin[16], const double dst_inv_cell[3], void* dst, int64_t mx,
+                          int64_t my, int64_t mz, const void* fill_cell, uint64_t* out_cells_written) {
+    return rz_wrap(h, nullptr, [&]() -> int {
+        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
+        ResampleArgs a;
+        if (int rc = check_resample_args(h, src, cell_bytes, nx, ny, nz, src_cell, origin, dst_inverse_origin, dst_inv_cell, dst, mx, my, mz,
+                                         fill_cell, a)) return rc;
+        HIP_TRY(h, hipSetDevice(h->device));
+        // the null stream throughout: source records through the cell staging, the result through the field staging
+        const size_t src_bytes = (size_t)a.n_src * cell_bytes, dst_bytes = (size_t)a.n_dst * cell_bytes;
+        h->tag_cached_bytes = 0;                        // (stage_in is about to be overwritten)
+        if (int rc = ensure(h, h->stage_in, src_bytes, "input staging")) return rc;
+        if (int rc = ensure(h, h->stage_out, dst_bytes, "output staging")) return rc;
+        if (int rc = copy_from_host(h, h->stage_in.ptr, src, src_bytes)) return rc;
+        a.src = h->stage_in.ptr; a.dst = h->stage_out.ptr;
+        if (int rc = resample_impl(h, a, out_cells_written, nullptr)) return rc;
+        return copy_to_host(h, dst, h->stage_out.ptr, dst_bytes);
     });
 }
 
