@@ -730,10 +730,11 @@ int sdfgpu_debug_resample_times(sdfgpu_handle h, double* out_winner_ms, double* 
  * may have launched a kernel ends with one check kernel over all of them and a synchronisation: a store outside a buffer
  * fails THAT call with SDFGPU_ERR_REDZONE and a message that names the buffer and the offset.  Debug mode (calls become
  * synchronous; results are unchanged).  sdfgpu_redzone_check runs the same check on demand (wrappers with device buffers from
- * sdfgpu_device_malloc: libsdfgpu_multi); SDFGPU_OK when the mode is off.  Switching the option (on or off) releases the
- * scratch the handle holds, the batch builds' included, so that it comes back with (or without) canaries: results of earlier
- * builds kept on the handle go with it, and sdfgpu_get_extrema / sdfgpu_get_extrema_batch / sdfgpu_last_batch_info answer
- * again after the next build of their kind (until then the batch pair returns INVALID_ARGUMENT). */
+ * sdfgpu_device_malloc: libsdfgpu_multi); SDFGPU_OK when the mode is off.  Switching the option (on or off) releases every
+ * buffer the handle holds (the single and batch builds' scratch, the staging, the scratch of the component, topology, surface,
+ * extrema and resample calls), so that it comes back with (or without) canaries: results of earlier calls kept on the handle
+ * go with it, and sdfgpu_get_extrema / sdfgpu_get_extrema_batch / sdfgpu_last_batch_info / sdfgpu_convex_last_info answer
+ * again after the next call of their kind (until then the batch pair and sdfgpu_convex_last_info return INVALID_ARGUMENT). */
 int sdfgpu_redzone_check(sdfgpu_handle h, void* stream);
 
 /* Debug / test hooks: copy the intermediates of the most recent

@@ -54,11 +54,30 @@ struct DeviceBuffer {
     size_t bytes = 0;
 };
 
-}  // namespace
+// Cross-stream ordering of work that shares state of the handle: an event behind the last such work and the stream it was
+// recorded on.  Work on that stream is ordered by the stream itself; work on any other stream waits for the event first.
+struct StreamOrder {
+    hipEvent_t ev = nullptr;         // created on first use
+    hipStream_t stream = nullptr;    // where ev was last recorded
+    bool recorded = false;
+    hipError_t create() { return ev ? hipSuccess : hipEventCreateWithFlags(&ev, hipEventDisableTiming); }
+    hipError_t wait(hipStream_t s) const { return recorded && s != stream ? hipStreamWaitEvent(s, ev, 0) : hipSuccess; }
+    hipError_t record(hipStream_t s) {
+        hipError_t e = create();
+        if (e == hipSuccess && (e = hipEventRecord(ev, s)) == hipSuccess) { recorded = true; stream = s; }
+        return e;
+    }
+    // `s` becomes the recorded stream WITHOUT a record: for a caller that has just waited on `s` and enqueues a sequence there whose
+    // steps would each wait again, ending in record(s).  Until then another stream's wait sees the event as the previous work left it.
+    hipError_t adopt(hipStream_t s) { const hipError_t e = create(); if (e == hipSuccess) { recorded = true; stream = s; } return e; }
+    hipError_t host_wait() const { return recorded ? hipEventSynchronize(ev) : hipSuccess; }
+    void destroy() { if (ev) (void)hipEventDestroy(ev); ev = nullptr; recorded = false; }
+    struct RecordAtExit { StreamOrder& order; hipStream_t s; ~RecordAtExit() { (void)order.record(s); } };   // record(s) on every path out of a scope
+};
 
-struct sdfgpu_context {
-    int device = 0;
-    std::string error;
+// Every DeviceBuffer of the context, and nothing else: sdfgpu_destroy and the "redzone" switch walk them as an array, so a buffer
+// added here is freed by the one and released by the other.
+struct ContextBuffers {
     DeviceBuffer zfield;     // int16 [N]   K1 output
     DeviceBuffer yzfield;    // int32 [N]   K2 output (32-bit pipeline) / side table (16-bit pipeline)
     DeviceBuffer plane16;    // int16 [N]   plane field of the 16-bit pipeline
@@ -70,10 +89,8 @@ struct sdfgpu_context {
     DeviceBuffer tagids;     // uint32 object id filter
     DeviceBuffer stage_in;   // host-API staging: mask / cells
     DeviceBuffer stage_bits; // host-API staging: the host-classified bit field (1 bit per voxel, linear order)
-    int host_pack = 1;       // host-buffer builds classify on the host and upload bits (option "host_pack"; 0 = upload the
-                             // caller's mask / cells and classify on the device, as rounds 1 - 4 did)
     DeviceBuffer stage_out;  // host-API staging: sdf
-    DeviceBuffer query_stage;   // host-API staging of sdfgpu_query_points: points | distance | gradient | flags
+    DeviceBuffer query_stage;   // host-API staging of the three point calls: points | three result sections (with_staged_points)
     DeviceBuffer cc_scratch;    // sdfgpu_components*: root flags, ranks, chunk counts, K (sdfgpu_components.hpp)
     DeviceBuffer tp_scratch;    // sdfgpu_component_topology*: counters, status, node bytes, node offsets (sdfgpu_topology.hpp)
     DeviceBuffer tp_nodes;      // sdfgpu_component_topology*: one union-find word per surface-vertex node
@@ -82,14 +99,28 @@ struct sdfgpu_context {
     DeviceBuffer sf_indices;    // sdfgpu_component_surfaces / _cells: the indices on their way to the caller's host buffer
     DeviceBuffer cx_scratch;    // sdfgpu_local_extrema* / sdfgpu_convex_segments_cells: doubling state, next, stats, ranks (sdfgpu_convex.hpp)
     DeviceBuffer cx_field;      // sdfgpu_local_extrema: the field; sdfgpu_convex_segments_cells: the named-object SDF, then the extrema
-    size_t cx_stats_off = 0;    // where the last extrema call left its CxStats in cx_scratch (0 = no call yet)
-    int cx_rounds = 0;          // doubling rounds of that call
     // Batches of same-shape grids (sdfgpu_batch.hpp).  Scratch of their own: a batch build leaves the single builds' fields, status
     // block, result block and policy as they were.
     DeviceBuffer batch_field;   // int16 [batch][N] signed in-plane d^2 between k_batch_zy and k_batch_x_finish
     DeviceBuffer batch_ext;     // uint32 [batch][2] per-grid maxima | 24 words: the single builds' result block while a slow-path batch runs
     DeviceBuffer batch_res;     // double [batch] per-grid resolutions
     DeviceBuffer batch_gscale;  // GradScale [batch] of sdfgpu_gradient_batch_device
+    DeviceBuffer planebits;  // row_any [nx * ny] bytes | plane_any [nx] bytes | row_bits [nx][ceil(ny / 32)] words (k_sweep_z_wave16, k_pack_row_flags, EnvDcArgs)
+    DeviceBuffer rs_scratch; // sdfgpu_resample_cells*: one winner word per result cell, the counter (sdfgpu_resample.hpp)
+    DeviceBuffer* begin() { return &zfield; }
+    DeviceBuffer* end() { return begin() + sizeof(ContextBuffers) / sizeof(DeviceBuffer); }
+};
+static_assert(sizeof(ContextBuffers) == 27 * sizeof(DeviceBuffer), "ContextBuffers holds DeviceBuffer members only");
+
+}  // namespace
+
+struct sdfgpu_context : ContextBuffers {
+    int device = 0;
+    std::string error;
+    int host_pack = 1;       // host-buffer builds classify on the host and upload bits (option "host_pack"; 0 = upload the
+                             // caller's mask / cells and classify on the device, as rounds 1 - 4 did)
+    size_t cx_stats_off = 0;    // where the last extrema call left its CxStats in cx_scratch (0 = no call yet)
+    int cx_rounds = 0;          // doubling rounds of that call
     char* batch_pin = nullptr;  // pinned ring through which per-grid parameters reach the device without a host wait
     size_t batch_pin_cap = 0, batch_pin_off = 0;
     std::vector<double> batch_resolutions;   // of the last batch build (sdfgpu_get_extrema_batch)
@@ -153,7 +184,6 @@ struct sdfgpu_context {
     bool flat_score_reset = false;   // "policy_reset": the next build clears the device-side habit of the two-valued tiles (status word 40)
     int flat_tiles = 1;              // (2: every such tile tries, whatever the habit says -- tests)
     // ... and y tiles whose 16 lines are all flat-positive (a floor under open space) skip the search (option "flat_tiles")
-    DeviceBuffer planebits;          // row_any [nx * ny] bytes | plane_any [nx] bytes | row_bits [nx][ceil(ny / 32)] words (k_sweep_z_wave16, k_pack_row_flags, EnvDcArgs)
     bool last_plane_skip = false;    // the last build used it (sdfgpu_debug_copy_yzsweep fills the skipped planes in)
     int64_t last_dims[3] = {0, 0, 0};
     bool dense3_fixed = true;        // KD3's nz = 512 instance (option "dense3_fixed")
@@ -197,19 +227,12 @@ struct sdfgpu_context {
     uint32_t* h_flags = nullptr;     // pinned host copy of the status block, written by the fold kernel of every build
     hipEvent_t flags_ev = nullptr;
     bool flags_pending = false;
-    hipEvent_t build_done_ev = nullptr;   // recorded behind every build (and every stage call that uses the status block):
+    StreamOrder build_order;              // recorded behind every build (and every stage call that uses the status block):
                                           // work on another stream waits for it first
-    bool order_valid = false;             // build_done_ev has been recorded on order_stream
-    hipStream_t order_stream = nullptr;
-    hipEvent_t cx_done_ev = nullptr;      // recorded behind every local-extrema computation, whose last three kernels are still
+    StreamOrder cx_order;                 // recorded behind every local-extrema computation, whose last three kernels are still
                                           // pending on its stream when the call returns: one on another stream waits for it first
-    bool cx_order_valid = false;          // cx_done_ev has been recorded on cx_stream
-    hipStream_t cx_stream = nullptr;
-    DeviceBuffer rs_scratch;              // sdfgpu_resample_cells*: one winner word per result cell, the counter (sdfgpu_resample.hpp)
-    hipEvent_t rs_done_ev = nullptr;      // recorded behind every resample, which may return with its kernels pending on its
+    StreamOrder rs_order;                 // recorded behind every resample, which may return with its kernels pending on its
                                           // stream: one on another stream waits for it before it clears the winner words
-    bool rs_order_valid = false;          // rs_done_ev has been recorded on rs_stream
-    hipStream_t rs_stream = nullptr;
     bool rs_plain_atomics = false;        // option "resample_plain_atomics": one atomic per lane (tools/resample_bench.py)
     bool rs_timing = false;               // option "resample_timing": events around the two kernels (sdfgpu_debug_resample_times)
     hipEvent_t rs_time_ev[3] = {nullptr, nullptr, nullptr};
@@ -1125,7 +1148,7 @@ int build_device_impl(sdfgpu_handle h, const uint8_t* d_filled, const void* d_ce
     // build's fold kernel; cleared here after a build that failed half-way (or before the first one)
     // Builds on one handle share its status block, extrema slots and scratch fields.  On the same stream they are
     // ordered by the stream; a build issued on ANOTHER stream first waits for the previous build's last kernel.
-    if (h->order_valid && s != h->order_stream) HIP_TRY(h, hipStreamWaitEvent(s, h->build_done_ev, 0));
+    HIP_TRY(h, h->build_order.wait(s));
     if (!h->small_clean) {
         HIP_TRY(h, hipMemsetAsync(h->d_small, 0, 128, s));
         HIP_TRY(h, hipMemsetAsync(h->d_slots, 0, (size_t)kSlots * kSlotWords * 4, s));   // a failed build may have left maxima behind
@@ -1403,8 +1426,7 @@ int build_device_impl(sdfgpu_handle h, const uint8_t* d_filled, const void* d_ce
         HIP_TRY(h, mark(7));
         for (auto e : ev) h->events.push_back(e);
     }
-    HIP_TRY(h, hipEventRecord(h->build_done_ev, s));
-    h->order_valid = true; h->order_stream = s;
+    HIP_TRY(h, h->build_order.record(s));
     h->last_stream = s;
     h->last_resolution = resolution;
     h->last_n = n;
@@ -1901,8 +1923,8 @@ int check_resample_args(sdfgpu_handle h, const void* src, size_t cell_bytes, int
 int resample_impl(sdfgpu_handle h, ResampleArgs& a, uint64_t* out_written, hipStream_t st) {
     // the winner words belong to the handle and the call may return with its kernels pending: a call on another stream waits for
     // them on the device first, as the local extrema do (ensure() below may free the scratch: hipFree waits for the device)
-    if (!h->rs_done_ev) HIP_TRY(h, hipEventCreateWithFlags(&h->rs_done_ev, hipEventDisableTiming));
-    if (h->rs_order_valid && st != h->rs_stream) HIP_TRY(h, hipStreamWaitEvent(st, h->rs_done_ev, 0));
+    HIP_TRY(h, h->rs_order.create());
+    HIP_TRY(h, h->rs_order.wait(st));
     if (int rc = ensure(h, h->rs_scratch, resample_scratch_bytes(a.n_dst, a.winner_bytes), "resample winners")) return rc;
     a.winner = h->rs_scratch.ptr;
     unsigned long long* const counter =
@@ -1914,7 +1936,7 @@ int resample_impl(sdfgpu_handle h, ResampleArgs& a, uint64_t* out_written, hipSt
     }
     const hipError_t le = resample_launch(a, st, h->rs_timing ? h->rs_time_ev[1] : nullptr);
     if (h->rs_timing) h->rs_timed = le == hipSuccess && hipEventRecord(h->rs_time_ev[2], st) == hipSuccess;
-    if (hipEventRecord(h->rs_done_ev, st) == hipSuccess) { h->rs_order_valid = true; h->rs_stream = st; }
+    (void)h->rs_order.record(st);                       // (also behind a failed launch: what it did enqueue is ordered)
     HIP_TRY(h, le);
     if (out_written) {
         unsigned long long count = 0;
@@ -1951,17 +1973,17 @@ int extrema_impl(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t ny, in
                  uint32_t* d_ext, hipStream_t st) {
     const CxPlan plan = cx_plan(nx, ny, nz);
     // cx_extrema returns with its basin / entry / final kernels still pending on `st`, and they read and write cx_scratch: a
-    // computation on another stream is ordered behind them, as the builds are ordered by build_done_ev.  (ensure() below may
+    // computation on another stream is ordered behind them, as the builds are ordered by build_order.  (ensure() below may
     // free the scratch: hipFree waits for the device.)
-    if (!h->cx_done_ev) HIP_TRY(h, hipEventCreateWithFlags(&h->cx_done_ev, hipEventDisableTiming));
-    if (h->cx_order_valid && st != h->cx_stream) HIP_TRY(h, hipStreamWaitEvent(st, h->cx_done_ev, 0));
+    HIP_TRY(h, h->cx_order.create());
+    HIP_TRY(h, h->cx_order.wait(st));
     if (int rc = ensure(h, h->cx_scratch, plan.scratch_bytes, "convex scratch")) return rc;
     CxRot rot;
     for (int i = 0; i < 4; ++i) { rot.q[i] = q_and_qinv[i]; rot.qi[i] = q_and_qinv[4 + i]; }
     int rounds = 0;
     h->cx_stats_off = 0;
     const hipError_t ce = cx_extrema(plan, d_sdf, resolution, rot, d_ext, h->cx_scratch.ptr, st, &rounds);
-    if (hipEventRecord(h->cx_done_ev, st) == hipSuccess) { h->cx_order_valid = true; h->cx_stream = st; }
+    (void)h->cx_order.record(st);                       // (also behind a failed launch: what it did enqueue is ordered)
     HIP_TRY(h, ce);
     h->cx_stats_off = plan.off_stats;
     h->cx_rounds = rounds;
@@ -1991,6 +2013,30 @@ int convex_sdf(sdfgpu_handle h, size_t stride, size_t occ_off, size_t obj_off, i
                                    nullptr))
         return rc;
     HIP_TRY(h, cx_combine((float*)h->stage_out.ptr, (const float*)h->cx_field.ptr, (uint64_t)n, nullptr));
+    return SDFGPU_OK;
+}
+
+// Host staging of the three point calls (sdfgpu_query_points, sdfgpu_project_points, sdfgpu_query_gradients) in query_stage, which
+// grows on demand and is re-used by the next call: points (24 bytes each) | three result sections of per_point[i] bytes per point,
+// the last one padded to 256 bytes.  Uploads the points, runs launch(device points, device sections: null where the caller passed
+// no out[i]) and downloads the sections that were asked for, in their order.
+template <class Launch>
+int with_staged_points(sdfgpu_handle h, const double* points, int64_t n_points, const size_t (&per_point)[3], void* const (&out)[3], Launch launch) {
+    const size_t n = (size_t)n_points;
+    size_t off[4] = {n * 24, 0, 0, 0};
+    for (int i = 0; i < 3; ++i) off[i + 1] = off[i] + n * per_point[i];
+    if (int rc = ensure(h, h->query_stage, off[2] + ((n * per_point[2] + 255) & ~(size_t)255), "query staging")) return rc;
+    char* const base = (char*)h->query_stage.ptr;
+    char* const dev[3] = {out[0] ? base + off[0] : nullptr, out[1] ? base + off[1] : nullptr, out[2] ? base + off[2] : nullptr};
+    // Round 5: the null stream of the context's device, ordered behind this handle's last build by its event --
+    // not h->last_stream, which is a handle of the CALLER's (an earlier *_device build's stream may have been destroyed since).
+    // A field produced ELSEWHERE (another handle, a caller's kernel) is ordered by the null stream's implicit synchronisation only
+    // when its stream is a blocking one: producers on hipStreamNonBlocking streams (PyTorch's are) must be synchronised by the caller
+    // before this call -- include/sdfgpu.h says so.
+    HIP_TRY(h, h->build_order.wait(nullptr));
+    if (int rc = copy_from_host(h, base, points, n * 24, nullptr)) return rc;
+    if (int rc = launch((const double*)base, dev)) return rc;
+    for (int i = 0; i < 3; ++i) if (out[i]) if (int rc = copy_to_host(h, out[i], dev[i], n * per_point[i], nullptr)) return rc;
     return SDFGPU_OK;
 }
 
@@ -2028,11 +2074,9 @@ int sdfgpu_create(int device, sdfgpu_handle* out_handle) {
     if (ce == hipSuccess) ce = hipMemset(ctx->d_slots, 0, (size_t)kSlots * kSlotWords * 4);
     if (ce == hipSuccess) ce = rz_malloc(ctx, "status block", 512, (void**)&ctx->d_small) == SDFGPU_OK ? hipSuccess : hipErrorOutOfMemory;
     if (ce == hipSuccess) ce = hipMemset(ctx->d_small, 0, 512);
-    if (ce == hipSuccess) ce = hipEventCreateWithFlags(&ctx->build_done_ev, hipEventDisableTiming);
     if (ce != hipSuccess) {
         if (ctx->d_slots) (void)rz_free(ctx, ctx->d_slots);
         if (ctx->d_small) (void)rz_free(ctx, ctx->d_small);
-        if (ctx->build_done_ev) (void)hipEventDestroy(ctx->build_done_ev);
         delete ctx;
         return fail(nullptr, SDFGPU_ERR_HIP, "HIP error %d (%s) while allocating the context's status blocks",
                     (int)ce, hipGetErrorString(ce));
@@ -2058,20 +2102,14 @@ int sdfgpu_create(int device, sdfgpu_handle* out_handle) {
 int sdfgpu_destroy(sdfgpu_handle h) {
     if (!h) return SDFGPU_OK;
     (void)hipSetDevice(h->device);
-    for (DeviceBuffer* b : {&h->zfield, &h->yzfield, &h->plane16, &h->bits, &h->unc, &h->tileflag, &h->fix_order, &h->tagmask, &h->tagids, &h->stage_in,
-                            &h->stage_bits, &h->stage_out, &h->query_stage, &h->planebits, &h->cc_scratch,
-                            &h->tp_scratch, &h->tp_nodes, &h->sf_scratch, &h->sf_sort, &h->sf_indices, &h->cx_scratch, &h->cx_field, &h->batch_field, &h->batch_ext, &h->batch_res,
-                            &h->batch_gscale, &h->rs_scratch})
-        if (b->ptr) (void)rz_free(h, b->ptr);
+    for (DeviceBuffer& b : *h) if (b.ptr) (void)rz_free(h, b.ptr);
     if (h->d_small) (void)rz_free(h, h->d_small);
     if (h->d_slots) (void)rz_free(h, h->d_slots);
     if (h->rz_table) (void)hipFree(h->rz_table);
     if (h->batch_pin) (void)hipHostFree(h->batch_pin);
     if (h->h_flags) { (void)hipHostFree(h->h_flags); (void)hipEventDestroy(h->flags_ev); }
     if (h->far_ev) (void)hipEventDestroy(h->far_ev);
-    if (h->build_done_ev) (void)hipEventDestroy(h->build_done_ev);
-    if (h->cx_done_ev) (void)hipEventDestroy(h->cx_done_ev);
-    if (h->rs_done_ev) (void)hipEventDestroy(h->rs_done_ev);
+    for (StreamOrder* o : {&h->build_order, &h->cx_order, &h->rs_order}) o->destroy();
     for (hipEvent_t e : h->rs_time_ev) if (e) (void)hipEventDestroy(e);
     for (int i = 0; i < 2; ++i) { if (h->pin[i]) (void)hipHostFree(h->pin[i]); if (h->pin_ev[i]) (void)hipEventDestroy(h->pin_ev[i]); }
     for (size_t i = 0; i < h->events.size(); ++i)
@@ -2219,7 +2257,7 @@ int sdfgpu_get_extrema(sdfgpu_handle h, double* out_max, double* out_min) {
     HIP_TRY(h, hipSetDevice(h->device));
     uint32_t v[4];
     // (the build's own event, not its stream: the stream is the caller's and may be gone by now -- ADVICE r4)
-    if (h->order_valid) HIP_TRY(h, hipEventSynchronize(h->build_done_ev));
+    HIP_TRY(h, h->build_order.host_wait());
     HIP_TRY(h, hipMemcpy(v, h->d_result, sizeof v, hipMemcpyDeviceToHost));
     return sdfgpu_extrema_from_dsq(v[0], v[1], h->last_resolution, out_max, out_min);
 }
@@ -2237,8 +2275,8 @@ int sdfgpu_sweep_zy_tiered_device(sdfgpu_handle h, const uint8_t* d_filled, int6
         hipStream_t s = (hipStream_t)stream;
         // (this call uses the handle's status block and scratch fields like a whole build does: it takes part in the same
         //  cross-stream ordering -- waits for the handle's previous work when that ran on another stream, and is waited for)
-        if (h->order_valid && s != h->order_stream) HIP_TRY(h, hipStreamWaitEvent(s, h->build_done_ev, 0));
-        struct OrderEnd { sdfgpu_handle h; hipStream_t s; ~OrderEnd() { if (hipEventRecord(h->build_done_ev, s) == hipSuccess) { h->order_valid = true; h->order_stream = s; } } } order_end{h, s};
+        HIP_TRY(h, h->build_order.wait(s));
+        StreamOrder::RecordAtExit order_end{h->build_order, s};
         const bool tiered = h->envelope_on && far_geometry_ok(h, 2, nxs, ny, nz) &&
                             (nz % 4) == 0 && (reinterpret_cast<uintptr_t>(d_plane_dsq) % 16) == 0;
         if (!tiered) {
@@ -2296,8 +2334,8 @@ int sdfgpu_sweep_x_lines_device(sdfgpu_handle h, const int32_t* d_plane_dsq, int
         hipStream_t s = (hipStream_t)stream;
         h->guard = nullptr;
         h->far_y = nullptr;
-        if (h->order_valid && s != h->order_stream) HIP_TRY(h, hipStreamWaitEvent(s, h->build_done_ev, 0));
-        struct OrderEnd { sdfgpu_handle h; hipStream_t s; ~OrderEnd() { if (hipEventRecord(h->build_done_ev, s) == hipSuccess) { h->order_valid = true; h->order_stream = s; } } } order_end{h, s};
+        HIP_TRY(h, h->build_order.wait(s));
+        StreamOrder::RecordAtExit order_end{h->build_order, s};
         const bool tiered = h->envelope_on && far_geometry_ok(h, 3, nx, nys, nz, ny_global) &&
                             (reinterpret_cast<uintptr_t>(d_plane_dsq) % 16) == 0;
         h->last_dc_x = 0;
@@ -2514,7 +2552,7 @@ namespace {
 int batch_stage_params(sdfgpu_handle h, void* d_dst, const void* src, size_t bytes, hipStream_t s) {
     const size_t want = (bytes + 63) & ~(size_t)63;
     if (want > h->batch_pin_cap) {
-        if (h->order_valid) HIP_TRY(h, hipEventSynchronize(h->build_done_ev));
+        HIP_TRY(h, h->build_order.host_wait());
         if (h->batch_pin) HIP_TRY(h, hipHostFree(h->batch_pin));
         h->batch_pin = nullptr; h->batch_pin_cap = 0; h->batch_pin_off = 0;
         const size_t cap = std::max<size_t>(want * 4, (size_t)64 << 10);
@@ -2522,7 +2560,7 @@ int batch_stage_params(sdfgpu_handle h, void* d_dst, const void* src, size_t byt
         h->batch_pin_cap = cap;
     }
     if (h->batch_pin_off + want > h->batch_pin_cap) {
-        if (h->order_valid) HIP_TRY(h, hipEventSynchronize(h->build_done_ev));
+        HIP_TRY(h, h->build_order.host_wait());
         h->batch_pin_off = 0;
     }
     char* p = h->batch_pin + h->batch_pin_off;
@@ -2564,7 +2602,7 @@ int build_batch_impl(sdfgpu_handle h, const uint8_t* d_filled, const BatchTagged
     else h->batch_resolutions.assign((size_t)batch, resolution);
     uint32_t* ext = (uint32_t*)h->batch_ext.ptr;
     if (fast) {
-        if (h->order_valid && s != h->order_stream) HIP_TRY(h, hipStreamWaitEvent(s, h->build_done_ev, 0));
+        HIP_TRY(h, h->build_order.wait(s));
         if (resolutions) if (int rc = batch_stage_params(h, h->batch_res.ptr, resolutions, (size_t)batch * 8, s)) return rc;
         BatchArgs a{};
         a.mask = tg ? nullptr : d_filled;
@@ -2581,9 +2619,9 @@ int build_batch_impl(sdfgpu_handle h, const uint8_t* d_filled, const BatchTagged
         const double keep_res = h->last_resolution;
         const int64_t keep_n = h->last_n;
         uint32_t* keep = ext + 2 * batch;
-        if (h->order_valid && s != h->order_stream) HIP_TRY(h, hipStreamWaitEvent(s, h->build_done_ev, 0));
+        HIP_TRY(h, h->build_order.wait(s));
         HIP_TRY(h, hipMemcpyAsync(keep, h->d_result, kStatusWords * 4, hipMemcpyDeviceToDevice, s));
-        h->order_valid = true; h->order_stream = s;
+        HIP_TRY(h, h->build_order.adopt(s));            // (the single builds below are on `s` too: none of them waits again)
         for (int64_t b = 0; b < batch; ++b) {
             const uint8_t* m = d_filled ? d_filled + b * n : (const uint8_t*)h->tagmask.ptr;
             if (tg) {      // (object_mode 2 with the single id ids[b]: a one-element list is sorted)
@@ -2599,8 +2637,7 @@ int build_batch_impl(sdfgpu_handle h, const uint8_t* d_filled, const BatchTagged
         h->have_result = had; h->last_resolution = keep_res; h->last_n = keep_n;
         h->batch_launches = -1;
     }
-    HIP_TRY(h, hipEventRecord(h->build_done_ev, s));
-    h->order_valid = true; h->order_stream = s;
+    HIP_TRY(h, h->build_order.record(s));
     h->batch_fast = fast ? 1 : 0;
     h->batch_valid = true;
     return SDFGPU_OK;
@@ -2611,7 +2648,7 @@ int get_extrema_batch(sdfgpu_handle h, int64_t batch, double* out_max, double* o
     if (batch != (int64_t)h->batch_resolutions.size())
         return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "the last batch build held %lld grids, not %lld", (long long)h->batch_resolutions.size(), (long long)batch);
     HIP_TRY(h, hipSetDevice(h->device));
-    if (h->order_valid) HIP_TRY(h, hipEventSynchronize(h->build_done_ev));
+    HIP_TRY(h, h->build_order.host_wait());
     std::vector<uint32_t> v((size_t)batch * 2);
     HIP_TRY(h, hipMemcpy(v.data(), h->batch_ext.ptr, v.size() * 4, hipMemcpyDeviceToHost));
     for (int64_t b = 0; b < batch; ++b)
@@ -2716,7 +2753,7 @@ int sdfgpu_gradient_batch_device(sdfgpu_handle h, const float* d_sdf, int64_t ba
             std::vector<GradScale> sc((size_t)batch);
             for (int64_t b = 0; b < batch; ++b) sc[(size_t)b] = scale_of(resolutions[b]);
             if (int rc = ensure(h, h->batch_gscale, sc.size() * sizeof(GradScale), "batch gradient scales")) return rc;
-            if (h->order_valid && s != h->order_stream) HIP_TRY(h, hipStreamWaitEvent(s, h->build_done_ev, 0));
+            HIP_TRY(h, h->build_order.wait(s));
             if (int rc = batch_stage_params(h, h->batch_gscale.ptr, sc.data(), sc.size() * sizeof(GradScale), s)) return rc;
             a.scales = h->batch_gscale.ptr;
         } else {
@@ -2725,8 +2762,7 @@ int sdfgpu_gradient_batch_device(sdfgpu_handle h, const float* d_sdf, int64_t ba
         }
         HIP_TRY(h, batch_gradient_launch(a, s));
         if (resolutions) {
-            HIP_TRY(h, hipEventRecord(h->build_done_ev, s));
-            h->order_valid = true; h->order_stream = s;
+            HIP_TRY(h, h->build_order.record(s));
         }
         return SDFGPU_OK;
     });
@@ -2927,28 +2963,11 @@ int sdfgpu_query_points(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t
         if (int rc = check_dims(h, nx, ny, nz)) return rc;
         if (n_points == 0 || (!out_distance && !out_gradient && !out_flags)) return SDFGPU_OK;
         HIP_TRY(h, hipSetDevice(h->device));
-        // staging in the context (grown on demand, re-used by the next call): points | distance | gradient | flags
-        const size_t n = (size_t)n_points;
-        const size_t o_d = n * 24, o_g = o_d + n * 8, o_f = o_g + n * 24, total = o_f + ((n + 255) & ~(size_t)255);
-        if (int rc = ensure(h, h->query_stage, total, "query staging")) return rc;
-        char* base = (char*)h->query_stage.ptr;
-        // Round 5: the null stream of the context's device, ordered behind this handle's last build by its event --
-        // not h->last_stream, which is a handle of the CALLER's (an earlier *_device build's stream may have been destroyed since).
-        // A field produced ELSEWHERE (another handle, a caller's kernel) is ordered by the null stream's implicit synchronisation only
-        // when its stream is a blocking one: producers on hipStreamNonBlocking streams (PyTorch's are) must be synchronised by the caller
-        // before this call -- include/sdfgpu.h says so.
-        hipStream_t s = nullptr;
-        if (h->order_valid && h->order_stream != nullptr) HIP_TRY(h, hipStreamWaitEvent(s, h->build_done_ev, 0));
-        if (int rc = copy_from_host(h, base, points, n * 24, s)) return rc;
-        if (int rc = sdfgpu_query_points_device(h, d_sdf, nx, ny, nz, resolution, world_to_grid, grid_to_world_rotation, oob_value,
-                                                (const double*)base, n_points, enable_edge_gradients,
-                                                out_distance ? (double*)(base + o_d) : nullptr,
-                                                out_gradient ? (double*)(base + o_g) : nullptr,
-                                                out_flags ? (uint8_t*)(base + o_f) : nullptr, s)) return rc;
-        if (out_distance) if (int rc = copy_to_host(h, out_distance, base + o_d, n * 8, s)) return rc;
-        if (out_gradient) if (int rc = copy_to_host(h, out_gradient, base + o_g, n * 24, s)) return rc;
-        if (out_flags) if (int rc = copy_to_host(h, out_flags, base + o_f, n, s)) return rc;
-        return SDFGPU_OK;
+        // points | distance | gradient | flags
+        return with_staged_points(h, points, n_points, {8, 24, 1}, {out_distance, out_gradient, out_flags}, [&](const double* d_points, char* const (&d)[3]) {
+            return sdfgpu_query_points_device(h, d_sdf, nx, ny, nz, resolution, world_to_grid, grid_to_world_rotation, oob_value, d_points, n_points,
+                                              enable_edge_gradients, (double*)d[0], (double*)d[1], (uint8_t*)d[2], nullptr);
+        });
     });
 }
 
@@ -2980,7 +2999,7 @@ int sdfgpu_debug_copy_zsweep(sdfgpu_handle h, int16_t* out_host, int64_t n) {
     if (h->last_fused) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "the last build fused the z sweep into the y sweep: no z field exists");
     if (h->last_standby) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "the last build's stand-by pair takes its z distances from the bit field: no z field exists");
     HIP_TRY(h, hipSetDevice(h->device));
-    if (h->order_valid) HIP_TRY(h, hipEventSynchronize(h->build_done_ev));
+    HIP_TRY(h, h->build_order.host_wait());
     HIP_TRY(h, hipMemcpy(out_host, h->zfield.ptr, (size_t)n * 2, hipMemcpyDeviceToHost));
     if (h->last_plane_skip && h->planebits.ptr && n == h->last_dims[0] * h->last_dims[1] * h->last_dims[2]) {
         // the z sweep of a build that went straight to the far-field pair does not write rows without a filled voxel
@@ -2997,7 +3016,7 @@ int sdfgpu_debug_copy_yzsweep(sdfgpu_handle h, int32_t* out_host, int64_t n) {
     if (!h || !out_host) return SDFGPU_ERR_INVALID_ARGUMENT;
     if (!h->have_result || n > h->last_n) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "no matching build");
     HIP_TRY(h, hipSetDevice(h->device));
-    if (h->order_valid) HIP_TRY(h, hipEventSynchronize(h->build_done_ev));
+    HIP_TRY(h, h->build_order.host_wait());
     HIP_TRY(h, hipMemcpy(out_host, h->yzfield.ptr, (size_t)n * 4, hipMemcpyDeviceToHost));
     if (h->last_plane_skip && h->planebits.ptr && n == h->last_dims[0] * h->last_dims[1] * h->last_dims[2]) {
         // the y sweep skipped the x-planes without a filled voxel: every voxel of such a plane is "free, no filled voxel in the plane"
@@ -3090,12 +3109,11 @@ int sdfgpu_set_option(sdfgpu_handle h, const char* name, int value) {
         // the status block and the slots are replaced at once
         HIP_TRY(h, hipSetDevice(h->device));
         HIP_TRY(h, hipDeviceSynchronize());
-        for (DeviceBuffer* b : {&h->zfield, &h->yzfield, &h->plane16, &h->bits, &h->unc, &h->tileflag, &h->fix_order, &h->tagmask, &h->tagids, &h->stage_in,
-                                &h->stage_bits, &h->stage_out, &h->query_stage, &h->planebits, &h->batch_field, &h->batch_ext, &h->batch_res,
-                                &h->batch_gscale, &h->rs_scratch})
-            if (b->ptr) { (void)rz_free(h, b->ptr); b->ptr = nullptr; b->bytes = 0; }
+        for (DeviceBuffer& b : *h) if (b.ptr) { (void)rz_free(h, b.ptr); b.ptr = nullptr; b.bytes = 0; }
+        // what the handle remembers of their contents goes with them (components, topology, surfaces, cx_field: nothing outlives a call)
         h->tag_cached_bytes = 0;
         h->batch_valid = false;                         // (the batch's extrema words went with batch_ext)
+        h->cx_stats_off = 0;                            // (sdfgpu_convex_last_info reads its statistics out of cx_scratch)
         (void)rz_free(h, h->d_small);
         (void)rz_free(h, h->d_slots);
         h->d_small = h->d_slots = nullptr;
@@ -3146,7 +3164,7 @@ int sdfgpu_last_dense_certified(sdfgpu_handle h, int* out_certified) {
     HIP_TRY(h, hipSetDevice(h->device));
     uint32_t v[8];
     // (the build's own event, not its stream: the stream is the caller's and may be gone by now -- ADVICE r4)
-    if (h->order_valid) HIP_TRY(h, hipEventSynchronize(h->build_done_ev));
+    HIP_TRY(h, h->build_order.host_wait());
     HIP_TRY(h, hipMemcpy(v, h->d_result, sizeof v, hipMemcpyDeviceToHost));
     // bit 0: dense kernel decided everything; bit 1 / 2: the y / x sweep was redone by the envelope kernel
     uint32_t why = 0;
@@ -3158,7 +3176,7 @@ int sdfgpu_last_dense_certified(sdfgpu_handle h, int* out_certified) {
 int sdfgpu_debug_flat_habit(sdfgpu_handle h, int* out_score, int* out_gate) {
     if (!h || !out_score || !out_gate) return SDFGPU_ERR_INVALID_ARGUMENT;
     HIP_TRY(h, hipSetDevice(h->device));
-    if (h->order_valid) HIP_TRY(h, hipEventSynchronize(h->build_done_ev));
+    HIP_TRY(h, h->build_order.host_wait());
     int v[2] = {0, 0};
     HIP_TRY(h, hipMemcpy(v, h->d_small + 40, sizeof v, hipMemcpyDeviceToHost));
     *out_score = v[0];
@@ -3453,24 +3471,13 @@ int sdfgpu_project_points(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64
                                         mode, points, n_points, out_points, a)) return rc;
         if (n_points == 0) return SDFGPU_OK;
         HIP_TRY(h, hipSetDevice(h->device));
-        // staging in the context (shared with sdfgpu_query_points): points | out points | steps | status
-        const size_t n = (size_t)n_points;
-        const size_t o_o = n * 24, o_s = o_o + n * 24, o_t = o_s + n * 4, total = o_t + ((n + 255) & ~(size_t)255);
-        if (int rc = ensure(h, h->query_stage, total, "query staging")) return rc;
-        char* base = (char*)h->query_stage.ptr;
-        // the ordering of sdfgpu_query_points: the null stream, behind this handle's last build
-        hipStream_t s = nullptr;
-        if (h->order_valid && h->order_stream != nullptr) HIP_TRY(h, hipStreamWaitEvent(s, h->build_done_ev, 0));
-        if (int rc = copy_from_host(h, base, points, n * 24, s)) return rc;
-        a.points = (const double*)base; a.out = (double*)(base + o_o);
-        a.steps = out_steps ? (int32_t*)(base + o_s) : nullptr;
-        a.status = out_status ? (uint8_t*)(base + o_t) : nullptr;
-        project_prepare(a, resolution, minimum_distance, stepsize_multiplier);
-        HIP_TRY(h, project_launch(a, s));
-        if (int rc = copy_to_host(h, out_points, base + o_o, n * 24, s)) return rc;
-        if (out_steps) if (int rc = copy_to_host(h, out_steps, base + o_s, n * 4, s)) return rc;
-        if (out_status) if (int rc = copy_to_host(h, out_status, base + o_t, n, s)) return rc;
-        return SDFGPU_OK;
+        // points | out points | steps | status
+        return with_staged_points(h, points, n_points, {24, 4, 1}, {out_points, out_steps, out_status}, [&](const double* d_points, char* const (&d)[3]) -> int {
+            a.points = d_points; a.out = (double*)d[0]; a.steps = (int32_t*)d[1]; a.status = (uint8_t*)d[2];
+            project_prepare(a, resolution, minimum_distance, stepsize_multiplier);
+            HIP_TRY(h, project_launch(a, nullptr));
+            return SDFGPU_OK;
+        });
     });
 }
 
@@ -3520,25 +3527,13 @@ int sdfgpu_query_gradients(sdfgpu_handle h, const float* d_sdf, int64_t nx, int6
         if (int rc = check_query_gradients_args(h, d_sdf, nx, ny, nz, resolution, world_to_grid, kind, window, points, n_points, a)) return rc;
         if (n_points == 0 || (!out_value && !out_gradient && !out_status)) return SDFGPU_OK;
         HIP_TRY(h, hipSetDevice(h->device));
-        // staging in the context (shared with sdfgpu_query_points): points | gradient | value | status
-        const size_t n = (size_t)n_points;
-        const size_t o_g = n * 24, o_v = o_g + n * 24, o_s = o_v + n * 8, total = o_s + ((n + 255) & ~(size_t)255);
-        if (int rc = ensure(h, h->query_stage, total, "query staging")) return rc;
-        char* base = (char*)h->query_stage.ptr;
-        // the ordering of sdfgpu_query_points: the null stream, behind this handle's last build
-        hipStream_t s = nullptr;
-        if (h->order_valid && h->order_stream != nullptr) HIP_TRY(h, hipStreamWaitEvent(s, h->build_done_ev, 0));
-        if (int rc = copy_from_host(h, base, points, n * 24, s)) return rc;
-        a.points = (const double*)base;
-        a.gradient = out_gradient ? (double*)(base + o_g) : nullptr;
-        a.value = out_value ? (double*)(base + o_v) : nullptr;
-        a.status = out_status ? (uint8_t*)(base + o_s) : nullptr;
-        query_gradients_prepare(a, resolution, window, oob_value);
-        HIP_TRY(h, query_gradients_launch(a, s));
-        if (out_gradient) if (int rc = copy_to_host(h, out_gradient, base + o_g, n * 24, s)) return rc;
-        if (out_value) if (int rc = copy_to_host(h, out_value, base + o_v, n * 8, s)) return rc;
-        if (out_status) if (int rc = copy_to_host(h, out_status, base + o_s, n, s)) return rc;
-        return SDFGPU_OK;
+        // points | gradient | value | status
+        return with_staged_points(h, points, n_points, {24, 8, 1}, {out_gradient, out_value, out_status}, [&](const double* d_points, char* const (&d)[3]) -> int {
+            a.points = d_points; a.gradient = (double*)d[0]; a.value = (double*)d[1]; a.status = (uint8_t*)d[2];
+            query_gradients_prepare(a, resolution, window, oob_value);
+            HIP_TRY(h, query_gradients_launch(a, nullptr));
+            return SDFGPU_OK;
+        });
     });
 }
 

@@ -89,6 +89,87 @@ def test_every_tier_and_entry_point_is_clean_under_red_zones(rz, shape):
     assert np.array_equal(got, ex) and ext == ex_ext
 
 
+def _analysis_scratch_bytes(shape, max_label):
+    """What components_bits_device, component_topology_device (no selection), component_surfaces_device and local_extrema_device
+    plan for a grid, by the formulas of cc_plan, tp_plan, sf_plan and cx_plan (the scratch_bytes each hands to the handle).  The
+    topology's node words and the surfaces' sort scratch depend on the scene and come on top."""
+    nx, ny, nz = shape
+    n, labels = nx * ny * nz, max_label + 1
+    align8 = lambda v: (v + 7) & ~7
+    # cc_plan: root bits | word ranks (256 words per chunk of 8192 voxels each) | chunk counts | chunk offsets | K and 3 spare words
+    chunks = -(-n // 8192)
+    cc = (2 * chunks * 256 + 2 * chunks + 4) * 4
+    # tp_plan: counters u64 [labels][5] | status (24 bytes) | node bytes, one per vertex in chunks of 8192 | a u32 per 8 vertices
+    # | chunk counts | chunk offsets
+    chunks = -(-(nx + 1) * (ny + 1) * (nz + 1) // 8192)
+    tp = align8(align8(labels * 5 * 8) + 24) + chunks * 8192 + chunks * 1024 * 4 + 2 * chunks * 4
+    # sf_plan: counts u32 [labels] | status (16 bytes) | one surface bit per voxel in tiles of 4096
+    sf = align8(align8(labels * 4) + 16) + -(-n // 4096) * 512
+    # cx_plan: A u64 [n] | B u64 [n] | next u32 [n] | CxStats (40 rounds x 64 slots + 64 slots + 3 single slots, 32 words per slot)
+    # | root bits | word ranks (256 words per chunk of 8192 each) | chunk counts | chunk offsets
+    chunks = -(-n // 8192)
+    cx = align8(20 * n) + align8((40 * 64 * 32 + 64 * 32 + 3 * 32) * 4) + 2 * chunks * 256 * 4 + 2 * chunks * 4
+    return cc + tp + sf + cx
+
+
+@pytest.fixture
+def fresh():
+    """A handle of its own, red zones off, that holds no scratch yet."""
+    ctx = capi.SdfGpu(0)
+    ctx.set_option("redzone", 0)
+    yield ctx
+    ctx.close()
+
+
+def test_switching_red_zones_on_releases_the_analysis_scratch(fresh):
+    """The analysis counterpart of test_gpu_batch_edges.py::test_switching_red_zones_on_releases_the_batch_scratch.  A handle that
+    ran the component, topology, surface and extrema entry points before set_option("redzone", 1) must not keep their scratch
+    without canaries: the switch releases it (the device's free memory rises by what the four calls planned at least),
+    sdfgpu_convex_last_info asks for a new extrema call instead of reading statistics that went with the scratch, and the same
+    four calls, on scratch with zones, give the same results and leave every canary alone.  Device forms on caller-owned buffers
+    only: the host forms go through the staging buffers, which the switch has always released."""
+    import torch
+    side = 128                                          # the smallest cube with nz % 32 == 0 that plans 32 MiB (the amount the
+    while _analysis_scratch_bytes((side,) * 3, 0) < (32 << 20):                          # batch test sees in mem_get_info)
+        side += 32
+    shape, n, res = (side,) * 3, side ** 3, 0.02
+    ctx = fresh
+    sizes = {"bits": (n + 31) // 32 * 4, "labels": n * 4, "indices": n * 4, "field": n * 4, "extrema": n * 4}
+    d = {k: ctx.device_malloc(v) for k, v in sizes.items()}
+    ctx.copy_from_host(d["bits"], capi.pack_bits_host(synth.bernoulli_mask(shape, 0.3, 21)))
+    ctx.copy_from_host(d["field"], (np.random.default_rng(21).random(shape) * 2 - 1).astype(np.float32))
+
+    def run():
+        k = ctx.components_bits_device(d["bits"], shape, d["labels"])
+        counters = ctx.component_topology_device(d["labels"], shape, k)
+        counts, total = ctx.component_surfaces_device(d["labels"], shape, k, d_indices=d["indices"], capacity=n)
+        ctx.local_extrema_device(d["field"], shape, res, d["extrema"])
+        info = ctx.convex_last_info()
+        torch.cuda.synchronize()
+        return (k, ctx.copy_to_host(np.empty(n, np.uint32), d["labels"]), counters, counts, total,
+                ctx.copy_to_host(np.empty(n, np.uint32), d["indices"])[:total], ctx.copy_to_host(np.empty(n, np.uint32), d["extrema"]), info)
+
+    first = run()
+    assert first[0] > 1 and first[4] > 0 and first[2][:, 4].sum() > 0       # components, reported voxels and surfaces: there was work
+    planned = _analysis_scratch_bytes(shape, first[0])
+    assert planned >= 32 << 20
+    torch.cuda.synchronize()
+    free0 = torch.cuda.mem_get_info()[0]
+    ctx.set_option("redzone", 1)
+    rise = torch.cuda.mem_get_info()[0] - free0
+    print("planned %d bytes, free memory rose by %d" % (planned, rise))
+    assert rise >= planned - (4 << 20)
+    with pytest.raises(capi.SdfGpuError) as e:          # (its statistics lay in the scratch)
+        ctx.convex_last_info()
+    assert e.value.code == -1
+    second = run()
+    ctx.redzone_check()
+    for a, b in zip(first, second):
+        assert np.array_equal(a, b) if isinstance(a, np.ndarray) else a == b
+    for p in d.values():
+        ctx.device_free(p)
+
+
 def test_multi_rank_builds_are_clean_under_red_zones(monkeypatch):
     """libsdfgpu_multi with 1 .. 4 logical ranks (contexts created with SDFGPU_REDZONE=1): slabs, bit planes, halos, the re-partition."""
     monkeypatch.setenv("SDFGPU_REDZONE", "1")
