@@ -768,7 +768,7 @@ int sdfgpu_get_stage_times(sdfgpu_handle h, double* out_ms_sum, int64_t* out_bui
 /* Named integer options.  EVERY option leaves the results exact: they move work between kernels, switch a measured optimisation
  * off for an A/B, or put the handle's policy into a state a test needs.  Unknown names return SDFGPU_ERR_INVALID_ARGUMENT.
  * No option skips work: the profiling builds whose switches did were removed after commit 4eb6a2c, and the names of those
- * switches are unknown names here.
+ * switches and the switches retired with this commit are unknown names here.
  * [T] = test / fuzz only (forces a state the policy reaches by itself), [AB] = A/B switch of a measured optimisation (default = the
  * faster setting; DESIGN.md / LAB_NOTES.md hold the measurement), [U] = for users.
  *
@@ -780,33 +780,29 @@ int sdfgpu_get_stage_times(sdfgpu_handle h, double* out_ms_sum, int64_t* out_bui
  *  "envelope_dc"             [AB]     1        0: never use the far-field kernel
  *  "envelope_mode"           [T]      0        1: the far-field kernel is the only sweep of both axes, no probes
  *  "far_predict"             [U]      1        handles whose recent builds were far-field skip probes + marching launches (0 off, 2 always)
- *  "far_threshold_y/_x", "far_fraction_den_y/_x"  [AB]  16, 9 / 5, 24   an axis is far-field when > 1/den of the probed voxels have d^2 >= thr
- *  "mid_threshold_y", "mid_fraction_den_y"        [AB]  16 / 24         radius-8 y window when > 1/den of them have d^2 >= thr (den 0: never)
+ *  "far_threshold_y/_x"      [T]      16, 9    an axis is far-field when > 1/5 (y), 1/24 (x) of the probed voxels have d^2 >= this
  *  "probe_window"            [AB]     1        tier probes as window statistics (0: level A of the far-field search on sampled tiles)
  *  "policy_reset"            [T]      -        forget what the handle learned from earlier builds
  *  "expect_dense"            [T]      0        put the handle into the "dense tier trusted" state (stand-by pair behind it)
  *  "fixup_mode", "dense3_mode" [T]    0        force the fix-up stage / KD3 in KD's place with the next build
  *
  *  dense tier
- *  "fixup"                   [AB]     1        fix-up kernel KF behind the ball kernel for almost-dense scenes
  *  "dense3"                  [AB]     1        wide ball kernel KD3 (|offset| <= 3) as the fix-up stage's first kernel
  *  "dense3_staged"           [AB]     1        builds that cannot expect KD to decide the scene carry KD3 + KF behind it, guarded
  *  "dense3_fixed"            [AB]     1        KD3's nz = 512 instance (compile-time row pitch)
  *  "dense_shell"             [AB]     1        shell pass KD6 (16 <= d^2 <= 36) between KD3 and KF
- *  "shell_min_words", "shell_budget_den"  [AB]  128 / 8   KD6: open words below which a tile group is left to KF; budget 1/den of the voxels
+ *  "shell_min_words"         [AB]     128      KD6: open words below which a tile group is left to KF
  *  "standby_far"             [AB]     1        stand-by behind a trusted dense tier = far-field pair (0: fused z+y + marching x, unbounded)
  *  "standby_fold"            [AB]     1        the stand-by x sweep's launch also folds the extrema (one launch less per build)
  *  "standby_grid"            [AB]     1024     workgroups of the stand-by launches
- *  "pack_variant", "ball_block", "nt_store"  [AB]  0   K0 unroll / KD workgroup size / non-temporal output stores
+ *  "ball_serpentine"         [AB]     1        a whole build that rewrites the last build's buffer walks KD's tiles in the opposite order
  *
  *  sweeps
  *  "fused_zy"                [AB]     1        let the policy use the fused z+y kernel (0 never, 2 always when the shape allows)
  *  "fused_window"            [AB]     2        its register-window radius at nz = 512 (2 or 3)
  *  "plane16"                 [AB]     1        int16 plane field + int32 side table between the y and x sweeps (0: int32 plane field)
- *  "y16"                     [AB]     1        y sweep of that pipeline through the packed 16-bit kernel
  *  "z_wave"                  [AB]     1        z sweep with whole rows per wave where nz = 64 ... 1024
- *  "x16_voxels_per_lane", "x16_window", "march_window"  [AB]  4 / 3 / 3   K3/16 variant; forced radius-8 windows (= 8)
- *  "rows_per_chunk_y/_x/_zy" [AB]     0        rows marched per thread (0: automatic); also sdfgpu_set_tuning
+ *  "x16_voxels_per_lane", "x16_window"  [AB]  4 / 3   K3/16 variant: voxels per lane (4 or 8), window radius (2, 3 or 8)
  *  "i32_handoff"             [AB]     1        far-field pair hands exact int32 plane values from the y to the x sweep
  *  "dc_fixed"                [AB]     1        far-field kernel: instances with the 512- / 1024-voxel line geometry at compile time
  *  "plane_skip"              [AB]     1        builds that go straight to the far-field pair skip the x-planes without a filled voxel

@@ -112,13 +112,96 @@ struct ContextBuffers {
 };
 static_assert(sizeof(ContextBuffers) == 27 * sizeof(DeviceBuffer), "ContextBuffers holds DeviceBuffer members only");
 
+// What sdfgpu_set_option and sdfgpu_set_tuning write and a build only reads (include/sdfgpu.h has the table).  The defaults here are
+// the documented ones.
+struct BuildOptions {
+    // tier selection
+    bool dense_on = true;            // try the bit-parallel dense kernel first when the shape allows
+    bool dense_generic_on = true;    // generic dense kernels for shapes / modes the tuned ones do not take
+    bool envelope_on = true;         // bound the outward scans and redo far-field sweeps with the envelope kernels
+    bool envelope_dc = true;         // use the divide-and-conquer envelope kernel (sdfgpu_envelope_dc.hpp) when the shape allows
+    int force_env = -1;              // -1 automatic, 1 = envelope kernels only (option "envelope_mode")
+    // an axis is far-field when more than 1 / kFarDen of the probed voxels have d^2 >= thr.  Per axis, from the measured
+    // break-even of the two sweeps at 512^3 (tools/p_sweep.py, tools/ythr_probe.py): the y marching sweep (2 B rows, radius-8
+    // windows) against the far-field PAIR (int32 hand-off, no x probe) breaks even at in-plane d^2 ~ 36 on an eighth of the
+    // voxels (Bernoulli p = 0.02: 1.31 vs 1.29 ms; p = 0.015: 1.54 vs 1.29 ms; p = 0.025: 1.21 vs 1.28 ms); the x marching sweep falls behind the far-field kernel as soon as its
+    // radius-3 window stops deciding nearly every voxel (Bernoulli p = 0.03: 0.65 ms against 0.55; p = 0.04 and denser:
+    // marching wins), so its threshold is d^2 >= 9 on 1 / 24 of the voxels (p = 0.03: 6 %, p = 0.04: 2.4 %)
+    // (round 3, third-generation far-field kernel: KE2 0.57 -> 0.39 ms moves the y break-even from Bernoulli p ~ 0.018 up to
+    //  p ~ 0.035 -- tools/tier_sweep.py: p = 0.03 1.01 vs 0.97 ms, p = 0.02 1.16 vs 0.985, p = 0.04 0.87 vs 0.97 -- i.e. from
+    //  "d^2 >= 36 on an eighth" to "d^2 >= 16 on a fifth" of the voxels: (1 - p)^49 = 0.225 at p = 0.03, 0.135 at p = 0.04)
+    int far_thr[2] = {16, 9};
+    bool probe_window = true;        // tier probes as window statistics (option "probe_window"; 0 = level A of the far-field search on sampled tiles)
+    // dense tier
+    bool dense3_fixed = true;        // KD3's nz = 512 instance (option "dense3_fixed")
+    bool shell_on = true;            // KD6, the bit-parallel shell pass between KD3 and KF (option "dense_shell")
+    int shell_min_words = kShellMinWords;   // option "shell_min_words"
+    bool standby_far = true;         // stand-by pipeline behind a trusted dense tier = the far-field pair (bounded whatever the scene
+                                     // turns into), not fused K12 + K3/16 with unbounded scans (option "standby_far")
+    bool standby_fold = true;        // the stand-by x sweep's launch folds the maxima and publishes the status block itself (option "standby_fold")
+    int standby_grid = 1024;         // workgroups of the stand-by launches (LOOP form; option "standby_grid"): 4 per CU = all resident at once
+    // Serpentine tile order (option "ball_serpentine"): a whole build that writes the buffer the handle's last KD launch wrote, at
+    // the same size, walks KD's tiles in the opposite order -- it starts on the lines the last one finished with, which are
+    // the ones the Infinity Cache still holds; walked the same way round every time, an LRU-like cache has evicted each
+    // line just before it is reached.  Speed only: the field, the maxima and the flags do not depend on the order.
+    bool ball_serpentine = true;
+    // sweeps
+    bool fused_zy = true;            // use K12 (z sweep fused into the y sweep) when the shape allows
+    bool fused_always = false;       // ... whenever it does (option "fused_zy" = 2)
+    int fused_h = 2;                 // its register-window radius at nz = 512: 2 or 3 (option "fused_window")
+    bool plane16_on = true;          // use the int16 plane field + side table when the shape allows
+    bool z_wave_on = true;           // z sweep with wave-private rows where nz allows it (option "z_wave"; 0 = the workgroup form)
+    int x16_v = 4, x16_h = 3;        // K3/16 variant: voxels per lane, window radius
+    int tune_ty = 0, tune_tx = 0;    // rows marched per thread by the y / x sweep (sdfgpu_set_tuning; 0 = automatic)
+    bool i32_handoff = true;         // far-field pair: int32 plane field between the y and x sweeps (option "i32_handoff")
+    bool dc_fixed = true;            // far-field kernel: the 512-voxel-line instances (option "dc_fixed")
+    bool plane_skip = true;          // builds that go straight to the far-field pair: the z sweep marks the x-planes that hold a filled voxel,
+                                     // the y sweep skips the tiles of the others, the x sweep their row loads (option "plane_skip")
+    // ... and y tiles whose 16 lines are all flat-positive (a floor under open space) skip the search (option "flat_tiles")
+    int flat_tiles = 1;              // (2: every such tile tries, whatever the habit says -- tests)
+    // host side / debugging
+    int host_pack = 1;       // host-buffer builds classify on the host and upload bits (option "host_pack"; 0 = upload the
+                             // caller's mask / cells and classify on the device, as rounds 1 - 4 did)
+    int defer_fold = 0;           // stage entry points leave their maxima in the slot array until sdfgpu_fold_extrema_device
+    bool rs_plain_atomics = false;        // option "resample_plain_atomics": one atomic per lane (tools/resample_bench.py)
+    bool rs_timing = false;               // option "resample_timing": events around the two kernels (sdfgpu_debug_resample_times)
+};
+
+// What the sdfgpu_last_* and sdfgpu_debug_* calls report about the most recent build or stage call.
+struct LastBuild {
+    hipStream_t last_stream = nullptr;
+    double last_resolution = 1.0;
+    int64_t last_n = 0;
+    bool have_result = false;
+    int64_t last_dims[3] = {0, 0, 0};
+    bool last_fused = false;
+    bool last_plane16 = false;
+    bool last_dense = false;
+    bool last_standby = false;       // the last build carried the far-field stand-by pair behind a trusted dense tier
+    bool last_dense3 = false, last_staged = false;   // ... ran KD3 + KF in KD's place / carried them behind KD, guarded on its verdict
+    bool last_predicted = false;     // the last build took the far-field pair on the strength of the handle's recent builds: no probes, no marching launches
+    bool last_lines_tiered = false;  // the last sdfgpu_sweep_x_lines_device call chose its tier on the device (probe / forced tier + far-field kernel behind the marching sweep)
+    int last_dc_x = 0;               // 1 + the far-field kernel instance (launch_envelope's `which`) of the last x sweep launched through it; 0: none since the last build / lines call began
+    bool last_plane_skip = false;    // the last build skipped the x-planes without a filled voxel (sdfgpu_debug_copy_yzsweep fills them in)
+};
+
+// What the launchers read off the handle while one call enqueues: the pointers are non-null only then (the scan bounds go with far_y).
+struct InFlight {
+    const uint32_t* guard = nullptr; // set while a build enqueues the flag-guarded general pipeline
+    uint32_t* far_y = nullptr;       // set while a build enqueues a bounded K2 / K3
+    int scan_y = kScanExpectNear, scan_x = kScanExpectNear;   // outward-scan bounds of the marching kernels
+    uint32_t* unc_override = nullptr;   // set around the staged KD3 launch: undecided bits in the z field's storage
+    size_t unc_override_bytes = 0;
+};
+
 }  // namespace
 
 struct sdfgpu_context : ContextBuffers {
     int device = 0;
     std::string error;
-    int host_pack = 1;       // host-buffer builds classify on the host and upload bits (option "host_pack"; 0 = upload the
-                             // caller's mask / cells and classify on the device, as rounds 1 - 4 did)
+    BuildOptions opt;
+    LastBuild last;
+    InFlight inflight;
     size_t cx_stats_off = 0;    // where the last extrema call left its CxStats in cx_scratch (0 = no call yet)
     int cx_rounds = 0;          // doubling rounds of that call
     char* batch_pin = nullptr;  // pinned ring through which per-grid parameters reach the device without a host wait
@@ -145,14 +228,6 @@ struct sdfgpu_context : ContextBuffers {
                                             // transfer, parked between calls, joined by sdfgpu_destroy (sdfgpu_hostteam.hpp)
     hipEvent_t pin_ev[2] = {nullptr, nullptr};
     uint32_t* d_small = nullptr;   // [0] max d^2 free, [1] max d^2 filled, [2] status, [3] uncertified, [4] far_y, [5] far_x
-    hipStream_t last_stream = nullptr;
-    double last_resolution = 1.0;
-    int64_t last_n = 0;
-    bool have_result = false;
-    bool last_fused = false;
-    bool last_lines_tiered = false;  // the last sdfgpu_sweep_x_lines_device call chose its tier on the device (probe / forced tier + far-field kernel behind the marching sweep)
-    int last_dc_x = 0;               // 1 + the far-field kernel instance (launch_envelope's `which`) of the last x sweep launched through it; 0: none since the last build / lines call began
-    bool last_predicted = false;     // the last build took the far-field pair on the strength of the handle's recent builds: no probes, no marching launches
     // "this handle's scene is a far-field scene on both axes": learnt from the status blocks that come back (never a wait).  Such a
     // build skips the two probes and the three guarded marching launches (35 us of a 0.8 - 1.4 ms build) and enqueues KE2 -> KE3
     // directly (int32 hand-off); every 16th build probes again.  The far-field pair is exact on any scene: a wrong prediction costs
@@ -162,64 +237,13 @@ struct sdfgpu_context : ContextBuffers {
     uint32_t* h_far_dev = nullptr;
     hipEvent_t far_ev = nullptr;
     bool far_pending = false;
-    bool last_standby = false;       // the last build carried the far-field stand-by pair behind a trusted dense tier
-    bool last_dense3 = false, last_staged = false;   // ... ran KD3 + KF in KD's place / carried them behind KD, guarded on its verdict
-    int tune_ty = 0, tune_tx = 0, tune_tzy = 0, fused_h = 0;
-    bool fused_zy = true;            // use K12 (z sweep fused into the y sweep) when the shape allows
-    bool dense_on = true;            // try the bit-parallel dense kernel first when the shape allows
-    int pack_variant = 0;
-    int ball_block = 0;
     DensePolicy pol;              // what the handle has learned about its scenes' dense tier (sdfgpu_policy.hpp)
-    uint32_t* unc_override = nullptr;   // set around the staged KD3 launch: undecided bits in the z field's storage
-    size_t unc_override_bytes = 0;
-    int defer_fold = 0;           // stage entry points leave their maxima in the slot array until sdfgpu_fold_extrema_device
-    int nt_store = 0;               // measured: non-temporal output stores slow the next build's pack (0.03 -> 0.08 ms)
-    bool envelope_on = true;         // bound the outward scans and redo far-field sweeps with the envelope kernels
-    bool envelope_dc = true;         // use the divide-and-conquer envelope kernel (sdfgpu_envelope_dc.hpp) when the shape allows
-    bool dense_generic_on = true;    // generic dense kernels for shapes / modes the tuned ones do not take
-    bool shell_on = true;            // KD6, the bit-parallel shell pass between KD3 and KF (option "dense_shell")
-    bool dc_fixed = true;            // far-field kernel: the 512-voxel-line instances (option "dc_fixed")
-    bool plane_skip = true;          // builds that go straight to the far-field pair: the z sweep marks the x-planes that hold a filled voxel,
-                                     // the y sweep skips the tiles of the others, the x sweep their row loads (option "plane_skip")
     bool flat_score_reset = false;   // "policy_reset": the next build clears the device-side habit of the two-valued tiles (status word 40)
-    int flat_tiles = 1;              // (2: every such tile tries, whatever the habit says -- tests)
-    // ... and y tiles whose 16 lines are all flat-positive (a floor under open space) skip the search (option "flat_tiles")
-    bool last_plane_skip = false;    // the last build used it (sdfgpu_debug_copy_yzsweep fills the skipped planes in)
-    int64_t last_dims[3] = {0, 0, 0};
-    bool dense3_fixed = true;        // KD3's nz = 512 instance (option "dense3_fixed")
-    // Serpentine tile order (option "ball_serpentine"): a whole build that writes the buffer the handle's last KD launch wrote, at
-    // the same size, walks KD's tiles in the opposite order -- it starts on the lines the last one finished with, which are
-    // the ones the Infinity Cache still holds; walked the same way round every time, an LRU-like cache has evicted each
-    // line just before it is reached.  Speed only: the field, the maxima and the flags do not depend on the order.
-    bool ball_serpentine = true;
-    const float* serp_out = nullptr; // output buffer and voxel count of the last whole-build KD launch, and its direction
+    const float* serp_out = nullptr; // "ball_serpentine": output buffer and voxel count of the last whole-build KD launch, and its direction
     int64_t serp_n = 0;
     int serp_flip = 0;
-    int shell_min_words = kShellMinWords;   // option "shell_min_words"
-    int shell_budget_den = 8;        // ... for scenes with at most 1 / 8 of their voxels undecided behind KD3 (option "shell_budget_den"): Bernoulli
-                                     // p = 0.01 leaves 8 % (0.78 ms against the far-field pair's 0.96), p = 0.007 17 % (1.07 ms against 0.97)
-    int force_env = -1;              // -1 automatic, 1 = envelope kernels only (option "envelope_mode")
-    // an axis is far-field when more than 1 / den of the probed voxels have d^2 >= thr.  Per axis, from the measured
-    // break-even of the two sweeps at 512^3 (tools/p_sweep.py, tools/ythr_probe.py): the y marching sweep (2 B rows, radius-8
-    // windows) against the far-field PAIR (int32 hand-off, no x probe) breaks even at in-plane d^2 ~ 36 on an eighth of the
-    // voxels (Bernoulli p = 0.02: 1.31 vs 1.29 ms; p = 0.015: 1.54 vs 1.29 ms; p = 0.025: 1.21 vs 1.28 ms); the x marching sweep falls behind the far-field kernel as soon as its
-    // radius-3 window stops deciding nearly every voxel (Bernoulli p = 0.03: 0.65 ms against 0.55; p = 0.04 and denser:
-    // marching wins), so its threshold is d^2 >= 9 on 1 / 24 of the voxels (p = 0.03: 6 %, p = 0.04: 2.4 %)
-    // (round 3, third-generation far-field kernel: KE2 0.57 -> 0.39 ms moves the y break-even from Bernoulli p ~ 0.018 up to
-    //  p ~ 0.035 -- tools/tier_sweep.py: p = 0.03 1.01 vs 0.97 ms, p = 0.02 1.16 vs 0.985, p = 0.04 0.87 vs 0.97 -- i.e. from
-    //  "d^2 >= 36 on an eighth" to "d^2 >= 16 on a fifth" of the voxels: (1 - p)^49 = 0.225 at p = 0.03, 0.135 at p = 0.04)
-    int far_thr[2] = {16, 9};
-    int far_den[2] = {5, 24};
-    bool i32_handoff = true;         // far-field pair: int32 plane field between the y and x sweeps (option "i32_handoff")
-    bool standby_far = true;         // stand-by pipeline behind a trusted dense tier = the far-field pair (bounded whatever the scene
-                                     // turns into), not fused K12 + K3/16 with unbounded scans (option "standby_far")
-    bool standby_fold = true;        // the stand-by x sweep's launch folds the maxima and publishes the status block itself (option "standby_fold")
-    int standby_grid = 1024;         // workgroups of the stand-by launches (LOOP form; option "standby_grid"): 4 per CU = all resident at once
     bool dc_attr_set[16] = {};   // MaxDynamicSharedMemorySize raised, per far-field kernel instantiation
     int k1_resident = 0;             // workgroups of k_sweep_z_vec16 the device holds at once (persistent grid size)
-    uint32_t* far_y = nullptr;       // set while a build enqueues a bounded K2 / K3
-    int scan_y = kScanExpectNear, scan_x = kScanExpectNear;   // outward-scan bounds of the marching kernels
-    bool fused_always = false;
     uint32_t* d_slots = nullptr;     // [kSlots][kSlotWords] extrema / flag slots of the dense kernel (kept zero between launches)
     uint32_t* d_result = nullptr;    // [8] the status block of the last finished build (d_small is cleared by its fold)
     bool small_clean = false;        // d_small is all zero (left so by the previous build's fold kernel)
@@ -233,20 +257,8 @@ struct sdfgpu_context : ContextBuffers {
                                           // pending on its stream when the call returns: one on another stream waits for it first
     StreamOrder rs_order;                 // recorded behind every resample, which may return with its kernels pending on its
                                           // stream: one on another stream waits for it before it clears the winner words
-    bool rs_plain_atomics = false;        // option "resample_plain_atomics": one atomic per lane (tools/resample_bench.py)
-    bool rs_timing = false;               // option "resample_timing": events around the two kernels (sdfgpu_debug_resample_times)
-    hipEvent_t rs_time_ev[3] = {nullptr, nullptr, nullptr};
+    hipEvent_t rs_time_ev[3] = {nullptr, nullptr, nullptr};   // "resample_timing"
     bool rs_timed = false;
-    bool last_dense = false;
-    const uint32_t* guard = nullptr; // set while a build enqueues the flag-guarded general pipeline
-    bool plane16_on = true;          // use the int16 plane field + side table when the shape allows
-    bool z_wave_on = true;           // z sweep with wave-private rows where nz allows it (option "z_wave"; 0 = the workgroup form)
-    bool probe_window = true;        // tier probes as window statistics (option "probe_window"; 0 = level A of the far-field search on sampled tiles)
-    bool y16_on = true;              // y sweep of that pipeline through the packed 16-bit kernel (option "y16"; 0 = the 32-bit marching kernel)
-    int x16_v = 4, x16_h = 3;        // K3/16 variant: voxels per lane, window radius
-    int march_h = 3;                 // K2 (y sweep) register-window radius: 3 or 8 (forced)
-    int mid_thr_y = 16, mid_den_y = 24;   // y probe: radius-8 marching window when more than 1 / den of the voxels have d^2 >= thr
-    bool last_plane16 = false;
     int profiling = 0;            // 0 off, 1 an event behind every stage, 2 events around the dense ball kernel only,
                                   // 3 like 2 but only on every 4th build
     uint32_t profiled_builds = 0; // builds seen while profiling (level 3 samples every 4th)
@@ -427,7 +439,7 @@ int rows_per_block(int nz) {
 
 // K1 launch.  cells == nullptr -> uint8 mask.
 bool z_wave16_shape(const sdfgpu_context* h, int64_t nz) {
-    return h->z_wave_on && (nz == 64 || nz == 128 || nz == 256 || nz == 512 || nz == 1024);
+    return h->opt.z_wave_on && (nz == 64 || nz == 128 || nz == 256 || nz == 512 || nz == 1024);
 }
 
 // d_row_any != nullptr (callers check z_wave16_shape and, for masks, the alignment first): the kernel also writes one "holds a filled voxel" byte per z row
@@ -438,17 +450,17 @@ int launch_sweep_z(sdfgpu_handle h, const uint8_t* d_mask, const void* d_cells, 
     if (d_bits) {
         // bits in (round 6): the wave-private form reads its 16 voxels as one 16-bit piece of the bit field; every other shape
         // goes through the generic kernel with a bit loader
-        if (h->z_wave_on && (nz == 64 || nz == 128 || nz == 256 || nz == 512 || nz == 1024)) {
+        if (h->opt.z_wave_on && (nz == 64 || nz == 128 || nz == 256 || nz == 512 || nz == 1024)) {
             const int rw = 1024 / (int)nz;
             const int64_t ngroups = (nrows + rw - 1) / rw;
             dim3 gw((unsigned)std::min<int64_t>((ngroups + kBlock / 64 - 1) / (kBlock / 64), 8192)), block(kBlock);
             const uint8_t* b8 = reinterpret_cast<const uint8_t*>(d_bits);
             switch ((int)nz) {
-                case 64: hipLaunchKernelGGL((k_sweep_z_wave16<4, true>), gw, block, 0, s, b8, d_out, nrows, h->guard, d_row_any); break;
-                case 128: hipLaunchKernelGGL((k_sweep_z_wave16<8, true>), gw, block, 0, s, b8, d_out, nrows, h->guard, d_row_any); break;
-                case 256: hipLaunchKernelGGL((k_sweep_z_wave16<16, true>), gw, block, 0, s, b8, d_out, nrows, h->guard, d_row_any); break;
-                case 512: hipLaunchKernelGGL((k_sweep_z_wave16<32, true>), gw, block, 0, s, b8, d_out, nrows, h->guard, d_row_any); break;
-                default: hipLaunchKernelGGL((k_sweep_z_wave16<64, true>), gw, block, 0, s, b8, d_out, nrows, h->guard, d_row_any); break;
+                case 64: hipLaunchKernelGGL((k_sweep_z_wave16<4, true>), gw, block, 0, s, b8, d_out, nrows, h->inflight.guard, d_row_any); break;
+                case 128: hipLaunchKernelGGL((k_sweep_z_wave16<8, true>), gw, block, 0, s, b8, d_out, nrows, h->inflight.guard, d_row_any); break;
+                case 256: hipLaunchKernelGGL((k_sweep_z_wave16<16, true>), gw, block, 0, s, b8, d_out, nrows, h->inflight.guard, d_row_any); break;
+                case 512: hipLaunchKernelGGL((k_sweep_z_wave16<32, true>), gw, block, 0, s, b8, d_out, nrows, h->inflight.guard, d_row_any); break;
+                default: hipLaunchKernelGGL((k_sweep_z_wave16<64, true>), gw, block, 0, s, b8, d_out, nrows, h->inflight.guard, d_row_any); break;
             }
         } else {
             const int rpb = rows_per_block((int)nz);
@@ -456,7 +468,7 @@ int launch_sweep_z(sdfgpu_handle h, const uint8_t* d_mask, const void* d_cells, 
             const size_t lds = (size_t)rpb * W * 8 + (size_t)rpb * 4;
             const int64_t nblocks = (nrows + rpb - 1) / rpb;
             BitsLoader ld{d_bits};
-            hipLaunchKernelGGL(k_sweep_z_generic<BitsLoader>, dim3((unsigned)std::min<int64_t>(nblocks, 2048)), dim3(kBlock), lds, s, ld, d_out, nrows, (int)nz, rpb, h->guard);
+            hipLaunchKernelGGL(k_sweep_z_generic<BitsLoader>, dim3((unsigned)std::min<int64_t>(nblocks, 2048)), dim3(kBlock), lds, s, ld, d_out, nrows, (int)nz, rpb, h->inflight.guard);
         }
         HIP_TRY(h, hipGetLastError());
         return SDFGPU_OK;
@@ -481,8 +493,8 @@ int launch_sweep_z(sdfgpu_handle h, const uint8_t* d_mask, const void* d_cells, 
     }
     if (d_cells) {
         CellLoader ld{reinterpret_cast<const char*>(d_cells), (int64_t)stride, (int64_t)off, unknown};
-        hipLaunchKernelGGL(k_sweep_z_generic<CellLoader>, grid, block, lds, s, ld, d_out, nrows, (int)nz, rpb, h->guard);
-    } else if (h->z_wave_on && (nz == 64 || nz == 128 || nz == 256 || nz == 512 || nz == 1024) &&
+        hipLaunchKernelGGL(k_sweep_z_generic<CellLoader>, grid, block, lds, s, ld, d_out, nrows, (int)nz, rpb, h->inflight.guard);
+    } else if (h->opt.z_wave_on && (nz == 64 || nz == 128 || nz == 256 || nz == 512 || nz == 1024) &&
                (reinterpret_cast<uintptr_t>(d_mask) % 16) == 0) {
         // whole rows per wave (16 nz-lanes): no workgroup barrier; 32 workgroups per CU's worth of persistent waves (measured
         // at 512^3: 8 per CU 0.099 ms, 16 0.093, 32 0.088, one step per wave 0.100)
@@ -490,17 +502,17 @@ int launch_sweep_z(sdfgpu_handle h, const uint8_t* d_mask, const void* d_cells, 
         const int64_t ngroups = (nrows + rw - 1) / rw;
         dim3 gw((unsigned)std::min<int64_t>((ngroups + kBlock / 64 - 1) / (kBlock / 64), 8192));
         switch ((int)nz) {
-            case 64: hipLaunchKernelGGL((k_sweep_z_wave16<4, false>), gw, block, 0, s, d_mask, d_out, nrows, h->guard, d_row_any); break;
-            case 128: hipLaunchKernelGGL((k_sweep_z_wave16<8, false>), gw, block, 0, s, d_mask, d_out, nrows, h->guard, d_row_any); break;
-            case 256: hipLaunchKernelGGL((k_sweep_z_wave16<16, false>), gw, block, 0, s, d_mask, d_out, nrows, h->guard, d_row_any); break;
-            case 512: hipLaunchKernelGGL((k_sweep_z_wave16<32, false>), gw, block, 0, s, d_mask, d_out, nrows, h->guard, d_row_any); break;
-            default: hipLaunchKernelGGL((k_sweep_z_wave16<64, false>), gw, block, 0, s, d_mask, d_out, nrows, h->guard, d_row_any); break;
+            case 64: hipLaunchKernelGGL((k_sweep_z_wave16<4, false>), gw, block, 0, s, d_mask, d_out, nrows, h->inflight.guard, d_row_any); break;
+            case 128: hipLaunchKernelGGL((k_sweep_z_wave16<8, false>), gw, block, 0, s, d_mask, d_out, nrows, h->inflight.guard, d_row_any); break;
+            case 256: hipLaunchKernelGGL((k_sweep_z_wave16<16, false>), gw, block, 0, s, d_mask, d_out, nrows, h->inflight.guard, d_row_any); break;
+            case 512: hipLaunchKernelGGL((k_sweep_z_wave16<32, false>), gw, block, 0, s, d_mask, d_out, nrows, h->inflight.guard, d_row_any); break;
+            default: hipLaunchKernelGGL((k_sweep_z_wave16<64, false>), gw, block, 0, s, d_mask, d_out, nrows, h->inflight.guard, d_row_any); break;
         }
     } else if ((nz % 16) == 0 && (reinterpret_cast<uintptr_t>(d_mask) % 16) == 0) {
-        hipLaunchKernelGGL(k_sweep_z_vec16, grid, block, lds, s, d_mask, d_out, nrows, (int)nz, rpb, h->guard);
+        hipLaunchKernelGGL(k_sweep_z_vec16, grid, block, lds, s, d_mask, d_out, nrows, (int)nz, rpb, h->inflight.guard);
     } else {
         MaskLoader ld{d_mask};
-        hipLaunchKernelGGL(k_sweep_z_generic<MaskLoader>, grid, block, lds, s, ld, d_out, nrows, (int)nz, rpb, h->guard);
+        hipLaunchKernelGGL(k_sweep_z_generic<MaskLoader>, grid, block, lds, s, ld, d_out, nrows, (int)nz, rpb, h->inflight.guard);
     }
     HIP_TRY(h, hipGetLastError());
     return SDFGPU_OK;
@@ -521,13 +533,13 @@ int launch_march(sdfgpu_handle h, SweepArgs a, bool vec4, hipStream_t s, int for
     dim3 grid((unsigned)nbx, (unsigned)nchunks), block(kBlock);
     bool wide = false;
     if constexpr (STAGE == 2 && !VB) {                       // radius-8 window: y sweep only
-        if (vec4 && force_window != 3 && (force_window == 8 || h->march_h == 8)) {
+        if (vec4 && force_window == 8) {
             hipLaunchKernelGGL((k_sweep_march<2, 4, 8, false>), grid, block, 0, s, a);
             wide = true;
         }
     }
     if (wide) {}
-    else if (STAGE == 2 && vec4 && a.out16 && h->y16_on && kH == 3)      // y sweep into the 16-bit plane field: packed 16-bit window
+    else if (STAGE == 2 && vec4 && a.out16 && kH == 3)      // y sweep into the 16-bit plane field: packed 16-bit window
         hipLaunchKernelGGL((k_sweep_y16<3>), grid, block, 0, s, a);
     else if (vec4) hipLaunchKernelGGL((k_sweep_march<STAGE, 4, kH, VB>), grid, block, 0, s, a);
     else hipLaunchKernelGGL((k_sweep_march<STAGE, 1, kH, VB>), grid, block, 0, s, a);
@@ -547,15 +559,15 @@ int launch_sweep_y(sdfgpu_handle h, const int16_t* d_in, void* d_out, int32_t* d
     SweepArgs a{};
     a.in = d_in; a.out = d_out;
     a.out16 = d_side ? 1 : 0; a.side = d_side;
-    a.guard = h->guard;
-    if (h->far_y) { a.max_scan = h->scan_y; a.far_flag = h->far_y; }
+    a.guard = h->inflight.guard;
+    if (h->inflight.far_y) { a.max_scan = h->inflight.scan_y; a.far_flag = h->inflight.far_y; }
     a.cpl = nz / V;
     a.ncols = nx * a.cpl;
     a.outer_stride = ny * nz;
     a.line_stride = nz;
     a.L = (int)ny; a.out_lo = 0; a.out_hi = (int)ny;
-    a.T = pick_T(h->tune_ty, (int)ny);
-    if (h->tune_ty <= 0 && vec4 && d_side && h->y16_on) {
+    a.T = pick_T(h->opt.tune_ty, (int)ny);
+    if (h->opt.tune_ty <= 0 && vec4 && d_side) {
         // K2/16: chunks of 16 batches of 7 rows while the launch still fills the device.  Measured at 512^3 (rocprofv3):
         // 56 rows 131 us, 64 rows 138, 112 rows 122, 119 / 126 rows 123 - 125, 128 rows 132 -- with a power-of-two chunk the
         // workgroups, which march in step, read addresses that differ by multiples of 64 KB only.
@@ -570,7 +582,7 @@ int launch_sweep_y(sdfgpu_handle h, const int16_t* d_in, void* d_out, int32_t* d
 
 // K12 launch: mask -> int32 in-plane signed d^2 in one kernel (nz = 512 or 1024, 16-B aligned mask)
 bool fused_zy_eligible(const sdfgpu_context* h, const uint8_t* d_mask, const void* d_out, int64_t nz) {
-    return h->fused_zy && d_mask && (nz == 512 || nz == 1024) &&
+    return h->opt.fused_zy && d_mask && (nz == 512 || nz == 1024) &&
            (reinterpret_cast<uintptr_t>(d_mask) % 16) == 0 && (reinterpret_cast<uintptr_t>(d_out) % 16) == 0;
 }
 
@@ -591,10 +603,10 @@ int launch_sweep_zy_fused(sdfgpu_handle h, const uint8_t* d_mask, void* d_out, i
                           int64_t ny, int64_t nz, hipStream_t s) {
     FusedZyArgs a{};
     a.mask = d_mask; a.out = d_out; a.side = d_side; a.nx = (int)nx; a.ny = (int)ny;
-    a.guard = h->guard;
-    const int T = h->tune_tzy > 0 ? h->tune_tzy : 64;
+    a.guard = h->inflight.guard;
+    const int T = 64;
     const bool o16 = d_side != nullptr;
-    if (nz == 512 && h->fused_h == 3) launch_fused_variant<8, 3>(a, T, nx, ny, o16, s);
+    if (nz == 512 && h->opt.fused_h == 3) launch_fused_variant<8, 3>(a, T, nx, ny, o16, s);
     else if (nz == 512) launch_fused_variant<8, 2>(a, T, nx, ny, o16, s);
     else launch_fused_variant<16, 2>(a, T, nx, ny, o16, s);
     HIP_TRY(h, hipGetLastError());
@@ -611,7 +623,7 @@ void launch_x16_variant(const SweepX16Args& a, dim3 grid, dim3 block, bool vb, b
 }
 
 bool plane16_eligible(const sdfgpu_context* h, int64_t ny, int64_t nz) {
-    return h->plane16_on && (nz % 4) == 0 && ((ny * nz) % 8) == 0;
+    return h->opt.plane16_on && (nz % 4) == 0 && ((ny * nz) % 8) == 0;
 }
 
 int launch_sweep_x16(sdfgpu_handle h, const int16_t* d_in16, const int32_t* d_side, float* d_out, int64_t halo_lo,
@@ -619,21 +631,21 @@ int launch_sweep_x16(sdfgpu_handle h, const int16_t* d_in16, const int32_t* d_si
                      int lo_trunc, int hi_trunc, int64_t x_global, int64_t nx_global, double resolution, int vb,
                      uint32_t* d_maxdsq, uint32_t* d_status, hipStream_t s) {
     const int64_t plane = ny * nz;
-    const int V = (h->x16_v == 8) ? 8 : 4;
+    const int V = (h->opt.x16_v == 8) ? 8 : 4;
     SweepX16Args a{};
     a.in16 = d_in16; a.side32 = d_side; a.out = d_out;
     a.ncols = plane / V; a.plane = plane;
     a.L = (int)(halo_lo + nxs + halo_hi);
     a.out_lo = (int)halo_lo; a.out_hi = (int)(halo_lo + nxs);
-    a.T = pick_T(h->tune_tx, (int)nxs);
+    a.T = pick_T(h->opt.tune_tx, (int)nxs);
     a.side_lo = (int)side_lo; a.side_hi = (int)side_hi;
     a.resolution = resolution;
     a.lo_truncated = lo_trunc; a.hi_truncated = hi_trunc;
     a.x_global = x_global; a.nx_global = nx_global; a.ny = ny; a.nz = nz;
     (void)d_maxdsq;                             // maxima go to the slot array; the caller folds them (fold_slots)
     a.maxdsq = h->d_slots; a.status = d_status;
-    a.guard = h->guard;
-    if (h->far_y) { a.max_scan = h->scan_x; a.far_flag = h->far_y + 1; }
+    a.guard = h->inflight.guard;
+    if (h->inflight.far_y) { a.max_scan = h->inflight.scan_x; a.far_flag = h->inflight.far_y + 1; }
     const int span = a.out_hi - a.out_lo;
     const int nchunks = (span + a.T - 1) / a.T;
     const int64_t nbx = (a.ncols + kBlock - 1) / kBlock;
@@ -641,8 +653,8 @@ int launch_sweep_x16(sdfgpu_handle h, const int16_t* d_in16, const int32_t* d_si
     dim3 grid((unsigned)nbx, (unsigned)nchunks), block(kBlock);
     const bool slab = lo_trunc || hi_trunc || side_lo > 0 || side_hi < a.L;
     if (V == 8) launch_x16_variant<8, 3>(a, grid, block, vb != 0, slab, s);
-    else if (h->x16_h == 2) launch_x16_variant<4, 2>(a, grid, block, vb != 0, slab, s);
-    else if (h->x16_h == 8 && !vb && !slab)      // wide window (option only): plain grids
+    else if (h->opt.x16_h == 2) launch_x16_variant<4, 2>(a, grid, block, vb != 0, slab, s);
+    else if (h->opt.x16_h == 8 && !vb && !slab)      // wide window (option only): plain grids
         hipLaunchKernelGGL((k_sweep_x16<4, 8, false, false>), grid, block, 0, s, a);
     else launch_x16_variant<4, 3>(a, grid, block, vb != 0, slab, s);
     HIP_TRY(h, hipGetLastError());
@@ -666,7 +678,7 @@ int launch_sweep_x(sdfgpu_handle h, const int32_t* d_in, float* d_out, int64_t h
     a.line_stride = plane;
     a.L = (int)(halo_lo + nxs + halo_hi);
     a.out_lo = (int)halo_lo; a.out_hi = (int)(halo_lo + nxs);
-    a.T = pick_T(h->tune_tx, (int)nxs);
+    a.T = pick_T(h->opt.tune_tx, (int)nxs);
     a.resolution = resolution;
     a.lo_truncated = lo_trunc; a.hi_truncated = hi_trunc;
     a.x_global = x_global; a.nx_global = nx_global; a.ny = ny; a.nz = nz;
@@ -674,7 +686,7 @@ int launch_sweep_x(sdfgpu_handle h, const int32_t* d_in, float* d_out, int64_t h
     a.max_scan = max_scan; a.far_flag = far_flag;
     (void)d_maxdsq;                             // maxima go to the slot array; the caller folds them (fold_slots)
     a.maxdsq = h->d_slots; a.status = d_status;
-    a.guard = h->guard;
+    a.guard = h->inflight.guard;
     return vb ? launch_march<3, true>(h, a, vec4, s) : launch_march<3, false>(h, a, vec4, s);
 }
 
@@ -698,6 +710,10 @@ struct DcExtra {                 // int32 plane fields instead of p16 + side tab
     uint32_t* fold_report = nullptr;
     uint32_t* fold_ticket = nullptr;
 };
+// The probes' fixed fractions (BuildOptions::far_thr holds the thresholds): an axis is far-field when more than 1 / kFarDen of the
+// probed voxels reach its threshold (y, x); the y sweep takes radius-8 windows when more than 1 / kMidDenY of them have d^2 >= kMidThrY.
+constexpr int kFarDen[2] = {5, 24};
+constexpr int kMidThrY = 16, kMidDenY = 24;
 struct DcDecide {                // a probe launch turns its counters into the tier decision itself (last workgroup)
     int stage = 0; bool dense_tried = false, handoff = false, window_choice = false;
 };
@@ -708,7 +724,7 @@ DcGeometry envelope_dc_geometry(const sdfgpu_context* h, int stage, int64_t nx, 
     DcGeometry g{};
     if (ny_full < 0) ny_full = ny;
     const int64_t L = stage == 2 ? ny : nx;
-    if (!h->envelope_dc || L < 1 || L > 2048 || nx * ny * nz >= (1ll << 31)) return g;
+    if (!h->opt.envelope_dc || L < 1 || L > 2048 || nx * ny * nz >= (1ll << 31)) return g;
     int B = 1;
     while ((1ll << B) < L) ++B;
     const int64_t finf = (nx - 1) * (nx - 1) + (ny_full - 1) * (ny_full - 1) + (nz - 1) * (nz - 1) + 1;   // > every real d^2
@@ -750,7 +766,7 @@ int launch_envelope(sdfgpu_handle h, int stage, const int16_t* d_in16, const int
             a.in_i32 = ex->in_i32; a.out_i32 = ex->out_i32; a.y_off = ex->y_off; a.i32_flag = ex->i32_flag;
             if (ex->ny_glob >= 0) a.ny_glob = ex->ny_glob;
             a.ran_flag = ex->ran_flag;
-            if (!probe_out) { a.row_bits = ex->row_bits; a.row_words = ex->row_words; a.plane_any = ex->plane_any; a.some_empty = h->d_small + 22; a.flat_on = h->flat_tiles; a.flat_score = h->d_small + 40; }
+            if (!probe_out) { a.row_bits = ex->row_bits; a.row_words = ex->row_words; a.plane_any = ex->plane_any; a.some_empty = h->d_small + 22; a.flat_on = h->opt.flat_tiles; a.flat_score = h->d_small + 40; }
             if (stage == 2) { a.bits = ex->bits; a.nzw = ex->nzw; }
             if (stage == 3 && ex->loop && ex->fold_ticket && !probe_out) {
                 a.fold_status = h->d_small; a.fold_result = ex->fold_result; a.fold_report = ex->fold_report; a.fold_ticket = ex->fold_ticket;
@@ -761,9 +777,9 @@ int launch_envelope(sdfgpu_handle h, int stage, const int16_t* d_in16, const int
         a.maxdsq = h->d_slots; a.guard = guard; a.guard_invert = guard_invert;
         if (ntiles > 0x7fffffffLL) return fail(h, SDFGPU_ERR_UNSUPPORTED_SIZE, "envelope grid too large");
         const int64_t all = ntiles;
-        if (probe_out && dec && h->probe_window) {
+        if (probe_out && dec && h->opt.probe_window) {
             // the window statistic (k_probe_window): thresholds up to 81 = windows up to radius 8
-            const int thr = h->far_thr[stage - 2], thr2 = stage == 2 ? h->mid_thr_y : 0, thr3 = stage == 2 ? h->far_thr[1] : 0;
+            const int thr = h->opt.far_thr[stage - 2], thr2 = stage == 2 ? kMidThrY : 0, thr3 = stage == 2 ? h->opt.far_thr[1] : 0;
             int W = 0;
             while ((W + 1) * (W + 1) < std::max(thr, std::max(thr2, thr3))) ++W;
             const bool handoff_in = ex && ex->i32_flag;                      // p16 shape: int32 values only behind the flag, which ends the probe
@@ -779,9 +795,9 @@ int launch_envelope(sdfgpu_handle h, int stage, const int16_t* d_in16, const int
                 if (pa.step > 0xffffff) pa.step = 0xffffff;                 // (the kernel hashes the offset inside a stretch in 24 bits)
                 pa.probe_out = probe_out; pa.guard = guard; pa.i32_flag = handoff_in ? ex->i32_flag : nullptr;
                 pa.decide_small = h->d_small; pa.decide_stage = dec->stage; pa.decide_dense_tried = dec->dense_tried ? 1 : 0;
-                pa.decide_force = h->force_env; pa.decide_den = h->far_den[dec->stage]; pa.decide_handoff = dec->handoff ? 1 : 0;
-                pa.decide_mid_den = (dec->stage == 0 && dec->window_choice) ? h->mid_den_y : 0;
-                pa.decide_xden = h->far_den[1];
+                pa.decide_force = h->opt.force_env; pa.decide_den = kFarDen[dec->stage]; pa.decide_handoff = dec->handoff ? 1 : 0;
+                pa.decide_mid_den = (dec->stage == 0 && dec->window_choice) ? kMidDenY : 0;
+                pa.decide_xden = kFarDen[1];
                 const unsigned nb = (pa.nsamples + 255u) / 256u;
                 if (stage == 2 && W <= 3) hipLaunchKernelGGL((k_probe_window<2, 3>), dim3(nb), dim3(256), 0, s, pa);
                 else if (stage == 2) hipLaunchKernelGGL((k_probe_window<2, 8>), dim3(nb), dim3(256), 0, s, pa);
@@ -793,15 +809,15 @@ int launch_envelope(sdfgpu_handle h, int stage, const int16_t* d_in16, const int
         }
         if (probe_out) {                                        // sample ~256 tiles spread over the grid, store nothing
             a.probe_stride = (int)std::max<int64_t>(1, std::min<int64_t>(64, ntiles / 256));
-            a.probe_thr = h->far_thr[stage - 2];
-            a.probe_thr2 = stage == 2 ? h->mid_thr_y : 0;
-            a.probe_thr3 = (stage == 2 && dec) ? h->far_thr[1] : 0;
+            a.probe_thr = h->opt.far_thr[stage - 2];
+            a.probe_thr2 = stage == 2 ? kMidThrY : 0;
+            a.probe_thr3 = (stage == 2 && dec) ? h->opt.far_thr[1] : 0;
             a.probe_out = probe_out;
             if (dec) {
                 a.decide_small = h->d_small; a.decide_stage = dec->stage; a.decide_dense_tried = dec->dense_tried ? 1 : 0;
-                a.decide_force = h->force_env; a.decide_den = h->far_den[dec->stage]; a.decide_handoff = dec->handoff ? 1 : 0;
-                a.decide_mid_den = (dec->stage == 0 && dec->window_choice) ? h->mid_den_y : 0;
-                a.decide_xden = h->far_den[1];
+                a.decide_force = h->opt.force_env; a.decide_den = kFarDen[dec->stage]; a.decide_handoff = dec->handoff ? 1 : 0;
+                a.decide_mid_den = (dec->stage == 0 && dec->window_choice) ? kMidDenY : 0;
+                a.decide_xden = kFarDen[1];
             }
             ntiles = (ntiles + a.probe_stride - 1) / a.probe_stride;
             while (ntiles > 0 && (ntiles - 1) * a.probe_stride + ((ntiles - 1) * 7) % a.probe_stride >= all) --ntiles;
@@ -823,13 +839,13 @@ int launch_envelope(sdfgpu_handle h, int stage, const int16_t* d_in16, const int
         a.ntiles = ntiles;
         // LOOP form: at most 2048 workgroups (a guarded exit costs 1.7 us up to there and grows with the grid), a multiple of 8
         // so that a workgroup's tiles stay on its XCD
-        const int64_t nwg = loop ? std::min<int64_t>(ntiles, h->standby_grid) : ntiles;
+        const int64_t nwg = loop ? std::min<int64_t>(ntiles, h->opt.standby_grid) : ntiles;
         // 512-voxel lines, vector loads, one tile per workgroup: the instances with the line's geometry as compile-time constants (option "dc_fixed")
-        const bool fixed512 = h->dc_fixed && a.L == 512 && vec && !loop && !big && a.B == 9 && a.pitch == 514 && a.M == 64 && a.h == 256;
-        const bool fixed1024 = h->dc_fixed && a.L == 1024 && vec && big && a.B == 10 && a.pitch == 1026 && a.M == 128 && a.h == 512;
+        const bool fixed512 = h->opt.dc_fixed && a.L == 512 && vec && !loop && !big && a.B == 9 && a.pitch == 514 && a.M == 64 && a.h == 256;
+        const bool fixed1024 = h->opt.dc_fixed && a.L == 1024 && vec && big && a.B == 10 && a.pitch == 1026 && a.M == 128 && a.h == 512;
         const int which = fixed512 ? 12 + (stage == 3 ? 1 : 0) : fixed1024 ? 14 + (stage == 3 ? 1 : 0) :
                           (stage == 3 ? 1 : 0) + (vec ? 2 : 0) + (loop ? 4 : 0) + (big ? 8 : 0);
-        if (stage == 3 && !probe_out) h->last_dc_x = which + 1;
+        if (stage == 3 && !probe_out) h->last.last_dc_x = which + 1;
         auto launch = [&](auto kern) -> int {
             // (the attribute is per kernel: raised once per instantiation, not on every launch -- ADVICE r3)
             if (lds > 64 * 1024 && !h->dc_attr_set[which]) {
@@ -866,17 +882,20 @@ int launch_envelope(sdfgpu_handle h, int stage, const int16_t* d_in16, const int
 
 int launch_decide(sdfgpu_handle h, int stage, bool dense_tried, hipStream_t s, bool handoff = false, bool window_choice = false);
 int launch_decide(sdfgpu_handle h, int stage, bool dense_tried, hipStream_t s, bool handoff, bool window_choice) {
-    hipLaunchKernelGGL(k_decide_tier, dim3(1), dim3(1), 0, s, h->d_small, stage, dense_tried ? 1 : 0, h->force_env,
-                       1, h->far_den[stage], handoff ? 1 : 0, (stage == 0 && window_choice) ? h->mid_den_y : 0);
+    hipLaunchKernelGGL(k_decide_tier, dim3(1), dim3(1), 0, s, h->d_small, stage, dense_tried ? 1 : 0, h->opt.force_env,
+                       1, kFarDen[stage], handoff ? 1 : 0, (stage == 0 && window_choice) ? kMidDenY : 0);
     HIP_TRY(h, hipGetLastError());
     return SDFGPU_OK;
 }
 
 // K0 + KD: pack to bits, then the bit-parallel ball kernel (sdfgpu_dense.hpp)
+constexpr int kBallLanes = 256;                   // lanes per workgroup of KD, KD3, KD6 and KF
+constexpr int kDenseMaxRowWords = 64;             // longest z-row the tuned dense kernels take, in 32-voxel words (DenseArgs::nzw)
+static_assert(kDenseMaxRowWords <= kBallLanes, "a ball-kernel tile holds at least one z-row: launch_ball_dense divides by kBallLanes / nzw");
 bool dense_eligible(const sdfgpu_context* h, int64_t nz, int vb) {
     const int64_t nzw = nz / 32;
     (void)vb;                                     // (the tuned ball kernel folds the virtual border itself)
-    return h->dense_on && (nz % 32) == 0 && nzw >= 1 && nzw <= 64 && (nzw & (nzw - 1)) == 0;
+    return h->opt.dense_on && (nz % 32) == 0 && nzw >= 1 && nzw <= kDenseMaxRowWords && (nzw & (nzw - 1)) == 0;
 }
 
 int launch_pack_bits(sdfgpu_handle h, const uint8_t* d_mask, const void* d_cells, size_t stride, size_t off, int unknown,
@@ -887,16 +906,8 @@ int launch_pack_bits(sdfgpu_handle h, const uint8_t* d_mask, const void* d_cells
                            ld, d_bits, n);
     } else if ((reinterpret_cast<uintptr_t>(d_mask) % 16) == 0) {
         const int64_t n16 = n / 16;
-        auto blocks = [&](int chunks) { const int64_t pb = (int64_t)kBlock * chunks; return dim3((unsigned)((n16 + pb - 1) / pb)); };
-        switch (h->pack_variant) {
-            case 1: hipLaunchKernelGGL((k_pack_bits_mask<1, false>), blocks(1), dim3(kBlock), 0, s, d_mask, d_bits, n16); break;
-            case 2: hipLaunchKernelGGL((k_pack_bits_mask<2, false>), blocks(2), dim3(kBlock), 0, s, d_mask, d_bits, n16); break;
-            case 3: hipLaunchKernelGGL((k_pack_bits_mask<8, false>), blocks(8), dim3(kBlock), 0, s, d_mask, d_bits, n16); break;
-            case 4: hipLaunchKernelGGL((k_pack_bits_mask<4, true>), blocks(4), dim3(kBlock), 0, s, d_mask, d_bits, n16); break;
-            case 5: hipLaunchKernelGGL((k_pack_bits_mask<1, true>), blocks(1), dim3(kBlock), 0, s, d_mask, d_bits, n16); break;
-            case 6: hipLaunchKernelGGL((k_pack_bits_mask<4, false>), blocks(4), dim3(kBlock), 0, s, d_mask, d_bits, n16); break;
-            default: hipLaunchKernelGGL((k_pack_bits_mask<4, true>), blocks(4), dim3(kBlock), 0, s, d_mask, d_bits, n16); break;
-        }
+        const int64_t pb = (int64_t)kBlock * 4;                     // 4 chunks of 16 voxels per lane
+        hipLaunchKernelGGL((k_pack_bits_mask<4, true>), dim3((unsigned)((n16 + pb - 1) / pb)), dim3(kBlock), 0, s, d_mask, d_bits, n16);
     } else {
         MaskLoader ld{d_mask};
         hipLaunchKernelGGL(k_pack_bits_generic<MaskLoader>, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
@@ -914,6 +925,10 @@ int fold_slots(sdfgpu_handle h, uint32_t* d_maxdsq, hipStream_t s, uint32_t* res
     return SDFGPU_OK;
 }
 
+// KD6 is for scenes with at most 1 / 8 of their voxels undecided behind KD3: Bernoulli p = 0.01 leaves 8 % (0.78 ms against the
+// far-field pair's 0.96), p = 0.007 17 % (1.07 ms against 0.97)
+constexpr int kShellBudgetDen = 8;
+
 int launch_ball_dense(sdfgpu_handle h, const uint32_t* d_bits, float* d_out, int64_t rows_x, int64_t out_lo, int64_t out_hi,
                       int64_t ny, int64_t nz, double resolution, uint32_t* d_maxdsq, uint32_t* d_uncert, hipStream_t s,
                       uint32_t* d_fix_needed = nullptr, bool early_out = false, int vb = 0, int64_t nx_glob = 0, int radius = 2,
@@ -927,9 +942,7 @@ int launch_ball_dense(sdfgpu_handle h, const uint32_t* d_bits, float* d_out, int
     a.log2_nzw = 0;
     while ((1 << a.log2_nzw) < a.nzw) ++a.log2_nzw;
     a.ny = (int)ny; a.rows_x = (int)rows_x; a.out_lo = (int)out_lo; a.out_hi = (int)out_hi;
-    int bd = h->ball_block > 0 ? h->ball_block : 256;
-    if (bd != 256 && bd != 512 && bd != 1024) bd = 256;
-    while (bd / a.nzw < 1) bd *= 2;
+    constexpr int bd = kBallLanes;                         // (every caller checks dense_eligible first: nzw <= kDenseMaxRowWords, 4 rows or more per tile)
     const int rows = bd / a.nzw;                           // tile rows per workgroup
     int best_tx = 1, best_ty = rows, best_cost = 1 << 30;
     for (int ty = 1; ty <= rows; ty *= 2) {                // smallest halo-inclusive footprint
@@ -948,13 +961,12 @@ int launch_ball_dense(sdfgpu_handle h, const uint32_t* d_bits, float* d_out, int
     for (int l = 0; l < 16; ++l) a.mag3[l] = l < 13 ? (float)(std::sqrt((double)level3_d2[l]) * resolution) : 0.0f;
     a.slots = h->d_slots; a.uncertified = d_uncert;
     a.reason = early_out ? h->d_small + 21 : nullptr;                // (whole builds: the context's status block; stage calls have none)
-    a.nt_store = h->nt_store;
     a.flip = radius == 3 ? 0 : flip;
     a.guard = d_guard;
     // KD3 gives up at once when a wave holds more undecided voxels than the stage behind it takes: KF's per-tile cap -- or, with
     // the shell pass in between (which turns words, not voxels, around and leaves KF what lies beyond d^2 = 36), three quarters
     // of the wave: the faces of a sparse noise grid, where a voxel sees a fraction of the ball, used to end the tier there
-    const bool shell = radius == 3 && h->shell_on && d_fix_needed && early_out;      // (whole builds: the status block carries the sample)
+    const bool shell = radius == 3 && h->opt.shell_on && d_fix_needed && early_out;      // (whole builds: the status block carries the sample)
     a.max_undecided = shell ? 1536 : kBall3MaxUndecided;
     a.und_sample = shell ? h->d_slots : nullptr;
     const int64_t gx = (ny + a.ty - 1) / a.ty, gy = (out_hi - out_lo + a.tx - 1) / a.tx;
@@ -968,11 +980,11 @@ int launch_ball_dense(sdfgpu_handle h, const uint32_t* d_bits, float* d_out, int
         // (the undecided bits of a STAGED fix-up stage live in the z field's storage, which the general pipeline only writes
         //  after KF has consumed them: a fresh context's first build does not pay a 17 MB allocation for a stage that a
         //  far-field scene leaves at once)
-        if (!h->unc_override) if (int rc = ensure(h, h->unc, (size_t)(out_hi - out_lo) * ny * a.nzw * 4, "undecided words")) return rc;
+        if (!h->inflight.unc_override) if (int rc = ensure(h, h->unc, (size_t)(out_hi - out_lo) * ny * a.nzw * 4, "undecided words")) return rc;
         uint32_t* tileflag = nullptr;
-        if (h->unc_override && h->unc_override_bytes >= (size_t)(out_hi - out_lo) * ny * a.nzw * 4 + 256 + tiles * 4) {
+        if (h->inflight.unc_override && h->inflight.unc_override_bytes >= (size_t)(out_hi - out_lo) * ny * a.nzw * 4 + 256 + tiles * 4) {
             // ... and so do its tile flags (behind the bits; cleared here: the storage is not ours between builds)
-            tileflag = h->unc_override + ((size_t)(out_hi - out_lo) * ny * a.nzw + 63) / 64 * 64;
+            tileflag = h->inflight.unc_override + ((size_t)(out_hi - out_lo) * ny * a.nzw + 63) / 64 * 64;
             HIP_TRY(h, hipMemsetAsync(tileflag, 0, tiles * 4, s));
         } else {
             if (h->tileflag.bytes < tiles * 4 || !h->tileflag.ptr) {
@@ -981,18 +993,16 @@ int launch_ball_dense(sdfgpu_handle h, const uint32_t* d_bits, float* d_out, int
             }
             tileflag = (uint32_t*)h->tileflag.ptr;
         }
-        a.unc = h->unc_override ? h->unc_override : (uint32_t*)h->unc.ptr; a.tileflag = tileflag; a.fix_needed = d_fix_needed;
+        a.unc = h->inflight.unc_override ? h->inflight.unc_override : (uint32_t*)h->unc.ptr; a.tileflag = tileflag; a.fix_needed = d_fix_needed;
     }
     const bool zinv = nz <= (int64_t)bd * 4;   // an expansion pass covers whole z-rows
     if (radius == 3) {
-        if (bd != 256 || vb) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "KD3: 256-lane tiles without virtual border only (internal)");
+        if (vb) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "KD3: grids without virtual border only (internal)");
         // nz = 512 (16 words per row, 4 x 4-row tiles): the instance with compile-time row pitch and halo width (option "dense3_fixed")
-        if (zinv && a.nzw == 16 && a.ty == 4 && a.tx == 4 && h->dense3_fixed) hipLaunchKernelGGL((k_ball_dense3<256, true, 16, 4>), grid, dim3(256), lds, s, a);
+        if (zinv && a.nzw == 16 && a.ty == 4 && a.tx == 4 && h->opt.dense3_fixed) hipLaunchKernelGGL((k_ball_dense3<256, true, 16, 4>), grid, dim3(256), lds, s, a);
         else if (zinv) hipLaunchKernelGGL((k_ball_dense3<256, true>), grid, dim3(256), lds, s, a);
         else hipLaunchKernelGGL((k_ball_dense3<256, false>), grid, dim3(256), lds, s, a);
     }
-    else if (bd == 1024) hipLaunchKernelGGL((k_ball_dense<1024, true>), grid, dim3(1024), lds, s, a);
-    else if (bd == 512) hipLaunchKernelGGL((k_ball_dense<512, true>), grid, dim3(512), lds, s, a);
     else if (zinv) hipLaunchKernelGGL((k_ball_dense<256, true>), grid, dim3(256), lds, s, a);
     else hipLaunchKernelGGL((k_ball_dense<256, false>), grid, dim3(256), lds, s, a);
     if (d_fix_needed) {
@@ -1009,16 +1019,16 @@ int launch_ball_dense(sdfgpu_handle h, const uint32_t* d_bits, float* d_out, int
         // KD6 (round 5): the bit-parallel shell pass 16 <= d^2 <= 36 over the words KD3 left undecided voxels in, in front of KF
         // (which then only sees what lies beyond d^2 = 36) -- sdfgpu_dense6.hpp.  Behind KD3 only: KD's undecided voxels start
         // at d^2 = 9, below the shell.
-        if (shell && bd == 256) {
+        if (shell) {
             ShellArgs sa{};
             sa.bits = d_bits; sa.out = d_out; sa.unc = a.unc; sa.tileflag = a.tileflag; sa.fix_needed = d_fix_needed;
             sa.uncertified = d_uncert;
-            // budget: 1 / shell_budget_den of the voxels undecided behind KD3 (the sample holds 1 / 16 of them; small grids: at least
+            // budget: 1 / kShellBudgetDen of the voxels undecided behind KD3 (the sample holds 1 / 16 of them; small grids: at least
             // one wave's worth)
-            const uint32_t budget = (uint32_t)std::max<int64_t>((out_hi - out_lo) * ny * nz / h->shell_budget_den / 16, 2048);
+            const uint32_t budget = (uint32_t)std::max<int64_t>((out_hi - out_lo) * ny * nz / kShellBudgetDen / 16, 2048);
             hipLaunchKernelGGL(k_shell_budget, dim3(1), dim3(kSlots), 0, s, h->d_slots, d_fix_needed, d_uncert, a.reason, budget);
             sa.nzw = a.nzw; sa.log2_nzw = a.log2_nzw; sa.ny = a.ny; sa.rows_x = a.rows_x; sa.out_lo = a.out_lo; sa.out_hi = a.out_hi;
-            sa.tx = a.tx; sa.ty = a.ty; sa.log2_ty = a.log2_ty; sa.resolution = resolution; sa.slots = h->d_slots; sa.min_words = h->shell_min_words;
+            sa.tx = a.tx; sa.ty = a.ty; sa.log2_ty = a.log2_ty; sa.resolution = resolution; sa.slots = h->d_slots; sa.min_words = h->opt.shell_min_words;
             const size_t slds = shell_lds_bytes(256, a.tx, a.ty, a.nzw);
             if (slds <= 64 * 1024) {
                 const dim3 sgrid((unsigned)((gx + kShellGroup - 1) / kShellGroup), (unsigned)gy);       // kShellGroup tiles (along y) per workgroup
@@ -1034,9 +1044,7 @@ int launch_ball_dense(sdfgpu_handle h, const uint32_t* d_bits, float* d_out, int
         f.slots = h->d_slots; f.uncertified = d_uncert; f.reason = a.reason;
         const size_t flds = (size_t)(2 * kFixOrderPad + kFixCap + 4) * 4 +
                             (size_t)(a.tx + 2 * kFixTileR) * (a.ty + 2 * kFixTileR) * (a.nzw + 2) * 4;
-        if (bd == 1024) hipLaunchKernelGGL(k_ball_fixup<1024>, grid, dim3(1024), flds, s, f);
-        else if (bd == 512) hipLaunchKernelGGL(k_ball_fixup<512>, grid, dim3(512), flds, s, f);
-        else hipLaunchKernelGGL(k_ball_fixup<256>, grid, dim3(256), flds, s, f);
+        hipLaunchKernelGGL(k_ball_fixup<256>, grid, dim3(256), flds, s, f);
     }
     HIP_TRY(h, hipGetLastError());
     return SDFGPU_OK;
@@ -1087,8 +1095,8 @@ int build_device_impl(sdfgpu_handle h, const uint8_t* d_filled, const void* d_ce
         return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cell_stride/occupancy_offset must be 4-byte aligned and in range");
     HIP_TRY(h, hipSetDevice(h->device));
     canonical_dims(nx, ny, nz);
-    h->last_dc_x = 0;
-    h->last_lines_tiered = false;
+    h->last.last_dc_x = 0;
+    h->last.last_lines_tiered = false;
     const int64_t n = nx * ny * nz;
     const bool p16 = plane16_eligible(h, ny, nz);
     if (int rc = ensure(h, h->yzfield, (size_t)n * 4, "int32 plane field / side table")) return rc;          // int32 plane field / side table
@@ -1097,7 +1105,7 @@ int build_device_impl(sdfgpu_handle h, const uint8_t* d_filled, const void* d_ce
     int32_t* zy_side = p16 ? (int32_t*)h->yzfield.ptr : nullptr;
     bool dense = dense_eligible(h, nz, vb) && ny <= 0x7fffffff;
     // shapes / modes the tuned dense kernels do not take go through their generic forms (any nz, virtual border)
-    const bool dense_generic = !dense && h->dense_on && h->dense_generic_on && nx <= 0x7fffffff && ny <= 0x7fffffff;
+    const bool dense_generic = !dense && h->opt.dense_on && h->opt.dense_generic_on && nx <= 0x7fffffff && ny <= 0x7fffffff;
     dense = dense || dense_generic;
     // Learn from an earlier build on this handle, if its status block has arrived (never a wait), and plan the dense tier of
     // this one: sdfgpu_policy.hpp.  Every outcome is exact; the policy only decides whether and in which form the DENSE tier is
@@ -1115,12 +1123,12 @@ int build_device_impl(sdfgpu_handle h, const uint8_t* d_filled, const void* d_ce
         h->far_pending = false;
         h->far.consume_report(h->h_far[4] != 0, h->h_far[5] != 0);
     }
-    const DensePlan plan = h->pol.plan(dense, dense_generic, nz / 32 <= 256 && h->ball_block <= 256, vb != 0);
+    const DensePlan plan = h->pol.plan(dense, dense_generic, nz / 32 <= 256, vb != 0);
     dense = plan.dense;
     // bounded marching scans + the far-field kernel behind them, on every shape that kernel takes; other shapes (lines beyond
     // 2048, keys beyond 32 bits) keep unbounded marching scans.  Shapes without the 16-bit plane field (nz % 4 != 0) hand
     // exact int32 plane values from the y to the x sweep.
-    const bool far_ok = h->envelope_on && far_geometry_ok(h, 2, nx, ny, nz) && far_geometry_ok(h, 3, nx, ny, nz);
+    const bool far_ok = h->opt.envelope_on && far_geometry_ok(h, 2, nx, ny, nz) && far_geometry_ok(h, 3, nx, ny, nz);
     const bool envelope = far_ok && !(h->pol.expect_dense && dense);
     // Stand-by behind a TRUSTED dense tier (round 4).  It nearly always exits on its guard, so it must be
     // few launches with small grids -- and since the scene of a stream can change under the handle (dense -> far-field), it
@@ -1130,7 +1138,7 @@ int build_device_impl(sdfgpu_handle h, const uint8_t* d_filled, const void* d_ce
     // K12 + K3/16 pair it replaces (a third one, a guarded K1, cost the dense-certified step 2.6 us: 0.1405 -> 0.1431 ms),
     // O(L log L) per line on any input (the old pair ran unbounded outward scans: tens of ms on the build in which a
     // dense scene turned into the two-box cloud).
-    const bool standby = far_ok && h->standby_far && h->pol.expect_dense && dense && !h->fused_always;
+    const bool standby = far_ok && h->opt.standby_far && h->pol.expect_dense && dense && !h->opt.fused_always;
     // Device-side tier selection: the marching-vs-far-field choice of each axis is made INSIDE this build from a probe of the
     // sweep's own input, so a fresh context (the reference's API is one-shot: collision_map.hpp:680-712 builds and returns)
     // never runs a sweep that is thrown away, and a handle's latency does not depend on what it built before.
@@ -1139,10 +1147,10 @@ int build_device_impl(sdfgpu_handle h, const uint8_t* d_filled, const void* d_ce
     // again; everywhere else K1 + K2 (rows from the int16 z field) scan much faster than the fused kernel
     // recomputes, and only they can hand a far-field y sweep to the envelope kernel.
     const bool fused = !standby && !d_cells && fused_zy_eligible(h, d_filled, zy_out, nz) &&
-                       (h->fused_always || (dense && h->pol.expect_dense) || (!envelope && !dense));
+                       (h->opt.fused_always || (dense && h->pol.expect_dense) || (!envelope && !dense));
     const bool select = dev_select && !fused;
     // (see far_predict: the handle's recent builds were far-field on both axes -- or the caller forces it)
-    const bool predicted = h->far.plan(select, h->force_env >= 0);
+    const bool predicted = h->far.plan(select, h->opt.force_env >= 0);
     if (!fused && !standby) if (int rc = ensure(h, h->zfield, (size_t)n * 2, "z field")) return rc;
     // status block [0..7]: maxima, status, uncertified, far flags, fix_needed.  Normally still zero from the previous
     // build's fold kernel; cleared here after a build that failed half-way (or before the first one)
@@ -1189,14 +1197,14 @@ int build_device_impl(sdfgpu_handle h, const uint8_t* d_filled, const void* d_ce
     bool cur_fix_mode = false, cur_dense3 = false, cur_staged = false;
     const uint32_t* dense_bits = nullptr;                       // the bit field the tuned dense kernels (and the stand-by y sweep) read
     uint8_t* row_any = nullptr;                                 // plane sparsity: one byte per z row, one per x-plane behind them (predicted far-field builds)
-    h->last_dense = dense;
-    h->guard = nullptr;
+    h->last.last_dense = dense;
+    h->inflight.guard = nullptr;
     if (dense && dense_generic) {
         HIP_TRY(h, mark(1));
         if (int rc = launch_dense_generic(h, d_filled, d_cells, stride, off, unknown, nx, ny, nz, resolution, vb, d_out,
                                           h->d_small + 3, s, d_bits_in)) return rc;
         launched_since_mark = true;
-        h->guard = h->d_small + 3;
+        h->inflight.guard = h->d_small + 3;
     } else if (dense) {
         if (d_bits_in && (reinterpret_cast<uintptr_t>(d_bits_in) % 16) == 0) {
             dense_bits = d_bits_in;                             // (nz % 32 == 0: the caller's linear bit field IS the [x][y][nz / 32] field K0 writes)
@@ -1220,39 +1228,39 @@ int build_device_impl(sdfgpu_handle h, const uint8_t* d_filled, const void* d_ce
         cur_staged = plan.staged;
         int flip = 0;
         if (!cur_dense3) {                                      // (KD; see ball_serpentine)
-            flip = (h->ball_serpentine && d_out == h->serp_out && n == h->serp_n) ? !h->serp_flip : 0;
+            flip = (h->opt.ball_serpentine && d_out == h->serp_out && n == h->serp_n) ? !h->serp_flip : 0;
             h->serp_out = d_out; h->serp_n = n; h->serp_flip = flip;
         }
         if (int rc = launch_ball_dense(h, dense_bits, d_out, nx, 0, nx, ny, nz, resolution, h->d_small,
                                        cur_staged ? h->d_small + 20 : h->d_small + 3, s,
                                        (fix || cur_dense3) ? h->d_small + 6 : nullptr, true, vb, nx, cur_dense3 ? 3 : 2, nullptr, flip)) return rc;
         if (cur_staged) {
-            h->unc_override = (!fused && h->zfield.ptr && h->zfield.bytes >= (size_t)n / 8) ? (uint32_t*)h->zfield.ptr : nullptr;
-            h->unc_override_bytes = h->unc_override ? h->zfield.bytes : 0;
+            h->inflight.unc_override = (!fused && h->zfield.ptr && h->zfield.bytes >= (size_t)n / 8) ? (uint32_t*)h->zfield.ptr : nullptr;
+            h->inflight.unc_override_bytes = h->inflight.unc_override ? h->zfield.bytes : 0;
             const int rc = launch_ball_dense(h, dense_bits, d_out, nx, 0, nx, ny, nz, resolution, h->d_small,
                                              h->d_small + 3, s, h->d_small + 6, true, 0, nx, 3, h->d_small + 20);
-            h->unc_override = nullptr;
+            h->inflight.unc_override = nullptr;
             if (rc) return rc;
         }
         launched_since_mark = true;
-        h->guard = h->d_small + 3;
+        h->inflight.guard = h->d_small + 3;
         cur_fix_mode = fix || cur_dense3;
     } else {
         HIP_TRY(h, mark(1));
     }
-    h->last_dense3 = cur_dense3;
-    h->last_staged = cur_staged;
+    h->last.last_dense3 = cur_dense3;
+    h->last.last_staged = cur_staged;
     HIP_TRY(h, mark(2));
-    h->last_fused = fused;
-    h->last_standby = standby;
-    h->last_predicted = predicted;
-    h->last_plane16 = p16;
-    h->far_y = (envelope && !fused) ? h->d_small + 4 : nullptr;
-    h->scan_y = h->scan_x = kScanExpectNear;
+    h->last.last_fused = fused;
+    h->last.last_standby = standby;
+    h->last.last_predicted = predicted;
+    h->last.last_plane16 = p16;
+    h->inflight.far_y = (envelope && !fused) ? h->d_small + 4 : nullptr;
+    h->inflight.scan_y = h->inflight.scan_x = kScanExpectNear;
     if (!fused && !standby) {                                   // (the stand-by pair takes its z distances from the bit field)
         // a build that goes straight to the far-field pair lets the z sweep mark the x-planes that hold a filled voxel at all: a sensed
         // scene leaves most planes without one, and the pair skips them (y sweep: the planes' tiles; x sweep: their row loads)
-        if (predicted && h->plane_skip && nx >= 8 && ny <= 1024 && z_wave16_shape(h, nz) && !d_cells &&
+        if (predicted && h->opt.plane_skip && nx >= 8 && ny <= 1024 && z_wave16_shape(h, nz) && !d_cells &&
             (d_bits_in || (reinterpret_cast<uintptr_t>(d_filled) % 16) == 0)) {
             const size_t o_bits = ((size_t)(nx * ny + nx) + 255) & ~(size_t)255;
             if (int rc = ensure(h, h->planebits, o_bits + (size_t)nx * ((ny + 31) / 32) * 4, "row / x-plane occupancy flags")) return rc;
@@ -1262,15 +1270,15 @@ int build_device_impl(sdfgpu_handle h, const uint8_t* d_filled, const void* d_ce
                                     (int16_t*)h->zfield.ptr, s, d_bits_in, row_any)) return rc;
         launched_since_mark = true;
     }
-    h->last_plane_skip = row_any != nullptr;
-    h->last_dims[0] = nx; h->last_dims[1] = ny; h->last_dims[2] = nz;
+    h->last.last_plane_skip = row_any != nullptr;
+    h->last.last_dims[0] = nx; h->last.last_dims[1] = ny; h->last.last_dims[2] = nz;
     HIP_TRY(h, mark(3));
     // y sweep: marching (bounded scan, may raise far_y) + guarded envelope, or the envelope kernel alone
-    const uint32_t* const general_guard = h->guard;           // nullptr, or "the dense tier left voxels undecided"
+    const uint32_t* const general_guard = h->inflight.guard;           // nullptr, or "the dense tier left voxels undecided"
     // Both axes far-field (decided by the y probe): the y sweep hands the x sweep exact int32 values in the side-table
     // buffer (used whole) instead of p16 + side table -- one store / one load per voxel, no saturation handling, and the
     // x probe is skipped.  d_small[7] carries the choice on the device.
-    const bool handoff = select && p16 && h->i32_handoff;        // (shapes without the 16-bit plane field hand int32 values over anyway)
+    const bool handoff = select && p16 && h->opt.i32_handoff;        // (shapes without the 16-bit plane field hand int32 values over anyway)
     DcExtra hand2{}, hand3{};
     hand2.out_i32 = (int32_t*)h->yzfield.ptr; hand2.i32_flag = h->d_small + 7;
     hand3.in_i32 = (const int32_t*)h->yzfield.ptr; hand3.i32_flag = h->d_small + 7;
@@ -1279,18 +1287,18 @@ int build_device_impl(sdfgpu_handle h, const uint8_t* d_filled, const void* d_ce
     plain3.in_i32 = (const int32_t*)h->yzfield.ptr;
     const DcExtra* const ex2 = !p16 ? &plain2 : handoff ? &hand2 : nullptr;
     const DcExtra* const ex3 = !p16 ? &plain3 : handoff ? &hand3 : nullptr;
-    // (the radius-8 y window exists for 4-voxel lanes only; a forced window leaves nothing to choose)
-    const bool window_choice = select && (nz % 4) == 0 && h->march_h != 8 && h->mid_den_y > 0;
+    // (the radius-8 y window exists for 4-voxel lanes only)
+    const bool window_choice = select && (nz % 4) == 0;
     auto decide = [&](int stage) -> int { return launch_decide(h, stage, dense, s, handoff, window_choice); };   // probe counters -> guard words
     DcExtra sb2{}, sb3{};                                       // stand-by pair: int32 hand-off unconditionally, LOOP form, self-reporting
     sb2.out_i32 = (int32_t*)h->yzfield.ptr; sb2.loop = true; sb2.ran_flag = h->d_small + 4;
     sb2.bits = dense_bits ? dense_bits : (const uint32_t*)h->bits.ptr; sb2.nzw = (int)((nz + 31) / 32);
     sb3.in_i32 = (const int32_t*)h->yzfield.ptr; sb3.loop = true; sb3.ran_flag = h->d_small + 5;
     // (moved up: the stand-by x sweep does the fold itself and needs to know where the report goes)
-    const bool report = h->envelope_on && h->h_flags_dev && !h->flags_pending && dense;
+    const bool report = h->opt.envelope_on && h->h_flags_dev && !h->flags_pending && dense;
     bool folded = false;
     if (standby) {
-        if (h->standby_fold) {
+        if (h->opt.standby_fold) {
             sb3.fold_result = h->d_result; sb3.fold_report = report ? h->h_flags_dev : nullptr; sb3.fold_ticket = h->d_small + 23;
             folded = true;
         }
@@ -1331,19 +1339,19 @@ int build_device_impl(sdfgpu_handle h, const uint8_t* d_filled, const void* d_ce
     if (select) {
         // probe + decision in one launch (the probe's last workgroup decides); a forced tier needs no probe
         DcDecide dy; dy.stage = 0; dy.dense_tried = dense; dy.handoff = handoff; dy.window_choice = window_choice;
-        if (h->force_env < 0) {
+        if (h->opt.force_env < 0) {
             if (int rc = launch_envelope(h, 2, (const int16_t*)h->zfield.ptr, nullptr, h->plane16.ptr, (int32_t*)h->yzfield.ptr,
                                          nx, ny, nz, resolution, vb, h->d_small, general_guard, s, 0, h->d_small + 12,
                                          !p16 ? &plain2 : nullptr, &dy)) return rc;
         } else if (int rc = decide(0)) return rc;
         // marching y sweep: general pipeline needed AND near-field; the probe also picks the window (radius 3 / radius 8)
-        h->guard = h->d_small + 8;
+        h->inflight.guard = h->d_small + 8;
         if (int rc = launch_sweep_y(h, (const int16_t*)h->zfield.ptr, zy_out, zy_side, nx, ny, nz, s, window_choice ? 3 : 0)) return rc;
         if (window_choice) {
-            h->guard = h->d_small + 9;
+            h->inflight.guard = h->d_small + 9;
             if (int rc = launch_sweep_y(h, (const int16_t*)h->zfield.ptr, zy_out, zy_side, nx, ny, nz, s, 8)) return rc;
         }
-        h->guard = general_guard;
+        h->inflight.guard = general_guard;
         launched_since_mark = true;
     } else if (fused) {
         if (int rc = launch_sweep_zy_fused(h, d_filled, zy_out, zy_side, nx, ny, nz, s)) return rc;
@@ -1360,23 +1368,23 @@ int build_device_impl(sdfgpu_handle h, const uint8_t* d_filled, const void* d_ce
     }
     HIP_TRY(h, mark(5));
     // x sweep: same choice
-    if (!envelope || fused) h->far_y = nullptr;
-    else h->far_y = h->d_small + 4;             // (K3/16 raises far_y + 1 = far_x)
+    if (!envelope || fused) h->inflight.far_y = nullptr;
+    else h->inflight.far_y = h->d_small + 4;             // (K3/16 raises far_y + 1 = far_x)
     if (select) {
         DcDecide dx; dx.stage = 1; dx.dense_tried = dense; dx.handoff = handoff; dx.window_choice = window_choice;
-        if (h->force_env < 0) {
+        if (h->opt.force_env < 0) {
             if (int rc = launch_envelope(h, 3, p16 ? (const int16_t*)h->plane16.ptr : nullptr, p16 ? (const int32_t*)h->yzfield.ptr : nullptr, d_out, nullptr,
                                          nx, ny, nz, resolution, vb, h->d_small, general_guard, s, 0, h->d_small + 12, ex3, &dx)) return rc;
         } else if (int rc = decide(1)) return rc;
-        h->guard = h->d_small + 10;
+        h->inflight.guard = h->d_small + 10;
         if (p16) {
             if (int rc = launch_sweep_x16(h, (const int16_t*)h->plane16.ptr, (const int32_t*)h->yzfield.ptr, d_out, 0, nx, 0,
                                           0, nx, ny, nz, 0, 0, 0, nx, resolution, vb, h->d_small, h->d_small + 2, s)) return rc;
         } else {
             if (int rc = launch_sweep_x(h, (const int32_t*)h->yzfield.ptr, d_out, 0, nx, 0, ny, nz, 0, 0, 0, nx,
-                                        resolution, vb, h->d_small, h->d_small + 2, s, 0, -1, h->scan_x, h->far_y + 1)) return rc;
+                                        resolution, vb, h->d_small, h->d_small + 2, s, 0, -1, h->inflight.scan_x, h->inflight.far_y + 1)) return rc;
         }
-        h->guard = general_guard;
+        h->inflight.guard = general_guard;
         launched_since_mark = true;
     } else if (p16) {
         if (int rc = launch_sweep_x16(h, (const int16_t*)h->plane16.ptr, (const int32_t*)h->yzfield.ptr, d_out, 0, nx, 0,
@@ -1415,8 +1423,8 @@ int build_device_impl(sdfgpu_handle h, const uint8_t* d_filled, const void* d_ce
         h->far_pending = true;
     }
     h->small_clean = true;
-    h->guard = nullptr;
-    h->far_y = nullptr;
+    h->inflight.guard = nullptr;
+    h->inflight.far_y = nullptr;
     if (report) {
         HIP_TRY(h, hipEventRecord(h->flags_ev, s));
         h->flags_pending = true;
@@ -1427,10 +1435,10 @@ int build_device_impl(sdfgpu_handle h, const uint8_t* d_filled, const void* d_ce
         for (auto e : ev) h->events.push_back(e);
     }
     HIP_TRY(h, h->build_order.record(s));
-    h->last_stream = s;
-    h->last_resolution = resolution;
-    h->last_n = n;
-    h->have_result = true;
+    h->last.last_stream = s;
+    h->last.last_resolution = resolution;
+    h->last.last_n = n;
+    h->last.have_result = true;
     return SDFGPU_OK;
 }
 
@@ -1675,7 +1683,7 @@ int build_host_impl(sdfgpu_handle h, const uint8_t* filled, const void* cells, s
     // chunk, and 1/8 B per voxel crosses PCIe (16 MiB at 512^3 instead of 128 MiB of mask or 1 GiB of COLLISION_CELL records);
     // k_unpack_bits_mask spreads them into the byte mask on the device.  Same predicate as the device classifier
     // (pack_cells_bits); "host_pack" = 0 keeps the upload-and-classify-on-device path (device-resident cells always take it).
-    const bool packed = !bits_in && (h->host_pack == 2 || (h->host_pack == 1 && in_bytes >= kPinMin));
+    const bool packed = !bits_in && (h->opt.host_pack == 2 || (h->opt.host_pack == 1 && in_bytes >= kPinMin));
     if (!packed && !bits_in) if (int rc = ensure(h, h->stage_in, in_bytes, "input staging")) return rc;
     if (!d_out_user) if (int rc = ensure(h, h->stage_out, (size_t)n * 4, "output staging")) return rc;
     float* const d_out = d_out_user ? d_out_user : (float*)h->stage_out.ptr;
@@ -1915,7 +1923,7 @@ int check_resample_args(sdfgpu_handle h, const void* src, size_t cell_bytes, int
     memcpy(a.fill, fill_cell, cell_bytes);
     a.cell_bytes = (int)cell_bytes;
     a.winner_bytes = resample_winner_bytes(a.n_src);
-    a.plain_atomics = h->rs_plain_atomics;
+    a.plain_atomics = h->opt.rs_plain_atomics;
     return SDFGPU_OK;
 }
 
@@ -1930,12 +1938,12 @@ int resample_impl(sdfgpu_handle h, ResampleArgs& a, uint64_t* out_written, hipSt
     unsigned long long* const counter =
         reinterpret_cast<unsigned long long*>(static_cast<char*>(h->rs_scratch.ptr) + resample_counter_offset(a.n_dst, a.winner_bytes));
     a.written = out_written ? counter : nullptr;
-    if (h->rs_timing) {
+    if (h->opt.rs_timing) {
         for (hipEvent_t& e : h->rs_time_ev) if (!e) HIP_TRY(h, hipEventCreate(&e));
         HIP_TRY(h, hipEventRecord(h->rs_time_ev[0], st));
     }
-    const hipError_t le = resample_launch(a, st, h->rs_timing ? h->rs_time_ev[1] : nullptr);
-    if (h->rs_timing) h->rs_timed = le == hipSuccess && hipEventRecord(h->rs_time_ev[2], st) == hipSuccess;
+    const hipError_t le = resample_launch(a, st, h->opt.rs_timing ? h->rs_time_ev[1] : nullptr);
+    if (h->opt.rs_timing) h->rs_timed = le == hipSuccess && hipEventRecord(h->rs_time_ev[2], st) == hipSuccess;
     (void)h->rs_order.record(st);                       // (also behind a failed launch: what it did enqueue is ordered)
     HIP_TRY(h, le);
     if (out_written) {
@@ -2029,7 +2037,7 @@ int with_staged_points(sdfgpu_handle h, const double* points, int64_t n_points, 
     char* const base = (char*)h->query_stage.ptr;
     char* const dev[3] = {out[0] ? base + off[0] : nullptr, out[1] ? base + off[1] : nullptr, out[2] ? base + off[2] : nullptr};
     // Round 5: the null stream of the context's device, ordered behind this handle's last build by its event --
-    // not h->last_stream, which is a handle of the CALLER's (an earlier *_device build's stream may have been destroyed since).
+    // not h->last.last_stream, which is a handle of the CALLER's (an earlier *_device build's stream may have been destroyed since).
     // A field produced ELSEWHERE (another handle, a caller's kernel) is ordered by the null stream's implicit synchronisation only
     // when its stream is a blocking one: producers on hipStreamNonBlocking streams (PyTorch's are) must be synchronised by the caller
     // before this call -- include/sdfgpu.h says so.
@@ -2253,21 +2261,21 @@ int sdfgpu_extrema_from_dsq(uint32_t max_dsq_free, uint32_t max_dsq_filled, doub
 
 int sdfgpu_get_extrema(sdfgpu_handle h, double* out_max, double* out_min) {
     if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-    if (!h->have_result) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "no build has been issued on this handle");
+    if (!h->last.have_result) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "no build has been issued on this handle");
     HIP_TRY(h, hipSetDevice(h->device));
     uint32_t v[4];
     // (the build's own event, not its stream: the stream is the caller's and may be gone by now -- ADVICE r4)
     HIP_TRY(h, h->build_order.host_wait());
     HIP_TRY(h, hipMemcpy(v, h->d_result, sizeof v, hipMemcpyDeviceToHost));
-    return sdfgpu_extrema_from_dsq(v[0], v[1], h->last_resolution, out_max, out_min);
+    return sdfgpu_extrema_from_dsq(v[0], v[1], h->last.last_resolution, out_max, out_min);
 }
 
 int sdfgpu_sweep_zy_tiered_device(sdfgpu_handle h, const uint8_t* d_filled, int64_t nxs, int64_t ny, int64_t nz,
                                   int32_t* d_plane_dsq, uint32_t* d_far, void* stream) {
     return rz_wrap(h, stream, [&]() -> int {
         if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-        h->guard = nullptr;
-        h->far_y = nullptr;
+        h->inflight.guard = nullptr;
+        h->inflight.far_y = nullptr;
         if (!d_filled || !d_plane_dsq) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null device pointer");
         if (int rc = check_dims(h, nxs, ny, nz)) return rc;
         HIP_TRY(h, hipSetDevice(h->device));
@@ -2277,7 +2285,7 @@ int sdfgpu_sweep_zy_tiered_device(sdfgpu_handle h, const uint8_t* d_filled, int6
         //  cross-stream ordering -- waits for the handle's previous work when that ran on another stream, and is waited for)
         HIP_TRY(h, h->build_order.wait(s));
         StreamOrder::RecordAtExit order_end{h->build_order, s};
-        const bool tiered = h->envelope_on && far_geometry_ok(h, 2, nxs, ny, nz) &&
+        const bool tiered = h->opt.envelope_on && far_geometry_ok(h, 2, nxs, ny, nz) &&
                             (nz % 4) == 0 && (reinterpret_cast<uintptr_t>(d_plane_dsq) % 16) == 0;
         if (!tiered) {
             if (fused_zy_eligible(h, d_filled, d_plane_dsq, nz)) return launch_sweep_zy_fused(h, d_filled, d_plane_dsq, nullptr, nxs, ny, nz, s);
@@ -2293,16 +2301,16 @@ int sdfgpu_sweep_zy_tiered_device(sdfgpu_handle h, const uint8_t* d_filled, int6
         DcExtra ex;
         ex.out_i32 = d_plane_dsq;
         DcDecide dy; dy.stage = 0;
-        if (h->force_env < 0) {
+        if (h->opt.force_env < 0) {
             if (int rc = launch_envelope(h, 2, (const int16_t*)h->zfield.ptr, nullptr, nullptr, nullptr, nxs, ny, nz, 1.0, 0,
                                          h->d_small, nullptr, s, 0, h->d_small + 12, &ex, &dy)) return rc;
         } else if (int rc = launch_decide(h, 0, false, s)) return rc;
-        h->guard = h->d_small + 8;
-        h->far_y = h->d_small + 4;
-        h->scan_y = kScanExpectNear;
+        h->inflight.guard = h->d_small + 8;
+        h->inflight.far_y = h->d_small + 4;
+        h->inflight.scan_y = kScanExpectNear;
         int rc = launch_sweep_y(h, (const int16_t*)h->zfield.ptr, d_plane_dsq, nullptr, nxs, ny, nz, s);
-        h->guard = nullptr;
-        h->far_y = nullptr;
+        h->inflight.guard = nullptr;
+        h->inflight.far_y = nullptr;
         if (rc) return rc;
         if (int rc2 = launch_envelope(h, 2, (const int16_t*)h->zfield.ptr, nullptr, nullptr, nullptr, nxs, ny, nz, 1.0, 0,
                                       h->d_small, h->d_small + 4, s, 0, nullptr, &ex)) return rc2;
@@ -2332,36 +2340,36 @@ int sdfgpu_sweep_x_lines_device(sdfgpu_handle h, const int32_t* d_plane_dsq, int
         if (int rc = check_dims(h, nx, ny_global, nz)) return rc;
         HIP_TRY(h, hipSetDevice(h->device));
         hipStream_t s = (hipStream_t)stream;
-        h->guard = nullptr;
-        h->far_y = nullptr;
+        h->inflight.guard = nullptr;
+        h->inflight.far_y = nullptr;
         HIP_TRY(h, h->build_order.wait(s));
         StreamOrder::RecordAtExit order_end{h->build_order, s};
-        const bool tiered = h->envelope_on && far_geometry_ok(h, 3, nx, nys, nz, ny_global) &&
+        const bool tiered = h->opt.envelope_on && far_geometry_ok(h, 3, nx, nys, nz, ny_global) &&
                             (reinterpret_cast<uintptr_t>(d_plane_dsq) % 16) == 0;
-        h->last_dc_x = 0;
-        h->last_lines_tiered = tiered;
+        h->last.last_dc_x = 0;
+        h->last.last_lines_tiered = tiered;
         if (!tiered) {
             if (int rc = launch_sweep_x(h, d_plane_dsq, d_out_sdf, 0, nx, 0, nys, nz, 0, 0, 0, nx, resolution, add_virtual_border,
                                         d_maxdsq, nullptr, s, y_global, ny_global)) return rc;
-            return h->defer_fold ? SDFGPU_OK : fold_slots(h, d_maxdsq, s);
+            return h->opt.defer_fold ? SDFGPU_OK : fold_slots(h, d_maxdsq, s);
         }
         HIP_TRY(h, hipMemsetAsync(h->d_small, 0, 128, s));
         h->small_clean = false;
         DcExtra ex;
         ex.in_i32 = d_plane_dsq; ex.y_off = y_global; ex.ny_glob = ny_global;
         DcDecide dx; dx.stage = 1;
-        if (h->force_env < 0) {
+        if (h->opt.force_env < 0) {
             if (int rc = launch_envelope(h, 3, nullptr, nullptr, d_out_sdf, nullptr, nx, nys, nz, resolution, add_virtual_border,
                                          h->d_small, nullptr, s, 0, h->d_small + 12, &ex, &dx)) return rc;
         } else if (int rc = launch_decide(h, 1, false, s)) return rc;
-        h->guard = h->d_small + 10;
+        h->inflight.guard = h->d_small + 10;
         int rc = launch_sweep_x(h, d_plane_dsq, d_out_sdf, 0, nx, 0, nys, nz, 0, 0, 0, nx, resolution, add_virtual_border,
                                 d_maxdsq, nullptr, s, y_global, ny_global, kScanExpectNear, h->d_small + 5);
-        h->guard = nullptr;
+        h->inflight.guard = nullptr;
         if (rc) return rc;
         if (int rc2 = launch_envelope(h, 3, nullptr, nullptr, d_out_sdf, nullptr, nx, nys, nz, resolution, add_virtual_border,
                                       h->d_small, h->d_small + 5, s, 0, nullptr, &ex)) return rc2;
-        if (!h->defer_fold) if (int rc3 = fold_slots(h, d_maxdsq, s)) return rc3;
+        if (!h->opt.defer_fold) if (int rc3 = fold_slots(h, d_maxdsq, s)) return rc3;
         HIP_TRY(h, hipMemsetAsync(h->d_small, 0, 128, s));
         h->small_clean = true;
         return SDFGPU_OK;
@@ -2379,15 +2387,15 @@ int sdfgpu_sweep_x_device(sdfgpu_handle h, const int32_t* d_plane_dsq, int64_t h
         if (halo_lo < 0 || halo_hi < 0 || x_global < 0 || x_global + nxs > nx_global)
             return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "inconsistent slab geometry");
         if (int rc = check_resolution(h, resolution)) return rc;
-        h->guard = nullptr;
-        h->far_y = nullptr;
+        h->inflight.guard = nullptr;
+        h->inflight.far_y = nullptr;
         if (int rc = check_dims(h, halo_lo + nxs + halo_hi, ny, nz)) return rc;
         if (int rc = check_dims(h, nx_global, ny, nz)) return rc;
         HIP_TRY(h, hipSetDevice(h->device));
         if (int rc = launch_sweep_x(h, d_plane_dsq, d_out_sdf, halo_lo, nxs, halo_hi, ny, nz, lo_truncated, hi_truncated,
                                     x_global, nx_global, resolution, add_virtual_border, d_maxdsq, d_status,
                                     (hipStream_t)stream)) return rc;
-        return h->defer_fold ? SDFGPU_OK : fold_slots(h, d_maxdsq, (hipStream_t)stream);
+        return h->opt.defer_fold ? SDFGPU_OK : fold_slots(h, d_maxdsq, (hipStream_t)stream);
     });
 }
 
@@ -2415,7 +2423,7 @@ int sdfgpu_dense_ball_device(sdfgpu_handle h, const uint32_t* d_bits, int64_t ro
         HIP_TRY(h, hipSetDevice(h->device));
         if (int rc = launch_ball_dense(h, d_bits, d_out_sdf, rows_x, out_lo, out_hi, ny, nz, resolution, d_maxdsq,
                                        d_uncertified, (hipStream_t)stream)) return rc;
-        return h->defer_fold ? SDFGPU_OK : fold_slots(h, d_maxdsq, (hipStream_t)stream);
+        return h->opt.defer_fold ? SDFGPU_OK : fold_slots(h, d_maxdsq, (hipStream_t)stream);
     });
 }
 
@@ -2615,9 +2623,9 @@ int build_batch_impl(sdfgpu_handle h, const uint8_t* d_filled, const BatchTagged
         HIP_TRY(h, batch_launch(a, s, &launches));
         h->batch_launches = launches;
     } else {
-        const bool had = h->have_result;
-        const double keep_res = h->last_resolution;
-        const int64_t keep_n = h->last_n;
+        const bool had = h->last.have_result;
+        const double keep_res = h->last.last_resolution;
+        const int64_t keep_n = h->last.last_n;
         uint32_t* keep = ext + 2 * batch;
         HIP_TRY(h, h->build_order.wait(s));
         HIP_TRY(h, hipMemcpyAsync(keep, h->d_result, kStatusWords * 4, hipMemcpyDeviceToDevice, s));
@@ -2634,7 +2642,7 @@ int build_batch_impl(sdfgpu_handle h, const uint8_t* d_filled, const BatchTagged
             HIP_TRY(h, hipMemcpyAsync(ext + 2 * b, h->d_result, 8, hipMemcpyDeviceToDevice, s));
         }
         HIP_TRY(h, hipMemcpyAsync(h->d_result, keep, kStatusWords * 4, hipMemcpyDeviceToDevice, s));
-        h->have_result = had; h->last_resolution = keep_res; h->last_n = keep_n;
+        h->last.have_result = had; h->last.last_resolution = keep_res; h->last.last_n = keep_n;
         h->batch_launches = -1;
     }
     HIP_TRY(h, h->build_order.record(s));
@@ -2995,15 +3003,15 @@ int sdfgpu_redzone_check(sdfgpu_handle h, void* stream) {
 
 int sdfgpu_debug_copy_zsweep(sdfgpu_handle h, int16_t* out_host, int64_t n) {
     if (!h || !out_host) return SDFGPU_ERR_INVALID_ARGUMENT;
-    if (!h->have_result || n > h->last_n) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "no matching build");
-    if (h->last_fused) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "the last build fused the z sweep into the y sweep: no z field exists");
-    if (h->last_standby) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "the last build's stand-by pair takes its z distances from the bit field: no z field exists");
+    if (!h->last.have_result || n > h->last.last_n) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "no matching build");
+    if (h->last.last_fused) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "the last build fused the z sweep into the y sweep: no z field exists");
+    if (h->last.last_standby) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "the last build's stand-by pair takes its z distances from the bit field: no z field exists");
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, h->build_order.host_wait());
     HIP_TRY(h, hipMemcpy(out_host, h->zfield.ptr, (size_t)n * 2, hipMemcpyDeviceToHost));
-    if (h->last_plane_skip && h->planebits.ptr && n == h->last_dims[0] * h->last_dims[1] * h->last_dims[2]) {
+    if (h->last.last_plane_skip && h->planebits.ptr && n == h->last.last_dims[0] * h->last.last_dims[1] * h->last.last_dims[2]) {
         // the z sweep of a build that went straight to the far-field pair does not write rows without a filled voxel
-        const int64_t nrows = h->last_dims[0] * h->last_dims[1], nz = h->last_dims[2];
+        const int64_t nrows = h->last.last_dims[0] * h->last.last_dims[1], nz = h->last.last_dims[2];
         std::vector<uint8_t> ra((size_t)nrows);
         HIP_TRY(h, hipMemcpy(ra.data(), h->planebits.ptr, ra.size(), hipMemcpyDeviceToHost));
         for (int64_t r = 0; r < nrows; ++r)
@@ -3014,21 +3022,21 @@ int sdfgpu_debug_copy_zsweep(sdfgpu_handle h, int16_t* out_host, int64_t n) {
 
 int sdfgpu_debug_copy_yzsweep(sdfgpu_handle h, int32_t* out_host, int64_t n) {
     if (!h || !out_host) return SDFGPU_ERR_INVALID_ARGUMENT;
-    if (!h->have_result || n > h->last_n) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "no matching build");
+    if (!h->last.have_result || n > h->last.last_n) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "no matching build");
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, h->build_order.host_wait());
     HIP_TRY(h, hipMemcpy(out_host, h->yzfield.ptr, (size_t)n * 4, hipMemcpyDeviceToHost));
-    if (h->last_plane_skip && h->planebits.ptr && n == h->last_dims[0] * h->last_dims[1] * h->last_dims[2]) {
+    if (h->last.last_plane_skip && h->planebits.ptr && n == h->last.last_dims[0] * h->last.last_dims[1] * h->last.last_dims[2]) {
         // the y sweep skipped the x-planes without a filled voxel: every voxel of such a plane is "free, no filled voxel in the plane"
-        std::vector<uint8_t> pa((size_t)h->last_dims[0]);
-        HIP_TRY(h, hipMemcpy(pa.data(), (const uint8_t*)h->planebits.ptr + h->last_dims[0] * h->last_dims[1], pa.size(), hipMemcpyDeviceToHost));
-        const int64_t plane = h->last_dims[1] * h->last_dims[2];
-        for (int64_t x = 0; x < h->last_dims[0]; ++x)
+        std::vector<uint8_t> pa((size_t)h->last.last_dims[0]);
+        HIP_TRY(h, hipMemcpy(pa.data(), (const uint8_t*)h->planebits.ptr + h->last.last_dims[0] * h->last.last_dims[1], pa.size(), hipMemcpyDeviceToHost));
+        const int64_t plane = h->last.last_dims[1] * h->last.last_dims[2];
+        for (int64_t x = 0; x < h->last.last_dims[0]; ++x)
             if (!pa[(size_t)x]) std::fill(out_host + x * plane, out_host + (x + 1) * plane, (int32_t)kInf32);
     }
     uint32_t st[8] = {0, 0, 0, 0, 0, 0, 0, 0};                 // status block of the last build ([7]: int32 hand-off used)
     HIP_TRY(h, hipMemcpy(st, h->d_result, sizeof st, hipMemcpyDeviceToHost));
-    if (h->last_plane16 && st[7] == 0u && !h->last_predicted) {
+    if (h->last.last_plane16 && st[7] == 0u && !h->last.last_predicted) {
         // 16-bit pipeline: the int32 buffer is the side table (valid only for saturated groups of 4)
         std::vector<int16_t> p16((size_t)n);
         HIP_TRY(h, hipMemcpy(p16.data(), h->plane16.ptr, (size_t)n * 2, hipMemcpyDeviceToHost));
@@ -3072,38 +3080,46 @@ int sdfgpu_get_stage_times(sdfgpu_handle h, double* out_ms_sum, int64_t* out_bui
 int sdfgpu_set_option(sdfgpu_handle h, const char* name, int value) {
     if (!h || !name) return SDFGPU_ERR_INVALID_ARGUMENT;
     const std::string n(name);
-    if (n == "fused_zy") { h->fused_zy = value != 0; h->fused_always = value == 2; }
-    else if (n == "rows_per_chunk_y") h->tune_ty = value;
-    else if (n == "rows_per_chunk_x") h->tune_tx = value;
-    else if (n == "rows_per_chunk_zy") h->tune_tzy = value;
-    else if (n == "fused_window") h->fused_h = value;
-    else if (n == "plane16") h->plane16_on = value != 0;
-    else if (n == "y16") h->y16_on = value != 0;
-    else if (n == "probe_window") h->probe_window = value != 0;
-    else if (n == "z_wave") h->z_wave_on = value != 0;
-    else if (n == "dense") h->dense_on = value != 0;
-    else if (n == "dense_generic") h->dense_generic_on = value != 0;
-    else if (n == "envelope") h->envelope_on = value != 0;
-    else if (n == "envelope_dc") h->envelope_dc = value != 0;
-    else if (n == "i32_handoff") h->i32_handoff = value != 0;
-    else if (n == "standby_far") h->standby_far = value != 0;
-    else if (n == "host_pack") h->host_pack = (value >= 0 && value <= 2) ? value : 1;
+    BuildOptions& o = h->opt;
+    // tier selection
+    if (n == "dense") o.dense_on = value != 0;
+    else if (n == "dense_generic") o.dense_generic_on = value != 0;
+    else if (n == "dense_retry") { h->pol.dense_retry = value; h->pol.dense_skip = 0; h->pol.dense_backoff = 0; }
+    else if (n == "envelope") o.envelope_on = value != 0;
+    else if (n == "envelope_dc") o.envelope_dc = value != 0;
+    else if (n == "envelope_mode") { h->flags_pending = false; o.force_env = value != 0 ? 1 : -1; }
     else if (n == "far_predict") h->far.set_mode(value);
-    else if (n == "standby_fold") h->standby_fold = value != 0;
-    else if (n == "standby_grid") h->standby_grid = value >= 32 ? value : 1024;
-    else if (n == "expect_dense") h->pol.expect_dense = value != 0;      // tests: put the handle into the "dense tier trusted" state
-    else if (n == "pack_variant") h->pack_variant = value;
-    else if (n == "nt_store") h->nt_store = value;
-    else if (n == "ball_block") h->ball_block = value;
-    else if (n == "defer_fold") h->defer_fold = value != 0;
+    else if (n == "far_threshold_y") o.far_thr[0] = value;
+    else if (n == "far_threshold_x") o.far_thr[1] = value;
+    else if (n == "probe_window") o.probe_window = value != 0;
     else if (n == "policy_reset") { h->flags_pending = false; h->pol.reset(); h->far.reset(); h->flat_score_reset = true; }
-    else if (n == "fixup") { h->pol.fixup_on = value != 0; h->pol.fix_mode = false; h->pol.dense3_mode = false; }
-    else if (n == "dense3") { h->pol.dense3_on = value != 0; h->pol.dense3_mode = false; }
+    else if (n == "expect_dense") h->pol.expect_dense = value != 0;      // tests: put the handle into the "dense tier trusted" state
+    else if (n == "fixup_mode") h->pol.fix_mode = value != 0;
     else if (n == "dense3_mode") h->pol.dense3_mode = value != 0;
-    else if (n == "dense_shell") h->shell_on = value != 0;
-    else if (n == "dc_fixed") h->dc_fixed = value != 0;
-    else if (n == "plane_skip") h->plane_skip = value != 0;
-    else if (n == "flat_tiles") h->flat_tiles = value < 0 ? 0 : value > 2 ? 2 : value;
+    // dense tier
+    else if (n == "dense3") { h->pol.dense3_on = value != 0; h->pol.dense3_mode = false; }
+    else if (n == "dense3_staged") h->pol.dense3_staged = value != 0;
+    else if (n == "dense3_fixed") o.dense3_fixed = value != 0;
+    else if (n == "dense_shell") o.shell_on = value != 0;
+    else if (n == "shell_min_words") o.shell_min_words = value >= 0 ? value : kShellMinWords;
+    else if (n == "standby_far") o.standby_far = value != 0;
+    else if (n == "standby_fold") o.standby_fold = value != 0;
+    else if (n == "standby_grid") o.standby_grid = value >= 32 ? value : 1024;
+    else if (n == "ball_serpentine") o.ball_serpentine = value != 0;
+    // sweeps
+    else if (n == "fused_zy") { o.fused_zy = value != 0; o.fused_always = value == 2; }
+    else if (n == "fused_window") o.fused_h = value;
+    else if (n == "plane16") o.plane16_on = value != 0;
+    else if (n == "z_wave") o.z_wave_on = value != 0;
+    else if (n == "x16_voxels_per_lane") o.x16_v = value;
+    else if (n == "x16_window") o.x16_h = value;
+    else if (n == "i32_handoff") o.i32_handoff = value != 0;
+    else if (n == "dc_fixed") o.dc_fixed = value != 0;
+    else if (n == "plane_skip") o.plane_skip = value != 0;
+    else if (n == "flat_tiles") o.flat_tiles = value < 0 ? 0 : value > 2 ? 2 : value;
+    // host side / debugging
+    else if (n == "host_pack") o.host_pack = (value >= 0 && value <= 2) ? value : 1;
+    else if (n == "defer_fold") o.defer_fold = value != 0;
     else if (n == "redzone") {
         // from now on: every buffer the context holds is released (and comes back with -- or without -- zones when it is next needed);
         // the status block and the slots are replaced at once
@@ -3124,43 +3140,26 @@ int sdfgpu_set_option(sdfgpu_handle h, const char* name, int value) {
         HIP_TRY(h, hipMemset(h->d_small, 0, 512));
         h->d_result = h->d_small + 64;
         h->small_clean = true;
-        h->have_result = false;
+        h->last.have_result = false;
         h->flags_pending = h->far_pending = false;
     }
-    else if (n == "dense3_fixed") h->dense3_fixed = value != 0;
-    else if (n == "resample_plain_atomics") h->rs_plain_atomics = value != 0;
-    else if (n == "resample_timing") { h->rs_timing = value != 0; h->rs_timed = false; }
-    else if (n == "ball_serpentine") h->ball_serpentine = value != 0;
-    else if (n == "shell_min_words") h->shell_min_words = value >= 0 ? value : kShellMinWords;
-    else if (n == "shell_budget_den") h->shell_budget_den = value >= 1 ? value : 8;
-    else if (n == "dense3_staged") h->pol.dense3_staged = value != 0;
-    else if (n == "fixup_mode") h->pol.fix_mode = value != 0;
-    else if (n == "dense_retry") { h->pol.dense_retry = value; h->pol.dense_skip = 0; h->pol.dense_backoff = 0; }
-    else if (n == "envelope_mode") { h->flags_pending = false; h->force_env = value != 0 ? 1 : -1; }
-    else if (n == "far_threshold_y") h->far_thr[0] = value;
-    else if (n == "far_threshold_x") h->far_thr[1] = value;
-    else if (n == "far_fraction_den_y") h->far_den[0] = value > 0 ? value : 8;
-    else if (n == "far_fraction_den_x") h->far_den[1] = value > 0 ? value : 24;
-    else if (n == "x16_voxels_per_lane") h->x16_v = value;
-    else if (n == "x16_window") h->x16_h = value;
-    else if (n == "march_window") h->march_h = value == 8 ? 8 : 3;
-    else if (n == "mid_threshold_y") h->mid_thr_y = value;
-    else if (n == "mid_fraction_den_y") h->mid_den_y = value;
+    else if (n == "resample_plain_atomics") o.rs_plain_atomics = value != 0;
+    else if (n == "resample_timing") { o.rs_timing = value != 0; h->rs_timed = false; }
     else return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "unknown option '%s'", name);
     return SDFGPU_OK;
 }
 
 int sdfgpu_last_build_info(sdfgpu_handle h, int* out_fused_zy) {
     if (!h || !out_fused_zy) return SDFGPU_ERR_INVALID_ARGUMENT;
-    *out_fused_zy = (h->last_fused ? 1 : 0) | (h->last_plane16 ? 2 : 0) | (h->last_dense ? 4 : 0) | (h->last_standby ? 8 : 0) |
-                    (h->last_dense3 ? 16 : 0) | (h->last_staged ? 32 : 0) | (h->last_predicted ? 64 : 0) |
-                    (h->last_lines_tiered ? 128 : 0) | ((h->last_dc_x & 31) << 8);
+    *out_fused_zy = (h->last.last_fused ? 1 : 0) | (h->last.last_plane16 ? 2 : 0) | (h->last.last_dense ? 4 : 0) | (h->last.last_standby ? 8 : 0) |
+                    (h->last.last_dense3 ? 16 : 0) | (h->last.last_staged ? 32 : 0) | (h->last.last_predicted ? 64 : 0) |
+                    (h->last.last_lines_tiered ? 128 : 0) | ((h->last.last_dc_x & 31) << 8);
     return SDFGPU_OK;
 }
 
 int sdfgpu_last_dense_certified(sdfgpu_handle h, int* out_certified) {
     if (!h || !out_certified) return SDFGPU_ERR_INVALID_ARGUMENT;
-    if (!h->have_result) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "no build has been issued on this handle");
+    if (!h->last.have_result) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "no build has been issued on this handle");
     HIP_TRY(h, hipSetDevice(h->device));
     uint32_t v[8];
     // (the build's own event, not its stream: the stream is the caller's and may be gone by now -- ADVICE r4)
@@ -3169,7 +3168,7 @@ int sdfgpu_last_dense_certified(sdfgpu_handle h, int* out_certified) {
     // bit 0: dense kernel decided everything; bit 1 / 2: the y / x sweep was redone by the envelope kernel
     uint32_t why = 0;
     HIP_TRY(h, hipMemcpy(&why, h->d_result + 21, sizeof why, hipMemcpyDeviceToHost));
-    *out_certified = ((h->last_dense && v[3] == 0) ? 1 : 0) | (v[4] ? 2 : 0) | (v[5] ? 4 : 0) | (int)((why & 0xffu) << 8);
+    *out_certified = ((h->last.last_dense && v[3] == 0) ? 1 : 0) | (v[4] ? 2 : 0) | (v[5] ? 4 : 0) | (int)((why & 0xffu) << 8);
     return SDFGPU_OK;
 }
 
@@ -3186,8 +3185,8 @@ int sdfgpu_debug_flat_habit(sdfgpu_handle h, int* out_score, int* out_gate) {
 
 int sdfgpu_set_tuning(sdfgpu_handle h, int rows_per_chunk_y, int rows_per_chunk_x) {
     if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-    h->tune_ty = rows_per_chunk_y;
-    h->tune_tx = rows_per_chunk_x;
+    h->opt.tune_ty = rows_per_chunk_y;
+    h->opt.tune_tx = rows_per_chunk_x;
     return SDFGPU_OK;
 }
 

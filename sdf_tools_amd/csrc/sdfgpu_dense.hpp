@@ -134,7 +134,6 @@ struct DenseArgs {
     // axes with more than one cell): inside the ball only b = 1 and b = 2 can bind, folded into levels 0 and 3
     int vb;
     int nx_glob;            // x extent of the whole grid (buffer plane 0 = grid plane 0 in this mode)
-    int nt_store;           // write the output with non-temporal stores (it is never re-read here)
     int flip;               // KD only: walk the tiles in the opposite order (whole builds that rewrite the previous build's buffer)
     const uint32_t* guard;  // KD3 only: non-null = run iff *guard != 0 (the staged fix-up stage behind KD in the same build)
     uint32_t* und_sample;   // KD3 only: nullptr, or the slot array: every 16th wave adds its undecided voxels to word 2 of a slot -- a 1 / 16
@@ -398,8 +397,7 @@ __global__ __launch_bounds__(BD) void k_ball_dense(const DenseArgs a) {
                 } else {
                     dst = reinterpret_cast<f4v*>(tile_out + (uint32_t)((((int)__umul24(txx, a.ny) + tyy) << lgz) + z) * 4u);
                 }
-                if (a.nt_store) __builtin_nontemporal_store(ov, dst);
-                else *dst = ov;
+                *dst = ov;
             }
         }
     };

@@ -283,8 +283,7 @@ __global__ __launch_bounds__(BD) void k_ball_dense3(const DenseArgs a) {
                 } else {
                     dst = reinterpret_cast<f4v*>(tile_out + (uint32_t)((((int)__umul24(txx, a.ny) + tyy) << lgz) + z) * 4u);
                 }
-                if (a.nt_store) __builtin_nontemporal_store(ov, dst);
-                else *dst = ov;
+                *dst = ov;
             }
         }
     };

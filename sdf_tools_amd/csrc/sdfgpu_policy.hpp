@@ -59,7 +59,6 @@ struct DensePlan {
 
 struct DensePolicy {
     // ---- options (sdfgpu_set_option) ----
-    int fixup_on = 1;             // fix-up kernel behind the dense ball kernel (almost-dense scenes)
     int dense3_on = 1;            // KD3 (ball kernel with |offset| <= 3) in KD's place whenever the fix-up kernel runs
     bool dense3_mode = false;     // KD3 + KF with every dense build (tests)
     int dense3_staged = 1;        // a build that does not expect KD to decide the scene carries KD3 + KF behind KD
@@ -91,7 +90,7 @@ struct DensePolicy {
         expect_dense = !general_ran && (!via_fix || fix_trust >= 4);
         // almost dense (the ball kernel left voxels undecided): first the fix-up stage; only if that cannot certify the scene
         // either are the dense kernels paused
-        if (prev.dense && fixup_on && !prev.generic) {
+        if (prev.dense && !prev.generic) {
             if (!prev.fix_mode) { fix_mode = prev.staged ? kd_uncertified : uncertified; fix_clean = 0; }   // KD alone could not
             else if (uncertified) fix_mode = false;                                 // KF could not certify it either
             else {                                                                  // keep the stage while it is needed: left
@@ -101,7 +100,7 @@ struct DensePolicy {
         }
         // dense attempted, not certified, nothing further to escalate to: pause the dense kernels (0.13 ms wasted per attempt
         // at 512^3) for dense_retry - 1 builds, twice as long (+1) after every failed probe
-        if (prev.dense && uncertified && dense_retry > 0 && (prev.fix_mode || prev.staged || !fixup_on || prev.generic)) {
+        if (prev.dense && uncertified && dense_retry > 0 && (prev.fix_mode || prev.staged || prev.generic)) {
             dense_backoff = dense_backoff ? std::min(255, 2 * dense_backoff + 1) : dense_retry - 1;
             dense_skip = dense_backoff;
         }
@@ -124,8 +123,8 @@ struct DensePolicy {
         if (dense && !generic) {
             // fix-up mode: undecided voxels go to KF, which raises `uncertified` only for what it cannot decide either
             // (with a virtual border KF stays out: a voxel it would finish may still be bound by b >= 3)
-            p.fix = fixup_on && fix_mode && !vb;
-            const bool d3_ok = dense3_on && fixup_on && !vb && d3_shape_ok;
+            p.fix = fix_mode && !vb;
+            const bool d3_ok = dense3_on && !vb && d3_shape_ok;
             p.dense3 = d3_ok && (p.fix || dense3_mode);
             // A build that has no reason to expect that KD decides the scene (a fresh context: the reference API is one-shot;
             // or the build after a failure) carries the fix-up stage behind KD in the SAME build, guarded on KD's verdict
