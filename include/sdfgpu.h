@@ -17,6 +17,10 @@
  *   - plain pointers and sizes only; no C++/torch types cross this boundary
  *   - voxel layout: index = x*ny*nz + y*nz + z (z fastest), the reference's
  *     VoxelGrid layout (src/sdf_tools/sdf.cpp:241-245, utils_3d.py:71-73)
+ *   - a device pointer needs the alignment of its element type only (uint8_t* none; float*, int32_t*, uint32_t* and cell
+ *     records 4 bytes; a double gradient 8): 16-byte alignment only selects faster kernels, never another result, and a
+ *     stage call (sdfgpu_dense_ball_device, sdfgpu_slab_dense_phase) whose bit planes or field are off 16 bytes goes
+ *     through copies in the handle's scratch
  *   - every function returns SDFGPU_OK (0) or a negative sdfgpu_status;
  *     nothing throws; sdfgpu_last_error() gives the message for the handle
  *   - a handle is bound to one GPU; use one handle per host thread

@@ -107,10 +107,12 @@ struct ContextBuffers {
     DeviceBuffer batch_gscale;  // GradScale [batch] of sdfgpu_gradient_batch_device
     DeviceBuffer planebits;  // row_any [nx * ny] bytes | plane_any [nx] bytes | row_bits [nx][ceil(ny / 32)] words (k_sweep_z_wave16, k_pack_row_flags, EnvDcArgs)
     DeviceBuffer rs_scratch; // sdfgpu_resample_cells*: one winner word per result cell, the counter (sdfgpu_resample.hpp)
+    DeviceBuffer ball_bits;  // sdfgpu_dense_ball_device / sdfgpu_slab_dense_phase: copy of a caller's bit planes that are off 16 bytes
+    DeviceBuffer ball_out;   // ... and the field of such a call while the caller's is off 16 bytes (launch_ball_dense)
     DeviceBuffer* begin() { return &zfield; }
     DeviceBuffer* end() { return begin() + sizeof(ContextBuffers) / sizeof(DeviceBuffer); }
 };
-static_assert(sizeof(ContextBuffers) == 27 * sizeof(DeviceBuffer), "ContextBuffers holds DeviceBuffer members only");
+static_assert(sizeof(ContextBuffers) == 29 * sizeof(DeviceBuffer), "ContextBuffers holds DeviceBuffer members only");
 
 // What sdfgpu_set_option and sdfgpu_set_tuning write and a build only reads (include/sdfgpu.h has the table).  The defaults here are
 // the documented ones.
@@ -934,6 +936,23 @@ int launch_ball_dense(sdfgpu_handle h, const uint32_t* d_bits, float* d_out, int
                       uint32_t* d_fix_needed = nullptr, bool early_out = false, int vb = 0, int64_t nx_glob = 0, int radius = 2,
                       const uint32_t* d_guard = nullptr, int flip = 0) {
     const int R = radius == 3 ? kBall3R : kBallR;                   // 3: KD3 (sdfgpu_dense3.hpp; whole-grid builds without virtual border only)
+    // The ball kernels stage bit rows with 16-byte loads and store 4 floats per lane.  Whole builds come here with the library's own
+    // bit field and a 16-byte-aligned field (build_device_impl); the stage entry points pass the caller's pointers, which need
+    // element alignment only (sdfgpu.h "Conventions"): planes off 16 bytes are copied into scratch first, and a field off 16 bytes
+    // is built in scratch and copied out behind the last kernel.  Both copies are on `s`.
+    float* const d_out_caller = d_out;
+    const size_t out_bytes = (size_t)(out_hi - out_lo) * (size_t)ny * (size_t)nz * 4;
+    const bool out_staged = (reinterpret_cast<uintptr_t>(d_out) % 16) != 0;
+    if (out_staged) {
+        if (int rc = ensure(h, h->ball_out, out_bytes, "dense stage field (caller's is off 16 bytes)")) return rc;
+        d_out = (float*)h->ball_out.ptr;
+    }
+    if ((reinterpret_cast<uintptr_t>(d_bits) % 16) != 0) {
+        const size_t bits_bytes = (size_t)rows_x * (size_t)ny * (size_t)(nz / 32) * 4;
+        if (int rc = ensure(h, h->ball_bits, bits_bytes, "dense stage bit planes (caller's are off 16 bytes)")) return rc;
+        HIP_TRY(h, hipMemcpyAsync(h->ball_bits.ptr, d_bits, bits_bytes, hipMemcpyDeviceToDevice, s));
+        d_bits = (const uint32_t*)h->ball_bits.ptr;
+    }
     DenseArgs a{};
     a.early_out = early_out ? 1 : 0;
     a.vb = vb; a.nx_glob = (int)nx_glob;
@@ -1047,6 +1066,7 @@ int launch_ball_dense(sdfgpu_handle h, const uint32_t* d_bits, float* d_out, int
         hipLaunchKernelGGL(k_ball_fixup<256>, grid, dim3(256), flds, s, f);
     }
     HIP_TRY(h, hipGetLastError());
+    if (out_staged) HIP_TRY(h, hipMemcpyAsync(d_out_caller, d_out, out_bytes, hipMemcpyDeviceToDevice, s));
     return SDFGPU_OK;
 }
 
@@ -1098,12 +1118,16 @@ int build_device_impl(sdfgpu_handle h, const uint8_t* d_filled, const void* d_ce
     h->last.last_dc_x = 0;
     h->last.last_lines_tiered = false;
     const int64_t n = nx * ny * nz;
-    const bool p16 = plane16_eligible(h, ny, nz);
+    // (the caller's pointers need element alignment only, sdfgpu.h "Conventions": K3/16 and the tuned ball kernels store 16 bytes
+    //  per lane, so a field off that alignment takes the int32 plane field -- launch_sweep_x tests the pointer itself -- and the
+    //  generic dense kernel, which store floats)
+    const bool out16 = (reinterpret_cast<uintptr_t>(d_out) % 16) == 0;
+    const bool p16 = plane16_eligible(h, ny, nz) && out16;
     if (int rc = ensure(h, h->yzfield, (size_t)n * 4, "int32 plane field / side table")) return rc;          // int32 plane field / side table
     if (p16) if (int rc = ensure(h, h->plane16, (size_t)n * 2, "16-bit plane field")) return rc;
     void* zy_out = p16 ? h->plane16.ptr : h->yzfield.ptr;
     int32_t* zy_side = p16 ? (int32_t*)h->yzfield.ptr : nullptr;
-    bool dense = dense_eligible(h, nz, vb) && ny <= 0x7fffffff;
+    bool dense = dense_eligible(h, nz, vb) && ny <= 0x7fffffff && out16;
     // shapes / modes the tuned dense kernels do not take go through their generic forms (any nz, virtual border)
     const bool dense_generic = !dense && h->opt.dense_on && h->opt.dense_generic_on && nx <= 0x7fffffff && ny <= 0x7fffffff;
     dense = dense || dense_generic;
@@ -2288,6 +2312,7 @@ int sdfgpu_sweep_zy_tiered_device(sdfgpu_handle h, const uint8_t* d_filled, int6
         const bool tiered = h->opt.envelope_on && far_geometry_ok(h, 2, nxs, ny, nz) &&
                             (nz % 4) == 0 && (reinterpret_cast<uintptr_t>(d_plane_dsq) % 16) == 0;
         if (!tiered) {
+            if (d_far) HIP_TRY(h, hipMemsetAsync(d_far, 0, 4, s));           // (no probe ran: "else to 0", sdfgpu.h)
             if (fused_zy_eligible(h, d_filled, d_plane_dsq, nz)) return launch_sweep_zy_fused(h, d_filled, d_plane_dsq, nullptr, nxs, ny, nz, s);
             if (int rc = ensure(h, h->zfield, (size_t)n * 2, "z field")) return rc;
             if (int rc = launch_sweep_z(h, d_filled, nullptr, 0, 0, 0, nxs, ny, nz, (int16_t*)h->zfield.ptr, s)) return rc;

@@ -20,6 +20,9 @@ import analysis_scenes as AS  # noqa: E402
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
 seed = int(sys.argv[2]) if len(sys.argv) > 2 else 0
 rng = np.random.default_rng(seed)
+# where the guard and bits modes put their buffers relative to a 16-byte boundary: a generator of its own, so that the scenes and
+# options of a seed stay the ones they were before the shifts were drawn
+shift_rng = np.random.default_rng([seed, 0xA119])
 ctx = capi.SdfGpu(0)
 VERBOSE = bool(os.environ.get("FUZZ_VERBOSE"))           # print every scene's shape and options before its build (to find a crash)
 if VERBOSE:
@@ -156,6 +159,7 @@ while time.time() - t0 < budget:
     # sdfgpu_device_malloc buffer used here carries canaries that each call checks.
     mode = str(rng.choice(["host", "guard", "guard", "bits", "multi", "rz_out"]))
     values_bad = None                                   # rz_out: what the gradient / query value check found
+    placed = ""                                         # guard / bits: where the buffers sat (printed with a failure)
     if os.environ.get("FUZZ_GUARD") and mode == "host":
         mode = "guard"
     if mode == "multi" and (shape[0] < 4 or vb and rng.random() < 0.5):
@@ -210,17 +214,21 @@ while time.time() - t0 < budget:
         import torch
         nvox = int(m.size)
         g = ((max(4096, 8 * shape[1] * shape[2]) + 3) // 4) * 4
-        buf = torch.full((g + nvox + g,), -12345.0, dtype=torch.float32, device="cuda")
+        # the field 0, 4, 8 or 12 bytes past a 16-byte boundary (every second scene: at one), the bit field 0 .. 3 words past one
+        o = int(shift_rng.choice([0, 1, 2, 3])) if shift_rng.random() < 0.5 else 0
+        buf = torch.full((g + nvox + g + 3,), -12345.0, dtype=torch.float32, device="cuda")
         words = capi.pack_bits_host(m).view(np.int32)
-        db = torch.zeros(words.size + 1, dtype=torch.int32, device="cuda")
+        db = torch.zeros(words.size + 3, dtype=torch.int32, device="cuda")
         sh = int(rng.integers(0, 2))               # (a field that is only 4-byte aligned takes the device copy)
+        sh += 2 * int(shift_rng.integers(0, 2))
+        placed = "bits +%d B, field +%d B" % (4 * sh, 4 * o)
         db[sh:sh + words.size] = torch.from_numpy(words).cuda()
-        ctx.build_bits_device(db.data_ptr() + 4 * sh, shape, buf.data_ptr() + 4 * g, res, vb, torch.cuda.current_stream().cuda_stream)
+        ctx.build_bits_device(db.data_ptr() + 4 * sh, shape, buf.data_ptr() + 4 * (g + o), res, vb, torch.cuda.current_stream().cuda_stream)
         torch.cuda.synchronize()
         ext = ctx.get_extrema()
-        got = buf[g:g + nvox].cpu().numpy().reshape(shape)
-        if not bool((buf[:g] == -12345.0).all().item()) or not bool((buf[g + nvox:] == -12345.0).all().item()):
-            print("GUARD BAND WRITTEN (bits in) shape", shape, "kind", kind, "res", res, "vb", vb)
+        got = buf[g + o:g + o + nvox].cpu().numpy().reshape(shape)
+        if not bool((buf[:g + o] == -12345.0).all().item()) or not bool((buf[g + o + nvox:] == -12345.0).all().item()):
+            print("GUARD BAND WRITTEN (bits in) shape", shape, "kind", kind, "res", res, "vb", vb, placed)
             np.save("gpurun_out/fuzz_fail_mask.npy", m)
             sys.exit(1)
     elif mode == "guard":
@@ -229,15 +237,21 @@ while time.time() - t0 < budget:
         import torch
         nvox = int(m.size)
         g = ((max(4096, 8 * shape[1] * shape[2]) + 3) // 4) * 4
-        buf = torch.full((g + nvox + g,), -12345.0, dtype=torch.float32, device="cuda")
-        dm = torch.from_numpy(m).cuda()
-        ctx.build_device(dm.data_ptr(), shape, buf.data_ptr() + 4 * g, res, vb, torch.cuda.current_stream().cuda_stream)
+        # every second scene: the mask 0 .. 15 bytes past a 16-byte boundary; every second: the field 0, 4, 8 or 12 bytes past one
+        # (element alignment is all the header asks for; the 16-byte kernels are chosen by the pointers)
+        ms = int(shift_rng.integers(0, 16)) if shift_rng.random() < 0.5 else 0
+        o = int(shift_rng.choice([0, 1, 2, 3])) if shift_rng.random() < 0.5 else 0
+        placed = "mask +%d B, field +%d B" % (ms, 4 * o)
+        buf = torch.full((g + nvox + g + 3,), -12345.0, dtype=torch.float32, device="cuda")
+        dm = torch.zeros(nvox + 16, dtype=torch.uint8, device="cuda")
+        dm[ms:ms + nvox] = torch.from_numpy(m.reshape(-1)).cuda()
+        ctx.build_device(dm.data_ptr() + ms, shape, buf.data_ptr() + 4 * (g + o), res, vb, torch.cuda.current_stream().cuda_stream)
         torch.cuda.synchronize()
         ext = ctx.get_extrema()
-        got = buf[g:g + nvox].cpu().numpy().reshape(shape)
-        if not bool((buf[:g] == -12345.0).all().item()) or not bool((buf[g + nvox:] == -12345.0).all().item()):
-            print("GUARD BAND WRITTEN shape", shape, "kind", kind, "res", res, "vb", vb,
-                  "before", int((buf[:g] != -12345.0).sum().item()), "behind", int((buf[g + nvox:] != -12345.0).sum().item()))
+        got = buf[g + o:g + o + nvox].cpu().numpy().reshape(shape)
+        if not bool((buf[:g + o] == -12345.0).all().item()) or not bool((buf[g + o + nvox:] == -12345.0).all().item()):
+            print("GUARD BAND WRITTEN shape", shape, "kind", kind, "res", res, "vb", vb, placed,
+                  "before", int((buf[:g + o] != -12345.0).sum().item()), "behind", int((buf[g + o + nvox:] != -12345.0).sum().item()))
             os.makedirs("gpurun_out", exist_ok=True)
             np.save("gpurun_out/fuzz_fail_mask.npy", m)
             sys.exit(1)
@@ -248,7 +262,7 @@ while time.time() - t0 < budget:
         bad = np.argwhere(got.view(np.uint32) != want.view(np.uint32))
         os.makedirs("gpurun_out", exist_ok=True)
         np.save("gpurun_out/fuzz_fail_mask.npy", m)
-        print("MISMATCH shape", shape, "kind", kind, "res", res, "vb", vb, "bad", len(bad), bad[:3].tolist(), ext, want_ext, values_bad or "")
+        print("MISMATCH shape", shape, "kind", kind, "res", res, "vb", vb, "bad", len(bad), bad[:3].tolist(), ext, want_ext, values_bad or "", placed)
         sys.exit(1)
     n += 1
     MODES[mode] = MODES.get(mode, 0) + 1
