@@ -183,18 +183,37 @@ struct LastBuild {
     bool last_dense3 = false, last_staged = false;   // ... ran KD3 + KF in KD's place / carried them behind KD, guarded on its verdict
     bool last_predicted = false;     // the last build took the far-field pair on the strength of the handle's recent builds: no probes, no marching launches
     bool last_lines_tiered = false;  // the last sdfgpu_sweep_x_lines_device call chose its tier on the device (probe / forced tier + far-field kernel behind the marching sweep)
-    int last_dc_x = 0;               // 1 + the far-field kernel instance (launch_envelope's `which`) of the last x sweep launched through it; 0: none since the last build / lines call began
+    int last_dc_x = 0;               // 1 + the far-field kernel instance (launch_envelope_kernel's `which`) of the last x sweep launched through it; 0: none since the last build / lines call began
     bool last_plane_skip = false;    // the last build skipped the x-planes without a filled voxel (sdfgpu_debug_copy_yzsweep fills them in)
 };
 
-// What the launchers read off the handle while one call enqueues: the pointers are non-null only then (the scan bounds go with far_y).
-struct InFlight {
-    const uint32_t* guard = nullptr; // set while a build enqueues the flag-guarded general pipeline
-    uint32_t* far_y = nullptr;       // set while a build enqueues a bounded K2 / K3
-    int scan_y = kScanExpectNear, scan_x = kScanExpectNear;   // outward-scan bounds of the marching kernels
-    uint32_t* unc_override = nullptr;   // set around the staged KD3 launch: undecided bits in the z field's storage
-    size_t unc_override_bytes = 0;
+// Where a build's occupancy comes from: a byte mask, or cell records (the float occupancy at `off` of every `stride` bytes; 0.5 is
+// filled iff `unknown`), or one bit per voxel in linear order (sdfgpu_build_bits*: the tuned dense kernels read it in place, the z
+// sweep and the generic dense tier through their bit loaders -- no byte mask exists).  Exactly one of the three pointers is set;
+// device memory for the launchers and build_device_impl, host memory for upload_packed and build_host_impl.
+struct Occupancy {
+    const uint8_t* mask = nullptr;
+    const void* cells = nullptr;
+    size_t stride = 0, off = 0;
+    int unknown = 0;
+    const uint32_t* bits = nullptr;
+    static Occupancy of_mask(const uint8_t* m) { Occupancy o; o.mask = m; return o; }
+    static Occupancy of_cells(const void* c, size_t stride, size_t off, int unknown) {
+        Occupancy o; o.cells = c; o.stride = stride; o.off = off; o.unknown = unknown; return o;
+    }
+    static Occupancy of_bits(const uint32_t* b) { Occupancy o; o.bits = b; return o; }
+    bool null() const { return !mask && !cells && !bits; }
+    CellLoader cell_loader() const { return CellLoader{reinterpret_cast<const char*>(cells), (int64_t)stride, (int64_t)off, unknown}; }
 };
+
+// What a launcher is told about the device words around its launch, spelt out at the call site.
+// guard: the launch does its work iff *guard != 0; kUnguarded: always.
+constexpr const uint32_t* kUnguarded = nullptr;
+// far_flag of a marching sweep: its outward scans are bounded (kScanExpectNear) and one that gives up raises the word, which guards
+// the far-field kernel behind the sweep; kUnbounded: unbounded scans, nothing raised.
+constexpr uint32_t* kUnbounded = nullptr;
+constexpr hipStream_t kNullStream = nullptr;  // the host-buffer entry points work on the null stream of the context's device
+constexpr int32_t* kNoSideTable = nullptr;    // d_side of a y sweep: int32 plane values, not the int16 plane field + side table
 
 }  // namespace
 
@@ -203,7 +222,6 @@ struct sdfgpu_context : ContextBuffers {
     std::string error;
     BuildOptions opt;
     LastBuild last;
-    InFlight inflight;
     size_t cx_stats_off = 0;    // where the last extrema call left its CxStats in cx_scratch (0 = no call yet)
     int cx_rounds = 0;          // doubling rounds of that call
     char* batch_pin = nullptr;  // pinned ring through which per-grid parameters reach the device without a host wait
@@ -229,7 +247,7 @@ struct sdfgpu_context : ContextBuffers {
     HostTeam* team = nullptr;               // the host threads that fill / drain the staging chunks: created with the first staged
                                             // transfer, parked between calls, joined by sdfgpu_destroy (sdfgpu_hostteam.hpp)
     hipEvent_t pin_ev[2] = {nullptr, nullptr};
-    uint32_t* d_small = nullptr;   // [0] max d^2 free, [1] max d^2 filled, [2] status, [3] uncertified, [4] far_y, [5] far_x
+    uint32_t* d_small = nullptr;   // the status block, indexed by StatusWord (sdfgpu_kernels.hpp)
     // "this handle's scene is a far-field scene on both axes": learnt from the status blocks that come back (never a wait).  Such a
     // build skips the two probes and the three guarded marching launches (35 us of a 0.8 - 1.4 ms build) and enqueues KE2 -> KE3
     // directly (int32 hand-off); every 16th build probes again.  The far-field pair is exact on any scene: a wrong prediction costs
@@ -240,7 +258,7 @@ struct sdfgpu_context : ContextBuffers {
     hipEvent_t far_ev = nullptr;
     bool far_pending = false;
     DensePolicy pol;              // what the handle has learned about its scenes' dense tier (sdfgpu_policy.hpp)
-    bool flat_score_reset = false;   // "policy_reset": the next build clears the device-side habit of the two-valued tiles (status word 40)
+    bool flat_score_reset = false;   // "policy_reset": the next build clears the device-side habit of the two-valued tiles (kSwFlatScore)
     const float* serp_out = nullptr; // "ball_serpentine": output buffer and voxel count of the last whole-build KD launch, and its direction
     int64_t serp_n = 0;
     int serp_flip = 0;
@@ -434,6 +452,23 @@ int check_resolution(sdfgpu_handle h, double resolution) {
     return SDFGPU_OK;
 }
 
+// The record layouts of the cell entry points: every field 4-byte aligned and inside the record.
+int check_cell_layout(sdfgpu_handle h, size_t stride, size_t occ_off) {
+    if (stride < 4 || (stride % 4) || (occ_off % 4) || occ_off + 4 > stride)
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cell_stride/occupancy_offset must be 4-byte aligned and in range");
+    return SDFGPU_OK;
+}
+int check_tagged_layout(sdfgpu_handle h, size_t stride, size_t occ_off, size_t obj_off) {
+    if (stride < 8 || (stride % 4) || (occ_off % 4) || (obj_off % 4) || occ_off + 4 > stride || obj_off + 4 > stride)
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cell layout must be 4-byte aligned and in range");
+    return SDFGPU_OK;
+}
+int check_component_layout(sdfgpu_handle h, size_t stride, size_t occ_off, size_t comp_off) {
+    if (stride < 8 || (stride % 4) || (occ_off % 4) || (comp_off % 4) || occ_off + 4 > stride || comp_off + 4 > stride || occ_off == comp_off)
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cell_stride / occupancy_offset / component_offset must be 4-byte aligned, in range and distinct");
+    return SDFGPU_OK;
+}
+
 int rows_per_block(int nz) {
     const int W = (nz + 63) / 64;
     return std::max(1, 4096 / (W * 64));
@@ -444,37 +479,27 @@ bool z_wave16_shape(const sdfgpu_context* h, int64_t nz) {
     return h->opt.z_wave_on && (nz == 64 || nz == 128 || nz == 256 || nz == 512 || nz == 1024);
 }
 
-// d_row_any != nullptr (callers check z_wave16_shape and, for masks, the alignment first): the kernel also writes one "holds a filled voxel" byte per z row
-int launch_sweep_z(sdfgpu_handle h, const uint8_t* d_mask, const void* d_cells, size_t stride, size_t off,
-                   int unknown, int64_t nx, int64_t ny, int64_t nz, int16_t* d_out, hipStream_t s, const uint32_t* d_bits = nullptr,
-                   uint8_t* d_row_any = nullptr) {
-    const int64_t nrows = nx * ny;
-    if (d_bits) {
-        // bits in (round 6): the wave-private form reads its 16 voxels as one 16-bit piece of the bit field; every other shape
-        // goes through the generic kernel with a bit loader
-        if (h->opt.z_wave_on && (nz == 64 || nz == 128 || nz == 256 || nz == 512 || nz == 1024)) {
-            const int rw = 1024 / (int)nz;
-            const int64_t ngroups = (nrows + rw - 1) / rw;
-            dim3 gw((unsigned)std::min<int64_t>((ngroups + kBlock / 64 - 1) / (kBlock / 64), 8192)), block(kBlock);
-            const uint8_t* b8 = reinterpret_cast<const uint8_t*>(d_bits);
-            switch ((int)nz) {
-                case 64: hipLaunchKernelGGL((k_sweep_z_wave16<4, true>), gw, block, 0, s, b8, d_out, nrows, h->inflight.guard, d_row_any); break;
-                case 128: hipLaunchKernelGGL((k_sweep_z_wave16<8, true>), gw, block, 0, s, b8, d_out, nrows, h->inflight.guard, d_row_any); break;
-                case 256: hipLaunchKernelGGL((k_sweep_z_wave16<16, true>), gw, block, 0, s, b8, d_out, nrows, h->inflight.guard, d_row_any); break;
-                case 512: hipLaunchKernelGGL((k_sweep_z_wave16<32, true>), gw, block, 0, s, b8, d_out, nrows, h->inflight.guard, d_row_any); break;
-                default: hipLaunchKernelGGL((k_sweep_z_wave16<64, true>), gw, block, 0, s, b8, d_out, nrows, h->inflight.guard, d_row_any); break;
-            }
-        } else {
-            const int rpb = rows_per_block((int)nz);
-            const int W = ((int)nz + 63) / 64;
-            const size_t lds = (size_t)rpb * W * 8 + (size_t)rpb * 4;
-            const int64_t nblocks = (nrows + rpb - 1) / rpb;
-            BitsLoader ld{d_bits};
-            hipLaunchKernelGGL(k_sweep_z_generic<BitsLoader>, dim3((unsigned)std::min<int64_t>(nblocks, 2048)), dim3(kBlock), lds, s, ld, d_out, nrows, (int)nz, rpb, h->inflight.guard);
-        }
-        HIP_TRY(h, hipGetLastError());
-        return SDFGPU_OK;
+// whole rows per wave (16 nz-lanes): no workgroup barrier; 32 workgroups per CU's worth of persistent waves (measured
+// at 512^3: 8 per CU 0.099 ms, 16 0.093, 32 0.088, one step per wave 0.100).  BITS (round 6): a wave reads its 16 voxels as one
+// 16-bit piece of the bit field.
+template <bool BITS>
+void launch_z_wave16(const uint8_t* d_in, int16_t* d_out, int64_t nrows, int64_t nz, const uint32_t* guard, uint8_t* d_row_any, hipStream_t s) {
+    const int rw = 1024 / (int)nz;                                  // rows per wave step
+    const int64_t ngroups = (nrows + rw - 1) / rw;
+    const dim3 gw((unsigned)std::min<int64_t>((ngroups + kBlock / 64 - 1) / (kBlock / 64), 8192)), block(kBlock);
+    switch ((int)nz) {
+        case 64: hipLaunchKernelGGL((k_sweep_z_wave16<4, BITS>), gw, block, 0, s, d_in, d_out, nrows, guard, d_row_any); break;
+        case 128: hipLaunchKernelGGL((k_sweep_z_wave16<8, BITS>), gw, block, 0, s, d_in, d_out, nrows, guard, d_row_any); break;
+        case 256: hipLaunchKernelGGL((k_sweep_z_wave16<16, BITS>), gw, block, 0, s, d_in, d_out, nrows, guard, d_row_any); break;
+        case 512: hipLaunchKernelGGL((k_sweep_z_wave16<32, BITS>), gw, block, 0, s, d_in, d_out, nrows, guard, d_row_any); break;
+        default: hipLaunchKernelGGL((k_sweep_z_wave16<64, BITS>), gw, block, 0, s, d_in, d_out, nrows, guard, d_row_any); break;
     }
+}
+
+// d_row_any != nullptr (callers check z_wave16_shape and, for masks, the alignment first): the kernel also writes one "holds a filled voxel" byte per z row
+int launch_sweep_z(sdfgpu_handle h, const Occupancy& occ, int64_t nx, int64_t ny, int64_t nz, int16_t* d_out, const uint32_t* guard,
+                   hipStream_t s, uint8_t* d_row_any = nullptr) {
+    const int64_t nrows = nx * ny;
     const int rpb = rows_per_block((int)nz);
     const int W = ((int)nz + 63) / 64;
     const size_t lds = (size_t)rpb * W * 8 + (size_t)rpb * 4;     // bitmap + one class word per row (vec16 kernel)
@@ -482,7 +507,8 @@ int launch_sweep_z(sdfgpu_handle h, const uint8_t* d_mask, const void* d_cells, 
     // persistent row-group loop inside the kernel: 8 workgroups per CU are plenty, and a small grid
     // makes the guard early-exit (dense path certified) a ~2 us launch instead of ~10 us
     dim3 grid((unsigned)std::min<int64_t>(nblocks, 2048)), block(kBlock);
-    if (!d_cells && (nz % 16) == 0 && (reinterpret_cast<uintptr_t>(d_mask) % 16) == 0) {
+    const bool mask16 = occ.mask && (reinterpret_cast<uintptr_t>(occ.mask) % 16) == 0;
+    if (mask16 && (nz % 16) == 0) {
         // the persistent grid must fit the device in ONE round: at 70 VGPRs 7 workgroups are resident per CU, and a grid of 8
         // per CU left 256 workgroups to run their 16 row groups alone after the others had finished
         if (h->k1_resident <= 0) {
@@ -493,28 +519,18 @@ int launch_sweep_z(sdfgpu_handle h, const uint8_t* d_mask, const void* d_cells, 
         }
         grid.x = (unsigned)std::min<int64_t>(nblocks, h->k1_resident);
     }
-    if (d_cells) {
-        CellLoader ld{reinterpret_cast<const char*>(d_cells), (int64_t)stride, (int64_t)off, unknown};
-        hipLaunchKernelGGL(k_sweep_z_generic<CellLoader>, grid, block, lds, s, ld, d_out, nrows, (int)nz, rpb, h->inflight.guard);
-    } else if (h->opt.z_wave_on && (nz == 64 || nz == 128 || nz == 256 || nz == 512 || nz == 1024) &&
-               (reinterpret_cast<uintptr_t>(d_mask) % 16) == 0) {
-        // whole rows per wave (16 nz-lanes): no workgroup barrier; 32 workgroups per CU's worth of persistent waves (measured
-        // at 512^3: 8 per CU 0.099 ms, 16 0.093, 32 0.088, one step per wave 0.100)
-        const int rw = 1024 / (int)nz;                                  // rows per wave step
-        const int64_t ngroups = (nrows + rw - 1) / rw;
-        dim3 gw((unsigned)std::min<int64_t>((ngroups + kBlock / 64 - 1) / (kBlock / 64), 8192));
-        switch ((int)nz) {
-            case 64: hipLaunchKernelGGL((k_sweep_z_wave16<4, false>), gw, block, 0, s, d_mask, d_out, nrows, h->inflight.guard, d_row_any); break;
-            case 128: hipLaunchKernelGGL((k_sweep_z_wave16<8, false>), gw, block, 0, s, d_mask, d_out, nrows, h->inflight.guard, d_row_any); break;
-            case 256: hipLaunchKernelGGL((k_sweep_z_wave16<16, false>), gw, block, 0, s, d_mask, d_out, nrows, h->inflight.guard, d_row_any); break;
-            case 512: hipLaunchKernelGGL((k_sweep_z_wave16<32, false>), gw, block, 0, s, d_mask, d_out, nrows, h->inflight.guard, d_row_any); break;
-            default: hipLaunchKernelGGL((k_sweep_z_wave16<64, false>), gw, block, 0, s, d_mask, d_out, nrows, h->inflight.guard, d_row_any); break;
-        }
-    } else if ((nz % 16) == 0 && (reinterpret_cast<uintptr_t>(d_mask) % 16) == 0) {
-        hipLaunchKernelGGL(k_sweep_z_vec16, grid, block, lds, s, d_mask, d_out, nrows, (int)nz, rpb, h->inflight.guard);
+    if (occ.bits) {
+        // every shape but the wave-private ones goes through the generic kernel with a bit loader
+        if (z_wave16_shape(h, nz)) launch_z_wave16<true>(reinterpret_cast<const uint8_t*>(occ.bits), d_out, nrows, nz, guard, d_row_any, s);
+        else hipLaunchKernelGGL(k_sweep_z_generic<BitsLoader>, grid, block, lds, s, BitsLoader{occ.bits}, d_out, nrows, (int)nz, rpb, guard);
+    } else if (occ.cells) {
+        hipLaunchKernelGGL(k_sweep_z_generic<CellLoader>, grid, block, lds, s, occ.cell_loader(), d_out, nrows, (int)nz, rpb, guard);
+    } else if (mask16 && z_wave16_shape(h, nz)) {
+        launch_z_wave16<false>(occ.mask, d_out, nrows, nz, guard, d_row_any, s);
+    } else if (mask16 && (nz % 16) == 0) {
+        hipLaunchKernelGGL(k_sweep_z_vec16, grid, block, lds, s, occ.mask, d_out, nrows, (int)nz, rpb, guard);
     } else {
-        MaskLoader ld{d_mask};
-        hipLaunchKernelGGL(k_sweep_z_generic<MaskLoader>, grid, block, lds, s, ld, d_out, nrows, (int)nz, rpb, h->inflight.guard);
+        hipLaunchKernelGGL(k_sweep_z_generic<MaskLoader>, grid, block, lds, s, MaskLoader{occ.mask}, d_out, nrows, (int)nz, rpb, guard);
     }
     HIP_TRY(h, hipGetLastError());
     return SDFGPU_OK;
@@ -527,7 +543,7 @@ int pick_T(int user, int span) {
 }
 
 template <int STAGE, bool VB>
-int launch_march(sdfgpu_handle h, SweepArgs a, bool vec4, hipStream_t s, int force_window = 0) {
+int launch_march(sdfgpu_handle h, SweepArgs a, bool vec4, hipStream_t s, bool wide_window = false) {
     const int span = a.out_hi - a.out_lo;
     const int nchunks = (span + a.T - 1) / a.T;
     const int64_t nbx = (a.ncols + kBlock - 1) / kBlock;
@@ -535,7 +551,7 @@ int launch_march(sdfgpu_handle h, SweepArgs a, bool vec4, hipStream_t s, int for
     dim3 grid((unsigned)nbx, (unsigned)nchunks), block(kBlock);
     bool wide = false;
     if constexpr (STAGE == 2 && !VB) {                       // radius-8 window: y sweep only
-        if (vec4 && force_window == 8) {
+        if (vec4 && wide_window) {
             hipLaunchKernelGGL((k_sweep_march<2, 4, 8, false>), grid, block, 0, s, a);
             wide = true;
         }
@@ -550,10 +566,11 @@ int launch_march(sdfgpu_handle h, SweepArgs a, bool vec4, hipStream_t s, int for
 }
 
 // K2 launch: int16 z field -> int32 in-plane signed d^2
-// (d_side != nullptr: write the int16 plane field to d_out and exact saturated groups to d_side;
+// (d_side != kNoSideTable: write the int16 plane field to d_out and exact saturated groups to d_side;
 //  requires the vec4 path)
+enum class YWindow { r3, r8 };       // register-window radius of the marching y sweep (r8: 4-voxel lanes only)
 int launch_sweep_y(sdfgpu_handle h, const int16_t* d_in, void* d_out, int32_t* d_side, int64_t nx, int64_t ny,
-                   int64_t nz, hipStream_t s, int force_window = 0) {
+                   int64_t nz, const uint32_t* guard, uint32_t* far_flag, hipStream_t s, YWindow window = YWindow::r3) {
     const bool vec4 = (nz % 4) == 0 && (reinterpret_cast<uintptr_t>(d_in) % 8) == 0 &&
                       (reinterpret_cast<uintptr_t>(d_out) % 16) == 0;
     if (d_side && !vec4) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "16-bit plane output needs nz % 4 == 0");
@@ -561,8 +578,8 @@ int launch_sweep_y(sdfgpu_handle h, const int16_t* d_in, void* d_out, int32_t* d
     SweepArgs a{};
     a.in = d_in; a.out = d_out;
     a.out16 = d_side ? 1 : 0; a.side = d_side;
-    a.guard = h->inflight.guard;
-    if (h->inflight.far_y) { a.max_scan = h->inflight.scan_y; a.far_flag = h->inflight.far_y; }
+    a.guard = guard;
+    if (far_flag) { a.max_scan = kScanExpectNear; a.far_flag = far_flag; }
     a.cpl = nz / V;
     a.ncols = nx * a.cpl;
     a.outer_stride = ny * nz;
@@ -579,7 +596,7 @@ int launch_sweep_y(sdfgpu_handle h, const int16_t* d_in, void* d_out, int32_t* d
             if (nbx * ((ny + t - 1) / t) >= 1024) break;
         }
     }
-    return launch_march<2, false>(h, a, vec4, s, force_window);
+    return launch_march<2, false>(h, a, vec4, s, window == YWindow::r8);
 }
 
 // K12 launch: mask -> int32 in-plane signed d^2 in one kernel (nz = 512 or 1024, 16-B aligned mask)
@@ -600,12 +617,12 @@ void launch_fused_variant(const FusedZyArgs& a0, int T, int64_t nx, int64_t ny, 
     else hipLaunchKernelGGL((k_sweep_zy_fused<V, H, false>), grid, block, lds, s, a);
 }
 
-// d_side != nullptr: d_out is the int16 plane field, saturated groups go to d_side
+// d_side != kNoSideTable: d_out is the int16 plane field, saturated groups go to d_side
 int launch_sweep_zy_fused(sdfgpu_handle h, const uint8_t* d_mask, void* d_out, int32_t* d_side, int64_t nx,
-                          int64_t ny, int64_t nz, hipStream_t s) {
+                          int64_t ny, int64_t nz, const uint32_t* guard, hipStream_t s) {
     FusedZyArgs a{};
     a.mask = d_mask; a.out = d_out; a.side = d_side; a.nx = (int)nx; a.ny = (int)ny;
-    a.guard = h->inflight.guard;
+    a.guard = guard;
     const int T = 64;
     const bool o16 = d_side != nullptr;
     if (nz == 512 && h->opt.fused_h == 3) launch_fused_variant<8, 3>(a, T, nx, ny, o16, s);
@@ -628,32 +645,41 @@ bool plane16_eligible(const sdfgpu_context* h, int64_t ny, int64_t nz) {
     return h->opt.plane16_on && (nz % 4) == 0 && ((ny * nz) % 8) == 0;
 }
 
-int launch_sweep_x16(sdfgpu_handle h, const int16_t* d_in16, const int32_t* d_side, float* d_out, int64_t halo_lo,
-                     int64_t nxs, int64_t halo_hi, int64_t side_lo, int64_t side_hi, int64_t ny, int64_t nz,
-                     int lo_trunc, int hi_trunc, int64_t x_global, int64_t nx_global, double resolution, int vb,
-                     uint32_t* d_maxdsq, uint32_t* d_status, hipStream_t s) {
+// The part of a grid an x sweep is launched on: planes [x_global, x_global + nxs) of nx_global with halo planes in front and behind,
+// rows [y_off, y_off + ny) of ny_glob.
+struct XSlab {
+    int64_t halo_lo = 0, nxs = 0, halo_hi = 0;
+    int lo_trunc = 0, hi_trunc = 0;         // the grid goes on beyond the halo on that side
+    int64_t x_global = 0, nx_global = 0;
+    int64_t y_off = 0, ny_glob = -1;        // K3 only; -1: the launch's own ny
+    int64_t side_lo = 0, side_hi = 0;       // K3/16 only: the planes the side table covers
+    uint32_t* status = nullptr;             // raised when a truncated halo was too short for a voxel (optional)
+    static XSlab whole(int64_t nx) { XSlab g; g.nxs = g.nx_global = g.side_hi = nx; return g; }
+};
+
+int launch_sweep_x16(sdfgpu_handle h, const int16_t* d_in16, const int32_t* d_side, float* d_out, const XSlab& g, int64_t ny,
+                     int64_t nz, double resolution, int vb, const uint32_t* guard, uint32_t* far_flag, hipStream_t s) {
     const int64_t plane = ny * nz;
     const int V = (h->opt.x16_v == 8) ? 8 : 4;
     SweepX16Args a{};
     a.in16 = d_in16; a.side32 = d_side; a.out = d_out;
     a.ncols = plane / V; a.plane = plane;
-    a.L = (int)(halo_lo + nxs + halo_hi);
-    a.out_lo = (int)halo_lo; a.out_hi = (int)(halo_lo + nxs);
-    a.T = pick_T(h->opt.tune_tx, (int)nxs);
-    a.side_lo = (int)side_lo; a.side_hi = (int)side_hi;
+    a.L = (int)(g.halo_lo + g.nxs + g.halo_hi);
+    a.out_lo = (int)g.halo_lo; a.out_hi = (int)(g.halo_lo + g.nxs);
+    a.T = pick_T(h->opt.tune_tx, (int)g.nxs);
+    a.side_lo = (int)g.side_lo; a.side_hi = (int)g.side_hi;
     a.resolution = resolution;
-    a.lo_truncated = lo_trunc; a.hi_truncated = hi_trunc;
-    a.x_global = x_global; a.nx_global = nx_global; a.ny = ny; a.nz = nz;
-    (void)d_maxdsq;                             // maxima go to the slot array; the caller folds them (fold_slots)
-    a.maxdsq = h->d_slots; a.status = d_status;
-    a.guard = h->inflight.guard;
-    if (h->inflight.far_y) { a.max_scan = h->inflight.scan_x; a.far_flag = h->inflight.far_y + 1; }
+    a.lo_truncated = g.lo_trunc; a.hi_truncated = g.hi_trunc;
+    a.x_global = g.x_global; a.nx_global = g.nx_global; a.ny = ny; a.nz = nz;
+    a.maxdsq = h->d_slots; a.status = g.status;                 // maxima go to the slot array; the caller folds them (fold_slots)
+    a.guard = guard;
+    if (far_flag) { a.max_scan = kScanExpectNear; a.far_flag = far_flag; }
     const int span = a.out_hi - a.out_lo;
     const int nchunks = (span + a.T - 1) / a.T;
     const int64_t nbx = (a.ncols + kBlock - 1) / kBlock;
     if (nbx > 0x7fffffffLL || nchunks > 65535) return fail(h, SDFGPU_ERR_UNSUPPORTED_SIZE, "sweep grid too large");
     dim3 grid((unsigned)nbx, (unsigned)nchunks), block(kBlock);
-    const bool slab = lo_trunc || hi_trunc || side_lo > 0 || side_hi < a.L;
+    const bool slab = g.lo_trunc || g.hi_trunc || g.side_lo > 0 || g.side_hi < a.L;
     if (V == 8) launch_x16_variant<8, 3>(a, grid, block, vb != 0, slab, s);
     else if (h->opt.x16_h == 2) launch_x16_variant<4, 2>(a, grid, block, vb != 0, slab, s);
     else if (h->opt.x16_h == 8 && !vb && !slab)      // wide window (option only): plain grids
@@ -664,10 +690,8 @@ int launch_sweep_x16(sdfgpu_handle h, const int16_t* d_in16, const int32_t* d_si
 }
 
 // K3 launch: int32 plane field (optionally with x halo) -> fp32 sdf
-int launch_sweep_x(sdfgpu_handle h, const int32_t* d_in, float* d_out, int64_t halo_lo, int64_t nxs,
-                   int64_t halo_hi, int64_t ny, int64_t nz, int lo_trunc, int hi_trunc, int64_t x_global,
-                   int64_t nx_global, double resolution, int vb, uint32_t* d_maxdsq, uint32_t* d_status,
-                   hipStream_t s, int64_t y_off = 0, int64_t ny_glob = -1, int max_scan = 0, uint32_t* far_flag = nullptr) {
+int launch_sweep_x(sdfgpu_handle h, const int32_t* d_in, float* d_out, const XSlab& g, int64_t ny, int64_t nz, double resolution,
+                   int vb, const uint32_t* guard, uint32_t* far_flag, hipStream_t s) {
     const int64_t plane = ny * nz;
     const bool vec4 = (plane % 4) == 0 && (reinterpret_cast<uintptr_t>(d_in) % 16) == 0 &&
                       (reinterpret_cast<uintptr_t>(d_out) % 16) == 0;
@@ -678,17 +702,16 @@ int launch_sweep_x(sdfgpu_handle h, const int32_t* d_in, float* d_out, int64_t h
     a.cpl = a.ncols;
     a.outer_stride = 0;
     a.line_stride = plane;
-    a.L = (int)(halo_lo + nxs + halo_hi);
-    a.out_lo = (int)halo_lo; a.out_hi = (int)(halo_lo + nxs);
-    a.T = pick_T(h->opt.tune_tx, (int)nxs);
+    a.L = (int)(g.halo_lo + g.nxs + g.halo_hi);
+    a.out_lo = (int)g.halo_lo; a.out_hi = (int)(g.halo_lo + g.nxs);
+    a.T = pick_T(h->opt.tune_tx, (int)g.nxs);
     a.resolution = resolution;
-    a.lo_truncated = lo_trunc; a.hi_truncated = hi_trunc;
-    a.x_global = x_global; a.nx_global = nx_global; a.ny = ny; a.nz = nz;
-    a.y_off = y_off; a.ny_glob = ny_glob < 0 ? ny : ny_glob;
-    a.max_scan = max_scan; a.far_flag = far_flag;
-    (void)d_maxdsq;                             // maxima go to the slot array; the caller folds them (fold_slots)
-    a.maxdsq = h->d_slots; a.status = d_status;
-    a.guard = h->inflight.guard;
+    a.lo_truncated = g.lo_trunc; a.hi_truncated = g.hi_trunc;
+    a.x_global = g.x_global; a.nx_global = g.nx_global; a.ny = ny; a.nz = nz;
+    a.y_off = g.y_off; a.ny_glob = g.ny_glob < 0 ? ny : g.ny_glob;
+    if (far_flag) { a.max_scan = kScanExpectNear; a.far_flag = far_flag; }
+    a.maxdsq = h->d_slots; a.status = g.status;                 // maxima go to the slot array; the caller folds them (fold_slots)
+    a.guard = guard;
     return vb ? launch_march<3, true>(h, a, vec4, s) : launch_march<3, false>(h, a, vec4, s);
 }
 
@@ -696,14 +719,22 @@ int launch_sweep_x(sdfgpu_handle h, const int32_t* d_in, float* d_out, int64_t h
 struct DcGeometry { bool ok; int B; uint32_t finf; int pitch; int M, Kp; };
 // dynamic LDS a far-field launch may ask for: the CU's 160 KB less the kernel's few static words (the fold of the stand-by x sweep)
 constexpr size_t kDcMaxDynamicLds = 160 * 1024 - 256;
-struct DcExtra {                 // int32 plane fields instead of p16 + side table, y-slab geometry
+// What a far-field launch (sweep or probe) reads and writes.  Stage 2 reads the z field (in16) or the dense tier's bit field and
+// writes the int16 plane field + side table (out, side_out) or an int32 plane field (out_i32); stage 3 reads either pair and
+// writes the fp32 field (out).
+struct DcIo {
+    const int16_t* in16 = nullptr;
+    const int32_t* side_in = nullptr;
+    void* out = nullptr;
+    int32_t* side_out = nullptr;
     const int32_t* in_i32 = nullptr;
     int32_t* out_i32 = nullptr;
-    int64_t y_off = 0, ny_glob = -1;
     const uint32_t* i32_flag = nullptr;     // device word: use the int32 fields only when it is non-zero (nullptr: always)
-    bool loop = false;                      // LOOP form of the kernel: a small grid whose workgroups walk the tiles (stand-by launches)
+    int64_t y_off = 0, ny_glob = -1;        // y-slab geometry (-1: the launch's own ny)
     const uint32_t* bits = nullptr;         // stage 2: z distances from the dense tier's bit field instead of the z field (forces the scalar form)
     int nzw = 0;
+    // sweeps only
+    bool loop = false;                      // LOOP form of the kernel: a small grid whose workgroups walk the tiles (stand-by launches)
     uint32_t* ran_flag = nullptr;           // status word raised by a launch that does work
     const uint32_t* row_bits = nullptr;     // plane sparsity (see EnvDcArgs); nullptr: every plane is processed
     int row_words = 0;
@@ -744,176 +775,169 @@ bool far_geometry_ok(const sdfgpu_context* h, int stage, int64_t nx, int64_t ny,
     return envelope_dc_geometry(h, stage, nx, ny, nz, ny_full).ok;
 }
 
-int launch_decide(sdfgpu_handle h, int stage, bool dense_tried, hipStream_t s, bool handoff, bool window_choice);
-
-// KE2 / KE3: exact far-field sweeps.  guard: run iff (*guard != 0) != guard_invert (nullptr: always).
-int launch_envelope(sdfgpu_handle h, int stage, const int16_t* d_in16, const int32_t* d_side_in, void* d_out,
-                    int32_t* d_side_out, int64_t nx, int64_t ny, int64_t nz, double resolution, int vb,
-                    uint32_t* d_maxdsq, const uint32_t* guard, hipStream_t s, int guard_invert = 0,
-                    uint32_t* probe_out = nullptr, const DcExtra* ex = nullptr, const DcDecide* dec = nullptr) {
-    (void)d_maxdsq;
-    const DcGeometry g = envelope_dc_geometry(h, stage, nx, ny, nz, ex ? ex->ny_glob : -1);
-    if (!g.ok) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "shape not taken by the far-field kernel (internal: callers check the geometry first)");
-    {
-        EnvDcArgs a{};
-        a.in16 = d_in16; a.side_in = d_side_in; a.out = d_out; a.side_out = d_side_out;
-        int64_t ntiles;
-        constexpr int NL = kDcLines;
-        if (stage == 2) { a.group_lines = nz; a.tiles_per_outer = (nz + NL - 1) / NL; ntiles = nx * a.tiles_per_outer; a.outer_stride = ny * nz; a.line_stride = nz; a.L = (int)ny; }
-        else { a.group_lines = ny * nz; a.tiles_per_outer = (ny * nz + NL - 1) / NL; ntiles = a.tiles_per_outer; a.outer_stride = 0; a.line_stride = ny * nz; a.L = (int)nx; }
-        a.B = g.B; a.finf = g.finf; a.pitch = g.pitch; a.M = g.M; a.Kp = 0; a.h = (a.L + 1) / 2;
-        a.resolution = resolution; a.vb = vb; a.nx = nx; a.ny = ny; a.nz = nz;
-        a.y_off = 0; a.ny_glob = ny;
-        if (ex) {
-            a.in_i32 = ex->in_i32; a.out_i32 = ex->out_i32; a.y_off = ex->y_off; a.i32_flag = ex->i32_flag;
-            if (ex->ny_glob >= 0) a.ny_glob = ex->ny_glob;
-            a.ran_flag = ex->ran_flag;
-            if (!probe_out) { a.row_bits = ex->row_bits; a.row_words = ex->row_words; a.plane_any = ex->plane_any; a.some_empty = h->d_small + 22; a.flat_on = h->opt.flat_tiles; a.flat_score = h->d_small + 40; }
-            if (stage == 2) { a.bits = ex->bits; a.nzw = ex->nzw; }
-            if (stage == 3 && ex->loop && ex->fold_ticket && !probe_out) {
-                a.fold_status = h->d_small; a.fold_result = ex->fold_result; a.fold_report = ex->fold_report; a.fold_ticket = ex->fold_ticket;
-                a.fold_report_mask = kReportDense;
-            }
-        }
-        const bool loop = ex && ex->loop && !probe_out;
-        a.maxdsq = h->d_slots; a.guard = guard; a.guard_invert = guard_invert;
-        if (ntiles > 0x7fffffffLL) return fail(h, SDFGPU_ERR_UNSUPPORTED_SIZE, "envelope grid too large");
-        const int64_t all = ntiles;
-        if (probe_out && dec && h->opt.probe_window) {
-            // the window statistic (k_probe_window): thresholds up to 81 = windows up to radius 8
-            const int thr = h->opt.far_thr[stage - 2], thr2 = stage == 2 ? kMidThrY : 0, thr3 = stage == 2 ? h->opt.far_thr[1] : 0;
-            int W = 0;
-            while ((W + 1) * (W + 1) < std::max(thr, std::max(thr2, thr3))) ++W;
-            const bool handoff_in = ex && ex->i32_flag;                      // p16 shape: int32 values only behind the flag, which ends the probe
-            const int32_t* in32 = (stage == 3 && ex && ex->in_i32 && !handoff_in) ? ex->in_i32 : nullptr;
-            const int16_t* in16 = in32 ? nullptr : d_in16;
-            if (W <= 8 && (in16 || in32)) {
-                ProbeArgs pa{};
-                pa.in16 = in16; pa.in32 = in32;
-                pa.n = nx * ny * nz; pa.ls = a.line_stride; pa.L = a.L; pa.W = W;
-                pa.thr = thr; pa.thr2 = thr2; pa.thr3 = thr3;
-                pa.nsamples = (uint32_t)std::min<int64_t>(pa.n, 32768);
-                pa.step = std::max<int64_t>(1, pa.n / pa.nsamples);
-                if (pa.step > 0xffffff) pa.step = 0xffffff;                 // (the kernel hashes the offset inside a stretch in 24 bits)
-                pa.probe_out = probe_out; pa.guard = guard; pa.i32_flag = handoff_in ? ex->i32_flag : nullptr;
-                pa.decide_small = h->d_small; pa.decide_stage = dec->stage; pa.decide_dense_tried = dec->dense_tried ? 1 : 0;
-                pa.decide_force = h->opt.force_env; pa.decide_den = kFarDen[dec->stage]; pa.decide_handoff = dec->handoff ? 1 : 0;
-                pa.decide_mid_den = (dec->stage == 0 && dec->window_choice) ? kMidDenY : 0;
-                pa.decide_xden = kFarDen[1];
-                const unsigned nb = (pa.nsamples + 255u) / 256u;
-                if (stage == 2 && W <= 3) hipLaunchKernelGGL((k_probe_window<2, 3>), dim3(nb), dim3(256), 0, s, pa);
-                else if (stage == 2) hipLaunchKernelGGL((k_probe_window<2, 8>), dim3(nb), dim3(256), 0, s, pa);
-                else if (W <= 3) hipLaunchKernelGGL((k_probe_window<3, 3>), dim3(nb), dim3(256), 0, s, pa);
-                else hipLaunchKernelGGL((k_probe_window<3, 8>), dim3(nb), dim3(256), 0, s, pa);
-                HIP_TRY(h, hipGetLastError());
-                return SDFGPU_OK;
-            }
-        }
-        if (probe_out) {                                        // sample ~256 tiles spread over the grid, store nothing
-            a.probe_stride = (int)std::max<int64_t>(1, std::min<int64_t>(64, ntiles / 256));
-            a.probe_thr = h->opt.far_thr[stage - 2];
-            a.probe_thr2 = stage == 2 ? kMidThrY : 0;
-            a.probe_thr3 = (stage == 2 && dec) ? h->opt.far_thr[1] : 0;
-            a.probe_out = probe_out;
-            if (dec) {
-                a.decide_small = h->d_small; a.decide_stage = dec->stage; a.decide_dense_tried = dec->dense_tried ? 1 : 0;
-                a.decide_force = h->opt.force_env; a.decide_den = kFarDen[dec->stage]; a.decide_handoff = dec->handoff ? 1 : 0;
-                a.decide_mid_den = (dec->stage == 0 && dec->window_choice) ? kMidDenY : 0;
-                a.decide_xden = kFarDen[1];
-            }
-            ntiles = (ntiles + a.probe_stride - 1) / a.probe_stride;
-            while (ntiles > 0 && (ntiles - 1) * a.probe_stride + ((ntiles - 1) * 7) % a.probe_stride >= all) --ntiles;
-            if (ntiles == 0) return dec ? launch_decide(h, dec->stage, dec->dense_tried, s, dec->handoff, dec->window_choice) : SDFGPU_OK;
-        }
-        // vector loads: 4 consecutive lines per load, whole tiles, aligned rows
-        auto al = [](const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) % n) == 0; };
-        const bool vec = !a.bits && (nz % 4) == 0 && (a.group_lines % NL) == 0 && al(d_in16, 8) && al(d_side_in, 16) && al(a.in_i32, 16);
-        const size_t lds = envelope_dc_lds_bytes(a.L, NL);
-        // (the kernel is a template over lines per tile and lanes; measured at 512^3: 8-line tiles -- 20 KB of LDS, 7 - 8
-        //  workgroups per CU -- with 128 or 256 lanes are 12 - 25 % slower than 16 lines x 256 lanes, 16 lines x 512 lanes
-        //  +-5 %, 32 lines x 512 lanes +-3 %; 2 instead of 4 workgroups per CU is 1.55x slower)
-        // lines above 512: the tile's keys take 66 KB and more, two workgroups per CU -- of 512 lanes then (round 4: with 256 they
-        // left the CU at 2 waves per SIMD, and 1024-voxel lines cost 1.5 - 2x their share).  Round 5 tried the other way out, 8 lines
-        // x 256 lanes (38 KB: four workgroups per CU again) on the 1024^3 scenes: same fields bit for bit, room 18.1 ms instead of
-        // 16.0, boxes / shells / spheres within 2 % -- the long lines are not short of resident workgroups
-        const bool big = a.L > 512 && !loop;
-        const int NT = big ? 512 : 256;
-        a.ntiles = ntiles;
-        // LOOP form: at most 2048 workgroups (a guarded exit costs 1.7 us up to there and grows with the grid), a multiple of 8
-        // so that a workgroup's tiles stay on its XCD
-        const int64_t nwg = loop ? std::min<int64_t>(ntiles, h->opt.standby_grid) : ntiles;
-        // 512-voxel lines, vector loads, one tile per workgroup: the instances with the line's geometry as compile-time constants (option "dc_fixed")
-        const bool fixed512 = h->opt.dc_fixed && a.L == 512 && vec && !loop && !big && a.B == 9 && a.pitch == 514 && a.M == 64 && a.h == 256;
-        const bool fixed1024 = h->opt.dc_fixed && a.L == 1024 && vec && big && a.B == 10 && a.pitch == 1026 && a.M == 128 && a.h == 512;
-        const int which = fixed512 ? 12 + (stage == 3 ? 1 : 0) : fixed1024 ? 14 + (stage == 3 ? 1 : 0) :
-                          (stage == 3 ? 1 : 0) + (vec ? 2 : 0) + (loop ? 4 : 0) + (big ? 8 : 0);
-        if (stage == 3 && !probe_out) h->last.last_dc_x = which + 1;
-        auto launch = [&](auto kern) -> int {
-            // (the attribute is per kernel: raised once per instantiation, not on every launch -- ADVICE r3)
-            if (lds > 64 * 1024 && !h->dc_attr_set[which]) {
-                HIP_TRY(h, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kDcMaxDynamicLds));
-                h->dc_attr_set[which] = true;
-            }
-            hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3((unsigned)NT), lds, s, a);
-            return SDFGPU_OK;
-        };
-        int rc;
-        switch (which) {
-            case 0: rc = launch(k_envelope_dc<2, false, 256, 16>); break;
-            case 1: rc = launch(k_envelope_dc<3, false, 256, 16>); break;
-            case 2: rc = launch(k_envelope_dc<2, true, 256, 16>); break;
-            case 3: rc = launch(k_envelope_dc<3, true, 256, 16>); break;
-            case 4: rc = launch(k_envelope_dc<2, false, 256, 16, true>); break;
-            case 5: rc = launch(k_envelope_dc<3, false, 256, 16, true>); break;
-            case 6: rc = launch(k_envelope_dc<2, true, 256, 16, true>); break;
-            case 7: rc = launch(k_envelope_dc<3, true, 256, 16, true>); break;
-            case 8: rc = launch(k_envelope_dc<2, false, 512, 16, false, 4>); break;
-            case 9: rc = launch(k_envelope_dc<3, false, 512, 16, false, 4>); break;
-            case 10: rc = launch(k_envelope_dc<2, true, 512, 16, false, 4>); break;
-            case 11: rc = launch(k_envelope_dc<3, true, 512, 16, false, 4>); break;
-            case 12: rc = launch(k_envelope_dc<2, true, 256, 16, false, 4, 512>); break;
-            case 13: rc = launch(k_envelope_dc<3, true, 256, 16, false, 4, 512>); break;
-            case 14: rc = launch(k_envelope_dc<2, true, 512, 16, false, 4, 1024>); break;
-            default: rc = launch(k_envelope_dc<3, true, 512, 16, false, 4, 1024>); break;
-        }
-        if (rc) return rc;
-        HIP_TRY(h, hipGetLastError());
-        return SDFGPU_OK;
-    }
-}
-
-int launch_decide(sdfgpu_handle h, int stage, bool dense_tried, hipStream_t s, bool handoff = false, bool window_choice = false);
-int launch_decide(sdfgpu_handle h, int stage, bool dense_tried, hipStream_t s, bool handoff, bool window_choice) {
-    hipLaunchKernelGGL(k_decide_tier, dim3(1), dim3(1), 0, s, h->d_small, stage, dense_tried ? 1 : 0, h->opt.force_env,
-                       1, kFarDen[stage], handoff ? 1 : 0, (stage == 0 && window_choice) ? kMidDenY : 0);
+// probe counters -> guard words, for a build whose tier is forced or whose probe has no tile to sample
+int launch_decide(sdfgpu_handle h, const DcDecide& dec, hipStream_t s) {
+    hipLaunchKernelGGL(k_decide_tier, dim3(1), dim3(1), 0, s, h->d_small, dec.stage, dec.dense_tried ? 1 : 0, h->opt.force_env,
+                       1, kFarDen[dec.stage], dec.handoff ? 1 : 0, (dec.stage == 0 && dec.window_choice) ? kMidDenY : 0);
     HIP_TRY(h, hipGetLastError());
     return SDFGPU_OK;
+}
+
+// What the far-field sweep and its tile probe share: the line geometry and the fields of `io` both read.
+int envelope_args(sdfgpu_handle h, int stage, const DcIo& io, int64_t nx, int64_t ny, int64_t nz, double resolution, int vb,
+                  const uint32_t* guard, EnvDcArgs& a) {
+    const DcGeometry g = envelope_dc_geometry(h, stage, nx, ny, nz, io.ny_glob);
+    if (!g.ok) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "shape not taken by the far-field kernel (internal: callers check the geometry first)");
+    a.in16 = io.in16; a.side_in = io.side_in; a.out = io.out; a.side_out = io.side_out;
+    constexpr int NL = kDcLines;
+    if (stage == 2) { a.group_lines = nz; a.tiles_per_outer = (nz + NL - 1) / NL; a.ntiles = nx * a.tiles_per_outer; a.outer_stride = ny * nz; a.line_stride = nz; a.L = (int)ny; }
+    else { a.group_lines = ny * nz; a.tiles_per_outer = (ny * nz + NL - 1) / NL; a.ntiles = a.tiles_per_outer; a.outer_stride = 0; a.line_stride = ny * nz; a.L = (int)nx; }
+    a.B = g.B; a.finf = g.finf; a.pitch = g.pitch; a.M = g.M; a.Kp = 0; a.h = (a.L + 1) / 2;
+    a.resolution = resolution; a.vb = vb; a.nx = nx; a.ny = ny; a.nz = nz;
+    a.in_i32 = io.in_i32; a.out_i32 = io.out_i32; a.y_off = io.y_off; a.i32_flag = io.i32_flag;
+    a.ny_glob = io.ny_glob >= 0 ? io.ny_glob : ny;
+    a.ran_flag = io.ran_flag;
+    if (stage == 2) { a.bits = io.bits; a.nzw = io.nzw; }
+    a.maxdsq = h->d_slots; a.guard = guard;
+    if (a.ntiles > 0x7fffffffLL) return fail(h, SDFGPU_ERR_UNSUPPORTED_SIZE, "envelope grid too large");
+    return SDFGPU_OK;
+}
+
+// Picks the kernel instance for `a` (a.ntiles = the tiles of this launch) and launches it.
+int launch_envelope_kernel(sdfgpu_handle h, int stage, EnvDcArgs& a, bool loop, bool probe, hipStream_t s) {
+    constexpr int NL = kDcLines;
+    // vector loads: 4 consecutive lines per load, whole tiles, aligned rows
+    auto al = [](const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) % n) == 0; };
+    const bool vec = !a.bits && (a.nz % 4) == 0 && (a.group_lines % NL) == 0 && al(a.in16, 8) && al(a.side_in, 16) && al(a.in_i32, 16);
+    const size_t lds = envelope_dc_lds_bytes(a.L, NL);
+    // (the kernel is a template over lines per tile and lanes; measured at 512^3: 8-line tiles -- 20 KB of LDS, 7 - 8
+    //  workgroups per CU -- with 128 or 256 lanes are 12 - 25 % slower than 16 lines x 256 lanes, 16 lines x 512 lanes
+    //  +-5 %, 32 lines x 512 lanes +-3 %; 2 instead of 4 workgroups per CU is 1.55x slower)
+    // lines above 512: the tile's keys take 66 KB and more, two workgroups per CU -- of 512 lanes then (round 4: with 256 they
+    // left the CU at 2 waves per SIMD, and 1024-voxel lines cost 1.5 - 2x their share).  Round 5 tried the other way out, 8 lines
+    // x 256 lanes (38 KB: four workgroups per CU again) on the 1024^3 scenes: same fields bit for bit, room 18.1 ms instead of
+    // 16.0, boxes / shells / spheres within 2 % -- the long lines are not short of resident workgroups
+    const bool big = a.L > 512 && !loop;
+    const int NT = big ? 512 : 256;
+    // LOOP form: at most 2048 workgroups (a guarded exit costs 1.7 us up to there and grows with the grid), a multiple of 8
+    // so that a workgroup's tiles stay on its XCD
+    const int64_t nwg = loop ? std::min<int64_t>(a.ntiles, h->opt.standby_grid) : a.ntiles;
+    // 512-voxel lines, vector loads, one tile per workgroup: the instances with the line's geometry as compile-time constants (option "dc_fixed")
+    const bool fixed512 = h->opt.dc_fixed && a.L == 512 && vec && !loop && !big && a.B == 9 && a.pitch == 514 && a.M == 64 && a.h == 256;
+    const bool fixed1024 = h->opt.dc_fixed && a.L == 1024 && vec && big && a.B == 10 && a.pitch == 1026 && a.M == 128 && a.h == 512;
+    const int which = fixed512 ? 12 + (stage == 3 ? 1 : 0) : fixed1024 ? 14 + (stage == 3 ? 1 : 0) :
+                      (stage == 3 ? 1 : 0) + (vec ? 2 : 0) + (loop ? 4 : 0) + (big ? 8 : 0);
+    if (stage == 3 && !probe) h->last.last_dc_x = which + 1;
+    // the instances by `which`: stage 2 / 3, scalar / vector loads, LOOP form, 512 lanes, fixed 512- / 1024-voxel lines
+    static void (*const kKernels[16])(const EnvDcArgs) = {
+        k_envelope_dc<2, false, 256, 16>, k_envelope_dc<3, false, 256, 16>, k_envelope_dc<2, true, 256, 16>, k_envelope_dc<3, true, 256, 16>,
+        k_envelope_dc<2, false, 256, 16, true>, k_envelope_dc<3, false, 256, 16, true>,
+        k_envelope_dc<2, true, 256, 16, true>, k_envelope_dc<3, true, 256, 16, true>,
+        k_envelope_dc<2, false, 512, 16, false, 4>, k_envelope_dc<3, false, 512, 16, false, 4>,
+        k_envelope_dc<2, true, 512, 16, false, 4>, k_envelope_dc<3, true, 512, 16, false, 4>,
+        k_envelope_dc<2, true, 256, 16, false, 4, 512>, k_envelope_dc<3, true, 256, 16, false, 4, 512>,
+        k_envelope_dc<2, true, 512, 16, false, 4, 1024>, k_envelope_dc<3, true, 512, 16, false, 4, 1024>};
+    // (the attribute is per kernel: raised once per instantiation, not on every launch -- ADVICE r3)
+    if (lds > 64 * 1024 && !h->dc_attr_set[which]) {
+        HIP_TRY(h, hipFuncSetAttribute((const void*)kKernels[which], hipFuncAttributeMaxDynamicSharedMemorySize, (int)kDcMaxDynamicLds));
+        h->dc_attr_set[which] = true;
+    }
+    hipLaunchKernelGGL(kKernels[which], dim3((unsigned)nwg), dim3((unsigned)NT), lds, s, a);
+    HIP_TRY(h, hipGetLastError());
+    return SDFGPU_OK;
+}
+
+// KE2 / KE3: exact far-field sweeps.  guard: run iff *guard != 0 (kUnguarded: always).
+int launch_envelope(sdfgpu_handle h, int stage, const DcIo& io, int64_t nx, int64_t ny, int64_t nz, double resolution, int vb,
+                    const uint32_t* guard, hipStream_t s) {
+    EnvDcArgs a{};
+    if (int rc = envelope_args(h, stage, io, nx, ny, nz, resolution, vb, guard, a)) return rc;
+    if (io.row_bits || io.plane_any) {                              // plane sparsity, and the flat tiles that go with the row masks
+        a.row_bits = io.row_bits; a.row_words = io.row_words; a.plane_any = io.plane_any;
+        a.some_empty = h->d_small + kSwPlaneEmpty; a.flat_on = h->opt.flat_tiles; a.flat_score = h->d_small + kSwFlatScore;
+    }
+    if (stage == 3 && io.loop && io.fold_ticket) {
+        a.fold_status = h->d_small; a.fold_result = io.fold_result; a.fold_report = io.fold_report; a.fold_ticket = io.fold_ticket;
+        a.fold_report_mask = kReportDense;
+    }
+    return launch_envelope_kernel(h, stage, a, io.loop, false, s);
+}
+
+// The tier probe of a far-field sweep: counts, on a sample of the sweep's own input, the voxels whose d^2 reaches the axis'
+// thresholds into the status block's probe counters; its last workgroup turns them into the tier decision `dec`.  Stores no field.
+// The window statistic (k_probe_window) where the thresholds allow it, else the far-field kernel itself on ~256 sampled tiles.
+int launch_envelope_probe(sdfgpu_handle h, int stage, const DcIo& io, int64_t nx, int64_t ny, int64_t nz, double resolution, int vb,
+                          const uint32_t* guard, const DcDecide& dec, hipStream_t s) {
+    EnvDcArgs a{};
+    if (int rc = envelope_args(h, stage, io, nx, ny, nz, resolution, vb, guard, a)) return rc;
+    uint32_t* const probe_out = h->d_small + kSwProbeFar;
+    auto set_decision = [&](auto& args) {                           // what the launch's last workgroup passes to decide_tier
+        args.decide_small = h->d_small; args.decide_stage = dec.stage; args.decide_dense_tried = dec.dense_tried ? 1 : 0;
+        args.decide_force = h->opt.force_env; args.decide_den = kFarDen[dec.stage]; args.decide_handoff = dec.handoff ? 1 : 0;
+        args.decide_mid_den = (dec.stage == 0 && dec.window_choice) ? kMidDenY : 0;
+        args.decide_xden = kFarDen[1];
+    };
+    if (h->opt.probe_window) {
+        // thresholds up to 81 = windows up to radius 8
+        const int thr = h->opt.far_thr[stage - 2], thr2 = stage == 2 ? kMidThrY : 0, thr3 = stage == 2 ? h->opt.far_thr[1] : 0;
+        int W = 0;
+        while ((W + 1) * (W + 1) < std::max(thr, std::max(thr2, thr3))) ++W;
+        const bool handoff_in = io.i32_flag != nullptr;                 // p16 shape: int32 values only behind the flag, which ends the probe
+        const int32_t* in32 = (stage == 3 && io.in_i32 && !handoff_in) ? io.in_i32 : nullptr;
+        const int16_t* in16 = in32 ? nullptr : io.in16;
+        if (W <= 8 && (in16 || in32)) {
+            ProbeArgs pa{};
+            pa.in16 = in16; pa.in32 = in32;
+            pa.n = nx * ny * nz; pa.ls = a.line_stride; pa.L = a.L; pa.W = W;
+            pa.thr = thr; pa.thr2 = thr2; pa.thr3 = thr3;
+            pa.nsamples = (uint32_t)std::min<int64_t>(pa.n, 32768);
+            pa.step = std::max<int64_t>(1, pa.n / pa.nsamples);
+            if (pa.step > 0xffffff) pa.step = 0xffffff;                 // (the kernel hashes the offset inside a stretch in 24 bits)
+            pa.probe_out = probe_out; pa.guard = guard; pa.i32_flag = io.i32_flag;
+            set_decision(pa);
+            const unsigned nb = (pa.nsamples + 255u) / 256u;
+            if (stage == 2 && W <= 3) hipLaunchKernelGGL((k_probe_window<2, 3>), dim3(nb), dim3(256), 0, s, pa);
+            else if (stage == 2) hipLaunchKernelGGL((k_probe_window<2, 8>), dim3(nb), dim3(256), 0, s, pa);
+            else if (W <= 3) hipLaunchKernelGGL((k_probe_window<3, 3>), dim3(nb), dim3(256), 0, s, pa);
+            else hipLaunchKernelGGL((k_probe_window<3, 8>), dim3(nb), dim3(256), 0, s, pa);
+            HIP_TRY(h, hipGetLastError());
+            return SDFGPU_OK;
+        }
+    }
+    // sample ~256 tiles spread over the grid, store nothing
+    const int64_t all = a.ntiles;
+    a.probe_stride = (int)std::max<int64_t>(1, std::min<int64_t>(64, all / 256));
+    a.probe_thr = h->opt.far_thr[stage - 2];
+    a.probe_thr2 = stage == 2 ? kMidThrY : 0;
+    a.probe_thr3 = stage == 2 ? h->opt.far_thr[1] : 0;
+    a.probe_out = probe_out;
+    set_decision(a);
+    a.ntiles = (all + a.probe_stride - 1) / a.probe_stride;
+    while (a.ntiles > 0 && (a.ntiles - 1) * a.probe_stride + ((a.ntiles - 1) * 7) % a.probe_stride >= all) --a.ntiles;
+    if (a.ntiles == 0) return launch_decide(h, dec, s);
+    return launch_envelope_kernel(h, stage, a, false, true, s);
 }
 
 // K0 + KD: pack to bits, then the bit-parallel ball kernel (sdfgpu_dense.hpp)
 constexpr int kBallLanes = 256;                   // lanes per workgroup of KD, KD3, KD6 and KF
 constexpr int kDenseMaxRowWords = 64;             // longest z-row the tuned dense kernels take, in 32-voxel words (DenseArgs::nzw)
 static_assert(kDenseMaxRowWords <= kBallLanes, "a ball-kernel tile holds at least one z-row: launch_ball_dense divides by kBallLanes / nzw");
-bool dense_eligible(const sdfgpu_context* h, int64_t nz, int vb) {
+bool dense_eligible(const sdfgpu_context* h, int64_t nz) {       // (with or without virtual border: the tuned ball kernel folds it itself)
     const int64_t nzw = nz / 32;
-    (void)vb;                                     // (the tuned ball kernel folds the virtual border itself)
     return h->opt.dense_on && (nz % 32) == 0 && nzw >= 1 && nzw <= kDenseMaxRowWords && (nzw & (nzw - 1)) == 0;
 }
 
-int launch_pack_bits(sdfgpu_handle h, const uint8_t* d_mask, const void* d_cells, size_t stride, size_t off, int unknown,
-                     int64_t n, uint32_t* d_bits, hipStream_t s) {
-    if (d_cells) {
-        CellLoader ld{reinterpret_cast<const char*>(d_cells), (int64_t)stride, (int64_t)off, unknown};
-        hipLaunchKernelGGL(k_pack_bits_generic<CellLoader>, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
-                           ld, d_bits, n);
-    } else if ((reinterpret_cast<uintptr_t>(d_mask) % 16) == 0) {
+// K0: byte mask or cell records -> bits (a bit field needs no packing: callers do not come here with one)
+int launch_pack_bits(sdfgpu_handle h, const Occupancy& occ, int64_t n, uint32_t* d_bits, hipStream_t s) {
+    const dim3 grid((unsigned)((n + kBlock - 1) / kBlock)), block(kBlock);
+    if (occ.cells) {
+        hipLaunchKernelGGL(k_pack_bits_generic<CellLoader>, grid, block, 0, s, occ.cell_loader(), d_bits, n);
+    } else if ((reinterpret_cast<uintptr_t>(occ.mask) % 16) == 0) {
         const int64_t n16 = n / 16;
         const int64_t pb = (int64_t)kBlock * 4;                     // 4 chunks of 16 voxels per lane
-        hipLaunchKernelGGL((k_pack_bits_mask<4, true>), dim3((unsigned)((n16 + pb - 1) / pb)), dim3(kBlock), 0, s, d_mask, d_bits, n16);
+        hipLaunchKernelGGL((k_pack_bits_mask<4, true>), dim3((unsigned)((n16 + pb - 1) / pb)), block, 0, s, occ.mask, d_bits, n16);
     } else {
-        MaskLoader ld{d_mask};
-        hipLaunchKernelGGL(k_pack_bits_generic<MaskLoader>, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
-                           ld, d_bits, n);
+        hipLaunchKernelGGL(k_pack_bits_generic<MaskLoader>, grid, block, 0, s, MaskLoader{occ.mask}, d_bits, n);
     }
     HIP_TRY(h, hipGetLastError());
     return SDFGPU_OK;
@@ -931,11 +955,24 @@ int fold_slots(sdfgpu_handle h, uint32_t* d_maxdsq, hipStream_t s, uint32_t* res
 // far-field pair's 0.96), p = 0.007 17 % (1.07 ms against 0.97)
 constexpr int kShellBudgetDen = 8;
 
+// How launch_ball_dense runs the dense tier.  The defaults are a stage call's: KD alone on a slab without virtual border, raising
+// *d_uncert itself for what it cannot decide.
+struct BallMode {
+    uint32_t* fix_needed = nullptr;  // non-null: fix-up mode -- the ball kernel raises this word instead and hands its undecided voxels to
+                                     // KF (behind KD3: to KD6 first), which raises *d_uncert only for what it cannot decide either
+    bool early_out = false;          // whole builds: a scene the tier will not certify is left early, the reason goes to the status block
+    int vb = 0;                      // virtual border around a grid of nx_glob planes
+    int64_t nx_glob = 0;
+    int radius = 2;                  // 3: KD3 (sdfgpu_dense3.hpp; whole-grid builds without virtual border only)
+    const uint32_t* guard = kUnguarded;
+    int flip = 0;                    // KD walks its tiles in the opposite order (option "ball_serpentine")
+    uint32_t* unc = nullptr;         // fix-up mode: storage of unc_bytes for the undecided bits (and, if it is large enough, the tile
+    size_t unc_bytes = 0;            // flags behind them) in place of the context's own buffers
+};
+
 int launch_ball_dense(sdfgpu_handle h, const uint32_t* d_bits, float* d_out, int64_t rows_x, int64_t out_lo, int64_t out_hi,
-                      int64_t ny, int64_t nz, double resolution, uint32_t* d_maxdsq, uint32_t* d_uncert, hipStream_t s,
-                      uint32_t* d_fix_needed = nullptr, bool early_out = false, int vb = 0, int64_t nx_glob = 0, int radius = 2,
-                      const uint32_t* d_guard = nullptr, int flip = 0) {
-    const int R = radius == 3 ? kBall3R : kBallR;                   // 3: KD3 (sdfgpu_dense3.hpp; whole-grid builds without virtual border only)
+                      int64_t ny, int64_t nz, double resolution, uint32_t* d_uncert, const BallMode& m, hipStream_t s) {
+    const int R = m.radius == 3 ? kBall3R : kBallR;                   // 3: KD3 (sdfgpu_dense3.hpp; whole-grid builds without virtual border only)
     // The ball kernels stage bit rows with 16-byte loads and store 4 floats per lane.  Whole builds come here with the library's own
     // bit field and a 16-byte-aligned field (build_device_impl); the stage entry points pass the caller's pointers, which need
     // element alignment only (sdfgpu.h "Conventions"): planes off 16 bytes are copied into scratch first, and a field off 16 bytes
@@ -954,8 +991,8 @@ int launch_ball_dense(sdfgpu_handle h, const uint32_t* d_bits, float* d_out, int
         d_bits = (const uint32_t*)h->ball_bits.ptr;
     }
     DenseArgs a{};
-    a.early_out = early_out ? 1 : 0;
-    a.vb = vb; a.nx_glob = (int)nx_glob;
+    a.early_out = m.early_out ? 1 : 0;
+    a.vb = m.vb; a.nx_glob = (int)m.nx_glob;
     a.bits = d_bits; a.out = d_out;
     a.nzw = (int)(nz / 32);
     a.log2_nzw = 0;
@@ -979,31 +1016,31 @@ int launch_ball_dense(sdfgpu_handle h, const uint32_t* d_bits, float* d_out, int
     static const int level3_d2[13] = {1, 2, 3, 4, 5, 6, 8, 9, 10, 11, 12, 13, 14};
     for (int l = 0; l < 16; ++l) a.mag3[l] = l < 13 ? (float)(std::sqrt((double)level3_d2[l]) * resolution) : 0.0f;
     a.slots = h->d_slots; a.uncertified = d_uncert;
-    a.reason = early_out ? h->d_small + 21 : nullptr;                // (whole builds: the context's status block; stage calls have none)
-    a.flip = radius == 3 ? 0 : flip;
-    a.guard = d_guard;
+    a.reason = m.early_out ? h->d_small + kSwReason : nullptr;                // (whole builds: the context's status block; stage calls have none)
+    a.flip = m.radius == 3 ? 0 : m.flip;
+    a.guard = m.guard;
     // KD3 gives up at once when a wave holds more undecided voxels than the stage behind it takes: KF's per-tile cap -- or, with
     // the shell pass in between (which turns words, not voxels, around and leaves KF what lies beyond d^2 = 36), three quarters
     // of the wave: the faces of a sparse noise grid, where a voxel sees a fraction of the ball, used to end the tier there
-    const bool shell = radius == 3 && h->opt.shell_on && d_fix_needed && early_out;      // (whole builds: the status block carries the sample)
+    const bool shell = m.radius == 3 && h->opt.shell_on && m.fix_needed && m.early_out;      // (whole builds: the status block carries the sample)
     a.max_undecided = shell ? 1536 : kBall3MaxUndecided;
     a.und_sample = shell ? h->d_slots : nullptr;
     const int64_t gx = (ny + a.ty - 1) / a.ty, gy = (out_hi - out_lo + a.tx - 1) / a.tx;
     if (gx > 0x7fffffffLL || gy > 65535) return fail(h, SDFGPU_ERR_UNSUPPORTED_SIZE, "dense grid too large");
     const size_t pitch = a.nzw < 32 ? a.nzw + 32 : a.nzw + 2;        // must match k_ball_dense
     const size_t tile_words = ((size_t)(a.tx + 2 * R) * (a.ty + 2 * R) * pitch + 3) & ~(size_t)3;
-    const size_t lds = radius == 3 ? tile_words * 4 + (size_t)bd * 20 + 1024 * 8 + 128 : tile_words * 4 + (size_t)bd * 16 + 256 * 8 + 64;
+    const size_t lds = m.radius == 3 ? tile_words * 4 + (size_t)bd * 20 + 1024 * 8 + 128 : tile_words * 4 + (size_t)bd * 16 + 256 * 8 + 64;
     const dim3 grid((unsigned)gx, (unsigned)gy);
-    if (d_fix_needed) {                                              // fix-up mode: hand the undecided voxels to KF
+    if (m.fix_needed) {                                              // fix-up mode: hand the undecided voxels to KF
         const size_t tiles = (size_t)gx * gy;
         // (the undecided bits of a STAGED fix-up stage live in the z field's storage, which the general pipeline only writes
         //  after KF has consumed them: a fresh context's first build does not pay a 17 MB allocation for a stage that a
         //  far-field scene leaves at once)
-        if (!h->inflight.unc_override) if (int rc = ensure(h, h->unc, (size_t)(out_hi - out_lo) * ny * a.nzw * 4, "undecided words")) return rc;
+        if (!m.unc) if (int rc = ensure(h, h->unc, (size_t)(out_hi - out_lo) * ny * a.nzw * 4, "undecided words")) return rc;
         uint32_t* tileflag = nullptr;
-        if (h->inflight.unc_override && h->inflight.unc_override_bytes >= (size_t)(out_hi - out_lo) * ny * a.nzw * 4 + 256 + tiles * 4) {
+        if (m.unc && m.unc_bytes >= (size_t)(out_hi - out_lo) * ny * a.nzw * 4 + 256 + tiles * 4) {
             // ... and so do its tile flags (behind the bits; cleared here: the storage is not ours between builds)
-            tileflag = h->inflight.unc_override + ((size_t)(out_hi - out_lo) * ny * a.nzw + 63) / 64 * 64;
+            tileflag = m.unc + ((size_t)(out_hi - out_lo) * ny * a.nzw + 63) / 64 * 64;
             HIP_TRY(h, hipMemsetAsync(tileflag, 0, tiles * 4, s));
         } else {
             if (h->tileflag.bytes < tiles * 4 || !h->tileflag.ptr) {
@@ -1012,11 +1049,11 @@ int launch_ball_dense(sdfgpu_handle h, const uint32_t* d_bits, float* d_out, int
             }
             tileflag = (uint32_t*)h->tileflag.ptr;
         }
-        a.unc = h->inflight.unc_override ? h->inflight.unc_override : (uint32_t*)h->unc.ptr; a.tileflag = tileflag; a.fix_needed = d_fix_needed;
+        a.unc = m.unc ? m.unc : (uint32_t*)h->unc.ptr; a.tileflag = tileflag; a.fix_needed = m.fix_needed;
     }
     const bool zinv = nz <= (int64_t)bd * 4;   // an expansion pass covers whole z-rows
-    if (radius == 3) {
-        if (vb) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "KD3: grids without virtual border only (internal)");
+    if (m.radius == 3) {
+        if (m.vb) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "KD3: grids without virtual border only (internal)");
         // nz = 512 (16 words per row, 4 x 4-row tiles): the instance with compile-time row pitch and halo width (option "dense3_fixed")
         if (zinv && a.nzw == 16 && a.ty == 4 && a.tx == 4 && h->opt.dense3_fixed) hipLaunchKernelGGL((k_ball_dense3<256, true, 16, 4>), grid, dim3(256), lds, s, a);
         else if (zinv) hipLaunchKernelGGL((k_ball_dense3<256, true>), grid, dim3(256), lds, s, a);
@@ -1024,7 +1061,7 @@ int launch_ball_dense(sdfgpu_handle h, const uint32_t* d_bits, float* d_out, int
     }
     else if (zinv) hipLaunchKernelGGL((k_ball_dense<256, true>), grid, dim3(256), lds, s, a);
     else hipLaunchKernelGGL((k_ball_dense<256, false>), grid, dim3(256), lds, s, a);
-    if (d_fix_needed) {
+    if (m.fix_needed) {
         HIP_TRY(h, hipGetLastError());
         if (!h->fix_order.ptr) {                                     // (dx, dy) rows by increasing dx^2 + dy^2, built once
             std::vector<uint32_t> order;
@@ -1040,12 +1077,12 @@ int launch_ball_dense(sdfgpu_handle h, const uint32_t* d_bits, float* d_out, int
         // at d^2 = 9, below the shell.
         if (shell) {
             ShellArgs sa{};
-            sa.bits = d_bits; sa.out = d_out; sa.unc = a.unc; sa.tileflag = a.tileflag; sa.fix_needed = d_fix_needed;
+            sa.bits = d_bits; sa.out = d_out; sa.unc = a.unc; sa.tileflag = a.tileflag; sa.fix_needed = m.fix_needed;
             sa.uncertified = d_uncert;
             // budget: 1 / kShellBudgetDen of the voxels undecided behind KD3 (the sample holds 1 / 16 of them; small grids: at least
             // one wave's worth)
             const uint32_t budget = (uint32_t)std::max<int64_t>((out_hi - out_lo) * ny * nz / kShellBudgetDen / 16, 2048);
-            hipLaunchKernelGGL(k_shell_budget, dim3(1), dim3(kSlots), 0, s, h->d_slots, d_fix_needed, d_uncert, a.reason, budget);
+            hipLaunchKernelGGL(k_shell_budget, dim3(1), dim3(kSlots), 0, s, h->d_slots, m.fix_needed, d_uncert, a.reason, budget);
             sa.nzw = a.nzw; sa.log2_nzw = a.log2_nzw; sa.ny = a.ny; sa.rows_x = a.rows_x; sa.out_lo = a.out_lo; sa.out_hi = a.out_hi;
             sa.tx = a.tx; sa.ty = a.ty; sa.log2_ty = a.log2_ty; sa.resolution = resolution; sa.slots = h->d_slots; sa.min_words = h->opt.shell_min_words;
             const size_t slds = shell_lds_bytes(256, a.tx, a.ty, a.nzw);
@@ -1056,7 +1093,7 @@ int launch_ball_dense(sdfgpu_handle h, const uint32_t* d_bits, float* d_out, int
             }
         }
         FixArgs f{};
-        f.bits = d_bits; f.out = d_out; f.unc = a.unc; f.tileflag = a.tileflag; f.fix_needed = d_fix_needed;
+        f.bits = d_bits; f.out = d_out; f.unc = a.unc; f.tileflag = a.tileflag; f.fix_needed = m.fix_needed;
         f.order = (const uint32_t*)h->fix_order.ptr;
         f.nzw = a.nzw; f.log2_nzw = a.log2_nzw; f.ny = a.ny; f.rows_x = a.rows_x; f.out_lo = a.out_lo; f.out_hi = a.out_hi;
         f.tx = a.tx; f.ty = a.ty; f.log2_ty = a.log2_ty; f.resolution = resolution;
@@ -1071,23 +1108,19 @@ int launch_ball_dense(sdfgpu_handle h, const uint32_t* d_bits, float* d_out, int
 }
 
 // Generic dense tier (any nz, virtual border): k_pack_bits_rows + k_ball_dense_generic
-int launch_dense_generic(sdfgpu_handle h, const uint8_t* d_mask, const void* d_cells, size_t stride, size_t off, int unknown,
-                         int64_t nx, int64_t ny, int64_t nz, double resolution, int vb, float* d_out, uint32_t* d_uncert,
-                         hipStream_t s, const uint32_t* d_bits_in = nullptr) {
+int launch_dense_generic(sdfgpu_handle h, const Occupancy& occ, int64_t nx, int64_t ny, int64_t nz, double resolution, int vb,
+                         float* d_out, uint32_t* d_uncert, hipStream_t s) {
     const int64_t nzw = (nz + 31) / 32, nrows = nx * ny, nwords = nrows * nzw;
     if (nwords > 0x7fffffffLL * (int64_t)kBlock) return fail(h, SDFGPU_ERR_UNSUPPORTED_SIZE, "dense grid too large");
     if (int rc = ensure(h, h->bits, (size_t)nwords * 4, "bit field")) return rc;
     const dim3 grid((unsigned)((nwords + kBlock - 1) / kBlock)), block(kBlock);
-    if (d_bits_in) {                                            // (linear bits -> rows padded to whole words)
-        BitsLoader ld{d_bits_in};
-        hipLaunchKernelGGL(k_pack_bits_rows<BitsLoader>, grid, block, 0, s, ld, (uint32_t*)h->bits.ptr, nrows, (int)nz, (int)nzw);
-    } else if (d_cells) {
-        CellLoader ld{reinterpret_cast<const char*>(d_cells), (int64_t)stride, (int64_t)off, unknown};
-        hipLaunchKernelGGL(k_pack_bits_rows<CellLoader>, grid, block, 0, s, ld, (uint32_t*)h->bits.ptr, nrows, (int)nz, (int)nzw);
-    } else {
-        MaskLoader ld{d_mask};
-        hipLaunchKernelGGL(k_pack_bits_rows<MaskLoader>, grid, block, 0, s, ld, (uint32_t*)h->bits.ptr, nrows, (int)nz, (int)nzw);
-    }
+    uint32_t* const rows = (uint32_t*)h->bits.ptr;
+    if (occ.bits)                                               // (linear bits -> rows padded to whole words)
+        hipLaunchKernelGGL(k_pack_bits_rows<BitsLoader>, grid, block, 0, s, BitsLoader{occ.bits}, rows, nrows, (int)nz, (int)nzw);
+    else if (occ.cells)
+        hipLaunchKernelGGL(k_pack_bits_rows<CellLoader>, grid, block, 0, s, occ.cell_loader(), rows, nrows, (int)nz, (int)nzw);
+    else
+        hipLaunchKernelGGL(k_pack_bits_rows<MaskLoader>, grid, block, 0, s, MaskLoader{occ.mask}, rows, nrows, (int)nz, (int)nzw);
     HIP_TRY(h, hipGetLastError());
     DenseGenArgs a{};
     a.bits = (const uint32_t*)h->bits.ptr; a.out = d_out;
@@ -1101,18 +1134,14 @@ int launch_dense_generic(sdfgpu_handle h, const uint8_t* d_mask, const void* d_c
     return SDFGPU_OK;
 }
 
-// d_bits_in != nullptr (round 6): the occupancy arrives as one bit per voxel, linear order (sdfgpu_build_bits*): the tuned dense
-// kernels read it in place (no K0), the z sweep and the generic dense tier read it through their bit loaders -- no byte mask exists.
-int build_device_impl(sdfgpu_handle h, const uint8_t* d_filled, const void* d_cells, size_t stride, size_t off,
-                      int unknown, int64_t nx, int64_t ny, int64_t nz, double resolution, int vb,
-                      float* d_out, hipStream_t s, const uint32_t* d_bits_in = nullptr) {
+int build_device_impl(sdfgpu_handle h, const Occupancy& occ, int64_t nx, int64_t ny, int64_t nz, double resolution, int vb,
+                      float* d_out, hipStream_t s) {
     if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-    if ((!d_filled && !d_cells && !d_bits_in) || !d_out) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null device pointer");
-    if (d_bits_in && (reinterpret_cast<uintptr_t>(d_bits_in) % 4) != 0) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "the bit field must be 4-byte aligned");
+    if (occ.null() || !d_out) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null device pointer");
+    if (occ.bits && (reinterpret_cast<uintptr_t>(occ.bits) % 4) != 0) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "the bit field must be 4-byte aligned");
     if (int rc = check_resolution(h, resolution)) return rc;
     if (int rc = check_dims(h, nx, ny, nz)) return rc;
-    if (d_cells && (stride < 4 || (stride % 4) || (off % 4) || off + 4 > stride))
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cell_stride/occupancy_offset must be 4-byte aligned and in range");
+    if (occ.cells) if (int rc = check_cell_layout(h, occ.stride, occ.off)) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     canonical_dims(nx, ny, nz);
     h->last.last_dc_x = 0;
@@ -1127,7 +1156,7 @@ int build_device_impl(sdfgpu_handle h, const uint8_t* d_filled, const void* d_ce
     if (p16) if (int rc = ensure(h, h->plane16, (size_t)n * 2, "16-bit plane field")) return rc;
     void* zy_out = p16 ? h->plane16.ptr : h->yzfield.ptr;
     int32_t* zy_side = p16 ? (int32_t*)h->yzfield.ptr : nullptr;
-    bool dense = dense_eligible(h, nz, vb) && ny <= 0x7fffffff && out16;
+    bool dense = dense_eligible(h, nz) && ny <= 0x7fffffff && out16;
     // shapes / modes the tuned dense kernels do not take go through their generic forms (any nz, virtual border)
     const bool dense_generic = !dense && h->opt.dense_on && h->opt.dense_generic_on && nx <= 0x7fffffff && ny <= 0x7fffffff;
     dense = dense || dense_generic;
@@ -1137,15 +1166,15 @@ int build_device_impl(sdfgpu_handle h, const uint8_t* d_filled, const void* d_ce
     // device inside the build).
     if (h->flags_pending && hipEventQuery(h->flags_ev) == hipSuccess) {
         h->flags_pending = false;
-        //   (a staged build -- KD, then KD3 + KF on KD's verdict -- reports KD's own verdict, status word 20, as word 8)
-        h->pol.consume_report(h->h_flags[3] != 0, h->h_flags[6] != 0, h->h_flags[8] != 0);
+        //   (a staged build -- KD, then KD3 + KF on KD's verdict -- reports KD's own verdict, kSwDenseVerdict, as word kSwReportVerdict)
+        h->pol.consume_report(h->h_flags[kSwUncertified] != 0, h->h_flags[kSwFixNeeded] != 0, h->h_flags[kSwReportVerdict] != 0);
         // (a predicted build's flags are raised by the launches themselves: they teach the habit nothing, and a near-field scene would
         //  keep a stale "far" alive through them -- ADVICE r5)
-        if (!h->pol.prev.predicted) h->far.consume_report(h->h_flags[4] != 0, h->h_flags[5] != 0);
+        if (!h->pol.prev.predicted) h->far.consume_report(h->h_flags[kSwFarY] != 0, h->h_flags[kSwFarX] != 0);
     }
     if (h->far_pending && hipEventQuery(h->far_ev) == hipSuccess) {
         h->far_pending = false;
-        h->far.consume_report(h->h_far[4] != 0, h->h_far[5] != 0);
+        h->far.consume_report(h->h_far[kSwFarY] != 0, h->h_far[kSwFarX] != 0);
     }
     const DensePlan plan = h->pol.plan(dense, dense_generic, nz / 32 <= 256, vb != 0);
     dense = plan.dense;
@@ -1170,7 +1199,7 @@ int build_device_impl(sdfgpu_handle h, const uint8_t* d_filled, const void* d_ce
     // K12 (fused z+y) only as the guarded stand-by behind a dense build that is expected to be certified
     // again; everywhere else K1 + K2 (rows from the int16 z field) scan much faster than the fused kernel
     // recomputes, and only they can hand a far-field y sweep to the envelope kernel.
-    const bool fused = !standby && !d_cells && fused_zy_eligible(h, d_filled, zy_out, nz) &&
+    const bool fused = !standby && fused_zy_eligible(h, occ.mask, zy_out, nz) &&
                        (h->opt.fused_always || (dense && h->pol.expect_dense) || (!envelope && !dense));
     const bool select = dev_select && !fused;
     // (see far_predict: the handle's recent builds were far-field on both axes -- or the caller forces it)
@@ -1217,28 +1246,26 @@ int build_device_impl(sdfgpu_handle h, const uint8_t* d_filled, const void* d_ce
     };
     HIP_TRY(h, mark(0));
     // Dense path first: exact wherever the nearest opposite voxel is within d^2 <= 8; raises
-    // d_small[3] otherwise, in which case (and only then) the general pipeline below does any work.
+    // kSwUncertified otherwise, in which case (and only then) the general pipeline below does any work.
+    uint32_t* const sw = h->d_small;                            // the status block, indexed by StatusWord
     bool cur_fix_mode = false, cur_dense3 = false, cur_staged = false;
     const uint32_t* dense_bits = nullptr;                       // the bit field the tuned dense kernels (and the stand-by y sweep) read
     uint8_t* row_any = nullptr;                                 // plane sparsity: one byte per z row, one per x-plane behind them (predicted far-field builds)
     h->last.last_dense = dense;
-    h->inflight.guard = nullptr;
     if (dense && dense_generic) {
         HIP_TRY(h, mark(1));
-        if (int rc = launch_dense_generic(h, d_filled, d_cells, stride, off, unknown, nx, ny, nz, resolution, vb, d_out,
-                                          h->d_small + 3, s, d_bits_in)) return rc;
+        if (int rc = launch_dense_generic(h, occ, nx, ny, nz, resolution, vb, d_out, sw + kSwUncertified, s)) return rc;
         launched_since_mark = true;
-        h->inflight.guard = h->d_small + 3;
     } else if (dense) {
-        if (d_bits_in && (reinterpret_cast<uintptr_t>(d_bits_in) % 16) == 0) {
-            dense_bits = d_bits_in;                             // (nz % 32 == 0: the caller's linear bit field IS the [x][y][nz / 32] field K0 writes)
-        } else if (d_bits_in) {                                 // (the dense kernels stage bit rows with 16-byte loads)
+        if (occ.bits && (reinterpret_cast<uintptr_t>(occ.bits) % 16) == 0) {
+            dense_bits = occ.bits;                              // (nz % 32 == 0: the caller's linear bit field IS the [x][y][nz / 32] field K0 writes)
+        } else if (occ.bits) {                                  // (the dense kernels stage bit rows with 16-byte loads)
             if (int rc = ensure(h, h->bits, (size_t)n / 8, "bit field")) return rc;
-            HIP_TRY(h, hipMemcpyAsync(h->bits.ptr, d_bits_in, (size_t)n / 8, hipMemcpyDeviceToDevice, s));
+            HIP_TRY(h, hipMemcpyAsync(h->bits.ptr, occ.bits, (size_t)n / 8, hipMemcpyDeviceToDevice, s));
             dense_bits = (const uint32_t*)h->bits.ptr;
         } else {
             if (int rc = ensure(h, h->bits, (size_t)n / 8, "bit field")) return rc;
-            if (int rc = launch_pack_bits(h, d_filled, d_cells, stride, off, unknown, n, (uint32_t*)h->bits.ptr, s)) return rc;
+            if (int rc = launch_pack_bits(h, occ, n, (uint32_t*)h->bits.ptr, s)) return rc;
             launched_since_mark = true;
             dense_bits = (const uint32_t*)h->bits.ptr;
         }
@@ -1250,28 +1277,29 @@ int build_device_impl(sdfgpu_handle h, const uint8_t* d_filled, const void* d_ce
         const bool fix = plan.fix;
         cur_dense3 = plan.dense3;
         cur_staged = plan.staged;
-        int flip = 0;
+        BallMode kd;
+        kd.early_out = true; kd.vb = vb; kd.nx_glob = nx; kd.radius = cur_dense3 ? 3 : 2;
+        if (fix || cur_dense3) kd.fix_needed = sw + kSwFixNeeded;
         if (!cur_dense3) {                                      // (KD; see ball_serpentine)
-            flip = (h->opt.ball_serpentine && d_out == h->serp_out && n == h->serp_n) ? !h->serp_flip : 0;
-            h->serp_out = d_out; h->serp_n = n; h->serp_flip = flip;
+            kd.flip = (h->opt.ball_serpentine && d_out == h->serp_out && n == h->serp_n) ? !h->serp_flip : 0;
+            h->serp_out = d_out; h->serp_n = n; h->serp_flip = kd.flip;
         }
-        if (int rc = launch_ball_dense(h, dense_bits, d_out, nx, 0, nx, ny, nz, resolution, h->d_small,
-                                       cur_staged ? h->d_small + 20 : h->d_small + 3, s,
-                                       (fix || cur_dense3) ? h->d_small + 6 : nullptr, true, vb, nx, cur_dense3 ? 3 : 2, nullptr, flip)) return rc;
-        if (cur_staged) {
-            h->inflight.unc_override = (!fused && h->zfield.ptr && h->zfield.bytes >= (size_t)n / 8) ? (uint32_t*)h->zfield.ptr : nullptr;
-            h->inflight.unc_override_bytes = h->inflight.unc_override ? h->zfield.bytes : 0;
-            const int rc = launch_ball_dense(h, dense_bits, d_out, nx, 0, nx, ny, nz, resolution, h->d_small,
-                                             h->d_small + 3, s, h->d_small + 6, true, 0, nx, 3, h->d_small + 20);
-            h->inflight.unc_override = nullptr;
-            if (rc) return rc;
+        if (int rc = launch_ball_dense(h, dense_bits, d_out, nx, 0, nx, ny, nz, resolution,
+                                       cur_staged ? sw + kSwDenseVerdict : sw + kSwUncertified, kd, s)) return rc;
+        if (cur_staged) {                                       // KD3 + KF behind KD, guarded on its verdict
+            BallMode kd3;
+            kd3.early_out = true; kd3.nx_glob = nx; kd3.radius = 3; kd3.fix_needed = sw + kSwFixNeeded; kd3.guard = sw + kSwDenseVerdict;
+            // (the undecided bits of this stage live in the z field's storage: launch_ball_dense)
+            if (!fused && h->zfield.ptr && h->zfield.bytes >= (size_t)n / 8) { kd3.unc = (uint32_t*)h->zfield.ptr; kd3.unc_bytes = h->zfield.bytes; }
+            if (int rc = launch_ball_dense(h, dense_bits, d_out, nx, 0, nx, ny, nz, resolution, sw + kSwUncertified, kd3, s)) return rc;
         }
         launched_since_mark = true;
-        h->inflight.guard = h->d_small + 3;
         cur_fix_mode = fix || cur_dense3;
     } else {
         HIP_TRY(h, mark(1));
     }
+    // what guards every launch of the general pipeline: "the dense tier left voxels undecided"
+    const uint32_t* const general_guard = dense ? sw + kSwUncertified : kUnguarded;
     h->last.last_dense3 = cur_dense3;
     h->last.last_staged = cur_staged;
     HIP_TRY(h, mark(2));
@@ -1279,153 +1307,126 @@ int build_device_impl(sdfgpu_handle h, const uint8_t* d_filled, const void* d_ce
     h->last.last_standby = standby;
     h->last.last_predicted = predicted;
     h->last.last_plane16 = p16;
-    h->inflight.far_y = (envelope && !fused) ? h->d_small + 4 : nullptr;
-    h->inflight.scan_y = h->inflight.scan_x = kScanExpectNear;
     if (!fused && !standby) {                                   // (the stand-by pair takes its z distances from the bit field)
         // a build that goes straight to the far-field pair lets the z sweep mark the x-planes that hold a filled voxel at all: a sensed
         // scene leaves most planes without one, and the pair skips them (y sweep: the planes' tiles; x sweep: their row loads)
-        if (predicted && h->opt.plane_skip && nx >= 8 && ny <= 1024 && z_wave16_shape(h, nz) && !d_cells &&
-            (d_bits_in || (reinterpret_cast<uintptr_t>(d_filled) % 16) == 0)) {
+        if (predicted && h->opt.plane_skip && nx >= 8 && ny <= 1024 && z_wave16_shape(h, nz) && !occ.cells &&
+            (occ.bits || (reinterpret_cast<uintptr_t>(occ.mask) % 16) == 0)) {
             const size_t o_bits = ((size_t)(nx * ny + nx) + 255) & ~(size_t)255;
             if (int rc = ensure(h, h->planebits, o_bits + (size_t)nx * ((ny + 31) / 32) * 4, "row / x-plane occupancy flags")) return rc;
             row_any = (uint8_t*)h->planebits.ptr;
         }
-        if (int rc = launch_sweep_z(h, d_filled, d_cells, stride, off, unknown, nx, ny, nz,
-                                    (int16_t*)h->zfield.ptr, s, d_bits_in, row_any)) return rc;
+        if (int rc = launch_sweep_z(h, occ, nx, ny, nz, (int16_t*)h->zfield.ptr, general_guard, s, row_any)) return rc;
         launched_since_mark = true;
     }
     h->last.last_plane_skip = row_any != nullptr;
     h->last.last_dims[0] = nx; h->last.last_dims[1] = ny; h->last.last_dims[2] = nz;
     HIP_TRY(h, mark(3));
-    // y sweep: marching (bounded scan, may raise far_y) + guarded envelope, or the envelope kernel alone
-    const uint32_t* const general_guard = h->inflight.guard;           // nullptr, or "the dense tier left voxels undecided"
+    const int16_t* const zf = (const int16_t*)h->zfield.ptr;
+    int32_t* const yz = (int32_t*)h->yzfield.ptr;
     // Both axes far-field (decided by the y probe): the y sweep hands the x sweep exact int32 values in the side-table
     // buffer (used whole) instead of p16 + side table -- one store / one load per voxel, no saturation handling, and the
-    // x probe is skipped.  d_small[7] carries the choice on the device.
+    // x probe is skipped.  kSwHandoff carries the choice on the device.
     const bool handoff = select && p16 && h->opt.i32_handoff;        // (shapes without the 16-bit plane field hand int32 values over anyway)
-    DcExtra hand2{}, hand3{};
-    hand2.out_i32 = (int32_t*)h->yzfield.ptr; hand2.i32_flag = h->d_small + 7;
-    hand3.in_i32 = (const int32_t*)h->yzfield.ptr; hand3.i32_flag = h->d_small + 7;
-    DcExtra plain2{}, plain3{};                                 // shapes without the 16-bit plane field: int32 in / out, unconditionally
-    plain2.out_i32 = (int32_t*)h->yzfield.ptr;
-    plain3.in_i32 = (const int32_t*)h->yzfield.ptr;
-    const DcExtra* const ex2 = !p16 ? &plain2 : handoff ? &hand2 : nullptr;
-    const DcExtra* const ex3 = !p16 ? &plain3 : handoff ? &hand3 : nullptr;
     // (the radius-8 y window exists for 4-voxel lanes only)
     const bool window_choice = select && (nz % 4) == 0;
-    auto decide = [&](int stage) -> int { return launch_decide(h, stage, dense, s, handoff, window_choice); };   // probe counters -> guard words
-    DcExtra sb2{}, sb3{};                                       // stand-by pair: int32 hand-off unconditionally, LOOP form, self-reporting
-    sb2.out_i32 = (int32_t*)h->yzfield.ptr; sb2.loop = true; sb2.ran_flag = h->d_small + 4;
-    sb2.bits = dense_bits ? dense_bits : (const uint32_t*)h->bits.ptr; sb2.nzw = (int)((nz + 31) / 32);
-    sb3.in_i32 = (const int32_t*)h->yzfield.ptr; sb3.loop = true; sb3.ran_flag = h->d_small + 5;
     // (moved up: the stand-by x sweep does the fold itself and needs to know where the report goes)
     const bool report = h->opt.envelope_on && h->h_flags_dev && !h->flags_pending && dense;
     bool folded = false;
-    if (standby) {
-        if (h->opt.standby_fold) {
-            sb3.fold_result = h->d_result; sb3.fold_report = report ? h->h_flags_dev : nullptr; sb3.fold_ticket = h->d_small + 23;
-            folded = true;
-        }
-        HIP_TRY(h, mark(4));                                    // (stage slot 3, the marching y sweep: nothing launched)
-        if (int rc = launch_envelope(h, 2, nullptr, nullptr, nullptr, nullptr, nx, ny, nz, resolution, vb,
-                                     h->d_small, general_guard, s, 0, nullptr, &sb2)) return rc;
-        launched_since_mark = true;
-        HIP_TRY(h, mark(5));
-        HIP_TRY(h, mark(6));                                    // (stage slot 5, the marching x sweep: nothing launched)
-        if (int rc = launch_envelope(h, 3, nullptr, nullptr, d_out, nullptr, nx, ny, nz, resolution, vb, h->d_small,
-                                     general_guard, s, 0, nullptr, &sb3)) return rc;
-        launched_since_mark = true;
-    } else if (predicted) {
-        // KE2 [general guard] -> KE3 [general guard], exact int32 plane values in between, each launch raising its far flag itself
-        DcExtra pr2 = plain2, pr3 = plain3;
-        pr2.ran_flag = h->d_small + 4;
-        pr3.ran_flag = h->d_small + 5;
-        if (row_any) {
-            // row bytes -> one bit per row, one byte per x-plane, "some plane is empty" (status word 22)
-            uint8_t* plane_any = row_any + nx * ny;
-            uint32_t* row_bits = (uint32_t*)(row_any + (((size_t)(nx * ny + nx) + 255) & ~(size_t)255));
-            const int row_words = (int)((ny + 31) / 32);
-            if (h->flat_score_reset) { h->flat_score_reset = false; HIP_TRY(h, hipMemsetAsync(h->d_small + 40, 0, 8, s)); }
-            hipLaunchKernelGGL(k_pack_row_flags, dim3((unsigned)std::min<int64_t>((nx + 15) / 16, 16)), dim3(1024), 0, s, row_any, (int)nx, (int)ny, row_words, row_bits, plane_any, h->d_small + 22, h->d_small + 40);
-            HIP_TRY(h, hipGetLastError());
-            pr2.row_bits = row_bits; pr2.row_words = row_words; pr2.plane_any = pr3.plane_any = plane_any;
-        }
-        HIP_TRY(h, mark(4));                                    // (stage slot 3, the marching y sweep: nothing launched)
-        if (int rc = launch_envelope(h, 2, (const int16_t*)h->zfield.ptr, nullptr, nullptr, nullptr, nx, ny, nz, resolution, vb,
-                                     h->d_small, general_guard, s, 0, nullptr, &pr2)) return rc;
-        launched_since_mark = true;
-        HIP_TRY(h, mark(5));
-        HIP_TRY(h, mark(6));                                    // (stage slot 5, the marching x sweep: nothing launched)
-        if (int rc = launch_envelope(h, 3, nullptr, nullptr, d_out, nullptr, nx, ny, nz, resolution, vb, h->d_small,
-                                     general_guard, s, 0, nullptr, &pr3)) return rc;
-        launched_since_mark = true;
-    } else {
-    if (select) {
-        // probe + decision in one launch (the probe's last workgroup decides); a forced tier needs no probe
-        DcDecide dy; dy.stage = 0; dy.dense_tried = dense; dy.handoff = handoff; dy.window_choice = window_choice;
-        if (h->opt.force_env < 0) {
-            if (int rc = launch_envelope(h, 2, (const int16_t*)h->zfield.ptr, nullptr, h->plane16.ptr, (int32_t*)h->yzfield.ptr,
-                                         nx, ny, nz, resolution, vb, h->d_small, general_guard, s, 0, h->d_small + 12,
-                                         !p16 ? &plain2 : nullptr, &dy)) return rc;
-        } else if (int rc = decide(0)) return rc;
-        // marching y sweep: general pipeline needed AND near-field; the probe also picks the window (radius 3 / radius 8)
-        h->inflight.guard = h->d_small + 8;
-        if (int rc = launch_sweep_y(h, (const int16_t*)h->zfield.ptr, zy_out, zy_side, nx, ny, nz, s, window_choice ? 3 : 0)) return rc;
-        if (window_choice) {
-            h->inflight.guard = h->d_small + 9;
-            if (int rc = launch_sweep_y(h, (const int16_t*)h->zfield.ptr, zy_out, zy_side, nx, ny, nz, s, 8)) return rc;
-        }
-        h->inflight.guard = general_guard;
-        launched_since_mark = true;
-    } else if (fused) {
-        if (int rc = launch_sweep_zy_fused(h, d_filled, zy_out, zy_side, nx, ny, nz, s)) return rc;
-        launched_since_mark = true;
-    } else {                                                    // (no far-field kernel for this shape / switched off: unbounded scans)
-        if (int rc = launch_sweep_y(h, (const int16_t*)h->zfield.ptr, zy_out, zy_side, nx, ny, nz, s)) return rc;
-        launched_since_mark = true;
-    }
-    HIP_TRY(h, mark(4));
-    if (select) {
-        if (int rc = launch_envelope(h, 2, (const int16_t*)h->zfield.ptr, nullptr, p16 ? h->plane16.ptr : nullptr, p16 ? (int32_t*)h->yzfield.ptr : nullptr,
-                                     nx, ny, nz, resolution, vb, h->d_small, h->d_small + 4, s, 0, nullptr, ex2)) return rc;
-        launched_since_mark = true;
-    }
-    HIP_TRY(h, mark(5));
-    // x sweep: same choice
-    if (!envelope || fused) h->inflight.far_y = nullptr;
-    else h->inflight.far_y = h->d_small + 4;             // (K3/16 raises far_y + 1 = far_x)
-    if (select) {
-        DcDecide dx; dx.stage = 1; dx.dense_tried = dense; dx.handoff = handoff; dx.window_choice = window_choice;
-        if (h->opt.force_env < 0) {
-            if (int rc = launch_envelope(h, 3, p16 ? (const int16_t*)h->plane16.ptr : nullptr, p16 ? (const int32_t*)h->yzfield.ptr : nullptr, d_out, nullptr,
-                                         nx, ny, nz, resolution, vb, h->d_small, general_guard, s, 0, h->d_small + 12, ex3, &dx)) return rc;
-        } else if (int rc = decide(1)) return rc;
-        h->inflight.guard = h->d_small + 10;
-        if (p16) {
-            if (int rc = launch_sweep_x16(h, (const int16_t*)h->plane16.ptr, (const int32_t*)h->yzfield.ptr, d_out, 0, nx, 0,
-                                          0, nx, ny, nz, 0, 0, 0, nx, resolution, vb, h->d_small, h->d_small + 2, s)) return rc;
+    if (standby || predicted) {
+        // KE2 [general guard] -> KE3 [general guard], exact int32 plane values in between, each launch raising its far flag itself:
+        // no probes, no marching launches
+        DcIo ke2, ke3;
+        ke2.out_i32 = yz; ke2.ran_flag = sw + kSwFarY;
+        ke3.in_i32 = yz; ke3.out = d_out; ke3.ran_flag = sw + kSwFarX;
+        if (standby) {                                          // LOOP form, z distances from the dense tier's bit field, self-reporting
+            ke2.loop = ke3.loop = true;
+            ke2.bits = dense_bits ? dense_bits : (const uint32_t*)h->bits.ptr; ke2.nzw = (int)((nz + 31) / 32);
+            if (h->opt.standby_fold) {
+                ke3.fold_result = h->d_result; ke3.fold_report = report ? h->h_flags_dev : nullptr; ke3.fold_ticket = sw + kSwFoldTicket;
+                folded = true;
+            }
         } else {
-            if (int rc = launch_sweep_x(h, (const int32_t*)h->yzfield.ptr, d_out, 0, nx, 0, ny, nz, 0, 0, 0, nx,
-                                        resolution, vb, h->d_small, h->d_small + 2, s, 0, -1, h->inflight.scan_x, h->inflight.far_y + 1)) return rc;
+            ke2.in16 = zf;
+            if (row_any) {
+                // row bytes -> one bit per row, one byte per x-plane, "some plane is empty" (kSwPlaneEmpty)
+                uint8_t* plane_any = row_any + nx * ny;
+                uint32_t* row_bits = (uint32_t*)(row_any + (((size_t)(nx * ny + nx) + 255) & ~(size_t)255));
+                const int row_words = (int)((ny + 31) / 32);
+                if (h->flat_score_reset) { h->flat_score_reset = false; HIP_TRY(h, hipMemsetAsync(sw + kSwFlatScore, 0, 8, s)); }
+                hipLaunchKernelGGL(k_pack_row_flags, dim3((unsigned)std::min<int64_t>((nx + 15) / 16, 16)), dim3(1024), 0, s, row_any, (int)nx, (int)ny, row_words, row_bits, plane_any, sw + kSwPlaneEmpty, sw + kSwFlatScore);
+                HIP_TRY(h, hipGetLastError());
+                ke2.row_bits = row_bits; ke2.row_words = row_words; ke2.plane_any = ke3.plane_any = plane_any;
+            }
         }
-        h->inflight.guard = general_guard;
+        HIP_TRY(h, mark(4));                                    // (stage slot 3, the marching y sweep: nothing launched)
+        if (int rc = launch_envelope(h, 2, ke2, nx, ny, nz, resolution, vb, general_guard, s)) return rc;
         launched_since_mark = true;
-    } else if (p16) {
-        if (int rc = launch_sweep_x16(h, (const int16_t*)h->plane16.ptr, (const int32_t*)h->yzfield.ptr, d_out, 0, nx, 0,
-                                      0, nx, ny, nz, 0, 0, 0, nx, resolution, vb, h->d_small, h->d_small + 2, s)) return rc;
+        HIP_TRY(h, mark(5));
+        HIP_TRY(h, mark(6));                                    // (stage slot 5, the marching x sweep: nothing launched)
+        if (int rc = launch_envelope(h, 3, ke3, nx, ny, nz, resolution, vb, general_guard, s)) return rc;
         launched_since_mark = true;
     } else {
-        if (int rc = launch_sweep_x(h, (const int32_t*)h->yzfield.ptr, d_out, 0, nx, 0, ny, nz, 0, 0, 0, nx,
-                                    resolution, vb, h->d_small, h->d_small + 2, s)) return rc;
+        // A probe-selected build (`select`): per axis a probe that decides, the marching sweep behind its guard word with bounded
+        // scans, and the far-field sweep behind the axis' far flag.  Every other build: one sweep per axis, unbounded scans, no far flag.
+        uint32_t* const far_y = select ? sw + kSwFarY : kUnbounded;
+        uint32_t* const far_x = select ? sw + kSwFarX : kUnbounded;
+        // the far-field pair: p16 + side table in between, or exact int32 values (always on shapes without the 16-bit plane
+        // field; behind kSwHandoff on the others)
+        DcIo ke2, ke3;
+        ke2.in16 = zf; ke3.out = d_out;
+        if (p16) { ke2.out = h->plane16.ptr; ke2.side_out = yz; ke3.in16 = (const int16_t*)h->plane16.ptr; ke3.side_in = yz; }
+        if (!p16 || handoff) { ke2.out_i32 = yz; ke3.in_i32 = yz; }
+        if (p16 && handoff) ke2.i32_flag = ke3.i32_flag = sw + kSwHandoff;
+        DcIo probe2;                                            // the y probe reads what KE2 reads (no hand-off flag: its own decision raises it)
+        probe2.in16 = zf; probe2.out = h->plane16.ptr; probe2.side_out = yz;
+        if (!p16) probe2.out_i32 = yz;
+        DcDecide dy, dx;
+        dy.stage = 0; dx.stage = 1;
+        dy.dense_tried = dx.dense_tried = dense; dy.handoff = dx.handoff = handoff; dy.window_choice = dx.window_choice = window_choice;
+        XSlab whole = XSlab::whole(nx);
+        whole.status = sw + kSwSlabStatus;
+        // y sweep
+        if (select) {
+            // probe + decision in one launch (the probe's last workgroup decides); a forced tier needs no probe
+            if (h->opt.force_env < 0) {
+                if (int rc = launch_envelope_probe(h, 2, probe2, nx, ny, nz, resolution, vb, general_guard, dy, s)) return rc;
+            } else if (int rc = launch_decide(h, dy, s)) return rc;
+            // marching y sweep: general pipeline needed AND near-field; the probe also picks the window (radius 3 / radius 8)
+            if (int rc = launch_sweep_y(h, zf, zy_out, zy_side, nx, ny, nz, sw + kSwMarchY, far_y, s)) return rc;
+            if (window_choice)
+                if (int rc = launch_sweep_y(h, zf, zy_out, zy_side, nx, ny, nz, sw + kSwMarchYWide, far_y, s, YWindow::r8)) return rc;
+        } else if (fused) {
+            if (int rc = launch_sweep_zy_fused(h, occ.mask, zy_out, zy_side, nx, ny, nz, general_guard, s)) return rc;
+        } else {                                                // (no far-field kernel for this shape / switched off: unbounded scans)
+            if (int rc = launch_sweep_y(h, zf, zy_out, zy_side, nx, ny, nz, general_guard, kUnbounded, s)) return rc;
+        }
         launched_since_mark = true;
-    }
-    HIP_TRY(h, mark(6));
-    if (select) {
-        if (int rc = launch_envelope(h, 3, p16 ? (const int16_t*)h->plane16.ptr : nullptr, p16 ? (const int32_t*)h->yzfield.ptr : nullptr, d_out, nullptr,
-                                     nx, ny, nz, resolution, vb, h->d_small, h->d_small + 5, s, 0, nullptr, ex3)) return rc;
+        HIP_TRY(h, mark(4));
+        if (select) {
+            if (int rc = launch_envelope(h, 2, ke2, nx, ny, nz, resolution, vb, sw + kSwFarY, s)) return rc;
+            launched_since_mark = true;
+        }
+        HIP_TRY(h, mark(5));
+        // x sweep: same choice
+        if (select) {
+            if (h->opt.force_env < 0) {
+                if (int rc = launch_envelope_probe(h, 3, ke3, nx, ny, nz, resolution, vb, general_guard, dx, s)) return rc;
+            } else if (int rc = launch_decide(h, dx, s)) return rc;
+        }
+        const uint32_t* const march_x_guard = select ? sw + kSwMarchX : general_guard;
+        if (p16) {
+            if (int rc = launch_sweep_x16(h, (const int16_t*)h->plane16.ptr, yz, d_out, whole, ny, nz, resolution, vb, march_x_guard, far_x, s)) return rc;
+        } else {
+            if (int rc = launch_sweep_x(h, yz, d_out, whole, ny, nz, resolution, vb, march_x_guard, far_x, s)) return rc;
+        }
         launched_since_mark = true;
+        HIP_TRY(h, mark(6));
+        if (select) {
+            if (int rc = launch_envelope(h, 3, ke3, nx, ny, nz, resolution, vb, sw + kSwFarX, s)) return rc;
+            launched_since_mark = true;
+        }
     }
-    }   // (!standby)
     // one kernel folds the maxima, publishes the status block (device copy for get_extrema, pinned host copy for the
     // next build's policy) and clears it for the next build
     // The report (status block -> pinned host memory + an event) is only taken when the previous report has been
@@ -1447,8 +1448,6 @@ int build_device_impl(sdfgpu_handle h, const uint8_t* d_filled, const void* d_ce
         h->far_pending = true;
     }
     h->small_clean = true;
-    h->inflight.guard = nullptr;
-    h->inflight.far_y = nullptr;
     if (report) {
         HIP_TRY(h, hipEventRecord(h->flags_ev, s));
         h->flags_pending = true;
@@ -1655,15 +1654,16 @@ void pack_cells_bits(const char* cells, size_t stride, size_t off, int unknown, 
 
 // Host cells / mask -> bits (team) -> device -> byte mask at d_mask_dst (n bytes), enqueued on `st`; the host buffer has been
 // consumed when this returns (the unpack kernel is stream-ordered behind the upload).
-int upload_packed(sdfgpu_handle h, const uint8_t* filled, const void* cells, size_t stride, size_t off, int unknown, int64_t n,
-                  uint8_t* d_mask_dst, hipStream_t st) {
+// d_mask_dst == kBitsOnly: the bits stay in h->stage_bits and are the caller's input.
+constexpr uint8_t* kBitsOnly = nullptr;
+int upload_packed(sdfgpu_handle h, const Occupancy& occ, int64_t n, uint8_t* d_mask_dst, hipStream_t st) {
     const size_t nbytes = ((size_t)n + 7) / 8, padded = (nbytes + 3) & ~(size_t)3;
     if (int rc = ensure(h, h->stage_bits, padded, "bit staging")) return rc;
     auto fill = [=](char* dst, size_t o, size_t len) {
         const size_t real = o >= nbytes ? 0 : std::min(len, nbytes - o);
         if (real) {
-            if (cells) pack_cells_bits(static_cast<const char*>(cells), stride, off, unknown, n, o, real, reinterpret_cast<uint8_t*>(dst));
-            else pack_mask_bits(filled, n, o, real, reinterpret_cast<uint8_t*>(dst));
+            if (occ.cells) pack_cells_bits(static_cast<const char*>(occ.cells), occ.stride, occ.off, occ.unknown, n, o, real, reinterpret_cast<uint8_t*>(dst));
+            else pack_mask_bits(occ.mask, n, o, real, reinterpret_cast<uint8_t*>(dst));
         }
         if (real < len) memset(dst + real, 0, len - real);
     };
@@ -1675,7 +1675,7 @@ int upload_packed(sdfgpu_handle h, const uint8_t* filled, const void* cells, siz
         HIP_TRY(h, hipMemcpyAsync(h->stage_bits.ptr, tmp.data(), padded, hipMemcpyHostToDevice, st));
         HIP_TRY(h, hipStreamSynchronize(st));                   // (tmp goes out of scope)
     }
-    if (!d_mask_dst) return SDFGPU_OK;                          // (the host-buffer builds: the bits are the build's input)
+    if (d_mask_dst == kBitsOnly) return SDFGPU_OK;              // (the host-buffer builds: the bits are the build's input)
     const int64_t nch = (n + 15) / 16;
     hipLaunchKernelGGL(k_unpack_bits_mask, dim3((unsigned)((nch + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
                        (const uint32_t*)h->stage_bits.ptr, d_mask_dst, n);
@@ -1690,25 +1690,39 @@ int upload_bits(sdfgpu_handle h, const uint32_t* bits, int64_t n, hipStream_t st
     return copy_from_host(h, h->stage_bits.ptr, bits, bytes, st);
 }
 
+// `occ` is host memory (occ.bits: the caller's occupancy is already one bit per voxel, sdfgpu_build_bits).
+// The cell records of the two tagged entry points in stage_in: uploaded, or (cells == nullptr) those the previous tagged call on
+// this handle left on the device.
+int stage_tagged_records(sdfgpu_handle h, const void* cells, size_t bytes) {
+    if (!cells) {
+        if (h->tag_cached_bytes == 0 || h->tag_cached_bytes != bytes)
+            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cells is null and the handle holds no cell records of this size");
+        return SDFGPU_OK;
+    }
+    h->tag_cached_bytes = 0;
+    if (int rc = ensure(h, h->stage_in, bytes, "input staging")) return rc;
+    if (int rc = copy_from_host(h, h->stage_in.ptr, cells, bytes)) return rc;
+    h->tag_cached_bytes = bytes;
+    return SDFGPU_OK;
+}
+
 // d_out_user != nullptr: the field stays on the device in the caller's buffer (no download; out_sdf is unused)
-// bits_in != nullptr: the caller's occupancy is already one bit per voxel (sdfgpu_build_bits)
-int build_host_impl(sdfgpu_handle h, const uint8_t* filled, const void* cells, size_t stride, size_t off,
-                    int unknown, int64_t nx, int64_t ny, int64_t nz, double resolution, int vb, float* out_sdf,
-                    double* out_max, double* out_min, float* d_out_user = nullptr, const uint32_t* bits_in = nullptr) {
+int build_host_impl(sdfgpu_handle h, const Occupancy& occ, int64_t nx, int64_t ny, int64_t nz, double resolution, int vb, float* out_sdf,
+                    double* out_max, double* out_min, float* d_out_user = nullptr) {
     if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-    if ((!filled && !cells && !bits_in) || (!out_sdf && !d_out_user)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
+    if (occ.null() || (!out_sdf && !d_out_user)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
     if (int rc = check_resolution(h, resolution)) return rc;                  // (before the upload: nothing is enqueued for a refused call)
     if (int rc = check_dims(h, nx, ny, nz)) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     const int64_t n = nx * ny * nz;
-    const size_t in_bytes = cells ? (size_t)n * stride : (size_t)n;
+    const size_t in_bytes = occ.cells ? (size_t)n * occ.stride : (size_t)n;
     h->tag_cached_bytes = 0;                        // (stage_in is about to be overwritten)
     // Round 5: the host's thread team classifies the caller's buffer into one bit per voxel while it fills the pinned staging
     // chunk, and 1/8 B per voxel crosses PCIe (16 MiB at 512^3 instead of 128 MiB of mask or 1 GiB of COLLISION_CELL records);
     // k_unpack_bits_mask spreads them into the byte mask on the device.  Same predicate as the device classifier
     // (pack_cells_bits); "host_pack" = 0 keeps the upload-and-classify-on-device path (device-resident cells always take it).
-    const bool packed = !bits_in && (h->opt.host_pack == 2 || (h->opt.host_pack == 1 && in_bytes >= kPinMin));
-    if (!packed && !bits_in) if (int rc = ensure(h, h->stage_in, in_bytes, "input staging")) return rc;
+    const bool packed = !occ.bits && (h->opt.host_pack == 2 || (h->opt.host_pack == 1 && in_bytes >= kPinMin));
+    if (!packed && !occ.bits) if (int rc = ensure(h, h->stage_in, in_bytes, "input staging")) return rc;
     if (!d_out_user) if (int rc = ensure(h, h->stage_out, (size_t)n * 4, "output staging")) return rc;
     float* const d_out = d_out_user ? d_out_user : (float*)h->stage_out.ptr;
     const bool timing = getenv("SDFGPU_HOST_TIMING") != nullptr;
@@ -1716,14 +1730,15 @@ int build_host_impl(sdfgpu_handle h, const uint8_t* filled, const void* cells, s
     const double t1 = now();
     // (out_sdf is scratch from here on: include/sdfgpu.h documents that its contents are undefined when the call fails)
     // (round 6: the uploaded bits ARE the build's input -- no byte mask is spread out on the device and packed again by K0)
-    if (packed) { if (int rc0 = upload_packed(h, filled, cells, stride, off, unknown, n, nullptr, nullptr)) return rc0; }
-    else if (bits_in) { if (int rc0 = upload_bits(h, bits_in, n, nullptr)) return rc0; }
-    else if (int rc0 = copy_from_host(h, h->stage_in.ptr, cells ? cells : (const void*)filled, in_bytes)) return rc0;
+    if (packed) { if (int rc0 = upload_packed(h, occ, n, kBitsOnly, kNullStream)) return rc0; }
+    else if (occ.bits) { if (int rc0 = upload_bits(h, occ.bits, n, kNullStream)) return rc0; }
+    else if (int rc0 = copy_from_host(h, h->stage_in.ptr, occ.cells ? occ.cells : (const void*)occ.mask, in_bytes)) return rc0;
+    // what the upload left on the device (read the staging pointers behind it: the upload may have allocated them)
+    const Occupancy d_occ = (packed || occ.bits) ? Occupancy::of_bits((const uint32_t*)h->stage_bits.ptr)
+                            : occ.cells ? Occupancy::of_cells(h->stage_in.ptr, occ.stride, occ.off, occ.unknown)
+                                        : Occupancy::of_mask((const uint8_t*)h->stage_in.ptr);
     const double t2 = now();
-    int rc = (packed || bits_in) ? build_device_impl(h, nullptr, nullptr, 0, 0, 0, nx, ny, nz, resolution, vb, d_out, nullptr, (const uint32_t*)h->stage_bits.ptr)
-                    : build_device_impl(h, cells ? nullptr : (const uint8_t*)h->stage_in.ptr,
-                                        cells ? h->stage_in.ptr : nullptr, stride, off, unknown, nx, ny, nz, resolution,
-                                        vb, d_out, nullptr);
+    int rc = build_device_impl(h, d_occ, nx, ny, nz, resolution, vb, d_out, kNullStream);
     if (rc) return rc;
     const double t3 = now();
     if (!d_out_user) if (int rc2 = copy_to_host(h, out_sdf, h->stage_out.ptr, (size_t)n * 4)) return rc2;
@@ -1764,10 +1779,9 @@ int components_impl(sdfgpu_handle h, const uint32_t* d_bits, int64_t nx, int64_t
 }
 
 // host mask / cell records -> bits (host team, 1 bit per voxel over PCIe) -> labels in the output staging
-int components_host(sdfgpu_handle h, const uint8_t* filled, const void* cells, size_t stride, size_t occ_off, int64_t nx, int64_t ny,
-                    int64_t nz, uint32_t* out_count) {
+int components_host(sdfgpu_handle h, const Occupancy& occ, int64_t nx, int64_t ny, int64_t nz, uint32_t* out_count) {
     const int64_t n = nx * ny * nz;
-    if (int rc = upload_packed(h, filled, cells, stride, occ_off, 0, n, nullptr, nullptr)) return rc;
+    if (int rc = upload_packed(h, occ, n, kBitsOnly, kNullStream)) return rc;
     if (int rc = ensure(h, h->stage_out, (size_t)n * 4, "output staging")) return rc;
     return components_impl(h, (const uint32_t*)h->stage_bits.ptr, nx, ny, nz, (uint32_t*)h->stage_out.ptr, out_count, nullptr);
 }
@@ -1842,7 +1856,8 @@ int stage_labels_selection(sdfgpu_handle h, const uint32_t* labels, const uint8_
     const bool selected = labels ? select != nullptr : (class_mask & 7) != 7;
     if (selected) {
         if (labels || class_mask == 1) {                       // a byte mask, or FILLED: the build's packers (occupancy > 0.5f)
-            if (int rc = upload_packed(h, labels ? select : nullptr, labels ? nullptr : cells, stride, occ_off, 0, n, nullptr, nullptr)) return rc;
+            const Occupancy occ = labels ? Occupancy::of_mask(select) : Occupancy::of_cells(cells, stride, occ_off, 0);
+            if (int rc = upload_packed(h, occ, n, kBitsOnly, kNullStream)) return rc;
         } else {
             const size_t nbytes = ((size_t)n + 7) / 8, padded = (nbytes + 3) & ~(size_t)3;
             if (int rc = ensure(h, h->stage_bits, padded, "bit staging")) return rc;
@@ -2034,15 +2049,15 @@ int convex_sdf(sdfgpu_handle h, size_t stride, size_t occ_off, size_t obj_off, i
     };
     // ExtractSignedDistanceField(+inf, {}, true, true): every filled cell (an empty id list is "any object", :826)
     HIP_TRY(h, classify(0));
-    if (int rc = build_device_impl(h, (const uint8_t*)h->tagmask.ptr, nullptr, 0, 0, 0, nx, ny, nz, resolution, add_virtual_border ? 1 : 0,
-                                   (float*)h->stage_out.ptr, nullptr))
+    const Occupancy tagged = Occupancy::of_mask((const uint8_t*)h->tagmask.ptr);
+    if (int rc = build_device_impl(h, tagged, nx, ny, nz, resolution, add_virtual_border ? 1 : 0, (float*)h->stage_out.ptr, kNullStream))
         return rc;
     if (add_virtual_border) return SDFGPU_OK;
     // ExtractFreeAndNamedObjectsSignedDistanceField(+inf, true): the free-space SDF above, the named-object SDF, combined as the
     // host does it (tagged_object_collision_map.hpp)
     HIP_TRY(h, classify(1));
-    if (int rc = build_device_impl(h, (const uint8_t*)h->tagmask.ptr, nullptr, 0, 0, 0, nx, ny, nz, resolution, 0, (float*)h->cx_field.ptr,
-                                   nullptr))
+    const int no_border = 0;
+    if (int rc = build_device_impl(h, tagged, nx, ny, nz, resolution, no_border, (float*)h->cx_field.ptr, kNullStream))
         return rc;
     HIP_TRY(h, cx_combine((float*)h->stage_out.ptr, (const float*)h->cx_field.ptr, (uint64_t)n, nullptr));
     return SDFGPU_OK;
@@ -2157,8 +2172,7 @@ const char* sdfgpu_last_error(sdfgpu_handle h) { return h ? h->error.c_str() : g
 int sdfgpu_build(sdfgpu_handle h, const uint8_t* filled, int64_t nx, int64_t ny, int64_t nz, double resolution,
                  int add_virtual_border, float* out_sdf, double* out_max, double* out_min) {
     return rz_wrap(h, nullptr, [&]() -> int {
-        return build_host_impl(h, filled, nullptr, 0, 0, 0, nx, ny, nz, resolution, add_virtual_border, out_sdf,
-                               out_max, out_min);
+        return build_host_impl(h, Occupancy::of_mask(filled), nx, ny, nz, resolution, add_virtual_border, out_sdf, out_max, out_min);
     });
 }
 
@@ -2167,9 +2181,8 @@ int sdfgpu_build_cells(sdfgpu_handle h, const void* cells, size_t cell_stride, s
                        int add_virtual_border, float* out_sdf, double* out_max, double* out_min) {
     return rz_wrap(h, nullptr, [&]() -> int {
         if (h && !cells) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cells is null");
-        if (h && (cell_stride < 4 || (cell_stride % 4) || (occupancy_offset % 4) || occupancy_offset + 4 > cell_stride))
-            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cell_stride/occupancy_offset must be 4-byte aligned and in range");
-        return build_host_impl(h, nullptr, cells, cell_stride, occupancy_offset, unknown_is_filled, nx, ny, nz,
+        if (h) if (int rc = check_cell_layout(h, cell_stride, occupancy_offset)) return rc;
+        return build_host_impl(h, Occupancy::of_cells(cells, cell_stride, occupancy_offset, unknown_is_filled), nx, ny, nz,
                                resolution, add_virtual_border, out_sdf, out_max, out_min);
     });
 }
@@ -2178,7 +2191,8 @@ int sdfgpu_build_to_device(sdfgpu_handle h, const uint8_t* filled, int64_t nx, i
                            int add_virtual_border, float* d_out_sdf, double* out_max, double* out_min) {
     return rz_wrap(h, nullptr, [&]() -> int {
         if (h && !d_out_sdf) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "d_out_sdf is null");
-        return build_host_impl(h, filled, nullptr, 0, 0, 0, nx, ny, nz, resolution, add_virtual_border, nullptr, out_max, out_min,
+        float* const no_host_field = nullptr;
+        return build_host_impl(h, Occupancy::of_mask(filled), nx, ny, nz, resolution, add_virtual_border, no_host_field, out_max, out_min,
                                d_out_sdf);
     });
 }
@@ -2189,10 +2203,10 @@ int sdfgpu_build_cells_to_device(sdfgpu_handle h, const void* cells, size_t cell
     return rz_wrap(h, nullptr, [&]() -> int {
         if (h && !cells) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cells is null");
         if (h && !d_out_sdf) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "d_out_sdf is null");
-        if (h && (cell_stride < 4 || (cell_stride % 4) || (occupancy_offset % 4) || occupancy_offset + 4 > cell_stride))
-            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cell_stride/occupancy_offset must be 4-byte aligned and in range");
-        return build_host_impl(h, nullptr, cells, cell_stride, occupancy_offset, unknown_is_filled, nx, ny, nz, resolution,
-                               add_virtual_border, nullptr, out_max, out_min, d_out_sdf);
+        if (h) if (int rc = check_cell_layout(h, cell_stride, occupancy_offset)) return rc;
+        float* const no_host_field = nullptr;
+        return build_host_impl(h, Occupancy::of_cells(cells, cell_stride, occupancy_offset, unknown_is_filled), nx, ny, nz, resolution,
+                               add_virtual_border, no_host_field, out_max, out_min, d_out_sdf);
     });
 }
 
@@ -2200,8 +2214,7 @@ int sdfgpu_build_device(sdfgpu_handle h, const uint8_t* d_filled, int64_t nx, in
                         double resolution, int add_virtual_border, float* d_out_sdf, void* stream) {
     return rz_wrap(h, stream, [&]() -> int {
         if (h && !d_filled) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "d_filled is null");
-        return build_device_impl(h, d_filled, nullptr, 0, 0, 0, nx, ny, nz, resolution, add_virtual_border, d_out_sdf,
-                                 (hipStream_t)stream);
+        return build_device_impl(h, Occupancy::of_mask(d_filled), nx, ny, nz, resolution, add_virtual_border, d_out_sdf, (hipStream_t)stream);
     });
 }
 
@@ -2210,7 +2223,7 @@ int sdfgpu_build_cells_device(sdfgpu_handle h, const void* d_cells, size_t cell_
                               int add_virtual_border, float* d_out_sdf, void* stream) {
     return rz_wrap(h, stream, [&]() -> int {
         if (h && !d_cells) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "d_cells is null");
-        return build_device_impl(h, nullptr, d_cells, cell_stride, occupancy_offset, unknown_is_filled, nx, ny, nz,
+        return build_device_impl(h, Occupancy::of_cells(d_cells, cell_stride, occupancy_offset, unknown_is_filled), nx, ny, nz,
                                  resolution, add_virtual_border, d_out_sdf, (hipStream_t)stream);
     });
 }
@@ -2219,8 +2232,7 @@ int sdfgpu_build_bits_device(sdfgpu_handle h, const uint32_t* d_bits, int64_t nx
                              double resolution, int add_virtual_border, float* d_out_sdf, void* stream) {
     return rz_wrap(h, stream, [&]() -> int {
         if (h && !d_bits) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "d_bits is null");
-        return build_device_impl(h, nullptr, nullptr, 0, 0, 0, nx, ny, nz, resolution, add_virtual_border, d_out_sdf,
-                                 (hipStream_t)stream, d_bits);
+        return build_device_impl(h, Occupancy::of_bits(d_bits), nx, ny, nz, resolution, add_virtual_border, d_out_sdf, (hipStream_t)stream);
     });
 }
 
@@ -2228,8 +2240,7 @@ int sdfgpu_build_bits(sdfgpu_handle h, const uint32_t* bits, int64_t nx, int64_t
                       int add_virtual_border, float* out_sdf, double* out_max, double* out_min) {
     return rz_wrap(h, nullptr, [&]() -> int {
         if (h && !bits) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "bits is null");
-        return build_host_impl(h, nullptr, nullptr, 0, 0, 0, nx, ny, nz, resolution, add_virtual_border, out_sdf, out_max, out_min,
-                               nullptr, bits);
+        return build_host_impl(h, Occupancy::of_bits(bits), nx, ny, nz, resolution, add_virtual_border, out_sdf, out_max, out_min);
     });
 }
 
@@ -2257,10 +2268,10 @@ int sdfgpu_upload_classified(sdfgpu_handle h, const uint8_t* filled, const void*
         if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
         if ((!filled && !cells) || !d_mask) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
         if (n <= 0) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "voxel count must be positive");
-        if (cells && (cell_stride < 4 || (cell_stride % 4) || (occupancy_offset % 4) || occupancy_offset + 4 > cell_stride))
-            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cell_stride/occupancy_offset must be 4-byte aligned and in range");
+        if (cells) if (int rc = check_cell_layout(h, cell_stride, occupancy_offset)) return rc;
         HIP_TRY(h, hipSetDevice(h->device));
-        return upload_packed(h, cells ? nullptr : filled, cells, cell_stride, occupancy_offset, unknown_is_filled, n, d_mask, (hipStream_t)stream);
+        const Occupancy occ = cells ? Occupancy::of_cells(cells, cell_stride, occupancy_offset, unknown_is_filled) : Occupancy::of_mask(filled);
+        return upload_packed(h, occ, n, d_mask, (hipStream_t)stream);
     });
 }
 
@@ -2291,15 +2302,13 @@ int sdfgpu_get_extrema(sdfgpu_handle h, double* out_max, double* out_min) {
     // (the build's own event, not its stream: the stream is the caller's and may be gone by now -- ADVICE r4)
     HIP_TRY(h, h->build_order.host_wait());
     HIP_TRY(h, hipMemcpy(v, h->d_result, sizeof v, hipMemcpyDeviceToHost));
-    return sdfgpu_extrema_from_dsq(v[0], v[1], h->last.last_resolution, out_max, out_min);
+    return sdfgpu_extrema_from_dsq(v[kSwMaxFree], v[kSwMaxFilled], h->last.last_resolution, out_max, out_min);
 }
 
 int sdfgpu_sweep_zy_tiered_device(sdfgpu_handle h, const uint8_t* d_filled, int64_t nxs, int64_t ny, int64_t nz,
                                   int32_t* d_plane_dsq, uint32_t* d_far, void* stream) {
     return rz_wrap(h, stream, [&]() -> int {
         if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-        h->inflight.guard = nullptr;
-        h->inflight.far_y = nullptr;
         if (!d_filled || !d_plane_dsq) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null device pointer");
         if (int rc = check_dims(h, nxs, ny, nz)) return rc;
         HIP_TRY(h, hipSetDevice(h->device));
@@ -2313,33 +2322,28 @@ int sdfgpu_sweep_zy_tiered_device(sdfgpu_handle h, const uint8_t* d_filled, int6
                             (nz % 4) == 0 && (reinterpret_cast<uintptr_t>(d_plane_dsq) % 16) == 0;
         if (!tiered) {
             if (d_far) HIP_TRY(h, hipMemsetAsync(d_far, 0, 4, s));           // (no probe ran: "else to 0", sdfgpu.h)
-            if (fused_zy_eligible(h, d_filled, d_plane_dsq, nz)) return launch_sweep_zy_fused(h, d_filled, d_plane_dsq, nullptr, nxs, ny, nz, s);
+            if (fused_zy_eligible(h, d_filled, d_plane_dsq, nz)) return launch_sweep_zy_fused(h, d_filled, d_plane_dsq, kNoSideTable, nxs, ny, nz, kUnguarded, s);
             if (int rc = ensure(h, h->zfield, (size_t)n * 2, "z field")) return rc;
-            if (int rc = launch_sweep_z(h, d_filled, nullptr, 0, 0, 0, nxs, ny, nz, (int16_t*)h->zfield.ptr, s)) return rc;
-            return launch_sweep_y(h, (const int16_t*)h->zfield.ptr, d_plane_dsq, nullptr, nxs, ny, nz, s);
+            if (int rc = launch_sweep_z(h, Occupancy::of_mask(d_filled), nxs, ny, nz, (int16_t*)h->zfield.ptr, kUnguarded, s)) return rc;
+            return launch_sweep_y(h, (const int16_t*)h->zfield.ptr, d_plane_dsq, kNoSideTable, nxs, ny, nz, kUnguarded, kUnbounded, s);
         }
         // K1, then the y sweep picked on the device: probe -> decide -> marching (bounded scan) / envelope, int32 output
         if (int rc = ensure(h, h->zfield, (size_t)n * 2, "z field")) return rc;
         HIP_TRY(h, hipMemsetAsync(h->d_small, 0, 128, s));
         h->small_clean = false;
-        if (int rc = launch_sweep_z(h, d_filled, nullptr, 0, 0, 0, nxs, ny, nz, (int16_t*)h->zfield.ptr, s)) return rc;
-        DcExtra ex;
-        ex.out_i32 = d_plane_dsq;
+        if (int rc = launch_sweep_z(h, Occupancy::of_mask(d_filled), nxs, ny, nz, (int16_t*)h->zfield.ptr, kUnguarded, s)) return rc;
+        uint32_t* const sw = h->d_small;
+        DcIo ke2;                                                   // z field -> the caller's int32 plane field; no field is finished here:
+        ke2.in16 = (const int16_t*)h->zfield.ptr; ke2.out_i32 = d_plane_dsq;
+        const double unit = 1.0;                                    // ... no resolution,
+        const int no_border = 0;                                    // ... no virtual border
         DcDecide dy; dy.stage = 0;
         if (h->opt.force_env < 0) {
-            if (int rc = launch_envelope(h, 2, (const int16_t*)h->zfield.ptr, nullptr, nullptr, nullptr, nxs, ny, nz, 1.0, 0,
-                                         h->d_small, nullptr, s, 0, h->d_small + 12, &ex, &dy)) return rc;
-        } else if (int rc = launch_decide(h, 0, false, s)) return rc;
-        h->inflight.guard = h->d_small + 8;
-        h->inflight.far_y = h->d_small + 4;
-        h->inflight.scan_y = kScanExpectNear;
-        int rc = launch_sweep_y(h, (const int16_t*)h->zfield.ptr, d_plane_dsq, nullptr, nxs, ny, nz, s);
-        h->inflight.guard = nullptr;
-        h->inflight.far_y = nullptr;
-        if (rc) return rc;
-        if (int rc2 = launch_envelope(h, 2, (const int16_t*)h->zfield.ptr, nullptr, nullptr, nullptr, nxs, ny, nz, 1.0, 0,
-                                      h->d_small, h->d_small + 4, s, 0, nullptr, &ex)) return rc2;
-        if (d_far) HIP_TRY(h, hipMemcpyAsync(d_far, h->d_small + 4, 4, hipMemcpyDeviceToDevice, s));
+            if (int rc = launch_envelope_probe(h, 2, ke2, nxs, ny, nz, unit, no_border, kUnguarded, dy, s)) return rc;
+        } else if (int rc = launch_decide(h, dy, s)) return rc;
+        if (int rc = launch_sweep_y(h, ke2.in16, d_plane_dsq, kNoSideTable, nxs, ny, nz, sw + kSwMarchY, sw + kSwFarY, s)) return rc;
+        if (int rc = launch_envelope(h, 2, ke2, nxs, ny, nz, unit, no_border, sw + kSwFarY, s)) return rc;
+        if (d_far) HIP_TRY(h, hipMemcpyAsync(d_far, sw + kSwFarY, 4, hipMemcpyDeviceToDevice, s));
         HIP_TRY(h, hipMemsetAsync(h->d_small, 0, 128, s));
         h->small_clean = true;
         return SDFGPU_OK;
@@ -2365,35 +2369,29 @@ int sdfgpu_sweep_x_lines_device(sdfgpu_handle h, const int32_t* d_plane_dsq, int
         if (int rc = check_dims(h, nx, ny_global, nz)) return rc;
         HIP_TRY(h, hipSetDevice(h->device));
         hipStream_t s = (hipStream_t)stream;
-        h->inflight.guard = nullptr;
-        h->inflight.far_y = nullptr;
         HIP_TRY(h, h->build_order.wait(s));
         StreamOrder::RecordAtExit order_end{h->build_order, s};
         const bool tiered = h->opt.envelope_on && far_geometry_ok(h, 3, nx, nys, nz, ny_global) &&
                             (reinterpret_cast<uintptr_t>(d_plane_dsq) % 16) == 0;
         h->last.last_dc_x = 0;
         h->last.last_lines_tiered = tiered;
+        XSlab rows = XSlab::whole(nx);                              // every plane, rows [y_global, y_global + nys) of ny_global
+        rows.y_off = y_global; rows.ny_glob = ny_global;
         if (!tiered) {
-            if (int rc = launch_sweep_x(h, d_plane_dsq, d_out_sdf, 0, nx, 0, nys, nz, 0, 0, 0, nx, resolution, add_virtual_border,
-                                        d_maxdsq, nullptr, s, y_global, ny_global)) return rc;
+            if (int rc = launch_sweep_x(h, d_plane_dsq, d_out_sdf, rows, nys, nz, resolution, add_virtual_border, kUnguarded, kUnbounded, s)) return rc;
             return h->opt.defer_fold ? SDFGPU_OK : fold_slots(h, d_maxdsq, s);
         }
-        HIP_TRY(h, hipMemsetAsync(h->d_small, 0, 128, s));
+        uint32_t* const sw = h->d_small;
+        HIP_TRY(h, hipMemsetAsync(sw, 0, 128, s));
         h->small_clean = false;
-        DcExtra ex;
-        ex.in_i32 = d_plane_dsq; ex.y_off = y_global; ex.ny_glob = ny_global;
+        DcIo ke3;
+        ke3.in_i32 = d_plane_dsq; ke3.out = d_out_sdf; ke3.y_off = y_global; ke3.ny_glob = ny_global;
         DcDecide dx; dx.stage = 1;
         if (h->opt.force_env < 0) {
-            if (int rc = launch_envelope(h, 3, nullptr, nullptr, d_out_sdf, nullptr, nx, nys, nz, resolution, add_virtual_border,
-                                         h->d_small, nullptr, s, 0, h->d_small + 12, &ex, &dx)) return rc;
-        } else if (int rc = launch_decide(h, 1, false, s)) return rc;
-        h->inflight.guard = h->d_small + 10;
-        int rc = launch_sweep_x(h, d_plane_dsq, d_out_sdf, 0, nx, 0, nys, nz, 0, 0, 0, nx, resolution, add_virtual_border,
-                                d_maxdsq, nullptr, s, y_global, ny_global, kScanExpectNear, h->d_small + 5);
-        h->inflight.guard = nullptr;
-        if (rc) return rc;
-        if (int rc2 = launch_envelope(h, 3, nullptr, nullptr, d_out_sdf, nullptr, nx, nys, nz, resolution, add_virtual_border,
-                                      h->d_small, h->d_small + 5, s, 0, nullptr, &ex)) return rc2;
+            if (int rc = launch_envelope_probe(h, 3, ke3, nx, nys, nz, resolution, add_virtual_border, kUnguarded, dx, s)) return rc;
+        } else if (int rc = launch_decide(h, dx, s)) return rc;
+        if (int rc = launch_sweep_x(h, d_plane_dsq, d_out_sdf, rows, nys, nz, resolution, add_virtual_border, sw + kSwMarchX, sw + kSwFarX, s)) return rc;
+        if (int rc = launch_envelope(h, 3, ke3, nx, nys, nz, resolution, add_virtual_border, sw + kSwFarX, s)) return rc;
         if (!h->opt.defer_fold) if (int rc3 = fold_slots(h, d_maxdsq, s)) return rc3;
         HIP_TRY(h, hipMemsetAsync(h->d_small, 0, 128, s));
         h->small_clean = true;
@@ -2412,13 +2410,13 @@ int sdfgpu_sweep_x_device(sdfgpu_handle h, const int32_t* d_plane_dsq, int64_t h
         if (halo_lo < 0 || halo_hi < 0 || x_global < 0 || x_global + nxs > nx_global)
             return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "inconsistent slab geometry");
         if (int rc = check_resolution(h, resolution)) return rc;
-        h->inflight.guard = nullptr;
-        h->inflight.far_y = nullptr;
         if (int rc = check_dims(h, halo_lo + nxs + halo_hi, ny, nz)) return rc;
         if (int rc = check_dims(h, nx_global, ny, nz)) return rc;
         HIP_TRY(h, hipSetDevice(h->device));
-        if (int rc = launch_sweep_x(h, d_plane_dsq, d_out_sdf, halo_lo, nxs, halo_hi, ny, nz, lo_truncated, hi_truncated,
-                                    x_global, nx_global, resolution, add_virtual_border, d_maxdsq, d_status,
+        XSlab slab;
+        slab.halo_lo = halo_lo; slab.nxs = nxs; slab.halo_hi = halo_hi; slab.lo_trunc = lo_truncated; slab.hi_trunc = hi_truncated;
+        slab.x_global = x_global; slab.nx_global = nx_global; slab.status = d_status;
+        if (int rc = launch_sweep_x(h, d_plane_dsq, d_out_sdf, slab, ny, nz, resolution, add_virtual_border, kUnguarded, kUnbounded,
                                     (hipStream_t)stream)) return rc;
         return h->opt.defer_fold ? SDFGPU_OK : fold_slots(h, d_maxdsq, (hipStream_t)stream);
     });
@@ -2431,7 +2429,7 @@ int sdfgpu_pack_bits_device(sdfgpu_handle h, const uint8_t* d_filled, int64_t n_
         if (!d_filled || !d_bits) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null device pointer");
         if (n_rows <= 0 || nz <= 0 || (nz % 32) != 0) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "pack_bits needs nz % 32 == 0");
         HIP_TRY(h, hipSetDevice(h->device));
-        return launch_pack_bits(h, d_filled, nullptr, 0, 0, 0, n_rows * nz, d_bits, (hipStream_t)stream);
+        return launch_pack_bits(h, Occupancy::of_mask(d_filled), n_rows * nz, d_bits, (hipStream_t)stream);
     });
 }
 
@@ -2444,10 +2442,10 @@ int sdfgpu_dense_ball_device(sdfgpu_handle h, const uint32_t* d_bits, int64_t ro
         if (out_lo < 0 || out_hi <= out_lo || out_hi > rows_x) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "inconsistent slab geometry");
         if (int rc = check_resolution(h, resolution)) return rc;
         if (int rc = check_dims(h, rows_x, ny, nz)) return rc;
-        if (!dense_eligible(h, nz, 0)) return fail(h, SDFGPU_ERR_UNSUPPORTED_SIZE, "dense kernel needs nz = 32 * 2^k <= 2048");
+        if (!dense_eligible(h, nz)) return fail(h, SDFGPU_ERR_UNSUPPORTED_SIZE, "dense kernel needs nz = 32 * 2^k <= 2048");
         HIP_TRY(h, hipSetDevice(h->device));
-        if (int rc = launch_ball_dense(h, d_bits, d_out_sdf, rows_x, out_lo, out_hi, ny, nz, resolution, d_maxdsq,
-                                       d_uncertified, (hipStream_t)stream)) return rc;
+        if (int rc = launch_ball_dense(h, d_bits, d_out_sdf, rows_x, out_lo, out_hi, ny, nz, resolution, d_uncertified, BallMode{},
+                                       (hipStream_t)stream)) return rc;
         return h->opt.defer_fold ? SDFGPU_OK : fold_slots(h, d_maxdsq, (hipStream_t)stream);
     });
 }
@@ -2469,7 +2467,7 @@ int sdfgpu_slab_dense_phase(sdfgpu_handle h, int phase, const uint8_t* d_mask_sl
             return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "inconsistent slab geometry");
         if (int rc = check_resolution(h, resolution)) return rc;
         if (int rc = check_dims(h, halo_lo + nxs + halo_hi, ny, nz)) return rc;
-        if (!dense_eligible(h, nz, 0)) return fail(h, SDFGPU_ERR_UNSUPPORTED_SIZE, "dense kernel needs nz = 32 * 2^k <= 2048");
+        if (!dense_eligible(h, nz)) return fail(h, SDFGPU_ERR_UNSUPPORTED_SIZE, "dense kernel needs nz = 32 * 2^k <= 2048");
         HIP_TRY(h, hipSetDevice(h->device));
         hipStream_t s = (hipStream_t)stream;
         const int64_t plane = ny * nz, wplane = ny * (nz / 32), rows_x = halo_lo + nxs + halo_hi;
@@ -2478,12 +2476,12 @@ int sdfgpu_slab_dense_phase(sdfgpu_handle h, int phase, const uint8_t* d_mask_sl
         const int64_t i_lo = (split && halo_lo) ? hb : 0, i_hi = (split && halo_hi) ? nxs - hb : nxs;
         auto pack = [&](int64_t p0, int64_t p1) -> int {
             if (p1 <= p0) return SDFGPU_OK;
-            return launch_pack_bits(h, d_mask_slab + p0 * plane, nullptr, 0, 0, 0, (p1 - p0) * plane, own + p0 * wplane, s);
+            return launch_pack_bits(h, Occupancy::of_mask(d_mask_slab + p0 * plane), (p1 - p0) * plane, own + p0 * wplane, s);
         };
         auto ball = [&](int64_t p0, int64_t p1) -> int {
             if (p1 <= p0) return SDFGPU_OK;
             return launch_ball_dense(h, d_bits_ext, d_out + p0 * plane, rows_x, halo_lo + p0, halo_lo + p1, ny, nz, resolution,
-                                     d_small, d_small + 3, s);
+                                     d_small + kSwUncertified, BallMode{}, s);
         };
         switch (phase) {
         case 0:
@@ -2528,9 +2526,7 @@ int sdfgpu_build_tagged_cells(sdfgpu_handle h, const void* cells, size_t cell_st
     return rz_wrap(h, nullptr, [&]() -> int {
         if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
         if (!out_sdf) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null host pointer");
-        if (cell_stride < 8 || (cell_stride % 4) || (occupancy_offset % 4) || (object_id_offset % 4) ||
-            occupancy_offset + 4 > cell_stride || object_id_offset + 4 > cell_stride)
-            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cell layout must be 4-byte aligned and in range");
+        if (int rc = check_tagged_layout(h, cell_stride, occupancy_offset, object_id_offset)) return rc;
         if (object_mode < 0 || object_mode > 2 || n_object_ids < 0 || n_object_ids > 0x7fffffffLL ||
             (object_mode == 2 && n_object_ids > 0 && !object_ids))
             return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "bad object filter");
@@ -2539,20 +2535,10 @@ int sdfgpu_build_tagged_cells(sdfgpu_handle h, const void* cells, size_t cell_st
         if (int rc = check_dims(h, nx, ny, nz)) return rc;
         HIP_TRY(h, hipSetDevice(h->device));
         const int64_t n = nx * ny * nz;
-        if (!cells) {                                  // the records of the previous call on this handle, still on the device
-            if (h->tag_cached_bytes == 0 || h->tag_cached_bytes != (size_t)n * cell_stride)
-                return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cells is null and the handle holds no cell records of this size");
-        } else {
-            h->tag_cached_bytes = 0;
-            if (int rc = ensure(h, h->stage_in, (size_t)n * cell_stride, "input staging")) return rc;
-        }
+        if (int rc = stage_tagged_records(h, cells, (size_t)n * cell_stride)) return rc;
         if (int rc = ensure(h, h->stage_out, (size_t)n * 4, "output staging")) return rc;
         if (int rc = ensure(h, h->tagmask, (size_t)n, "tagged-object mask")) return rc;
         if (int rc = ensure(h, h->tagids, (size_t)std::max<int64_t>(n_object_ids, 1) * 4, "object id list")) return rc;
-        if (cells) {
-            if (int rc0 = copy_from_host(h, h->stage_in.ptr, cells, (size_t)n * cell_stride)) return rc0;
-            h->tag_cached_bytes = (size_t)n * cell_stride;
-        }
         if (n_object_ids > 0) {                        // sorted copy: the classify kernel binary-searches it
             std::vector<uint32_t> sorted_ids(object_ids, object_ids + n_object_ids);
             std::sort(sorted_ids.begin(), sorted_ids.end());
@@ -2563,8 +2549,8 @@ int sdfgpu_build_tagged_cells(sdfgpu_handle h, const void* cells, size_t cell_st
                            unknown_is_filled, object_mode, (const uint32_t*)h->tagids.ptr, (int)n_object_ids, n,
                            (uint8_t*)h->tagmask.ptr);
         HIP_TRY(h, hipGetLastError());
-        int rc = build_device_impl(h, (const uint8_t*)h->tagmask.ptr, nullptr, 0, 0, 0, nx, ny, nz, resolution, add_virtual_border,
-                                   (float*)h->stage_out.ptr, nullptr);
+        int rc = build_device_impl(h, Occupancy::of_mask((const uint8_t*)h->tagmask.ptr), nx, ny, nz, resolution, add_virtual_border,
+                                   (float*)h->stage_out.ptr, kNullStream);
         if (rc) return rc;
         if (int rc2 = copy_to_host(h, out_sdf, h->stage_out.ptr, (size_t)n * 4)) return rc2;
         double mx, mn;
@@ -2663,7 +2649,7 @@ int build_batch_impl(sdfgpu_handle h, const uint8_t* d_filled, const BatchTagged
                                    (uint8_t*)h->tagmask.ptr);
                 HIP_TRY(h, hipGetLastError());
             }
-            if (int rc = build_device_impl(h, m, nullptr, 0, 0, 0, nx, ny, nz, h->batch_resolutions[(size_t)b], vb, d_out + b * n, s)) return rc;
+            if (int rc = build_device_impl(h, Occupancy::of_mask(m), nx, ny, nz, h->batch_resolutions[(size_t)b], vb, d_out + b * n, s)) return rc;
             HIP_TRY(h, hipMemcpyAsync(ext + 2 * b, h->d_result, 8, hipMemcpyDeviceToDevice, s));
         }
         HIP_TRY(h, hipMemcpyAsync(h->d_result, keep, kStatusWords * 4, hipMemcpyDeviceToDevice, s));
@@ -2731,25 +2717,13 @@ int sdfgpu_build_tagged_objects(sdfgpu_handle h, const void* cells, size_t cell_
     return rz_wrap(h, nullptr, [&]() -> int {
         if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
         if (!out_sdf || !object_ids) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null host pointer");
-        if (cell_stride < 8 || (cell_stride % 4) || (occupancy_offset % 4) || (object_id_offset % 4) ||
-            occupancy_offset + 4 > cell_stride || object_id_offset + 4 > cell_stride)
-            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cell layout must be 4-byte aligned and in range");
+        if (int rc = check_tagged_layout(h, cell_stride, occupancy_offset, object_id_offset)) return rc;
         if (int rc = check_batch_args(h, n_object_ids, nx, ny, nz, resolution, nullptr)) return rc;
         HIP_TRY(h, hipSetDevice(h->device));
         const int64_t n = nx * ny * nz;
-        if (!cells) {                                  // the records of the previous tagged call on this handle, still on the device
-            if (h->tag_cached_bytes == 0 || h->tag_cached_bytes != (size_t)n * cell_stride)
-                return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cells is null and the handle holds no cell records of this size");
-        } else {
-            h->tag_cached_bytes = 0;
-            if (int rc = ensure(h, h->stage_in, (size_t)n * cell_stride, "input staging")) return rc;
-        }
+        if (int rc = stage_tagged_records(h, cells, (size_t)n * cell_stride)) return rc;
         if (int rc = ensure(h, h->stage_out, (size_t)(n_object_ids * n) * 4, "output staging")) return rc;
         if (int rc = ensure(h, h->tagids, (size_t)n_object_ids * 4, "object id list")) return rc;
-        if (cells) {
-            if (int rc0 = copy_from_host(h, h->stage_in.ptr, cells, (size_t)n * cell_stride)) return rc0;
-            h->tag_cached_bytes = (size_t)n * cell_stride;
-        }
         HIP_TRY(h, hipMemcpy(h->tagids.ptr, object_ids, (size_t)n_object_ids * 4, hipMemcpyHostToDevice));
         const BatchTagged tg{(const char*)h->stage_in.ptr, cell_stride, occupancy_offset, object_id_offset, unknown_is_filled, (const uint32_t*)h->tagids.ptr};
         if (int rc = build_batch_impl(h, nullptr, &tg, n_object_ids, nx, ny, nz, resolution, nullptr, add_virtual_border, (float*)h->stage_out.ptr, nullptr))
@@ -2814,8 +2788,7 @@ int sdfgpu_classify_cells_device(sdfgpu_handle h, const void* d_cells, size_t ce
     return rz_wrap(h, stream, [&]() -> int {
         if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
         if (!d_cells || !d_mask || n_cells < 0) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "bad classify arguments");
-        if (cell_stride < 4 || (cell_stride % 4) || (occupancy_offset % 4) || occupancy_offset + 4 > cell_stride)
-            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cell_stride/occupancy_offset must be 4-byte aligned and in range");
+        if (int rc = check_cell_layout(h, cell_stride, occupancy_offset)) return rc;
         HIP_TRY(h, hipSetDevice(h->device));
         if (n_cells == 0) return SDFGPU_OK;
         CellLoader ld{reinterpret_cast<const char*>(d_cells), (int64_t)cell_stride, (int64_t)occupancy_offset, unknown_is_filled};
@@ -3192,8 +3165,8 @@ int sdfgpu_last_dense_certified(sdfgpu_handle h, int* out_certified) {
     HIP_TRY(h, hipMemcpy(v, h->d_result, sizeof v, hipMemcpyDeviceToHost));
     // bit 0: dense kernel decided everything; bit 1 / 2: the y / x sweep was redone by the envelope kernel
     uint32_t why = 0;
-    HIP_TRY(h, hipMemcpy(&why, h->d_result + 21, sizeof why, hipMemcpyDeviceToHost));
-    *out_certified = ((h->last.last_dense && v[3] == 0) ? 1 : 0) | (v[4] ? 2 : 0) | (v[5] ? 4 : 0) | (int)((why & 0xffu) << 8);
+    HIP_TRY(h, hipMemcpy(&why, h->d_result + kSwReason, sizeof why, hipMemcpyDeviceToHost));
+    *out_certified = ((h->last.last_dense && v[kSwUncertified] == 0) ? 1 : 0) | (v[kSwFarY] ? 2 : 0) | (v[kSwFarX] ? 4 : 0) | (int)((why & 0xffu) << 8);
     return SDFGPU_OK;
 }
 
@@ -3201,8 +3174,8 @@ int sdfgpu_debug_flat_habit(sdfgpu_handle h, int* out_score, int* out_gate) {
     if (!h || !out_score || !out_gate) return SDFGPU_ERR_INVALID_ARGUMENT;
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, h->build_order.host_wait());
-    int v[2] = {0, 0};
-    HIP_TRY(h, hipMemcpy(v, h->d_small + 40, sizeof v, hipMemcpyDeviceToHost));
+    int v[2] = {0, 0};                                          // kSwFlatScore, kSwFlatGate
+    HIP_TRY(h, hipMemcpy(v, h->d_small + kSwFlatScore, sizeof v, hipMemcpyDeviceToHost));
     *out_score = v[0];
     *out_gate = v[1];
     return SDFGPU_OK;
@@ -3234,7 +3207,7 @@ int sdfgpu_components(sdfgpu_handle h, const uint8_t* filled, int64_t nx, int64_
         if (!filled || !out_labels || !out_count) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
         if (int rc = check_components_dims(h, nx, ny, nz)) return rc;
         HIP_TRY(h, hipSetDevice(h->device));
-        if (int rc = components_host(h, filled, nullptr, 0, 0, nx, ny, nz, out_count)) return rc;
+        if (int rc = components_host(h, Occupancy::of_mask(filled), nx, ny, nz, out_count)) return rc;
         return copy_to_host(h, out_labels, h->stage_out.ptr, (size_t)(nx * ny * nz) * 4);
     });
 }
@@ -3244,12 +3217,10 @@ int sdfgpu_components_cells(sdfgpu_handle h, void* cells, size_t cell_stride, si
     return rz_wrap(h, nullptr, [&]() -> int {
         if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
         if (!cells || !out_count) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
-        if (cell_stride < 8 || (cell_stride % 4) || (occupancy_offset % 4) || (component_offset % 4) || occupancy_offset + 4 > cell_stride ||
-            component_offset + 4 > cell_stride || occupancy_offset == component_offset)
-            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cell_stride / occupancy_offset / component_offset must be 4-byte aligned, in range and distinct");
+        if (int rc = check_component_layout(h, cell_stride, occupancy_offset, component_offset)) return rc;
         if (int rc = check_components_dims(h, nx, ny, nz)) return rc;
         HIP_TRY(h, hipSetDevice(h->device));
-        if (int rc = components_host(h, nullptr, cells, cell_stride, occupancy_offset, nx, ny, nz, out_count)) return rc;
+        if (int rc = components_host(h, Occupancy::of_cells(cells, cell_stride, occupancy_offset, 0), nx, ny, nz, out_count)) return rc;
         char* const rec = static_cast<char*>(cells) + component_offset;
         // the drain team writes each label into its record (download offsets are multiples of 4: whole labels)
         return staged_download_hip(h, h->stage_out.ptr, (size_t)(nx * ny * nz) * 4, nullptr, [=](const char* src, size_t goff, size_t len) {
@@ -3288,9 +3259,7 @@ int sdfgpu_component_topology_cells(sdfgpu_handle h, const void* cells, size_t c
     return rz_wrap(h, nullptr, [&]() -> int {
         if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
         if (!cells) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
-        if (cell_stride < 8 || (cell_stride % 4) || (occupancy_offset % 4) || (component_offset % 4) || occupancy_offset + 4 > cell_stride ||
-            component_offset + 4 > cell_stride || occupancy_offset == component_offset)
-            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cell_stride / occupancy_offset / component_offset must be 4-byte aligned, in range and distinct");
+        if (int rc = check_component_layout(h, cell_stride, occupancy_offset, component_offset)) return rc;
         if (class_mask < 1 || class_mask > 7)
             return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "class_mask must be a nonzero combination of FILLED (1), EMPTY (2) and UNKNOWN (4)");
         if (int rc = check_topology_args(h, nx, ny, nz, max_label, out_counts)) return rc;
@@ -3333,9 +3302,7 @@ int sdfgpu_component_surfaces_cells(sdfgpu_handle h, const void* cells, size_t c
     return rz_wrap(h, nullptr, [&]() -> int {
         if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
         if (!cells) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
-        if (cell_stride < 8 || (cell_stride % 4) || (occupancy_offset % 4) || (component_offset % 4) || occupancy_offset + 4 > cell_stride ||
-            component_offset + 4 > cell_stride || occupancy_offset == component_offset)
-            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cell_stride / occupancy_offset / component_offset must be 4-byte aligned, in range and distinct");
+        if (int rc = check_component_layout(h, cell_stride, occupancy_offset, component_offset)) return rc;
         if (class_mask < 1 || class_mask > 7)
             return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "class_mask must be a nonzero combination of FILLED (1), EMPTY (2) and UNKNOWN (4)");
         if (int rc = check_surfaces_args(h, nx, ny, nz, max_label, out_counts, out_indices != nullptr, capacity, out_total)) return rc;

@@ -317,7 +317,7 @@ SDFGPU_KERNEL __launch_bounds__(1024) void k_pack_row_flags(const uint8_t* __res
     // without one exists (the y sweep then looks at plane_any / the row masks at all: a scene of floors and walls never does)
     const int wg_empty = __syncthreads_or(saw_empty ? 1 : 0), wg_hole = __syncthreads_or(saw_hole ? 1 : 0);
     if (threadIdx.x == 0 && wg_empty) __hip_atomic_store(some_empty, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (threadIdx.x == 0 && wg_hole) __hip_atomic_store(some_empty - 3, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (threadIdx.x == 0 && wg_hole) __hip_atomic_store(some_empty + (kSwRowHole - kSwPlaneEmpty), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 constexpr int kDcLines = 16;          // lines per tile (the kernel is a template over 8 / 16 lines and 128 / 256 / 512 lanes: 16 x 256 is the measured optimum)
@@ -351,27 +351,27 @@ __device__ __forceinline__ int imax(int a, int b) { return a > b ? a : b; }
 __device__ __forceinline__ void decide_tier(uint32_t* __restrict__ small, int stage, int dense_tried, int force, int num, int den,
                                             int handoff, int mid_den, int xden = 0) {
     auto ld = [&](int i) -> uint32_t { return __hip_atomic_load(small + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
-    const bool active = dense_tried ? ld(3) != 0u : true;
-    const uint32_t far_n = ld(12), tot = ld(13), mid_n = ld(11);
+    const bool active = dense_tried ? ld(kSwUncertified) != 0u : true;
+    const uint32_t far_n = ld(kSwProbeFar), tot = ld(kSwProbeTotal), mid_n = ld(kSwProbeMid);
     // far when more than num / den of the sampled voxels need a long scan (64-bit: counts are < 2^24, factors small)
     bool far = force >= 0 ? force != 0 : (uint64_t)far_n * (uint64_t)den > (uint64_t)tot * (uint64_t)num;
-    if (stage == 1 && ld(7) != 0u) far = true;                  // the y probe chose the far-field pair with int32 hand-off
-    if (stage == 1 && force < 0 && ld(18) != 0u) far = false;   // the y probe already settled it: near-field (no x probe ran)
+    if (stage == 1 && ld(kSwHandoff) != 0u) far = true;                  // the y probe chose the far-field pair with int32 hand-off
+    if (stage == 1 && force < 0 && ld(kSwXNear) != 0u) far = false;   // the y probe already settled it: near-field (no x probe ran)
     // (only when the y sweep itself stays near-field: a far-field y sweep may hand the x sweep int32 values, which only the
     //  far-field x kernel reads)
-    if (stage == 0) small[18] = (force < 0 && !far && tot != 0u && (uint64_t)ld(17) * (uint64_t)xden <= (uint64_t)tot) ? 1u : 0u;
+    if (stage == 0) small[kSwXNear] = (force < 0 && !far && tot != 0u && (uint64_t)ld(kSwProbeX) * (uint64_t)xden <= (uint64_t)tot) ? 1u : 0u;
     // y sweep, near-field: radius-8 register windows when more than 1 / mid_den of the voxels are beyond the radius-3 one
     const bool wide = stage == 0 && mid_den > 0 && (uint64_t)mid_n * (uint64_t)mid_den > (uint64_t)tot;
-    small[8 + 2 * stage] = (active && !far && !wide) ? 1u : 0u;
-    if (stage == 0) small[9] = (active && !far && wide) ? 1u : 0u;
-    if (active && far) small[4 + stage] = 1u;
-    if (stage == 0 && active && far && handoff) small[7] = 1u;
-    small[11] = 0u;
-    small[12] = 0u;
-    small[13] = 0u;
-    small[17] = 0u;
-    if (stage == 1) small[18] = 0u;
-    small[14 + stage] = tot ? (far_n * 1000u) / tot : 0u;         // per-mille of far voxels in the sample (diagnostics)
+    small[kSwMarchY + 2 * stage] = (active && !far && !wide) ? 1u : 0u;
+    if (stage == 0) small[kSwMarchYWide] = (active && !far && wide) ? 1u : 0u;
+    if (active && far) small[kSwFarY + stage] = 1u;
+    if (stage == 0 && active && far && handoff) small[kSwHandoff] = 1u;
+    small[kSwProbeMid] = 0u;
+    small[kSwProbeFar] = 0u;
+    small[kSwProbeTotal] = 0u;
+    small[kSwProbeX] = 0u;
+    if (stage == 1) small[kSwXNear] = 0u;
+    small[kSwFarPermille + stage] = tot ? (far_n * 1000u) / tot : 0u;         // per-mille of far voxels in the sample (diagnostics)
 }
 SDFGPU_KERNEL void k_decide_tier(uint32_t* __restrict__ small, int stage, int dense_tried, int force, int num, int den, int handoff,
                               int mid_den) {
@@ -381,10 +381,10 @@ SDFGPU_KERNEL void k_decide_tier(uint32_t* __restrict__ small, int stage, int de
 __device__ __forceinline__ void probe_done(const EnvDcArgs& a) {
     if (!a.decide_small || threadIdx.x != 0) return;
     __threadfence();
-    if (atomicAdd(a.decide_small + 16, 1u) == gridDim.x - 1u) {
+    if (atomicAdd(a.decide_small + kSwProbeTicket, 1u) == gridDim.x - 1u) {
         __threadfence();
         decide_tier(a.decide_small, a.decide_stage, a.decide_dense_tried, a.decide_force, 1, a.decide_den, a.decide_handoff, a.decide_mid_den, a.decide_xden);
-        a.decide_small[16] = 0u;
+        a.decide_small[kSwProbeTicket] = 0u;
     }
 }
 
@@ -401,7 +401,7 @@ struct ProbeArgs {
     int L, W;                 // positions along the axis, window radius
     int thr, thr2, thr3;
     uint32_t nsamples;
-    uint32_t* probe_out;      // status word 12 (see decide_tier)
+    uint32_t* probe_out;      // status word kSwProbeFar (see decide_tier)
     const uint32_t* guard;    // nullptr: always run; else run iff *guard != 0
     const uint32_t* i32_flag; // stage 3: non-zero = the y probe chose the int32 hand-off, the x tier is decided
     uint32_t* decide_small;
@@ -416,7 +416,7 @@ __global__ __launch_bounds__(256) void k_probe_window(const ProbeArgs a) {
     bool run = true;
     if (a.guard && *a.guard == 0u) run = false;
     if (STAGE == 3 && a.i32_flag && *a.i32_flag != 0u) run = false;
-    if (STAGE == 3 && __hip_atomic_load(a.decide_small + 18, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) run = false;   // settled by the y probe
+    if (STAGE == 3 && __hip_atomic_load(a.decide_small + kSwXNear, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) run = false;   // settled by the y probe
     if (run) {                                                  // (block-uniform)
         if (t < 4) cnt[t] = 0u;
         __syncthreads();
@@ -461,18 +461,18 @@ __global__ __launch_bounds__(256) void k_probe_window(const ProbeArgs a) {
         if ((t & 63) == 0) { atomicAdd(&cnt[0], bf); atomicAdd(&cnt[1], bt); atomicAdd(&cnt[2], bm); atomicAdd(&cnt[3], bx); }
         __syncthreads();
         if (t == 0) {
-            atomicAdd(a.probe_out, cnt[0]); atomicAdd(a.probe_out + 1, cnt[1]);
-            if (a.thr2 > 0) atomicAdd(a.probe_out - 1, cnt[2]);
-            if (a.thr3 > 0) atomicAdd(a.probe_out + 5, cnt[3]);
+            atomicAdd(a.probe_out, cnt[0]); atomicAdd(a.probe_out + (kSwProbeTotal - kSwProbeFar), cnt[1]);
+            if (a.thr2 > 0) atomicAdd(a.probe_out + (kSwProbeMid - kSwProbeFar), cnt[2]);
+            if (a.thr3 > 0) atomicAdd(a.probe_out + (kSwProbeX - kSwProbeFar), cnt[3]);
         }
     }
     if (t == 0) {                                               // every workgroup passes here once: the last one decides
         __threadfence();
-        if (atomicAdd(a.decide_small + 16, 1u) == gridDim.x - 1u) {
+        if (atomicAdd(a.decide_small + kSwProbeTicket, 1u) == gridDim.x - 1u) {
             __threadfence();
             decide_tier(a.decide_small, a.decide_stage, a.decide_dense_tried, a.decide_force, 1, a.decide_den, a.decide_handoff,
                         a.decide_mid_den, a.decide_xden);
-            a.decide_small[16] = 0u;
+            a.decide_small[kSwProbeTicket] = 0u;
         }
     }
 }
@@ -520,7 +520,7 @@ __global__ __launch_bounds__(NT, WPS) void k_envelope_dc(const EnvDcArgs a) {
     // (The two words are requested TOGETHER: with the gate's load behind the test of word 19 every tile waited a second round trip, +3.6 %.)
     uint32_t w19 = 0u, wgate = 0u;
     if (STAGE == 2 && a.row_bits) {
-        w19 = __hip_atomic_load(a.some_empty - 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        w19 = __hip_atomic_load(a.some_empty + (kSwRowHole - kSwPlaneEmpty), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         wgate = __hip_atomic_load(a.flat_score + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     const bool rows_known = STAGE == 2 && a.row_bits && w19 != 0u;
@@ -531,7 +531,7 @@ __global__ __launch_bounds__(NT, WPS) void k_envelope_dc(const EnvDcArgs a) {
     const bool flat_gate = floorlike && (a.flat_on == 2 || wgate != 0u);
     if (a.probe_stride > 0 && a.i32_flag && i32) { probe_done(a); return; }       // the x tier is already decided: no probe
     if (a.probe_stride > 0 && STAGE == 3 && a.decide_small &&
-        __hip_atomic_load(a.decide_small + 18, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) { probe_done(a); return; }   // ... settled by the y probe
+        __hip_atomic_load(a.decide_small + kSwXNear, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) { probe_done(a); return; }   // ... settled by the y probe
     const int L = LC ? LC : a.L, B = LC ? dc_clog2(LC ? LC : 2) : a.B, pitch = LC ? ((LC + 63) / 64) * 64 + 2 : a.pitch, M = LC ? (LC + 7) / 8 : a.M,
               h = LC ? (LC + 1) / 2 : a.h;
     const int MA = (L + 63) >> 6;
@@ -1445,9 +1445,9 @@ __global__ __launch_bounds__(NT, WPS) void k_envelope_dc(const EnvDcArgs a) {
         if ((t & 63) == 0) { atomicAdd(&misc[26], (uint32_t)probe_far); atomicAdd(&misc[27], (uint32_t)probe_tot); atomicAdd(&misc[28], (uint32_t)probe_mid); atomicAdd(&misc[29], (uint32_t)probe_x9); }
         __syncthreads();
         if (t == 0) {
-            atomicAdd(a.probe_out, misc[26]); atomicAdd(a.probe_out + 1, misc[27]);
-            if (a.probe_thr2 > 0) atomicAdd(a.probe_out - 1, misc[28]);
-            if (a.probe_thr3 > 0) atomicAdd(a.probe_out + 5, misc[29]);        // (probe_out = status word 12: + 5 = word 17)
+            atomicAdd(a.probe_out, misc[26]); atomicAdd(a.probe_out + (kSwProbeTotal - kSwProbeFar), misc[27]);
+            if (a.probe_thr2 > 0) atomicAdd(a.probe_out + (kSwProbeMid - kSwProbeFar), misc[28]);
+            if (a.probe_thr3 > 0) atomicAdd(a.probe_out + (kSwProbeX - kSwProbeFar), misc[29]);
         }
         probe_done(a);
         return;

@@ -76,8 +76,38 @@ __device__ __forceinline__ void raise_flag(uint32_t* p) {
 constexpr int kSlots = 512;
 constexpr int kStatusWords = 24;      // words of the status block that the end-of-build fold publishes and clears
 constexpr int kSlotWords = 32;
-constexpr uint32_t kReportDense = 0x1000FFu;      // status words a dense-tier report publishes to the host
-constexpr uint32_t kReportFar = 0x30u;            // ... a far-flag report (words 4, 5)
+// The context's status block, word by word: every index the host or a kernel uses.  Words below kStatusWords are published and
+// cleared by the end-of-build fold; the flat-tile habit beyond them is the handle's and no build clears it.  (The caller-owned
+// blocks of the stage calls and of sdfgpu_multi.cpp share words 0 .. 3 only.)
+enum StatusWord : int {
+    kSwMaxFree = 0, kSwMaxFilled = 1,  // largest d^2 over the free / the filled voxels
+    kSwSlabStatus = 2,                 // raised by a slab x sweep whose truncated halo was too short
+    kSwUncertified = 3,                // the dense tier left voxels undecided: the general pipeline's guard
+    kSwFarY = 4, kSwFarX = 5,          // "the y / x sweep belongs to the far-field kernel" (kSwFarY + stage), also raised by a marching
+                                       // sweep that hits its scan bound and by a far-field launch that does work
+    kSwFixNeeded = 6,                  // the dense ball kernel left voxels to its fix-up kernel
+    kSwHandoff = 7,                    // the y probe chose the far-field pair with the int32 hand-off
+    kSwMarchY = 8,                     // guard of the marching y sweep, radius-3 window (kSwMarchY + 2 * stage = kSwMarchX)
+    kSwMarchYWide = 9,                 // ... of its radius-8 form
+    kSwMarchX = 10,                    // guard of the marching x sweep
+    kSwProbeMid = 11,                  // probe counters, addressed from kSwProbeFar: voxels beyond the radius-3 window,
+    kSwProbeFar = 12,                  // ... at or beyond the axis' far threshold,
+    kSwProbeTotal = 13,                // ... sampled,
+    kSwFarPermille = 14,               // per-mille of far voxels in the sample (kSwFarPermille + stage; diagnostics)
+    kSwProbeTicket = 16,               // workgroups of a probe launch that have passed: the last one decides
+    kSwProbeX = 17,                    // y probe: voxels at or beyond the x sweep's far threshold
+    kSwXNear = 18,                     // the y probe settled the x tier: near-field, no x probe
+    kSwRowHole = 19,                   // plane sparsity: a z row without a filled voxel exists (addressed from kSwPlaneEmpty)
+    kSwDenseVerdict = 20,              // a staged build: KD's own "uncertified", which guards KD3 + KF
+    kSwReason = 21,                    // why the dense tier gave up
+    kSwPlaneEmpty = 22,                // plane sparsity: an x-plane without a filled voxel exists
+    kSwFoldTicket = 23,                // workgroups of the stand-by x sweep that have finished: the last one folds
+    kSwFlatScore = 40, kSwFlatGate = 41,   // habit of the two-valued y tiles and the gate it publishes
+    kSwReportVerdict = 8               // where the host copy of a dense-tier report carries kSwDenseVerdict
+};
+constexpr uint32_t kReportDense = ((2u << kSwHandoff) - 1u) | (1u << kSwDenseVerdict);   // status words a dense-tier report publishes to the host
+constexpr uint32_t kReportFar = (1u << kSwFarY) | (1u << kSwFarX);                        // ... a far-flag report
+static_assert(kReportDense == 0x1000FFu && kReportFar == 0x30u && kSwFoldTicket < kStatusWords && kSwFlatScore >= kStatusWords, "status words");
 __device__ __forceinline__ void slot_max2(uint32_t* slots, uint32_t wave, int mxF, int mxQ) {
     uint32_t* p = slots + (size_t)(wave & (kSlots - 1)) * kSlotWords;
     if (mxF) atomic_max_if_larger(p + 0, (uint32_t)mxF);
@@ -119,17 +149,17 @@ __device__ __forceinline__ void fold_slots_device(uint32_t* __restrict__ slots, 
 #pragma unroll
         for (int w = 0; w < NT / 64; ++w) { f = max(f, part[2 * w]); q = max(q, part[2 * w + 1]); }
         if (!result) {
-            if (t == 0 && f) atomic_max_if_larger(maxdsq + 0, f);
-            if (t == 1 && q) atomic_max_if_larger(maxdsq + 1, q);
+            if (t == kSwMaxFree && f) atomic_max_if_larger(maxdsq + kSwMaxFree, f);
+            if (t == kSwMaxFilled && q) atomic_max_if_larger(maxdsq + kSwMaxFilled, q);
         } else {
-            if (t == 0) st = max(st, f);
-            if (t == 1) st = max(st, q);
+            if (t == kSwMaxFree) st = max(st, f);
+            if (t == kSwMaxFilled) st = max(st, q);
             result[t] = st;
-            // (host copy: the words of report_mask -- kReportDense: words 0..7, and KD's own verdict, word 20, as word 8; kReportFar: the
+            // (host copy: the words of report_mask -- kReportDense: words 0 .. kSwHandoff, and kSwDenseVerdict as word kSwReportVerdict; kReportFar: the
             //  two far flags.  Every word is a separate write across PCIe that the kernel's end waits for: publishing all 24 made
             //  every build 0.04 ms longer)
             if (report && ((report_mask >> t) & 1u))
-                __hip_atomic_store(report + (t == 20 ? 8 : t), st, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                __hip_atomic_store(report + (t == kSwDenseVerdict ? kSwReportVerdict : t), st, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             maxdsq[t] = 0;
         }
     }
