@@ -186,7 +186,9 @@ __device__ __forceinline__ uint32_t ball_level_pass(const uint32_t* c0, int hy, 
 template <int BD, bool ZINV>
 __global__ __launch_bounds__(BD) void k_ball_dense(const DenseArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    // (block-uniform; an atomic load: a plain one may be served from a scalar / L1 cache line read before the flag went up)
+    // (block-uniform; an atomic load: a plain one may be served from a scalar / L1 cache line read before the flag went up.  Issuing
+    //  it in front of the tile loads and testing it behind them -- one round trip in front of the LDS writes instead of two -- was
+    //  measured on top of the epilogue below and bought nothing: LAB_NOTES.md 4.1)
     if (a.early_out && __hip_atomic_load(a.uncertified, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) return;
     const int nzw = a.nzw, lg = a.log2_nzw;
     const int rwu = nzw + 2;                                  // words used per staged row (edge words replicated)
@@ -277,6 +279,25 @@ __global__ __launch_bounds__(BD) void k_ball_dense(const DenseArgs a) {
     }
     __syncthreads();
 
+    // What the wave's first lane needs from the L2 for its bookkeeping, asked for NOW and used in front of the expansion: behind
+    // the wave's stores these reads would first wait for every store's acknowledgement (one counter covers both) and then cost
+    // dependent round trips while the wave holds its slot on the CU with nothing in flight.
+    //   maxima_void: the early-out test at the top is per wave.  If the flag rises between the loads of two waves of one workgroup, some
+    //     waves leave and the others run on over a partly staged tile -- what they find is garbage.  The field is rewritten by
+    //     the stage behind (the flag is up), but maxima are max-folded: they must not leave this wave.  Reading the
+    //     flag again anywhere behind the barrier above is late enough: a sibling that left on the flag had read it set before this
+    //     wave passed that barrier (the barrier releases only when every wave has arrived or ended), the flag only ever rises, and
+    //     this is an agent-scope atomic load, served where that sibling's was.  And then the stage behind recomputes every maximum.
+    //   slot_seen: both words of this wave's maxima slot (slot_peek).
+    const uint32_t tile_id = by * gridDim.x + bx;
+    const uint32_t wave_id = tile_id * (BD / 64) + ((uint32_t)t >> 6);
+    uint32_t flag_again = 0u;                                 // (read whether or not the launch has an early out: a load under a
+    uint64_t slot_seen = 0u;                                  //  condition of its own is waited for before the next one is sent)
+    if ((t & 63) == 0) {
+        flag_again = __hip_atomic_load(a.uncertified, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        slot_seen = slot_peek(a.slots, wave_id);
+    }
+
     const int r = t >> lg, w = t & (nzw - 1);                 // tile row, word in row
     const int ty_ = r & (a.ty - 1), tx_ = r >> a.log2_ty;
     const uint32_t* c0 = tile + ((tx_ + kBallR) * hy + (ty_ + kBallR)) * rw + (w + 1);
@@ -327,6 +348,19 @@ __global__ __launch_bounds__(BD) void k_ball_dense(const DenseArgs a) {
     const bool row_in_grid = (x0 + tx_ < a.out_hi) && (y0 + ty_ < a.ny);
     const bool uncert = row_in_grid && (~acc[6] != 0u);
     if (!row_in_grid) { mxF = 0; mxQ = 0; }
+    // The wave's bookkeeping -- everything it has to tell the rest of the build -- happens here and in front of the expansion
+    // below, so that a wave ends behind its eight stores the way a fill's does.  All inputs are final at this point.
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        mxF = max(mxF, __shfl_xor(mxF, off));
+        mxQ = max(mxQ, __shfl_xor(mxQ, off));
+    }
+    const bool any_uncert = __any(uncert);
+    const bool all_undecided = __all(row_in_grid && acc[6] == 0u);
+    if (any_uncert && a.unc) {
+        if (row_in_grid)
+            a.unc[((int64_t)(x0 + tx_ - a.out_lo) * a.ny + (y0 + ty_)) * nzw + w] = ~acc[6];
+    }
 
     // level index per voxel = number of levels it was NOT found at (0..6, 7 = not found) as 3 bit-planes
     {
@@ -345,6 +379,26 @@ __global__ __launch_bounds__(BD) void k_ball_dense(const DenseArgs a) {
                               __uint_as_float(__float_as_uint(lut_b) | ((uint32_t)(t & 2) << 30)));
     }
     __syncthreads();
+
+    // (taken out of the first lane by the whole wave: the one wait for the two reads then stands here, in straight-line code, and
+    //  nothing behind it -- the stores least of all -- has to wait for them again)
+    const bool maxima_void = a.early_out && __builtin_amdgcn_readfirstlane((int)flag_again) != 0;
+    const uint64_t slot_was = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)slot_seen) |
+                              ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(slot_seen >> 32)) << 32);
+    if ((t & 63) == 0) {
+        if (!maxima_void) slot_max2_seen(a.slots, wave_id, mxF, mxQ, slot_was);
+        if (any_uncert) {
+            if (a.unc) {
+                atomicOr(a.tileflag + tile_id, 1u << (t >> 6));      // one word per tile: no same-address pile-up
+                raise_flag(a.fix_needed);
+                // a wave without a single decided voxel sits in empty (or solid) space: nothing for the fix-up kernel
+                if (a.early_out && all_undecided) { raise_flag(a.uncertified); note_reason(a.reason, kGiveUpWaveAllUndecided); }
+            } else {
+                raise_flag(a.uncertified);
+                note_reason(a.reason, kGiveUpBeyondBall);
+            }
+        }
+    }
 
     // expansion: a lane finishes 4 consecutive voxels per pass -> every store instruction writes one
     // fully contiguous 1 KiB segment per wave (8 voxels per lane halves the instruction count but
@@ -403,39 +457,6 @@ __global__ __launch_bounds__(BD) void k_ball_dense(const DenseArgs a) {
     };
     if ((x0 + a.tx <= a.out_hi) && (y0 + a.ty <= a.ny)) expand(std::true_type{});
     else expand(std::false_type{});
-
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        mxF = max(mxF, __shfl_xor(mxF, off));
-        mxQ = max(mxQ, __shfl_xor(mxQ, off));
-    }
-    const bool any_uncert = __any(uncert);
-    const bool all_undecided = __all(row_in_grid && acc[6] == 0u);
-    if (any_uncert && a.unc) {
-        if (row_in_grid)
-            a.unc[((int64_t)(x0 + tx_ - a.out_lo) * a.ny + (y0 + ty_)) * nzw + w] = ~acc[6];
-    }
-    if ((t & 63) == 0) {
-        const uint32_t tile_id = by * gridDim.x + bx;
-        // The early-out test at the top is per wave: if the flag rises between the loads of two waves of one workgroup, some
-        // waves leave and the others run on over a partly staged tile -- what they find is garbage.  The field is rewritten
-        // by the stage behind (the flag is up), but maxima are max-folded: they must not leave this wave.  A wave that can
-        // have been affected sees the flag set HERE (it only ever rises), and then the stage behind recomputes every
-        // maximum anyway.
-        const bool void_maxima = a.early_out && __hip_atomic_load(a.uncertified, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
-        if (!void_maxima) slot_max2(a.slots, tile_id * (BD / 64) + ((uint32_t)t >> 6), mxF, mxQ);
-        if (any_uncert) {
-            if (a.unc) {
-                atomicOr(a.tileflag + tile_id, 1u << (t >> 6));      // one word per tile: no same-address pile-up
-                raise_flag(a.fix_needed);
-                // a wave without a single decided voxel sits in empty (or solid) space: nothing for the fix-up kernel
-                if (a.early_out && all_undecided) { raise_flag(a.uncertified); note_reason(a.reason, kGiveUpWaveAllUndecided); }
-            } else {
-                raise_flag(a.uncertified);
-                note_reason(a.reason, kGiveUpBeyondBall);
-            }
-        }
-    }
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -203,6 +203,36 @@ __global__ __launch_bounds__(BD) void k_ball_dense3(const DenseArgs a) {
     const bool row_in_grid = (x0 + tx_ < a.out_hi) && (y0 + ty_ < a.ny);
     const bool uncert = row_in_grid && (~acc[kBall3Levels - 1] != 0u);
     if (!row_in_grid) { mxF = 0; mxQ = 0; }
+    // the first lane's reads for the wave's bookkeeping, issued now and used in front of the expansion (see KD for both, and for
+    // why the flag may be read again anywhere behind the staging barrier).  KD issues them in front of its level passes; here the
+    // 13 level words leave no registers for that at 6 waves per SIMD, so they overlap the plane exchange and the table build.
+    const uint32_t tile_id = (uint32_t)blockIdx.y * gridDim.x + blockIdx.x;
+    const uint32_t wave_id = tile_id * (BD / 64) + ((uint32_t)t >> 6);
+    uint32_t flag_again = 0u;                                 // (read whether or not the launch has an early out: a load under a
+    uint64_t slot_seen = 0u;                                  //  condition of its own is waited for before the next one is sent)
+    if ((t & 63) == 0) {
+        flag_again = __hip_atomic_load(a.uncertified, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        slot_seen = slot_peek(a.slots, wave_id);
+    }
+    // the wave's bookkeeping, here and in front of the expansion below: a wave ends behind its stores (see KD)
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        mxF = max(mxF, __shfl_xor(mxF, off));
+        mxQ = max(mxQ, __shfl_xor(mxQ, off));
+    }
+    // more than kBall3MaxUndecided undecided voxels in this wave's 2048: the scene is too sparse for this tier (the fix-up
+    // kernel behind would take longer than the sweeps) -- say so now, the later workgroups return at once
+    int nund = row_in_grid ? __popc(~acc[kBall3Levels - 1]) : 0;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) nund += __shfl_xor(nund, off);
+    const bool hopeless = nund > a.max_undecided;
+    const bool any_uncert = __any(uncert);
+    const uint32_t open_words = (uint32_t)__popcll(__ballot(uncert));    // words of this wave that hold undecided voxels
+    const bool all_undecided = __all(row_in_grid && acc[kBall3Levels - 1] == 0u);
+    if (any_uncert && a.unc) {
+        if (row_in_grid)
+            a.unc[((int64_t)(x0 + tx_ - a.out_lo) * a.ny + (y0 + ty_)) * nzw + w] = ~acc[kBall3Levels - 1];
+    }
 
     // level index per voxel = number of levels it was NOT found at (0..12, 13 = not found): the U_l are nested, so bit k of
     // the count is the parity of the U_l with l = 2^k - 1 (mod 2^(k+1))
@@ -225,6 +255,37 @@ __global__ __launch_bounds__(BD) void k_ball_dense3(const DenseArgs a) {
                               __uint_as_float(__float_as_uint(magl[lb]) | ((uint32_t)(i & 2) << 30)));
     }
     __syncthreads();
+
+    // (taken out of the first lane by the whole wave: the one wait for the two reads then stands here, in straight-line code, and
+    //  nothing behind it -- the stores least of all -- has to wait for them again)
+    const bool maxima_void = a.early_out && __builtin_amdgcn_readfirstlane((int)flag_again) != 0;
+    const uint64_t slot_was = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)slot_seen) |
+                              ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(slot_seen >> 32)) << 32);
+    if ((t & 63) == 0) {
+        if (!maxima_void) slot_max2_seen(a.slots, wave_id, mxF, mxQ, slot_was);
+        // (every 16th wave adds its undecided voxels to one of the 512 extrema slots' third word: a 1 / 16 sample of the scene's total
+        //  for k_shell_budget.  ONE status word for all of them -- a thousand same-address atomics -- cost this kernel 76 - 190 us.)
+        if (a.und_sample && nund) {
+            if ((wave_id & 15u) == 0u) atomicAdd(a.und_sample + (size_t)((wave_id >> 4) & (kSlots - 1)) * kSlotWords + 2, (uint32_t)nund);
+        }
+        if (any_uncert) {
+            if (a.unc) {
+                // one word per tile: no same-address pile-up.  Bits 0 .. 15: the wave's flag; bits 16 ..: the number of WORDS this wave
+                // leaves undecided voxels in, summed over the tile's waves -- the shell pass reads four of these words and knows at
+                // once whether the group is worth staging (round 5).  (Every wave adds its own bit exactly once: add == or.)
+                atomicAdd(a.tileflag + tile_id, (1u << (t >> 6)) + (open_words << 16));
+                raise_flag(a.fix_needed);
+                // a wave without a single decided voxel sits in empty (or solid) space: nothing for the fix-up kernel
+                if ((a.early_out && all_undecided) || hopeless) {
+                    raise_flag(a.uncertified);
+                    note_reason(a.reason, hopeless ? kGiveUpWaveTooMany : kGiveUpWaveAllUndecided);
+                }
+            } else {
+                raise_flag(a.uncertified);
+                note_reason(a.reason, kGiveUpBeyondBall);
+            }
+        }
+    }
 
     // expansion: a lane finishes 4 consecutive voxels per pass -> every store instruction writes one
     // fully contiguous 1 KiB segment per wave (8 voxels per lane halves the instruction count but
@@ -289,58 +350,6 @@ __global__ __launch_bounds__(BD) void k_ball_dense3(const DenseArgs a) {
     };
     if ((x0 + a_tx <= a.out_hi) && (y0 + a_ty <= a.ny)) expand(std::true_type{});
     else expand(std::false_type{});
-
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        mxF = max(mxF, __shfl_xor(mxF, off));
-        mxQ = max(mxQ, __shfl_xor(mxQ, off));
-    }
-    // more than kBall3MaxUndecided undecided voxels in this wave's 2048: the scene is too sparse for this tier (the fix-up
-    // kernel behind would take longer than the sweeps) -- say so now, the later workgroups return at once
-    int nund = row_in_grid ? __popc(~acc[kBall3Levels - 1]) : 0;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) nund += __shfl_xor(nund, off);
-    const bool hopeless = nund > a.max_undecided;
-    const bool any_uncert = __any(uncert);
-    const uint32_t open_words = (uint32_t)__popcll(__ballot(uncert));    // words of this wave that hold undecided voxels
-    const bool all_undecided = __all(row_in_grid && acc[kBall3Levels - 1] == 0u);
-    if (any_uncert && a.unc) {
-        if (row_in_grid)
-            a.unc[((int64_t)(x0 + tx_ - a.out_lo) * a.ny + (y0 + ty_)) * nzw + w] = ~acc[kBall3Levels - 1];
-    }
-    if ((t & 63) == 0) {
-        const uint32_t tile_id = (uint32_t)blockIdx.y * gridDim.x + blockIdx.x;
-        // The early-out test at the top is per wave: if the flag rises between the loads of two waves of one workgroup, some
-        // waves leave and the others run on over a partly staged tile -- what they find is garbage.  The field is rewritten
-        // by the stage behind (the flag is up), but maxima are max-folded: they must not leave this wave.  A wave that can
-        // have been affected sees the flag set HERE (it only ever rises), and then the stage behind recomputes every
-        // maximum anyway.
-        const bool void_maxima = a.early_out && __hip_atomic_load(a.uncertified, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
-        if (!void_maxima) slot_max2(a.slots, tile_id * (BD / 64) + ((uint32_t)t >> 6), mxF, mxQ);
-        // (every 16th wave adds its undecided voxels to one of the 512 extrema slots' third word: a 1 / 16 sample of the scene's total
-        //  for k_shell_budget.  ONE status word for all of them -- a thousand same-address atomics -- cost this kernel 76 - 190 us.)
-        if (a.und_sample && nund) {
-            const uint32_t wg = tile_id * (BD / 64) + ((uint32_t)t >> 6);
-            if ((wg & 15u) == 0u) atomicAdd(a.und_sample + (size_t)((wg >> 4) & (kSlots - 1)) * kSlotWords + 2, (uint32_t)nund);
-        }
-        if (any_uncert) {
-            if (a.unc) {
-                // one word per tile: no same-address pile-up.  Bits 0 .. 15: the wave's flag; bits 16 ..: the number of WORDS this wave
-                // leaves undecided voxels in, summed over the tile's waves -- the shell pass reads four of these words and knows at
-                // once whether the group is worth staging (round 5).  (Every wave adds its own bit exactly once: add == or.)
-                atomicAdd(a.tileflag + tile_id, (1u << (t >> 6)) + (open_words << 16));
-                raise_flag(a.fix_needed);
-                // a wave without a single decided voxel sits in empty (or solid) space: nothing for the fix-up kernel
-                if ((a.early_out && all_undecided) || hopeless) {
-                    raise_flag(a.uncertified);
-                    note_reason(a.reason, hopeless ? kGiveUpWaveTooMany : kGiveUpWaveAllUndecided);
-                }
-            } else {
-                raise_flag(a.uncertified);
-                note_reason(a.reason, kGiveUpBeyondBall);
-            }
-        }
-    }
 }
 
 

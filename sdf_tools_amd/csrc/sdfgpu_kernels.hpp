@@ -108,10 +108,21 @@ enum StatusWord : int {
 constexpr uint32_t kReportDense = ((2u << kSwHandoff) - 1u) | (1u << kSwDenseVerdict);   // status words a dense-tier report publishes to the host
 constexpr uint32_t kReportFar = (1u << kSwFarY) | (1u << kSwFarX);                        // ... a far-flag report
 static_assert(kReportDense == 0x1000FFu && kReportFar == 0x30u && kSwFoldTicket < kStatusWords && kSwFlatScore >= kStatusWords, "status words");
-__device__ __forceinline__ void slot_max2(uint32_t* slots, uint32_t wave, int mxF, int mxQ) {
+// The read-before-atomic filter of a slot, both words in ONE 8-byte load (a slot is 128 bytes and 128-byte aligned): one L2 round
+// trip instead of two dependent ones.  slot_peek issues the load, slot_max2_seen consumes it -- a kernel whose tail must not wait
+// (KD, KD3) peeks early and works meanwhile.  The slot's words only grow while a kernel runs (the fold that clears them is a launch
+// of its own), so an old peek can only make a wave send an atomic it would not have needed, never withhold one.
+__device__ __forceinline__ uint64_t slot_peek(const uint32_t* slots, uint32_t wave) {
+    const uint32_t* p = slots + (size_t)(wave & (kSlots - 1)) * kSlotWords;
+    return __hip_atomic_load(reinterpret_cast<const uint64_t*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void slot_max2_seen(uint32_t* slots, uint32_t wave, int mxF, int mxQ, uint64_t seen) {
     uint32_t* p = slots + (size_t)(wave & (kSlots - 1)) * kSlotWords;
-    if (mxF) atomic_max_if_larger(p + 0, (uint32_t)mxF);
-    if (mxQ) atomic_max_if_larger(p + 1, (uint32_t)mxQ);
+    if ((uint32_t)mxF > (uint32_t)seen) atomicMax(p + 0, (uint32_t)mxF);
+    if ((uint32_t)mxQ > (uint32_t)(seen >> 32)) atomicMax(p + 1, (uint32_t)mxQ);
+}
+__device__ __forceinline__ void slot_max2(uint32_t* slots, uint32_t wave, int mxF, int mxQ) {
+    slot_max2_seen(slots, wave, mxF, mxQ, slot_peek(slots, wave));
 }
 
 // End-of-build form (result != nullptr; `maxdsq` is then the context's 8-word status block {maxima, status,
