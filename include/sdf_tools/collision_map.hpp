@@ -6,7 +6,8 @@
 // and their topology (ComputeComponentTopology :620-671, holes and voids per component) by sdfgpu_component_topology_cells.
 // and the surface voxels of each component (ExtractComponentSurfaces :697-754 and its wrappers) by
 // sdfgpu_component_surfaces_cells; CheckIfCandidateCorner (hpp :508-619) is a host query on the stored labels.
-// Convex segments and RViz export are out of scope.  Wire formats (N3): SerializeSelf / DeserializeSelf, SaveToFile /
+// Convex segments are out of scope.  The display export (ExportForDisplay and its kin, :317-562)
+// selects on the GPU (include/sdfgpu.h "Display export", include/sdf_tools/display.hpp).  Wire formats (N3): SerializeSelf / DeserializeSelf, SaveToFile /
 // LoadFromFile ("CMGZ" / "CMGR") and the CollisionMap message pair in the field order of
 // src/sdf_tools/collision_map.cpp:21-62, :205-283, :285-315.  The byte layout of the primitives
 // (arc_utilities::SerializeFixedSizePOD / SerializeEigen / SerializeVector / SerializeString) is the in-tree
@@ -29,6 +30,7 @@
 #include "arc_utilities/zlib_helpers.hpp"
 #include "sdf_tools/component_surfaces.hpp"
 #include "sdf_tools/component_topology.hpp"
+#include "sdf_tools/display.hpp"
 #include "sdf_tools/resample.hpp"
 #include "sdf_tools/sdf.hpp"
 #include "sdf_tools/sdf_generation.hpp"
@@ -191,6 +193,41 @@ public:
         return ExtractComponentSurfaceIndicesFromCells(data_.data(), sizeof(COLLISION_CELL), offsetof(COLLISION_CELL, occupancy),
                                                        offsetof(COLLISION_CELL, component), GetNumXCells(), GetNumYCells(), GetNumZCells(),
                                                        (int)component_types_to_extract, max_label);
+    }
+
+    // ---- display export (reference collision_map.cpp:317-562; include/sdf_tools/display.hpp) -----------------------------------------
+    // Which cells are drawn, and in which order, comes from the GPU (include/sdfgpu.h "Display export"); a class whose colour has
+    // alpha <= 0 is not drawn.  Points are GridIndexToLocationGridFrame of the cell, in the marker's pose = the origin transform.
+    static std_msgs::ColorRGBA GenerateComponentColor(const uint32_t component, const float alpha = 1.0f) { return GenerateUniqueColor(component, alpha); }
+    display::Cells DisplayCells() const {
+        display::Cells c;
+        c.data = data_.data(); c.stride = sizeof(COLLISION_CELL); c.occupancy_offset = offsetof(COLLISION_CELL, occupancy);
+        c.nx = GetNumXCells(); c.ny = GetNumYCells(); c.nz = GetNumZCells(); c.cell_sizes = GetCellSizes();
+        return c;
+    }
+    visualization_msgs::Marker DisplayMarker(const std::string& ns) const { return display::MakeMarker(frame_, ns, GetOriginTransform(), GetResolution()); }
+    visualization_msgs::Marker ExportForDisplay(const std_msgs::ColorRGBA& collision_color, const std_msgs::ColorRGBA& free_color,
+                                                const std_msgs::ColorRGBA& unknown_color) const {
+        return display::ExportOccupancy(DisplayMarker("collision_map_display"), DisplayCells(), collision_color, free_color, unknown_color, false);
+    }
+    visualization_msgs::Marker ExportSurfacesForDisplay(const std_msgs::ColorRGBA& collision_color, const std_msgs::ColorRGBA& free_color,
+                                                        const std_msgs::ColorRGBA& unknown_color) const {
+        return display::ExportOccupancy(DisplayMarker("collision_map_display"), DisplayCells(), collision_color, free_color, unknown_color, true);
+    }
+    // collision, free and unknown cells as three markers, from one grouped selection
+    visualization_msgs::MarkerArray ExportForSeparateDisplay(const std_msgs::ColorRGBA& collision_color, const std_msgs::ColorRGBA& free_color,
+                                                             const std_msgs::ColorRGBA& unknown_color) const {
+        static const char* const ns[3] = {"collision_only", "free_only", "unknown_only"};
+        return display::ExportOccupancySeparate(DisplayMarker("collision_map_display"), DisplayCells(), collision_color, free_color, unknown_color, false, ns);
+    }
+    visualization_msgs::MarkerArray ExportSurfacesForSeparateDisplay(const std_msgs::ColorRGBA& collision_color,
+                                                                     const std_msgs::ColorRGBA& free_color,
+                                                                     const std_msgs::ColorRGBA& unknown_color) const {
+        static const char* const ns[3] = {"collision_surfaces_only", "free_surfaces_only", "unknown_surfaces_only"};
+        return display::ExportOccupancySeparate(DisplayMarker("collision_map_display"), DisplayCells(), collision_color, free_color, unknown_color, true, ns);
+    }
+    visualization_msgs::Marker ExportConnectedComponentsForDisplay(const bool color_unknown_components) const {
+        return display::ExportComponents(DisplayMarker("connected_components_display"), DisplayCells(), data_, color_unknown_components);
     }
 
     // ---- candidate corners (reference collision_map.hpp:508-619): (two or more in-grid face neighbours of another component, index in the grid)

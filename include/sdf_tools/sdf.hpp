@@ -5,7 +5,8 @@
 // and file / message forms (src/sdf_tools/sdf.cpp:213-502), the local extrema map (sdf.cpp:23-207, on the GPU) and projection
 // out of collision / into the valid volume (:996-1190; batched on the GPU through DeviceSignedDistanceField::ProjectBatch), and
 // the smooth and autodiff gradients and DistanceToBoundary (:528-653, :963-988; batched on the GPU through
-// DeviceSignedDistanceField::QueryGradientsBatch).  Out of scope here: RViz export.
+// DeviceSignedDistanceField::QueryGradientsBatch).  ExportForDisplay / ExportForDisplayCollisionOnly (sdf.cpp:504-640) take their selection and
+// colour map from the GPU (include/sdfgpu.h "Display export", include/sdf_tools/display.hpp).
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -23,6 +24,7 @@
 #include "arc_utilities/voxel_grid.hpp"
 #include "arc_utilities/zlib_helpers.hpp"
 #include "sdf_tools/autodiff.hpp"
+#include "sdf_tools/display.hpp"
 #include "sdf_tools/eigen_lite.hpp"
 #include "sdf_tools/gpu_context.hpp"
 
@@ -110,6 +112,52 @@ public:
 
     double GetResolution() const { return GetCellSizes().x(); }
     std::string GetFrame() const { return frame_; }
+
+    // ---- display export (reference sdf.cpp:504-640; include/sdfgpu.h "Display export") ------------------------------------------------
+    // Every cell as a point, coloured by the GPU's colour map: green by d / max for d > 0, red by d / min for d < 0, blue for 0 and NaN.
+    visualization_msgs::Marker ExportForDisplay(const float alpha = 0.01f) const {
+        visualization_msgs::Marker m = display::MakeMarker(frame_, "sdf_display", GetOriginTransform(), GetResolution());
+        const size_t n = data_.size();
+        if (n == 0) return m;
+        std::vector<float> rgba(n * 4);
+        {
+            const std::shared_ptr<sdf_generation::SharedGpuContext> ctx = sdf_generation::GpuContext::Shared();
+            const std::lock_guard<std::mutex> lock(ctx->mutex);
+            sdf_generation::ThrowOnStatus(ctx->handle, sdfgpu_display_sdf_colors(ctx->handle, data_.data(), GetNumXCells(), GetNumYCells(),
+                                                                                 GetNumZCells(), alpha, rgba.data()));
+        }
+        display::Cells c;
+        c.nx = GetNumXCells(); c.ny = GetNumYCells(); c.nz = GetNumZCells(); c.cell_sizes = GetCellSizes();
+        m.points.resize(n);
+        m.colors.resize(n);
+        display::ParallelFor(n, [&](const size_t lo, const size_t hi) {
+            for (size_t i = lo; i < hi; ++i) {
+                m.points[i] = display::PointOf(c, (uint32_t)i);
+                m.colors[i] = display::MakeColor(rgba[4 * i], rgba[4 * i + 1], rgba[4 * i + 2], rgba[4 * i + 3]);
+            }
+        });
+        return m;
+    }
+    // The cells with d <= 0 as points of one colour (the marker's `color`: red with the caller's alpha); no per-point colours.
+    visualization_msgs::Marker ExportForDisplayCollisionOnly(const float alpha = 0.01f) const {
+        visualization_msgs::Marker m = display::MakeMarker(frame_, "sdf_display", GetOriginTransform(), GetResolution());
+        m.color = display::MakeColor(1.0f, 0.0f, 0.0f, alpha);
+        if (data_.empty()) return m;
+        display::Selection s;
+        s.indices.resize(data_.size());
+        int64_t total = 0;
+        {
+            const std::shared_ptr<sdf_generation::SharedGpuContext> ctx = sdf_generation::GpuContext::Shared();
+            const std::lock_guard<std::mutex> lock(ctx->mutex);
+            sdf_generation::ThrowOnStatus(ctx->handle, sdfgpu_display_select_sdf(ctx->handle, data_.data(), GetNumXCells(), GetNumYCells(), GetNumZCells(),
+                                                                                 s.indices.data(), (int64_t)s.indices.size(), &total));
+        }
+        s.indices.resize((size_t)total);
+        display::Cells c;
+        c.nx = GetNumXCells(); c.ny = GetNumYCells(); c.nz = GetNumZCells(); c.cell_sizes = GetCellSizes();
+        display::Append(m, c, s, 0, s.indices.size(), false, [](uint32_t, uint32_t) { return std_msgs::ColorRGBA(); });
+        return m;
+    }
     void SetFrame(const std::string& f) { frame_ = f; }
     bool IsLocked() const { return locked_; }
     void Lock() { locked_ = true; }

@@ -11,7 +11,8 @@
 // CollisionMapGrid's) are computed on the GPU by sdfgpu_components_cells, and their topology (ComputeComponentTopology,
 // :424-490) by sdfgpu_component_topology_cells, and the convex segments (UpdateConvexSegments, :552-654) by
 // sdfgpu_convex_segments_cells, and the surface voxels of each component (ExtractComponentSurfaces, :492-550) by
-// sdfgpu_component_surfaces_cells.  RViz export is out of scope.
+// sdfgpu_component_surfaces_cells.  The display export (ExportForDisplay and its kin, :661-1364) selects on the GPU
+// (include/sdfgpu.h "Display export", include/sdf_tools/display.hpp); the four ExportContourOnlyForDisplay overloads are not mirrored.
 // Every SDF is built on the GPU through sdfgpu_build_tagged_cells (device-side predicate).
 #pragma once
 #include <cstddef>
@@ -32,6 +33,7 @@
 #include "arc_utilities/zlib_helpers.hpp"
 #include "sdf_tools/component_surfaces.hpp"
 #include "sdf_tools/component_topology.hpp"
+#include "sdf_tools/display.hpp"
 #include "sdf_tools/resample.hpp"
 #include "sdf_tools/sdf.hpp"
 #include "sdf_tools/sdf_generation.hpp"
@@ -121,6 +123,153 @@ public:
     double GetResolution() const { return GetCellSizes().x(); }
     std::string GetFrame() const { return frame_; }
     void SetFrame(const std::string& f) { frame_ = f; }
+
+    // ---- display export (reference tagged_object_collision_map.cpp:661-1364; include/sdf_tools/display.hpp) ---------------------------
+    // Which cells are drawn and in which order comes from the GPU (include/sdfgpu.h "Display export", rule KEY_FIELD on object_id or
+    // convex_segment, OCCUPANCY for the occupancy form); a cell whose colour has alpha <= 0 is not drawn, and the palette gives id 0
+    // alpha 0.  Not mirrored: the four ExportContourOnlyForDisplay overloads.
+    static std_msgs::ColorRGBA GenerateComponentColor(const uint32_t component, const float alpha = 1.0f) { return GenerateUniqueColor(component, alpha); }
+    display::Cells DisplayCells() const {
+        display::Cells c;
+        c.data = data_.data(); c.stride = sizeof(TAGGED_OBJECT_COLLISION_CELL); c.occupancy_offset = offsetof(TAGGED_OBJECT_COLLISION_CELL, occupancy);
+        c.nx = GetNumXCells(); c.ny = GetNumYCells(); c.nz = GetNumZCells(); c.cell_sizes = GetCellSizes();
+        return c;
+    }
+    // (does not fill the namespace)
+    visualization_msgs::Marker DefaultMarker() const { return display::MakeMarker(frame_, "", GetOriginTransform(), GetResolution()); }
+
+private:
+    static constexpr const char* kDisplayNs = "tagged_object_collision_map_display";
+    visualization_msgs::Marker NamedMarker(const std::string& ns) const { visualization_msgs::Marker m = DefaultMarker(); m.ns = ns; return m; }
+    display::Selection SelectObjects(const std::vector<uint32_t>* draw, const bool draw_zero, const bool grouped) const {
+        return display::SelectCells(DisplayCells(), SDFGPU_DISPLAY_KEY_FIELD, offsetof(TAGGED_OBJECT_COLLISION_CELL, object_id), 7, false, draw,
+                                    draw_zero, grouped);
+    }
+    // One marker per object from a grouped selection: `first` are the ids that get a marker up front, in that order (a repeated id
+    // keeps its last place, as the reference's map does); the other drawn ids follow in the order of their first cell in the scan
+    // when `others`.  Markers without points are pruned.
+    template <typename ColorOf>
+    visualization_msgs::MarkerArray UniqueNsMarkers(const display::Selection& s, const std::vector<uint32_t>& first, const bool others,
+                                                    ColorOf color_of) const {
+        std::map<uint32_t, size_t> group_of;
+        for (size_t g = 0; g < s.group_keys.size(); ++g) group_of[s.group_keys[g]] = g;
+        std::map<uint32_t, size_t> place;                                  // id -> its place among the up-front markers
+        for (size_t i = 0; i < first.size(); ++i) place[first[i]] = i;
+        std::vector<uint32_t> order;
+        for (size_t i = 0; i < first.size(); ++i) if (place[first[i]] == i) order.push_back(first[i]);
+        if (others) {
+            std::vector<std::pair<uint32_t, uint32_t>> rest;               // (first index, id)
+            for (size_t g = 0; g < s.group_keys.size(); ++g)
+                if (!place.count(s.group_keys[g])) rest.emplace_back(s.indices[s.group_offsets[g]], s.group_keys[g]);
+            std::sort(rest.begin(), rest.end());
+            for (const auto& r : rest) order.push_back(r.second);
+        }
+        visualization_msgs::MarkerArray out;
+        const display::Cells c = DisplayCells();
+        for (const uint32_t id : order) {
+            const auto found = group_of.find(id);
+            if (found == group_of.end()) continue;                         // (no drawn cell: the marker would be pruned)
+            const size_t g = found->second;
+            out.markers.push_back(NamedMarker(std::string(kDisplayNs) + "_" + std::to_string(id)));
+            display::Append(out.markers.back(), c, s, s.group_offsets[g], s.group_offsets[g + 1], true,
+                            [&](const uint32_t key, uint32_t) { return color_of(key); });
+        }
+        return out;
+    }
+    // colour of an object under a caller's colour map: the map's entry, else the palette's
+    static std_msgs::ColorRGBA MappedColor(const std::map<uint32_t, std_msgs::ColorRGBA>& color_map, const uint32_t id) {
+        const auto found = color_map.find(id);
+        return found != color_map.end() ? found->second : GenerateComponentColor(id);
+    }
+    // the selection of the colour-map forms: every object whose colour is visible (the GPU draws all ids, 0 only when the map makes
+    // it visible; objects that the map hides are dropped here)
+    display::Selection SelectMapped(const std::map<uint32_t, std_msgs::ColorRGBA>& color_map, const bool grouped) const {
+        display::Selection s = SelectObjects(nullptr, MappedColor(color_map, 0u).a > 0.0f, grouped);
+        std::vector<uint32_t> hidden;
+        for (const auto& kv : color_map) if (!(kv.second.a > 0.0f) && kv.first != 0u) hidden.push_back(kv.first);
+        if (hidden.empty() || s.indices.empty()) return s;
+        display::Selection kept;
+        kept.group_offsets.assign(1, 0u);
+        auto is_hidden = [&](const uint32_t id) { return std::binary_search(hidden.begin(), hidden.end(), id); };
+        if (!grouped) {
+            for (size_t i = 0; i < s.indices.size(); ++i)
+                if (!is_hidden(s.keys[i])) { kept.indices.push_back(s.indices[i]); kept.keys.push_back(s.keys[i]); }
+            return kept;
+        }
+        for (size_t g = 0; g < s.group_keys.size(); ++g) {
+            if (is_hidden(s.group_keys[g])) continue;
+            kept.indices.insert(kept.indices.end(), s.indices.begin() + s.group_offsets[g], s.indices.begin() + s.group_offsets[g + 1]);
+            kept.keys.insert(kept.keys.end(), s.keys.begin() + s.group_offsets[g], s.keys.begin() + s.group_offsets[g + 1]);
+            kept.group_keys.push_back(s.group_keys[g]);
+            kept.group_offsets.push_back((uint32_t)kept.indices.size());
+        }
+        return kept;
+    }
+
+public:
+    visualization_msgs::Marker ExportForDisplay(const float alpha = 1.0f, const std::vector<uint32_t>& objects_to_draw = std::vector<uint32_t>()) const {
+        visualization_msgs::Marker m = NamedMarker(kDisplayNs);
+        if (!(alpha > 0.0f)) return m;                                     // (every colour would be invisible)
+        const display::Selection s = SelectObjects(objects_to_draw.empty() ? nullptr : &objects_to_draw, false, false);
+        display::Append(m, DisplayCells(), s, 0, s.indices.size(), true, [&](const uint32_t key, uint32_t) { return GenerateComponentColor(key, alpha); });
+        return m;
+    }
+    visualization_msgs::MarkerArray ExportForDisplayUniqueNs(const float alpha = 1.0f,
+                                                             const std::vector<uint32_t>& objects_to_draw = std::vector<uint32_t>()) const {
+        if (!(alpha > 0.0f)) return visualization_msgs::MarkerArray();
+        const display::Selection s = SelectObjects(objects_to_draw.empty() ? nullptr : &objects_to_draw, false, true);
+        return UniqueNsMarkers(s, objects_to_draw, objects_to_draw.empty(), [&](const uint32_t key) { return GenerateComponentColor(key, alpha); });
+    }
+    visualization_msgs::Marker ExportForDisplay(const std::map<uint32_t, std_msgs::ColorRGBA>& color_map) const {
+        visualization_msgs::Marker m = NamedMarker(kDisplayNs);
+        const display::Selection s = SelectMapped(color_map, false);
+        display::Append(m, DisplayCells(), s, 0, s.indices.size(), true, [&](const uint32_t key, uint32_t) { return MappedColor(color_map, key); });
+        return m;
+    }
+    // markers of the map's objects first, in ascending id, then the others in the order of their first cell
+    visualization_msgs::MarkerArray ExportForDisplayUniqueNs(const std::map<uint32_t, std_msgs::ColorRGBA>& color_map) const {
+        std::vector<uint32_t> first;
+        for (const auto& kv : color_map) first.push_back(kv.first);
+        return UniqueNsMarkers(SelectMapped(color_map, true), first, true, [&](const uint32_t key) { return MappedColor(color_map, key); });
+    }
+    visualization_msgs::Marker ExportForDisplayOccupancyOnly(const std_msgs::ColorRGBA& collision_color, const std_msgs::ColorRGBA& free_color,
+                                                             const std_msgs::ColorRGBA& unknown_color) const {
+        return display::ExportOccupancy(NamedMarker("tagged_object_collision_map_occupancy_display"), DisplayCells(), collision_color, free_color,
+                                        unknown_color, false);
+    }
+    visualization_msgs::Marker ExportConnectedComponentsForDisplay(const bool color_unknown_components) const {
+        return display::ExportComponents(NamedMarker("tagged_object_connected_components_display"), DisplayCells(), data_, color_unknown_components);
+    }
+    // The cells of one convex segment of one object: the GPU selects the segment, the object id is tested on the records here.
+    // Below 22 segments the palette colours the segment; from 22 up the reference interpolates hot to cold, which is not vendored:
+    // the palette stands in (UNVERIFIED, include/sdf_tools/display.hpp).
+    visualization_msgs::Marker ExportConvexSegmentForDisplay(const uint32_t object_id, const uint32_t convex_segment) const {
+        visualization_msgs::Marker m = NamedMarker("tagged_object_" + std::to_string(object_id) + "_convex_segment_" + std::to_string(convex_segment) + "_display");
+        const std::vector<uint32_t> segment(1, convex_segment);
+        display::Selection s = display::SelectCells(DisplayCells(), SDFGPU_DISPLAY_KEY_FIELD, offsetof(TAGGED_OBJECT_COLLISION_CELL, convex_segment), 7,
+                                                    false, &segment, true, false);
+        size_t kept = 0;
+        for (size_t i = 0; i < s.indices.size(); ++i)
+            if (data_[s.indices[i]].object_id == object_id) { s.indices[kept] = s.indices[i]; s.keys[kept] = s.keys[i]; ++kept; }
+        s.indices.resize(kept);
+        s.keys.resize(kept);
+        display::Append(m, DisplayCells(), s, 0, kept, true, [&](const uint32_t key, uint32_t) { return GenerateComponentColor(key); });
+        return m;
+    }
+    // host only: walks the caller's map (its order), keeping the entries marked 1
+    visualization_msgs::Marker ExportSurfaceForDisplay(const std::unordered_map<GRID_INDEX, uint8_t>& surface,
+                                                       const std_msgs::ColorRGBA& surface_color) const {
+        visualization_msgs::Marker m = NamedMarker("tagged_object_collision_map_surface");
+        for (const auto& entry : surface) {
+            if (entry.second != 1) continue;
+            const Eigen::Vector4d l = GridIndexToLocationGridFrame(entry.first);
+            geometry_msgs::Point p;
+            p.x = l(0); p.y = l(1); p.z = l(2);
+            m.points.push_back(p);
+            m.colors.push_back(surface_color);
+        }
+        return m;
+    }
 
     bool SetValue(const int64_t x, const int64_t y, const int64_t z, const TAGGED_OBJECT_COLLISION_CELL& value) override {
         if (!IndexInBounds(x, y, z)) return false;

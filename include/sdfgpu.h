@@ -728,6 +728,73 @@ int sdfgpu_resample_cells(sdfgpu_handle h, const void* src, size_t cell_bytes, i
  * gather kernel, in milliseconds, from HIP events on its stream (synchronises with them; tools/resample_bench.py). */
 int sdfgpu_debug_resample_times(sdfgpu_handle h, double* out_winner_ms, double* out_gather_ms);
 
+/* ---------------------------------------------------------------------------
+ * Display export: the device side of the reference's ExportForDisplay family (CollisionMapGrid, TaggedObjectCollisionMapGrid,
+ * SignedDistanceField): which voxels are drawn, in which order, where they are and in which colour.  DESIGN.md section 23.
+ * Indices: voxel (x, y, z) is (x ny + y) nz + z, a uint32; a grid of more than 2^32 - 1 voxels is refused by its shape before
+ * anything is allocated.  Scan order is ascending index, the order of the reference's x -> y -> z loops.
+ *
+ * SELECT.  A rule yields "drawn?" and a uint32 key per voxel.
+ *   SDFGPU_DISPLAY_OCCUPANCY: the class of the occupancy float by the reference's literal comparisons -- F occ > 0.5, E occ < 0.5,
+ *     U occ == 0.5, N (NaN) none of them.  key = 0 for F, 1 for E, 2 for U and N (NaN falls into the reference's `else`).  Drawn iff
+ *     bit `key` of class_mask (FILLED 1, EMPTY 2, UNKNOWN 4; 0 .. 7) is set and, with surface_only, some in-bounds cell o of the 26
+ *     around it makes one of these true: cell E and o in {F, U}; cell F and o in {E, U}; cell U and o in {F, E, N}.  An N cell is
+ *     never a surface.  Cells outside the grid do not exist.  key_offset is not used.
+ *   SDFGPU_DISPLAY_KEY_FIELD: key = the uint32 at key_offset (component, object_id, convex_segment).  Drawn iff (draw_keys is NULL or
+ *     holds the key) and (draw_zero or key != 0) and bit `class of the occupancy` of class_mask is set (7 = every cell; the
+ *     occupancy is then not read).  draw_keys is a HOST array of n_draw_keys ascending keys in both forms (non-NULL with
+ *     n_draw_keys = 0 draws nothing); surface_only is not used.
+ *   sdfgpu_display_select_sdf*: drawn iff d <= 0.0f (NaN is not); key 0.
+ * RESULT.  *out_total = the number of drawn voxels, always.  indices = NULL asks for that alone.  Otherwise
+ *   grouped = 0: indices[0 .. total) ascending; keys[i] beside them when keys != NULL;
+ *   grouped = 1: the same pairs ordered by (key, index), stably; *out_groups = the number of distinct keys G, group_keys[g]
+ *     ascending, group g = elements [group_offsets[g], group_offsets[g + 1]), group_offsets[G] = total.  The group arrays are
+ *     written on the device; group_offsets holds group_capacity + 1 words.  Only the key bits in which the drawn keys differ
+ *     are sorted (eight a pass, from a device reduction of the smallest and largest key); with none it is the plain compaction.
+ *   capacity < total, or group_capacity < G: SDFGPU_ERR_INVALID_ARGUMENT; *out_total (and *out_groups) are valid, so the caller
+ *     can size the buffers and call again, and nothing is written past either capacity (with a short index buffer nothing
+ *     is written at all).
+ * EXPAND (sdfgpu_display_expand_device).  Per element e of d_indices[0 .. count): d_points[3 e ..] = cell_sizes[a] * ((double)i_a +
+ *   0.5) for the three axis indices of the voxel (one rounding: VoxelGrid::GridIndexToLocationGridFrame bit for bit); d_colors[4 e ..]
+ *   = d_color_table[4 key ..] when key = d_keys[e] (0 with d_keys = NULL) is below table_entries, else default_color.  Either of
+ *   d_points / d_colors may be NULL.  Returns with its kernel pending on `stream`; uses no scratch.  The indices are TRUSTED: nx, ny, nz
+ *   only decompose them, and an index at or past nx ny nz yields a point outside the grid without a word from the call (nothing is
+ *   read or written out of bounds: every access is by element number).
+ * SDF COLOUR MAP (SignedDistanceField::ExportForDisplay).  max_distance and min_distance are doubles that start at 0.0 and move
+ *   on d > max / d < min (NaN moves neither).  Per voxel one rgba: a = min(max(alpha, 0), 1); d > 0: g = float(fabs((double)d / max)
+ *   * 0.8 + 0.2); d < 0: r likewise with min; else (0, NaN) b = 1; the other channels 0.  Double arithmetic, the product and the sum
+ *   rounded separately.  A NaN alpha is refused.
+ * All select and colour-map calls are synchronous (they read status words back and their scratch belongs to the handle: scratch
+ * of their own from the library's allocator; the SDF scratch, status block and policy are left as they were).  Device pointers
+ * need 4-byte alignment only (d_points included).  The host forms stage records / fields through the handle's staging buffers on
+ * the null stream.
+ * ------------------------------------------------------------------------- */
+#define SDFGPU_DISPLAY_OCCUPANCY 0
+#define SDFGPU_DISPLAY_KEY_FIELD 1
+#define SDFGPU_DISPLAY_FILLED 1
+#define SDFGPU_DISPLAY_EMPTY 2
+#define SDFGPU_DISPLAY_UNKNOWN 4
+int sdfgpu_display_select_cells_device(sdfgpu_handle h, const void* d_cells, size_t cell_stride, size_t occupancy_offset, size_t key_offset,
+                                       int64_t nx, int64_t ny, int64_t nz, int rule, int class_mask, int surface_only,
+                                       const uint32_t* draw_keys, int64_t n_draw_keys, int draw_zero, int grouped, uint32_t* d_indices,
+                                       uint32_t* d_keys, int64_t capacity, int64_t* out_total, uint32_t* d_group_keys,
+                                       uint32_t* d_group_offsets, int64_t group_capacity, int64_t* out_groups, void* stream);
+int sdfgpu_display_select_cells(sdfgpu_handle h, const void* cells, size_t cell_stride, size_t occupancy_offset, size_t key_offset, int64_t nx,
+                                int64_t ny, int64_t nz, int rule, int class_mask, int surface_only, const uint32_t* draw_keys,
+                                int64_t n_draw_keys, int draw_zero, int grouped, uint32_t* out_indices, uint32_t* out_keys, int64_t capacity,
+                                int64_t* out_total, uint32_t* out_group_keys, uint32_t* out_group_offsets, int64_t group_capacity,
+                                int64_t* out_groups);
+int sdfgpu_display_select_sdf_device(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t ny, int64_t nz, uint32_t* d_indices,
+                                     int64_t capacity, int64_t* out_total, void* stream);
+int sdfgpu_display_select_sdf(sdfgpu_handle h, const float* sdf, int64_t nx, int64_t ny, int64_t nz, uint32_t* out_indices, int64_t capacity,
+                              int64_t* out_total);
+int sdfgpu_display_expand_device(sdfgpu_handle h, const uint32_t* d_indices, const uint32_t* d_keys, int64_t count, int64_t nx, int64_t ny,
+                                 int64_t nz, const double cell_sizes[3], double* d_points, float* d_colors, const float* d_color_table,
+                                 int64_t table_entries, const float default_color[4], void* stream);
+int sdfgpu_display_sdf_colors_device(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t ny, int64_t nz, float alpha, float* d_colors,
+                                     void* stream);
+int sdfgpu_display_sdf_colors(sdfgpu_handle h, const float* sdf, int64_t nx, int64_t ny, int64_t nz, float alpha, float* out_colors);
+
 /* Red zones (round 6).  With SDFGPU_REDZONE=1 in the environment when sdfgpu_create runs -- or after
  * sdfgpu_set_option(h, "redzone", 1) -- every device allocation of the library (scratch fields, status block, extrema slots,
  * staging buffers, sdfgpu_device_malloc memory) carries 4 KiB of canary bytes in front and behind, and every entry point that

@@ -33,11 +33,11 @@ def _hipcc():
 
 
 def build_libsdfgpu(force=False, verbose=False):
-    """Eleven translation units -> objects (compiled side by side) -> libsdfgpu.so: sdfgpu.hip (C ABI, host orchestration, most
+    """Twelve translation units -> objects (compiled side by side) -> libsdfgpu.so: sdfgpu.hip (C ABI, host orchestration, most
     kernels), sdfgpu_envelope_tu.hip (the far-field kernel's instantiations), sdfgpu_dense6_tu.hip (the shell pass),
     sdfgpu_components.hip (connected components), sdfgpu_topology.hip (component topology), sdfgpu_surfaces.hip (component surfaces), sdfgpu_convex.hip (local extrema
     and convex segments), sdfgpu_project.hip (projection out of collision) sdfgpu_query.hip (smooth and autodiff gradients,
-    distance to the boundary), sdfgpu_batch.hip (batches of small same-shape grids) and sdfgpu_resample.hip (Resample).  Each object is rebuilt when its
+    distance to the boundary), sdfgpu_batch.hip (batches of small same-shape grids), sdfgpu_resample.hip (Resample) and sdfgpu_display.hip (display export).  Each object is rebuilt when its
     source or ANY header it can include is newer (a stale library after a header-only edit is the kind of bug that
     invalidates measurements without failing anything)."""
     from concurrent.futures import ThreadPoolExecutor
@@ -56,7 +56,8 @@ def build_libsdfgpu(force=False, verbose=False):
              (os.path.join(CSRC, "sdfgpu_query.hip"), [os.path.join(CSRC, f) for f in ("sdfgpu_query.hpp", "sdfgpu_kernels.hpp")] +
               [os.path.join(INCLUDE, "sdfgpu.h"), os.path.join(INCLUDE, "sdf_tools", "autodiff.hpp")]),
              (os.path.join(CSRC, "sdfgpu_batch.hip"), [os.path.join(CSRC, f) for f in ("sdfgpu_batch.hpp", "sdfgpu_kernels.hpp")]),
-             (os.path.join(CSRC, "sdfgpu_resample.hip"), [os.path.join(CSRC, "sdfgpu_resample.hpp")])]
+             (os.path.join(CSRC, "sdfgpu_resample.hip"), [os.path.join(CSRC, "sdfgpu_resample.hpp")]),
+             (os.path.join(CSRC, "sdfgpu_display.hip"), [os.path.join(CSRC, f) for f in ("sdfgpu_display.hpp", "sdfgpu_surfaces.hpp")])]
     objdir = os.path.join(CSRC, ".obj")
     os.makedirs(objdir, exist_ok=True)
     todo, objs = [], []

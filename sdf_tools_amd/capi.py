@@ -37,6 +37,8 @@ EXPORTS = [
     "sdfgpu_build_batch_device", "sdfgpu_get_extrema_batch", "sdfgpu_build_batch", "sdfgpu_build_tagged_objects",
     "sdfgpu_gradient_batch_device", "sdfgpu_last_batch_info",
     "sdfgpu_resample_cells_device", "sdfgpu_resample_cells", "sdfgpu_debug_resample_times",
+    "sdfgpu_display_select_cells_device", "sdfgpu_display_select_cells", "sdfgpu_display_select_sdf_device", "sdfgpu_display_select_sdf",
+    "sdfgpu_display_expand_device", "sdfgpu_display_sdf_colors_device", "sdfgpu_display_sdf_colors",
 ]
 
 # include/sdfgpu.h "Projection": modes and per-point statuses
@@ -47,6 +49,10 @@ PROJECT_MAX_STEPS_CEILING = 1048576
 # include/sdfgpu.h "Interpolated gradients": kinds and per-point statuses
 QUERY_SMOOTH_GRADIENT, QUERY_AUTODIFF_GRADIENT, QUERY_DISTANCE_TO_BOUNDARY = 0, 1, 2
 QUERY_OK, QUERY_OUTSIDE, QUERY_WINDOW_TOO_LARGE, QUERY_NON_FINITE = range(4)
+
+# include/sdfgpu.h "Display export": rules and class bits
+DISPLAY_OCCUPANCY, DISPLAY_KEY_FIELD = 0, 1
+DISPLAY_FILLED, DISPLAY_EMPTY, DISPLAY_UNKNOWN = 1, 2, 4
 
 
 class SdfGpuError(RuntimeError):
@@ -146,6 +152,13 @@ def load_library():
     L.sdfgpu_resample_cells_device.argtypes = [vp, vp, sz, i64, i64, i64, vp, vp, vp, vp, vp, i64, i64, i64, vp, vp, vp]
     L.sdfgpu_resample_cells.argtypes = [vp, vp, sz, i64, i64, i64, vp, vp, vp, vp, vp, i64, i64, i64, vp, vp]
     L.sdfgpu_debug_resample_times.argtypes = [vp, vp, vp]
+    L.sdfgpu_display_select_cells_device.argtypes = [vp, vp, sz, sz, sz, i64, i64, i64, ci, ci, ci, vp, i64, ci, ci, vp, vp, i64, vp, vp, vp, i64, vp, vp]
+    L.sdfgpu_display_select_cells.argtypes = [vp, vp, sz, sz, sz, i64, i64, i64, ci, ci, ci, vp, i64, ci, ci, vp, vp, i64, vp, vp, vp, i64, vp]
+    L.sdfgpu_display_select_sdf_device.argtypes = [vp, vp, i64, i64, i64, vp, i64, vp, vp]
+    L.sdfgpu_display_select_sdf.argtypes = [vp, vp, i64, i64, i64, vp, i64, vp]
+    L.sdfgpu_display_expand_device.argtypes = [vp, vp, vp, i64, i64, i64, i64, vp, vp, vp, vp, i64, vp, vp]
+    L.sdfgpu_display_sdf_colors_device.argtypes = [vp, vp, i64, i64, i64, ctypes.c_float, vp, vp]
+    L.sdfgpu_display_sdf_colors.argtypes = [vp, vp, i64, i64, i64, ctypes.c_float, vp]
     L.sdfgpu_build_batch_device.argtypes = [vp, vp, i64, i64, i64, i64, dbl, vp, ci, vp, vp]
     L.sdfgpu_get_extrema_batch.argtypes = [vp, i64, vp, vp]
     L.sdfgpu_build_batch.argtypes = [vp, vp, i64, i64, i64, i64, dbl, vp, ci, vp, vp, vp]
@@ -693,6 +706,126 @@ class SdfGpu:
                                                            mx, my, mz, fill.ctypes.data, ctypes.byref(written) if count else None,
                                                            stream or None))
         return int(written.value) if count else None
+
+    # ---- display export (the ExportForDisplay family, include/sdfgpu.h "Display export") -----------------
+    @staticmethod
+    def _draw_keys(draw_keys):
+        if draw_keys is None:
+            return None, 0, None
+        k = np.ascontiguousarray(draw_keys, dtype=np.uint32).reshape(-1)
+        n = int(k.size)
+        if n == 0:
+            k = np.zeros(1, np.uint32)                          # (an empty list is still a list: a non-null pointer)
+        return k, n, k.ctypes.data
+
+    def display_select_cells(self, cells, shape, rule, cell_stride=8, occupancy_offset=0, key_offset=4, class_mask=7, surface_only=False,
+                             draw_keys=None, draw_zero=True, grouped=False, capacity=None, group_capacity=None):
+        """cells: contiguous records; rule: DISPLAY_OCCUPANCY or DISPLAY_KEY_FIELD.  Returns (indices uint32 [total], keys uint32
+        [total]) in scan order, or with grouped (indices, keys, group_keys uint32 [G], group_offsets uint32 [G + 1]) ordered by
+        (key, index).  Without a capacity a count-only call sizes the arrays first; a short capacity / group_capacity raises
+        SdfGpuError whose `total` and `groups` attributes hold the numbers needed."""
+        nx, ny, nz = (int(v) for v in shape)
+        if not (isinstance(cells, np.ndarray) and cells.flags.c_contiguous):
+            raise ValueError("cells must be a C-contiguous numpy array")
+        if cells.nbytes != nx * ny * nz * cell_stride:
+            raise ValueError("cells buffer size does not match shape * cell_stride")
+        total, groups = ctypes.c_int64(-1), ctypes.c_int64(-1)
+        dk, n_dk, p_dk = self._draw_keys(draw_keys)
+        if capacity is None:                                    # a count-only call sizes the arrays (4 words per VOXEL otherwise)
+            self._check(self._lib.sdfgpu_display_select_cells(
+                self._h, cells.ctypes.data, cell_stride, occupancy_offset, key_offset, nx, ny, nz, int(rule), int(class_mask),
+                int(bool(surface_only)), p_dk, n_dk, int(bool(draw_zero)), 0, None, None, 0, ctypes.byref(total), None, None, 0, None))
+        cap = int(total.value) if capacity is None else int(capacity)
+        # (at most one group per drawn voxel; the occupancy rule has three keys)
+        gcap = (min(cap, 3) if int(rule) == DISPLAY_OCCUPANCY else cap) if group_capacity is None else int(group_capacity)
+        idx, keys = np.empty(max(cap, 1), np.uint32), np.empty(max(cap, 1), np.uint32)
+        gkeys, goffs = np.empty(max(gcap, 1), np.uint32), np.empty(gcap + 1, np.uint32)
+        try:
+            self._check(self._lib.sdfgpu_display_select_cells(
+                self._h, cells.ctypes.data, cell_stride, occupancy_offset, key_offset, nx, ny, nz, int(rule), int(class_mask),
+                int(bool(surface_only)), p_dk, n_dk, int(bool(draw_zero)), int(bool(grouped)), idx.ctypes.data, keys.ctypes.data, cap,
+                ctypes.byref(total), gkeys.ctypes.data if grouped else None, goffs.ctypes.data if grouped else None, gcap,
+                ctypes.byref(groups) if grouped else None))
+        except SdfGpuError as e:
+            e.total, e.groups = int(total.value), int(groups.value)
+            raise
+        t, g = int(total.value), int(groups.value)
+        if grouped:
+            return idx[:t].copy(), keys[:t].copy(), gkeys[:g].copy(), goffs[:g + 1].copy()
+        return idx[:t].copy(), keys[:t].copy()
+
+    def display_select_cells_device(self, d_cells, shape, rule, cell_stride=8, occupancy_offset=0, key_offset=4, class_mask=7,
+                                    surface_only=False, draw_keys=None, draw_zero=True, grouped=False, d_indices=None, d_keys=None,
+                                    capacity=0, d_group_keys=None, d_group_offsets=None, group_capacity=0, stream=0):
+        """Device records and device result arrays (uint32 [capacity]; d_group_offsets [group_capacity + 1]); draw_keys is a host
+        list.  Without d_indices only the total is computed.  Returns (total, groups); synchronises `stream`."""
+        nx, ny, nz = (int(v) for v in shape)
+        total, groups = ctypes.c_int64(-1), ctypes.c_int64(-1)
+        dk, n_dk, p_dk = self._draw_keys(draw_keys)
+        try:
+            self._check(self._lib.sdfgpu_display_select_cells_device(
+                self._h, d_cells, cell_stride, occupancy_offset, key_offset, nx, ny, nz, int(rule), int(class_mask), int(bool(surface_only)),
+                p_dk, n_dk, int(bool(draw_zero)), int(bool(grouped)), d_indices or None, d_keys or None, int(capacity), ctypes.byref(total),
+                d_group_keys or None, d_group_offsets or None, int(group_capacity), ctypes.byref(groups) if grouped else None,
+                stream or None))
+        except SdfGpuError as e:
+            e.total, e.groups = int(total.value), int(groups.value)
+            raise
+        return int(total.value), int(groups.value) if grouped else 0
+
+    def display_select_sdf(self, sdf, capacity=None):
+        """sdf: float32 [nx, ny, nz].  Returns the indices of the voxels with d <= 0, ascending (uint32)."""
+        f = np.ascontiguousarray(sdf, dtype=np.float32)
+        if f.ndim != 3:
+            raise ValueError("sdf must be [nx, ny, nz]")
+        total = ctypes.c_int64(-1)
+        if capacity is None:                                    # a count-only call sizes the array
+            self._check(self._lib.sdfgpu_display_select_sdf(self._h, f.ctypes.data, *f.shape, None, 0, ctypes.byref(total)))
+        cap = int(total.value) if capacity is None else int(capacity)
+        idx = np.empty(max(cap, 1), np.uint32)
+        try:
+            self._check(self._lib.sdfgpu_display_select_sdf(self._h, f.ctypes.data, *f.shape, idx.ctypes.data, cap, ctypes.byref(total)))
+        except SdfGpuError as e:
+            e.total = int(total.value)
+            raise
+        return idx[:total.value].copy()
+
+    def display_select_sdf_device(self, d_sdf, shape, d_indices=None, capacity=0, stream=0):
+        """Device field; d_indices: device uint32 [capacity] or None (the total only).  Returns the total; synchronises `stream`."""
+        nx, ny, nz = (int(v) for v in shape)
+        total = ctypes.c_int64(-1)
+        try:
+            self._check(self._lib.sdfgpu_display_select_sdf_device(self._h, d_sdf, nx, ny, nz, d_indices or None, int(capacity),
+                                                                    ctypes.byref(total), stream or None))
+        except SdfGpuError as e:
+            e.total = int(total.value)
+            raise
+        return int(total.value)
+
+    def display_expand_device(self, d_indices, count, shape, cell_sizes, d_points=None, d_colors=None, d_keys=None, d_color_table=None,
+                              table_entries=0, default_color=(0.0, 0.0, 0.0, 0.0), stream=0):
+        """indices (+ keys) -> d_points (float64 [count, 3], grid frame) and / or d_colors (float32 [count, 4]) from the device table
+        (float32 [table_entries, 4]; keys at or past its end get default_color).  Returns with the kernel pending on `stream`."""
+        nx, ny, nz = (int(v) for v in shape)
+        cs = _doubles(cell_sizes, 3)
+        dc = np.ascontiguousarray(default_color, dtype=np.float32).reshape(4)
+        self._check(self._lib.sdfgpu_display_expand_device(self._h, d_indices, d_keys or None, int(count), nx, ny, nz, cs,
+                                                            d_points or None, d_colors or None, d_color_table or None, int(table_entries),
+                                                            dc.ctypes.data, stream or None))
+
+    def display_sdf_colors(self, sdf, alpha):
+        """sdf: float32 [nx, ny, nz].  Returns the colour map of SignedDistanceField::ExportForDisplay, float32 [nx, ny, nz, 4]."""
+        f = np.ascontiguousarray(sdf, dtype=np.float32)
+        if f.ndim != 3:
+            raise ValueError("sdf must be [nx, ny, nz]")
+        out = np.empty(f.shape + (4,), np.float32)
+        self._check(self._lib.sdfgpu_display_sdf_colors(self._h, f.ctypes.data, *f.shape, float(alpha), out.ctypes.data))
+        return out
+
+    def display_sdf_colors_device(self, d_sdf, shape, alpha, d_colors, stream=0):
+        """Device field -> d_colors (float32 [n, 4]).  Synchronises `stream`."""
+        nx, ny, nz = (int(v) for v in shape)
+        self._check(self._lib.sdfgpu_display_sdf_colors_device(self._h, d_sdf, nx, ny, nz, float(alpha), d_colors, stream or None))
 
     def debug_resample_times(self):
         """(memset + winner kernel, gather kernel) of the last resample call in ms, after set_option("resample_timing", 1)"""

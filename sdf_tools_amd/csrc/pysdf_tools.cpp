@@ -9,7 +9,9 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <array>
 #include <cstdint>
+#include <map>
 #include <cstring>
 #include <type_traits>
 #include <utility>
@@ -96,6 +98,68 @@ void DefSurfaces(Class& cls) {
     cls.attr("UNKNOWN_COMPONENTS") = py::int_(4);
 }
 
+// ---- display export for Python: the reference binds none of it, so these are numpy forms of the C++ methods.  A Marker becomes
+// (points float64 [n, 3] in the grid frame, colors float32 [n, 4]); a MarkerArray a list of (ns, points, colors); colours go in as
+// (r, g, b, a).  MarkerInfo gives what every method fills besides the elements.
+static_assert(sizeof(geometry_msgs::Point) == 24 && sizeof(std_msgs::ColorRGBA) == 16, "points and colours are copied as plain arrays");
+
+using Rgba = std::array<float, 4>;
+std_msgs::ColorRGBA ColorOf(const Rgba& c) { return sdf_tools::display::MakeColor(c[0], c[1], c[2], c[3]); }
+
+py::tuple MarkerNumpy(const visualization_msgs::Marker& m) {
+    py::array_t<double> points({(py::ssize_t)m.points.size(), (py::ssize_t)3});
+    py::array_t<float> colors({(py::ssize_t)m.colors.size(), (py::ssize_t)4});
+    if (!m.points.empty()) std::memcpy(points.mutable_data(), m.points.data(), m.points.size() * sizeof(geometry_msgs::Point));
+    if (!m.colors.empty()) std::memcpy(colors.mutable_data(), m.colors.data(), m.colors.size() * sizeof(std_msgs::ColorRGBA));
+    return py::make_tuple(points, colors);
+}
+
+py::list MarkerArrayNumpy(const visualization_msgs::MarkerArray& a) {
+    py::list out;
+    for (const visualization_msgs::Marker& m : a.markers) {
+        const py::tuple t = MarkerNumpy(m);
+        out.append(py::make_tuple(m.ns, t[0], t[1]));
+    }
+    return out;
+}
+
+py::dict MarkerInfo(const visualization_msgs::Marker& m) {
+    py::dict d;
+    d["frame_id"] = m.header.frame_id;
+    d["ns"] = m.ns;
+    d["id"] = m.id;
+    d["type"] = m.type;
+    d["action"] = m.action;
+    d["lifetime"] = m.lifetime;
+    d["frame_locked"] = m.frame_locked;
+    d["position"] = py::make_tuple(m.pose.position.x, m.pose.position.y, m.pose.position.z);
+    d["orientation"] = py::make_tuple(m.pose.orientation.x, m.pose.orientation.y, m.pose.orientation.z, m.pose.orientation.w);
+    d["scale"] = py::make_tuple(m.scale.x, m.scale.y, m.scale.z);
+    d["color"] = py::make_tuple(m.color.r, m.color.g, m.color.b, m.color.a);
+    d["points"] = m.points.size();
+    d["colors"] = m.colors.size();
+    return d;
+}
+
+template <typename Make>
+py::tuple ReleasedMarker(Make make) {
+    visualization_msgs::Marker m;
+    { py::gil_scoped_release release; m = make(); }
+    return MarkerNumpy(m);
+}
+template <typename Make>
+py::list ReleasedMarkerArray(Make make) {
+    visualization_msgs::MarkerArray a;
+    { py::gil_scoped_release release; a = make(); }
+    return MarkerArrayNumpy(a);
+}
+
+std::map<uint32_t, std_msgs::ColorRGBA> ColorMapOf(const std::map<uint32_t, Rgba>& in) {
+    std::map<uint32_t, std_msgs::ColorRGBA> out;
+    for (const auto& kv : in) out[kv.first] = ColorOf(kv.second);
+    return out;
+}
+
 // Resample, and the cell records in bulk (uint8 [nx, ny, nz, sizeof(cell)]) so that whole grids go in and out without per-cell calls
 template <typename Grid, typename Class>
 void DefResample(Class& cls) {
@@ -170,6 +234,39 @@ PYBIND11_MODULE(pysdf_tools, m) {
     DefSurfaces<TaggedObjectCollisionMapGrid>(tagged_grid);
     DefResample<TaggedObjectCollisionMapGrid>(tagged_grid);
     tagged_grid
+        .def("DefaultMarker", [](const TaggedObjectCollisionMapGrid& g) { return MarkerInfo(g.DefaultMarker()); },
+             "what every display method fills besides ns and the elements, as a dict")
+        .def("ExportForDisplay", [](const TaggedObjectCollisionMapGrid& g, float alpha, const std::vector<uint32_t>& objects_to_draw) {
+            return ReleasedMarker([&]() { return g.ExportForDisplay(alpha, objects_to_draw); });
+        }, py::arg("alpha") = 1.0f, py::arg("objects_to_draw") = std::vector<uint32_t>(), "(points, colors) of the cells of the listed objects (all when empty)")
+        .def("ExportForDisplay", [](const TaggedObjectCollisionMapGrid& g, const std::map<uint32_t, Rgba>& color_map) {
+            return ReleasedMarker([&]() { return g.ExportForDisplay(ColorMapOf(color_map)); });
+        }, py::arg("color_map"))
+        .def("ExportForDisplayUniqueNs", [](const TaggedObjectCollisionMapGrid& g, float alpha, const std::vector<uint32_t>& objects_to_draw) {
+            return ReleasedMarkerArray([&]() { return g.ExportForDisplayUniqueNs(alpha, objects_to_draw); });
+        }, py::arg("alpha") = 1.0f, py::arg("objects_to_draw") = std::vector<uint32_t>(), "[(ns, points, colors)]: one entry per drawn object")
+        .def("ExportForDisplayUniqueNs", [](const TaggedObjectCollisionMapGrid& g, const std::map<uint32_t, Rgba>& color_map) {
+            return ReleasedMarkerArray([&]() { return g.ExportForDisplayUniqueNs(ColorMapOf(color_map)); });
+        }, py::arg("color_map"))
+        .def("ExportForDisplayOccupancyOnly", [](const TaggedObjectCollisionMapGrid& g, const Rgba& c, const Rgba& f, const Rgba& u) {
+            return ReleasedMarker([&]() { return g.ExportForDisplayOccupancyOnly(ColorOf(c), ColorOf(f), ColorOf(u)); });
+        }, py::arg("collision_color"), py::arg("free_color"), py::arg("unknown_color"))
+        .def("ExportConnectedComponentsForDisplay", [](const TaggedObjectCollisionMapGrid& g, bool color_unknown_components) {
+            return ReleasedMarker([&]() { return g.ExportConnectedComponentsForDisplay(color_unknown_components); });
+        }, py::arg("color_unknown_components"))
+        .def("ExportConvexSegmentForDisplay", [](const TaggedObjectCollisionMapGrid& g, uint32_t object_id, uint32_t convex_segment) {
+            return ReleasedMarker([&]() { return g.ExportConvexSegmentForDisplay(object_id, convex_segment); });
+        }, py::arg("object_id"), py::arg("convex_segment"))
+        .def("ExportSurfaceForDisplay", [](const TaggedObjectCollisionMapGrid& g, const std::vector<std::array<int64_t, 3>>& surface, const Rgba& color) {
+            std::unordered_map<VoxelGrid::GRID_INDEX, uint8_t> map;
+            for (const auto& i : surface) map[VoxelGrid::GRID_INDEX(i[0], i[1], i[2])] = 1;
+            return MarkerNumpy(g.ExportSurfaceForDisplay(map, ColorOf(color)));
+        }, py::arg("surface"), py::arg("color"), "host only; the elements come in the order of the hash map built from `surface`")
+        .def_static("GenerateComponentColor", [](uint32_t id, float alpha) {
+            const std_msgs::ColorRGBA c = TaggedObjectCollisionMapGrid::GenerateComponentColor(id, alpha);
+            return py::make_tuple(c.r, c.g, c.b, c.a);
+        }, py::arg("component"), py::arg("alpha") = 1.0f, "the in-tree palette (parity with arc_helpers UNVERIFIED); id 0 has alpha 0");
+    tagged_grid
         .def(py::init<Isometry3d const&, std::string, double, int64_t, int64_t, int64_t, TAGGED_OBJECT_COLLISION_CELL const&>())
         .def(py::init<>())
         .def("SetValue", [](TaggedObjectCollisionMapGrid& g, int64_t x, int64_t y, int64_t z, const TAGGED_OBJECT_COLLISION_CELL& c) { return g.SetValue(x, y, z, c); })
@@ -213,6 +310,14 @@ PYBIND11_MODULE(pysdf_tools, m) {
 
     py::class_<SignedDistanceField>(m, "SignedDistanceField")
         .def(py::init<>())
+        .def("ExportForDisplay", [](const SignedDistanceField& f, float alpha) { return ReleasedMarker([&]() { return f.ExportForDisplay(alpha); }); },
+             py::arg("alpha") = 0.01f, "(points float64 [n, 3], colors float32 [n, 4]) of every cell, the colour map computed on the GPU")
+        .def("ExportForDisplayCollisionOnly", [](const SignedDistanceField& f, float alpha) {
+            return ReleasedMarker([&]() { return f.ExportForDisplayCollisionOnly(alpha); });
+        }, py::arg("alpha") = 0.01f, "(points of the cells with d <= 0, an empty colour array: the marker has one colour)")
+        .def("ExportForDisplayInfo", [](const SignedDistanceField& f, float alpha, bool collision_only) {
+            return MarkerInfo(collision_only ? f.ExportForDisplayCollisionOnly(alpha) : f.ExportForDisplay(alpha));
+        }, py::arg("alpha") = 0.01f, py::arg("collision_only") = false, "header, ns, id, type, action, pose, scale, color and the element counts")
         .def("GetRawData", &SignedDistanceField::GetImmutableRawData, "Please don't mutate this")
         .def("GetFullGradient", &SignedDistanceField::GetFullGradient)
         .def("GetResolution", &SignedDistanceField::GetResolution)
@@ -452,6 +557,26 @@ PYBIND11_MODULE(pysdf_tools, m) {
     py::class_<CollisionMapGrid> collision_grid(m, "CollisionMapGrid");
     DefSurfaces<CollisionMapGrid>(collision_grid);
     DefResample<CollisionMapGrid>(collision_grid);
+    collision_grid
+        .def("ExportForDisplay", [](const CollisionMapGrid& g, const Rgba& c, const Rgba& f, const Rgba& u) {
+            return ReleasedMarker([&]() { return g.ExportForDisplay(ColorOf(c), ColorOf(f), ColorOf(u)); });
+        }, py::arg("collision_color"), py::arg("free_color"), py::arg("unknown_color"),
+             "(points float64 [n, 3], colors float32 [n, 4]) of the cells whose class colour has alpha > 0, in scan order")
+        .def("ExportSurfacesForDisplay", [](const CollisionMapGrid& g, const Rgba& c, const Rgba& f, const Rgba& u) {
+            return ReleasedMarker([&]() { return g.ExportSurfacesForDisplay(ColorOf(c), ColorOf(f), ColorOf(u)); });
+        }, py::arg("collision_color"), py::arg("free_color"), py::arg("unknown_color"), "... of the surface cells (26-neighbour rule)")
+        .def("ExportForSeparateDisplay", [](const CollisionMapGrid& g, const Rgba& c, const Rgba& f, const Rgba& u) {
+            return ReleasedMarkerArray([&]() { return g.ExportForSeparateDisplay(ColorOf(c), ColorOf(f), ColorOf(u)); });
+        }, py::arg("collision_color"), py::arg("free_color"), py::arg("unknown_color"), "[(ns, points, colors)] x 3: collision, free, unknown")
+        .def("ExportSurfacesForSeparateDisplay", [](const CollisionMapGrid& g, const Rgba& c, const Rgba& f, const Rgba& u) {
+            return ReleasedMarkerArray([&]() { return g.ExportSurfacesForSeparateDisplay(ColorOf(c), ColorOf(f), ColorOf(u)); });
+        }, py::arg("collision_color"), py::arg("free_color"), py::arg("unknown_color"))
+        .def("ExportConnectedComponentsForDisplay", [](const CollisionMapGrid& g, bool color_unknown_components) {
+            return ReleasedMarker([&]() { return g.ExportConnectedComponentsForDisplay(color_unknown_components); });
+        }, py::arg("color_unknown_components"))
+        .def("ExportForDisplayInfo", [](const CollisionMapGrid& g, const Rgba& c, const Rgba& f, const Rgba& u) {
+            return MarkerInfo(g.ExportForDisplay(ColorOf(c), ColorOf(f), ColorOf(u)));
+        }, "header, ns, id, type, action, pose, scale and the element counts of ExportForDisplay");
     collision_grid
         .def(py::init<Isometry3d const&, std::string, double, int64_t, int64_t, int64_t, COLLISION_CELL const&>())
         .def("SetValue", [](CollisionMapGrid& g, int64_t x, int64_t y, int64_t z, const COLLISION_CELL& c) { return g.SetValue(x, y, z, c); })

@@ -106,8 +106,10 @@ struct SortArgs {
     uint64_t tiles;                            // of this pass
     int shift, nb;                             // digit = (label >> shift) & (2^nb - 1)
     uint32_t* table;                           // [2^nb][tiles]
+    uint32_t* sums;                            // the scan's segment sums
     uint2* dst_pairs;                          // or, on the last pass,
     uint32_t* dst_idx;
+    uint32_t* dst_key;                         // ... and the labels beside them, or nullptr (sf_launch_sort_pairs)
 };
 
 // element (tile, round r, lane) of the pass's input, in order; `any` is wave-uniform: some lane of the round has an element
@@ -182,8 +184,12 @@ __global__ __launch_bounds__(64) void k_sf_scatter(const SortArgs a) {
         base = __shfl(base, leader);
         if (has) {
             const uint32_t pos = base + (uint32_t)__popcll(m & lt);       // (< total <= the destination's capacity)
-            if (LAST) a.dst_idx[pos] = idx;
-            else a.dst_pairs[pos] = make_uint2(lab, idx);
+            if (LAST) {
+                a.dst_idx[pos] = idx;
+                if (a.dst_key) a.dst_key[pos] = lab;
+            } else {
+                a.dst_pairs[pos] = make_uint2(lab, idx);
+            }
         }
         __syncthreads();                                    // (run is read by other lanes in the next round)
     }
@@ -297,13 +303,36 @@ hipError_t sf_launch_flag(const SfPlan& p, const uint32_t* d_labels, const uint3
     return hipGetLastError();
 }
 
+void sf_launch_scan(uint32_t* d_table, uint64_t entries, uint32_t* d_sums, hipStream_t s) {
+    if (entries == 0) return;
+    const uint64_t segs = (entries + kSfScanSeg - 1) / kSfScanSeg;
+    hipLaunchKernelGGL(k_sf_scan_reduce, dim3((unsigned)segs), dim3(kScanThreads), 0, s, (const uint32_t*)d_table, entries, d_sums);
+    hipLaunchKernelGGL(k_sf_scan_top, dim3(1), dim3(kTopThreads), 0, s, d_sums, segs);
+    hipLaunchKernelGGL(k_sf_scan_apply, dim3((unsigned)segs), dim3(kScanThreads), 0, s, d_table, entries, (const uint32_t*)d_sums);
+}
+
+namespace {
+
+// one pass of the sort: histogram, scan of the table, scatter
+hipError_t launch_pass(const SortArgs& a, bool first, bool last, hipStream_t s) {
+    const dim3 grid((unsigned)a.tiles), block(64);
+    if (first) hipLaunchKernelGGL(k_sf_hist<true>, grid, block, 0, s, a);
+    else hipLaunchKernelGGL(k_sf_hist<false>, grid, block, 0, s, a);
+    sf_launch_scan(a.table, a.tiles << a.nb, a.sums, s);
+    if (first && last) hipLaunchKernelGGL((k_sf_scatter<true, true>), grid, block, 0, s, a);
+    else if (first) hipLaunchKernelGGL((k_sf_scatter<true, false>), grid, block, 0, s, a);
+    else if (last) hipLaunchKernelGGL((k_sf_scatter<false, true>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((k_sf_scatter<false, false>), grid, block, 0, s, a);
+    return hipGetLastError();
+}
+
+}  // namespace
+
 hipError_t sf_launch_sort(const SfPlan& p, const SfSortPlan& sp, const uint32_t* d_labels, const void* d_scratch, void* d_sort,
                           uint32_t* d_indices, hipStream_t s) {
     if (sp.total == 0) return hipSuccess;
     char* q = static_cast<char*>(d_sort);
     uint2* const pairs[2] = {reinterpret_cast<uint2*>(q), reinterpret_cast<uint2*>(q + sp.off_b)};
-    uint32_t* const table = reinterpret_cast<uint32_t*>(q + sp.off_table);
-    uint32_t* const sums = reinterpret_cast<uint32_t*>(q + sp.off_sums);
     for (int k = 0; k < p.passes; ++k) {
         const bool first = k == 0, last = k == p.passes - 1;
         SortArgs a;
@@ -314,21 +343,49 @@ hipError_t sf_launch_sort(const SfPlan& p, const SfSortPlan& sp, const uint32_t*
         a.tiles = first ? p.tiles : (sp.total + kSfTile - 1) / kSfTile;
         a.shift = k * kSfDigitBits;
         a.nb = std::max(0, std::min(kSfDigitBits, p.label_bits - a.shift));
-        a.table = table;
+        a.table = reinterpret_cast<uint32_t*>(q + sp.off_table);
+        a.sums = reinterpret_cast<uint32_t*>(q + sp.off_sums);
         a.dst_pairs = last ? nullptr : pairs[k & 1];
         a.dst_idx = last ? d_indices : nullptr;
-        const uint64_t entries = a.tiles << a.nb, segs = (entries + kSfScanSeg - 1) / kSfScanSeg;
-        const dim3 grid((unsigned)a.tiles), block(64);
-        if (first) hipLaunchKernelGGL(k_sf_hist<true>, grid, block, 0, s, a);
-        else hipLaunchKernelGGL(k_sf_hist<false>, grid, block, 0, s, a);
-        hipLaunchKernelGGL(k_sf_scan_reduce, dim3((unsigned)segs), dim3(kScanThreads), 0, s, (const uint32_t*)table, entries, sums);
-        hipLaunchKernelGGL(k_sf_scan_top, dim3(1), dim3(kTopThreads), 0, s, sums, segs);
-        hipLaunchKernelGGL(k_sf_scan_apply, dim3((unsigned)segs), dim3(kScanThreads), 0, s, table, entries, (const uint32_t*)sums);
-        if (first && last) hipLaunchKernelGGL((k_sf_scatter<true, true>), grid, block, 0, s, a);
-        else if (first) hipLaunchKernelGGL((k_sf_scatter<true, false>), grid, block, 0, s, a);
-        else if (last) hipLaunchKernelGGL((k_sf_scatter<false, true>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((k_sf_scatter<false, false>), grid, block, 0, s, a);
-        const hipError_t e = hipGetLastError();
+        a.dst_key = nullptr;
+        const hipError_t e = launch_pass(a, first, last, s);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+SfPairSortPlan sf_pair_sort_plan(uint64_t total, int key_bits) {
+    SfPairSortPlan sp;
+    sp.total = total;
+    sp.passes = (key_bits + kSfDigitBits - 1) / kSfDigitBits;
+    const uint64_t entries = ((total + kSfTile - 1) / kSfTile) << std::min(key_bits, kSfDigitBits);
+    sp.off_b = (size_t)total * 8;
+    sp.off_table = 2 * sp.off_b;
+    sp.off_sums = sp.off_table + align8((size_t)entries * 4);
+    sp.bytes = sp.off_sums + align8((size_t)((entries + kSfScanSeg - 1) / kSfScanSeg) * 4);
+    return sp;
+}
+
+hipError_t sf_launch_sort_pairs(const SfPairSortPlan& sp, int key_bits, void* d_sort, uint32_t* d_indices, uint32_t* d_keys, hipStream_t s) {
+    if (sp.total == 0) return hipSuccess;
+    char* q = static_cast<char*>(d_sort);
+    uint2* const pairs[2] = {reinterpret_cast<uint2*>(q), reinterpret_cast<uint2*>(q + sp.off_b)};
+    for (int k = 0; k < sp.passes; ++k) {
+        const bool last = k == sp.passes - 1;
+        SortArgs a;
+        a.L = nullptr;
+        a.bits = nullptr;
+        a.src = pairs[k & 1];
+        a.total = sp.total;
+        a.tiles = (sp.total + kSfTile - 1) / kSfTile;
+        a.shift = k * kSfDigitBits;
+        a.nb = std::min(kSfDigitBits, key_bits - a.shift);
+        a.table = reinterpret_cast<uint32_t*>(q + sp.off_table);
+        a.sums = reinterpret_cast<uint32_t*>(q + sp.off_sums);
+        a.dst_pairs = last ? nullptr : pairs[(k + 1) & 1];
+        a.dst_idx = last ? d_indices : nullptr;
+        a.dst_key = last ? d_keys : nullptr;
+        const hipError_t e = launch_pass(a, false, last, s);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;

@@ -68,4 +68,21 @@ hipError_t sf_launch_flag(const SfPlan& p, const uint32_t* d_labels, const uint3
 hipError_t sf_launch_sort(const SfPlan& p, const SfSortPlan& sp, const uint32_t* d_labels, const void* d_scratch, void* d_sort,
                           uint32_t* d_indices, hipStream_t s);
 
+
+// ---- the scan and the sort on their own (sdfgpu_display.hpp: the display export compacts and groups with them) ---------------------
+// In-place exclusive scan of `entries` uint32 on `s`; d_sums: ceil(entries / kSfScanSeg) words of scratch.
+void sf_launch_scan(uint32_t* d_table, uint64_t entries, uint32_t* d_sums, hipStream_t s);
+
+// The later passes of the sort without the first: `total` (key, index) pairs that stand in index order at the start of d_sort are
+// ordered stably on key bits [0, key_bits), key_bits >= 1 (keys must agree in every bit above).  Scratch: pairs A | pairs B |
+// table | segment sums.  The last pass stores the indices into d_indices and the keys into d_keys (both hold `total`).
+struct SfPairSortPlan {
+    uint64_t total = 0;
+    int passes = 0;                            // ceil(key_bits / kSfDigitBits)
+    size_t off_b = 0, off_table = 0, off_sums = 0;
+    size_t bytes = 0;
+};
+SfPairSortPlan sf_pair_sort_plan(uint64_t total, int key_bits);
+hipError_t sf_launch_sort_pairs(const SfPairSortPlan& sp, int key_bits, void* d_sort, uint32_t* d_indices, uint32_t* d_keys, hipStream_t s);
+
 }  // namespace sdfgpu
