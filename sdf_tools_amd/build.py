@@ -1,6 +1,6 @@
 """In-tree builds of the native pieces (no network, no cmake needed).
 
-  libsdfgpu.so   HIP kernels + C ABI (include/sdfgpu.h), hipcc --offload-arch=gfx950
+  libsdfgpu.so   HIP kernels + C ABI (include/sdfgpu.h): every csrc/*.hip, hipcc --offload-arch=gfx950
   pysdf_tools    pybind11 module mirroring the reference's src/sdf_tools/bindings.cpp
 
 hipcc cross-compiles gfx950 without a GPU, so this runs in the CPU container;
@@ -32,41 +32,47 @@ def _hipcc():
             return c
 
 
+def _depfile_sources(depfile):
+    """The files a Makefile-style depfile (hipcc -MD -MF) names as prerequisites; None when it is missing or unreadable.
+    Split on whitespace: a path with a space in it (written as `\\ `) comes out as names that do not exist, which _stale reads as
+    "rebuild" -- such a tree over-builds on every run and never goes stale."""
+    try:
+        text = open(depfile).read()
+    except OSError:
+        return None
+    words = text.replace("\\\n", " ").split()
+    return [w for w in words if not w.endswith(":")]
+
+
+def _stale(obj, src):
+    """An object is rebuilt when it or its depfile is missing, or when its source or any file the depfile names is newer."""
+    deps = _depfile_sources(obj + ".d")
+    if deps is None or not os.path.exists(obj):
+        return True
+    t = os.path.getmtime(obj)
+    return any(not os.path.exists(d) or os.path.getmtime(d) > t for d in [src] + deps)
+
+
 def build_libsdfgpu(force=False, verbose=False):
-    """Twelve translation units -> objects (compiled side by side) -> libsdfgpu.so: sdfgpu.hip (C ABI, host orchestration, most
-    kernels), sdfgpu_envelope_tu.hip (the far-field kernel's instantiations), sdfgpu_dense6_tu.hip (the shell pass),
-    sdfgpu_components.hip (connected components), sdfgpu_topology.hip (component topology), sdfgpu_surfaces.hip (component surfaces), sdfgpu_convex.hip (local extrema
-    and convex segments), sdfgpu_project.hip (projection out of collision) sdfgpu_query.hip (smooth and autodiff gradients,
-    distance to the boundary), sdfgpu_batch.hip (batches of small same-shape grids), sdfgpu_resample.hip (Resample) and sdfgpu_display.hip (display export).  Each object is rebuilt when its
-    source or ANY header it can include is newer (a stale library after a header-only edit is the kind of bug that
+    """Every csrc/*.hip -> an object (compiled side by side) -> libsdfgpu.so.  DESIGN.md section 5 has the table of the units:
+    sdfgpu.hip (the SDF build: its C ABI, host orchestration and most kernels), sdfgpu_context.hip (the handle), the two
+    instantiation units (sdfgpu_envelope_tu.hip, sdfgpu_dense6_tu.hip) and one unit per family with its kernels, launchers, host
+    code and entry points (components, topology, surfaces, convex, project, query, batch, resample, display).
+
+    Dependencies are the compiler's: each compile writes <obj>.d (-MD -MF), and an object is rebuilt when its source or ANY file
+    named there is newer, or when the depfile is missing (a stale library after a header-only edit is the kind of bug that
     invalidates measurements without failing anything)."""
     from concurrent.futures import ThreadPoolExecutor
-    hdrs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.startswith("sdfgpu") and f.endswith(".hpp")) + [
-        os.path.join(INCLUDE, "sdfgpu.h")]
-    env_hdrs = [os.path.join(CSRC, f) for f in ("sdfgpu_envelope_dc.hpp", "sdfgpu_kernels.hpp", "sdfgpu_sweep_x16.hpp")]
-    d6_hdrs = [os.path.join(CSRC, f) for f in ("sdfgpu_dense6.hpp", "sdfgpu_dense3.hpp", "sdfgpu_dense.hpp", "sdfgpu_kernels.hpp")]
-    units = [(os.path.join(CSRC, "sdfgpu.hip"), hdrs), (os.path.join(CSRC, "sdfgpu_envelope_tu.hip"), env_hdrs),
-             (os.path.join(CSRC, "sdfgpu_dense6_tu.hip"), d6_hdrs),
-             (os.path.join(CSRC, "sdfgpu_components.hip"), [os.path.join(CSRC, "sdfgpu_components.hpp")]),
-             (os.path.join(CSRC, "sdfgpu_topology.hip"), [os.path.join(CSRC, "sdfgpu_topology.hpp")]),
-             (os.path.join(CSRC, "sdfgpu_surfaces.hip"), [os.path.join(CSRC, "sdfgpu_surfaces.hpp")]),
-             (os.path.join(CSRC, "sdfgpu_convex.hip"), [os.path.join(CSRC, f) for f in ("sdfgpu_convex.hpp", "sdfgpu_kernels.hpp")]),
-             (os.path.join(CSRC, "sdfgpu_project.hip"), [os.path.join(CSRC, f) for f in ("sdfgpu_project.hpp", "sdfgpu_kernels.hpp")] +
-              [os.path.join(INCLUDE, "sdfgpu.h")]),
-             (os.path.join(CSRC, "sdfgpu_query.hip"), [os.path.join(CSRC, f) for f in ("sdfgpu_query.hpp", "sdfgpu_kernels.hpp")] +
-              [os.path.join(INCLUDE, "sdfgpu.h"), os.path.join(INCLUDE, "sdf_tools", "autodiff.hpp")]),
-             (os.path.join(CSRC, "sdfgpu_batch.hip"), [os.path.join(CSRC, f) for f in ("sdfgpu_batch.hpp", "sdfgpu_kernels.hpp")]),
-             (os.path.join(CSRC, "sdfgpu_resample.hip"), [os.path.join(CSRC, "sdfgpu_resample.hpp")]),
-             (os.path.join(CSRC, "sdfgpu_display.hip"), [os.path.join(CSRC, f) for f in ("sdfgpu_display.hpp", "sdfgpu_surfaces.hpp")])]
+    units = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hip"))
     objdir = os.path.join(CSRC, ".obj")
     os.makedirs(objdir, exist_ok=True)
     todo, objs = [], []
-    for src, deps in units:
+    for src in units:
         obj = os.path.join(objdir, os.path.basename(src)[:-4] + ".o")
         objs.append(obj)
-        if force or _newer(obj, [src] + deps):
-            todo.append([_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-pthread", "-I", INCLUDE, "-c", src,
-                         "-o", obj])
+        if force or _stale(obj, src):
+            todo.append([_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-pthread", "-I", INCLUDE, "-MD", "-MF", obj + ".d",
+                         "-c", src, "-o", obj])
     if not todo and not _newer(LIB, objs):
         return LIB
     if verbose:

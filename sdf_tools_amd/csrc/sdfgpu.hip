@@ -1,6 +1,8 @@
-// sdfgpu.hip -- C ABI (include/sdfgpu.h) over the gfx950 kernels in sdfgpu_kernels.hpp.
-// Host side of the drop-in boundary for sdf_generation::ExtractSignedDistanceField
-// (reference include/sdf_tools/sdf_generation.hpp:209-420).  No CPU fallback.
+// sdfgpu.hip -- the SDF build: C ABI (include/sdfgpu.h) over the gfx950 kernels in sdfgpu_kernels.hpp and its sibling build
+// headers, and the one unit that launches them.  Host side of the drop-in boundary for
+// sdf_generation::ExtractSignedDistanceField (reference include/sdf_tools/sdf_generation.hpp:209-420).  No CPU fallback.
+// The handle and its helpers are in sdfgpu_context.hpp / .hip; the analysis families (components, topology, surfaces, local
+// extrema, projection, query gradients, resample, display) keep their host code and entry points in their own units.
 #include "sdfgpu_kernels.hpp"
 #include "sdfgpu_sweep_x16.hpp"
 #include "sdfgpu_sweep_y16.hpp"
@@ -9,22 +11,9 @@
 #include "sdfgpu_fused_zy.hpp"
 #include "sdfgpu_dense.hpp"
 #include "sdfgpu_envelope_dc.hpp"
-#include "sdfgpu_policy.hpp"
-#include "sdfgpu_hostteam.hpp"
-#include "sdfgpu_components.hpp"
-#include "sdfgpu_topology.hpp"
-#include "sdfgpu_surfaces.hpp"
 #include "sdfgpu_convex.hpp"
-#include "sdfgpu_project.hpp"
-#include "sdfgpu_query.hpp"
 #include "sdfgpu_batch.hpp"
-#include "sdfgpu_resample.hpp"
-#include "sdfgpu_display.hpp"
-
-#include <sys/mman.h>
-#if defined(__SSE2__)
-#include <emmintrin.h>
-#endif
+#include "sdfgpu_context.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -39,439 +28,18 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/sdfgpu.h"
-
 using namespace sdfgpu;
 
 namespace {
 
 constexpr int kH = 3;            // register-window radius of the marching sweeps
-constexpr int64_t kMaxDim = 16384;
 
-thread_local std::string g_create_error = "";
-
-struct DeviceBuffer {
-    void* ptr = nullptr;
-    size_t bytes = 0;
-};
-
-// Cross-stream ordering of work that shares state of the handle: an event behind the last such work and the stream it was
-// recorded on.  Work on that stream is ordered by the stream itself; work on any other stream waits for the event first.
-struct StreamOrder {
-    hipEvent_t ev = nullptr;         // created on first use
-    hipStream_t stream = nullptr;    // where ev was last recorded
-    bool recorded = false;
-    hipError_t create() { return ev ? hipSuccess : hipEventCreateWithFlags(&ev, hipEventDisableTiming); }
-    hipError_t wait(hipStream_t s) const { return recorded && s != stream ? hipStreamWaitEvent(s, ev, 0) : hipSuccess; }
-    hipError_t record(hipStream_t s) {
-        hipError_t e = create();
-        if (e == hipSuccess && (e = hipEventRecord(ev, s)) == hipSuccess) { recorded = true; stream = s; }
-        return e;
-    }
-    // `s` becomes the recorded stream WITHOUT a record: for a caller that has just waited on `s` and enqueues a sequence there whose
-    // steps would each wait again, ending in record(s).  Until then another stream's wait sees the event as the previous work left it.
-    hipError_t adopt(hipStream_t s) { const hipError_t e = create(); if (e == hipSuccess) { recorded = true; stream = s; } return e; }
-    hipError_t host_wait() const { return recorded ? hipEventSynchronize(ev) : hipSuccess; }
-    void destroy() { if (ev) (void)hipEventDestroy(ev); ev = nullptr; recorded = false; }
-    struct RecordAtExit { StreamOrder& order; hipStream_t s; ~RecordAtExit() { (void)order.record(s); } };   // record(s) on every path out of a scope
-};
-
-// Every DeviceBuffer of the context, and nothing else: sdfgpu_destroy and the "redzone" switch walk them as an array, so a buffer
-// added here is freed by the one and released by the other.
-struct ContextBuffers {
-    DeviceBuffer zfield;     // int16 [N]   K1 output
-    DeviceBuffer yzfield;    // int32 [N]   K2 output (32-bit pipeline) / side table (16-bit pipeline)
-    DeviceBuffer plane16;    // int16 [N]   plane field of the 16-bit pipeline
-    DeviceBuffer bits;       // uint32 [N/32] packed occupancy of the dense path
-    DeviceBuffer unc;        // uint32 [N/32] undecided bits handed from the dense ball kernel to its fix-up kernel
-    DeviceBuffer tileflag;   // uint32 [tiles] which waves of a tile wrote unc words (kept zero between builds)
-    DeviceBuffer fix_order;  // uint32 [kFixRows] (dx, dy) rows of the fix-up kernel sorted by dx^2 + dy^2
-    DeviceBuffer tagmask;    // uint8 [N] mask produced by the tagged-object classify kernel
-    DeviceBuffer tagids;     // uint32 object id filter
-    DeviceBuffer stage_in;   // host-API staging: mask / cells
-    DeviceBuffer stage_bits; // host-API staging: the host-classified bit field (1 bit per voxel, linear order)
-    DeviceBuffer stage_out;  // host-API staging: sdf
-    DeviceBuffer query_stage;   // host-API staging of the three point calls: points | three result sections (with_staged_points)
-    DeviceBuffer cc_scratch;    // sdfgpu_components*: root flags, ranks, chunk counts, K (sdfgpu_components.hpp)
-    DeviceBuffer tp_scratch;    // sdfgpu_component_topology*: counters, status, node bytes, node offsets (sdfgpu_topology.hpp)
-    DeviceBuffer tp_nodes;      // sdfgpu_component_topology*: one union-find word per surface-vertex node
-    DeviceBuffer sf_scratch;    // sdfgpu_component_surfaces*: per-label counts, status, surface bit words (sdfgpu_surfaces.hpp)
-    DeviceBuffer sf_sort;       // sdfgpu_component_surfaces*: the sort's pair buffers and histogram table
-    DeviceBuffer sf_indices;    // sdfgpu_component_surfaces / _cells: the indices on their way to the caller's host buffer
-    DeviceBuffer cx_scratch;    // sdfgpu_local_extrema* / sdfgpu_convex_segments_cells: doubling state, next, stats, ranks (sdfgpu_convex.hpp)
-    DeviceBuffer cx_field;      // sdfgpu_local_extrema: the field; sdfgpu_convex_segments_cells: the named-object SDF, then the extrema
-    // Batches of same-shape grids (sdfgpu_batch.hpp).  Scratch of their own: a batch build leaves the single builds' fields, status
-    // block, result block and policy as they were.
-    DeviceBuffer batch_field;   // int16 [batch][N] signed in-plane d^2 between k_batch_zy and k_batch_x_finish
-    DeviceBuffer batch_ext;     // uint32 [batch][2] per-grid maxima | 24 words: the single builds' result block while a slow-path batch runs
-    DeviceBuffer batch_res;     // double [batch] per-grid resolutions
-    DeviceBuffer batch_gscale;  // GradScale [batch] of sdfgpu_gradient_batch_device
-    DeviceBuffer planebits;  // row_any [nx * ny] bytes | plane_any [nx] bytes | row_bits [nx][ceil(ny / 32)] words (k_sweep_z_wave16, k_pack_row_flags, EnvDcArgs)
-    DeviceBuffer rs_scratch; // sdfgpu_resample_cells*: one winner word per result cell, the counter (sdfgpu_resample.hpp)
-    DeviceBuffer ball_bits;  // sdfgpu_dense_ball_device / sdfgpu_slab_dense_phase: copy of a caller's bit planes that are off 16 bytes
-    DeviceBuffer ball_out;   // ... and the field of such a call while the caller's is off 16 bytes (launch_ball_dense)
-    DeviceBuffer dp_scratch; // sdfgpu_display_*: status, draw keys, drawn bit words, tile counts, segment sums (sdfgpu_display.hpp)
-    DeviceBuffer dp_sort;    // sdfgpu_display_select_*: the sort's pair buffers and table; the sorted keys when the caller takes none
-    DeviceBuffer dp_out;     // host forms of sdfgpu_display_select_*: indices, keys, group keys and offsets on their way to the caller
-    DeviceBuffer* begin() { return &zfield; }
-    DeviceBuffer* end() { return begin() + sizeof(ContextBuffers) / sizeof(DeviceBuffer); }
-};
-static_assert(sizeof(ContextBuffers) == 32 * sizeof(DeviceBuffer), "ContextBuffers holds DeviceBuffer members only");
-
-// What sdfgpu_set_option and sdfgpu_set_tuning write and a build only reads (include/sdfgpu.h has the table).  The defaults here are
-// the documented ones.
-struct BuildOptions {
-    // tier selection
-    bool dense_on = true;            // try the bit-parallel dense kernel first when the shape allows
-    bool dense_generic_on = true;    // generic dense kernels for shapes / modes the tuned ones do not take
-    bool envelope_on = true;         // bound the outward scans and redo far-field sweeps with the envelope kernels
-    bool envelope_dc = true;         // use the divide-and-conquer envelope kernel (sdfgpu_envelope_dc.hpp) when the shape allows
-    int force_env = -1;              // -1 automatic, 1 = envelope kernels only (option "envelope_mode")
-    // an axis is far-field when more than 1 / kFarDen of the probed voxels have d^2 >= thr.  Per axis, from the measured
-    // break-even of the two sweeps at 512^3 (tools/p_sweep.py, tools/ythr_probe.py): the y marching sweep (2 B rows, radius-8
-    // windows) against the far-field PAIR (int32 hand-off, no x probe) breaks even at in-plane d^2 ~ 36 on an eighth of the
-    // voxels (Bernoulli p = 0.02: 1.31 vs 1.29 ms; p = 0.015: 1.54 vs 1.29 ms; p = 0.025: 1.21 vs 1.28 ms); the x marching sweep falls behind the far-field kernel as soon as its
-    // radius-3 window stops deciding nearly every voxel (Bernoulli p = 0.03: 0.65 ms against 0.55; p = 0.04 and denser:
-    // marching wins), so its threshold is d^2 >= 9 on 1 / 24 of the voxels (p = 0.03: 6 %, p = 0.04: 2.4 %)
-    // (round 3, third-generation far-field kernel: KE2 0.57 -> 0.39 ms moves the y break-even from Bernoulli p ~ 0.018 up to
-    //  p ~ 0.035 -- tools/tier_sweep.py: p = 0.03 1.01 vs 0.97 ms, p = 0.02 1.16 vs 0.985, p = 0.04 0.87 vs 0.97 -- i.e. from
-    //  "d^2 >= 36 on an eighth" to "d^2 >= 16 on a fifth" of the voxels: (1 - p)^49 = 0.225 at p = 0.03, 0.135 at p = 0.04)
-    int far_thr[2] = {16, 9};
-    bool probe_window = true;        // tier probes as window statistics (option "probe_window"; 0 = level A of the far-field search on sampled tiles)
-    // dense tier
-    bool dense3_fixed = true;        // KD3's nz = 512 instance (option "dense3_fixed")
-    bool shell_on = true;            // KD6, the bit-parallel shell pass between KD3 and KF (option "dense_shell")
-    int shell_min_words = kShellMinWords;   // option "shell_min_words"
-    bool standby_far = true;         // stand-by pipeline behind a trusted dense tier = the far-field pair (bounded whatever the scene
-                                     // turns into), not fused K12 + K3/16 with unbounded scans (option "standby_far")
-    bool standby_fold = true;        // the stand-by x sweep's launch folds the maxima and publishes the status block itself (option "standby_fold")
-    int standby_grid = 1024;         // workgroups of the stand-by launches (LOOP form; option "standby_grid"): 4 per CU = all resident at once
-    // Serpentine tile order (option "ball_serpentine"): a whole build that writes the buffer the handle's last KD launch wrote, at
-    // the same size, walks KD's tiles in the opposite order -- it starts on the lines the last one finished with, which are
-    // the ones the Infinity Cache still holds; walked the same way round every time, an LRU-like cache has evicted each
-    // line just before it is reached.  Speed only: the field, the maxima and the flags do not depend on the order.
-    bool ball_serpentine = true;
-    // sweeps
-    bool fused_zy = true;            // use K12 (z sweep fused into the y sweep) when the shape allows
-    bool fused_always = false;       // ... whenever it does (option "fused_zy" = 2)
-    int fused_h = 2;                 // its register-window radius at nz = 512: 2 or 3 (option "fused_window")
-    bool plane16_on = true;          // use the int16 plane field + side table when the shape allows
-    bool z_wave_on = true;           // z sweep with wave-private rows where nz allows it (option "z_wave"; 0 = the workgroup form)
-    int x16_v = 4, x16_h = 3;        // K3/16 variant: voxels per lane, window radius
-    int tune_ty = 0, tune_tx = 0;    // rows marched per thread by the y / x sweep (sdfgpu_set_tuning; 0 = automatic)
-    bool i32_handoff = true;         // far-field pair: int32 plane field between the y and x sweeps (option "i32_handoff")
-    bool dc_fixed = true;            // far-field kernel: the 512-voxel-line instances (option "dc_fixed")
-    bool plane_skip = true;          // builds that go straight to the far-field pair: the z sweep marks the x-planes that hold a filled voxel,
-                                     // the y sweep skips the tiles of the others, the x sweep their row loads (option "plane_skip")
-    // ... and y tiles whose 16 lines are all flat-positive (a floor under open space) skip the search (option "flat_tiles")
-    int flat_tiles = 1;              // (2: every such tile tries, whatever the habit says -- tests)
-    // host side / debugging
-    int host_pack = 1;       // host-buffer builds classify on the host and upload bits (option "host_pack"; 0 = upload the
-                             // caller's mask / cells and classify on the device, as rounds 1 - 4 did)
-    int defer_fold = 0;           // stage entry points leave their maxima in the slot array until sdfgpu_fold_extrema_device
-    bool rs_plain_atomics = false;        // option "resample_plain_atomics": one atomic per lane (tools/resample_bench.py)
-    bool rs_timing = false;               // option "resample_timing": events around the two kernels (sdfgpu_debug_resample_times)
-};
-
-// What the sdfgpu_last_* and sdfgpu_debug_* calls report about the most recent build or stage call.
-struct LastBuild {
-    hipStream_t last_stream = nullptr;
-    double last_resolution = 1.0;
-    int64_t last_n = 0;
-    bool have_result = false;
-    int64_t last_dims[3] = {0, 0, 0};
-    bool last_fused = false;
-    bool last_plane16 = false;
-    bool last_dense = false;
-    bool last_standby = false;       // the last build carried the far-field stand-by pair behind a trusted dense tier
-    bool last_dense3 = false, last_staged = false;   // ... ran KD3 + KF in KD's place / carried them behind KD, guarded on its verdict
-    bool last_predicted = false;     // the last build took the far-field pair on the strength of the handle's recent builds: no probes, no marching launches
-    bool last_lines_tiered = false;  // the last sdfgpu_sweep_x_lines_device call chose its tier on the device (probe / forced tier + far-field kernel behind the marching sweep)
-    int last_dc_x = 0;               // 1 + the far-field kernel instance (launch_envelope_kernel's `which`) of the last x sweep launched through it; 0: none since the last build / lines call began
-    bool last_plane_skip = false;    // the last build skipped the x-planes without a filled voxel (sdfgpu_debug_copy_yzsweep fills them in)
-};
-
-// Where a build's occupancy comes from: a byte mask, or cell records (the float occupancy at `off` of every `stride` bytes; 0.5 is
-// filled iff `unknown`), or one bit per voxel in linear order (sdfgpu_build_bits*: the tuned dense kernels read it in place, the z
-// sweep and the generic dense tier through their bit loaders -- no byte mask exists).  Exactly one of the three pointers is set;
-// device memory for the launchers and build_device_impl, host memory for upload_packed and build_host_impl.
-struct Occupancy {
-    const uint8_t* mask = nullptr;
-    const void* cells = nullptr;
-    size_t stride = 0, off = 0;
-    int unknown = 0;
-    const uint32_t* bits = nullptr;
-    static Occupancy of_mask(const uint8_t* m) { Occupancy o; o.mask = m; return o; }
-    static Occupancy of_cells(const void* c, size_t stride, size_t off, int unknown) {
-        Occupancy o; o.cells = c; o.stride = stride; o.off = off; o.unknown = unknown; return o;
-    }
-    static Occupancy of_bits(const uint32_t* b) { Occupancy o; o.bits = b; return o; }
-    bool null() const { return !mask && !cells && !bits; }
-    CellLoader cell_loader() const { return CellLoader{reinterpret_cast<const char*>(cells), (int64_t)stride, (int64_t)off, unknown}; }
-};
-
-// What a launcher is told about the device words around its launch, spelt out at the call site.
-// guard: the launch does its work iff *guard != 0; kUnguarded: always.
-constexpr const uint32_t* kUnguarded = nullptr;
-// far_flag of a marching sweep: its outward scans are bounded (kScanExpectNear) and one that gives up raises the word, which guards
-// the far-field kernel behind the sweep; kUnbounded: unbounded scans, nothing raised.
-constexpr uint32_t* kUnbounded = nullptr;
-constexpr hipStream_t kNullStream = nullptr;  // the host-buffer entry points work on the null stream of the context's device
-constexpr int32_t* kNoSideTable = nullptr;    // d_side of a y sweep: int32 plane values, not the int16 plane field + side table
-
-}  // namespace
-
-struct sdfgpu_context : ContextBuffers {
-    int device = 0;
-    std::string error;
-    BuildOptions opt;
-    LastBuild last;
-    size_t cx_stats_off = 0;    // where the last extrema call left its CxStats in cx_scratch (0 = no call yet)
-    int cx_rounds = 0;          // doubling rounds of that call
-    char* batch_pin = nullptr;  // pinned ring through which per-grid parameters reach the device without a host wait
-    size_t batch_pin_cap = 0, batch_pin_off = 0;
-    std::vector<double> batch_resolutions;   // of the last batch build (sdfgpu_get_extrema_batch)
-    int batch_fast = 0, batch_launches = 0;  // sdfgpu_last_batch_info
-    bool batch_valid = false;
-    size_t tag_cached_bytes = 0;            // stage_in holds the tagged cell records of the last sdfgpu_build_tagged_cells call
-    void* pin[2] = {nullptr, nullptr};      // pinned host staging of copy_to_host (two chunks in flight)
-    // Red zones (round 6, VERDICT r5 "next round" 2): with SDFGPU_REDZONE=1 in the environment of sdfgpu_create (or option
-    // "redzone") every device allocation of the library -- the scratch fields, the status block, the slots, the staging buffers,
-    // what sdfgpu_device_malloc hands out -- carries kRzPad canary bytes in front and behind, and every ABI call that may have
-    // launched something ends with one check kernel over all of them (then synchronises): a store outside a buffer fails the
-    // call that made it, with the buffer's name (SDFGPU_ERR_REDZONE).  The only net rounds 1 - 5 had was the VALUE of the
-    // output, and a store past the end of a field lived in the product for three rounds.
-    bool redzone = false;
-    int rz_depth = 0;                       // entry points call each other: the outermost one checks
-    struct Zone { std::string name; char* base; char* user; size_t bytes, total; };
-    std::vector<Zone> zones;
-    bool rz_table_dirty = true;
-    void* rz_table = nullptr;               // device copy of {base, user bytes, total} per zone + results
-    size_t rz_table_cap = 0;
-    HostTeam* team = nullptr;               // the host threads that fill / drain the staging chunks: created with the first staged
-                                            // transfer, parked between calls, joined by sdfgpu_destroy (sdfgpu_hostteam.hpp)
-    hipEvent_t pin_ev[2] = {nullptr, nullptr};
-    uint32_t* d_small = nullptr;   // the status block, indexed by StatusWord (sdfgpu_kernels.hpp)
-    // "this handle's scene is a far-field scene on both axes": learnt from the status blocks that come back (never a wait).  Such a
-    // build skips the two probes and the three guarded marching launches (35 us of a 0.8 - 1.4 ms build) and enqueues KE2 -> KE3
-    // directly (int32 hand-off); every 16th build probes again.  The far-field pair is exact on any scene: a wrong prediction costs
-    // time, never a voxel.  Option "far_predict" (0 off, 1 on, 2 every build: tests and the fuzz).
-    FarHabit far;                    // (sdfgpu_policy.hpp: plain C++, driven on the CPU by tests/policy_harness.cpp)
-    uint32_t* h_far = nullptr;       // second report slot (pinned): builds that do not carry the dense tier report their far flags here
-    uint32_t* h_far_dev = nullptr;
-    hipEvent_t far_ev = nullptr;
-    bool far_pending = false;
-    DensePolicy pol;              // what the handle has learned about its scenes' dense tier (sdfgpu_policy.hpp)
-    bool flat_score_reset = false;   // "policy_reset": the next build clears the device-side habit of the two-valued tiles (kSwFlatScore)
-    const float* serp_out = nullptr; // "ball_serpentine": output buffer and voxel count of the last whole-build KD launch, and its direction
-    int64_t serp_n = 0;
-    int serp_flip = 0;
-    bool dc_attr_set[16] = {};   // MaxDynamicSharedMemorySize raised, per far-field kernel instantiation
-    int k1_resident = 0;             // workgroups of k_sweep_z_vec16 the device holds at once (persistent grid size)
-    uint32_t* d_slots = nullptr;     // [kSlots][kSlotWords] extrema / flag slots of the dense kernel (kept zero between launches)
-    uint32_t* d_result = nullptr;    // [8] the status block of the last finished build (d_small is cleared by its fold)
-    bool small_clean = false;        // d_small is all zero (left so by the previous build's fold kernel)
-    uint32_t* h_flags_dev = nullptr; // device-side address of h_flags
-    uint32_t* h_flags = nullptr;     // pinned host copy of the status block, written by the fold kernel of every build
-    hipEvent_t flags_ev = nullptr;
-    bool flags_pending = false;
-    StreamOrder build_order;              // recorded behind every build (and every stage call that uses the status block):
-                                          // work on another stream waits for it first
-    StreamOrder cx_order;                 // recorded behind every local-extrema computation, whose last three kernels are still
-                                          // pending on its stream when the call returns: one on another stream waits for it first
-    StreamOrder rs_order;                 // recorded behind every resample, which may return with its kernels pending on its
-                                          // stream: one on another stream waits for it before it clears the winner words
-    hipEvent_t rs_time_ev[3] = {nullptr, nullptr, nullptr};   // "resample_timing"
-    bool rs_timed = false;
-    int profiling = 0;            // 0 off, 1 an event behind every stage, 2 events around the dense ball kernel only,
-                                  // 3 like 2 but only on every 4th build
-    uint32_t profiled_builds = 0; // builds seen while profiling (level 3 samples every 4th)
-    std::vector<hipEvent_t> event_pool;   // recycled profiling events
-    std::vector<hipEvent_t> events;   // 8 per profiled build: start, after pack, ball, K1, K2/K12, KE2, K3, KE3
-};
-
-namespace {
-
-int fail(sdfgpu_handle h, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (h) h->error = buf; else g_create_error = buf;
-    return code;
+// the cell records of `occ` as the kernels read them
+CellLoader cell_loader(const Occupancy& occ) {
+    return CellLoader{reinterpret_cast<const char*>(occ.cells), (int64_t)occ.stride, (int64_t)occ.off, occ.unknown};
 }
-
-#define HIP_TRY(h, expr)                                                                  \
-    do {                                                                                  \
-        hipError_t e_ = (expr);                                                           \
-        if (e_ != hipSuccess)                                                             \
-            return fail(h, SDFGPU_ERR_HIP, "HIP error %d (%s) at %s", (int)e_,            \
-                        hipGetErrorString(e_), #expr);                                    \
-    } while (0)
-
-constexpr size_t kRzPad = 4096;
-constexpr int kRzByte = 0xC5;
-
-// every device allocation of the library goes through here (name = what a red-zone report calls it)
-int rz_malloc(sdfgpu_handle h, const char* name, size_t bytes, void** out) {
-    *out = nullptr;
-    if (!h->redzone) {
-        HIP_TRY(h, hipMalloc(out, bytes));
-        return SDFGPU_OK;
-    }
-    const size_t total = kRzPad + ((bytes + 255) & ~(size_t)255) + kRzPad;
-    char* base = nullptr;
-    HIP_TRY(h, hipMalloc((void**)&base, total));
-    HIP_TRY(h, hipMemset(base, kRzByte, kRzPad));
-    HIP_TRY(h, hipMemset(base + kRzPad + bytes, kRzByte, total - kRzPad - bytes));      // (from the first byte behind the buffer)
-    h->zones.push_back({name, base, base + kRzPad, bytes, total});
-    h->rz_table_dirty = true;
-    *out = base + kRzPad;
-    return SDFGPU_OK;
-}
-int rz_free(sdfgpu_handle h, void* ptr) {
-    if (!ptr) return SDFGPU_OK;
-    for (size_t i = 0; i < h->zones.size(); ++i)
-        if (h->zones[i].user == ptr) {
-            char* base = h->zones[i].base;
-            h->zones.erase(h->zones.begin() + (long)i);
-            h->rz_table_dirty = true;
-            HIP_TRY(h, hipFree(base));
-            return SDFGPU_OK;
-        }
-    HIP_TRY(h, hipFree(ptr));               // (allocated before the switch went on)
-    return SDFGPU_OK;
-}
-
-int ensure(sdfgpu_handle h, DeviceBuffer& b, size_t bytes, const char* name = "scratch") {
-    if (b.bytes >= bytes && b.ptr) return SDFGPU_OK;
-    if (b.ptr) { if (int rc = rz_free(h, b.ptr)) return rc; b.ptr = nullptr; b.bytes = 0; }
-    // (red zones: the buffer is exactly as large as asked for, so that the first byte behind it is canary)
-    const size_t want = h->redzone ? std::max<size_t>(bytes, 4) : std::max<size_t>(bytes, 256);
-    if (int rc = rz_malloc(h, name, want, &b.ptr)) return rc;
-    b.bytes = want;
-    return SDFGPU_OK;
-}
-
-__global__ __launch_bounds__(256) void k_redzone_check(const uint64_t* __restrict__ table, uint32_t* __restrict__ result) {
-    // table[3 z] = base address, [3 z + 1] = user bytes, [3 z + 2] = total bytes; result[2 z] = overwritten bytes, [2 z + 1] = first
-    // overwritten byte as an offset from the buffer's start + kRzPad (so that "before the buffer" stays non-negative)
-    const int z = blockIdx.x;
-    const unsigned char* base = reinterpret_cast<const unsigned char*>(table[3 * z]);
-    const size_t bytes = table[3 * z + 1], total = table[3 * z + 2];
-    __shared__ uint32_t cnt, first;
-    if (threadIdx.x == 0) { cnt = 0u; first = 0xFFFFFFFFu; }
-    __syncthreads();
-    uint32_t c = 0, f = 0xFFFFFFFFu;
-    for (size_t i = threadIdx.x; i < kRzPad; i += 256) if (base[i] != (unsigned char)kRzByte) { ++c; f = min(f, (uint32_t)i); }
-    for (size_t i = kRzPad + bytes + threadIdx.x; i < total; i += 256)
-        if (base[i] != (unsigned char)kRzByte) { ++c; f = min(f, (uint32_t)min(i - bytes, (size_t)0xFFFFFFFEu)); }
-    if (c) { atomicAdd(&cnt, c); atomicMin(&first, f); }
-    __syncthreads();
-    if (threadIdx.x == 0) { result[2 * z] = cnt; result[2 * z + 1] = first; }
-}
-
-// One kernel over every zone, then a synchronisation (debug mode: calls become synchronous).  Overwritten zones fail the call
-// with the buffer's name and are repaired, so that the next call reports only what IT did.
-int redzone_check(sdfgpu_handle h, hipStream_t s) {
-    const size_t nz = h->zones.size();
-    if (!h->redzone || nz == 0) return SDFGPU_OK;
-    HIP_TRY(h, hipSetDevice(h->device));
-    const size_t need = nz * 3 * 8 + nz * 2 * 4;
-    if (h->rz_table_cap < need) {
-        if (h->rz_table) HIP_TRY(h, hipFree(h->rz_table));
-        h->rz_table = nullptr;
-        h->rz_table_cap = 0;
-        HIP_TRY(h, hipMalloc(&h->rz_table, need * 2));
-        h->rz_table_cap = need * 2;
-        h->rz_table_dirty = true;
-    }
-    uint32_t* d_res = reinterpret_cast<uint32_t*>(static_cast<char*>(h->rz_table) + nz * 3 * 8);
-    if (h->rz_table_dirty) {
-        std::vector<uint64_t> t(nz * 3);
-        for (size_t i = 0; i < nz; ++i) { t[3 * i] = reinterpret_cast<uint64_t>(h->zones[i].base); t[3 * i + 1] = h->zones[i].bytes; t[3 * i + 2] = h->zones[i].total; }
-        HIP_TRY(h, hipStreamSynchronize(s));
-        HIP_TRY(h, hipMemcpy(h->rz_table, t.data(), nz * 3 * 8, hipMemcpyHostToDevice));
-        h->rz_table_dirty = false;
-    }
-    hipLaunchKernelGGL(k_redzone_check, dim3((unsigned)nz), dim3(256), 0, s, (const uint64_t*)h->rz_table, d_res);
-    HIP_TRY(h, hipGetLastError());
-    std::vector<uint32_t> res(nz * 2);
-    HIP_TRY(h, hipMemcpyAsync(res.data(), d_res, nz * 2 * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    std::string msg;
-    for (size_t i = 0; i < nz; ++i) {
-        if (res[2 * i] == 0) continue;
-        const sdfgpu_context::Zone& z = h->zones[i];
-        char buf[256];
-        const long long off = (long long)res[2 * i + 1] - (long long)kRzPad;
-        snprintf(buf, sizeof buf, "%s'%s' (%zu bytes): %u canary bytes overwritten, the first %lld bytes %s", msg.empty() ? "" : "; ", z.name.c_str(), z.bytes,
-                 res[2 * i], off < 0 ? -off : off - (long long)z.bytes, off < 0 ? "BEFORE its start" : "BEHIND its end");
-        msg += buf;
-        (void)hipMemset(z.base, kRzByte, kRzPad);
-        (void)hipMemset(z.base + kRzPad + z.bytes, kRzByte, z.total - kRzPad - z.bytes);
-    }
-    if (!msg.empty()) return fail(h, SDFGPU_ERR_REDZONE, "red zone: a kernel of this call stored outside %s", msg.c_str());
-    return SDFGPU_OK;
-}
-
-template <class F>
-int rz_wrap(sdfgpu_handle h, void* stream, F&& body) {
-    if (!h || !h->redzone) return body();
-    ++h->rz_depth;
-    int rc = body();
-    if (--h->rz_depth == 0) {
-        const int rz = redzone_check(h, (hipStream_t)stream);
-        if (rz != SDFGPU_OK) rc = rz;
-    }
-    return rc;
-}
-
-// The EDT is symmetric under axis renaming, and a grid with singleton axes has
-// the same memory layout when those axes are moved to the front (index =
-// x*ny*nz + y*nz + z).  Canonicalising keeps the contiguous axis long, so 2-D
-// grids (the reference's test_bindings.py case is 20x40x1) sweep coalesced.
-void canonical_dims(int64_t& nx, int64_t& ny, int64_t& nz) {
-    if (nz == 1) { nz = ny; ny = nx; nx = 1; }
-    if (nz == 1) { nz = ny; ny = nx; nx = 1; }
-    if (ny == 1) { ny = nx; nx = 1; }
-}
-
-int check_dims(sdfgpu_handle h, int64_t nx, int64_t ny, int64_t nz) {
-    if (nx <= 0 || ny <= 0 || nz <= 0)
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "grid dimensions must be positive (got %lld x %lld x %lld)",
-                    (long long)nx, (long long)ny, (long long)nz);
-    if (nx > kMaxDim || ny > kMaxDim || nz > kMaxDim || nx * nx + ny * ny + nz * nz >= (int64_t)kInf32)
-        return fail(h, SDFGPU_ERR_UNSUPPORTED_SIZE,
-                    "grid %lld x %lld x %lld exceeds the supported extent (dims <= 16384, nx^2+ny^2+nz^2 < 2^30)",
-                    (long long)nx, (long long)ny, (long long)nz);
-    return SDFGPU_OK;
-}
-
-// include/sdfgpu.h "Resolutions": positive and finite (subnormal and huge finite values included), refused before anything is enqueued
-int check_resolution(sdfgpu_handle h, double resolution) {
-    if (!(resolution > 0.0) || !std::isfinite(resolution))
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "resolution must be positive and finite (got %g)", resolution);
-    return SDFGPU_OK;
-}
-
-// The record layouts of the cell entry points: every field 4-byte aligned and inside the record.
-int check_cell_layout(sdfgpu_handle h, size_t stride, size_t occ_off) {
-    if (stride < 4 || (stride % 4) || (occ_off % 4) || occ_off + 4 > stride)
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cell_stride/occupancy_offset must be 4-byte aligned and in range");
-    return SDFGPU_OK;
-}
-int check_tagged_layout(sdfgpu_handle h, size_t stride, size_t occ_off, size_t obj_off) {
-    if (stride < 8 || (stride % 4) || (occ_off % 4) || (obj_off % 4) || occ_off + 4 > stride || obj_off + 4 > stride)
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cell layout must be 4-byte aligned and in range");
-    return SDFGPU_OK;
-}
-int check_component_layout(sdfgpu_handle h, size_t stride, size_t occ_off, size_t comp_off) {
-    if (stride < 8 || (stride % 4) || (occ_off % 4) || (comp_off % 4) || occ_off + 4 > stride || comp_off + 4 > stride || occ_off == comp_off)
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cell_stride / occupancy_offset / component_offset must be 4-byte aligned, in range and distinct");
-    return SDFGPU_OK;
-}
+// (kShellMinWords is the default of a host option and lives with BuildOptions; its unit is the words of one KD6 group)
+static_assert(kShellMinWords <= kShellGroup * 256, "shell_min_words counts active words of a group of kShellGroup x 256");
 
 int rows_per_block(int nz) {
     const int W = (nz + 63) / 64;
@@ -528,7 +96,7 @@ int launch_sweep_z(sdfgpu_handle h, const Occupancy& occ, int64_t nx, int64_t ny
         if (z_wave16_shape(h, nz)) launch_z_wave16<true>(reinterpret_cast<const uint8_t*>(occ.bits), d_out, nrows, nz, guard, d_row_any, s);
         else hipLaunchKernelGGL(k_sweep_z_generic<BitsLoader>, grid, block, lds, s, BitsLoader{occ.bits}, d_out, nrows, (int)nz, rpb, guard);
     } else if (occ.cells) {
-        hipLaunchKernelGGL(k_sweep_z_generic<CellLoader>, grid, block, lds, s, occ.cell_loader(), d_out, nrows, (int)nz, rpb, guard);
+        hipLaunchKernelGGL(k_sweep_z_generic<CellLoader>, grid, block, lds, s, cell_loader(occ), d_out, nrows, (int)nz, rpb, guard);
     } else if (mask16 && z_wave16_shape(h, nz)) {
         launch_z_wave16<false>(occ.mask, d_out, nrows, nz, guard, d_row_any, s);
     } else if (mask16 && (nz % 16) == 0) {
@@ -935,7 +503,7 @@ bool dense_eligible(const sdfgpu_context* h, int64_t nz) {       // (with or wit
 int launch_pack_bits(sdfgpu_handle h, const Occupancy& occ, int64_t n, uint32_t* d_bits, hipStream_t s) {
     const dim3 grid((unsigned)((n + kBlock - 1) / kBlock)), block(kBlock);
     if (occ.cells) {
-        hipLaunchKernelGGL(k_pack_bits_generic<CellLoader>, grid, block, 0, s, occ.cell_loader(), d_bits, n);
+        hipLaunchKernelGGL(k_pack_bits_generic<CellLoader>, grid, block, 0, s, cell_loader(occ), d_bits, n);
     } else if ((reinterpret_cast<uintptr_t>(occ.mask) % 16) == 0) {
         const int64_t n16 = n / 16;
         const int64_t pb = (int64_t)kBlock * 4;                     // 4 chunks of 16 voxels per lane
@@ -1122,7 +690,7 @@ int launch_dense_generic(sdfgpu_handle h, const Occupancy& occ, int64_t nx, int6
     if (occ.bits)                                               // (linear bits -> rows padded to whole words)
         hipLaunchKernelGGL(k_pack_bits_rows<BitsLoader>, grid, block, 0, s, BitsLoader{occ.bits}, rows, nrows, (int)nz, (int)nzw);
     else if (occ.cells)
-        hipLaunchKernelGGL(k_pack_bits_rows<CellLoader>, grid, block, 0, s, occ.cell_loader(), rows, nrows, (int)nz, (int)nzw);
+        hipLaunchKernelGGL(k_pack_bits_rows<CellLoader>, grid, block, 0, s, cell_loader(occ), rows, nrows, (int)nz, (int)nzw);
     else
         hipLaunchKernelGGL(k_pack_bits_rows<MaskLoader>, grid, block, 0, s, MaskLoader{occ.mask}, rows, nrows, (int)nz, (int)nzw);
     HIP_TRY(h, hipGetLastError());
@@ -1138,8 +706,11 @@ int launch_dense_generic(sdfgpu_handle h, const Occupancy& occ, int64_t nx, int6
     return SDFGPU_OK;
 }
 
-int build_device_impl(sdfgpu_handle h, const Occupancy& occ, int64_t nx, int64_t ny, int64_t nz, double resolution, int vb,
-                      float* d_out, hipStream_t s) {
+}  // namespace
+
+// (declared in sdfgpu_context.hpp: the families' host code builds SDFs through it)
+int sdfgpu::build_device_impl(sdfgpu_handle h, const Occupancy& occ, int64_t nx, int64_t ny, int64_t nz, double resolution, int vb,
+                              float* d_out, hipStream_t s) {
     if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
     if (occ.null() || !d_out) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null device pointer");
     if (occ.bits && (reinterpret_cast<uintptr_t>(occ.bits) % 4) != 0) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "the bit field must be 4-byte aligned");
@@ -1469,247 +1040,9 @@ int build_device_impl(sdfgpu_handle h, const Occupancy& occ, int64_t nx, int64_t
     return SDFGPU_OK;
 }
 
-// Device -> pageable host memory at PCIe rate, for destinations nobody has touched yet (the std::vector / numpy array
-// the reference API returns is fresh: 512^3 floats are 131 072 first-touch page faults, ~40 ms on one thread, and a plain
-// hipMemcpy takes them one by one on the runtime's copy thread).  The DMA lands in two pinned staging chunks of the
-// context; a small team of host threads copies each chunk out while the next one is in flight, so the faults are spread
-// over the team and overlap the transfer.  Enqueued on `st` (ordered after the work already there).  (Round 1 pre-touched the destination from threads running beside the upload:
-// the faults and the runtime's pinning of the source pages fought over the address space, and the 128 MiB upload took
-// 29 ms instead of 2.5.)  Returns when the data is in dst.
-constexpr size_t kPinChunk = (size_t)32 << 20;
-constexpr size_t kPinMin = (size_t)4 << 20;      // below this a plain (runtime-staged) copy is as fast as the team
-
-// `drain(src, offset_in_download, len)` consumes bytes [offset, offset + len) of the download from pinned (or, for transfers
-// below kPinMin, temporary) host memory: a memcpy for copy_to_host, the scatter of labels into cell records for
-// sdfgpu_components_cells.
-template <class Drain>
-int staged_download_hip(sdfgpu_handle h, const void* d_src, size_t bytes, hipStream_t st, Drain drain) {
-    if (bytes == 0) return SDFGPU_OK;
-    for (int i = 0; i < 2 && bytes >= kPinMin; ++i) {
-        if (!h->pin[i] && hipHostMalloc(&h->pin[i], kPinChunk, hipHostMallocDefault) != hipSuccess) h->pin[i] = nullptr;
-        if (h->pin[i] && !h->pin_ev[i] && hipEventCreateWithFlags(&h->pin_ev[i], hipEventDisableTiming) != hipSuccess) h->pin_ev[i] = nullptr;
-    }
-    if (bytes < kPinMin || !h->pin[0] || !h->pin[1] || !h->pin_ev[0] || !h->pin_ev[1]) {
-        (void)hipGetLastError();
-        std::vector<char> tmp(std::min(bytes, kPinChunk));
-        for (size_t o = 0; o < bytes; o += tmp.size()) {
-            const size_t len = std::min(tmp.size(), bytes - o);
-            HIP_TRY(h, hipMemcpyAsync(tmp.data(), static_cast<const char*>(d_src) + o, len, hipMemcpyDeviceToHost, st));
-            HIP_TRY(h, hipStreamSynchronize(st));
-            drain(tmp.data(), o, len);
-        }
-        return SDFGPU_OK;
-    }
-    if (!h->team) h->team = new (std::nothrow) HostTeam();
-    if (!h->team) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "out of host memory");
-    // (the scheduler is host-only code, tests/sched_harness.cpp runs it under -fsanitize=thread: sdfgpu_hostteam.hpp)
-    hipError_t herr = hipSuccess;
-    const int rc = staged_drain(
-        *h->team, bytes, kPinChunk, host_team_size(16),
-        [&](int64_t i, int buf, size_t len) -> int {
-            herr = hipMemcpyAsync(h->pin[buf], static_cast<const char*>(d_src) + (size_t)i * kPinChunk, len, hipMemcpyDeviceToHost, st);
-            if (herr == hipSuccess) herr = hipEventRecord(h->pin_ev[buf], st);
-            return herr == hipSuccess ? 0 : 1;
-        },
-        [&](int buf) -> int { herr = hipEventSynchronize(h->pin_ev[buf]); return herr == hipSuccess ? 0 : 1; },
-        [&](int buf, size_t off, size_t goff, size_t len) { drain(static_cast<const char*>(h->pin[buf]) + off, goff, len); });
-    if (rc != 0) {
-        (void)hipDeviceSynchronize();
-        return fail(h, SDFGPU_ERR_HIP, "HIP error %d (%s) in the device-to-host copy", (int)herr, hipGetErrorString(herr));
-    }
-    return SDFGPU_OK;
-}
-
-int copy_to_host(sdfgpu_handle h, void* dst, const void* d_src, size_t bytes, hipStream_t st = nullptr) {
-    if (bytes == 0) return SDFGPU_OK;
-    if (bytes < kPinMin) {
-        HIP_TRY(h, hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(h, hipStreamSynchronize(st));
-        return SDFGPU_OK;
-    }
-    {   // huge pages on the 2 MiB-aligned interior, where the kernel grants them: one fault then maps 512 small pages' worth
-        constexpr uintptr_t kHuge = (uintptr_t)2 << 20;
-        const uintptr_t lo = (reinterpret_cast<uintptr_t>(dst) + kHuge - 1) & ~(kHuge - 1);
-        const uintptr_t hi = (reinterpret_cast<uintptr_t>(dst) + bytes) & ~(kHuge - 1);
-        if (hi > lo) (void)madvise(reinterpret_cast<void*>(lo), hi - lo, MADV_HUGEPAGE);
-    }
-    return staged_download_hip(h, d_src, bytes, st, [dst](const char* src, size_t goff, size_t len) { memcpy(static_cast<char*>(dst) + goff, src, len); });
-}
-
-// Pageable host -> device, the mirror image of copy_to_host: a synchronous hipMemcpy from pageable memory goes through
-// the runtime's staging copy on one host thread (measured: 128 MiB in 24 - 30 ms, i.e. 5 GB/s, where the link does 52);
-// here a team of threads fills the two pinned chunks and the DMA of one chunk overlaps the filling of the next.
-// Enqueued on `st`; returns when the last chunk's DMA has completed.
-// `fill(dst, out_offset, len)` produces bytes [out_offset, out_offset + len) of the upload into dst (slices are multiples
-// of 4096 bytes except the last): a plain memcpy for copy_from_host, the cells / mask -> bits classification for the
-// host-buffer builds (round 5), which is what makes the team worth more than a copy -- it reads 8 or 64 bytes per byte sent.
-template <class Fill>
-int staged_upload_hip(sdfgpu_handle h, void* d_dst, size_t bytes, hipStream_t st, int team_cap, Fill fill) {
-    if (bytes == 0) return SDFGPU_OK;
-    for (int i = 0; i < 2; ++i) {
-        if (!h->pin[i] && hipHostMalloc(&h->pin[i], kPinChunk, hipHostMallocDefault) != hipSuccess) h->pin[i] = nullptr;
-        if (h->pin[i] && !h->pin_ev[i] && hipEventCreateWithFlags(&h->pin_ev[i], hipEventDisableTiming) != hipSuccess) h->pin_ev[i] = nullptr;
-    }
-    if (!h->pin[0] || !h->pin[1] || !h->pin_ev[0] || !h->pin_ev[1]) {
-        // no pinned staging (a locked-memory limit): produce the bytes into a pageable temporary, one runtime-staged copy each
-        // (slower, never wrong -- ADVICE r5: rounds 1 - 4 had this fallback, round 5 had dropped it)
-        (void)hipGetLastError();
-        std::vector<char> tmp(std::min(bytes, kPinChunk));
-        for (size_t o = 0; o < bytes; o += tmp.size()) {
-            const size_t len = std::min(tmp.size(), bytes - o);
-            fill(tmp.data(), o, len);
-            HIP_TRY(h, hipMemcpyAsync(static_cast<char*>(d_dst) + o, tmp.data(), len, hipMemcpyHostToDevice, st));
-            HIP_TRY(h, hipStreamSynchronize(st));           // (tmp is refilled by the next round)
-        }
-        return SDFGPU_OK;
-    }
-    if (!h->team) h->team = new (std::nothrow) HostTeam();
-    if (!h->team) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "out of host memory");
-    hipError_t herr = hipSuccess;
-    const int rc = sdfgpu::staged_upload(
-        *h->team, bytes, kPinChunk, host_team_size(team_cap),
-        [&](int buf, size_t off, size_t goff, size_t len) { fill(static_cast<char*>(h->pin[buf]) + off, goff, len); },
-        [&](int64_t i, int buf, size_t len) -> int {
-            herr = hipMemcpyAsync(static_cast<char*>(d_dst) + (size_t)i * kPinChunk, h->pin[buf], len, hipMemcpyHostToDevice, st);
-            if (herr == hipSuccess) herr = hipEventRecord(h->pin_ev[buf], st);
-            return herr == hipSuccess ? 0 : 1;
-        },
-        [&](int buf) -> int { herr = hipEventSynchronize(h->pin_ev[buf]); return herr == hipSuccess ? 0 : 1; });
-    if (rc != 0) {
-        (void)hipDeviceSynchronize();
-        return fail(h, SDFGPU_ERR_HIP, "HIP error %d (%s) in the host-to-device copy", (int)herr, hipGetErrorString(herr));
-    }
-    return SDFGPU_OK;
-}
-
-int copy_from_host(sdfgpu_handle h, void* d_dst, const void* src, size_t bytes, hipStream_t st = nullptr) {
-    if (bytes == 0) return SDFGPU_OK;
-    if (bytes < kPinMin) {
-        HIP_TRY(h, hipMemcpyAsync(d_dst, src, bytes, hipMemcpyHostToDevice, st));
-        HIP_TRY(h, hipStreamSynchronize(st));
-        return SDFGPU_OK;
-    }
-    return staged_upload_hip(h, d_dst, bytes, st, 16, [src](char* dst, size_t o, size_t len) { memcpy(dst, static_cast<const char*>(src) + o, len); });
-}
-
-// ---- host-side classification: cells / mask -> one bit per voxel (round 5) ----------------------------------
-// Bit (v & 7) of byte (v >> 3) = voxel v is filled, with the predicates of the device classifiers: mask byte != 0;
-// occupancy > 0.5f || (unknown_is_filled && occupancy == 0.5f) (collision_map.hpp:689-704 -- the reference compares the float
-// with the double 0.5, which is the float 0.5f exactly; NaN is "free" in both).  out[0 .. len) covers voxels
-// [8 ob, 8 (ob + len)); bits of voxels >= n are 0.
-void pack_mask_bits(const uint8_t* m, int64_t n, size_t ob, size_t len, uint8_t* out) {
-    const int64_t v0 = (int64_t)ob * 8, v1 = std::min<int64_t>(n, v0 + (int64_t)len * 8);
-    int64_t v = v0;
-    size_t o = 0;
-#if defined(__SSE2__)
-    const __m128i zero = _mm_setzero_si128();
-    for (; v + 16 <= v1; v += 16, o += 2) {
-        const __m128i x = _mm_loadu_si128(reinterpret_cast<const __m128i*>(m + v));
-        const uint32_t nz = ~(uint32_t)_mm_movemask_epi8(_mm_cmpeq_epi8(x, zero)) & 0xffffu;
-        out[o] = (uint8_t)nz; out[o + 1] = (uint8_t)(nz >> 8);
-    }
-#else       // (hosts without SSE2: eight bytes -> eight bits by the multiply trick)
-    for (; v + 8 <= v1; v += 8, ++o) {
-        uint64_t x;
-        memcpy(&x, m + v, 8);
-        x = (x | ((x & 0x7f7f7f7f7f7f7f7full) + 0x7f7f7f7f7f7f7f7full)) & 0x8080808080808080ull;
-        out[o] = (uint8_t)(((x >> 7) * 0x0102040810204080ull) >> 56);
-    }
-#endif
-    for (; o < len; ++o) {
-        uint32_t b = 0;
-        for (int k = 0; k < 8; ++k, ++v) if (v < v1 && m[v]) b |= 1u << k;
-        out[o] = (uint8_t)b;
-    }
-}
-void pack_cells_bits(const char* cells, size_t stride, size_t off, int unknown, int64_t n, size_t ob, size_t len, uint8_t* out) {
-    const int64_t v0 = (int64_t)ob * 8, v1 = std::min<int64_t>(n, v0 + (int64_t)len * 8);
-    int64_t v = v0;
-    size_t o = 0;
-#if defined(__SSE2__)
-    if (stride == 8 && (off == 0 || off == 4)) {                // COLLISION_CELL {float occupancy; uint32 component}: 4 records per pair of loads
-        const __m128 half = _mm_set1_ps(0.5f);
-        const __m128 unk = _mm_castsi128_ps(_mm_set1_epi32(unknown ? -1 : 0));
-        const char* p = cells + (size_t)v0 * 8;
-        for (; v + 8 <= v1; v += 8, ++o, p += 64) {
-            uint32_t b = 0;
-            for (int g = 0; g < 2; ++g) {
-                const __m128 a0 = _mm_loadu_ps(reinterpret_cast<const float*>(p + 32 * g));
-                const __m128 a1 = _mm_loadu_ps(reinterpret_cast<const float*>(p + 32 * g + 16));
-                const __m128 occ = off == 0 ? _mm_shuffle_ps(a0, a1, _MM_SHUFFLE(2, 0, 2, 0)) : _mm_shuffle_ps(a0, a1, _MM_SHUFFLE(3, 1, 3, 1));
-                const __m128 f = _mm_or_ps(_mm_cmpgt_ps(occ, half), _mm_and_ps(_mm_cmpeq_ps(occ, half), unk));
-                b |= (uint32_t)_mm_movemask_ps(f) << (4 * g);
-            }
-            out[o] = (uint8_t)b;
-        }
-    }
-#endif
-    for (; o < len; ++o) {
-        uint32_t b = 0;
-        for (int k = 0; k < 8; ++k, ++v) {
-            if (v >= v1) continue;
-            float occ;
-            memcpy(&occ, cells + (size_t)v * stride + off, 4);
-            if (occ > 0.5f || (unknown && occ == 0.5f)) b |= 1u << k;
-        }
-        out[o] = (uint8_t)b;
-    }
-}
-
-// Host cells / mask -> bits (team) -> device -> byte mask at d_mask_dst (n bytes), enqueued on `st`; the host buffer has been
-// consumed when this returns (the unpack kernel is stream-ordered behind the upload).
-// d_mask_dst == kBitsOnly: the bits stay in h->stage_bits and are the caller's input.
-constexpr uint8_t* kBitsOnly = nullptr;
-int upload_packed(sdfgpu_handle h, const Occupancy& occ, int64_t n, uint8_t* d_mask_dst, hipStream_t st) {
-    const size_t nbytes = ((size_t)n + 7) / 8, padded = (nbytes + 3) & ~(size_t)3;
-    if (int rc = ensure(h, h->stage_bits, padded, "bit staging")) return rc;
-    auto fill = [=](char* dst, size_t o, size_t len) {
-        const size_t real = o >= nbytes ? 0 : std::min(len, nbytes - o);
-        if (real) {
-            if (occ.cells) pack_cells_bits(static_cast<const char*>(occ.cells), occ.stride, occ.off, occ.unknown, n, o, real, reinterpret_cast<uint8_t*>(dst));
-            else pack_mask_bits(occ.mask, n, o, real, reinterpret_cast<uint8_t*>(dst));
-        }
-        if (real < len) memset(dst + real, 0, len - real);
-    };
-    if (padded >= ((size_t)256 << 10)) {
-        if (int rc = staged_upload_hip(h, h->stage_bits.ptr, padded, st, 32, fill)) return rc;
-    } else {                                                    // small grids: one thread, one runtime-staged copy
-        std::vector<char> tmp(padded);
-        fill(tmp.data(), 0, padded);
-        HIP_TRY(h, hipMemcpyAsync(h->stage_bits.ptr, tmp.data(), padded, hipMemcpyHostToDevice, st));
-        HIP_TRY(h, hipStreamSynchronize(st));                   // (tmp goes out of scope)
-    }
-    if (d_mask_dst == kBitsOnly) return SDFGPU_OK;              // (the host-buffer builds: the bits are the build's input)
-    const int64_t nch = (n + 15) / 16;
-    hipLaunchKernelGGL(k_unpack_bits_mask, dim3((unsigned)((nch + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
-                       (const uint32_t*)h->stage_bits.ptr, d_mask_dst, n);
-    HIP_TRY(h, hipGetLastError());
-    return SDFGPU_OK;
-}
-
-// the caller's host bit field (ceil(n / 32) words) -> h->stage_bits
-int upload_bits(sdfgpu_handle h, const uint32_t* bits, int64_t n, hipStream_t st) {
-    const size_t bytes = (((size_t)n + 31) / 32) * 4;
-    if (int rc = ensure(h, h->stage_bits, bytes, "bit staging")) return rc;
-    return copy_from_host(h, h->stage_bits.ptr, bits, bytes, st);
-}
+namespace {
 
 // `occ` is host memory (occ.bits: the caller's occupancy is already one bit per voxel, sdfgpu_build_bits).
-// The cell records of the two tagged entry points in stage_in: uploaded, or (cells == nullptr) those the previous tagged call on
-// this handle left on the device.
-int stage_tagged_records(sdfgpu_handle h, const void* cells, size_t bytes) {
-    if (!cells) {
-        if (h->tag_cached_bytes == 0 || h->tag_cached_bytes != bytes)
-            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cells is null and the handle holds no cell records of this size");
-        return SDFGPU_OK;
-    }
-    h->tag_cached_bytes = 0;
-    if (int rc = ensure(h, h->stage_in, bytes, "input staging")) return rc;
-    if (int rc = copy_from_host(h, h->stage_in.ptr, cells, bytes)) return rc;
-    h->tag_cached_bytes = bytes;
-    return SDFGPU_OK;
-}
-
 // d_out_user != nullptr: the field stays on the device in the caller's buffer (no download; out_sdf is unused)
 int build_host_impl(sdfgpu_handle h, const Occupancy& occ, int64_t nx, int64_t ny, int64_t nz, double resolution, int vb, float* out_sdf,
                     double* out_max, double* out_min, float* d_out_user = nullptr) {
@@ -1720,13 +1053,13 @@ int build_host_impl(sdfgpu_handle h, const Occupancy& occ, int64_t nx, int64_t n
     HIP_TRY(h, hipSetDevice(h->device));
     const int64_t n = nx * ny * nz;
     const size_t in_bytes = occ.cells ? (size_t)n * occ.stride : (size_t)n;
-    h->tag_cached_bytes = 0;                        // (stage_in is about to be overwritten)
+    h->tag_cached_bytes = 0;                        // (every host-buffer build, also one whose input goes up as bits and leaves stage_in alone)
     // Round 5: the host's thread team classifies the caller's buffer into one bit per voxel while it fills the pinned staging
     // chunk, and 1/8 B per voxel crosses PCIe (16 MiB at 512^3 instead of 128 MiB of mask or 1 GiB of COLLISION_CELL records);
     // k_unpack_bits_mask spreads them into the byte mask on the device.  Same predicate as the device classifier
     // (pack_cells_bits); "host_pack" = 0 keeps the upload-and-classify-on-device path (device-resident cells always take it).
     const bool packed = !occ.bits && (h->opt.host_pack == 2 || (h->opt.host_pack == 1 && in_bytes >= kPinMin));
-    if (!packed && !occ.bits) if (int rc = ensure(h, h->stage_in, in_bytes, "input staging")) return rc;
+    if (!packed && !occ.bits) if (int rc = stage_input(h, in_bytes)) return rc;
     if (!d_out_user) if (int rc = ensure(h, h->stage_out, (size_t)n * 4, "output staging")) return rc;
     float* const d_out = d_out_user ? d_out_user : (float*)h->stage_out.ptr;
     const bool timing = getenv("SDFGPU_HOST_TIMING") != nullptr;
@@ -1734,7 +1067,7 @@ int build_host_impl(sdfgpu_handle h, const Occupancy& occ, int64_t nx, int64_t n
     const double t1 = now();
     // (out_sdf is scratch from here on: include/sdfgpu.h documents that its contents are undefined when the call fails)
     // (round 6: the uploaded bits ARE the build's input -- no byte mask is spread out on the device and packed again by K0)
-    if (packed) { if (int rc0 = upload_packed(h, occ, n, kBitsOnly, kNullStream)) return rc0; }
+    if (packed) { if (int rc0 = upload_packed(h, occ, n, kNullStream)) return rc0; }
     else if (occ.bits) { if (int rc0 = upload_bits(h, occ.bits, n, kNullStream)) return rc0; }
     else if (int rc0 = copy_from_host(h, h->stage_in.ptr, occ.cells ? occ.cells : (const void*)occ.mask, in_bytes)) return rc0;
     // what the upload left on the device (read the staging pointers behind it: the upload may have allocated them)
@@ -1756,499 +1089,12 @@ int build_host_impl(sdfgpu_handle h, const Occupancy& occ, int64_t nx, int64_t n
     return SDFGPU_OK;
 }
 
-// ---- connected components (sdfgpu_components.hpp) ------------------------------------------------------------------------------
-// Uses only cc_scratch (and, in the host forms, the bit / output staging and the pinned chunks, which every host-buffer call
-// owns while it runs): the SDF builds' scratch, status block and policy are not touched.
-int check_components_dims(sdfgpu_handle h, int64_t nx, int64_t ny, int64_t nz) {
-    if (nx <= 0 || ny <= 0 || nz <= 0)
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "grid dimensions must be positive (got %lld x %lld x %lld)",
-                    (long long)nx, (long long)ny, (long long)nz);
-    if ((unsigned __int128)nx * (unsigned __int128)ny * (unsigned __int128)nz > (unsigned __int128)0xFFFFFFFFu)
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "grid %lld x %lld x %lld has more than 2^32 - 1 voxels: uint32 component labels cannot number it",
-                    (long long)nx, (long long)ny, (long long)nz);
-    return SDFGPU_OK;
-}
-
-// bits (device) -> labels (device), K -> *out_count; synchronises `st` (K is read back)
-int components_impl(sdfgpu_handle h, const uint32_t* d_bits, int64_t nx, int64_t ny, int64_t nz, uint32_t* d_labels, uint32_t* out_count,
-                    hipStream_t st) {
-    const CcPlan plan = cc_plan(nx, ny, nz);
-    if (int rc = ensure(h, h->cc_scratch, plan.scratch_bytes, "components scratch")) return rc;
-    HIP_TRY(h, cc_launch(plan, d_bits, d_labels, h->cc_scratch.ptr, st));
-    uint32_t k = 0;
-    HIP_TRY(h, hipMemcpyAsync(&k, cc_count_word(plan, h->cc_scratch.ptr), 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipStreamSynchronize(st));
-    if (out_count) *out_count = k;
-    return SDFGPU_OK;
-}
-
-// host mask / cell records -> bits (host team, 1 bit per voxel over PCIe) -> labels in the output staging
-int components_host(sdfgpu_handle h, const Occupancy& occ, int64_t nx, int64_t ny, int64_t nz, uint32_t* out_count) {
-    const int64_t n = nx * ny * nz;
-    if (int rc = upload_packed(h, occ, n, kBitsOnly, kNullStream)) return rc;
-    if (int rc = ensure(h, h->stage_out, (size_t)n * 4, "output staging")) return rc;
-    return components_impl(h, (const uint32_t*)h->stage_bits.ptr, nx, ny, nz, (uint32_t*)h->stage_out.ptr, out_count, nullptr);
-}
-
-// ---- component topology (sdfgpu_topology.hpp) ----------------------------------------------------------------------------------
-// Like the components: only tp_scratch and tp_nodes (and, in the host forms, the label / bit staging and the pinned chunks) are
-// used; the SDF builds' scratch, status block and policy are not touched.
-int check_topology_args(sdfgpu_handle h, int64_t nx, int64_t ny, int64_t nz, uint32_t max_label, const int64_t* out_counts) {
-    if (!out_counts) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
-    if (int rc = check_components_dims(h, nx, ny, nz)) return rc;
-    if (max_label == 0xFFFFFFFFu) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "max_label must be below 2^32 - 1");
-    return SDFGPU_OK;
-}
-
-// labels (device) + selection bits (device or null) -> (max_label + 1) x 5 counters (host); synchronises `st`
-int topology_impl(sdfgpu_handle h, const uint32_t* d_labels, const uint32_t* d_select, int64_t nx, int64_t ny, int64_t nz, uint32_t max_label,
-                  int64_t* out_counts, hipStream_t st) {
-    const TpPlan plan = tp_plan(nx, ny, nz, max_label, d_select != nullptr);
-    if (int rc = ensure(h, h->tp_scratch, plan.scratch_bytes, "topology scratch")) return rc;
-    HIP_TRY(h, tp_launch_count(plan, d_labels, d_select, h->tp_scratch.ptr, st));
-    TpStatus status;
-    HIP_TRY(h, hipMemcpyAsync(&status, static_cast<char*>(h->tp_scratch.ptr) + plan.off_status, sizeof status, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipStreamSynchronize(st));
-    if (status.err & kTpErrLabel)
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "label %u exceeds max_label %u", status.label_over, max_label);
-    if (status.err & kTpErrMixed)
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT,
-                    "label %u has both selected and unselected voxels: its surface is undefined under this selection "
-                    "(labels must come from the connected components of the same occupancy)", status.label_mixed);
-    if (status.nodes > 0xFFFFFFFFull)
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT,
-                    "%llu surface-vertex nodes: more than the 2^32 - 1 that the union-find's 32-bit node ids can number",
-                    (unsigned long long)status.nodes);
-    if (int rc = ensure(h, h->tp_nodes, (size_t)std::max<uint64_t>(status.nodes, 1) * 4, "topology nodes")) return rc;
-    HIP_TRY(h, tp_launch_surfaces(plan, d_labels, h->tp_scratch.ptr, (uint32_t*)h->tp_nodes.ptr, status.nodes, st));
-    // (uint64 counters, read as int64: every count is below 2^32)
-    return copy_to_host(h, out_counts, h->tp_scratch.ptr, ((size_t)max_label + 1) * kTpCounters * 8, st);
-}
-
-// Bit (v & 7) of byte (v >> 3) = voxel v's occupancy class is in class_mask: FILLED (1) occupancy > 0.5f, EMPTY (2) < 0.5f,
-// UNKNOWN (4) the rest (0.5 and NaN), as the reference's tagged is_surface_index_fn branches (tagged_object_collision_map.cpp:448-481).
-void pack_cells_class_bits(const char* cells, size_t stride, size_t off, int class_mask, int64_t n, size_t ob, size_t len, uint8_t* out) {
-    int64_t v = (int64_t)ob * 8;
-    for (size_t o = 0; o < len; ++o) {
-        uint32_t b = 0;
-        for (int k = 0; k < 8; ++k, ++v) {
-            if (v >= n) continue;
-            float occ;
-            memcpy(&occ, cells + (size_t)v * stride + off, 4);
-            const int cls = occ > 0.5f ? 1 : occ < 0.5f ? 2 : 4;
-            if (cls & class_mask) b |= 1u << k;
-        }
-        out[o] = (uint8_t)b;
-    }
-}
-
-// host labels / cell records -> stage_out (labels) and, unless every voxel is selected, stage_bits (selection); *out_selected
-// says which
-int stage_labels_selection(sdfgpu_handle h, const uint32_t* labels, const uint8_t* select, const void* cells, size_t stride, size_t occ_off,
-                           size_t comp_off, int class_mask, int64_t n, bool* out_selected) {
-    if (int rc = ensure(h, h->stage_out, (size_t)n * 4, "output staging")) return rc;
-    if (labels) {
-        if (int rc = copy_from_host(h, h->stage_out.ptr, labels, (size_t)n * 4)) return rc;
-    } else {
-        const char* const rec = static_cast<const char*>(cells) + comp_off;
-        if (int rc = staged_upload_hip(h, h->stage_out.ptr, (size_t)n * 4, nullptr, 32, [=](char* dst, size_t o, size_t len) {
-                const char* src = rec + (o / 4) * stride;
-                for (size_t q = 0; q < len; q += 4, src += stride) memcpy(dst + q, src, 4);
-            }))
-            return rc;
-    }
-    const bool selected = labels ? select != nullptr : (class_mask & 7) != 7;
-    if (selected) {
-        if (labels || class_mask == 1) {                       // a byte mask, or FILLED: the build's packers (occupancy > 0.5f)
-            const Occupancy occ = labels ? Occupancy::of_mask(select) : Occupancy::of_cells(cells, stride, occ_off, 0);
-            if (int rc = upload_packed(h, occ, n, kBitsOnly, kNullStream)) return rc;
-        } else {
-            const size_t nbytes = ((size_t)n + 7) / 8, padded = (nbytes + 3) & ~(size_t)3;
-            if (int rc = ensure(h, h->stage_bits, padded, "bit staging")) return rc;
-            if (int rc = staged_upload_hip(h, h->stage_bits.ptr, padded, nullptr, 32, [=](char* dst, size_t o, size_t len) {
-                    const size_t real = o >= nbytes ? 0 : std::min(len, nbytes - o);
-                    if (real) pack_cells_class_bits(static_cast<const char*>(cells), stride, occ_off, class_mask, n, o, real, reinterpret_cast<uint8_t*>(dst));
-                    if (real < len) memset(dst + real, 0, len - real);
-                }))
-                return rc;
-        }
-    }
-    *out_selected = selected;
-    return SDFGPU_OK;
-}
-
-// host labels / cell records -> counters
-int topology_host(sdfgpu_handle h, const uint32_t* labels, const uint8_t* select, const void* cells, size_t stride, size_t occ_off,
-                  size_t comp_off, int class_mask, int64_t nx, int64_t ny, int64_t nz, uint32_t max_label, int64_t* out_counts) {
-    bool selected = false;
-    if (int rc = stage_labels_selection(h, labels, select, cells, stride, occ_off, comp_off, class_mask, nx * ny * nz, &selected)) return rc;
-    return topology_impl(h, (const uint32_t*)h->stage_out.ptr, selected ? (const uint32_t*)h->stage_bits.ptr : nullptr, nx, ny, nz,
-                         max_label, out_counts, nullptr);
-}
-
-// ---- component surfaces (sdfgpu_surfaces.hpp) -----------------------------------------------------------------------------------
-// Like the topology: only sf_scratch, sf_sort and sf_indices (and, in the host forms, the label / bit staging and the pinned
-// chunks) are used; the SDF builds' scratch, status block and policy are not touched.
-int check_surfaces_args(sdfgpu_handle h, int64_t nx, int64_t ny, int64_t nz, uint32_t max_label, const int64_t* out_counts, bool want_indices,
-                        int64_t capacity, const int64_t* out_total) {
-    if (!out_counts || !out_total) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
-    if (int rc = check_components_dims(h, nx, ny, nz)) return rc;
-    if (max_label == 0xFFFFFFFFu) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "max_label must be below 2^32 - 1");
-    if (want_indices && capacity < 0) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "capacity must not be negative (got %lld)", (long long)capacity);
-    return SDFGPU_OK;
-}
-
-// labels (device) + selection bits (device or null) -> counts (host) and, when asked, the grouped indices: into d_indices
-// (device) or, through sf_indices, into host_indices.  Synchronises `st`.
-int surfaces_impl(sdfgpu_handle h, const uint32_t* d_labels, const uint32_t* d_select, int64_t nx, int64_t ny, int64_t nz, uint32_t max_label,
-                  int64_t* out_counts, uint32_t* d_indices, uint32_t* host_indices, int64_t capacity, int64_t* out_total,
-                  uint32_t* d_surface_bits, hipStream_t st) {
-    const SfPlan plan = sf_plan(nx, ny, nz, max_label);
-    if (int rc = ensure(h, h->sf_scratch, plan.scratch_bytes, "surfaces scratch")) return rc;
-    HIP_TRY(h, sf_launch_flag(plan, d_labels, d_select, d_surface_bits, h->sf_scratch.ptr, st));
-    SfStatus status;
-    HIP_TRY(h, hipMemcpyAsync(&status, static_cast<char*>(h->sf_scratch.ptr) + plan.off_status, sizeof status, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipStreamSynchronize(st));
-    if (status.err & kSfErrLabel)
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "label %u exceeds max_label %u", status.label_over, max_label);
-    *out_total = (int64_t)status.total;
-    {                                                           // (uint32 counters, widened: every count is below 2^32)
-        std::vector<uint32_t> c32((size_t)max_label + 1);
-        if (int rc = copy_to_host(h, c32.data(), h->sf_scratch.ptr, c32.size() * 4, st)) return rc;
-        for (size_t c = 0; c < c32.size(); ++c) out_counts[c] = (int64_t)c32[c];
-    }
-    if (!d_indices && !host_indices) return SDFGPU_OK;          // counts only
-    if ((uint64_t)capacity < status.total)
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "the index buffer holds %lld indices, the surfaces have %llu (counts and total are valid)",
-                    (long long)capacity, (unsigned long long)status.total);
-    if (status.total == 0) return SDFGPU_OK;
-    if (host_indices) {
-        if (int rc = ensure(h, h->sf_indices, (size_t)status.total * 4, "surfaces indices")) return rc;
-        d_indices = (uint32_t*)h->sf_indices.ptr;
-    }
-    const SfSortPlan sp = sf_sort_plan(plan, status.total);
-    if (int rc = ensure(h, h->sf_sort, sp.bytes, "surfaces sort scratch")) return rc;
-    HIP_TRY(h, sf_launch_sort(plan, sp, d_labels, h->sf_scratch.ptr, h->sf_sort.ptr, d_indices, st));
-    if (host_indices) return copy_to_host(h, host_indices, d_indices, (size_t)status.total * 4, st);
-    HIP_TRY(h, hipStreamSynchronize(st));
-    return SDFGPU_OK;
-}
-
-int surfaces_host(sdfgpu_handle h, const uint32_t* labels, const uint8_t* select, const void* cells, size_t stride, size_t occ_off,
-                  size_t comp_off, int class_mask, int64_t nx, int64_t ny, int64_t nz, uint32_t max_label, int64_t* out_counts,
-                  uint32_t* out_indices, int64_t capacity, int64_t* out_total) {
-    bool selected = false;
-    if (int rc = stage_labels_selection(h, labels, select, cells, stride, occ_off, comp_off, class_mask, nx * ny * nz, &selected)) return rc;
-    return surfaces_impl(h, (const uint32_t*)h->stage_out.ptr, selected ? (const uint32_t*)h->stage_bits.ptr : nullptr, nx, ny, nz,
-                         max_label, out_counts, nullptr, out_indices, capacity, out_total, nullptr, nullptr);
-}
-
-// ---- display export (sdfgpu_display.hpp) --------------------------------------------------------------------------------------------
-// Only dp_scratch, dp_sort and dp_out (and, in the host forms, the cell / field staging and the pinned chunks) are used.
-int check_display_dims(sdfgpu_handle h, int64_t nx, int64_t ny, int64_t nz) {
-    if (nx <= 0 || ny <= 0 || nz <= 0)
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "grid dimensions must be positive (got %lld x %lld x %lld)",
-                    (long long)nx, (long long)ny, (long long)nz);
-    if ((unsigned __int128)nx * (unsigned __int128)ny * (unsigned __int128)nz > (unsigned __int128)0xFFFFFFFFu)
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "grid %lld x %lld x %lld has more than 2^32 - 1 voxels: the display export's uint32 indices cannot number it",
-                    (long long)nx, (long long)ny, (long long)nz);
-    return SDFGPU_OK;
-}
-
-struct DisplayRequest {
-    int rule = kDpRuleOccupancy;
-    const uint32_t* draw_keys = nullptr;       // host, ascending; nullptr = no list
-    int64_t n_draw_keys = 0;
-    bool grouped = false;
-    bool to_host = false;                      // the four result pointers are host memory (filled through dp_out)
-    uint32_t* indices = nullptr;               // nullptr = the total only
-    uint32_t* keys = nullptr;
-    int64_t capacity = 0;
-    uint32_t* group_keys = nullptr;
-    uint32_t* group_offsets = nullptr;
-    int64_t group_capacity = 0;
-    int64_t* out_total = nullptr;
-    int64_t* out_groups = nullptr;
-};
-
-int check_display_request(sdfgpu_handle h, const DisplayRequest& rq) {
-    if (!rq.out_total) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: null pointer");
-    if (rq.n_draw_keys < 0 || rq.n_draw_keys > (int64_t)0xFFFFFFFFll || (rq.n_draw_keys > 0 && !rq.draw_keys))
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: n_draw_keys must be in [0, 2^32) and come with a list (got %lld)", (long long)rq.n_draw_keys);
-    for (int64_t i = 1; rq.draw_keys && i < rq.n_draw_keys; ++i)
-        if (rq.draw_keys[i] < rq.draw_keys[i - 1])
-            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: draw_keys must be ascending (entry %lld is %u after %u)", (long long)i,
-                        rq.draw_keys[i], rq.draw_keys[i - 1]);
-    if (rq.indices && rq.capacity < 0) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: capacity must not be negative (got %lld)", (long long)rq.capacity);
-    if (rq.grouped && (!rq.indices || !rq.group_keys || !rq.group_offsets || !rq.out_groups || rq.group_capacity < 0))
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: the grouped form needs indices, group_keys, group_offsets, out_groups and a group capacity >= 0");
-    if (!rq.to_host && ((reinterpret_cast<uintptr_t>(rq.indices) | reinterpret_cast<uintptr_t>(rq.keys) | reinterpret_cast<uintptr_t>(rq.group_keys) |
-                         reinterpret_cast<uintptr_t>(rq.group_offsets)) & 3))
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: device pointers must be 4-byte aligned");
-    return SDFGPU_OK;
-}
-
-size_t dp_align8(size_t x) { return (x + 7) & ~(size_t)7; }
-int dp_bit_length(uint32_t x) { int b = 0; while (b < 32 && (x >> b) != 0) ++b; return b; }
-
-// sel: the source, the rule's options and the shape (device records).  Synchronises `st`.
-int display_select_impl(sdfgpu_handle h, DpSelect sel, const DisplayRequest& rq, hipStream_t st) {
-    const uint64_t n = sel.n, tiles = dp_tiles(n);
-    const size_t key_bytes = dp_align8((size_t)rq.n_draw_keys * 4);
-    const size_t off_keys = sizeof(DpStatus), off_bits = off_keys + key_bytes, off_counts = off_bits + (size_t)tiles * (kDpTile / 8),
-                 off_sums = off_counts + dp_align8((size_t)tiles * 4),
-                 bytes = off_sums + dp_align8((size_t)((tiles + kDpScanSeg - 1) / kDpScanSeg) * 4);
-    if (int rc = ensure(h, h->dp_scratch, bytes, "display scratch")) return rc;
-    char* const b = static_cast<char*>(h->dp_scratch.ptr);
-    DpStatus* const d_st = reinterpret_cast<DpStatus*>(b);
-    uint32_t* const bits = reinterpret_cast<uint32_t*>(b + off_bits);
-    uint32_t* const counts = reinterpret_cast<uint32_t*>(b + off_counts);
-    uint32_t* const sums = reinterpret_cast<uint32_t*>(b + off_sums);
-    HIP_TRY(h, hipMemsetAsync(d_st, 0, sizeof(DpStatus), st));
-    if (rq.n_draw_keys) HIP_TRY(h, hipMemcpyAsync(b + off_keys, rq.draw_keys, (size_t)rq.n_draw_keys * 4, hipMemcpyHostToDevice, st));
-    sel.draw_keys = reinterpret_cast<const uint32_t*>(b + off_keys);
-    sel.n_draw = (uint32_t)rq.n_draw_keys;
-    sel.filter = rq.draw_keys != nullptr;
-    sel.bits = bits;
-    sel.tile_counts = counts;
-    sel.total = &d_st->total;
-    sel.key_max = &d_st->key_max;
-    HIP_TRY(h, dp_launch_select(rq.rule, sel, st));
-    DpStatus status;
-    HIP_TRY(h, hipMemcpyAsync(&status, d_st, sizeof status, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipStreamSynchronize(st));
-    const uint64_t total = status.total;
-    *rq.out_total = (int64_t)total;
-    if (rq.out_groups) *rq.out_groups = 0;
-    if (!rq.indices) return SDFGPU_OK;                          // the total only
-    if ((uint64_t)rq.capacity < total)
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: the buffers hold %lld elements, %llu voxels are drawn (the total is valid)",
-                    (long long)rq.capacity, (unsigned long long)total);
-    // where the results are built: the caller's device arrays or dp_out
-    const uint64_t gmax = std::min<uint64_t>(total, rq.grouped ? (uint64_t)rq.group_capacity : 0);
-    uint32_t *d_idx = rq.indices, *d_keys = rq.keys, *d_gkeys = rq.group_keys, *d_goffs = rq.group_offsets;
-    if (rq.to_host) {                                           // indices | keys (only when someone reads them) | group keys | group offsets
-        const size_t key_words = rq.keys || rq.grouped ? (size_t)total : 0;
-        if (int rc = ensure(h, h->dp_out, ((size_t)total + key_words + (size_t)gmax * 2 + 1) * 4, "display results")) return rc;
-        d_idx = static_cast<uint32_t*>(h->dp_out.ptr);
-        d_keys = key_words ? d_idx + total : nullptr;
-        d_gkeys = d_idx + total + key_words;
-        d_goffs = d_gkeys + gmax;
-    }
-    // sort only the bits in which the drawn keys differ: all of them agree above bit_length(max ^ min)
-    const int key_bits = rq.grouped && total ? dp_bit_length(status.key_max ^ ~status.key_inv_max) : 0;
-    const SfPairSortPlan sp = key_bits ? sf_pair_sort_plan(total, key_bits) : SfPairSortPlan();
-    const bool own_keys = rq.grouped && !d_keys;               // the group boundaries are read from the sorted keys
-    if (sp.bytes || own_keys) {
-        if (int rc = ensure(h, h->dp_sort, sp.bytes + (own_keys ? (size_t)total * 4 : 0), "display sort scratch")) return rc;
-        if (own_keys) d_keys = reinterpret_cast<uint32_t*>(static_cast<char*>(h->dp_sort.ptr) + sp.bytes);
-    }
-    if (total) {
-        sf_launch_scan(counts, tiles, sums, st);
-        DpCompact c;
-        c.src = sel.src;
-        c.key_mode = rq.rule == kDpRuleOccupancy ? kDpKeyClass : rq.rule == kDpRuleKeyField ? kDpKeyWord : kDpKeyZero;
-        c.n = n;
-        c.bits = bits;
-        c.tile_offsets = counts;
-        c.capacity = total;
-        if (key_bits) c.pairs = static_cast<uint2*>(h->dp_sort.ptr);
-        else { c.idx = d_idx; c.keys = d_keys; }
-        HIP_TRY(h, dp_launch_compact(c, st));
-        if (key_bits) HIP_TRY(h, sf_launch_sort_pairs(sp, key_bits, h->dp_sort.ptr, d_idx, d_keys, st));
-    }
-    uint64_t groups = 0;
-    if (rq.grouped) {
-        if (total) {                                            // the same three steps over the sorted keys (their tiles fit the main pass's scratch)
-            DpSelect g;
-            g.src.cells = reinterpret_cast<const char*>(d_keys);
-            g.src.stride = 4;
-            g.src.occ_off = 0;                                  // (not read by this rule)
-            g.src.key_off = 0;                                  // the key IS the record: k_dp_compact reads it at offset 0
-            g.n = total;
-            g.bits = bits;
-            g.tile_counts = counts;
-            g.total = &d_st->groups;
-            HIP_TRY(h, dp_launch_select(kDpRuleGroupStart, g, st));
-            HIP_TRY(h, hipMemcpyAsync(&status, d_st, sizeof status, hipMemcpyDeviceToHost, st));
-            HIP_TRY(h, hipStreamSynchronize(st));
-            groups = status.groups;
-            *rq.out_groups = (int64_t)groups;
-            if ((uint64_t)rq.group_capacity < groups)
-                return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: the group arrays hold %lld groups, the drawn voxels have %llu keys (total and groups are valid)",
-                            (long long)rq.group_capacity, (unsigned long long)groups);
-            sf_launch_scan(counts, dp_tiles(total), sums, st);
-            // the same kernel with other meanings: its "voxels" are the positions in the sorted key array (records of one word,
-            // stride 4, key at offset 0), so c.idx receives the positions of the group starts = the group offsets, and c.keys
-            // load_word(sorted keys, position) = the group keys
-            DpCompact c;
-            c.src = g.src;
-            c.key_mode = kDpKeyWord;
-            c.n = total;
-            c.bits = bits;
-            c.tile_offsets = counts;
-            c.capacity = groups;
-            c.idx = d_goffs;
-            c.keys = d_gkeys;
-            HIP_TRY(h, dp_launch_compact(c, st));
-        }
-        HIP_TRY(h, hipMemcpyAsync(d_goffs + groups, &d_st->total, 4, hipMemcpyDeviceToDevice, st));      // group_offsets[groups] = total
-    }
-    HIP_TRY(h, hipGetLastError());
-    if (rq.to_host) {
-        if (int rc = copy_to_host(h, rq.indices, d_idx, (size_t)total * 4, st)) return rc;
-        if (rq.keys) if (int rc = copy_to_host(h, rq.keys, d_keys, (size_t)total * 4, st)) return rc;
-        if (rq.grouped) {
-            if (int rc = copy_to_host(h, rq.group_keys, d_gkeys, (size_t)groups * 4, st)) return rc;
-            if (int rc = copy_to_host(h, rq.group_offsets, d_goffs, ((size_t)groups + 1) * 4, st)) return rc;
-        }
-    }
-    HIP_TRY(h, hipStreamSynchronize(st));
-    return SDFGPU_OK;
-}
-
-int check_display_cells(sdfgpu_handle h, const void* cells, size_t stride, size_t occ_off, size_t key_off, int64_t nx, int64_t ny, int64_t nz,
-                        int rule, int class_mask, DpSelect& sel) {
-    if (!cells) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: null pointer");
-    if (rule != SDFGPU_DISPLAY_OCCUPANCY && rule != SDFGPU_DISPLAY_KEY_FIELD)
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: rule must be SDFGPU_DISPLAY_OCCUPANCY (0) or SDFGPU_DISPLAY_KEY_FIELD (1), got %d", rule);
-    if (int rc = check_cell_layout(h, stride, occ_off)) return rc;
-    if (rule == SDFGPU_DISPLAY_KEY_FIELD && ((key_off % 4) || key_off + 4 > stride))
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: key_offset must be 4-byte aligned and inside the record");
-    if (class_mask < 0 || class_mask > 7)
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: class_mask must be a combination of FILLED (1), EMPTY (2) and UNKNOWN (4)");
-    if (int rc = check_display_dims(h, nx, ny, nz)) return rc;
-    sel.src.stride = stride;
-    sel.src.occ_off = (uint32_t)occ_off;
-    sel.src.key_off = (uint32_t)key_off;
-    sel.class_mask = (uint32_t)class_mask;
-    sel.nx = (uint32_t)nx; sel.ny = (uint32_t)ny; sel.nz = (uint32_t)nz;
-    sel.n = (uint64_t)nx * (uint64_t)ny * (uint64_t)nz;
-    return SDFGPU_OK;
-}
-
-int check_display_sdf(sdfgpu_handle h, const float* sdf, int64_t nx, int64_t ny, int64_t nz, DpSelect& sel) {
-    if (!sdf) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: null pointer");
-    if (int rc = check_display_dims(h, nx, ny, nz)) return rc;
-    sel.src.stride = 4;
-    sel.nx = (uint32_t)nx; sel.ny = (uint32_t)ny; sel.nz = (uint32_t)nz;
-    sel.n = (uint64_t)nx * (uint64_t)ny * (uint64_t)nz;
-    return SDFGPU_OK;
-}
-
-// a = min(max(alpha, 0), 1); the extrema into dp_scratch's status words, then one rgba per voxel.  Synchronises `st` (the status
-// words are scratch of the handle).
-int display_sdf_colors_impl(sdfgpu_handle h, const float* d_sdf, uint64_t n, float alpha, float* d_colors, hipStream_t st) {
-    if (int rc = ensure(h, h->dp_scratch, sizeof(DpStatus), "display scratch")) return rc;
-    DpStatus* const d_st = static_cast<DpStatus*>(h->dp_scratch.ptr);
-    HIP_TRY(h, hipMemsetAsync(d_st, 0, sizeof(DpStatus), st));
-    HIP_TRY(h, dp_launch_minmax(d_sdf, n, d_st, st));
-    HIP_TRY(h, dp_launch_sdf_colors(d_sdf, n, std::min(std::max(alpha, 0.0f), 1.0f), d_st, d_colors, st));
-    HIP_TRY(h, hipStreamSynchronize(st));
-    return SDFGPU_OK;
-}
-
-// ---- resample (sdfgpu_resample.hpp) ------------------------------------------------------------------------------------------------
-// Only rs_scratch (and, in the host form, the cell and field staging and the pinned chunks) is used.
-int check_resample_args(sdfgpu_handle h, const void* src, size_t cell_bytes, int64_t nx, int64_t ny, int64_t nz, const double* src_cell,
-                        const double* origin, const double* dst_inverse_origin, const double* dst_inv_cell, const void* dst, int64_t mx,
-                        int64_t my, int64_t mz, const void* fill_cell, ResampleArgs& a) {
-    if (!src || !dst || !src_cell || !origin || !dst_inverse_origin || !dst_inv_cell || !fill_cell)
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "resample: null pointer");
-    if (cell_bytes != 4 && cell_bytes != 8 && cell_bytes != 16)
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "resample: cell_bytes must be 4, 8 or 16 (got %zu)", cell_bytes);
-    if (src == dst) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "resample: the source and the result must be different buffers");
-    const int64_t kMaxCells = INT64_MAX / 16;
-    if (nx <= 0 || ny <= 0 || nz <= 0 || nx > kMaxCells / ny || nx * ny > kMaxCells / nz)
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "resample: unsupported source grid %lld x %lld x %lld", (long long)nx, (long long)ny, (long long)nz);
-    if (mx <= 0 || my <= 0 || mz <= 0 || mx > kMaxCells / my || mx * my > kMaxCells / mz)
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "resample: unsupported result grid %lld x %lld x %lld", (long long)mx, (long long)my, (long long)mz);
-    a = ResampleArgs{};
-    a.nx = nx; a.ny = ny; a.nz = nz; a.mx = mx; a.my = my; a.mz = mz;
-    a.n_src = nx * ny * nz; a.n_dst = mx * my * mz;
-    for (int i = 0; i < 3; ++i) { a.cell[i] = src_cell[i]; a.inv_cell[i] = dst_inv_cell[i]; }
-    for (int i = 0; i < 16; ++i) { a.origin[i] = origin[i]; a.inverse[i] = dst_inverse_origin[i]; }
-    memcpy(a.fill, fill_cell, cell_bytes);
-    a.cell_bytes = (int)cell_bytes;
-    a.winner_bytes = resample_winner_bytes(a.n_src);
-    a.plain_atomics = h->opt.rs_plain_atomics;
-    return SDFGPU_OK;
-}
-
-// a.src -> a.dst (device) on `st`; synchronises `st` only when out_written is asked for
-int resample_impl(sdfgpu_handle h, ResampleArgs& a, uint64_t* out_written, hipStream_t st) {
-    // the winner words belong to the handle and the call may return with its kernels pending: a call on another stream waits for
-    // them on the device first, as the local extrema do (ensure() below may free the scratch: hipFree waits for the device)
-    HIP_TRY(h, h->rs_order.create());
-    HIP_TRY(h, h->rs_order.wait(st));
-    if (int rc = ensure(h, h->rs_scratch, resample_scratch_bytes(a.n_dst, a.winner_bytes), "resample winners")) return rc;
-    a.winner = h->rs_scratch.ptr;
-    unsigned long long* const counter =
-        reinterpret_cast<unsigned long long*>(static_cast<char*>(h->rs_scratch.ptr) + resample_counter_offset(a.n_dst, a.winner_bytes));
-    a.written = out_written ? counter : nullptr;
-    if (h->opt.rs_timing) {
-        for (hipEvent_t& e : h->rs_time_ev) if (!e) HIP_TRY(h, hipEventCreate(&e));
-        HIP_TRY(h, hipEventRecord(h->rs_time_ev[0], st));
-    }
-    const hipError_t le = resample_launch(a, st, h->opt.rs_timing ? h->rs_time_ev[1] : nullptr);
-    if (h->opt.rs_timing) h->rs_timed = le == hipSuccess && hipEventRecord(h->rs_time_ev[2], st) == hipSuccess;
-    (void)h->rs_order.record(st);                       // (also behind a failed launch: what it did enqueue is ordered)
-    HIP_TRY(h, le);
-    if (out_written) {
-        unsigned long long count = 0;
-        HIP_TRY(h, hipMemcpyAsync(&count, counter, sizeof count, hipMemcpyDeviceToHost, st));
-        HIP_TRY(h, hipStreamSynchronize(st));
-        *out_written = (uint64_t)count;
-    }
-    return SDFGPU_OK;
-}
-
-// ---- local extrema and convex segments (sdfgpu_convex.hpp) ---------------------------------------------------------------------
-// The extrema and segment stages use only cx_scratch and cx_field (and, in the host forms, the staging buffers and the pinned
-// chunks); the SDF scratch, status block and policy are left as they were.  sdfgpu_convex_segments_cells builds its SDF with the
-// ordinary tagged build.
-int check_convex_args(sdfgpu_handle h, int64_t nx, int64_t ny, int64_t nz, double resolution, const double* q_and_qinv) {
-    if (!q_and_qinv) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
-    if (nx <= 0 || ny <= 0 || nz <= 0)
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "grid dimensions must be positive (got %lld x %lld x %lld)",
-                    (long long)nx, (long long)ny, (long long)nz);
-    // Indices, kCxOff and the doubling markers share one uint32 space (sdfgpu_convex.hip): the markers are 2^32 - 1 (= kCxOff),
-    // 2^32 - 2 and 2^32 - 3, so every index must stay below 2^32 - 3 and n may be at most 2^32 - 3.
-    if ((unsigned __int128)nx * (unsigned __int128)ny * (unsigned __int128)nz >= (unsigned __int128)0xFFFFFFFEu)
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT,
-                    "grid %lld x %lld x %lld has 2^32 - 2 voxels or more: uint32 indices share their space with the OFF sentinel and "
-                    "the doubling markers 2^32 - 1, 2^32 - 2, 2^32 - 3, so at most 2^32 - 3 voxels can be numbered",
-                    (long long)nx, (long long)ny, (long long)nz);
-    if (!(resolution > 0.0) || !std::isfinite(resolution))
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "resolution must be positive and finite (got %g)", resolution);
-    return SDFGPU_OK;
-}
-
-// d_sdf (device) -> d_ext (device); synchronises `st` once per doubling round
-int extrema_impl(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t ny, int64_t nz, double resolution, const double* q_and_qinv,
-                 uint32_t* d_ext, hipStream_t st) {
-    const CxPlan plan = cx_plan(nx, ny, nz);
-    // cx_extrema returns with its basin / entry / final kernels still pending on `st`, and they read and write cx_scratch: a
-    // computation on another stream is ordered behind them, as the builds are ordered by build_order.  (ensure() below may
-    // free the scratch: hipFree waits for the device.)
-    HIP_TRY(h, h->cx_order.create());
-    HIP_TRY(h, h->cx_order.wait(st));
-    if (int rc = ensure(h, h->cx_scratch, plan.scratch_bytes, "convex scratch")) return rc;
-    CxRot rot;
-    for (int i = 0; i < 4; ++i) { rot.q[i] = q_and_qinv[i]; rot.qi[i] = q_and_qinv[4 + i]; }
-    int rounds = 0;
-    h->cx_stats_off = 0;
-    const hipError_t ce = cx_extrema(plan, d_sdf, resolution, rot, d_ext, h->cx_scratch.ptr, st, &rounds);
-    (void)h->cx_order.record(st);                       // (also behind a failed launch: what it did enqueue is ordered)
-    HIP_TRY(h, ce);
-    h->cx_stats_off = plan.off_stats;
-    h->cx_rounds = rounds;
-    return SDFGPU_OK;
-}
+}  // namespace
 
 // records in stage_in -> SDF in stage_out (float), the virtual-border or the free-and-named-objects form
-int convex_sdf(sdfgpu_handle h, size_t stride, size_t occ_off, size_t obj_off, int64_t nx, int64_t ny, int64_t nz, double resolution,
-               int add_virtual_border) {
+// (called from sdfgpu_convex.hip; here because it launches k_classify_tagged and builds SDFs)
+int sdfgpu::convex_sdf(sdfgpu_handle h, size_t stride, size_t occ_off, size_t obj_off, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                       int add_virtual_border) {
     const int64_t n = nx * ny * nz;
     auto classify = [&](int mode) {
         hipLaunchKernelGGL(k_classify_tagged, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, nullptr,
@@ -2272,111 +1118,7 @@ int convex_sdf(sdfgpu_handle h, size_t stride, size_t occ_off, size_t obj_off, i
     return SDFGPU_OK;
 }
 
-// Host staging of the three point calls (sdfgpu_query_points, sdfgpu_project_points, sdfgpu_query_gradients) in query_stage, which
-// grows on demand and is re-used by the next call: points (24 bytes each) | three result sections of per_point[i] bytes per point,
-// the last one padded to 256 bytes.  Uploads the points, runs launch(device points, device sections: null where the caller passed
-// no out[i]) and downloads the sections that were asked for, in their order.
-template <class Launch>
-int with_staged_points(sdfgpu_handle h, const double* points, int64_t n_points, const size_t (&per_point)[3], void* const (&out)[3], Launch launch) {
-    const size_t n = (size_t)n_points;
-    size_t off[4] = {n * 24, 0, 0, 0};
-    for (int i = 0; i < 3; ++i) off[i + 1] = off[i] + n * per_point[i];
-    if (int rc = ensure(h, h->query_stage, off[2] + ((n * per_point[2] + 255) & ~(size_t)255), "query staging")) return rc;
-    char* const base = (char*)h->query_stage.ptr;
-    char* const dev[3] = {out[0] ? base + off[0] : nullptr, out[1] ? base + off[1] : nullptr, out[2] ? base + off[2] : nullptr};
-    // Round 5: the null stream of the context's device, ordered behind this handle's last build by its event --
-    // not h->last.last_stream, which is a handle of the CALLER's (an earlier *_device build's stream may have been destroyed since).
-    // A field produced ELSEWHERE (another handle, a caller's kernel) is ordered by the null stream's implicit synchronisation only
-    // when its stream is a blocking one: producers on hipStreamNonBlocking streams (PyTorch's are) must be synchronised by the caller
-    // before this call -- include/sdfgpu.h says so.
-    HIP_TRY(h, h->build_order.wait(nullptr));
-    if (int rc = copy_from_host(h, base, points, n * 24, nullptr)) return rc;
-    if (int rc = launch((const double*)base, dev)) return rc;
-    for (int i = 0; i < 3; ++i) if (out[i]) if (int rc = copy_to_host(h, out[i], dev[i], n * per_point[i], nullptr)) return rc;
-    return SDFGPU_OK;
-}
-
-}  // namespace
-
 extern "C" {
-
-const char* sdfgpu_version(void) { return "sdfgpu 0.1 (gfx950, HIP)"; }
-
-int sdfgpu_device_count(void) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-    return n;
-}
-
-int sdfgpu_create(int device, sdfgpu_handle* out_handle) {
-    if (!out_handle) return fail(nullptr, SDFGPU_ERR_INVALID_ARGUMENT, "out_handle is null");
-    *out_handle = nullptr;
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess || n <= 0)
-        return fail(nullptr, SDFGPU_ERR_NO_DEVICE, "no HIP device available (%s); this library has no CPU fallback",
-                    e == hipSuccess ? "device count 0" : hipGetErrorString(e));
-    if (device < 0 || device >= n)
-        return fail(nullptr, SDFGPU_ERR_NO_DEVICE, "device index %d out of range (0..%d)", device, n - 1);
-    HIP_TRY(nullptr, hipSetDevice(device));
-    sdfgpu_context* ctx = new (std::nothrow) sdfgpu_context();
-    if (!ctx) return fail(nullptr, SDFGPU_ERR_INVALID_ARGUMENT, "out of host memory");
-    ctx->device = device;
-    {
-        const char* rz = getenv("SDFGPU_REDZONE");
-        ctx->redzone = rz && rz[0] && rz[0] != '0';
-    }
-    hipError_t ce = rz_malloc(ctx, "extrema slots", (size_t)kSlots * kSlotWords * 4, (void**)&ctx->d_slots) == SDFGPU_OK ? hipSuccess : hipErrorOutOfMemory;
-    if (ce == hipSuccess) ce = hipMemset(ctx->d_slots, 0, (size_t)kSlots * kSlotWords * 4);
-    if (ce == hipSuccess) ce = rz_malloc(ctx, "status block", 512, (void**)&ctx->d_small) == SDFGPU_OK ? hipSuccess : hipErrorOutOfMemory;
-    if (ce == hipSuccess) ce = hipMemset(ctx->d_small, 0, 512);
-    if (ce != hipSuccess) {
-        if (ctx->d_slots) (void)rz_free(ctx, ctx->d_slots);
-        if (ctx->d_small) (void)rz_free(ctx, ctx->d_small);
-        delete ctx;
-        return fail(nullptr, SDFGPU_ERR_HIP, "HIP error %d (%s) while allocating the context's status blocks",
-                    (int)ce, hipGetErrorString(ce));
-    }
-    ctx->d_result = ctx->d_small + 64;                       // second half of the same allocation
-    if (hipHostMalloc((void**)&ctx->h_flags, 256, hipHostMallocMapped) != hipSuccess) ctx->h_flags = nullptr;
-    if (ctx->h_flags && hipHostGetDevicePointer((void**)&ctx->h_flags_dev, ctx->h_flags, 0) != hipSuccess) ctx->h_flags_dev = nullptr;
-    if (ctx->h_flags && hipEventCreateWithFlags(&ctx->flags_ev, hipEventDisableTiming) != hipSuccess) {
-        (void)hipHostFree(ctx->h_flags);
-        ctx->h_flags = nullptr;
-    }
-    if (ctx->h_flags && ctx->h_flags_dev && hipEventCreateWithFlags(&ctx->far_ev, hipEventDisableTiming) == hipSuccess) {
-        memset(ctx->h_flags, 0, 256);
-        ctx->h_far = ctx->h_flags + 32;                        // second half of the same pinned allocation
-        ctx->h_far_dev = ctx->h_flags_dev + 32;
-    } else {
-        ctx->far_ev = nullptr;
-    }
-    *out_handle = ctx;
-    return SDFGPU_OK;
-}
-
-int sdfgpu_destroy(sdfgpu_handle h) {
-    if (!h) return SDFGPU_OK;
-    (void)hipSetDevice(h->device);
-    for (DeviceBuffer& b : *h) if (b.ptr) (void)rz_free(h, b.ptr);
-    if (h->d_small) (void)rz_free(h, h->d_small);
-    if (h->d_slots) (void)rz_free(h, h->d_slots);
-    if (h->rz_table) (void)hipFree(h->rz_table);
-    if (h->batch_pin) (void)hipHostFree(h->batch_pin);
-    if (h->h_flags) { (void)hipHostFree(h->h_flags); (void)hipEventDestroy(h->flags_ev); }
-    if (h->far_ev) (void)hipEventDestroy(h->far_ev);
-    for (StreamOrder* o : {&h->build_order, &h->cx_order, &h->rs_order}) o->destroy();
-    for (hipEvent_t e : h->rs_time_ev) if (e) (void)hipEventDestroy(e);
-    for (int i = 0; i < 2; ++i) { if (h->pin[i]) (void)hipHostFree(h->pin[i]); if (h->pin_ev[i]) (void)hipEventDestroy(h->pin_ev[i]); }
-    for (size_t i = 0; i < h->events.size(); ++i)
-        if (i % 8 == 0 || h->events[i] != h->events[i - 1]) (void)hipEventDestroy(h->events[i]);
-    for (hipEvent_t e : h->event_pool) (void)hipEventDestroy(e);
-    delete h->team;                                             // (joins the parked host threads)
-    delete h;
-    return SDFGPU_OK;
-}
-
-const char* sdfgpu_last_error(sdfgpu_handle h) { return h ? h->error.c_str() : g_create_error.c_str(); }
 
 int sdfgpu_build(sdfgpu_handle h, const uint8_t* filled, int64_t nx, int64_t ny, int64_t nz, double resolution,
                  int add_virtual_border, float* out_sdf, double* out_max, double* out_min) {
@@ -2389,8 +1131,8 @@ int sdfgpu_build_cells(sdfgpu_handle h, const void* cells, size_t cell_stride, s
                        int unknown_is_filled, int64_t nx, int64_t ny, int64_t nz, double resolution,
                        int add_virtual_border, float* out_sdf, double* out_max, double* out_min) {
     return rz_wrap(h, nullptr, [&]() -> int {
-        if (h && !cells) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cells is null");
-        if (h) if (int rc = check_cell_layout(h, cell_stride, occupancy_offset)) return rc;
+        if (!cells) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cells is null");
+        if (int rc = check_cell_layout(h, cell_stride, occupancy_offset)) return rc;
         return build_host_impl(h, Occupancy::of_cells(cells, cell_stride, occupancy_offset, unknown_is_filled), nx, ny, nz,
                                resolution, add_virtual_border, out_sdf, out_max, out_min);
     });
@@ -2399,7 +1141,7 @@ int sdfgpu_build_cells(sdfgpu_handle h, const void* cells, size_t cell_stride, s
 int sdfgpu_build_to_device(sdfgpu_handle h, const uint8_t* filled, int64_t nx, int64_t ny, int64_t nz, double resolution,
                            int add_virtual_border, float* d_out_sdf, double* out_max, double* out_min) {
     return rz_wrap(h, nullptr, [&]() -> int {
-        if (h && !d_out_sdf) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "d_out_sdf is null");
+        if (!d_out_sdf) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "d_out_sdf is null");
         float* const no_host_field = nullptr;
         return build_host_impl(h, Occupancy::of_mask(filled), nx, ny, nz, resolution, add_virtual_border, no_host_field, out_max, out_min,
                                d_out_sdf);
@@ -2410,9 +1152,9 @@ int sdfgpu_build_cells_to_device(sdfgpu_handle h, const void* cells, size_t cell
                                  int unknown_is_filled, int64_t nx, int64_t ny, int64_t nz, double resolution,
                                  int add_virtual_border, float* d_out_sdf, double* out_max, double* out_min) {
     return rz_wrap(h, nullptr, [&]() -> int {
-        if (h && !cells) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cells is null");
-        if (h && !d_out_sdf) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "d_out_sdf is null");
-        if (h) if (int rc = check_cell_layout(h, cell_stride, occupancy_offset)) return rc;
+        if (!cells) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "cells is null");
+        if (!d_out_sdf) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "d_out_sdf is null");
+        if (int rc = check_cell_layout(h, cell_stride, occupancy_offset)) return rc;
         float* const no_host_field = nullptr;
         return build_host_impl(h, Occupancy::of_cells(cells, cell_stride, occupancy_offset, unknown_is_filled), nx, ny, nz, resolution,
                                add_virtual_border, no_host_field, out_max, out_min, d_out_sdf);
@@ -2422,7 +1164,7 @@ int sdfgpu_build_cells_to_device(sdfgpu_handle h, const void* cells, size_t cell
 int sdfgpu_build_device(sdfgpu_handle h, const uint8_t* d_filled, int64_t nx, int64_t ny, int64_t nz,
                         double resolution, int add_virtual_border, float* d_out_sdf, void* stream) {
     return rz_wrap(h, stream, [&]() -> int {
-        if (h && !d_filled) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "d_filled is null");
+        if (!d_filled) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "d_filled is null");
         return build_device_impl(h, Occupancy::of_mask(d_filled), nx, ny, nz, resolution, add_virtual_border, d_out_sdf, (hipStream_t)stream);
     });
 }
@@ -2431,7 +1173,7 @@ int sdfgpu_build_cells_device(sdfgpu_handle h, const void* d_cells, size_t cell_
                               int unknown_is_filled, int64_t nx, int64_t ny, int64_t nz, double resolution,
                               int add_virtual_border, float* d_out_sdf, void* stream) {
     return rz_wrap(h, stream, [&]() -> int {
-        if (h && !d_cells) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "d_cells is null");
+        if (!d_cells) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "d_cells is null");
         return build_device_impl(h, Occupancy::of_cells(d_cells, cell_stride, occupancy_offset, unknown_is_filled), nx, ny, nz,
                                  resolution, add_virtual_border, d_out_sdf, (hipStream_t)stream);
     });
@@ -2440,7 +1182,7 @@ int sdfgpu_build_cells_device(sdfgpu_handle h, const void* d_cells, size_t cell_
 int sdfgpu_build_bits_device(sdfgpu_handle h, const uint32_t* d_bits, int64_t nx, int64_t ny, int64_t nz,
                              double resolution, int add_virtual_border, float* d_out_sdf, void* stream) {
     return rz_wrap(h, stream, [&]() -> int {
-        if (h && !d_bits) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "d_bits is null");
+        if (!d_bits) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "d_bits is null");
         return build_device_impl(h, Occupancy::of_bits(d_bits), nx, ny, nz, resolution, add_virtual_border, d_out_sdf, (hipStream_t)stream);
     });
 }
@@ -2448,39 +1190,26 @@ int sdfgpu_build_bits_device(sdfgpu_handle h, const uint32_t* d_bits, int64_t nx
 int sdfgpu_build_bits(sdfgpu_handle h, const uint32_t* bits, int64_t nx, int64_t ny, int64_t nz, double resolution,
                       int add_virtual_border, float* out_sdf, double* out_max, double* out_min) {
     return rz_wrap(h, nullptr, [&]() -> int {
-        if (h && !bits) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "bits is null");
+        if (!bits) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "bits is null");
         return build_host_impl(h, Occupancy::of_bits(bits), nx, ny, nz, resolution, add_virtual_border, out_sdf, out_max, out_min);
-    });
-}
-
-int sdfgpu_copy_to_host(sdfgpu_handle h, void* dst, const void* d_src, size_t bytes, void* stream) {
-    return rz_wrap(h, stream, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-        if (bytes > 0 && (!dst || !d_src)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
-        HIP_TRY(h, hipSetDevice(h->device));
-        return copy_to_host(h, dst, d_src, bytes, (hipStream_t)stream);
-    });
-}
-
-int sdfgpu_copy_from_host(sdfgpu_handle h, void* d_dst, const void* src, size_t bytes, void* stream) {
-    return rz_wrap(h, stream, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-        if (bytes > 0 && (!d_dst || !src)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
-        HIP_TRY(h, hipSetDevice(h->device));
-        return copy_from_host(h, d_dst, src, bytes, (hipStream_t)stream);
     });
 }
 
 int sdfgpu_upload_classified(sdfgpu_handle h, const uint8_t* filled, const void* cells, size_t cell_stride, size_t occupancy_offset,
                              int unknown_is_filled, int64_t n, uint8_t* d_mask, void* stream) {
     return rz_wrap(h, stream, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
         if ((!filled && !cells) || !d_mask) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
         if (n <= 0) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "voxel count must be positive");
         if (cells) if (int rc = check_cell_layout(h, cell_stride, occupancy_offset)) return rc;
         HIP_TRY(h, hipSetDevice(h->device));
         const Occupancy occ = cells ? Occupancy::of_cells(cells, cell_stride, occupancy_offset, unknown_is_filled) : Occupancy::of_mask(filled);
-        return upload_packed(h, occ, n, d_mask, (hipStream_t)stream);
+        if (int rc = upload_packed(h, occ, n, (hipStream_t)stream)) return rc;
+        // bits -> the caller's byte mask, stream-ordered behind the upload
+        const int64_t nch = (n + 15) / 16;
+        hipLaunchKernelGGL(k_unpack_bits_mask, dim3((unsigned)((nch + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream,
+                           (const uint32_t*)h->stage_bits.ptr, d_mask, n);
+        HIP_TRY(h, hipGetLastError());
+        return SDFGPU_OK;
     });
 }
 
@@ -2517,7 +1246,6 @@ int sdfgpu_get_extrema(sdfgpu_handle h, double* out_max, double* out_min) {
 int sdfgpu_sweep_zy_tiered_device(sdfgpu_handle h, const uint8_t* d_filled, int64_t nxs, int64_t ny, int64_t nz,
                                   int32_t* d_plane_dsq, uint32_t* d_far, void* stream) {
     return rz_wrap(h, stream, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
         if (!d_filled || !d_plane_dsq) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null device pointer");
         if (int rc = check_dims(h, nxs, ny, nz)) return rc;
         HIP_TRY(h, hipSetDevice(h->device));
@@ -2570,7 +1298,6 @@ int sdfgpu_sweep_x_lines_device(sdfgpu_handle h, const int32_t* d_plane_dsq, int
                                 int64_t y_global, int64_t ny_global, double resolution, int add_virtual_border,
                                 float* d_out_sdf, uint32_t* d_maxdsq, void* stream) {
     return rz_wrap(h, stream, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
         if (!d_plane_dsq || !d_out_sdf || !d_maxdsq) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null device pointer");
         if (y_global < 0 || y_global + nys > ny_global) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "inconsistent slab geometry");
         if (int rc = check_resolution(h, resolution)) return rc;
@@ -2613,7 +1340,6 @@ int sdfgpu_sweep_x_device(sdfgpu_handle h, const int32_t* d_plane_dsq, int64_t h
                           int64_t x_global, int64_t nx_global, double resolution, int add_virtual_border,
                           float* d_out_sdf, uint32_t* d_maxdsq, uint32_t* d_status, void* stream) {
     return rz_wrap(h, stream, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
         if (!d_plane_dsq || !d_out_sdf || !d_maxdsq)
             return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null device pointer");
         if (halo_lo < 0 || halo_hi < 0 || x_global < 0 || x_global + nxs > nx_global)
@@ -2634,7 +1360,6 @@ int sdfgpu_sweep_x_device(sdfgpu_handle h, const int32_t* d_plane_dsq, int64_t h
 int sdfgpu_pack_bits_device(sdfgpu_handle h, const uint8_t* d_filled, int64_t n_rows, int64_t nz, uint32_t* d_bits,
                             void* stream) {
     return rz_wrap(h, stream, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
         if (!d_filled || !d_bits) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null device pointer");
         if (n_rows <= 0 || nz <= 0 || (nz % 32) != 0) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "pack_bits needs nz % 32 == 0");
         HIP_TRY(h, hipSetDevice(h->device));
@@ -2646,7 +1371,6 @@ int sdfgpu_dense_ball_device(sdfgpu_handle h, const uint32_t* d_bits, int64_t ro
                              int64_t ny, int64_t nz, double resolution, float* d_out_sdf, uint32_t* d_maxdsq,
                              uint32_t* d_uncertified, void* stream) {
     return rz_wrap(h, stream, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
         if (!d_bits || !d_out_sdf || !d_maxdsq || !d_uncertified) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null device pointer");
         if (out_lo < 0 || out_hi <= out_lo || out_hi > rows_x) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "inconsistent slab geometry");
         if (int rc = check_resolution(h, resolution)) return rc;
@@ -2669,7 +1393,6 @@ int sdfgpu_slab_dense_phase(sdfgpu_handle h, int phase, const uint8_t* d_mask_sl
                             uint32_t* d_bits_ext, int64_t halo_lo, int64_t halo_hi, double resolution, float* d_out,
                             uint32_t* d_small, void* stream) {
     return rz_wrap(h, stream, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
         if (!d_mask_slab || !d_bits_ext || !d_out || !d_small) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null device pointer");
         const int64_t hb = kBallR;
         if (nxs <= 0 || (halo_lo != 0 && halo_lo != hb) || (halo_hi != 0 && halo_hi != hb))
@@ -2721,7 +1444,6 @@ int sdfgpu_slab_dense_phase(sdfgpu_handle h, int phase, const uint8_t* d_mask_sl
 
 int sdfgpu_fold_extrema_device(sdfgpu_handle h, uint32_t* d_maxdsq, void* stream) {
     return rz_wrap(h, stream, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
         if (!d_maxdsq) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null device pointer");
         HIP_TRY(h, hipSetDevice(h->device));
         return fold_slots(h, d_maxdsq, (hipStream_t)stream);
@@ -2733,7 +1455,6 @@ int sdfgpu_build_tagged_cells(sdfgpu_handle h, const void* cells, size_t cell_st
                               int unknown_is_filled, int64_t nx, int64_t ny, int64_t nz, double resolution,
                               int add_virtual_border, float* out_sdf, double* out_max, double* out_min) {
     return rz_wrap(h, nullptr, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
         if (!out_sdf) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null host pointer");
         if (int rc = check_tagged_layout(h, cell_stride, occupancy_offset, object_id_offset)) return rc;
         if (object_mode < 0 || object_mode > 2 || n_object_ids < 0 || n_object_ids > 0x7fffffffLL ||
@@ -2889,7 +1610,6 @@ int get_extrema_batch(sdfgpu_handle h, int64_t batch, double* out_max, double* o
 int sdfgpu_build_batch_device(sdfgpu_handle h, const uint8_t* d_filled, int64_t batch, int64_t nx, int64_t ny, int64_t nz, double resolution,
                               const double* resolutions, int add_virtual_border, float* d_out_sdf, void* stream) {
     return rz_wrap(h, stream, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
         if (!d_filled || !d_out_sdf) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null device pointer");
         if (int rc = check_batch_args(h, batch, nx, ny, nz, resolution, resolutions)) return rc;
         return build_batch_impl(h, d_filled, nullptr, batch, nx, ny, nz, resolution, resolutions, add_virtual_border, d_out_sdf, (hipStream_t)stream);
@@ -2904,13 +1624,11 @@ int sdfgpu_get_extrema_batch(sdfgpu_handle h, int64_t batch, double* out_max, do
 int sdfgpu_build_batch(sdfgpu_handle h, const uint8_t* filled, int64_t batch, int64_t nx, int64_t ny, int64_t nz, double resolution,
                        const double* resolutions, int add_virtual_border, float* out_sdf, double* out_max, double* out_min) {
     return rz_wrap(h, nullptr, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
         if (!filled || !out_sdf) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null host pointer");
         if (int rc = check_batch_args(h, batch, nx, ny, nz, resolution, resolutions)) return rc;
         HIP_TRY(h, hipSetDevice(h->device));
         const size_t total = (size_t)(batch * nx * ny * nz);
-        h->tag_cached_bytes = 0;                        // (stage_in is about to be overwritten)
-        if (int rc = ensure(h, h->stage_in, total, "input staging")) return rc;
+        if (int rc = stage_input(h, total)) return rc;
         if (int rc = ensure(h, h->stage_out, total * 4, "output staging")) return rc;
         if (int rc = copy_from_host(h, h->stage_in.ptr, filled, total)) return rc;
         if (int rc = build_batch_impl(h, (const uint8_t*)h->stage_in.ptr, nullptr, batch, nx, ny, nz, resolution, resolutions, add_virtual_border,
@@ -2924,7 +1642,6 @@ int sdfgpu_build_tagged_objects(sdfgpu_handle h, const void* cells, size_t cell_
                                 const uint32_t* object_ids, int64_t n_object_ids, int unknown_is_filled, int64_t nx, int64_t ny, int64_t nz,
                                 double resolution, int add_virtual_border, float* out_sdf, double* out_max, double* out_min) {
     return rz_wrap(h, nullptr, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
         if (!out_sdf || !object_ids) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null host pointer");
         if (int rc = check_tagged_layout(h, cell_stride, occupancy_offset, object_id_offset)) return rc;
         if (int rc = check_batch_args(h, n_object_ids, nx, ny, nz, resolution, nullptr)) return rc;
@@ -2945,7 +1662,6 @@ int sdfgpu_build_tagged_objects(sdfgpu_handle h, const void* cells, size_t cell_
 int sdfgpu_gradient_batch_device(sdfgpu_handle h, const float* d_sdf, int64_t batch, int64_t nx, int64_t ny, int64_t nz, double resolution,
                                  const double* resolutions, int enable_edge_gradients, int f64, void* d_out, void* stream) {
     return rz_wrap(h, stream, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
         if (!d_sdf || !d_out) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null device pointer");
         if (batch < 1 || batch > ((int64_t)1 << 24)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "batch must be in 1 .. 2^24 (got %lld)", (long long)batch);
         for (int64_t b = 0; b < (resolutions ? batch : 1); ++b)
@@ -2995,7 +1711,6 @@ int sdfgpu_last_batch_info(sdfgpu_handle h, int* out_fast_path, int* out_launche
 int sdfgpu_classify_cells_device(sdfgpu_handle h, const void* d_cells, size_t cell_stride, size_t occupancy_offset,
                                  int unknown_is_filled, int64_t n_cells, uint8_t* d_mask, void* stream) {
     return rz_wrap(h, stream, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
         if (!d_cells || !d_mask || n_cells < 0) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "bad classify arguments");
         if (int rc = check_cell_layout(h, cell_stride, occupancy_offset)) return rc;
         HIP_TRY(h, hipSetDevice(h->device));
@@ -3012,7 +1727,6 @@ int sdfgpu_voxelize_points_device(sdfgpu_handle h, const float* d_points, int64_
                                   double resolution, int64_t nx, int64_t ny, int64_t nz, uint8_t* d_mask, int clear_first,
                                   void* stream) {
     return rz_wrap(h, stream, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
         if (!d_mask || !origin || (n_points > 0 && !d_points) || n_points < 0)
             return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "bad voxelize arguments");
         if (int rc = check_resolution(h, resolution)) return rc;
@@ -3033,7 +1747,6 @@ int sdfgpu_voxelize_points_bits_device(sdfgpu_handle h, const float* d_points, i
                                        double resolution, int64_t nx, int64_t ny, int64_t nz, uint32_t* d_bits, int clear_first,
                                        void* stream) {
     return rz_wrap(h, stream, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
         if (!d_bits || !origin || (n_points > 0 && !d_points) || n_points < 0)
             return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "bad voxelize arguments");
         if (int rc = check_resolution(h, resolution)) return rc;
@@ -3054,7 +1767,6 @@ int sdfgpu_gradient_device(sdfgpu_handle h, const float* d_sdf, int64_t nx, int6
                            double resolution, int enable_edge_gradients, void* d_out_grad, int out_is_f64,
                            void* stream) {
     return rz_wrap(h, stream, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
         if (!d_sdf || !d_out_grad) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null device pointer");
         if (int rc = check_resolution(h, resolution)) return rc;
         if (int rc = check_dims(h, nx, ny, nz)) return rc;
@@ -3091,7 +1803,6 @@ int sdfgpu_gradient_device(sdfgpu_handle h, const float* d_sdf, int64_t nx, int6
 int sdfgpu_gradient(sdfgpu_handle h, const float* sdf, int64_t nx, int64_t ny, int64_t nz, double resolution,
                     int enable_edge_gradients, void* out_grad, int out_is_f64) {
     return rz_wrap(h, nullptr, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
         if (!sdf || !out_grad) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null host pointer");
         if (int rc = check_resolution(h, resolution)) return rc;
         if (int rc = check_dims(h, nx, ny, nz)) return rc;
@@ -3102,8 +1813,7 @@ int sdfgpu_gradient(sdfgpu_handle h, const float* sdf, int64_t nx, int64_t ny, i
         const int64_t plane = ny * nz;
         const int64_t max_rows = std::max<int64_t>(1, ((int64_t)1 << 26) / std::max<int64_t>(plane, 1));   // <= 64 Mi voxels per chunk
         const int64_t rows = std::min<int64_t>(nx, max_rows);
-        h->tag_cached_bytes = 0;
-        if (int rc = ensure(h, h->stage_in, (size_t)(rows + 2) * plane * 4, "input staging")) return rc;
+        if (int rc = stage_input(h, (size_t)(rows + 2) * plane * 4)) return rc;
         if (int rc = ensure(h, h->stage_out, (size_t)(rows + 2) * plane * 3 * esz, "output staging")) return rc;
         (void)n;
         for (int64_t x0 = 0; x0 < nx; x0 += rows) {
@@ -3127,7 +1837,6 @@ int sdfgpu_query_points_device(sdfgpu_handle h, const float* d_sdf, int64_t nx, 
                                const double* d_points, int64_t n_points, int enable_edge_gradients, double* d_distance,
                                double* d_gradient, uint8_t* d_flags, void* stream) {
     return rz_wrap(h, stream, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
         if (!d_sdf || (n_points > 0 && !d_points)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null device pointer");
         if (n_points < 0) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "bad point count");
         if (int rc = check_resolution(h, resolution)) return rc;
@@ -3150,28 +1859,11 @@ int sdfgpu_query_points_device(sdfgpu_handle h, const float* d_sdf, int64_t nx, 
     });
 }
 
-int sdfgpu_device_malloc(sdfgpu_handle h, size_t bytes, void** out_ptr) {
-    if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-    if (!out_ptr) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "out_ptr is null");
-    *out_ptr = nullptr;
-    HIP_TRY(h, hipSetDevice(h->device));
-    return rz_malloc(h, "sdfgpu_device_malloc", h->redzone ? std::max<size_t>(bytes, 4) : std::max<size_t>(bytes, 256), out_ptr);
-}
-
-int sdfgpu_device_free(sdfgpu_handle h, void* ptr) {
-    if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-    if (!ptr) return SDFGPU_OK;
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (h->redzone) if (int rc = redzone_check(h, nullptr)) { (void)rz_free(h, ptr); return rc; }      // (last look at this buffer's zones)
-    return rz_free(h, ptr);
-}
-
 int sdfgpu_query_points(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t ny, int64_t nz, double resolution,
                         const double* world_to_grid, const double* grid_to_world_rotation, float oob_value,
                         const double* points, int64_t n_points, int enable_edge_gradients, double* out_distance,
                         double* out_gradient, uint8_t* out_flags) {
     return rz_wrap(h, nullptr, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
         if (!d_sdf || (n_points > 0 && !points)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
         if (n_points < 0) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "bad point count");
         if (int rc = check_resolution(h, resolution)) return rc;
@@ -3188,7 +1880,7 @@ int sdfgpu_query_points(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t
 
 int sdfgpu_debug_finish_table(sdfgpu_handle h, float* d_out, int64_t n, double resolution, int fast, uint32_t* out_slow_lanes) {
     return rz_wrap(h, nullptr, [&]() -> int {
-        if (!h || !d_out || n <= 0 || n > (1ll << 24)) return SDFGPU_ERR_INVALID_ARGUMENT;
+        if (!d_out || n <= 0 || n > (1ll << 24)) return SDFGPU_ERR_INVALID_ARGUMENT;
         HIP_TRY(h, hipSetDevice(h->device));
         if (int rc = ensure(h, h->tagids, 4, "object id list")) return rc;
         h->tag_cached_bytes = 0;
@@ -3201,11 +1893,6 @@ int sdfgpu_debug_finish_table(sdfgpu_handle h, float* d_out, int64_t n, double r
         if (out_slow_lanes) *out_slow_lanes = c;
         return SDFGPU_OK;
     });
-}
-
-int sdfgpu_redzone_check(sdfgpu_handle h, void* stream) {
-    if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-    return redzone_check(h, (hipStream_t)stream);
 }
 
 int sdfgpu_debug_copy_zsweep(sdfgpu_handle h, int16_t* out_host, int64_t n) {
@@ -3395,548 +2082,6 @@ int sdfgpu_set_tuning(sdfgpu_handle h, int rows_per_chunk_y, int rows_per_chunk_
     h->opt.tune_ty = rows_per_chunk_y;
     h->opt.tune_tx = rows_per_chunk_x;
     return SDFGPU_OK;
-}
-
-int sdfgpu_components_bits_device(sdfgpu_handle h, const uint32_t* d_bits, int64_t nx, int64_t ny, int64_t nz, uint32_t* d_labels,
-                                  uint32_t* out_count, void* stream) {
-    return rz_wrap(h, stream, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-        if (!d_bits || !d_labels || !out_count) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
-        if ((reinterpret_cast<uintptr_t>(d_bits) | reinterpret_cast<uintptr_t>(d_labels)) & 3)
-            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "d_bits and d_labels must be 4-byte aligned");
-        if (int rc = check_components_dims(h, nx, ny, nz)) return rc;
-        HIP_TRY(h, hipSetDevice(h->device));
-        return components_impl(h, d_bits, nx, ny, nz, d_labels, out_count, (hipStream_t)stream);
-    });
-}
-
-int sdfgpu_components(sdfgpu_handle h, const uint8_t* filled, int64_t nx, int64_t ny, int64_t nz, uint32_t* out_labels, uint32_t* out_count) {
-    return rz_wrap(h, nullptr, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-        if (!filled || !out_labels || !out_count) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
-        if (int rc = check_components_dims(h, nx, ny, nz)) return rc;
-        HIP_TRY(h, hipSetDevice(h->device));
-        if (int rc = components_host(h, Occupancy::of_mask(filled), nx, ny, nz, out_count)) return rc;
-        return copy_to_host(h, out_labels, h->stage_out.ptr, (size_t)(nx * ny * nz) * 4);
-    });
-}
-
-int sdfgpu_components_cells(sdfgpu_handle h, void* cells, size_t cell_stride, size_t occupancy_offset, size_t component_offset,
-                            int64_t nx, int64_t ny, int64_t nz, uint32_t* out_count) {
-    return rz_wrap(h, nullptr, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-        if (!cells || !out_count) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
-        if (int rc = check_component_layout(h, cell_stride, occupancy_offset, component_offset)) return rc;
-        if (int rc = check_components_dims(h, nx, ny, nz)) return rc;
-        HIP_TRY(h, hipSetDevice(h->device));
-        if (int rc = components_host(h, Occupancy::of_cells(cells, cell_stride, occupancy_offset, 0), nx, ny, nz, out_count)) return rc;
-        char* const rec = static_cast<char*>(cells) + component_offset;
-        // the drain team writes each label into its record (download offsets are multiples of 4: whole labels)
-        return staged_download_hip(h, h->stage_out.ptr, (size_t)(nx * ny * nz) * 4, nullptr, [=](const char* src, size_t goff, size_t len) {
-            char* dst = rec + (goff / 4) * cell_stride;
-            for (size_t o = 0; o < len; o += 4, dst += cell_stride) memcpy(dst, src + o, 4);
-        });
-    });
-}
-
-int sdfgpu_component_topology_device(sdfgpu_handle h, const uint32_t* d_labels, const uint32_t* d_select_bits, int64_t nx, int64_t ny,
-                                     int64_t nz, uint32_t max_label, int64_t* out_counts, void* stream) {
-    return rz_wrap(h, stream, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-        if (!d_labels) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
-        if ((reinterpret_cast<uintptr_t>(d_labels) | reinterpret_cast<uintptr_t>(d_select_bits)) & 3)
-            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "d_labels and d_select_bits must be 4-byte aligned");
-        if (int rc = check_topology_args(h, nx, ny, nz, max_label, out_counts)) return rc;
-        HIP_TRY(h, hipSetDevice(h->device));
-        return topology_impl(h, d_labels, d_select_bits, nx, ny, nz, max_label, out_counts, (hipStream_t)stream);
-    });
-}
-
-int sdfgpu_component_topology(sdfgpu_handle h, const uint32_t* labels, const uint8_t* select_mask, int64_t nx, int64_t ny, int64_t nz,
-                              uint32_t max_label, int64_t* out_counts) {
-    return rz_wrap(h, nullptr, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-        if (!labels) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
-        if (int rc = check_topology_args(h, nx, ny, nz, max_label, out_counts)) return rc;
-        HIP_TRY(h, hipSetDevice(h->device));
-        return topology_host(h, labels, select_mask, nullptr, 0, 0, 0, 7, nx, ny, nz, max_label, out_counts);
-    });
-}
-
-int sdfgpu_component_topology_cells(sdfgpu_handle h, const void* cells, size_t cell_stride, size_t occupancy_offset, size_t component_offset,
-                                    int64_t nx, int64_t ny, int64_t nz, int class_mask, uint32_t max_label, int64_t* out_counts) {
-    return rz_wrap(h, nullptr, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-        if (!cells) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
-        if (int rc = check_component_layout(h, cell_stride, occupancy_offset, component_offset)) return rc;
-        if (class_mask < 1 || class_mask > 7)
-            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "class_mask must be a nonzero combination of FILLED (1), EMPTY (2) and UNKNOWN (4)");
-        if (int rc = check_topology_args(h, nx, ny, nz, max_label, out_counts)) return rc;
-        HIP_TRY(h, hipSetDevice(h->device));
-        return topology_host(h, nullptr, nullptr, cells, cell_stride, occupancy_offset, component_offset, class_mask, nx, ny, nz, max_label,
-                             out_counts);
-    });
-}
-
-int sdfgpu_component_surfaces_device(sdfgpu_handle h, const uint32_t* d_labels, const uint32_t* d_select_bits, int64_t nx, int64_t ny,
-                                     int64_t nz, uint32_t max_label, int64_t* out_counts, uint32_t* d_indices, int64_t capacity,
-                                     int64_t* out_total, uint32_t* d_surface_bits, void* stream) {
-    return rz_wrap(h, stream, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-        if (!d_labels) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
-        if ((reinterpret_cast<uintptr_t>(d_labels) | reinterpret_cast<uintptr_t>(d_select_bits) | reinterpret_cast<uintptr_t>(d_indices) |
-             reinterpret_cast<uintptr_t>(d_surface_bits)) & 3)
-            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "d_labels, d_select_bits, d_indices and d_surface_bits must be 4-byte aligned");
-        if (int rc = check_surfaces_args(h, nx, ny, nz, max_label, out_counts, d_indices != nullptr, capacity, out_total)) return rc;
-        HIP_TRY(h, hipSetDevice(h->device));
-        return surfaces_impl(h, d_labels, d_select_bits, nx, ny, nz, max_label, out_counts, d_indices, nullptr, capacity, out_total,
-                             d_surface_bits, (hipStream_t)stream);
-    });
-}
-
-int sdfgpu_component_surfaces(sdfgpu_handle h, const uint32_t* labels, const uint8_t* select_mask, int64_t nx, int64_t ny, int64_t nz,
-                              uint32_t max_label, int64_t* out_counts, uint32_t* out_indices, int64_t capacity, int64_t* out_total) {
-    return rz_wrap(h, nullptr, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-        if (!labels) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
-        if (int rc = check_surfaces_args(h, nx, ny, nz, max_label, out_counts, out_indices != nullptr, capacity, out_total)) return rc;
-        HIP_TRY(h, hipSetDevice(h->device));
-        return surfaces_host(h, labels, select_mask, nullptr, 0, 0, 0, 7, nx, ny, nz, max_label, out_counts, out_indices, capacity, out_total);
-    });
-}
-
-int sdfgpu_component_surfaces_cells(sdfgpu_handle h, const void* cells, size_t cell_stride, size_t occupancy_offset, size_t component_offset,
-                                    int64_t nx, int64_t ny, int64_t nz, int class_mask, uint32_t max_label, int64_t* out_counts,
-                                    uint32_t* out_indices, int64_t capacity, int64_t* out_total) {
-    return rz_wrap(h, nullptr, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-        if (!cells) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
-        if (int rc = check_component_layout(h, cell_stride, occupancy_offset, component_offset)) return rc;
-        if (class_mask < 1 || class_mask > 7)
-            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "class_mask must be a nonzero combination of FILLED (1), EMPTY (2) and UNKNOWN (4)");
-        if (int rc = check_surfaces_args(h, nx, ny, nz, max_label, out_counts, out_indices != nullptr, capacity, out_total)) return rc;
-        HIP_TRY(h, hipSetDevice(h->device));
-        return surfaces_host(h, nullptr, nullptr, cells, cell_stride, occupancy_offset, component_offset, class_mask, nx, ny, nz, max_label,
-                             out_counts, out_indices, capacity, out_total);
-    });
-}
-
-int sdfgpu_local_extrema_device(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t ny, int64_t nz, double resolution,
-                                const double q_and_qinv[8], uint32_t* d_extremum, void* stream) {
-    return rz_wrap(h, stream, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-        if (!d_sdf || !d_extremum) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
-        if ((reinterpret_cast<uintptr_t>(d_sdf) | reinterpret_cast<uintptr_t>(d_extremum)) & 3)
-            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "d_sdf and d_extremum must be 4-byte aligned");
-        if (int rc = check_convex_args(h, nx, ny, nz, resolution, q_and_qinv)) return rc;
-        HIP_TRY(h, hipSetDevice(h->device));
-        return extrema_impl(h, d_sdf, nx, ny, nz, resolution, q_and_qinv, d_extremum, (hipStream_t)stream);
-    });
-}
-
-int sdfgpu_local_extrema(sdfgpu_handle h, const float* sdf, int64_t nx, int64_t ny, int64_t nz, double resolution,
-                         const double q_and_qinv[8], uint32_t* out_extremum) {
-    return rz_wrap(h, nullptr, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-        if (!sdf || !out_extremum) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
-        if (int rc = check_convex_args(h, nx, ny, nz, resolution, q_and_qinv)) return rc;
-        HIP_TRY(h, hipSetDevice(h->device));
-        const size_t n = (size_t)(nx * ny * nz);
-        if (int rc = ensure(h, h->cx_field, n * 4, "convex field")) return rc;
-        if (int rc = ensure(h, h->stage_out, n * 4, "output staging")) return rc;
-        if (int rc = copy_from_host(h, h->cx_field.ptr, sdf, n * 4)) return rc;
-        if (int rc = extrema_impl(h, (const float*)h->cx_field.ptr, nx, ny, nz, resolution, q_and_qinv, (uint32_t*)h->stage_out.ptr, nullptr))
-            return rc;
-        return copy_to_host(h, out_extremum, h->stage_out.ptr, n * 4);
-    });
-}
-
-int sdfgpu_convex_segments_cells(sdfgpu_handle h, void* cells, size_t cell_stride, size_t occupancy_offset, size_t object_id_offset,
-                                 size_t segment_offset, int64_t nx, int64_t ny, int64_t nz, double resolution,
-                                 const double q_and_qinv[8], double connected_threshold, int add_virtual_border, uint32_t* out_count) {
-    return rz_wrap(h, nullptr, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-        if (!cells || !out_count) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
-        if (cell_stride < 12 || (cell_stride % 4) || (occupancy_offset % 4) || (object_id_offset % 4) || (segment_offset % 4) ||
-            occupancy_offset + 4 > cell_stride || object_id_offset + 4 > cell_stride || segment_offset + 4 > cell_stride ||
-            occupancy_offset == object_id_offset || segment_offset == occupancy_offset || segment_offset == object_id_offset)
-            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT,
-                        "cell_stride / occupancy_offset / object_id_offset / segment_offset must be 4-byte aligned, in range and distinct");
-        if (int rc = check_convex_args(h, nx, ny, nz, resolution, q_and_qinv)) return rc;
-        if (int rc = check_dims(h, nx, ny, nz)) return rc;                     // (the SDF build's own limits)
-        HIP_TRY(h, hipSetDevice(h->device));
-        const int64_t n = nx * ny * nz;
-        const CxPlan plan = cx_plan(nx, ny, nz);
-        h->tag_cached_bytes = 0;
-        if (int rc = ensure(h, h->stage_in, (size_t)n * cell_stride, "input staging")) return rc;
-        if (int rc = ensure(h, h->stage_out, (size_t)n * 4, "output staging")) return rc;
-        if (int rc = ensure(h, h->tagmask, (size_t)n, "tagged-object mask")) return rc;
-        if (int rc = ensure(h, h->tagids, 4, "object id list")) return rc;
-        if (int rc = ensure(h, h->cx_field, (size_t)n * 4, "convex field")) return rc;
-        if (int rc = ensure(h, h->cx_scratch, plan.scratch_bytes, "convex scratch")) return rc;
-        if (int rc = copy_from_host(h, h->stage_in.ptr, cells, (size_t)n * cell_stride)) return rc;
-        if (int rc = convex_sdf(h, cell_stride, occupancy_offset, object_id_offset, nx, ny, nz, resolution, add_virtual_border)) return rc;
-        uint32_t* d_ext = (uint32_t*)h->cx_field.ptr;                          // (the named-object SDF is consumed by now)
-        if (int rc = extrema_impl(h, (const float*)h->stage_out.ptr, nx, ny, nz, resolution, q_and_qinv, d_ext, nullptr)) return rc;
-        uint32_t* d_labels = (uint32_t*)h->stage_out.ptr;                      // (the SDF is consumed by the extrema)
-        HIP_TRY(h, cx_segments(plan, d_ext, (const char*)h->stage_in.ptr, cell_stride, occupancy_offset, object_id_offset, resolution,
-                               connected_threshold, d_labels, h->cx_scratch.ptr, nullptr));
-        uint32_t count = 0;
-        HIP_TRY(h, hipMemcpyAsync(&count, static_cast<char*>(h->cx_scratch.ptr) + plan.off_stats + offsetof(CxStats, count), 4,
-                                  hipMemcpyDeviceToHost, nullptr));
-        HIP_TRY(h, hipStreamSynchronize(nullptr));
-        char* const rec = static_cast<char*>(cells) + segment_offset;
-        if (int rc = staged_download_hip(h, d_labels, (size_t)n * 4, nullptr, [=](const char* src, size_t goff, size_t len) {
-                char* dst = rec + (goff / 4) * cell_stride;
-                for (size_t o = 0; o < len; o += 4, dst += cell_stride) memcpy(dst, src + o, 4);
-            }))
-            return rc;
-        *out_count = count;
-        return SDFGPU_OK;
-    });
-}
-
-int sdfgpu_convex_last_info(sdfgpu_handle h, int* out_rounds, uint32_t* out_cycles, uint32_t* out_longest_cycle,
-                            uint32_t* out_longest_entry) {
-    if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-    if (h->cx_stats_off == 0 || !h->cx_scratch.ptr) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "no local extrema computed on this handle");
-    HIP_TRY(h, hipSetDevice(h->device));
-    static thread_local CxStats st;                            // (336 KiB: not on the stack)
-    HIP_TRY(h, hipDeviceSynchronize());
-    HIP_TRY(h, hipMemcpy(&st, static_cast<char*>(h->cx_scratch.ptr) + h->cx_stats_off, sizeof st, hipMemcpyDeviceToHost));
-    if (out_rounds) *out_rounds = h->cx_rounds;
-    if (out_cycles) *out_cycles = cx_row_sum(st.cycles);
-    if (out_longest_cycle) *out_longest_cycle = st.longest_cycle[0];
-    if (out_longest_entry) *out_longest_entry = st.longest_entry[0];
-    return SDFGPU_OK;
-}
-
-int sdfgpu_project_step_limit(int64_t nx, int64_t ny, int64_t nz, double stepsize_multiplier, int max_steps, int* out_limit) {
-    if (!out_limit || nx <= 0 || ny <= 0 || nz <= 0) return SDFGPU_ERR_INVALID_ARGUMENT;
-    const int limit = project_step_limit(nx, ny, nz, stepsize_multiplier, max_steps);
-    if (limit < 0) return SDFGPU_ERR_INVALID_ARGUMENT;
-    *out_limit = limit;
-    return SDFGPU_OK;
-}
-
-namespace {
-int check_project_args(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t ny, int64_t nz, double resolution,
-                       const double* world_to_grid, const double* grid_to_world, double stepsize_multiplier, int max_steps, int mode,
-                       const double* points, int64_t n_points, const double* out_points, ProjectArgs& a) {
-    if (!d_sdf) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "projection: null field pointer");
-    if (n_points < 0 || n_points > ((int64_t)1 << 40)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "projection: point count %lld out of range [0, 2^40]", (long long)n_points);
-    if (n_points > 0 && (!points || !out_points)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "projection: null points or out_points");
-    if (!world_to_grid || !grid_to_world) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "projection: world_to_grid and grid_to_world are required");
-    if (nx <= 0 || ny <= 0 || nz <= 0 || nx > INT64_MAX / ny || nx * ny > INT64_MAX / nz)
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "projection: unsupported grid %lld x %lld x %lld", (long long)nx, (long long)ny, (long long)nz);
-    if (!(resolution > 0.0) || !std::isfinite(resolution)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "projection: resolution must be positive and finite");
-    if (mode != SDFGPU_PROJECT_OUT_OF_COLLISION && mode != SDFGPU_PROJECT_INTO_VALID_VOLUME)
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "projection: unknown mode %d", mode);
-    const int limit = project_step_limit(nx, ny, nz, stepsize_multiplier, max_steps);
-    if (limit < 0) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "projection: stepsize_multiplier must be positive and finite and max_steps >= 0");
-    a = ProjectArgs{};
-    a.sdf = d_sdf; a.n = n_points; a.nx = nx; a.ny = ny; a.nz = nz;
-    a.step_limit = limit; a.mode = mode;
-    for (int i = 0; i < 12; ++i) { a.w2g[i] = world_to_grid[i]; a.g2w[i] = grid_to_world[i]; }
-    return SDFGPU_OK;
-}
-}  // namespace
-
-int sdfgpu_project_points_device(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t ny, int64_t nz, double resolution,
-                                 const double world_to_grid[12], const double grid_to_world[12], double minimum_distance,
-                                 double stepsize_multiplier, int max_steps, int mode, const double* d_points, int64_t n_points,
-                                 double* d_out_points, uint8_t* d_out_status, int32_t* d_out_steps, void* stream) {
-    return rz_wrap(h, stream, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-        ProjectArgs a;
-        if (int rc = check_project_args(h, d_sdf, nx, ny, nz, resolution, world_to_grid, grid_to_world, stepsize_multiplier, max_steps,
-                                        mode, d_points, n_points, d_out_points, a)) return rc;
-        if (n_points == 0) return SDFGPU_OK;
-        HIP_TRY(h, hipSetDevice(h->device));
-        a.points = d_points; a.out = d_out_points; a.status = d_out_status; a.steps = d_out_steps;
-        project_prepare(a, resolution, minimum_distance, stepsize_multiplier);
-        HIP_TRY(h, project_launch(a, (hipStream_t)stream));
-        return SDFGPU_OK;
-    });
-}
-
-int sdfgpu_project_points(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t ny, int64_t nz, double resolution,
-                          const double world_to_grid[12], const double grid_to_world[12], double minimum_distance,
-                          double stepsize_multiplier, int max_steps, int mode, const double* points, int64_t n_points,
-                          double* out_points, uint8_t* out_status, int32_t* out_steps) {
-    return rz_wrap(h, nullptr, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-        ProjectArgs a;
-        if (int rc = check_project_args(h, d_sdf, nx, ny, nz, resolution, world_to_grid, grid_to_world, stepsize_multiplier, max_steps,
-                                        mode, points, n_points, out_points, a)) return rc;
-        if (n_points == 0) return SDFGPU_OK;
-        HIP_TRY(h, hipSetDevice(h->device));
-        // points | out points | steps | status
-        return with_staged_points(h, points, n_points, {24, 4, 1}, {out_points, out_steps, out_status}, [&](const double* d_points, char* const (&d)[3]) -> int {
-            a.points = d_points; a.out = (double*)d[0]; a.steps = (int32_t*)d[1]; a.status = (uint8_t*)d[2];
-            project_prepare(a, resolution, minimum_distance, stepsize_multiplier);
-            HIP_TRY(h, project_launch(a, nullptr));
-            return SDFGPU_OK;
-        });
-    });
-}
-
-namespace {
-int check_query_gradients_args(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t ny, int64_t nz, double resolution,
-                               const double* world_to_grid, int kind, double window, const double* points, int64_t n_points,
-                               GradientQueryArgs& a) {
-    if (!d_sdf) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "gradient query: null field pointer");
-    if (n_points < 0 || n_points > ((int64_t)1 << 40)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "gradient query: point count %lld out of range [0, 2^40]", (long long)n_points);
-    if (n_points > 0 && !points) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "gradient query: null points");
-    if (!world_to_grid) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "gradient query: world_to_grid is required");
-    if (nx <= 0 || ny <= 0 || nz <= 0 || nx > INT64_MAX / ny || nx * ny > INT64_MAX / nz)
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "gradient query: unsupported grid %lld x %lld x %lld", (long long)nx, (long long)ny, (long long)nz);
-    if (!(resolution > 0.0) || !std::isfinite(resolution)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "gradient query: resolution must be positive and finite");
-    if (kind != SDFGPU_QUERY_SMOOTH_GRADIENT && kind != SDFGPU_QUERY_AUTODIFF_GRADIENT && kind != SDFGPU_QUERY_DISTANCE_TO_BOUNDARY)
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "gradient query: unknown kind %d", kind);
-    if (!std::isfinite(window)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "gradient query: the window must be finite");
-    a = GradientQueryArgs{};
-    a.sdf = d_sdf; a.n = n_points; a.nx = nx; a.ny = ny; a.nz = nz; a.kind = kind;
-    for (int i = 0; i < 12; ++i) a.w2g[i] = world_to_grid[i];
-    return SDFGPU_OK;
-}
-}  // namespace
-
-int sdfgpu_query_gradients_device(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t ny, int64_t nz, double resolution,
-                                  const double world_to_grid[12], float oob_value, int kind, double window, const double* d_points,
-                                  int64_t n_points, double* d_value, double* d_gradient, uint8_t* d_status, void* stream) {
-    return rz_wrap(h, stream, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-        GradientQueryArgs a;
-        if (int rc = check_query_gradients_args(h, d_sdf, nx, ny, nz, resolution, world_to_grid, kind, window, d_points, n_points, a)) return rc;
-        if (n_points == 0 || (!d_value && !d_gradient && !d_status)) return SDFGPU_OK;
-        HIP_TRY(h, hipSetDevice(h->device));
-        a.points = d_points; a.value = d_value; a.gradient = d_gradient; a.status = d_status;
-        query_gradients_prepare(a, resolution, window, oob_value);
-        HIP_TRY(h, query_gradients_launch(a, (hipStream_t)stream));
-        return SDFGPU_OK;
-    });
-}
-
-int sdfgpu_query_gradients(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t ny, int64_t nz, double resolution,
-                           const double world_to_grid[12], float oob_value, int kind, double window, const double* points,
-                           int64_t n_points, double* out_value, double* out_gradient, uint8_t* out_status) {
-    return rz_wrap(h, nullptr, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-        GradientQueryArgs a;
-        if (int rc = check_query_gradients_args(h, d_sdf, nx, ny, nz, resolution, world_to_grid, kind, window, points, n_points, a)) return rc;
-        if (n_points == 0 || (!out_value && !out_gradient && !out_status)) return SDFGPU_OK;
-        HIP_TRY(h, hipSetDevice(h->device));
-        // points | gradient | value | status
-        return with_staged_points(h, points, n_points, {24, 8, 1}, {out_gradient, out_value, out_status}, [&](const double* d_points, char* const (&d)[3]) -> int {
-            a.points = d_points; a.gradient = (double*)d[0]; a.value = (double*)d[1]; a.status = (uint8_t*)d[2];
-            query_gradients_prepare(a, resolution, window, oob_value);
-            HIP_TRY(h, query_gradients_launch(a, nullptr));
-            return SDFGPU_OK;
-        });
-    });
-}
-
-int sdfgpu_resample_cells_device(sdfgpu_handle h, const void* d_src, size_t cell_bytes, int64_t nx, int64_t ny, int64_t nz,
-                                 const double src_cell[3], const double origin[16], const double dst_inverse_origin[16],
-                                 const double dst_inv_cell[3], void* d_dst, int64_t mx, int64_t my, int64_t mz, const void* fill_cell,
-                                 uint64_t* out_cells_written, void* stream) {
-    return rz_wrap(h, stream, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-        ResampleArgs a;
-        if (int rc = check_resample_args(h, d_src, cell_bytes, nx, ny, nz, src_cell, origin, dst_inverse_origin, dst_inv_cell, d_dst, mx, my,
-                                         mz, fill_cell, a)) return rc;
-        if ((reinterpret_cast<uintptr_t>(d_src) | reinterpret_cast<uintptr_t>(d_dst)) & 3)
-            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "resample: d_src and d_dst must be 4-byte aligned");
-        HIP_TRY(h, hipSetDevice(h->device));
-        a.src = d_src; a.dst = d_dst;
-        return resample_impl(h, a, out_cells_written, (hipStream_t)stream);
-    });
-}
-
-int sdfgpu_debug_resample_times(sdfgpu_handle h, double* out_winner_ms, double* out_gather_ms) {
-    if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-    if (!out_winner_ms || !out_gather_ms) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
-    if (!h->rs_timed) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "no resample timed on this handle (option \"resample_timing\")");
-    HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, hipEventSynchronize(h->rs_time_ev[2]));
-    float a = 0.0f, b = 0.0f;
-    HIP_TRY(h, hipEventElapsedTime(&a, h->rs_time_ev[0], h->rs_time_ev[1]));
-    HIP_TRY(h, hipEventElapsedTime(&b, h->rs_time_ev[1], h->rs_time_ev[2]));
-    *out_winner_ms = (double)a;
-    *out_gather_ms = (double)b;
-    return SDFGPU_OK;
-}
-
-int sdfgpu_resample_cells(sdfgpu_handle h, const void* src, size_t cell_bytes, int64_t nx, int64_t ny, int64_t nz, const double src_cell[3],
-                          const double origin[16], const double dst_inverse_origin[16], const double dst_inv_cell[3], void* dst, int64_t mx,
-                          int64_t my, int64_t mz, const void* fill_cell, uint64_t* out_cells_written) {
-    return rz_wrap(h, nullptr, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-        ResampleArgs a;
-        if (int rc = check_resample_args(h, src, cell_bytes, nx, ny, nz, src_cell, origin, dst_inverse_origin, dst_inv_cell, dst, mx, my, mz,
-                                         fill_cell, a)) return rc;
-        HIP_TRY(h, hipSetDevice(h->device));
-        // the null stream throughout: source records through the cell staging, the result through the field staging
-        const size_t src_bytes = (size_t)a.n_src * cell_bytes, dst_bytes = (size_t)a.n_dst * cell_bytes;
-        h->tag_cached_bytes = 0;                        // (stage_in is about to be overwritten)
-        if (int rc = ensure(h, h->stage_in, src_bytes, "input staging")) return rc;
-        if (int rc = ensure(h, h->stage_out, dst_bytes, "output staging")) return rc;
-        if (int rc = copy_from_host(h, h->stage_in.ptr, src, src_bytes)) return rc;
-        a.src = h->stage_in.ptr; a.dst = h->stage_out.ptr;
-        if (int rc = resample_impl(h, a, out_cells_written, nullptr)) return rc;
-        return copy_to_host(h, dst, h->stage_out.ptr, dst_bytes);
-    });
-}
-
-int sdfgpu_display_select_cells_device(sdfgpu_handle h, const void* d_cells, size_t cell_stride, size_t occupancy_offset, size_t key_offset,
-                                       int64_t nx, int64_t ny, int64_t nz, int rule, int class_mask, int surface_only,
-                                       const uint32_t* draw_keys, int64_t n_draw_keys, int draw_zero, int grouped, uint32_t* d_indices,
-                                       uint32_t* d_keys, int64_t capacity, int64_t* out_total, uint32_t* d_group_keys,
-                                       uint32_t* d_group_offsets, int64_t group_capacity, int64_t* out_groups, void* stream) {
-    return rz_wrap(h, stream, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-        DpSelect sel;
-        if (int rc = check_display_cells(h, d_cells, cell_stride, occupancy_offset, key_offset, nx, ny, nz, rule, class_mask, sel)) return rc;
-        if (reinterpret_cast<uintptr_t>(d_cells) & 3) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: d_cells must be 4-byte aligned");
-        DisplayRequest rq;
-        rq.rule = rule == SDFGPU_DISPLAY_OCCUPANCY ? kDpRuleOccupancy : kDpRuleKeyField;
-        rq.draw_keys = draw_keys; rq.n_draw_keys = n_draw_keys; rq.grouped = grouped != 0;
-        rq.indices = d_indices; rq.keys = d_keys; rq.capacity = capacity; rq.out_total = out_total;
-        rq.group_keys = d_group_keys; rq.group_offsets = d_group_offsets; rq.group_capacity = group_capacity; rq.out_groups = out_groups;
-        if (int rc = check_display_request(h, rq)) return rc;
-        HIP_TRY(h, hipSetDevice(h->device));
-        sel.src.cells = static_cast<const char*>(d_cells);
-        sel.surface_only = surface_only != 0;
-        sel.draw_zero = draw_zero != 0;
-        return display_select_impl(h, sel, rq, (hipStream_t)stream);
-    });
-}
-
-int sdfgpu_display_select_cells(sdfgpu_handle h, const void* cells, size_t cell_stride, size_t occupancy_offset, size_t key_offset, int64_t nx,
-                                int64_t ny, int64_t nz, int rule, int class_mask, int surface_only, const uint32_t* draw_keys,
-                                int64_t n_draw_keys, int draw_zero, int grouped, uint32_t* out_indices, uint32_t* out_keys, int64_t capacity,
-                                int64_t* out_total, uint32_t* out_group_keys, uint32_t* out_group_offsets, int64_t group_capacity,
-                                int64_t* out_groups) {
-    return rz_wrap(h, nullptr, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-        DpSelect sel;
-        if (int rc = check_display_cells(h, cells, cell_stride, occupancy_offset, key_offset, nx, ny, nz, rule, class_mask, sel)) return rc;
-        DisplayRequest rq;
-        rq.rule = rule == SDFGPU_DISPLAY_OCCUPANCY ? kDpRuleOccupancy : kDpRuleKeyField;
-        rq.draw_keys = draw_keys; rq.n_draw_keys = n_draw_keys; rq.grouped = grouped != 0; rq.to_host = true;
-        rq.indices = out_indices; rq.keys = out_keys; rq.capacity = capacity; rq.out_total = out_total;
-        rq.group_keys = out_group_keys; rq.group_offsets = out_group_offsets; rq.group_capacity = group_capacity; rq.out_groups = out_groups;
-        if (int rc = check_display_request(h, rq)) return rc;
-        HIP_TRY(h, hipSetDevice(h->device));
-        const size_t bytes = (size_t)sel.n * cell_stride;       // the null stream throughout: records through the cell staging
-        h->tag_cached_bytes = 0;                                // (stage_in is about to be overwritten)
-        if (int rc = ensure(h, h->stage_in, bytes, "input staging")) return rc;
-        if (int rc = copy_from_host(h, h->stage_in.ptr, cells, bytes)) return rc;
-        sel.src.cells = static_cast<const char*>(h->stage_in.ptr);
-        sel.surface_only = surface_only != 0;
-        sel.draw_zero = draw_zero != 0;
-        return display_select_impl(h, sel, rq, nullptr);
-    });
-}
-
-int sdfgpu_display_select_sdf_device(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t ny, int64_t nz, uint32_t* d_indices,
-                                     int64_t capacity, int64_t* out_total, void* stream) {
-    return rz_wrap(h, stream, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-        DpSelect sel;
-        if (int rc = check_display_sdf(h, d_sdf, nx, ny, nz, sel)) return rc;
-        if (reinterpret_cast<uintptr_t>(d_sdf) & 3) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: d_sdf must be 4-byte aligned");
-        DisplayRequest rq;
-        rq.rule = kDpRuleSdfNonPositive;
-        rq.indices = d_indices; rq.capacity = capacity; rq.out_total = out_total;
-        if (int rc = check_display_request(h, rq)) return rc;
-        HIP_TRY(h, hipSetDevice(h->device));
-        sel.src.cells = reinterpret_cast<const char*>(d_sdf);
-        return display_select_impl(h, sel, rq, (hipStream_t)stream);
-    });
-}
-
-int sdfgpu_display_select_sdf(sdfgpu_handle h, const float* sdf, int64_t nx, int64_t ny, int64_t nz, uint32_t* out_indices, int64_t capacity,
-                              int64_t* out_total) {
-    return rz_wrap(h, nullptr, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-        DpSelect sel;
-        if (int rc = check_display_sdf(h, sdf, nx, ny, nz, sel)) return rc;
-        DisplayRequest rq;
-        rq.rule = kDpRuleSdfNonPositive;
-        rq.to_host = true;
-        rq.indices = out_indices; rq.capacity = capacity; rq.out_total = out_total;
-        if (int rc = check_display_request(h, rq)) return rc;
-        HIP_TRY(h, hipSetDevice(h->device));
-        h->tag_cached_bytes = 0;
-        if (int rc = ensure(h, h->stage_in, (size_t)sel.n * 4, "input staging")) return rc;
-        if (int rc = copy_from_host(h, h->stage_in.ptr, sdf, (size_t)sel.n * 4)) return rc;
-        sel.src.cells = static_cast<const char*>(h->stage_in.ptr);
-        return display_select_impl(h, sel, rq, nullptr);
-    });
-}
-
-int sdfgpu_display_expand_device(sdfgpu_handle h, const uint32_t* d_indices, const uint32_t* d_keys, int64_t count, int64_t nx, int64_t ny,
-                                 int64_t nz, const double cell_sizes[3], double* d_points, float* d_colors, const float* d_color_table,
-                                 int64_t table_entries, const float default_color[4], void* stream) {
-    return rz_wrap(h, stream, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-        if (!d_indices || !cell_sizes || (!d_points && !d_colors)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: null pointer");
-        if (d_colors && (!default_color || table_entries < 0 || table_entries > (int64_t)0xFFFFFFFFll || (table_entries > 0 && !d_color_table)))
-            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: colours need a default colour and a table of [0, 2^32) entries");
-        if (count < 0 || count > (int64_t)0xFFFFFFFFll)
-            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: count must be in [0, 2^32) (got %lld)", (long long)count);
-        if (int rc = check_display_dims(h, nx, ny, nz)) return rc;
-        if ((reinterpret_cast<uintptr_t>(d_indices) | reinterpret_cast<uintptr_t>(d_keys) | reinterpret_cast<uintptr_t>(d_points) |
-             reinterpret_cast<uintptr_t>(d_colors) | reinterpret_cast<uintptr_t>(d_color_table)) & 3)
-            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: device pointers must be 4-byte aligned");
-        HIP_TRY(h, hipSetDevice(h->device));
-        DpExpand a;
-        a.idx = d_indices; a.keys = d_keys; a.count = (uint64_t)count;
-        a.ny = (uint32_t)ny; a.nz = (uint32_t)nz;
-        for (int i = 0; i < 3; ++i) a.cell[i] = cell_sizes[i];
-        a.points = reinterpret_cast<uint32_t*>(d_points);
-        a.colors = d_colors;
-        if (d_colors) {
-            a.table = d_color_table; a.table_len = (uint32_t)table_entries;
-            for (int i = 0; i < 4; ++i) a.fallback[i] = default_color[i];
-        }
-        HIP_TRY(h, dp_launch_expand(a, (hipStream_t)stream));
-        return SDFGPU_OK;
-    });
-}
-
-int sdfgpu_display_sdf_colors_device(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t ny, int64_t nz, float alpha, float* d_colors,
-                                     void* stream) {
-    return rz_wrap(h, stream, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-        DpSelect sel;
-        if (!d_colors) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: null pointer");
-        if (int rc = check_display_sdf(h, d_sdf, nx, ny, nz, sel)) return rc;
-        if (std::isnan(alpha)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: alpha must not be NaN");
-        if ((reinterpret_cast<uintptr_t>(d_sdf) | reinterpret_cast<uintptr_t>(d_colors)) & 3)
-            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: d_sdf and d_colors must be 4-byte aligned");
-        HIP_TRY(h, hipSetDevice(h->device));
-        return display_sdf_colors_impl(h, d_sdf, sel.n, alpha, d_colors, (hipStream_t)stream);
-    });
-}
-
-int sdfgpu_display_sdf_colors(sdfgpu_handle h, const float* sdf, int64_t nx, int64_t ny, int64_t nz, float alpha, float* out_colors) {
-    return rz_wrap(h, nullptr, [&]() -> int {
-        if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-        DpSelect sel;
-        if (!out_colors) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: null pointer");
-        if (int rc = check_display_sdf(h, sdf, nx, ny, nz, sel)) return rc;
-        if (std::isnan(alpha)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: alpha must not be NaN");
-        HIP_TRY(h, hipSetDevice(h->device));
-        h->tag_cached_bytes = 0;
-        if (int rc = ensure(h, h->stage_in, (size_t)sel.n * 4, "input staging")) return rc;
-        if (int rc = ensure(h, h->stage_out, (size_t)sel.n * 16, "output staging")) return rc;
-        if (int rc = copy_from_host(h, h->stage_in.ptr, sdf, (size_t)sel.n * 4)) return rc;
-        if (int rc = display_sdf_colors_impl(h, (const float*)h->stage_in.ptr, sel.n, alpha, (float*)h->stage_out.ptr, nullptr)) return rc;
-        return copy_to_host(h, out_colors, h->stage_out.ptr, (size_t)sel.n * 16);
-    });
 }
 
 }  // extern "C"

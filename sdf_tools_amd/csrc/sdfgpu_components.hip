@@ -1,11 +1,15 @@
 // sdfgpu_components.hip -- the connected-components kernels (sdfgpu_components.hpp) and their launcher.  Compiled beside
-// sdfgpu.hip and linked into the same libsdfgpu.so (sdf_tools_amd/build.py); the C ABI entry points live in sdfgpu.hip.
+// sdfgpu.hip and linked into the same libsdfgpu.so (sdf_tools_amd/build.py).
+// The family's host orchestration and C ABI entry points (sdfgpu_components*) are at the end of this file, over the handle of
+// sdfgpu_context.hpp.
 //
 // Union-find invariant, relied on by every find below: a label word only ever DECREASES, and it never holds a value above its
 // own index (a provisional label is the index of a tile-local root <= the voxel; a link stores a smaller root into a larger
 // one with atomicMin).  Every parent chain is therefore strictly decreasing until it meets a self-loop, so every find ends,
 // and the root of a component is its minimum linear index -- the voxel at which the reference's x -> y -> z scan starts it.
+#include "sdfgpu_context.hpp"
 #include "sdfgpu_components.hpp"
+#include "sdfgpu.h"
 
 #include <algorithm>
 
@@ -348,3 +352,78 @@ hipError_t cc_launch(const CcPlan& p, const uint32_t* d_bits, uint32_t* d_labels
 }
 
 }  // namespace sdfgpu
+
+// ---- host side: argument checks, orchestration and the C ABI entry points -----------------------------------------------------------
+using namespace sdfgpu;
+
+namespace {
+
+// ---- connected components (sdfgpu_components.hpp) ------------------------------------------------------------------------------
+// Uses only cc_scratch (and, in the host forms, the bit / output staging and the pinned chunks, which every host-buffer call
+// owns while it runs): the SDF builds' scratch, status block and policy are not touched.
+
+// bits (device) -> labels (device), K -> *out_count; synchronises `st` (K is read back)
+int components_impl(sdfgpu_handle h, const uint32_t* d_bits, int64_t nx, int64_t ny, int64_t nz, uint32_t* d_labels, uint32_t* out_count,
+                    hipStream_t st) {
+    const CcPlan plan = cc_plan(nx, ny, nz);
+    if (int rc = ensure(h, h->cc_scratch, plan.scratch_bytes, "components scratch")) return rc;
+    HIP_TRY(h, cc_launch(plan, d_bits, d_labels, h->cc_scratch.ptr, st));
+    uint32_t k = 0;
+    HIP_TRY(h, hipMemcpyAsync(&k, cc_count_word(plan, h->cc_scratch.ptr), 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    if (out_count) *out_count = k;
+    return SDFGPU_OK;
+}
+
+// host mask / cell records -> bits (host team, 1 bit per voxel over PCIe) -> labels in the output staging
+int components_host(sdfgpu_handle h, const Occupancy& occ, int64_t nx, int64_t ny, int64_t nz, uint32_t* out_count) {
+    const int64_t n = nx * ny * nz;
+    if (int rc = upload_packed(h, occ, n, kNullStream)) return rc;
+    if (int rc = ensure(h, h->stage_out, (size_t)n * 4, "output staging")) return rc;
+    return components_impl(h, (const uint32_t*)h->stage_bits.ptr, nx, ny, nz, (uint32_t*)h->stage_out.ptr, out_count, nullptr);
+}
+
+}  // namespace
+
+extern "C" {
+
+int sdfgpu_components_bits_device(sdfgpu_handle h, const uint32_t* d_bits, int64_t nx, int64_t ny, int64_t nz, uint32_t* d_labels,
+                                  uint32_t* out_count, void* stream) {
+    return rz_wrap(h, stream, [&]() -> int {
+        if (!d_bits || !d_labels || !out_count) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
+        if ((reinterpret_cast<uintptr_t>(d_bits) | reinterpret_cast<uintptr_t>(d_labels)) & 3)
+            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "d_bits and d_labels must be 4-byte aligned");
+        if (int rc = check_dims_u32(h, nx, ny, nz, kLabelsTail)) return rc;
+        HIP_TRY(h, hipSetDevice(h->device));
+        return components_impl(h, d_bits, nx, ny, nz, d_labels, out_count, (hipStream_t)stream);
+    });
+}
+
+int sdfgpu_components(sdfgpu_handle h, const uint8_t* filled, int64_t nx, int64_t ny, int64_t nz, uint32_t* out_labels, uint32_t* out_count) {
+    return rz_wrap(h, nullptr, [&]() -> int {
+        if (!filled || !out_labels || !out_count) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
+        if (int rc = check_dims_u32(h, nx, ny, nz, kLabelsTail)) return rc;
+        HIP_TRY(h, hipSetDevice(h->device));
+        if (int rc = components_host(h, Occupancy::of_mask(filled), nx, ny, nz, out_count)) return rc;
+        return copy_to_host(h, out_labels, h->stage_out.ptr, (size_t)(nx * ny * nz) * 4);
+    });
+}
+
+int sdfgpu_components_cells(sdfgpu_handle h, void* cells, size_t cell_stride, size_t occupancy_offset, size_t component_offset,
+                            int64_t nx, int64_t ny, int64_t nz, uint32_t* out_count) {
+    return rz_wrap(h, nullptr, [&]() -> int {
+        if (!cells || !out_count) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
+        if (int rc = check_component_layout(h, cell_stride, occupancy_offset, component_offset)) return rc;
+        if (int rc = check_dims_u32(h, nx, ny, nz, kLabelsTail)) return rc;
+        HIP_TRY(h, hipSetDevice(h->device));
+        if (int rc = components_host(h, Occupancy::of_cells(cells, cell_stride, occupancy_offset, 0), nx, ny, nz, out_count)) return rc;
+        char* const rec = static_cast<char*>(cells) + component_offset;
+        // the drain team writes each label into its record (download offsets are multiples of 4: whole labels)
+        return staged_download_hip(h, h->stage_out.ptr, (size_t)(nx * ny * nz) * 4, nullptr, [=](const char* src, size_t goff, size_t len) {
+            char* dst = rec + (goff / 4) * cell_stride;
+            for (size_t o = 0; o < len; o += 4, dst += cell_stride) memcpy(dst, src + o, 4);
+        });
+    });
+}
+
+}  // extern "C"

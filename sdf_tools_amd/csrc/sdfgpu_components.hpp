@@ -1,6 +1,6 @@
 // sdfgpu_components.hpp -- connected components of a two-class occupancy grid (CollisionMapGrid::UpdateConnectedComponents,
 // reference src/sdf_tools/collision_map.cpp:564-618 over topology_computation.hpp:25-150), the interface between the kernels in
-// sdfgpu_components.hip and the C ABI in sdfgpu.hip (which owns the scratch and the ordering).
+// sdfgpu_components.hip and the host code at the end of that file (which owns the scratch and the ordering).
 //
 // Contract: a voxel's class is its bit of the linear bit field (bit v & 31 of word v >> 5); two voxels are in one component iff a
 // path of face neighbours of their class joins them; components are numbered 1..K by their minimum linear index (the reference's

@@ -1,12 +1,18 @@
 // sdfgpu_convex.hip -- the local-extrema and convex-segment kernels (sdfgpu_convex.hpp) and their launchers.  Compiled beside
-// sdfgpu.hip and linked into the same libsdfgpu.so (sdf_tools_amd/build.py); the C ABI entry points live in sdfgpu.hip.
+// sdfgpu.hip and linked into the same libsdfgpu.so (sdf_tools_amd/build.py).
+// The family's host orchestration and C ABI entry points (sdfgpu_local_extrema*, sdfgpu_convex_segments_cells, sdfgpu_convex_last_info) are at the end of this file, over the handle of
+// sdfgpu_context.hpp.
 //
 // Arithmetic: the rotated gradient and the extremum distance must round exactly as the reference's host code does (separate
 // products and sums, eigen_lite order), so nothing in this file may be contracted into an FMA (hipcc contracts by default).
+// The host code at the end of this file falls under the pragma too.  It is compiled for baseline x86-64, which has no FMA to
+// contract into, so the pragma changes nothing there -- look again before giving the host pass a -march.
 #pragma clang fp contract(off)
 #define SDFGPU_AUX_TU
 #include "sdfgpu_kernels.hpp"
+#include "sdfgpu_context.hpp"
 #include "sdfgpu_convex.hpp"
+#include "sdfgpu.h"
 
 #include <algorithm>
 
@@ -489,3 +495,143 @@ hipError_t cx_combine(float* free_sdf, const float* named_sdf, uint64_t n, hipSt
 }
 
 }  // namespace sdfgpu
+
+// ---- host side: argument checks, orchestration and the C ABI entry points -----------------------------------------------------------
+using namespace sdfgpu;
+
+namespace {
+
+// ---- local extrema and convex segments (sdfgpu_convex.hpp) ---------------------------------------------------------------------
+// The extrema and segment stages use only cx_scratch and cx_field (and, in the host forms, the staging buffers and the pinned
+// chunks); the SDF scratch, status block and policy are left as they were.  sdfgpu_convex_segments_cells builds its SDF with the
+// ordinary tagged build.
+int check_convex_args(sdfgpu_handle h, int64_t nx, int64_t ny, int64_t nz, double resolution, const double* q_and_qinv) {
+    if (!q_and_qinv) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
+    if (nx <= 0 || ny <= 0 || nz <= 0)
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "grid dimensions must be positive (got %lld x %lld x %lld)",
+                    (long long)nx, (long long)ny, (long long)nz);
+    // Indices, kCxOff and the doubling markers share one uint32 space (sdfgpu_convex.hip): the markers are 2^32 - 1 (= kCxOff),
+    // 2^32 - 2 and 2^32 - 3, so every index must stay below 2^32 - 3 and n may be at most 2^32 - 3.
+    if ((unsigned __int128)nx * (unsigned __int128)ny * (unsigned __int128)nz >= (unsigned __int128)0xFFFFFFFEu)
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT,
+                    "grid %lld x %lld x %lld has 2^32 - 2 voxels or more: uint32 indices share their space with the OFF sentinel and "
+                    "the doubling markers 2^32 - 1, 2^32 - 2, 2^32 - 3, so at most 2^32 - 3 voxels can be numbered",
+                    (long long)nx, (long long)ny, (long long)nz);
+    if (!(resolution > 0.0) || !std::isfinite(resolution))
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "resolution must be positive and finite (got %g)", resolution);
+    return SDFGPU_OK;
+}
+
+// d_sdf (device) -> d_ext (device); synchronises `st` once per doubling round
+int extrema_impl(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t ny, int64_t nz, double resolution, const double* q_and_qinv,
+                 uint32_t* d_ext, hipStream_t st) {
+    const CxPlan plan = cx_plan(nx, ny, nz);
+    // cx_extrema returns with its basin / entry / final kernels still pending on `st`, and they read and write cx_scratch: a
+    // computation on another stream is ordered behind them, as the builds are ordered by build_order.  (ensure() below may
+    // free the scratch: hipFree waits for the device.)
+    HIP_TRY(h, h->cx_order.create());
+    HIP_TRY(h, h->cx_order.wait(st));
+    if (int rc = ensure(h, h->cx_scratch, plan.scratch_bytes, "convex scratch")) return rc;
+    CxRot rot;
+    for (int i = 0; i < 4; ++i) { rot.q[i] = q_and_qinv[i]; rot.qi[i] = q_and_qinv[4 + i]; }
+    int rounds = 0;
+    h->cx_stats_off = 0;
+    const hipError_t ce = cx_extrema(plan, d_sdf, resolution, rot, d_ext, h->cx_scratch.ptr, st, &rounds);
+    (void)h->cx_order.record(st);                       // (also behind a failed launch: what it did enqueue is ordered)
+    HIP_TRY(h, ce);
+    h->cx_stats_off = plan.off_stats;
+    h->cx_rounds = rounds;
+    return SDFGPU_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sdfgpu_local_extrema_device(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                                const double q_and_qinv[8], uint32_t* d_extremum, void* stream) {
+    return rz_wrap(h, stream, [&]() -> int {
+        if (!d_sdf || !d_extremum) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
+        if ((reinterpret_cast<uintptr_t>(d_sdf) | reinterpret_cast<uintptr_t>(d_extremum)) & 3)
+            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "d_sdf and d_extremum must be 4-byte aligned");
+        if (int rc = check_convex_args(h, nx, ny, nz, resolution, q_and_qinv)) return rc;
+        HIP_TRY(h, hipSetDevice(h->device));
+        return extrema_impl(h, d_sdf, nx, ny, nz, resolution, q_and_qinv, d_extremum, (hipStream_t)stream);
+    });
+}
+
+int sdfgpu_local_extrema(sdfgpu_handle h, const float* sdf, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                         const double q_and_qinv[8], uint32_t* out_extremum) {
+    return rz_wrap(h, nullptr, [&]() -> int {
+        if (!sdf || !out_extremum) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
+        if (int rc = check_convex_args(h, nx, ny, nz, resolution, q_and_qinv)) return rc;
+        HIP_TRY(h, hipSetDevice(h->device));
+        const size_t n = (size_t)(nx * ny * nz);
+        if (int rc = ensure(h, h->cx_field, n * 4, "convex field")) return rc;
+        if (int rc = ensure(h, h->stage_out, n * 4, "output staging")) return rc;
+        if (int rc = copy_from_host(h, h->cx_field.ptr, sdf, n * 4)) return rc;
+        if (int rc = extrema_impl(h, (const float*)h->cx_field.ptr, nx, ny, nz, resolution, q_and_qinv, (uint32_t*)h->stage_out.ptr, nullptr))
+            return rc;
+        return copy_to_host(h, out_extremum, h->stage_out.ptr, n * 4);
+    });
+}
+
+int sdfgpu_convex_segments_cells(sdfgpu_handle h, void* cells, size_t cell_stride, size_t occupancy_offset, size_t object_id_offset,
+                                 size_t segment_offset, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                                 const double q_and_qinv[8], double connected_threshold, int add_virtual_border, uint32_t* out_count) {
+    return rz_wrap(h, nullptr, [&]() -> int {
+        if (!cells || !out_count) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
+        if (cell_stride < 12 || (cell_stride % 4) || (occupancy_offset % 4) || (object_id_offset % 4) || (segment_offset % 4) ||
+            occupancy_offset + 4 > cell_stride || object_id_offset + 4 > cell_stride || segment_offset + 4 > cell_stride ||
+            occupancy_offset == object_id_offset || segment_offset == occupancy_offset || segment_offset == object_id_offset)
+            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT,
+                        "cell_stride / occupancy_offset / object_id_offset / segment_offset must be 4-byte aligned, in range and distinct");
+        if (int rc = check_convex_args(h, nx, ny, nz, resolution, q_and_qinv)) return rc;
+        if (int rc = check_dims(h, nx, ny, nz)) return rc;                     // (the SDF build's own limits)
+        HIP_TRY(h, hipSetDevice(h->device));
+        const int64_t n = nx * ny * nz;
+        const CxPlan plan = cx_plan(nx, ny, nz);
+        if (int rc = stage_input(h, (size_t)n * cell_stride)) return rc;
+        if (int rc = ensure(h, h->stage_out, (size_t)n * 4, "output staging")) return rc;
+        if (int rc = ensure(h, h->tagmask, (size_t)n, "tagged-object mask")) return rc;
+        if (int rc = ensure(h, h->tagids, 4, "object id list")) return rc;
+        if (int rc = ensure(h, h->cx_field, (size_t)n * 4, "convex field")) return rc;
+        if (int rc = ensure(h, h->cx_scratch, plan.scratch_bytes, "convex scratch")) return rc;
+        if (int rc = copy_from_host(h, h->stage_in.ptr, cells, (size_t)n * cell_stride)) return rc;
+        if (int rc = convex_sdf(h, cell_stride, occupancy_offset, object_id_offset, nx, ny, nz, resolution, add_virtual_border)) return rc;
+        uint32_t* d_ext = (uint32_t*)h->cx_field.ptr;                          // (the named-object SDF is consumed by now)
+        if (int rc = extrema_impl(h, (const float*)h->stage_out.ptr, nx, ny, nz, resolution, q_and_qinv, d_ext, nullptr)) return rc;
+        uint32_t* d_labels = (uint32_t*)h->stage_out.ptr;                      // (the SDF is consumed by the extrema)
+        HIP_TRY(h, cx_segments(plan, d_ext, (const char*)h->stage_in.ptr, cell_stride, occupancy_offset, object_id_offset, resolution,
+                               connected_threshold, d_labels, h->cx_scratch.ptr, nullptr));
+        uint32_t count = 0;
+        HIP_TRY(h, hipMemcpyAsync(&count, static_cast<char*>(h->cx_scratch.ptr) + plan.off_stats + offsetof(CxStats, count), 4,
+                                  hipMemcpyDeviceToHost, nullptr));
+        HIP_TRY(h, hipStreamSynchronize(nullptr));
+        char* const rec = static_cast<char*>(cells) + segment_offset;
+        if (int rc = staged_download_hip(h, d_labels, (size_t)n * 4, nullptr, [=](const char* src, size_t goff, size_t len) {
+                char* dst = rec + (goff / 4) * cell_stride;
+                for (size_t o = 0; o < len; o += 4, dst += cell_stride) memcpy(dst, src + o, 4);
+            }))
+            return rc;
+        *out_count = count;
+        return SDFGPU_OK;
+    });
+}
+
+int sdfgpu_convex_last_info(sdfgpu_handle h, int* out_rounds, uint32_t* out_cycles, uint32_t* out_longest_cycle,
+                            uint32_t* out_longest_entry) {
+    if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
+    if (h->cx_stats_off == 0 || !h->cx_scratch.ptr) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "no local extrema computed on this handle");
+    HIP_TRY(h, hipSetDevice(h->device));
+    static thread_local CxStats st;                            // (336 KiB: not on the stack)
+    HIP_TRY(h, hipDeviceSynchronize());
+    HIP_TRY(h, hipMemcpy(&st, static_cast<char*>(h->cx_scratch.ptr) + h->cx_stats_off, sizeof st, hipMemcpyDeviceToHost));
+    if (out_rounds) *out_rounds = h->cx_rounds;
+    if (out_cycles) *out_cycles = cx_row_sum(st.cycles);
+    if (out_longest_cycle) *out_longest_cycle = st.longest_cycle[0];
+    if (out_longest_entry) *out_longest_entry = st.longest_entry[0];
+    return SDFGPU_OK;
+}
+
+}  // extern "C"

@@ -1,6 +1,7 @@
 // sdfgpu_convex.hpp -- local extrema maps (SignedDistanceField::ComputeLocalExtremaMap, reference src/sdf_tools/sdf.cpp:23-207)
 // and convex segments (TaggedObjectCollisionMapGrid::UpdateConvexSegments, tagged_object_collision_map.cpp:552-654), the interface
-// between the kernels in sdfgpu_convex.hip and the C ABI in sdfgpu.hip (which owns the scratch, the SDF build and the ordering).
+// between the kernels in sdfgpu_convex.hip and the host code at the end of that file (which owns the scratch and the ordering;
+// the SDF build is sdfgpu.hip's).
 //
 // Contract (include/sdfgpu.h "Local extrema and convex segments"): next(v) is the cell the reference's walk steps to from v (v itself
 // when no axis steps, kCxOff when the step leaves the grid); the extremum of v is the terminal of its forward orbit (a fixed point,

@@ -145,7 +145,8 @@ SDFGPU_KERNEL __launch_bounds__(kSlots) void k_shell_budget(uint32_t* __restrict
 // workgroup -- ran ONE wave per tile behind a 256-row staging round with three workgroups per CU: 0.93 ms at p = 0.03, every LDS
 // latency of its 339 row reads exposed (63 M VALU wave instructions at a sixth of KD3's rate).
 constexpr int kShellGroup = 2;
-constexpr int kShellMinWords = 128;                           // active words (of kShellGroup x 256) below which a group is left to KF
+// (kShellMinWords, the active words of kShellGroup x 256 below which a group is left to KF, is the default of a host option:
+//  sdfgpu_context.hpp)
 
 template <int BD>
 __global__ __launch_bounds__(BD) void k_ball_shell(const ShellArgs a) {

@@ -1,13 +1,19 @@
 // sdfgpu_display.hip -- the display-export kernels (sdfgpu_display.hpp) and their launchers.  Compiled beside sdfgpu.hip and linked
-// into the same libsdfgpu.so (sdf_tools_amd/build.py); the C ABI entry points live in sdfgpu.hip.
+// into the same libsdfgpu.so (sdf_tools_amd/build.py).
+// The family's host orchestration and C ABI entry points (sdfgpu_display_*) are at the end of this file, over the handle of
+// sdfgpu_context.hpp.
 //
 // The SDF colour map restates the host's `fabs(d / extremum) * 0.8 + 0.2` in double with the product and the sum rounded
 // separately, so nothing in this file may be contracted into an FMA (hipcc contracts by default), as in sdfgpu_resample.hip.
 //
 // Launch sizes: every workgroup owns kDpTile voxels or elements, so the largest grid (2^32 - 1 voxels) is 2^20 workgroups -- no
 // launch comes near 2^32 threads.
+// The host code at the end of this file falls under the pragma too.  It is compiled for baseline x86-64, which has no FMA to
+// contract into, so the pragma changes nothing there -- look again before giving the host pass a -march.
 #pragma clang fp contract(off)
+#include "sdfgpu_context.hpp"
 #include "sdfgpu_display.hpp"
+#include "sdfgpu.h"
 
 namespace sdfgpu {
 
@@ -268,3 +274,351 @@ hipError_t dp_launch_sdf_colors(const float* d_sdf, uint64_t n, float alpha, con
 }
 
 }  // namespace sdfgpu
+
+// ---- host side: argument checks, orchestration and the C ABI entry points -----------------------------------------------------------
+using namespace sdfgpu;
+
+namespace {
+
+// ---- display export (sdfgpu_display.hpp) --------------------------------------------------------------------------------------------
+// Only dp_scratch, dp_sort and dp_out (and, in the host forms, the cell / field staging and the pinned chunks) are used.
+constexpr const char* kDisplayTail = "the display export's uint32 indices cannot number it";
+
+struct DisplayRequest {
+    int rule = kDpRuleOccupancy;
+    const uint32_t* draw_keys = nullptr;       // host, ascending; nullptr = no list
+    int64_t n_draw_keys = 0;
+    bool grouped = false;
+    bool to_host = false;                      // the four result pointers are host memory (filled through dp_out)
+    uint32_t* indices = nullptr;               // nullptr = the total only
+    uint32_t* keys = nullptr;
+    int64_t capacity = 0;
+    uint32_t* group_keys = nullptr;
+    uint32_t* group_offsets = nullptr;
+    int64_t group_capacity = 0;
+    int64_t* out_total = nullptr;
+    int64_t* out_groups = nullptr;
+};
+
+int check_display_request(sdfgpu_handle h, const DisplayRequest& rq) {
+    if (!rq.out_total) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: null pointer");
+    if (rq.n_draw_keys < 0 || rq.n_draw_keys > (int64_t)0xFFFFFFFFll || (rq.n_draw_keys > 0 && !rq.draw_keys))
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: n_draw_keys must be in [0, 2^32) and come with a list (got %lld)", (long long)rq.n_draw_keys);
+    for (int64_t i = 1; rq.draw_keys && i < rq.n_draw_keys; ++i)
+        if (rq.draw_keys[i] < rq.draw_keys[i - 1])
+            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: draw_keys must be ascending (entry %lld is %u after %u)", (long long)i,
+                        rq.draw_keys[i], rq.draw_keys[i - 1]);
+    if (rq.indices && rq.capacity < 0) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: capacity must not be negative (got %lld)", (long long)rq.capacity);
+    if (rq.grouped && (!rq.indices || !rq.group_keys || !rq.group_offsets || !rq.out_groups || rq.group_capacity < 0))
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: the grouped form needs indices, group_keys, group_offsets, out_groups and a group capacity >= 0");
+    if (!rq.to_host && ((reinterpret_cast<uintptr_t>(rq.indices) | reinterpret_cast<uintptr_t>(rq.keys) | reinterpret_cast<uintptr_t>(rq.group_keys) |
+                         reinterpret_cast<uintptr_t>(rq.group_offsets)) & 3))
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: device pointers must be 4-byte aligned");
+    return SDFGPU_OK;
+}
+
+size_t dp_align8(size_t x) { return (x + 7) & ~(size_t)7; }
+int dp_bit_length(uint32_t x) { int b = 0; while (b < 32 && (x >> b) != 0) ++b; return b; }
+
+// sel: the source, the rule's options and the shape (device records).  Synchronises `st`.
+int display_select_impl(sdfgpu_handle h, DpSelect sel, const DisplayRequest& rq, hipStream_t st) {
+    const uint64_t n = sel.n, tiles = dp_tiles(n);
+    const size_t key_bytes = dp_align8((size_t)rq.n_draw_keys * 4);
+    const size_t off_keys = sizeof(DpStatus), off_bits = off_keys + key_bytes, off_counts = off_bits + (size_t)tiles * (kDpTile / 8),
+                 off_sums = off_counts + dp_align8((size_t)tiles * 4),
+                 bytes = off_sums + dp_align8((size_t)((tiles + kDpScanSeg - 1) / kDpScanSeg) * 4);
+    if (int rc = ensure(h, h->dp_scratch, bytes, "display scratch")) return rc;
+    char* const b = static_cast<char*>(h->dp_scratch.ptr);
+    DpStatus* const d_st = reinterpret_cast<DpStatus*>(b);
+    uint32_t* const bits = reinterpret_cast<uint32_t*>(b + off_bits);
+    uint32_t* const counts = reinterpret_cast<uint32_t*>(b + off_counts);
+    uint32_t* const sums = reinterpret_cast<uint32_t*>(b + off_sums);
+    HIP_TRY(h, hipMemsetAsync(d_st, 0, sizeof(DpStatus), st));
+    if (rq.n_draw_keys) HIP_TRY(h, hipMemcpyAsync(b + off_keys, rq.draw_keys, (size_t)rq.n_draw_keys * 4, hipMemcpyHostToDevice, st));
+    sel.draw_keys = reinterpret_cast<const uint32_t*>(b + off_keys);
+    sel.n_draw = (uint32_t)rq.n_draw_keys;
+    sel.filter = rq.draw_keys != nullptr;
+    sel.bits = bits;
+    sel.tile_counts = counts;
+    sel.total = &d_st->total;
+    sel.key_max = &d_st->key_max;
+    HIP_TRY(h, dp_launch_select(rq.rule, sel, st));
+    DpStatus status;
+    HIP_TRY(h, hipMemcpyAsync(&status, d_st, sizeof status, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    const uint64_t total = status.total;
+    *rq.out_total = (int64_t)total;
+    if (rq.out_groups) *rq.out_groups = 0;
+    if (!rq.indices) return SDFGPU_OK;                          // the total only
+    if ((uint64_t)rq.capacity < total)
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: the buffers hold %lld elements, %llu voxels are drawn (the total is valid)",
+                    (long long)rq.capacity, (unsigned long long)total);
+    // where the results are built: the caller's device arrays or dp_out
+    const uint64_t gmax = std::min<uint64_t>(total, rq.grouped ? (uint64_t)rq.group_capacity : 0);
+    uint32_t *d_idx = rq.indices, *d_keys = rq.keys, *d_gkeys = rq.group_keys, *d_goffs = rq.group_offsets;
+    if (rq.to_host) {                                           // indices | keys (only when someone reads them) | group keys | group offsets
+        const size_t key_words = rq.keys || rq.grouped ? (size_t)total : 0;
+        if (int rc = ensure(h, h->dp_out, ((size_t)total + key_words + (size_t)gmax * 2 + 1) * 4, "display results")) return rc;
+        d_idx = static_cast<uint32_t*>(h->dp_out.ptr);
+        d_keys = key_words ? d_idx + total : nullptr;
+        d_gkeys = d_idx + total + key_words;
+        d_goffs = d_gkeys + gmax;
+    }
+    // sort only the bits in which the drawn keys differ: all of them agree above bit_length(max ^ min)
+    const int key_bits = rq.grouped && total ? dp_bit_length(status.key_max ^ ~status.key_inv_max) : 0;
+    const SfPairSortPlan sp = key_bits ? sf_pair_sort_plan(total, key_bits) : SfPairSortPlan();
+    const bool own_keys = rq.grouped && !d_keys;               // the group boundaries are read from the sorted keys
+    if (sp.bytes || own_keys) {
+        if (int rc = ensure(h, h->dp_sort, sp.bytes + (own_keys ? (size_t)total * 4 : 0), "display sort scratch")) return rc;
+        if (own_keys) d_keys = reinterpret_cast<uint32_t*>(static_cast<char*>(h->dp_sort.ptr) + sp.bytes);
+    }
+    if (total) {
+        sf_launch_scan(counts, tiles, sums, st);
+        DpCompact c;
+        c.src = sel.src;
+        c.key_mode = rq.rule == kDpRuleOccupancy ? kDpKeyClass : rq.rule == kDpRuleKeyField ? kDpKeyWord : kDpKeyZero;
+        c.n = n;
+        c.bits = bits;
+        c.tile_offsets = counts;
+        c.capacity = total;
+        if (key_bits) c.pairs = static_cast<uint2*>(h->dp_sort.ptr);
+        else { c.idx = d_idx; c.keys = d_keys; }
+        HIP_TRY(h, dp_launch_compact(c, st));
+        if (key_bits) HIP_TRY(h, sf_launch_sort_pairs(sp, key_bits, h->dp_sort.ptr, d_idx, d_keys, st));
+    }
+    uint64_t groups = 0;
+    if (rq.grouped) {
+        if (total) {                                            // the same three steps over the sorted keys (their tiles fit the main pass's scratch)
+            DpSelect g;
+            g.src.cells = reinterpret_cast<const char*>(d_keys);
+            g.src.stride = 4;
+            g.src.occ_off = 0;                                  // (not read by this rule)
+            g.src.key_off = 0;                                  // the key IS the record: k_dp_compact reads it at offset 0
+            g.n = total;
+            g.bits = bits;
+            g.tile_counts = counts;
+            g.total = &d_st->groups;
+            HIP_TRY(h, dp_launch_select(kDpRuleGroupStart, g, st));
+            HIP_TRY(h, hipMemcpyAsync(&status, d_st, sizeof status, hipMemcpyDeviceToHost, st));
+            HIP_TRY(h, hipStreamSynchronize(st));
+            groups = status.groups;
+            *rq.out_groups = (int64_t)groups;
+            if ((uint64_t)rq.group_capacity < groups)
+                return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: the group arrays hold %lld groups, the drawn voxels have %llu keys (total and groups are valid)",
+                            (long long)rq.group_capacity, (unsigned long long)groups);
+            sf_launch_scan(counts, dp_tiles(total), sums, st);
+            // the same kernel with other meanings: its "voxels" are the positions in the sorted key array (records of one word,
+            // stride 4, key at offset 0), so c.idx receives the positions of the group starts = the group offsets, and c.keys
+            // load_word(sorted keys, position) = the group keys
+            DpCompact c;
+            c.src = g.src;
+            c.key_mode = kDpKeyWord;
+            c.n = total;
+            c.bits = bits;
+            c.tile_offsets = counts;
+            c.capacity = groups;
+            c.idx = d_goffs;
+            c.keys = d_gkeys;
+            HIP_TRY(h, dp_launch_compact(c, st));
+        }
+        HIP_TRY(h, hipMemcpyAsync(d_goffs + groups, &d_st->total, 4, hipMemcpyDeviceToDevice, st));      // group_offsets[groups] = total
+    }
+    HIP_TRY(h, hipGetLastError());
+    if (rq.to_host) {
+        if (int rc = copy_to_host(h, rq.indices, d_idx, (size_t)total * 4, st)) return rc;
+        if (rq.keys) if (int rc = copy_to_host(h, rq.keys, d_keys, (size_t)total * 4, st)) return rc;
+        if (rq.grouped) {
+            if (int rc = copy_to_host(h, rq.group_keys, d_gkeys, (size_t)groups * 4, st)) return rc;
+            if (int rc = copy_to_host(h, rq.group_offsets, d_goffs, ((size_t)groups + 1) * 4, st)) return rc;
+        }
+    }
+    HIP_TRY(h, hipStreamSynchronize(st));
+    return SDFGPU_OK;
+}
+
+int check_display_cells(sdfgpu_handle h, const void* cells, size_t stride, size_t occ_off, size_t key_off, int64_t nx, int64_t ny, int64_t nz,
+                        int rule, int class_mask, DpSelect& sel) {
+    if (!cells) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: null pointer");
+    if (rule != SDFGPU_DISPLAY_OCCUPANCY && rule != SDFGPU_DISPLAY_KEY_FIELD)
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: rule must be SDFGPU_DISPLAY_OCCUPANCY (0) or SDFGPU_DISPLAY_KEY_FIELD (1), got %d", rule);
+    if (int rc = check_cell_layout(h, stride, occ_off)) return rc;
+    if (rule == SDFGPU_DISPLAY_KEY_FIELD && ((key_off % 4) || key_off + 4 > stride))
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: key_offset must be 4-byte aligned and inside the record");
+    if (class_mask < 0 || class_mask > 7)
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: class_mask must be a combination of FILLED (1), EMPTY (2) and UNKNOWN (4)");
+    if (int rc = check_dims_u32(h, nx, ny, nz, kDisplayTail)) return rc;
+    sel.src.stride = stride;
+    sel.src.occ_off = (uint32_t)occ_off;
+    sel.src.key_off = (uint32_t)key_off;
+    sel.class_mask = (uint32_t)class_mask;
+    sel.nx = (uint32_t)nx; sel.ny = (uint32_t)ny; sel.nz = (uint32_t)nz;
+    sel.n = (uint64_t)nx * (uint64_t)ny * (uint64_t)nz;
+    return SDFGPU_OK;
+}
+
+int check_display_sdf(sdfgpu_handle h, const float* sdf, int64_t nx, int64_t ny, int64_t nz, DpSelect& sel) {
+    if (!sdf) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: null pointer");
+    if (int rc = check_dims_u32(h, nx, ny, nz, kDisplayTail)) return rc;
+    sel.src.stride = 4;
+    sel.nx = (uint32_t)nx; sel.ny = (uint32_t)ny; sel.nz = (uint32_t)nz;
+    sel.n = (uint64_t)nx * (uint64_t)ny * (uint64_t)nz;
+    return SDFGPU_OK;
+}
+
+// a = min(max(alpha, 0), 1); the extrema into dp_scratch's status words, then one rgba per voxel.  Synchronises `st` (the status
+// words are scratch of the handle).
+int display_sdf_colors_impl(sdfgpu_handle h, const float* d_sdf, uint64_t n, float alpha, float* d_colors, hipStream_t st) {
+    if (int rc = ensure(h, h->dp_scratch, sizeof(DpStatus), "display scratch")) return rc;
+    DpStatus* const d_st = static_cast<DpStatus*>(h->dp_scratch.ptr);
+    HIP_TRY(h, hipMemsetAsync(d_st, 0, sizeof(DpStatus), st));
+    HIP_TRY(h, dp_launch_minmax(d_sdf, n, d_st, st));
+    HIP_TRY(h, dp_launch_sdf_colors(d_sdf, n, std::min(std::max(alpha, 0.0f), 1.0f), d_st, d_colors, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    return SDFGPU_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sdfgpu_display_select_cells_device(sdfgpu_handle h, const void* d_cells, size_t cell_stride, size_t occupancy_offset, size_t key_offset,
+                                       int64_t nx, int64_t ny, int64_t nz, int rule, int class_mask, int surface_only,
+                                       const uint32_t* draw_keys, int64_t n_draw_keys, int draw_zero, int grouped, uint32_t* d_indices,
+                                       uint32_t* d_keys, int64_t capacity, int64_t* out_total, uint32_t* d_group_keys,
+                                       uint32_t* d_group_offsets, int64_t group_capacity, int64_t* out_groups, void* stream) {
+    return rz_wrap(h, stream, [&]() -> int {
+        DpSelect sel;
+        if (int rc = check_display_cells(h, d_cells, cell_stride, occupancy_offset, key_offset, nx, ny, nz, rule, class_mask, sel)) return rc;
+        if (reinterpret_cast<uintptr_t>(d_cells) & 3) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: d_cells must be 4-byte aligned");
+        DisplayRequest rq;
+        rq.rule = rule == SDFGPU_DISPLAY_OCCUPANCY ? kDpRuleOccupancy : kDpRuleKeyField;
+        rq.draw_keys = draw_keys; rq.n_draw_keys = n_draw_keys; rq.grouped = grouped != 0;
+        rq.indices = d_indices; rq.keys = d_keys; rq.capacity = capacity; rq.out_total = out_total;
+        rq.group_keys = d_group_keys; rq.group_offsets = d_group_offsets; rq.group_capacity = group_capacity; rq.out_groups = out_groups;
+        if (int rc = check_display_request(h, rq)) return rc;
+        HIP_TRY(h, hipSetDevice(h->device));
+        sel.src.cells = static_cast<const char*>(d_cells);
+        sel.surface_only = surface_only != 0;
+        sel.draw_zero = draw_zero != 0;
+        return display_select_impl(h, sel, rq, (hipStream_t)stream);
+    });
+}
+
+int sdfgpu_display_select_cells(sdfgpu_handle h, const void* cells, size_t cell_stride, size_t occupancy_offset, size_t key_offset, int64_t nx,
+                                int64_t ny, int64_t nz, int rule, int class_mask, int surface_only, const uint32_t* draw_keys,
+                                int64_t n_draw_keys, int draw_zero, int grouped, uint32_t* out_indices, uint32_t* out_keys, int64_t capacity,
+                                int64_t* out_total, uint32_t* out_group_keys, uint32_t* out_group_offsets, int64_t group_capacity,
+                                int64_t* out_groups) {
+    return rz_wrap(h, nullptr, [&]() -> int {
+        DpSelect sel;
+        if (int rc = check_display_cells(h, cells, cell_stride, occupancy_offset, key_offset, nx, ny, nz, rule, class_mask, sel)) return rc;
+        DisplayRequest rq;
+        rq.rule = rule == SDFGPU_DISPLAY_OCCUPANCY ? kDpRuleOccupancy : kDpRuleKeyField;
+        rq.draw_keys = draw_keys; rq.n_draw_keys = n_draw_keys; rq.grouped = grouped != 0; rq.to_host = true;
+        rq.indices = out_indices; rq.keys = out_keys; rq.capacity = capacity; rq.out_total = out_total;
+        rq.group_keys = out_group_keys; rq.group_offsets = out_group_offsets; rq.group_capacity = group_capacity; rq.out_groups = out_groups;
+        if (int rc = check_display_request(h, rq)) return rc;
+        HIP_TRY(h, hipSetDevice(h->device));
+        const size_t bytes = (size_t)sel.n * cell_stride;       // the null stream throughout: records through the cell staging
+        if (int rc = stage_input(h, bytes)) return rc;
+        if (int rc = copy_from_host(h, h->stage_in.ptr, cells, bytes)) return rc;
+        sel.src.cells = static_cast<const char*>(h->stage_in.ptr);
+        sel.surface_only = surface_only != 0;
+        sel.draw_zero = draw_zero != 0;
+        return display_select_impl(h, sel, rq, nullptr);
+    });
+}
+
+int sdfgpu_display_select_sdf_device(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t ny, int64_t nz, uint32_t* d_indices,
+                                     int64_t capacity, int64_t* out_total, void* stream) {
+    return rz_wrap(h, stream, [&]() -> int {
+        DpSelect sel;
+        if (int rc = check_display_sdf(h, d_sdf, nx, ny, nz, sel)) return rc;
+        if (reinterpret_cast<uintptr_t>(d_sdf) & 3) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: d_sdf must be 4-byte aligned");
+        DisplayRequest rq;
+        rq.rule = kDpRuleSdfNonPositive;
+        rq.indices = d_indices; rq.capacity = capacity; rq.out_total = out_total;
+        if (int rc = check_display_request(h, rq)) return rc;
+        HIP_TRY(h, hipSetDevice(h->device));
+        sel.src.cells = reinterpret_cast<const char*>(d_sdf);
+        return display_select_impl(h, sel, rq, (hipStream_t)stream);
+    });
+}
+
+int sdfgpu_display_select_sdf(sdfgpu_handle h, const float* sdf, int64_t nx, int64_t ny, int64_t nz, uint32_t* out_indices, int64_t capacity,
+                              int64_t* out_total) {
+    return rz_wrap(h, nullptr, [&]() -> int {
+        DpSelect sel;
+        if (int rc = check_display_sdf(h, sdf, nx, ny, nz, sel)) return rc;
+        DisplayRequest rq;
+        rq.rule = kDpRuleSdfNonPositive;
+        rq.to_host = true;
+        rq.indices = out_indices; rq.capacity = capacity; rq.out_total = out_total;
+        if (int rc = check_display_request(h, rq)) return rc;
+        HIP_TRY(h, hipSetDevice(h->device));
+        if (int rc = stage_input(h, (size_t)sel.n * 4)) return rc;
+        if (int rc = copy_from_host(h, h->stage_in.ptr, sdf, (size_t)sel.n * 4)) return rc;
+        sel.src.cells = static_cast<const char*>(h->stage_in.ptr);
+        return display_select_impl(h, sel, rq, nullptr);
+    });
+}
+
+int sdfgpu_display_expand_device(sdfgpu_handle h, const uint32_t* d_indices, const uint32_t* d_keys, int64_t count, int64_t nx, int64_t ny,
+                                 int64_t nz, const double cell_sizes[3], double* d_points, float* d_colors, const float* d_color_table,
+                                 int64_t table_entries, const float default_color[4], void* stream) {
+    return rz_wrap(h, stream, [&]() -> int {
+        if (!d_indices || !cell_sizes || (!d_points && !d_colors)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: null pointer");
+        if (d_colors && (!default_color || table_entries < 0 || table_entries > (int64_t)0xFFFFFFFFll || (table_entries > 0 && !d_color_table)))
+            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: colours need a default colour and a table of [0, 2^32) entries");
+        if (count < 0 || count > (int64_t)0xFFFFFFFFll)
+            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: count must be in [0, 2^32) (got %lld)", (long long)count);
+        if (int rc = check_dims_u32(h, nx, ny, nz, kDisplayTail)) return rc;
+        if ((reinterpret_cast<uintptr_t>(d_indices) | reinterpret_cast<uintptr_t>(d_keys) | reinterpret_cast<uintptr_t>(d_points) |
+             reinterpret_cast<uintptr_t>(d_colors) | reinterpret_cast<uintptr_t>(d_color_table)) & 3)
+            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: device pointers must be 4-byte aligned");
+        HIP_TRY(h, hipSetDevice(h->device));
+        DpExpand a;
+        a.idx = d_indices; a.keys = d_keys; a.count = (uint64_t)count;
+        a.ny = (uint32_t)ny; a.nz = (uint32_t)nz;
+        for (int i = 0; i < 3; ++i) a.cell[i] = cell_sizes[i];
+        a.points = reinterpret_cast<uint32_t*>(d_points);
+        a.colors = d_colors;
+        if (d_colors) {
+            a.table = d_color_table; a.table_len = (uint32_t)table_entries;
+            for (int i = 0; i < 4; ++i) a.fallback[i] = default_color[i];
+        }
+        HIP_TRY(h, dp_launch_expand(a, (hipStream_t)stream));
+        return SDFGPU_OK;
+    });
+}
+
+int sdfgpu_display_sdf_colors_device(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t ny, int64_t nz, float alpha, float* d_colors,
+                                     void* stream) {
+    return rz_wrap(h, stream, [&]() -> int {
+        DpSelect sel;
+        if (!d_colors) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: null pointer");
+        if (int rc = check_display_sdf(h, d_sdf, nx, ny, nz, sel)) return rc;
+        if (std::isnan(alpha)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: alpha must not be NaN");
+        if ((reinterpret_cast<uintptr_t>(d_sdf) | reinterpret_cast<uintptr_t>(d_colors)) & 3)
+            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: d_sdf and d_colors must be 4-byte aligned");
+        HIP_TRY(h, hipSetDevice(h->device));
+        return display_sdf_colors_impl(h, d_sdf, sel.n, alpha, d_colors, (hipStream_t)stream);
+    });
+}
+
+int sdfgpu_display_sdf_colors(sdfgpu_handle h, const float* sdf, int64_t nx, int64_t ny, int64_t nz, float alpha, float* out_colors) {
+    return rz_wrap(h, nullptr, [&]() -> int {
+        DpSelect sel;
+        if (!out_colors) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: null pointer");
+        if (int rc = check_display_sdf(h, sdf, nx, ny, nz, sel)) return rc;
+        if (std::isnan(alpha)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: alpha must not be NaN");
+        HIP_TRY(h, hipSetDevice(h->device));
+        if (int rc = stage_input(h, (size_t)sel.n * 4)) return rc;
+        if (int rc = ensure(h, h->stage_out, (size_t)sel.n * 16, "output staging")) return rc;
+        if (int rc = copy_from_host(h, h->stage_in.ptr, sdf, (size_t)sel.n * 4)) return rc;
+        if (int rc = display_sdf_colors_impl(h, (const float*)h->stage_in.ptr, sel.n, alpha, (float*)h->stage_out.ptr, nullptr)) return rc;
+        return copy_to_host(h, out_colors, h->stage_out.ptr, (size_t)sel.n * 16);
+    });
+}
+
+}  // extern "C"

@@ -1,6 +1,6 @@
 // sdfgpu_display.hpp -- the display export of the grid classes and the SDF (the reference's ExportForDisplay family,
 // src/sdf_tools/collision_map.cpp, tagged_object_collision_map.cpp, sdf.cpp): which voxels are drawn, in which order, where and in
-// which colour.  The interface between the kernels in sdfgpu_display.hip and the C ABI in sdfgpu.hip (which owns the scratch and
+// which colour.  The interface between the kernels in sdfgpu_display.hip and the host code at the end of that file (which owns the scratch and
 // reads the status words back).  Contract: include/sdfgpu.h "Display export", DESIGN.md section 23.  Launches:
 //   k_dp_select  one lane per voxel, kDpTile voxels per workgroup: the rule (drawn?, key), one ballot per wave = two bit words, the
 //                workgroup's count -> tile_counts[tile], one atomic each for the total and the smallest / largest drawn key

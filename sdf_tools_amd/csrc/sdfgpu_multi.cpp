@@ -255,7 +255,7 @@ int wait_rank(sdfgpu_multi_handle h, int q) {
     return SDFGPU_OK;
 }
 
-// The limits of sdfgpu_build* (check_dims in sdfgpu.hip), applied before anything is allocated or uploaded: an oversized
+// The limits of sdfgpu_build* (check_dims in sdfgpu_context.hip), applied before anything is allocated or uploaded: an oversized
 // or malformed request must come back as UNSUPPORTED_SIZE / INVALID_ARGUMENT, not as a hipMalloc failure half-way.
 // (the resolution: include/sdfgpu.h "Resolutions" -- positive and finite, or nothing is uploaded, enqueued or written)
 int check_resolution(sdfgpu_multi_handle h, double res) {

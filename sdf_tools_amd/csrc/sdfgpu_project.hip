@@ -1,12 +1,17 @@
 // sdfgpu_project.hip -- the projection kernel (sdfgpu_project.hpp) and its launcher.  Compiled beside sdfgpu.hip and linked into
-// the same libsdfgpu.so (sdf_tools_amd/build.py); the C ABI entry points live in sdfgpu.hip.
+// the same libsdfgpu.so (sdf_tools_amd/build.py).
+// The family's host orchestration and C ABI entry points (sdfgpu_project_*) are at the end of this file, over the handle of
+// sdfgpu_context.hpp.
 //
 // Arithmetic: every location, distance and step must round exactly as the host walk does (separate products and sums in
 // eigen_lite order, correctly rounded division and square root), so nothing in this file may be contracted into an FMA (hipcc
 // contracts by default).
+// The host code at the end of this file falls under the pragma too.  It is compiled for baseline x86-64, which has no FMA to
+// contract into, so the pragma changes nothing there -- look again before giving the host pass a -march.
 #pragma clang fp contract(off)
 #define SDFGPU_AUX_TU
 #include "sdfgpu_kernels.hpp"
+#include "sdfgpu_context.hpp"
 #include "sdfgpu_project.hpp"
 #include "sdfgpu.h"
 
@@ -196,3 +201,80 @@ hipError_t project_launch(const ProjectArgs& a, hipStream_t s) {
 }
 
 }  // namespace sdfgpu
+
+// ---- host side: argument checks, orchestration and the C ABI entry points -----------------------------------------------------------
+using namespace sdfgpu;
+
+namespace {
+
+int check_project_args(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                       const double* world_to_grid, const double* grid_to_world, double stepsize_multiplier, int max_steps, int mode,
+                       const double* points, int64_t n_points, const double* out_points, ProjectArgs& a) {
+    if (!d_sdf) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "projection: null field pointer");
+    if (n_points < 0 || n_points > ((int64_t)1 << 40)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "projection: point count %lld out of range [0, 2^40]", (long long)n_points);
+    if (n_points > 0 && (!points || !out_points)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "projection: null points or out_points");
+    if (!world_to_grid || !grid_to_world) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "projection: world_to_grid and grid_to_world are required");
+    if (nx <= 0 || ny <= 0 || nz <= 0 || nx > INT64_MAX / ny || nx * ny > INT64_MAX / nz)
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "projection: unsupported grid %lld x %lld x %lld", (long long)nx, (long long)ny, (long long)nz);
+    if (!(resolution > 0.0) || !std::isfinite(resolution)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "projection: resolution must be positive and finite");
+    if (mode != SDFGPU_PROJECT_OUT_OF_COLLISION && mode != SDFGPU_PROJECT_INTO_VALID_VOLUME)
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "projection: unknown mode %d", mode);
+    const int limit = project_step_limit(nx, ny, nz, stepsize_multiplier, max_steps);
+    if (limit < 0) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "projection: stepsize_multiplier must be positive and finite and max_steps >= 0");
+    a = ProjectArgs{};
+    a.sdf = d_sdf; a.n = n_points; a.nx = nx; a.ny = ny; a.nz = nz;
+    a.step_limit = limit; a.mode = mode;
+    for (int i = 0; i < 12; ++i) { a.w2g[i] = world_to_grid[i]; a.g2w[i] = grid_to_world[i]; }
+    return SDFGPU_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sdfgpu_project_step_limit(int64_t nx, int64_t ny, int64_t nz, double stepsize_multiplier, int max_steps, int* out_limit) {
+    if (!out_limit || nx <= 0 || ny <= 0 || nz <= 0) return SDFGPU_ERR_INVALID_ARGUMENT;
+    const int limit = project_step_limit(nx, ny, nz, stepsize_multiplier, max_steps);
+    if (limit < 0) return SDFGPU_ERR_INVALID_ARGUMENT;
+    *out_limit = limit;
+    return SDFGPU_OK;
+}
+
+int sdfgpu_project_points_device(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                                 const double world_to_grid[12], const double grid_to_world[12], double minimum_distance,
+                                 double stepsize_multiplier, int max_steps, int mode, const double* d_points, int64_t n_points,
+                                 double* d_out_points, uint8_t* d_out_status, int32_t* d_out_steps, void* stream) {
+    return rz_wrap(h, stream, [&]() -> int {
+        ProjectArgs a;
+        if (int rc = check_project_args(h, d_sdf, nx, ny, nz, resolution, world_to_grid, grid_to_world, stepsize_multiplier, max_steps,
+                                        mode, d_points, n_points, d_out_points, a)) return rc;
+        if (n_points == 0) return SDFGPU_OK;
+        HIP_TRY(h, hipSetDevice(h->device));
+        a.points = d_points; a.out = d_out_points; a.status = d_out_status; a.steps = d_out_steps;
+        project_prepare(a, resolution, minimum_distance, stepsize_multiplier);
+        HIP_TRY(h, project_launch(a, (hipStream_t)stream));
+        return SDFGPU_OK;
+    });
+}
+
+int sdfgpu_project_points(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                          const double world_to_grid[12], const double grid_to_world[12], double minimum_distance,
+                          double stepsize_multiplier, int max_steps, int mode, const double* points, int64_t n_points,
+                          double* out_points, uint8_t* out_status, int32_t* out_steps) {
+    return rz_wrap(h, nullptr, [&]() -> int {
+        ProjectArgs a;
+        if (int rc = check_project_args(h, d_sdf, nx, ny, nz, resolution, world_to_grid, grid_to_world, stepsize_multiplier, max_steps,
+                                        mode, points, n_points, out_points, a)) return rc;
+        if (n_points == 0) return SDFGPU_OK;
+        HIP_TRY(h, hipSetDevice(h->device));
+        // points | out points | steps | status
+        return with_staged_points(h, points, n_points, {24, 4, 1}, {out_points, out_steps, out_status}, [&](const double* d_points, char* const (&d)[3]) -> int {
+            a.points = d_points; a.out = (double*)d[0]; a.steps = (int32_t*)d[1]; a.status = (uint8_t*)d[2];
+            project_prepare(a, resolution, minimum_distance, stepsize_multiplier);
+            HIP_TRY(h, project_launch(a, nullptr));
+            return SDFGPU_OK;
+        });
+    });
+}
+
+}  // extern "C"

@@ -1,6 +1,6 @@
 // sdfgpu_project.hpp -- projection out of collision / into the valid volume (SignedDistanceField::ProjectOutOfCollision*,
 // ProjectIntoValidVolume*, reference include/sdf_tools/sdf.hpp:996-1190), the interface between the kernel in sdfgpu_project.hip
-// and the C ABI in sdfgpu.hip (which checks the arguments, precomputes the constants below and owns the staging).
+// and the host code at the end of that file (which checks the arguments, precomputes the constants below and owns the staging).
 //
 // Contract: include/sdfgpu.h "Projection".  One lane per point walks the reference's loop in double, bounded by step_limit; the
 // constants are computed once on the host with the host walk's expressions (SignedDistanceField::

@@ -1,13 +1,18 @@
 // sdfgpu_query.hip -- the interpolated-gradient kernel (sdfgpu_query.hpp) and its launcher.  Compiled beside sdfgpu.hip and
-// linked into the same libsdfgpu.so (sdf_tools_amd/build.py); the C ABI entry points live in sdfgpu.hip.
+// linked into the same libsdfgpu.so (sdf_tools_amd/build.py).
+// The family's host orchestration and C ABI entry points (sdfgpu_query_gradients*) are at the end of this file, over the handle of
+// sdfgpu_context.hpp.
 //
 // Arithmetic: every estimate, difference, derivative and displacement must round exactly as the host core
 // (SignedDistanceField::QueryGradient4d) does -- separate products and sums in eigen_lite order, the AutoDiff3 operators of
 // include/sdf_tools/autodiff.hpp, correctly rounded division -- so nothing in this file (nor in that header, included below) may
 // be contracted into an FMA (hipcc contracts by default).
+// The host code at the end of this file falls under the pragma too.  It is compiled for baseline x86-64, which has no FMA to
+// contract into, so the pragma changes nothing there -- look again before giving the host pass a -march.
 #pragma clang fp contract(off)
 #define SDFGPU_AUX_TU
 #include "sdfgpu_kernels.hpp"
+#include "sdfgpu_context.hpp"
 #include "sdfgpu_query.hpp"
 #include "sdfgpu.h"
 #include "sdf_tools/autodiff.hpp"
@@ -172,3 +177,66 @@ hipError_t query_gradients_launch(const GradientQueryArgs& a, hipStream_t s) {
 }
 
 }  // namespace sdfgpu
+
+// ---- host side: argument checks, orchestration and the C ABI entry points -----------------------------------------------------------
+using namespace sdfgpu;
+
+namespace {
+
+int check_query_gradients_args(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                               const double* world_to_grid, int kind, double window, const double* points, int64_t n_points,
+                               GradientQueryArgs& a) {
+    if (!d_sdf) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "gradient query: null field pointer");
+    if (n_points < 0 || n_points > ((int64_t)1 << 40)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "gradient query: point count %lld out of range [0, 2^40]", (long long)n_points);
+    if (n_points > 0 && !points) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "gradient query: null points");
+    if (!world_to_grid) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "gradient query: world_to_grid is required");
+    if (nx <= 0 || ny <= 0 || nz <= 0 || nx > INT64_MAX / ny || nx * ny > INT64_MAX / nz)
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "gradient query: unsupported grid %lld x %lld x %lld", (long long)nx, (long long)ny, (long long)nz);
+    if (!(resolution > 0.0) || !std::isfinite(resolution)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "gradient query: resolution must be positive and finite");
+    if (kind != SDFGPU_QUERY_SMOOTH_GRADIENT && kind != SDFGPU_QUERY_AUTODIFF_GRADIENT && kind != SDFGPU_QUERY_DISTANCE_TO_BOUNDARY)
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "gradient query: unknown kind %d", kind);
+    if (!std::isfinite(window)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "gradient query: the window must be finite");
+    a = GradientQueryArgs{};
+    a.sdf = d_sdf; a.n = n_points; a.nx = nx; a.ny = ny; a.nz = nz; a.kind = kind;
+    for (int i = 0; i < 12; ++i) a.w2g[i] = world_to_grid[i];
+    return SDFGPU_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sdfgpu_query_gradients_device(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                                  const double world_to_grid[12], float oob_value, int kind, double window, const double* d_points,
+                                  int64_t n_points, double* d_value, double* d_gradient, uint8_t* d_status, void* stream) {
+    return rz_wrap(h, stream, [&]() -> int {
+        GradientQueryArgs a;
+        if (int rc = check_query_gradients_args(h, d_sdf, nx, ny, nz, resolution, world_to_grid, kind, window, d_points, n_points, a)) return rc;
+        if (n_points == 0 || (!d_value && !d_gradient && !d_status)) return SDFGPU_OK;
+        HIP_TRY(h, hipSetDevice(h->device));
+        a.points = d_points; a.value = d_value; a.gradient = d_gradient; a.status = d_status;
+        query_gradients_prepare(a, resolution, window, oob_value);
+        HIP_TRY(h, query_gradients_launch(a, (hipStream_t)stream));
+        return SDFGPU_OK;
+    });
+}
+
+int sdfgpu_query_gradients(sdfgpu_handle h, const float* d_sdf, int64_t nx, int64_t ny, int64_t nz, double resolution,
+                           const double world_to_grid[12], float oob_value, int kind, double window, const double* points,
+                           int64_t n_points, double* out_value, double* out_gradient, uint8_t* out_status) {
+    return rz_wrap(h, nullptr, [&]() -> int {
+        GradientQueryArgs a;
+        if (int rc = check_query_gradients_args(h, d_sdf, nx, ny, nz, resolution, world_to_grid, kind, window, points, n_points, a)) return rc;
+        if (n_points == 0 || (!out_value && !out_gradient && !out_status)) return SDFGPU_OK;
+        HIP_TRY(h, hipSetDevice(h->device));
+        // points | gradient | value | status
+        return with_staged_points(h, points, n_points, {24, 8, 1}, {out_gradient, out_value, out_status}, [&](const double* d_points, char* const (&d)[3]) -> int {
+            a.points = d_points; a.gradient = (double*)d[0]; a.value = (double*)d[1]; a.status = (uint8_t*)d[2];
+            query_gradients_prepare(a, resolution, window, oob_value);
+            HIP_TRY(h, query_gradients_launch(a, nullptr));
+            return SDFGPU_OK;
+        });
+    });
+}
+
+}  // extern "C"

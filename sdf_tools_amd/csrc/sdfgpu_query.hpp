@@ -1,6 +1,6 @@
 // sdfgpu_query.hpp -- the interpolated gradients (SignedDistanceField::GetSmoothGradient*, GetAutoDiffGradient*,
 // DistanceToBoundary*, reference include/sdf_tools/sdf.hpp:528-653, 963-988), the interface between the kernel in
-// sdfgpu_query.hip and the C ABI in sdfgpu.hip (which checks the arguments and owns the staging).
+// sdfgpu_query.hip and the host code at the end of that file (which checks the arguments and owns the staging).
 //
 // Contract: include/sdfgpu.h "Interpolated gradients".  One lane per point, in double; the constants are computed once on the
 // host with the host core's expressions (SignedDistanceField::QueryGradient4d) so that the device repeats its arithmetic

@@ -1,12 +1,18 @@
 // sdfgpu_resample.hip -- the two Resample kernels (sdfgpu_resample.hpp) and their launcher.  Compiled beside sdfgpu.hip and linked
-// into the same libsdfgpu.so (sdf_tools_amd/build.py); the C ABI entry points live in sdfgpu.hip.
+// into the same libsdfgpu.so (sdf_tools_amd/build.py).
+// The family's host orchestration and C ABI entry points (sdfgpu_resample_cells*, sdfgpu_debug_resample_times) are at the end of this file, over the handle of
+// sdfgpu_context.hpp.
 //
 // Arithmetic: the destination of a source cell must round exactly as VoxelGrid::GridIndexToLocation followed by
 // VoxelGrid::LocationToGridIndex4d does on the host (separate products and sums in eigen_lite order), because a source centre
 // that sits on a result cell boundary is placed by rounding noise alone; so nothing in this file may be contracted into an FMA
 // (hipcc contracts by default).
+// The host code at the end of this file falls under the pragma too.  It is compiled for baseline x86-64, which has no FMA to
+// contract into, so the pragma changes nothing there -- look again before giving the host pass a -march.
 #pragma clang fp contract(off)
+#include "sdfgpu_context.hpp"
 #include "sdfgpu_resample.hpp"
+#include "sdfgpu.h"
 
 namespace sdfgpu {
 
@@ -151,3 +157,118 @@ hipError_t resample_launch(const ResampleArgs& a, hipStream_t s, hipEvent_t afte
 }
 
 }  // namespace sdfgpu
+
+// ---- host side: argument checks, orchestration and the C ABI entry points -----------------------------------------------------------
+using namespace sdfgpu;
+
+namespace {
+
+// ---- resample (sdfgpu_resample.hpp) ------------------------------------------------------------------------------------------------
+// Only rs_scratch (and, in the host form, the cell and field staging and the pinned chunks) is used.
+int check_resample_args(sdfgpu_handle h, const void* src, size_t cell_bytes, int64_t nx, int64_t ny, int64_t nz, const double* src_cell,
+                        const double* origin, const double* dst_inverse_origin, const double* dst_inv_cell, const void* dst, int64_t mx,
+                        int64_t my, int64_t mz, const void* fill_cell, ResampleArgs& a) {
+    if (!src || !dst || !src_cell || !origin || !dst_inverse_origin || !dst_inv_cell || !fill_cell)
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "resample: null pointer");
+    if (cell_bytes != 4 && cell_bytes != 8 && cell_bytes != 16)
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "resample: cell_bytes must be 4, 8 or 16 (got %zu)", cell_bytes);
+    if (src == dst) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "resample: the source and the result must be different buffers");
+    const int64_t kMaxCells = INT64_MAX / 16;
+    if (nx <= 0 || ny <= 0 || nz <= 0 || nx > kMaxCells / ny || nx * ny > kMaxCells / nz)
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "resample: unsupported source grid %lld x %lld x %lld", (long long)nx, (long long)ny, (long long)nz);
+    if (mx <= 0 || my <= 0 || mz <= 0 || mx > kMaxCells / my || mx * my > kMaxCells / mz)
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "resample: unsupported result grid %lld x %lld x %lld", (long long)mx, (long long)my, (long long)mz);
+    a = ResampleArgs{};
+    a.nx = nx; a.ny = ny; a.nz = nz; a.mx = mx; a.my = my; a.mz = mz;
+    a.n_src = nx * ny * nz; a.n_dst = mx * my * mz;
+    for (int i = 0; i < 3; ++i) { a.cell[i] = src_cell[i]; a.inv_cell[i] = dst_inv_cell[i]; }
+    for (int i = 0; i < 16; ++i) { a.origin[i] = origin[i]; a.inverse[i] = dst_inverse_origin[i]; }
+    memcpy(a.fill, fill_cell, cell_bytes);
+    a.cell_bytes = (int)cell_bytes;
+    a.winner_bytes = resample_winner_bytes(a.n_src);
+    a.plain_atomics = h->opt.rs_plain_atomics;
+    return SDFGPU_OK;
+}
+
+// a.src -> a.dst (device) on `st`; synchronises `st` only when out_written is asked for
+int resample_impl(sdfgpu_handle h, ResampleArgs& a, uint64_t* out_written, hipStream_t st) {
+    // the winner words belong to the handle and the call may return with its kernels pending: a call on another stream waits for
+    // them on the device first, as the local extrema do (ensure() below may free the scratch: hipFree waits for the device)
+    HIP_TRY(h, h->rs_order.create());
+    HIP_TRY(h, h->rs_order.wait(st));
+    if (int rc = ensure(h, h->rs_scratch, resample_scratch_bytes(a.n_dst, a.winner_bytes), "resample winners")) return rc;
+    a.winner = h->rs_scratch.ptr;
+    unsigned long long* const counter =
+        reinterpret_cast<unsigned long long*>(static_cast<char*>(h->rs_scratch.ptr) + resample_counter_offset(a.n_dst, a.winner_bytes));
+    a.written = out_written ? counter : nullptr;
+    if (h->opt.rs_timing) {
+        for (hipEvent_t& e : h->rs_time_ev) if (!e) HIP_TRY(h, hipEventCreate(&e));
+        HIP_TRY(h, hipEventRecord(h->rs_time_ev[0], st));
+    }
+    const hipError_t le = resample_launch(a, st, h->opt.rs_timing ? h->rs_time_ev[1] : nullptr);
+    if (h->opt.rs_timing) h->rs_timed = le == hipSuccess && hipEventRecord(h->rs_time_ev[2], st) == hipSuccess;
+    (void)h->rs_order.record(st);                       // (also behind a failed launch: what it did enqueue is ordered)
+    HIP_TRY(h, le);
+    if (out_written) {
+        unsigned long long count = 0;
+        HIP_TRY(h, hipMemcpyAsync(&count, counter, sizeof count, hipMemcpyDeviceToHost, st));
+        HIP_TRY(h, hipStreamSynchronize(st));
+        *out_written = (uint64_t)count;
+    }
+    return SDFGPU_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sdfgpu_resample_cells_device(sdfgpu_handle h, const void* d_src, size_t cell_bytes, int64_t nx, int64_t ny, int64_t nz,
+                                 const double src_cell[3], const double origin[16], const double dst_inverse_origin[16],
+                                 const double dst_inv_cell[3], void* d_dst, int64_t mx, int64_t my, int64_t mz, const void* fill_cell,
+                                 uint64_t* out_cells_written, void* stream) {
+    return rz_wrap(h, stream, [&]() -> int {
+        ResampleArgs a;
+        if (int rc = check_resample_args(h, d_src, cell_bytes, nx, ny, nz, src_cell, origin, dst_inverse_origin, dst_inv_cell, d_dst, mx, my,
+                                         mz, fill_cell, a)) return rc;
+        if ((reinterpret_cast<uintptr_t>(d_src) | reinterpret_cast<uintptr_t>(d_dst)) & 3)
+            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "resample: d_src and d_dst must be 4-byte aligned");
+        HIP_TRY(h, hipSetDevice(h->device));
+        a.src = d_src; a.dst = d_dst;
+        return resample_impl(h, a, out_cells_written, (hipStream_t)stream);
+    });
+}
+
+int sdfgpu_debug_resample_times(sdfgpu_handle h, double* out_winner_ms, double* out_gather_ms) {
+    if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
+    if (!out_winner_ms || !out_gather_ms) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
+    if (!h->rs_timed) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "no resample timed on this handle (option \"resample_timing\")");
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipEventSynchronize(h->rs_time_ev[2]));
+    float a = 0.0f, b = 0.0f;
+    HIP_TRY(h, hipEventElapsedTime(&a, h->rs_time_ev[0], h->rs_time_ev[1]));
+    HIP_TRY(h, hipEventElapsedTime(&b, h->rs_time_ev[1], h->rs_time_ev[2]));
+    *out_winner_ms = (double)a;
+    *out_gather_ms = (double)b;
+    return SDFGPU_OK;
+}
+
+int sdfgpu_resample_cells(sdfgpu_handle h, const void* src, size_t cell_bytes, int64_t nx, int64_t ny, int64_t nz, const double src_cell[3],
+                          const double origin[16], const double dst_inverse_origin[16], const double dst_inv_cell[3], void* dst, int64_t mx,
+                          int64_t my, int64_t mz, const void* fill_cell, uint64_t* out_cells_written) {
+    return rz_wrap(h, nullptr, [&]() -> int {
+        ResampleArgs a;
+        if (int rc = check_resample_args(h, src, cell_bytes, nx, ny, nz, src_cell, origin, dst_inverse_origin, dst_inv_cell, dst, mx, my, mz,
+                                         fill_cell, a)) return rc;
+        HIP_TRY(h, hipSetDevice(h->device));
+        // the null stream throughout: source records through the cell staging, the result through the field staging
+        const size_t src_bytes = (size_t)a.n_src * cell_bytes, dst_bytes = (size_t)a.n_dst * cell_bytes;
+        if (int rc = stage_input(h, src_bytes)) return rc;
+        if (int rc = ensure(h, h->stage_out, dst_bytes, "output staging")) return rc;
+        if (int rc = copy_from_host(h, h->stage_in.ptr, src, src_bytes)) return rc;
+        a.src = h->stage_in.ptr; a.dst = h->stage_out.ptr;
+        if (int rc = resample_impl(h, a, out_cells_written, nullptr)) return rc;
+        return copy_to_host(h, dst, h->stage_out.ptr, dst_bytes);
+    });
+}
+
+}  // extern "C"

@@ -1,6 +1,6 @@
 // sdfgpu_resample.hpp -- CollisionMapGrid / TaggedObjectCollisionMapGrid::Resample (reference src/sdf_tools/collision_map.cpp:673-695,
-// tagged_object_collision_map.cpp:399-422) on the GPU: the interface between the kernels in sdfgpu_resample.hip and the C ABI in
-// sdfgpu.hip (which owns the scratch and the ordering).
+// tagged_object_collision_map.cpp:399-422) on the GPU: the interface between the kernels in sdfgpu_resample.hip and the host code
+// at the end of that file (which owns the scratch and the ordering).
 //
 // Contract (include/sdfgpu.h "Resample"): every source cell (x, y, z), in x -> y -> z order, goes to
 //   loc = origin * (cell * (i + 0.5), 1),  p = dst_inverse_origin * loc,  idx = floor(p * dst_inv_cell) per axis

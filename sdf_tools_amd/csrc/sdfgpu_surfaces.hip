@@ -1,9 +1,13 @@
 // sdfgpu_surfaces.hip -- the component-surface kernels (sdfgpu_surfaces.hpp) and their launchers.  Compiled beside sdfgpu.hip and
-// linked into the same libsdfgpu.so (sdf_tools_amd/build.py); the C ABI entry points live in sdfgpu.hip.
+// linked into the same libsdfgpu.so (sdf_tools_amd/build.py).
+// The family's host orchestration and C ABI entry points (sdfgpu_component_surfaces*) are at the end of this file, over the handle of
+// sdfgpu_context.hpp.
 //
 // Launch sizes: every workgroup owns kSfTile voxels or elements, so the largest grid (2^32 - 1 voxels) is 2^20 workgroups of 256
 // threads -- far below the 2^32 threads a single launch may have; the scan's table has at most 2^8 x 2^20 entries.
+#include "sdfgpu_context.hpp"
 #include "sdfgpu_surfaces.hpp"
+#include "sdfgpu.h"
 
 #include <algorithm>
 
@@ -392,3 +396,111 @@ hipError_t sf_launch_sort_pairs(const SfPairSortPlan& sp, int key_bits, void* d_
 }
 
 }  // namespace sdfgpu
+
+// ---- host side: argument checks, orchestration and the C ABI entry points -----------------------------------------------------------
+using namespace sdfgpu;
+
+namespace {
+
+// ---- component surfaces (sdfgpu_surfaces.hpp) -----------------------------------------------------------------------------------
+// Like the topology: only sf_scratch, sf_sort and sf_indices (and, in the host forms, the label / bit staging and the pinned
+// chunks) are used; the SDF builds' scratch, status block and policy are not touched.
+int check_surfaces_args(sdfgpu_handle h, int64_t nx, int64_t ny, int64_t nz, uint32_t max_label, const int64_t* out_counts, bool want_indices,
+                        int64_t capacity, const int64_t* out_total) {
+    if (!out_counts || !out_total) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
+    if (int rc = check_dims_u32(h, nx, ny, nz, kLabelsTail)) return rc;
+    if (max_label == 0xFFFFFFFFu) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "max_label must be below 2^32 - 1");
+    if (want_indices && capacity < 0) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "capacity must not be negative (got %lld)", (long long)capacity);
+    return SDFGPU_OK;
+}
+
+// labels (device) + selection bits (device or null) -> counts (host) and, when asked, the grouped indices: into d_indices
+// (device) or, through sf_indices, into host_indices.  Synchronises `st`.
+int surfaces_impl(sdfgpu_handle h, const uint32_t* d_labels, const uint32_t* d_select, int64_t nx, int64_t ny, int64_t nz, uint32_t max_label,
+                  int64_t* out_counts, uint32_t* d_indices, uint32_t* host_indices, int64_t capacity, int64_t* out_total,
+                  uint32_t* d_surface_bits, hipStream_t st) {
+    const SfPlan plan = sf_plan(nx, ny, nz, max_label);
+    if (int rc = ensure(h, h->sf_scratch, plan.scratch_bytes, "surfaces scratch")) return rc;
+    HIP_TRY(h, sf_launch_flag(plan, d_labels, d_select, d_surface_bits, h->sf_scratch.ptr, st));
+    SfStatus status;
+    HIP_TRY(h, hipMemcpyAsync(&status, static_cast<char*>(h->sf_scratch.ptr) + plan.off_status, sizeof status, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    if (status.err & kSfErrLabel)
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "label %u exceeds max_label %u", status.label_over, max_label);
+    *out_total = (int64_t)status.total;
+    {                                                           // (uint32 counters, widened: every count is below 2^32)
+        std::vector<uint32_t> c32((size_t)max_label + 1);
+        if (int rc = copy_to_host(h, c32.data(), h->sf_scratch.ptr, c32.size() * 4, st)) return rc;
+        for (size_t c = 0; c < c32.size(); ++c) out_counts[c] = (int64_t)c32[c];
+    }
+    if (!d_indices && !host_indices) return SDFGPU_OK;          // counts only
+    if ((uint64_t)capacity < status.total)
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "the index buffer holds %lld indices, the surfaces have %llu (counts and total are valid)",
+                    (long long)capacity, (unsigned long long)status.total);
+    if (status.total == 0) return SDFGPU_OK;
+    if (host_indices) {
+        if (int rc = ensure(h, h->sf_indices, (size_t)status.total * 4, "surfaces indices")) return rc;
+        d_indices = (uint32_t*)h->sf_indices.ptr;
+    }
+    const SfSortPlan sp = sf_sort_plan(plan, status.total);
+    if (int rc = ensure(h, h->sf_sort, sp.bytes, "surfaces sort scratch")) return rc;
+    HIP_TRY(h, sf_launch_sort(plan, sp, d_labels, h->sf_scratch.ptr, h->sf_sort.ptr, d_indices, st));
+    if (host_indices) return copy_to_host(h, host_indices, d_indices, (size_t)status.total * 4, st);
+    HIP_TRY(h, hipStreamSynchronize(st));
+    return SDFGPU_OK;
+}
+
+int surfaces_host(sdfgpu_handle h, const uint32_t* labels, const uint8_t* select, const void* cells, size_t stride, size_t occ_off,
+                  size_t comp_off, int class_mask, int64_t nx, int64_t ny, int64_t nz, uint32_t max_label, int64_t* out_counts,
+                  uint32_t* out_indices, int64_t capacity, int64_t* out_total) {
+    bool selected = false;
+    if (int rc = stage_labels_selection(h, labels, select, cells, stride, occ_off, comp_off, class_mask, nx * ny * nz, &selected)) return rc;
+    return surfaces_impl(h, (const uint32_t*)h->stage_out.ptr, selected ? (const uint32_t*)h->stage_bits.ptr : nullptr, nx, ny, nz,
+                         max_label, out_counts, nullptr, out_indices, capacity, out_total, nullptr, nullptr);
+}
+
+}  // namespace
+
+extern "C" {
+
+int sdfgpu_component_surfaces_device(sdfgpu_handle h, const uint32_t* d_labels, const uint32_t* d_select_bits, int64_t nx, int64_t ny,
+                                     int64_t nz, uint32_t max_label, int64_t* out_counts, uint32_t* d_indices, int64_t capacity,
+                                     int64_t* out_total, uint32_t* d_surface_bits, void* stream) {
+    return rz_wrap(h, stream, [&]() -> int {
+        if (!d_labels) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
+        if ((reinterpret_cast<uintptr_t>(d_labels) | reinterpret_cast<uintptr_t>(d_select_bits) | reinterpret_cast<uintptr_t>(d_indices) |
+             reinterpret_cast<uintptr_t>(d_surface_bits)) & 3)
+            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "d_labels, d_select_bits, d_indices and d_surface_bits must be 4-byte aligned");
+        if (int rc = check_surfaces_args(h, nx, ny, nz, max_label, out_counts, d_indices != nullptr, capacity, out_total)) return rc;
+        HIP_TRY(h, hipSetDevice(h->device));
+        return surfaces_impl(h, d_labels, d_select_bits, nx, ny, nz, max_label, out_counts, d_indices, nullptr, capacity, out_total,
+                             d_surface_bits, (hipStream_t)stream);
+    });
+}
+
+int sdfgpu_component_surfaces(sdfgpu_handle h, const uint32_t* labels, const uint8_t* select_mask, int64_t nx, int64_t ny, int64_t nz,
+                              uint32_t max_label, int64_t* out_counts, uint32_t* out_indices, int64_t capacity, int64_t* out_total) {
+    return rz_wrap(h, nullptr, [&]() -> int {
+        if (!labels) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
+        if (int rc = check_surfaces_args(h, nx, ny, nz, max_label, out_counts, out_indices != nullptr, capacity, out_total)) return rc;
+        HIP_TRY(h, hipSetDevice(h->device));
+        return surfaces_host(h, labels, select_mask, nullptr, 0, 0, 0, 7, nx, ny, nz, max_label, out_counts, out_indices, capacity, out_total);
+    });
+}
+
+int sdfgpu_component_surfaces_cells(sdfgpu_handle h, const void* cells, size_t cell_stride, size_t occupancy_offset, size_t component_offset,
+                                    int64_t nx, int64_t ny, int64_t nz, int class_mask, uint32_t max_label, int64_t* out_counts,
+                                    uint32_t* out_indices, int64_t capacity, int64_t* out_total) {
+    return rz_wrap(h, nullptr, [&]() -> int {
+        if (!cells) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
+        if (int rc = check_component_layout(h, cell_stride, occupancy_offset, component_offset)) return rc;
+        if (class_mask < 1 || class_mask > 7)
+            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "class_mask must be a nonzero combination of FILLED (1), EMPTY (2) and UNKNOWN (4)");
+        if (int rc = check_surfaces_args(h, nx, ny, nz, max_label, out_counts, out_indices != nullptr, capacity, out_total)) return rc;
+        HIP_TRY(h, hipSetDevice(h->device));
+        return surfaces_host(h, nullptr, nullptr, cells, cell_stride, occupancy_offset, component_offset, class_mask, nx, ny, nz, max_label,
+                             out_counts, out_indices, capacity, out_total);
+    });
+}
+
+}  // extern "C"

@@ -1,7 +1,7 @@
 // sdfgpu_surfaces.hpp -- the surface voxels of every connected component, grouped by component (CollisionMapGrid /
 // TaggedObjectCollisionMapGrid::ExtractComponentSurfaces, reference src/sdf_tools/collision_map.cpp:697-754,
-// tagged_object_collision_map.cpp:492-550), the interface between the kernels in sdfgpu_surfaces.hip and the C ABI in sdfgpu.hip
-// (which owns the scratch and the ordering).
+// tagged_object_collision_map.cpp:492-550), the interface between the kernels in sdfgpu_surfaces.hip and the host code at the end
+// of that file (which owns the scratch and the ordering).
 //
 // Contract (include/sdfgpu.h "Component surfaces"): voxel v of label c is REPORTED iff it is selected and one of its six face
 // neighbours has another label (out-of-grid voxels are component -1).  Result: per-label counts, and the reported indices

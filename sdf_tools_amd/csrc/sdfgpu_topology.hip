@@ -1,10 +1,14 @@
 // sdfgpu_topology.hip -- the component-topology kernels (sdfgpu_topology.hpp) and their launchers.  Compiled beside sdfgpu.hip
-// and linked into the same libsdfgpu.so (sdf_tools_amd/build.py); the C ABI entry points live in sdfgpu.hip.
+// and linked into the same libsdfgpu.so (sdf_tools_amd/build.py).
+// The family's host orchestration and C ABI entry points (sdfgpu_component_topology*) are at the end of this file, over the handle of
+// sdfgpu_context.hpp.
 //
 // Union-find invariant (the same as sdfgpu_components.hip's): a node word holds kRoot (the node is a root) or a node id BELOW
 // its own, and only ever decreases (a link stores a smaller root into a larger one with atomicMin).  Every parent chain is
 // strictly decreasing until it meets a root, so every find ends, and a surface's root is its smallest node id.
+#include "sdfgpu_context.hpp"
 #include "sdfgpu_topology.hpp"
+#include "sdfgpu.h"
 
 #include <algorithm>
 
@@ -436,3 +440,94 @@ hipError_t tp_launch_surfaces(const TpPlan& p, const uint32_t* d_labels, void* d
 }
 
 }  // namespace sdfgpu
+
+// ---- host side: argument checks, orchestration and the C ABI entry points -----------------------------------------------------------
+using namespace sdfgpu;
+
+namespace {
+
+// ---- component topology (sdfgpu_topology.hpp) ----------------------------------------------------------------------------------
+// Like the components: only tp_scratch and tp_nodes (and, in the host forms, the label / bit staging and the pinned chunks) are
+// used; the SDF builds' scratch, status block and policy are not touched.
+int check_topology_args(sdfgpu_handle h, int64_t nx, int64_t ny, int64_t nz, uint32_t max_label, const int64_t* out_counts) {
+    if (!out_counts) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
+    if (int rc = check_dims_u32(h, nx, ny, nz, kLabelsTail)) return rc;
+    if (max_label == 0xFFFFFFFFu) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "max_label must be below 2^32 - 1");
+    return SDFGPU_OK;
+}
+
+// labels (device) + selection bits (device or null) -> (max_label + 1) x 5 counters (host); synchronises `st`
+int topology_impl(sdfgpu_handle h, const uint32_t* d_labels, const uint32_t* d_select, int64_t nx, int64_t ny, int64_t nz, uint32_t max_label,
+                  int64_t* out_counts, hipStream_t st) {
+    const TpPlan plan = tp_plan(nx, ny, nz, max_label, d_select != nullptr);
+    if (int rc = ensure(h, h->tp_scratch, plan.scratch_bytes, "topology scratch")) return rc;
+    HIP_TRY(h, tp_launch_count(plan, d_labels, d_select, h->tp_scratch.ptr, st));
+    TpStatus status;
+    HIP_TRY(h, hipMemcpyAsync(&status, static_cast<char*>(h->tp_scratch.ptr) + plan.off_status, sizeof status, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    if (status.err & kTpErrLabel)
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "label %u exceeds max_label %u", status.label_over, max_label);
+    if (status.err & kTpErrMixed)
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT,
+                    "label %u has both selected and unselected voxels: its surface is undefined under this selection "
+                    "(labels must come from the connected components of the same occupancy)", status.label_mixed);
+    if (status.nodes > 0xFFFFFFFFull)
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT,
+                    "%llu surface-vertex nodes: more than the 2^32 - 1 that the union-find's 32-bit node ids can number",
+                    (unsigned long long)status.nodes);
+    if (int rc = ensure(h, h->tp_nodes, (size_t)std::max<uint64_t>(status.nodes, 1) * 4, "topology nodes")) return rc;
+    HIP_TRY(h, tp_launch_surfaces(plan, d_labels, h->tp_scratch.ptr, (uint32_t*)h->tp_nodes.ptr, status.nodes, st));
+    // (uint64 counters, read as int64: every count is below 2^32)
+    return copy_to_host(h, out_counts, h->tp_scratch.ptr, ((size_t)max_label + 1) * kTpCounters * 8, st);
+}
+
+// host labels / cell records -> counters
+int topology_host(sdfgpu_handle h, const uint32_t* labels, const uint8_t* select, const void* cells, size_t stride, size_t occ_off,
+                  size_t comp_off, int class_mask, int64_t nx, int64_t ny, int64_t nz, uint32_t max_label, int64_t* out_counts) {
+    bool selected = false;
+    if (int rc = stage_labels_selection(h, labels, select, cells, stride, occ_off, comp_off, class_mask, nx * ny * nz, &selected)) return rc;
+    return topology_impl(h, (const uint32_t*)h->stage_out.ptr, selected ? (const uint32_t*)h->stage_bits.ptr : nullptr, nx, ny, nz,
+                         max_label, out_counts, nullptr);
+}
+
+}  // namespace
+
+extern "C" {
+
+int sdfgpu_component_topology_device(sdfgpu_handle h, const uint32_t* d_labels, const uint32_t* d_select_bits, int64_t nx, int64_t ny,
+                                     int64_t nz, uint32_t max_label, int64_t* out_counts, void* stream) {
+    return rz_wrap(h, stream, [&]() -> int {
+        if (!d_labels) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
+        if ((reinterpret_cast<uintptr_t>(d_labels) | reinterpret_cast<uintptr_t>(d_select_bits)) & 3)
+            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "d_labels and d_select_bits must be 4-byte aligned");
+        if (int rc = check_topology_args(h, nx, ny, nz, max_label, out_counts)) return rc;
+        HIP_TRY(h, hipSetDevice(h->device));
+        return topology_impl(h, d_labels, d_select_bits, nx, ny, nz, max_label, out_counts, (hipStream_t)stream);
+    });
+}
+
+int sdfgpu_component_topology(sdfgpu_handle h, const uint32_t* labels, const uint8_t* select_mask, int64_t nx, int64_t ny, int64_t nz,
+                              uint32_t max_label, int64_t* out_counts) {
+    return rz_wrap(h, nullptr, [&]() -> int {
+        if (!labels) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
+        if (int rc = check_topology_args(h, nx, ny, nz, max_label, out_counts)) return rc;
+        HIP_TRY(h, hipSetDevice(h->device));
+        return topology_host(h, labels, select_mask, nullptr, 0, 0, 0, 7, nx, ny, nz, max_label, out_counts);
+    });
+}
+
+int sdfgpu_component_topology_cells(sdfgpu_handle h, const void* cells, size_t cell_stride, size_t occupancy_offset, size_t component_offset,
+                                    int64_t nx, int64_t ny, int64_t nz, int class_mask, uint32_t max_label, int64_t* out_counts) {
+    return rz_wrap(h, nullptr, [&]() -> int {
+        if (!cells) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
+        if (int rc = check_component_layout(h, cell_stride, occupancy_offset, component_offset)) return rc;
+        if (class_mask < 1 || class_mask > 7)
+            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "class_mask must be a nonzero combination of FILLED (1), EMPTY (2) and UNKNOWN (4)");
+        if (int rc = check_topology_args(h, nx, ny, nz, max_label, out_counts)) return rc;
+        HIP_TRY(h, hipSetDevice(h->device));
+        return topology_host(h, nullptr, nullptr, cells, cell_stride, occupancy_offset, component_offset, class_mask, nx, ny, nz, max_label,
+                             out_counts);
+    });
+}
+
+}  // extern "C"

@@ -1,6 +1,6 @@
 // sdfgpu_topology.hpp -- holes and voids of every connected component (CollisionMapGrid::ComputeComponentTopology, reference
 // src/sdf_tools/collision_map.cpp:620-671 over topology_computation.hpp:297-672), the interface between the kernels in
-// sdfgpu_topology.hip and the C ABI in sdfgpu.hip (which owns the scratch, the node buffer and the ordering).
+// sdfgpu_topology.hip and the host code at the end of that file (which owns the scratch, the node buffer and the ordering).
 //
 // Contract (include/sdfgpu.h "Component topology"): vertex (i, j, k), 0 <= i <= nx ..., is the corner of the voxels
 // (i-1..i, j-1..j, k-1..k), its cube, slot s = 4 dx + 2 dy + dz; out-of-grid voxels are component -1.  A NODE is a pair

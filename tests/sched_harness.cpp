@@ -35,7 +35,7 @@ void nap(std::mt19937& rng, int max_us) {
     if (us > 0) std::this_thread::sleep_for(std::chrono::microseconds(us));
 }
 
-// A DMA engine with two staging buffers and one "event" per buffer, like the pinned chunks + hipEvents of sdfgpu.hip: copies are
+// A DMA engine with two staging buffers and one "event" per buffer, like the pinned chunks + hipEvents of sdfgpu_context.hpp: copies are
 // executed by the engine's own thread some time after they were issued.
 struct FakeDma {
     struct Op { char* dst; const char* src; size_t len; int buf; };

@@ -214,7 +214,7 @@ def doubling_model(nxt):
 
 
 # ---- the five extrema kernels restated on W-bit words ------------------------------------------------------------------------------
-# The accepted grid size, in one place: check_convex_args (sdfgpu.hip) refuses n >= 2^32 - 2, so the largest grid it accepts has
+# The accepted grid size, in one place: check_convex_args (sdfgpu_convex.hip) refuses n >= 2^32 - 2, so the largest grid it accepts has
 # n = 2^32 - 3 voxels.  At word width W that is n = 2^W - CX_N_MARGIN; indices then stay below the three markers.
 CX_N_MARGIN = 3
 

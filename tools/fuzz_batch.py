@@ -53,7 +53,7 @@ PRELUDE_SLOW = ((3, 5, 129), 2)
 
 # ---- the launch plan of DESIGN section 18, restated --------------------------------------------------------------------------------
 def canonical(shape):
-    """singleton axes to the front (sdfgpu.hip canonical_dims)"""
+    """singleton axes to the front (sdfgpu_context.hip canonical_dims)"""
     nx, ny, nz = (int(s) for s in shape)
     if nz == 1:
         nx, ny, nz = 1, nx, ny
