@@ -42,27 +42,29 @@ def reference(occ, keys, rule, grouped, **opts):
     return R.grouped(idx, k) if grouped else (idx, k)
 
 
-def run_host(ctx, cells, shape, rule, stride, grouped, **opts):
+def run_host(ctx, cells, shape, rule, stride, grouped, offsets=(0, 4), **opts):
+    """offsets: (occupancy_offset, key_offset) of the records"""
     before = cells.copy()
-    got = ctx.display_select_cells(cells, shape, rule, stride, 0, 4, grouped=grouped, **dict(DEFAULTS, **opts))
+    got = ctx.display_select_cells(cells, shape, rule, stride, offsets[0], offsets[1], grouped=grouped, **dict(DEFAULTS, **opts))
     assert np.array_equal(cells, before), "the records are read only"
     return got
 
 
-def run_device(ctx, cells, shape, rule, stride, grouped, stream=0, **opts):
+def run_device(ctx, cells, shape, rule, stride, grouped, stream=0, offsets=(0, 4), **opts):
     """count first, then buffers of exactly the total (and the group count) with a sentinel word behind each"""
     o = dict(DEFAULTS, **opts)
+    occ_off, key_off = offsets
     d_cells = dev(cells)
-    total, _ = ctx.display_select_cells_device(d_cells.data_ptr(), shape, rule, stride, 0, 4, stream=stream, **o)
+    total, _ = ctx.display_select_cells_device(d_cells.data_ptr(), shape, rule, stride, occ_off, key_off, stream=stream, **o)
     idx, keys = words(total), words(total)
     if not grouped:
-        t, _ = ctx.display_select_cells_device(d_cells.data_ptr(), shape, rule, stride, 0, 4, d_indices=idx.data_ptr(), d_keys=keys.data_ptr(),
+        t, _ = ctx.display_select_cells_device(d_cells.data_ptr(), shape, rule, stride, occ_off, key_off, d_indices=idx.data_ptr(), d_keys=keys.data_ptr(),
                                                capacity=total, stream=stream, **o)
         assert t == total
         return host_words(idx, total), host_words(keys, total)
     groups = None
     try:                                                        # group capacity 0: the count of groups comes back with the refusal
-        ctx.display_select_cells_device(d_cells.data_ptr(), shape, rule, stride, 0, 4, grouped=True, d_indices=idx.data_ptr(), capacity=total,
+        ctx.display_select_cells_device(d_cells.data_ptr(), shape, rule, stride, occ_off, key_off, grouped=True, d_indices=idx.data_ptr(), capacity=total,
                                         d_group_keys=words(0).data_ptr(), d_group_offsets=words(1).data_ptr(), group_capacity=0,
                                         stream=stream, **o)
         groups = 0
@@ -71,7 +73,7 @@ def run_device(ctx, cells, shape, rule, stride, grouped, stream=0, **opts):
         groups = e.groups
     idx = words(total)
     gk, go = words(groups), words(groups + 1)
-    t, g = ctx.display_select_cells_device(d_cells.data_ptr(), shape, rule, stride, 0, 4, grouped=True, d_indices=idx.data_ptr(),
+    t, g = ctx.display_select_cells_device(d_cells.data_ptr(), shape, rule, stride, occ_off, key_off, grouped=True, d_indices=idx.data_ptr(),
                                            d_keys=keys.data_ptr(), capacity=total, d_group_keys=gk.data_ptr(), d_group_offsets=go.data_ptr(),
                                            group_capacity=groups, stream=stream, **o)
     assert (t, g) == (total, groups)
@@ -84,17 +86,30 @@ def same(what, got, want):
         assert g.dtype == np.uint32 and np.array_equal(g, w), "%s: %s differ (%d got, %d expected)" % (what, name, len(g), len(w))
 
 
-def check(ctx, occ, keys, rule, strides=(8, 16), forms=("host", "device"), groupings=(False, True), **opts):
-    """every stride, form and result form of one selection against the restatement; returns the scan-order reference"""
+def check(ctx, occ, keys, rule, strides=(8, 16), forms=("host", "device"), groupings=(False, True), layouts=None, filler=None, **opts):
+    """every stride, form and result form of one selection against the restatement; returns the scan-order reference.
+    layouts: (stride, occupancy_offset, key_offset) triples in place of `strides` (which puts the occupancy at 0 and the key at 4);
+    filler: filler(stride) -> the words of R.cells_of that are neither field"""
     shape = occ.shape
+    if layouts is None:
+        layouts = [(stride, 0, 4) for stride in strides]
     for grouped in groupings:
         want = reference(occ, keys, rule, grouped, **opts)
-        for stride in strides:
-            cells = R.cells_of(occ, keys, stride)
+        for stride, occ_off, key_off in layouts:
+            cells = R.cells_of(occ, keys, stride, key_off, occ_off, None if filler is None else filler(stride))
             for form in forms:
-                got = (run_host if form == "host" else run_device)(ctx, cells, shape, rule, stride, grouped, **opts)
-                same("%s form, %d-byte records, grouped %s, shape %s, rule %d, %s" % (form, stride, grouped, shape, rule, opts), got, want)
+                got = (run_host if form == "host" else run_device)(ctx, cells, shape, rule, stride, grouped, offsets=(occ_off, key_off), **opts)
+                same("%s form, %d-byte records (occupancy at %d, key at %d), grouped %s, shape %s, rule %d, %s"
+                     % (form, stride, occ_off, key_off, grouped, shape, rule, describe(opts)), got, want)
     return reference(occ, keys, rule, False, **opts)
+
+
+def describe(opts):
+    """the options of a case for a message: a long draw list by its length and ends"""
+    d = opts.get("draw_keys")
+    if d is None or len(d) <= 8:
+        return opts
+    return dict(opts, draw_keys="%d keys %d .. %d" % (len(d), int(d[0]), int(d[-1])))
 
 
 KEY_POOLS = [[0], [5], [0, 1, 2, 3], [0, 1, 255, 256, 300], [0, 7, 65536, 70000, 2 ** 24 + 3], [0, 2 ** 31, 2 ** 32 - 1, 2 ** 32 - 2, 9],

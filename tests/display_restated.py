@@ -8,7 +8,9 @@ Rules, per voxel in scan order (x -> y -> z, z fastest): drawn? and a uint32 key
   key field   key = the record's uint32; drawn iff (draw_keys is None or holds it) and (draw_zero or key != 0) and the class bit
   sdf         drawn iff d <= 0 (NaN is not); key 0
 Results: scan order (indices ascending, keys beside them); grouped (the same pairs by (key, index), group keys, group offsets);
-points cell * (i + 0.5); table colours; the SDF colour map in float64 with the product and the sum rounded separately."""
+points cell * (i + 0.5); table colours; the SDF colour map in float64 with the product and the sum rounded separately.
+cells_of builds the records of a layout (stride, occupancy offset, key offset); filler_words fills their other words with values that
+would change an answer if read by mistake (tests/test_gpu_display_layouts.py pins both against records built by hand)."""
 import numpy as np
 
 F, E, U, N = 0, 1, 2, 3
@@ -140,10 +142,25 @@ def sdf_colors(sdf, alpha):
     return out
 
 
-def cells_of(occ, key, stride, key_offset=4):
-    """records of `stride` bytes: occupancy at 0, the key word at key_offset, other words filled with a pattern"""
+FILLER_WORD = 0x7B7B7B7B
+
+
+def cells_of(occ, key, stride, key_offset=4, occupancy_offset=0, filler=None):
+    """records of `stride` bytes: occupancy at occupancy_offset, the key word at key_offset, the other words from `filler` (uint32,
+    broadcast to [..., stride / 4]; a fixed pattern without one).  With both fields at one offset the key is stored last."""
     occ = np.asarray(occ, np.float32)
-    c = np.full(occ.shape + (stride // 4,), 0x7B7B7B7B, np.uint32)
-    c[..., 0] = occ.view(np.uint32)
+    words = stride // 4
+    assert stride == words * 4 and 0 <= occupancy_offset < stride and 0 <= key_offset < stride and occupancy_offset % 4 == 0 and key_offset % 4 == 0
+    c = np.empty(occ.shape + (words,), np.uint32)
+    c[...] = FILLER_WORD if filler is None else np.asarray(filler, np.uint32)
+    c[..., occupancy_offset // 4] = occ.view(np.uint32)
     c[..., key_offset // 4] = np.asarray(key, np.uint32)
     return np.ascontiguousarray(c)
+
+
+def filler_words(rng, shape, stride, key_pool):
+    """uint32 [shape..., stride / 4] for cells_of: every word drawn from values that would change an answer if a kernel read them for a
+    field -- the floats 0.0, 0.5, 1.0 and NaN as bits (one of each occupancy class), the keys of the case's own pool, and the fixed pattern"""
+    pool = np.concatenate([np.array([0.0, 0.5, 1.0, np.nan], np.float32).view(np.uint32), np.asarray(key_pool, np.uint32).reshape(-1),
+                           np.array([FILLER_WORD], np.uint32)])
+    return rng.choice(pool, size=tuple(shape) + (stride // 4,))

@@ -4,7 +4,10 @@ the numpy restatement (tests/display_restated.py), through the host and the devi
 Chunk sizes of the kernels (sdfgpu_display.hpp, which takes them from sdfgpu_surfaces.hpp): a wave handles 64 voxels a round,
 k_dp_select 256, a tile is kDpTile = kSfTile = 4096 voxels or elements, the scan of the tile counts works in segments of
 kDpScanSeg = kSfScanSeg = 2048 entries, and the sort takes kSfDigitBits = 8 key bits a pass.  test_more_tiles_than_one_scan_segment
-reads the two constants from the headers and runs a grid of just over kDpScanSeg * kDpTile voxels (129 x 256 x 257 with these)."""
+reads the two constants from the headers and runs a grid of just over kDpScanSeg * kDpTile voxels (129 x 256 x 257 with these).
+test_long_draw_lists runs key_listed's lower-bound search on lists of 1 to 65 537 entries; test_lines_of_a_word_and_a_tile and
+test_drawn_total_on_a_tile_edge put grids and drawn totals on, one short of and one past those chunk sizes.  Record layouts other
+than "occupancy at 0, key at 4" are in tests/test_gpu_display_layouts.py, a grid past 2^31 voxels in tests/test_gpu_display_large.py."""
 import os
 import re
 import subprocess
@@ -97,6 +100,125 @@ def test_more_tiles_than_one_scan_segment(gpu):
     C.check(gpu, occ, keys, OCC, class_mask=5, surface_only=True, strides=(8,), forms=("device",), groupings=(True,))
     C.check(gpu, occ, keys, KEY, draw_zero=False, strides=(16,), forms=("device",), groupings=(True,))
     C.check(gpu, occ, keys, KEY, draw_keys=[300], strides=(8,), forms=("host",), groupings=(False,))
+
+
+# ---- long draw lists: the lower-bound search of key_listed --------------------------------------------------------------------------
+DRAW_LENGTHS = [1, 2, 3, 63, 64, 65, 1000, 65537]
+
+
+def _draw_list(rng, length, with_zero, with_last):
+    """ascending uint32 list of `length` entries from a seeded pool in [1000, 2^32 - 1000), 0 and 2^32 - 1 planted on request; with
+    duplicates: the first entry twice from 3 entries on (0 twice where it is planted), the last twice from 5 on, the two-entry
+    list that holds neither end value, and whatever the draw from a pool of half the length repeats"""
+    pool = rng.integers(1000, 2 ** 32 - 1000, size=max(2, length // 2 + 1), dtype=np.uint64)
+    draw = np.sort(rng.choice(pool, size=length))
+    if with_zero:
+        draw[0] = 0
+    if with_last:
+        draw[-1] = 2 ** 32 - 1
+    if length >= 3 or (length == 2 and not (with_zero or with_last)):
+        draw[1] = draw[0]
+    if length >= 5:
+        draw[-2] = draw[-1]
+    draw = draw.astype(np.uint32)
+    assert len(draw) == length and (np.diff(draw.astype(np.int64)) >= 0).all() and (length < 3 or (np.diff(draw.astype(np.int64)) == 0).any())
+    return draw
+
+
+def _keys_around(rng, draw, shape):
+    """a key grid that holds the list's first and last entries, entries in between, values between two entries, values below and
+    above the list (where there are any), 0 and 2^32 - 1; -> (keys, the pool by kind)"""
+    d = np.unique(draw).astype(np.int64)
+    inside = d[rng.integers(0, len(d), size=6)]
+    gaps = np.flatnonzero(np.diff(d) > 1)
+    between = (d[gaps] + 1 + (np.diff(d)[gaps] - 2) // 2)[rng.integers(0, max(len(gaps), 1), size=6 if len(gaps) else 0)]
+    near = np.concatenate([d[:3] + 1, d[-3:] - 1, inside + 1, inside - 1])
+    near = near[(near > d[0]) & (near < d[-1]) & ~np.isin(near, d)]
+    below = np.array([v for v in (0, d[0] - 1, d[0] // 2) if v < d[0]], np.int64)
+    above = np.array([v for v in (2 ** 32 - 1, d[-1] + 1, d[-1] + (2 ** 32 - 1 - d[-1]) // 2) if v > d[-1]], np.int64)
+    kinds = dict(first=d[:1], last=d[-1:], inside=inside, between=np.concatenate([between, near]), below=below, above=above,
+                 ends=np.array([0, 2 ** 32 - 1], np.int64))
+    pool = np.unique(np.concatenate(list(kinds.values()))).astype(np.uint32)
+    keys = rng.choice(pool, size=shape)
+    keys.reshape(-1)[:len(pool)] = pool                             # every value of the pool at least once
+    return keys, kinds
+
+
+@pytest.mark.parametrize("length", DRAW_LENGTHS)
+def test_long_draw_lists(gpu, length):
+    shape = (17, 16, 33)
+    at = DRAW_LENGTHS.index(length)
+    rng = np.random.default_rng(100 + length)
+    occ = _occ(rng, shape)
+    first = (bool(at & 1), bool(at & 2))
+    variants = [first, (not first[0], not first[1])]               # over the lengths: each end value in some lists, absent from others
+    if length <= 2:                                                 # the shortest lists in every variant they can have
+        variants = [(False, False), (True, False), (False, True)] + [(True, True)] * (length == 2)
+    for with_zero, with_last in variants:
+        draw = _draw_list(rng, length, with_zero, with_last)
+        assert (0 in draw) == with_zero and (2 ** 32 - 1 in draw) == with_last
+        keys, kinds = _keys_around(rng, draw, shape)
+        listed = np.isin(keys, draw)
+        assert listed.any() and not listed.all()
+        assert (keys == draw[0]).any() and (keys == draw[-1]).any()
+        if not with_zero:
+            assert len(kinds["below"]) and (keys < draw[0]).any()
+        if not with_last:
+            assert len(kinds["above"]) and (keys > draw[-1]).any()
+        if length >= 3:
+            assert len(kinds["between"]) and ((keys > draw[0]) & (keys < draw[-1]) & ~listed).any()
+        for draw_zero in (False, True):
+            idx, k = C.check(gpu, occ, keys, KEY, draw_keys=draw, draw_zero=draw_zero, strides=(8,))
+            assert len(idx) == int((listed & (draw_zero | (keys != 0))).sum())
+            assert set(np.unique(k).tolist()) == set(np.unique(keys[listed & (draw_zero | (keys != 0))]).tolist())
+    # the list as the only filter and with a class mask beside it; a list that holds every key of the grid; one that holds none
+    C.check(gpu, occ, keys, KEY, draw_keys=draw, class_mask=5, strides=(16,), forms=("device",))
+    C.check(gpu, occ, keys, KEY, draw_keys=np.sort(np.concatenate([draw, np.unique(keys)])), strides=(8,), forms=("device",))
+    none = np.sort(rng.choice(np.setdiff1d(np.arange(2000, 2000 + 4 * length, dtype=np.uint32), keys), size=length))
+    assert len(C.check(gpu, occ, keys, KEY, draw_keys=none, strides=(8,), forms=("host",), groupings=(False,))[0]) == 0
+
+
+# ---- tile and word edges --------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n", [63, 64, 65, 4095, 4096, 4097, 8192])
+def test_lines_of_a_word_and_a_tile(gpu, n):
+    """a wave's ballot is 64 voxels, a tile kDpTile = 4096: lines of those lengths and one more or less, along each axis (the surface
+    rule's neighbours then lie along that axis alone)"""
+    assert _constants()["kDpTile"] == 4096
+    rng = np.random.default_rng(n)
+    for shape in ((1, 1, n), (1, n, 1), (n, 1, 1)):
+        occ = _occ(rng, shape)
+        keys = rng.choice(np.array([0, 3, 300, 2 ** 32 - 1], np.uint32), size=shape)
+        C.check(gpu, occ, keys, OCC, class_mask=7, surface_only=True, strides=(8,), forms=("device",))
+        C.check(gpu, occ, keys, KEY, draw_zero=False, strides=(16,), forms=("device",))
+        idx, _ = C.check(gpu, np.ones(shape, np.float32), keys, KEY, strides=(8,), forms=("device",))     # every voxel drawn: the last lane of the last word
+        assert len(idx) == n and idx[-1] == n - 1
+
+
+@pytest.mark.parametrize("total", [4095, 4096, 4097])
+def test_drawn_total_on_a_tile_edge(gpu, total):
+    """exactly `total` voxels of 17 x 16 x 33 carry a key: the second stage (group starts over the sorted keys) then has a tile that is
+    one short, full, or followed by a tile of one element.  Three groups of 1500, total - 1501 and 1 elements: with 4097 drawn the
+    last group starts exactly at element 4096, the first of the second tile; with 4096 that is where the results end."""
+    tile = _constants()["kDpTile"]
+    assert tile == 4096
+    shape = (17, 16, 33)
+    rng = np.random.default_rng(total)
+    occ = _occ(rng, shape)
+    where = rng.permutation(int(np.prod(shape)))[:total]
+    keys = np.zeros(shape, np.uint32)
+    keys.reshape(-1)[where[:1500]] = 3
+    keys.reshape(-1)[where[1500:total - 1]] = 300
+    keys.reshape(-1)[where[total - 1:]] = 2 ** 32 - 1
+    want = C.reference(occ, keys, KEY, True, draw_zero=False)
+    assert len(want[0]) == total and want[2].tolist() == [3, 300, 2 ** 32 - 1] and want[3].tolist() == [0, 1500, total - 1, total]
+    assert (total - 1 == tile) == (total == 4097)
+    C.check(gpu, occ, keys, KEY, draw_zero=False, strides=(8,), forms=("device",))
+    C.check(gpu, occ, keys, KEY, draw_keys=[3, 300, 2 ** 32 - 1], strides=(16,), forms=("device",))
+    # the same total in scan order under the occupancy rule: exactly `total` filled voxels
+    filled = np.zeros(shape, np.float32)
+    filled.reshape(-1)[where] = 1.0
+    idx, _ = C.check(gpu, filled, keys, OCC, class_mask=1, strides=(8,), forms=("device",))
+    assert len(idx) == total
 
 
 def _both_sdf_forms(gpu, d):
