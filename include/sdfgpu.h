@@ -320,9 +320,15 @@ int sdfgpu_gradient(sdfgpu_handle h, const float* sdf,
  *   d_distance[n]  the estimate, or oob_value where the point is outside the grid; every product and sum is rounded on its own
  *                  (no fused multiply-add).  With world_to_grid = NULL (the identity) or a pure translation (rotation part the
  *                  identity: 1 x + 0 y + 0 z + t is x + t, one rounding) it is bit-equal to the host's EstimateDistance4d; the
- *                  tests pin these two cases.  With a rotation the grid coordinates are the four-term sums above, which the
- *                  host's transform need not round the same way: no bit-level claim is made there
- *   d_gradient[3n] world-frame gradient of the cell holding the point; NaN where the reference returns
+ *                  tests pin these two cases.  With a rotation the grid coordinates are the four-term sums w0 x + w1 y + w2 z + w3,
+ *                  which the host's transform need not round the same way.  What holds there, and is tested against exact
+ *                  rational arithmetic in frames whose nine rotation entries are all nonzero (u = 2^-53, S_i = |w_i0 x| + |w_i1 y|
+ *                  + |w_i2 z| + |w_i3|, S the largest of the three): the cell is the exact one, floor(W (p, 1) / resolution),
+ *                  unless a coordinate is within 8 u S_i / resolution (in cells) of a cell face, where either neighbour may
+ *                  answer (on an outer face: the estimate or oob_value); the distance is within 64 u (1 + S / resolution)
+ *                  sum |D_c| of the exact estimate at the exact grid coordinates, D_c the 8 half-cell-corrected corner values
+ *   d_gradient[3n] world-frame gradient of the cell holding the point, rounded product by product and sum by sum: each component
+ *                  within 4 u sum_j |R_ij| |g_j| of the exactly rotated grid-frame gradient g of that cell; NaN where the reference returns
  *                  an empty vector (outside, or boundary shell without enable_edge_gradients)
  *   d_flags[n]     bit0 = point inside the grid, bit1 = gradient available */
 int sdfgpu_query_points_device(sdfgpu_handle h, const float* d_sdf,

@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+import frame_judge
 import scenes
 from oracle import oracle as O
 from sdf_tools_amd import synth, utils_2d, utils_3d
@@ -130,6 +131,27 @@ def test_device_resident_field_answers_batched_queries():
         else:
             assert np.isinf(dist[i])
     assert inside > 300
+    # dist, grad and flags against the exact judge (tests/frame_judge.py): the marshalling of device_sdf.hpp in the z turn ...
+    w2g, rot = frame_judge.transforms([[0, -1, 0, 0.3], [1, 0, 0, -0.2], [0, 0, 1, 0.1], [0, 0, 0, 1]])
+    sub = slice(0, 1500)                                              # (the judge works in fractions: a third of the points)
+    exact = frame_judge.Exact(host.GetRawDataNumpy(), res, w2g, rot, pts[sub])
+    assert exact.ambiguous().mean() <= frame_judge.AMBIGUITY_CAP
+    got = frame_judge.judge(exact.sdf, res, w2g, rot, pts[sub], True, exact).check(dist[sub], grad[sub], flags[sub])
+    assert 300 < got["inside"] < 1500 and got["unjudged"] == 0
+    # ... and in a frame whose nine rotation entries are all nonzero, on an anisotropic grid
+    shape, gres = frame_judge.FIELDS[0]
+    go = frame_judge.frames()["general"]
+    gg = m.CollisionMapGrid(m.Isometry3d(go), "world", gres, *shape, m.COLLISION_CELL(0.0))
+    gg.SetOccupancyFromNumpy(frame_judge.case_mask(shape).astype(np.float32))
+    gd, _ = gg.ExtractSignedDistanceFieldDevice(float("inf"), False, False)
+    gpts, parts = frame_judge.case_points(shape, gres, go, frame_judge.case_seed("general", shape))
+    w2g, rot = frame_judge.transforms(go)
+    field = gd.Host().GetRawDataNumpy()
+    exact = frame_judge.Exact(field, gres, w2g, rot, gpts)
+    assert exact.ambiguous()[parts["uniform"]].mean() <= frame_judge.AMBIGUITY_CAP
+    for edge in (False, True):
+        got = frame_judge.judge(field, gres, w2g, rot, gpts, edge, exact).check(*gd.QueryBatch(gpts, edge))
+        assert 500 < got["inside"] < len(gpts) and got["unjudged"] == 0
     back = dsdf.Host()
     assert dsdf.HostCopyExists() and np.array_equal(back.GetRawDataNumpy(), host.GetRawDataNumpy())
     assert back.GetFrame() == "world"

@@ -16,6 +16,19 @@ m = load_pysdf_tools()
 
 MODES = [False, True]                      # into_valid_volume_only
 MULTIPLIERS = [0.125, 0.5]
+# "rotated" turns about z, which leaves the z couplings of both transforms at zero; "general" (all nine rotation entries nonzero)
+# and "cyclic" (x -> y -> z -> x, R != R^T) of tests/frame_judge.py do not
+FRAMES = ["identity", "rotated", "general", "cyclic"]
+
+
+def _frame(frame):
+    """(origin, what the frame adds to the seed of a scene's points)"""
+    if frame == "identity":
+        return np.eye(4), 0
+    if frame == "rotated":
+        return rigid(0.6, (-0.4, 1.25, 0.3)), 1
+    import frame_judge
+    return frame_judge.frames()[frame], {"general": 2, "cyclic": 100}[frame]
 
 
 def _field(ctx, sdf, res, origin):
@@ -85,14 +98,14 @@ def ctx():
     c.close()
 
 
-@pytest.mark.parametrize("frame", ["identity", "rotated"])
+@pytest.mark.parametrize("frame", FRAMES)
 @pytest.mark.parametrize("scene", ["bernoulli", "room", "solid_boxes"])
 def test_gpu_equals_host_walk(ctx, scene, frame):
     name, mask, res = next(s for s in _scenes() if s[0] == scene)
-    origin = np.eye(4) if frame == "identity" else rigid(0.6, (-0.4, 1.25, 0.3))
+    origin, seed = _frame(frame)
     sdf, _ = ctx.build(mask, res)
     d, ptr, host = _field(ctx, sdf, res, origin)
-    pts = _points(sdf, res, origin, mask, 1500, 3 * ["bernoulli", "room", "solid_boxes"].index(scene) + (frame == "rotated"))
+    pts = _points(sdf, res, origin, mask, 1500, 3 * ["bernoulli", "room", "solid_boxes"].index(scene) + seed)
     seen = set()
     for valid_only in MODES:
         for md in (0.0, 1.5 * res, 4.0 * res):

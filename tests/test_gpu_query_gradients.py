@@ -9,7 +9,7 @@ import torch
 
 from sdf_tools_amd import capi, synth
 from sdf_tools_amd._bindings import load_pysdf_tools
-from test_gpu_projection import _field, _points, _same
+from test_gpu_projection import FRAMES, _field, _frame, _points, _same
 from test_projection_cpu import inverse, rigid
 
 pytestmark = pytest.mark.gpu
@@ -63,14 +63,14 @@ def ctx():
     c.close()
 
 
-@pytest.mark.parametrize("frame", ["identity", "rotated"])
+@pytest.mark.parametrize("frame", FRAMES)
 @pytest.mark.parametrize("scene", SCENES)
 def test_gpu_equals_host_core(ctx, scene, frame):
     name, mask, res = next(s for s in _scenes() if s[0] == scene)
-    origin = np.eye(4) if frame == "identity" else rigid(0.6, (-0.4, 1.25, 0.3))
+    origin, seed = _frame(frame)
     sdf, _ = ctx.build(mask, res)
     d, ptr, host = _field(ctx, sdf, res, origin)
-    pts = _points(sdf, res, origin, mask, 1500, 3 * SCENES.index(scene) + (frame == "rotated"))
+    pts = _points(sdf, res, origin, mask, 1500, 3 * SCENES.index(scene) + seed)
     seen = set()
     for kind in KINDS:
         for window in (_windows(res, sdf.shape) if kind == capi.QUERY_SMOOTH_GRADIENT else [0.0]):

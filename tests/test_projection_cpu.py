@@ -123,7 +123,31 @@ ALL_MEMBERS = [(k, f) for k in range(4) for f in range(3)]
 # ---- a point already free --------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("res", [1.0, 0.05])
 def test_free_point_takes_no_step_and_comes_back_through_both_transforms(res):
-    origin = rigid(0.3, (1.5, -2.0, 0.25))
+    _free_point(rigid(0.3, (1.5, -2.0, 0.25)), res)
+
+
+@pytest.mark.parametrize("frame", ["general", "about-x", "cyclic"])
+def test_frames_with_z_couplings(frame):
+    """rigid() turns about z: entries [0][2], [1][2], [2][0], [2][1] of both transforms are zero there.  The same claims in frames
+    where they are not (tests/frame_judge.py): eigen_lite's inverse and Transform * vector against inverse() and apply() bit for
+    bit, and the walk along a gradient that has three world components."""
+    import frame_judge                                           # (it imports this module)
+    origin = frame_judge.frames()[frame]
+    _free_point(origin, 0.05)
+    _rotated_and_shifted(origin)
+    f = Field(slab(0.5), 0.5, origin)                            # inside points come back from the valid volume bit-identical
+    rng = np.random.default_rng(3)
+    checked = 0
+    for _ in range(50):
+        g = (rng.uniform(0.01, NX * 0.5 - 0.01), rng.uniform(0.01, NY * 0.5 - 0.01), rng.uniform(0.01, NZ * 0.5 - 0.01))
+        p = apply(origin, g)
+        st, out, steps = f.counted(p, 0.0, 0.125, valid_only=True)
+        assert (st, steps) == (CONVERGED, 0) and bits(out) == bits(p)
+        checked += 1
+    assert checked == 50
+
+
+def _free_point(origin, res):
     f = Field(slab(res), res, origin)
     g = (5.2 * res, 2.3 * res, 1.7 * res)                        # grid frame, d = 4.8 res
     p = apply(origin, g)
@@ -231,7 +255,10 @@ def test_inside_points_come_back_from_the_valid_volume_bit_identical():
 
 # ---- a rotated and shifted origin ---------------------------------------------------------------------------------------------------
 def test_rotated_and_shifted_origin():
-    origin = rigid(0.7, (-3.25, 1.5, 2.0))
+    _rotated_and_shifted(rigid(0.7, (-3.25, 1.5, 2.0)), z_turn=True)
+
+
+def _rotated_and_shifted(origin, z_turn=False):
     inv = inverse(origin)
     f = Field(slab(0.1), 0.1, origin)
     g = (1.43, 0.41, 0.37)                                       # grid frame, 4.3 cells deep
@@ -246,7 +273,11 @@ def test_rotated_and_shifted_origin():
     p = apply(origin, (-0.5, 0.31, 0.22))
     st, out, steps = f.counted(p)
     assert st == CONVERGED and steps == 0
-    assert bits(out) == bits(apply(origin, (0.1 * 1e-4, 0.31, 0.22))) or bits(out) == bits(apply(origin, apply(inv, apply(origin, (0.1 * 1e-4, 0.31, 0.22)))))
+    q = apply(inv, p)                                            # only the coordinate that left the grid is replaced; then the
+    start = apply(origin, (0.1 * 1e-4, q[1], q[2]))              # clamped point goes to the world, back to the grid for the walk
+    assert bits(out) == bits(apply(origin, apply(inv, start)))   # (no step) and to the world again
+    if z_turn:
+        assert bits(out) == bits(apply(origin, (0.1 * 1e-4, 0.31, 0.22))) or bits(out) == bits(apply(origin, apply(inv, apply(origin, (0.1 * 1e-4, 0.31, 0.22)))))
 
 
 # ---- infinite fields ------------------------------------------------------------------------------------------------------------------

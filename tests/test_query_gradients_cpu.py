@@ -143,8 +143,12 @@ def test_slab_known_answers(frame):
 
 def test_autodiff_matches_restatement_bit_for_bit():
     rng = np.random.default_rng(5)
+    import frame_judge                                           # (imports this directory's modules: not at module level)
+    fr = frame_judge.frames()                                    # frames with z couplings, which rigid() leaves at zero
     cases = [((7, 9, 6), 0.05, None), ((11, 5, 8), 0.02, rigid(0.4, (0.2, -0.1, 0.3))), ((20, 40, 1), 0.1, None),
-             ((20, 40, 1), 0.1, rigid(-1.1, (1.0, 2.0, -0.5))), ((1, 1, 9), 0.3, rigid(2.0, (0.0, 0.5, 0.25)))]
+             ((20, 40, 1), 0.1, rigid(-1.1, (1.0, 2.0, -0.5))), ((1, 1, 9), 0.3, rigid(2.0, (0.0, 0.5, 0.25))),
+             ((7, 9, 6), 0.05, fr["general"]), ((11, 5, 8), 0.02, fr["about-x"]), ((9, 4, 7), 0.05, fr["cyclic"]),
+             ((20, 40, 1), 0.1, fr["general"])]
     checked = 0
     for shape, res, origin in cases:
         data = rng.uniform(-3 * res, 5 * res, shape).astype(np.float32)
@@ -167,7 +171,7 @@ def test_autodiff_matches_restatement_bit_for_bit():
             assert np.array_equal(bits(grad[i]), bits(r[1])), (shape, p, grad[i], r[1])
             assert np.array_equal(bits(s.GetAutoDiffGradient(*p)), bits(r[1]))
             checked += 1
-    assert checked > 1000
+    assert checked > 2000
 
 
 def test_autodiff_value_is_estimate_distance():
@@ -254,10 +258,19 @@ def test_smooth_edges_and_refusals():
 
 
 def test_smooth_restated_on_random_field():
+    _smooth_restated(rigid(-0.6, (0.1, 0.2, -0.3)))
+
+
+@pytest.mark.parametrize("frame", ["general", "about-x", "cyclic"])
+def test_smooth_restated_in_frames_with_z_couplings(frame):
+    import frame_judge
+    _smooth_restated(frame_judge.frames()[frame])
+
+
+def _smooth_restated(origin):
     rng = np.random.default_rng(21)
     res = 0.05
     data = rng.uniform(-0.2, 0.3, (9, 8, 10)).astype(np.float32)
-    origin = rigid(-0.6, (0.1, 0.2, -0.3))
     s = field(data, res, origin)
     for w in (res / 8, res, 3 * res):
         pts = [world(origin, tuple(rng.uniform(-0.05, 1.05, 3) * np.array(data.shape) * res)) for _ in range(200)]

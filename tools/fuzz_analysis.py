@@ -9,7 +9,8 @@ output compared bit for bit with its restatement (the checkers of tests/, import
   segments          sdfgpu_convex_segments_cells                                        restated_segments
   projection        sdfgpu_project_points, _device, DeviceSignedDistanceField           the host walk (ProjectCounted4d)
   query_gradients   sdfgpu_query_gradients, _device, DeviceSignedDistanceField          the host core (QueryGradient4d)
-  query_points      sdfgpu_query_points (bit-equal, distance included)                  analysis_scenes.query_points
+  query_points      sdfgpu_query_points in any frame of random_frame                    the exact judge of tests/frame_judge.py;
+                    (identity and translations: bit-equal, distance included)           analysis_scenes.query_points
   gradient          sdfgpu_gradient_device, fp32 and fp64, aligned or not               analysis_scenes.grid_gradient
 
 The operations that use atomics (components, topology, segments) run twice on the same input; both results must match.
@@ -31,6 +32,8 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import analysis_scenes as A  # noqa: E402
+import frame_judge  # noqa: E402
+import resample_restated  # noqa: E402
 from sdf_tools_amd import capi, synth  # noqa: E402
 from test_components_cpu import restated_labels  # noqa: E402
 from test_gpu_components import _all_entry_points as components_all  # noqa: E402
@@ -42,6 +45,10 @@ from test_projection_cpu import inverse, rigid  # noqa: E402
 
 OPS = ["components", "topology", "extrema", "segments", "projection", "query_gradients", "query_points", "gradient"]
 BERNOULLI_P = [0.001, 0.02, 0.1, 0.3, 0.3116, 0.5, 0.7, 0.9, 0.99]
+# The frames' own generator, seeded [seed, tag] in main(): the general-quaternion arm and the frames of op_query_points are drawn
+# from it, so that the scenes, points and parameters that the main generator gives a seed stay what they were before the arm existed.
+FRAME_TAG = 0xF4A3
+frame_rng = None
 
 
 def draw_shape(rng, op):
@@ -108,7 +115,18 @@ def random_quaternion(rng):
     return tuple(float(v) for v in q / np.linalg.norm(q))
 
 
-def random_frame(rng):
+def random_frame(rng, extra=None):
+    """A translation, an exact signed permutation or a turn about z from `rng`; with `extra` (a generator), three times in ten a
+    general quaternion and a translation from `extra` instead: all nine rotation entries nonzero.  What `rng` gives is the same
+    with and without `extra`."""
+    o = _frame_without_z_coupling(rng)
+    if extra is not None and extra.random() < 0.3:
+        q = extra.normal(size=4)
+        return resample_restated.quaternion_origin(tuple(float(v) for v in q), tuple(float(v) for v in extra.uniform(-2.0, 2.0, 3)))
+    return o
+
+
+def _frame_without_z_coupling(rng):
     t = tuple(float(v) for v in rng.uniform(-2.0, 2.0, 3))
     r = rng.random()
     if r < 0.3:
@@ -195,7 +213,7 @@ def op_segments(ctx, rng, mask, res):
 
 def _device_field(ctx, rng, mask, res):
     sdf, _ = ctx.build(mask, res)
-    origin = random_frame(rng)
+    origin = random_frame(rng, frame_rng)
     d, ptr, host = _field(ctx, sdf, res, origin)
     return sdf, origin, d, ptr, host
 
@@ -236,14 +254,19 @@ def _near(a, b):
 
 def op_query_points(ctx, rng, mask, res):
     sdf, _ = ctx.build(mask, res)
-    origin = np.eye(4)
-    origin[:3, 3] = rng.uniform(-2.0, 2.0, 3)
+    rng.uniform(-2.0, 2.0, 3)                               # (the translation this operation drew before its frames had their own generator)
+    origin = random_frame(frame_rng, frame_rng)
     pts = points(rng, sdf, res, origin, mask)
     edge = bool(rng.integers(0, 2))
     oob = float(rng.choice([math.inf, 55.0, -1.0]))
     d_sdf = torch.from_numpy(sdf).cuda()
-    dist, grad, flags = ctx.query_points(d_sdf.data_ptr(), sdf.shape, res, pts, world_to_grid=inverse(origin)[:3], oob_value=oob,
+    w2g, rot = frame_judge.transforms(origin)
+    dist, grad, flags = ctx.query_points(d_sdf.data_ptr(), sdf.shape, res, pts, world_to_grid=w2g, rotation=rot, oob_value=oob,
                                          enable_edge_gradients=edge)
+    # any frame: the exact cell unless rounding can move it, the exact estimate and the exactly rotated gradient within their bounds
+    frame_judge.judge(sdf, res, w2g, rot, pts, edge).check(dist, grad, flags, oob)
+    if not np.array_equal(origin[:3, :3], np.eye(3)):
+        return
     # grid frame: w2g = (I, -t), so the kernel's 1 x + 0 y + 0 z - t is x - t exactly, fused or not (finite points)
     g = pts - origin[:3, 3]
     wd, wg, wf = A.query_points(sdf, res, g, oob, edge)
@@ -288,6 +311,7 @@ def main():
     verbose = bool(os.environ.get("FUZZ_VERBOSE"))
     out_dir = os.environ.get("FUZZ_OUT_DIR", "fuzz_out")
     rng = np.random.default_rng(seed)
+    globals()["frame_rng"] = np.random.default_rng([seed, FRAME_TAG])
     ctx = capi.SdfGpu(0)
     counts = {op: 0 for op in OPS}
     order = []
