@@ -123,9 +123,11 @@ struct Selection {
     std::vector<uint32_t> group_keys, group_offsets;   // grouped form: group g is [group_offsets[g], group_offsets[g + 1])
 };
 
-// One selection on the GPU: a count-only call sizes the buffers, the second call fills them.
-inline Selection SelectCells(const Cells& c, const int rule, const size_t key_offset, const int class_mask, const bool surface_only,
-                             const std::vector<uint32_t>* draw_keys, const bool draw_zero, const bool grouped) {
+// One selection on the GPU: a count-only call sizes the buffers, the second call fills them.  call(handle, list, n_list, grouped, idx,
+// keys, capacity, total, group_keys, group_offsets, group_capacity, groups) is the entry point with its own leading arguments bound;
+// max_groups bounds the number of groups when it is known (0: one per drawn voxel at most).
+template <typename Call>
+inline Selection SelectThrough(const Cells& c, const std::vector<uint32_t>* draw_keys, const bool grouped, const size_t max_groups, Call call) {
     Selection s;
     s.group_offsets.assign(1, 0u);
     if (c.count() <= 0) return s;
@@ -139,28 +141,46 @@ inline Selection SelectCells(const Cells& c, const int rule, const size_t key_of
     const uint32_t* list = draw_keys ? sorted.data() : nullptr;
     const std::shared_ptr<sdf_generation::SharedGpuContext> ctx = sdf_generation::GpuContext::Shared();
     const std::lock_guard<std::mutex> lock(ctx->mutex);
-    auto call = [&](uint32_t* idx, uint32_t* keys, int64_t cap, int64_t* total, uint32_t* gk, uint32_t* go, int64_t gcap, int64_t* groups) {
-        return sdfgpu_display_select_cells(ctx->handle, c.data, c.stride, c.occupancy_offset, key_offset, c.nx, c.ny, c.nz, rule, class_mask,
-                                           surface_only ? 1 : 0, list, (int64_t)sorted.size(), draw_zero ? 1 : 0, idx ? (grouped ? 1 : 0) : 0, idx,
-                                           keys, cap, total, gk, go, gcap, groups);
-    };
     int64_t total = 0, groups = 0;
-    sdf_generation::ThrowOnStatus(ctx->handle, call(nullptr, nullptr, 0, &total, nullptr, nullptr, 0, nullptr));
+    sdf_generation::ThrowOnStatus(ctx->handle, call(ctx->handle, list, (int64_t)sorted.size(), 0, nullptr, nullptr, 0, &total, nullptr, nullptr, 0, nullptr));
     if (total == 0) return s;
     s.indices.resize((size_t)total);
     s.keys.resize((size_t)total);
-    if (grouped) {                                          // (at most one group per drawn voxel; three for the occupancy rule)
-        const size_t gcap = rule == SDFGPU_DISPLAY_OCCUPANCY ? 3 : (size_t)total;
+    if (grouped) {                                          // (at most one group per drawn voxel)
+        const size_t gcap = max_groups ? max_groups : (size_t)total;
         s.group_keys.resize(gcap);
         s.group_offsets.resize(gcap + 1);
     }
-    sdf_generation::ThrowOnStatus(ctx->handle, call(s.indices.data(), s.keys.data(), total, &total, grouped ? s.group_keys.data() : nullptr,
-                                                    grouped ? s.group_offsets.data() : nullptr, (int64_t)s.group_keys.size(), grouped ? &groups : nullptr));
+    sdf_generation::ThrowOnStatus(ctx->handle, call(ctx->handle, list, (int64_t)sorted.size(), grouped ? 1 : 0, s.indices.data(), s.keys.data(), total, &total,
+                                                    grouped ? s.group_keys.data() : nullptr, grouped ? s.group_offsets.data() : nullptr,
+                                                    (int64_t)s.group_keys.size(), grouped ? &groups : nullptr));
     if (grouped) {
         s.group_keys.resize((size_t)groups);
         s.group_offsets.resize((size_t)groups + 1);
     }
     return s;
+}
+
+inline Selection SelectCells(const Cells& c, const int rule, const size_t key_offset, const int class_mask, const bool surface_only,
+                             const std::vector<uint32_t>* draw_keys, const bool draw_zero, const bool grouped) {
+    return SelectThrough(c, draw_keys, grouped, rule == SDFGPU_DISPLAY_OCCUPANCY ? 3 : 0,          // (three keys for the occupancy rule)
+                         [&](sdfgpu_handle h, const uint32_t* list, int64_t n_list, int g, uint32_t* idx, uint32_t* keys, int64_t cap, int64_t* total,
+                             uint32_t* gk, uint32_t* go, int64_t gcap, int64_t* groups) {
+                             return sdfgpu_display_select_cells(h, c.data, c.stride, c.occupancy_offset, key_offset, c.nx, c.ny, c.nz, rule, class_mask,
+                                                                surface_only ? 1 : 0, list, n_list, draw_zero ? 1 : 0, g, idx, keys, cap, total, gk, go,
+                                                                gcap, groups);
+                         });
+}
+
+// The object contours (include/sdfgpu.h "Display export: contours"): cells filled for their own key (unknown cells count as filled,
+// key 0 is never drawn) with a cell that is not within squared offset `reach`.
+inline Selection SelectContour(const Cells& c, const size_t key_offset, const int reach, const std::vector<uint32_t>* draw_keys, const bool grouped) {
+    return SelectThrough(c, draw_keys, grouped, 0,
+                         [&](sdfgpu_handle h, const uint32_t* list, int64_t n_list, int g, uint32_t* idx, uint32_t* keys, int64_t cap, int64_t* total,
+                             uint32_t* gk, uint32_t* go, int64_t gcap, int64_t* groups) {
+                             return sdfgpu_display_select_contour(h, c.data, c.stride, c.occupancy_offset, key_offset, c.nx, c.ny, c.nz, reach, 1, list,
+                                                                  n_list, 0, g, idx, keys, cap, total, gk, go, gcap, groups);
+                         });
 }
 
 // body(begin, end) over [0, n) on a few host threads (one below 2^16 elements): every element is written once, by one thread

@@ -12,7 +12,8 @@
 // :424-490) by sdfgpu_component_topology_cells, and the convex segments (UpdateConvexSegments, :552-654) by
 // sdfgpu_convex_segments_cells, and the surface voxels of each component (ExtractComponentSurfaces, :492-550) by
 // sdfgpu_component_surfaces_cells.  The display export (ExportForDisplay and its kin, :661-1364) selects on the GPU
-// (include/sdfgpu.h "Display export", include/sdf_tools/display.hpp); the four ExportContourOnlyForDisplay overloads are not mirrored.
+// (include/sdfgpu.h "Display export", include/sdf_tools/display.hpp), the four ExportContourOnlyForDisplay overloads (:917-1180) included:
+// a 26-neighbour stencil over the records stands in for their per-object SDFs (include/sdfgpu.h "Display export: contours").
 // Every SDF is built on the GPU through sdfgpu_build_tagged_cells (device-side predicate).
 #pragma once
 #include <cstddef>
@@ -127,7 +128,7 @@ public:
     // ---- display export (reference tagged_object_collision_map.cpp:661-1364; include/sdf_tools/display.hpp) ---------------------------
     // Which cells are drawn and in which order comes from the GPU (include/sdfgpu.h "Display export", rule KEY_FIELD on object_id or
     // convex_segment, OCCUPANCY for the occupancy form); a cell whose colour has alpha <= 0 is not drawn, and the palette gives id 0
-    // alpha 0.  Not mirrored: the four ExportContourOnlyForDisplay overloads.
+    // alpha 0.
     static std_msgs::ColorRGBA GenerateComponentColor(const uint32_t component, const float alpha = 1.0f) { return GenerateUniqueColor(component, alpha); }
     display::Cells DisplayCells() const {
         display::Cells c;
@@ -184,7 +185,9 @@ private:
     // the selection of the colour-map forms: every object whose colour is visible (the GPU draws all ids, 0 only when the map makes
     // it visible; objects that the map hides are dropped here)
     display::Selection SelectMapped(const std::map<uint32_t, std_msgs::ColorRGBA>& color_map, const bool grouped) const {
-        display::Selection s = SelectObjects(nullptr, MappedColor(color_map, 0u).a > 0.0f, grouped);
+        return DropHidden(SelectObjects(nullptr, MappedColor(color_map, 0u).a > 0.0f, grouped), color_map, grouped);
+    }
+    static display::Selection DropHidden(display::Selection s, const std::map<uint32_t, std_msgs::ColorRGBA>& color_map, const bool grouped) {
         std::vector<uint32_t> hidden;
         for (const auto& kv : color_map) if (!(kv.second.a > 0.0f) && kv.first != 0u) hidden.push_back(kv.first);
         if (hidden.empty() || s.indices.empty()) return s;
@@ -232,6 +235,67 @@ public:
         for (const auto& kv : color_map) first.push_back(kv.first);
         return UniqueNsMarkers(SelectMapped(color_map, true), first, true, [&](const uint32_t key) { return MappedColor(color_map, key); });
     }
+    // ---- contours (reference :917-1180) --------------------------------------------------------------------------------------------
+    // The reference builds MakeObjectSDFs(ids, unknown_is_filled = true, add_virtual_border = false) and draws a cell iff its own
+    // object's distance lies in (-1.9 resolution, 0): the cells within squared distance `reach` of a cell that is not theirs
+    // (sdfgpu_display_contour_reach; 3 at every ordinary resolution), which the GPU finds by a 26-neighbour stencil without any SDF.
+    // Objects: the listed ones, or every id > 0 (MakeAllObjectSDFs drops id 0; a listed id 0 has the palette's alpha 0).  Throws what
+    // MakeObjectSDFs throws on a non-uniform grid.
+private:
+    int ContourReach() const {
+        const Eigen::Vector3d cell_sizes = GetCellSizes();
+        if ((cell_sizes.x() != cell_sizes.y()) || (cell_sizes.x() != cell_sizes.z()))
+            throw std::invalid_argument("Grid must have uniform resolution");
+        int reach = 0;
+        if (sdfgpu_display_contour_reach(GetResolution(), &reach) != SDFGPU_OK) throw std::invalid_argument("sdfgpu_display_contour_reach refused");
+        return reach;
+    }
+    display::Selection SelectContour(const std::vector<uint32_t>* draw, const bool grouped) const {
+        return display::SelectContour(DisplayCells(), offsetof(TAGGED_OBJECT_COLLISION_CELL, object_id), ContourReach(), draw, grouped);
+    }
+    // one marker per drawn object in ascending id (the order of the reference's std::map of SDFs); objects without a drawn cell have none
+    template <typename ColorOf>
+    visualization_msgs::MarkerArray ContourMarkers(const display::Selection& s, ColorOf color_of) const {
+        visualization_msgs::MarkerArray out;
+        const display::Cells c = DisplayCells();
+        for (size_t g = 0; g < s.group_keys.size(); ++g) {
+            if (s.group_offsets[g] == s.group_offsets[g + 1]) continue;
+            out.markers.push_back(NamedMarker(std::string(kDisplayNs) + "_" + std::to_string(s.group_keys[g])));
+            display::Append(out.markers.back(), c, s, s.group_offsets[g], s.group_offsets[g + 1], true,
+                            [&](const uint32_t key, uint32_t) { return color_of(key); });
+        }
+        return out;
+    }
+
+public:
+    visualization_msgs::Marker ExportContourOnlyForDisplay(const float alpha = 1.0f,
+                                                           const std::vector<uint32_t>& objects_to_draw = std::vector<uint32_t>()) const {
+        visualization_msgs::Marker m = NamedMarker(kDisplayNs);
+        const int reach = ContourReach();                                  // (throws first, as the reference's SDF build does)
+        if (!(alpha > 0.0f) || reach == 0) return m;                       // (every colour would be invisible)
+        const display::Selection s = SelectContour(objects_to_draw.empty() ? nullptr : &objects_to_draw, false);
+        display::Append(m, DisplayCells(), s, 0, s.indices.size(), true, [&](const uint32_t key, uint32_t) { return GenerateComponentColor(key, alpha); });
+        return m;
+    }
+    visualization_msgs::MarkerArray ExportContourOnlyForDisplayUniqueNs(const float alpha = 1.0f,
+                                                                        const std::vector<uint32_t>& objects_to_draw = std::vector<uint32_t>()) const {
+        const int reach = ContourReach();
+        if (!(alpha > 0.0f) || reach == 0) return visualization_msgs::MarkerArray();
+        const display::Selection s = SelectContour(objects_to_draw.empty() ? nullptr : &objects_to_draw, true);
+        return ContourMarkers(s, [&](const uint32_t key) { return GenerateComponentColor(key, alpha); });
+    }
+    // every id > 0 in the map's colour, or the palette's where the map has none; ids the map hides are dropped; id 0 is never drawn,
+    // even when the map makes it visible (unlike ExportForDisplay(color_map))
+    visualization_msgs::Marker ExportContourOnlyForDisplay(const std::map<uint32_t, std_msgs::ColorRGBA>& color_map) const {
+        visualization_msgs::Marker m = NamedMarker(kDisplayNs);
+        const display::Selection s = DropHidden(SelectContour(nullptr, false), color_map, false);
+        display::Append(m, DisplayCells(), s, 0, s.indices.size(), true, [&](const uint32_t key, uint32_t) { return MappedColor(color_map, key); });
+        return m;
+    }
+    visualization_msgs::MarkerArray ExportContourOnlyForDisplayUniqueNs(const std::map<uint32_t, std_msgs::ColorRGBA>& color_map) const {
+        return ContourMarkers(DropHidden(SelectContour(nullptr, true), color_map, true), [&](const uint32_t key) { return MappedColor(color_map, key); });
+    }
+
     visualization_msgs::Marker ExportForDisplayOccupancyOnly(const std_msgs::ColorRGBA& collision_color, const std_msgs::ColorRGBA& free_color,
                                                              const std_msgs::ColorRGBA& unknown_color) const {
         return display::ExportOccupancy(NamedMarker("tagged_object_collision_map_occupancy_display"), DisplayCells(), collision_color, free_color,

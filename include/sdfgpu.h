@@ -801,6 +801,36 @@ int sdfgpu_display_sdf_colors_device(sdfgpu_handle h, const float* d_sdf, int64_
                                      void* stream);
 int sdfgpu_display_sdf_colors(sdfgpu_handle h, const float* sdf, int64_t nx, int64_t ny, int64_t nz, float alpha, float* out_colors);
 
+/* ---------------------------------------------------------------------------
+ * Display export: contours -- the device side of TaggedObjectCollisionMapGrid::ExportContourOnlyForDisplay and its kin (reference
+ * tagged_object_collision_map.cpp:917-1180): the outline of every object, without a distance field.  DESIGN.md section 25.
+ * The reference builds one SDF per object (unknown cells filled, no virtual border) and draws a cell iff its own object's distance
+ * lies in (-1.9 resolution, 0).  That field is an exact EDT, so the test admits only cells whose squared distance D, in cells, to
+ * the nearest cell that is not filled for the object is at most `reach`, a number in 0 .. 3 that depends on the resolution alone:
+ *   sdfgpu_display_contour_reach(cell_size, out_reach): host only, no handle.  The largest D in {1, 2, 3} with
+ *     dist < 0.0 && dist > bdy for dist = -(float)(sqrt((double)D) * cell_size) and (float)bdy = -1.9 * cell_size, else 0.  3 at every
+ *     ordinary size; less only where dist underflows or overflows (2^-149: 2; 1.5 * 2^127: 1; 2^-160, 2^128: 0).  NaN, zero and
+ *     negative sizes fail every comparison and give reach 0 with SDFGPU_OK; only out_reach = NULL is refused.
+ * SELECT (sdfgpu_display_select_contour*).  key = the uint32 at key_offset.  A cell is filled for key k iff its key is k and its
+ *   occupancy is > 0.5, or == 0.5 with unknown_is_filled (NaN never).  Drawn iff the cell is filled for its own key, and (draw_keys
+ *   is NULL or holds the key) and (draw_zero or key != 0), and some in-bounds cell n of the 26 around it is not filled for that key
+ *   at a squared offset |n - c|^2 <= reach: 1 tests the 6 faces, 2 adds the 12 edges, 3 the 8 corners, 0 draws nothing.  Cells
+ *   outside the grid do not exist, so an object that fills the grid draws nothing.  A reach outside 0 .. 3 is refused.
+ * RESULT, capacities, refusals, layout checks (key_offset 4-byte aligned and inside the record), the 2^32 - 1 voxel limit, 4-byte
+ *   pointer alignment and synchronisation: those of sdfgpu_display_select_cells*, word for word; draw_keys is a HOST array of
+ *   ascending keys in both forms.
+ * ------------------------------------------------------------------------- */
+int sdfgpu_display_contour_reach(double cell_size, int* out_reach);
+int sdfgpu_display_select_contour_device(sdfgpu_handle h, const void* d_cells, size_t cell_stride, size_t occupancy_offset, size_t key_offset,
+                                         int64_t nx, int64_t ny, int64_t nz, int reach, int unknown_is_filled, const uint32_t* draw_keys,
+                                         int64_t n_draw_keys, int draw_zero, int grouped, uint32_t* d_indices, uint32_t* d_keys,
+                                         int64_t capacity, int64_t* out_total, uint32_t* d_group_keys, uint32_t* d_group_offsets,
+                                         int64_t group_capacity, int64_t* out_groups, void* stream);
+int sdfgpu_display_select_contour(sdfgpu_handle h, const void* cells, size_t cell_stride, size_t occupancy_offset, size_t key_offset, int64_t nx,
+                                  int64_t ny, int64_t nz, int reach, int unknown_is_filled, const uint32_t* draw_keys, int64_t n_draw_keys,
+                                  int draw_zero, int grouped, uint32_t* out_indices, uint32_t* out_keys, int64_t capacity, int64_t* out_total,
+                                  uint32_t* out_group_keys, uint32_t* out_group_offsets, int64_t group_capacity, int64_t* out_groups);
+
 /* Red zones (round 6).  With SDFGPU_REDZONE=1 in the environment when sdfgpu_create runs -- or after
  * sdfgpu_set_option(h, "redzone", 1) -- every device allocation of the library (scratch fields, status block, extrema slots,
  * staging buffers, sdfgpu_device_malloc memory) carries 4 KiB of canary bytes in front and behind, and every entry point that

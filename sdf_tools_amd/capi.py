@@ -39,6 +39,7 @@ EXPORTS = [
     "sdfgpu_resample_cells_device", "sdfgpu_resample_cells", "sdfgpu_debug_resample_times",
     "sdfgpu_display_select_cells_device", "sdfgpu_display_select_cells", "sdfgpu_display_select_sdf_device", "sdfgpu_display_select_sdf",
     "sdfgpu_display_expand_device", "sdfgpu_display_sdf_colors_device", "sdfgpu_display_sdf_colors",
+    "sdfgpu_display_contour_reach", "sdfgpu_display_select_contour_device", "sdfgpu_display_select_contour",
 ]
 
 # include/sdfgpu.h "Projection": modes and per-point statuses
@@ -159,6 +160,9 @@ def load_library():
     L.sdfgpu_display_expand_device.argtypes = [vp, vp, vp, i64, i64, i64, i64, vp, vp, vp, vp, i64, vp, vp]
     L.sdfgpu_display_sdf_colors_device.argtypes = [vp, vp, i64, i64, i64, ctypes.c_float, vp, vp]
     L.sdfgpu_display_sdf_colors.argtypes = [vp, vp, i64, i64, i64, ctypes.c_float, vp]
+    L.sdfgpu_display_contour_reach.argtypes = [dbl, vp]
+    L.sdfgpu_display_select_contour_device.argtypes = [vp, vp, sz, sz, sz, i64, i64, i64, ci, ci, vp, i64, ci, ci, vp, vp, i64, vp, vp, vp, i64, vp, vp]
+    L.sdfgpu_display_select_contour.argtypes = [vp, vp, sz, sz, sz, i64, i64, i64, ci, ci, vp, i64, ci, ci, vp, vp, i64, vp, vp, vp, i64, vp]
     L.sdfgpu_build_batch_device.argtypes = [vp, vp, i64, i64, i64, i64, dbl, vp, ci, vp, vp]
     L.sdfgpu_get_extrema_batch.argtypes = [vp, i64, vp, vp]
     L.sdfgpu_build_batch.argtypes = [vp, vp, i64, i64, i64, i64, dbl, vp, ci, vp, vp, vp]
@@ -271,6 +275,16 @@ def project_step_limit(shape, stepsize_multiplier=1.0 / 8.0, max_steps=0):
     if rc != 0:
         raise SdfGpuError(rc, "stepsize_multiplier must be positive and finite, max_steps >= 0, dims positive")
     return out.value
+
+
+def display_contour_reach(cell_size):
+    """include/sdfgpu.h "Display export: contours": the largest squared distance D in 0 .. 3 that ExportContourOnlyForDisplay draws
+    at this cell size (the reference's literal float comparisons; NaN and sizes <= 0 give 0).  Host only."""
+    reach = ctypes.c_int(-1)
+    rc = load_library().sdfgpu_display_contour_reach(float(cell_size), ctypes.byref(reach))
+    if rc != 0:
+        raise SdfGpuError(rc, "sdfgpu_display_contour_reach")
+    return int(reach.value)
 
 
 def device_count():
@@ -768,6 +782,55 @@ class SdfGpu:
                 p_dk, n_dk, int(bool(draw_zero)), int(bool(grouped)), d_indices or None, d_keys or None, int(capacity), ctypes.byref(total),
                 d_group_keys or None, d_group_offsets or None, int(group_capacity), ctypes.byref(groups) if grouped else None,
                 stream or None))
+        except SdfGpuError as e:
+            e.total, e.groups = int(total.value), int(groups.value)
+            raise
+        return int(total.value), int(groups.value) if grouped else 0
+
+    def display_select_contour(self, cells, shape, reach, cell_stride=16, occupancy_offset=0, key_offset=8, unknown_is_filled=True,
+                               draw_keys=None, draw_zero=False, grouped=False, capacity=None, group_capacity=None):
+        """The object contours (include/sdfgpu.h "Display export: contours"): cells filled for their own key with a cell that is not
+        within squared offset `reach` (0 .. 3, display_contour_reach).  Arguments and results as display_select_cells."""
+        nx, ny, nz = (int(v) for v in shape)
+        if not (isinstance(cells, np.ndarray) and cells.flags.c_contiguous):
+            raise ValueError("cells must be a C-contiguous numpy array")
+        if cells.nbytes != nx * ny * nz * cell_stride:
+            raise ValueError("cells buffer size does not match shape * cell_stride")
+        total, groups = ctypes.c_int64(-1), ctypes.c_int64(-1)
+        dk, n_dk, p_dk = self._draw_keys(draw_keys)
+        head = (self._h, cells.ctypes.data, cell_stride, occupancy_offset, key_offset, nx, ny, nz, int(reach), int(bool(unknown_is_filled)),
+                p_dk, n_dk, int(bool(draw_zero)))
+        if capacity is None:                                    # a count-only call sizes the arrays
+            self._check(self._lib.sdfgpu_display_select_contour(*head, 0, None, None, 0, ctypes.byref(total), None, None, 0, None))
+        cap = int(total.value) if capacity is None else int(capacity)
+        gcap = cap if group_capacity is None else int(group_capacity)
+        idx, keys = np.empty(max(cap, 1), np.uint32), np.empty(max(cap, 1), np.uint32)
+        gkeys, goffs = np.empty(max(gcap, 1), np.uint32), np.empty(gcap + 1, np.uint32)
+        try:
+            self._check(self._lib.sdfgpu_display_select_contour(
+                *head, int(bool(grouped)), idx.ctypes.data, keys.ctypes.data, cap, ctypes.byref(total), gkeys.ctypes.data if grouped else None,
+                goffs.ctypes.data if grouped else None, gcap, ctypes.byref(groups) if grouped else None))
+        except SdfGpuError as e:
+            e.total, e.groups = int(total.value), int(groups.value)
+            raise
+        t, g = int(total.value), int(groups.value)
+        if grouped:
+            return idx[:t].copy(), keys[:t].copy(), gkeys[:g].copy(), goffs[:g + 1].copy()
+        return idx[:t].copy(), keys[:t].copy()
+
+    def display_select_contour_device(self, d_cells, shape, reach, cell_stride=16, occupancy_offset=0, key_offset=8, unknown_is_filled=True,
+                                      draw_keys=None, draw_zero=False, grouped=False, d_indices=None, d_keys=None, capacity=0,
+                                      d_group_keys=None, d_group_offsets=None, group_capacity=0, stream=0):
+        """Device form of display_select_contour (device addresses as ints; draw_keys is a host list).  Without d_indices only the
+        total is computed.  Returns (total, groups); synchronises `stream`."""
+        nx, ny, nz = (int(v) for v in shape)
+        total, groups = ctypes.c_int64(-1), ctypes.c_int64(-1)
+        dk, n_dk, p_dk = self._draw_keys(draw_keys)
+        try:
+            self._check(self._lib.sdfgpu_display_select_contour_device(
+                self._h, d_cells, cell_stride, occupancy_offset, key_offset, nx, ny, nz, int(reach), int(bool(unknown_is_filled)), p_dk, n_dk,
+                int(bool(draw_zero)), int(bool(grouped)), d_indices or None, d_keys or None, int(capacity), ctypes.byref(total),
+                d_group_keys or None, d_group_offsets or None, int(group_capacity), ctypes.byref(groups) if grouped else None, stream or None))
         except SdfGpuError as e:
             e.total, e.groups = int(total.value), int(groups.value)
             raise

@@ -248,6 +248,22 @@ PYBIND11_MODULE(pysdf_tools, m) {
         .def("ExportForDisplayUniqueNs", [](const TaggedObjectCollisionMapGrid& g, const std::map<uint32_t, Rgba>& color_map) {
             return ReleasedMarkerArray([&]() { return g.ExportForDisplayUniqueNs(ColorMapOf(color_map)); });
         }, py::arg("color_map"))
+        .def("ExportContourOnlyForDisplay", [](const TaggedObjectCollisionMapGrid& g, float alpha, const std::vector<uint32_t>& objects_to_draw) {
+            return ReleasedMarker([&]() { return g.ExportContourOnlyForDisplay(alpha, objects_to_draw); });
+        }, py::arg("alpha") = 1.0f, py::arg("objects_to_draw") = std::vector<uint32_t>(),
+             "(points, colors) of the outline cells of the listed objects (every id > 0 when empty): include/sdfgpu.h \"Display export: contours\"")
+        .def("ExportContourOnlyForDisplay", [](const TaggedObjectCollisionMapGrid& g, const std::map<uint32_t, Rgba>& color_map) {
+            return ReleasedMarker([&]() { return g.ExportContourOnlyForDisplay(ColorMapOf(color_map)); });
+        }, py::arg("color_map"))
+        .def("ExportContourOnlyForDisplayUniqueNs", [](const TaggedObjectCollisionMapGrid& g, float alpha, const std::vector<uint32_t>& objects_to_draw) {
+            return ReleasedMarkerArray([&]() { return g.ExportContourOnlyForDisplayUniqueNs(alpha, objects_to_draw); });
+        }, py::arg("alpha") = 1.0f, py::arg("objects_to_draw") = std::vector<uint32_t>(), "[(ns, points, colors)]: one entry per drawn object, in ascending id")
+        .def("ExportContourOnlyForDisplayUniqueNs", [](const TaggedObjectCollisionMapGrid& g, const std::map<uint32_t, Rgba>& color_map) {
+            return ReleasedMarkerArray([&]() { return g.ExportContourOnlyForDisplayUniqueNs(ColorMapOf(color_map)); });
+        }, py::arg("color_map"))
+        .def("ExportContourOnlyForDisplayInfo", [](const TaggedObjectCollisionMapGrid& g, float alpha) {
+            return MarkerInfo(g.ExportContourOnlyForDisplay(alpha));
+        }, py::arg("alpha") = 1.0f, "header, ns, id, type, action, pose, scale and the element counts of ExportContourOnlyForDisplay")
         .def("ExportForDisplayOccupancyOnly", [](const TaggedObjectCollisionMapGrid& g, const Rgba& c, const Rgba& f, const Rgba& u) {
             return ReleasedMarker([&]() { return g.ExportForDisplayOccupancyOnly(ColorOf(c), ColorOf(f), ColorOf(u)); });
         }, py::arg("collision_color"), py::arg("free_color"), py::arg("unknown_color"))

@@ -119,6 +119,122 @@ __global__ __launch_bounds__(kDpThreads) void k_dp_select(const DpSelect a) {
     }
 }
 
+// ---- k_dp_contour ---------------------------------------------------------------------------------------------------------------
+// The object contours: a cell that is filled for its own key is drawn iff some in-bounds cell n of the 26
+// around it is NOT filled for that key (filled: occ > 0.5, or occ == 0.5 with unknown_is_filled; NaN never) at a squared offset
+// |n - c|^2 <= reach.  Output contract of k_dp_select (bit words, tile counts, total, smallest and largest drawn key).
+// A wave round is 64 consecutive cells of the scan order, so 64 consecutive z (of one row or of several short ones).  A round without
+// a candidate loads nothing more.  Otherwise the nine (dx, dy) rows come in three phases -- the cell's own row, the four rows at
+// dx^2 + dy^2 = 1, the four at 2 -- and a phase starts only while some candidate of the wave is undecided and the reach admits it.
+// Within a phase all loads are issued before any is used: per row every in-grid lane loads the record (x + dx, y + dy, z) -- the
+// lanes' addresses are consecutive records -- and z - 1 / z + 1 of that row come from lanes - 1 / + 1, which hold exactly those cells
+// whenever they lie in the lane's own row; only lane 0 (z - 1) and lane 63 (z + 1) lack such a lane, and ONE more load per row serves
+// both.  Indices are clamped at the grid faces: nothing outside the grid is read.
+struct CtTag { uint32_t key, filled; };
+
+__device__ __forceinline__ CtTag ct_load(const DpSelect& a, uint64_t v) {
+    const float o = __uint_as_float(load_word(a.src, v, a.src.occ_off));
+    CtTag t;
+    t.key = load_word(a.src, v, a.src.key_off);                 // (not behind the occupancy: two independent loads of one record)
+    t.filled = (o > 0.5f || (a.unknown_is_filled && o == 0.5f)) ? 1u : 0u;
+    return t;
+}
+
+struct CtRow { CtTag c, e; bool ok; };                          // the row's cell at this lane's z; lane 0 / 63: the cell at z - 1 / z + 1
+
+struct CtLane { uint32_t x, y, z, key; bool in, has_lo, has_hi; int lane; };
+
+template <bool OWN>
+__device__ __forceinline__ CtRow ct_row_load(const DpSelect& a, const CtLane& l, uint64_t v, CtTag own, int dx, int dy, bool with_dz) {
+    CtRow r;
+    r.ok = l.in && (dx < 0 ? l.x > 0u : dx > 0 ? l.x + 1u < a.nx : true) && (dy < 0 ? l.y > 0u : dy > 0 ? l.y + 1u < a.ny : true);
+    r.c.key = 0u; r.c.filled = 0u;
+    r.e = r.c;
+    const uint64_t nb = OWN ? v : ((uint64_t)(l.x + dx) * a.ny + (uint64_t)(l.y + dy)) * a.nz + l.z;
+    if (OWN) r.c = own;
+    else if (r.ok) r.c = ct_load(a, nb);
+    if (with_dz && r.ok && ((l.lane == 0 && l.has_lo) || (l.lane == 63 && l.has_hi))) r.e = ct_load(a, l.lane == 0 ? nb - 1 : nb + 1);
+    return r;
+}
+
+// does the row show this lane a cell that is not filled for its key?  (whole waves: a ballot and two shuffles)
+template <bool OWN>
+__device__ __forceinline__ bool ct_row_foreign(const CtLane& l, const CtRow& r, bool with_dz) {
+    bool foreign = !OWN && r.ok && !(r.c.filled && r.c.key == l.key);
+    if (with_dz) {                                              // (uniform)
+        const uint64_t fb = __ballot(r.c.filled != 0u);
+        CtTag lo, hi;
+        lo.key = __shfl_up(r.c.key, 1); hi.key = __shfl_down(r.c.key, 1);
+        lo.filled = (uint32_t)(fb >> ((l.lane + 63) & 63)) & 1u; hi.filled = (uint32_t)(fb >> ((l.lane + 1) & 63)) & 1u;
+        if (l.lane == 0) lo = r.e;
+        if (l.lane == 63) hi = r.e;
+        if (r.ok && l.has_lo && !(lo.filled && lo.key == l.key)) foreign = true;
+        if (r.ok && l.has_hi && !(hi.filled && hi.key == l.key)) foreign = true;
+    }
+    return foreign;
+}
+
+// `v` < n in the lanes that are `in`; cand: this lane's cell is filled, listed and not the undrawn key 0.  Called by whole waves
+// with reach >= 1.
+__device__ __forceinline__ bool ct_round(const DpSelect& a, uint64_t v, bool in, CtTag own, bool cand, int lane) {
+    constexpr int kDx[8] = {-1, 1, 0, 0, -1, -1, 1, 1}, kDy[8] = {0, 0, -1, 1, -1, 1, -1, 1};
+    const uint32_t v32 = in ? (uint32_t)v : 0u, t = v32 / a.nz, z = v32 - t * a.nz, x = t / a.ny;     // (v < n < 2^32)
+    CtLane l;
+    l.x = x; l.y = t - x * a.ny; l.z = z; l.key = own.key; l.in = in; l.has_lo = in && z > 0u; l.has_hi = in && z + 1u < a.nz; l.lane = lane;
+    const int reach = a.reach;
+    bool drawn = ct_row_foreign<true>(l, ct_row_load<true>(a, l, v, own, 0, 0, true), true);
+#pragma unroll
+    for (int phase = 0; phase < 2; ++phase) {                   // rows at dx^2 + dy^2 = 1, then 2
+        if (reach < phase + 1 || !__any(cand && !drawn)) break; // (uniform)
+        const bool with_dz = reach >= phase + 2;
+        CtRow r[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) r[j] = ct_row_load<false>(a, l, v, own, kDx[phase * 4 + j], kDy[phase * 4 + j], with_dz);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) drawn |= ct_row_foreign<false>(l, r[j], with_dz);
+    }
+    return cand && drawn;
+}
+
+__global__ __launch_bounds__(kDpThreads) void k_dp_contour(const DpSelect a) {
+    __shared__ uint32_t s_total, s_kmax, s_kinv;
+    const int lane = threadIdx.x & 63;
+    if (threadIdx.x == 0) { s_total = 0u; s_kmax = 0u; s_kinv = 0u; }
+    __syncthreads();
+    uint32_t wtotal = 0, kmax = 0, kinv = 0;
+    for (int r = 0; r < kDpRounds; ++r) {
+        const uint64_t v = (uint64_t)blockIdx.x * kDpTile + (uint64_t)r * kDpThreads + threadIdx.x;
+        const bool in = v < a.n;
+        CtTag own;
+        own.key = 0u; own.filled = 0u;
+        if (in) own = ct_load(a, v);
+        bool cand = in && own.filled && a.reach > 0 && (a.draw_zero || own.key != 0u);
+        if (cand && a.filter) cand = key_listed(a, own.key);
+        bool drawn = false;
+        if (__any(cand)) drawn = ct_round(a, v, in, own, cand, lane);     // (uniform in the wave)
+        const uint64_t bal = __ballot(drawn);
+        if (lane == 0) {                                        // (as in k_dp_select)
+            a.bits[v >> 5] = (uint32_t)bal;
+            a.bits[(v >> 5) + 1] = (uint32_t)(bal >> 32);
+        }
+        wtotal += (uint32_t)__popcll(bal);
+        if (drawn) { kmax = max(kmax, own.key); kinv = max(kinv, ~own.key); }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        kmax = max(kmax, (uint32_t)__shfl_down(kmax, o));
+        kinv = max(kinv, (uint32_t)__shfl_down(kinv, o));
+    }
+    if (lane == 0 && wtotal) { atomicAdd(&s_total, wtotal); atomicMax(&s_kmax, kmax); atomicMax(&s_kinv, kinv); }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        a.tile_counts[blockIdx.x] = s_total;
+        if (s_total) {
+            atomicAdd(a.total, s_total);
+            if (a.key_max) { atomicMax(a.key_max, s_kmax); atomicMax(a.key_max + 1, s_kinv); }
+        }
+    }
+}
+
 // ---- k_dp_compact ---------------------------------------------------------------------------------------------------------------
 // One workgroup of four waves per tile.  Every wave loads the tile's 64 bit words (lane l: word l) and scans their popcounts, so
 // each word's offset is known before any element moves; wave w then places the voxels of words 16 w .. 16 w + 15, one word a round,
@@ -247,6 +363,7 @@ hipError_t dp_launch_select(int rule, const DpSelect& a, hipStream_t s) {
         case kDpRuleKeyField: hipLaunchKernelGGL(k_dp_select<kDpRuleKeyField>, grid, block, 0, s, a); break;
         case kDpRuleSdfNonPositive: hipLaunchKernelGGL(k_dp_select<kDpRuleSdfNonPositive>, grid, block, 0, s, a); break;
         case kDpRuleGroupStart: hipLaunchKernelGGL(k_dp_select<kDpRuleGroupStart>, grid, block, 0, s, a); break;
+        case kDpRuleContour: hipLaunchKernelGGL(k_dp_contour, grid, block, 0, s, a); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -376,7 +493,7 @@ int display_select_impl(sdfgpu_handle h, DpSelect sel, const DisplayRequest& rq,
         sf_launch_scan(counts, tiles, sums, st);
         DpCompact c;
         c.src = sel.src;
-        c.key_mode = rq.rule == kDpRuleOccupancy ? kDpKeyClass : rq.rule == kDpRuleKeyField ? kDpKeyWord : kDpKeyZero;
+        c.key_mode = rq.rule == kDpRuleOccupancy ? kDpKeyClass : rq.rule == kDpRuleKeyField || rq.rule == kDpRuleContour ? kDpKeyWord : kDpKeyZero;
         c.n = n;
         c.bits = bits;
         c.tile_offsets = counts;
@@ -456,6 +573,16 @@ int check_display_cells(sdfgpu_handle h, const void* cells, size_t stride, size_
     return SDFGPU_OK;
 }
 
+// the contour's records: the layout checks of the key-field rule, and a reach of 0 .. 3
+int check_display_contour(sdfgpu_handle h, const void* cells, size_t stride, size_t occ_off, size_t key_off, int64_t nx, int64_t ny, int64_t nz,
+                          int reach, DpSelect& sel) {
+    if (int rc = check_display_cells(h, cells, stride, occ_off, key_off, nx, ny, nz, SDFGPU_DISPLAY_KEY_FIELD, 7, sel)) return rc;
+    if (reach < 0 || reach > 3)
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: the contour's reach must be 0 .. 3 (sdfgpu_display_contour_reach), got %d", reach);
+    sel.reach = reach;
+    return SDFGPU_OK;
+}
+
 int check_display_sdf(sdfgpu_handle h, const float* sdf, int64_t nx, int64_t ny, int64_t nz, DpSelect& sel) {
     if (!sdf) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: null pointer");
     if (int rc = check_dims_u32(h, nx, ny, nz, kDisplayTail)) return rc;
@@ -524,6 +651,67 @@ int sdfgpu_display_select_cells(sdfgpu_handle h, const void* cells, size_t cell_
         if (int rc = copy_from_host(h, h->stage_in.ptr, cells, bytes)) return rc;
         sel.src.cells = static_cast<const char*>(h->stage_in.ptr);
         sel.surface_only = surface_only != 0;
+        sel.draw_zero = draw_zero != 0;
+        return display_select_impl(h, sel, rq, nullptr);
+    });
+}
+
+int sdfgpu_display_contour_reach(double cell_size, int* out_reach) {
+    if (!out_reach) return SDFGPU_ERR_INVALID_ARGUMENT;
+    // the reference's own lines: `const float bdy = -1.9 * GetResolution()`, dist = the finished field of a filled cell at squared
+    // distance D, drawn iff `dist < 0.0 && dist > bdy`.  NaN, zero and negative sizes fail every comparison: reach 0.
+    const float bdy = -1.9 * cell_size;
+    int reach = 0;
+    for (int d = 1; d <= 3; ++d) {
+        const float dist = -(float)(std::sqrt((double)d) * cell_size);
+        if (dist < 0.0 && dist > bdy) reach = d;
+    }
+    *out_reach = reach;
+    return SDFGPU_OK;
+}
+
+int sdfgpu_display_select_contour_device(sdfgpu_handle h, const void* d_cells, size_t cell_stride, size_t occupancy_offset, size_t key_offset,
+                                         int64_t nx, int64_t ny, int64_t nz, int reach, int unknown_is_filled, const uint32_t* draw_keys,
+                                         int64_t n_draw_keys, int draw_zero, int grouped, uint32_t* d_indices, uint32_t* d_keys,
+                                         int64_t capacity, int64_t* out_total, uint32_t* d_group_keys, uint32_t* d_group_offsets,
+                                         int64_t group_capacity, int64_t* out_groups, void* stream) {
+    return rz_wrap(h, stream, [&]() -> int {
+        DpSelect sel;
+        if (int rc = check_display_contour(h, d_cells, cell_stride, occupancy_offset, key_offset, nx, ny, nz, reach, sel)) return rc;
+        if (reinterpret_cast<uintptr_t>(d_cells) & 3) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "display: d_cells must be 4-byte aligned");
+        DisplayRequest rq;
+        rq.rule = kDpRuleContour;
+        rq.draw_keys = draw_keys; rq.n_draw_keys = n_draw_keys; rq.grouped = grouped != 0;
+        rq.indices = d_indices; rq.keys = d_keys; rq.capacity = capacity; rq.out_total = out_total;
+        rq.group_keys = d_group_keys; rq.group_offsets = d_group_offsets; rq.group_capacity = group_capacity; rq.out_groups = out_groups;
+        if (int rc = check_display_request(h, rq)) return rc;
+        HIP_TRY(h, hipSetDevice(h->device));
+        sel.src.cells = static_cast<const char*>(d_cells);
+        sel.unknown_is_filled = unknown_is_filled != 0;
+        sel.draw_zero = draw_zero != 0;
+        return display_select_impl(h, sel, rq, (hipStream_t)stream);
+    });
+}
+
+int sdfgpu_display_select_contour(sdfgpu_handle h, const void* cells, size_t cell_stride, size_t occupancy_offset, size_t key_offset, int64_t nx,
+                                  int64_t ny, int64_t nz, int reach, int unknown_is_filled, const uint32_t* draw_keys, int64_t n_draw_keys,
+                                  int draw_zero, int grouped, uint32_t* out_indices, uint32_t* out_keys, int64_t capacity, int64_t* out_total,
+                                  uint32_t* out_group_keys, uint32_t* out_group_offsets, int64_t group_capacity, int64_t* out_groups) {
+    return rz_wrap(h, nullptr, [&]() -> int {
+        DpSelect sel;
+        if (int rc = check_display_contour(h, cells, cell_stride, occupancy_offset, key_offset, nx, ny, nz, reach, sel)) return rc;
+        DisplayRequest rq;
+        rq.rule = kDpRuleContour;
+        rq.draw_keys = draw_keys; rq.n_draw_keys = n_draw_keys; rq.grouped = grouped != 0; rq.to_host = true;
+        rq.indices = out_indices; rq.keys = out_keys; rq.capacity = capacity; rq.out_total = out_total;
+        rq.group_keys = out_group_keys; rq.group_offsets = out_group_offsets; rq.group_capacity = group_capacity; rq.out_groups = out_groups;
+        if (int rc = check_display_request(h, rq)) return rc;
+        HIP_TRY(h, hipSetDevice(h->device));
+        const size_t bytes = (size_t)sel.n * cell_stride;       // the null stream throughout: records through the cell staging
+        if (int rc = stage_input(h, bytes)) return rc;
+        if (int rc = copy_from_host(h, h->stage_in.ptr, cells, bytes)) return rc;
+        sel.src.cells = static_cast<const char*>(h->stage_in.ptr);
+        sel.unknown_is_filled = unknown_is_filled != 0;
         sel.draw_zero = draw_zero != 0;
         return display_select_impl(h, sel, rq, nullptr);
     });

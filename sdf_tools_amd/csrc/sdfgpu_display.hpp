@@ -11,6 +11,9 @@
 //   sf_launch_sort_pairs   (sdfgpu_surfaces.hpp) the stable radix sort of section 19 on the key bits in which the drawn keys differ
 //   group boundaries: k_dp_select<kDpRuleGroupStart> over the sorted keys (element i starts a group iff i = 0 or its key differs
 //                from the one before), scan, k_dp_compact -> group offsets and group keys: the same three steps once more
+//   k_dp_contour the object contours (kDpRuleContour) under k_dp_select's output contract: a wave round holds 64
+//                consecutive z cells; each lane loads the record at its own z of the nine (dx, dy) rows and takes z - 1 / z + 1 from
+//                the lanes beside it
 //   k_dp_expand  indices (+ keys) -> points (3 doubles) and colours (4 floats) per element
 //   k_dp_minmax, k_dp_sdf_colors   the SDF colour map
 // Voxel indices are uint64 wherever they are formed; counts, offsets and totals fit uint32 (at most 2^32 - 1 voxels).
@@ -29,6 +32,7 @@ constexpr int kDpRuleOccupancy = 0;            // SDFGPU_DISPLAY_OCCUPANCY
 constexpr int kDpRuleKeyField = 1;             // SDFGPU_DISPLAY_KEY_FIELD
 constexpr int kDpRuleSdfNonPositive = 2;       // sdfgpu_display_select_sdf*
 constexpr int kDpRuleGroupStart = 3;           // internal: first elements of the runs of a sorted key array
+constexpr int kDpRuleContour = 4;              // sdfgpu_display_select_contour*: k_dp_contour
 
 constexpr int kDpKeyZero = 0, kDpKeyWord = 1, kDpKeyClass = 2;   // how k_dp_compact finds an element's key again
 
@@ -60,6 +64,8 @@ struct DpSelect {
     uint32_t* tile_counts = nullptr;           // tiles
     uint32_t* total = nullptr;                 // DpStatus::total or ::groups
     uint32_t* key_max = nullptr;               // DpStatus::key_max (key_inv_max follows it) or nullptr
+    int reach = 0;                             // kDpRuleContour: the largest squared offset (0 .. 3) at which a foreign cell draws
+    int unknown_is_filled = 0;                 // kDpRuleContour: occ == 0.5 counts as filled
 };
 
 struct DpCompact {
