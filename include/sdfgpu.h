@@ -138,6 +138,9 @@ int sdfgpu_build_tagged_cells(sdfgpu_handle h, const void* cells,
  * hipStream_t (NULL = default stream).  Asynchronous: kernels are enqueued on
  * `stream`, nothing is copied to the host.  Call sdfgpu_get_extrema afterwards
  * (it synchronises `stream`) to obtain (max, min) of the most recent build.
+ * sdfgpu_get_extrema and sdfgpu_last_dense_certified fail with SDFGPU_ERR_HIP
+ * (and a message) when the build's single stand-by launch gave up its bounded
+ * in-launch wait (option "standby_single"): the field of that build is not valid.
  * ------------------------------------------------------------------------- */
 int sdfgpu_build_device(sdfgpu_handle h, const uint8_t* d_filled,
                         int64_t nx, int64_t ny, int64_t nz,
@@ -901,6 +904,7 @@ int sdfgpu_get_stage_times(sdfgpu_handle h, double* out_ms_sum, int64_t* out_bui
  *  "shell_min_words"         [AB]     128      KD6: open words below which a tile group is left to KF
  *  "standby_far"             [AB]     1        stand-by behind a trusted dense tier = far-field pair (0: fused z+y + marching x, unbounded)
  *  "standby_fold"            [AB]     1        the stand-by x sweep's launch also folds the extrema (one launch less per build)
+ *  "standby_single"          [AB]     1        the stand-by y sweep, x sweep and fold are ONE guarded launch (tiles by ticket; 0: two launches)
  *  "standby_grid"            [AB]     1024     workgroups of the stand-by launches
  *  "ball_serpentine"         [AB]     1        a whole build that rewrites the last build's buffer walks KD's tiles in the opposite order
  *
@@ -939,7 +943,8 @@ int sdfgpu_set_option(sdfgpu_handle h, const char* name, int value);
  * kernel enqueued behind the marching sweep; 0: the marching sweep alone, unbounded).  Bits 8..12 = 1 + the instance of the
  * far-field kernel that the last build or lines call enqueued for its x sweep (0: none): + 1 stage 3, + 2 vector loads, + 4 the
  * looping stand-by form, + 8 512 lanes (lines above 512); 13 / 15 = the instances with a 512- / 1024-voxel line as compile-time
- * constants.  (Enqueued, not necessarily run: whether a guarded launch did work is sdfgpu_last_dense_certified's far flags.) */
+ * constants.  Bit 13 = the stand-by pair of bit 3 was enqueued as ONE launch (option "standby_single").  (Enqueued, not
+ * necessarily run: whether a guarded launch did work is sdfgpu_last_dense_certified's far flags.) */
 int sdfgpu_last_build_info(sdfgpu_handle h, int* out_fused_zy);
 
 /* Which path did the work of the last build (synchronises): bit 0 = the dense kernel decided every voxel

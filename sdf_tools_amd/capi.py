@@ -1112,7 +1112,7 @@ class SdfGpu:
         return {"fused_zy": bool(v.value & 1), "plane16": bool(v.value & 2), "dense": bool(v.value & 4),
                 "standby_far": bool(v.value & 8), "dense3": bool(v.value & 16), "dense3_staged": bool(v.value & 32),
                 "far_predicted": bool(v.value & 64), "lines_tiered": bool(v.value & 128),
-                "far_x_instance": ((v.value >> 8) & 31) - 1}
+                "far_x_instance": ((v.value >> 8) & 31) - 1, "standby_single": bool(v.value & (1 << 13))}
 
     def last_path(self):
         """{'dense_certified', 'far_y', 'far_x'} of the last build (synchronises)."""

@@ -375,12 +375,16 @@ int envelope_args(sdfgpu_handle h, int stage, const DcIo& io, int64_t nx, int64_
     return SDFGPU_OK;
 }
 
+// vector loads: 4 consecutive lines per load, whole tiles, aligned rows
+bool envelope_vector_form(const EnvDcArgs& a) {
+    auto al = [](const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) % n) == 0; };
+    return !a.bits && (a.nz % 4) == 0 && (a.group_lines % kDcLines) == 0 && al(a.in16, 8) && al(a.side_in, 16) && al(a.in_i32, 16);
+}
+
 // Picks the kernel instance for `a` (a.ntiles = the tiles of this launch) and launches it.
 int launch_envelope_kernel(sdfgpu_handle h, int stage, EnvDcArgs& a, bool loop, bool probe, hipStream_t s) {
     constexpr int NL = kDcLines;
-    // vector loads: 4 consecutive lines per load, whole tiles, aligned rows
-    auto al = [](const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) % n) == 0; };
-    const bool vec = !a.bits && (a.nz % 4) == 0 && (a.group_lines % NL) == 0 && al(a.in16, 8) && al(a.side_in, 16) && al(a.in_i32, 16);
+    const bool vec = envelope_vector_form(a);
     const size_t lds = envelope_dc_lds_bytes(a.L, NL);
     // (the kernel is a template over lines per tile and lanes; measured at 512^3: 8-line tiles -- 20 KB of LDS, 7 - 8
     //  workgroups per CU -- with 128 or 256 lanes are 12 - 25 % slower than 16 lines x 256 lanes, 16 lines x 512 lanes
@@ -433,6 +437,41 @@ int launch_envelope(sdfgpu_handle h, int stage, const DcIo& io, int64_t nx, int6
         a.fold_report_mask = kReportDense;
     }
     return launch_envelope_kernel(h, stage, a, io.loop, false, s);
+}
+
+// The stand-by pair behind a trusted dense tier as ONE launch (k_envelope_standby; option "standby_single"): the LOOP-form y sweep
+// (`ke2`), the LOOP-form x sweep (`ke3`) and, when ke3 carries a fold ticket, the end-of-build fold.  The workgroups take the tiles
+// of both stages by ticket (sdfgpu_tickets.hpp); the ticket words live in the status block and the fold clears them with the rest.
+int launch_envelope_standby(sdfgpu_handle h, const DcIo& ke2, const DcIo& ke3, int64_t nx, int64_t ny, int64_t nz, double resolution, int vb,
+                            const uint32_t* guard, hipStream_t s) {
+    if (guard == kUnguarded) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "the single stand-by launch stands behind a guard word (internal)");
+    EnvDcArgs ay{}, ax{};
+    if (int rc = envelope_args(h, 2, ke2, nx, ny, nz, resolution, vb, guard, ay)) return rc;
+    if (int rc = envelope_args(h, 3, ke3, nx, ny, nz, resolution, vb, guard, ax)) return rc;
+    if (ke3.fold_ticket) {
+        ax.fold_status = h->d_small; ax.fold_result = ke3.fold_result; ax.fold_report = ke3.fold_report; ax.fold_ticket = ke3.fold_ticket;
+        ax.fold_report_mask = kReportDense;
+    }
+    StandbyTickets tk{};
+    tk.next = h->d_small + kSwTicketNext; tk.done_y = h->d_small + kSwTicketDoneY; tk.failed = h->d_small + kSwStandbyFailed;
+    tk.t2 = (uint32_t)((ay.ntiles + kStandbyRun - 1) / kStandbyRun); tk.t3 = (uint32_t)((ax.ntiles + kStandbyRun - 1) / kStandbyRun);
+    if (ay.ntiles + ax.ntiles > 0x7fffffffLL) return fail(h, SDFGPU_ERR_UNSUPPORTED_SIZE, "envelope grid too large");
+    // an x tile waits for the y sweep at most this long (100 MHz ticks): the y sweep of the largest grid the kernel takes is tens of ms
+    tk.budget = 2ull * 100000000ull;
+    const bool vec3 = envelope_vector_form(ax);
+    const int which = vec3 ? 1 : 0;
+    h->last.last_dc_x = (1 + (vec3 ? 2 : 0) + 4) + 1;             // (what the x sweep's own LOOP-form launch would have reported)
+    // dynamic LDS: the larger of the two stages' needs (their line lengths differ)
+    const size_t lds = std::max(envelope_dc_lds_bytes(ay.L, kDcLines), envelope_dc_lds_bytes(ax.L, kDcLines));
+    static void (*const kKernels[2])(const EnvDcArgs, const EnvDcArgs, const StandbyTickets) = {k_envelope_standby<false>, k_envelope_standby<true>};
+    if (lds > 64 * 1024 && !h->standby_attr_set[which]) {
+        HIP_TRY(h, hipFuncSetAttribute((const void*)kKernels[which], hipFuncAttributeMaxDynamicSharedMemorySize, (int)kDcMaxDynamicLds));
+        h->standby_attr_set[which] = true;
+    }
+    const int64_t nwg = std::min<int64_t>((int64_t)tk.t2 + tk.t3, h->opt.standby_grid);
+    hipLaunchKernelGGL(kKernels[which], dim3((unsigned)nwg), dim3(256), lds, s, ay, ax, tk);
+    HIP_TRY(h, hipGetLastError());
+    return SDFGPU_OK;
 }
 
 // The tier probe of a far-field sweep: counts, on a sample of the sweep's own input, the voxels whose d^2 reaches the axis'
@@ -880,6 +919,7 @@ int sdfgpu::build_device_impl(sdfgpu_handle h, const Occupancy& occ, int64_t nx,
     HIP_TRY(h, mark(2));
     h->last.last_fused = fused;
     h->last.last_standby = standby;
+    h->last.last_standby_single = false;
     h->last.last_predicted = predicted;
     h->last.last_plane16 = p16;
     if (!fused && !standby) {                                   // (the stand-by pair takes its z distances from the bit field)
@@ -935,12 +975,21 @@ int sdfgpu::build_device_impl(sdfgpu_handle h, const Occupancy& occ, int64_t nx,
             }
         }
         HIP_TRY(h, mark(4));                                    // (stage slot 3, the marching y sweep: nothing launched)
-        if (int rc = launch_envelope(h, 2, ke2, nx, ny, nz, resolution, vb, general_guard, s)) return rc;
-        launched_since_mark = true;
-        HIP_TRY(h, mark(5));
-        HIP_TRY(h, mark(6));                                    // (stage slot 5, the marching x sweep: nothing launched)
-        if (int rc = launch_envelope(h, 3, ke3, nx, ny, nz, resolution, vb, general_guard, s)) return rc;
-        launched_since_mark = true;
+        if (standby && h->opt.standby_single) {
+            // ONE launch: its time goes to the y-envelope slot, the x-envelope slot shares its mark
+            if (int rc = launch_envelope_standby(h, ke2, ke3, nx, ny, nz, resolution, vb, general_guard, s)) return rc;
+            launched_since_mark = true;
+            h->last.last_standby_single = true;
+            HIP_TRY(h, mark(5));
+            HIP_TRY(h, mark(6));
+        } else {
+            if (int rc = launch_envelope(h, 2, ke2, nx, ny, nz, resolution, vb, general_guard, s)) return rc;
+            launched_since_mark = true;
+            HIP_TRY(h, mark(5));
+            HIP_TRY(h, mark(6));                                // (stage slot 5, the marching x sweep: nothing launched)
+            if (int rc = launch_envelope(h, 3, ke3, nx, ny, nz, resolution, vb, general_guard, s)) return rc;
+            launched_since_mark = true;
+        }
     } else {
         // A probe-selected build (`select`): per axis a probe that decides, the marching sweep behind its guard word with bounded
         // scans, and the far-field sweep behind the axis' far flag.  Every other build: one sweep per axis, unbounded scans, no far flag.
@@ -1232,14 +1281,24 @@ int sdfgpu_extrema_from_dsq(uint32_t max_dsq_free, uint32_t max_dsq_filled, doub
     return SDFGPU_OK;
 }
 
+namespace {
+// The single stand-by launch bounds the wait of its x tiles for its y sweep (k_envelope_standby).  A build in which that bound ran
+// out has left a field that is not valid: every read of the build's status block says so.
+int standby_failed(sdfgpu_handle h, const uint32_t* status) {
+    if (status[kSwStandbyFailed] == 0u) return SDFGPU_OK;
+    return fail(h, SDFGPU_ERR_HIP, "the stand-by launch of the last build gave up waiting for its y sweep: the field of that build is not valid");
+}
+}  // namespace
+
 int sdfgpu_get_extrema(sdfgpu_handle h, double* out_max, double* out_min) {
     if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
     if (!h->last.have_result) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "no build has been issued on this handle");
     HIP_TRY(h, hipSetDevice(h->device));
-    uint32_t v[4];
+    uint32_t v[kStatusWords];
     // (the build's own event, not its stream: the stream is the caller's and may be gone by now -- ADVICE r4)
     HIP_TRY(h, h->build_order.host_wait());
     HIP_TRY(h, hipMemcpy(v, h->d_result, sizeof v, hipMemcpyDeviceToHost));
+    if (int rc = standby_failed(h, v)) return rc;
     return sdfgpu_extrema_from_dsq(v[kSwMaxFree], v[kSwMaxFilled], h->last.last_resolution, out_max, out_min);
 }
 
@@ -1998,6 +2057,7 @@ int sdfgpu_set_option(sdfgpu_handle h, const char* name, int value) {
     else if (n == "shell_min_words") o.shell_min_words = value >= 0 ? value : kShellMinWords;
     else if (n == "standby_far") o.standby_far = value != 0;
     else if (n == "standby_fold") o.standby_fold = value != 0;
+    else if (n == "standby_single") o.standby_single = value != 0;
     else if (n == "standby_grid") o.standby_grid = value >= 32 ? value : 1024;
     else if (n == "ball_serpentine") o.ball_serpentine = value != 0;
     // sweeps
@@ -2047,7 +2107,7 @@ int sdfgpu_last_build_info(sdfgpu_handle h, int* out_fused_zy) {
     if (!h || !out_fused_zy) return SDFGPU_ERR_INVALID_ARGUMENT;
     *out_fused_zy = (h->last.last_fused ? 1 : 0) | (h->last.last_plane16 ? 2 : 0) | (h->last.last_dense ? 4 : 0) | (h->last.last_standby ? 8 : 0) |
                     (h->last.last_dense3 ? 16 : 0) | (h->last.last_staged ? 32 : 0) | (h->last.last_predicted ? 64 : 0) |
-                    (h->last.last_lines_tiered ? 128 : 0) | ((h->last.last_dc_x & 31) << 8);
+                    (h->last.last_lines_tiered ? 128 : 0) | ((h->last.last_dc_x & 31) << 8) | (h->last.last_standby_single ? (1 << 13) : 0);
     return SDFGPU_OK;
 }
 
@@ -2055,10 +2115,11 @@ int sdfgpu_last_dense_certified(sdfgpu_handle h, int* out_certified) {
     if (!h || !out_certified) return SDFGPU_ERR_INVALID_ARGUMENT;
     if (!h->last.have_result) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "no build has been issued on this handle");
     HIP_TRY(h, hipSetDevice(h->device));
-    uint32_t v[8];
+    uint32_t v[kStatusWords];
     // (the build's own event, not its stream: the stream is the caller's and may be gone by now -- ADVICE r4)
     HIP_TRY(h, h->build_order.host_wait());
     HIP_TRY(h, hipMemcpy(v, h->d_result, sizeof v, hipMemcpyDeviceToHost));
+    if (int rc = standby_failed(h, v)) return rc;
     // bit 0: dense kernel decided everything; bit 1 / 2: the y / x sweep was redone by the envelope kernel
     uint32_t why = 0;
     HIP_TRY(h, hipMemcpy(&why, h->d_result + kSwReason, sizeof why, hipMemcpyDeviceToHost));

@@ -78,7 +78,7 @@ struct ContextBuffers {
     // Batches of same-shape grids (sdfgpu_batch.hpp).  Scratch of their own: a batch build leaves the single builds' fields, status
     // block, result block and policy as they were.
     DeviceBuffer batch_field;   // int16 [batch][N] signed in-plane d^2 between k_batch_zy and k_batch_x_finish
-    DeviceBuffer batch_ext;     // uint32 [batch][2] per-grid maxima | 24 words: the single builds' result block while a slow-path batch runs
+    DeviceBuffer batch_ext;     // uint32 [batch][2] per-grid maxima | 32 words: the single builds' result block while a slow-path batch runs
     DeviceBuffer batch_res;     // double [batch] per-grid resolutions
     DeviceBuffer batch_gscale;  // GradScale [batch] of sdfgpu_gradient_batch_device
     DeviceBuffer planebits;  // row_any [nx * ny] bytes | plane_any [nx] bytes | row_bits [nx][ceil(ny / 32)] words (k_sweep_z_wave16, k_pack_row_flags, EnvDcArgs)
@@ -120,6 +120,8 @@ struct BuildOptions {
     bool standby_far = true;         // stand-by pipeline behind a trusted dense tier = the far-field pair (bounded whatever the scene
                                      // turns into), not fused K12 + K3/16 with unbounded scans (option "standby_far")
     bool standby_fold = true;        // the stand-by x sweep's launch folds the maxima and publishes the status block itself (option "standby_fold")
+    bool standby_single = true;      // the stand-by pair and the fold are ONE guarded launch whose workgroups take tiles by ticket (k_envelope_standby;
+                                     // option "standby_single"; 0: the y and the x sweep as two launches)
     int standby_grid = 1024;         // workgroups of the stand-by launches (LOOP form; option "standby_grid"): 4 per CU = all resident at once
     // Serpentine tile order (option "ball_serpentine"): a whole build that writes the buffer the handle's last KD launch wrote, at
     // the same size, walks KD's tiles in the opposite order -- it starts on the lines the last one finished with, which are
@@ -159,6 +161,7 @@ struct LastBuild {
     bool last_plane16 = false;
     bool last_dense = false;
     bool last_standby = false;       // the last build carried the far-field stand-by pair behind a trusted dense tier
+    bool last_standby_single = false;  // ... as one launch (k_envelope_standby)
     bool last_dense3 = false, last_staged = false;   // ... ran KD3 + KF in KD's place / carried them behind KD, guarded on its verdict
     bool last_predicted = false;     // the last build took the far-field pair on the strength of the handle's recent builds: no probes, no marching launches
     bool last_lines_tiered = false;  // the last sdfgpu_sweep_x_lines_device call chose its tier on the device (probe / forced tier + far-field kernel behind the marching sweep)
@@ -241,9 +244,10 @@ struct sdfgpu_context : sdfgpu::ContextBuffers {
     int64_t serp_n = 0;
     int serp_flip = 0;
     bool dc_attr_set[16] = {};   // MaxDynamicSharedMemorySize raised, per far-field kernel instantiation
+    bool standby_attr_set[2] = {};   // ... per instance of the single stand-by launch (k_envelope_standby)
     int k1_resident = 0;             // workgroups of k_sweep_z_vec16 the device holds at once (persistent grid size)
     uint32_t* d_slots = nullptr;     // [kSlots][kSlotWords] extrema / flag slots of the dense kernel (kept zero between launches)
-    uint32_t* d_result = nullptr;    // [8] the status block of the last finished build (d_small is cleared by its fold)
+    uint32_t* d_result = nullptr;    // [kStatusWords] the status block of the last finished build (d_small is cleared by its fold)
     bool small_clean = false;        // d_small is all zero (left so by the previous build's fold kernel)
     uint32_t* h_flags_dev = nullptr; // device-side address of h_flags
     uint32_t* h_flags = nullptr;     // pinned host copy of the status block, written by the fold kernel of every build

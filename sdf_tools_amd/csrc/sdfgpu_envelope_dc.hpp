@@ -52,6 +52,7 @@
 #include "sdfgpu_kernels.hpp"
 #include "sdfgpu_sweep_x16.hpp"
 #include "sdfgpu_finish.hpp"
+#include "sdfgpu_tickets.hpp"
 
 namespace sdfgpu {
 
@@ -491,8 +492,13 @@ __global__ __launch_bounds__(256) void k_probe_window(const ProbeArgs a) {
 // LC: 0 = the line's geometry (length, key bits, LDS pitch, chunk count, centre) from the arguments; otherwise the compile-time line length
 // (the launcher picks the instance that matches: 512-voxel lines): loop bounds, the level structure and the LDS addressing are then constants.
 __host__ __device__ constexpr int dc_clog2(int L) { int b = 1; while ((1 << b) < L) ++b; return b; }
-template <int STAGE, bool VEC, int NT = 256, int NL = kDcLines, bool LOOP = false, int WPS = (NL == 8 ? 8 : 4) * (NT / 64) / 4, int LC = 0>
-__global__ __launch_bounds__(NT, WPS) void k_envelope_dc(const EnvDcArgs a) {
+//
+// The body of the kernel behind its guard, as a device function: the tiles of one workgroup, from tile `vblk` on for as long as
+// next(vblk) hands out another one.  k_envelope_dc wraps it (one tile, or the LOOP form's static walk blockIdx.x, + gridDim.x, ...);
+// k_envelope_standby calls the stage 2 and the stage 3 body from ONE launch, a tile per call, in the order of its tickets.  mxF / mxQ
+// collect the stage 3 maxima of the workgroup.  Returns false when the launch was a probe or had nothing to do: the caller leaves at once.
+template <int STAGE, bool VEC, int NT, int NL, bool LOOP, int LC, class Next>
+__device__ __forceinline__ bool envelope_dc_body(const EnvDcArgs& a, uint32_t vblk, int& mxF, int& mxQ, Next next) {
     constexpr int S = NT / NL;              // lanes per line
     constexpr int LPR = NL / 4;             // staging: lanes per row (4 lines each)
     constexpr int LPR_SH = NL == 16 ? 2 : 1;
@@ -501,17 +507,6 @@ __global__ __launch_bounds__(NT, WPS) void k_envelope_dc(const EnvDcArgs a) {
     constexpr int NW = NT / 64;             // waves
     static_assert(NL == 8 || NL == 16, "tile of 8 or 16 lines");
     extern __shared__ __attribute__((aligned(16))) uint32_t dc_smem[];
-    if (a.guard) {
-        const uint32_t gv = *a.guard;
-        if ((gv != 0u) == (a.guard_invert != 0)) {
-            if constexpr (LOOP && STAGE == 3) {
-                if (a.fold_status && blockIdx.x == 0)           // (block-uniform; nothing of this launch writes the slots or the status block)
-                    fold_slots_device<NT>(a.maxdsq, a.fold_status, a.fold_result, a.fold_report, a.fold_report_mask, (int)threadIdx.x);
-            }
-            probe_done(a);
-            return;
-        }
-    }
     const bool i32 = !a.i32_flag || *a.i32_flag != 0u;        // (block-uniform)
     // plane sparsity: the y sweep in front skipped at least one x-plane (launch-uniform; its launch is complete)
     const bool planes = STAGE == 3 && a.plane_any && __hip_atomic_load(a.some_empty, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
@@ -529,9 +524,9 @@ __global__ __launch_bounds__(NT, WPS) void k_envelope_dc(const EnvDcArgs a) {
     //  closes the gate on scenes that do not qualify either way.)
     const bool floorlike = STAGE == 2 && a.row_bits && a.flat_on && (w19 == 0u || (LC ? LC : a.L) > 512);
     const bool flat_gate = floorlike && (a.flat_on == 2 || wgate != 0u);
-    if (a.probe_stride > 0 && a.i32_flag && i32) { probe_done(a); return; }       // the x tier is already decided: no probe
+    if (a.probe_stride > 0 && a.i32_flag && i32) { probe_done(a); return false; }       // the x tier is already decided: no probe
     if (a.probe_stride > 0 && STAGE == 3 && a.decide_small &&
-        __hip_atomic_load(a.decide_small + kSwXNear, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) { probe_done(a); return; }   // ... settled by the y probe
+        __hip_atomic_load(a.decide_small + kSwXNear, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) { probe_done(a); return false; }   // ... settled by the y probe
     const int L = LC ? LC : a.L, B = LC ? dc_clog2(LC ? LC : 2) : a.B, pitch = LC ? ((LC + 63) / 64) * 64 + 2 : a.pitch, M = LC ? (LC + 7) / 8 : a.M,
               h = LC ? (LC + 1) / 2 : a.h;
     const int MA = (L + 63) >> 6;
@@ -545,10 +540,8 @@ __global__ __launch_bounds__(NT, WPS) void k_envelope_dc(const EnvDcArgs a) {
     uint32_t* const fl_mx = misc + 64;                          // [16] ... largest entry
     uint32_t* const flist = misc + kDcMisc;                         // [kDcLocalFilled] filled voxels of pass 0: line << 28 | p << 12 | min(S, kDcLocalSat)
     const int t = threadIdx.x;
-    if (a.ran_flag && blockIdx.x == 0 && t == 0) *a.ran_flag = 1u;
-    int mxF = 0, mxQ = 0;
+    if (a.ran_flag && vblk == 0u && t == 0) *a.ran_flag = 1u;              // (the workgroup that takes the launch's -- the stage's -- first tile)
     const uint32_t nblk = LOOP ? (uint32_t)a.ntiles : gridDim.x;          // "virtual" workgroups = tiles
-    uint32_t vblk = blockIdx.x;
     do {
 
     // tile of this workgroup.  Four consecutive tiles share cache lines (16 lines x 2 B = 32 B of a 128-B line), so an XCD
@@ -572,7 +565,7 @@ __global__ __launch_bounds__(NT, WPS) void k_envelope_dc(const EnvDcArgs a) {
         // an x-plane without a single filled voxel: every voxel of it is free with no site in its plane, and the x sweep will know
         if (rows_known) {
             const int pstate = a.plane_any[o];                  // (block-uniform, a scalar load)
-            if (pstate == 0) { if constexpr (LOOP) continue; else return; }
+            if (pstate == 0) { if constexpr (LOOP) continue; else return false; }
             masked = pstate == 1;                               // (2: every row holds a filled voxel -- nothing to look up, nothing to replace)
             // the plane's row mask through scalar loads (uniform address), then one bit per row this lane will stage: row PP * j + t / LPR
             constexpr int kLPR = NL / 4, kPP = NT / kLPR, kWPJ = kPP / 32;       // words of the mask per staging step (2 at 256 lanes, 4 at 512)
@@ -1450,9 +1443,29 @@ __global__ __launch_bounds__(NT, WPS) void k_envelope_dc(const EnvDcArgs a) {
             if (a.probe_thr3 > 0) atomicAdd(a.probe_out + (kSwProbeX - kSwProbeFar), misc[29]);
         }
         probe_done(a);
-        return;
+        return false;
     }
-    } while (LOOP && (vblk += gridDim.x) < nblk);
+    } while (LOOP && next(vblk));
+    return true;
+}
+
+template <int STAGE, bool VEC, int NT = 256, int NL = kDcLines, bool LOOP = false, int WPS = (NL == 8 ? 8 : 4) * (NT / 64) / 4, int LC = 0>
+__global__ __launch_bounds__(NT, WPS) void k_envelope_dc(const EnvDcArgs a) {
+    if (a.guard) {
+        const uint32_t gv = *a.guard;
+        if ((gv != 0u) == (a.guard_invert != 0)) {
+            if constexpr (LOOP && STAGE == 3) {
+                if (a.fold_status && blockIdx.x == 0)           // (block-uniform; nothing of this launch writes the slots or the status block)
+                    fold_slots_device<NT>(a.maxdsq, a.fold_status, a.fold_result, a.fold_report, a.fold_report_mask, (int)threadIdx.x);
+            }
+            probe_done(a);
+            return;
+        }
+    }
+    const int t = threadIdx.x;
+    int mxF = 0, mxQ = 0;
+    if (!envelope_dc_body<STAGE, VEC, NT, NL, LOOP, LC>(a, blockIdx.x, mxF, mxQ,
+            [&](uint32_t& v) -> bool { return (v += gridDim.x) < (uint32_t)a.ntiles; })) return;      // (asked in the LOOP form only)
     if constexpr (STAGE == 3) {
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) {
@@ -1475,6 +1488,121 @@ __global__ __launch_bounds__(NT, WPS) void k_envelope_dc(const EnvDcArgs a) {
         }
     }
 }
+
+// The stand-by pair behind a trusted dense tier as ONE launch (option "standby_single"): the LOOP-form y sweep, the LOOP-form x sweep and
+// the end-of-build fold.  Behind a certified dense kernel -- nearly every build -- every workgroup reads the guard and leaves, workgroup 0
+// folds on its way out: one guarded launch where there were two.  In the build in which the scene left the dense tier the workgroups take
+// tiles by ticket (sdfgpu_tickets.hpp): [0, t2) the y tiles, [t2, t2 + t3) the x tiles, which wait for ALL y tiles -- an x line crosses
+// every x-plane.  The int32 plane field in between crosses XCDs (private L2s) by the agent-scope release of ticket_arrive and the
+// agent-scope acquire behind ticket_wait, and by nothing else.
+// A ticket is a RUN of kStandbyRun consecutive tiles: four consecutive tiles share cache lines (k_envelope_dc's tile order keeps such a
+// run on one XCD for that reason), and tickets go to whichever workgroup asks next, on any XCD.  With one tile per ticket the build in
+// which a 512^3 scene leaves the dense tier took 1.87 - 1.94 ms against the two launches' 1.29 - 1.32.
+constexpr uint32_t kStandbyRun = 4;
+struct StandbyTickets {
+    uint32_t* next;           // status word kSwTicketNext
+    uint32_t* done_y;         // status word kSwTicketDoneY
+    uint32_t* failed;         // status word kSwStandbyFailed
+    uint32_t t2, t3;          // tickets of the y stage and of the x stage: ceil(tiles / kStandbyRun)
+    uint64_t budget;          // ticks of the constant 100 MHz clock an x tile may wait for the y sweep
+};
+struct TicketOpsDevice {
+    __device__ __forceinline__ uint32_t fetch_add(uint32_t* p) { return __hip_atomic_fetch_add(p, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+    __device__ __forceinline__ uint32_t load(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+    // (the wait BEHIND the fence and in front of the counter's add stays: the fence's own wait is the compiler's to merge away)
+    __device__ __forceinline__ void release() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent"); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+    __device__ __forceinline__ void acquire() { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); }
+    __device__ __forceinline__ void pause() { __builtin_amdgcn_s_sleep(32); }
+    __device__ __forceinline__ uint64_t now() { return wall_clock64(); }
+};
+template <bool VEC3>
+__global__ __launch_bounds__(256, 4) void k_envelope_standby(const EnvDcArgs ay, const EnvDcArgs ax, const StandbyTickets tk) {
+    constexpr int NT = 256, NL = kDcLines;
+    const int t = threadIdx.x;
+    {
+        const uint32_t gv = *ay.guard;                          // (both stages stand behind the same guard word)
+        if ((gv != 0u) == (ay.guard_invert != 0)) {
+            if (ax.fold_status && blockIdx.x == 0)              // (block-uniform; nothing of this launch writes the slots or the status block)
+                fold_slots_device<NT>(ax.maxdsq, ax.fold_status, ax.fold_result, ax.fold_report, ax.fold_report_mask, t);
+            return;
+        }
+    }
+    __shared__ uint32_t sb_ticket, sb_ok;
+    TicketOpsDevice ops;
+    // tile -> the "virtual workgroup" index the body's tile order maps back to that tile (see the body: runs of 4, dealt round-robin)
+    const auto vblk_of = [](uint32_t tile, uint32_t nblk) -> uint32_t {
+        return (nblk & 31u) == 0u ? ((((tile >> 5) << 2) | (tile & 3u)) << 3) | ((tile >> 2) & 7u) : tile;
+    };
+    const uint32_t nty = (uint32_t)ay.ntiles, ntx = (uint32_t)ax.ntiles;
+    int mxF = 0, mxQ = 0;
+    bool y_seen = false;                                        // this workgroup has seen the whole y sweep arrive, and acquired
+    const uint32_t tickets = tk.t2 + tk.t3;
+    for (;;) {
+        if (t == 0) sb_ticket = ticket_claim(ops, tk.next);
+        __syncthreads();
+        const uint32_t ticket = sb_ticket;                      // (block-uniform)
+        __syncthreads();
+        if (ticket >= tickets) break;
+        if (ticket < tk.t2) {
+            uint32_t tile = ticket * kStandbyRun;
+            const uint32_t tend = min(tile + kStandbyRun, nty);
+            (void)envelope_dc_body<2, false, NT, NL, true, 0>(ay, vblk_of(tile, nty), mxF, mxQ, [&](uint32_t& v) -> bool {
+                if (++tile >= tend) return false;
+                v = vblk_of(tile, nty);
+                return true;
+            });
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // every wave: its stores of the tile have left it ...
+            __syncthreads();                                    // ... all of them, before ONE lane releases and counts the run
+            if (t == 0) ticket_arrive(ops, tk.done_y);
+        } else {
+            if (!y_seen) {
+                // No deadlock, whatever the grid and however few of its workgroups are resident: tickets come out in increasing order,
+                // so whoever waits here holds a ticket >= t2 -- every y ticket has then been claimed already, by a workgroup that is
+                // running (it claimed from inside the kernel) and that reaches ticket_arrive without waiting for anybody.  The wait is
+                // bounded all the same (a y sweep of the largest grid is tens of ms; the budget is seconds): when it runs out the
+                // workgroup raises kSwStandbyFailed, which the host turns into an error at its next status read, stops claiming and
+                // still counts itself for the fold -- never a hang and never a silently wrong field.
+                if (t == 0) {
+                    const bool ok = ticket_wait(ops, tk.done_y, tk.t2, tk.budget);
+                    if (!ok) __hip_atomic_store(tk.failed, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    sb_ok = ok ? 1u : 0u;
+                }
+                __syncthreads();
+                if (sb_ok == 0u) break;                         // (block-uniform)
+                ops.acquire();                                  // every wave, once: the plane field is read with plain vector loads from here on
+                y_seen = true;
+            }
+            uint32_t tile = (ticket - tk.t2) * kStandbyRun;
+            const uint32_t tend = min(tile + kStandbyRun, ntx);
+            (void)envelope_dc_body<3, VEC3, NT, NL, true, 0>(ax, vblk_of(tile, ntx), mxF, mxQ, [&](uint32_t& v) -> bool {
+                if (++tile >= tend) return false;
+                v = vblk_of(tile, ntx);
+                return true;
+            });
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        mxF = imax(mxF, __shfl_xor(mxF, off));
+        mxQ = imax(mxQ, __shfl_xor(mxQ, off));
+    }
+    if ((t & 63) == 0) slot_max2(ax.maxdsq, blockIdx.x * (NT / 64) + (t >> 6), mxF, mxQ);
+    if (ax.fold_status) {                                       // (launch-uniform)
+        __shared__ uint32_t fold_last;
+        __threadfence();                                        // this workgroup's slot maxima and ran flags before its ticket
+        __syncthreads();
+        if (t == 0) fold_last = (atomicAdd(ax.fold_ticket, 1u) == gridDim.x - 1u) ? 1u : 0u;
+        __syncthreads();
+        if (fold_last) {                                        // (block-uniform) every other workgroup has finished
+            __threadfence();
+            fold_slots_device<NT>(ax.maxdsq, ax.fold_status, ax.fold_result, ax.fold_report, ax.fold_report_mask, t);   // (clears the tickets with the status block)
+        }
+    }
+}
+#ifndef SDFGPU_ENVELOPE_TU
+extern template __global__ void k_envelope_standby<false>(const EnvDcArgs, const EnvDcArgs, const StandbyTickets);
+extern template __global__ void k_envelope_standby<true>(const EnvDcArgs, const EnvDcArgs, const StandbyTickets);
+#endif
 
 // The instantiations the launcher (launch_envelope, sdfgpu.hip) uses, compiled in their own translation unit
 // (sdfgpu_envelope_tu.hip: the far-field kernel is a third of the library's device code and most of its compile time, and it

@@ -74,7 +74,7 @@ __device__ __forceinline__ void raise_flag(uint32_t* p) {
 // channels, ~16 first-generation waves per slot), and the one-block k_fold_slots launched at the end of every
 // ABI call folds the slots into the caller's {max free, max filled} words and clears them again.
 constexpr int kSlots = 512;
-constexpr int kStatusWords = 24;      // words of the status block that the end-of-build fold publishes and clears
+constexpr int kStatusWords = 32;      // words of the status block that the end-of-build fold publishes and clears
 constexpr int kSlotWords = 32;
 // The context's status block, word by word: every index the host or a kernel uses.  Words below kStatusWords are published and
 // cleared by the end-of-build fold; the flat-tile habit beyond them is the handle's and no build clears it.  (The caller-owned
@@ -102,12 +102,15 @@ enum StatusWord : int {
     kSwReason = 21,                    // why the dense tier gave up
     kSwPlaneEmpty = 22,                // plane sparsity: an x-plane without a filled voxel exists
     kSwFoldTicket = 23,                // workgroups of the stand-by x sweep that have finished: the last one folds
+    kSwTicketNext = 24,                // single stand-by launch (k_envelope_standby): the next tile ticket,
+    kSwTicketDoneY = 25,               // ... y tiles that have arrived (the x tiles wait for all of them),
+    kSwStandbyFailed = 26,             // ... raised by a workgroup whose bounded wait ran out: the build's field is not valid
     kSwFlatScore = 40, kSwFlatGate = 41,   // habit of the two-valued y tiles and the gate it publishes
     kSwReportVerdict = 8               // where the host copy of a dense-tier report carries kSwDenseVerdict
 };
 constexpr uint32_t kReportDense = ((2u << kSwHandoff) - 1u) | (1u << kSwDenseVerdict);   // status words a dense-tier report publishes to the host
 constexpr uint32_t kReportFar = (1u << kSwFarY) | (1u << kSwFarX);                        // ... a far-flag report
-static_assert(kReportDense == 0x1000FFu && kReportFar == 0x30u && kSwFoldTicket < kStatusWords && kSwFlatScore >= kStatusWords, "status words");
+static_assert(kReportDense == 0x1000FFu && kReportFar == 0x30u && kSwFoldTicket < kStatusWords && kSwStandbyFailed < kStatusWords && kSwFlatScore >= kStatusWords, "status words");
 // The read-before-atomic filter of a slot, both words in ONE 8-byte load (a slot is 128 bytes and 128-byte aligned): one L2 round
 // trip instead of two dependent ones.  slot_peek issues the load, slot_max2_seen consumes it -- a kernel whose tail must not wait
 // (KD, KD3) peeks early and works meanwhile.  The slot's words only grow while a kernel runs (the fold that clears them is a launch
@@ -156,7 +159,7 @@ __device__ __forceinline__ void fold_slots_device(uint32_t* __restrict__ slots, 
     }
     if ((t & 63) == 0) { part[2 * (t >> 6)] = f; part[2 * (t >> 6) + 1] = q; }
     __syncthreads();
-    if (t < kStatusWords) {                                    // lanes 0..23 of wave 0: one status word each
+    if (t < kStatusWords) {                                    // lanes 0..31 of wave 0: one status word each
 #pragma unroll
         for (int w = 0; w < NT / 64; ++w) { f = max(f, part[2 * w]); q = max(q, part[2 * w + 1]); }
         if (!result) {
