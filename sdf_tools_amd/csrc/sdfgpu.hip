@@ -172,8 +172,10 @@ int launch_sweep_y(sdfgpu_handle h, const int16_t* d_in, void* d_out, int32_t* d
 }
 
 // K12 launch: mask -> int32 in-plane signed d^2 in one kernel (nz = 512 or 1024, 16-B aligned mask)
+bool fused_zy_nz(int64_t nz) { return nz == 512 || nz == 1024; }       // the kernel's instances
+// (a stage call's test; a whole build's is plan_build's)
 bool fused_zy_eligible(const sdfgpu_context* h, const uint8_t* d_mask, const void* d_out, int64_t nz) {
-    return h->opt.fused_zy && d_mask && (nz == 512 || nz == 1024) &&
+    return h->opt.fused_zy && d_mask && fused_zy_nz(nz) &&
            (reinterpret_cast<uintptr_t>(d_mask) % 16) == 0 && (reinterpret_cast<uintptr_t>(d_out) % 16) == 0;
 }
 
@@ -211,10 +213,6 @@ void launch_x16_variant(const SweepX16Args& a, dim3 grid, dim3 block, bool vb, b
     else if (vb) hipLaunchKernelGGL((k_sweep_x16<V, H, true, false>), grid, block, 0, s, a);
     else if (slab) hipLaunchKernelGGL((k_sweep_x16<V, H, false, true>), grid, block, 0, s, a);
     else hipLaunchKernelGGL((k_sweep_x16<V, H, false, false>), grid, block, 0, s, a);
-}
-
-bool plane16_eligible(const sdfgpu_context* h, int64_t ny, int64_t nz) {
-    return h->opt.plane16_on && (nz % 4) == 0 && ((ny * nz) % 8) == 0;
 }
 
 // The part of a grid an x sweep is launched on: planes [x_global, x_global + nxs) of nx_global with halo planes in front and behind,
@@ -529,14 +527,23 @@ int launch_envelope_probe(sdfgpu_handle h, int stage, const DcIo& io, int64_t nx
     return launch_envelope_kernel(h, stage, a, false, true, s);
 }
 
+// What stands in front of a sweep whose tier is chosen on the device: probe + decision in one launch (the probe's last workgroup
+// decides), or the decision alone when an option forces the tier (nothing to probe).
+int launch_probe_or_decide(sdfgpu_handle h, int stage, const DcIo& io, int64_t nx, int64_t ny, int64_t nz, double resolution, int vb,
+                           const uint32_t* guard, const DcDecide& dec, hipStream_t s) {
+    if (h->opt.force_env < 0) return launch_envelope_probe(h, stage, io, nx, ny, nz, resolution, vb, guard, dec, s);
+    return launch_decide(h, dec, s);
+}
+
 // K0 + KD: pack to bits, then the bit-parallel ball kernel (sdfgpu_dense.hpp)
 constexpr int kBallLanes = 256;                   // lanes per workgroup of KD, KD3, KD6 and KF
 constexpr int kDenseMaxRowWords = 64;             // longest z-row the tuned dense kernels take, in 32-voxel words (DenseArgs::nzw)
 static_assert(kDenseMaxRowWords <= kBallLanes, "a ball-kernel tile holds at least one z-row: launch_ball_dense divides by kBallLanes / nzw");
-bool dense_eligible(const sdfgpu_context* h, int64_t nz) {       // (with or without virtual border: the tuned ball kernel folds it itself)
+bool dense_shape_ok(int64_t nz) {                                // (with or without virtual border: the tuned ball kernel folds it itself)
     const int64_t nzw = nz / 32;
-    return h->opt.dense_on && (nz % 32) == 0 && nzw >= 1 && nzw <= kDenseMaxRowWords && (nzw & (nzw - 1)) == 0;
+    return (nz % 32) == 0 && nzw >= 1 && nzw <= kDenseMaxRowWords && (nzw & (nzw - 1)) == 0;
 }
+bool dense_eligible(const sdfgpu_context* h, int64_t nz) { return h->opt.dense_on && dense_shape_ok(nz); }   // (a stage call's test; a whole build's is plan_build's)
 
 // K0: byte mask or cell records -> bits (a bit field needs no packing: callers do not come here with one)
 int launch_pack_bits(sdfgpu_handle h, const Occupancy& occ, int64_t n, uint32_t* d_bits, hipStream_t s) {
@@ -565,6 +572,14 @@ int fold_slots(sdfgpu_handle h, uint32_t* d_maxdsq, hipStream_t s, uint32_t* res
 // KD6 is for scenes with at most 1 / 8 of their voxels undecided behind KD3: Bernoulli p = 0.01 leaves 8 % (0.78 ms against the
 // far-field pair's 0.96), p = 0.007 17 % (1.07 ms against 0.97)
 constexpr int kShellBudgetDen = 8;
+
+// The ball kernels' level magnitudes, float(sqrt(double(d^2)) * resolution): the 7 levels of KD and the generic kernel (mag[7] = 0:
+// not found) and, where asked for, the 13 levels of KD3 (mag3[13..15] = 0).
+void fill_ball_magnitudes(double resolution, float (&mag)[8], float* mag3 = nullptr) {
+    static const int level3_d2[13] = {1, 2, 3, 4, 5, 6, 8, 9, 10, 11, 12, 13, 14};          // (KD's levels are the first seven)
+    for (int l = 0; l < 8; ++l) mag[l] = l < 7 ? (float)(std::sqrt((double)level3_d2[l]) * resolution) : 0.0f;
+    if (mag3) for (int l = 0; l < 16; ++l) mag3[l] = l < 13 ? (float)(std::sqrt((double)level3_d2[l]) * resolution) : 0.0f;
+}
 
 // How launch_ball_dense runs the dense tier.  The defaults are a stage call's: KD alone on a slab without virtual border, raising
 // *d_uncert itself for what it cannot decide.
@@ -621,11 +636,7 @@ int launch_ball_dense(sdfgpu_handle h, const uint32_t* d_bits, float* d_out, int
     a.log2_ty = 0;
     while ((1 << a.log2_ty) < a.ty) ++a.log2_ty;
     a.inv_hy = (65536 + (a.ty + 2 * R) - 1) / (a.ty + 2 * R);
-    static const int level_d2[7] = {1, 2, 3, 4, 5, 6, 8};
-    for (int l = 0; l < 7; ++l) a.mag[l] = (float)(std::sqrt((double)level_d2[l]) * resolution);
-    a.mag[7] = 0.0f;
-    static const int level3_d2[13] = {1, 2, 3, 4, 5, 6, 8, 9, 10, 11, 12, 13, 14};
-    for (int l = 0; l < 16; ++l) a.mag3[l] = l < 13 ? (float)(std::sqrt((double)level3_d2[l]) * resolution) : 0.0f;
+    fill_ball_magnitudes(resolution, a.mag, a.mag3);
     a.slots = h->d_slots; a.uncertified = d_uncert;
     a.reason = m.early_out ? h->d_small + kSwReason : nullptr;                // (whole builds: the context's status block; stage calls have none)
     a.flip = m.radius == 3 ? 0 : m.flip;
@@ -718,14 +729,13 @@ int launch_ball_dense(sdfgpu_handle h, const uint32_t* d_bits, float* d_out, int
     return SDFGPU_OK;
 }
 
-// Generic dense tier (any nz, virtual border): k_pack_bits_rows + k_ball_dense_generic
+// Generic dense tier (any nz, virtual border): k_pack_bits_rows + k_ball_dense_generic.  `rows`: storage for the bit field, every
+// z-row padded to whole words (BuildPlan::bits_bytes).
 int launch_dense_generic(sdfgpu_handle h, const Occupancy& occ, int64_t nx, int64_t ny, int64_t nz, double resolution, int vb,
-                         float* d_out, uint32_t* d_uncert, hipStream_t s) {
+                         uint32_t* rows, float* d_out, uint32_t* d_uncert, hipStream_t s) {
     const int64_t nzw = (nz + 31) / 32, nrows = nx * ny, nwords = nrows * nzw;
     if (nwords > 0x7fffffffLL * (int64_t)kBlock) return fail(h, SDFGPU_ERR_UNSUPPORTED_SIZE, "dense grid too large");
-    if (int rc = ensure(h, h->bits, (size_t)nwords * 4, "bit field")) return rc;
     const dim3 grid((unsigned)((nwords + kBlock - 1) / kBlock)), block(kBlock);
-    uint32_t* const rows = (uint32_t*)h->bits.ptr;
     if (occ.bits)                                               // (linear bits -> rows padded to whole words)
         hipLaunchKernelGGL(k_pack_bits_rows<BitsLoader>, grid, block, 0, s, BitsLoader{occ.bits}, rows, nrows, (int)nz, (int)nzw);
     else if (occ.cells)
@@ -734,113 +744,37 @@ int launch_dense_generic(sdfgpu_handle h, const Occupancy& occ, int64_t nx, int6
         hipLaunchKernelGGL(k_pack_bits_rows<MaskLoader>, grid, block, 0, s, MaskLoader{occ.mask}, rows, nrows, (int)nz, (int)nzw);
     HIP_TRY(h, hipGetLastError());
     DenseGenArgs a{};
-    a.bits = (const uint32_t*)h->bits.ptr; a.out = d_out;
+    a.bits = rows; a.out = d_out;
     a.nx = (int)nx; a.ny = (int)ny; a.nz = (int)nz; a.nzw = (int)nzw; a.vb = vb;
-    static const int level_d2[7] = {1, 2, 3, 4, 5, 6, 8};
-    for (int l = 0; l < 7; ++l) a.mag[l] = (float)(std::sqrt((double)level_d2[l]) * resolution);
-    a.mag[7] = 0.0f;
+    fill_ball_magnitudes(resolution, a.mag);
     a.slots = h->d_slots; a.uncertified = d_uncert;
     hipLaunchKernelGGL(k_ball_dense_generic, grid, block, 0, s, a);
     HIP_TRY(h, hipGetLastError());
     return SDFGPU_OK;
 }
 
-}  // namespace
+// ---- a whole build: plan (sdfgpu_plan.hpp), allocate, enqueue ---------------------------------------------------------------------
 
-// (declared in sdfgpu_context.hpp: the families' host code builds SDFs through it)
-int sdfgpu::build_device_impl(sdfgpu_handle h, const Occupancy& occ, int64_t nx, int64_t ny, int64_t nz, double resolution, int vb,
-                              float* d_out, hipStream_t s) {
-    if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
-    if (occ.null() || !d_out) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null device pointer");
-    if (occ.bits && (reinterpret_cast<uintptr_t>(occ.bits) % 4) != 0) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "the bit field must be 4-byte aligned");
-    if (int rc = check_resolution(h, resolution)) return rc;
-    if (int rc = check_dims(h, nx, ny, nz)) return rc;
-    if (occ.cells) if (int rc = check_cell_layout(h, occ.stride, occ.off)) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    canonical_dims(nx, ny, nz);
-    h->last.last_dc_x = 0;
-    h->last.last_lines_tiered = false;
-    const int64_t n = nx * ny * nz;
-    // (the caller's pointers need element alignment only, sdfgpu.h "Conventions": K3/16 and the tuned ball kernels store 16 bytes
-    //  per lane, so a field off that alignment takes the int32 plane field -- launch_sweep_x tests the pointer itself -- and the
-    //  generic dense kernel, which store floats)
-    const bool out16 = (reinterpret_cast<uintptr_t>(d_out) % 16) == 0;
-    const bool p16 = plane16_eligible(h, ny, nz) && out16;
-    if (int rc = ensure(h, h->yzfield, (size_t)n * 4, "int32 plane field / side table")) return rc;          // int32 plane field / side table
-    if (p16) if (int rc = ensure(h, h->plane16, (size_t)n * 2, "16-bit plane field")) return rc;
-    void* zy_out = p16 ? h->plane16.ptr : h->yzfield.ptr;
-    int32_t* zy_side = p16 ? (int32_t*)h->yzfield.ptr : nullptr;
-    bool dense = dense_eligible(h, nz) && ny <= 0x7fffffff && out16;
-    // shapes / modes the tuned dense kernels do not take go through their generic forms (any nz, virtual border)
-    const bool dense_generic = !dense && h->opt.dense_on && h->opt.dense_generic_on && nx <= 0x7fffffff && ny <= 0x7fffffff;
-    dense = dense || dense_generic;
-    // Learn from an earlier build on this handle, if its status block has arrived (never a wait), and plan the dense tier of
-    // this one: sdfgpu_policy.hpp.  Every outcome is exact; the policy only decides whether and in which form the DENSE tier is
-    // enqueued and whether the pipeline behind it may be the two-launch stand-by (which tier does a sweep is decided on the
-    // device inside the build).
-    if (h->flags_pending && hipEventQuery(h->flags_ev) == hipSuccess) {
-        h->flags_pending = false;
-        //   (a staged build -- KD, then KD3 + KF on KD's verdict -- reports KD's own verdict, kSwDenseVerdict, as word kSwReportVerdict)
-        h->pol.consume_report(h->h_flags[kSwUncertified] != 0, h->h_flags[kSwFixNeeded] != 0, h->h_flags[kSwReportVerdict] != 0);
-        // (a predicted build's flags are raised by the launches themselves: they teach the habit nothing, and a near-field scene would
-        //  keep a stale "far" alive through them -- ADVICE r5)
-        if (!h->pol.prev.predicted) h->far.consume_report(h->h_flags[kSwFarY] != 0, h->h_flags[kSwFarX] != 0);
-    }
-    if (h->far_pending && hipEventQuery(h->far_ev) == hipSuccess) {
-        h->far_pending = false;
-        h->far.consume_report(h->h_far[kSwFarY] != 0, h->h_far[kSwFarX] != 0);
-    }
-    const DensePlan plan = h->pol.plan(dense, dense_generic, nz / 32 <= 256, vb != 0);
-    dense = plan.dense;
-    // bounded marching scans + the far-field kernel behind them, on every shape that kernel takes; other shapes (lines beyond
-    // 2048, keys beyond 32 bits) keep unbounded marching scans.  Shapes without the 16-bit plane field (nz % 4 != 0) hand
-    // exact int32 plane values from the y to the x sweep.
-    const bool far_ok = h->opt.envelope_on && far_geometry_ok(h, 2, nx, ny, nz) && far_geometry_ok(h, 3, nx, ny, nz);
-    const bool envelope = far_ok && !(h->pol.expect_dense && dense);
-    // Stand-by behind a TRUSTED dense tier (round 4).  It nearly always exits on its guard, so it must be
-    // few launches with small grids -- and since the scene of a stream can change under the handle (dense -> far-field), it
-    // must be BOUNDED whatever the scene turns into.  That is the far-field pair with no probes and no marching sweeps:
-    // KE2 [guard] -> KE3 [guard], int32 hand-off, LOOP form (1024 workgroups each); KE2 takes its z distances straight from
-    // the dense tier's bit field (zdist_from_bits), so no z sweep is launched in front: TWO guarded launches like the
-    // K12 + K3/16 pair it replaces (a third one, a guarded K1, cost the dense-certified step 2.6 us: 0.1405 -> 0.1431 ms),
-    // O(L log L) per line on any input (the old pair ran unbounded outward scans: tens of ms on the build in which a
-    // dense scene turned into the two-box cloud).
-    const bool standby = far_ok && h->opt.standby_far && h->pol.expect_dense && dense && !h->opt.fused_always;
-    // Device-side tier selection: the marching-vs-far-field choice of each axis is made INSIDE this build from a probe of the
-    // sweep's own input, so a fresh context (the reference's API is one-shot: collision_map.hpp:680-712 builds and returns)
-    // never runs a sweep that is thrown away, and a handle's latency does not depend on what it built before.
-    const bool dev_select = envelope;
-    // K12 (fused z+y) only as the guarded stand-by behind a dense build that is expected to be certified
-    // again; everywhere else K1 + K2 (rows from the int16 z field) scan much faster than the fused kernel
-    // recomputes, and only they can hand a far-field y sweep to the envelope kernel.
-    const bool fused = !standby && fused_zy_eligible(h, occ.mask, zy_out, nz) &&
-                       (h->opt.fused_always || (dense && h->pol.expect_dense) || (!envelope && !dense));
-    const bool select = dev_select && !fused;
-    // (see far_predict: the handle's recent builds were far-field on both axes -- or the caller forces it)
-    const bool predicted = h->far.plan(select, h->opt.force_env >= 0);
-    if (!fused && !standby) if (int rc = ensure(h, h->zfield, (size_t)n * 2, "z field")) return rc;
-    // status block [0..7]: maxima, status, uncertified, far flags, fix_needed.  Normally still zero from the previous
-    // build's fold kernel; cleared here after a build that failed half-way (or before the first one)
-    // Builds on one handle share its status block, extrema slots and scratch fields.  On the same stream they are
-    // ordered by the stream; a build issued on ANOTHER stream first waits for the previous build's last kernel.
-    HIP_TRY(h, h->build_order.wait(s));
-    if (!h->small_clean) {
-        HIP_TRY(h, hipMemsetAsync(h->d_small, 0, 128, s));
-        HIP_TRY(h, hipMemsetAsync(h->d_slots, 0, (size_t)kSlots * kSlotWords * 4, s));   // a failed build may have left maxima behind
-    }
-    h->small_clean = false;
-    // profiling marks: an event is recorded only behind a stage that launched something; a stage that
-    // was not launched shares the previous mark (elapsed 0), so profiling adds as few packets as possible
+// Profiling marks of one build: eight event slots (start, after pack, ball, K1, K2 / K12, KE2, K3, KE3), seven intervals for
+// sdfgpu_get_stage_times.  An event is recorded only behind a stage that launched something; a stage that launched nothing shares
+// the previous mark (elapsed 0), so profiling adds as few packets as possible.  Events come from the handle's pool.
+struct StageMarks {
+    sdfgpu_handle h;
+    hipStream_t s;
+    int prof = 0;                    // 0 off, 1 every stage, 2 only the dominant kernel of the dense path: stage 1 = [ev1, ev2], every
+                                     // other stage shares a mark with its neighbour (builds without the dense tier: like 1)
+    bool dense = false;
     hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     bool launched_since_mark = true;
-    // level 3 = level 2 on every 4th build (a sampled timing costs the loop a quarter of the event overhead)
-    int prof = h->profiling;
-    if (prof == 3) prof = ((h->profiled_builds++ & 3u) == 0 && dense) ? 2 : 0;
-    auto mark = [&](int k) -> hipError_t {
+
+    StageMarks(sdfgpu_handle h_, hipStream_t s_, bool dense_) : h(h_), s(s_), prof(h_->profiling), dense(dense_) {
+        // level 3 = level 2 on every 4th build (a sampled timing costs the loop a quarter of the event overhead)
+        if (prof == 3) prof = ((h->profiled_builds++ & 3u) == 0 && dense) ? 2 : 0;
+    }
+    void launched() { launched_since_mark = true; }
+    hipError_t mark(int k) {
         if (!prof) return hipSuccess;
         if (prof == 2 && dense) {
-            // only the dominant kernel of the dense path is bracketed: stage 1 = [ev1, ev2], every other stage
-            // shares a mark with its neighbour (elapsed 0)
             if (k == 0) return hipSuccess;
             if (k > 2) { ev[k] = ev[k - 1]; return hipSuccess; }
         } else if (k > 0 && !launched_since_mark) {
@@ -857,216 +791,282 @@ int sdfgpu::build_device_impl(sdfgpu_handle h, const Occupancy& occ, int64_t nx,
         if (k == 1 && ev[0] == nullptr) ev[0] = ev[1];
         launched_since_mark = false;
         return hipEventRecord(ev[k], s);
-    };
-    HIP_TRY(h, mark(0));
-    // Dense path first: exact wherever the nearest opposite voxel is within d^2 <= 8; raises
-    // kSwUncertified otherwise, in which case (and only then) the general pipeline below does any work.
-    uint32_t* const sw = h->d_small;                            // the status block, indexed by StatusWord
-    bool cur_fix_mode = false, cur_dense3 = false, cur_staged = false;
-    const uint32_t* dense_bits = nullptr;                       // the bit field the tuned dense kernels (and the stand-by y sweep) read
-    uint8_t* row_any = nullptr;                                 // plane sparsity: one byte per z row, one per x-plane behind them (predicted far-field builds)
-    h->last.last_dense = dense;
-    if (dense && dense_generic) {
-        HIP_TRY(h, mark(1));
-        if (int rc = launch_dense_generic(h, occ, nx, ny, nz, resolution, vb, d_out, sw + kSwUncertified, s)) return rc;
-        launched_since_mark = true;
-    } else if (dense) {
-        if (occ.bits && (reinterpret_cast<uintptr_t>(occ.bits) % 16) == 0) {
-            dense_bits = occ.bits;                              // (nz % 32 == 0: the caller's linear bit field IS the [x][y][nz / 32] field K0 writes)
-        } else if (occ.bits) {                                  // (the dense kernels stage bit rows with 16-byte loads)
-            if (int rc = ensure(h, h->bits, (size_t)n / 8, "bit field")) return rc;
-            HIP_TRY(h, hipMemcpyAsync(h->bits.ptr, occ.bits, (size_t)n / 8, hipMemcpyDeviceToDevice, s));
-            dense_bits = (const uint32_t*)h->bits.ptr;
-        } else {
-            if (int rc = ensure(h, h->bits, (size_t)n / 8, "bit field")) return rc;
-            if (int rc = launch_pack_bits(h, occ, n, (uint32_t*)h->bits.ptr, s)) return rc;
-            launched_since_mark = true;
-            dense_bits = (const uint32_t*)h->bits.ptr;
-        }
-        HIP_TRY(h, mark(1));
-        // fix-up mode (policy): undecided voxels go to the fix-up kernel, which raises `uncertified` only for what it
-        // cannot decide either; otherwise the ball kernel raises it directly and nothing extra is launched
-        // (with a virtual border the fix-up kernel stays out: a voxel it would finish may still be bound by b >= 3)
-        // (fix-up mode, KD3 in KD's place, the fix-up stage staged behind KD: DensePolicy::plan)
-        const bool fix = plan.fix;
-        cur_dense3 = plan.dense3;
-        cur_staged = plan.staged;
-        BallMode kd;
-        kd.early_out = true; kd.vb = vb; kd.nx_glob = nx; kd.radius = cur_dense3 ? 3 : 2;
-        if (fix || cur_dense3) kd.fix_needed = sw + kSwFixNeeded;
-        if (!cur_dense3) {                                      // (KD; see ball_serpentine)
-            kd.flip = (h->opt.ball_serpentine && d_out == h->serp_out && n == h->serp_n) ? !h->serp_flip : 0;
-            h->serp_out = d_out; h->serp_n = n; h->serp_flip = kd.flip;
-        }
-        if (int rc = launch_ball_dense(h, dense_bits, d_out, nx, 0, nx, ny, nz, resolution,
-                                       cur_staged ? sw + kSwDenseVerdict : sw + kSwUncertified, kd, s)) return rc;
-        if (cur_staged) {                                       // KD3 + KF behind KD, guarded on its verdict
-            BallMode kd3;
-            kd3.early_out = true; kd3.nx_glob = nx; kd3.radius = 3; kd3.fix_needed = sw + kSwFixNeeded; kd3.guard = sw + kSwDenseVerdict;
-            // (the undecided bits of this stage live in the z field's storage: launch_ball_dense)
-            if (!fused && h->zfield.ptr && h->zfield.bytes >= (size_t)n / 8) { kd3.unc = (uint32_t*)h->zfield.ptr; kd3.unc_bytes = h->zfield.bytes; }
-            if (int rc = launch_ball_dense(h, dense_bits, d_out, nx, 0, nx, ny, nz, resolution, sw + kSwUncertified, kd3, s)) return rc;
-        }
-        launched_since_mark = true;
-        cur_fix_mode = fix || cur_dense3;
-    } else {
-        HIP_TRY(h, mark(1));
     }
-    // what guards every launch of the general pipeline: "the dense tier left voxels undecided"
-    const uint32_t* const general_guard = dense ? sw + kSwUncertified : kUnguarded;
-    h->last.last_dense3 = cur_dense3;
-    h->last.last_staged = cur_staged;
-    HIP_TRY(h, mark(2));
-    h->last.last_fused = fused;
-    h->last.last_standby = standby;
-    h->last.last_standby_single = false;
-    h->last.last_predicted = predicted;
-    h->last.last_plane16 = p16;
-    if (!fused && !standby) {                                   // (the stand-by pair takes its z distances from the bit field)
-        // a build that goes straight to the far-field pair lets the z sweep mark the x-planes that hold a filled voxel at all: a sensed
-        // scene leaves most planes without one, and the pair skips them (y sweep: the planes' tiles; x sweep: their row loads)
-        if (predicted && h->opt.plane_skip && nx >= 8 && ny <= 1024 && z_wave16_shape(h, nz) && !occ.cells &&
-            (occ.bits || (reinterpret_cast<uintptr_t>(occ.mask) % 16) == 0)) {
-            const size_t o_bits = ((size_t)(nx * ny + nx) + 255) & ~(size_t)255;
-            if (int rc = ensure(h, h->planebits, o_bits + (size_t)nx * ((ny + 31) / 32) * 4, "row / x-plane occupancy flags")) return rc;
-            row_any = (uint8_t*)h->planebits.ptr;
-        }
-        if (int rc = launch_sweep_z(h, occ, nx, ny, nz, (int16_t*)h->zfield.ptr, general_guard, s, row_any)) return rc;
-        launched_since_mark = true;
+    hipError_t finish() {                                        // the last mark; the build's events go to the handle
+        if (!prof) return hipSuccess;
+        const hipError_t e = mark(7);
+        if (e == hipSuccess) for (auto x : ev) h->events.push_back(x);
+        return e;
     }
-    h->last.last_plane_skip = row_any != nullptr;
-    h->last.last_dims[0] = nx; h->last.last_dims[1] = ny; h->last.last_dims[2] = nz;
-    HIP_TRY(h, mark(3));
-    const int16_t* const zf = (const int16_t*)h->zfield.ptr;
-    int32_t* const yz = (int32_t*)h->yzfield.ptr;
-    // Both axes far-field (decided by the y probe): the y sweep hands the x sweep exact int32 values in the side-table
-    // buffer (used whole) instead of p16 + side table -- one store / one load per voxel, no saturation handling, and the
-    // x probe is skipped.  kSwHandoff carries the choice on the device.
-    const bool handoff = select && p16 && h->opt.i32_handoff;        // (shapes without the 16-bit plane field hand int32 values over anyway)
-    // (the radius-8 y window exists for 4-voxel lanes only)
-    const bool window_choice = select && (nz % 4) == 0;
-    // (moved up: the stand-by x sweep does the fold itself and needs to know where the report goes)
-    const bool report = h->opt.envelope_on && h->h_flags_dev && !h->flags_pending && dense;
-    bool folded = false;
-    if (standby || predicted) {
-        // KE2 [general guard] -> KE3 [general guard], exact int32 plane values in between, each launch raising its far flag itself:
-        // no probes, no marching launches
-        DcIo ke2, ke3;
-        ke2.out_i32 = yz; ke2.ran_flag = sw + kSwFarY;
-        ke3.in_i32 = yz; ke3.out = d_out; ke3.ran_flag = sw + kSwFarX;
-        if (standby) {                                          // LOOP form, z distances from the dense tier's bit field, self-reporting
-            ke2.loop = ke3.loop = true;
-            ke2.bits = dense_bits ? dense_bits : (const uint32_t*)h->bits.ptr; ke2.nzw = (int)((nz + 31) / 32);
-            if (h->opt.standby_fold) {
-                ke3.fold_result = h->d_result; ke3.fold_report = report ? h->h_flags_dev : nullptr; ke3.fold_ticket = sw + kSwFoldTicket;
-                folded = true;
-            }
-        } else {
-            ke2.in16 = zf;
-            if (row_any) {
-                // row bytes -> one bit per row, one byte per x-plane, "some plane is empty" (kSwPlaneEmpty)
-                uint8_t* plane_any = row_any + nx * ny;
-                uint32_t* row_bits = (uint32_t*)(row_any + (((size_t)(nx * ny + nx) + 255) & ~(size_t)255));
-                const int row_words = (int)((ny + 31) / 32);
-                if (h->flat_score_reset) { h->flat_score_reset = false; HIP_TRY(h, hipMemsetAsync(sw + kSwFlatScore, 0, 8, s)); }
-                hipLaunchKernelGGL(k_pack_row_flags, dim3((unsigned)std::min<int64_t>((nx + 15) / 16, 16)), dim3(1024), 0, s, row_any, (int)nx, (int)ny, row_words, row_bits, plane_any, sw + kSwPlaneEmpty, sw + kSwFlatScore);
-                HIP_TRY(h, hipGetLastError());
-                ke2.row_bits = row_bits; ke2.row_words = row_words; ke2.plane_any = ke3.plane_any = plane_any;
-            }
-        }
-        HIP_TRY(h, mark(4));                                    // (stage slot 3, the marching y sweep: nothing launched)
-        if (standby && h->opt.standby_single) {
-            // ONE launch: its time goes to the y-envelope slot, the x-envelope slot shares its mark
-            if (int rc = launch_envelope_standby(h, ke2, ke3, nx, ny, nz, resolution, vb, general_guard, s)) return rc;
-            launched_since_mark = true;
-            h->last.last_standby_single = true;
-            HIP_TRY(h, mark(5));
-            HIP_TRY(h, mark(6));
-        } else {
-            if (int rc = launch_envelope(h, 2, ke2, nx, ny, nz, resolution, vb, general_guard, s)) return rc;
-            launched_since_mark = true;
-            HIP_TRY(h, mark(5));
-            HIP_TRY(h, mark(6));                                // (stage slot 5, the marching x sweep: nothing launched)
-            if (int rc = launch_envelope(h, 3, ke3, nx, ny, nz, resolution, vb, general_guard, s)) return rc;
-            launched_since_mark = true;
+};
+
+// What the stages of one build share: the grid, the caller's buffers, the handle's scratch fields (allocated before the first
+// launch) and the device words that steer the launches.
+struct BuildIo {
+    const Occupancy& occ;
+    int64_t nx, ny, nz;
+    double resolution;
+    int vb;
+    float* d_out;
+    hipStream_t s;
+    uint32_t* sw;                    // the status block, indexed by StatusWord
+    const uint32_t* general_guard;   // what guards every launch of the general pipeline: "the dense tier left voxels undecided"
+    int16_t* zf;                     // z field
+    int32_t* yz;                     // int32 plane field / side table
+    int16_t* p16;                    // 16-bit plane field (BuildPlan::p16)
+    const uint32_t* dense_bits;      // the bit field the dense kernels (and the stand-by y sweep) read
+    uint8_t* row_any;                // plane sparsity: one byte per z row, one per x-plane behind them (BuildPlan::plane_skip)
+};
+
+// What plan_build needs and only this unit can know, but for the report slots (nx, ny, nz: canonical)
+BuildFacts shape_and_pointer_facts(const sdfgpu_context* h, const Occupancy& occ, int64_t nx, int64_t ny, int64_t nz, int vb, const float* d_out) {
+    // (the caller's pointers need element alignment only, sdfgpu.h "Conventions")
+    auto aligned16 = [](const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) % 16) == 0; };
+    BuildFacts f;
+    f.nx = nx; f.ny = ny; f.nz = nz; f.vb = vb != 0;
+    f.occ = occ.bits ? BuildFacts::Occ::bits : occ.cells ? BuildFacts::Occ::cells : BuildFacts::Occ::mask;
+    f.occ16 = aligned16(occ.bits ? (const void*)occ.bits : occ.cells ? occ.cells : (const void*)occ.mask);
+    f.out16 = aligned16(d_out);
+    f.dense_shape = dense_shape_ok(nz);
+    f.far_shape[0] = far_geometry_ok(h, 2, nx, ny, nz); f.far_shape[1] = far_geometry_ok(h, 3, nx, ny, nz);
+    f.z_wave_shape = z_wave16_shape(h, nz);
+    f.fused_nz = fused_zy_nz(nz);
+    return f;
+}
+
+// Learn from an earlier build on this handle, if its status block has arrived (never a wait): sdfgpu_policy.hpp.  Every
+// outcome is exact; the policy only decides whether and in which form the DENSE tier is enqueued and whether the pipeline
+// behind it may be the two-launch stand-by (which tier does a sweep is decided on the device inside the build).
+void consume_arrived_reports(sdfgpu_handle h) {
+    if (h->flags_pending && hipEventQuery(h->flags_ev) == hipSuccess) {
+        h->flags_pending = false;
+        //   (a staged build -- KD, then KD3 + KF on KD's verdict -- reports KD's own verdict, kSwDenseVerdict, as word kSwReportVerdict)
+        h->pol.consume_report(h->h_flags[kSwUncertified] != 0, h->h_flags[kSwFixNeeded] != 0, h->h_flags[kSwReportVerdict] != 0);
+        // (a predicted build's flags are raised by the launches themselves: they teach the habit nothing, and a near-field scene would
+        //  keep a stale "far" alive through them -- ADVICE r5)
+        if (!h->pol.prev.predicted) h->far.consume_report(h->h_flags[kSwFarY] != 0, h->h_flags[kSwFarX] != 0);
+    }
+    if (h->far_pending && hipEventQuery(h->far_ev) == hipSuccess) {
+        h->far_pending = false;
+        h->far.consume_report(h->h_far[kSwFarY] != 0, h->h_far[kSwFarX] != 0);
+    }
+}
+
+// The dense tier, with the profiling mark between its bit field and its kernels: generic, or KD (KD3 in fix-up mode) with KD3 + KF
+// staged behind it.  Exact wherever the nearest opposite voxel is within d^2 <= 8; raises kSwUncertified otherwise.
+int enqueue_dense_tier(sdfgpu_handle h, const BuildPlan& p, const BuildIo& b, StageMarks& marks) {
+    const int64_t n = b.nx * b.ny * b.nz;
+    uint32_t* const sw = b.sw;
+    if (p.bits == BuildPlan::Bits::copy) {                      // (the dense kernels stage bit rows with 16-byte loads)
+        HIP_TRY(h, hipMemcpyAsync(h->bits.ptr, b.occ.bits, (size_t)n / 8, hipMemcpyDeviceToDevice, b.s));
+    } else if (p.bits == BuildPlan::Bits::pack) {
+        if (int rc = launch_pack_bits(h, b.occ, n, (uint32_t*)h->bits.ptr, b.s)) return rc;
+        marks.launched();
+    }
+    HIP_TRY(h, marks.mark(1));
+    if (!p.dense) return SDFGPU_OK;
+    if (p.dense_generic) {
+        if (int rc = launch_dense_generic(h, b.occ, b.nx, b.ny, b.nz, b.resolution, b.vb, (uint32_t*)h->bits.ptr, b.d_out, sw + kSwUncertified, b.s)) return rc;
+        marks.launched();
+        return SDFGPU_OK;
+    }
+    // fix-up mode (policy): undecided voxels go to the fix-up kernel, which raises `uncertified` only for what it
+    // cannot decide either; otherwise the ball kernel raises it directly and nothing extra is launched
+    // (with a virtual border the fix-up kernel stays out: a voxel it would finish may still be bound by b >= 3)
+    // (fix-up mode, KD3 in KD's place, the fix-up stage staged behind KD: DensePolicy::plan)
+    BallMode kd;
+    kd.early_out = true; kd.vb = b.vb; kd.nx_glob = b.nx; kd.radius = p.tier.dense3 ? 3 : 2;
+    if (p.tier.fix_mode_build()) kd.fix_needed = sw + kSwFixNeeded;
+    if (!p.tier.dense3) {                                       // (KD; see ball_serpentine)
+        kd.flip = (h->opt.ball_serpentine && b.d_out == h->serp_out && n == h->serp_n) ? !h->serp_flip : 0;
+        h->serp_out = b.d_out; h->serp_n = n; h->serp_flip = kd.flip;
+    }
+    if (int rc = launch_ball_dense(h, b.dense_bits, b.d_out, b.nx, 0, b.nx, b.ny, b.nz, b.resolution,
+                                   p.tier.staged ? sw + kSwDenseVerdict : sw + kSwUncertified, kd, b.s)) return rc;
+    if (p.tier.staged) {                                        // KD3 + KF behind KD, guarded on its verdict
+        BallMode kd3;
+        kd3.early_out = true; kd3.nx_glob = b.nx; kd3.radius = 3; kd3.fix_needed = sw + kSwFixNeeded; kd3.guard = sw + kSwDenseVerdict;
+        // (the undecided bits of this stage live in the z field's storage: launch_ball_dense.  Every build that sweeps z has
+        //  allocated the field by now, so the stage finds it on a fresh context too)
+        if (!p.fused && h->zfield.ptr && h->zfield.bytes >= (size_t)n / 8) { kd3.unc = (uint32_t*)h->zfield.ptr; kd3.unc_bytes = h->zfield.bytes; }
+        if (int rc = launch_ball_dense(h, b.dense_bits, b.d_out, b.nx, 0, b.nx, b.ny, b.nz, b.resolution, sw + kSwUncertified, kd3, b.s)) return rc;
+    }
+    marks.launched();
+    return SDFGPU_OK;
+}
+
+// K1, unless the build's y sweep computes the z distances itself (K12; the stand-by pair reads the bit field)
+int enqueue_z_sweep(sdfgpu_handle h, const BuildPlan& p, const BuildIo& b, StageMarks& marks) {
+    if (!p.z_sweep()) return SDFGPU_OK;
+    if (int rc = launch_sweep_z(h, b.occ, b.nx, b.ny, b.nz, b.zf, b.general_guard, b.s, b.row_any)) return rc;
+    marks.launched();
+    return SDFGPU_OK;
+}
+
+// Stand-by and predicted builds: KE2 [general guard] -> KE3 [general guard], exact int32 plane values in between, each launch
+// raising its far flag itself: no probes, no marching launches.
+int enqueue_far_pair(sdfgpu_handle h, const BuildPlan& p, const BuildIo& b, StageMarks& marks) {
+    const int64_t nx = b.nx, ny = b.ny, nz = b.nz;
+    uint32_t* const sw = b.sw;
+    DcIo ke2, ke3;
+    ke2.out_i32 = b.yz; ke2.ran_flag = sw + kSwFarY;
+    ke3.in_i32 = b.yz; ke3.out = b.d_out; ke3.ran_flag = sw + kSwFarX;
+    if (p.standby) {                                            // LOOP form, z distances from the dense tier's bit field, self-reporting
+        ke2.loop = ke3.loop = true;
+        ke2.bits = b.dense_bits; ke2.nzw = (int)((nz + 31) / 32);
+        if (p.standby_folds) {
+            ke3.fold_result = h->d_result; ke3.fold_report = p.report == BuildPlan::Report::dense ? h->h_flags_dev : nullptr;
+            ke3.fold_ticket = sw + kSwFoldTicket;
         }
     } else {
-        // A probe-selected build (`select`): per axis a probe that decides, the marching sweep behind its guard word with bounded
-        // scans, and the far-field sweep behind the axis' far flag.  Every other build: one sweep per axis, unbounded scans, no far flag.
-        uint32_t* const far_y = select ? sw + kSwFarY : kUnbounded;
-        uint32_t* const far_x = select ? sw + kSwFarX : kUnbounded;
-        // the far-field pair: p16 + side table in between, or exact int32 values (always on shapes without the 16-bit plane
-        // field; behind kSwHandoff on the others)
-        DcIo ke2, ke3;
-        ke2.in16 = zf; ke3.out = d_out;
-        if (p16) { ke2.out = h->plane16.ptr; ke2.side_out = yz; ke3.in16 = (const int16_t*)h->plane16.ptr; ke3.side_in = yz; }
-        if (!p16 || handoff) { ke2.out_i32 = yz; ke3.in_i32 = yz; }
-        if (p16 && handoff) ke2.i32_flag = ke3.i32_flag = sw + kSwHandoff;
-        DcIo probe2;                                            // the y probe reads what KE2 reads (no hand-off flag: its own decision raises it)
-        probe2.in16 = zf; probe2.out = h->plane16.ptr; probe2.side_out = yz;
-        if (!p16) probe2.out_i32 = yz;
-        DcDecide dy, dx;
-        dy.stage = 0; dx.stage = 1;
-        dy.dense_tried = dx.dense_tried = dense; dy.handoff = dx.handoff = handoff; dy.window_choice = dx.window_choice = window_choice;
-        XSlab whole = XSlab::whole(nx);
-        whole.status = sw + kSwSlabStatus;
-        // y sweep
-        if (select) {
-            // probe + decision in one launch (the probe's last workgroup decides); a forced tier needs no probe
-            if (h->opt.force_env < 0) {
-                if (int rc = launch_envelope_probe(h, 2, probe2, nx, ny, nz, resolution, vb, general_guard, dy, s)) return rc;
-            } else if (int rc = launch_decide(h, dy, s)) return rc;
-            // marching y sweep: general pipeline needed AND near-field; the probe also picks the window (radius 3 / radius 8)
-            if (int rc = launch_sweep_y(h, zf, zy_out, zy_side, nx, ny, nz, sw + kSwMarchY, far_y, s)) return rc;
-            if (window_choice)
-                if (int rc = launch_sweep_y(h, zf, zy_out, zy_side, nx, ny, nz, sw + kSwMarchYWide, far_y, s, YWindow::r8)) return rc;
-        } else if (fused) {
-            if (int rc = launch_sweep_zy_fused(h, occ.mask, zy_out, zy_side, nx, ny, nz, general_guard, s)) return rc;
-        } else {                                                // (no far-field kernel for this shape / switched off: unbounded scans)
-            if (int rc = launch_sweep_y(h, zf, zy_out, zy_side, nx, ny, nz, general_guard, kUnbounded, s)) return rc;
-        }
-        launched_since_mark = true;
-        HIP_TRY(h, mark(4));
-        if (select) {
-            if (int rc = launch_envelope(h, 2, ke2, nx, ny, nz, resolution, vb, sw + kSwFarY, s)) return rc;
-            launched_since_mark = true;
-        }
-        HIP_TRY(h, mark(5));
-        // x sweep: same choice
-        if (select) {
-            if (h->opt.force_env < 0) {
-                if (int rc = launch_envelope_probe(h, 3, ke3, nx, ny, nz, resolution, vb, general_guard, dx, s)) return rc;
-            } else if (int rc = launch_decide(h, dx, s)) return rc;
-        }
-        const uint32_t* const march_x_guard = select ? sw + kSwMarchX : general_guard;
-        if (p16) {
-            if (int rc = launch_sweep_x16(h, (const int16_t*)h->plane16.ptr, yz, d_out, whole, ny, nz, resolution, vb, march_x_guard, far_x, s)) return rc;
-        } else {
-            if (int rc = launch_sweep_x(h, yz, d_out, whole, ny, nz, resolution, vb, march_x_guard, far_x, s)) return rc;
-        }
-        launched_since_mark = true;
-        HIP_TRY(h, mark(6));
-        if (select) {
-            if (int rc = launch_envelope(h, 3, ke3, nx, ny, nz, resolution, vb, sw + kSwFarX, s)) return rc;
-            launched_since_mark = true;
+        ke2.in16 = b.zf;
+        if (b.row_any) {
+            // row bytes -> one bit per row, one byte per x-plane, "some plane is empty" (kSwPlaneEmpty)
+            uint8_t* plane_any = b.row_any + nx * ny;
+            uint32_t* row_bits = (uint32_t*)(b.row_any + plane_row_bits_offset(nx, ny));
+            const int row_words = (int)((ny + 31) / 32);
+            if (h->flat_score_reset) { h->flat_score_reset = false; HIP_TRY(h, hipMemsetAsync(sw + kSwFlatScore, 0, 8, b.s)); }
+            hipLaunchKernelGGL(k_pack_row_flags, dim3((unsigned)std::min<int64_t>((nx + 15) / 16, 16)), dim3(1024), 0, b.s, b.row_any, (int)nx, (int)ny, row_words, row_bits, plane_any, sw + kSwPlaneEmpty, sw + kSwFlatScore);
+            HIP_TRY(h, hipGetLastError());
+            ke2.row_bits = row_bits; ke2.row_words = row_words; ke2.plane_any = ke3.plane_any = plane_any;
         }
     }
+    HIP_TRY(h, marks.mark(4));                                  // (stage slot 3, the marching y sweep: nothing launched)
+    if (p.standby_single) {
+        // ONE launch: its time goes to the y-envelope slot, the x-envelope slot shares its mark
+        if (int rc = launch_envelope_standby(h, ke2, ke3, nx, ny, nz, b.resolution, b.vb, b.general_guard, b.s)) return rc;
+        marks.launched();
+        HIP_TRY(h, marks.mark(5));
+        HIP_TRY(h, marks.mark(6));
+        return SDFGPU_OK;
+    }
+    if (int rc = launch_envelope(h, 2, ke2, nx, ny, nz, b.resolution, b.vb, b.general_guard, b.s)) return rc;
+    marks.launched();
+    HIP_TRY(h, marks.mark(5));
+    HIP_TRY(h, marks.mark(6));                                  // (stage slot 5, the marching x sweep: nothing launched)
+    if (int rc = launch_envelope(h, 3, ke3, nx, ny, nz, b.resolution, b.vb, b.general_guard, b.s)) return rc;
+    marks.launched();
+    return SDFGPU_OK;
+}
+
+// Every other build.  A probe-selected one (`select`): per axis a probe that decides, the marching sweep behind its guard word with
+// bounded scans, and the far-field sweep behind the axis' far flag.  The rest: one sweep per axis (K12 for z and y where the plan
+// says so), unbounded scans, no far flag.
+int enqueue_swept_axes(sdfgpu_handle h, const BuildPlan& p, const BuildIo& b, StageMarks& marks) {
+    const int64_t nx = b.nx, ny = b.ny, nz = b.nz;
+    uint32_t* const sw = b.sw;
+    void* const zy_out = p.p16 ? (void*)b.p16 : (void*)b.yz;
+    int32_t* const zy_side = p.p16 ? b.yz : kNoSideTable;
+    uint32_t* const far_y = p.select ? sw + kSwFarY : kUnbounded;
+    uint32_t* const far_x = p.select ? sw + kSwFarX : kUnbounded;
+    // the far-field pair: p16 + side table in between, or exact int32 values (always on shapes without the 16-bit plane
+    // field; behind kSwHandoff on the others)
+    DcIo ke2, ke3;
+    ke2.in16 = b.zf; ke3.out = b.d_out;
+    if (p.p16) { ke2.out = b.p16; ke2.side_out = b.yz; ke3.in16 = b.p16; ke3.side_in = b.yz; }
+    if (!p.p16 || p.handoff) { ke2.out_i32 = b.yz; ke3.in_i32 = b.yz; }
+    if (p.p16 && p.handoff) ke2.i32_flag = ke3.i32_flag = sw + kSwHandoff;
+    DcIo probe2;                                                // the y probe reads what KE2 reads (no hand-off flag: its own decision raises it)
+    probe2.in16 = b.zf; probe2.out = b.p16; probe2.side_out = b.yz;
+    if (!p.p16) probe2.out_i32 = b.yz;
+    DcDecide dy, dx;
+    dy.stage = 0; dx.stage = 1;
+    dy.dense_tried = dx.dense_tried = p.dense; dy.handoff = dx.handoff = p.handoff; dy.window_choice = dx.window_choice = p.window_choice;
+    XSlab whole = XSlab::whole(nx);
+    whole.status = sw + kSwSlabStatus;
+    // y sweep
+    if (p.select) {
+        if (int rc = launch_probe_or_decide(h, 2, probe2, nx, ny, nz, b.resolution, b.vb, b.general_guard, dy, b.s)) return rc;
+        // marching y sweep: general pipeline needed AND near-field; the probe also picks the window (radius 3 / radius 8)
+        if (int rc = launch_sweep_y(h, b.zf, zy_out, zy_side, nx, ny, nz, sw + kSwMarchY, far_y, b.s)) return rc;
+        if (p.window_choice)
+            if (int rc = launch_sweep_y(h, b.zf, zy_out, zy_side, nx, ny, nz, sw + kSwMarchYWide, far_y, b.s, YWindow::r8)) return rc;
+    } else if (p.fused) {
+        if (int rc = launch_sweep_zy_fused(h, b.occ.mask, zy_out, zy_side, nx, ny, nz, b.general_guard, b.s)) return rc;
+    } else {                                                    // (no far-field kernel for this shape / switched off: unbounded scans)
+        if (int rc = launch_sweep_y(h, b.zf, zy_out, zy_side, nx, ny, nz, b.general_guard, kUnbounded, b.s)) return rc;
+    }
+    marks.launched();
+    HIP_TRY(h, marks.mark(4));
+    if (p.select) {
+        if (int rc = launch_envelope(h, 2, ke2, nx, ny, nz, b.resolution, b.vb, sw + kSwFarY, b.s)) return rc;
+        marks.launched();
+    }
+    HIP_TRY(h, marks.mark(5));
+    // x sweep: same choice
+    if (p.select) if (int rc = launch_probe_or_decide(h, 3, ke3, nx, ny, nz, b.resolution, b.vb, b.general_guard, dx, b.s)) return rc;
+    const uint32_t* const march_x_guard = p.select ? sw + kSwMarchX : b.general_guard;
+    if (p.p16) {
+        if (int rc = launch_sweep_x16(h, b.p16, b.yz, b.d_out, whole, ny, nz, b.resolution, b.vb, march_x_guard, far_x, b.s)) return rc;
+    } else {
+        if (int rc = launch_sweep_x(h, b.yz, b.d_out, whole, ny, nz, b.resolution, b.vb, march_x_guard, far_x, b.s)) return rc;
+    }
+    marks.launched();
+    HIP_TRY(h, marks.mark(6));
+    if (p.select) {
+        if (int rc = launch_envelope(h, 3, ke3, nx, ny, nz, b.resolution, b.vb, sw + kSwFarX, b.s)) return rc;
+        marks.launched();
+    }
+    return SDFGPU_OK;
+}
+
+}  // namespace
+
+// (declared in sdfgpu_context.hpp: the families' host code builds SDFs through it)
+int sdfgpu::build_device_impl(sdfgpu_handle h, const Occupancy& occ, int64_t nx, int64_t ny, int64_t nz, double resolution, int vb,
+                              float* d_out, hipStream_t s) {
+    if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
+    if (occ.null() || !d_out) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null device pointer");
+    if (occ.bits && (reinterpret_cast<uintptr_t>(occ.bits) % 4) != 0) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "the bit field must be 4-byte aligned");
+    if (int rc = check_resolution(h, resolution)) return rc;
+    if (int rc = check_dims(h, nx, ny, nz)) return rc;
+    if (occ.cells) if (int rc = check_cell_layout(h, occ.stride, occ.off)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    canonical_dims(nx, ny, nz);
+    h->last.last_dc_x = 0;                                      // (the far-field launchers of this build write it)
+    h->last.last_lines_tiered = false;
+    BuildFacts f = shape_and_pointer_facts(h, occ, nx, ny, nz, vb, d_out);
+    consume_arrived_reports(h);
+    f.dense_slot_free = h->h_flags_dev && !h->flags_pending;
+    f.far_slot_free = h->h_far_dev && !h->far_pending;
+    const BuildPlan p = plan_build(h->opt, h->pol, h->far, f);
+    // every scratch field of the build: nothing has been enqueued when an allocation fails
+    if (int rc = ensure(h, h->yzfield, p.yz_bytes, "int32 plane field / side table")) return rc;
+    if (p.plane16_bytes) if (int rc = ensure(h, h->plane16, p.plane16_bytes, "16-bit plane field")) return rc;
+    if (p.z_bytes) if (int rc = ensure(h, h->zfield, p.z_bytes, "z field")) return rc;
+    if (p.bits_bytes) if (int rc = ensure(h, h->bits, p.bits_bytes, "bit field")) return rc;
+    if (p.unc_bytes) if (int rc = ensure(h, h->unc, p.unc_bytes, "undecided words")) return rc;
+    if (p.planebits_bytes) if (int rc = ensure(h, h->planebits, p.planebits_bytes, "row / x-plane occupancy flags")) return rc;
+    // Builds on one handle share its status block, extrema slots and scratch fields.  On the same stream they are
+    // ordered by the stream; a build issued on ANOTHER stream first waits for the previous build's last kernel.
+    HIP_TRY(h, h->build_order.wait(s));
+    // status block: maxima, status, uncertified, far flags, fix_needed.  Normally still zero from the previous
+    // build's fold kernel; cleared here after a build that failed half-way (or before the first one)
+    if (!h->small_clean) {
+        HIP_TRY(h, hipMemsetAsync(h->d_small, 0, 128, s));
+        HIP_TRY(h, hipMemsetAsync(h->d_slots, 0, (size_t)kSlots * kSlotWords * 4, s));   // a failed build may have left maxima behind
+    }
+    h->small_clean = false;
+    uint32_t* const sw = h->d_small;
+    const BuildIo b{occ, nx, ny, nz, resolution, vb, d_out, s, sw,
+                    p.dense ? sw + kSwUncertified : kUnguarded,
+                    (int16_t*)h->zfield.ptr, (int32_t*)h->yzfield.ptr, (int16_t*)h->plane16.ptr,
+                    p.bits == BuildPlan::Bits::caller ? occ.bits : (const uint32_t*)h->bits.ptr,
+                    p.plane_skip ? (uint8_t*)h->planebits.ptr : nullptr};
+    StageMarks marks(h, s, p.dense);
+    HIP_TRY(h, marks.mark(0));
+    if (int rc = enqueue_dense_tier(h, p, b, marks)) return rc;
+    HIP_TRY(h, marks.mark(2));
+    if (int rc = enqueue_z_sweep(h, p, b, marks)) return rc;
+    HIP_TRY(h, marks.mark(3));
+    if (int rc = p.far_pair() ? enqueue_far_pair(h, p, b, marks) : enqueue_swept_axes(h, p, b, marks)) return rc;
     // one kernel folds the maxima, publishes the status block (device copy for get_extrema, pinned host copy for the
-    // next build's policy) and clears it for the next build
-    // The report (status block -> pinned host memory + an event) is only taken when the previous report has been
-    // consumed: the event is then never re-recorded while the host still waits for it, so even a caller that
-    // enqueues builds back to back without ever synchronising keeps feeding the policy (a few builds late), and the
-    // builds in between skip the host write.  What the reported build was (dense? fix-up? envelope mode?) is
-    // remembered with the report -- not with whatever build happens to be the latest when it is read.
-    // (only a build that carried the dense tier has anything to teach the policy: the builds of a pause leave the report slot
-    //  free, so that the PROBE at its end is the build whose verdict comes back -- with every build reporting, the slot was
-    //  usually taken by a paused build when the probe came, its failure went unseen and the pause never grew; tests/policy_harness)
-    // (a stand-by build: the x sweep's launch has done it -- one launch less behind the dense kernel)
-    // (a build without the dense tier reports to the second slot: its far flags teach far_predict)
-    // (... the builds that probed: a predicted build's flags say nothing new, and a report is PCIe writes the fold waits for)
-    const bool report_far = !report && select && !predicted && h->h_far_dev && !h->far_pending;
-    if (!folded) if (int rc = fold_slots(h, h->d_small, s, h->d_result, report ? h->h_flags_dev : report_far ? h->h_far_dev : nullptr,
-                                         report ? kReportDense : kReportFar)) return rc;
+    // next build's policy) and clears it for the next build -- unless the stand-by x sweep's launch has done it.  What the
+    // reported build was (dense? fix-up? predicted?) is remembered with the report -- not with whatever build happens to be
+    // the latest when it is read.
+    const bool report = p.report == BuildPlan::Report::dense, report_far = p.report == BuildPlan::Report::far;
+    if (!p.standby_folds) if (int rc = fold_slots(h, h->d_small, s, h->d_result, report ? h->h_flags_dev : report_far ? h->h_far_dev : nullptr,
+                                                  report ? kReportDense : kReportFar)) return rc;
     if (report_far) {
         HIP_TRY(h, hipEventRecord(h->far_ev, s));
         h->far_pending = true;
@@ -1075,17 +1075,19 @@ int sdfgpu::build_device_impl(sdfgpu_handle h, const Occupancy& occ, int64_t nx,
     if (report) {
         HIP_TRY(h, hipEventRecord(h->flags_ev, s));
         h->flags_pending = true;
-        h->pol.prev = ReportedBuild{dense, dense_generic, cur_fix_mode, cur_staged, predicted};
+        h->pol.prev = ReportedBuild{p.dense, p.dense_generic, p.tier.fix_mode_build(), p.tier.staged, p.predicted};
     }
-    if (prof) {
-        HIP_TRY(h, mark(7));
-        for (auto e : ev) h->events.push_back(e);
-    }
+    HIP_TRY(h, marks.finish());
     HIP_TRY(h, h->build_order.record(s));
-    h->last.last_stream = s;
-    h->last.last_resolution = resolution;
-    h->last.last_n = n;
-    h->last.have_result = true;
+    LastBuild& last = h->last;
+    last.last_dense = p.dense; last.last_dense3 = p.tier.dense3; last.last_staged = p.tier.staged;
+    last.last_fused = p.fused; last.last_standby = p.standby; last.last_standby_single = p.standby_single;
+    last.last_predicted = p.predicted; last.last_plane16 = p.p16; last.last_plane_skip = p.plane_skip;
+    last.last_dims[0] = nx; last.last_dims[1] = ny; last.last_dims[2] = nz;
+    last.last_stream = s;
+    last.last_resolution = resolution;
+    last.last_n = nx * ny * nz;
+    last.have_result = true;
     return SDFGPU_OK;
 }
 
@@ -1334,9 +1336,7 @@ int sdfgpu_sweep_zy_tiered_device(sdfgpu_handle h, const uint8_t* d_filled, int6
         const double unit = 1.0;                                    // ... no resolution,
         const int no_border = 0;                                    // ... no virtual border
         DcDecide dy; dy.stage = 0;
-        if (h->opt.force_env < 0) {
-            if (int rc = launch_envelope_probe(h, 2, ke2, nxs, ny, nz, unit, no_border, kUnguarded, dy, s)) return rc;
-        } else if (int rc = launch_decide(h, dy, s)) return rc;
+        if (int rc = launch_probe_or_decide(h, 2, ke2, nxs, ny, nz, unit, no_border, kUnguarded, dy, s)) return rc;
         if (int rc = launch_sweep_y(h, ke2.in16, d_plane_dsq, kNoSideTable, nxs, ny, nz, sw + kSwMarchY, sw + kSwFarY, s)) return rc;
         if (int rc = launch_envelope(h, 2, ke2, nxs, ny, nz, unit, no_border, sw + kSwFarY, s)) return rc;
         if (d_far) HIP_TRY(h, hipMemcpyAsync(d_far, sw + kSwFarY, 4, hipMemcpyDeviceToDevice, s));
@@ -1382,9 +1382,7 @@ int sdfgpu_sweep_x_lines_device(sdfgpu_handle h, const int32_t* d_plane_dsq, int
         DcIo ke3;
         ke3.in_i32 = d_plane_dsq; ke3.out = d_out_sdf; ke3.y_off = y_global; ke3.ny_glob = ny_global;
         DcDecide dx; dx.stage = 1;
-        if (h->opt.force_env < 0) {
-            if (int rc = launch_envelope_probe(h, 3, ke3, nx, nys, nz, resolution, add_virtual_border, kUnguarded, dx, s)) return rc;
-        } else if (int rc = launch_decide(h, dx, s)) return rc;
+        if (int rc = launch_probe_or_decide(h, 3, ke3, nx, nys, nz, resolution, add_virtual_border, kUnguarded, dx, s)) return rc;
         if (int rc = launch_sweep_x(h, d_plane_dsq, d_out_sdf, rows, nys, nz, resolution, add_virtual_border, sw + kSwMarchX, sw + kSwFarX, s)) return rc;
         if (int rc = launch_envelope(h, 3, ke3, nx, nys, nz, resolution, add_virtual_border, sw + kSwFarX, s)) return rc;
         if (!h->opt.defer_fold) if (int rc3 = fold_slots(h, d_maxdsq, s)) return rc3;

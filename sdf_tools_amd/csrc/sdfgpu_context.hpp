@@ -1,7 +1,8 @@
 // sdfgpu_context.hpp -- the handle behind include/sdfgpu.h (struct sdfgpu_context) and what the host code of every translation
 // unit needs from it: errors, the allocator with its red zones, the argument checks that more than one family shares, the staged
 // host transfers.  Host code only.  The non-template functions are defined in sdfgpu_context.hip, except build_device_impl and
-// convex_sdf, which sdfgpu.hip (the unit that launches the build kernels) offers to the families.
+// convex_sdf, which sdfgpu.hip (the unit that launches the build kernels) offers to the families.  The options a build reads
+// (BuildOptions) and what it decides from them on the host (plan_build) are in sdfgpu_plan.hpp, plain C++ like the policy header.
 //
 // It includes no kernel header, so that a unit which includes it gains no device code: a kernel defined in sdfgpu_kernels.hpp or
 // one of its sibling build headers is launched from sdfgpu.hip only, and a unit that wants those headers' constants defines
@@ -10,7 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "sdfgpu_policy.hpp"
+#include "sdfgpu_plan.hpp"
 #include "sdfgpu_hostteam.hpp"
 #include "sdfgpu.h"
 
@@ -22,8 +23,6 @@
 #include <vector>
 
 namespace sdfgpu {
-
-constexpr int kShellMinWords = 128;           // KD6 (sdfgpu_dense6.hpp): active words (of kShellGroup x 256) below which a group is left to KF
 
 struct DeviceBuffer {
     void* ptr = nullptr;
@@ -92,63 +91,6 @@ struct ContextBuffers {
     DeviceBuffer* end() { return begin() + sizeof(ContextBuffers) / sizeof(DeviceBuffer); }
 };
 static_assert(sizeof(ContextBuffers) == 32 * sizeof(DeviceBuffer), "ContextBuffers holds DeviceBuffer members only");
-
-// What sdfgpu_set_option and sdfgpu_set_tuning write and a build only reads (include/sdfgpu.h has the table).  The defaults here are
-// the documented ones.
-struct BuildOptions {
-    // tier selection
-    bool dense_on = true;            // try the bit-parallel dense kernel first when the shape allows
-    bool dense_generic_on = true;    // generic dense kernels for shapes / modes the tuned ones do not take
-    bool envelope_on = true;         // bound the outward scans and redo far-field sweeps with the envelope kernels
-    bool envelope_dc = true;         // use the divide-and-conquer envelope kernel (sdfgpu_envelope_dc.hpp) when the shape allows
-    int force_env = -1;              // -1 automatic, 1 = envelope kernels only (option "envelope_mode")
-    // an axis is far-field when more than 1 / kFarDen of the probed voxels have d^2 >= thr.  Per axis, from the measured
-    // break-even of the two sweeps at 512^3 (tools/p_sweep.py, tools/ythr_probe.py): the y marching sweep (2 B rows, radius-8
-    // windows) against the far-field PAIR (int32 hand-off, no x probe) breaks even at in-plane d^2 ~ 36 on an eighth of the
-    // voxels (Bernoulli p = 0.02: 1.31 vs 1.29 ms; p = 0.015: 1.54 vs 1.29 ms; p = 0.025: 1.21 vs 1.28 ms); the x marching sweep falls behind the far-field kernel as soon as its
-    // radius-3 window stops deciding nearly every voxel (Bernoulli p = 0.03: 0.65 ms against 0.55; p = 0.04 and denser:
-    // marching wins), so its threshold is d^2 >= 9 on 1 / 24 of the voxels (p = 0.03: 6 %, p = 0.04: 2.4 %)
-    // (round 3, third-generation far-field kernel: KE2 0.57 -> 0.39 ms moves the y break-even from Bernoulli p ~ 0.018 up to
-    //  p ~ 0.035 -- tools/tier_sweep.py: p = 0.03 1.01 vs 0.97 ms, p = 0.02 1.16 vs 0.985, p = 0.04 0.87 vs 0.97 -- i.e. from
-    //  "d^2 >= 36 on an eighth" to "d^2 >= 16 on a fifth" of the voxels: (1 - p)^49 = 0.225 at p = 0.03, 0.135 at p = 0.04)
-    int far_thr[2] = {16, 9};
-    bool probe_window = true;        // tier probes as window statistics (option "probe_window"; 0 = level A of the far-field search on sampled tiles)
-    // dense tier
-    bool dense3_fixed = true;        // KD3's nz = 512 instance (option "dense3_fixed")
-    bool shell_on = true;            // KD6, the bit-parallel shell pass between KD3 and KF (option "dense_shell")
-    int shell_min_words = kShellMinWords;   // option "shell_min_words"
-    bool standby_far = true;         // stand-by pipeline behind a trusted dense tier = the far-field pair (bounded whatever the scene
-                                     // turns into), not fused K12 + K3/16 with unbounded scans (option "standby_far")
-    bool standby_fold = true;        // the stand-by x sweep's launch folds the maxima and publishes the status block itself (option "standby_fold")
-    bool standby_single = true;      // the stand-by pair and the fold are ONE guarded launch whose workgroups take tiles by ticket (k_envelope_standby;
-                                     // option "standby_single"; 0: the y and the x sweep as two launches)
-    int standby_grid = 1024;         // workgroups of the stand-by launches (LOOP form; option "standby_grid"): 4 per CU = all resident at once
-    // Serpentine tile order (option "ball_serpentine"): a whole build that writes the buffer the handle's last KD launch wrote, at
-    // the same size, walks KD's tiles in the opposite order -- it starts on the lines the last one finished with, which are
-    // the ones the Infinity Cache still holds; walked the same way round every time, an LRU-like cache has evicted each
-    // line just before it is reached.  Speed only: the field, the maxima and the flags do not depend on the order.
-    bool ball_serpentine = true;
-    // sweeps
-    bool fused_zy = true;            // use K12 (z sweep fused into the y sweep) when the shape allows
-    bool fused_always = false;       // ... whenever it does (option "fused_zy" = 2)
-    int fused_h = 2;                 // its register-window radius at nz = 512: 2 or 3 (option "fused_window")
-    bool plane16_on = true;          // use the int16 plane field + side table when the shape allows
-    bool z_wave_on = true;           // z sweep with wave-private rows where nz allows it (option "z_wave"; 0 = the workgroup form)
-    int x16_v = 4, x16_h = 3;        // K3/16 variant: voxels per lane, window radius
-    int tune_ty = 0, tune_tx = 0;    // rows marched per thread by the y / x sweep (sdfgpu_set_tuning; 0 = automatic)
-    bool i32_handoff = true;         // far-field pair: int32 plane field between the y and x sweeps (option "i32_handoff")
-    bool dc_fixed = true;            // far-field kernel: the 512-voxel-line instances (option "dc_fixed")
-    bool plane_skip = true;          // builds that go straight to the far-field pair: the z sweep marks the x-planes that hold a filled voxel,
-                                     // the y sweep skips the tiles of the others, the x sweep their row loads (option "plane_skip")
-    // ... and y tiles whose 16 lines are all flat-positive (a floor under open space) skip the search (option "flat_tiles")
-    int flat_tiles = 1;              // (2: every such tile tries, whatever the habit says -- tests)
-    // host side / debugging
-    int host_pack = 1;       // host-buffer builds classify on the host and upload bits (option "host_pack"; 0 = upload the
-                             // caller's mask / cells and classify on the device, as rounds 1 - 4 did)
-    int defer_fold = 0;           // stage entry points leave their maxima in the slot array until sdfgpu_fold_extrema_device
-    bool rs_plain_atomics = false;        // option "resample_plain_atomics": one atomic per lane (tools/resample_bench.py)
-    bool rs_timing = false;               // option "resample_timing": events around the two kernels (sdfgpu_debug_resample_times)
-};
 
 // What the sdfgpu_last_* and sdfgpu_debug_* calls report about the most recent build or stage call.
 struct LastBuild {

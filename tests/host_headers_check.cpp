@@ -3,7 +3,8 @@
 // that drives everything on the path that runs on the HOST and needs no GPU:
 //   * the oracle's C restatement (oracle/sdf_oracle.c: reference algorithm, virtual border, exact EDT, brute force) on small
 //     scenes, cross-checked against each other;
-//   * the dense tier's policy object (sdf_tools_amd/csrc/sdfgpu_policy.hpp) through a build / report sequence;
+//   * the dense tier's policy object (sdf_tools_amd/csrc/sdfgpu_policy.hpp) through a build / report sequence, and the build
+//     planner over it (sdfgpu_plan.hpp);
 //   * the mirror headers' host logic (include/sdf_tools, include/arc_utilities): the uninitialised result storage of the
 //     build seams, moves that must not copy, serialisation round trips, hostile headers, per-point queries.
 // TEST INFRASTRUCTURE.  Linked against libsdfgpu.so only because the inline seams of the headers name its symbols; no ABI call
@@ -31,6 +32,7 @@ int sdf_oracle_exact_sdf(const uint8_t* filled, int64_t nx, int64_t ny, int64_t 
                          float* out_sdf, double* out_extrema, int64_t* out_dsq);
 }
 
+#include "../sdf_tools_amd/csrc/sdfgpu_plan.hpp"
 #include "../sdf_tools_amd/csrc/sdfgpu_policy.hpp"
 #include "sdf_tools/collision_map.hpp"
 #include "sdf_tools/sdf.hpp"
@@ -104,6 +106,31 @@ static int check_policy() {
         if (b == 4500) far.set_mode(0);
     }
     CHECK(predicted > 2000 && far.streak >= 0 && far.seq == 5000);
+    // the planner over both (sdfgpu_plan.hpp): options, facts and reports that change from build to build, sizes near 2^31 voxels
+    sdfgpu::BuildOptions opt;
+    size_t bytes = 0;
+    for (int b = 0; b < 4000; ++b) {
+        sdfgpu::BuildFacts f;
+        f.nx = (b % 5 == 0) ? 2047 : 1 + b % 40; f.ny = (b % 5 == 0) ? 1024 : 1 + (b * 7) % 1100; f.nz = (b % 3) ? 32 << (b % 6) : 1 + b % 1000;
+        f.vb = b % 2; f.occ = sdfgpu::BuildFacts::Occ(b % 3); f.occ16 = b % 4 != 1; f.out16 = b % 8 != 3;
+        f.dense_shape = (f.nz % 32) == 0; f.far_shape[0] = b % 9 != 0; f.far_shape[1] = b % 10 != 0;
+        f.z_wave_shape = f.nz >= 64 && f.dense_shape; f.fused_nz = f.nz == 512 || f.nz == 1024;
+        f.dense_slot_free = b % 3 != 0; f.far_slot_free = b % 4 != 0;
+        opt.dense_on = b % 16 != 5; opt.envelope_on = b % 32 != 7; opt.fused_always = b % 64 == 9; opt.standby_far = b % 6 != 2;
+        opt.force_env = b % 50 == 11 ? 1 : -1;
+        if (b % 100 == 50) pol.expect_dense = !pol.expect_dense;
+        const uint64_t seq = far.seq;
+        const sdfgpu::BuildPlan p = sdfgpu::plan_build(opt, pol, far, f);
+        CHECK(far.seq == seq + 1);
+        CHECK(!p.predicted || p.select);
+        CHECK(!p.standby || (!p.fused && !p.select));
+        CHECK((p.z_bytes != 0) == p.z_sweep() && p.yz_bytes == (size_t)(f.nx * f.ny * f.nz) * 4);
+        bytes += p.bits_bytes + p.unc_bytes + p.planebits_bytes + p.plane16_bytes;
+        if (p.report == sdfgpu::BuildPlan::Report::dense) pol.prev = sdfgpu::ReportedBuild{p.dense, p.dense_generic, p.tier.fix_mode_build(), p.tier.staged, p.predicted};
+        if (p.report == sdfgpu::BuildPlan::Report::dense && b % 3 == 1) pol.consume_report(b % 7 == 0, b % 5 == 0, b % 7 == 0);
+        if (p.report == sdfgpu::BuildPlan::Report::far) far.consume_report(b % 200 < 150, b % 200 < 150);
+    }
+    CHECK(bytes > 0);
     return 0;
 }
 
