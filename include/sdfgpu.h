@@ -738,6 +738,66 @@ int sdfgpu_resample_cells(sdfgpu_handle h, const void* src, size_t cell_bytes, i
 int sdfgpu_debug_resample_times(sdfgpu_handle h, double* out_winner_ms, double* out_gather_ms);
 
 /* ---------------------------------------------------------------------------
+ * Shape rasteriser: what the reference's SDF_Builder asks MoveIt per voxel (src/sdf_tools/sdf_builder.cpp:281-363), decided on
+ * the GPU for a list of primitive shapes.  DESIGN.md section 26.
+ * PREDICATE.  Voxel (x, y, z) of an nx x ny x nz grid is filled iff the closed probe cube {p : |p_a - c_a| <= voxel_size / 2 for
+ * a = x, y, z} meets the closed solid of at least one shape; touching counts.  The cube's axes are the WORLD's axes, whatever the
+ * rotation of `origin` (the reference's prismatic probe does the same: on a rotated origin the probes do not tile the grid), and
+ *   c = origin * (voxel_size (x + 0.5), voxel_size (y + 0.5), voxel_size (z + 0.5), 1).
+ * voxel_size is the grid's resolution (the classes' GetResolution(): cubic voxels); the message of a refusal calls it the resolution.
+ * A shape follows shape_msgs::SolidPrimitive: `pose` is a row-major 4 x 4 mapping the shape frame to the world (its first three
+ * rows are read, all 12 entries; the fourth row is not), its rotation block is taken as orthonormal, and the solid is the image
+ * of the canonical solid:
+ *   SDFGPU_SHAPE_BOX (1)       dims = full extents x, y, z.  The 15 separating axes of cube and oriented box; an axis separates
+ *                              only when |t . L| > r_cube + r_box, so a cross axis that degenerates to 0 never does.
+ *   SDFGPU_SHAPE_SPHERE (2)    dims = radius.  sum_a max(|c_a - s_a| - voxel_size / 2, 0)^2 <= radius^2.
+ *   SDFGPU_SHAPE_CYLINDER (3)  dims = height, radius; the axis is the shape's z.  With q the centre in the shape frame and
+ *                              h = voxel_size / 2: empty when |q_z| - height / 2 > 1.75 h or q_x^2 + q_y^2 > (radius + 1.75 h)^2;
+ *                              filled when the centre is in the solid; else each of the cube's six faces, in the shape frame,
+ *                              is clipped to |z| <= height / 2 (two Sutherland-Hodgman passes) and the voxel is filled iff the
+ *                              least squared distance from the axis to the xy projection of a clipped face's edge is <= radius^2,
+ *                              or the axis segment passes through the cube (slab test in the world's axes).
+ * Every other type (a cone (4), a mesh, a plane) is refused.  Arithmetic: double precision, the centre's rows as
+ * ((m0 v0 + m1 v1) + m2 v2) + m3 as in Resample, separate products and sums throughout (no FMA); tests/scene_raster_restated.py
+ * states every operation.  A shape reaches this test only in regions its world bounds, inflated by `voxel_size` (more than the
+ * probe's circum-radius), meet; the slack is far above the rounding, so the culling changes no voxel.
+ * OUTPUTS, each optional, at least one: bits (the linear bit field of sdfgpu_build_bits_device: bit v & 31 of word v >> 5 is voxel
+ * v = (x ny + y) nz + z, ceil(n / 32) words, the spare bits of the last word zero), mask (uint8 0 / 1 per voxel), object_ids
+ * (uint32 per voxel: the object_id of the FIRST shape in list order that meets the probe, 0 where none does; every shape's
+ * object_id must then be >= 1).  Every word, byte and id is written by exactly one thread: the result does not depend on scheduling.
+ * n_shapes == 0 is valid and clears the outputs; n_shapes above SDFGPU_MAX_SHAPES is refused.
+ * Refused (SDFGPU_ERR_INVALID_ARGUMENT, with a message, nothing written): every output null; a dimension or a voxel_size that is
+ * not positive (or not finite); an origin entry that is not finite; too many shapes; null shapes with n_shapes > 0; in the device
+ * form d_shapes off 8 bytes, d_bits or d_object_ids off 4.  A shape is refused for an unknown type, a dim (of those its type
+ * uses) that is negative or not finite, a pose entry (of the 12) that is not finite, or object_id 0 when ids are asked for.
+ *
+ *   sdfgpu_rasterize_shapes: host shapes and outputs, through the handle's staging buffers on the null stream; synchronous.  The
+ *       shapes are checked on the host before anything is launched; the message names the first refused shape's index.
+ *   sdfgpu_rasterize_shapes_device: device pointers; a memset and three kernels on `stream`, nothing elsewhere, no host
+ *       synchronisation.  The shapes are checked on the device: when one is refused the outputs are CLEARED (all zero) and a
+ *       status word holds the lowest such index.  out_bad_shape (optional): the call synchronises `stream`, stores that index
+ *       (-1: none) and, if there is one, returns SDFGPU_ERR_INVALID_ARGUMENT naming it; without it the call never waits.  The
+ *       scratch (one status block, 48 bytes per shape, one candidate bit per coarse region and shape; at most 4096 regions, so
+ *       at most 35 MiB, sized from nx, ny, nz and n_shapes alone) belongs to the handle: a call on another stream is ordered
+ *       behind the last one on the device.
+ * ------------------------------------------------------------------------- */
+#define SDFGPU_SHAPE_BOX 1
+#define SDFGPU_SHAPE_SPHERE 2
+#define SDFGPU_SHAPE_CYLINDER 3
+#define SDFGPU_MAX_SHAPES 65536
+typedef struct sdfgpu_shape {
+    uint32_t type;
+    uint32_t object_id;
+    double dims[3];
+    double pose[16];
+} sdfgpu_shape;
+int sdfgpu_rasterize_shapes_device(sdfgpu_handle h, const sdfgpu_shape* d_shapes, int64_t n_shapes, const double origin[16], double voxel_size,
+                                   int64_t nx, int64_t ny, int64_t nz, uint32_t* d_bits, uint8_t* d_mask, uint32_t* d_object_ids,
+                                   int64_t* out_bad_shape, void* stream);
+int sdfgpu_rasterize_shapes(sdfgpu_handle h, const sdfgpu_shape* shapes, int64_t n_shapes, const double origin[16], double voxel_size,
+                            int64_t nx, int64_t ny, int64_t nz, uint32_t* bits, uint8_t* mask, uint32_t* object_ids);
+
+/* ---------------------------------------------------------------------------
  * Display export: the device side of the reference's ExportForDisplay family (CollisionMapGrid, TaggedObjectCollisionMapGrid,
  * SignedDistanceField): which voxels are drawn, in which order, where they are and in which colour.  DESIGN.md section 23.
  * Indices: voxel (x, y, z) is (x ny + y) nz + z, a uint32; a grid of more than 2^32 - 1 voxels is refused by its shape before

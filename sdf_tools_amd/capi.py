@@ -40,6 +40,7 @@ EXPORTS = [
     "sdfgpu_display_select_cells_device", "sdfgpu_display_select_cells", "sdfgpu_display_select_sdf_device", "sdfgpu_display_select_sdf",
     "sdfgpu_display_expand_device", "sdfgpu_display_sdf_colors_device", "sdfgpu_display_sdf_colors",
     "sdfgpu_display_contour_reach", "sdfgpu_display_select_contour_device", "sdfgpu_display_select_contour",
+    "sdfgpu_rasterize_shapes_device", "sdfgpu_rasterize_shapes",
 ]
 
 # include/sdfgpu.h "Projection": modes and per-point statuses
@@ -54,6 +55,11 @@ QUERY_OK, QUERY_OUTSIDE, QUERY_WINDOW_TOO_LARGE, QUERY_NON_FINITE = range(4)
 # include/sdfgpu.h "Display export": rules and class bits
 DISPLAY_OCCUPANCY, DISPLAY_KEY_FIELD = 0, 1
 DISPLAY_FILLED, DISPLAY_EMPTY, DISPLAY_UNKNOWN = 1, 2, 4
+
+# include/sdfgpu.h "Shape rasteriser": the types, the limit and struct sdfgpu_shape as a numpy record (160 bytes)
+SHAPE_BOX, SHAPE_SPHERE, SHAPE_CYLINDER = 1, 2, 3
+MAX_SHAPES = 65536
+SHAPE_DTYPE = np.dtype([("type", np.uint32), ("object_id", np.uint32), ("dims", np.float64, (3,)), ("pose", np.float64, (16,))], align=True)
 
 
 class SdfGpuError(RuntimeError):
@@ -163,6 +169,8 @@ def load_library():
     L.sdfgpu_display_contour_reach.argtypes = [dbl, vp]
     L.sdfgpu_display_select_contour_device.argtypes = [vp, vp, sz, sz, sz, i64, i64, i64, ci, ci, vp, i64, ci, ci, vp, vp, i64, vp, vp, vp, i64, vp, vp]
     L.sdfgpu_display_select_contour.argtypes = [vp, vp, sz, sz, sz, i64, i64, i64, ci, ci, vp, i64, ci, ci, vp, vp, i64, vp, vp, vp, i64, vp]
+    L.sdfgpu_rasterize_shapes_device.argtypes = [vp, vp, i64, vp, dbl, i64, i64, i64, vp, vp, vp, vp, vp]
+    L.sdfgpu_rasterize_shapes.argtypes = [vp, vp, i64, vp, dbl, i64, i64, i64, vp, vp, vp]
     L.sdfgpu_build_batch_device.argtypes = [vp, vp, i64, i64, i64, i64, dbl, vp, ci, vp, vp]
     L.sdfgpu_get_extrema_batch.argtypes = [vp, i64, vp, vp]
     L.sdfgpu_build_batch.argtypes = [vp, vp, i64, i64, i64, i64, dbl, vp, ci, vp, vp, vp]
@@ -264,6 +272,19 @@ def _doubles(v, n):
     if a.size != n:
         raise ValueError("expected %d values, got %d" % (n, a.size))
     return (ctypes.c_double * n)(*a)
+
+
+def make_shapes(items):
+    """[(type, object_id, dims, pose 4 x 4 or 3 x 4)] -> SHAPE_DTYPE records (missing dims are 0, the pose's fourth row 0 0 0 1)"""
+    out = np.zeros(len(items), SHAPE_DTYPE)
+    for rec, (kind, object_id, dims, pose) in zip(out, items):
+        rec["type"], rec["object_id"] = kind, object_id
+        d = np.asarray(dims, np.float64).reshape(-1)
+        rec["dims"][:d.size] = d
+        m = np.eye(4)
+        m[:3] = np.asarray(pose, np.float64).reshape(-1, 4)[:3]
+        rec["pose"] = m.reshape(-1)
+    return out
 
 
 def project_step_limit(shape, stepsize_multiplier=1.0 / 8.0, max_steps=0):
@@ -889,6 +910,36 @@ class SdfGpu:
         """Device field -> d_colors (float32 [n, 4]).  Synchronises `stream`."""
         nx, ny, nz = (int(v) for v in shape)
         self._check(self._lib.sdfgpu_display_sdf_colors_device(self._h, d_sdf, nx, ny, nz, float(alpha), d_colors, stream or None))
+
+    # ---- shape rasteriser (include/sdfgpu.h "Shape rasteriser") -------------
+    def rasterize_shapes(self, shapes, origin, resolution, shape, bits=True, mask=False, object_ids=False):
+        """shapes: a numpy array of SHAPE_DTYPE records (see make_shapes); origin: 4 x 4, grid frame -> world.  Returns a dict of the
+        outputs asked for: "bits" uint32 [ceil(n / 32)], "mask" uint8 [nx, ny, nz], "object_ids" uint32 [nx, ny, nz]."""
+        nx, ny, nz = (int(v) for v in shape)
+        sh = np.ascontiguousarray(shapes, dtype=SHAPE_DTYPE).reshape(-1)
+        n = nx * ny * nz
+        out = {}
+        if bits:
+            out["bits"] = np.empty((max(n, 0) + 31) // 32, np.uint32)
+        if mask:
+            out["mask"] = np.empty((nx, ny, nz), np.uint8)
+        if object_ids:
+            out["object_ids"] = np.empty((nx, ny, nz), np.uint32)
+        ptr = [out[k].ctypes.data if k in out else None for k in ("bits", "mask", "object_ids")]
+        self._check(self._lib.sdfgpu_rasterize_shapes(self._h, sh.ctypes.data if sh.size else None, int(sh.size), _doubles(origin, 16),
+                                                      float(resolution), nx, ny, nz, *ptr))
+        return out
+
+    def rasterize_shapes_device(self, d_shapes, n_shapes, origin, resolution, shape, d_bits=0, d_mask=0, d_object_ids=0, check=False,
+                                stream=0):
+        """Device form (device addresses as ints), enqueued on `stream`.  check: synchronise the stream and return the index of the
+        first refused shape (-1: none; a refused shape also raises); without it the call does not wait and returns None."""
+        nx, ny, nz = (int(v) for v in shape)
+        bad = ctypes.c_int64(-2)
+        self._check(self._lib.sdfgpu_rasterize_shapes_device(self._h, d_shapes or None, int(n_shapes), _doubles(origin, 16), float(resolution),
+                                                             nx, ny, nz, d_bits or None, d_mask or None, d_object_ids or None,
+                                                             ctypes.byref(bad) if check else None, stream or None))
+        return int(bad.value) if check else None
 
     def debug_resample_times(self):
         """(memset + winner kernel, gather kernel) of the last resample call in ms, after set_option("resample_timing", 1)"""

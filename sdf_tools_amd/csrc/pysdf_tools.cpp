@@ -19,6 +19,7 @@
 #include "arc_utilities/zlib_helpers.hpp"
 #include "sdf_tools/collision_map.hpp"
 #include "sdf_tools/device_sdf.hpp"
+#include "sdf_tools/sdf_builder.hpp"
 #include "sdf_tools/tagged_object_collision_map.hpp"
 
 namespace py = pybind11;
@@ -672,6 +673,89 @@ PYBIND11_MODULE(pysdf_tools, m) {
         .def("DeserializeSelf", [](VoxelGridVecd& g, const std::vector<uint8_t>& buffer, uint64_t current, py::object) {
             return g.DeserializeSelf(buffer, current, arc_utilities::DeserializeVectorOfDoubles); },
              "deserialize", py::arg("buffer"), py::arg("current"), py::arg("value_deserializer") = py::none());
+
+    // ---- SDF_Builder and the message mirrors it reads (include/sdf_tools/sdf_builder.hpp, planning_scene.hpp) ------------------------------
+    py::class_<geometry_msgs::Pose>(m, "Pose")
+        .def(py::init([](const std::array<double, 3>& position, const std::array<double, 4>& orientation_xyzw) {
+            geometry_msgs::Pose p;
+            p.position.x = position[0]; p.position.y = position[1]; p.position.z = position[2];
+            p.orientation.x = orientation_xyzw[0]; p.orientation.y = orientation_xyzw[1]; p.orientation.z = orientation_xyzw[2]; p.orientation.w = orientation_xyzw[3];
+            return p;
+        }), py::arg("position") = std::array<double, 3>{0.0, 0.0, 0.0}, py::arg("orientation_xyzw") = std::array<double, 4>{0.0, 0.0, 0.0, 1.0})
+        .def("matrix", [](const geometry_msgs::Pose& p) {
+            py::array_t<double> out({4, 4});
+            sdf_tools::PoseToMatrix(p, out.mutable_data());
+            return out;
+        }, "row-major 4 x 4 as SDF_Builder passes it to the rasteriser");
+    py::class_<shape_msgs::SolidPrimitive>(m, "SolidPrimitive")
+        .def(py::init([](int type, const std::vector<double>& dimensions) {
+            shape_msgs::SolidPrimitive s;
+            s.type = (uint8_t)type; s.dimensions = dimensions;
+            return s;
+        }), py::arg("type") = 0, py::arg("dimensions") = std::vector<double>())
+        .def_readwrite("type", &shape_msgs::SolidPrimitive::type)
+        .def_readwrite("dimensions", &shape_msgs::SolidPrimitive::dimensions)
+        .def_property_readonly_static("BOX", [](py::object) { return (int)shape_msgs::SolidPrimitive::BOX; })
+        .def_property_readonly_static("SPHERE", [](py::object) { return (int)shape_msgs::SolidPrimitive::SPHERE; })
+        .def_property_readonly_static("CYLINDER", [](py::object) { return (int)shape_msgs::SolidPrimitive::CYLINDER; })
+        .def_property_readonly_static("CONE", [](py::object) { return (int)shape_msgs::SolidPrimitive::CONE; });
+    py::class_<shape_msgs::Mesh>(m, "Mesh").def(py::init<>());
+    py::class_<shape_msgs::Plane>(m, "Plane").def(py::init<>());
+    py::class_<moveit_msgs::CollisionObject>(m, "CollisionObject")
+        .def(py::init<>())
+        .def_readwrite("id", &moveit_msgs::CollisionObject::id)
+        .def_readwrite("primitives", &moveit_msgs::CollisionObject::primitives)
+        .def_readwrite("primitive_poses", &moveit_msgs::CollisionObject::primitive_poses)
+        .def_readwrite("meshes", &moveit_msgs::CollisionObject::meshes)
+        .def_readwrite("mesh_poses", &moveit_msgs::CollisionObject::mesh_poses)
+        .def_readwrite("planes", &moveit_msgs::CollisionObject::planes)
+        .def_readwrite("plane_poses", &moveit_msgs::CollisionObject::plane_poses);
+    py::class_<octomap_msgs::OctomapBoxesWithPose>(m, "OctomapBoxesWithPose")
+        .def(py::init<>())
+        .def_readwrite("origin", &octomap_msgs::OctomapBoxesWithPose::origin)
+        .def("SetBoxesNumpy", [](octomap_msgs::OctomapBoxesWithPose& o, const py::array_t<double, py::array::c_style | py::array::forcecast>& centers,
+                                 const py::array_t<double, py::array::c_style | py::array::forcecast>& sizes) {
+            if (centers.ndim() != 2 || centers.shape(1) != 3 || sizes.ndim() != 1 || sizes.shape(0) != centers.shape(0))
+                throw std::invalid_argument("centers must be [n, 3] and sizes [n]");
+            const size_t n = (size_t)sizes.shape(0);
+            o.octomap.centers.resize(n);
+            o.octomap.sizes.assign(sizes.data(), sizes.data() + n);
+            for (size_t i = 0; i < n; ++i) { o.octomap.centers[i].x = centers.data()[3 * i]; o.octomap.centers[i].y = centers.data()[3 * i + 1]; o.octomap.centers[i].z = centers.data()[3 * i + 2]; }
+        }, py::arg("centers"), py::arg("sizes"), "occupied leaves as boxes: centres [n, 3] and edge lengths [n] in the octomap's frame")
+        .def("NumBoxes", [](const octomap_msgs::OctomapBoxesWithPose& o) { return o.octomap.centers.size(); });
+    py::class_<moveit_msgs::PlanningSceneWorld>(m, "PlanningSceneWorld")
+        .def(py::init<>())
+        .def_readwrite("collision_objects", &moveit_msgs::PlanningSceneWorld::collision_objects)
+        .def_readwrite("octomap", &moveit_msgs::PlanningSceneWorld::octomap);
+    py::class_<moveit_msgs::PlanningScene>(m, "PlanningScene")
+        .def(py::init<>())
+        .def_readwrite("name", &moveit_msgs::PlanningScene::name)
+        .def_readwrite("world", &moveit_msgs::PlanningScene::world);
+    m.attr("USE_CACHED") = (int)sdf_tools::USE_CACHED;
+    m.attr("USE_ONLY_OCTOMAP") = (int)sdf_tools::USE_ONLY_OCTOMAP;
+    m.attr("USE_ONLY_COLLISION_OBJECTS") = (int)sdf_tools::USE_ONLY_COLLISION_OBJECTS;
+    m.attr("USE_FULL_PLANNING_SCENE") = (int)sdf_tools::USE_FULL_PLANNING_SCENE;
+    const auto collision_map_numpy = [](const VoxelGrid::VoxelGrid<uint8_t>& g) {
+        py::array_t<uint8_t> out({g.GetNumXCells(), g.GetNumYCells(), g.GetNumZCells()});
+        std::memcpy(out.mutable_data(), g.GetImmutableRawData().data(), g.GetImmutableRawData().size());
+        return out;
+    };
+    py::class_<sdf_tools::SDF_Builder>(m, "SDF_Builder")
+        .def(py::init<>())
+        .def(py::init<const Isometry3d&, const std::string&, double, double, double, double, float, const sdf_tools::SDF_Builder::PlanningSceneSource&>(),
+             py::arg("origin_transform"), py::arg("frame"), py::arg("x_size"), py::arg("y_size"), py::arg("z_size"), py::arg("resolution"),
+             py::arg("OOB_value"), py::arg("planning_scene_source") = sdf_tools::SDF_Builder::PlanningSceneSource())
+        .def(py::init<const std::string&, double, double, double, double, float, const sdf_tools::SDF_Builder::PlanningSceneSource&>(),
+             py::arg("frame"), py::arg("x_size"), py::arg("y_size"), py::arg("z_size"), py::arg("resolution"), py::arg("OOB_value"),
+             py::arg("planning_scene_source") = sdf_tools::SDF_Builder::PlanningSceneSource())
+        .def("UpdatePlanningSceneFromMessage", &sdf_tools::SDF_Builder::UpdatePlanningSceneFromMessage)
+        .def("UpdateSDF", [](sdf_tools::SDF_Builder& b, int mode) { return b.UpdateSDF((uint8_t)mode); })
+        .def("GetCachedSDF", [](const sdf_tools::SDF_Builder& b) { return b.GetCachedSDF(); })
+        .def("UpdateCollisionMap", [collision_map_numpy](sdf_tools::SDF_Builder& b, int mode) { return collision_map_numpy(b.UpdateCollisionMap((uint8_t)mode)); },
+             "the VoxelGrid<uint8_t> of the reference as uint8 [nx, ny, nz]")
+        .def("GetCachedCollisionMap", [collision_map_numpy](const sdf_tools::SDF_Builder& b) { return collision_map_numpy(b.GetCachedCollisionMap()); })
+        .def("UpdateSDFDevice", [](sdf_tools::SDF_Builder& b, int mode) { return b.UpdateSDFDevice((uint8_t)mode); })
+        .def("UpdateTaggedCollisionMap", [](sdf_tools::SDF_Builder& b, int mode) { return b.UpdateTaggedCollisionMap((uint8_t)mode); });
     m.def("ExtractSignedDistanceFieldBatch", [](const std::vector<const CollisionMapGrid*>& maps, float oob_value, bool unknown_is_filled,
                                                 bool add_virtual_border) {
         return sdf_tools::ExtractSignedDistanceFieldBatch(maps, oob_value, unknown_is_filled, add_virtual_border);

@@ -87,10 +87,11 @@ struct ContextBuffers {
     DeviceBuffer dp_scratch; // sdfgpu_display_*: status, draw keys, drawn bit words, tile counts, segment sums (sdfgpu_display.hpp)
     DeviceBuffer dp_sort;    // sdfgpu_display_select_*: the sort's pair buffers and table; the sorted keys when the caller takes none
     DeviceBuffer dp_out;     // host forms of sdfgpu_display_select_*: indices, keys, group keys and offsets on their way to the caller
+    DeviceBuffer sc_scratch; // sdfgpu_rasterize_shapes*: status, world bounds per shape, candidate bits per coarse region (sdfgpu_scene.hpp)
     DeviceBuffer* begin() { return &zfield; }
     DeviceBuffer* end() { return begin() + sizeof(ContextBuffers) / sizeof(DeviceBuffer); }
 };
-static_assert(sizeof(ContextBuffers) == 32 * sizeof(DeviceBuffer), "ContextBuffers holds DeviceBuffer members only");
+static_assert(sizeof(ContextBuffers) == 33 * sizeof(DeviceBuffer), "ContextBuffers holds DeviceBuffer members only");
 
 // What the sdfgpu_last_* and sdfgpu_debug_* calls report about the most recent build or stage call.
 struct LastBuild {
@@ -201,6 +202,7 @@ struct sdfgpu_context : sdfgpu::ContextBuffers {
                                           // pending on its stream when the call returns: one on another stream waits for it first
     sdfgpu::StreamOrder rs_order;         // recorded behind every resample, which may return with its kernels pending on its
                                           // stream: one on another stream waits for it before it clears the winner words
+    sdfgpu::StreamOrder sc_order;         // recorded behind every shape rasterisation (the same rule, for sc_scratch)
     hipEvent_t rs_time_ev[3] = {nullptr, nullptr, nullptr};   // "resample_timing"
     bool rs_timed = false;
     int profiling = 0;            // 0 off, 1 an event behind every stage, 2 events around the dense ball kernel only,
