@@ -1,8 +1,9 @@
 // sdf_builder -- sdf_tools::SDF_Builder (reference include/sdf_tools/sdf_builder.hpp, src/sdf_tools/sdf_builder.cpp): from the
 // shapes of a planning scene to a collision map and a signed distance field.  The reference places a cube of side `resolution` at
 // every voxel centre and asks MoveIt whether it collides with the world, one check per voxel on one host thread; here the shapes go to
-// the GPU (a few KB), the same predicate is decided there for every voxel (include/sdfgpu.h "Shape rasteriser", DESIGN.md section
-// 26) and the bit field it writes feeds the SDF build in place.  No per-voxel data crosses the bus on the way in.
+// the GPU (a few KB, and the meshes' vertices and triangles), the same predicate is decided there for every voxel (include/sdfgpu.h
+// "Shape rasteriser" and "Planes and triangle meshes", DESIGN.md sections 26 and 27) and the bit field it writes feeds the SDF build
+// in place.  No per-voxel data crosses the bus on the way in.
 //
 // What is kept: the names, the USE_* constants, the exception texts, the cached results, the virtual border off.
 // What differs, because there is no ROS here:
@@ -13,10 +14,12 @@
 //     USE_ONLY_OCTOMAP the octomap, USE_ONLY_COLLISION_OBJECTS the collision objects, USE_FULL_PLANNING_SCENE both.
 //     UpdatePlanningSceneFromMessage keeps the whole message.
 //   - the messages are the plain mirrors of planning_scene.hpp; the octomap arrives as boxes.
-//   - primitives are boxes, spheres and cylinders.  A cone, a mesh or a plane is refused with std::invalid_argument naming the object
-//     (the reference hands them to FCL).
-//   - whether FCL counts exact contact as a collision is UNVERIFIED (FCL and MoveIt are not available to this project); here touching
-//     counts.
+//   - primitives are boxes, spheres and cylinders; a cone is refused with std::invalid_argument naming the object (the reference
+//     hands it to FCL).  Meshes are taken as their surface (a triangle soup: a probe wholly inside a closed mesh is empty) and planes
+//     as infinite and without thickness, each with a pose of its own; one without a pose, with a vertex index out of range, a vertex,
+//     a normal or a pose that is not finite, or a zero normal is refused in the same way.
+//   - whether FCL counts exact contact as a collision, and whether it reads meshes and planes as said, is UNVERIFIED (FCL and MoveIt
+//     are not available to this project); here touching counts.
 // Extensions: UpdateSDFDevice (the field stays in HBM) and UpdateTaggedCollisionMap (object ids: the 1-based index of the collision
 // object, and one more id for the octomap).
 #pragma once
@@ -86,15 +89,29 @@ protected:
             for (int j = 0; j < 4; ++j) out[4 * i + j] = a[4 * i] * b[j] + a[4 * i + 1] * b[4 + j] + a[4 * i + 2] * b[8 + j] + a[4 * i + 3] * b[12 + j];
     }
 
-    // The shapes of the kept scene in list order: every collision object's primitives (object id = its 1-based index), then the
-    // octomap's boxes (one more id).  Refuses what the rasteriser does not decide.
-    std::vector<sdfgpu_shape> SceneShapes() const {
+    // what the rasterisers take: the shape list, and the meshes with their shared vertex and triangle arrays
+    struct SceneGeometry {
         std::vector<sdfgpu_shape> shapes;
+        std::vector<sdfgpu_mesh> meshes;
+        std::vector<double> vertices;
+        std::vector<uint32_t> triangles;
+    };
+
+    // The kept scene in list order: every collision object's primitives, then its planes (object id = its 1-based index), then the
+    // octomap's boxes (one more id); every object's meshes beside them under the same id.  Refuses what the rasterisers do not
+    // decide, before the GPU is touched.
+    SceneGeometry SceneShapes() const {
+        SceneGeometry scene;
+        std::vector<sdfgpu_shape>& shapes = scene.shapes;
         const std::vector<moveit_msgs::CollisionObject>& objects = planning_scene_.world.collision_objects;
         for (size_t o = 0; o < objects.size(); ++o) {
             const moveit_msgs::CollisionObject& object = objects[o];
-            if (!object.meshes.empty()) throw std::invalid_argument("Collision object '" + object.id + "' has meshes (only boxes, spheres and cylinders are rasterised)");
-            if (!object.planes.empty()) throw std::invalid_argument("Collision object '" + object.id + "' has planes (only boxes, spheres and cylinders are rasterised)");
+            if (object.meshes.size() != object.mesh_poses.size())
+                throw std::invalid_argument("Collision object '" + object.id + "' has meshes without a pose each (" + std::to_string(object.meshes.size()) +
+                                            " meshes, " + std::to_string(object.mesh_poses.size()) + " mesh poses)");
+            if (object.planes.size() != object.plane_poses.size())
+                throw std::invalid_argument("Collision object '" + object.id + "' has planes without a pose each (" + std::to_string(object.planes.size()) +
+                                            " planes, " + std::to_string(object.plane_poses.size()) + " plane poses)");
             if (object.primitives.size() != object.primitive_poses.size())
                 throw std::invalid_argument("Collision object '" + object.id + "' has a different number of primitives and primitive poses");
             for (size_t k = 0; k < object.primitives.size(); ++k) {
@@ -119,6 +136,54 @@ protected:
                     if (!std::isfinite(s.pose[i])) throw std::invalid_argument("Collision object '" + object.id + "' has a primitive pose that is not finite");
                 shapes.push_back(s);
             }
+            // a plane a x + b y + c z + d = 0 of the pose's frame: through p0 = (-d / (a^2 + b^2 + c^2)) (a, b, c), normal (a, b, c)
+            for (size_t k = 0; k < object.planes.size(); ++k) {
+                const double* coef = object.planes[k].coef;
+                const double nn = coef[0] * coef[0] + coef[1] * coef[1] + coef[2] * coef[2];
+                const double scale = -coef[3] / nn;
+                if (!(std::isfinite(coef[0]) && std::isfinite(coef[1]) && std::isfinite(coef[2]) && nn > 0.0 && std::isfinite(scale) &&
+                      std::isfinite(scale * coef[0]) && std::isfinite(scale * coef[1]) && std::isfinite(scale * coef[2])))
+                    throw std::invalid_argument("Collision object '" + object.id + "' has a plane with a zero or non-finite normal");
+                sdfgpu_shape s = sdfgpu_shape();
+                s.type = SDFGPU_SHAPE_PLANE;
+                s.object_id = (uint32_t)(o + 1);
+                for (int d = 0; d < 3; ++d) s.dims[d] = coef[d];
+                double frame[16];
+                PoseToMatrix(object.plane_poses[k], frame);
+                const double local[16] = {1.0, 0.0, 0.0, scale * coef[0], 0.0, 1.0, 0.0, scale * coef[1], 0.0, 0.0, 1.0, scale * coef[2], 0.0, 0.0, 0.0, 1.0};
+                Multiply(frame, local, s.pose);
+                for (int i = 0; i < 12; ++i)
+                    if (!std::isfinite(s.pose[i])) throw std::invalid_argument("Collision object '" + object.id + "' has a plane pose that is not finite");
+                shapes.push_back(s);
+            }
+            for (size_t k = 0; k < object.meshes.size(); ++k) {
+                const shape_msgs::Mesh& mesh = object.meshes[k];
+                sdfgpu_mesh m = sdfgpu_mesh();
+                m.object_id = (uint32_t)(o + 1);
+                m.first_triangle = (int64_t)(scene.triangles.size() / 3);
+                m.n_triangles = (int64_t)mesh.triangles.size();
+                m.first_vertex = (int64_t)(scene.vertices.size() / 3);
+                m.n_vertices = (int64_t)mesh.vertices.size();
+                PoseToMatrix(object.mesh_poses[k], m.pose);
+                for (int i = 0; i < 12; ++i)
+                    if (!std::isfinite(m.pose[i])) throw std::invalid_argument("Collision object '" + object.id + "' has a mesh pose that is not finite");
+                for (const geometry_msgs::Point& v : mesh.vertices) {
+                    if (!(std::isfinite(v.x) && std::isfinite(v.y) && std::isfinite(v.z)))
+                        throw std::invalid_argument("Collision object '" + object.id + "' has a mesh with a vertex that is not finite");
+                    scene.vertices.push_back(v.x); scene.vertices.push_back(v.y); scene.vertices.push_back(v.z);
+                }
+                for (const shape_msgs::MeshTriangle& t : mesh.triangles)
+                    for (int i = 0; i < 3; ++i) {
+                        if ((size_t)t.vertex_indices[i] >= mesh.vertices.size())
+                            throw std::invalid_argument("Collision object '" + object.id + "' has a mesh with a vertex index out of range");
+                        scene.triangles.push_back(t.vertex_indices[i]);
+                    }
+                scene.meshes.push_back(m);
+                if ((int64_t)scene.meshes.size() > (int64_t)SDFGPU_MAX_MESHES)
+                    throw std::invalid_argument("The planning scene has more than " + std::to_string(SDFGPU_MAX_MESHES) + " meshes, the rasteriser takes no more");
+                if ((int64_t)(scene.triangles.size() / 3) > (int64_t)SDFGPU_MAX_TRIANGLES)
+                    throw std::invalid_argument("The planning scene has more than " + std::to_string(SDFGPU_MAX_TRIANGLES) + " triangles, the rasteriser takes no more");
+            }
         }
         const octomap_msgs::OctomapBoxesWithPose& octomap = planning_scene_.world.octomap;
         if (octomap.octomap.centers.size() != octomap.octomap.sizes.size()) throw std::invalid_argument("The octomap has a different number of centers and sizes");
@@ -139,7 +204,37 @@ protected:
         }
         if ((int64_t)shapes.size() > (int64_t)SDFGPU_MAX_SHAPES)
             throw std::invalid_argument("The planning scene has " + std::to_string(shapes.size()) + " shapes, the rasteriser takes " + std::to_string(SDFGPU_MAX_SHAPES));
-        return shapes;
+        return scene;
+    }
+
+    // scene -> device, rasterised on the null stream of the context into whichever of the three outputs is given: the shape list
+    // first, then the meshes accumulated onto the same outputs (a scene without meshes enqueues the shape rasteriser alone).  Nothing
+    // is waited for; the scratch is freed when this returns (hipFree waits for the device, so the work enqueued here has finished by
+    // then).  The caller holds the context's mutex.
+    void RasterizeOnDevice(sdfgpu_handle h, const SceneGeometry& scene, const int64_t nx, const int64_t ny, const int64_t nz, uint32_t* d_bits, uint8_t* d_mask,
+                           uint32_t* d_ids) const {
+        double origin[16];
+        Origin16(origin);
+        const std::vector<sdfgpu_shape>& shapes = scene.shapes;
+        Scratch d_shapes(h, shapes.size() * sizeof(sdfgpu_shape));
+        if (!shapes.empty())
+            sdf_generation::ThrowOnStatus(h, sdfgpu_copy_from_host(h, d_shapes.p, shapes.data(), shapes.size() * sizeof(sdfgpu_shape), nullptr));
+        sdf_generation::ThrowOnStatus(h, sdfgpu_rasterize_shapes_device(h, shapes.empty() ? nullptr : static_cast<const sdfgpu_shape*>(d_shapes.p),
+                                                                        (int64_t)shapes.size(), origin, resolution_, nx, ny, nz, d_bits, d_mask, d_ids, nullptr,
+                                                                        nullptr));
+        if (scene.meshes.empty()) return;
+        Scratch d_meshes(h, scene.meshes.size() * sizeof(sdfgpu_mesh));
+        Scratch d_vertices(h, scene.vertices.size() * sizeof(double));
+        Scratch d_triangles(h, scene.triangles.size() * sizeof(uint32_t));
+        sdf_generation::ThrowOnStatus(h, sdfgpu_copy_from_host(h, d_meshes.p, scene.meshes.data(), scene.meshes.size() * sizeof(sdfgpu_mesh), nullptr));
+        if (!scene.vertices.empty())
+            sdf_generation::ThrowOnStatus(h, sdfgpu_copy_from_host(h, d_vertices.p, scene.vertices.data(), scene.vertices.size() * sizeof(double), nullptr));
+        if (!scene.triangles.empty())
+            sdf_generation::ThrowOnStatus(h, sdfgpu_copy_from_host(h, d_triangles.p, scene.triangles.data(), scene.triangles.size() * sizeof(uint32_t), nullptr));
+        sdf_generation::ThrowOnStatus(h, sdfgpu_rasterize_meshes_device(h, static_cast<const sdfgpu_mesh*>(d_meshes.p), (int64_t)scene.meshes.size(),
+                                                                        static_cast<const double*>(d_vertices.p), (int64_t)(scene.vertices.size() / 3),
+                                                                        static_cast<const uint32_t*>(d_triangles.p), (int64_t)(scene.triangles.size() / 3), origin,
+                                                                        resolution_, nx, ny, nz, d_bits, d_mask, d_ids, 1, nullptr, nullptr));
     }
 
     // the reference's UpdateSDF / UpdateCollisionMap preamble: the exceptions, and the scene the mode asks for
@@ -159,25 +254,18 @@ protected:
         has_planning_scene_ = true;
     }
 
-    // shapes -> device, rasterised to the bit field, the SDF built from it in place (virtual border off, as in the reference): all on
-    // the null stream of the context, nothing waited for.  The caller holds the context's mutex.
-    void BuildOnDevice(sdfgpu_handle h, const std::vector<sdfgpu_shape>& shapes, const VoxelGrid::VoxelGrid<uint8_t>& geometry, float* d_sdf) const {
+    // scene -> the bit field (shapes, then meshes onto the same bits), the SDF built from it in place (virtual border off, as in the
+    // reference): all on the null stream of the context, nothing waited for.  The caller holds the context's mutex.
+    void BuildOnDevice(sdfgpu_handle h, const SceneGeometry& scene, const VoxelGrid::VoxelGrid<uint8_t>& geometry, float* d_sdf) const {
         const int64_t nx = geometry.GetNumXCells(), ny = geometry.GetNumYCells(), nz = geometry.GetNumZCells();
-        double origin[16];
-        Origin16(origin);
-        Scratch d_shapes(h, shapes.size() * sizeof(sdfgpu_shape));
         Scratch d_bits(h, (size_t)((nx * ny * nz + 31) / 32) * 4);
-        if (!shapes.empty())
-            sdf_generation::ThrowOnStatus(h, sdfgpu_copy_from_host(h, d_shapes.p, shapes.data(), shapes.size() * sizeof(sdfgpu_shape), nullptr));
-        sdf_generation::ThrowOnStatus(h, sdfgpu_rasterize_shapes_device(h, shapes.empty() ? nullptr : static_cast<const sdfgpu_shape*>(d_shapes.p),
-                                                                        (int64_t)shapes.size(), origin, resolution_, nx, ny, nz,
-                                                                        static_cast<uint32_t*>(d_bits.p), nullptr, nullptr, nullptr, nullptr));
+        RasterizeOnDevice(h, scene, nx, ny, nz, static_cast<uint32_t*>(d_bits.p), nullptr, nullptr);
         sdf_generation::ThrowOnStatus(h, sdfgpu_build_bits_device(h, static_cast<const uint32_t*>(d_bits.p), nx, ny, nz, resolution_, 0, d_sdf, nullptr));
         // (the scratch is freed when this returns: hipFree waits for the device, so the work enqueued above has finished by then)
     }
 
     SignedDistanceField UpdateSDFFromPlanningScene() {
-        const std::vector<sdfgpu_shape> shapes = SceneShapes();                 // (refusals come before the GPU is touched)
+        const SceneGeometry shapes = SceneShapes();                             // (refusals come before the GPU is touched)
         const VoxelGrid::VoxelGrid<uint8_t> temp_grid(origin_transform_, resolution_, x_size_, y_size_, z_size_, 0);
         const int64_t nx = temp_grid.GetNumXCells(), ny = temp_grid.GetNumYCells(), nz = temp_grid.GetNumZCells();
         SignedDistanceField new_sdf(SignedDistanceField::ForBuild{}, origin_transform_, frame_, resolution_, nx, ny, nz, OOB_value_);
@@ -196,16 +284,23 @@ protected:
 
     VoxelGrid::VoxelGrid<uint8_t> UpdateCollisionMapFromPlanningScene() {
         VoxelGrid::VoxelGrid<uint8_t> collision_field(origin_transform_, resolution_, x_size_, y_size_, z_size_, 0);
-        const std::vector<sdfgpu_shape> shapes = SceneShapes();
+        const SceneGeometry scene = SceneShapes();
+        const std::vector<sdfgpu_shape>& shapes = scene.shapes;
+        const int64_t nx = collision_field.GetNumXCells(), ny = collision_field.GetNumYCells(), nz = collision_field.GetNumZCells();
         double origin[16];
         Origin16(origin);
         {
             const std::shared_ptr<sdf_generation::SharedGpuContext> ctx = sdf_generation::GpuContext::Shared();
             const std::lock_guard<std::mutex> lock(ctx->mutex);
-            sdf_generation::ThrowOnStatus(ctx->handle, sdfgpu_rasterize_shapes(ctx->handle, shapes.empty() ? nullptr : shapes.data(), (int64_t)shapes.size(), origin,
-                                                                               resolution_, collision_field.GetNumXCells(), collision_field.GetNumYCells(),
-                                                                               collision_field.GetNumZCells(), nullptr,
-                                                                               collision_field.GetMutableRawData().data(), nullptr));
+            sdfgpu_handle h = ctx->handle;
+            if (scene.meshes.empty()) {
+                sdf_generation::ThrowOnStatus(h, sdfgpu_rasterize_shapes(h, shapes.empty() ? nullptr : shapes.data(), (int64_t)shapes.size(), origin, resolution_, nx,
+                                                                         ny, nz, nullptr, collision_field.GetMutableRawData().data(), nullptr));
+            } else {                                                            // shapes, then meshes onto the same mask; one download
+                Scratch d_mask(h, (size_t)(nx * ny * nz));
+                RasterizeOnDevice(h, scene, nx, ny, nz, nullptr, static_cast<uint8_t*>(d_mask.p), nullptr);
+                sdf_generation::ThrowOnStatus(h, sdfgpu_copy_to_host(h, collision_field.GetMutableRawData().data(), d_mask.p, (size_t)(nx * ny * nz), nullptr));
+            }
         }
         cached_collmap_ = collision_field;
         has_cached_collmap_ = true;
@@ -263,7 +358,7 @@ public:
     // cached SDF is not touched.
     DeviceSignedDistanceField UpdateSDFDevice(const uint8_t update_mode) {
         PrepareScene(update_mode);
-        const std::vector<sdfgpu_shape> shapes = SceneShapes();
+        const SceneGeometry shapes = SceneShapes();
         const VoxelGrid::VoxelGrid<uint8_t> temp_grid(origin_transform_, resolution_, x_size_, y_size_, z_size_, 0);
         DeviceSignedDistanceField new_sdf(origin_transform_, frame_, resolution_, temp_grid.GetNumXCells(), temp_grid.GetNumYCells(),
                                           temp_grid.GetNumZCells(), OOB_value_);
@@ -277,20 +372,29 @@ public:
 
     // The collision map with object ids: a filled cell (occupancy 1) carries the id of the first shape in scene order that its probe
     // meets -- the 1-based index of the collision object, or the number of collision objects + 1 for the octomap; empty cells carry
-    // occupancy 0 and id 0.
+    // occupancy 0 and id 0.  With meshes it is the smallest id among the shapes and meshes the probe meets, which is the same thing:
+    // ids ascend with scene order.
     TaggedObjectCollisionMapGrid UpdateTaggedCollisionMap(const uint8_t update_mode) {
         PrepareScene(update_mode);
         TaggedObjectCollisionMapGrid map(origin_transform_, frame_, resolution_, x_size_, y_size_, z_size_, TAGGED_OBJECT_COLLISION_CELL());
-        const std::vector<sdfgpu_shape> shapes = SceneShapes();
-        std::vector<uint32_t> ids((size_t)(map.GetNumXCells() * map.GetNumYCells() * map.GetNumZCells()));
+        const SceneGeometry scene = SceneShapes();
+        const std::vector<sdfgpu_shape>& shapes = scene.shapes;
+        const int64_t nx = map.GetNumXCells(), ny = map.GetNumYCells(), nz = map.GetNumZCells();
+        std::vector<uint32_t> ids((size_t)(nx * ny * nz));
         double origin[16];
         Origin16(origin);
         {
             const std::shared_ptr<sdf_generation::SharedGpuContext> ctx = sdf_generation::GpuContext::Shared();
             const std::lock_guard<std::mutex> lock(ctx->mutex);
-            sdf_generation::ThrowOnStatus(ctx->handle, sdfgpu_rasterize_shapes(ctx->handle, shapes.empty() ? nullptr : shapes.data(), (int64_t)shapes.size(), origin,
-                                                                               resolution_, map.GetNumXCells(), map.GetNumYCells(), map.GetNumZCells(), nullptr,
-                                                                               nullptr, ids.data()));
+            sdfgpu_handle h = ctx->handle;
+            if (scene.meshes.empty()) {
+                sdf_generation::ThrowOnStatus(h, sdfgpu_rasterize_shapes(h, shapes.empty() ? nullptr : shapes.data(), (int64_t)shapes.size(), origin, resolution_, nx,
+                                                                         ny, nz, nullptr, nullptr, ids.data()));
+            } else {
+                Scratch d_ids(h, ids.size() * sizeof(uint32_t));
+                RasterizeOnDevice(h, scene, nx, ny, nz, nullptr, nullptr, static_cast<uint32_t*>(d_ids.p));
+                sdf_generation::ThrowOnStatus(h, sdfgpu_copy_to_host(h, ids.data(), d_ids.p, ids.size() * sizeof(uint32_t), nullptr));
+            }
         }
         std::vector<TAGGED_OBJECT_COLLISION_CELL>& cells = map.GetMutableRawData();
         for (size_t i = 0; i < ids.size(); ++i)

@@ -757,7 +757,8 @@ int sdfgpu_debug_resample_times(sdfgpu_handle h, double* out_winner_ms, double* 
  *                              is clipped to |z| <= height / 2 (two Sutherland-Hodgman passes) and the voxel is filled iff the
  *                              least squared distance from the axis to the xy projection of a clipped face's edge is <= radius^2,
  *                              or the axis segment passes through the cube (slab test in the world's axes).
- * Every other type (a cone (4), a mesh, a plane) is refused.  Arithmetic: double precision, the centre's rows as
+ *   SDFGPU_SHAPE_PLANE (5)     see "Planes and triangle meshes" below.
+ * Every other type (a cone (4) among them) is refused; meshes have an entry point of their own below.  Arithmetic: double precision, the centre's rows as
  * ((m0 v0 + m1 v1) + m2 v2) + m3 as in Resample, separate products and sums throughout (no FMA); tests/scene_raster_restated.py
  * states every operation.  A shape reaches this test only in regions its world bounds, inflated by `voxel_size` (more than the
  * probe's circum-radius), meet; the slack is far above the rounding, so the culling changes no voxel.
@@ -796,6 +797,68 @@ int sdfgpu_rasterize_shapes_device(sdfgpu_handle h, const sdfgpu_shape* d_shapes
                                    int64_t* out_bad_shape, void* stream);
 int sdfgpu_rasterize_shapes(sdfgpu_handle h, const sdfgpu_shape* shapes, int64_t n_shapes, const double origin[16], double voxel_size,
                             int64_t nx, int64_t ny, int64_t nz, uint32_t* bits, uint8_t* mask, uint32_t* object_ids);
+
+/* ---------------------------------------------------------------------------
+ * Planes and triangle meshes of a planning scene (shape_msgs::Plane, shape_msgs::Mesh).  DESIGN.md section 27.  The probe, its
+ * centre c, h = voxel_size / 2, the outputs' layout and the arithmetic (doubles, separate products and sums, no FMA) are those of
+ * the shape rasteriser above; tests/mesh_raster_restated.py states every operation.  Both readings below -- a mesh is its SURFACE
+ * (a triangle soup, as MoveIt hands it to FCL), a plane is infinite and has no thickness -- and that touching counts are UNVERIFIED
+ * against FCL and MoveIt, which are not available to this project.
+ *
+ *   SDFGPU_SHAPE_PLANE (5), a member of the shape list above: the plane through the shape frame's origin T with normal
+ *       n = dims[0 .. 2] in the shape frame (any sign; refused when a component is not finite or all three are zero).
+ *       N_a = (r_a0 n_0 + r_a1 n_1) + r_a2 n_2, s = (N_0 (c_0 - T_0) + N_1 (c_1 - T_1)) + N_2 (c_2 - T_2); the voxel is filled iff
+ *       |s| <= h ((|N_0| + |N_1|) + |N_2|).  Its world bounds are unbounded: it is a candidate in every region.
+ *
+ *   MESHES.  struct sdfgpu_mesh names a run of triangles and a run of vertices of two shared arrays: vertices are double[3] in the
+ *       mesh frame, triangles uint32[3] indices RELATIVE to the mesh's first_vertex; `pose` is row-major, mesh frame to world,
+ *       12 entries read.  A voxel is filled iff the closed probe cube meets at least one closed triangle; a probe wholly inside a
+ *       closed mesh is NOT filled.  Per triangle: W_i = pose * v_i (rows as ((m0 v0 + m1 v1) + m2 v2) + m3), edges f_0 = W_1 - W_0,
+ *       f_1 = W_2 - W_1, f_2 = W_0 - W_2, n = f_0 x f_1, u_i = W_i - c.  Thirteen axes in this order: e_x, e_y, e_z; n; e_a x f_j
+ *       for a = x, y, z and j = 0, 1, 2.  For an axis a: p_i = a . u_i, r = h (|a_x| + |a_y| + |a_z|); it separates iff
+ *       min p > r or max p < -r (both strict), so an axis that degenerates to 0 never separates and a triangle of no area (a
+ *       segment, a point) is still decided exactly.  Filled iff no axis separates.  A triangle reaches this test only in voxels of
+ *       an index box around it inflated by far more than the probe's circum-radius: culling, which changes no voxel.
+ *       The sum of the meshes' n_triangles may not exceed the triangle array's n_triangles (runs may be shared or given in any
+ *       order within that).
+ *   OUTPUTS as above (bits, mask, object_ids; each optional, at least one).  accumulate == 0: cleared, then written.
+ *       accumulate == 1: bits and mask are OR-ed onto what is there (sdfgpu_rasterize_shapes' output, say).  An id is the SMALLEST
+ *       object_id among the meshes that meet the probe and, under accumulate, the non-zero id already there; 0 where there is none.
+ *       The rule is commutative: the result depends neither on scheduling nor on the order of triangles or meshes.  It DIFFERS
+ *       from the shape list's "first in list order"; the two coincide when ids ascend with list order (SDF_Builder's do).
+ *   Refused with a message, nothing written (under accumulate: nothing changed): a null or misaligned pointer (meshes and vertices
+ *       off 8 bytes; triangles, bits, ids off 4), a count that is negative or above SDFGPU_MAX_MESHES / SDFGPU_MAX_TRIANGLES (or
+ *       n_vertices above 2^32), no output, the grid and voxel_size refusals of the shape rasteriser, a value of accumulate other
+ *       than 0 and 1.  Per mesh: a triangle or vertex run outside the arrays, triangle counts that sum past n_triangles, a pose
+ *       entry or a referenced vertex that is not finite, a vertex index >= the mesh's n_vertices, object_id 0 or 0xFFFFFFFF when
+ *       ids are asked for.
+ *
+ *   sdfgpu_rasterize_meshes: host arrays and outputs on the null stream, synchronous; always clears; everything is checked on the
+ *       host first and the message names the first refused mesh.
+ *   sdfgpu_rasterize_meshes_device: device pointers; memsets and five kernels (k_mr_meshes, k_mr_setup, k_mr_scan_blocks,
+ *       k_mr_scan_top, k_mr_scatter) on `stream`, no host synchronisation.  The meshes are checked on the device: the lowest refused
+ *       mesh index goes to a status word that the scatter kernel reads before it writes anything, so a refused call leaves cleared
+ *       outputs (accumulate == 0) or untouched ones (accumulate == 1).  out_bad_mesh behaves as out_bad_shape does.  The scratch
+ *       (a status block, 8 bytes per mesh, 84 bytes per triangle and 8 per 1024 triangles; sized from n_meshes and n_triangles
+ *       alone, 1.4 GiB at the limit) belongs to the handle; a call on another stream is ordered behind the last one on the device.
+ * ------------------------------------------------------------------------- */
+#define SDFGPU_SHAPE_PLANE 5
+#define SDFGPU_MAX_MESHES 65536
+#define SDFGPU_MAX_TRIANGLES 16777216
+typedef struct sdfgpu_mesh {
+    uint32_t object_id;
+    uint32_t reserved;
+    int64_t first_triangle, n_triangles;
+    int64_t first_vertex, n_vertices;
+    double pose[16];
+} sdfgpu_mesh;
+int sdfgpu_rasterize_meshes_device(sdfgpu_handle h, const sdfgpu_mesh* d_meshes, int64_t n_meshes, const double* d_vertices, int64_t n_vertices,
+                                   const uint32_t* d_triangles, int64_t n_triangles, const double origin[16], double voxel_size, int64_t nx,
+                                   int64_t ny, int64_t nz, uint32_t* d_bits, uint8_t* d_mask, uint32_t* d_object_ids, int accumulate,
+                                   int64_t* out_bad_mesh, void* stream);
+int sdfgpu_rasterize_meshes(sdfgpu_handle h, const sdfgpu_mesh* meshes, int64_t n_meshes, const double* vertices, int64_t n_vertices,
+                            const uint32_t* triangles, int64_t n_triangles, const double origin[16], double voxel_size, int64_t nx, int64_t ny,
+                            int64_t nz, uint32_t* bits, uint8_t* mask, uint32_t* object_ids);
 
 /* ---------------------------------------------------------------------------
  * Display export: the device side of the reference's ExportForDisplay family (CollisionMapGrid, TaggedObjectCollisionMapGrid,

@@ -41,6 +41,7 @@ EXPORTS = [
     "sdfgpu_display_expand_device", "sdfgpu_display_sdf_colors_device", "sdfgpu_display_sdf_colors",
     "sdfgpu_display_contour_reach", "sdfgpu_display_select_contour_device", "sdfgpu_display_select_contour",
     "sdfgpu_rasterize_shapes_device", "sdfgpu_rasterize_shapes",
+    "sdfgpu_rasterize_meshes_device", "sdfgpu_rasterize_meshes",
 ]
 
 # include/sdfgpu.h "Projection": modes and per-point statuses
@@ -58,8 +59,13 @@ DISPLAY_FILLED, DISPLAY_EMPTY, DISPLAY_UNKNOWN = 1, 2, 4
 
 # include/sdfgpu.h "Shape rasteriser": the types, the limit and struct sdfgpu_shape as a numpy record (160 bytes)
 SHAPE_BOX, SHAPE_SPHERE, SHAPE_CYLINDER = 1, 2, 3
+SHAPE_PLANE = 5
 MAX_SHAPES = 65536
+MAX_MESHES = 65536
+MAX_TRIANGLES = 1 << 24
 SHAPE_DTYPE = np.dtype([("type", np.uint32), ("object_id", np.uint32), ("dims", np.float64, (3,)), ("pose", np.float64, (16,))], align=True)
+MESH_DTYPE = np.dtype([("object_id", np.uint32), ("reserved", np.uint32), ("first_triangle", np.int64), ("n_triangles", np.int64),
+                       ("first_vertex", np.int64), ("n_vertices", np.int64), ("pose", np.float64, (16,))], align=True)
 
 
 class SdfGpuError(RuntimeError):
@@ -171,6 +177,8 @@ def load_library():
     L.sdfgpu_display_select_contour.argtypes = [vp, vp, sz, sz, sz, i64, i64, i64, ci, ci, vp, i64, ci, ci, vp, vp, i64, vp, vp, vp, i64, vp]
     L.sdfgpu_rasterize_shapes_device.argtypes = [vp, vp, i64, vp, dbl, i64, i64, i64, vp, vp, vp, vp, vp]
     L.sdfgpu_rasterize_shapes.argtypes = [vp, vp, i64, vp, dbl, i64, i64, i64, vp, vp, vp]
+    L.sdfgpu_rasterize_meshes_device.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, dbl, i64, i64, i64, vp, vp, vp, ctypes.c_int, vp, vp]
+    L.sdfgpu_rasterize_meshes.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, dbl, i64, i64, i64, vp, vp, vp]
     L.sdfgpu_build_batch_device.argtypes = [vp, vp, i64, i64, i64, i64, dbl, vp, ci, vp, vp]
     L.sdfgpu_get_extrema_batch.argtypes = [vp, i64, vp, vp]
     L.sdfgpu_build_batch.argtypes = [vp, vp, i64, i64, i64, i64, dbl, vp, ci, vp, vp, vp]
@@ -285,6 +293,27 @@ def make_shapes(items):
         m[:3] = np.asarray(pose, np.float64).reshape(-1, 4)[:3]
         rec["pose"] = m.reshape(-1)
     return out
+
+
+def make_meshes(items):
+    """[(object_id, vertices [n, 3], triangles [m, 3] of indices into those vertices, pose 4 x 4 or 3 x 4)] ->
+    (MESH_DTYPE records, vertices float64 [sum n, 3], triangles uint32 [sum m, 3]): the arrays of sdfgpu_rasterize_meshes, every
+    mesh's runs one behind the other"""
+    out = np.zeros(len(items), MESH_DTYPE)
+    vs, ts = [np.zeros((0, 3), np.float64)], [np.zeros((0, 3), np.uint32)]
+    nv = nt = 0
+    for rec, (object_id, vertices, triangles, pose) in zip(out, items):
+        v = np.asarray(vertices, np.float64).reshape(-1, 3)
+        t = np.asarray(triangles, np.uint32).reshape(-1, 3)
+        rec["object_id"] = object_id
+        rec["first_triangle"], rec["n_triangles"], rec["first_vertex"], rec["n_vertices"] = nt, len(t), nv, len(v)
+        m = np.eye(4)
+        m[:3] = np.asarray(pose, np.float64).reshape(-1, 4)[:3]
+        rec["pose"] = m.reshape(-1)
+        vs.append(v)
+        ts.append(t)
+        nv, nt = nv + len(v), nt + len(t)
+    return out, np.ascontiguousarray(np.concatenate(vs)), np.ascontiguousarray(np.concatenate(ts))
 
 
 def project_step_limit(shape, stepsize_multiplier=1.0 / 8.0, max_steps=0):
@@ -939,6 +968,41 @@ class SdfGpu:
         self._check(self._lib.sdfgpu_rasterize_shapes_device(self._h, d_shapes or None, int(n_shapes), _doubles(origin, 16), float(resolution),
                                                              nx, ny, nz, d_bits or None, d_mask or None, d_object_ids or None,
                                                              ctypes.byref(bad) if check else None, stream or None))
+        return int(bad.value) if check else None
+
+    # ---- mesh rasteriser (include/sdfgpu.h "Planes and triangle meshes") ----
+    def rasterize_meshes(self, meshes, vertices, triangles, origin, resolution, shape, bits=True, mask=False, object_ids=False):
+        """meshes: MESH_DTYPE records, vertices: float64 [n, 3], triangles: uint32 [m, 3] (see make_meshes).  Returns a dict of the
+        outputs asked for, as rasterize_shapes does."""
+        nx, ny, nz = (int(v) for v in shape)
+        ms = np.ascontiguousarray(meshes, dtype=MESH_DTYPE).reshape(-1)
+        vs = np.ascontiguousarray(vertices, dtype=np.float64).reshape(-1, 3)
+        ts = np.ascontiguousarray(triangles, dtype=np.uint32).reshape(-1, 3)
+        n = nx * ny * nz
+        out = {}
+        if bits:
+            out["bits"] = np.empty((max(n, 0) + 31) // 32, np.uint32)
+        if mask:
+            out["mask"] = np.empty((nx, ny, nz), np.uint8)
+        if object_ids:
+            out["object_ids"] = np.empty((nx, ny, nz), np.uint32)
+        ptr = [out[k].ctypes.data if k in out else None for k in ("bits", "mask", "object_ids")]
+        self._check(self._lib.sdfgpu_rasterize_meshes(self._h, ms.ctypes.data if ms.size else None, int(ms.size),
+                                                      vs.ctypes.data if vs.size else None, len(vs), ts.ctypes.data if ts.size else None, len(ts),
+                                                      _doubles(origin, 16), float(resolution), nx, ny, nz, *ptr))
+        return out
+
+    def rasterize_meshes_device(self, d_meshes, n_meshes, d_vertices, n_vertices, d_triangles, n_triangles, origin, resolution, shape,
+                                d_bits=0, d_mask=0, d_object_ids=0, accumulate=False, check=False, stream=0):
+        """Device form (device addresses as ints), enqueued on `stream`.  accumulate: OR onto the bits and the mask that are there,
+        ids to the smallest non-zero.  check: synchronise the stream and return the index of the first refused mesh (-1: none; a
+        refused mesh also raises); without it the call does not wait and returns None."""
+        nx, ny, nz = (int(v) for v in shape)
+        bad = ctypes.c_int64(-2)
+        self._check(self._lib.sdfgpu_rasterize_meshes_device(self._h, d_meshes or None, int(n_meshes), d_vertices or None, int(n_vertices),
+                                                             d_triangles or None, int(n_triangles), _doubles(origin, 16), float(resolution),
+                                                             nx, ny, nz, d_bits or None, d_mask or None, d_object_ids or None,
+                                                             int(accumulate), ctypes.byref(bad) if check else None, stream or None))
         return int(bad.value) if check else None
 
     def debug_resample_times(self):

@@ -699,8 +699,43 @@ PYBIND11_MODULE(pysdf_tools, m) {
         .def_property_readonly_static("SPHERE", [](py::object) { return (int)shape_msgs::SolidPrimitive::SPHERE; })
         .def_property_readonly_static("CYLINDER", [](py::object) { return (int)shape_msgs::SolidPrimitive::CYLINDER; })
         .def_property_readonly_static("CONE", [](py::object) { return (int)shape_msgs::SolidPrimitive::CONE; });
-    py::class_<shape_msgs::Mesh>(m, "Mesh").def(py::init<>());
-    py::class_<shape_msgs::Plane>(m, "Plane").def(py::init<>());
+    py::class_<shape_msgs::MeshTriangle>(m, "MeshTriangle")
+        .def(py::init([](const std::array<uint32_t, 3>& vertex_indices) {
+            shape_msgs::MeshTriangle t;
+            for (int i = 0; i < 3; ++i) t.vertex_indices[i] = vertex_indices[i];
+            return t;
+        }), py::arg("vertex_indices") = std::array<uint32_t, 3>{0, 0, 0})
+        .def_property("vertex_indices", [](const shape_msgs::MeshTriangle& t) { return std::array<uint32_t, 3>{t.vertex_indices[0], t.vertex_indices[1], t.vertex_indices[2]}; },
+                      [](shape_msgs::MeshTriangle& t, const std::array<uint32_t, 3>& v) { for (int i = 0; i < 3; ++i) t.vertex_indices[i] = v[i]; });
+    py::class_<shape_msgs::Mesh>(m, "Mesh")
+        .def(py::init<>())
+        .def_readwrite("triangles", &shape_msgs::Mesh::triangles)
+        .def_property_readonly("vertices", [](const shape_msgs::Mesh& mesh) {
+            py::array_t<double> out({(py::ssize_t)mesh.vertices.size(), (py::ssize_t)3});
+            if (!mesh.vertices.empty()) std::memcpy(out.mutable_data(), mesh.vertices.data(), mesh.vertices.size() * sizeof(geometry_msgs::Point));
+            return out;
+        }, "a copy of the vertices as a numpy array [n, 3]; set them with set_vertices")
+        .def("set_vertices", [](shape_msgs::Mesh& mesh, const py::array_t<double, py::array::c_style | py::array::forcecast>& vertices) {
+            if (vertices.ndim() != 2 || vertices.shape(1) != 3) throw std::invalid_argument("vertices must be [n, 3]");
+            mesh.vertices.resize((size_t)vertices.shape(0));
+            for (size_t i = 0; i < mesh.vertices.size(); ++i) {
+                mesh.vertices[i].x = vertices.data()[3 * i]; mesh.vertices[i].y = vertices.data()[3 * i + 1]; mesh.vertices[i].z = vertices.data()[3 * i + 2];
+            }
+        }, py::arg("vertices"), "vertices as a numpy array [n, 3] in the mesh frame")
+        .def("set_triangles", [](shape_msgs::Mesh& mesh, const py::array_t<uint32_t, py::array::c_style | py::array::forcecast>& triangles) {
+            if (triangles.ndim() != 2 || triangles.shape(1) != 3) throw std::invalid_argument("triangles must be [n, 3]");
+            mesh.triangles.resize((size_t)triangles.shape(0));
+            for (size_t i = 0; i < mesh.triangles.size(); ++i)
+                for (int k = 0; k < 3; ++k) mesh.triangles[i].vertex_indices[k] = triangles.data()[3 * i + k];
+        }, py::arg("triangles"), "triangles as a numpy array [n, 3] of vertex indices");
+    py::class_<shape_msgs::Plane>(m, "Plane")
+        .def(py::init([](const std::array<double, 4>& coef) {
+            shape_msgs::Plane p;
+            for (int i = 0; i < 4; ++i) p.coef[i] = coef[i];
+            return p;
+        }), py::arg("coef") = std::array<double, 4>{0.0, 0.0, 0.0, 0.0})
+        .def_property("coef", [](const shape_msgs::Plane& p) { return std::array<double, 4>{p.coef[0], p.coef[1], p.coef[2], p.coef[3]}; },
+                      [](shape_msgs::Plane& p, const std::array<double, 4>& c) { for (int i = 0; i < 4; ++i) p.coef[i] = c[i]; });
     py::class_<moveit_msgs::CollisionObject>(m, "CollisionObject")
         .def(py::init<>())
         .def_readwrite("id", &moveit_msgs::CollisionObject::id)

@@ -38,6 +38,10 @@ __global__ __launch_bounds__(kScThreads) void k_sc_prepare(const SceneArgs a) {
         for (int k = 0; k < 3; ++k) { b[k] = 1.0; b[3 + k] = -1.0; }
         return;
     }
+    if (s.type == SDFGPU_SHAPE_PLANE) {                                      // unbounded: a candidate everywhere
+        for (int k = 0; k < 3; ++k) { b[k] = -1.0e308; b[3 + k] = 1.0e308; }
+        return;
+    }
     double e[3];
     sc_half_extents(s, e);
     for (int k = 0; k < 3; ++k) {
@@ -292,7 +296,7 @@ int sdfgpu_rasterize_shapes(sdfgpu_handle h, const sdfgpu_shape* shapes, int64_t
         for (int64_t i = 0; i < n_shapes; ++i)
             if (!sc_shape_valid(shapes[i]) || (object_ids && shapes[i].object_id == 0))
                 return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "rasterize_shapes: shape %lld is refused (type %u: a box, sphere or cylinder with finite "
-                            "dims >= 0, a finite pose and, for object ids, an id >= 1 is taken)", (long long)i, shapes[i].type);
+                            "dims >= 0 or a plane with a finite non-zero normal, a finite pose and, for object ids, an id >= 1 is taken)", (long long)i, shapes[i].type);
         HIP_TRY(h, hipSetDevice(h->device));
         // the null stream throughout: the shapes through the cell staging, the outputs through the field staging
         const size_t shape_bytes = (size_t)n_shapes * sizeof(sdfgpu_shape);

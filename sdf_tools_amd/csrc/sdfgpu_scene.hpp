@@ -68,8 +68,15 @@ SC_HD void sc_centre(const double* o, double res, int64_t x, int64_t y, int64_t 
     for (int r = 0; r < 3; ++r) c[r] = o[4 * r] * g0 + o[4 * r + 1] * g1 + o[4 * r + 2] * g2 + o[4 * r + 3];
 }
 
-// type known, dims finite and >= 0 (those the type uses), the 12 used pose entries finite
+// type known, dims finite and >= 0 (those the type uses), the 12 used pose entries finite; a plane's dims are its normal: finite,
+// of either sign, not all zero
 SC_HD bool sc_shape_valid(const sdfgpu_shape& s) {
+    if (s.type == SDFGPU_SHAPE_PLANE) {
+        for (int i = 0; i < 3; ++i) if (!sc_finite(s.dims[i])) return false;
+        if (s.dims[0] == 0.0 && s.dims[1] == 0.0 && s.dims[2] == 0.0) return false;
+        for (int i = 0; i < 12; ++i) if (!sc_finite(s.pose[i])) return false;
+        return true;
+    }
     const int nd = s.type == SDFGPU_SHAPE_BOX ? 3 : s.type == SDFGPU_SHAPE_SPHERE ? 1 : s.type == SDFGPU_SHAPE_CYLINDER ? 2 : -1;
     if (nd < 0) return false;
     for (int i = 0; i < nd; ++i) if (!(sc_finite(s.dims[i]) && s.dims[i] >= 0.0)) return false;
@@ -217,8 +224,20 @@ SC_HD bool sc_cylinder(const sdfgpu_shape& s, const double c[3], double h) {
     return lo <= hi;
 }
 
+// PLANE (through the shape frame's origin, normal dims[0..2] in the shape frame; infinite, no thickness): N = R n, s = N . (c - T),
+// filled iff |s| <= h (|N_0| + |N_1| + |N_2|).  It belongs to the shape list, so it lives here; sdfgpu_mesh.hpp states it beside
+// the triangle's axes.
+SC_HD bool sc_plane(const sdfgpu_shape& s, const double c[3], double h) {
+    const double* p = s.pose;
+    double N[3];
+    for (int a = 0; a < 3; ++a) N[a] = (p[4 * a] * s.dims[0] + p[4 * a + 1] * s.dims[1]) + p[4 * a + 2] * s.dims[2];
+    const double d = (N[0] * (c[0] - p[3]) + N[1] * (c[1] - p[7])) + N[2] * (c[2] - p[11]);
+    return sc_abs(d) <= h * ((sc_abs(N[0]) + sc_abs(N[1])) + sc_abs(N[2]));
+}
+
 // a valid shape against the probe cube of half side h about c
 SC_HD bool sc_hit(const sdfgpu_shape& s, const double c[3], double h) {
+    if (s.type == SDFGPU_SHAPE_PLANE) return sc_plane(s, c, h);
     if (s.type == SDFGPU_SHAPE_SPHERE) return sc_sphere(s, c, h);
     if (s.type == SDFGPU_SHAPE_BOX) return sc_box(s, c, h);
     return sc_cylinder(s, c, h);
