@@ -23,9 +23,12 @@
 // Extensions: UpdateSDFDevice (the field stays in HBM) and UpdateTaggedCollisionMap (object ids: the 1-based index of the collision
 // object, and one more id for the octomap).
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <functional>
+#include <map>
+#include <memory>
 #include <mutex>
 #include <stdexcept>
 #include <string>
@@ -47,6 +50,12 @@ static const uint8_t USE_ONLY_OCTOMAP = 0x01;
 static const uint8_t USE_ONLY_COLLISION_OBJECTS = 0x02;
 static const uint8_t USE_FULL_PLANNING_SCENE = 0x03;
 
+// How a collision object's meshes are filled (an extension; SetMeshFill, SetObjectMeshFill).  SURFACE, the default, is the reading
+// above: a triangle soup.  SOLID also fills the cells whose centres lie inside a closed mesh (even-odd, per mesh: include/sdfgpu.h
+// "Solid meshes"); a mesh that is not closed is refused.
+static const uint8_t MESH_FILL_SURFACE = 0x00;
+static const uint8_t MESH_FILL_SOLID = 0x01;
+
 class SDF_Builder {
 public:
     using PlanningSceneSource = std::function<moveit_msgs::PlanningScene(uint8_t update_mode)>;
@@ -67,6 +76,8 @@ protected:
     VoxelGrid::VoxelGrid<uint8_t> cached_collmap_;
     moveit_msgs::PlanningScene planning_scene_;
     PlanningSceneSource planning_scene_source_;
+    uint8_t mesh_fill_ = MESH_FILL_SURFACE;
+    std::map<std::string, uint8_t> object_mesh_fill_;      // CollisionObject::id -> mode, where it differs from mesh_fill_
 
     // a device allocation of the handle, freed on every way out (the caller holds the context's mutex)
     struct Scratch {
@@ -92,7 +103,10 @@ protected:
     // what the rasterisers take: the shape list, and the meshes with their shared vertex and triangle arrays
     struct SceneGeometry {
         std::vector<sdfgpu_shape> shapes;
-        std::vector<sdfgpu_mesh> meshes;
+        std::vector<sdfgpu_mesh> meshes;               // taken as their surface
+        std::vector<sdfgpu_mesh> solid_meshes;         // filled inside as well; runs of the same two arrays
+        std::vector<size_t> solid_objects;             // the collision object of each solid mesh
+        bool HasMeshes() const { return !meshes.empty() || !solid_meshes.empty(); }
         std::vector<double> vertices;
         std::vector<uint32_t> triangles;
     };
@@ -178,8 +192,14 @@ protected:
                             throw std::invalid_argument("Collision object '" + object.id + "' has a mesh with a vertex index out of range");
                         scene.triangles.push_back(t.vertex_indices[i]);
                     }
-                scene.meshes.push_back(m);
-                if ((int64_t)scene.meshes.size() > (int64_t)SDFGPU_MAX_MESHES)
+                const std::map<std::string, uint8_t>::const_iterator own = object_mesh_fill_.find(object.id);
+                if ((own == object_mesh_fill_.end() ? mesh_fill_ : own->second) == MESH_FILL_SOLID) {
+                    scene.solid_meshes.push_back(m);
+                    scene.solid_objects.push_back(o);
+                } else {
+                    scene.meshes.push_back(m);
+                }
+                if ((int64_t)(scene.meshes.size() + scene.solid_meshes.size()) > (int64_t)SDFGPU_MAX_MESHES)
                     throw std::invalid_argument("The planning scene has more than " + std::to_string(SDFGPU_MAX_MESHES) + " meshes, the rasteriser takes no more");
                 if ((int64_t)(scene.triangles.size() / 3) > (int64_t)SDFGPU_MAX_TRIANGLES)
                     throw std::invalid_argument("The planning scene has more than " + std::to_string(SDFGPU_MAX_TRIANGLES) + " triangles, the rasteriser takes no more");
@@ -204,11 +224,21 @@ protected:
         }
         if ((int64_t)shapes.size() > (int64_t)SDFGPU_MAX_SHAPES)
             throw std::invalid_argument("The planning scene has " + std::to_string(shapes.size()) + " shapes, the rasteriser takes " + std::to_string(SDFGPU_MAX_SHAPES));
+        if (!scene.solid_meshes.empty()) {                 // on the host, no GPU: an even number of triangles on every edge
+            int64_t bad_mesh = -1, bad_triangle = -1;
+            if (sdfgpu_check_closed_meshes(scene.solid_meshes.data(), (int64_t)scene.solid_meshes.size(), scene.vertices.data(),
+                                           (int64_t)(scene.vertices.size() / 3), scene.triangles.data(), (int64_t)(scene.triangles.size() / 3), &bad_mesh,
+                                           &bad_triangle) != SDFGPU_OK)
+                throw std::invalid_argument("Collision object '" + (bad_mesh >= 0 ? objects[scene.solid_objects[(size_t)bad_mesh]].id : std::string("?")) +
+                                            "' has a mesh that is to be filled as a solid but is not closed (an edge of its triangle " +
+                                            std::to_string(bad_triangle) + " is used by an odd number of triangles)");
+        }
         return scene;
     }
 
     // scene -> device, rasterised on the null stream of the context into whichever of the three outputs is given: the shape list
-    // first, then the meshes accumulated onto the same outputs (a scene without meshes enqueues the shape rasteriser alone).  Nothing
+    // first, then the surface meshes, then the solid meshes (at most SDFGPU_MAX_SOLID_MESHES a call), each accumulated onto the same
+    // outputs (a scene without meshes enqueues the shape rasteriser alone, one without solid meshes what it always did).  Nothing
     // is waited for; the scratch is freed when this returns (hipFree waits for the device, so the work enqueued here has finished by
     // then).  The caller holds the context's mutex.
     void RasterizeOnDevice(sdfgpu_handle h, const SceneGeometry& scene, const int64_t nx, const int64_t ny, const int64_t nz, uint32_t* d_bits, uint8_t* d_mask,
@@ -222,19 +252,34 @@ protected:
         sdf_generation::ThrowOnStatus(h, sdfgpu_rasterize_shapes_device(h, shapes.empty() ? nullptr : static_cast<const sdfgpu_shape*>(d_shapes.p),
                                                                         (int64_t)shapes.size(), origin, resolution_, nx, ny, nz, d_bits, d_mask, d_ids, nullptr,
                                                                         nullptr));
-        if (scene.meshes.empty()) return;
-        Scratch d_meshes(h, scene.meshes.size() * sizeof(sdfgpu_mesh));
+        if (!scene.HasMeshes()) return;
+        // (the record buffers of the kind of mesh the scene does not have are not allocated: a scene of surface meshes alone
+        // allocates, enqueues and frees what it always did)
+        std::unique_ptr<Scratch> d_meshes, d_solid;
+        if (!scene.meshes.empty()) d_meshes.reset(new Scratch(h, scene.meshes.size() * sizeof(sdfgpu_mesh)));
         Scratch d_vertices(h, scene.vertices.size() * sizeof(double));
         Scratch d_triangles(h, scene.triangles.size() * sizeof(uint32_t));
-        sdf_generation::ThrowOnStatus(h, sdfgpu_copy_from_host(h, d_meshes.p, scene.meshes.data(), scene.meshes.size() * sizeof(sdfgpu_mesh), nullptr));
         if (!scene.vertices.empty())
             sdf_generation::ThrowOnStatus(h, sdfgpu_copy_from_host(h, d_vertices.p, scene.vertices.data(), scene.vertices.size() * sizeof(double), nullptr));
         if (!scene.triangles.empty())
             sdf_generation::ThrowOnStatus(h, sdfgpu_copy_from_host(h, d_triangles.p, scene.triangles.data(), scene.triangles.size() * sizeof(uint32_t), nullptr));
-        sdf_generation::ThrowOnStatus(h, sdfgpu_rasterize_meshes_device(h, static_cast<const sdfgpu_mesh*>(d_meshes.p), (int64_t)scene.meshes.size(),
-                                                                        static_cast<const double*>(d_vertices.p), (int64_t)(scene.vertices.size() / 3),
-                                                                        static_cast<const uint32_t*>(d_triangles.p), (int64_t)(scene.triangles.size() / 3), origin,
-                                                                        resolution_, nx, ny, nz, d_bits, d_mask, d_ids, 1, nullptr, nullptr));
+        if (!scene.meshes.empty()) {
+            sdf_generation::ThrowOnStatus(h, sdfgpu_copy_from_host(h, d_meshes->p, scene.meshes.data(), scene.meshes.size() * sizeof(sdfgpu_mesh), nullptr));
+            sdf_generation::ThrowOnStatus(h, sdfgpu_rasterize_meshes_device(h, static_cast<const sdfgpu_mesh*>(d_meshes->p), (int64_t)scene.meshes.size(),
+                                                                            static_cast<const double*>(d_vertices.p), (int64_t)(scene.vertices.size() / 3),
+                                                                            static_cast<const uint32_t*>(d_triangles.p), (int64_t)(scene.triangles.size() / 3), origin,
+                                                                            resolution_, nx, ny, nz, d_bits, d_mask, d_ids, 1, nullptr, nullptr));
+        }
+        if (scene.solid_meshes.empty()) return;
+        d_solid.reset(new Scratch(h, scene.solid_meshes.size() * sizeof(sdfgpu_mesh)));
+        sdf_generation::ThrowOnStatus(h, sdfgpu_copy_from_host(h, d_solid->p, scene.solid_meshes.data(), scene.solid_meshes.size() * sizeof(sdfgpu_mesh), nullptr));
+        for (size_t first = 0; first < scene.solid_meshes.size(); first += (size_t)SDFGPU_MAX_SOLID_MESHES) {
+            const size_t count = std::min(scene.solid_meshes.size() - first, (size_t)SDFGPU_MAX_SOLID_MESHES);
+            sdf_generation::ThrowOnStatus(h, sdfgpu_rasterize_solid_meshes_device(h, static_cast<const sdfgpu_mesh*>(d_solid->p) + first, (int64_t)count,
+                                                                                  static_cast<const double*>(d_vertices.p), (int64_t)(scene.vertices.size() / 3),
+                                                                                  static_cast<const uint32_t*>(d_triangles.p), (int64_t)(scene.triangles.size() / 3),
+                                                                                  origin, resolution_, nx, ny, nz, d_bits, d_mask, d_ids, 1, nullptr, nullptr));
+        }
     }
 
     // the reference's UpdateSDF / UpdateCollisionMap preamble: the exceptions, and the scene the mode asks for
@@ -293,7 +338,7 @@ protected:
             const std::shared_ptr<sdf_generation::SharedGpuContext> ctx = sdf_generation::GpuContext::Shared();
             const std::lock_guard<std::mutex> lock(ctx->mutex);
             sdfgpu_handle h = ctx->handle;
-            if (scene.meshes.empty()) {
+            if (!scene.HasMeshes()) {
                 sdf_generation::ThrowOnStatus(h, sdfgpu_rasterize_shapes(h, shapes.empty() ? nullptr : shapes.data(), (int64_t)shapes.size(), origin, resolution_, nx,
                                                                          ny, nz, nullptr, collision_field.GetMutableRawData().data(), nullptr));
             } else {                                                            // shapes, then meshes onto the same mask; one download
@@ -336,6 +381,18 @@ public:
     SignedDistanceField UpdateSDF(const uint8_t update_mode) {
         PrepareScene(update_mode);
         return UpdateSDFFromPlanningScene();
+    }
+
+    // How meshes are filled from the next update on: MESH_FILL_SURFACE (the default) or MESH_FILL_SOLID; per collision object
+    // (CollisionObject::id) with SetObjectMeshFill, which overrides the builder's mode for that object.
+    void SetMeshFill(const uint8_t mode) {
+        if (mode != MESH_FILL_SURFACE && mode != MESH_FILL_SOLID) throw std::invalid_argument("Invalid mesh fill mode (mode not recognized)");
+        mesh_fill_ = mode;
+    }
+
+    void SetObjectMeshFill(const std::string& object_id, const uint8_t mode) {
+        if (mode != MESH_FILL_SURFACE && mode != MESH_FILL_SOLID) throw std::invalid_argument("Invalid mesh fill mode (mode not recognized)");
+        object_mesh_fill_[object_id] = mode;
     }
 
     const SignedDistanceField& GetCachedSDF() const {
@@ -387,7 +444,7 @@ public:
             const std::shared_ptr<sdf_generation::SharedGpuContext> ctx = sdf_generation::GpuContext::Shared();
             const std::lock_guard<std::mutex> lock(ctx->mutex);
             sdfgpu_handle h = ctx->handle;
-            if (scene.meshes.empty()) {
+            if (!scene.HasMeshes()) {
                 sdf_generation::ThrowOnStatus(h, sdfgpu_rasterize_shapes(h, shapes.empty() ? nullptr : shapes.data(), (int64_t)shapes.size(), origin, resolution_, nx,
                                                                          ny, nz, nullptr, nullptr, ids.data()));
             } else {

@@ -57,7 +57,8 @@ def build_libsdfgpu(force=False, verbose=False):
     """Every csrc/*.hip -> an object (compiled side by side) -> libsdfgpu.so.  DESIGN.md section 5 has the table of the units:
     sdfgpu.hip (the SDF build: its C ABI, host orchestration and most kernels), sdfgpu_context.hip (the handle), the two
     instantiation units (sdfgpu_envelope_tu.hip, sdfgpu_dense6_tu.hip) and one unit per family with its kernels, launchers, host
-    code and entry points (components, topology, surfaces, convex, project, query, batch, resample, display, scene, mesh).
+    code and entry points (components, topology, surfaces, convex, project, query, batch, resample, display, scene, mesh;
+    mesh_solid holds the solid fill's kernels and the closedness check, its entry points sit in mesh).
 
     Dependencies are the compiler's: each compile writes <obj>.d (-MD -MF), and an object is rebuilt when its source or ANY file
     named there is newer, or when the depfile is missing (a stale library after a header-only edit is the kind of bug that

@@ -42,6 +42,7 @@ EXPORTS = [
     "sdfgpu_display_contour_reach", "sdfgpu_display_select_contour_device", "sdfgpu_display_select_contour",
     "sdfgpu_rasterize_shapes_device", "sdfgpu_rasterize_shapes",
     "sdfgpu_rasterize_meshes_device", "sdfgpu_rasterize_meshes",
+    "sdfgpu_rasterize_solid_meshes_device", "sdfgpu_rasterize_solid_meshes", "sdfgpu_check_closed_meshes",
 ]
 
 # include/sdfgpu.h "Projection": modes and per-point statuses
@@ -179,6 +180,9 @@ def load_library():
     L.sdfgpu_rasterize_shapes.argtypes = [vp, vp, i64, vp, dbl, i64, i64, i64, vp, vp, vp]
     L.sdfgpu_rasterize_meshes_device.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, dbl, i64, i64, i64, vp, vp, vp, ctypes.c_int, vp, vp]
     L.sdfgpu_rasterize_meshes.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, dbl, i64, i64, i64, vp, vp, vp]
+    L.sdfgpu_rasterize_solid_meshes_device.argtypes = L.sdfgpu_rasterize_meshes_device.argtypes
+    L.sdfgpu_rasterize_solid_meshes.argtypes = L.sdfgpu_rasterize_meshes.argtypes
+    L.sdfgpu_check_closed_meshes.argtypes = [vp, i64, vp, i64, vp, i64, vp, vp]
     L.sdfgpu_build_batch_device.argtypes = [vp, vp, i64, i64, i64, i64, dbl, vp, ci, vp, vp]
     L.sdfgpu_get_extrema_batch.argtypes = [vp, i64, vp, vp]
     L.sdfgpu_build_batch.argtypes = [vp, vp, i64, i64, i64, i64, dbl, vp, ci, vp, vp, vp]
@@ -295,6 +299,9 @@ def make_shapes(items):
     return out
 
 
+MAX_SOLID_MESHES = 256                # SDFGPU_MAX_SOLID_MESHES
+
+
 def make_meshes(items):
     """[(object_id, vertices [n, 3], triangles [m, 3] of indices into those vertices, pose 4 x 4 or 3 x 4)] ->
     (MESH_DTYPE records, vertices float64 [sum n, 3], triangles uint32 [sum m, 3]): the arrays of sdfgpu_rasterize_meshes, every
@@ -314,6 +321,24 @@ def make_meshes(items):
         ts.append(t)
         nv, nt = nv + len(v), nt + len(t)
     return out, np.ascontiguousarray(np.concatenate(vs)), np.ascontiguousarray(np.concatenate(ts))
+
+
+def check_closed_meshes(meshes, vertices, triangles):
+    """sdfgpu_check_closed_meshes (no GPU needed): None when every mesh is closed -- each undirected edge, its endpoints keyed by
+    world position, is used by an even number of the mesh's triangles -- else (mesh index, triangle index within the mesh); the
+    triangle is -1 for a refused mesh record.  Refused arrays raise."""
+    L = load_library()
+    ms = np.ascontiguousarray(meshes, dtype=MESH_DTYPE).reshape(-1)
+    vs = np.ascontiguousarray(vertices, dtype=np.float64).reshape(-1, 3)
+    ts = np.ascontiguousarray(triangles, dtype=np.uint32).reshape(-1, 3)
+    bad_mesh, bad_triangle = ctypes.c_int64(-2), ctypes.c_int64(-2)
+    rc = L.sdfgpu_check_closed_meshes(ms.ctypes.data if ms.size else None, int(ms.size), vs.ctypes.data if vs.size else None, len(vs),
+                                      ts.ctypes.data if ts.size else None, len(ts), ctypes.byref(bad_mesh), ctypes.byref(bad_triangle))
+    if rc == 0:
+        return None
+    if bad_mesh.value < 0:
+        raise ValueError("sdfgpu_check_closed_meshes: refused arguments")
+    return int(bad_mesh.value), int(bad_triangle.value)
 
 
 def project_step_limit(shape, stepsize_multiplier=1.0 / 8.0, max_steps=0):
@@ -970,10 +995,9 @@ class SdfGpu:
                                                              ctypes.byref(bad) if check else None, stream or None))
         return int(bad.value) if check else None
 
-    # ---- mesh rasteriser (include/sdfgpu.h "Planes and triangle meshes") ----
-    def rasterize_meshes(self, meshes, vertices, triangles, origin, resolution, shape, bits=True, mask=False, object_ids=False):
-        """meshes: MESH_DTYPE records, vertices: float64 [n, 3], triangles: uint32 [m, 3] (see make_meshes).  Returns a dict of the
-        outputs asked for, as rasterize_shapes does."""
+    # ---- mesh rasteriser (include/sdfgpu.h "Planes and triangle meshes") and solid meshes ("Solid meshes") ----
+    def _meshes_host(self, call, meshes, vertices, triangles, origin, resolution, shape, bits, mask, object_ids):
+        """the host form of either mesh call: the arrays in, a dict of the outputs asked for back"""
         nx, ny, nz = (int(v) for v in shape)
         ms = np.ascontiguousarray(meshes, dtype=MESH_DTYPE).reshape(-1)
         vs = np.ascontiguousarray(vertices, dtype=np.float64).reshape(-1, 3)
@@ -987,23 +1011,44 @@ class SdfGpu:
         if object_ids:
             out["object_ids"] = np.empty((nx, ny, nz), np.uint32)
         ptr = [out[k].ctypes.data if k in out else None for k in ("bits", "mask", "object_ids")]
-        self._check(self._lib.sdfgpu_rasterize_meshes(self._h, ms.ctypes.data if ms.size else None, int(ms.size),
-                                                      vs.ctypes.data if vs.size else None, len(vs), ts.ctypes.data if ts.size else None, len(ts),
-                                                      _doubles(origin, 16), float(resolution), nx, ny, nz, *ptr))
+        self._check(call(self._h, ms.ctypes.data if ms.size else None, int(ms.size),
+                         vs.ctypes.data if vs.size else None, len(vs), ts.ctypes.data if ts.size else None, len(ts),
+                         _doubles(origin, 16), float(resolution), nx, ny, nz, *ptr))
         return out
+
+    def _meshes_device(self, call, d_meshes, n_meshes, d_vertices, n_vertices, d_triangles, n_triangles, origin, resolution, shape,
+                       d_bits, d_mask, d_object_ids, accumulate, check, stream):
+        """the device form of either mesh call"""
+        nx, ny, nz = (int(v) for v in shape)
+        bad = ctypes.c_int64(-2)
+        self._check(call(self._h, d_meshes or None, int(n_meshes), d_vertices or None, int(n_vertices),
+                         d_triangles or None, int(n_triangles), _doubles(origin, 16), float(resolution),
+                         nx, ny, nz, d_bits or None, d_mask or None, d_object_ids or None,
+                         int(accumulate), ctypes.byref(bad) if check else None, stream or None))
+        return int(bad.value) if check else None
+
+    def rasterize_meshes(self, meshes, vertices, triangles, origin, resolution, shape, bits=True, mask=False, object_ids=False):
+        """meshes: MESH_DTYPE records, vertices: float64 [n, 3], triangles: uint32 [m, 3] (see make_meshes).  Returns a dict of the
+        outputs asked for, as rasterize_shapes does."""
+        return self._meshes_host(self._lib.sdfgpu_rasterize_meshes, meshes, vertices, triangles, origin, resolution, shape, bits, mask, object_ids)
 
     def rasterize_meshes_device(self, d_meshes, n_meshes, d_vertices, n_vertices, d_triangles, n_triangles, origin, resolution, shape,
                                 d_bits=0, d_mask=0, d_object_ids=0, accumulate=False, check=False, stream=0):
         """Device form (device addresses as ints), enqueued on `stream`.  accumulate: OR onto the bits and the mask that are there,
         ids to the smallest non-zero.  check: synchronise the stream and return the index of the first refused mesh (-1: none; a
         refused mesh also raises); without it the call does not wait and returns None."""
-        nx, ny, nz = (int(v) for v in shape)
-        bad = ctypes.c_int64(-2)
-        self._check(self._lib.sdfgpu_rasterize_meshes_device(self._h, d_meshes or None, int(n_meshes), d_vertices or None, int(n_vertices),
-                                                             d_triangles or None, int(n_triangles), _doubles(origin, 16), float(resolution),
-                                                             nx, ny, nz, d_bits or None, d_mask or None, d_object_ids or None,
-                                                             int(accumulate), ctypes.byref(bad) if check else None, stream or None))
-        return int(bad.value) if check else None
+        return self._meshes_device(self._lib.sdfgpu_rasterize_meshes_device, d_meshes, n_meshes, d_vertices, n_vertices, d_triangles, n_triangles,
+                                   origin, resolution, shape, d_bits, d_mask, d_object_ids, accumulate, check, stream)
+
+    def rasterize_solid_meshes(self, meshes, vertices, triangles, origin, resolution, shape, bits=True, mask=False, object_ids=False):
+        """rasterize_meshes with every mesh filled inside (even-odd, per mesh); an open mesh is refused"""
+        return self._meshes_host(self._lib.sdfgpu_rasterize_solid_meshes, meshes, vertices, triangles, origin, resolution, shape, bits, mask, object_ids)
+
+    def rasterize_solid_meshes_device(self, d_meshes, n_meshes, d_vertices, n_vertices, d_triangles, n_triangles, origin, resolution, shape,
+                                      d_bits=0, d_mask=0, d_object_ids=0, accumulate=False, check=False, stream=0):
+        """rasterize_meshes_device with every mesh filled inside; at most MAX_SOLID_MESHES meshes, closedness is not checked"""
+        return self._meshes_device(self._lib.sdfgpu_rasterize_solid_meshes_device, d_meshes, n_meshes, d_vertices, n_vertices, d_triangles, n_triangles,
+                                   origin, resolution, shape, d_bits, d_mask, d_object_ids, accumulate, check, stream)
 
     def debug_resample_times(self):
         """(memset + winner kernel, gather kernel) of the last resample call in ms, after set_option("resample_timing", 1)"""

@@ -770,6 +770,8 @@ PYBIND11_MODULE(pysdf_tools, m) {
     m.attr("USE_ONLY_OCTOMAP") = (int)sdf_tools::USE_ONLY_OCTOMAP;
     m.attr("USE_ONLY_COLLISION_OBJECTS") = (int)sdf_tools::USE_ONLY_COLLISION_OBJECTS;
     m.attr("USE_FULL_PLANNING_SCENE") = (int)sdf_tools::USE_FULL_PLANNING_SCENE;
+    m.attr("MESH_FILL_SURFACE") = (int)sdf_tools::MESH_FILL_SURFACE;
+    m.attr("MESH_FILL_SOLID") = (int)sdf_tools::MESH_FILL_SOLID;
     const auto collision_map_numpy = [](const VoxelGrid::VoxelGrid<uint8_t>& g) {
         py::array_t<uint8_t> out({g.GetNumXCells(), g.GetNumYCells(), g.GetNumZCells()});
         std::memcpy(out.mutable_data(), g.GetImmutableRawData().data(), g.GetImmutableRawData().size());
@@ -784,6 +786,10 @@ PYBIND11_MODULE(pysdf_tools, m) {
              py::arg("frame"), py::arg("x_size"), py::arg("y_size"), py::arg("z_size"), py::arg("resolution"), py::arg("OOB_value"),
              py::arg("planning_scene_source") = sdf_tools::SDF_Builder::PlanningSceneSource())
         .def("UpdatePlanningSceneFromMessage", &sdf_tools::SDF_Builder::UpdatePlanningSceneFromMessage)
+        .def("SetMeshFill", [](sdf_tools::SDF_Builder& b, int mode) { b.SetMeshFill((uint8_t)mode); }, py::arg("mode"),
+             "MESH_FILL_SURFACE (default) or MESH_FILL_SOLID: closed meshes are filled inside as well")
+        .def("SetObjectMeshFill", [](sdf_tools::SDF_Builder& b, const std::string& object_id, int mode) { b.SetObjectMeshFill(object_id, (uint8_t)mode); },
+             py::arg("object_id"), py::arg("mode"), "the mode for the meshes of one collision object, by its id")
         .def("UpdateSDF", [](sdf_tools::SDF_Builder& b, int mode) { return b.UpdateSDF((uint8_t)mode); })
         .def("GetCachedSDF", [](const sdf_tools::SDF_Builder& b) { return b.GetCachedSDF(); })
         .def("UpdateCollisionMap", [collision_map_numpy](sdf_tools::SDF_Builder& b, int mode) { return collision_map_numpy(b.UpdateCollisionMap((uint8_t)mode)); },

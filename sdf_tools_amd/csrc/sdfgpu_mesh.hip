@@ -17,7 +17,7 @@
 // Arithmetic: the decision procedure may not be contracted into FMAs (sdfgpu_mesh.hpp).
 #pragma clang fp contract(off)
 #include "sdfgpu_context.hpp"
-#include "sdfgpu_mesh.hpp"
+#include "sdfgpu_mesh_solid.hpp"
 #include "sdfgpu.h"
 
 namespace sdfgpu {
@@ -228,25 +228,41 @@ __global__ __launch_bounds__(kMrThreads) void k_mr_scatter(const MeshArgs a) {
 
 }  // namespace
 
-// the kernels on `s`, behind a memset of the status block
-hipError_t mesh_launch(const MeshArgs& a, hipStream_t s) {
+// the kernels on `s`, behind a memset of the status block, in three parts that the solid call (sdfgpu_mesh_solid.hip) interleaves
+// with its own: the checks and world vertices | the scan of a.scan into a.top and the total | the scatter
+hipError_t mesh_launch_setup(const MeshArgs& a, hipStream_t s) {
     hipError_t e = hipMemsetAsync(a.status, 0xFF, kScStatusBytes, s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_mr_meshes, dim3(1), dim3(kMrThreads), 0, s, a);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (a.n_triangles > 0) {
         hipLaunchKernelGGL(k_mr_setup, dim3((unsigned)((a.n_triangles + kMrThreads - 1) / kMrThreads)), dim3(kMrThreads), 0, s, a);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        hipLaunchKernelGGL(k_mr_scan_blocks, dim3((unsigned)mr_scan_blocks(a.n_triangles)), dim3(kMrThreads), 0, s, a);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(k_mr_scan_top, dim3(1), dim3(kMrThreads), 0, s, a);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (a.n_triangles > 0) {
-        if (a.ids) hipLaunchKernelGGL(k_mr_scatter<true>, dim3(kMrScatterGroups), dim3(kMrThreads), 0, s, a);
-        else hipLaunchKernelGGL(k_mr_scatter<false>, dim3(kMrScatterGroups), dim3(kMrThreads), 0, s, a);
         e = hipGetLastError();
     }
+    return e;
+}
+
+hipError_t mesh_launch_scan(const MeshArgs& a, hipStream_t s) {
+    if (a.n_triangles > 0) {
+        hipLaunchKernelGGL(k_mr_scan_blocks, dim3((unsigned)mr_scan_blocks(a.n_triangles)), dim3(kMrThreads), 0, s, a);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_mr_scan_top, dim3(1), dim3(kMrThreads), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t mesh_launch_scatter(const MeshArgs& a, hipStream_t s) {
+    if (a.n_triangles <= 0) return hipSuccess;
+    if (a.ids) hipLaunchKernelGGL(k_mr_scatter<true>, dim3(kMrScatterGroups), dim3(kMrThreads), 0, s, a);
+    else hipLaunchKernelGGL(k_mr_scatter<false>, dim3(kMrScatterGroups), dim3(kMrThreads), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t mesh_launch(const MeshArgs& a, hipStream_t s) {
+    hipError_t e = mesh_launch_setup(a, s);
+    if (e == hipSuccess) e = mesh_launch_scan(a, s);
+    if (e == hipSuccess) e = mesh_launch_scatter(a, s);
     return e;
 }
 
@@ -259,50 +275,49 @@ namespace {
 
 int check_mesh_args(sdfgpu_handle h, const sdfgpu_mesh* meshes, int64_t n_meshes, const double* vertices, int64_t n_vertices,
                     const uint32_t* triangles, int64_t n_triangles, const double* origin, double resolution, int64_t nx, int64_t ny, int64_t nz,
-                    const void* bits, const void* mask, const void* ids, int accumulate, MeshArgs& a) {
-    if (!origin) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "rasterize_meshes: null origin");
-    if (!bits && !mask && !ids) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "rasterize_meshes: no output asked for");
-    if (accumulate != 0 && accumulate != 1) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "rasterize_meshes: accumulate must be 0 or 1");
+                    const void* bits, const void* mask, const void* ids, int accumulate, MeshArgs& a, bool solid = false) {
+    const char* const who = solid ? "rasterize_solid_meshes" : "rasterize_meshes";
+    if (!origin) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "%s: null origin", who);
+    if (!bits && !mask && !ids) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "%s: no output asked for", who);
+    if (accumulate != 0 && accumulate != 1) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "%s: accumulate must be 0 or 1", who);
     if (n_meshes < 0 || n_meshes > kMrMaxMeshes)
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "rasterize_meshes: %lld meshes, the limit is %lld", (long long)n_meshes, (long long)kMrMaxMeshes);
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "%s: %lld meshes, the limit is %lld", who, (long long)n_meshes, (long long)kMrMaxMeshes);
+    if (solid && n_meshes > kMsMaxMeshes)
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "%s: %lld meshes, the limit is %lld (one pair of launches each)", who, (long long)n_meshes, (long long)kMsMaxMeshes);
     if (n_triangles < 0 || n_triangles > kMrMaxTriangles)
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "rasterize_meshes: %lld triangles, the limit is %lld", (long long)n_triangles, (long long)kMrMaxTriangles);
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "%s: %lld triangles, the limit is %lld", who, (long long)n_triangles, (long long)kMrMaxTriangles);
     if (n_vertices < 0 || n_vertices > ((int64_t)1 << 32))
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "rasterize_meshes: %lld vertices, the limit is 2^32", (long long)n_vertices);
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "%s: %lld vertices, the limit is 2^32", who, (long long)n_vertices);
     if ((n_meshes > 0 && !meshes) || (n_vertices > 0 && !vertices) || (n_triangles > 0 && !triangles))
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "rasterize_meshes: null meshes, vertices or triangles");
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "%s: null meshes, vertices or triangles", who);
     if ((reinterpret_cast<uintptr_t>(meshes) | reinterpret_cast<uintptr_t>(vertices)) & 7)
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "rasterize_meshes: meshes and vertices must be 8-byte aligned");
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "%s: meshes and vertices must be 8-byte aligned", who);
     if ((reinterpret_cast<uintptr_t>(triangles) | reinterpret_cast<uintptr_t>(bits) | reinterpret_cast<uintptr_t>(ids)) & 3)
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "rasterize_meshes: triangles, bits and object ids must be 4-byte aligned");
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "%s: triangles, bits and object ids must be 4-byte aligned", who);
     const int64_t kMaxCells = INT64_MAX / 16;
     if (nx <= 0 || ny <= 0 || nz <= 0 || nx > kMaxCells / ny || nx * ny > kMaxCells / nz)
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "rasterize_meshes: unsupported grid %lld x %lld x %lld", (long long)nx, (long long)ny, (long long)nz);
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "%s: unsupported grid %lld x %lld x %lld", who, (long long)nx, (long long)ny, (long long)nz);
     if (!(std::isfinite(resolution) && resolution > 0.0))
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "rasterize_meshes: the resolution must be positive and finite");
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "%s: the resolution must be positive and finite", who);
     for (int i = 0; i < 16; ++i)
-        if (!std::isfinite(origin[i])) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "rasterize_meshes: origin entry %d is not finite", i);
+        if (!std::isfinite(origin[i])) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "%s: origin entry %d is not finite", who, i);
     a = MeshArgs{};
     a.n_meshes = n_meshes; a.n_vertices = n_vertices; a.n_triangles = n_triangles;
     for (int i = 0; i < 12; ++i) a.origin[i] = origin[i];
-    // the inverse of the origin's 3 x 3 block by cofactors, for the index boxes alone
-    const double* o = origin;
-    const double c00 = o[5] * o[10] - o[6] * o[9], c01 = o[6] * o[8] - o[4] * o[10], c02 = o[4] * o[9] - o[5] * o[8];
-    const double det = o[0] * c00 + o[1] * c01 + o[2] * c02;
-    const double inv[9] = {c00 / det, (o[2] * o[9] - o[1] * o[10]) / det, (o[1] * o[6] - o[2] * o[5]) / det,
-                           c01 / det, (o[0] * o[10] - o[2] * o[8]) / det, (o[2] * o[4] - o[0] * o[6]) / det,
-                           c02 / det, (o[1] * o[8] - o[0] * o[9]) / det, (o[0] * o[5] - o[1] * o[4]) / det};
-    a.no_inverse = !(std::isfinite(det) && det != 0.0);
-    for (int i = 0; i < 9; ++i) if (!std::isfinite(inv[i])) a.no_inverse = 1;
-    for (int i = 0; i < 9; ++i) a.inverse[i] = a.no_inverse ? 0.0 : inv[i];
+    // the inverse of the origin's 3 x 3 block by cofactors: for the index boxes, and the frame of the solid fill
+    a.no_inverse = ms_inverse(origin, a.inverse) ? 0 : 1;
     a.res = resolution; a.half = resolution * 0.5;
     a.nx = nx; a.ny = ny; a.nz = nz; a.n = nx * ny * nz;
     a.accumulate = accumulate;
+    if (solid && a.no_inverse)
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "%s: the origin's 3 x 3 block has no inverse (the fill works in grid coordinates)", who);
     return SDFGPU_OK;
 }
 
 // a.meshes, a.vertices, a.triangles -> a.bits / a.mask / a.ids (device) on `st`; synchronises `st` only when out_bad_mesh is asked for
-int rasterize_meshes_impl(sdfgpu_handle h, MeshArgs& a, int64_t* out_bad_mesh, hipStream_t st) {
+// solid: the meshes are also filled inside (sdfgpu_mesh_solid.hpp); the toggle field is the handle's and all zero between calls
+int rasterize_meshes_impl(sdfgpu_handle h, MeshArgs& a, int64_t* out_bad_mesh, hipStream_t st, bool solid = false) {
+    const char* const who = solid ? "rasterize_solid_meshes" : "rasterize_meshes";
     if (!a.accumulate) {
         if (a.bits) HIP_TRY(h, hipMemsetAsync(a.bits, 0, (size_t)((a.n + 31) / 32) * 4, st));
         if (a.mask) HIP_TRY(h, hipMemsetAsync(a.mask, 0, (size_t)a.n, st));
@@ -316,7 +331,8 @@ int rasterize_meshes_impl(sdfgpu_handle h, MeshArgs& a, int64_t* out_bad_mesh, h
     // on the device first, as a shape rasterisation does (ensure() below may free the scratch: hipFree waits for the device)
     HIP_TRY(h, h->mr_order.create());
     HIP_TRY(h, h->mr_order.wait(st));
-    if (int rc = ensure(h, h->mr_scratch, mesh_scratch_bytes(a.n_meshes, a.n_triangles), "mesh rasteriser scratch")) return rc;
+    if (int rc = ensure(h, h->mr_scratch, solid ? mesh_solid_scratch_bytes(a.n_meshes, a.n_triangles) : mesh_scratch_bytes(a.n_meshes, a.n_triangles),
+                        "mesh rasteriser scratch")) return rc;
     char* const base = static_cast<char*>(h->mr_scratch.ptr);
     a.status = reinterpret_cast<uint32_t*>(base);
     a.first = reinterpret_cast<int64_t*>(base + mr_first_offset());
@@ -324,7 +340,26 @@ int rasterize_meshes_impl(sdfgpu_handle h, MeshArgs& a, int64_t* out_bad_mesh, h
     a.scan = reinterpret_cast<int64_t*>(base + mr_scan_offset(a.n_meshes, a.n_triangles));
     a.world = reinterpret_cast<double*>(base + mr_world_offset(a.n_meshes, a.n_triangles));
     a.slot_id = reinterpret_cast<uint32_t*>(base + mr_id_offset(a.n_meshes, a.n_triangles));
-    const hipError_t le = mesh_launch(a, st);
+    hipError_t le;
+    if (solid) {
+        SolidArgs sa{};
+        sa.wz = ms_row_words(a.nz);
+        const size_t toggle_bytes = (size_t)(a.nx * a.ny * sa.wz) * 4;
+        const void* const had = h->ms_toggle.bytes >= toggle_bytes ? h->ms_toggle.ptr : nullptr;
+        if (int rc = ensure(h, h->ms_toggle, toggle_bytes, "solid mesh toggle field")) return rc;
+        if (h->ms_toggle.ptr != had || h->ms_dirty) HIP_TRY(h, hipMemsetAsync(h->ms_toggle.ptr, 0, h->ms_toggle.bytes, st));
+        sa.m = a;
+        sa.scan = reinterpret_cast<int64_t*>(base + ms_scan_offset(a.n_meshes, a.n_triangles));
+        sa.top = reinterpret_cast<int64_t*>(base + ms_top_offset(a.n_meshes, a.n_triangles));
+        sa.box_lo = reinterpret_cast<unsigned long long*>(base + ms_box_offset(a.n_meshes, a.n_triangles));
+        sa.box_hi = reinterpret_cast<unsigned long long*>(base + ms_box_offset(a.n_meshes, a.n_triangles) + ms_box_bytes(a.n_meshes));
+        sa.toggle = static_cast<uint32_t*>(h->ms_toggle.ptr);
+        h->ms_dirty = true;                             // (until every merge that clears what a scatter set is enqueued)
+        le = mesh_solid_launch(sa, st);
+        if (le == hipSuccess) h->ms_dirty = false;
+    } else {
+        le = mesh_launch(a, st);
+    }
     (void)h->mr_order.record(st);                       // (also behind a failed launch: what it did enqueue is ordered)
     HIP_TRY(h, le);
     if (out_bad_mesh) {
@@ -333,8 +368,9 @@ int rasterize_meshes_impl(sdfgpu_handle h, MeshArgs& a, int64_t* out_bad_mesh, h
         HIP_TRY(h, hipStreamSynchronize(st));
         *out_bad_mesh = word == kMrNoBadMesh ? -1 : (int64_t)word;
         if (word != kMrNoBadMesh)
-            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "rasterize_meshes: mesh %lld is refused (ranges, pose, vertices, vertex indices or object id); "
-                        "the outputs are %s", (long long)word, a.accumulate ? "unchanged" : "cleared");
+            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "%s: mesh %lld is refused (ranges, pose, vertices, vertex indices or object id%s); "
+                        "the outputs are %s", who, (long long)word, solid ? ", or a vertex whose grid coordinates are not finite" : "",
+                        a.accumulate ? "unchanged" : "cleared");
     }
     return SDFGPU_OK;
 }
@@ -343,39 +379,54 @@ int rasterize_meshes_impl(sdfgpu_handle h, MeshArgs& a, int64_t* out_bad_mesh, h
 
 extern "C" {
 
-int sdfgpu_rasterize_meshes_device(sdfgpu_handle h, const sdfgpu_mesh* d_meshes, int64_t n_meshes, const double* d_vertices, int64_t n_vertices,
+static int rasterize_meshes_device_form(bool solid, sdfgpu_handle h, const sdfgpu_mesh* d_meshes, int64_t n_meshes, const double* d_vertices, int64_t n_vertices,
                                    const uint32_t* d_triangles, int64_t n_triangles, const double origin[16], double voxel_size, int64_t nx,
                                    int64_t ny, int64_t nz, uint32_t* d_bits, uint8_t* d_mask, uint32_t* d_object_ids, int accumulate,
                                    int64_t* out_bad_mesh, void* stream) {
     return rz_wrap(h, stream, [&]() -> int {
         MeshArgs a;
         if (int rc = check_mesh_args(h, d_meshes, n_meshes, d_vertices, n_vertices, d_triangles, n_triangles, origin, voxel_size, nx, ny, nz,
-                                     d_bits, d_mask, d_object_ids, accumulate, a)) return rc;
+                                     d_bits, d_mask, d_object_ids, accumulate, a, solid)) return rc;
         HIP_TRY(h, hipSetDevice(h->device));
         a.meshes = d_meshes; a.vertices = d_vertices; a.triangles = d_triangles;
         a.bits = d_bits; a.mask = d_mask; a.ids = d_object_ids;
-        return rasterize_meshes_impl(h, a, out_bad_mesh, (hipStream_t)stream);
+        return rasterize_meshes_impl(h, a, out_bad_mesh, (hipStream_t)stream, solid);
     });
 }
 
-int sdfgpu_rasterize_meshes(sdfgpu_handle h, const sdfgpu_mesh* meshes, int64_t n_meshes, const double* vertices, int64_t n_vertices,
+static int rasterize_meshes_host_form(bool solid, sdfgpu_handle h, const sdfgpu_mesh* meshes, int64_t n_meshes, const double* vertices, int64_t n_vertices,
                             const uint32_t* triangles, int64_t n_triangles, const double origin[16], double voxel_size, int64_t nx, int64_t ny,
                             int64_t nz, uint32_t* bits, uint8_t* mask, uint32_t* object_ids) {
     return rz_wrap(h, nullptr, [&]() -> int {
         MeshArgs a;
         if (int rc = check_mesh_args(h, meshes, n_meshes, vertices, n_vertices, triangles, n_triangles, origin, voxel_size, nx, ny, nz, bits,
-                                     mask, object_ids, 0, a)) return rc;
+                                     mask, object_ids, 0, a, solid)) return rc;
+        const char* const who = solid ? "rasterize_solid_meshes" : "rasterize_meshes";
         int64_t slots = 0;
         for (int64_t m = 0; m < n_meshes; ++m) {
             const sdfgpu_mesh& mesh = meshes[m];
             bool ok = mr_mesh_valid(mesh, n_vertices, n_triangles, object_ids != nullptr);
             if (ok) { slots += mesh.n_triangles; ok = slots <= n_triangles; }
             double W[9];
-            for (int64_t j = 0; ok && j < mesh.n_triangles; ++j) ok = mr_triangle_valid(mesh, vertices, triangles + 3 * (mesh.first_triangle + j), W);
+            for (int64_t j = 0; ok && j < mesh.n_triangles; ++j) {
+                ok = mr_triangle_valid(mesh, vertices, triangles + 3 * (mesh.first_triangle + j), W);
+                double G[3][3];
+                if (ok && solid) ok = ms_grid_triangle(a, W, G);
+            }
             if (!ok)
-                return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "rasterize_meshes: mesh %lld is refused (its triangle and vertex runs must lie inside the "
+                return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "%s: mesh %lld is refused (its triangle and vertex runs must lie inside the "
                             "arrays and its triangles, with those of the meshes before it, number n_triangles at most; a finite pose, finite "
-                            "vertices, vertex indices below its n_vertices and, for object ids, an id other than 0 and 0xFFFFFFFF are taken)", (long long)m);
+                            "vertices, vertex indices below its n_vertices and, for object ids, an id other than 0 and 0xFFFFFFFF are taken%s)", who, (long long)m,
+                            solid ? "; for the fill, grid coordinates that are finite" : "");
+        }
+        if (solid) {                                    // every record and vertex is valid by now: what is left is an open mesh, or no memory
+            int64_t bad_mesh = -1, bad_triangle = -1;
+            if (sdfgpu_check_closed_meshes(meshes, n_meshes, vertices, n_vertices, triangles, n_triangles, &bad_mesh, &bad_triangle) != SDFGPU_OK) {
+                if (bad_mesh < 0 || bad_triangle < 0)
+                    return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "%s: the closedness check could not be made (out of host memory?)", who);
+                return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "%s: mesh %lld is not closed: an edge of its triangle %lld is used by an odd number of "
+                            "triangles", who, (long long)bad_mesh, (long long)bad_triangle);
+            }
         }
         HIP_TRY(h, hipSetDevice(h->device));
         // the null stream throughout: meshes | vertices | triangles through the cell staging, the outputs through the field staging
@@ -396,12 +447,42 @@ int sdfgpu_rasterize_meshes(sdfgpu_handle h, const sdfgpu_mesh* meshes, int64_t 
         a.bits = bits ? reinterpret_cast<uint32_t*>(out) : nullptr;
         a.mask = mask ? reinterpret_cast<uint8_t*>(out + off_mask) : nullptr;
         a.ids = object_ids ? reinterpret_cast<uint32_t*>(out + off_ids) : nullptr;
-        if (int rc = rasterize_meshes_impl(h, a, nullptr, nullptr)) return rc;
+        if (int rc = rasterize_meshes_impl(h, a, nullptr, nullptr, solid)) return rc;
         if (bits) if (int rc = copy_to_host(h, bits, a.bits, (size_t)((a.n + 31) / 32) * 4)) return rc;
         if (mask) if (int rc = copy_to_host(h, mask, a.mask, (size_t)a.n)) return rc;
         if (object_ids) if (int rc = copy_to_host(h, object_ids, a.ids, (size_t)a.n * 4)) return rc;
         return SDFGPU_OK;
     });
+}
+
+int sdfgpu_rasterize_meshes_device(sdfgpu_handle h, const sdfgpu_mesh* d_meshes, int64_t n_meshes, const double* d_vertices, int64_t n_vertices,
+                                   const uint32_t* d_triangles, int64_t n_triangles, const double origin[16], double voxel_size, int64_t nx,
+                                   int64_t ny, int64_t nz, uint32_t* d_bits, uint8_t* d_mask, uint32_t* d_object_ids, int accumulate,
+                                   int64_t* out_bad_mesh, void* stream) {
+    return rasterize_meshes_device_form(false, h, d_meshes, n_meshes, d_vertices, n_vertices, d_triangles, n_triangles, origin, voxel_size, nx, ny, nz,
+                                        d_bits, d_mask, d_object_ids, accumulate, out_bad_mesh, stream);
+}
+
+int sdfgpu_rasterize_solid_meshes_device(sdfgpu_handle h, const sdfgpu_mesh* d_meshes, int64_t n_meshes, const double* d_vertices, int64_t n_vertices,
+                                         const uint32_t* d_triangles, int64_t n_triangles, const double origin[16], double voxel_size, int64_t nx,
+                                         int64_t ny, int64_t nz, uint32_t* d_bits, uint8_t* d_mask, uint32_t* d_object_ids, int accumulate,
+                                         int64_t* out_bad_mesh, void* stream) {
+    return rasterize_meshes_device_form(true, h, d_meshes, n_meshes, d_vertices, n_vertices, d_triangles, n_triangles, origin, voxel_size, nx, ny, nz,
+                                        d_bits, d_mask, d_object_ids, accumulate, out_bad_mesh, stream);
+}
+
+int sdfgpu_rasterize_meshes(sdfgpu_handle h, const sdfgpu_mesh* meshes, int64_t n_meshes, const double* vertices, int64_t n_vertices,
+                            const uint32_t* triangles, int64_t n_triangles, const double origin[16], double voxel_size, int64_t nx, int64_t ny,
+                            int64_t nz, uint32_t* bits, uint8_t* mask, uint32_t* object_ids) {
+    return rasterize_meshes_host_form(false, h, meshes, n_meshes, vertices, n_vertices, triangles, n_triangles, origin, voxel_size, nx, ny, nz, bits,
+                                      mask, object_ids);
+}
+
+int sdfgpu_rasterize_solid_meshes(sdfgpu_handle h, const sdfgpu_mesh* meshes, int64_t n_meshes, const double* vertices, int64_t n_vertices,
+                                  const uint32_t* triangles, int64_t n_triangles, const double origin[16], double voxel_size, int64_t nx, int64_t ny,
+                                  int64_t nz, uint32_t* bits, uint8_t* mask, uint32_t* object_ids) {
+    return rasterize_meshes_host_form(true, h, meshes, n_meshes, vertices, n_vertices, triangles, n_triangles, origin, voxel_size, nx, ny, nz, bits,
+                                      mask, object_ids);
 }
 
 }  // extern "C"
