@@ -7,6 +7,9 @@
 //                                       sdfgpu_mesh records | n_vertices x 3 doubles | n_triangles x 3 uint32
 //                                   OUT: int64: the lowest refused mesh index, -1 for none, -2 for an origin without an inverse; per
 //                                       voxel one uint32: the smallest object id among the meshes that fill it, 0 for none
+//   mesh_solid_host cull IN OUT     IN: int64 n, nx, ny | double res | n x 9 doubles: triangles in GRID coordinates (ms_grid's output)
+//                                   OUT: per triangle seven int64: ms_column_box's lo[0], lo[1], hi[0], hi[1], then ms_tiles' per[0],
+//                                       per[1] and its count
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -106,12 +109,35 @@ static int run_fill(FILE* in, FILE* out) {
     return 0;
 }
 
+// the culling, which run_fill never calls: ms_column_box and ms_tiles per triangle, given in grid coordinates
+static int run_cull(FILE* in, FILE* out) {
+    int64_t count[3];
+    double res = 0.0;
+    if (fread(count, 8, 3, in) != 3 || fread(&res, 8, 1, in) != 1 || count[0] < 0) return 4;
+    std::vector<double> grid((size_t)count[0] * 9);
+    if (count[0] && fread(grid.data(), 8, grid.size(), in) != grid.size()) return 4;
+    MeshArgs a{};
+    a.res = res; a.half = res * 0.5;
+    a.nx = count[1]; a.ny = count[2];
+    std::vector<int64_t> rows((size_t)count[0] * 7);
+    for (int64_t j = 0; j < count[0]; ++j) {
+        double G[3][3];
+        std::memcpy(G, &grid[9 * j], sizeof G);
+        int64_t* r = &rows[7 * j];
+        ms_column_box(a, G, r, r + 2);
+        r[6] = ms_tiles(r, r + 2, r + 4);
+    }
+    if (!rows.empty()) fwrite(rows.data(), 8, rows.size(), out);
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc != 4) return 2;
     FILE* in = fopen(argv[2], "rb");
     FILE* out = fopen(argv[3], "wb");
     if (!in || !out) return 3;
-    const int rc = std::strcmp(argv[1], "orient") == 0 ? run_orient(in, out) : std::strcmp(argv[1], "fill") == 0 ? run_fill(in, out) : 2;
+    const int rc = std::strcmp(argv[1], "orient") == 0 ? run_orient(in, out) : std::strcmp(argv[1], "fill") == 0 ? run_fill(in, out)
+                   : std::strcmp(argv[1], "cull") == 0 ? run_cull(in, out) : 2;
     fclose(in);
     fclose(out);
     return rc;

@@ -9,7 +9,9 @@ Fraction directly in test_mesh_solid_cpu.py).
 What is NOT restated is the culling (ms_column_box).  A triangle is evaluated at the columns whose centres lie in the closed
 bounding rectangle of its grid vertices: a centre strictly outside it is covered under no tie rule.
 
-restated() returns the byte mask, the smallest-id field and the packed bit field, as mesh_raster_restated.restated does."""
+restated() returns the byte mask, the smallest-id field and the packed bit field, as mesh_raster_restated.restated does.
+toggles_of() gives one mesh's crossings per cell for chosen columns, parity_of() and inside_at_columns() their prefix parity: over
+the whole grid, and over a window of columns of a grid too large to enumerate."""
 from fractions import Fraction
 
 import numpy as np
@@ -85,8 +87,9 @@ def crossing(G, C):
     return covered, np.where(z <= zmax, z, zmax)
 
 
-def parity_of(W, origin, res, shape):
-    """the cells inside ONE mesh with world triangles W [n, 3, 3] by the even-odd rule: bool [nx, ny, nz]"""
+def toggles_of(W, origin, res, shape, xs=None, ys=None):
+    """the crossings of ONE mesh with world triangles W [n, 3, 3], counted at the first cell above each: int64 [len(xs), len(ys), nz + 1]
+    for the columns xs x ys (index arrays; default: every column).  Entry nz counts the crossings above the last centre."""
     nx, ny, nz = shape
     inv = inverse(origin)
     if inv is None:
@@ -94,18 +97,31 @@ def parity_of(W, origin, res, shape):
     G = grid_vertices(inv, origin, W)
     if not np.isfinite(G).all():
         raise ValueError("a mesh is refused")
-    cx, cy, cz = (res * (np.arange(k, dtype=np.float64) + 0.5) for k in (nx, ny, nz))
-    toggles = np.zeros((nx, ny, nz + 1), np.int64)
+    xs = np.arange(nx, dtype=np.int64) if xs is None else np.asarray(xs, np.int64).reshape(-1)
+    ys = np.arange(ny, dtype=np.int64) if ys is None else np.asarray(ys, np.int64).reshape(-1)
+    cx, cy = res * (xs.astype(np.float64) + 0.5), res * (ys.astype(np.float64) + 0.5)
+    cz = res * (np.arange(nz, dtype=np.float64) + 0.5)
+    toggles = np.zeros((len(xs), len(ys), nz + 1), np.int64)
     for g in G:
-        xs = np.flatnonzero((cx >= g[:, 0].min()) & (cx <= g[:, 0].max()))
-        ys = np.flatnonzero((cy >= g[:, 1].min()) & (cy <= g[:, 1].max()))
-        if not len(xs) or not len(ys):
+        ix = np.flatnonzero((cx >= g[:, 0].min()) & (cx <= g[:, 0].max()))
+        iy = np.flatnonzero((cy >= g[:, 1].min()) & (cy <= g[:, 1].max()))
+        if not len(ix) or not len(iy):
             continue
-        X, Y = (a.reshape(-1) for a in np.meshgrid(xs, ys, indexing="ij"))
+        X, Y = (a.reshape(-1) for a in np.meshgrid(ix, iy, indexing="ij"))
         covered, zc = crossing([[float(v) for v in row] for row in g], np.stack([cx[X], cy[Y]], 1))
         cell = np.searchsorted(cz, zc[covered], side="right")                # the number of centres <= z_c: the first one above
         np.add.at(toggles, (X[covered], Y[covered], cell), 1)
-    return (np.cumsum(toggles[:, :, :nz], axis=2) & 1).astype(bool)
+    return toggles
+
+
+def inside_at_columns(W, origin, res, shape, xs, ys):
+    """parity_of for a window of columns with full z: bool [len(xs), len(ys), nz] (a grid too large to enumerate)"""
+    return (np.cumsum(toggles_of(W, origin, res, shape, xs, ys)[:, :, :shape[2]], axis=2) & 1).astype(bool)
+
+
+def parity_of(W, origin, res, shape):
+    """the cells inside ONE mesh with world triangles W [n, 3, 3] by the even-odd rule: bool [nx, ny, nz]"""
+    return (np.cumsum(toggles_of(W, origin, res, shape)[:, :, :shape[2]], axis=2) & 1).astype(bool)
 
 
 def restated(meshes, vertices, triangles, origin, res, shape, onto=None):

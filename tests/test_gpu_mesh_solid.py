@@ -1,8 +1,18 @@
 """GPU: sdfgpu_rasterize_solid_meshes[_device] against the numpy restatement (mesh_solid_restated.py), bit for bit in bits, mask and ids.
 
   - every scene of mesh_solid_cases.py through both forms; the centre voxel of a closed cube is filled
-  - grids chosen as the smallest at which each mechanism can break: 1 x 1 x 1; nz = 1; one bit in a second word; an odd nz (columns
-    start at every bit offset, the carry crosses words); 16 x 16 column-tile edges; more than 64 words per column (the chunk carry)
+  - grids chosen as the smallest at which each mechanism can break (mesh_solid_cases.GRIDS): 1 x 1 x 1 (every index 0); 3 x 2 x 1
+    (nz = 1: six columns in one word of the field); 5 x 4 x 33 (one bit in a second word: the word carry, a full lane group of 2, a
+    spill word); 7 x 6 x 67 (an odd nz: columns start at every bit offset; a lane group with an idle lane); 17 x 33 x 40 (the edges of
+    the 16 x 16 column tiles); 16 x 16 x 2100 (more than 64 words per column: the chunk carry, always 1 there)
+  - mesh_solid_cases.stack_scene on 12 x 6 x nz for nz = 32 .. 4128: every lane-group size of the merge (1 .. 64), exactly full and one
+    word over; nz % 32 == 0 (no tail mask, no shift, no spill word) and not; one, two and three chunks, the last a single word; at
+    every boundary a column whose parity is 1 across it and one whose parity is 0 after earlier toggles; a column that is inside
+    where it ends.  test_mesh_solid_cpu.py shows on a word-level model that each of these grids tells a merge without its word
+    carry, chunk carry, tail mask, spill word or word before a chunk from the truth, wherever that step can act
+  - mesh_solid_cases.slot_scene: 1328 triangles in one call -- slots past a scan block of 1024, empty meshes beside others, meshes
+    and slots with zero column tiles between slots with some, 25 tiles in a slot (chunks of 16 end inside it), unused trailing
+    triangles, two records on one triangle run -- also shuffled; two stack grids back to back on one handle (another row length)
   - shuffled triangle and mesh order; accumulate 0 and 1 onto a pre-filled field; refusals; the toggle field zero after every call
     (two scenes back to back on one handle against fresh handles); a non-blocking side stream with late inputs; red zones
   - a generic-pose box as 12 solid triangles equals the same box as SDFGPU_SHAPE_BOX; the surface call's bits are a subset"""
@@ -28,7 +38,8 @@ pytestmark = pytest.mark.gpu
 CASES = SC.cases()
 DYADIC = SC.dyadic_cases()
 SENTINEL, GUARD = 0xA5, 64
-GRIDS = [(1, 1, 1), (3, 2, 1), (5, 4, 33), (7, 6, 67), (17, 33, 40), (16, 16, 2100)]
+GRIDS = SC.GRIDS                                                               # (mesh_solid_cases.py says which mechanism each is the smallest for)
+STACK_IDS = ["x".join(map(str, g)) for g in SC.STACK_GRIDS]
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -106,19 +117,7 @@ def _want(name):
     return S.restated(*(CASES.get(name) or DYADIC[name]))
 
 
-def grid_scene(grid, res=SC.RES):
-    """three closed meshes sized to the grid: a stretched icosahedron (on the tallest grid a grid-aligned box) along its whole height and
-    out of both ends, a box in a generic pose, a torus through the top face"""
-    origin = SC.MC.origins()["translation" if grid[2] > 1000 else "general"]
-    ext = np.asarray(grid, np.float64) * res
-    v, t = SC.icosahedron(1.0)
-    long = (2, v * np.array([0.45 * ext[0] + res, 0.4 * ext[1] + res, 0.6 * ext[2]]), t, origin @ SC._local((0.999, 0.02, -0.03, 0.01), 0.5 * ext))
-    if grid[2] > 1000:                                                         # (thin world boxes per triangle keep the restatement quick: no rotation)
-        long = (2, *SC.box_triangles((0.5 * ext[0] + 0.37 * res, 0.45 * ext[1] + 0.21 * res, 1.2 * ext[2])),
-                origin @ SC._local(SC.IDENT_Q, 0.5 * ext + np.array([0.13, -0.08, 0.0]) * res))
-    box = (1, *SC.box_triangles(np.minimum(0.6 * ext + res, 9.3 * res)), origin @ SC._local(SC.GENERIC_Q, ext * np.array([0.4, 0.55, 0.3])))
-    tor = (3, *SC.torus(3.1 * res, 1.4 * res), origin @ SC._local((0.9, 0.3, -0.2, 0.1), ext * np.array([0.55, 0.5, 1.0])))
-    return capi.make_meshes([long, box, tor]) + (origin, res, grid)
+grid_scene = SC.grid_scene                                                     # (shared with test_mesh_solid_cpu.py, which puts the word model on it)
 
 
 # ---- scenes and grids ------------------------------------------------------------------------------------------------------------------
@@ -148,6 +147,71 @@ def test_grids_at_which_a_mechanism_can_break(gpu, grid):
     _check_all(gpu, "grid %s" % (grid,), scene, want, host=grid != GRIDS[-1])
     d_bits, _, _, _ = _device(gpu, *scene, mask=False, ids=False, solid=False)
     assert not (d_bits & ~want[2]).any(), "the surface call's bits are a subset of the solid call's"
+
+
+@functools.lru_cache(maxsize=None)
+def _want_stack(grid):
+    return S.restated(*SC.stack_scene(grid))
+
+
+@functools.lru_cache(maxsize=None)
+def _want_slot(variant):
+    return S.restated(*SC.slot_scene(variant))
+
+
+@pytest.mark.parametrize("grid", SC.STACK_GRIDS, ids=STACK_IDS)
+def test_the_stack_scene_at_every_lane_group_word_and_chunk_boundary(gpu, grid):
+    """test_mesh_solid_cpu.py shows that a merge without its word carry, chunk carry, tail mask, spill word or word before a chunk
+    gives other bits than these on every grid on which that step can act"""
+    _check_all(gpu, "stack %s" % (grid,), SC.stack_scene(grid), _want_stack(grid), host=grid[2] <= 1030)
+
+
+@pytest.mark.parametrize("variant", SC.SLOT_VARIANTS)
+def test_the_slot_scene_against_the_work_distribution(gpu, variant):
+    _check_all(gpu, "slots (%s)" % variant, SC.slot_scene(variant), _want_slot(variant))
+
+
+def _shuffled(scene, rng):
+    """the records in another order, every mesh's triangle rows in another order"""
+    meshes, vertices, triangles = scene[:3]
+    items = []
+    for m in meshes[rng.permutation(len(meshes))]:
+        ft, nt, fv, nv = (int(m[k]) for k in ("first_triangle", "n_triangles", "first_vertex", "n_vertices"))
+        items.append((int(m["object_id"]), vertices[fv:fv + nv], triangles[ft:ft + nt][rng.permutation(nt)], np.asarray(m["pose"]).reshape(4, 4)))
+    return capi.make_meshes(items) + scene[3:]
+
+
+def test_the_slot_scene_with_mesh_and_triangle_order_shuffled(gpu):
+    scene = SC.slot_scene("trailing")
+    rng = np.random.default_rng(6)
+    for _ in range(2):
+        other = _shuffled(scene, rng)
+        assert [int(m["n_triangles"]) for m in other[0]] != [int(m["n_triangles"]) for m in scene[0]]
+        d_bits, d_mask, d_ids, _ = _device(gpu, *other)
+        mask, ids, bits = _want_slot("trailing")
+        _equal("shuffled slots bits", d_bits, bits)
+        _equal("shuffled slots mask", d_mask, mask)
+        _equal("shuffled slots ids", d_ids, ids)
+
+
+def test_two_stack_grids_back_to_back_reuse_the_toggle_field_with_another_row_length():
+    """one handle, grids of wz = 66, 3, 17 and 66 again: the toggle field is kept, laid out anew per call, and must be all zero whatever
+    the row length of the call before; each result against a fresh handle's and against the restatement"""
+    grids = [(12, 6, 2081), (12, 6, 96), (12, 6, 530)]
+    fresh = []
+    for grid in grids:
+        ctx = capi.SdfGpu(0)
+        fresh.append(_device(ctx, *SC.stack_scene(grid)))
+        ctx.close()
+    ctx = capi.SdfGpu(0)
+    try:
+        for k in (0, 1, 2, 0, 2, 1):
+            got = _device(ctx, *SC.stack_scene(grids[k]))
+            for j, what in enumerate(("bits", "mask", "ids")):
+                _equal("%s after another grid: %s" % (grids[k], what), got[j], fresh[k][j])
+            _equal("%s bits" % (grids[k],), got[0], _want_stack(grids[k])[2])
+    finally:
+        ctx.close()
 
 
 def test_triangle_and_mesh_order_play_no_part(gpu):
@@ -329,6 +393,8 @@ def core_cases_on(ctx):
         _check_all(ctx, name + " (red zones)", CASES[name], _want(name))
     scene = grid_scene((7, 6, 67))
     _check_all(ctx, "7x6x67 (red zones)", scene, S.restated(*scene))
+    _check_all(ctx, "stack 12x6x2081 (red zones)", SC.stack_scene((12, 6, 2081)), _want_stack((12, 6, 2081)), host=False)
+    _check_all(ctx, "slots (red zones)", SC.slot_scene(), _want_slot("trailing"))
 
 
 def test_the_core_cases_in_a_child_process_with_red_zones_from_the_environment():

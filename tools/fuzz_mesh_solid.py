@@ -2,7 +2,8 @@
 """Differential fuzz of the solid mesh fill: random closed meshes (tests/mesh_solid_cases.random_closed_meshes: randomly posed
 icosahedra, tori and boxes, randomly subdivided, with random flips, some as soups), grids, origins and resolutions on ONE red-zoned
 handle, through the device form with and without accumulation onto a random field, and through the host form, every bit, byte and
-id against the numpy restatement (tests/mesh_solid_restated.py).
+id against the numpy restatement (tests/mesh_solid_restated.py).  run(generator=...) takes the scenes from the caller instead
+(tests/test_gpu_fuzz_mesh_solid.py: mesh_solid_cases.random_tall_scene).
 usage: fuzz_mesh_solid.py [seconds] [seed]     prints "fuzz OK: N scenes ..." and exits 0, or raises at the first mismatch"""
 import os
 import sys
@@ -37,16 +38,24 @@ def upload(a):
     return d
 
 
-def run(seconds, seed, least=50):
-    """(scenes, filled cells, cells filled by parity alone); raises AssertionError at the first mismatch"""
+def run(seconds, seed, least=50, generator=None):
+    """(scenes, filled cells, cells filled by parity alone); raises AssertionError at the first mismatch.  generator: an iterable of
+    scenes (mesh_solid_cases tuples) to run through instead of `seconds` of scene(rng); seed then only draws the fields accumulated onto"""
     rng = np.random.default_rng(seed)
     ctx = capi.SdfGpu(0)
     ctx.set_option("redzone", 1)
     stream = torch.cuda.current_stream().cuda_stream
     t0, scenes, filled, inside = time.time(), 0, 0, 0
+    given = iter(generator) if generator is not None else None
     try:
-        while time.time() - t0 < seconds or scenes < least:
-            meshes, vertices, triangles, origin, res, grid = scene(rng)
+        while given is not None or time.time() - t0 < seconds or scenes < least:
+            if given is not None:
+                try:
+                    meshes, vertices, triangles, origin, res, grid = next(given)
+                except StopIteration:
+                    break
+            else:
+                meshes, vertices, triangles, origin, res, grid = scene(rng)
             n = int(np.prod(grid))
             onto = None
             if rng.random() < 0.5:
