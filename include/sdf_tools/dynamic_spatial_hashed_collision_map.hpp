@@ -1,0 +1,330 @@
+// DynamicSpatialHashedCollisionMapGrid -- the reference's class of the same name (include/sdf_tools/dynamic_spatial_hashed_collision_map.hpp,
+// src/sdf_tools/dynamic_spatial_hashed_collision_map.cpp) over the device-resident map of include/sdfgpu.h "Dynamic spatial hashed map":
+// the reference's constructors and methods with their signatures, and batch forms beside them (SetCells, SetChunks, GetBatch,
+// InsertPointCloud, the window extractions), which are what the map is for -- one SetCell per call costs a kernel launch sequence.
+//
+// The reference keeps its cells in arc_utilities' DynamicSpatialHashedVoxelGrid, which this project has never seen: the contract
+// (location -> cell by floor, chunk states, what Get and the setters return) is this project's own, DESIGN.md section 29, UNVERIFIED
+// against that class.  So are the values of VoxelGrid::FOUND_STATUS / SET_STATUS below, and the place of a chunk's marker: the
+// reference asks the chunk for the location of its index (0, 0, 0); here the marker sits at the chunk's centre, where a cube of the
+// chunk's size covers the chunk.
+//
+// Uninitialised maps: the reference's default constructor leaves the underlying grid empty.  Here Get on such a map returns
+// (COLLISION_CELL(), NOT_FOUND), the setters return NOT_SET, the batch forms and extractions throw std::runtime_error and
+// ExportForDisplay returns no marker.  (The reference's two other constructors never set initialized_; here they do.)
+#pragma once
+#include <cstring>
+#include <memory>
+#include <mutex>
+#include <stdexcept>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "sdf_tools/collision_map.hpp"
+#include "sdf_tools/device_sdf.hpp"
+#include "sdf_tools/display.hpp"
+#include "sdf_tools/gpu_context.hpp"
+#include "sdfgpu.h"
+
+namespace VoxelGrid {
+enum FOUND_STATUS { NOT_FOUND = SDFGPU_DSH_NOT_FOUND, FOUND_IN_CHUNK = SDFGPU_DSH_FOUND_IN_CHUNK, FOUND_IN_CELL = SDFGPU_DSH_FOUND_IN_CELL };
+enum SET_STATUS { NOT_SET = SDFGPU_DSH_NOT_SET, SET_CHUNK = SDFGPU_DSH_SET_CHUNK, SET_CELL = SDFGPU_DSH_SET_CELL };
+}  // namespace VoxelGrid
+
+namespace sdf_tools {
+
+class DynamicSpatialHashedCollisionMapGrid {
+protected:
+    // the device map and the context it lives on (shared by copies of the grid: a copy is another name for the same map)
+    struct DeviceMap {
+        std::shared_ptr<sdf_generation::SharedGpuContext> ctx;
+        sdfgpu_dsh_map map = nullptr;
+        ~DeviceMap() {
+            if (!map) return;
+            const std::lock_guard<std::mutex> lock(ctx->mutex);
+            sdfgpu_dsh_destroy(map);
+        }
+    };
+    std::shared_ptr<DeviceMap> collision_field_;
+    Eigen::Isometry3d origin_transform_;
+    double resolution_ = 0.0;
+    int64_t chunk_sizes_[3] = {0, 0, 0};
+    COLLISION_CELL default_value_;
+    uint32_t number_of_components_;
+    std::string frame_;
+    bool initialized_;
+    bool components_valid_;
+
+    void Create(const uint64_t byte_limit) {
+        std::shared_ptr<DeviceMap> fresh = std::make_shared<DeviceMap>();
+        fresh->ctx = sdf_generation::GpuContext::Shared();
+        const Eigen::Isometry3d inverse = origin_transform_.inverse();
+        double inv16[16];
+        for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) inv16[4 * r + c] = inverse.matrix()(r, c);
+        const std::lock_guard<std::mutex> lock(fresh->ctx->mutex);
+        sdf_generation::ThrowOnStatus(fresh->ctx->handle, sdfgpu_dsh_create(fresh->ctx->handle, inv16, resolution_, chunk_sizes_[0], chunk_sizes_[1],
+                                                                            chunk_sizes_[2], &default_value_, 0, byte_limit, &fresh->map));
+        collision_field_ = std::move(fresh);
+        initialized_ = true;
+    }
+    void RequireInitialized() const {
+        if (!initialized_) throw std::runtime_error("DynamicSpatialHashedCollisionMapGrid is not initialized");
+    }
+    template <typename Call>
+    void Locked(Call call) const {
+        const std::lock_guard<std::mutex> lock(collision_field_->ctx->mutex);
+        sdf_generation::ThrowOnStatus(collision_field_->ctx->handle, call(collision_field_->map));
+    }
+
+public:
+    EIGEN_MAKE_ALIGNED_OPERATOR_NEW
+
+    DynamicSpatialHashedCollisionMapGrid(std::string frame, double resolution, int64_t chunk_x_size, int64_t chunk_y_size, int64_t chunk_z_size,
+                                         COLLISION_CELL OOB_value)
+        : DynamicSpatialHashedCollisionMapGrid(Eigen::Isometry3d::Identity(), std::move(frame), resolution, chunk_x_size, chunk_y_size, chunk_z_size, OOB_value) {}
+
+    DynamicSpatialHashedCollisionMapGrid(Eigen::Isometry3d origin_transform, std::string frame, double resolution, int64_t chunk_x_size,
+                                         int64_t chunk_y_size, int64_t chunk_z_size, COLLISION_CELL OOB_value, uint64_t byte_limit = 0)
+        : origin_transform_(origin_transform), resolution_(resolution), default_value_(OOB_value), number_of_components_(0), frame_(std::move(frame)),
+          initialized_(false), components_valid_(false) {
+        chunk_sizes_[0] = chunk_x_size; chunk_sizes_[1] = chunk_y_size; chunk_sizes_[2] = chunk_z_size;
+        Create(byte_limit);
+    }
+
+    DynamicSpatialHashedCollisionMapGrid() : number_of_components_(0), initialized_(false), components_valid_(false) {}
+
+    bool IsInitialized() const { return initialized_; }
+    bool AreComponentsValid() const { return components_valid_; }     // never true: no method of the reference computes them
+    std::string GetFrame() const { return frame_; }
+    double GetResolution() const { return resolution_; }
+    std::vector<double> GetCellSizes() const { return {resolution_, resolution_, resolution_}; }
+    std::vector<double> GetChunkSizes() const {
+        return {resolution_ * (double)chunk_sizes_[0], resolution_ * (double)chunk_sizes_[1], resolution_ * (double)chunk_sizes_[2]};
+    }
+    std::vector<int64_t> GetChunkNumCells() const { return {chunk_sizes_[0], chunk_sizes_[1], chunk_sizes_[2]}; }
+    COLLISION_CELL GetDefaultValue() const { return default_value_; }
+    Eigen::Isometry3d GetOriginTransform() const { return origin_transform_; }
+    // the C ABI's map, for callers of the *_device entry points (hold Context()->mutex around such calls)
+    sdfgpu_dsh_map DeviceMapHandle() const { return collision_field_ ? collision_field_->map : nullptr; }
+    std::shared_ptr<sdf_generation::SharedGpuContext> Context() const { return collision_field_ ? collision_field_->ctx : nullptr; }
+
+    // ---- the reference's accessors ----------------------------------------------------------------------------------------------------
+    std::pair<COLLISION_CELL, VoxelGrid::FOUND_STATUS> Get(const double x, const double y, const double z) const {
+        if (!initialized_) return std::make_pair(COLLISION_CELL(), VoxelGrid::NOT_FOUND);
+        const double location[3] = {x, y, z};
+        COLLISION_CELL cell;
+        uint8_t status = 0;
+        Locked([&](sdfgpu_dsh_map m) { return sdfgpu_dsh_get(m, location, 1, &cell, &status); });
+        return std::make_pair(cell, (VoxelGrid::FOUND_STATUS)status);
+    }
+    std::pair<COLLISION_CELL, VoxelGrid::FOUND_STATUS> Get(const Eigen::Vector3d& location) const { return Get(location.x(), location.y(), location.z()); }
+
+    VoxelGrid::SET_STATUS SetCell(const double x, const double y, const double z, COLLISION_CELL value) {
+        if (!initialized_) return VoxelGrid::NOT_SET;
+        const double location[3] = {x, y, z};
+        uint8_t status = 0;
+        Locked([&](sdfgpu_dsh_map m) { return sdfgpu_dsh_set_cells(m, location, 1, nullptr, &value, &status); });
+        if (status != VoxelGrid::NOT_SET) components_valid_ = false;
+        return (VoxelGrid::SET_STATUS)status;
+    }
+    VoxelGrid::SET_STATUS SetCell(const Eigen::Vector3d& location, COLLISION_CELL value) { return SetCell(location.x(), location.y(), location.z(), value); }
+
+    VoxelGrid::SET_STATUS SetChunk(const double x, const double y, const double z, COLLISION_CELL value) {
+        if (!initialized_) return VoxelGrid::NOT_SET;
+        const double location[3] = {x, y, z};
+        uint8_t status = 0;
+        Locked([&](sdfgpu_dsh_map m) { return sdfgpu_dsh_set_chunks(m, location, 1, nullptr, &value, &status); });
+        if (status != VoxelGrid::NOT_SET) components_valid_ = false;
+        return (VoxelGrid::SET_STATUS)status;
+    }
+    VoxelGrid::SET_STATUS SetChunk(const Eigen::Vector3d& location, COLLISION_CELL value) { return SetChunk(location.x(), location.y(), location.z(), value); }
+
+    // ---- batches (additions): as if applied one after the other in list order ------------------------------------------------------------
+    // locations_xyz: n x 3 doubles; values: one record for the whole batch, or one per location.  Returns the statuses.
+    std::vector<VoxelGrid::SET_STATUS> SetCells(const std::vector<double>& locations_xyz, const std::vector<COLLISION_CELL>& values) {
+        return SetBatch(false, locations_xyz, values);
+    }
+    std::vector<VoxelGrid::SET_STATUS> SetChunks(const std::vector<double>& locations_xyz, const std::vector<COLLISION_CELL>& values) {
+        return SetBatch(true, locations_xyz, values);
+    }
+    std::pair<std::vector<COLLISION_CELL>, std::vector<VoxelGrid::FOUND_STATUS>> GetBatch(const std::vector<double>& locations_xyz) const {
+        RequireInitialized();
+        if (locations_xyz.size() % 3) throw std::invalid_argument("GetBatch: locations are x, y, z triples");
+        const size_t n = locations_xyz.size() / 3;
+        std::vector<COLLISION_CELL> cells(n);
+        std::vector<uint8_t> raw(n);
+        if (n) Locked([&](sdfgpu_dsh_map m) { return sdfgpu_dsh_get(m, locations_xyz.data(), (int64_t)n, cells.data(), raw.data()); });
+        std::vector<VoxelGrid::FOUND_STATUS> statuses(n);
+        for (size_t i = 0; i < n; ++i) statuses[i] = (VoxelGrid::FOUND_STATUS)raw[i];
+        return std::make_pair(std::move(cells), std::move(statuses));
+    }
+    // A point cloud (n x 3 floats, as a depth camera delivers it) as cell sets of one value; returns how many points were set.
+    size_t InsertPointCloud(const std::vector<float>& points_xyz, const COLLISION_CELL value) {
+        RequireInitialized();
+        if (points_xyz.size() % 3) throw std::invalid_argument("InsertPointCloud: points are x, y, z triples");
+        const size_t n = points_xyz.size() / 3;
+        if (!n) return 0;
+        const std::lock_guard<std::mutex> lock(collision_field_->ctx->mutex);
+        sdfgpu_handle h = collision_field_->ctx->handle;
+        void* d_points = nullptr;
+        void* d_statuses = nullptr;
+        std::vector<uint8_t> statuses(n);
+        int rc = sdfgpu_device_malloc(h, n * 12, &d_points);
+        if (rc == SDFGPU_OK) rc = sdfgpu_device_malloc(h, n, &d_statuses);
+        if (rc == SDFGPU_OK) rc = sdfgpu_copy_from_host(h, d_points, points_xyz.data(), n * 12, nullptr);
+        if (rc == SDFGPU_OK) rc = sdfgpu_dsh_insert_points_device(collision_field_->map, static_cast<const float*>(d_points), (int64_t)n, &value,
+                                                                  static_cast<uint8_t*>(d_statuses), nullptr);
+        if (rc == SDFGPU_OK) rc = sdfgpu_copy_to_host(h, statuses.data(), d_statuses, n, nullptr);
+        const std::string message = rc == SDFGPU_OK ? "" : sdfgpu_last_error(h);
+        (void)sdfgpu_device_free(h, d_points);
+        (void)sdfgpu_device_free(h, d_statuses);
+        if (rc == SDFGPU_ERR_INVALID_ARGUMENT) throw std::invalid_argument("sdfgpu: " + message);
+        if (rc != SDFGPU_OK) throw std::runtime_error("sdfgpu: " + message);
+        size_t set = 0;
+        for (const uint8_t s : statuses) set += s != VoxelGrid::NOT_SET;
+        if (set) components_valid_ = false;
+        return set;
+    }
+
+    // ---- dense windows (additions) ------------------------------------------------------------------------------------------------------
+    // The nx x ny x nz cells from global cell lower_index on as a CollisionMapGrid: cell (x, y, z) is what Get returns there.  The
+    // result's origin is the map's origin times the translation to that corner; its OOB value is the map's default.
+    CollisionMapGrid ExtractCollisionMapGrid(const VoxelGrid::GRID_INDEX& lower_index, const int64_t nx, const int64_t ny, const int64_t nz) const {
+        RequireInitialized();
+        if (nx <= 0 || ny <= 0 || nz <= 0) throw std::invalid_argument("ExtractCollisionMapGrid: cell counts must be positive");
+        CollisionMapGrid grid(WindowOrigin(lower_index), frame_, resolution_, nx, ny, nz, default_value_);
+        const int64_t lower[3] = {lower_index.x, lower_index.y, lower_index.z};
+        Locked([&](sdfgpu_dsh_map m) { return sdfgpu_dsh_extract_window(m, lower, nx, ny, nz, 0, grid.GetMutableRawData().data(), nullptr); });
+        return grid;
+    }
+    // The SDF of a window, built from the window's bit field without a cell record leaving the device.
+    std::pair<DeviceSignedDistanceField, std::pair<double, double>> ExtractSignedDistanceFieldDevice(
+        const VoxelGrid::GRID_INDEX& lower_index, const int64_t nx, const int64_t ny, const int64_t nz, const float oob_value,
+        const bool unknown_is_filled, const bool add_virtual_border) const {
+        RequireInitialized();
+        DeviceSignedDistanceField sdf(WindowOrigin(lower_index), frame_, resolution_, nx, ny, nz, oob_value);
+        if (sdf.Context() != collision_field_->ctx) throw std::runtime_error("DynamicSpatialHashedCollisionMapGrid: the map lives on another thread's GPU context");
+        const int64_t lower[3] = {lower_index.x, lower_index.y, lower_index.z};
+        double max_distance = 0.0, min_distance = 0.0;
+        int rc = SDFGPU_OK;
+        std::string message;
+        {   // (the lock is released before anything is thrown: the field's destructor takes it)
+            const std::lock_guard<std::mutex> lock(collision_field_->ctx->mutex);
+            sdfgpu_handle h = collision_field_->ctx->handle;
+            void* d_bits = nullptr;
+            rc = sdfgpu_device_malloc(h, (size_t)((nx * ny * nz + 31) / 32) * 4, &d_bits);
+            if (rc == SDFGPU_OK) rc = sdfgpu_dsh_extract_window_device(collision_field_->map, lower, nx, ny, nz, unknown_is_filled ? 1 : 0, nullptr,
+                                                                       static_cast<uint32_t*>(d_bits), nullptr);
+            if (rc == SDFGPU_OK) rc = sdfgpu_build_bits_device(h, static_cast<const uint32_t*>(d_bits), nx, ny, nz, resolution_, add_virtual_border ? 1 : 0,
+                                                               sdf.DevicePointer(), nullptr);
+            if (rc == SDFGPU_OK) rc = sdfgpu_get_extrema(h, &max_distance, &min_distance);
+            if (rc != SDFGPU_OK) message = sdfgpu_last_error(h);
+            (void)sdfgpu_device_free(h, d_bits);
+        }
+        if (rc == SDFGPU_ERR_INVALID_ARGUMENT) throw std::invalid_argument("sdfgpu: " + message);
+        if (rc != SDFGPU_OK) throw std::runtime_error("sdfgpu: " + message);
+        sdf.SetExtrema(std::make_pair(max_distance, min_distance));
+        return std::make_pair(std::move(sdf), std::make_pair(max_distance, min_distance));
+    }
+    std::pair<SignedDistanceField, std::pair<double, double>> ExtractSignedDistanceField(
+        const VoxelGrid::GRID_INDEX& lower_index, const int64_t nx, const int64_t ny, const int64_t nz, const float oob_value,
+        const bool unknown_is_filled, const bool add_virtual_border) const {
+        std::pair<DeviceSignedDistanceField, std::pair<double, double>> device =
+            ExtractSignedDistanceFieldDevice(lower_index, nx, ny, nz, oob_value, unknown_is_filled, add_virtual_border);
+        return std::make_pair(device.first.Host(), device.second);
+    }
+
+    // ---- display (reference dynamic_spatial_hashed_collision_map.cpp:85-199) ---------------------------------------------------------------
+    // 0, 1 or 2 markers: the chunk-filled chunks as cubes of the chunk's size at their centres, then the cells of the cell-filled
+    // chunks as cubes of the cell's size; a marker without a point is left out.  Chunks in ascending (c_x, c_y, c_z) order (the
+    // reference's is its hash map's), cells x -> y -> z inside a chunk.
+    std::vector<visualization_msgs::Marker> ExportForDisplay(const std_msgs::ColorRGBA& collision_color, const std_msgs::ColorRGBA& free_color,
+                                                             const std_msgs::ColorRGBA& unknown_color) const {
+        std::vector<visualization_msgs::Marker> display_markers;
+        if (!initialized_) return display_markers;
+        std::vector<sdfgpu_dsh_chunk> chunks;
+        std::vector<COLLISION_CELL> cells;
+        Export(chunks, cells);
+        visualization_msgs::Marker chunks_display_rep =
+            display::MakeMarker(frame_, "dynamic_spatial_hashed_collision_map_chunks_display", Eigen::Isometry3d::Identity(), 1.0);
+        const std::vector<double> chunk_sizes = GetChunkSizes();
+        chunks_display_rep.scale.x = chunk_sizes[0]; chunks_display_rep.scale.y = chunk_sizes[1]; chunks_display_rep.scale.z = chunk_sizes[2];
+        visualization_msgs::Marker cells_display_rep =
+            display::MakeMarker(frame_, "dynamic_spatial_hashed_collision_map_cells_display", Eigen::Isometry3d::Identity(), resolution_);
+        const auto color_of = [&](const float occupancy) -> const std_msgs::ColorRGBA& {
+            return occupancy > 0.5 ? collision_color : occupancy < 0.5 ? free_color : unknown_color;
+        };
+        const auto point_of = [&](const double gx, const double gy, const double gz) {
+            const Eigen::Vector3d location = origin_transform_ * Eigen::Vector3d(gx, gy, gz);
+            geometry_msgs::Point p;
+            p.x = location.x(); p.y = location.y(); p.z = location.z();
+            return p;
+        };
+        for (const sdfgpu_dsh_chunk& chunk : chunks) {
+            const double base[3] = {(double)(chunk.c[0] * chunk_sizes_[0]), (double)(chunk.c[1] * chunk_sizes_[1]), (double)(chunk.c[2] * chunk_sizes_[2])};
+            if (chunk.state == SDFGPU_DSH_FOUND_IN_CHUNK) {
+                COLLISION_CELL cell;
+                std::memcpy(static_cast<void*>(&cell), &chunk.record, sizeof cell);
+                chunks_display_rep.points.push_back(point_of((base[0] + 0.5 * (double)chunk_sizes_[0]) * resolution_, (base[1] + 0.5 * (double)chunk_sizes_[1]) * resolution_,
+                                                             (base[2] + 0.5 * (double)chunk_sizes_[2]) * resolution_));
+                chunks_display_rep.colors.push_back(color_of(cell.occupancy));
+                continue;
+            }
+            const COLLISION_CELL* cell = cells.data() + chunk.first_cell;
+            for (int64_t x = 0; x < chunk_sizes_[0]; ++x)
+                for (int64_t y = 0; y < chunk_sizes_[1]; ++y)
+                    for (int64_t z = 0; z < chunk_sizes_[2]; ++z, ++cell) {
+                        cells_display_rep.points.push_back(point_of((base[0] + (double)x + 0.5) * resolution_, (base[1] + (double)y + 0.5) * resolution_,
+                                                                    (base[2] + (double)z + 0.5) * resolution_));
+                        cells_display_rep.colors.push_back(color_of(cell->occupancy));
+                    }
+        }
+        if (chunks_display_rep.points.size() > 0) display_markers.push_back(chunks_display_rep);
+        if (cells_display_rep.points.size() > 0) display_markers.push_back(cells_display_rep);
+        return display_markers;
+    }
+
+    // the live chunks in ascending (c_x, c_y, c_z) order and the cell-filled chunks' cells (sdfgpu_dsh_export)
+    void Export(std::vector<sdfgpu_dsh_chunk>& chunks, std::vector<COLLISION_CELL>& cells) const {
+        RequireInitialized();
+        int64_t n_chunks = 0, n_cells = 0;
+        Locked([&](sdfgpu_dsh_map m) { return sdfgpu_dsh_export(m, nullptr, 0, nullptr, 0, &n_chunks, &n_cells); });
+        chunks.assign((size_t)n_chunks, sdfgpu_dsh_chunk());
+        cells.assign((size_t)n_cells, COLLISION_CELL());
+        if (n_chunks) Locked([&](sdfgpu_dsh_map m) { return sdfgpu_dsh_export(m, chunks.data(), n_chunks, cells.data(), n_cells, &n_chunks, &n_cells); });
+    }
+    sdfgpu_dsh_counts GetCounts() const {
+        RequireInitialized();
+        sdfgpu_dsh_counts counts;
+        Locked([&](sdfgpu_dsh_map m) { return sdfgpu_dsh_info(m, &counts); });
+        return counts;
+    }
+
+private:
+    Eigen::Isometry3d WindowOrigin(const VoxelGrid::GRID_INDEX& lower_index) const {
+        Eigen::Isometry3d corner;
+        corner.setTranslation((double)lower_index.x * resolution_, (double)lower_index.y * resolution_, (double)lower_index.z * resolution_);
+        return origin_transform_ * corner;
+    }
+    std::vector<VoxelGrid::SET_STATUS> SetBatch(const bool chunk_sets, const std::vector<double>& locations_xyz, const std::vector<COLLISION_CELL>& values) {
+        RequireInitialized();
+        if (locations_xyz.size() % 3) throw std::invalid_argument("SetCells / SetChunks: locations are x, y, z triples");
+        const size_t n = locations_xyz.size() / 3;
+        const bool one = values.size() == 1;
+        if (!one && values.size() != n) throw std::invalid_argument("SetCells / SetChunks: one value, or one per location");
+        std::vector<uint8_t> raw(n);
+        if (n) Locked([&](sdfgpu_dsh_map m) {
+            return (chunk_sets ? sdfgpu_dsh_set_chunks : sdfgpu_dsh_set_cells)(m, locations_xyz.data(), (int64_t)n, one ? nullptr : values.data(),
+                                                                               one ? values.data() : nullptr, raw.data());
+        });
+        std::vector<VoxelGrid::SET_STATUS> statuses(n);
+        for (size_t i = 0; i < n; ++i) {
+            statuses[i] = (VoxelGrid::SET_STATUS)raw[i];
+            if (raw[i] != VoxelGrid::NOT_SET) components_valid_ = false;
+        }
+        return statuses;
+    }
+};
+
+}  // namespace sdf_tools

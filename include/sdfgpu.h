@@ -1021,6 +1021,110 @@ int sdfgpu_display_select_contour(sdfgpu_handle h, const void* cells, size_t cel
                                   int draw_zero, int grouped, uint32_t* out_indices, uint32_t* out_keys, int64_t capacity, int64_t* out_total,
                                   uint32_t* out_group_keys, uint32_t* out_group_offsets, int64_t group_capacity, int64_t* out_groups);
 
+/* ---------------------------------------------------------------------------
+ * Dynamic spatial hashed map: the device-resident counterpart of DynamicSpatialHashedCollisionMapGrid
+ * (reference include/sdf_tools/dynamic_spatial_hashed_collision_map.hpp), a sparse map of 8-byte COLLISION_CELL records
+ * that is hashed by chunk, outlives a frame and hands out dense windows as the bit field of sdfgpu_build_bits_device.
+ * DESIGN.md section 29 holds the contract (UNVERIFIED against arc_utilities' DynamicSpatialHashedVoxelGrid, which this
+ * project has never seen) and the kernels.  In short:
+ *   - location -> cell: g = inverse_origin * p in double (row a: ((m_a0 x + m_a1 y) + m_a2 z) + m_a3, no FMA), global cell
+ *     i_a = floor(g_a * (1 / cell_size)), chunk c_a = floor_div(i_a, n_a), local l_a = i_a - c_a n_a, cell slot
+ *     (l_x n_y + l_y) n_z + l_z
+ *   - a location is valid iff it is finite and every c_a lies in [-2^20, 2^20)
+ *   - a chunk is absent, chunk-filled (one record stands for all its cells) or cell-filled (one record per cell)
+ *   - Get: (default, NOT_FOUND) for an absent chunk or an invalid location, (chunk record, FOUND_IN_CHUNK),
+ *     (cell record, FOUND_IN_CELL)
+ *   - SetCell: an absent chunk becomes cell-filled with every cell the default, a chunk-filled one cell-filled with every cell
+ *     the chunk's record; then the cell is written (SET_CELL).  SetChunk: the chunk becomes chunk-filled with the value, its
+ *     cells are dropped (SET_CHUNK).  An invalid location changes nothing (NOT_SET).  Records move byte for byte.
+ *   - a batch (one kind: cell sets or chunk sets) leaves the map as if its operations had been applied one after the other in
+ *     list order (the last of several writes to one cell or chunk wins); values are one record for the whole batch (one_value,
+ *     host memory, 8 bytes) or one per operation (d_values / values, n records) -- exactly one of the two pointers is set
+ *
+ * A map is an object created on a handle; it owns its table and its chunk pool (device memory of the handle's device, inside
+ * red zones when the handle has them) and must be destroyed before the handle.  It grows by itself.  byte_limit (0 = none)
+ * bounds the bytes of table + pool: a batch (or a creation) that would pass it is refused with SDFGPU_ERR_UNSUPPORTED_SIZE and
+ * leaves the map's content as it was.  initial_chunks (0 = 64) sizes the first pool.  Errors go to the handle's
+ * sdfgpu_last_error.
+ *
+ * Streams: the _device forms run on the caller's stream.  The two setters and sdfgpu_dsh_insert_points_device synchronise that
+ * stream once (they read the number of new chunks back before the pool may grow), sdfgpu_dsh_info and the two export forms
+ * synchronise too (they read counts back); sdfgpu_dsh_get_device and sdfgpu_dsh_extract_window_device return with their kernels
+ * pending.  Calls on one map from different streams are ordered by the map (an event behind its last call); one host thread
+ * per map at a time.
+ * ------------------------------------------------------------------------- */
+typedef struct sdfgpu_dsh_map_object* sdfgpu_dsh_map;
+
+#define SDFGPU_DSH_NOT_FOUND 0
+#define SDFGPU_DSH_FOUND_IN_CHUNK 1
+#define SDFGPU_DSH_FOUND_IN_CELL 2
+#define SDFGPU_DSH_NOT_SET 0
+#define SDFGPU_DSH_SET_CHUNK 1
+#define SDFGPU_DSH_SET_CELL 2
+#define SDFGPU_DSH_MAX_CHUNK_CELLS 32768
+
+typedef struct sdfgpu_dsh_counts {
+    uint64_t chunk_filled;       /* live chunks by state */
+    uint64_t cell_filled;
+    uint64_t capacity_chunks;    /* chunks the pool holds before it grows */
+    uint64_t table_capacity;     /* entries of the hash table (a power of two, at least twice the live chunks) */
+    uint64_t bytes_held;         /* table + pool: what byte_limit bounds */
+    uint64_t scratch_bytes;      /* per-batch scratch and host-form staging kept between calls (not bounded by byte_limit) */
+    uint64_t byte_limit;
+} sdfgpu_dsh_counts;
+
+/* One live chunk as the export lists it (48 bytes). */
+typedef struct sdfgpu_dsh_chunk {
+    int64_t c[3];                /* chunk coordinate */
+    uint32_t state;              /* SDFGPU_DSH_FOUND_IN_CHUNK or SDFGPU_DSH_FOUND_IN_CELL */
+    uint32_t reserved;           /* 0 */
+    uint64_t record;             /* the chunk's record (chunk-filled); 0 for a cell-filled chunk */
+    int64_t first_cell;          /* cell-filled: where its n_x n_y n_z records start in the cell list (in records); else -1 */
+} sdfgpu_dsh_chunk;
+
+int sdfgpu_dsh_create(sdfgpu_handle h, const double inverse_origin[16], double cell_size, int64_t chunk_nx, int64_t chunk_ny,
+                      int64_t chunk_nz, const void* default_cell, int64_t initial_chunks, uint64_t byte_limit, sdfgpu_dsh_map* out_map);
+int sdfgpu_dsh_destroy(sdfgpu_dsh_map map);
+int sdfgpu_dsh_info(sdfgpu_dsh_map map, sdfgpu_dsh_counts* out_counts);
+
+/* Batches.  locations: n x 3 doubles (x, y, z interleaved); points: n x 3 floats as the streaming path holds them (widened to
+ * double, then the same arithmetic).  d_statuses / statuses (optional): one byte per operation, SDFGPU_DSH_SET_* or
+ * SDFGPU_DSH_NOT_SET; undefined when the call fails. */
+int sdfgpu_dsh_set_cells_device(sdfgpu_dsh_map map, const double* d_locations, int64_t n, const void* d_values, const void* one_value,
+                                uint8_t* d_statuses, void* stream);
+int sdfgpu_dsh_set_cells(sdfgpu_dsh_map map, const double* locations, int64_t n, const void* values, const void* one_value,
+                         uint8_t* statuses);
+int sdfgpu_dsh_set_chunks_device(sdfgpu_dsh_map map, const double* d_locations, int64_t n, const void* d_values, const void* one_value,
+                                 uint8_t* d_statuses, void* stream);
+int sdfgpu_dsh_set_chunks(sdfgpu_dsh_map map, const double* locations, int64_t n, const void* values, const void* one_value,
+                          uint8_t* statuses);
+int sdfgpu_dsh_insert_points_device(sdfgpu_dsh_map map, const float* d_points, int64_t n, const void* one_value, uint8_t* d_statuses,
+                                    void* stream);
+
+/* Get for n locations: 8-byte records and / or one status byte each (SDFGPU_DSH_NOT_FOUND / FOUND_IN_CHUNK / FOUND_IN_CELL);
+ * either output may be null, not both. */
+int sdfgpu_dsh_get_device(sdfgpu_dsh_map map, const double* d_locations, int64_t n, void* d_records, uint8_t* d_statuses, void* stream);
+int sdfgpu_dsh_get(sdfgpu_dsh_map map, const double* locations, int64_t n, void* records, uint8_t* statuses);
+
+/* A dense window: voxel (x, y, z) of an nx x ny x nz grid (at most 2^32 - 1 voxels) gets what Get returns at global cell
+ * lower[] + (x, y, z).  Outputs, either or both: the 8-byte records in x -> y -> z order, and the bit field of
+ * sdfgpu_build_bits_device under the CollisionMapGrid predicate (occupancy > 0.5f || (unknown_is_filled && occupancy == 0.5f)),
+ * ceil(nx ny nz / 32) words, each written whole by one owner (bits behind the last voxel are 0): the caller clears nothing.
+ * A global cell whose chunk coordinate is out of range reads as the default. */
+int sdfgpu_dsh_extract_window_device(sdfgpu_dsh_map map, const int64_t lower[3], int64_t nx, int64_t ny, int64_t nz, int unknown_is_filled,
+                                     void* d_records, uint32_t* d_bits, void* stream);
+int sdfgpu_dsh_extract_window(sdfgpu_dsh_map map, const int64_t lower[3], int64_t nx, int64_t ny, int64_t nz, int unknown_is_filled,
+                              void* records, uint32_t* bits);
+
+/* The whole map: the live chunks in ascending (c_x, c_y, c_z) order as sdfgpu_dsh_chunk records, and the cell-filled chunks'
+ * cells (x -> y -> z inside a chunk) in the same order.  chunk_capacity is in chunks, cell_capacity in records; the totals
+ * always go to out_chunks / out_cells (either may be null), and a list whose capacity is too small is not written (nor is
+ * the other), which is not an error: call once with capacities 0 to size the buffers, or use sdfgpu_dsh_info. */
+int sdfgpu_dsh_export_device(sdfgpu_dsh_map map, sdfgpu_dsh_chunk* d_chunks, int64_t chunk_capacity, void* d_cells, int64_t cell_capacity,
+                             int64_t* out_chunks, int64_t* out_cells, void* stream);
+int sdfgpu_dsh_export(sdfgpu_dsh_map map, sdfgpu_dsh_chunk* chunks, int64_t chunk_capacity, void* cells, int64_t cell_capacity,
+                      int64_t* out_chunks, int64_t* out_cells);
+
 /* Red zones (round 6).  With SDFGPU_REDZONE=1 in the environment when sdfgpu_create runs -- or after
  * sdfgpu_set_option(h, "redzone", 1) -- every device allocation of the library (scratch fields, status block, extrema slots,
  * staging buffers, sdfgpu_device_malloc memory) carries 4 KiB of canary bytes in front and behind, and every entry point that

@@ -43,6 +43,10 @@ EXPORTS = [
     "sdfgpu_rasterize_shapes_device", "sdfgpu_rasterize_shapes",
     "sdfgpu_rasterize_meshes_device", "sdfgpu_rasterize_meshes",
     "sdfgpu_rasterize_solid_meshes_device", "sdfgpu_rasterize_solid_meshes", "sdfgpu_check_closed_meshes",
+    "sdfgpu_dsh_create", "sdfgpu_dsh_destroy", "sdfgpu_dsh_info",
+    "sdfgpu_dsh_set_cells_device", "sdfgpu_dsh_set_cells", "sdfgpu_dsh_set_chunks_device", "sdfgpu_dsh_set_chunks",
+    "sdfgpu_dsh_insert_points_device", "sdfgpu_dsh_get_device", "sdfgpu_dsh_get",
+    "sdfgpu_dsh_extract_window_device", "sdfgpu_dsh_extract_window", "sdfgpu_dsh_export_device", "sdfgpu_dsh_export",
 ]
 
 # include/sdfgpu.h "Projection": modes and per-point statuses
@@ -189,6 +193,20 @@ def load_library():
     L.sdfgpu_build_tagged_objects.argtypes = [vp, vp, sz, sz, sz, vp, i64, ci, i64, i64, i64, dbl, ci, vp, vp, vp]
     L.sdfgpu_gradient_batch_device.argtypes = [vp, vp, i64, i64, i64, i64, dbl, vp, ci, ci, vp, vp]
     L.sdfgpu_last_batch_info.argtypes = [vp, vp, vp]
+    L.sdfgpu_dsh_create.argtypes = [vp, vp, dbl, i64, i64, i64, vp, i64, ctypes.c_uint64, ctypes.POINTER(vp)]
+    L.sdfgpu_dsh_destroy.argtypes = [vp]
+    L.sdfgpu_dsh_info.argtypes = [vp, vp]
+    L.sdfgpu_dsh_set_cells_device.argtypes = [vp, vp, i64, vp, vp, vp, vp]
+    L.sdfgpu_dsh_set_cells.argtypes = [vp, vp, i64, vp, vp, vp]
+    L.sdfgpu_dsh_set_chunks_device.argtypes = L.sdfgpu_dsh_set_cells_device.argtypes
+    L.sdfgpu_dsh_set_chunks.argtypes = L.sdfgpu_dsh_set_cells.argtypes
+    L.sdfgpu_dsh_insert_points_device.argtypes = [vp, vp, i64, vp, vp, vp]
+    L.sdfgpu_dsh_get_device.argtypes = [vp, vp, i64, vp, vp, vp]
+    L.sdfgpu_dsh_get.argtypes = [vp, vp, i64, vp, vp]
+    L.sdfgpu_dsh_extract_window_device.argtypes = [vp, vp, i64, i64, i64, ci, vp, vp, vp]
+    L.sdfgpu_dsh_extract_window.argtypes = [vp, vp, i64, i64, i64, ci, vp, vp]
+    L.sdfgpu_dsh_export_device.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp]
+    L.sdfgpu_dsh_export.argtypes = [vp, vp, i64, vp, i64, vp, vp]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is ctypes.c_int or name not in ("sdfgpu_version", "sdfgpu_last_error"):
@@ -1306,6 +1324,142 @@ class SdfGpu:
 
     def set_tuning(self, rows_per_chunk_y=0, rows_per_chunk_x=0):
         self._check(self._lib.sdfgpu_set_tuning(self._h, int(rows_per_chunk_y), int(rows_per_chunk_x)))
+
+    def dsh_create(self, inverse_origin=None, cell_size=1.0, chunk_dims=(16, 16, 16), default_cell=0, initial_chunks=0, byte_limit=0):
+        """A DshMap on this context (close it before the context)."""
+        return DshMap(self, inverse_origin, cell_size, chunk_dims, default_cell, initial_chunks, byte_limit)
+
+
+# ---- include/sdfgpu.h "Dynamic spatial hashed map" ------------------------------------------------------------------
+DSH_NOT_FOUND, DSH_FOUND_IN_CHUNK, DSH_FOUND_IN_CELL = 0, 1, 2
+DSH_NOT_SET, DSH_SET_CHUNK, DSH_SET_CELL = 0, 1, 2
+DSH_MAX_CHUNK_CELLS = 32768
+DSH_COUNTS_DTYPE = np.dtype([(n, np.uint64) for n in ("chunk_filled", "cell_filled", "capacity_chunks", "table_capacity", "bytes_held",
+                                                      "scratch_bytes", "byte_limit")])
+DSH_CHUNK_DTYPE = np.dtype([("c", np.int64, (3,)), ("state", np.uint32), ("reserved", np.uint32), ("record", np.uint64),
+                            ("first_cell", np.int64)])
+
+
+def dsh_record(occupancy, component=0):
+    """A COLLISION_CELL {float occupancy; uint32 component} as the uint64 the map moves (little endian: occupancy in the low word)."""
+    return int(np.array([occupancy], np.float32).view(np.uint32)[0]) | (int(component) & 0xFFFFFFFF) << 32
+
+
+class DshMap:
+    """One sparse map on a context's GPU (wraps sdfgpu_dsh_create / sdfgpu_dsh_destroy).  Records are uint64 (dsh_record);
+    locations are [n, 3] float64; device pointers are integers."""
+
+    def __init__(self, ctx, inverse_origin=None, cell_size=1.0, chunk_dims=(16, 16, 16), default_cell=0, initial_chunks=0, byte_limit=0):
+        self._ctx, self._lib = ctx, ctx._lib
+        inv = np.eye(4) if inverse_origin is None else np.ascontiguousarray(inverse_origin, dtype=np.float64).reshape(4, 4)
+        m = ctypes.c_void_p()
+        default = np.array([default_cell], np.uint64)
+        ctx._check(self._lib.sdfgpu_dsh_create(ctx._h, inv.ctypes.data, float(cell_size), *(int(d) for d in chunk_dims), default.ctypes.data,
+                                               int(initial_chunks), int(byte_limit), ctypes.byref(m)))
+        self._m = m
+        self.chunk_dims = tuple(int(d) for d in chunk_dims)
+        self.cells_per_chunk = int(np.prod(self.chunk_dims))
+
+    def close(self):
+        if getattr(self, "_m", None) and getattr(self._ctx, "_h", None):
+            self._lib.sdfgpu_dsh_destroy(self._m)
+        self._m = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc):
+        self._ctx._check(rc)
+
+    def info(self):
+        out = np.zeros(1, DSH_COUNTS_DTYPE)
+        self._check(self._lib.sdfgpu_dsh_info(self._m, out.ctypes.data))
+        return {k: int(out[0][k]) for k in DSH_COUNTS_DTYPE.names}
+
+    @staticmethod
+    def _values(value, n):
+        """(values array or None, one-value array or None): a scalar is the batch's one record"""
+        if np.ndim(value) == 0:
+            return None, np.array([value], np.uint64)
+        v = np.ascontiguousarray(value, dtype=np.uint64).reshape(-1)
+        if v.size != n:
+            raise ValueError("one value per operation (or a scalar)")
+        return v, None
+
+    def _set(self, call, locations, value, statuses):
+        loc = np.ascontiguousarray(locations, dtype=np.float64).reshape(-1, 3)
+        values, one = self._values(value, len(loc))
+        st = np.zeros(len(loc), np.uint8) if statuses else None
+        self._check(call(self._m, loc.ctypes.data, len(loc), None if values is None else values.ctypes.data, None if one is None else one.ctypes.data,
+                         None if st is None else st.ctypes.data))
+        return st
+
+    def set_cells(self, locations, value, statuses=True):
+        return self._set(self._lib.sdfgpu_dsh_set_cells, locations, value, statuses)
+
+    def set_chunks(self, locations, value, statuses=True):
+        return self._set(self._lib.sdfgpu_dsh_set_chunks, locations, value, statuses)
+
+    def _set_device(self, call, d_locations, n, d_values, one_value, d_statuses, stream):
+        one = None if one_value is None else np.array([one_value], np.uint64)
+        self._check(call(self._m, d_locations, int(n), d_values or None, None if one is None else one.ctypes.data, d_statuses or None, stream or None))
+
+    def set_cells_device(self, d_locations, n, d_values=0, one_value=None, d_statuses=0, stream=0):
+        self._set_device(self._lib.sdfgpu_dsh_set_cells_device, d_locations, n, d_values, one_value, d_statuses, stream)
+
+    def set_chunks_device(self, d_locations, n, d_values=0, one_value=None, d_statuses=0, stream=0):
+        self._set_device(self._lib.sdfgpu_dsh_set_chunks_device, d_locations, n, d_values, one_value, d_statuses, stream)
+
+    def insert_points_device(self, d_points, n, one_value, d_statuses=0, stream=0):
+        one = np.array([one_value], np.uint64)
+        self._check(self._lib.sdfgpu_dsh_insert_points_device(self._m, d_points, int(n), one.ctypes.data, d_statuses or None, stream or None))
+
+    def get(self, locations):
+        """(records uint64 [n], statuses uint8 [n])"""
+        loc = np.ascontiguousarray(locations, dtype=np.float64).reshape(-1, 3)
+        rec, st = np.zeros(len(loc), np.uint64), np.zeros(len(loc), np.uint8)
+        self._check(self._lib.sdfgpu_dsh_get(self._m, loc.ctypes.data, len(loc), rec.ctypes.data, st.ctypes.data))
+        return rec, st
+
+    def get_device(self, d_locations, n, d_records=0, d_statuses=0, stream=0):
+        self._check(self._lib.sdfgpu_dsh_get_device(self._m, d_locations, int(n), d_records or None, d_statuses or None, stream or None))
+
+    def extract_window(self, lower, shape, unknown_is_filled=False, records=True, bits=True):
+        """(records uint64 [nx, ny, nz] or None, bits uint32 [ceil(n / 32)] or None)"""
+        lo = np.ascontiguousarray(lower, dtype=np.int64).reshape(3)
+        nx, ny, nz = (int(s) for s in shape)
+        n = nx * ny * nz
+        rec = np.zeros(max(n, 0), np.uint64) if records else None
+        bit = np.zeros(max((n + 31) // 32, 0), np.uint32) if bits else None
+        self._check(self._lib.sdfgpu_dsh_extract_window(self._m, lo.ctypes.data, nx, ny, nz, int(bool(unknown_is_filled)),
+                                                        None if rec is None else rec.ctypes.data, None if bit is None else bit.ctypes.data))
+        return (None if rec is None else rec.reshape(nx, ny, nz)), bit
+
+    def extract_window_device(self, lower, shape, unknown_is_filled=False, d_records=0, d_bits=0, stream=0):
+        lo = np.ascontiguousarray(lower, dtype=np.int64).reshape(3)
+        nx, ny, nz = (int(s) for s in shape)
+        self._check(self._lib.sdfgpu_dsh_extract_window_device(self._m, lo.ctypes.data, nx, ny, nz, int(bool(unknown_is_filled)), d_records or None,
+                                                               d_bits or None, stream or None))
+
+    def export(self):
+        """(chunks DSH_CHUNK_DTYPE [n] in ascending (c_x, c_y, c_z) order, cells uint64 [cell-filled chunks, n_x, n_y, n_z])"""
+        nc, ncell = ctypes.c_int64(), ctypes.c_int64()
+        self._check(self._lib.sdfgpu_dsh_export(self._m, None, 0, None, 0, ctypes.byref(nc), ctypes.byref(ncell)))
+        chunks, cells = np.zeros(nc.value, DSH_CHUNK_DTYPE), np.zeros(ncell.value, np.uint64)
+        if nc.value:
+            self._check(self._lib.sdfgpu_dsh_export(self._m, chunks.ctypes.data, nc.value, cells.ctypes.data, ncell.value, ctypes.byref(nc), ctypes.byref(ncell)))
+            assert nc.value == len(chunks) and ncell.value == len(cells)
+        return chunks, cells.reshape((-1,) + self.chunk_dims)
+
+    def export_device(self, d_chunks, chunk_capacity, d_cells, cell_capacity, stream=0):
+        """(chunks, cell records) the map holds; the lists are written iff both capacities suffice"""
+        nc, ncell = ctypes.c_int64(), ctypes.c_int64()
+        self._check(self._lib.sdfgpu_dsh_export_device(self._m, d_chunks or None, int(chunk_capacity), d_cells or None, int(cell_capacity), ctypes.byref(nc),
+                                                       ctypes.byref(ncell), stream or None))
+        return nc.value, ncell.value
 
 
 # ---- multi-GPU C ABI (include/sdfgpu_multi.h, libsdfgpu_multi.so) -------------------------------------------------

@@ -19,6 +19,7 @@
 #include "arc_utilities/zlib_helpers.hpp"
 #include "sdf_tools/collision_map.hpp"
 #include "sdf_tools/device_sdf.hpp"
+#include "sdf_tools/dynamic_spatial_hashed_collision_map.hpp"
 #include "sdf_tools/sdf_builder.hpp"
 #include "sdf_tools/tagged_object_collision_map.hpp"
 
@@ -797,6 +798,91 @@ PYBIND11_MODULE(pysdf_tools, m) {
         .def("GetCachedCollisionMap", [collision_map_numpy](const sdf_tools::SDF_Builder& b) { return collision_map_numpy(b.GetCachedCollisionMap()); })
         .def("UpdateSDFDevice", [](sdf_tools::SDF_Builder& b, int mode) { return b.UpdateSDFDevice((uint8_t)mode); })
         .def("UpdateTaggedCollisionMap", [](sdf_tools::SDF_Builder& b, int mode) { return b.UpdateTaggedCollisionMap((uint8_t)mode); });
+    // The sparse map that stays on the GPU.  Batch forms take numpy: locations float64 [n, 3], records uint64 [n] (a COLLISION_CELL's
+    // 8 bytes: occupancy in the low word, component in the high one) or one COLLISION_CELL for the whole batch.
+    using DshGrid = sdf_tools::DynamicSpatialHashedCollisionMapGrid;
+    auto dsh_cells = [](const py::object& value, size_t n) {
+        std::vector<COLLISION_CELL> cells;
+        if (py::isinstance<COLLISION_CELL>(value)) { cells.push_back(value.cast<COLLISION_CELL>()); return cells; }
+        const auto records = py::array_t<uint64_t, py::array::c_style | py::array::forcecast>::ensure(value);
+        if (!records || (size_t)records.size() != n) throw std::invalid_argument("values: one COLLISION_CELL, or uint64 records, one per location");
+        cells.resize(n);
+        if (n) std::memcpy(static_cast<void*>(cells.data()), records.data(), n * 8);
+        return cells;
+    };
+    auto dsh_locations = [](const py::array_t<double, py::array::c_style | py::array::forcecast>& locations) {
+        if (locations.size() % 3) throw std::invalid_argument("locations: float64 [n, 3]");
+        return std::vector<double>(locations.data(), locations.data() + locations.size());
+    };
+    auto dsh_statuses = [](const std::vector<VoxelGrid::SET_STATUS>& statuses) {
+        py::array_t<uint8_t> out((py::ssize_t)statuses.size());
+        for (size_t i = 0; i < statuses.size(); ++i) out.mutable_data()[i] = (uint8_t)statuses[i];
+        return out;
+    };
+    py::class_<DshGrid>(m, "DynamicSpatialHashedCollisionMapGrid")
+        .def(py::init<>())
+        .def(py::init<std::string, double, int64_t, int64_t, int64_t, COLLISION_CELL>(), py::arg("frame"), py::arg("resolution"), py::arg("chunk_x_size"),
+             py::arg("chunk_y_size"), py::arg("chunk_z_size"), py::arg("OOB_value"))
+        .def(py::init<Isometry3d, std::string, double, int64_t, int64_t, int64_t, COLLISION_CELL, uint64_t>(), py::arg("origin_transform"), py::arg("frame"),
+             py::arg("resolution"), py::arg("chunk_x_size"), py::arg("chunk_y_size"), py::arg("chunk_z_size"), py::arg("OOB_value"), py::arg("byte_limit") = 0)
+        .def("IsInitialized", &DshGrid::IsInitialized)
+        .def("AreComponentsValid", &DshGrid::AreComponentsValid)
+        .def("GetOriginTransform", &DshGrid::GetOriginTransform)
+        .def("GetFrame", &DshGrid::GetFrame)
+        .def("GetResolution", &DshGrid::GetResolution)
+        .def("Get", [](const DshGrid& g, double x, double y, double z) { const auto r = g.Get(x, y, z); return py::make_tuple(r.first, (int)r.second); })
+        .def("SetCell", [](DshGrid& g, double x, double y, double z, COLLISION_CELL v) { return (int)g.SetCell(x, y, z, v); })
+        .def("SetChunk", [](DshGrid& g, double x, double y, double z, COLLISION_CELL v) { return (int)g.SetChunk(x, y, z, v); })
+        .def("SetCells", [=](DshGrid& g, const py::array_t<double, py::array::c_style | py::array::forcecast>& locations, const py::object& values) {
+            const std::vector<double> loc = dsh_locations(locations);
+            return dsh_statuses(g.SetCells(loc, dsh_cells(values, loc.size() / 3)));
+        }, py::arg("locations"), py::arg("values"), "uint8 statuses; as if applied one after the other in list order")
+        .def("SetChunks", [=](DshGrid& g, const py::array_t<double, py::array::c_style | py::array::forcecast>& locations, const py::object& values) {
+            const std::vector<double> loc = dsh_locations(locations);
+            return dsh_statuses(g.SetChunks(loc, dsh_cells(values, loc.size() / 3)));
+        }, py::arg("locations"), py::arg("values"))
+        .def("GetBatch", [=](const DshGrid& g, const py::array_t<double, py::array::c_style | py::array::forcecast>& locations) {
+            const auto got = g.GetBatch(dsh_locations(locations));
+            py::array_t<uint64_t> records((py::ssize_t)got.first.size());
+            py::array_t<uint8_t> statuses((py::ssize_t)got.second.size());
+            if (!got.first.empty()) std::memcpy(records.mutable_data(), static_cast<const void*>(got.first.data()), got.first.size() * 8);
+            for (size_t i = 0; i < got.second.size(); ++i) statuses.mutable_data()[i] = (uint8_t)got.second[i];
+            return py::make_tuple(records, statuses);
+        }, py::arg("locations"), "(records uint64 [n], statuses uint8 [n])")
+        .def("InsertPointCloud", [](DshGrid& g, const py::array_t<float, py::array::c_style | py::array::forcecast>& points, COLLISION_CELL value) {
+            if (points.size() % 3) throw std::invalid_argument("points: float32 [n, 3]");
+            return g.InsertPointCloud(std::vector<float>(points.data(), points.data() + points.size()), value);
+        }, py::arg("points"), py::arg("value"), "cell sets of one value; returns how many points were set")
+        .def("ExtractCollisionMapGrid", [](const DshGrid& g, const std::array<int64_t, 3>& lower, int64_t nx, int64_t ny, int64_t nz) {
+            return g.ExtractCollisionMapGrid(VoxelGrid::GRID_INDEX(lower[0], lower[1], lower[2]), nx, ny, nz);
+        }, py::arg("lower_index"), py::arg("nx"), py::arg("ny"), py::arg("nz"))
+        .def("ExtractWindowRecords", [](const DshGrid& g, const std::array<int64_t, 3>& lower, int64_t nx, int64_t ny, int64_t nz) {
+            const CollisionMapGrid grid = g.ExtractCollisionMapGrid(VoxelGrid::GRID_INDEX(lower[0], lower[1], lower[2]), nx, ny, nz);
+            py::array_t<uint64_t> out({nx, ny, nz});
+            std::memcpy(out.mutable_data(), static_cast<const void*>(grid.GetImmutableRawData().data()), (size_t)(nx * ny * nz) * 8);
+            return out;
+        }, py::arg("lower_index"), py::arg("nx"), py::arg("ny"), py::arg("nz"), "the window's records as uint64 [nx, ny, nz]")
+        .def("ExtractSignedDistanceField", [](const DshGrid& g, const std::array<int64_t, 3>& lower, int64_t nx, int64_t ny, int64_t nz, float oob_value,
+                                              bool unknown_is_filled, bool add_virtual_border) {
+            return g.ExtractSignedDistanceField(VoxelGrid::GRID_INDEX(lower[0], lower[1], lower[2]), nx, ny, nz, oob_value, unknown_is_filled, add_virtual_border);
+        }, py::arg("lower_index"), py::arg("nx"), py::arg("ny"), py::arg("nz"), py::arg("oob_value"), py::arg("unknown_is_filled"), py::arg("add_virtual_border"))
+        .def("ExtractSignedDistanceFieldDevice", [](const DshGrid& g, const std::array<int64_t, 3>& lower, int64_t nx, int64_t ny, int64_t nz, float oob_value,
+                                                    bool unknown_is_filled, bool add_virtual_border) {
+            return g.ExtractSignedDistanceFieldDevice(VoxelGrid::GRID_INDEX(lower[0], lower[1], lower[2]), nx, ny, nz, oob_value, unknown_is_filled, add_virtual_border);
+        }, py::arg("lower_index"), py::arg("nx"), py::arg("ny"), py::arg("nz"), py::arg("oob_value"), py::arg("unknown_is_filled"), py::arg("add_virtual_border"))
+        .def("GetCounts", [](const DshGrid& g) {
+            const sdfgpu_dsh_counts c = g.GetCounts();
+            py::dict d;
+            d["chunk_filled"] = c.chunk_filled; d["cell_filled"] = c.cell_filled; d["capacity_chunks"] = c.capacity_chunks;
+            d["table_capacity"] = c.table_capacity; d["bytes_held"] = c.bytes_held; d["scratch_bytes"] = c.scratch_bytes; d["byte_limit"] = c.byte_limit;
+            return d;
+        })
+        .def("ExportForDisplay", [](const DshGrid& g, const Rgba& collision_color, const Rgba& free_color, const Rgba& unknown_color) {
+            visualization_msgs::MarkerArray a;
+            a.markers = g.ExportForDisplay(ColorOf(collision_color), ColorOf(free_color), ColorOf(unknown_color));
+            return MarkerArrayNumpy(a);
+        }, py::arg("collision_color"), py::arg("free_color"), py::arg("unknown_color"),
+             "0, 1 or 2 markers as [(ns, points float64 [n, 3], colors float32 [n, 4])]: chunk-filled chunks, then the cells of cell-filled chunks");
     m.def("ExtractSignedDistanceFieldBatch", [](const std::vector<const CollisionMapGrid*>& maps, float oob_value, bool unknown_is_filled,
                                                 bool add_virtual_border) {
         return sdf_tools::ExtractSignedDistanceFieldBatch(maps, oob_value, unknown_is_filled, add_virtual_border);

@@ -1,0 +1,831 @@
+// sdfgpu_dsh.hip -- the chunk-hashed sparse collision map (sdfgpu_dsh.hpp, include/sdfgpu.h "Dynamic spatial hashed map", DESIGN.md
+// section 29): its kernels, the host orchestration of a batch, growth, and the C ABI entry points sdfgpu_dsh_*.  Compiled beside
+// sdfgpu.hip and linked into the same libsdfgpu.so (sdf_tools_amd/build.py).
+//
+// How the kernels of one call talk to each other: through kernel boundaries, and inside a launch through atomics only.
+//   - the table's keys are claimed by 64-bit compare-and-swap and looked at, inside the inserting launch, by atomic loads; every other
+//     word a kernel reads was written by an EARLIER launch (or by the reading thread itself)
+//   - no kernel waits for another workgroup, and every probe loop ends after `capacity` steps
+//   - the order rule of a batch with one value per operation is a winner stamp by 64-bit atomic max (operation index + 1) that lives,
+//     between two launches, in the 8 bytes it is about to overwrite: zero the targets | stamp | decide (one flag per operation) | apply
+//
+// Arithmetic: a location on a cell boundary is placed by the rounding of g = inverse_origin * p alone, and tests/dsh_restated.py states
+// that product in numpy (separate products and sums), so nothing here may be contracted into an FMA (hipcc contracts by default).  The
+// host code below falls under the pragma too; it is compiled for baseline x86-64, which has no FMA to contract into.
+#pragma clang fp contract(off)
+#include "sdfgpu_context.hpp"
+#include "sdfgpu_dsh.hpp"
+#include "sdfgpu.h"
+
+namespace sdfgpu {
+
+namespace {
+
+constexpr uint32_t kDshNoPos = 0xFFFFFFFFu;       // an operation at an invalid location
+
+dim3 dsh_grid(int64_t items) {
+    const int64_t workgroups = std::max<int64_t>(1, (items + kDshThreads - 1) / kDshThreads);
+    if (workgroups <= kDshGridX) return dim3((unsigned)workgroups);
+    return dim3((unsigned)kDshGridX, (unsigned)((workgroups + kDshGridX - 1) / kDshGridX));
+}
+__device__ __forceinline__ int64_t dsh_item() { return ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * kDshThreads + threadIdx.x; }
+
+// location -> (key, cell slot); false for an invalid location
+__device__ __forceinline__ bool dsh_locate(const DshGeometry& g, double px, double py, double pz, uint64_t& key, uint32_t& cell) {
+    if (!(isfinite(px) && isfinite(py) && isfinite(pz))) return false;
+    int64_t c[3], l[3];
+    for (int a = 0; a < 3; ++a) {
+        const double* m = g.inverse + 4 * a;
+        const double ga = ((m[0] * px + m[1] * py) + m[2] * pz) + m[3];
+        const double v = floor(ga * g.inv_cell);
+        const double lim = (double)(kDshChunkBias * g.n[a]);               // exact: at most 2^35
+        if (!(v >= -lim && v < lim)) return false;                           // (NaN and the infinities fail: no cast of such a double)
+        const int64_t i = (int64_t)v;
+        c[a] = dsh_floor_div(i, g.n[a]);
+        l[a] = i - c[a] * g.n[a];
+    }
+    key = dsh_pack_key(c[0], c[1], c[2]);
+    cell = (uint32_t)((l[0] * g.n[1] + l[1]) * g.n[2] + l[2]);
+    return true;
+}
+
+// the position of `key` in a table no launch is inserting into, or kDshNoPos
+__device__ __forceinline__ uint32_t dsh_find(const DshTable& t, uint64_t key) {
+    uint64_t pos = dsh_hash(key) & t.mask;
+    for (uint64_t probe = 0; probe <= t.mask; ++probe) {
+        const uint64_t k = t.keys[pos];
+        if (k == key) return (uint32_t)pos;
+        if (k == kDshEmptyKey) return kDshNoPos;
+        pos = (pos + 1) & t.mask;
+    }
+    return kDshNoPos;
+}
+
+// ---- a batch: insert keys ------------------------------------------------------------------------------------------------------------
+// counters[0] = new chunks of this batch, counters[1] = operations that found no entry (cannot happen in a table sized for the batch)
+template <typename LOC>
+__global__ __launch_bounds__(kDshThreads) void k_dsh_insert(const DshGeometry g, const DshTable t, const LOC* __restrict__ loc, int64_t n,
+                                                            uint32_t n_live, uint32_t* __restrict__ op_pos, uint32_t* __restrict__ op_cell,
+                                                            uint32_t* __restrict__ newlist, uint32_t* counters, uint8_t* __restrict__ statuses,
+                                                            uint8_t set_status) {
+    const int64_t i = dsh_item();
+    if (i >= n) return;
+    uint64_t key = 0;
+    uint32_t cell = 0, found = kDshNoPos;
+    if (dsh_locate(g, (double)loc[3 * i], (double)loc[3 * i + 1], (double)loc[3 * i + 2], key, cell)) {
+        uint64_t pos = dsh_hash(key) & t.mask;
+        unsigned long long* const keys = reinterpret_cast<unsigned long long*>(t.keys);
+        bool placed = false;
+        for (uint64_t probe = 0; probe <= t.mask && !placed; ++probe) {
+            unsigned long long k = __hip_atomic_load(keys + pos, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (k == kDshEmptyKey) {
+                k = atomicCAS(keys + pos, (unsigned long long)kDshEmptyKey, (unsigned long long)key);
+                if (k == kDshEmptyKey) {                                     // this thread made the entry: it numbers the chunk
+                    const uint32_t fresh = atomicAdd(&counters[0], 1u);
+                    newlist[fresh] = (uint32_t)pos;
+                    t.slots[pos] = n_live + fresh;                           // (read by later launches only)
+                    k = key;
+                }
+            }
+            if (k == key) { found = (uint32_t)pos; placed = true; }
+            pos = (pos + 1) & t.mask;
+        }
+        if (!placed) atomicAdd(&counters[1], 1u);
+    }
+    op_pos[i] = found;
+    op_cell[i] = cell;
+    if (statuses) statuses[i] = found != kDshNoPos ? set_status : (uint8_t)SDFGPU_DSH_NOT_SET;
+}
+
+// a refused batch: the entries it made become empty again.  Every other key sits where it sat before the batch (an insert moves
+// nothing), so the table is exactly the one the batch found.
+__global__ __launch_bounds__(kDshThreads) void k_dsh_rollback(const DshTable t, const uint32_t* __restrict__ newlist, uint32_t n_new) {
+    const int64_t i = dsh_item();
+    if (i < n_new) t.keys[newlist[i]] = kDshEmptyKey;
+}
+
+__global__ __launch_bounds__(kDshThreads) void k_dsh_init_new(const DshTable t, DshChunkHead* __restrict__ heads,
+                                                              const uint32_t* __restrict__ newlist, uint32_t n_new, uint32_t n_live) {
+    const int64_t i = dsh_item();
+    if (i >= n_new) return;
+    DshChunkHead hd;
+    hd.key = t.keys[newlist[i]];
+    hd.record = 0; hd.state = 0; hd.reserved = 0;
+    heads[n_live + i] = hd;
+}
+
+// the table after it grew: every live chunk's key goes into the new (empty) table
+__global__ __launch_bounds__(kDshThreads) void k_dsh_rehash(const DshTable t, const DshChunkHead* __restrict__ heads, uint32_t n_live,
+                                                            uint32_t* counters) {
+    const int64_t s = dsh_item();
+    if (s >= n_live) return;
+    const uint64_t key = heads[s].key;
+    uint64_t pos = dsh_hash(key) & t.mask;
+    unsigned long long* const keys = reinterpret_cast<unsigned long long*>(t.keys);
+    for (uint64_t probe = 0; probe <= t.mask; ++probe) {
+        if (atomicCAS(keys + pos, (unsigned long long)kDshEmptyKey, (unsigned long long)key) == kDshEmptyKey) {
+            t.slots[pos] = (uint32_t)s;
+            return;
+        }
+        pos = (pos + 1) & t.mask;
+    }
+    atomicAdd(&counters[1], 1u);
+}
+
+// ---- a batch of cell sets: which chunks must hold cells ----------------------------------------------------------------------------------
+__global__ __launch_bounds__(kDshThreads) void k_dsh_touch(const DshTable t, DshChunkHead* heads, const uint32_t* __restrict__ op_pos, int64_t n) {
+    const int64_t i = dsh_item();
+    const uint32_t pos = i < n ? op_pos[i] : kDshNoPos;
+    // neighbouring operations mostly share a chunk: a lane whose predecessor in the wave names the same entry leaves the flag to it
+    const uint32_t before = (uint32_t)__shfl_up((int)pos, 1);
+    if (pos != kDshNoPos && ((threadIdx.x & 63) == 0 || before != pos)) atomicOr(&heads[t.slots[pos]].state, kDshTouched);
+}
+
+// one workgroup per chunk: a touched chunk that holds no cells yet gets them (the default, or the chunk's record in every cell)
+__global__ __launch_bounds__(kDshThreads) void k_dsh_expand(const DshPool p, uint64_t n_live, uint64_t cells_per_chunk, uint64_t default_record) {
+    const uint64_t slot = (uint64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    if (slot >= n_live) return;                                                // (the last row of a two-dimensional launch)
+    DshChunkHead* const hd = p.heads + slot;
+    const uint32_t state = hd->state;
+    if (!(state & kDshTouched)) return;                                        // (uniform over the workgroup)
+    if ((state & kDshStateMask) != kDshCellFilled) {
+        const uint64_t fill = (state & kDshStateMask) == kDshChunkFilled ? hd->record : default_record;
+        uint64_t* const cells = p.cells + slot * cells_per_chunk;
+        for (uint64_t k = threadIdx.x; k < cells_per_chunk; k += kDshThreads) cells[k] = fill;
+    }
+    __syncthreads();                                                           // every thread has read the state word
+    if (threadIdx.x == 0) { hd->state = kDshCellFilled; hd->record = 0; }
+}
+
+// ---- a batch: write ------------------------------------------------------------------------------------------------------------------
+// what operation i writes: a cell of its chunk, or (CHUNK) the chunk's record
+template <bool CHUNK>
+__device__ __forceinline__ uint64_t* dsh_target(const DshTable& t, const DshPool& p, uint64_t cells_per_chunk, uint32_t pos, uint32_t cell) {
+    const uint64_t slot = t.slots[pos];
+    return CHUNK ? &p.heads[slot].record : p.cells + slot * cells_per_chunk + cell;
+}
+
+// every valid operation stores `value` (the one-value batch, whose order cannot matter; and, with 0, the first step of the order rule)
+template <bool CHUNK>
+__global__ __launch_bounds__(kDshThreads) void k_dsh_store_one(const DshTable t, const DshPool p, uint64_t cells_per_chunk,
+                                                               const uint32_t* __restrict__ op_pos, const uint32_t* __restrict__ op_cell,
+                                                               int64_t n, uint64_t value) {
+    const int64_t i = dsh_item();
+    if (i >= n || op_pos[i] == kDshNoPos) return;
+    *dsh_target<CHUNK>(t, p, cells_per_chunk, op_pos[i], op_cell[i]) = value;
+    if (CHUNK) p.heads[t.slots[op_pos[i]]].state = kDshChunkFilled;
+}
+
+template <bool CHUNK>
+__global__ __launch_bounds__(kDshThreads) void k_dsh_stamp(const DshTable t, const DshPool p, uint64_t cells_per_chunk,
+                                                           const uint32_t* __restrict__ op_pos, const uint32_t* __restrict__ op_cell, int64_t n) {
+    const int64_t i = dsh_item();
+    if (i >= n || op_pos[i] == kDshNoPos) return;
+    atomicMax(reinterpret_cast<unsigned long long*>(dsh_target<CHUNK>(t, p, cells_per_chunk, op_pos[i], op_cell[i])), (unsigned long long)(i + 1));
+}
+
+template <bool CHUNK>
+__global__ __launch_bounds__(kDshThreads) void k_dsh_decide(const DshTable t, const DshPool p, uint64_t cells_per_chunk,
+                                                            const uint32_t* __restrict__ op_pos, const uint32_t* __restrict__ op_cell, int64_t n,
+                                                            uint8_t* __restrict__ wins) {
+    const int64_t i = dsh_item();
+    if (i >= n) return;
+    wins[i] = op_pos[i] != kDshNoPos && *dsh_target<CHUNK>(t, p, cells_per_chunk, op_pos[i], op_cell[i]) == (uint64_t)(i + 1);
+}
+
+template <bool CHUNK>
+__global__ __launch_bounds__(kDshThreads) void k_dsh_apply(const DshTable t, const DshPool p, uint64_t cells_per_chunk,
+                                                           const uint32_t* __restrict__ op_pos, const uint32_t* __restrict__ op_cell, int64_t n,
+                                                           const uint8_t* __restrict__ wins, const uint64_t* __restrict__ values) {
+    const int64_t i = dsh_item();
+    if (i >= n || !wins[i]) return;
+    *dsh_target<CHUNK>(t, p, cells_per_chunk, op_pos[i], op_cell[i]) = values[i];
+}
+
+// ---- reads ---------------------------------------------------------------------------------------------------------------------------
+// what Get returns for (key, cell) of a valid location
+__device__ __forceinline__ uint32_t dsh_read(const DshTable& t, const DshPool& p, uint64_t cells_per_chunk, uint64_t key, uint32_t cell,
+                                             uint64_t& record) {
+    const uint32_t pos = dsh_find(t, key);
+    if (pos == kDshNoPos) return SDFGPU_DSH_NOT_FOUND;
+    const uint64_t slot = t.slots[pos];
+    const uint32_t state = p.heads[slot].state & kDshStateMask;
+    if (state == kDshChunkFilled) record = p.heads[slot].record;
+    else if (state == kDshCellFilled) record = p.cells[slot * cells_per_chunk + cell];
+    return state;
+}
+
+__global__ __launch_bounds__(kDshThreads) void k_dsh_get(const DshGeometry g, const DshTable t, const DshPool p, const double* __restrict__ loc,
+                                                         int64_t n, uint64_t* __restrict__ records, uint8_t* __restrict__ statuses) {
+    const int64_t i = dsh_item();
+    if (i >= n) return;
+    uint64_t key = 0, record = g.default_record;
+    uint32_t cell = 0, status = SDFGPU_DSH_NOT_FOUND;
+    if (dsh_locate(g, loc[3 * i], loc[3 * i + 1], loc[3 * i + 2], key, cell)) status = dsh_read(t, p, (uint64_t)g.cells_per_chunk, key, cell, record);
+    if (records) records[i] = record;
+    if (statuses) statuses[i] = (uint8_t)status;
+}
+
+struct DshWindow {
+    int64_t lower[3];
+    uint32_t ny, nz;
+    uint64_t n;             // voxels (< 2^32)
+    int unknown_is_filled;
+    uint64_t* records;      // either may be null
+    uint32_t* bits;
+};
+
+// One thread per voxel, a wave per two bit words: the words' bits come out of a ballot, lanes 0 and 32 store them whole.
+__global__ __launch_bounds__(kDshThreads) void k_dsh_window(const DshGeometry g, const DshTable t, const DshPool p, const DshWindow w) {
+    const uint64_t v = (uint64_t)dsh_item();
+    if (v - threadIdx.x >= w.n) return;                                        // (the last row of a two-dimensional launch)
+    bool filled = false;
+    if (v < w.n) {
+        const uint32_t u = (uint32_t)v, q = u / w.nz;
+        const uint32_t z = u - q * w.nz, x = q / w.ny, y = q - x * w.ny;
+        const int64_t i[3] = {w.lower[0] + (int64_t)x, w.lower[1] + (int64_t)y, w.lower[2] + (int64_t)z};
+        int64_t c[3], l[3];
+        bool valid = true;
+        for (int a = 0; a < 3; ++a) {
+            c[a] = dsh_floor_div(i[a], g.n[a]);
+            l[a] = i[a] - c[a] * g.n[a];
+            valid = valid && dsh_chunk_in_range(c[a]);
+        }
+        uint64_t record = g.default_record;
+        if (valid) (void)dsh_read(t, p, (uint64_t)g.cells_per_chunk, dsh_pack_key(c[0], c[1], c[2]), (uint32_t)((l[0] * g.n[1] + l[1]) * g.n[2] + l[2]), record);
+        if (w.records) w.records[v] = record;
+        const float occ = __uint_as_float((uint32_t)record);                  // COLLISION_CELL: occupancy in the low word
+        filled = occ > 0.5f || (w.unknown_is_filled && occ == 0.5f);
+    }
+    if (w.bits) {                                                             // (uniform)
+        const unsigned long long b = __ballot(filled);
+        const int lane = threadIdx.x & 63;
+        if (v < w.n && (lane == 0 || lane == 32)) w.bits[v >> 5] = (uint32_t)(b >> lane);
+    }
+}
+
+// ---- export and counts -----------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kDshThreads) void k_dsh_count(const DshChunkHead* __restrict__ heads, uint32_t n_live, unsigned long long* counts) {
+    const int64_t s = dsh_item();
+    const uint32_t state = s < n_live ? heads[s].state & kDshStateMask : 0;
+    const unsigned long long chunk = __ballot(state == kDshChunkFilled), cell = __ballot(state == kDshCellFilled);
+    if ((threadIdx.x & 63) == 0) {
+        if (chunk) atomicAdd(&counts[0], (unsigned long long)__popcll(chunk));
+        if (cell) atomicAdd(&counts[1], (unsigned long long)__popcll(cell));
+    }
+}
+
+// A chunk's place in the export is the number of live keys below its own, and its cells start behind those of the cell-filled chunks
+// among them: every thread counts over all chunks, a tile of kDshThreads heads at a time through LDS.  Quadratic in the number of
+// chunks and free of scratch, atomics and order effects; the export feeds a display or a test, not a frame.
+__global__ __launch_bounds__(kDshThreads) void k_dsh_rank(const DshChunkHead* __restrict__ heads, uint32_t n_live, uint64_t cells_per_chunk,
+                                                          sdfgpu_dsh_chunk* __restrict__ out, uint32_t* __restrict__ slot_of_rank) {
+    __shared__ uint64_t tile_key[kDshThreads];
+    __shared__ uint32_t tile_cell[kDshThreads];
+    const int64_t s = dsh_item();
+    const bool live = s < n_live;
+    const DshChunkHead mine = live ? heads[s] : DshChunkHead{kDshEmptyKey, 0, 0, 0};
+    uint32_t below = 0, cells_below = 0;
+    for (uint32_t base = 0; base < n_live; base += kDshThreads) {
+        const uint32_t j = base + threadIdx.x;
+        tile_key[threadIdx.x] = j < n_live ? heads[j].key : kDshEmptyKey;      // (no key is above the empty key's value)
+        tile_cell[threadIdx.x] = j < n_live && (heads[j].state & kDshStateMask) == kDshCellFilled;
+        __syncthreads();
+        for (int k = 0; k < kDshThreads; ++k) {
+            const uint32_t lt = tile_key[k] < mine.key;
+            below += lt;
+            cells_below += lt & tile_cell[k];
+        }
+        __syncthreads();
+    }
+    if (!live) return;
+    sdfgpu_dsh_chunk c;
+    dsh_unpack_key(mine.key, c.c[0], c.c[1], c.c[2]);
+    c.state = mine.state & kDshStateMask;
+    c.reserved = 0;
+    c.record = c.state == kDshChunkFilled ? mine.record : 0;
+    c.first_cell = c.state == kDshCellFilled ? (int64_t)((uint64_t)cells_below * cells_per_chunk) : -1;
+    out[below] = c;
+    slot_of_rank[below] = (uint32_t)s;
+}
+
+__global__ __launch_bounds__(kDshThreads) void k_dsh_export_cells(const DshPool p, uint64_t n_live, uint64_t cells_per_chunk,
+                                                                  const sdfgpu_dsh_chunk* __restrict__ chunks, const uint32_t* __restrict__ slot_of_rank,
+                                                                  uint64_t* __restrict__ out) {
+    const uint64_t r = (uint64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    if (r >= n_live) return;
+    const int64_t first = chunks[r].first_cell;
+    if (first < 0) return;
+    const uint64_t* const cells = p.cells + (uint64_t)slot_of_rank[r] * cells_per_chunk;
+    for (uint64_t k = threadIdx.x; k < cells_per_chunk; k += kDshThreads) out[(uint64_t)first + k] = cells[k];
+}
+
+dim3 dsh_chunk_grid(uint64_t chunks) {                                        // one workgroup per chunk
+    if (chunks <= (uint64_t)kDshGridX) return dim3((unsigned)std::max<uint64_t>(chunks, 1));
+    return dim3((unsigned)kDshGridX, (unsigned)((chunks + kDshGridX - 1) / kDshGridX));
+}
+
+}  // namespace
+
+}  // namespace sdfgpu
+
+// ---- host side ---------------------------------------------------------------------------------------------------------------------------
+using namespace sdfgpu;
+
+struct sdfgpu_dsh_map_object {
+    sdfgpu_handle h = nullptr;
+    DshGeometry g{};
+    DshTable table{};
+    uint64_t table_cap = 0;
+    DshPool pool{};
+    uint64_t pool_cap = 0;          // chunks
+    uint64_t n_live = 0;            // chunks in use: slots 0 .. n_live - 1, every one chunk-filled or cell-filled
+    uint64_t byte_limit = 0;
+    DeviceBuffer scratch;           // per batch: table position, cell slot, new entries, winner flags, counters; the export's order
+    DeviceBuffer stage;             // host forms: locations | values | records | statuses
+    StreamOrder order;              // recorded behind every call: one on another stream waits for it first
+};
+
+namespace {
+
+constexpr size_t kDshCounterBytes = 256;
+
+size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+uint64_t dsh_bytes_held(const sdfgpu_dsh_map_object* m) { return dsh_table_bytes(m->table_cap) + dsh_pool_bytes(m->pool_cap, (uint64_t)m->g.cells_per_chunk); }
+
+int dsh_alloc_table(sdfgpu_handle h, uint64_t cap, DshTable& t, hipStream_t st) {
+    void* base = nullptr;
+    if (int rc = rz_malloc(h, "dsh table", (size_t)dsh_table_bytes(cap), &base)) return rc;
+    t.keys = static_cast<uint64_t*>(base);
+    t.slots = reinterpret_cast<uint32_t*>(t.keys + cap);
+    t.mask = cap - 1;
+    HIP_TRY(h, hipMemsetAsync(t.keys, 0xFF, (size_t)cap * 8, st));
+    return SDFGPU_OK;
+}
+
+int dsh_alloc_pool(sdfgpu_handle h, uint64_t chunks, uint64_t cells_per_chunk, DshPool& p) {
+    p = DshPool{};
+    if (int rc = rz_malloc(h, "dsh chunk heads", (size_t)(chunks * sizeof(DshChunkHead)), (void**)&p.heads)) return rc;
+    if (int rc = rz_malloc(h, "dsh chunk cells", (size_t)(chunks * cells_per_chunk * 8), (void**)&p.cells)) {
+        (void)rz_free(h, p.heads);
+        p = DshPool{};
+        return rc;
+    }
+    return SDFGPU_OK;
+}
+
+uint32_t* dsh_counters(sdfgpu_dsh_map_object* m) { return static_cast<uint32_t*>(m->scratch.ptr); }
+
+// the table for `chunks` keys: grown (new table, rehash kernel) when it is too small.  Refused before anything changes when the
+// larger table would pass the byte limit.
+int dsh_reserve_table(sdfgpu_dsh_map_object* m, uint64_t chunks, hipStream_t st) {
+    sdfgpu_handle h = m->h;
+    const uint64_t want = dsh_table_capacity(chunks);
+    if (want <= m->table_cap) return SDFGPU_OK;
+    if (want > ((uint64_t)1 << 31)) return fail(h, SDFGPU_ERR_UNSUPPORTED_SIZE, "dsh: a table of %llu entries is not supported", (unsigned long long)want);
+    if (m->byte_limit && dsh_table_bytes(want) + dsh_pool_bytes(m->pool_cap, (uint64_t)m->g.cells_per_chunk) > m->byte_limit)
+        return fail(h, SDFGPU_ERR_UNSUPPORTED_SIZE, "dsh: the table for %llu chunks would pass the map's byte limit of %llu", (unsigned long long)chunks,
+                    (unsigned long long)m->byte_limit);
+    DshTable grown{};
+    if (int rc = dsh_alloc_table(h, want, grown, st)) return rc;
+    uint32_t lost = 0;
+    if (m->n_live) {
+        HIP_TRY(h, hipMemsetAsync(dsh_counters(m), 0, kDshCounterBytes, st));
+        hipLaunchKernelGGL(k_dsh_rehash, dsh_grid((int64_t)m->n_live), dim3(kDshThreads), 0, st, grown, m->pool.heads, (uint32_t)m->n_live, dsh_counters(m));
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipMemcpyAsync(&lost, dsh_counters(m) + 1, 4, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(h, hipStreamSynchronize(st));                                       // (the old table may still be read by pending work)
+    if (lost) { (void)rz_free(h, grown.keys); return fail(h, SDFGPU_ERR_HIP, "dsh: the rehash lost %u keys (internal error)", lost); }
+    if (int rc = rz_free(h, m->table.keys)) return rc;
+    m->table = grown;
+    m->table_cap = want;
+    return SDFGPU_OK;
+}
+
+// the pool for `needed` chunks: grown (new allocations, device-to-device copies of the chunks in use) when it is too small
+int dsh_reserve_pool(sdfgpu_dsh_map_object* m, uint64_t needed, hipStream_t st) {
+    sdfgpu_handle h = m->h;
+    const uint64_t cpc = (uint64_t)m->g.cells_per_chunk;
+    uint64_t want = 0;
+    if (!dsh_plan_pool(m->pool_cap, needed, cpc, dsh_table_bytes(m->table_cap), m->byte_limit, &want))
+        return fail(h, SDFGPU_ERR_UNSUPPORTED_SIZE, "dsh: a pool of %llu chunks would pass the map's byte limit of %llu", (unsigned long long)needed,
+                    (unsigned long long)m->byte_limit);
+    if (want == m->pool_cap) return SDFGPU_OK;
+    DshPool grown{};
+    if (int rc = dsh_alloc_pool(h, want, cpc, grown)) {
+        if (want == needed) return rc;
+        (void)hipGetLastError();                                                // the doubling does not fit the device: exactly what is needed
+        want = needed;
+        if (int rc2 = dsh_alloc_pool(h, want, cpc, grown)) return rc2;
+    }
+    if (m->n_live) {
+        HIP_TRY(h, hipMemcpyAsync(grown.heads, m->pool.heads, (size_t)(m->n_live * sizeof(DshChunkHead)), hipMemcpyDeviceToDevice, st));
+        HIP_TRY(h, hipMemcpyAsync(grown.cells, m->pool.cells, (size_t)(m->n_live * cpc * 8), hipMemcpyDeviceToDevice, st));
+    }
+    HIP_TRY(h, hipStreamSynchronize(st));
+    (void)rz_free(h, m->pool.heads);
+    (void)rz_free(h, m->pool.cells);
+    m->pool = grown;
+    m->pool_cap = want;
+    return SDFGPU_OK;
+}
+
+int dsh_check_map(sdfgpu_dsh_map m) { return m && m->h ? SDFGPU_OK : SDFGPU_ERR_INVALID_ARGUMENT; }
+
+int dsh_aligned8(sdfgpu_handle h, const void* p, const char* what) {
+    if (reinterpret_cast<uintptr_t>(p) & 7) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: %s must be 8-byte aligned", what);
+    return SDFGPU_OK;
+}
+
+// One batch on `st`: cell sets (locations as doubles, or points as floats) or chunk sets.
+template <typename LOC>
+int dsh_batch(sdfgpu_dsh_map_object* m, bool chunk_sets, const LOC* d_loc, int64_t n, const void* d_values, const void* one_value,
+              uint8_t* d_statuses, hipStream_t st) {
+    sdfgpu_handle h = m->h;
+    if (n < 0 || n >= kDshMaxBatch) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: a batch holds 0 .. 2^31 - 1 operations (got %lld)", (long long)n);
+    if ((d_values != nullptr) == (one_value != nullptr))
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: give one record for the batch or one per operation, not both and not neither");
+    if (n == 0) return SDFGPU_OK;
+    if (!d_loc) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: null locations");
+    if (int rc = dsh_aligned8(h, d_values, "the values")) return rc;
+    if (reinterpret_cast<uintptr_t>(d_loc) & (sizeof(LOC) - 1)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: the locations are not aligned for their type");
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, m->order.create());
+    HIP_TRY(h, m->order.wait(st));
+    StreamOrder::RecordAtExit record_at_exit{m->order, st};
+
+    const size_t un = (size_t)n;
+    const size_t off_pos = kDshCounterBytes, off_cell = off_pos + align256(un * 4), off_new = off_cell + align256(un * 4), off_win = off_new + align256(un * 4);
+    if (int rc = ensure(h, m->scratch, off_win + align256(un), "dsh batch scratch")) return rc;
+    char* const base = static_cast<char*>(m->scratch.ptr);
+    uint32_t* const counters = dsh_counters(m);
+    uint32_t* const op_pos = reinterpret_cast<uint32_t*>(base + off_pos);
+    uint32_t* const op_cell = reinterpret_cast<uint32_t*>(base + off_cell);
+    uint32_t* const newlist = reinterpret_cast<uint32_t*>(base + off_new);
+    uint8_t* const wins = reinterpret_cast<uint8_t*>(base + off_win);
+
+    // the table cannot fill while the batch inserts: the number of operations bounds the number of new chunks
+    if (int rc = dsh_reserve_table(m, m->n_live + (uint64_t)n, st)) return rc;
+    const dim3 grid = dsh_grid(n), block(kDshThreads);
+    const uint64_t cpc = (uint64_t)m->g.cells_per_chunk;
+    HIP_TRY(h, hipMemsetAsync(counters, 0, kDshCounterBytes, st));
+    hipLaunchKernelGGL((k_dsh_insert<LOC>), grid, block, 0, st, m->g, m->table, d_loc, n, (uint32_t)m->n_live, op_pos, op_cell, newlist, counters, d_statuses,
+                       (uint8_t)(chunk_sets ? SDFGPU_DSH_SET_CHUNK : SDFGPU_DSH_SET_CELL));
+    HIP_TRY(h, hipGetLastError());
+    uint32_t back[2] = {0, 0};                                                  // new chunks, lost operations
+    HIP_TRY(h, hipMemcpyAsync(back, counters, sizeof back, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    const uint32_t n_new = back[0];
+    int rc = back[1] ? fail(h, SDFGPU_ERR_HIP, "dsh: %u operations found no table entry (internal error)", back[1]) : SDFGPU_OK;
+    if (rc == SDFGPU_OK) rc = dsh_reserve_pool(m, m->n_live + n_new, st);
+    if (rc != SDFGPU_OK) {                                                      // refused: the table forgets the batch's keys
+        if (n_new) hipLaunchKernelGGL(k_dsh_rollback, dsh_grid(n_new), block, 0, st, m->table, newlist, n_new);
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    if (n_new) hipLaunchKernelGGL(k_dsh_init_new, dsh_grid(n_new), block, 0, st, m->table, m->pool.heads, newlist, n_new, (uint32_t)m->n_live);
+    m->n_live += n_new;
+    uint64_t value = 0;
+    if (one_value) memcpy(&value, one_value, 8);
+    const uint64_t* const values = static_cast<const uint64_t*>(d_values);
+    if (!chunk_sets) {
+        hipLaunchKernelGGL(k_dsh_touch, grid, block, 0, st, m->table, m->pool.heads, op_pos, n);
+        hipLaunchKernelGGL(k_dsh_expand, dsh_chunk_grid(m->n_live), block, 0, st, m->pool, m->n_live, cpc, m->g.default_record);
+        if (one_value) {
+            hipLaunchKernelGGL((k_dsh_store_one<false>), grid, block, 0, st, m->table, m->pool, cpc, op_pos, op_cell, n, value);
+        } else {
+            hipLaunchKernelGGL((k_dsh_store_one<false>), grid, block, 0, st, m->table, m->pool, cpc, op_pos, op_cell, n, (uint64_t)0);
+            hipLaunchKernelGGL((k_dsh_stamp<false>), grid, block, 0, st, m->table, m->pool, cpc, op_pos, op_cell, n);
+            hipLaunchKernelGGL((k_dsh_decide<false>), grid, block, 0, st, m->table, m->pool, cpc, op_pos, op_cell, n, wins);
+            hipLaunchKernelGGL((k_dsh_apply<false>), grid, block, 0, st, m->table, m->pool, cpc, op_pos, op_cell, n, wins, values);
+        }
+    } else if (one_value) {
+        hipLaunchKernelGGL((k_dsh_store_one<true>), grid, block, 0, st, m->table, m->pool, cpc, op_pos, op_cell, n, value);
+    } else {
+        hipLaunchKernelGGL((k_dsh_store_one<true>), grid, block, 0, st, m->table, m->pool, cpc, op_pos, op_cell, n, (uint64_t)0);
+        hipLaunchKernelGGL((k_dsh_stamp<true>), grid, block, 0, st, m->table, m->pool, cpc, op_pos, op_cell, n);
+        hipLaunchKernelGGL((k_dsh_decide<true>), grid, block, 0, st, m->table, m->pool, cpc, op_pos, op_cell, n, wins);
+        hipLaunchKernelGGL((k_dsh_apply<true>), grid, block, 0, st, m->table, m->pool, cpc, op_pos, op_cell, n, wins, values);
+    }
+    HIP_TRY(h, hipGetLastError());
+    return SDFGPU_OK;
+}
+
+int dsh_get_impl(sdfgpu_dsh_map_object* m, const double* d_loc, int64_t n, void* d_records, uint8_t* d_statuses, hipStream_t st) {
+    sdfgpu_handle h = m->h;
+    if (n < 0 || n >= kDshMaxBatch) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: a batch holds 0 .. 2^31 - 1 locations (got %lld)", (long long)n);
+    if (!d_records && !d_statuses) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: get needs an output");
+    if (n == 0) return SDFGPU_OK;
+    if (!d_loc) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: null locations");
+    if (int rc = dsh_aligned8(h, d_records, "the records")) return rc;
+    if (int rc = dsh_aligned8(h, d_loc, "the locations")) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, m->order.create());
+    HIP_TRY(h, m->order.wait(st));
+    StreamOrder::RecordAtExit record_at_exit{m->order, st};
+    hipLaunchKernelGGL(k_dsh_get, dsh_grid(n), dim3(kDshThreads), 0, st, m->g, m->table, m->pool, d_loc, n, static_cast<uint64_t*>(d_records), d_statuses);
+    HIP_TRY(h, hipGetLastError());
+    return SDFGPU_OK;
+}
+
+int dsh_check_window(sdfgpu_handle h, const int64_t* lower, int64_t nx, int64_t ny, int64_t nz, const void* records, const void* bits) {
+    if (!lower) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: null lower corner");
+    if (!records && !bits) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: a window needs an output");
+    if (int rc = check_dims_u32(h, nx, ny, nz, "the window's voxels are numbered by uint32")) return rc;
+    const int64_t far = (int64_t)1 << 61;                                      // lower + extent cannot overflow; anything near is out of range anyway
+    for (int a = 0; a < 3; ++a)
+        if (lower[a] < -far || lower[a] > far) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: the window's lower corner is beyond +-2^61 cells");
+    return SDFGPU_OK;
+}
+
+int dsh_window_impl(sdfgpu_dsh_map_object* m, const int64_t* lower, int64_t nx, int64_t ny, int64_t nz, int unknown_is_filled, void* d_records,
+                    uint32_t* d_bits, hipStream_t st) {
+    sdfgpu_handle h = m->h;
+    if (int rc = dsh_aligned8(h, d_records, "the records")) return rc;
+    if (reinterpret_cast<uintptr_t>(d_bits) & 3) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: the bit field must be 4-byte aligned");
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, m->order.create());
+    HIP_TRY(h, m->order.wait(st));
+    StreamOrder::RecordAtExit record_at_exit{m->order, st};
+    DshWindow w{};
+    for (int a = 0; a < 3; ++a) w.lower[a] = lower[a];
+    w.ny = (uint32_t)ny; w.nz = (uint32_t)nz;
+    w.n = (uint64_t)nx * (uint64_t)ny * (uint64_t)nz;
+    w.unknown_is_filled = unknown_is_filled != 0;
+    w.records = static_cast<uint64_t*>(d_records);
+    w.bits = d_bits;
+    hipLaunchKernelGGL(k_dsh_window, dsh_grid((int64_t)w.n), dim3(kDshThreads), 0, st, m->g, m->table, m->pool, w);
+    HIP_TRY(h, hipGetLastError());
+    return SDFGPU_OK;
+}
+
+// live chunks by state (synchronises st)
+int dsh_count(sdfgpu_dsh_map_object* m, uint64_t* chunk_filled, uint64_t* cell_filled, hipStream_t st) {
+    sdfgpu_handle h = m->h;
+    *chunk_filled = *cell_filled = 0;
+    if (!m->n_live) return SDFGPU_OK;
+    if (int rc = ensure(h, m->scratch, kDshCounterBytes, "dsh batch scratch")) return rc;
+    unsigned long long* const counts = static_cast<unsigned long long*>(m->scratch.ptr);
+    HIP_TRY(h, hipMemsetAsync(counts, 0, kDshCounterBytes, st));
+    hipLaunchKernelGGL(k_dsh_count, dsh_grid((int64_t)m->n_live), dim3(kDshThreads), 0, st, m->pool.heads, (uint32_t)m->n_live, counts);
+    HIP_TRY(h, hipGetLastError());
+    unsigned long long back[2] = {0, 0};
+    HIP_TRY(h, hipMemcpyAsync(back, counts, sizeof back, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    *chunk_filled = back[0];
+    *cell_filled = back[1];
+    return SDFGPU_OK;
+}
+
+int dsh_export_impl(sdfgpu_dsh_map_object* m, sdfgpu_dsh_chunk* d_chunks, int64_t chunk_capacity, void* d_cells, int64_t cell_capacity,
+                    int64_t* out_chunks, int64_t* out_cells, hipStream_t st) {
+    sdfgpu_handle h = m->h;
+    if (chunk_capacity < 0 || cell_capacity < 0 || (chunk_capacity > 0 && !d_chunks) || (cell_capacity > 0 && !d_cells))
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: export: a capacity without a buffer");
+    if (int rc = dsh_aligned8(h, d_chunks, "the chunk list")) return rc;
+    if (int rc = dsh_aligned8(h, d_cells, "the cell list")) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, m->order.create());
+    HIP_TRY(h, m->order.wait(st));
+    StreamOrder::RecordAtExit record_at_exit{m->order, st};
+    uint64_t chunk_filled = 0, cell_filled = 0;
+    if (int rc = dsh_count(m, &chunk_filled, &cell_filled, st)) return rc;
+    const uint64_t cpc = (uint64_t)m->g.cells_per_chunk, total_cells = cell_filled * cpc;
+    if (out_chunks) *out_chunks = (int64_t)m->n_live;
+    if (out_cells) *out_cells = (int64_t)total_cells;
+    if (!m->n_live || (uint64_t)chunk_capacity < m->n_live || (uint64_t)cell_capacity < total_cells) return SDFGPU_OK;
+    if (int rc = ensure(h, m->scratch, kDshCounterBytes + (size_t)m->n_live * 4, "dsh batch scratch")) return rc;
+    uint32_t* const slot_of_rank = reinterpret_cast<uint32_t*>(static_cast<char*>(m->scratch.ptr) + kDshCounterBytes);
+    hipLaunchKernelGGL(k_dsh_rank, dsh_grid((int64_t)m->n_live), dim3(kDshThreads), 0, st, m->pool.heads, (uint32_t)m->n_live, cpc, d_chunks, slot_of_rank);
+    if (total_cells)
+        hipLaunchKernelGGL(k_dsh_export_cells, dsh_chunk_grid(m->n_live), dim3(kDshThreads), 0, st, m->pool, m->n_live, cpc, d_chunks, slot_of_rank, static_cast<uint64_t*>(d_cells));
+    HIP_TRY(h, hipGetLastError());
+    return SDFGPU_OK;
+}
+
+// the host forms' staging: sections of the map's stage buffer, 256-byte aligned
+struct DshStage {
+    size_t total = 0;
+    size_t add(size_t bytes) { const size_t at = total; total += align256(bytes); return at; }
+};
+
+template <class Body>
+int dsh_entry(sdfgpu_dsh_map m, void* stream, Body&& body) {
+    if (dsh_check_map(m)) return SDFGPU_ERR_INVALID_ARGUMENT;
+    return rz_wrap(m->h, stream, body);
+}
+
+int dsh_set_host(sdfgpu_dsh_map m, bool chunk_sets, const double* locations, int64_t n, const void* values, const void* one_value, uint8_t* statuses) {
+    return dsh_entry(m, nullptr, [&]() -> int {
+        sdfgpu_handle h = m->h;
+        if (n < 0 || n >= kDshMaxBatch) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: a batch holds 0 .. 2^31 - 1 operations (got %lld)", (long long)n);
+        if (n == 0) return dsh_batch<double>(m, chunk_sets, nullptr, 0, values, one_value, nullptr, nullptr);
+        if (!locations) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: null locations");
+        HIP_TRY(h, hipSetDevice(h->device));
+        HIP_TRY(h, m->order.wait(nullptr));
+        DshStage s;
+        const size_t un = (size_t)n, at_loc = s.add(un * 24), at_val = s.add(values ? un * 8 : 0), at_st = s.add(statuses ? un : 0);
+        if (int rc = ensure(h, m->stage, s.total, "dsh staging")) return rc;
+        char* const base = static_cast<char*>(m->stage.ptr);
+        if (int rc = copy_from_host(h, base + at_loc, locations, un * 24)) return rc;
+        if (values) if (int rc = copy_from_host(h, base + at_val, values, un * 8)) return rc;
+        if (int rc = dsh_batch<double>(m, chunk_sets, reinterpret_cast<const double*>(base + at_loc), n, values ? base + at_val : nullptr, one_value,
+                                       statuses ? reinterpret_cast<uint8_t*>(base + at_st) : nullptr, nullptr)) return rc;
+        if (statuses) return copy_to_host(h, statuses, base + at_st, un);
+        return SDFGPU_OK;
+    });
+}
+
+}  // namespace
+
+extern "C" {
+
+int sdfgpu_dsh_create(sdfgpu_handle h, const double inverse_origin[16], double cell_size, int64_t chunk_nx, int64_t chunk_ny, int64_t chunk_nz,
+                      const void* default_cell, int64_t initial_chunks, uint64_t byte_limit, sdfgpu_dsh_map* out_map) {
+    if (!h) return SDFGPU_ERR_INVALID_ARGUMENT;
+    if (!out_map) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: out_map is null");
+    *out_map = nullptr;
+    if (!inverse_origin || !default_cell) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: null pointer");
+    if (!(cell_size > 0.0) || !std::isfinite(cell_size)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: cell_size must be positive and finite (got %g)", cell_size);
+    if (chunk_nx < 1 || chunk_ny < 1 || chunk_nz < 1 || chunk_nx > kDshMaxChunkCells || chunk_ny > kDshMaxChunkCells || chunk_nz > kDshMaxChunkCells ||
+        chunk_nx * chunk_ny * chunk_nz > kDshMaxChunkCells)
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: chunk dimensions must be at least 1 with a product of at most 32768 (got %lld x %lld x %lld)",
+                    (long long)chunk_nx, (long long)chunk_ny, (long long)chunk_nz);
+    for (int i = 0; i < 16; ++i)
+        if (!std::isfinite(inverse_origin[i])) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: the inverse origin transform is not finite");
+    if (initial_chunks < 0 || initial_chunks >= kDshMaxBatch) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: initial_chunks out of range");
+    return rz_wrap(h, nullptr, [&]() -> int {
+        HIP_TRY(h, hipSetDevice(h->device));
+        sdfgpu_dsh_map_object* m = new (std::nothrow) sdfgpu_dsh_map_object();
+        if (!m) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "out of host memory");
+        m->h = h;
+        for (int i = 0; i < 12; ++i) m->g.inverse[i] = inverse_origin[i];
+        m->g.inv_cell = 1.0 / cell_size;
+        m->g.n[0] = chunk_nx; m->g.n[1] = chunk_ny; m->g.n[2] = chunk_nz;
+        m->g.cells_per_chunk = chunk_nx * chunk_ny * chunk_nz;
+        memcpy(&m->g.default_record, default_cell, 8);
+        m->byte_limit = byte_limit;
+        const uint64_t chunks = initial_chunks ? (uint64_t)initial_chunks : 64, table = dsh_table_capacity(chunks);
+        int rc = SDFGPU_OK;
+        if (byte_limit && dsh_table_bytes(table) + dsh_pool_bytes(chunks, (uint64_t)m->g.cells_per_chunk) > byte_limit)
+            rc = fail(h, SDFGPU_ERR_UNSUPPORTED_SIZE, "dsh: a map of %llu chunks would pass its byte limit of %llu", (unsigned long long)chunks,
+                      (unsigned long long)byte_limit);
+        if (rc == SDFGPU_OK) rc = dsh_alloc_table(h, table, m->table, nullptr);
+        if (rc == SDFGPU_OK) { m->table_cap = table; rc = dsh_alloc_pool(h, chunks, (uint64_t)m->g.cells_per_chunk, m->pool); }
+        if (rc == SDFGPU_OK) { m->pool_cap = chunks; rc = ensure(h, m->scratch, kDshCounterBytes, "dsh batch scratch"); }
+        if (rc == SDFGPU_OK && hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(h, SDFGPU_ERR_HIP, "dsh: clearing the table failed");
+        if (rc != SDFGPU_OK) {
+            if (m->table.keys) (void)rz_free(h, m->table.keys);
+            if (m->pool.heads) { (void)rz_free(h, m->pool.heads); (void)rz_free(h, m->pool.cells); }
+            delete m;
+            return rc;
+        }
+        *out_map = m;
+        return SDFGPU_OK;
+    });
+}
+
+int sdfgpu_dsh_destroy(sdfgpu_dsh_map map) {
+    if (!map) return SDFGPU_OK;
+    sdfgpu_handle h = map->h;
+    (void)hipSetDevice(h->device);
+    (void)map->order.host_wait();
+    for (void* p : {(void*)map->table.keys, (void*)map->pool.heads, (void*)map->pool.cells, map->scratch.ptr, map->stage.ptr}) (void)rz_free(h, p);
+    map->order.destroy();
+    delete map;
+    return SDFGPU_OK;
+}
+
+int sdfgpu_dsh_info(sdfgpu_dsh_map map, sdfgpu_dsh_counts* out_counts) {
+    return dsh_entry(map, nullptr, [&]() -> int {
+        sdfgpu_handle h = map->h;
+        if (!out_counts) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: out_counts is null");
+        HIP_TRY(h, hipSetDevice(h->device));
+        HIP_TRY(h, map->order.wait(nullptr));
+        StreamOrder::RecordAtExit record_at_exit{map->order, nullptr};
+        sdfgpu_dsh_counts c{};
+        if (int rc = dsh_count(map, &c.chunk_filled, &c.cell_filled, nullptr)) return rc;
+        c.capacity_chunks = map->pool_cap;
+        c.table_capacity = map->table_cap;
+        c.bytes_held = dsh_bytes_held(map);
+        c.scratch_bytes = map->scratch.bytes + map->stage.bytes;
+        c.byte_limit = map->byte_limit;
+        *out_counts = c;
+        return SDFGPU_OK;
+    });
+}
+
+int sdfgpu_dsh_set_cells_device(sdfgpu_dsh_map map, const double* d_locations, int64_t n, const void* d_values, const void* one_value,
+                                uint8_t* d_statuses, void* stream) {
+    return dsh_entry(map, stream, [&]() -> int { return dsh_batch<double>(map, false, d_locations, n, d_values, one_value, d_statuses, (hipStream_t)stream); });
+}
+
+int sdfgpu_dsh_set_chunks_device(sdfgpu_dsh_map map, const double* d_locations, int64_t n, const void* d_values, const void* one_value,
+                                 uint8_t* d_statuses, void* stream) {
+    return dsh_entry(map, stream, [&]() -> int { return dsh_batch<double>(map, true, d_locations, n, d_values, one_value, d_statuses, (hipStream_t)stream); });
+}
+
+int sdfgpu_dsh_insert_points_device(sdfgpu_dsh_map map, const float* d_points, int64_t n, const void* one_value, uint8_t* d_statuses, void* stream) {
+    return dsh_entry(map, stream, [&]() -> int {
+        if (!one_value) return fail(map->h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: insert_points needs its one record");
+        return dsh_batch<float>(map, false, d_points, n, nullptr, one_value, d_statuses, (hipStream_t)stream);
+    });
+}
+
+int sdfgpu_dsh_set_cells(sdfgpu_dsh_map map, const double* locations, int64_t n, const void* values, const void* one_value, uint8_t* statuses) {
+    return dsh_set_host(map, false, locations, n, values, one_value, statuses);
+}
+
+int sdfgpu_dsh_set_chunks(sdfgpu_dsh_map map, const double* locations, int64_t n, const void* values, const void* one_value, uint8_t* statuses) {
+    return dsh_set_host(map, true, locations, n, values, one_value, statuses);
+}
+
+int sdfgpu_dsh_get_device(sdfgpu_dsh_map map, const double* d_locations, int64_t n, void* d_records, uint8_t* d_statuses, void* stream) {
+    return dsh_entry(map, stream, [&]() -> int { return dsh_get_impl(map, d_locations, n, d_records, d_statuses, (hipStream_t)stream); });
+}
+
+int sdfgpu_dsh_get(sdfgpu_dsh_map map, const double* locations, int64_t n, void* records, uint8_t* statuses) {
+    return dsh_entry(map, nullptr, [&]() -> int {
+        sdfgpu_handle h = map->h;
+        if (n < 0 || n >= kDshMaxBatch) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: a batch holds 0 .. 2^31 - 1 locations (got %lld)", (long long)n);
+        if (!records && !statuses) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: get needs an output");
+        if (n == 0) return SDFGPU_OK;
+        if (!locations) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: null locations");
+        HIP_TRY(h, hipSetDevice(h->device));
+        HIP_TRY(h, map->order.wait(nullptr));
+        DshStage s;
+        const size_t un = (size_t)n, at_loc = s.add(un * 24), at_rec = s.add(records ? un * 8 : 0), at_st = s.add(statuses ? un : 0);
+        if (int rc = ensure(h, map->stage, s.total, "dsh staging")) return rc;
+        char* const base = static_cast<char*>(map->stage.ptr);
+        if (int rc = copy_from_host(h, base + at_loc, locations, un * 24)) return rc;
+        if (int rc = dsh_get_impl(map, reinterpret_cast<const double*>(base + at_loc), n, records ? base + at_rec : nullptr,
+                                  statuses ? reinterpret_cast<uint8_t*>(base + at_st) : nullptr, nullptr)) return rc;
+        if (records) if (int rc = copy_to_host(h, records, base + at_rec, un * 8)) return rc;
+        if (statuses) return copy_to_host(h, statuses, base + at_st, un);
+        return SDFGPU_OK;
+    });
+}
+
+int sdfgpu_dsh_extract_window_device(sdfgpu_dsh_map map, const int64_t lower[3], int64_t nx, int64_t ny, int64_t nz, int unknown_is_filled,
+                                     void* d_records, uint32_t* d_bits, void* stream) {
+    return dsh_entry(map, stream, [&]() -> int {
+        if (int rc = dsh_check_window(map->h, lower, nx, ny, nz, d_records, d_bits)) return rc;
+        return dsh_window_impl(map, lower, nx, ny, nz, unknown_is_filled, d_records, d_bits, (hipStream_t)stream);
+    });
+}
+
+int sdfgpu_dsh_extract_window(sdfgpu_dsh_map map, const int64_t lower[3], int64_t nx, int64_t ny, int64_t nz, int unknown_is_filled, void* records,
+                              uint32_t* bits) {
+    return dsh_entry(map, nullptr, [&]() -> int {
+        sdfgpu_handle h = map->h;
+        if (int rc = dsh_check_window(h, lower, nx, ny, nz, records, bits)) return rc;
+        HIP_TRY(h, hipSetDevice(h->device));
+        HIP_TRY(h, map->order.wait(nullptr));
+        const size_t n = (size_t)nx * (size_t)ny * (size_t)nz, words = (n + 31) / 32;
+        DshStage s;
+        const size_t at_rec = s.add(records ? n * 8 : 0), at_bits = s.add(bits ? words * 4 : 0);
+        if (int rc = ensure(h, map->stage, s.total, "dsh staging")) return rc;
+        char* const base = static_cast<char*>(map->stage.ptr);
+        if (int rc = dsh_window_impl(map, lower, nx, ny, nz, unknown_is_filled, records ? base + at_rec : nullptr,
+                                     bits ? reinterpret_cast<uint32_t*>(base + at_bits) : nullptr, nullptr)) return rc;
+        if (records) if (int rc = copy_to_host(h, records, base + at_rec, n * 8)) return rc;
+        if (bits) return copy_to_host(h, bits, base + at_bits, words * 4);
+        return SDFGPU_OK;
+    });
+}
+
+int sdfgpu_dsh_export_device(sdfgpu_dsh_map map, sdfgpu_dsh_chunk* d_chunks, int64_t chunk_capacity, void* d_cells, int64_t cell_capacity,
+                             int64_t* out_chunks, int64_t* out_cells, void* stream) {
+    return dsh_entry(map, stream, [&]() -> int {
+        return dsh_export_impl(map, d_chunks, chunk_capacity, d_cells, cell_capacity, out_chunks, out_cells, (hipStream_t)stream);
+    });
+}
+
+int sdfgpu_dsh_export(sdfgpu_dsh_map map, sdfgpu_dsh_chunk* chunks, int64_t chunk_capacity, void* cells, int64_t cell_capacity, int64_t* out_chunks,
+                      int64_t* out_cells) {
+    return dsh_entry(map, nullptr, [&]() -> int {
+        sdfgpu_handle h = map->h;
+        if (chunk_capacity < 0 || cell_capacity < 0 || (chunk_capacity > 0 && !chunks) || (cell_capacity > 0 && !cells))
+            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: export: a capacity without a buffer");
+        HIP_TRY(h, hipSetDevice(h->device));
+        HIP_TRY(h, map->order.wait(nullptr));
+        int64_t n_chunks = 0, n_cells = 0;
+        if (int rc = dsh_export_impl(map, nullptr, 0, nullptr, 0, &n_chunks, &n_cells, nullptr)) return rc;
+        if (out_chunks) *out_chunks = n_chunks;
+        if (out_cells) *out_cells = n_cells;
+        if (n_chunks == 0 || chunk_capacity < n_chunks || cell_capacity < n_cells) return SDFGPU_OK;
+        DshStage s;
+        const size_t at_chunks = s.add((size_t)n_chunks * sizeof(sdfgpu_dsh_chunk)), at_cells = s.add((size_t)n_cells * 8);
+        if (int rc = ensure(h, map->stage, s.total, "dsh staging")) return rc;
+        char* const base = static_cast<char*>(map->stage.ptr);
+        if (int rc = dsh_export_impl(map, reinterpret_cast<sdfgpu_dsh_chunk*>(base + at_chunks), n_chunks, base + at_cells, n_cells, nullptr, nullptr, nullptr))
+            return rc;
+        if (int rc = copy_to_host(h, chunks, base + at_chunks, (size_t)n_chunks * sizeof(sdfgpu_dsh_chunk))) return rc;
+        if (n_cells) return copy_to_host(h, cells, base + at_cells, (size_t)n_cells * 8);
+        return SDFGPU_OK;
+    });
+}
+
+}  // extern "C"
