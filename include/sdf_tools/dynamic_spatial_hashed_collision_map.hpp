@@ -187,6 +187,24 @@ public:
         return set;
     }
 
+    // One frame of a range sensor (an addition; include/sdfgpu.h "Sensor rays"): the cells between
+    // sensor_origin and each point become free_value, then the points' cells become filled_value; a point beyond max_range carves
+    // up to that range and fills nothing, a point that is not finite is skipped.  max_range must span more than 0 and at most 65536
+    // cells, and the sensor must be a valid location: otherwise std::invalid_argument, and nothing is written.  Returns the frame's
+    // counts.  The contract is this project's own, UNVERIFIED against octomap's insertPointCloud.
+    sdfgpu_dsh_ray_counts InsertPointCloudRays(const std::vector<float>& points_xyz, const Eigen::Vector3d& sensor_origin, const double max_range,
+                                               const COLLISION_CELL free_value, const COLLISION_CELL filled_value) {
+        RequireInitialized();
+        if (points_xyz.size() % 3) throw std::invalid_argument("InsertPointCloudRays: points are x, y, z triples");
+        const double sensor[3] = {sensor_origin.x(), sensor_origin.y(), sensor_origin.z()};
+        sdfgpu_dsh_ray_counts counts = sdfgpu_dsh_ray_counts();
+        Locked([&](sdfgpu_dsh_map m) {
+            return sdfgpu_dsh_insert_rays(m, sensor, points_xyz.data(), (int64_t)(points_xyz.size() / 3), max_range, &free_value, &filled_value, nullptr, &counts);
+        });
+        if (counts.rays_hit + counts.rays_truncated) components_valid_ = false;
+        return counts;
+    }
+
     // ---- dense windows (additions) ------------------------------------------------------------------------------------------------------
     // The nx x ny x nz cells from global cell lower_index on as a CollisionMapGrid: cell (x, y, z) is what Get returns there.  The
     // result's origin is the map's origin times the translation to that corner; its OOB value is the map's default.

@@ -1047,8 +1047,9 @@ int sdfgpu_display_select_contour(sdfgpu_handle h, const void* cells, size_t cel
  * leaves the map's content as it was.  initial_chunks (0 = 64) sizes the first pool.  Errors go to the handle's
  * sdfgpu_last_error.
  *
- * Streams: the _device forms run on the caller's stream.  The two setters and sdfgpu_dsh_insert_points_device synchronise that
- * stream once (they read the number of new chunks back before the pool may grow), sdfgpu_dsh_info and the two export forms
+ * Streams: the _device forms run on the caller's stream.  The two setters, sdfgpu_dsh_insert_points_device and
+ * sdfgpu_dsh_insert_rays_device synchronise that stream once (they read the number of new chunks back before the pool may grow;
+ * a call that grows the table or the pool synchronises once more per growth), sdfgpu_dsh_info and the two export forms
  * synchronise too (they read counts back); sdfgpu_dsh_get_device and sdfgpu_dsh_extract_window_device return with their kernels
  * pending.  Calls on one map from different streams are ordered by the map (an event behind its last call); one host thread
  * per map at a time.
@@ -1100,6 +1101,51 @@ int sdfgpu_dsh_set_chunks(sdfgpu_dsh_map map, const double* locations, int64_t n
                           uint8_t* statuses);
 int sdfgpu_dsh_insert_points_device(sdfgpu_dsh_map map, const float* d_points, int64_t n, const void* one_value, uint8_t* d_statuses,
                                     void* stream);
+
+/* Sensor rays: one frame of a range sensor carved into the map.  The cells between the sensor and each
+ * return become free_value, then the returns become hit_value.  The contract is this project's own, UNVERIFIED against octomap's
+ * insertPointCloud and against arc_utilities; tests/dsh_rays_restated.py restates it.  All of it is IEEE double with separate
+ * products and sums (no FMA):
+ *   - grid coordinates: gs_a = (((m_a0 sx + m_a1 sy) + m_a2 sz) + m_a3) * (1 / cell_size) for the sensor s, ge_a likewise for a
+ *     point (n x 3 floats, widened to double); i0 = floor(gs), i1 = floor(ge); R = max_range * (1 / cell_size)
+ *   - the whole call is refused with SDFGPU_ERR_INVALID_ARGUMENT, nothing written, when s is not finite or not a valid location, or
+ *     when R is not in (0, 65536] (NaN included; there is no unlimited range).  A ray whose point is not finite or not a valid
+ *     location is skipped: status SDFGPU_DSH_RAY_SKIPPED, nothing written for it
+ *   - the walk: d = ge - gs, len2 = (d_x d_x + d_y d_y) + d_z d_z.  Axis a has |i1_a - i0_a| steps left in direction
+ *     sign(i1_a - i0_a) and the crossing parameter t_a = (B_a - gs_a) / d_a, B_a the current cell index (+ 1 when the direction is
+ *     positive), +inf when no step is left.  A step takes the axis with the smallest t_a (ties: x before y before z), moves one
+ *     cell, and recomputes that axis's t_a.  The walk is c_0 = i0 .. c_N = i1, N = sum_a |i1_a - i0_a|, with entry parameters
+ *     t_0 = 0 and t_k = the t_a that step k consumed
+ *   - range: cell c_k is in range iff (t_k t_k) len2 <= R R, which holds for a prefix of the walk; a ray is long iff len2 > R R
+ *   - a ray that is not long carves c_0 .. c_(N-1) and hits c_N (SDFGPU_DSH_RAY_HIT); a long ray carves the in-range prefix of
+ *     c_0 .. c_N and hits nothing (SDFGPU_DSH_RAY_TRUNCATED)
+ *   - the frame leaves the map as SetCell(c, free_value) for every carved cell of every ray, then SetCell(c, hit_value) for every
+ *     hit cell: a cell that one ray carves and another hits ends up hit; absent and chunk-filled chunks the rays cross become
+ *     cell-filled as SetCell makes them
+ *   - byte_limit refuses the whole frame (SDFGPU_ERR_UNSUPPORTED_SIZE) and leaves the map, its table and its pool as they were: the
+ *     table and the pool are sized for the frees and the hits before a cell is stored.  The table is sized for the live chunks plus
+ *     a bound on the chunks the frame can enter (the smallest of: rays x chunks a ray of R cells can cross; the chunks within R of
+ *     the sensor; the sum over the rays of the chunks between a ray's two ends), which counts a chunk once per ray that enters it
+ *     and so may refuse a frame whose chunks would in fact have fitted
+ * free_value, hit_value and sensor are host memory.  d_statuses / statuses (optional): one byte per ray; undefined when the call
+ * fails.  out_counts (optional, host memory) is filled when the call succeeds.  The device form synchronises the stream once, as
+ * the setters do (it reads the number of new chunks and the counts back before the pool may grow), and once more in front of
+ * that on a frame whose worst case would make the table grow (the rays' chunks are counted first). */
+enum { SDFGPU_DSH_RAY_SKIPPED = 0, SDFGPU_DSH_RAY_HIT = 1, SDFGPU_DSH_RAY_TRUNCATED = 2 };   /* a ray's status byte */
+
+typedef struct sdfgpu_dsh_ray_counts {
+    uint64_t rays_hit;
+    uint64_t rays_truncated;
+    uint64_t rays_skipped;
+    uint64_t cells_carved;       /* with multiplicity: the sum of the rays' carved counts */
+    uint64_t new_chunks;         /* chunks that were absent before the frame */
+} sdfgpu_dsh_ray_counts;
+
+int sdfgpu_dsh_insert_rays_device(sdfgpu_dsh_map map, const double sensor[3], const float* d_points, int64_t n, double max_range,
+                                  const void* free_value, const void* hit_value, uint8_t* d_statuses, sdfgpu_dsh_ray_counts* out_counts,
+                                  void* stream);
+int sdfgpu_dsh_insert_rays(sdfgpu_dsh_map map, const double sensor[3], const float* points, int64_t n, double max_range,
+                           const void* free_value, const void* hit_value, uint8_t* statuses, sdfgpu_dsh_ray_counts* out_counts);
 
 /* Get for n locations: 8-byte records and / or one status byte each (SDFGPU_DSH_NOT_FOUND / FOUND_IN_CHUNK / FOUND_IN_CELL);
  * either output may be null, not both. */

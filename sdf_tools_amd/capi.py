@@ -45,7 +45,7 @@ EXPORTS = [
     "sdfgpu_rasterize_solid_meshes_device", "sdfgpu_rasterize_solid_meshes", "sdfgpu_check_closed_meshes",
     "sdfgpu_dsh_create", "sdfgpu_dsh_destroy", "sdfgpu_dsh_info",
     "sdfgpu_dsh_set_cells_device", "sdfgpu_dsh_set_cells", "sdfgpu_dsh_set_chunks_device", "sdfgpu_dsh_set_chunks",
-    "sdfgpu_dsh_insert_points_device", "sdfgpu_dsh_get_device", "sdfgpu_dsh_get",
+    "sdfgpu_dsh_insert_points_device", "sdfgpu_dsh_insert_rays_device", "sdfgpu_dsh_insert_rays", "sdfgpu_dsh_get_device", "sdfgpu_dsh_get",
     "sdfgpu_dsh_extract_window_device", "sdfgpu_dsh_extract_window", "sdfgpu_dsh_export_device", "sdfgpu_dsh_export",
 ]
 
@@ -201,6 +201,8 @@ def load_library():
     L.sdfgpu_dsh_set_chunks_device.argtypes = L.sdfgpu_dsh_set_cells_device.argtypes
     L.sdfgpu_dsh_set_chunks.argtypes = L.sdfgpu_dsh_set_cells.argtypes
     L.sdfgpu_dsh_insert_points_device.argtypes = [vp, vp, i64, vp, vp, vp]
+    L.sdfgpu_dsh_insert_rays_device.argtypes = [vp, vp, vp, i64, dbl, vp, vp, vp, vp, vp]
+    L.sdfgpu_dsh_insert_rays.argtypes = [vp, vp, vp, i64, dbl, vp, vp, vp, vp]
     L.sdfgpu_dsh_get_device.argtypes = [vp, vp, i64, vp, vp, vp]
     L.sdfgpu_dsh_get.argtypes = [vp, vp, i64, vp, vp]
     L.sdfgpu_dsh_extract_window_device.argtypes = [vp, vp, i64, i64, i64, ci, vp, vp, vp]
@@ -1333,9 +1335,11 @@ class SdfGpu:
 # ---- include/sdfgpu.h "Dynamic spatial hashed map" ------------------------------------------------------------------
 DSH_NOT_FOUND, DSH_FOUND_IN_CHUNK, DSH_FOUND_IN_CELL = 0, 1, 2
 DSH_NOT_SET, DSH_SET_CHUNK, DSH_SET_CELL = 0, 1, 2
+DSH_RAY_SKIPPED, DSH_RAY_HIT, DSH_RAY_TRUNCATED = 0, 1, 2
 DSH_MAX_CHUNK_CELLS = 32768
 DSH_COUNTS_DTYPE = np.dtype([(n, np.uint64) for n in ("chunk_filled", "cell_filled", "capacity_chunks", "table_capacity", "bytes_held",
                                                       "scratch_bytes", "byte_limit")])
+DSH_RAY_COUNTS_DTYPE = np.dtype([(n, np.uint64) for n in ("rays_hit", "rays_truncated", "rays_skipped", "cells_carved", "new_chunks")])
 DSH_CHUNK_DTYPE = np.dtype([("c", np.int64, (3,)), ("state", np.uint32), ("reserved", np.uint32), ("record", np.uint64),
                             ("first_cell", np.int64)])
 
@@ -1416,6 +1420,25 @@ class DshMap:
     def insert_points_device(self, d_points, n, one_value, d_statuses=0, stream=0):
         one = np.array([one_value], np.uint64)
         self._check(self._lib.sdfgpu_dsh_insert_points_device(self._m, d_points, int(n), one.ctypes.data, d_statuses or None, stream or None))
+
+    def insert_rays(self, sensor, points, max_range, free_value, hit_value):
+        """One frame of sensor rays (sdfgpu_dsh_insert_rays): points float32 [n, 3] -> (statuses uint8 [n], counts dict)"""
+        pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        s = np.ascontiguousarray(sensor, dtype=np.float64).reshape(3)
+        free, hit = np.array([free_value], np.uint64), np.array([hit_value], np.uint64)
+        st, counts = np.zeros(len(pts), np.uint8), np.zeros(1, DSH_RAY_COUNTS_DTYPE)
+        self._check(self._lib.sdfgpu_dsh_insert_rays(self._m, s.ctypes.data, pts.ctypes.data, len(pts), float(max_range), free.ctypes.data, hit.ctypes.data,
+                                                     st.ctypes.data, counts.ctypes.data))
+        return st, {k: int(counts[0][k]) for k in DSH_RAY_COUNTS_DTYPE.names}
+
+    def insert_rays_device(self, sensor, d_points, n, max_range, free_value, hit_value, d_statuses=0, stream=0):
+        """The device form on `stream` (points float32 [n, 3] in device memory); returns the counts dict"""
+        s = np.ascontiguousarray(sensor, dtype=np.float64).reshape(3)
+        free, hit = np.array([free_value], np.uint64), np.array([hit_value], np.uint64)
+        counts = np.zeros(1, DSH_RAY_COUNTS_DTYPE)
+        self._check(self._lib.sdfgpu_dsh_insert_rays_device(self._m, s.ctypes.data, d_points or None, int(n), float(max_range), free.ctypes.data,
+                                                            hit.ctypes.data, d_statuses or None, counts.ctypes.data, stream or None))
+        return {k: int(counts[0][k]) for k in DSH_RAY_COUNTS_DTYPE.names}
 
     def get(self, locations):
         """(records uint64 [n], statuses uint8 [n])"""

@@ -853,6 +853,17 @@ PYBIND11_MODULE(pysdf_tools, m) {
             if (points.size() % 3) throw std::invalid_argument("points: float32 [n, 3]");
             return g.InsertPointCloud(std::vector<float>(points.data(), points.data() + points.size()), value);
         }, py::arg("points"), py::arg("value"), "cell sets of one value; returns how many points were set")
+        .def("InsertPointCloudRays", [](DshGrid& g, const py::array_t<float, py::array::c_style | py::array::forcecast>& points,
+                                        const std::array<double, 3>& sensor_origin, double max_range, COLLISION_CELL free_value, COLLISION_CELL filled_value) {
+            if (points.size() % 3) throw std::invalid_argument("points: float32 [n, 3]");
+            const sdfgpu_dsh_ray_counts c = g.InsertPointCloudRays(std::vector<float>(points.data(), points.data() + points.size()),
+                                                                   Eigen::Vector3d(sensor_origin[0], sensor_origin[1], sensor_origin[2]), max_range, free_value, filled_value);
+            py::dict d;
+            d["rays_hit"] = c.rays_hit; d["rays_truncated"] = c.rays_truncated; d["rays_skipped"] = c.rays_skipped;
+            d["cells_carved"] = c.cells_carved; d["new_chunks"] = c.new_chunks;
+            return d;
+        }, py::arg("points"), py::arg("sensor_origin"), py::arg("max_range"), py::arg("free_value"), py::arg("filled_value"),
+           "one frame of sensor rays: free space carved up to each point, then the points filled; returns the frame's counts")
         .def("ExtractCollisionMapGrid", [](const DshGrid& g, const std::array<int64_t, 3>& lower, int64_t nx, int64_t ny, int64_t nz) {
             return g.ExtractCollisionMapGrid(VoxelGrid::GRID_INDEX(lower[0], lower[1], lower[2]), nx, ny, nz);
         }, py::arg("lower_index"), py::arg("nx"), py::arg("ny"), py::arg("nz"))

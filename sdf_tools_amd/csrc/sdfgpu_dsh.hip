@@ -1,5 +1,6 @@
 // sdfgpu_dsh.hip -- the chunk-hashed sparse collision map (sdfgpu_dsh.hpp, include/sdfgpu.h "Dynamic spatial hashed map", DESIGN.md
-// section 29): its kernels, the host orchestration of a batch, growth, and the C ABI entry points sdfgpu_dsh_*.  Compiled beside
+// sections 29 and 30): its kernels, the host orchestration of a batch and of a frame of sensor rays, growth, and the C ABI entry
+// points sdfgpu_dsh_*.  Compiled beside
 // sdfgpu.hip and linked into the same libsdfgpu.so (sdf_tools_amd/build.py).
 //
 // How the kernels of one call talk to each other: through kernel boundaries, and inside a launch through atomics only.
@@ -8,6 +9,8 @@
 //   - no kernel waits for another workgroup, and every probe loop ends after `capacity` steps
 //   - the order rule of a batch with one value per operation is a winner stamp by 64-bit atomic max (operation index + 1) that lives,
 //     between two launches, in the 8 bytes it is about to overwrite: zero the targets | stamp | decide (one flag per operation) | apply
+//   - a frame of sensor rays marks the chunks it writes into in a byte map by table position, and carves with one record: wherever
+//     several threads of a launch store to one address, they store the same value
 //
 // Arithmetic: a location on a cell boundary is placed by the rounding of g = inverse_origin * p alone, and tests/dsh_restated.py states
 // that product in numpy (separate products and sums), so nothing here may be contracted into an FMA (hipcc contracts by default).  The
@@ -63,6 +66,28 @@ __device__ __forceinline__ uint32_t dsh_find(const DshTable& t, uint64_t key) {
 
 // ---- a batch: insert keys ------------------------------------------------------------------------------------------------------------
 // counters[0] = new chunks of this batch, counters[1] = operations that found no entry (cannot happen in a table sized for the batch)
+// The position of `key` in a table this launch inserts into: the thread that makes the entry numbers the chunk and lists it.
+__device__ __forceinline__ uint32_t dsh_claim(const DshTable& t, uint64_t key, uint32_t n_live, uint32_t* __restrict__ newlist, uint32_t* counters) {
+    uint64_t pos = dsh_hash(key) & t.mask;
+    unsigned long long* const keys = reinterpret_cast<unsigned long long*>(t.keys);
+    for (uint64_t probe = 0; probe <= t.mask; ++probe) {
+        unsigned long long k = __hip_atomic_load(keys + pos, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (k == kDshEmptyKey) {
+            k = atomicCAS(keys + pos, (unsigned long long)kDshEmptyKey, (unsigned long long)key);
+            if (k == kDshEmptyKey) {                                         // this thread made the entry: it numbers the chunk
+                const uint32_t fresh = atomicAdd(&counters[0], 1u);
+                newlist[fresh] = (uint32_t)pos;
+                t.slots[pos] = n_live + fresh;                               // (read by later launches only)
+                k = key;
+            }
+        }
+        if (k == key) return (uint32_t)pos;
+        pos = (pos + 1) & t.mask;
+    }
+    atomicAdd(&counters[1], 1u);
+    return kDshNoPos;
+}
+
 template <typename LOC>
 __global__ __launch_bounds__(kDshThreads) void k_dsh_insert(const DshGeometry g, const DshTable t, const LOC* __restrict__ loc, int64_t n,
                                                             uint32_t n_live, uint32_t* __restrict__ op_pos, uint32_t* __restrict__ op_cell,
@@ -72,26 +97,8 @@ __global__ __launch_bounds__(kDshThreads) void k_dsh_insert(const DshGeometry g,
     if (i >= n) return;
     uint64_t key = 0;
     uint32_t cell = 0, found = kDshNoPos;
-    if (dsh_locate(g, (double)loc[3 * i], (double)loc[3 * i + 1], (double)loc[3 * i + 2], key, cell)) {
-        uint64_t pos = dsh_hash(key) & t.mask;
-        unsigned long long* const keys = reinterpret_cast<unsigned long long*>(t.keys);
-        bool placed = false;
-        for (uint64_t probe = 0; probe <= t.mask && !placed; ++probe) {
-            unsigned long long k = __hip_atomic_load(keys + pos, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (k == kDshEmptyKey) {
-                k = atomicCAS(keys + pos, (unsigned long long)kDshEmptyKey, (unsigned long long)key);
-                if (k == kDshEmptyKey) {                                     // this thread made the entry: it numbers the chunk
-                    const uint32_t fresh = atomicAdd(&counters[0], 1u);
-                    newlist[fresh] = (uint32_t)pos;
-                    t.slots[pos] = n_live + fresh;                           // (read by later launches only)
-                    k = key;
-                }
-            }
-            if (k == key) { found = (uint32_t)pos; placed = true; }
-            pos = (pos + 1) & t.mask;
-        }
-        if (!placed) atomicAdd(&counters[1], 1u);
-    }
+    if (dsh_locate(g, (double)loc[3 * i], (double)loc[3 * i + 1], (double)loc[3 * i + 2], key, cell))
+        found = dsh_claim(t, key, n_live, newlist, counters);
     op_pos[i] = found;
     op_cell[i] = cell;
     if (statuses) statuses[i] = found != kDshNoPos ? set_status : (uint8_t)SDFGPU_DSH_NOT_SET;
@@ -320,6 +327,178 @@ __global__ __launch_bounds__(kDshThreads) void k_dsh_export_cells(const DshPool 
     for (uint64_t k = threadIdx.x; k < cells_per_chunk; k += kDshThreads) out[(uint64_t)first + k] = cells[k];
 }
 
+// ---- a frame of sensor rays (include/sdfgpu.h "Sensor rays") ---------------------------------------------------------
+// One lane per ray.  A ray's walk is stated once (dsh_ray_begin, dsh_ray_step, dsh_ray_walk) and run twice: k_dsh_ray_insert claims
+// the key of every chunk the walk writes into, k_dsh_ray_carve repeats it and stores.  Nothing is kept per cell between the two.
+// Every array below is indexed by unrolled constants only (a == axis), so the walk's state stays in registers.
+struct DshRayWalk {
+    double gs[3], d[3];         // the sensor and end - sensor, in cells
+    double t[3];                // the parameter at which the ray crosses into the next cell along each axis (+inf: no step left)
+    double bound[3];            // that crossing's coordinate: the next cell boundary along the axis
+    double len2;
+    int64_t rem[3];             // steps left along each axis
+    int64_t c[3];               // the current cell: chunk, and cell inside the chunk
+    int32_t l[3];
+    int32_t sg[3];
+    bool is_long;
+};
+
+// SDFGPU_DSH_RAY_SKIPPED for a point that is no valid location; else _HIT or _TRUNCATED, and the walk stands on the sensor's cell
+__device__ __forceinline__ uint32_t dsh_ray_begin(const DshGeometry& g, const DshRayFrame& f, double px, double py, double pz, DshRayWalk& w) {
+    if (!(isfinite(px) && isfinite(py) && isfinite(pz))) return SDFGPU_DSH_RAY_SKIPPED;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const double* m = g.inverse + 4 * a;
+        const double ga = ((m[0] * px + m[1] * py) + m[2] * pz) + m[3];
+        const double ge = ga * g.inv_cell;
+        const double v = floor(ge);
+        const double lim = (double)(kDshChunkBias * g.n[a]);
+        if (!(v >= -lim && v < lim)) return SDFGPU_DSH_RAY_SKIPPED;
+        const int64_t diff = (int64_t)v - f.i0[a];
+        w.sg[a] = diff > 0 ? 1 : diff < 0 ? -1 : 0;
+        w.rem[a] = diff < 0 ? -diff : diff;
+        w.gs[a] = f.gs[a];
+        w.d[a] = ge - f.gs[a];
+        w.bound[a] = (double)(f.i0[a] + (diff > 0 ? 1 : 0));                   // exact: below 2^36
+        w.t[a] = diff != 0 ? (w.bound[a] - w.gs[a]) / w.d[a] : INFINITY;       // (the floors differ, so d is not 0)
+        w.c[a] = f.c0[a];
+        w.l[a] = (int32_t)f.l0[a];
+    }
+    w.len2 = (w.d[0] * w.d[0] + w.d[1] * w.d[1]) + w.d[2] * w.d[2];
+    w.is_long = w.len2 > f.range2;
+    return w.is_long ? SDFGPU_DSH_RAY_TRUNCATED : SDFGPU_DSH_RAY_HIT;
+}
+
+// One step: along the axis with the smallest crossing parameter, x before y before z.  Returns that parameter, the entry parameter
+// of the cell the walk now stands on; `chunk_changed` says whether that cell lies in another chunk.
+__device__ __forceinline__ double dsh_ray_step(const DshGeometry& g, DshRayWalk& w, bool& chunk_changed) {
+    int axis = 0;
+    double tk = w.t[0];
+    if (w.t[1] < tk) { axis = 1; tk = w.t[1]; }
+    if (w.t[2] < tk) { axis = 2; tk = w.t[2]; }
+    chunk_changed = false;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        if (a != axis) continue;
+        w.bound[a] += (double)w.sg[a];
+        w.rem[a] -= 1;
+        w.t[a] = w.rem[a] != 0 ? (w.bound[a] - w.gs[a]) / w.d[a] : INFINITY;
+        w.l[a] += w.sg[a];
+        if (w.l[a] < 0) { w.l[a] = (int32_t)g.n[a] - 1; w.c[a] -= 1; chunk_changed = true; }
+        else if (w.l[a] >= (int32_t)g.n[a]) { w.l[a] = 0; w.c[a] += 1; chunk_changed = true; }
+    }
+    return tk;
+}
+
+__device__ __forceinline__ uint32_t dsh_ray_cell(const DshGeometry& g, const DshRayWalk& w) {
+    return (uint32_t)((w.l[0] * (int32_t)g.n[1] + w.l[1]) * (int32_t)g.n[2] + w.l[2]);
+}
+
+// The cells a ray writes, in walk order: cell(chunk_changed, is_hit) for each.  A ray that is not long carves c_0 .. c_(N-1) and
+// hits c_N; a long one carves the prefix of c_0 .. c_N whose entry parameters are in range.  Returns how many cells it carved.
+// The loop ends with the steps left (rem) or the range; max_steps is a guard that neither can pass.
+template <class Cell>
+__device__ __forceinline__ uint32_t dsh_ray_walk(const DshGeometry& g, const DshRayFrame& f, DshRayWalk& w, Cell&& cell) {
+    uint32_t carved = 0;
+    bool chunk_changed = true;                                                // (the first cell: its chunk has not been looked up)
+    for (uint64_t step = 0; step <= f.max_steps; ++step) {
+        const bool last = (w.rem[0] | w.rem[1] | w.rem[2]) == 0;
+        if (last && !w.is_long) { cell(chunk_changed, true); break; }
+        cell(chunk_changed, false);
+        ++carved;
+        if (last) break;
+        const double tk = dsh_ray_step(g, w, chunk_changed);
+        if (w.is_long && !((tk * tk) * w.len2 <= f.range2)) break;
+    }
+    return carved;
+}
+
+// counters: [0] new chunks, [1] lost operations (uint32); from byte 8 on, four uint64: rays hit, truncated, skipped, cells carved
+constexpr int kDshRayCounts = 4;
+
+__device__ __forceinline__ uint32_t dsh_wave_sum(uint32_t v) {
+    for (int off = 32; off > 0; off >>= 1) v += (uint32_t)__shfl_down((int)v, off);
+    return v;                                                                 // (lane 0 holds the sum)
+}
+
+// The chunks the frame's rays can enter, summed over the rays (dsh_ray_chunks: arithmetic on a ray's two ends, no walk) into the
+// uint64 at byte 8 of the counters.  Run only where the bound that needs no ray would make the table grow.
+__global__ __launch_bounds__(kDshThreads) void k_dsh_ray_count(const DshGeometry g, const DshRayFrame f, const float* __restrict__ points, int64_t n,
+                                                               uint32_t* counters) {
+    const int64_t i = dsh_item();
+    uint32_t chunks = 0;
+    if (i < n) {
+        DshRayWalk w;
+        if (dsh_ray_begin(g, f, (double)points[3 * i], (double)points[3 * i + 1], (double)points[3 * i + 2], w) != SDFGPU_DSH_RAY_SKIPPED) {
+            const int64_t i1[3] = {f.i0[0] + w.sg[0] * w.rem[0], f.i0[1] + w.sg[1] * w.rem[1], f.i0[2] + w.sg[2] * w.rem[2]};
+            chunks = (uint32_t)dsh_ray_chunks(f.i0, i1, g.n, w.is_long, f.range_cells);      // at most 1 + 3 * 2^21
+        }
+    }
+    const uint32_t sum = dsh_wave_sum(chunks);                               // at most 64 * (1 + 3 * 2^21): fits
+    if ((threadIdx.x & 63) == 0 && sum) atomicAdd(reinterpret_cast<unsigned long long*>(counters + 2), (unsigned long long)sum);
+}
+
+__global__ __launch_bounds__(kDshThreads) void k_dsh_ray_insert(const DshGeometry g, const DshTable t, const DshRayFrame f,
+                                                                const float* __restrict__ points, int64_t n, uint32_t n_live,
+                                                                uint32_t* __restrict__ op_pos, uint32_t* __restrict__ op_cell,
+                                                                uint32_t* __restrict__ newlist, uint8_t* __restrict__ marks, uint32_t* counters,
+                                                                uint8_t* __restrict__ statuses) {
+    const int64_t i = dsh_item();
+    uint32_t status = SDFGPU_DSH_RAY_SKIPPED, carved = 0;
+    if (i < n) {
+        DshRayWalk w;
+        uint32_t pos = kDshNoPos, hit_pos = kDshNoPos, hit_cell = 0;
+        status = dsh_ray_begin(g, f, (double)points[3 * i], (double)points[3 * i + 1], (double)points[3 * i + 2], w);
+        if (status != SDFGPU_DSH_RAY_SKIPPED)
+            carved = dsh_ray_walk(g, f, w, [&](bool chunk_changed, bool is_hit) {
+                if (chunk_changed) {
+                    pos = dsh_claim(t, dsh_pack_key(w.c[0], w.c[1], w.c[2]), n_live, newlist, counters);
+                    if (pos != kDshNoPos) marks[pos] = 1;                      // (every writer stores the same byte)
+                }
+                if (is_hit) { hit_pos = pos; hit_cell = dsh_ray_cell(g, w); }
+            });
+        op_pos[i] = hit_pos;
+        op_cell[i] = hit_cell;
+        if (statuses) statuses[i] = (uint8_t)status;
+    }
+    // the frame's counts: one atomic per wave and count (lanes behind the last ray count as nothing)
+    const bool live = i < n;
+    const unsigned long long hit = __ballot(live && status == SDFGPU_DSH_RAY_HIT), cut = __ballot(live && status == SDFGPU_DSH_RAY_TRUNCATED),
+                             skipped = __ballot(live && status == SDFGPU_DSH_RAY_SKIPPED);
+    const uint32_t sum = dsh_wave_sum(carved);                               // at most 64 * (3 * 65538 + 3): fits
+    if ((threadIdx.x & 63) == 0) {
+        unsigned long long* const counts = reinterpret_cast<unsigned long long*>(counters + 2);
+        if (hit) atomicAdd(&counts[0], (unsigned long long)__popcll(hit));
+        if (cut) atomicAdd(&counts[1], (unsigned long long)__popcll(cut));
+        if (skipped) atomicAdd(&counts[2], (unsigned long long)__popcll(skipped));
+        if (sum) atomicAdd(&counts[3], (unsigned long long)sum);
+    }
+}
+
+// the chunks the frame writes into, by table position -> the touched flag k_dsh_expand reads (one thread per position)
+__global__ __launch_bounds__(kDshThreads) void k_dsh_ray_touch(const DshTable t, DshChunkHead* heads, const uint8_t* __restrict__ marks) {
+    const uint64_t pos = (uint64_t)dsh_item();
+    if (pos <= t.mask && marks[pos]) heads[t.slots[pos]].state |= kDshTouched;
+}
+
+// the walk again: every carved cell gets `free_value`.  All writers store the same record, so their order cannot matter; the hits
+// follow behind a kernel boundary (k_dsh_store_one).
+__global__ __launch_bounds__(kDshThreads) void k_dsh_ray_carve(const DshGeometry g, const DshTable t, const DshPool p, const DshRayFrame f,
+                                                               const float* __restrict__ points, int64_t n, uint64_t free_value) {
+    const int64_t i = dsh_item();
+    if (i >= n) return;
+    DshRayWalk w;
+    if (dsh_ray_begin(g, f, (double)points[3 * i], (double)points[3 * i + 1], (double)points[3 * i + 2], w) == SDFGPU_DSH_RAY_SKIPPED) return;
+    uint64_t* cells = nullptr;
+    (void)dsh_ray_walk(g, f, w, [&](bool chunk_changed, bool is_hit) {
+        if (chunk_changed) {
+            const uint32_t pos = dsh_find(t, dsh_pack_key(w.c[0], w.c[1], w.c[2]));
+            cells = pos != kDshNoPos ? p.cells + (uint64_t)t.slots[pos] * (uint64_t)g.cells_per_chunk : nullptr;
+        }
+        if (!is_hit && cells) cells[dsh_ray_cell(g, w)] = free_value;
+    });
+}
+
 dim3 dsh_chunk_grid(uint64_t chunks) {                                        // one workgroup per chunk
     if (chunks <= (uint64_t)kDshGridX) return dim3((unsigned)std::max<uint64_t>(chunks, 1));
     return dim3((unsigned)kDshGridX, (unsigned)((chunks + kDshGridX - 1) / kDshGridX));
@@ -378,8 +557,9 @@ int dsh_alloc_pool(sdfgpu_handle h, uint64_t chunks, uint64_t cells_per_chunk, D
 uint32_t* dsh_counters(sdfgpu_dsh_map_object* m) { return static_cast<uint32_t*>(m->scratch.ptr); }
 
 // the table for `chunks` keys: grown (new table, rehash kernel) when it is too small.  Refused before anything changes when the
-// larger table would pass the byte limit.
-int dsh_reserve_table(sdfgpu_dsh_map_object* m, uint64_t chunks, hipStream_t st) {
+// larger table would pass the byte limit.  With `kept`, a table that was replaced is handed to the caller instead of being freed
+// (kept->keys stays null when the table did not grow): a call that may still be refused puts it back, and nothing has changed.
+int dsh_reserve_table(sdfgpu_dsh_map_object* m, uint64_t chunks, hipStream_t st, DshTable* kept = nullptr, uint64_t* kept_cap = nullptr) {
     sdfgpu_handle h = m->h;
     const uint64_t want = dsh_table_capacity(chunks);
     if (want <= m->table_cap) return SDFGPU_OK;
@@ -398,7 +578,8 @@ int dsh_reserve_table(sdfgpu_dsh_map_object* m, uint64_t chunks, hipStream_t st)
     }
     HIP_TRY(h, hipStreamSynchronize(st));                                       // (the old table may still be read by pending work)
     if (lost) { (void)rz_free(h, grown.keys); return fail(h, SDFGPU_ERR_HIP, "dsh: the rehash lost %u keys (internal error)", lost); }
-    if (int rc = rz_free(h, m->table.keys)) return rc;
+    if (kept) { *kept = m->table; *kept_cap = m->table_cap; }
+    else if (int rc = rz_free(h, m->table.keys)) return rc;
     m->table = grown;
     m->table_cap = want;
     return SDFGPU_OK;
@@ -510,6 +691,130 @@ int dsh_batch(sdfgpu_dsh_map_object* m, bool chunk_sets, const LOC* d_loc, int64
         hipLaunchKernelGGL((k_dsh_apply<true>), grid, block, 0, st, m->table, m->pool, cpc, op_pos, op_cell, n, wins, values);
     }
     HIP_TRY(h, hipGetLastError());
+    return SDFGPU_OK;
+}
+
+// What a frame of rays is refused for before anything is enqueued, and what the host works out about the sensor (in the arithmetic
+// of dsh_locate: this file is compiled without contraction).
+int dsh_ray_frame(sdfgpu_dsh_map_object* m, const double* sensor, int64_t n, double max_range, const void* free_value, const void* hit_value,
+                  DshRayFrame& f, uint64_t& range_cells) {
+    sdfgpu_handle h = m->h;
+    if (n < 0 || n >= kDshMaxBatch) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: a frame holds 0 .. 2^31 - 1 rays (got %lld)", (long long)n);
+    if (!sensor || !free_value || !hit_value) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: insert_rays needs the sensor, the free record and the hit record");
+    const DshGeometry& g = m->g;
+    const double range = max_range * g.inv_cell;
+    if (!(range > 0.0 && range <= kDshMaxRangeCells))
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: max_range must span more than 0 and at most 65536 cells (got %g, %g cells)", max_range, range);
+    if (!(std::isfinite(sensor[0]) && std::isfinite(sensor[1]) && std::isfinite(sensor[2])))
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: the sensor position is not finite");
+    for (int a = 0; a < 3; ++a) {
+        const double* row = g.inverse + 4 * a;
+        const double ga = ((row[0] * sensor[0] + row[1] * sensor[1]) + row[2] * sensor[2]) + row[3];
+        f.gs[a] = ga * g.inv_cell;
+        const double v = std::floor(f.gs[a]);
+        const double lim = (double)(kDshChunkBias * g.n[a]);
+        if (!(v >= -lim && v < lim)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: the sensor position is not a valid location of the map");
+        f.i0[a] = (int64_t)v;
+        f.c0[a] = dsh_floor_div(f.i0[a], g.n[a]);
+        f.l0[a] = f.i0[a] - f.c0[a] * g.n[a];
+    }
+    f.range2 = range * range;
+    range_cells = (uint64_t)std::ceil(range);
+    f.range_cells = range_cells;
+    f.max_steps = dsh_ray_max_steps(range_cells);
+    return SDFGPU_OK;
+}
+
+// One frame of rays on `st` (the frame was checked by dsh_ray_frame).
+int dsh_rays_impl(sdfgpu_dsh_map_object* m, const DshRayFrame& f, uint64_t range_cells, const float* d_points, int64_t n, const void* free_value,
+                  const void* hit_value, uint8_t* d_statuses, sdfgpu_dsh_ray_counts* out_counts, hipStream_t st) {
+    sdfgpu_handle h = m->h;
+    if (out_counts) *out_counts = sdfgpu_dsh_ray_counts{};
+    if (n == 0) return SDFGPU_OK;
+    if (!d_points) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: null points");
+    if (reinterpret_cast<uintptr_t>(d_points) & 3) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: the points are not aligned for their type");
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, m->order.create());
+    HIP_TRY(h, m->order.wait(st));
+    StreamOrder::RecordAtExit record_at_exit{m->order, st};
+
+    // the table cannot fill while the frame inserts: it is sized for every chunk the rays can enter.  Where the bound that needs no
+    // ray would make it grow, the rays are counted first (one more read-back)
+    uint64_t bound = dsh_ray_chunk_bound((uint64_t)n, range_cells, m->g.n);
+    if (bound > ((uint64_t)1 << 30) || dsh_table_capacity(m->n_live + bound) > m->table_cap) {
+        unsigned long long by_rays = 0;
+        HIP_TRY(h, hipMemsetAsync(dsh_counters(m), 0, kDshCounterBytes, st));
+        hipLaunchKernelGGL(k_dsh_ray_count, dsh_grid(n), dim3(kDshThreads), 0, st, m->g, f, d_points, n, dsh_counters(m));
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipMemcpyAsync(&by_rays, dsh_counters(m) + 2, sizeof by_rays, hipMemcpyDeviceToHost, st));
+        HIP_TRY(h, hipStreamSynchronize(st));
+        bound = std::min<uint64_t>(bound, by_rays);
+    }
+    if (m->n_live + bound > ((uint64_t)1 << 30))
+        return fail(h, SDFGPU_ERR_UNSUPPORTED_SIZE, "dsh: a frame of %lld rays of %llu cells may enter %llu chunks: more than a table holds", (long long)n,
+                    (unsigned long long)range_cells, (unsigned long long)bound);
+    const uint64_t table_cap = std::max(m->table_cap, dsh_table_capacity(m->n_live + bound));
+    const size_t un = (size_t)n;
+    const size_t off_pos = kDshCounterBytes, off_cell = off_pos + align256(un * 4), off_new = off_cell + align256(un * 4),
+                 off_marks = off_new + align256((size_t)table_cap * 4);
+    if (int rc = ensure(h, m->scratch, off_marks + align256((size_t)table_cap), "dsh batch scratch")) return rc;
+    DshTable old_table{};
+    uint64_t old_cap = 0;
+    if (int rc = dsh_reserve_table(m, m->n_live + bound, st, &old_table, &old_cap)) return rc;
+    char* const base = static_cast<char*>(m->scratch.ptr);
+    uint32_t* const counters = dsh_counters(m);
+    uint32_t* const op_pos = reinterpret_cast<uint32_t*>(base + off_pos);
+    uint32_t* const op_cell = reinterpret_cast<uint32_t*>(base + off_cell);
+    uint32_t* const newlist = reinterpret_cast<uint32_t*>(base + off_new);
+    uint8_t* const marks = reinterpret_cast<uint8_t*>(base + off_marks);
+    const dim3 grid = dsh_grid(n), block(kDshThreads);
+    const uint64_t cpc = (uint64_t)m->g.cells_per_chunk;
+
+    struct { uint32_t n_new, lost; unsigned long long counts[kDshRayCounts]; } back{};
+    static_assert(sizeof back == 8 + 8 * kDshRayCounts && sizeof back <= kDshCounterBytes, "the counters' layout");
+    // walk A, the read-back of the new-chunk count and the pool: until the pool is reserved the frame can still be refused
+    const int rc = [&]() -> int {
+        HIP_TRY(h, hipMemsetAsync(counters, 0, kDshCounterBytes, st));
+        HIP_TRY(h, hipMemsetAsync(marks, 0, (size_t)m->table_cap, st));
+        hipLaunchKernelGGL(k_dsh_ray_insert, grid, block, 0, st, m->g, m->table, f, d_points, n, (uint32_t)m->n_live, op_pos, op_cell, newlist, marks, counters,
+                           d_statuses);
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipMemcpyAsync(&back, counters, sizeof back, hipMemcpyDeviceToHost, st));
+        HIP_TRY(h, hipStreamSynchronize(st));
+        if (back.lost) return fail(h, SDFGPU_ERR_HIP, "dsh: %u chunk keys found no table entry (internal error)", back.lost);
+        return dsh_reserve_pool(m, m->n_live + back.n_new, st);
+    }();
+    if (rc != SDFGPU_OK) {                                                      // refused: the table is the one the frame found
+        (void)hipStreamSynchronize(st);
+        if (old_table.keys) {
+            (void)rz_free(h, m->table.keys);
+            m->table = old_table;
+            m->table_cap = old_cap;
+        } else if (back.n_new) {
+            hipLaunchKernelGGL(k_dsh_rollback, dsh_grid(back.n_new), block, 0, st, m->table, newlist, back.n_new);
+            (void)hipStreamSynchronize(st);
+        }
+        return rc;
+    }
+    if (old_table.keys) (void)rz_free(h, old_table.keys);
+    const uint32_t n_new = back.n_new;
+    if (n_new) hipLaunchKernelGGL(k_dsh_init_new, dsh_grid(n_new), block, 0, st, m->table, m->pool.heads, newlist, n_new, (uint32_t)m->n_live);
+    m->n_live += n_new;
+    uint64_t free_record = 0, hit_record = 0;
+    memcpy(&free_record, free_value, 8);
+    memcpy(&hit_record, hit_value, 8);
+    hipLaunchKernelGGL(k_dsh_ray_touch, dsh_grid((int64_t)m->table_cap), block, 0, st, m->table, m->pool.heads, marks);
+    hipLaunchKernelGGL(k_dsh_expand, dsh_chunk_grid(m->n_live), block, 0, st, m->pool, m->n_live, cpc, m->g.default_record);
+    hipLaunchKernelGGL(k_dsh_ray_carve, grid, block, 0, st, m->g, m->table, m->pool, f, d_points, n, free_record);
+    hipLaunchKernelGGL((k_dsh_store_one<false>), grid, block, 0, st, m->table, m->pool, cpc, op_pos, op_cell, n, hit_record);
+    HIP_TRY(h, hipGetLastError());
+    if (out_counts) {
+        out_counts->rays_hit = back.counts[0];
+        out_counts->rays_truncated = back.counts[1];
+        out_counts->rays_skipped = back.counts[2];
+        out_counts->cells_carved = back.counts[3];
+        out_counts->new_chunks = n_new;
+    }
     return SDFGPU_OK;
 }
 
@@ -731,6 +1036,39 @@ int sdfgpu_dsh_insert_points_device(sdfgpu_dsh_map map, const float* d_points, i
     return dsh_entry(map, stream, [&]() -> int {
         if (!one_value) return fail(map->h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: insert_points needs its one record");
         return dsh_batch<float>(map, false, d_points, n, nullptr, one_value, d_statuses, (hipStream_t)stream);
+    });
+}
+
+int sdfgpu_dsh_insert_rays_device(sdfgpu_dsh_map map, const double sensor[3], const float* d_points, int64_t n, double max_range, const void* free_value,
+                                  const void* hit_value, uint8_t* d_statuses, sdfgpu_dsh_ray_counts* out_counts, void* stream) {
+    return dsh_entry(map, stream, [&]() -> int {
+        DshRayFrame f{};
+        uint64_t range_cells = 0;
+        if (int rc = dsh_ray_frame(map, sensor, n, max_range, free_value, hit_value, f, range_cells)) return rc;
+        return dsh_rays_impl(map, f, range_cells, d_points, n, free_value, hit_value, d_statuses, out_counts, (hipStream_t)stream);
+    });
+}
+
+int sdfgpu_dsh_insert_rays(sdfgpu_dsh_map map, const double sensor[3], const float* points, int64_t n, double max_range, const void* free_value,
+                           const void* hit_value, uint8_t* statuses, sdfgpu_dsh_ray_counts* out_counts) {
+    return dsh_entry(map, nullptr, [&]() -> int {
+        sdfgpu_handle h = map->h;
+        DshRayFrame f{};
+        uint64_t range_cells = 0;
+        if (int rc = dsh_ray_frame(map, sensor, n, max_range, free_value, hit_value, f, range_cells)) return rc;
+        if (n == 0) return dsh_rays_impl(map, f, range_cells, nullptr, 0, free_value, hit_value, nullptr, out_counts, nullptr);
+        if (!points) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: null points");
+        HIP_TRY(h, hipSetDevice(h->device));
+        HIP_TRY(h, map->order.wait(nullptr));
+        DshStage s;
+        const size_t un = (size_t)n, at_pts = s.add(un * 12), at_st = s.add(statuses ? un : 0);
+        if (int rc = ensure(h, map->stage, s.total, "dsh staging")) return rc;
+        char* const base = static_cast<char*>(map->stage.ptr);
+        if (int rc = copy_from_host(h, base + at_pts, points, un * 12)) return rc;
+        if (int rc = dsh_rays_impl(map, f, range_cells, reinterpret_cast<const float*>(base + at_pts), n, free_value, hit_value,
+                                   statuses ? reinterpret_cast<uint8_t*>(base + at_st) : nullptr, out_counts, nullptr)) return rc;
+        if (statuses) return copy_to_host(h, statuses, base + at_st, un);
+        return SDFGPU_OK;
     });
 }
 

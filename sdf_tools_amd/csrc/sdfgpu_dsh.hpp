@@ -1,7 +1,8 @@
 // sdfgpu_dsh.hpp -- the chunk-hashed sparse collision map (include/sdfgpu.h "Dynamic spatial hashed map"): its
 // constants, the packing of a chunk coordinate into a table key, the hash, and the planning of the table's and the pool's sizes.
 // Plain C++ without a HIP header, as sdfgpu_plan.hpp and sdfgpu_policy.hpp are: sdfgpu_dsh.hip includes it for its kernels and its host
-// code, and tests/dsh_plan_harness.cpp drives the arithmetic on the CPU under -fsanitize=address,undefined.
+// code, and tests/dsh_plan_harness.cpp and tests/dsh_rays_plan_harness.cpp drive the arithmetic on the CPU under
+// -fsanitize=address,undefined.
 #pragma once
 #include <stdint.h>
 
@@ -82,6 +83,48 @@ inline bool dsh_plan_pool(uint64_t capacity, uint64_t needed, uint64_t cells_per
     return true;
 }
 
+// ---- a frame of sensor rays ------------------------------------------------------------------------------------------
+constexpr double kDshMaxRangeCells = 65536.0;              // R = max_range / cell_size lies in (0, 65536]
+constexpr uint64_t kDshRayBoundCap = (uint64_t)1 << 62;    // where the bound below saturates
+
+// Along one axis a ray writes cells whose boundary lies within R (1 + a few ulp) cells of the sensor, and one more: at most
+// ceil(R) + 2 steps.  `range_cells` is that ceil(R), at most 65536.
+SDFGPU_DSH_HD uint64_t dsh_ray_axis_steps(uint64_t range_cells) { return range_cells + 2; }
+
+// How many chunks one ray from global cell i0 to i1 can write into.  Its walk is monotone along every axis, so it crosses each chunk
+// boundary between its two ends once: a ray that is not long enters exactly this many chunks.  A long ray stops inside the range.
+SDFGPU_DSH_HD uint64_t dsh_ray_chunks(const int64_t i0[3], const int64_t i1[3], const int64_t n[3], bool is_long, uint64_t range_cells) {
+    uint64_t chunks = 1;
+    for (int a = 0; a < 3; ++a) {
+        const int64_t c0 = dsh_floor_div(i0[a], n[a]), c1 = dsh_floor_div(i1[a], n[a]);
+        uint64_t across = (uint64_t)(c1 > c0 ? c1 - c0 : c0 - c1);                          // at most 2^21
+        const uint64_t within = dsh_ray_axis_steps(range_cells) / (uint64_t)n[a] + 1;
+        if (is_long && across > within) across = within;
+        chunks += across;
+    }
+    return chunks;
+}
+
+// Steps of one ray's walk that cannot be passed (the kernels' loop guard; the walk ends earlier by itself).
+inline uint64_t dsh_ray_max_steps(uint64_t range_cells) { return 3 * dsh_ray_axis_steps(range_cells) + 2; }
+
+// How many chunks a frame of `rays` rays of at most `range_cells` cells can enter, whatever the map holds: the smaller of
+//   rays * (1 + sum over the axes of (steps / n_a + 1))    a ray changes chunk along an axis once per n_a steps, and once more
+//   product over the axes of ((2 steps) / n_a + 2)         every cell lies within `steps` cells of the sensor's cell
+// saturating at kDshRayBoundCap.  The table of a frame is sized for the live chunks plus this; where that would make the table
+// grow, the frame's rays are counted first (the sum of dsh_ray_chunks) and the smaller of the two numbers sizes it.
+inline uint64_t dsh_ray_chunk_bound(uint64_t rays, uint64_t range_cells, const int64_t n[3]) {
+    const uint64_t steps = dsh_ray_axis_steps(range_cells);
+    uint64_t per_ray = 1, box = 1;
+    for (int a = 0; a < 3; ++a) {
+        per_ray += steps / (uint64_t)n[a] + 1;                                 // at most 1 + 3 * 65539
+        const uint64_t across = (2 * steps) / (uint64_t)n[a] + 2;               // at most 131078: three of them stay below 2^52
+        box *= across;
+    }
+    const uint64_t by_rays = rays > kDshRayBoundCap / per_ray ? kDshRayBoundCap : rays * per_ray;
+    return by_rays < box ? by_rays : box;
+}
+
 // ---- what the kernels are told ----------------------------------------------------------------------------------------------------------
 struct DshGeometry {
     double inverse[12];         // rows 0 - 2 of the inverse origin transform, row-major
@@ -100,6 +143,17 @@ struct DshTable {
 struct DshPool {
     DshChunkHead* heads;        // [capacity in chunks]
     uint64_t* cells;            // [capacity in chunks][cells_per_chunk]
+};
+
+// A frame of sensor rays: what the host worked out about the sensor, once for all rays.
+struct DshRayFrame {
+    double gs[3];               // the sensor in grid coordinates (cells, before the floor)
+    int64_t i0[3];              // floor(gs): the sensor's global cell
+    int64_t c0[3];              // its chunk
+    int64_t l0[3];              // its cell inside the chunk
+    double range2;              // R * R, R in cells
+    uint64_t range_cells;       // ceil(R)
+    uint64_t max_steps;         // dsh_ray_max_steps
 };
 
 constexpr int kDshThreads = 256;
