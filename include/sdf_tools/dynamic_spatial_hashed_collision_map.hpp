@@ -205,6 +205,34 @@ public:
         return counts;
     }
 
+    // The sensor model of FusePointCloudRays: how much one return (prob_hit) and one ray passing through (prob_miss) say about a
+    // cell, and where the occupancy is clamped.  The defaults are octomap's.  All four lie in [0.001, 0.999], clamp_min <= clamp_max.
+    struct SensorModel {
+        float prob_hit, prob_miss, clamp_min, clamp_max;
+        SensorModel() : prob_hit(0.7f), prob_miss(0.4f), clamp_min(0.12f), clamp_max(0.97f) {}
+        SensorModel(float hit, float miss, float min, float max) : prob_hit(hit), prob_miss(miss), clamp_min(min), clamp_max(max) {}
+    };
+
+    // One frame of a range sensor fused into the occupancies (an addition; include/sdfgpu.h "Sensor rays: fusion", DESIGN.md section
+    // 31): the rays are those of InsertPointCloudRays, but every cell they pass is updated once with prob_miss and every cell a
+    // point falls into once with prob_hit (Bayes' rule on the clamped occupancy; the component word of a cell is kept), so evidence
+    // accumulates over frames where InsertPointCloudRays overwrites.  std::invalid_argument, and nothing written, for a model outside
+    // its domain and for what InsertPointCloudRays refuses.  Returns the frame's counts.  The contract is this project's own,
+    // UNVERIFIED against octomap's insertPointCloud.
+    sdfgpu_dsh_ray_counts FusePointCloudRays(const std::vector<float>& points_xyz, const Eigen::Vector3d& sensor_origin, const double max_range,
+                                             const SensorModel model = SensorModel()) {
+        RequireInitialized();
+        if (points_xyz.size() % 3) throw std::invalid_argument("FusePointCloudRays: points are x, y, z triples");
+        const double sensor[3] = {sensor_origin.x(), sensor_origin.y(), sensor_origin.z()};
+        const sdfgpu_dsh_sensor_model raw = {model.prob_hit, model.prob_miss, model.clamp_min, model.clamp_max};
+        sdfgpu_dsh_ray_counts counts = sdfgpu_dsh_ray_counts();
+        Locked([&](sdfgpu_dsh_map m) {
+            return sdfgpu_dsh_fuse_rays(m, sensor, points_xyz.data(), (int64_t)(points_xyz.size() / 3), max_range, &raw, nullptr, &counts);
+        });
+        if (counts.rays_hit + counts.rays_truncated) components_valid_ = false;
+        return counts;
+    }
+
     // ---- dense windows (additions) ------------------------------------------------------------------------------------------------------
     // The nx x ny x nz cells from global cell lower_index on as a CollisionMapGrid: cell (x, y, z) is what Get returns there.  The
     // result's origin is the map's origin times the translation to that corner; its OOB value is the map's default.

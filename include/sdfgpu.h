@@ -1047,8 +1047,8 @@ int sdfgpu_display_select_contour(sdfgpu_handle h, const void* cells, size_t cel
  * leaves the map's content as it was.  initial_chunks (0 = 64) sizes the first pool.  Errors go to the handle's
  * sdfgpu_last_error.
  *
- * Streams: the _device forms run on the caller's stream.  The two setters, sdfgpu_dsh_insert_points_device and
- * sdfgpu_dsh_insert_rays_device synchronise that stream once (they read the number of new chunks back before the pool may grow;
+ * Streams: the _device forms run on the caller's stream.  The two setters, sdfgpu_dsh_insert_points_device,
+ * sdfgpu_dsh_insert_rays_device and sdfgpu_dsh_fuse_rays_device synchronise that stream once (they read the number of new chunks back before the pool may grow;
  * a call that grows the table or the pool synchronises once more per growth), sdfgpu_dsh_info and the two export forms
  * synchronise too (they read counts back); sdfgpu_dsh_get_device and sdfgpu_dsh_extract_window_device return with their kernels
  * pending.  Calls on one map from different streams are ordered by the map (an event behind its last call); one host thread
@@ -1146,6 +1146,51 @@ int sdfgpu_dsh_insert_rays_device(sdfgpu_dsh_map map, const double sensor[3], co
                                   void* stream);
 int sdfgpu_dsh_insert_rays(sdfgpu_dsh_map map, const double sensor[3], const float* points, int64_t n, double max_range,
                            const void* free_value, const void* hit_value, uint8_t* statuses, sdfgpu_dsh_ray_counts* out_counts);
+
+/* Sensor rays: fusion.  One frame of a range sensor folded into the cells' occupancies as evidence, where
+ * the carve above overwrites them: a cell seen occupied once among many free sightings stays free, and an obstacle that left
+ * fades over a few frames.  The contract is this project's own, UNVERIFIED against octomap's insertPointCloud / updateNode and
+ * against arc_utilities; tests/dsh_fusion_restated.py restates it.
+ *
+ * Everything about the rays is the section above, unchanged: grid coordinates, the walk and its tie order, the range prefix, long,
+ * hit and skipped rays, the status bytes, the whole-call refusals (sensor, R outside (0, 65536]), n in 0 .. 2^31 - 1, how the
+ * table and the pool are sized, what byte_limit refuses and leaves behind, the stream behaviour, and sdfgpu_dsh_ray_counts with the
+ * same meanings (cells_carved with multiplicity).  What differs is what the frame does to the cells:
+ *   - H is the set of the frame's hit cells; M the set of cells carved by at least one ray, without H
+ *   - the frame leaves the map as SetCell(c, fuse(Get(c), prob_hit)) for every c in H and SetCell(c, fuse(Get(c), prob_miss)) for
+ *     every c in M: each cell is updated once, whatever the number of rays through it, and a hit beats a miss
+ *   - Get(c) is the record before the frame: the default for an absent chunk, the chunk's record for a chunk-filled one; those
+ *     chunks become cell-filled as SetCell makes them.  Every other cell of a touched chunk keeps its bytes (NaN payloads too)
+ *   - only the occupancy word (the low 4 bytes) of an updated record changes; the component word is kept
+ *   - fuse(p, m) in IEEE float32, every operation rounded by itself (no FMA), the division correctly rounded:
+ *         q = p >= clamp_min ? p : clamp_min          (a NaN becomes clamp_min)
+ *         q = q <= clamp_max ? q : clamp_max
+ *         a = q * m
+ *         b = (1.0f - q) * (1.0f - m)                 (1.0f - m is computed once, in float)
+ *         r = a / (a + b)
+ *         r = r >= clamp_min ? r : clamp_min
+ *         r = r <= clamp_max ? r : clamp_max
+ *     Bayes' rule in probability space: octomap's log-odds addition without logf / expf.  Clamping before the update is what lets
+ *     a default of 0.0 or 1.0 ever change
+ *   - the whole call is refused with SDFGPU_ERR_INVALID_ARGUMENT, nothing written, unless prob_hit, prob_miss, clamp_min and
+ *     clamp_max all lie in [0.001f, 0.999f] and clamp_min <= clamp_max (a NaN fails).  Inside that domain no product is below
+ *     1e-6: no operand is denormal and a + b > 0.  prob_miss <= 0.5 <= prob_hit is not required
+ * Memory: a map that has taken a fused frame keeps a mark plane, one byte per cell of the pool's capacity (an eighth of the
+ * pool's cell bytes) ON TOP of what byte_limit bounds; sdfgpu_dsh_info counts it in scratch_bytes, not in bytes_held.  It is made
+ * by the first fused frame and grows with the pool at a fused frame; where it cannot be allocated the frame is refused and the
+ * map, its table and its pool are as they were. */
+typedef struct sdfgpu_dsh_sensor_model {
+    float prob_hit;              /* octomap's defaults: 0.7 */
+    float prob_miss;             /*                     0.4 */
+    float clamp_min;             /*                     0.12 */
+    float clamp_max;             /*                     0.97 */
+} sdfgpu_dsh_sensor_model;
+
+int sdfgpu_dsh_fuse_rays_device(sdfgpu_dsh_map map, const double sensor[3], const float* d_points, int64_t n, double max_range,
+                                const sdfgpu_dsh_sensor_model* model, uint8_t* d_statuses, sdfgpu_dsh_ray_counts* out_counts,
+                                void* stream);
+int sdfgpu_dsh_fuse_rays(sdfgpu_dsh_map map, const double sensor[3], const float* points, int64_t n, double max_range,
+                         const sdfgpu_dsh_sensor_model* model, uint8_t* statuses, sdfgpu_dsh_ray_counts* out_counts);
 
 /* Get for n locations: 8-byte records and / or one status byte each (SDFGPU_DSH_NOT_FOUND / FOUND_IN_CHUNK / FOUND_IN_CELL);
  * either output may be null, not both. */

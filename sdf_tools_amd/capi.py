@@ -45,7 +45,8 @@ EXPORTS = [
     "sdfgpu_rasterize_solid_meshes_device", "sdfgpu_rasterize_solid_meshes", "sdfgpu_check_closed_meshes",
     "sdfgpu_dsh_create", "sdfgpu_dsh_destroy", "sdfgpu_dsh_info",
     "sdfgpu_dsh_set_cells_device", "sdfgpu_dsh_set_cells", "sdfgpu_dsh_set_chunks_device", "sdfgpu_dsh_set_chunks",
-    "sdfgpu_dsh_insert_points_device", "sdfgpu_dsh_insert_rays_device", "sdfgpu_dsh_insert_rays", "sdfgpu_dsh_get_device", "sdfgpu_dsh_get",
+    "sdfgpu_dsh_insert_points_device", "sdfgpu_dsh_insert_rays_device", "sdfgpu_dsh_insert_rays", "sdfgpu_dsh_fuse_rays_device", "sdfgpu_dsh_fuse_rays",
+    "sdfgpu_dsh_get_device", "sdfgpu_dsh_get",
     "sdfgpu_dsh_extract_window_device", "sdfgpu_dsh_extract_window", "sdfgpu_dsh_export_device", "sdfgpu_dsh_export",
 ]
 
@@ -203,6 +204,8 @@ def load_library():
     L.sdfgpu_dsh_insert_points_device.argtypes = [vp, vp, i64, vp, vp, vp]
     L.sdfgpu_dsh_insert_rays_device.argtypes = [vp, vp, vp, i64, dbl, vp, vp, vp, vp, vp]
     L.sdfgpu_dsh_insert_rays.argtypes = [vp, vp, vp, i64, dbl, vp, vp, vp, vp]
+    L.sdfgpu_dsh_fuse_rays_device.argtypes = [vp, vp, vp, i64, dbl, vp, vp, vp, vp]
+    L.sdfgpu_dsh_fuse_rays.argtypes = [vp, vp, vp, i64, dbl, vp, vp, vp]
     L.sdfgpu_dsh_get_device.argtypes = [vp, vp, i64, vp, vp, vp]
     L.sdfgpu_dsh_get.argtypes = [vp, vp, i64, vp, vp]
     L.sdfgpu_dsh_extract_window_device.argtypes = [vp, vp, i64, i64, i64, ci, vp, vp, vp]
@@ -1340,6 +1343,8 @@ DSH_MAX_CHUNK_CELLS = 32768
 DSH_COUNTS_DTYPE = np.dtype([(n, np.uint64) for n in ("chunk_filled", "cell_filled", "capacity_chunks", "table_capacity", "bytes_held",
                                                       "scratch_bytes", "byte_limit")])
 DSH_RAY_COUNTS_DTYPE = np.dtype([(n, np.uint64) for n in ("rays_hit", "rays_truncated", "rays_skipped", "cells_carved", "new_chunks")])
+DSH_SENSOR_MODEL_DTYPE = np.dtype([(n, np.float32) for n in ("prob_hit", "prob_miss", "clamp_min", "clamp_max")])
+DSH_SENSOR_MODEL_DEFAULT = (0.7, 0.4, 0.12, 0.97)                             # octomap's numbers
 DSH_CHUNK_DTYPE = np.dtype([("c", np.int64, (3,)), ("state", np.uint32), ("reserved", np.uint32), ("record", np.uint64),
                             ("first_cell", np.int64)])
 
@@ -1438,6 +1443,33 @@ class DshMap:
         counts = np.zeros(1, DSH_RAY_COUNTS_DTYPE)
         self._check(self._lib.sdfgpu_dsh_insert_rays_device(self._m, s.ctypes.data, d_points or None, int(n), float(max_range), free.ctypes.data,
                                                             hit.ctypes.data, d_statuses or None, counts.ctypes.data, stream or None))
+        return {k: int(counts[0][k]) for k in DSH_RAY_COUNTS_DTYPE.names}
+
+    @staticmethod
+    def _model(model):
+        """(prob_hit, prob_miss, clamp_min, clamp_max), or None for the defaults -> one DSH_SENSOR_MODEL_DTYPE record"""
+        out = np.zeros(1, DSH_SENSOR_MODEL_DTYPE)
+        out[0] = tuple(DSH_SENSOR_MODEL_DEFAULT if model is None else model)
+        return out
+
+    def fuse_rays(self, sensor, points, max_range, model=None):
+        """One frame of sensor rays fused into the occupancies (sdfgpu_dsh_fuse_rays): points float32 [n, 3], model a tuple
+        (prob_hit, prob_miss, clamp_min, clamp_max) or None for DSH_SENSOR_MODEL_DEFAULT -> (statuses uint8 [n], counts dict)"""
+        pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        s = np.ascontiguousarray(sensor, dtype=np.float64).reshape(3)
+        mdl = self._model(model)
+        st, counts = np.zeros(len(pts), np.uint8), np.zeros(1, DSH_RAY_COUNTS_DTYPE)
+        self._check(self._lib.sdfgpu_dsh_fuse_rays(self._m, s.ctypes.data, pts.ctypes.data, len(pts), float(max_range), mdl.ctypes.data, st.ctypes.data,
+                                                   counts.ctypes.data))
+        return st, {k: int(counts[0][k]) for k in DSH_RAY_COUNTS_DTYPE.names}
+
+    def fuse_rays_device(self, sensor, d_points, n, max_range, model=None, d_statuses=0, stream=0):
+        """The device form on `stream` (points float32 [n, 3] in device memory); returns the counts dict"""
+        s = np.ascontiguousarray(sensor, dtype=np.float64).reshape(3)
+        mdl = self._model(model)
+        counts = np.zeros(1, DSH_RAY_COUNTS_DTYPE)
+        self._check(self._lib.sdfgpu_dsh_fuse_rays_device(self._m, s.ctypes.data, d_points or None, int(n), float(max_range), mdl.ctypes.data,
+                                                          d_statuses or None, counts.ctypes.data, stream or None))
         return {k: int(counts[0][k]) for k in DSH_RAY_COUNTS_DTYPE.names}
 
     def get(self, locations):

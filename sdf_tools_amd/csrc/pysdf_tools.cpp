@@ -864,6 +864,20 @@ PYBIND11_MODULE(pysdf_tools, m) {
             return d;
         }, py::arg("points"), py::arg("sensor_origin"), py::arg("max_range"), py::arg("free_value"), py::arg("filled_value"),
            "one frame of sensor rays: free space carved up to each point, then the points filled; returns the frame's counts")
+        .def("FusePointCloudRays", [](DshGrid& g, const py::array_t<float, py::array::c_style | py::array::forcecast>& points,
+                                      const std::array<double, 3>& sensor_origin, double max_range, float prob_hit, float prob_miss, float clamp_min, float clamp_max) {
+            if (points.size() % 3) throw std::invalid_argument("points: float32 [n, 3]");
+            DshGrid::SensorModel model;
+            model.prob_hit = prob_hit; model.prob_miss = prob_miss; model.clamp_min = clamp_min; model.clamp_max = clamp_max;
+            const sdfgpu_dsh_ray_counts c = g.FusePointCloudRays(std::vector<float>(points.data(), points.data() + points.size()),
+                                                                 Eigen::Vector3d(sensor_origin[0], sensor_origin[1], sensor_origin[2]), max_range, model);
+            py::dict d;
+            d["rays_hit"] = c.rays_hit; d["rays_truncated"] = c.rays_truncated; d["rays_skipped"] = c.rays_skipped;
+            d["cells_carved"] = c.cells_carved; d["new_chunks"] = c.new_chunks;
+            return d;
+        }, py::arg("points"), py::arg("sensor_origin"), py::arg("max_range"), py::arg("prob_hit") = 0.7f, py::arg("prob_miss") = 0.4f, py::arg("clamp_min") = 0.12f,
+           py::arg("clamp_max") = 0.97f,
+           "one frame of sensor rays fused into the occupancies: each passed cell updated once with prob_miss, each hit cell once with prob_hit; returns the counts")
         .def("ExtractCollisionMapGrid", [](const DshGrid& g, const std::array<int64_t, 3>& lower, int64_t nx, int64_t ny, int64_t nz) {
             return g.ExtractCollisionMapGrid(VoxelGrid::GRID_INDEX(lower[0], lower[1], lower[2]), nx, ny, nz);
         }, py::arg("lower_index"), py::arg("nx"), py::arg("ny"), py::arg("nz"))

@@ -1,5 +1,5 @@
 // sdfgpu_dsh.hip -- the chunk-hashed sparse collision map (sdfgpu_dsh.hpp, include/sdfgpu.h "Dynamic spatial hashed map", DESIGN.md
-// sections 29 and 30): its kernels, the host orchestration of a batch and of a frame of sensor rays, growth, and the C ABI entry
+// sections 29, 30 and 31): its kernels, the host orchestration of a batch and of a frame of sensor rays (carved or fused), growth, and the C ABI entry
 // points sdfgpu_dsh_*.  Compiled beside
 // sdfgpu.hip and linked into the same libsdfgpu.so (sdf_tools_amd/build.py).
 //
@@ -11,6 +11,8 @@
 //     between two launches, in the 8 bytes it is about to overwrite: zero the targets | stamp | decide (one flag per operation) | apply
 //   - a frame of sensor rays marks the chunks it writes into in a byte map by table position, and carves with one record: wherever
 //     several threads of a launch store to one address, they store the same value
+//   - a fused frame tells its cells to a mark plane the same way (one byte value per launch), and one workgroup per touched chunk then
+//     updates each marked record once and clears its mark
 //
 // Arithmetic: a location on a cell boundary is placed by the rounding of g = inverse_origin * p alone, and tests/dsh_restated.py states
 // that product in numpy (separate products and sums), so nothing here may be contracted into an FMA (hipcc contracts by default).  The
@@ -499,6 +501,80 @@ __global__ __launch_bounds__(kDshThreads) void k_dsh_ray_carve(const DshGeometry
     });
 }
 
+// ---- a fused frame (include/sdfgpu.h "Sensor rays: fusion") ------------------------------------------------------------
+// Behind walk A the frame is told to the mark plane, one byte per cell, and then folded into the records chunk by chunk, so that a
+// cell is updated once however many rays cross it: walk B stores kDshMarkMiss for every carved cell (all writers store the same
+// byte), the hits store kDshMarkHit behind a kernel boundary (a hit beats a miss by launch order), and k_dsh_ray_fuse reads each
+// touched chunk's marks, updates the marked records and clears the marks.  No atomics, and nothing depends on the order of lanes.
+__global__ __launch_bounds__(kDshThreads) void k_dsh_ray_mark(const DshGeometry g, const DshTable t, uint8_t* __restrict__ plane, const DshRayFrame f,
+                                                              const float* __restrict__ points, int64_t n) {
+    const int64_t i = dsh_item();
+    if (i >= n) return;
+    DshRayWalk w;
+    if (dsh_ray_begin(g, f, (double)points[3 * i], (double)points[3 * i + 1], (double)points[3 * i + 2], w) == SDFGPU_DSH_RAY_SKIPPED) return;
+    uint8_t* marks = nullptr;
+    (void)dsh_ray_walk(g, f, w, [&](bool chunk_changed, bool is_hit) {
+        if (chunk_changed) {
+            const uint32_t pos = dsh_find(t, dsh_pack_key(w.c[0], w.c[1], w.c[2]));
+            marks = pos != kDshNoPos ? plane + dsh_mark_offset(t.slots[pos], (uint64_t)g.cells_per_chunk, 0) : nullptr;
+        }
+        if (!is_hit && marks) marks[dsh_ray_cell(g, w)] = kDshMarkMiss;
+    });
+}
+
+__global__ __launch_bounds__(kDshThreads) void k_dsh_ray_mark_hits(const DshTable t, uint8_t* __restrict__ plane, uint64_t cells_per_chunk,
+                                                                   const uint32_t* __restrict__ op_pos, const uint32_t* __restrict__ op_cell, int64_t n) {
+    const int64_t i = dsh_item();
+    if (i >= n || op_pos[i] == kDshNoPos) return;
+    plane[dsh_mark_offset(t.slots[op_pos[i]], cells_per_chunk, op_cell[i])] = kDshMarkHit;
+}
+
+__device__ __forceinline__ void dsh_fuse_cell(uint64_t* cell, uint32_t mark, const DshFuse& u) {
+    uint32_t* const occupancy = reinterpret_cast<uint32_t*>(cell);            // COLLISION_CELL: occupancy in the low word; the component stays
+    const bool hit = mark == kDshMarkHit;
+    *occupancy = __float_as_uint(dsh_fuse_update(__uint_as_float(*occupancy), hit ? u.hit : u.miss, hit ? u.one_minus_hit : u.one_minus_miss,
+                                                 u.clamp_min, u.clamp_max));
+}
+
+// One workgroup per chunk; the chunks the frame touched carry kDshTouched again (k_dsh_ray_touch a second time: k_dsh_expand consumed
+// the first).  The chunk's marks go through LDS (dsh_fuse_lds_bytes per workgroup), so that both sides are coalesced: a lane loads 16
+// marks in one load where the chunk's marks are 16-byte aligned (cells_per_chunk a multiple of 16: the plane's base is), else the
+// lanes take a byte each; whoever loaded a mark clears it.  Then the lanes sweep the cells in lane order, and a marked record's
+// occupancy word is loaded, updated and stored beside its neighbours'.
+__global__ __launch_bounds__(kDshThreads) void k_dsh_ray_fuse(const DshPool p, uint8_t* __restrict__ plane, uint64_t n_live, uint32_t cells_per_chunk,
+                                                              const DshFuse u) {
+    extern __shared__ uint4 staged_vectors[];                                  // ceil(cells_per_chunk / 16) of them
+    const uint64_t slot = (uint64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    if (slot >= n_live) return;                                                // (the last row of a two-dimensional launch)
+    DshChunkHead* const hd = p.heads + slot;
+    const uint32_t state = hd->state;
+    if (!(state & kDshTouched)) return;                                        // (uniform over the workgroup)
+    uint64_t* const cells = p.cells + slot * (uint64_t)cells_per_chunk;
+    uint8_t* const marks = plane + dsh_mark_offset(slot, cells_per_chunk, 0);
+    uint8_t* const staged = reinterpret_cast<uint8_t*>(staged_vectors);
+    if ((cells_per_chunk & 15u) == 0) {
+        for (uint32_t k = threadIdx.x * 16u; k < cells_per_chunk; k += kDshThreads * 16u) {
+            const uint4 v = *reinterpret_cast<const uint4*>(marks + k);
+            staged_vectors[k >> 4] = v;
+            if ((v.x | v.y | v.z | v.w) != 0) *reinterpret_cast<uint4*>(marks + k) = make_uint4(0, 0, 0, 0);
+        }
+    } else {
+        for (uint32_t k = threadIdx.x; k < cells_per_chunk; k += kDshThreads) {
+            const uint8_t mark = marks[k];
+            staged[k] = mark;
+            if (mark) marks[k] = 0;
+        }
+    }
+    __syncthreads();                                                           // the marks are staged, and every thread has read the state word
+    if (threadIdx.x == 0) hd->state = state & ~kDshTouched;
+    for (uint32_t k = threadIdx.x; k < cells_per_chunk; k += kDshThreads) {
+        const uint32_t mark = staged[k];
+        if (mark) dsh_fuse_cell(cells + k, mark, u);
+    }
+}
+
+size_t dsh_fuse_lds_bytes(uint64_t cells_per_chunk) { return (size_t)((cells_per_chunk + 15) / 16 * 16); }   // at most 32 KiB
+
 dim3 dsh_chunk_grid(uint64_t chunks) {                                        // one workgroup per chunk
     if (chunks <= (uint64_t)kDshGridX) return dim3((unsigned)std::max<uint64_t>(chunks, 1));
     return dim3((unsigned)kDshGridX, (unsigned)((chunks + kDshGridX - 1) / kDshGridX));
@@ -522,7 +598,9 @@ struct sdfgpu_dsh_map_object {
     uint64_t byte_limit = 0;
     DeviceBuffer scratch;           // per batch: table position, cell slot, new entries, winner flags, counters; the export's order
     DeviceBuffer stage;             // host forms: locations | values | records | statuses
-    StreamOrder order;              // recorded behind every call: one on another stream waits for it first
+    uint8_t* marks = nullptr;       // the mark plane of fused frames (null until the first): all zero between frames
+    uint64_t marks_cap = 0;         // chunks it covers: at least pool_cap while a fused frame runs
+    StreamOrder order;             // recorded behind every call: one on another stream waits for it first
 };
 
 namespace {
@@ -610,6 +688,33 @@ int dsh_reserve_pool(sdfgpu_dsh_map_object* m, uint64_t needed, hipStream_t st) 
     (void)rz_free(h, m->pool.cells);
     m->pool = grown;
     m->pool_cap = want;
+    return SDFGPU_OK;
+}
+
+// the mark plane for the pool dsh_reserve_pool(needed) will leave: made, or replaced by a larger one, and cleared.  Nothing is copied
+// (it is all zero between frames).  Called in front of dsh_reserve_pool, so a frame this refuses has grown nothing; a pool that a
+// batch grew in between is caught up with here, at the next fused frame.
+int dsh_reserve_marks(sdfgpu_dsh_map_object* m, uint64_t needed, hipStream_t st) {
+    sdfgpu_handle h = m->h;
+    const uint64_t cpc = (uint64_t)m->g.cells_per_chunk;
+    uint64_t want = m->pool_cap;
+    (void)dsh_plan_pool(m->pool_cap, needed, cpc, dsh_table_bytes(m->table_cap), m->byte_limit, &want);   // (refused: dsh_reserve_pool says so)
+    if (want <= m->marks_cap) return SDFGPU_OK;
+    void* grown = nullptr;
+    if (int rc = rz_malloc(h, "dsh fusion marks", (size_t)dsh_mark_bytes(want, cpc), &grown)) {
+        const uint64_t least = std::max(needed, m->pool_cap);
+        if (want == least) return rc;
+        (void)hipGetLastError();                                                // as the pool does: exactly what is needed
+        want = least;
+        if (int rc2 = rz_malloc(h, "dsh fusion marks", (size_t)dsh_mark_bytes(want, cpc), &grown)) return rc2;
+    }
+    if (hipMemsetAsync(grown, 0, (size_t)dsh_mark_bytes(want, cpc), st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+        (void)rz_free(h, grown);
+        return fail(h, SDFGPU_ERR_HIP, "dsh: clearing the fusion marks failed");
+    }
+    if (m->marks) (void)rz_free(h, m->marks);
+    m->marks = static_cast<uint8_t*>(grown);
+    m->marks_cap = want;
     return SDFGPU_OK;
 }
 
@@ -725,9 +830,24 @@ int dsh_ray_frame(sdfgpu_dsh_map_object* m, const double* sensor, int64_t n, dou
     return SDFGPU_OK;
 }
 
-// One frame of rays on `st` (the frame was checked by dsh_ray_frame).
+// The sensor model of a fused frame, checked and turned into what k_dsh_ray_fuse is told.
+int dsh_fuse_model(sdfgpu_handle h, const sdfgpu_dsh_sensor_model* model, DshFuse& u) {
+    if (!model) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: fuse_rays needs the sensor model");
+    if (!dsh_fuse_model_ok(model->prob_hit, model->prob_miss, model->clamp_min, model->clamp_max))
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: the sensor model's numbers must lie in [0.001, 0.999] with clamp_min <= clamp_max (got %g, %g, %g, %g)",
+                    (double)model->prob_hit, (double)model->prob_miss, (double)model->clamp_min, (double)model->clamp_max);
+    u.hit = model->prob_hit;
+    u.one_minus_hit = 1.0f - model->prob_hit;
+    u.miss = model->prob_miss;
+    u.one_minus_miss = 1.0f - model->prob_miss;
+    u.clamp_min = model->clamp_min;
+    u.clamp_max = model->clamp_max;
+    return SDFGPU_OK;
+}
+
+// One frame of rays on `st` (the frame was checked by dsh_ray_frame): carved with the two records, or (fuse) fused with the model.
 int dsh_rays_impl(sdfgpu_dsh_map_object* m, const DshRayFrame& f, uint64_t range_cells, const float* d_points, int64_t n, const void* free_value,
-                  const void* hit_value, uint8_t* d_statuses, sdfgpu_dsh_ray_counts* out_counts, hipStream_t st) {
+                  const void* hit_value, const DshFuse* fuse, uint8_t* d_statuses, sdfgpu_dsh_ray_counts* out_counts, hipStream_t st) {
     sdfgpu_handle h = m->h;
     if (out_counts) *out_counts = sdfgpu_dsh_ray_counts{};
     if (n == 0) return SDFGPU_OK;
@@ -782,6 +902,7 @@ int dsh_rays_impl(sdfgpu_dsh_map_object* m, const DshRayFrame& f, uint64_t range
         HIP_TRY(h, hipMemcpyAsync(&back, counters, sizeof back, hipMemcpyDeviceToHost, st));
         HIP_TRY(h, hipStreamSynchronize(st));
         if (back.lost) return fail(h, SDFGPU_ERR_HIP, "dsh: %u chunk keys found no table entry (internal error)", back.lost);
+        if (fuse) if (int rc_marks = dsh_reserve_marks(m, m->n_live + back.n_new, st)) return rc_marks;
         return dsh_reserve_pool(m, m->n_live + back.n_new, st);
     }();
     if (rc != SDFGPU_OK) {                                                      // refused: the table is the one the frame found
@@ -800,13 +921,20 @@ int dsh_rays_impl(sdfgpu_dsh_map_object* m, const DshRayFrame& f, uint64_t range
     const uint32_t n_new = back.n_new;
     if (n_new) hipLaunchKernelGGL(k_dsh_init_new, dsh_grid(n_new), block, 0, st, m->table, m->pool.heads, newlist, n_new, (uint32_t)m->n_live);
     m->n_live += n_new;
-    uint64_t free_record = 0, hit_record = 0;
-    memcpy(&free_record, free_value, 8);
-    memcpy(&hit_record, hit_value, 8);
     hipLaunchKernelGGL(k_dsh_ray_touch, dsh_grid((int64_t)m->table_cap), block, 0, st, m->table, m->pool.heads, marks);
     hipLaunchKernelGGL(k_dsh_expand, dsh_chunk_grid(m->n_live), block, 0, st, m->pool, m->n_live, cpc, m->g.default_record);
-    hipLaunchKernelGGL(k_dsh_ray_carve, grid, block, 0, st, m->g, m->table, m->pool, f, d_points, n, free_record);
-    hipLaunchKernelGGL((k_dsh_store_one<false>), grid, block, 0, st, m->table, m->pool, cpc, op_pos, op_cell, n, hit_record);
+    if (!fuse) {
+        uint64_t free_record = 0, hit_record = 0;
+        memcpy(&free_record, free_value, 8);
+        memcpy(&hit_record, hit_value, 8);
+        hipLaunchKernelGGL(k_dsh_ray_carve, grid, block, 0, st, m->g, m->table, m->pool, f, d_points, n, free_record);
+        hipLaunchKernelGGL((k_dsh_store_one<false>), grid, block, 0, st, m->table, m->pool, cpc, op_pos, op_cell, n, hit_record);
+    } else {                                                                    // walk B into the mark plane, the hits behind it, then one update per marked cell
+        hipLaunchKernelGGL(k_dsh_ray_mark, grid, block, 0, st, m->g, m->table, m->marks, f, d_points, n);
+        hipLaunchKernelGGL(k_dsh_ray_mark_hits, grid, block, 0, st, m->table, m->marks, cpc, op_pos, op_cell, n);
+        hipLaunchKernelGGL(k_dsh_ray_touch, dsh_grid((int64_t)m->table_cap), block, 0, st, m->table, m->pool.heads, marks);
+        hipLaunchKernelGGL(k_dsh_ray_fuse, dsh_chunk_grid(m->n_live), block, dsh_fuse_lds_bytes(cpc), st, m->pool, m->marks, m->n_live, (uint32_t)cpc, *fuse);
+    }
     HIP_TRY(h, hipGetLastError());
     if (out_counts) {
         out_counts->rays_hit = back.counts[0];
@@ -943,6 +1071,25 @@ int dsh_set_host(sdfgpu_dsh_map m, bool chunk_sets, const double* locations, int
     });
 }
 
+// The host form of a frame: the points are staged, the statuses copied back.
+int dsh_rays_host(sdfgpu_dsh_map m, const DshRayFrame& f, uint64_t range_cells, const float* points, int64_t n, const void* free_value, const void* hit_value,
+                  const DshFuse* fuse, uint8_t* statuses, sdfgpu_dsh_ray_counts* out_counts) {
+    sdfgpu_handle h = m->h;
+    if (n == 0) return dsh_rays_impl(m, f, range_cells, nullptr, 0, free_value, hit_value, fuse, nullptr, out_counts, nullptr);
+    if (!points) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: null points");
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, m->order.wait(nullptr));
+    DshStage s;
+    const size_t un = (size_t)n, at_pts = s.add(un * 12), at_st = s.add(statuses ? un : 0);
+    if (int rc = ensure(h, m->stage, s.total, "dsh staging")) return rc;
+    char* const base = static_cast<char*>(m->stage.ptr);
+    if (int rc = copy_from_host(h, base + at_pts, points, un * 12)) return rc;
+    if (int rc = dsh_rays_impl(m, f, range_cells, reinterpret_cast<const float*>(base + at_pts), n, free_value, hit_value, fuse,
+                               statuses ? reinterpret_cast<uint8_t*>(base + at_st) : nullptr, out_counts, nullptr)) return rc;
+    if (statuses) return copy_to_host(h, statuses, base + at_st, un);
+    return SDFGPU_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -997,7 +1144,7 @@ int sdfgpu_dsh_destroy(sdfgpu_dsh_map map) {
     sdfgpu_handle h = map->h;
     (void)hipSetDevice(h->device);
     (void)map->order.host_wait();
-    for (void* p : {(void*)map->table.keys, (void*)map->pool.heads, (void*)map->pool.cells, map->scratch.ptr, map->stage.ptr}) (void)rz_free(h, p);
+    for (void* p : {(void*)map->table.keys, (void*)map->pool.heads, (void*)map->pool.cells, map->scratch.ptr, map->stage.ptr, (void*)map->marks}) (void)rz_free(h, p);
     map->order.destroy();
     delete map;
     return SDFGPU_OK;
@@ -1015,7 +1162,7 @@ int sdfgpu_dsh_info(sdfgpu_dsh_map map, sdfgpu_dsh_counts* out_counts) {
         c.capacity_chunks = map->pool_cap;
         c.table_capacity = map->table_cap;
         c.bytes_held = dsh_bytes_held(map);
-        c.scratch_bytes = map->scratch.bytes + map->stage.bytes;
+        c.scratch_bytes = map->scratch.bytes + map->stage.bytes + (map->marks ? dsh_mark_bytes(map->marks_cap, (uint64_t)map->g.cells_per_chunk) : 0);
         c.byte_limit = map->byte_limit;
         *out_counts = c;
         return SDFGPU_OK;
@@ -1045,30 +1192,43 @@ int sdfgpu_dsh_insert_rays_device(sdfgpu_dsh_map map, const double sensor[3], co
         DshRayFrame f{};
         uint64_t range_cells = 0;
         if (int rc = dsh_ray_frame(map, sensor, n, max_range, free_value, hit_value, f, range_cells)) return rc;
-        return dsh_rays_impl(map, f, range_cells, d_points, n, free_value, hit_value, d_statuses, out_counts, (hipStream_t)stream);
+        return dsh_rays_impl(map, f, range_cells, d_points, n, free_value, hit_value, nullptr, d_statuses, out_counts, (hipStream_t)stream);
+    });
+}
+
+int sdfgpu_dsh_fuse_rays_device(sdfgpu_dsh_map map, const double sensor[3], const float* d_points, int64_t n, double max_range,
+                                const sdfgpu_dsh_sensor_model* model, uint8_t* d_statuses, sdfgpu_dsh_ray_counts* out_counts, void* stream) {
+    return dsh_entry(map, stream, [&]() -> int {
+        DshRayFrame f{};
+        DshFuse u{};
+        uint64_t range_cells = 0;
+        const uint64_t no_record = 0;                                           // (a fused frame stores no record of the caller's)
+        if (int rc = dsh_fuse_model(map->h, model, u)) return rc;
+        if (int rc = dsh_ray_frame(map, sensor, n, max_range, &no_record, &no_record, f, range_cells)) return rc;
+        return dsh_rays_impl(map, f, range_cells, d_points, n, nullptr, nullptr, &u, d_statuses, out_counts, (hipStream_t)stream);
     });
 }
 
 int sdfgpu_dsh_insert_rays(sdfgpu_dsh_map map, const double sensor[3], const float* points, int64_t n, double max_range, const void* free_value,
                            const void* hit_value, uint8_t* statuses, sdfgpu_dsh_ray_counts* out_counts) {
     return dsh_entry(map, nullptr, [&]() -> int {
-        sdfgpu_handle h = map->h;
         DshRayFrame f{};
         uint64_t range_cells = 0;
         if (int rc = dsh_ray_frame(map, sensor, n, max_range, free_value, hit_value, f, range_cells)) return rc;
-        if (n == 0) return dsh_rays_impl(map, f, range_cells, nullptr, 0, free_value, hit_value, nullptr, out_counts, nullptr);
-        if (!points) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: null points");
-        HIP_TRY(h, hipSetDevice(h->device));
-        HIP_TRY(h, map->order.wait(nullptr));
-        DshStage s;
-        const size_t un = (size_t)n, at_pts = s.add(un * 12), at_st = s.add(statuses ? un : 0);
-        if (int rc = ensure(h, map->stage, s.total, "dsh staging")) return rc;
-        char* const base = static_cast<char*>(map->stage.ptr);
-        if (int rc = copy_from_host(h, base + at_pts, points, un * 12)) return rc;
-        if (int rc = dsh_rays_impl(map, f, range_cells, reinterpret_cast<const float*>(base + at_pts), n, free_value, hit_value,
-                                   statuses ? reinterpret_cast<uint8_t*>(base + at_st) : nullptr, out_counts, nullptr)) return rc;
-        if (statuses) return copy_to_host(h, statuses, base + at_st, un);
-        return SDFGPU_OK;
+        return dsh_rays_host(map, f, range_cells, points, n, free_value, hit_value, nullptr, statuses, out_counts);
+    });
+}
+
+int sdfgpu_dsh_fuse_rays(sdfgpu_dsh_map map, const double sensor[3], const float* points, int64_t n, double max_range,
+                         const sdfgpu_dsh_sensor_model* model, uint8_t* statuses, sdfgpu_dsh_ray_counts* out_counts) {
+    return dsh_entry(map, nullptr, [&]() -> int {
+        DshRayFrame f{};
+        DshFuse u{};
+        uint64_t range_cells = 0;
+        const uint64_t no_record = 0;
+        if (int rc = dsh_fuse_model(map->h, model, u)) return rc;
+        if (int rc = dsh_ray_frame(map, sensor, n, max_range, &no_record, &no_record, f, range_cells)) return rc;
+        return dsh_rays_host(map, f, range_cells, points, n, nullptr, nullptr, &u, statuses, out_counts);
     });
 }
 

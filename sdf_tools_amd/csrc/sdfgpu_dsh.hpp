@@ -1,7 +1,7 @@
 // sdfgpu_dsh.hpp -- the chunk-hashed sparse collision map (include/sdfgpu.h "Dynamic spatial hashed map"): its
 // constants, the packing of a chunk coordinate into a table key, the hash, and the planning of the table's and the pool's sizes.
 // Plain C++ without a HIP header, as sdfgpu_plan.hpp and sdfgpu_policy.hpp are: sdfgpu_dsh.hip includes it for its kernels and its host
-// code, and tests/dsh_plan_harness.cpp and tests/dsh_rays_plan_harness.cpp drive the arithmetic on the CPU under
+// code, and tests/dsh_plan_harness.cpp, tests/dsh_rays_plan_harness.cpp and tests/dsh_fusion_plan_harness.cpp drive the arithmetic on the CPU under
 // -fsanitize=address,undefined.
 #pragma once
 #include <stdint.h>
@@ -20,7 +20,8 @@ constexpr int64_t kDshMaxChunkCells = 32768;               // n_x * n_y * n_z of
 constexpr uint64_t kDshEmptyKey = ~(uint64_t)0;            // three 21-bit coordinates fill 63 bits: all ones is no key
 constexpr uint32_t kDshChunkFilled = 1, kDshCellFilled = 2;   // a live chunk's state (SDFGPU_DSH_FOUND_IN_CHUNK / _IN_CELL)
 constexpr uint32_t kDshStateMask = 3;
-constexpr uint32_t kDshTouched = 0x80000000u;              // set in a chunk's state word between k_dsh_touch and k_dsh_expand only
+constexpr uint32_t kDshTouched = 0x80000000u;              // set in a chunk's state word between k_dsh_touch and k_dsh_expand (and, in a fused
+                                                           // frame, again between k_dsh_ray_touch and k_dsh_ray_fuse) only
 constexpr uint64_t kDshMinTable = 16;                      // entries; the table's capacity is a power of two
 constexpr int64_t kDshMaxBatch = (int64_t)1 << 31;         // operations of one batch (their table positions are uint32)
 
@@ -124,6 +125,46 @@ inline uint64_t dsh_ray_chunk_bound(uint64_t rays, uint64_t range_cells, const i
     const uint64_t by_rays = rays > kDshRayBoundCap / per_ray ? kDshRayBoundCap : rays * per_ray;
     return by_rays < box ? by_rays : box;
 }
+
+// ---- a fused frame of sensor rays -----------------------------------------------------------------------------------
+constexpr float kDshFuseLow = 0.001f, kDshFuseHigh = 0.999f;   // the domain of the sensor model's four numbers
+constexpr uint8_t kDshMarkMiss = 1, kDshMarkHit = 2;           // a cell's byte in the mark plane while a frame is in flight (else 0)
+
+// prob_hit, prob_miss, clamp_min and clamp_max all lie in [0.001, 0.999] and clamp_min <= clamp_max (a NaN fails every comparison)
+SDFGPU_DSH_HD bool dsh_fuse_model_ok(float prob_hit, float prob_miss, float clamp_min, float clamp_max) {
+    const float v[4] = {prob_hit, prob_miss, clamp_min, clamp_max};
+    for (int k = 0; k < 4; ++k)
+        if (!(v[k] >= kDshFuseLow && v[k] <= kDshFuseHigh)) return false;
+    return clamp_min <= clamp_max;
+}
+
+// One measurement m (prob_hit or prob_miss; one_minus_m = 1.0f - m, worked out once on the host) folded into the occupancy p: Bayes'
+// rule on the clamped prior, clamped again.  IEEE float32, every operation rounded by itself (nothing contracted: the pragma for
+// clang, -ffp-contract=off for the CPU harness), the division correctly rounded.  Inside the model's domain no operand is denormal
+// and a + b > 0.  A NaN prior becomes clamp_min.
+SDFGPU_DSH_HD float dsh_fuse_update(float p, float m, float one_minus_m, float clamp_min, float clamp_max) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    float q = p >= clamp_min ? p : clamp_min;
+    q = q <= clamp_max ? q : clamp_max;
+    const float a = q * m;
+    const float b = (1.0f - q) * one_minus_m;
+    float r = a / (a + b);
+    r = r >= clamp_min ? r : clamp_min;
+    r = r <= clamp_max ? r : clamp_max;
+    return r;
+}
+
+// The mark plane of a fused map: one byte per cell of the pool's capacity, indexed like the cells.  64-bit: a pool of 2^17 chunks of
+// 32768 cells has 2^32 of them.
+inline uint64_t dsh_mark_bytes(uint64_t pool_chunks, uint64_t cells_per_chunk) { return pool_chunks * cells_per_chunk; }
+SDFGPU_DSH_HD uint64_t dsh_mark_offset(uint64_t slot, uint64_t cells_per_chunk, uint32_t cell) { return slot * cells_per_chunk + (uint64_t)cell; }
+
+// what k_dsh_ray_fuse is told about the model
+struct DshFuse {
+    float hit, one_minus_hit, miss, one_minus_miss, clamp_min, clamp_max;
+};
 
 // ---- what the kernels are told ----------------------------------------------------------------------------------------------------------
 struct DshGeometry {
