@@ -233,6 +233,46 @@ public:
         return counts;
     }
 
+    // ---- removal (additions; include/sdfgpu.h "Removal") ------------------------------------------------------------
+    // A removed chunk is absent again: Get says NOT_FOUND, a window reads the default.  On an uninitialised map RemoveChunk returns
+    // false and Clear 0; the others throw std::runtime_error, as the batch forms do.
+    bool RemoveChunk(const double x, const double y, const double z) {
+        if (!initialized_) return false;
+        const double location[3] = {x, y, z};
+        int64_t removed = 0;
+        Locked([&](sdfgpu_dsh_map m) { return sdfgpu_dsh_remove_chunks(m, location, 1, nullptr, &removed); });
+        if (removed) components_valid_ = false;
+        return removed != 0;
+    }
+    bool RemoveChunk(const Eigen::Vector3d& location) { return RemoveChunk(location.x(), location.y(), location.z()); }
+    // locations_xyz: n x 3 doubles, removed in list order; true for the first location that names a live chunk
+    std::vector<bool> RemoveChunks(const std::vector<double>& locations_xyz) {
+        RequireInitialized();
+        if (locations_xyz.size() % 3) throw std::invalid_argument("RemoveChunks: locations are x, y, z triples");
+        const size_t n = locations_xyz.size() / 3;
+        std::vector<uint8_t> raw(n);
+        int64_t removed = 0;
+        if (n) Locked([&](sdfgpu_dsh_map m) { return sdfgpu_dsh_remove_chunks(m, locations_xyz.data(), (int64_t)n, raw.data(), &removed); });
+        if (removed) components_valid_ = false;
+        std::vector<bool> statuses(n);
+        for (size_t i = 0; i < n; ++i) statuses[i] = raw[i] == SDFGPU_DSH_CHUNK_REMOVED;
+        return statuses;
+    }
+    // Keep the chunks that hold at least one of the nx x ny x nz cells from global cell lower_index on, remove every other one
+    // (RemoveBox: the other way round).  Returns how many chunks were removed.
+    int64_t RetainBox(const VoxelGrid::GRID_INDEX& lower_index, const int64_t nx, const int64_t ny, const int64_t nz) {
+        return BoxRemoval(lower_index, nx, ny, nz, 0);
+    }
+    int64_t RemoveBox(const VoxelGrid::GRID_INDEX& lower_index, const int64_t nx, const int64_t ny, const int64_t nz) {
+        return BoxRemoval(lower_index, nx, ny, nz, 1);
+    }
+    int64_t Clear() { return initialized_ ? BoxRemoval(VoxelGrid::GRID_INDEX(0, 0, 0), 0, 0, 0, 0) : 0; }
+    // Hand memory back: the pool keeps room for the live chunks and spare_chunks more, the table follows.
+    void ShrinkToFit(const int64_t spare_chunks = 0) {
+        RequireInitialized();
+        Locked([&](sdfgpu_dsh_map m) { return sdfgpu_dsh_shrink(m, spare_chunks, nullptr); });
+    }
+
     // ---- dense windows (additions) ------------------------------------------------------------------------------------------------------
     // The nx x ny x nz cells from global cell lower_index on as a CollisionMapGrid: cell (x, y, z) is what Get returns there.  The
     // result's origin is the map's origin times the translation to that corner; its OOB value is the map's default.
@@ -348,6 +388,14 @@ public:
     }
 
 private:
+    int64_t BoxRemoval(const VoxelGrid::GRID_INDEX& lower_index, const int64_t nx, const int64_t ny, const int64_t nz, const int invert) {
+        RequireInitialized();
+        const int64_t lower[3] = {lower_index.x, lower_index.y, lower_index.z}, extent[3] = {nx, ny, nz};
+        int64_t removed = 0;
+        Locked([&](sdfgpu_dsh_map m) { return sdfgpu_dsh_retain_box(m, lower, extent, invert, &removed, nullptr); });
+        if (removed) components_valid_ = false;
+        return removed;
+    }
     Eigen::Isometry3d WindowOrigin(const VoxelGrid::GRID_INDEX& lower_index) const {
         Eigen::Isometry3d corner;
         corner.setTranslation((double)lower_index.x * resolution_, (double)lower_index.y * resolution_, (double)lower_index.z * resolution_);

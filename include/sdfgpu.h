@@ -1051,7 +1051,9 @@ int sdfgpu_display_select_contour(sdfgpu_handle h, const void* cells, size_t cel
  * sdfgpu_dsh_insert_rays_device and sdfgpu_dsh_fuse_rays_device synchronise that stream once (they read the number of new chunks back before the pool may grow;
  * a call that grows the table or the pool synchronises once more per growth), sdfgpu_dsh_info and the two export forms
  * synchronise too (they read counts back); sdfgpu_dsh_get_device and sdfgpu_dsh_extract_window_device return with their kernels
- * pending.  Calls on one map from different streams are ordered by the map (an event behind its last call); one host thread
+ * pending.  The removals (sdfgpu_dsh_remove_chunks_device, sdfgpu_dsh_retain_box) synchronise the stream once, to read the
+ * removed count back; a call that removed something and kept something synchronises once more behind the rebuilt table (the
+ * rehash's check that no key was lost).  sdfgpu_dsh_shrink synchronises before it frees what it replaced.  Calls on one map from different streams are ordered by the map (an event behind its last call); one host thread
  * per map at a time.
  * ------------------------------------------------------------------------- */
 typedef struct sdfgpu_dsh_map_object* sdfgpu_dsh_map;
@@ -1191,6 +1193,43 @@ int sdfgpu_dsh_fuse_rays_device(sdfgpu_dsh_map map, const double sensor[3], cons
                                 void* stream);
 int sdfgpu_dsh_fuse_rays(sdfgpu_dsh_map map, const double sensor[3], const float* points, int64_t n, double max_range,
                          const sdfgpu_dsh_sensor_model* model, uint8_t* statuses, sdfgpu_dsh_ray_counts* out_counts);
+
+/* Removal: chunks leave the map by list or by an axis-aligned box of cells, and the map hands memory back.
+ * The reference's map has no removal: the contract is this project's own, like the two sections above;
+ * tests/dsh_remove_restated.py restates it.
+ *
+ * A removed chunk becomes ABSENT: Get on any of its cells returns (default, NOT_FOUND), a window reads the default there, the
+ * export no longer lists it, a later SetCell into it makes a fresh cell-filled chunk whose other cells are the default, and a
+ * later carved or fused frame treats it as an absent chunk.  Nothing else in the map changes by a byte.
+ *
+ * sdfgpu_dsh_remove_chunks_device / sdfgpu_dsh_remove_chunks: n in 0 .. 2^31 - 1 locations (n x 3 doubles), each mapped to a
+ *   chunk exactly as SetChunk maps it.  The batch leaves the map as if the removals had been applied one after the other in list
+ *   order: the first operation in list order that names a live chunk gets SDFGPU_DSH_CHUNK_REMOVED; a later duplicate, an absent
+ *   chunk and an invalid location get SDFGPU_DSH_CHUNK_NOT_REMOVED and change nothing.  out_removed (optional, host memory) is
+ *   the number of REMOVED.  d_statuses / statuses (optional): one byte per operation; undefined when the call fails.
+ * sdfgpu_dsh_retain_box: the box is the global cells lower[a] .. lower[a] + extent[a] - 1, in the coordinates of
+ *   sdfgpu_dsh_extract_window's lower.  With invert == 0 every live chunk that holds NO cell of the box is removed (chunks the
+ *   box cuts stay whole); with invert != 0 every live chunk that holds AT LEAST ONE cell of the box is removed.  An extent of 0
+ *   on any axis is the empty box: invert == 0 then clears the map, invert != 0 removes nothing.  Refused with
+ *   SDFGPU_ERR_INVALID_ARGUMENT, nothing written, unless every |lower[a]| <= 2^40 and 0 <= extent[a] <= 2^40.  The host turns the
+ *   box into a closed range of chunk coordinates per axis (floor division by the chunk's dimensions, clamped to [-2^20, 2^20));
+ *   the kernel compares unpacked keys with it, so nothing can overflow.  lower, extent and out_removed are host memory.
+ * sdfgpu_dsh_shrink: the pool is reallocated to max(live + spare_chunks, 1) chunks and the table to the smallest power of two
+ *   that is at least 16 and at least 2 (live + spare_chunks) entries, each only where that is smaller than what the map holds
+ *   (spare_chunks >= 0).  The mark plane of fused frames, where one exists, is freed; the next fused frame makes it again.
+ *   Content is unchanged by a byte, and sdfgpu_dsh_info afterwards reports exactly the planned capacity_chunks, table_capacity
+ *   and bytes_held.  If an allocation fails, the map is as it was.
+ * All of them: capacity_chunks, table_capacity and bytes_held do not change on a removal; freed pool slots are reused by the next
+ *   batch or frame.  No removal is ever refused by byte_limit: it allocates per-call scratch only, and if that fails the map is as
+ *   it was.  Which pool slot a chunk lives in is not visible through this interface. */
+enum { SDFGPU_DSH_CHUNK_NOT_REMOVED = 0, SDFGPU_DSH_CHUNK_REMOVED = 1 };   /* a removal's status byte */
+
+int sdfgpu_dsh_remove_chunks_device(sdfgpu_dsh_map map, const double* d_locations, int64_t n, uint8_t* d_statuses, int64_t* out_removed,
+                                    void* stream);
+int sdfgpu_dsh_remove_chunks(sdfgpu_dsh_map map, const double* locations, int64_t n, uint8_t* statuses, int64_t* out_removed);
+int sdfgpu_dsh_retain_box(sdfgpu_dsh_map map, const int64_t lower[3], const int64_t extent[3], int invert, int64_t* out_removed,
+                          void* stream);
+int sdfgpu_dsh_shrink(sdfgpu_dsh_map map, int64_t spare_chunks, void* stream);
 
 /* Get for n locations: 8-byte records and / or one status byte each (SDFGPU_DSH_NOT_FOUND / FOUND_IN_CHUNK / FOUND_IN_CELL);
  * either output may be null, not both. */

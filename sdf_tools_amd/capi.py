@@ -46,6 +46,7 @@ EXPORTS = [
     "sdfgpu_dsh_create", "sdfgpu_dsh_destroy", "sdfgpu_dsh_info",
     "sdfgpu_dsh_set_cells_device", "sdfgpu_dsh_set_cells", "sdfgpu_dsh_set_chunks_device", "sdfgpu_dsh_set_chunks",
     "sdfgpu_dsh_insert_points_device", "sdfgpu_dsh_insert_rays_device", "sdfgpu_dsh_insert_rays", "sdfgpu_dsh_fuse_rays_device", "sdfgpu_dsh_fuse_rays",
+    "sdfgpu_dsh_remove_chunks_device", "sdfgpu_dsh_remove_chunks", "sdfgpu_dsh_retain_box", "sdfgpu_dsh_shrink",
     "sdfgpu_dsh_get_device", "sdfgpu_dsh_get",
     "sdfgpu_dsh_extract_window_device", "sdfgpu_dsh_extract_window", "sdfgpu_dsh_export_device", "sdfgpu_dsh_export",
 ]
@@ -206,6 +207,10 @@ def load_library():
     L.sdfgpu_dsh_insert_rays.argtypes = [vp, vp, vp, i64, dbl, vp, vp, vp, vp]
     L.sdfgpu_dsh_fuse_rays_device.argtypes = [vp, vp, vp, i64, dbl, vp, vp, vp, vp]
     L.sdfgpu_dsh_fuse_rays.argtypes = [vp, vp, vp, i64, dbl, vp, vp, vp]
+    L.sdfgpu_dsh_remove_chunks_device.argtypes = [vp, vp, i64, vp, vp, vp]
+    L.sdfgpu_dsh_remove_chunks.argtypes = [vp, vp, i64, vp, vp]
+    L.sdfgpu_dsh_retain_box.argtypes = [vp, vp, vp, ci, vp, vp]
+    L.sdfgpu_dsh_shrink.argtypes = [vp, i64, vp]
     L.sdfgpu_dsh_get_device.argtypes = [vp, vp, i64, vp, vp, vp]
     L.sdfgpu_dsh_get.argtypes = [vp, vp, i64, vp, vp]
     L.sdfgpu_dsh_extract_window_device.argtypes = [vp, vp, i64, i64, i64, ci, vp, vp, vp]
@@ -1339,6 +1344,7 @@ class SdfGpu:
 DSH_NOT_FOUND, DSH_FOUND_IN_CHUNK, DSH_FOUND_IN_CELL = 0, 1, 2
 DSH_NOT_SET, DSH_SET_CHUNK, DSH_SET_CELL = 0, 1, 2
 DSH_RAY_SKIPPED, DSH_RAY_HIT, DSH_RAY_TRUNCATED = 0, 1, 2
+DSH_CHUNK_NOT_REMOVED, DSH_CHUNK_REMOVED = 0, 1
 DSH_MAX_CHUNK_CELLS = 32768
 DSH_COUNTS_DTYPE = np.dtype([(n, np.uint64) for n in ("chunk_filled", "cell_filled", "capacity_chunks", "table_capacity", "bytes_held",
                                                       "scratch_bytes", "byte_limit")])
@@ -1471,6 +1477,40 @@ class DshMap:
         self._check(self._lib.sdfgpu_dsh_fuse_rays_device(self._m, s.ctypes.data, d_points or None, int(n), float(max_range), mdl.ctypes.data,
                                                           d_statuses or None, counts.ctypes.data, stream or None))
         return {k: int(counts[0][k]) for k in DSH_RAY_COUNTS_DTYPE.names}
+
+    def remove_chunks(self, locations, statuses=True):
+        """Remove the chunks of the locations, in list order (sdfgpu_dsh_remove_chunks) -> (statuses uint8 [n] or None, removed)"""
+        loc = np.ascontiguousarray(locations, dtype=np.float64).reshape(-1, 3)
+        st = np.zeros(len(loc), np.uint8) if statuses else None
+        removed = ctypes.c_int64()
+        self._check(self._lib.sdfgpu_dsh_remove_chunks(self._m, loc.ctypes.data, len(loc), None if st is None else st.ctypes.data, ctypes.byref(removed)))
+        return st, removed.value
+
+    def remove_chunks_device(self, d_locations, n, d_statuses=0, stream=0):
+        """The device form on `stream` (locations float64 [n, 3] in device memory); returns the number of chunks removed"""
+        removed = ctypes.c_int64()
+        self._check(self._lib.sdfgpu_dsh_remove_chunks_device(self._m, d_locations or None, int(n), d_statuses or None, ctypes.byref(removed), stream or None))
+        return removed.value
+
+    def retain_box(self, lower, extent, invert=False, stream=0):
+        """Remove every chunk that holds no cell of the box of global cells lower .. lower + extent - 1 (invert: every chunk that
+        holds at least one); returns the number of chunks removed"""
+        lo = np.array([int(v) for v in lower], np.int64).reshape(3)
+        ext = np.array([int(v) for v in extent], np.int64).reshape(3)
+        removed = ctypes.c_int64()
+        self._check(self._lib.sdfgpu_dsh_retain_box(self._m, lo.ctypes.data, ext.ctypes.data, int(bool(invert)), ctypes.byref(removed), stream or None))
+        return removed.value
+
+    def remove_box(self, lower, extent, stream=0):
+        return self.retain_box(lower, extent, True, stream)
+
+    def clear(self, stream=0):
+        """Remove every chunk (the empty box retains nothing); returns the number of chunks removed"""
+        return self.retain_box((0, 0, 0), (0, 0, 0), False, stream)
+
+    def shrink(self, spare_chunks=0, stream=0):
+        """Hand memory back: the pool to max(live + spare_chunks, 1) chunks, the table to match, the mark plane freed"""
+        self._check(self._lib.sdfgpu_dsh_shrink(self._m, int(spare_chunks), stream or None))
 
     def get(self, locations):
         """(records uint64 [n], statuses uint8 [n])"""

@@ -878,6 +878,21 @@ PYBIND11_MODULE(pysdf_tools, m) {
         }, py::arg("points"), py::arg("sensor_origin"), py::arg("max_range"), py::arg("prob_hit") = 0.7f, py::arg("prob_miss") = 0.4f, py::arg("clamp_min") = 0.12f,
            py::arg("clamp_max") = 0.97f,
            "one frame of sensor rays fused into the occupancies: each passed cell updated once with prob_miss, each hit cell once with prob_hit; returns the counts")
+        .def("RemoveChunk", [](DshGrid& g, double x, double y, double z) { return g.RemoveChunk(x, y, z); })
+        .def("RemoveChunks", [=](DshGrid& g, const py::array_t<double, py::array::c_style | py::array::forcecast>& locations) {
+            const std::vector<bool> removed = g.RemoveChunks(dsh_locations(locations));
+            py::array_t<uint8_t> out((py::ssize_t)removed.size());
+            for (size_t i = 0; i < removed.size(); ++i) out.mutable_data()[i] = removed[i] ? 1 : 0;
+            return out;
+        }, py::arg("locations"), "uint8 statuses (1 = removed); as if applied one after the other in list order")
+        .def("RetainBox", [](DshGrid& g, const std::array<int64_t, 3>& lower, int64_t nx, int64_t ny, int64_t nz) {
+            return g.RetainBox(VoxelGrid::GRID_INDEX(lower[0], lower[1], lower[2]), nx, ny, nz);
+        }, py::arg("lower_index"), py::arg("nx"), py::arg("ny"), py::arg("nz"), "removes every chunk that holds no cell of the box; returns how many")
+        .def("RemoveBox", [](DshGrid& g, const std::array<int64_t, 3>& lower, int64_t nx, int64_t ny, int64_t nz) {
+            return g.RemoveBox(VoxelGrid::GRID_INDEX(lower[0], lower[1], lower[2]), nx, ny, nz);
+        }, py::arg("lower_index"), py::arg("nx"), py::arg("ny"), py::arg("nz"), "removes every chunk that holds a cell of the box; returns how many")
+        .def("Clear", &DshGrid::Clear)
+        .def("ShrinkToFit", &DshGrid::ShrinkToFit, py::arg("spare_chunks") = 0)
         .def("ExtractCollisionMapGrid", [](const DshGrid& g, const std::array<int64_t, 3>& lower, int64_t nx, int64_t ny, int64_t nz) {
             return g.ExtractCollisionMapGrid(VoxelGrid::GRID_INDEX(lower[0], lower[1], lower[2]), nx, ny, nz);
         }, py::arg("lower_index"), py::arg("nx"), py::arg("ny"), py::arg("nz"))

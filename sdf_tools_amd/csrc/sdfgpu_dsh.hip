@@ -1,6 +1,6 @@
 // sdfgpu_dsh.hip -- the chunk-hashed sparse collision map (sdfgpu_dsh.hpp, include/sdfgpu.h "Dynamic spatial hashed map", DESIGN.md
-// sections 29, 30 and 31): its kernels, the host orchestration of a batch and of a frame of sensor rays (carved or fused), growth, and the C ABI entry
-// points sdfgpu_dsh_*.  Compiled beside
+// sections 29 to 32): its kernels, the host orchestration of a batch, of a frame of sensor rays (carved or fused) and of a removal, growth and
+// shrinking, and the C ABI entry points sdfgpu_dsh_*.  Compiled beside
 // sdfgpu.hip and linked into the same libsdfgpu.so (sdf_tools_amd/build.py).
 //
 // How the kernels of one call talk to each other: through kernel boundaries, and inside a launch through atomics only.
@@ -13,6 +13,8 @@
 //     several threads of a launch store to one address, they store the same value
 //   - a fused frame tells its cells to a mark plane the same way (one byte value per launch), and one workgroup per touched chunk then
 //     updates each marked record once and clears its mark
+//   - a removal flags slots by a 32-bit atomic min of the operation index, and moves chunks from slots at or above `keep` into
+//     flagged slots below it: the sources and the destinations of the one launch are disjoint
 //
 // Arithmetic: a location on a cell boundary is placed by the rounding of g = inverse_origin * p alone, and tests/dsh_restated.py states
 // that product in numpy (separate products and sums), so nothing here may be contracted into an FMA (hipcc contracts by default).  The
@@ -573,6 +575,149 @@ __global__ __launch_bounds__(kDshThreads) void k_dsh_ray_fuse(const DshPool p, u
     }
 }
 
+// ---- removal (include/sdfgpu.h "Removal") --------------------------------------------------------------------------------
+// One uint32 per live slot says whether the chunk goes: kDshKept, or the smallest index of an operation that names it (by box: 0).
+// The pool keeps its invariant (slots 0 .. n_live - 1 in use) by hole filling: with `keep` survivors, the j-th flagged slot below
+// `keep` takes the j-th unflagged slot at or above it.  Their ranks come out of a two-level scan of linear work over tiles of
+// kDshPairTile slots (count per tile | one workgroup scans the tiles' counts | list), so the pairing depends on the flags alone.
+__global__ __launch_bounds__(kDshThreads) void k_dsh_remove_stamp(const DshGeometry g, const DshTable t, const double* __restrict__ loc, int64_t n,
+                                                                  uint32_t* flags, uint32_t* __restrict__ op_slot) {
+    const int64_t i = dsh_item();
+    if (i >= n) return;
+    uint64_t key = 0;
+    uint32_t cell = 0, slot = kDshNoPos;
+    if (dsh_locate(g, loc[3 * i], loc[3 * i + 1], loc[3 * i + 2], key, cell)) {
+        const uint32_t pos = dsh_find(t, key);
+        if (pos != kDshNoPos) {
+            slot = t.slots[pos];
+            atomicMin(&flags[slot], (uint32_t)i);
+        }
+    }
+    op_slot[i] = slot;
+}
+
+// (behind a kernel boundary) the first operation in list order that names a live chunk removed it
+__global__ __launch_bounds__(kDshThreads) void k_dsh_remove_decide(const uint32_t* __restrict__ flags, const uint32_t* __restrict__ op_slot, int64_t n,
+                                                                   uint8_t* __restrict__ statuses) {
+    const int64_t i = dsh_item();
+    if (i >= n) return;
+    const uint32_t slot = op_slot[i];
+    statuses[i] = slot != kDshNoPos && flags[slot] == (uint32_t)i ? SDFGPU_DSH_CHUNK_REMOVED : SDFGPU_DSH_CHUNK_NOT_REMOVED;
+}
+
+__global__ __launch_bounds__(kDshThreads) void k_dsh_remove_box(const DshChunkHead* __restrict__ heads, uint32_t n_live, const DshChunkRange range,
+                                                                int invert, uint32_t* __restrict__ flags) {
+    const int64_t s = dsh_item();
+    if (s >= n_live) return;
+    const bool in = dsh_key_in_range(heads[s].key, range);
+    flags[s] = in == (invert != 0) ? 0u : kDshKept;
+}
+
+// counters[0] = flagged slots, one atomic per wave
+__global__ __launch_bounds__(kDshThreads) void k_dsh_remove_count(const uint32_t* __restrict__ flags, uint32_t n_live, uint32_t* counters) {
+    const int64_t s = dsh_item();
+    const unsigned long long gone = __ballot(s < n_live && flags[s] != kDshKept);
+    if ((threadIdx.x & 63) == 0 && gone) atomicAdd(&counters[0], (uint32_t)__popcll(gone));
+}
+
+// the holes (low 16 bits) and the movers (high 16 bits) among the thread's kDshPairItems slots from `first` on
+__device__ __forceinline__ uint32_t dsh_pair_local(const uint32_t* __restrict__ flags, uint32_t n_live, uint32_t keep, uint32_t first) {
+    uint32_t both = 0;
+    for (uint32_t k = 0; k < kDshPairItems; ++k) {
+        const uint32_t s = first + k;
+        if (s >= n_live) break;
+        const bool gone = flags[s] != kDshKept;
+        both += (s < keep && gone ? 1u : 0u) + (s >= keep && !gone ? 0x10000u : 0u);
+    }
+    return both;
+}
+
+// exclusive prefix of v over the workgroup's threads and the workgroup's total (v's sums stay below 2^32)
+__device__ __forceinline__ uint32_t dsh_block_exclusive(uint32_t v, uint32_t* wave_sum, uint32_t& total) {
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t inclusive = v;
+    for (uint32_t d = 1; d < 64; d <<= 1) {
+        const uint32_t other = (uint32_t)__shfl_up((int)inclusive, d);
+        if (lane >= d) inclusive += other;
+    }
+    __syncthreads();                                                           // (wave_sum may still be read from an earlier call)
+    if (lane == 63) wave_sum[wave] = inclusive;
+    __syncthreads();
+    uint32_t base = 0;
+    total = 0;
+    for (uint32_t w = 0; w < kDshThreads / 64; ++w) {
+        if (w < wave) base += wave_sum[w];
+        total += wave_sum[w];
+    }
+    return base + inclusive - v;
+}
+
+__global__ __launch_bounds__(kDshThreads) void k_dsh_pair_count(const uint32_t* __restrict__ flags, uint32_t n_live, uint32_t keep,
+                                                                uint32_t* __restrict__ tile_counts) {
+    __shared__ uint32_t wave_sum[kDshThreads / 64];
+    uint32_t total = 0;
+    (void)dsh_block_exclusive(dsh_pair_local(flags, n_live, keep, blockIdx.x * kDshPairTile + threadIdx.x * kDshPairItems), wave_sum, total);
+    if (threadIdx.x == 0) { tile_counts[2 * blockIdx.x] = total & 0xFFFFu; tile_counts[2 * blockIdx.x + 1] = total >> 16; }
+}
+
+// One workgroup: the tiles' counts become their exclusive prefixes, in place; counters[2] = the number of holes.
+__global__ __launch_bounds__(kDshThreads) void k_dsh_pair_scan(uint32_t* __restrict__ tile_counts, uint32_t tiles, uint32_t* counters) {
+    __shared__ uint32_t wave_sum[kDshThreads / 64];
+    const uint32_t per = (tiles + kDshThreads - 1) / kDshThreads;
+    const uint32_t begin = min(threadIdx.x * per, tiles), end = min(begin + per, tiles);
+    uint32_t sum[2] = {0, 0};
+    for (uint32_t k = begin; k < end; ++k) { sum[0] += tile_counts[2 * k]; sum[1] += tile_counts[2 * k + 1]; }
+    uint32_t total = 0;
+    uint32_t holes = dsh_block_exclusive(sum[0], wave_sum, total);
+    if (threadIdx.x == 0) counters[2] = total;
+    uint32_t movers = dsh_block_exclusive(sum[1], wave_sum, total);
+    for (uint32_t k = begin; k < end; ++k) {
+        const uint32_t h = tile_counts[2 * k], m = tile_counts[2 * k + 1];
+        tile_counts[2 * k] = holes; tile_counts[2 * k + 1] = movers;
+        holes += h; movers += m;
+    }
+}
+
+__global__ __launch_bounds__(kDshThreads) void k_dsh_pair_list(const uint32_t* __restrict__ flags, uint32_t n_live, uint32_t keep,
+                                                               const uint32_t* __restrict__ tile_counts, uint32_t* __restrict__ holes,
+                                                               uint32_t* __restrict__ movers) {
+    __shared__ uint32_t wave_sum[kDshThreads / 64];
+    const uint32_t first = blockIdx.x * kDshPairTile + threadIdx.x * kDshPairItems;
+    uint32_t total = 0;
+    const uint32_t before = dsh_block_exclusive(dsh_pair_local(flags, n_live, keep, first), wave_sum, total);
+    uint32_t hole = tile_counts[2 * blockIdx.x] + (before & 0xFFFFu), mover = tile_counts[2 * blockIdx.x + 1] + (before >> 16);
+    for (uint32_t k = 0; k < kDshPairItems; ++k) {
+        const uint32_t s = first + k;
+        if (s >= n_live) break;
+        const bool gone = flags[s] != kDshKept;
+        if (s < keep && gone) holes[hole++] = s;
+        if (s >= keep && !gone) movers[mover++] = s;
+    }
+}
+
+// One workgroup per pair: the mover's head, and its cells when it holds any, go into the hole.  Sources lie at or above `keep`,
+// destinations below it: the moves of one launch are disjoint.  Two records per lane where the chunk's cells are 16-byte aligned
+// (a slot's cells start at slot * cells_per_chunk * 8: an even cells_per_chunk).  The launch is sized by a bound on the pairs;
+// counters[2] holds their number.
+__global__ __launch_bounds__(kDshThreads) void k_dsh_remove_move(const DshPool p, uint64_t cells_per_chunk, const uint32_t* __restrict__ holes,
+                                                                 const uint32_t* __restrict__ movers, const uint32_t* __restrict__ counters) {
+    const uint64_t j = (uint64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    if (j >= counters[2]) return;
+    const uint64_t src = movers[j], dst = holes[j];
+    const DshChunkHead hd = p.heads[src];
+    if (threadIdx.x == 0) p.heads[dst] = hd;
+    if ((hd.state & kDshStateMask) != kDshCellFilled) return;                   // (uniform over the workgroup)
+    const uint64_t* const from = p.cells + src * cells_per_chunk;
+    uint64_t* const to = p.cells + dst * cells_per_chunk;
+    if ((cells_per_chunk & 1) == 0) {
+        const ulonglong2* const from2 = reinterpret_cast<const ulonglong2*>(from);
+        ulonglong2* const to2 = reinterpret_cast<ulonglong2*>(to);
+        for (uint64_t k = threadIdx.x; k < cells_per_chunk / 2; k += kDshThreads) to2[k] = from2[k];
+    } else {
+        for (uint64_t k = threadIdx.x; k < cells_per_chunk; k += kDshThreads) to[k] = from[k];
+    }
+}
+
 size_t dsh_fuse_lds_bytes(uint64_t cells_per_chunk) { return (size_t)((cells_per_chunk + 15) / 16 * 16); }   // at most 32 KiB
 
 dim3 dsh_chunk_grid(uint64_t chunks) {                                        // one workgroup per chunk
@@ -1038,6 +1183,131 @@ int dsh_export_impl(sdfgpu_dsh_map_object* m, sdfgpu_dsh_chunk* d_chunks, int64_
     return SDFGPU_OK;
 }
 
+// One removal on `st`: by list (d_loc, n) or, with `range`, by box.  Flag | count and read back | pair | move | rebuild the table.
+int dsh_remove_impl(sdfgpu_dsh_map_object* m, const double* d_loc, int64_t n, const DshChunkRange* range, int invert, uint8_t* d_statuses,
+                    int64_t* out_removed, hipStream_t st) {
+    sdfgpu_handle h = m->h;
+    if (out_removed) *out_removed = 0;
+    if (!range) {
+        if (n < 0 || n >= kDshMaxBatch) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: a batch holds 0 .. 2^31 - 1 operations (got %lld)", (long long)n);
+        if (n == 0) return SDFGPU_OK;
+        if (!d_loc) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: null locations");
+        if (int rc = dsh_aligned8(h, d_loc, "the locations")) return rc;
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, m->order.create());
+    HIP_TRY(h, m->order.wait(st));
+    StreamOrder::RecordAtExit record_at_exit{m->order, st};
+
+    const size_t live = (size_t)m->n_live, ops = range ? 0 : (size_t)n, tiles = (size_t)dsh_pair_tiles(m->n_live), half = live / 2 + 1;
+    const size_t off_flags = kDshCounterBytes, off_ops = off_flags + align256(live * 4), off_tiles = off_ops + align256(ops * 4),
+                 off_holes = off_tiles + align256(tiles * 8), off_movers = off_holes + align256(half * 4);
+    if (int rc = ensure(h, m->scratch, off_movers + align256(half * 4), "dsh batch scratch")) return rc;
+    char* const base = static_cast<char*>(m->scratch.ptr);
+    uint32_t* const counters = dsh_counters(m);
+    uint32_t* const flags = reinterpret_cast<uint32_t*>(base + off_flags);
+    uint32_t* const op_slot = reinterpret_cast<uint32_t*>(base + off_ops);
+    uint32_t* const tile_counts = reinterpret_cast<uint32_t*>(base + off_tiles);
+    uint32_t* const holes = reinterpret_cast<uint32_t*>(base + off_holes);
+    uint32_t* const movers = reinterpret_cast<uint32_t*>(base + off_movers);
+    const dim3 block(kDshThreads), live_grid = dsh_grid((int64_t)live);
+    const uint32_t n_live = (uint32_t)m->n_live;
+
+    HIP_TRY(h, hipMemsetAsync(counters, 0, kDshCounterBytes, st));
+    if (range) {
+        if (live) hipLaunchKernelGGL(k_dsh_remove_box, live_grid, block, 0, st, m->pool.heads, n_live, *range, invert, flags);
+    } else {
+        if (live) HIP_TRY(h, hipMemsetAsync(flags, 0xFF, live * 4, st));
+        hipLaunchKernelGGL(k_dsh_remove_stamp, dsh_grid(n), block, 0, st, m->g, m->table, d_loc, n, flags, op_slot);
+        if (d_statuses) hipLaunchKernelGGL(k_dsh_remove_decide, dsh_grid(n), block, 0, st, flags, op_slot, n, d_statuses);
+    }
+    if (live) hipLaunchKernelGGL(k_dsh_remove_count, live_grid, block, 0, st, flags, n_live, counters);
+    HIP_TRY(h, hipGetLastError());
+    uint32_t removed = 0;
+    HIP_TRY(h, hipMemcpyAsync(&removed, counters, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));                                       // the call's one synchronisation while nothing is lost
+    if (removed == 0) return SDFGPU_OK;
+    if (removed > n_live) return fail(h, SDFGPU_ERR_HIP, "dsh: %u of %u chunks flagged (internal error)", removed, n_live);
+    const uint32_t keep = n_live - removed;
+    if (keep) {
+        hipLaunchKernelGGL(k_dsh_pair_count, dim3((unsigned)tiles), block, 0, st, flags, n_live, keep, tile_counts);
+        hipLaunchKernelGGL(k_dsh_pair_scan, dim3(1), block, 0, st, tile_counts, (uint32_t)tiles, counters);
+        hipLaunchKernelGGL(k_dsh_pair_list, dim3((unsigned)tiles), block, 0, st, flags, n_live, keep, tile_counts, holes, movers);
+        hipLaunchKernelGGL(k_dsh_remove_move, dsh_chunk_grid(std::min(removed, keep)), block, 0, st, m->pool, (uint64_t)m->g.cells_per_chunk, holes, movers,
+                           counters);
+    }
+    // linear probing has no parallel deletion: the table is made again from the heads that stay
+    HIP_TRY(h, hipMemsetAsync(m->table.keys, 0xFF, (size_t)m->table_cap * 8, st));
+    m->n_live = keep;
+    if (out_removed) *out_removed = (int64_t)removed;
+    if (!keep) return SDFGPU_OK;
+    uint32_t lost = 0;
+    hipLaunchKernelGGL(k_dsh_rehash, dsh_grid((int64_t)keep), block, 0, st, m->table, m->pool.heads, keep, counters);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(&lost, counters + 1, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    if (lost) return fail(h, SDFGPU_ERR_HIP, "dsh: the rehash lost %u keys (internal error)", lost);
+    return SDFGPU_OK;
+}
+
+// shrink-to-fit: dsh_reserve_pool and dsh_reserve_table run downwards.  Both new allocations are made before anything is copied,
+// so a failure leaves the map as it was; the mark plane is given up (dsh_reserve_marks makes it again).
+int dsh_shrink_impl(sdfgpu_dsh_map_object* m, int64_t spare_chunks, hipStream_t st) {
+    sdfgpu_handle h = m->h;
+    if (spare_chunks < 0) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: spare_chunks must not be negative (got %lld)", (long long)spare_chunks);
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, m->order.create());
+    HIP_TRY(h, m->order.wait(st));
+    StreamOrder::RecordAtExit record_at_exit{m->order, st};
+    const uint64_t cpc = (uint64_t)m->g.cells_per_chunk;
+    uint64_t pool_cap = 0, table_cap = 0;
+    dsh_plan_shrink(m->n_live, (uint64_t)spare_chunks, m->pool_cap, m->table_cap, &pool_cap, &table_cap);
+    DshTable table{};
+    DshPool pool{};
+    uint32_t lost = 0;
+    int rc = SDFGPU_OK;
+    if (table_cap < m->table_cap) rc = dsh_alloc_table(h, table_cap, table, st);
+    if (rc == SDFGPU_OK && pool_cap < m->pool_cap) rc = dsh_alloc_pool(h, pool_cap, cpc, pool);
+    if (rc == SDFGPU_OK) rc = [&]() -> int {
+        if (table.keys && m->n_live) {
+            HIP_TRY(h, hipMemsetAsync(dsh_counters(m), 0, kDshCounterBytes, st));
+            hipLaunchKernelGGL(k_dsh_rehash, dsh_grid((int64_t)m->n_live), dim3(kDshThreads), 0, st, table, m->pool.heads, (uint32_t)m->n_live, dsh_counters(m));
+            HIP_TRY(h, hipGetLastError());
+            HIP_TRY(h, hipMemcpyAsync(&lost, dsh_counters(m) + 1, 4, hipMemcpyDeviceToHost, st));
+        }
+        if (pool.heads && m->n_live) {
+            HIP_TRY(h, hipMemcpyAsync(pool.heads, m->pool.heads, (size_t)(m->n_live * sizeof(DshChunkHead)), hipMemcpyDeviceToDevice, st));
+            HIP_TRY(h, hipMemcpyAsync(pool.cells, m->pool.cells, (size_t)(m->n_live * cpc * 8), hipMemcpyDeviceToDevice, st));
+        }
+        HIP_TRY(h, hipStreamSynchronize(st));                                   // (what is replaced may still be read by pending work)
+        if (lost) return fail(h, SDFGPU_ERR_HIP, "dsh: the rehash lost %u keys (internal error)", lost);
+        return SDFGPU_OK;
+    }();
+    if (rc != SDFGPU_OK) {
+        (void)hipStreamSynchronize(st);
+        if (table.keys) (void)rz_free(h, table.keys);
+        if (pool.heads) { (void)rz_free(h, pool.heads); (void)rz_free(h, pool.cells); }
+        return rc;
+    }
+    if (table.keys) {
+        (void)rz_free(h, m->table.keys);
+        m->table = table;
+        m->table_cap = table_cap;
+    }
+    if (pool.heads) {
+        (void)rz_free(h, m->pool.heads);
+        (void)rz_free(h, m->pool.cells);
+        m->pool = pool;
+        m->pool_cap = pool_cap;
+    }
+    if (m->marks) {
+        (void)rz_free(h, m->marks);
+        m->marks = nullptr;
+        m->marks_cap = 0;
+    }
+    return SDFGPU_OK;
+}
+
 // the host forms' staging: sections of the map's stage buffer, 256-byte aligned
 struct DshStage {
     size_t total = 0;
@@ -1238,6 +1508,44 @@ int sdfgpu_dsh_set_cells(sdfgpu_dsh_map map, const double* locations, int64_t n,
 
 int sdfgpu_dsh_set_chunks(sdfgpu_dsh_map map, const double* locations, int64_t n, const void* values, const void* one_value, uint8_t* statuses) {
     return dsh_set_host(map, true, locations, n, values, one_value, statuses);
+}
+
+int sdfgpu_dsh_remove_chunks_device(sdfgpu_dsh_map map, const double* d_locations, int64_t n, uint8_t* d_statuses, int64_t* out_removed, void* stream) {
+    return dsh_entry(map, stream, [&]() -> int { return dsh_remove_impl(map, d_locations, n, nullptr, 0, d_statuses, out_removed, (hipStream_t)stream); });
+}
+
+int sdfgpu_dsh_remove_chunks(sdfgpu_dsh_map map, const double* locations, int64_t n, uint8_t* statuses, int64_t* out_removed) {
+    return dsh_entry(map, nullptr, [&]() -> int {
+        sdfgpu_handle h = map->h;
+        if (n <= 0 || n >= kDshMaxBatch) return dsh_remove_impl(map, nullptr, n, nullptr, 0, nullptr, out_removed, nullptr);
+        if (!locations) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: null locations");
+        HIP_TRY(h, hipSetDevice(h->device));
+        HIP_TRY(h, map->order.wait(nullptr));
+        DshStage s;
+        const size_t un = (size_t)n, at_loc = s.add(un * 24), at_st = s.add(statuses ? un : 0);
+        if (int rc = ensure(h, map->stage, s.total, "dsh staging")) return rc;
+        char* const base = static_cast<char*>(map->stage.ptr);
+        if (int rc = copy_from_host(h, base + at_loc, locations, un * 24)) return rc;
+        if (int rc = dsh_remove_impl(map, reinterpret_cast<const double*>(base + at_loc), n, nullptr, 0,
+                                     statuses ? reinterpret_cast<uint8_t*>(base + at_st) : nullptr, out_removed, nullptr)) return rc;
+        if (statuses) return copy_to_host(h, statuses, base + at_st, un);
+        return SDFGPU_OK;
+    });
+}
+
+int sdfgpu_dsh_retain_box(sdfgpu_dsh_map map, const int64_t lower[3], const int64_t extent[3], int invert, int64_t* out_removed, void* stream) {
+    return dsh_entry(map, stream, [&]() -> int {
+        sdfgpu_handle h = map->h;
+        if (!lower || !extent) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: retain_box needs the box");
+        if (!dsh_box_ok(lower, extent))
+            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: a box has |lower| <= 2^40 and 0 <= extent <= 2^40 on every axis");
+        const DshChunkRange range = dsh_box_chunk_range(lower, extent, map->g.n);
+        return dsh_remove_impl(map, nullptr, 0, &range, invert, nullptr, out_removed, (hipStream_t)stream);
+    });
+}
+
+int sdfgpu_dsh_shrink(sdfgpu_dsh_map map, int64_t spare_chunks, void* stream) {
+    return dsh_entry(map, stream, [&]() -> int { return dsh_shrink_impl(map, spare_chunks, (hipStream_t)stream); });
 }
 
 int sdfgpu_dsh_get_device(sdfgpu_dsh_map map, const double* d_locations, int64_t n, void* d_records, uint8_t* d_statuses, void* stream) {

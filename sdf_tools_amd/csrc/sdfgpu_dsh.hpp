@@ -1,8 +1,8 @@
 // sdfgpu_dsh.hpp -- the chunk-hashed sparse collision map (include/sdfgpu.h "Dynamic spatial hashed map"): its
 // constants, the packing of a chunk coordinate into a table key, the hash, and the planning of the table's and the pool's sizes.
 // Plain C++ without a HIP header, as sdfgpu_plan.hpp and sdfgpu_policy.hpp are: sdfgpu_dsh.hip includes it for its kernels and its host
-// code, and tests/dsh_plan_harness.cpp, tests/dsh_rays_plan_harness.cpp and tests/dsh_fusion_plan_harness.cpp drive the arithmetic on the CPU under
-// -fsanitize=address,undefined.
+// code, and tests/dsh_plan_harness.cpp, tests/dsh_rays_plan_harness.cpp, tests/dsh_fusion_plan_harness.cpp and
+// tests/dsh_remove_plan_harness.cpp drive the arithmetic on the CPU under -fsanitize=address,undefined.
 #pragma once
 #include <stdint.h>
 
@@ -82,6 +82,69 @@ inline bool dsh_plan_pool(uint64_t capacity, uint64_t needed, uint64_t cells_per
     if (byte_limit && table_bytes + dsh_pool_bytes(want, cells_per_chunk) > byte_limit) return false;
     *out_capacity = want;
     return true;
+}
+
+// ---- removal ----------------------------------------------------------------------------------------------------------
+constexpr int64_t kDshMaxBoxCell = (int64_t)1 << 40;       // |lower| and extent of a box of cells are at most this
+constexpr uint32_t kDshKept = 0xFFFFFFFFu;                 // a slot's word in the removal's flag array while nothing removes it
+constexpr uint32_t kDshPairItems = 16;                     // slots per thread of the pairing scan: a tile is kDshPairTile slots
+constexpr uint32_t kDshPairTile = 256 * kDshPairItems;
+
+// A box of cells as a closed range of chunk coordinates per axis, clamped to the key range; `empty` when it holds no chunk.
+struct DshChunkRange {
+    int64_t lo[3], hi[3];
+    int empty;
+};
+
+inline bool dsh_box_ok(const int64_t lower[3], const int64_t extent[3]) {
+    for (int a = 0; a < 3; ++a)
+        if (lower[a] < -kDshMaxBoxCell || lower[a] > kDshMaxBoxCell || extent[a] < 0 || extent[a] > kDshMaxBoxCell) return false;
+    return true;
+}
+
+// The chunks that hold at least one of the cells lower[a] .. lower[a] + extent[a] - 1 (dsh_box_ok holds: no sum passes 2^41).
+inline DshChunkRange dsh_box_chunk_range(const int64_t lower[3], const int64_t extent[3], const int64_t n[3]) {
+    DshChunkRange r{};
+    for (int a = 0; a < 3; ++a) {
+        if (extent[a] == 0) { r.empty = 1; r.lo[a] = 0; r.hi[a] = -1; continue; }
+        const int64_t lo = dsh_floor_div(lower[a], n[a]), hi = dsh_floor_div(lower[a] + extent[a] - 1, n[a]);
+        r.lo[a] = lo < -kDshChunkBias ? -kDshChunkBias : lo;
+        r.hi[a] = hi > kDshChunkBias - 1 ? kDshChunkBias - 1 : hi;
+        if (r.lo[a] > r.hi[a]) r.empty = 1;
+    }
+    return r;
+}
+
+// whether the chunk of `key` holds a cell of the box (unpacked coordinates only)
+SDFGPU_DSH_HD bool dsh_key_in_range(uint64_t key, const DshChunkRange& r) {
+    int64_t c[3];
+    dsh_unpack_key(key, c[0], c[1], c[2]);
+    bool in = !r.empty;
+    for (int a = 0; a < 3; ++a) in = in && c[a] >= r.lo[a] && c[a] <= r.hi[a];
+    return in;
+}
+
+// The pairing of a removal, on the host (tests/dsh_remove_plan_harness.cpp holds the kernels' scan against it): with `keep` slots
+// unflagged, the j-th flagged slot below `keep` (a hole) takes the j-th unflagged slot at or above it (a mover), both ascending.
+// Returns the number of pairs; holes / movers need room for min(keep, n - keep) entries.
+inline uint64_t dsh_pair_model(const uint8_t* flagged, uint64_t n, uint64_t keep, uint32_t* holes, uint32_t* movers) {
+    uint64_t n_holes = 0, n_movers = 0;
+    for (uint64_t s = 0; s < n; ++s) {
+        if (s < keep && flagged[s]) holes[n_holes++] = (uint32_t)s;
+        if (s >= keep && !flagged[s]) movers[n_movers++] = (uint32_t)s;
+    }
+    return n_holes == n_movers ? n_holes : ~(uint64_t)0;
+}
+inline uint64_t dsh_pair_tiles(uint64_t n) { return (n + kDshPairTile - 1) / kDshPairTile; }
+
+// What shrink leaves: the pool at max(live + spare, 1) chunks and the table at dsh_table_capacity(live + spare), each only where
+// that is smaller than what the map holds.  (spare is clamped where it cannot matter: no sum overflows.)
+inline void dsh_plan_shrink(uint64_t live, uint64_t spare, uint64_t pool_cap, uint64_t table_cap, uint64_t* out_pool, uint64_t* out_table) {
+    if (spare > ((uint64_t)1 << 32)) spare = (uint64_t)1 << 32;
+    const uint64_t chunks = live + spare;
+    const uint64_t pool = chunks > 1 ? chunks : 1, table = dsh_table_capacity(chunks);
+    *out_pool = pool < pool_cap ? pool : pool_cap;
+    *out_table = table < table_cap ? table : table_cap;
 }
 
 // ---- a frame of sensor rays ------------------------------------------------------------------------------------------
