@@ -13,6 +13,7 @@
 // (COLLISION_CELL(), NOT_FOUND), the setters return NOT_SET, the batch forms and extractions throw std::runtime_error and
 // ExportForDisplay returns no marker.  (The reference's two other constructors never set initialized_; here they do.)
 #pragma once
+#include <cmath>
 #include <cstring>
 #include <memory>
 #include <mutex>
@@ -273,6 +274,64 @@ public:
         Locked([&](sdfgpu_dsh_map m) { return sdfgpu_dsh_shrink(m, spare_chunks, nullptr); });
     }
 
+    // ---- ray casts (additions; include/sdfgpu.h "Ray casts") -----------------------------------------------------------
+    // What a ray meets first: the walk of InsertPointCloudRays, read-only, stopped at the first cell whose record satisfies the
+    // CollisionMapGrid predicate (occupancy > 0.5, or == 0.5 with unknown_is_filled).  skip_first leaves the start's cell untested,
+    // skip_last the end's; both together ask whether the segment between two cells is clear.  max_range must span more than 0 and at
+    // most 65536 cells, and CastRays' sensor must be a valid location: otherwise std::invalid_argument.  A ray with an invalid end
+    // is SKIPPED.  The contract is this project's own, UNVERIFIED against octomap's castRay.
+    enum CAST_STATUS { CAST_SKIPPED = SDFGPU_DSH_CAST_SKIPPED, CAST_CLEAR = SDFGPU_DSH_CAST_CLEAR, CAST_CLEAR_IN_RANGE = SDFGPU_DSH_CAST_CLEAR_IN_RANGE,
+                       CAST_BLOCKED = SDFGPU_DSH_CAST_BLOCKED };
+    struct RayCast {
+        CAST_STATUS status;               // BLOCKED: the fields below describe the blocker; CLEAR / CLEAR_IN_RANGE: the last cell walked
+        VoxelGrid::GRID_INDEX cell;       // global cell index (the coordinates of the window extractions' lower_index)
+        COLLISION_CELL value;             // what Get returns there
+        VoxelGrid::FOUND_STATUS found;
+        double t;                         // the fraction of start -> end at which the ray enters the cell (0 for the start's cell)
+        uint32_t step;                    // the cell's place in the walk
+        double distance;                  // t * sqrt((dx dx + dy dy) + dz dz) of end - start in world units, in double on the host
+    };
+    std::vector<RayCast> CastRays(const std::vector<float>& points_xyz, const Eigen::Vector3d& sensor_origin, const double max_range,
+                                  const bool unknown_is_filled, const bool skip_first = false, const bool skip_last = false) const {
+        RequireInitialized();
+        if (points_xyz.size() % 3) throw std::invalid_argument("CastRays: points are x, y, z triples");
+        const size_t n = points_xyz.size() / 3;
+        const double sensor[3] = {sensor_origin.x(), sensor_origin.y(), sensor_origin.z()};
+        std::vector<uint8_t> statuses(n);
+        std::vector<sdfgpu_dsh_cast_hit> hits(n);
+        uint8_t no_status = 0;                                                 // (an output must be given, with no ray too)
+        Locked([&](sdfgpu_dsh_map m) {
+            return sdfgpu_dsh_cast_rays(m, sensor, points_xyz.data(), (int64_t)n, max_range, CastFlags(unknown_is_filled, skip_first, skip_last),
+                                        n ? statuses.data() : &no_status, hits.data());
+        });
+        std::vector<RayCast> casts(n);
+        for (size_t i = 0; i < n; ++i) {
+            const double end[3] = {(double)points_xyz[3 * i], (double)points_xyz[3 * i + 1], (double)points_xyz[3 * i + 2]};
+            casts[i] = MakeRayCast(statuses[i], hits[i], sensor, end);
+        }
+        return casts;
+    }
+    std::vector<RayCast> CastSegments(const std::vector<double>& starts_xyz, const std::vector<double>& ends_xyz, const double max_range,
+                                      const bool unknown_is_filled, const bool skip_first = false, const bool skip_last = false) const {
+        RequireInitialized();
+        if (starts_xyz.size() % 3 || starts_xyz.size() != ends_xyz.size()) throw std::invalid_argument("CastSegments: starts and ends are as many x, y, z triples");
+        const size_t n = starts_xyz.size() / 3;
+        std::vector<uint8_t> statuses(n);
+        std::vector<sdfgpu_dsh_cast_hit> hits(n);
+        uint8_t no_status = 0;
+        Locked([&](sdfgpu_dsh_map m) {
+            return sdfgpu_dsh_cast_segments(m, starts_xyz.data(), ends_xyz.data(), (int64_t)n, max_range, CastFlags(unknown_is_filled, skip_first, skip_last),
+                                            n ? statuses.data() : &no_status, hits.data());
+        });
+        std::vector<RayCast> casts(n);
+        for (size_t i = 0; i < n; ++i) casts[i] = MakeRayCast(statuses[i], hits[i], starts_xyz.data() + 3 * i, ends_xyz.data() + 3 * i);
+        return casts;
+    }
+    RayCast CastRay(const Eigen::Vector3d& origin, const Eigen::Vector3d& end, const double max_range, const bool unknown_is_filled,
+                    const bool skip_first = false, const bool skip_last = false) const {
+        return CastSegments({origin.x(), origin.y(), origin.z()}, {end.x(), end.y(), end.z()}, max_range, unknown_is_filled, skip_first, skip_last)[0];
+    }
+
     // ---- dense windows (additions) ------------------------------------------------------------------------------------------------------
     // The nx x ny x nz cells from global cell lower_index on as a CollisionMapGrid: cell (x, y, z) is what Get returns there.  The
     // result's origin is the map's origin times the translation to that corner; its OOB value is the map's default.
@@ -388,6 +447,22 @@ public:
     }
 
 private:
+    static uint32_t CastFlags(const bool unknown_is_filled, const bool skip_first, const bool skip_last) {
+        return (unknown_is_filled ? (uint32_t)SDFGPU_DSH_CAST_UNKNOWN_IS_FILLED : 0u) | (skip_first ? (uint32_t)SDFGPU_DSH_CAST_SKIP_FIRST : 0u) |
+               (skip_last ? (uint32_t)SDFGPU_DSH_CAST_SKIP_LAST : 0u);
+    }
+    static RayCast MakeRayCast(const uint8_t status, const sdfgpu_dsh_cast_hit& hit, const double* start, const double* end) {
+        RayCast cast;
+        cast.status = (CAST_STATUS)status;
+        cast.cell = VoxelGrid::GRID_INDEX(hit.cell[0], hit.cell[1], hit.cell[2]);
+        std::memcpy(static_cast<void*>(&cast.value), &hit.record, sizeof cast.value);
+        cast.found = (VoxelGrid::FOUND_STATUS)hit.found;
+        cast.t = hit.t;
+        cast.step = hit.step;
+        const double dx = end[0] - start[0], dy = end[1] - start[1], dz = end[2] - start[2];
+        cast.distance = status == SDFGPU_DSH_CAST_SKIPPED ? 0.0 : hit.t * std::sqrt((dx * dx + dy * dy) + dz * dz);
+        return cast;
+    }
     int64_t BoxRemoval(const VoxelGrid::GRID_INDEX& lower_index, const int64_t nx, const int64_t ny, const int64_t nz, const int invert) {
         RequireInitialized();
         const int64_t lower[3] = {lower_index.x, lower_index.y, lower_index.z}, extent[3] = {nx, ny, nz};

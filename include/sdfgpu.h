@@ -1050,8 +1050,8 @@ int sdfgpu_display_select_contour(sdfgpu_handle h, const void* cells, size_t cel
  * Streams: the _device forms run on the caller's stream.  The two setters, sdfgpu_dsh_insert_points_device,
  * sdfgpu_dsh_insert_rays_device and sdfgpu_dsh_fuse_rays_device synchronise that stream once (they read the number of new chunks back before the pool may grow;
  * a call that grows the table or the pool synchronises once more per growth), sdfgpu_dsh_info and the two export forms
- * synchronise too (they read counts back); sdfgpu_dsh_get_device and sdfgpu_dsh_extract_window_device return with their kernels
- * pending.  The removals (sdfgpu_dsh_remove_chunks_device, sdfgpu_dsh_retain_box) synchronise the stream once, to read the
+ * synchronise too (they read counts back); sdfgpu_dsh_get_device, sdfgpu_dsh_extract_window_device and the two cast forms
+ * (sdfgpu_dsh_cast_rays_device, sdfgpu_dsh_cast_segments_device) return with their kernels pending.  The removals (sdfgpu_dsh_remove_chunks_device, sdfgpu_dsh_retain_box) synchronise the stream once, to read the
  * removed count back; a call that removed something and kept something synchronises once more behind the rebuilt table (the
  * rehash's check that no key was lost).  sdfgpu_dsh_shrink synchronises before it frees what it replaced.  Calls on one map from different streams are ordered by the map (an event behind its last call); one host thread
  * per map at a time.
@@ -1230,6 +1230,60 @@ int sdfgpu_dsh_remove_chunks(sdfgpu_dsh_map map, const double* locations, int64_
 int sdfgpu_dsh_retain_box(sdfgpu_dsh_map map, const int64_t lower[3], const int64_t extent[3], int invert, int64_t* out_removed,
                           void* stream);
 int sdfgpu_dsh_shrink(sdfgpu_dsh_map map, int64_t spare_chunks, void* stream);
+
+/* Ray casts: what does a ray meet first.  The map is read the way the frames above wrote it: one walk per
+ * ray, stopped at the first cell that blocks.  The contract is this project's own, UNVERIFIED against octomap's castRay;
+ * tests/dsh_cast_restated.py restates it.
+ *
+ * Everything about a ray is the "Sensor rays" section, unchanged: grid coordinates, i0, i1, d, len2, R = max_range * (1 / cell_size),
+ * the walk c_0 .. c_N with its tie order and its entry parameters t_k, "long iff len2 > R R", the in-range prefix
+ * (t_k t_k) len2 <= R R, IEEE double with separate products and sums.  A walk between two valid locations never leaves the valid
+ * chunk range: each axis moves monotonically between its ends.
+ *
+ * The result of one ray:
+ *   1. W is the walk's cells: c_0 .. c_N for a ray that is not long, the in-range prefix (which always holds c_0) for a long one
+ *   2. the tested cells are W, without c_0 when SDFGPU_DSH_CAST_SKIP_FIRST is set, and without c_N (where the walk reaches it)
+ *      when SDFGPU_DSH_CAST_SKIP_LAST is set; both together ask "is the segment between these two cells clear, ends excepted"
+ *   3. a cell blocks iff the record Get returns there (the default for an absent chunk, the chunk's record for a chunk-filled one,
+ *      the cell's own otherwise) satisfies the window predicate on its low 4 bytes read as a float:
+ *      occupancy > 0.5f || (SDFGPU_DSH_CAST_UNKNOWN_IS_FILLED && occupancy == 0.5f).  A NaN occupancy never blocks
+ *   4. the first tested cell in walk order that blocks gives SDFGPU_DSH_CAST_BLOCKED, and the hit record describes that cell
+ *   5. if no tested cell blocks: SDFGPU_DSH_CAST_CLEAR for a ray that is not long, SDFGPU_DSH_CAST_CLEAR_IN_RANGE for a long one;
+ *      the hit record then describes the last cell of W, tested or not
+ *   6. a ray with an end that is not finite or not a valid location (in the segment form: either end) gets
+ *      SDFGPU_DSH_CAST_SKIPPED and a hit record of 48 zero bytes
+ * The kernel writes t and takes no square root: a world distance is the caller's arithmetic (t times the length of end - start).
+ *
+ * sdfgpu_dsh_cast_rays*: one sensor (host memory) and n x 3 float points, exactly as a frame takes them; the whole call is refused
+ *   with SDFGPU_ERR_INVALID_ARGUMENT for a sensor that is not finite or not a valid location.
+ * sdfgpu_dsh_cast_segments*: n x 3 doubles each for starts and ends (the type of Get's locations); each start goes through the
+ *   grid-coordinate expression on the device, and an invalid start skips that ray only.
+ * Both: n in 0 .. 2^31 - 1; R must lie in (0, 65536] (NaN refused), which bounds every walk: there is no unlimited range; a flag
+ *   bit outside the three is refused; statuses and hits are each optional, but one must be given, and both are undefined when the
+ *   call fails; buffers need their natural alignment (points 4, starts / ends 8, statuses 1, hits 8 bytes).  The device forms
+ *   enqueue one kernel on the caller's stream and return with it pending, as sdfgpu_dsh_get_device does; they allocate nothing and
+ *   are ordered behind the map's last call by the map's event.  The map is not changed by a byte, and sdfgpu_dsh_info reads the
+ *   same before and after (the host forms stage through the map's staging buffer, which scratch_bytes counts and a first call may
+ *   grow). */
+enum { SDFGPU_DSH_CAST_SKIPPED = 0, SDFGPU_DSH_CAST_CLEAR = 1, SDFGPU_DSH_CAST_CLEAR_IN_RANGE = 2, SDFGPU_DSH_CAST_BLOCKED = 3 };   /* a cast's status byte */
+enum { SDFGPU_DSH_CAST_SKIP_FIRST = 1, SDFGPU_DSH_CAST_SKIP_LAST = 2, SDFGPU_DSH_CAST_UNKNOWN_IS_FILLED = 4 };                      /* a cast's flags */
+
+typedef struct sdfgpu_dsh_cast_hit {    /* 48 bytes */
+    int64_t cell[3];             /* global cell index, the coordinates of sdfgpu_dsh_extract_window's lower */
+    uint64_t record;             /* what Get returns there, byte for byte */
+    double t;                    /* the cell's entry parameter t_k (0 for c_0): the fraction of start -> end at which the ray enters it */
+    uint32_t step;               /* k: the cell's place in the walk */
+    uint32_t found;              /* SDFGPU_DSH_NOT_FOUND / FOUND_IN_CHUNK / FOUND_IN_CELL of that cell */
+} sdfgpu_dsh_cast_hit;
+
+int sdfgpu_dsh_cast_rays_device(sdfgpu_dsh_map map, const double sensor[3], const float* d_points, int64_t n, double max_range,
+                                uint32_t flags, uint8_t* d_statuses, sdfgpu_dsh_cast_hit* d_hits, void* stream);
+int sdfgpu_dsh_cast_rays(sdfgpu_dsh_map map, const double sensor[3], const float* points, int64_t n, double max_range, uint32_t flags,
+                         uint8_t* statuses, sdfgpu_dsh_cast_hit* hits);
+int sdfgpu_dsh_cast_segments_device(sdfgpu_dsh_map map, const double* d_starts, const double* d_ends, int64_t n, double max_range,
+                                    uint32_t flags, uint8_t* d_statuses, sdfgpu_dsh_cast_hit* d_hits, void* stream);
+int sdfgpu_dsh_cast_segments(sdfgpu_dsh_map map, const double* starts, const double* ends, int64_t n, double max_range, uint32_t flags,
+                             uint8_t* statuses, sdfgpu_dsh_cast_hit* hits);
 
 /* Get for n locations: 8-byte records and / or one status byte each (SDFGPU_DSH_NOT_FOUND / FOUND_IN_CHUNK / FOUND_IN_CELL);
  * either output may be null, not both. */

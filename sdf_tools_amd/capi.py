@@ -47,6 +47,7 @@ EXPORTS = [
     "sdfgpu_dsh_set_cells_device", "sdfgpu_dsh_set_cells", "sdfgpu_dsh_set_chunks_device", "sdfgpu_dsh_set_chunks",
     "sdfgpu_dsh_insert_points_device", "sdfgpu_dsh_insert_rays_device", "sdfgpu_dsh_insert_rays", "sdfgpu_dsh_fuse_rays_device", "sdfgpu_dsh_fuse_rays",
     "sdfgpu_dsh_remove_chunks_device", "sdfgpu_dsh_remove_chunks", "sdfgpu_dsh_retain_box", "sdfgpu_dsh_shrink",
+    "sdfgpu_dsh_cast_rays_device", "sdfgpu_dsh_cast_rays", "sdfgpu_dsh_cast_segments_device", "sdfgpu_dsh_cast_segments",
     "sdfgpu_dsh_get_device", "sdfgpu_dsh_get",
     "sdfgpu_dsh_extract_window_device", "sdfgpu_dsh_extract_window", "sdfgpu_dsh_export_device", "sdfgpu_dsh_export",
 ]
@@ -211,6 +212,10 @@ def load_library():
     L.sdfgpu_dsh_remove_chunks.argtypes = [vp, vp, i64, vp, vp]
     L.sdfgpu_dsh_retain_box.argtypes = [vp, vp, vp, ci, vp, vp]
     L.sdfgpu_dsh_shrink.argtypes = [vp, i64, vp]
+    L.sdfgpu_dsh_cast_rays_device.argtypes = [vp, vp, vp, i64, dbl, ctypes.c_uint32, vp, vp, vp]
+    L.sdfgpu_dsh_cast_rays.argtypes = [vp, vp, vp, i64, dbl, ctypes.c_uint32, vp, vp]
+    L.sdfgpu_dsh_cast_segments_device.argtypes = [vp, vp, vp, i64, dbl, ctypes.c_uint32, vp, vp, vp]
+    L.sdfgpu_dsh_cast_segments.argtypes = [vp, vp, vp, i64, dbl, ctypes.c_uint32, vp, vp]
     L.sdfgpu_dsh_get_device.argtypes = [vp, vp, i64, vp, vp, vp]
     L.sdfgpu_dsh_get.argtypes = [vp, vp, i64, vp, vp]
     L.sdfgpu_dsh_extract_window_device.argtypes = [vp, vp, i64, i64, i64, ci, vp, vp, vp]
@@ -1345,11 +1350,14 @@ DSH_NOT_FOUND, DSH_FOUND_IN_CHUNK, DSH_FOUND_IN_CELL = 0, 1, 2
 DSH_NOT_SET, DSH_SET_CHUNK, DSH_SET_CELL = 0, 1, 2
 DSH_RAY_SKIPPED, DSH_RAY_HIT, DSH_RAY_TRUNCATED = 0, 1, 2
 DSH_CHUNK_NOT_REMOVED, DSH_CHUNK_REMOVED = 0, 1
+DSH_CAST_SKIPPED, DSH_CAST_CLEAR, DSH_CAST_CLEAR_IN_RANGE, DSH_CAST_BLOCKED = 0, 1, 2, 3
+DSH_CAST_SKIP_FIRST, DSH_CAST_SKIP_LAST, DSH_CAST_UNKNOWN_IS_FILLED = 1, 2, 4
 DSH_MAX_CHUNK_CELLS = 32768
 DSH_COUNTS_DTYPE = np.dtype([(n, np.uint64) for n in ("chunk_filled", "cell_filled", "capacity_chunks", "table_capacity", "bytes_held",
                                                       "scratch_bytes", "byte_limit")])
 DSH_RAY_COUNTS_DTYPE = np.dtype([(n, np.uint64) for n in ("rays_hit", "rays_truncated", "rays_skipped", "cells_carved", "new_chunks")])
 DSH_SENSOR_MODEL_DTYPE = np.dtype([(n, np.float32) for n in ("prob_hit", "prob_miss", "clamp_min", "clamp_max")])
+DSH_CAST_HIT_DTYPE = np.dtype([("cell", np.int64, (3,)), ("record", np.uint64), ("t", np.float64), ("step", np.uint32), ("found", np.uint32)])
 DSH_SENSOR_MODEL_DEFAULT = (0.7, 0.4, 0.12, 0.97)                             # octomap's numbers
 DSH_CHUNK_DTYPE = np.dtype([("c", np.int64, (3,)), ("state", np.uint32), ("reserved", np.uint32), ("record", np.uint64),
                             ("first_cell", np.int64)])
@@ -1511,6 +1519,39 @@ class DshMap:
     def shrink(self, spare_chunks=0, stream=0):
         """Hand memory back: the pool to max(live + spare_chunks, 1) chunks, the table to match, the mark plane freed"""
         self._check(self._lib.sdfgpu_dsh_shrink(self._m, int(spare_chunks), stream or None))
+
+    def cast_rays(self, sensor, points, max_range, flags=0, statuses=True, hits=True):
+        """The first blocking cell of each ray sensor -> point (sdfgpu_dsh_cast_rays): points float32 [n, 3], flags of DSH_CAST_* ->
+        (statuses uint8 [n] or None, hits DSH_CAST_HIT_DTYPE [n] or None)"""
+        s = np.ascontiguousarray(sensor, np.float64).reshape(3)
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        st = np.zeros(len(pts), np.uint8) if statuses else None
+        ht = np.zeros(len(pts), DSH_CAST_HIT_DTYPE) if hits else None
+        self._check(self._lib.sdfgpu_dsh_cast_rays(self._m, s.ctypes.data, pts.ctypes.data, len(pts), float(max_range), int(flags),
+                                                   None if st is None else st.ctypes.data, None if ht is None else ht.ctypes.data))
+        return st, ht
+
+    def cast_rays_device(self, sensor, d_points, n, max_range, flags=0, d_statuses=0, d_hits=0, stream=0):
+        """sdfgpu_dsh_cast_rays_device: one kernel on `stream`, pending on return; d_hits takes n records of DSH_CAST_HIT_DTYPE"""
+        s = np.ascontiguousarray(sensor, np.float64).reshape(3)
+        self._check(self._lib.sdfgpu_dsh_cast_rays_device(self._m, s.ctypes.data, d_points or None, int(n), float(max_range), int(flags), d_statuses or None,
+                                                          d_hits or None, stream or None))
+
+    def cast_segments(self, starts, ends, max_range, flags=0, statuses=True, hits=True):
+        """The first blocking cell of each segment start -> end (sdfgpu_dsh_cast_segments): float64 [n, 3] each -> as cast_rays"""
+        a = np.ascontiguousarray(starts, np.float64).reshape(-1, 3)
+        b = np.ascontiguousarray(ends, np.float64).reshape(-1, 3)
+        if len(a) != len(b):
+            raise ValueError("cast_segments: %d starts and %d ends" % (len(a), len(b)))
+        st = np.zeros(len(a), np.uint8) if statuses else None
+        ht = np.zeros(len(a), DSH_CAST_HIT_DTYPE) if hits else None
+        self._check(self._lib.sdfgpu_dsh_cast_segments(self._m, a.ctypes.data, b.ctypes.data, len(a), float(max_range), int(flags),
+                                                       None if st is None else st.ctypes.data, None if ht is None else ht.ctypes.data))
+        return st, ht
+
+    def cast_segments_device(self, d_starts, d_ends, n, max_range, flags=0, d_statuses=0, d_hits=0, stream=0):
+        self._check(self._lib.sdfgpu_dsh_cast_segments_device(self._m, d_starts or None, d_ends or None, int(n), float(max_range), int(flags),
+                                                              d_statuses or None, d_hits or None, stream or None))
 
     def get(self, locations):
         """(records uint64 [n], statuses uint8 [n])"""

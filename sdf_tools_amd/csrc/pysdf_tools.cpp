@@ -819,6 +819,27 @@ PYBIND11_MODULE(pysdf_tools, m) {
         for (size_t i = 0; i < statuses.size(); ++i) out.mutable_data()[i] = (uint8_t)statuses[i];
         return out;
     };
+    auto dsh_casts = [](const std::vector<DshGrid::RayCast>& casts) {
+        const py::ssize_t n = (py::ssize_t)casts.size();
+        py::array_t<uint8_t> status(n);
+        py::array_t<int64_t> cell({n, (py::ssize_t)3});
+        py::array_t<uint64_t> record(n);
+        py::array_t<uint32_t> found(n), step(n);
+        py::array_t<double> t(n), distance(n);
+        for (py::ssize_t i = 0; i < n; ++i) {
+            const DshGrid::RayCast& c = casts[(size_t)i];
+            status.mutable_data()[i] = (uint8_t)c.status;
+            cell.mutable_data()[3 * i] = c.cell.x; cell.mutable_data()[3 * i + 1] = c.cell.y; cell.mutable_data()[3 * i + 2] = c.cell.z;
+            std::memcpy(record.mutable_data() + i, static_cast<const void*>(&c.value), 8);
+            found.mutable_data()[i] = (uint32_t)c.found;
+            step.mutable_data()[i] = c.step;
+            t.mutable_data()[i] = c.t;
+            distance.mutable_data()[i] = c.distance;
+        }
+        py::dict d;
+        d["status"] = status; d["cell"] = cell; d["record"] = record; d["found"] = found; d["t"] = t; d["step"] = step; d["distance"] = distance;
+        return d;
+    };
     py::class_<DshGrid>(m, "DynamicSpatialHashedCollisionMapGrid")
         .def(py::init<>())
         .def(py::init<std::string, double, int64_t, int64_t, int64_t, COLLISION_CELL>(), py::arg("frame"), py::arg("resolution"), py::arg("chunk_x_size"),
@@ -878,6 +899,26 @@ PYBIND11_MODULE(pysdf_tools, m) {
         }, py::arg("points"), py::arg("sensor_origin"), py::arg("max_range"), py::arg("prob_hit") = 0.7f, py::arg("prob_miss") = 0.4f, py::arg("clamp_min") = 0.12f,
            py::arg("clamp_max") = 0.97f,
            "one frame of sensor rays fused into the occupancies: each passed cell updated once with prob_miss, each hit cell once with prob_hit; returns the counts")
+        .def("CastRays", [=](const DshGrid& g, const py::array_t<float, py::array::c_style | py::array::forcecast>& points,
+                             const std::array<double, 3>& sensor_origin, double max_range, bool unknown_is_filled, bool skip_first, bool skip_last) {
+            if (points.size() % 3) throw std::invalid_argument("points: float32 [n, 3]");
+            return dsh_casts(g.CastRays(std::vector<float>(points.data(), points.data() + points.size()),
+                                        Eigen::Vector3d(sensor_origin[0], sensor_origin[1], sensor_origin[2]), max_range, unknown_is_filled, skip_first, skip_last));
+        }, py::arg("points"), py::arg("sensor_origin"), py::arg("max_range"), py::arg("unknown_is_filled"), py::arg("skip_first") = false,
+           py::arg("skip_last") = false,
+           "the first blocking cell of each ray sensor -> point: a dict of arrays (status uint8, cell int64 [n, 3], record uint64, found, t, step, distance)")
+        .def("CastSegments", [=](const DshGrid& g, const py::array_t<double, py::array::c_style | py::array::forcecast>& starts,
+                                 const py::array_t<double, py::array::c_style | py::array::forcecast>& ends, double max_range, bool unknown_is_filled,
+                                 bool skip_first, bool skip_last) {
+            return dsh_casts(g.CastSegments(dsh_locations(starts), dsh_locations(ends), max_range, unknown_is_filled, skip_first, skip_last));
+        }, py::arg("starts"), py::arg("ends"), py::arg("max_range"), py::arg("unknown_is_filled"), py::arg("skip_first") = false, py::arg("skip_last") = false,
+           "the first blocking cell of each segment start -> end (float64 [n, 3] each): the dict of CastRays")
+        .def("CastRay", [=](const DshGrid& g, const std::array<double, 3>& origin, const std::array<double, 3>& end, double max_range, bool unknown_is_filled,
+                            bool skip_first, bool skip_last) {
+            return dsh_casts({g.CastRay(Eigen::Vector3d(origin[0], origin[1], origin[2]), Eigen::Vector3d(end[0], end[1], end[2]), max_range, unknown_is_filled,
+                                        skip_first, skip_last)});
+        }, py::arg("origin"), py::arg("end"), py::arg("max_range"), py::arg("unknown_is_filled"), py::arg("skip_first") = false, py::arg("skip_last") = false,
+           "one ray: the dict of CastRays with arrays of length 1")
         .def("RemoveChunk", [](DshGrid& g, double x, double y, double z) { return g.RemoveChunk(x, y, z); })
         .def("RemoveChunks", [=](DshGrid& g, const py::array_t<double, py::array::c_style | py::array::forcecast>& locations) {
             const std::vector<bool> removed = g.RemoveChunks(dsh_locations(locations));

@@ -1,6 +1,6 @@
 // sdfgpu_dsh.hip -- the chunk-hashed sparse collision map (sdfgpu_dsh.hpp, include/sdfgpu.h "Dynamic spatial hashed map", DESIGN.md
-// sections 29 to 32): its kernels, the host orchestration of a batch, of a frame of sensor rays (carved or fused) and of a removal, growth and
-// shrinking, and the C ABI entry points sdfgpu_dsh_*.  Compiled beside
+// sections 29 to 33): its kernels, the host orchestration of a batch, of a frame of sensor rays (carved or fused), of a removal and of a
+// ray cast, growth and shrinking, and the C ABI entry points sdfgpu_dsh_*.  Compiled beside
 // sdfgpu.hip and linked into the same libsdfgpu.so (sdf_tools_amd/build.py).
 //
 // How the kernels of one call talk to each other: through kernel boundaries, and inside a launch through atomics only.
@@ -13,6 +13,7 @@
 //     several threads of a launch store to one address, they store the same value
 //   - a fused frame tells its cells to a mark plane the same way (one byte value per launch), and one workgroup per touched chunk then
 //     updates each marked record once and clears its mark
+//   - a ray cast reads only: one kernel, no scratch, and nothing another thread of the launch wrote
 //   - a removal flags slots by a 32-bit atomic min of the operation index, and moves chunks from slots at or above `keep` into
 //     flagged slots below it: the sources and the destinations of the one launch are disjoint
 //
@@ -347,8 +348,16 @@ struct DshRayWalk {
     bool is_long;
 };
 
-// SDFGPU_DSH_RAY_SKIPPED for a point that is no valid location; else _HIT or _TRUNCATED, and the walk stands on the sensor's cell
-__device__ __forceinline__ uint32_t dsh_ray_begin(const DshGeometry& g, const DshRayFrame& f, double px, double py, double pz, DshRayWalk& w) {
+// Where a ray starts: its grid coordinates, their floors, and the floors' chunk and cell inside the chunk.  A frame's rays share the
+// host's (dsh_ray_frame); a cast segment works its own out in the lane (dsh_ray_start).
+struct DshRayStart {
+    double gs[3];
+    int64_t i0[3], c0[3], l0[3];
+};
+
+// SDFGPU_DSH_RAY_SKIPPED for a point that is no valid location; else _HIT or _TRUNCATED, and the walk stands on the start's cell
+template <class Start>
+__device__ __forceinline__ uint32_t dsh_ray_begin(const DshGeometry& g, const Start& f, double range2, double px, double py, double pz, DshRayWalk& w) {
     if (!(isfinite(px) && isfinite(py) && isfinite(pz))) return SDFGPU_DSH_RAY_SKIPPED;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
@@ -369,8 +378,29 @@ __device__ __forceinline__ uint32_t dsh_ray_begin(const DshGeometry& g, const Ds
         w.l[a] = (int32_t)f.l0[a];
     }
     w.len2 = (w.d[0] * w.d[0] + w.d[1] * w.d[1]) + w.d[2] * w.d[2];
-    w.is_long = w.len2 > f.range2;
+    w.is_long = w.len2 > range2;
     return w.is_long ? SDFGPU_DSH_RAY_TRUNCATED : SDFGPU_DSH_RAY_HIT;
+}
+__device__ __forceinline__ uint32_t dsh_ray_begin(const DshGeometry& g, const DshRayFrame& f, double px, double py, double pz, DshRayWalk& w) {
+    return dsh_ray_begin(g, f, f.range2, px, py, pz, w);
+}
+
+// a segment's start in the lane: dsh_ray_frame's arithmetic (this file is compiled without contraction); false for an invalid one
+__device__ __forceinline__ bool dsh_ray_start(const DshGeometry& g, double sx, double sy, double sz, DshRayStart& s) {
+    if (!(isfinite(sx) && isfinite(sy) && isfinite(sz))) return false;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const double* m = g.inverse + 4 * a;
+        const double ga = ((m[0] * sx + m[1] * sy) + m[2] * sz) + m[3];
+        s.gs[a] = ga * g.inv_cell;
+        const double v = floor(s.gs[a]);
+        const double lim = (double)(kDshChunkBias * g.n[a]);
+        if (!(v >= -lim && v < lim)) return false;
+        s.i0[a] = (int64_t)v;
+        s.c0[a] = dsh_floor_div(s.i0[a], g.n[a]);
+        s.l0[a] = s.i0[a] - s.c0[a] * g.n[a];
+    }
+    return true;
 }
 
 // One step: along the axis with the smallest crossing parameter, x before y before z.  Returns that parameter, the entry parameter
@@ -573,6 +603,91 @@ __global__ __launch_bounds__(kDshThreads) void k_dsh_ray_fuse(const DshPool p, u
         const uint32_t mark = staged[k];
         if (mark) dsh_fuse_cell(cells + k, mark, u);
     }
+}
+
+// ---- ray casts (include/sdfgpu.h "Ray casts") ------------------------------------------------------------------------------
+// One lane per ray, read-only: the walk of a frame (dsh_ray_begin, dsh_ray_step), stopped at the first tested cell whose record
+// satisfies the window predicate.  A chunk is looked up once, when the walk enters it; an absent or chunk-filled one is decided there
+// and then stepped through without a memory access, a cell-filled one costs one 8-byte load per tested cell.  No atomics, no LDS.
+__device__ __forceinline__ bool dsh_cast_blocks(uint64_t record, bool unknown_is_filled) {
+    const float occ = __uint_as_float((uint32_t)record);                      // k_dsh_window's predicate: a NaN fails both comparisons
+    return occ > 0.5f || (unknown_is_filled && occ == 0.5f);
+}
+
+template <bool SEGMENTS>
+__global__ __launch_bounds__(kDshThreads) void k_dsh_cast(const DshGeometry g, const DshTable t, const DshPool p, const DshRayFrame f,
+                                                          const float* __restrict__ points, const double* __restrict__ starts,
+                                                          const double* __restrict__ ends, int64_t n, uint32_t flags,
+                                                          uint8_t* __restrict__ statuses, sdfgpu_dsh_cast_hit* __restrict__ hits) {
+    const int64_t i = dsh_item();
+    if (i >= n) return;
+    const bool skip_first = (flags & SDFGPU_DSH_CAST_SKIP_FIRST) != 0, skip_last = (flags & SDFGPU_DSH_CAST_SKIP_LAST) != 0;
+    const bool unknown_is_filled = (flags & SDFGPU_DSH_CAST_UNKNOWN_IS_FILLED) != 0;
+    DshRayWalk w;
+    uint32_t status;
+    if (SEGMENTS) {
+        DshRayStart s;
+        status = dsh_ray_start(g, starts[3 * i], starts[3 * i + 1], starts[3 * i + 2], s)
+                     ? dsh_ray_begin(g, s, f.range2, ends[3 * i], ends[3 * i + 1], ends[3 * i + 2], w) : (uint32_t)SDFGPU_DSH_RAY_SKIPPED;
+    } else {
+        status = dsh_ray_begin(g, f, (double)points[3 * i], (double)points[3 * i + 1], (double)points[3 * i + 2], w);
+    }
+    sdfgpu_dsh_cast_hit hit{};
+    uint32_t out = SDFGPU_DSH_CAST_SKIPPED;
+    if (status != SDFGPU_DSH_RAY_SKIPPED) {
+        out = w.is_long ? SDFGPU_DSH_CAST_CLEAR_IN_RANGE : SDFGPU_DSH_CAST_CLEAR;
+        const uint64_t* cells = nullptr;                                       // the current chunk's cells while it is cell-filled
+        uint64_t record = g.default_record;                                    // the current cell's record where it was read or is uniform
+        uint32_t found = SDFGPU_DSH_NOT_FOUND, k = 0;
+        double tk = 0.0;
+        bool chunk_changed = true, uniform_blocks = false, have_record = false;
+        for (uint64_t step = 0; step <= f.max_steps; ++step) {
+            const bool last = (w.rem[0] | w.rem[1] | w.rem[2]) == 0;
+            if (chunk_changed) {
+                const uint32_t pos = dsh_find(t, dsh_pack_key(w.c[0], w.c[1], w.c[2]));
+                cells = nullptr;
+                record = g.default_record;
+                found = SDFGPU_DSH_NOT_FOUND;
+                if (pos != kDshNoPos) {
+                    const uint64_t slot = t.slots[pos];
+                    found = p.heads[slot].state & kDshStateMask;
+                    if (found == kDshCellFilled) cells = p.cells + slot * (uint64_t)g.cells_per_chunk;
+                    else record = p.heads[slot].record;
+                }
+                uniform_blocks = !cells && dsh_cast_blocks(record, unknown_is_filled);
+            }
+            have_record = !cells;
+            if (!(skip_first && step == 0) && !(skip_last && last)) {
+                bool blocks = uniform_blocks;
+                if (cells) {
+                    record = cells[dsh_ray_cell(g, w)];
+                    have_record = true;
+                    blocks = dsh_cast_blocks(record, unknown_is_filled);
+                }
+                if (blocks) { out = SDFGPU_DSH_CAST_BLOCKED; break; }
+            }
+            if (last) break;
+            if (w.is_long) {                                                   // the next cell's entry parameter: what dsh_ray_step is about to return
+                double tn = w.t[0];
+                if (w.t[1] < tn) tn = w.t[1];
+                if (w.t[2] < tn) tn = w.t[2];
+                if (!((tn * tn) * w.len2 <= f.range2)) break;                  // it is out of range: this cell is the last of W
+            }
+            tk = dsh_ray_step(g, w, chunk_changed);
+            ++k;
+        }
+        if (hits) {
+            if (!have_record) record = cells[dsh_ray_cell(g, w)];             // (an untested cell of a cell-filled chunk)
+#pragma unroll
+            for (int a = 0; a < 3; ++a) hit.cell[a] = w.c[a] * g.n[a] + (int64_t)w.l[a];
+            hit.record = record;
+            hit.t = tk;
+            hit.step = k;
+            hit.found = found;
+        }
+    }
+    if (statuses) statuses[i] = (uint8_t)out;
+    if (hits) hits[i] = hit;
 }
 
 // ---- removal (include/sdfgpu.h "Removal") --------------------------------------------------------------------------------
@@ -1108,6 +1223,59 @@ int dsh_get_impl(sdfgpu_dsh_map_object* m, const double* d_loc, int64_t n, void*
     return SDFGPU_OK;
 }
 
+// What a cast is refused for before anything is enqueued; the range of a cast in what the kernel is told (and, with a sensor, the
+// sensor as dsh_ray_frame works it out).
+int dsh_cast_frame(sdfgpu_dsh_map_object* m, const double* sensor, bool segments, int64_t n, double max_range, uint32_t flags, const void* statuses,
+                   const void* hits, DshRayFrame& f) {
+    sdfgpu_handle h = m->h;
+    const uint64_t no_record = 0;
+    uint64_t range_cells = 0;
+    if (segments) {
+        const double range = max_range * m->g.inv_cell;                        // (every start is the lane's own: only the range is the frame's)
+        if (n < 0 || n >= kDshMaxBatch) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: a cast holds 0 .. 2^31 - 1 segments (got %lld)", (long long)n);
+        if (!(range > 0.0 && range <= kDshMaxRangeCells))
+            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: max_range must span more than 0 and at most 65536 cells (got %g, %g cells)", max_range, range);
+        f = DshRayFrame{};
+        f.range2 = range * range;
+        f.range_cells = (uint64_t)std::ceil(range);
+        f.max_steps = dsh_ray_max_steps(f.range_cells);
+    } else {
+        if (!sensor) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: cast_rays needs the sensor");
+        if (int rc = dsh_ray_frame(m, sensor, n, max_range, &no_record, &no_record, f, range_cells)) return rc;
+    }
+    if (flags & ~(uint32_t)(SDFGPU_DSH_CAST_SKIP_FIRST | SDFGPU_DSH_CAST_SKIP_LAST | SDFGPU_DSH_CAST_UNKNOWN_IS_FILLED))
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: a cast knows the flags SKIP_FIRST, SKIP_LAST and UNKNOWN_IS_FILLED (got 0x%x)", flags);
+    if (!statuses && !hits) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: a cast needs an output");
+    return SDFGPU_OK;
+}
+
+// One cast on `st` (checked by dsh_cast_frame): rays from the frame's sensor to d_points, or the segments d_starts -> d_ends.
+int dsh_cast_impl(sdfgpu_dsh_map_object* m, const DshRayFrame& f, bool segments, const float* d_points, const double* d_starts, const double* d_ends,
+                  int64_t n, uint32_t flags, uint8_t* d_statuses, sdfgpu_dsh_cast_hit* d_hits, hipStream_t st) {
+    sdfgpu_handle h = m->h;
+    if (n == 0) return SDFGPU_OK;
+    if (segments ? !d_starts || !d_ends : !d_points) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: a cast needs its %s", segments ? "starts and ends" : "points");
+    if (segments) {
+        if (int rc = dsh_aligned8(h, d_starts, "the starts")) return rc;
+        if (int rc = dsh_aligned8(h, d_ends, "the ends")) return rc;
+    } else if (reinterpret_cast<uintptr_t>(d_points) & 3) {
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: the points must be 4-byte aligned");
+    }
+    if (int rc = dsh_aligned8(h, d_hits, "the hits")) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, m->order.create());
+    HIP_TRY(h, m->order.wait(st));
+    StreamOrder::RecordAtExit record_at_exit{m->order, st};
+    if (segments)
+        hipLaunchKernelGGL((k_dsh_cast<true>), dsh_grid(n), dim3(kDshThreads), 0, st, m->g, m->table, m->pool, f, d_points, d_starts, d_ends, n, flags,
+                           d_statuses, d_hits);
+    else
+        hipLaunchKernelGGL((k_dsh_cast<false>), dsh_grid(n), dim3(kDshThreads), 0, st, m->g, m->table, m->pool, f, d_points, d_starts, d_ends, n, flags,
+                           d_statuses, d_hits);
+    HIP_TRY(h, hipGetLastError());
+    return SDFGPU_OK;
+}
+
 int dsh_check_window(sdfgpu_handle h, const int64_t* lower, int64_t nx, int64_t ny, int64_t nz, const void* records, const void* bits) {
     if (!lower) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: null lower corner");
     if (!records && !bits) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: a window needs an output");
@@ -1360,6 +1528,32 @@ int dsh_rays_host(sdfgpu_dsh_map m, const DshRayFrame& f, uint64_t range_cells, 
     return SDFGPU_OK;
 }
 
+// The host form of a cast: the points (12 bytes a ray), or the starts and the ends (24 each), are staged; statuses and hits copied back.
+int dsh_cast_host(sdfgpu_dsh_map m, const DshRayFrame& f, bool segments, const void* first, const void* second, int64_t n, uint32_t flags, uint8_t* statuses,
+                  sdfgpu_dsh_cast_hit* hits) {
+    sdfgpu_handle h = m->h;
+    if (n == 0) return SDFGPU_OK;
+    if (!first || (segments && !second)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: a cast needs its %s", segments ? "starts and ends" : "points");
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, m->order.wait(nullptr));
+    DshStage s;
+    const size_t un = (size_t)n, each = segments ? un * 24 : un * 12;
+    const size_t at_first = s.add(each), at_second = s.add(segments ? each : 0), at_st = s.add(statuses ? un : 0),
+                 at_hits = s.add(hits ? un * sizeof(sdfgpu_dsh_cast_hit) : 0);
+    if (int rc = ensure(h, m->stage, s.total, "dsh staging")) return rc;
+    char* const base = static_cast<char*>(m->stage.ptr);
+    if (int rc = copy_from_host(h, base + at_first, first, each)) return rc;
+    if (segments) if (int rc = copy_from_host(h, base + at_second, second, each)) return rc;
+    if (int rc = dsh_cast_impl(m, f, segments, segments ? nullptr : reinterpret_cast<const float*>(base + at_first),
+                               segments ? reinterpret_cast<const double*>(base + at_first) : nullptr,
+                               segments ? reinterpret_cast<const double*>(base + at_second) : nullptr, n, flags,
+                               statuses ? reinterpret_cast<uint8_t*>(base + at_st) : nullptr,
+                               hits ? reinterpret_cast<sdfgpu_dsh_cast_hit*>(base + at_hits) : nullptr, nullptr)) return rc;
+    if (statuses) if (int rc = copy_to_host(h, statuses, base + at_st, un)) return rc;
+    if (hits) return copy_to_host(h, hits, base + at_hits, un * sizeof(sdfgpu_dsh_cast_hit));
+    return SDFGPU_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1571,6 +1765,42 @@ int sdfgpu_dsh_get(sdfgpu_dsh_map map, const double* locations, int64_t n, void*
         if (records) if (int rc = copy_to_host(h, records, base + at_rec, un * 8)) return rc;
         if (statuses) return copy_to_host(h, statuses, base + at_st, un);
         return SDFGPU_OK;
+    });
+}
+
+int sdfgpu_dsh_cast_rays_device(sdfgpu_dsh_map map, const double sensor[3], const float* d_points, int64_t n, double max_range, uint32_t flags,
+                                uint8_t* d_statuses, sdfgpu_dsh_cast_hit* d_hits, void* stream) {
+    return dsh_entry(map, stream, [&]() -> int {
+        DshRayFrame f{};
+        if (int rc = dsh_cast_frame(map, sensor, false, n, max_range, flags, d_statuses, d_hits, f)) return rc;
+        return dsh_cast_impl(map, f, false, d_points, nullptr, nullptr, n, flags, d_statuses, d_hits, (hipStream_t)stream);
+    });
+}
+
+int sdfgpu_dsh_cast_segments_device(sdfgpu_dsh_map map, const double* d_starts, const double* d_ends, int64_t n, double max_range, uint32_t flags,
+                                    uint8_t* d_statuses, sdfgpu_dsh_cast_hit* d_hits, void* stream) {
+    return dsh_entry(map, stream, [&]() -> int {
+        DshRayFrame f{};
+        if (int rc = dsh_cast_frame(map, nullptr, true, n, max_range, flags, d_statuses, d_hits, f)) return rc;
+        return dsh_cast_impl(map, f, true, nullptr, d_starts, d_ends, n, flags, d_statuses, d_hits, (hipStream_t)stream);
+    });
+}
+
+int sdfgpu_dsh_cast_rays(sdfgpu_dsh_map map, const double sensor[3], const float* points, int64_t n, double max_range, uint32_t flags, uint8_t* statuses,
+                         sdfgpu_dsh_cast_hit* hits) {
+    return dsh_entry(map, nullptr, [&]() -> int {
+        DshRayFrame f{};
+        if (int rc = dsh_cast_frame(map, sensor, false, n, max_range, flags, statuses, hits, f)) return rc;
+        return dsh_cast_host(map, f, false, points, nullptr, n, flags, statuses, hits);
+    });
+}
+
+int sdfgpu_dsh_cast_segments(sdfgpu_dsh_map map, const double* starts, const double* ends, int64_t n, double max_range, uint32_t flags, uint8_t* statuses,
+                             sdfgpu_dsh_cast_hit* hits) {
+    return dsh_entry(map, nullptr, [&]() -> int {
+        DshRayFrame f{};
+        if (int rc = dsh_cast_frame(map, nullptr, true, n, max_range, flags, statuses, hits, f)) return rc;
+        return dsh_cast_host(map, f, true, starts, ends, n, flags, statuses, hits);
     });
 }
 
