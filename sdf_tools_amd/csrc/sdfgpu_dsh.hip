@@ -19,7 +19,9 @@
 //
 // Arithmetic: a location on a cell boundary is placed by the rounding of g = inverse_origin * p alone, and tests/dsh_restated.py states
 // that product in numpy (separate products and sums), so nothing here may be contracted into an FMA (hipcc contracts by default).  The
-// host code below falls under the pragma too; it is compiled for baseline x86-64, which has no FMA to contract into.
+// product, its floor and range check, and the split into chunk and cell are written once (dsh_axis_cell, dsh_split_cell,
+// dsh_cell_index) for the lanes and for the host, which works a frame's sensor out with them: the host code below falls under the
+// pragma too; it is compiled for baseline x86-64, which has no FMA to contract into.
 #pragma clang fp contract(off)
 #include "sdfgpu_context.hpp"
 #include "sdfgpu_dsh.hpp"
@@ -38,23 +40,47 @@ dim3 dsh_grid(int64_t items) {
 }
 __device__ __forceinline__ int64_t dsh_item() { return ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * kDshThreads + threadIdx.x; }
 
+// ---- the cell arithmetic, stated once for the device and the host ---------------------------------------------------------------------
+// One axis of one point (x, y, z): `row` of the inverse origin transform gives the grid coordinate in cells `coord` (products and sums
+// in exactly this order, then the scale), its floor the global cell; false where that is no cell of a chunk in [-2^20, 2^20).
+__host__ __device__ __forceinline__ bool dsh_axis_cell(const double* row, double inv_cell, int64_t n_a, double x, double y, double z, double& coord,
+                                                       int64_t& cell) {
+    const double ga = ((row[0] * x + row[1] * y) + row[2] * z) + row[3];
+    coord = ga * inv_cell;
+    const double v = floor(coord);
+    const double lim = (double)(kDshChunkBias * n_a);                          // exact: at most 2^35
+    if (!(v >= -lim && v < lim)) return false;                                 // (NaN and the infinities fail: no cast of such a double)
+    cell = (int64_t)v;
+    return true;
+}
+// a global cell along one axis -> its chunk and the cell inside the chunk
+__host__ __device__ __forceinline__ void dsh_split_cell(int64_t i, int64_t n_a, int64_t& chunk, int64_t& local) {
+    chunk = dsh_floor_div(i, n_a);
+    local = i - chunk * n_a;
+}
+// the cell slot of (l_x, l_y, l_z) in a chunk of n cells
+__host__ __device__ __forceinline__ uint32_t dsh_cell_index(const int64_t l[3], const int64_t n[3]) { return (uint32_t)((l[0] * n[1] + l[1]) * n[2] + l[2]); }
+
 // location -> (key, cell slot); false for an invalid location
 __device__ __forceinline__ bool dsh_locate(const DshGeometry& g, double px, double py, double pz, uint64_t& key, uint32_t& cell) {
     if (!(isfinite(px) && isfinite(py) && isfinite(pz))) return false;
     int64_t c[3], l[3];
     for (int a = 0; a < 3; ++a) {
-        const double* m = g.inverse + 4 * a;
-        const double ga = ((m[0] * px + m[1] * py) + m[2] * pz) + m[3];
-        const double v = floor(ga * g.inv_cell);
-        const double lim = (double)(kDshChunkBias * g.n[a]);               // exact: at most 2^35
-        if (!(v >= -lim && v < lim)) return false;                           // (NaN and the infinities fail: no cast of such a double)
-        const int64_t i = (int64_t)v;
-        c[a] = dsh_floor_div(i, g.n[a]);
-        l[a] = i - c[a] * g.n[a];
+        double coord;
+        int64_t i;
+        if (!dsh_axis_cell(g.inverse + 4 * a, g.inv_cell, g.n[a], px, py, pz, coord, i)) return false;
+        dsh_split_cell(i, g.n[a], c[a], l[a]);
     }
     key = dsh_pack_key(c[0], c[1], c[2]);
-    cell = (uint32_t)((l[0] * g.n[1] + l[1]) * g.n[2] + l[2]);
+    cell = dsh_cell_index(l, g.n);
     return true;
+}
+
+// whether a cell with this record stops a ray and counts as filled in a window (COLLISION_CELL: occupancy in the low word; a NaN
+// fails both comparisons)
+__device__ __forceinline__ bool dsh_record_blocks(uint64_t record, bool unknown_is_filled) {
+    const float occ = __uint_as_float((uint32_t)record);
+    return occ > 0.5f || (unknown_is_filled && occ == 0.5f);
 }
 
 // the position of `key` in a table no launch is inserting into, or kDshNoPos
@@ -259,15 +285,13 @@ __global__ __launch_bounds__(kDshThreads) void k_dsh_window(const DshGeometry g,
         int64_t c[3], l[3];
         bool valid = true;
         for (int a = 0; a < 3; ++a) {
-            c[a] = dsh_floor_div(i[a], g.n[a]);
-            l[a] = i[a] - c[a] * g.n[a];
+            dsh_split_cell(i[a], g.n[a], c[a], l[a]);
             valid = valid && dsh_chunk_in_range(c[a]);
         }
         uint64_t record = g.default_record;
-        if (valid) (void)dsh_read(t, p, (uint64_t)g.cells_per_chunk, dsh_pack_key(c[0], c[1], c[2]), (uint32_t)((l[0] * g.n[1] + l[1]) * g.n[2] + l[2]), record);
+        if (valid) (void)dsh_read(t, p, (uint64_t)g.cells_per_chunk, dsh_pack_key(c[0], c[1], c[2]), dsh_cell_index(l, g.n), record);
         if (w.records) w.records[v] = record;
-        const float occ = __uint_as_float((uint32_t)record);                  // COLLISION_CELL: occupancy in the low word
-        filled = occ > 0.5f || (w.unknown_is_filled && occ == 0.5f);
+        filled = dsh_record_blocks(record, w.unknown_is_filled != 0);
     }
     if (w.bits) {                                                             // (uniform)
         const unsigned long long b = __ballot(filled);
@@ -361,13 +385,10 @@ __device__ __forceinline__ uint32_t dsh_ray_begin(const DshGeometry& g, const St
     if (!(isfinite(px) && isfinite(py) && isfinite(pz))) return SDFGPU_DSH_RAY_SKIPPED;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        const double* m = g.inverse + 4 * a;
-        const double ga = ((m[0] * px + m[1] * py) + m[2] * pz) + m[3];
-        const double ge = ga * g.inv_cell;
-        const double v = floor(ge);
-        const double lim = (double)(kDshChunkBias * g.n[a]);
-        if (!(v >= -lim && v < lim)) return SDFGPU_DSH_RAY_SKIPPED;
-        const int64_t diff = (int64_t)v - f.i0[a];
+        double ge;
+        int64_t i1;
+        if (!dsh_axis_cell(g.inverse + 4 * a, g.inv_cell, g.n[a], px, py, pz, ge, i1)) return SDFGPU_DSH_RAY_SKIPPED;
+        const int64_t diff = i1 - f.i0[a];
         w.sg[a] = diff > 0 ? 1 : diff < 0 ? -1 : 0;
         w.rem[a] = diff < 0 ? -diff : diff;
         w.gs[a] = f.gs[a];
@@ -385,22 +406,19 @@ __device__ __forceinline__ uint32_t dsh_ray_begin(const DshGeometry& g, const Ds
     return dsh_ray_begin(g, f, f.range2, px, py, pz, w);
 }
 
-// a segment's start in the lane: dsh_ray_frame's arithmetic (this file is compiled without contraction); false for an invalid one
-__device__ __forceinline__ bool dsh_ray_start(const DshGeometry& g, double sx, double sy, double sz, DshRayStart& s) {
-    if (!(isfinite(sx) && isfinite(sy) && isfinite(sz))) return false;
+// Where a ray starts, worked out from a finite point: by the host for a frame's sensor (dsh_ray_frame), in the lane for a segment
+// (dsh_ray_start).  False where the point is no valid location.
+template <class Start>
+__host__ __device__ __forceinline__ bool dsh_start_cell(const DshGeometry& g, double sx, double sy, double sz, Start& s) {
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        const double* m = g.inverse + 4 * a;
-        const double ga = ((m[0] * sx + m[1] * sy) + m[2] * sz) + m[3];
-        s.gs[a] = ga * g.inv_cell;
-        const double v = floor(s.gs[a]);
-        const double lim = (double)(kDshChunkBias * g.n[a]);
-        if (!(v >= -lim && v < lim)) return false;
-        s.i0[a] = (int64_t)v;
-        s.c0[a] = dsh_floor_div(s.i0[a], g.n[a]);
-        s.l0[a] = s.i0[a] - s.c0[a] * g.n[a];
+        if (!dsh_axis_cell(g.inverse + 4 * a, g.inv_cell, g.n[a], sx, sy, sz, s.gs[a], s.i0[a])) return false;
+        dsh_split_cell(s.i0[a], g.n[a], s.c0[a], s.l0[a]);
     }
     return true;
+}
+__device__ __forceinline__ bool dsh_ray_start(const DshGeometry& g, double sx, double sy, double sz, DshRayStart& s) {
+    return isfinite(sx) && isfinite(sy) && isfinite(sz) && dsh_start_cell(g, sx, sy, sz, s);
 }
 
 // One step: along the axis with the smallest crossing parameter, x before y before z.  Returns that parameter, the entry parameter
@@ -609,11 +627,6 @@ __global__ __launch_bounds__(kDshThreads) void k_dsh_ray_fuse(const DshPool p, u
 // One lane per ray, read-only: the walk of a frame (dsh_ray_begin, dsh_ray_step), stopped at the first tested cell whose record
 // satisfies the window predicate.  A chunk is looked up once, when the walk enters it; an absent or chunk-filled one is decided there
 // and then stepped through without a memory access, a cell-filled one costs one 8-byte load per tested cell.  No atomics, no LDS.
-__device__ __forceinline__ bool dsh_cast_blocks(uint64_t record, bool unknown_is_filled) {
-    const float occ = __uint_as_float((uint32_t)record);                      // k_dsh_window's predicate: a NaN fails both comparisons
-    return occ > 0.5f || (unknown_is_filled && occ == 0.5f);
-}
-
 template <bool SEGMENTS>
 __global__ __launch_bounds__(kDshThreads) void k_dsh_cast(const DshGeometry g, const DshTable t, const DshPool p, const DshRayFrame f,
                                                           const float* __restrict__ points, const double* __restrict__ starts,
@@ -654,7 +667,7 @@ __global__ __launch_bounds__(kDshThreads) void k_dsh_cast(const DshGeometry g, c
                     if (found == kDshCellFilled) cells = p.cells + slot * (uint64_t)g.cells_per_chunk;
                     else record = p.heads[slot].record;
                 }
-                uniform_blocks = !cells && dsh_cast_blocks(record, unknown_is_filled);
+                uniform_blocks = !cells && dsh_record_blocks(record, unknown_is_filled);
             }
             have_record = !cells;
             if (!(skip_first && step == 0) && !(skip_last && last)) {
@@ -662,7 +675,7 @@ __global__ __launch_bounds__(kDshThreads) void k_dsh_cast(const DshGeometry g, c
                 if (cells) {
                     record = cells[dsh_ray_cell(g, w)];
                     have_record = true;
-                    blocks = dsh_cast_blocks(record, unknown_is_filled);
+                    blocks = dsh_record_blocks(record, unknown_is_filled);
                 }
                 if (blocks) { out = SDFGPU_DSH_CAST_BLOCKED; break; }
             }
@@ -894,6 +907,71 @@ int dsh_alloc_pool(sdfgpu_handle h, uint64_t chunks, uint64_t cells_per_chunk, D
 
 uint32_t* dsh_counters(sdfgpu_dsh_map_object* m) { return static_cast<uint32_t*>(m->scratch.ptr); }
 
+// What every call does before it touches the map: the context's device, the map's event, and `st` behind the call before this one
+// wherever that ran.
+int dsh_wait(sdfgpu_dsh_map_object* m, hipStream_t st) {
+    sdfgpu_handle h = m->h;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, m->order.create());
+    HIP_TRY(h, m->order.wait(st));
+    return SDFGPU_OK;
+}
+
+// The scope of one device body on `st`: open() is dsh_wait, and the map's event is recorded on `st` on every path out of the scope
+// that open() did not refuse (a refused call has enqueued nothing).
+struct DshCall {
+    sdfgpu_dsh_map_object* m;
+    hipStream_t st;
+    bool armed = false;
+    int open() { const int rc = dsh_wait(m, st); armed = rc == SDFGPU_OK; return rc; }
+    ~DshCall() { if (armed) (void)m->order.record(st); }
+};
+
+// A buffer cut into 256-byte aligned sections: a running total, and each section as a typed pointer (null for an absent optional
+// one, which takes no room).  dsh_cut runs a layout twice, to size the buffer and then, in the buffer, to hand the sections out.
+struct DshCut {
+    char* base;             // null while the layout is only measured
+    size_t total;
+    template <class T>
+    T* take(size_t bytes, bool present = true) {
+        if (!present) return nullptr;
+        T* const at = base ? reinterpret_cast<T*>(base + total) : nullptr;
+        total += align256(bytes);
+        return at;
+    }
+};
+
+template <class Layout>
+int dsh_cut(sdfgpu_handle h, DeviceBuffer& b, const char* name, size_t first, Layout&& layout) {
+    DshCut cut{nullptr, first};
+    layout(cut);
+    if (int rc = ensure(h, b, cut.total, name)) return rc;
+    cut = DshCut{static_cast<char*>(b.ptr), first};
+    layout(cut);
+    return SDFGPU_OK;
+}
+
+// the per-call scratch: the counters are its first kDshCounterBytes, the call's sections follow
+template <class Layout>
+int dsh_scratch(sdfgpu_dsh_map_object* m, Layout&& layout) { return dsh_cut(m->h, m->scratch, "dsh batch scratch", kDshCounterBytes, layout); }
+
+// every live chunk's key into `table` (empty, or holding none of them) and the count of keys that found no entry on its way to
+// `lost`: enqueued, not waited for.  The counters are the caller's to clear.
+int dsh_rehash_into(sdfgpu_dsh_map_object* m, const DshTable& table, uint64_t n_live, hipStream_t st, uint32_t* lost) {
+    hipLaunchKernelGGL(k_dsh_rehash, dsh_grid((int64_t)n_live), dim3(kDshThreads), 0, st, table, m->pool.heads, (uint32_t)n_live, dsh_counters(m));
+    HIP_TRY(m->h, hipGetLastError());
+    HIP_TRY(m->h, hipMemcpyAsync(lost, dsh_counters(m) + 1, 4, hipMemcpyDeviceToHost, st));
+    return SDFGPU_OK;
+}
+
+// the heads and the cells of the chunks in use into another pool: enqueued, not waited for
+int dsh_copy_pool(sdfgpu_dsh_map_object* m, const DshPool& dst, hipStream_t st) {
+    if (!m->n_live) return SDFGPU_OK;
+    HIP_TRY(m->h, hipMemcpyAsync(dst.heads, m->pool.heads, (size_t)(m->n_live * sizeof(DshChunkHead)), hipMemcpyDeviceToDevice, st));
+    HIP_TRY(m->h, hipMemcpyAsync(dst.cells, m->pool.cells, (size_t)(m->n_live * (uint64_t)m->g.cells_per_chunk * 8), hipMemcpyDeviceToDevice, st));
+    return SDFGPU_OK;
+}
+
 // the table for `chunks` keys: grown (new table, rehash kernel) when it is too small.  Refused before anything changes when the
 // larger table would pass the byte limit.  With `kept`, a table that was replaced is handed to the caller instead of being freed
 // (kept->keys stays null when the table did not grow): a call that may still be refused puts it back, and nothing has changed.
@@ -910,9 +988,7 @@ int dsh_reserve_table(sdfgpu_dsh_map_object* m, uint64_t chunks, hipStream_t st,
     uint32_t lost = 0;
     if (m->n_live) {
         HIP_TRY(h, hipMemsetAsync(dsh_counters(m), 0, kDshCounterBytes, st));
-        hipLaunchKernelGGL(k_dsh_rehash, dsh_grid((int64_t)m->n_live), dim3(kDshThreads), 0, st, grown, m->pool.heads, (uint32_t)m->n_live, dsh_counters(m));
-        HIP_TRY(h, hipGetLastError());
-        HIP_TRY(h, hipMemcpyAsync(&lost, dsh_counters(m) + 1, 4, hipMemcpyDeviceToHost, st));
+        if (int rc = dsh_rehash_into(m, grown, m->n_live, st, &lost)) return rc;
     }
     HIP_TRY(h, hipStreamSynchronize(st));                                       // (the old table may still be read by pending work)
     if (lost) { (void)rz_free(h, grown.keys); return fail(h, SDFGPU_ERR_HIP, "dsh: the rehash lost %u keys (internal error)", lost); }
@@ -939,10 +1015,7 @@ int dsh_reserve_pool(sdfgpu_dsh_map_object* m, uint64_t needed, hipStream_t st) 
         want = needed;
         if (int rc2 = dsh_alloc_pool(h, want, cpc, grown)) return rc2;
     }
-    if (m->n_live) {
-        HIP_TRY(h, hipMemcpyAsync(grown.heads, m->pool.heads, (size_t)(m->n_live * sizeof(DshChunkHead)), hipMemcpyDeviceToDevice, st));
-        HIP_TRY(h, hipMemcpyAsync(grown.cells, m->pool.cells, (size_t)(m->n_live * cpc * 8), hipMemcpyDeviceToDevice, st));
-    }
+    if (int rc = dsh_copy_pool(m, grown, st)) return rc;
     HIP_TRY(h, hipStreamSynchronize(st));
     (void)rz_free(h, m->pool.heads);
     (void)rz_free(h, m->pool.cells);
@@ -978,11 +1051,55 @@ int dsh_reserve_marks(sdfgpu_dsh_map_object* m, uint64_t needed, hipStream_t st)
     return SDFGPU_OK;
 }
 
+// What follows an inserting kernel, its read-back and their synchronisation: the `n_new` chunks of `newlist` are committed or refused.
+// `rc` says what the caller made of the read-back (lost operations, a HIP error).  The mark plane (fused frames only) is reserved in
+// front of the pool.  Refused, the table is the one the call found: a frame hands over the table it replaced (`kept`; kept->keys is
+// null where it did not grow) and gets it back, where none was handed over the new entries become empty again -- so a refused
+// batch, which hands nothing over, keeps a table it grew.  A frame's work is waited for before its table goes (its HIP calls may
+// have failed half way), a batch's rollback is waited for.
+int dsh_commit_new(sdfgpu_dsh_map_object* m, int rc, uint32_t n_new, const uint32_t* newlist, bool marks, DshTable* kept, uint64_t kept_cap, hipStream_t st) {
+    sdfgpu_handle h = m->h;
+    const dim3 block(kDshThreads);
+    if (rc == SDFGPU_OK && marks) rc = dsh_reserve_marks(m, m->n_live + n_new, st);
+    if (rc == SDFGPU_OK) rc = dsh_reserve_pool(m, m->n_live + n_new, st);
+    if (rc != SDFGPU_OK) {
+        if (kept) (void)hipStreamSynchronize(st);
+        if (kept && kept->keys) {
+            (void)rz_free(h, m->table.keys);
+            m->table = *kept;
+            m->table_cap = kept_cap;
+            return rc;
+        }
+        if (n_new) hipLaunchKernelGGL(k_dsh_rollback, dsh_grid(n_new), block, 0, st, m->table, newlist, n_new);
+        if (n_new || !kept) (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    if (kept && kept->keys) (void)rz_free(h, kept->keys);
+    if (n_new) hipLaunchKernelGGL(k_dsh_init_new, dsh_grid(n_new), block, 0, st, m->table, m->pool.heads, newlist, n_new, (uint32_t)m->n_live);
+    m->n_live += n_new;
+    return SDFGPU_OK;
+}
+
 int dsh_check_map(sdfgpu_dsh_map m) { return m && m->h ? SDFGPU_OK : SDFGPU_ERR_INVALID_ARGUMENT; }
 
 int dsh_aligned8(sdfgpu_handle h, const void* p, const char* what) {
     if (reinterpret_cast<uintptr_t>(p) & 7) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: %s must be 8-byte aligned", what);
     return SDFGPU_OK;
+}
+
+// the writes of a batch into the cells (or, CHUNK, the chunk records) its operations name: one record for all of them, or the order rule
+template <bool CHUNK>
+void dsh_write(sdfgpu_dsh_map_object* m, const uint32_t* op_pos, const uint32_t* op_cell, int64_t n, uint8_t* wins, const void* d_values,
+               const void* one_value, hipStream_t st) {
+    const dim3 grid = dsh_grid(n), block(kDshThreads);
+    const uint64_t cpc = (uint64_t)m->g.cells_per_chunk;
+    uint64_t value = 0;
+    if (one_value) memcpy(&value, one_value, 8);
+    hipLaunchKernelGGL((k_dsh_store_one<CHUNK>), grid, block, 0, st, m->table, m->pool, cpc, op_pos, op_cell, n, value);
+    if (one_value) return;
+    hipLaunchKernelGGL((k_dsh_stamp<CHUNK>), grid, block, 0, st, m->table, m->pool, cpc, op_pos, op_cell, n);
+    hipLaunchKernelGGL((k_dsh_decide<CHUNK>), grid, block, 0, st, m->table, m->pool, cpc, op_pos, op_cell, n, wins);
+    hipLaunchKernelGGL((k_dsh_apply<CHUNK>), grid, block, 0, st, m->table, m->pool, cpc, op_pos, op_cell, n, wins, static_cast<const uint64_t*>(d_values));
 }
 
 // One batch on `st`: cell sets (locations as doubles, or points as floats) or chunk sets.
@@ -997,25 +1114,20 @@ int dsh_batch(sdfgpu_dsh_map_object* m, bool chunk_sets, const LOC* d_loc, int64
     if (!d_loc) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: null locations");
     if (int rc = dsh_aligned8(h, d_values, "the values")) return rc;
     if (reinterpret_cast<uintptr_t>(d_loc) & (sizeof(LOC) - 1)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: the locations are not aligned for their type");
-    HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, m->order.create());
-    HIP_TRY(h, m->order.wait(st));
-    StreamOrder::RecordAtExit record_at_exit{m->order, st};
+    DshCall call{m, st};
+    if (int rc = call.open()) return rc;
 
     const size_t un = (size_t)n;
-    const size_t off_pos = kDshCounterBytes, off_cell = off_pos + align256(un * 4), off_new = off_cell + align256(un * 4), off_win = off_new + align256(un * 4);
-    if (int rc = ensure(h, m->scratch, off_win + align256(un), "dsh batch scratch")) return rc;
-    char* const base = static_cast<char*>(m->scratch.ptr);
+    uint32_t *op_pos = nullptr, *op_cell = nullptr, *newlist = nullptr;
+    uint8_t* wins = nullptr;
+    if (int rc = dsh_scratch(m, [&](DshCut& c) {
+            op_pos = c.take<uint32_t>(un * 4); op_cell = c.take<uint32_t>(un * 4); newlist = c.take<uint32_t>(un * 4); wins = c.take<uint8_t>(un);
+        })) return rc;
     uint32_t* const counters = dsh_counters(m);
-    uint32_t* const op_pos = reinterpret_cast<uint32_t*>(base + off_pos);
-    uint32_t* const op_cell = reinterpret_cast<uint32_t*>(base + off_cell);
-    uint32_t* const newlist = reinterpret_cast<uint32_t*>(base + off_new);
-    uint8_t* const wins = reinterpret_cast<uint8_t*>(base + off_win);
 
     // the table cannot fill while the batch inserts: the number of operations bounds the number of new chunks
     if (int rc = dsh_reserve_table(m, m->n_live + (uint64_t)n, st)) return rc;
     const dim3 grid = dsh_grid(n), block(kDshThreads);
-    const uint64_t cpc = (uint64_t)m->g.cells_per_chunk;
     HIP_TRY(h, hipMemsetAsync(counters, 0, kDshCounterBytes, st));
     hipLaunchKernelGGL((k_dsh_insert<LOC>), grid, block, 0, st, m->g, m->table, d_loc, n, (uint32_t)m->n_live, op_pos, op_cell, newlist, counters, d_statuses,
                        (uint8_t)(chunk_sets ? SDFGPU_DSH_SET_CHUNK : SDFGPU_DSH_SET_CELL));
@@ -1023,71 +1135,50 @@ int dsh_batch(sdfgpu_dsh_map_object* m, bool chunk_sets, const LOC* d_loc, int64
     uint32_t back[2] = {0, 0};                                                  // new chunks, lost operations
     HIP_TRY(h, hipMemcpyAsync(back, counters, sizeof back, hipMemcpyDeviceToHost, st));
     HIP_TRY(h, hipStreamSynchronize(st));
-    const uint32_t n_new = back[0];
-    int rc = back[1] ? fail(h, SDFGPU_ERR_HIP, "dsh: %u operations found no table entry (internal error)", back[1]) : SDFGPU_OK;
-    if (rc == SDFGPU_OK) rc = dsh_reserve_pool(m, m->n_live + n_new, st);
-    if (rc != SDFGPU_OK) {                                                      // refused: the table forgets the batch's keys
-        if (n_new) hipLaunchKernelGGL(k_dsh_rollback, dsh_grid(n_new), block, 0, st, m->table, newlist, n_new);
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
-    if (n_new) hipLaunchKernelGGL(k_dsh_init_new, dsh_grid(n_new), block, 0, st, m->table, m->pool.heads, newlist, n_new, (uint32_t)m->n_live);
-    m->n_live += n_new;
-    uint64_t value = 0;
-    if (one_value) memcpy(&value, one_value, 8);
-    const uint64_t* const values = static_cast<const uint64_t*>(d_values);
+    const int lost = back[1] ? fail(h, SDFGPU_ERR_HIP, "dsh: %u operations found no table entry (internal error)", back[1]) : SDFGPU_OK;
+    if (int rc = dsh_commit_new(m, lost, back[0], newlist, false, nullptr, 0, st)) return rc;
     if (!chunk_sets) {
         hipLaunchKernelGGL(k_dsh_touch, grid, block, 0, st, m->table, m->pool.heads, op_pos, n);
-        hipLaunchKernelGGL(k_dsh_expand, dsh_chunk_grid(m->n_live), block, 0, st, m->pool, m->n_live, cpc, m->g.default_record);
-        if (one_value) {
-            hipLaunchKernelGGL((k_dsh_store_one<false>), grid, block, 0, st, m->table, m->pool, cpc, op_pos, op_cell, n, value);
-        } else {
-            hipLaunchKernelGGL((k_dsh_store_one<false>), grid, block, 0, st, m->table, m->pool, cpc, op_pos, op_cell, n, (uint64_t)0);
-            hipLaunchKernelGGL((k_dsh_stamp<false>), grid, block, 0, st, m->table, m->pool, cpc, op_pos, op_cell, n);
-            hipLaunchKernelGGL((k_dsh_decide<false>), grid, block, 0, st, m->table, m->pool, cpc, op_pos, op_cell, n, wins);
-            hipLaunchKernelGGL((k_dsh_apply<false>), grid, block, 0, st, m->table, m->pool, cpc, op_pos, op_cell, n, wins, values);
-        }
-    } else if (one_value) {
-        hipLaunchKernelGGL((k_dsh_store_one<true>), grid, block, 0, st, m->table, m->pool, cpc, op_pos, op_cell, n, value);
+        hipLaunchKernelGGL(k_dsh_expand, dsh_chunk_grid(m->n_live), block, 0, st, m->pool, m->n_live, (uint64_t)m->g.cells_per_chunk, m->g.default_record);
+        dsh_write<false>(m, op_pos, op_cell, n, wins, d_values, one_value, st);
     } else {
-        hipLaunchKernelGGL((k_dsh_store_one<true>), grid, block, 0, st, m->table, m->pool, cpc, op_pos, op_cell, n, (uint64_t)0);
-        hipLaunchKernelGGL((k_dsh_stamp<true>), grid, block, 0, st, m->table, m->pool, cpc, op_pos, op_cell, n);
-        hipLaunchKernelGGL((k_dsh_decide<true>), grid, block, 0, st, m->table, m->pool, cpc, op_pos, op_cell, n, wins);
-        hipLaunchKernelGGL((k_dsh_apply<true>), grid, block, 0, st, m->table, m->pool, cpc, op_pos, op_cell, n, wins, values);
+        dsh_write<true>(m, op_pos, op_cell, n, wins, d_values, one_value, st);
     }
     HIP_TRY(h, hipGetLastError());
     return SDFGPU_OK;
 }
 
-// What a frame of rays is refused for before anything is enqueued, and what the host works out about the sensor (in the arithmetic
-// of dsh_locate: this file is compiled without contraction).
-int dsh_ray_frame(sdfgpu_dsh_map_object* m, const double* sensor, int64_t n, double max_range, const void* free_value, const void* hit_value,
-                  DshRayFrame& f, uint64_t& range_cells) {
+constexpr char kDshFrameNeeds[] = "dsh: insert_rays needs the sensor, the free record and the hit record";
+
+// the range of a frame or a cast, R = max_range in cells with 0 < R <= 65536, in what the kernels are told
+int dsh_ray_range(sdfgpu_dsh_map_object* m, double max_range, DshRayFrame& f) {
+    const double range = max_range * m->g.inv_cell;
+    if (!(range > 0.0 && range <= kDshMaxRangeCells))
+        return fail(m->h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: max_range must span more than 0 and at most 65536 cells (got %g, %g cells)", max_range, range);
+    f.range2 = range * range;
+    f.range_cells = (uint64_t)std::ceil(range);
+    f.max_steps = dsh_ray_max_steps(f.range_cells);
+    return SDFGPU_OK;
+}
+
+// What a frame of rays is refused for before anything is enqueued, and what the host works out about the sensor (dsh_start_cell: the
+// arithmetic of the lanes, compiled without contraction here too).
+int dsh_ray_frame(sdfgpu_dsh_map_object* m, const double* sensor, int64_t n, double max_range, DshRayFrame& f) {
     sdfgpu_handle h = m->h;
     if (n < 0 || n >= kDshMaxBatch) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: a frame holds 0 .. 2^31 - 1 rays (got %lld)", (long long)n);
-    if (!sensor || !free_value || !hit_value) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: insert_rays needs the sensor, the free record and the hit record");
-    const DshGeometry& g = m->g;
-    const double range = max_range * g.inv_cell;
-    if (!(range > 0.0 && range <= kDshMaxRangeCells))
-        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: max_range must span more than 0 and at most 65536 cells (got %g, %g cells)", max_range, range);
+    if (!sensor) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "%s", kDshFrameNeeds);
+    if (int rc = dsh_ray_range(m, max_range, f)) return rc;
     if (!(std::isfinite(sensor[0]) && std::isfinite(sensor[1]) && std::isfinite(sensor[2])))
         return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: the sensor position is not finite");
-    for (int a = 0; a < 3; ++a) {
-        const double* row = g.inverse + 4 * a;
-        const double ga = ((row[0] * sensor[0] + row[1] * sensor[1]) + row[2] * sensor[2]) + row[3];
-        f.gs[a] = ga * g.inv_cell;
-        const double v = std::floor(f.gs[a]);
-        const double lim = (double)(kDshChunkBias * g.n[a]);
-        if (!(v >= -lim && v < lim)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: the sensor position is not a valid location of the map");
-        f.i0[a] = (int64_t)v;
-        f.c0[a] = dsh_floor_div(f.i0[a], g.n[a]);
-        f.l0[a] = f.i0[a] - f.c0[a] * g.n[a];
-    }
-    f.range2 = range * range;
-    range_cells = (uint64_t)std::ceil(range);
-    f.range_cells = range_cells;
-    f.max_steps = dsh_ray_max_steps(range_cells);
+    if (!dsh_start_cell(m->g, sensor[0], sensor[1], sensor[2], f))
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: the sensor position is not a valid location of the map");
     return SDFGPU_OK;
+}
+
+// What the carve entry points, device and host form, check: the two records every ray stores, then the frame.
+int dsh_carve_frame(sdfgpu_dsh_map_object* m, const double* sensor, int64_t n, double max_range, const void* free_value, const void* hit_value, DshRayFrame& f) {
+    if (!free_value || !hit_value) return fail(m->h, SDFGPU_ERR_INVALID_ARGUMENT, "%s", kDshFrameNeeds);
+    return dsh_ray_frame(m, sensor, n, max_range, f);
 }
 
 // The sensor model of a fused frame, checked and turned into what k_dsh_ray_fuse is told.
@@ -1106,21 +1197,19 @@ int dsh_fuse_model(sdfgpu_handle h, const sdfgpu_dsh_sensor_model* model, DshFus
 }
 
 // One frame of rays on `st` (the frame was checked by dsh_ray_frame): carved with the two records, or (fuse) fused with the model.
-int dsh_rays_impl(sdfgpu_dsh_map_object* m, const DshRayFrame& f, uint64_t range_cells, const float* d_points, int64_t n, const void* free_value,
-                  const void* hit_value, const DshFuse* fuse, uint8_t* d_statuses, sdfgpu_dsh_ray_counts* out_counts, hipStream_t st) {
+int dsh_rays_impl(sdfgpu_dsh_map_object* m, const DshRayFrame& f, const float* d_points, int64_t n, const void* free_value, const void* hit_value,
+                  const DshFuse* fuse, uint8_t* d_statuses, sdfgpu_dsh_ray_counts* out_counts, hipStream_t st) {
     sdfgpu_handle h = m->h;
     if (out_counts) *out_counts = sdfgpu_dsh_ray_counts{};
     if (n == 0) return SDFGPU_OK;
     if (!d_points) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: null points");
     if (reinterpret_cast<uintptr_t>(d_points) & 3) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: the points are not aligned for their type");
-    HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, m->order.create());
-    HIP_TRY(h, m->order.wait(st));
-    StreamOrder::RecordAtExit record_at_exit{m->order, st};
+    DshCall call{m, st};
+    if (int rc = call.open()) return rc;
 
     // the table cannot fill while the frame inserts: it is sized for every chunk the rays can enter.  Where the bound that needs no
     // ray would make it grow, the rays are counted first (one more read-back)
-    uint64_t bound = dsh_ray_chunk_bound((uint64_t)n, range_cells, m->g.n);
+    uint64_t bound = dsh_ray_chunk_bound((uint64_t)n, f.range_cells, m->g.n);
     if (bound > ((uint64_t)1 << 30) || dsh_table_capacity(m->n_live + bound) > m->table_cap) {
         unsigned long long by_rays = 0;
         HIP_TRY(h, hipMemsetAsync(dsh_counters(m), 0, kDshCounterBytes, st));
@@ -1132,28 +1221,24 @@ int dsh_rays_impl(sdfgpu_dsh_map_object* m, const DshRayFrame& f, uint64_t range
     }
     if (m->n_live + bound > ((uint64_t)1 << 30))
         return fail(h, SDFGPU_ERR_UNSUPPORTED_SIZE, "dsh: a frame of %lld rays of %llu cells may enter %llu chunks: more than a table holds", (long long)n,
-                    (unsigned long long)range_cells, (unsigned long long)bound);
-    const uint64_t table_cap = std::max(m->table_cap, dsh_table_capacity(m->n_live + bound));
-    const size_t un = (size_t)n;
-    const size_t off_pos = kDshCounterBytes, off_cell = off_pos + align256(un * 4), off_new = off_cell + align256(un * 4),
-                 off_marks = off_new + align256((size_t)table_cap * 4);
-    if (int rc = ensure(h, m->scratch, off_marks + align256((size_t)table_cap), "dsh batch scratch")) return rc;
+                    (unsigned long long)f.range_cells, (unsigned long long)bound);
+    const size_t un = (size_t)n, table_cap = (size_t)std::max(m->table_cap, dsh_table_capacity(m->n_live + bound));
+    uint32_t *op_pos = nullptr, *op_cell = nullptr, *newlist = nullptr;
+    uint8_t* marks = nullptr;
+    if (int rc = dsh_scratch(m, [&](DshCut& c) {
+            op_pos = c.take<uint32_t>(un * 4); op_cell = c.take<uint32_t>(un * 4); newlist = c.take<uint32_t>(table_cap * 4); marks = c.take<uint8_t>(table_cap);
+        })) return rc;
+    uint32_t* const counters = dsh_counters(m);
     DshTable old_table{};
     uint64_t old_cap = 0;
     if (int rc = dsh_reserve_table(m, m->n_live + bound, st, &old_table, &old_cap)) return rc;
-    char* const base = static_cast<char*>(m->scratch.ptr);
-    uint32_t* const counters = dsh_counters(m);
-    uint32_t* const op_pos = reinterpret_cast<uint32_t*>(base + off_pos);
-    uint32_t* const op_cell = reinterpret_cast<uint32_t*>(base + off_cell);
-    uint32_t* const newlist = reinterpret_cast<uint32_t*>(base + off_new);
-    uint8_t* const marks = reinterpret_cast<uint8_t*>(base + off_marks);
     const dim3 grid = dsh_grid(n), block(kDshThreads);
     const uint64_t cpc = (uint64_t)m->g.cells_per_chunk;
 
     struct { uint32_t n_new, lost; unsigned long long counts[kDshRayCounts]; } back{};
     static_assert(sizeof back == 8 + 8 * kDshRayCounts && sizeof back <= kDshCounterBytes, "the counters' layout");
-    // walk A, the read-back of the new-chunk count and the pool: until the pool is reserved the frame can still be refused
-    const int rc = [&]() -> int {
+    // walk A and the read-back of the new-chunk count: until dsh_commit_new has reserved the pool the frame can still be refused
+    const int walked = [&]() -> int {
         HIP_TRY(h, hipMemsetAsync(counters, 0, kDshCounterBytes, st));
         HIP_TRY(h, hipMemsetAsync(marks, 0, (size_t)m->table_cap, st));
         hipLaunchKernelGGL(k_dsh_ray_insert, grid, block, 0, st, m->g, m->table, f, d_points, n, (uint32_t)m->n_live, op_pos, op_cell, newlist, marks, counters,
@@ -1162,25 +1247,9 @@ int dsh_rays_impl(sdfgpu_dsh_map_object* m, const DshRayFrame& f, uint64_t range
         HIP_TRY(h, hipMemcpyAsync(&back, counters, sizeof back, hipMemcpyDeviceToHost, st));
         HIP_TRY(h, hipStreamSynchronize(st));
         if (back.lost) return fail(h, SDFGPU_ERR_HIP, "dsh: %u chunk keys found no table entry (internal error)", back.lost);
-        if (fuse) if (int rc_marks = dsh_reserve_marks(m, m->n_live + back.n_new, st)) return rc_marks;
-        return dsh_reserve_pool(m, m->n_live + back.n_new, st);
+        return SDFGPU_OK;
     }();
-    if (rc != SDFGPU_OK) {                                                      // refused: the table is the one the frame found
-        (void)hipStreamSynchronize(st);
-        if (old_table.keys) {
-            (void)rz_free(h, m->table.keys);
-            m->table = old_table;
-            m->table_cap = old_cap;
-        } else if (back.n_new) {
-            hipLaunchKernelGGL(k_dsh_rollback, dsh_grid(back.n_new), block, 0, st, m->table, newlist, back.n_new);
-            (void)hipStreamSynchronize(st);
-        }
-        return rc;
-    }
-    if (old_table.keys) (void)rz_free(h, old_table.keys);
-    const uint32_t n_new = back.n_new;
-    if (n_new) hipLaunchKernelGGL(k_dsh_init_new, dsh_grid(n_new), block, 0, st, m->table, m->pool.heads, newlist, n_new, (uint32_t)m->n_live);
-    m->n_live += n_new;
+    if (int rc = dsh_commit_new(m, walked, back.n_new, newlist, fuse != nullptr, &old_table, old_cap, st)) return rc;
     hipLaunchKernelGGL(k_dsh_ray_touch, dsh_grid((int64_t)m->table_cap), block, 0, st, m->table, m->pool.heads, marks);
     hipLaunchKernelGGL(k_dsh_expand, dsh_chunk_grid(m->n_live), block, 0, st, m->pool, m->n_live, cpc, m->g.default_record);
     if (!fuse) {
@@ -1201,7 +1270,7 @@ int dsh_rays_impl(sdfgpu_dsh_map_object* m, const DshRayFrame& f, uint64_t range
         out_counts->rays_truncated = back.counts[1];
         out_counts->rays_skipped = back.counts[2];
         out_counts->cells_carved = back.counts[3];
-        out_counts->new_chunks = n_new;
+        out_counts->new_chunks = back.n_new;
     }
     return SDFGPU_OK;
 }
@@ -1214,10 +1283,8 @@ int dsh_get_impl(sdfgpu_dsh_map_object* m, const double* d_loc, int64_t n, void*
     if (!d_loc) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: null locations");
     if (int rc = dsh_aligned8(h, d_records, "the records")) return rc;
     if (int rc = dsh_aligned8(h, d_loc, "the locations")) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, m->order.create());
-    HIP_TRY(h, m->order.wait(st));
-    StreamOrder::RecordAtExit record_at_exit{m->order, st};
+    DshCall call{m, st};
+    if (int rc = call.open()) return rc;
     hipLaunchKernelGGL(k_dsh_get, dsh_grid(n), dim3(kDshThreads), 0, st, m->g, m->table, m->pool, d_loc, n, static_cast<uint64_t*>(d_records), d_statuses);
     HIP_TRY(h, hipGetLastError());
     return SDFGPU_OK;
@@ -1228,20 +1295,13 @@ int dsh_get_impl(sdfgpu_dsh_map_object* m, const double* d_loc, int64_t n, void*
 int dsh_cast_frame(sdfgpu_dsh_map_object* m, const double* sensor, bool segments, int64_t n, double max_range, uint32_t flags, const void* statuses,
                    const void* hits, DshRayFrame& f) {
     sdfgpu_handle h = m->h;
-    const uint64_t no_record = 0;
-    uint64_t range_cells = 0;
-    if (segments) {
-        const double range = max_range * m->g.inv_cell;                        // (every start is the lane's own: only the range is the frame's)
+    if (segments) {                                                            // (every start is the lane's own: only the range is the frame's)
         if (n < 0 || n >= kDshMaxBatch) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: a cast holds 0 .. 2^31 - 1 segments (got %lld)", (long long)n);
-        if (!(range > 0.0 && range <= kDshMaxRangeCells))
-            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: max_range must span more than 0 and at most 65536 cells (got %g, %g cells)", max_range, range);
         f = DshRayFrame{};
-        f.range2 = range * range;
-        f.range_cells = (uint64_t)std::ceil(range);
-        f.max_steps = dsh_ray_max_steps(f.range_cells);
+        if (int rc = dsh_ray_range(m, max_range, f)) return rc;
     } else {
         if (!sensor) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: cast_rays needs the sensor");
-        if (int rc = dsh_ray_frame(m, sensor, n, max_range, &no_record, &no_record, f, range_cells)) return rc;
+        if (int rc = dsh_ray_frame(m, sensor, n, max_range, f)) return rc;
     }
     if (flags & ~(uint32_t)(SDFGPU_DSH_CAST_SKIP_FIRST | SDFGPU_DSH_CAST_SKIP_LAST | SDFGPU_DSH_CAST_UNKNOWN_IS_FILLED))
         return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: a cast knows the flags SKIP_FIRST, SKIP_LAST and UNKNOWN_IS_FILLED (got 0x%x)", flags);
@@ -1262,16 +1322,10 @@ int dsh_cast_impl(sdfgpu_dsh_map_object* m, const DshRayFrame& f, bool segments,
         return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: the points must be 4-byte aligned");
     }
     if (int rc = dsh_aligned8(h, d_hits, "the hits")) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, m->order.create());
-    HIP_TRY(h, m->order.wait(st));
-    StreamOrder::RecordAtExit record_at_exit{m->order, st};
-    if (segments)
-        hipLaunchKernelGGL((k_dsh_cast<true>), dsh_grid(n), dim3(kDshThreads), 0, st, m->g, m->table, m->pool, f, d_points, d_starts, d_ends, n, flags,
-                           d_statuses, d_hits);
-    else
-        hipLaunchKernelGGL((k_dsh_cast<false>), dsh_grid(n), dim3(kDshThreads), 0, st, m->g, m->table, m->pool, f, d_points, d_starts, d_ends, n, flags,
-                           d_statuses, d_hits);
+    DshCall call{m, st};
+    if (int rc = call.open()) return rc;
+    const auto kernel = segments ? k_dsh_cast<true> : k_dsh_cast<false>;
+    hipLaunchKernelGGL(kernel, dsh_grid(n), dim3(kDshThreads), 0, st, m->g, m->table, m->pool, f, d_points, d_starts, d_ends, n, flags, d_statuses, d_hits);
     HIP_TRY(h, hipGetLastError());
     return SDFGPU_OK;
 }
@@ -1291,10 +1345,8 @@ int dsh_window_impl(sdfgpu_dsh_map_object* m, const int64_t* lower, int64_t nx, 
     sdfgpu_handle h = m->h;
     if (int rc = dsh_aligned8(h, d_records, "the records")) return rc;
     if (reinterpret_cast<uintptr_t>(d_bits) & 3) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: the bit field must be 4-byte aligned");
-    HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, m->order.create());
-    HIP_TRY(h, m->order.wait(st));
-    StreamOrder::RecordAtExit record_at_exit{m->order, st};
+    DshCall call{m, st};
+    if (int rc = call.open()) return rc;
     DshWindow w{};
     for (int a = 0; a < 3; ++a) w.lower[a] = lower[a];
     w.ny = (uint32_t)ny; w.nz = (uint32_t)nz;
@@ -1332,18 +1384,16 @@ int dsh_export_impl(sdfgpu_dsh_map_object* m, sdfgpu_dsh_chunk* d_chunks, int64_
         return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: export: a capacity without a buffer");
     if (int rc = dsh_aligned8(h, d_chunks, "the chunk list")) return rc;
     if (int rc = dsh_aligned8(h, d_cells, "the cell list")) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, m->order.create());
-    HIP_TRY(h, m->order.wait(st));
-    StreamOrder::RecordAtExit record_at_exit{m->order, st};
+    DshCall call{m, st};
+    if (int rc = call.open()) return rc;
     uint64_t chunk_filled = 0, cell_filled = 0;
     if (int rc = dsh_count(m, &chunk_filled, &cell_filled, st)) return rc;
     const uint64_t cpc = (uint64_t)m->g.cells_per_chunk, total_cells = cell_filled * cpc;
     if (out_chunks) *out_chunks = (int64_t)m->n_live;
     if (out_cells) *out_cells = (int64_t)total_cells;
     if (!m->n_live || (uint64_t)chunk_capacity < m->n_live || (uint64_t)cell_capacity < total_cells) return SDFGPU_OK;
-    if (int rc = ensure(h, m->scratch, kDshCounterBytes + (size_t)m->n_live * 4, "dsh batch scratch")) return rc;
-    uint32_t* const slot_of_rank = reinterpret_cast<uint32_t*>(static_cast<char*>(m->scratch.ptr) + kDshCounterBytes);
+    uint32_t* slot_of_rank = nullptr;
+    if (int rc = dsh_scratch(m, [&](DshCut& c) { slot_of_rank = c.take<uint32_t>((size_t)m->n_live * 4); })) return rc;
     hipLaunchKernelGGL(k_dsh_rank, dsh_grid((int64_t)m->n_live), dim3(kDshThreads), 0, st, m->pool.heads, (uint32_t)m->n_live, cpc, d_chunks, slot_of_rank);
     if (total_cells)
         hipLaunchKernelGGL(k_dsh_export_cells, dsh_chunk_grid(m->n_live), dim3(kDshThreads), 0, st, m->pool, m->n_live, cpc, d_chunks, slot_of_rank, static_cast<uint64_t*>(d_cells));
@@ -1362,22 +1412,16 @@ int dsh_remove_impl(sdfgpu_dsh_map_object* m, const double* d_loc, int64_t n, co
         if (!d_loc) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: null locations");
         if (int rc = dsh_aligned8(h, d_loc, "the locations")) return rc;
     }
-    HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, m->order.create());
-    HIP_TRY(h, m->order.wait(st));
-    StreamOrder::RecordAtExit record_at_exit{m->order, st};
+    DshCall call{m, st};
+    if (int rc = call.open()) return rc;
 
     const size_t live = (size_t)m->n_live, ops = range ? 0 : (size_t)n, tiles = (size_t)dsh_pair_tiles(m->n_live), half = live / 2 + 1;
-    const size_t off_flags = kDshCounterBytes, off_ops = off_flags + align256(live * 4), off_tiles = off_ops + align256(ops * 4),
-                 off_holes = off_tiles + align256(tiles * 8), off_movers = off_holes + align256(half * 4);
-    if (int rc = ensure(h, m->scratch, off_movers + align256(half * 4), "dsh batch scratch")) return rc;
-    char* const base = static_cast<char*>(m->scratch.ptr);
+    uint32_t *flags = nullptr, *op_slot = nullptr, *tile_counts = nullptr, *holes = nullptr, *movers = nullptr;
+    if (int rc = dsh_scratch(m, [&](DshCut& c) {
+            flags = c.take<uint32_t>(live * 4); op_slot = c.take<uint32_t>(ops * 4); tile_counts = c.take<uint32_t>(tiles * 8);
+            holes = c.take<uint32_t>(half * 4); movers = c.take<uint32_t>(half * 4);
+        })) return rc;
     uint32_t* const counters = dsh_counters(m);
-    uint32_t* const flags = reinterpret_cast<uint32_t*>(base + off_flags);
-    uint32_t* const op_slot = reinterpret_cast<uint32_t*>(base + off_ops);
-    uint32_t* const tile_counts = reinterpret_cast<uint32_t*>(base + off_tiles);
-    uint32_t* const holes = reinterpret_cast<uint32_t*>(base + off_holes);
-    uint32_t* const movers = reinterpret_cast<uint32_t*>(base + off_movers);
     const dim3 block(kDshThreads), live_grid = dsh_grid((int64_t)live);
     const uint32_t n_live = (uint32_t)m->n_live;
 
@@ -1410,9 +1454,7 @@ int dsh_remove_impl(sdfgpu_dsh_map_object* m, const double* d_loc, int64_t n, co
     if (out_removed) *out_removed = (int64_t)removed;
     if (!keep) return SDFGPU_OK;
     uint32_t lost = 0;
-    hipLaunchKernelGGL(k_dsh_rehash, dsh_grid((int64_t)keep), block, 0, st, m->table, m->pool.heads, keep, counters);
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(&lost, counters + 1, 4, hipMemcpyDeviceToHost, st));
+    if (int rc = dsh_rehash_into(m, m->table, keep, st, &lost)) return rc;    // (counters[1] is still the zero the call began with)
     HIP_TRY(h, hipStreamSynchronize(st));
     if (lost) return fail(h, SDFGPU_ERR_HIP, "dsh: the rehash lost %u keys (internal error)", lost);
     return SDFGPU_OK;
@@ -1423,10 +1465,8 @@ int dsh_remove_impl(sdfgpu_dsh_map_object* m, const double* d_loc, int64_t n, co
 int dsh_shrink_impl(sdfgpu_dsh_map_object* m, int64_t spare_chunks, hipStream_t st) {
     sdfgpu_handle h = m->h;
     if (spare_chunks < 0) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: spare_chunks must not be negative (got %lld)", (long long)spare_chunks);
-    HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, m->order.create());
-    HIP_TRY(h, m->order.wait(st));
-    StreamOrder::RecordAtExit record_at_exit{m->order, st};
+    DshCall call{m, st};
+    if (int rc = call.open()) return rc;
     const uint64_t cpc = (uint64_t)m->g.cells_per_chunk;
     uint64_t pool_cap = 0, table_cap = 0;
     dsh_plan_shrink(m->n_live, (uint64_t)spare_chunks, m->pool_cap, m->table_cap, &pool_cap, &table_cap);
@@ -1439,14 +1479,9 @@ int dsh_shrink_impl(sdfgpu_dsh_map_object* m, int64_t spare_chunks, hipStream_t 
     if (rc == SDFGPU_OK) rc = [&]() -> int {
         if (table.keys && m->n_live) {
             HIP_TRY(h, hipMemsetAsync(dsh_counters(m), 0, kDshCounterBytes, st));
-            hipLaunchKernelGGL(k_dsh_rehash, dsh_grid((int64_t)m->n_live), dim3(kDshThreads), 0, st, table, m->pool.heads, (uint32_t)m->n_live, dsh_counters(m));
-            HIP_TRY(h, hipGetLastError());
-            HIP_TRY(h, hipMemcpyAsync(&lost, dsh_counters(m) + 1, 4, hipMemcpyDeviceToHost, st));
+            if (int rc_rehash = dsh_rehash_into(m, table, m->n_live, st, &lost)) return rc_rehash;
         }
-        if (pool.heads && m->n_live) {
-            HIP_TRY(h, hipMemcpyAsync(pool.heads, m->pool.heads, (size_t)(m->n_live * sizeof(DshChunkHead)), hipMemcpyDeviceToDevice, st));
-            HIP_TRY(h, hipMemcpyAsync(pool.cells, m->pool.cells, (size_t)(m->n_live * cpc * 8), hipMemcpyDeviceToDevice, st));
-        }
+        if (pool.heads) if (int rc_copy = dsh_copy_pool(m, pool, st)) return rc_copy;
         HIP_TRY(h, hipStreamSynchronize(st));                                   // (what is replaced may still be read by pending work)
         if (lost) return fail(h, SDFGPU_ERR_HIP, "dsh: the rehash lost %u keys (internal error)", lost);
         return SDFGPU_OK;
@@ -1476,82 +1511,82 @@ int dsh_shrink_impl(sdfgpu_dsh_map_object* m, int64_t spare_chunks, hipStream_t 
     return SDFGPU_OK;
 }
 
-// the host forms' staging: sections of the map's stage buffer, 256-byte aligned
-struct DshStage {
-    size_t total = 0;
-    size_t add(size_t bytes) { const size_t at = total; total += align256(bytes); return at; }
-};
-
 template <class Body>
 int dsh_entry(sdfgpu_dsh_map m, void* stream, Body&& body) {
     if (dsh_check_map(m)) return SDFGPU_ERR_INVALID_ARGUMENT;
     return rz_wrap(m->h, stream, body);
 }
 
+// What a host form says about its arrays while dsh_staged lays the map's stage buffer out: in() and out() give the array's section
+// (null for an absent array) and note the copy.
+struct DshStaging {
+    struct Copy { void* host; void* dev; size_t bytes; };
+    DshCut* cut = nullptr;
+    Copy ins[2], outs[2];
+    int n_in = 0, n_out = 0;
+    void* take(const void* host, size_t bytes, Copy* list, int& count) {
+        void* const dev = cut->take<char>(bytes, host && bytes);
+        if (dev) list[count++] = Copy{const_cast<void*>(host), dev, bytes};
+        return dev;
+    }
+    template <class T> const T* in(const T* host, size_t bytes) { return static_cast<const T*>(take(host, bytes, ins, n_in)); }
+    template <class T> T* out(T* host, size_t bytes) { return static_cast<T*>(take(host, bytes, outs, n_out)); }
+};
+
+// A host form on the null stream: behind the call before it (dsh_wait) the stage buffer is sized and cut as `layout` says, the inputs
+// go up in the order they were named, `body` (the device form, on the staged arrays) runs, and the outputs come down in theirs.
+template <class Layout, class Body>
+int dsh_staged(sdfgpu_dsh_map_object* m, Layout&& layout, Body&& body) {
+    sdfgpu_handle h = m->h;
+    if (int rc = dsh_wait(m, nullptr)) return rc;
+    DshStaging s;
+    if (int rc = dsh_cut(h, m->stage, "dsh staging", 0, [&](DshCut& c) { s = DshStaging{}; s.cut = &c; layout(s); })) return rc;
+    for (int k = 0; k < s.n_in; ++k) if (int rc = copy_from_host(h, s.ins[k].dev, s.ins[k].host, s.ins[k].bytes)) return rc;
+    if (int rc = body()) return rc;
+    for (int k = 0; k < s.n_out; ++k) if (int rc = copy_to_host(h, s.outs[k].host, s.outs[k].dev, s.outs[k].bytes)) return rc;
+    return SDFGPU_OK;
+}
+
 int dsh_set_host(sdfgpu_dsh_map m, bool chunk_sets, const double* locations, int64_t n, const void* values, const void* one_value, uint8_t* statuses) {
     return dsh_entry(m, nullptr, [&]() -> int {
-        sdfgpu_handle h = m->h;
-        if (n < 0 || n >= kDshMaxBatch) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: a batch holds 0 .. 2^31 - 1 operations (got %lld)", (long long)n);
-        if (n == 0) return dsh_batch<double>(m, chunk_sets, nullptr, 0, values, one_value, nullptr, nullptr);
-        if (!locations) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: null locations");
-        HIP_TRY(h, hipSetDevice(h->device));
-        HIP_TRY(h, m->order.wait(nullptr));
-        DshStage s;
-        const size_t un = (size_t)n, at_loc = s.add(un * 24), at_val = s.add(values ? un * 8 : 0), at_st = s.add(statuses ? un : 0);
-        if (int rc = ensure(h, m->stage, s.total, "dsh staging")) return rc;
-        char* const base = static_cast<char*>(m->stage.ptr);
-        if (int rc = copy_from_host(h, base + at_loc, locations, un * 24)) return rc;
-        if (values) if (int rc = copy_from_host(h, base + at_val, values, un * 8)) return rc;
-        if (int rc = dsh_batch<double>(m, chunk_sets, reinterpret_cast<const double*>(base + at_loc), n, values ? base + at_val : nullptr, one_value,
-                                       statuses ? reinterpret_cast<uint8_t*>(base + at_st) : nullptr, nullptr)) return rc;
-        if (statuses) return copy_to_host(h, statuses, base + at_st, un);
-        return SDFGPU_OK;
+        if (n <= 0 || n >= kDshMaxBatch) return dsh_batch<double>(m, chunk_sets, nullptr, n, values, one_value, nullptr, nullptr);   // (its refusals, or nothing to do)
+        if (!locations) return fail(m->h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: null locations");
+        const size_t un = (size_t)n;
+        const double* d_loc = nullptr;
+        const void* d_values = nullptr;
+        uint8_t* d_statuses = nullptr;
+        return dsh_staged(m, [&](DshStaging& s) { d_loc = s.in(locations, un * 24); d_values = s.in(values, un * 8); d_statuses = s.out(statuses, un); },
+                          [&] { return dsh_batch<double>(m, chunk_sets, d_loc, n, d_values, one_value, d_statuses, nullptr); });
     });
 }
 
 // The host form of a frame: the points are staged, the statuses copied back.
-int dsh_rays_host(sdfgpu_dsh_map m, const DshRayFrame& f, uint64_t range_cells, const float* points, int64_t n, const void* free_value, const void* hit_value,
-                  const DshFuse* fuse, uint8_t* statuses, sdfgpu_dsh_ray_counts* out_counts) {
-    sdfgpu_handle h = m->h;
-    if (n == 0) return dsh_rays_impl(m, f, range_cells, nullptr, 0, free_value, hit_value, fuse, nullptr, out_counts, nullptr);
-    if (!points) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: null points");
-    HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, m->order.wait(nullptr));
-    DshStage s;
-    const size_t un = (size_t)n, at_pts = s.add(un * 12), at_st = s.add(statuses ? un : 0);
-    if (int rc = ensure(h, m->stage, s.total, "dsh staging")) return rc;
-    char* const base = static_cast<char*>(m->stage.ptr);
-    if (int rc = copy_from_host(h, base + at_pts, points, un * 12)) return rc;
-    if (int rc = dsh_rays_impl(m, f, range_cells, reinterpret_cast<const float*>(base + at_pts), n, free_value, hit_value, fuse,
-                               statuses ? reinterpret_cast<uint8_t*>(base + at_st) : nullptr, out_counts, nullptr)) return rc;
-    if (statuses) return copy_to_host(h, statuses, base + at_st, un);
-    return SDFGPU_OK;
+int dsh_rays_host(sdfgpu_dsh_map m, const DshRayFrame& f, const float* points, int64_t n, const void* free_value, const void* hit_value, const DshFuse* fuse,
+                  uint8_t* statuses, sdfgpu_dsh_ray_counts* out_counts) {
+    if (n == 0) return dsh_rays_impl(m, f, nullptr, 0, free_value, hit_value, fuse, nullptr, out_counts, nullptr);
+    if (!points) return fail(m->h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: null points");
+    const float* d_points = nullptr;
+    uint8_t* d_statuses = nullptr;
+    return dsh_staged(m, [&](DshStaging& s) { d_points = s.in(points, (size_t)n * 12); d_statuses = s.out(statuses, (size_t)n); },
+                      [&] { return dsh_rays_impl(m, f, d_points, n, free_value, hit_value, fuse, d_statuses, out_counts, nullptr); });
 }
 
 // The host form of a cast: the points (12 bytes a ray), or the starts and the ends (24 each), are staged; statuses and hits copied back.
 int dsh_cast_host(sdfgpu_dsh_map m, const DshRayFrame& f, bool segments, const void* first, const void* second, int64_t n, uint32_t flags, uint8_t* statuses,
                   sdfgpu_dsh_cast_hit* hits) {
-    sdfgpu_handle h = m->h;
     if (n == 0) return SDFGPU_OK;
-    if (!first || (segments && !second)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: a cast needs its %s", segments ? "starts and ends" : "points");
-    HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, m->order.wait(nullptr));
-    DshStage s;
+    if (!first || (segments && !second)) return fail(m->h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: a cast needs its %s", segments ? "starts and ends" : "points");
     const size_t un = (size_t)n, each = segments ? un * 24 : un * 12;
-    const size_t at_first = s.add(each), at_second = s.add(segments ? each : 0), at_st = s.add(statuses ? un : 0),
-                 at_hits = s.add(hits ? un * sizeof(sdfgpu_dsh_cast_hit) : 0);
-    if (int rc = ensure(h, m->stage, s.total, "dsh staging")) return rc;
-    char* const base = static_cast<char*>(m->stage.ptr);
-    if (int rc = copy_from_host(h, base + at_first, first, each)) return rc;
-    if (segments) if (int rc = copy_from_host(h, base + at_second, second, each)) return rc;
-    if (int rc = dsh_cast_impl(m, f, segments, segments ? nullptr : reinterpret_cast<const float*>(base + at_first),
-                               segments ? reinterpret_cast<const double*>(base + at_first) : nullptr,
-                               segments ? reinterpret_cast<const double*>(base + at_second) : nullptr, n, flags,
-                               statuses ? reinterpret_cast<uint8_t*>(base + at_st) : nullptr,
-                               hits ? reinterpret_cast<sdfgpu_dsh_cast_hit*>(base + at_hits) : nullptr, nullptr)) return rc;
-    if (statuses) if (int rc = copy_to_host(h, statuses, base + at_st, un)) return rc;
-    if (hits) return copy_to_host(h, hits, base + at_hits, un * sizeof(sdfgpu_dsh_cast_hit));
-    return SDFGPU_OK;
+    const void *d_first = nullptr, *d_second = nullptr;
+    uint8_t* d_statuses = nullptr;
+    sdfgpu_dsh_cast_hit* d_hits = nullptr;
+    return dsh_staged(m, [&](DshStaging& s) {
+            d_first = s.in(first, each); d_second = s.in(segments ? second : nullptr, each);
+            d_statuses = s.out(statuses, un); d_hits = s.out(hits, un * sizeof(sdfgpu_dsh_cast_hit));
+        }, [&] {
+            return dsh_cast_impl(m, f, segments, segments ? nullptr : static_cast<const float*>(d_first), segments ? static_cast<const double*>(d_first) : nullptr,
+                                 static_cast<const double*>(d_second), n, flags, d_statuses, d_hits, nullptr);
+        });
 }
 
 }  // namespace
@@ -1618,9 +1653,8 @@ int sdfgpu_dsh_info(sdfgpu_dsh_map map, sdfgpu_dsh_counts* out_counts) {
     return dsh_entry(map, nullptr, [&]() -> int {
         sdfgpu_handle h = map->h;
         if (!out_counts) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: out_counts is null");
-        HIP_TRY(h, hipSetDevice(h->device));
-        HIP_TRY(h, map->order.wait(nullptr));
-        StreamOrder::RecordAtExit record_at_exit{map->order, nullptr};
+        DshCall call{map, nullptr};
+        if (int rc = call.open()) return rc;
         sdfgpu_dsh_counts c{};
         if (int rc = dsh_count(map, &c.chunk_filled, &c.cell_filled, nullptr)) return rc;
         c.capacity_chunks = map->pool_cap;
@@ -1654,9 +1688,8 @@ int sdfgpu_dsh_insert_rays_device(sdfgpu_dsh_map map, const double sensor[3], co
                                   const void* hit_value, uint8_t* d_statuses, sdfgpu_dsh_ray_counts* out_counts, void* stream) {
     return dsh_entry(map, stream, [&]() -> int {
         DshRayFrame f{};
-        uint64_t range_cells = 0;
-        if (int rc = dsh_ray_frame(map, sensor, n, max_range, free_value, hit_value, f, range_cells)) return rc;
-        return dsh_rays_impl(map, f, range_cells, d_points, n, free_value, hit_value, nullptr, d_statuses, out_counts, (hipStream_t)stream);
+        if (int rc = dsh_carve_frame(map, sensor, n, max_range, free_value, hit_value, f)) return rc;
+        return dsh_rays_impl(map, f, d_points, n, free_value, hit_value, nullptr, d_statuses, out_counts, (hipStream_t)stream);
     });
 }
 
@@ -1665,11 +1698,9 @@ int sdfgpu_dsh_fuse_rays_device(sdfgpu_dsh_map map, const double sensor[3], cons
     return dsh_entry(map, stream, [&]() -> int {
         DshRayFrame f{};
         DshFuse u{};
-        uint64_t range_cells = 0;
-        const uint64_t no_record = 0;                                           // (a fused frame stores no record of the caller's)
         if (int rc = dsh_fuse_model(map->h, model, u)) return rc;
-        if (int rc = dsh_ray_frame(map, sensor, n, max_range, &no_record, &no_record, f, range_cells)) return rc;
-        return dsh_rays_impl(map, f, range_cells, d_points, n, nullptr, nullptr, &u, d_statuses, out_counts, (hipStream_t)stream);
+        if (int rc = dsh_ray_frame(map, sensor, n, max_range, f)) return rc;
+        return dsh_rays_impl(map, f, d_points, n, nullptr, nullptr, &u, d_statuses, out_counts, (hipStream_t)stream);
     });
 }
 
@@ -1677,9 +1708,8 @@ int sdfgpu_dsh_insert_rays(sdfgpu_dsh_map map, const double sensor[3], const flo
                            const void* hit_value, uint8_t* statuses, sdfgpu_dsh_ray_counts* out_counts) {
     return dsh_entry(map, nullptr, [&]() -> int {
         DshRayFrame f{};
-        uint64_t range_cells = 0;
-        if (int rc = dsh_ray_frame(map, sensor, n, max_range, free_value, hit_value, f, range_cells)) return rc;
-        return dsh_rays_host(map, f, range_cells, points, n, free_value, hit_value, nullptr, statuses, out_counts);
+        if (int rc = dsh_carve_frame(map, sensor, n, max_range, free_value, hit_value, f)) return rc;
+        return dsh_rays_host(map, f, points, n, free_value, hit_value, nullptr, statuses, out_counts);
     });
 }
 
@@ -1688,11 +1718,9 @@ int sdfgpu_dsh_fuse_rays(sdfgpu_dsh_map map, const double sensor[3], const float
     return dsh_entry(map, nullptr, [&]() -> int {
         DshRayFrame f{};
         DshFuse u{};
-        uint64_t range_cells = 0;
-        const uint64_t no_record = 0;
         if (int rc = dsh_fuse_model(map->h, model, u)) return rc;
-        if (int rc = dsh_ray_frame(map, sensor, n, max_range, &no_record, &no_record, f, range_cells)) return rc;
-        return dsh_rays_host(map, f, range_cells, points, n, nullptr, nullptr, &u, statuses, out_counts);
+        if (int rc = dsh_ray_frame(map, sensor, n, max_range, f)) return rc;
+        return dsh_rays_host(map, f, points, n, nullptr, nullptr, &u, statuses, out_counts);
     });
 }
 
@@ -1713,17 +1741,10 @@ int sdfgpu_dsh_remove_chunks(sdfgpu_dsh_map map, const double* locations, int64_
         sdfgpu_handle h = map->h;
         if (n <= 0 || n >= kDshMaxBatch) return dsh_remove_impl(map, nullptr, n, nullptr, 0, nullptr, out_removed, nullptr);
         if (!locations) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: null locations");
-        HIP_TRY(h, hipSetDevice(h->device));
-        HIP_TRY(h, map->order.wait(nullptr));
-        DshStage s;
-        const size_t un = (size_t)n, at_loc = s.add(un * 24), at_st = s.add(statuses ? un : 0);
-        if (int rc = ensure(h, map->stage, s.total, "dsh staging")) return rc;
-        char* const base = static_cast<char*>(map->stage.ptr);
-        if (int rc = copy_from_host(h, base + at_loc, locations, un * 24)) return rc;
-        if (int rc = dsh_remove_impl(map, reinterpret_cast<const double*>(base + at_loc), n, nullptr, 0,
-                                     statuses ? reinterpret_cast<uint8_t*>(base + at_st) : nullptr, out_removed, nullptr)) return rc;
-        if (statuses) return copy_to_host(h, statuses, base + at_st, un);
-        return SDFGPU_OK;
+        const double* d_loc = nullptr;
+        uint8_t* d_statuses = nullptr;
+        return dsh_staged(map, [&](DshStaging& s) { d_loc = s.in(locations, (size_t)n * 24); d_statuses = s.out(statuses, (size_t)n); },
+                          [&] { return dsh_remove_impl(map, d_loc, n, nullptr, 0, d_statuses, out_removed, nullptr); });
     });
 }
 
@@ -1748,23 +1769,14 @@ int sdfgpu_dsh_get_device(sdfgpu_dsh_map map, const double* d_locations, int64_t
 
 int sdfgpu_dsh_get(sdfgpu_dsh_map map, const double* locations, int64_t n, void* records, uint8_t* statuses) {
     return dsh_entry(map, nullptr, [&]() -> int {
-        sdfgpu_handle h = map->h;
-        if (n < 0 || n >= kDshMaxBatch) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: a batch holds 0 .. 2^31 - 1 locations (got %lld)", (long long)n);
-        if (!records && !statuses) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: get needs an output");
-        if (n == 0) return SDFGPU_OK;
-        if (!locations) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: null locations");
-        HIP_TRY(h, hipSetDevice(h->device));
-        HIP_TRY(h, map->order.wait(nullptr));
-        DshStage s;
-        const size_t un = (size_t)n, at_loc = s.add(un * 24), at_rec = s.add(records ? un * 8 : 0), at_st = s.add(statuses ? un : 0);
-        if (int rc = ensure(h, map->stage, s.total, "dsh staging")) return rc;
-        char* const base = static_cast<char*>(map->stage.ptr);
-        if (int rc = copy_from_host(h, base + at_loc, locations, un * 24)) return rc;
-        if (int rc = dsh_get_impl(map, reinterpret_cast<const double*>(base + at_loc), n, records ? base + at_rec : nullptr,
-                                  statuses ? reinterpret_cast<uint8_t*>(base + at_st) : nullptr, nullptr)) return rc;
-        if (records) if (int rc = copy_to_host(h, records, base + at_rec, un * 8)) return rc;
-        if (statuses) return copy_to_host(h, statuses, base + at_st, un);
-        return SDFGPU_OK;
+        if (n <= 0 || n >= kDshMaxBatch || (!records && !statuses)) return dsh_get_impl(map, nullptr, n, records, statuses, nullptr);   // (its refusals, or nothing to do)
+        if (!locations) return fail(map->h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: null locations");
+        const size_t un = (size_t)n;
+        const double* d_loc = nullptr;
+        void* d_records = nullptr;
+        uint8_t* d_statuses = nullptr;
+        return dsh_staged(map, [&](DshStaging& s) { d_loc = s.in(locations, un * 24); d_records = s.out(records, un * 8); d_statuses = s.out(statuses, un); },
+                          [&] { return dsh_get_impl(map, d_loc, n, d_records, d_statuses, nullptr); });
     });
 }
 
@@ -1817,18 +1829,11 @@ int sdfgpu_dsh_extract_window(sdfgpu_dsh_map map, const int64_t lower[3], int64_
     return dsh_entry(map, nullptr, [&]() -> int {
         sdfgpu_handle h = map->h;
         if (int rc = dsh_check_window(h, lower, nx, ny, nz, records, bits)) return rc;
-        HIP_TRY(h, hipSetDevice(h->device));
-        HIP_TRY(h, map->order.wait(nullptr));
         const size_t n = (size_t)nx * (size_t)ny * (size_t)nz, words = (n + 31) / 32;
-        DshStage s;
-        const size_t at_rec = s.add(records ? n * 8 : 0), at_bits = s.add(bits ? words * 4 : 0);
-        if (int rc = ensure(h, map->stage, s.total, "dsh staging")) return rc;
-        char* const base = static_cast<char*>(map->stage.ptr);
-        if (int rc = dsh_window_impl(map, lower, nx, ny, nz, unknown_is_filled, records ? base + at_rec : nullptr,
-                                     bits ? reinterpret_cast<uint32_t*>(base + at_bits) : nullptr, nullptr)) return rc;
-        if (records) if (int rc = copy_to_host(h, records, base + at_rec, n * 8)) return rc;
-        if (bits) return copy_to_host(h, bits, base + at_bits, words * 4);
-        return SDFGPU_OK;
+        void* d_records = nullptr;
+        uint32_t* d_bits = nullptr;
+        return dsh_staged(map, [&](DshStaging& s) { d_records = s.out(records, n * 8); d_bits = s.out(bits, words * 4); },
+                          [&] { return dsh_window_impl(map, lower, nx, ny, nz, unknown_is_filled, d_records, d_bits, nullptr); });
     });
 }
 
@@ -1845,22 +1850,16 @@ int sdfgpu_dsh_export(sdfgpu_dsh_map map, sdfgpu_dsh_chunk* chunks, int64_t chun
         sdfgpu_handle h = map->h;
         if (chunk_capacity < 0 || cell_capacity < 0 || (chunk_capacity > 0 && !chunks) || (cell_capacity > 0 && !cells))
             return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: export: a capacity without a buffer");
-        HIP_TRY(h, hipSetDevice(h->device));
-        HIP_TRY(h, map->order.wait(nullptr));
+        if (int rc = dsh_wait(map, nullptr)) return rc;
         int64_t n_chunks = 0, n_cells = 0;
         if (int rc = dsh_export_impl(map, nullptr, 0, nullptr, 0, &n_chunks, &n_cells, nullptr)) return rc;
         if (out_chunks) *out_chunks = n_chunks;
         if (out_cells) *out_cells = n_cells;
         if (n_chunks == 0 || chunk_capacity < n_chunks || cell_capacity < n_cells) return SDFGPU_OK;
-        DshStage s;
-        const size_t at_chunks = s.add((size_t)n_chunks * sizeof(sdfgpu_dsh_chunk)), at_cells = s.add((size_t)n_cells * 8);
-        if (int rc = ensure(h, map->stage, s.total, "dsh staging")) return rc;
-        char* const base = static_cast<char*>(map->stage.ptr);
-        if (int rc = dsh_export_impl(map, reinterpret_cast<sdfgpu_dsh_chunk*>(base + at_chunks), n_chunks, base + at_cells, n_cells, nullptr, nullptr, nullptr))
-            return rc;
-        if (int rc = copy_to_host(h, chunks, base + at_chunks, (size_t)n_chunks * sizeof(sdfgpu_dsh_chunk))) return rc;
-        if (n_cells) return copy_to_host(h, cells, base + at_cells, (size_t)n_cells * 8);
-        return SDFGPU_OK;
+        sdfgpu_dsh_chunk* d_chunks = nullptr;
+        void* d_cells = nullptr;
+        return dsh_staged(map, [&](DshStaging& s) { d_chunks = s.out(chunks, (size_t)n_chunks * sizeof(sdfgpu_dsh_chunk)); d_cells = s.out(cells, (size_t)n_cells * 8); },
+                          [&] { return dsh_export_impl(map, d_chunks, n_chunks, d_cells, n_cells, nullptr, nullptr, nullptr); });
     });
 }
 
