@@ -3,12 +3,11 @@
 // The family's host orchestration and C ABI entry points (sdfgpu_components*) are at the end of this file, over the handle of
 // sdfgpu_context.hpp.
 //
-// Union-find invariant, relied on by every find below: a label word only ever DECREASES, and it never holds a value above its
-// own index (a provisional label is the index of a tile-local root <= the voxel; a link stores a smaller root into a larger
-// one with atomicMin).  Every parent chain is therefore strictly decreasing until it meets a self-loop, so every find ends,
-// and the root of a component is its minimum linear index -- the voxel at which the reference's x -> y -> z scan starts it.
+// The global union-find of k_cc_merge (its invariant, its memory scope) and the root ranking of k_cc_flatten / k_cc_scan /
+// k_cc_relabel are stated once, in sdfgpu_unionfind.hpp.
 #include "sdfgpu_context.hpp"
 #include "sdfgpu_components.hpp"
+#include "sdfgpu_unionfind.hpp"
 #include "sdfgpu.h"
 
 #include <algorithm>
@@ -19,7 +18,6 @@ namespace {
 
 constexpr int kLocalThreads = 1024;
 constexpr int kMergeThreads = 256;
-constexpr int kScanThreads = 1024;
 constexpr int kRelabelPerThread = 4;
 
 __device__ __forceinline__ uint32_t bit_at(const uint32_t* __restrict__ bits, uint64_t g) {
@@ -42,41 +40,6 @@ __device__ __forceinline__ void lds_union(uint32_t* l, uint32_t a, uint32_t b) {
         const uint32_t old = atomicMin(&l[a], b);    // a was a root: it now hangs under b; else retry from what a had become
         if (old == a) return;
         a = old;
-    }
-}
-
-// ---- global union-find (k_cc_merge) -------------------------------------------------------------------------------------------
-// Other workgroups, on other XCDs, link roots while this one walks: every read of a label word is an agent-scope load (sc1, past
-// this CU's L1 and never a stale line of this XCD's L2 for words another XCD's atomic wrote) and every write an agent-scope atomic.
-// A stale read would still be safe (it returns an older, larger ancestor), but nothing here depends on that.
-__device__ __forceinline__ uint32_t ld_agent(uint32_t* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ uint32_t min_agent(uint32_t* p, uint32_t v) {
-    return __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// find with path halving: a hop whose grandparent differs is shortened with atomicMin (monotone, stays in the component)
-__device__ __forceinline__ uint32_t g_find(uint32_t* L, uint32_t a) {
-    for (;;) {
-        const uint32_t p = ld_agent(&L[a]);
-        if (p == a) return a;
-        const uint32_t gp = ld_agent(&L[p]);
-        if (gp == p) return p;
-        (void)min_agent(&L[a], gp);
-        a = gp;
-    }
-}
-
-__device__ __forceinline__ void g_union(uint32_t* L, uint32_t a, uint32_t b) {
-    for (;;) {
-        a = g_find(L, a);
-        b = g_find(L, b);
-        if (a == b) return;
-        if (a < b) { const uint32_t t = a; a = b; b = t; }
-        const uint32_t old = min_agent(&L[a], b);
-        if (old == a) return;
-        a = old;                                      // a had been linked meanwhile (old < a): join its new root instead
     }
 }
 
@@ -193,7 +156,7 @@ __global__ __launch_bounds__(kMergeThreads) void k_cc_merge(const CcArgs a) {
             const uint32_t c = bit_at(a.bits, v);
             if (bit_at(a.bits, u) != c) continue;
             if (iz > 0 && bit_at(a.bits, v - 1) == c && bit_at(a.bits, u - 1) == c) continue;
-            g_union(a.L, (uint32_t)v, (uint32_t)u);
+            uf_union<RootIsSelf>(a.L, (uint32_t)v, (uint32_t)u);
         }
     }
     if (ly) {                               // neighbour (x, y0 - 1, z)
@@ -205,7 +168,7 @@ __global__ __launch_bounds__(kMergeThreads) void k_cc_merge(const CcArgs a) {
             const uint32_t c = bit_at(a.bits, v);
             if (bit_at(a.bits, u) != c) continue;
             if (iz > 0 && bit_at(a.bits, v - 1) == c && bit_at(a.bits, u - 1) == c) continue;
-            g_union(a.L, (uint32_t)v, (uint32_t)u);
+            uf_union<RootIsSelf>(a.L, (uint32_t)v, (uint32_t)u);
         }
     }
     if (lz) {                               // neighbour (x, y, z0 - 1); skip when (y - 1) pairs up the same way
@@ -217,78 +180,22 @@ __global__ __launch_bounds__(kMergeThreads) void k_cc_merge(const CcArgs a) {
             const uint32_t c = bit_at(a.bits, v);
             if (bit_at(a.bits, u) != c) continue;
             if (iy > 0 && bit_at(a.bits, v - nz) == c && bit_at(a.bits, u - nz) == c) continue;
-            g_union(a.L, (uint32_t)v, (uint32_t)u);
+            uf_union<RootIsSelf>(a.L, (uint32_t)v, (uint32_t)u);
         }
     }
 }
 
-// ---- k_cc_flatten -------------------------------------------------------------------------------------------------------------
-// After k_cc_merge (stream order: its atomics are visible).  Writes inside this launch only replace a label by its root, so any
-// value a plain load sees is an ancestor of the voxel.  rb[w]: root flags of voxels 32 w .. 32 w + 31; wr[w]: roots in the
-// chunk's words before w; cc[chunk]: roots in the chunk.
+// ---- k_cc_flatten / k_cc_scan / k_cc_relabel: the root ranking of sdfgpu_unionfind.hpp; every self-labelled voxel is a root --------
 __global__ __launch_bounds__(256) void k_cc_flatten(uint32_t* __restrict__ L, uint64_t n, uint32_t* __restrict__ rb,
                                                     uint32_t* __restrict__ wr, uint32_t* __restrict__ cc) {
-    __shared__ uint32_t wc[kCcChunk / 32];
-    const uint64_t base = (uint64_t)blockIdx.x * kCcChunk;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int j = 0; j < kCcChunk / 256; ++j) {
-        const uint64_t v = base + (uint64_t)j * 256 + threadIdx.x;
-        bool root = false;
-        if (v < n) {
-            const uint32_t r = L[v];
-            if (r == (uint32_t)v) {
-                root = true;
-            } else {
-                uint32_t q = r, p = L[q];
-                while (p != q) { q = p; p = L[q]; }
-                if (q != r) L[v] = q;
-            }
-        }
-        const uint64_t m = __ballot(root);
-        if (lane == 0) {
-            const int w = j * 8 + 2 * wave;
-            rb[base / 32 + w] = (uint32_t)m;
-            rb[base / 32 + w + 1] = (uint32_t)(m >> 32);
-            wc[w] = __popc((uint32_t)m);
-            wc[w + 1] = __popc((uint32_t)(m >> 32));
-        }
-    }
-    __syncthreads();
-    const int t = threadIdx.x;
-    const uint32_t own = wc[t];
-    for (int d = 1; d < 256; d <<= 1) {     // inclusive scan of the 256 word counts
-        const uint32_t add = t >= d ? wc[t - d] : 0u;
-        __syncthreads();
-        wc[t] += add;
-        __syncthreads();
-    }
-    wr[base / 32 + t] = wc[t] - own;
-    if (t == 255) cc[blockIdx.x] = wc[255];
+    rank_flatten(L, n, RankTables{rb, wr, cc, nullptr}, [](uint64_t) { return true; });
 }
 
-// ---- k_cc_scan: one workgroup, exclusive scan of the chunk counts, K -----------------------------------------------------------
-__global__ __launch_bounds__(kScanThreads) void k_cc_scan(const uint32_t* __restrict__ cc, uint32_t* __restrict__ co, uint64_t chunks,
-                                                          uint32_t* __restrict__ count) {
-    __shared__ uint32_t s[kScanThreads];
-    const int t = threadIdx.x;
-    const uint64_t per = (chunks + kScanThreads - 1) / kScanThreads;
-    const uint64_t lo = std::min<uint64_t>(chunks, per * t), hi = std::min<uint64_t>(chunks, lo + per);
-    uint32_t sum = 0;
-    for (uint64_t i = lo; i < hi; ++i) sum += cc[i];
-    s[t] = sum;
-    __syncthreads();
-    for (int d = 1; d < kScanThreads; d <<= 1) {
-        const uint32_t add = t >= d ? s[t - d] : 0u;
-        __syncthreads();
-        s[t] += add;
-        __syncthreads();
-    }
-    uint32_t run = s[t] - sum;
-    for (uint64_t i = lo; i < hi; ++i) { const uint32_t c = cc[i]; co[i] = run; run += c; }
-    if (t == kScanThreads - 1) *count = s[t];
+__global__ __launch_bounds__(kRankScanThreads) void k_cc_scan(const uint32_t* __restrict__ cc, uint32_t* __restrict__ co,
+                                                              uint64_t chunks, uint32_t* __restrict__ count) {
+    rank_scan(cc, co, chunks, count);
 }
 
-// ---- k_cc_relabel -------------------------------------------------------------------------------------------------------------
 // Reads only the voxel's own label (its root r) and the rank tables, so rewriting labels in place races with nothing.
 __global__ __launch_bounds__(256) void k_cc_relabel(uint32_t* __restrict__ L, uint64_t n, const uint32_t* __restrict__ rb,
                                                     const uint32_t* __restrict__ wr, const uint32_t* __restrict__ co) {
@@ -297,8 +204,7 @@ __global__ __launch_bounds__(256) void k_cc_relabel(uint32_t* __restrict__ L, ui
     for (int j = 0; j < kRelabelPerThread; ++j) {
         const uint64_t v = base + (uint64_t)j * 256;
         if (v >= n) return;
-        const uint32_t r = L[v], w = r >> 5;
-        L[v] = co[w / (kCcChunk / 32)] + wr[w] + (uint32_t)__popc(rb[w] & ((1u << (r & 31)) - 1u)) + 1u;
+        L[v] = rank_of(L[v], rb, wr, co);
     }
 }
 
@@ -323,9 +229,13 @@ CcPlan cc_plan(int64_t nx, int64_t ny, int64_t nz) {
     p.nty = (ny + p.ty - 1) / p.ty;
     p.ntz = (nz + p.tz - 1) / p.tz;
     p.n = (uint64_t)nx * (uint64_t)ny * (uint64_t)nz;
-    p.chunks = (p.n + kCcChunk - 1) / kCcChunk;
-    p.scratch_bytes = (size_t)(2 * p.chunks * (kCcChunk / 32) + 2 * p.chunks + 4) * 4;
+    p.chunks = rank_chunks(p.n);
+    p.scratch_bytes = rank_tables_bytes(p.chunks) + 4 * 4;     // K and three spare words
     return p;
+}
+
+uint32_t* cc_count_word(const CcPlan& p, void* d_scratch) {
+    return reinterpret_cast<uint32_t*>(static_cast<char*>(d_scratch) + rank_tables_bytes(p.chunks));
 }
 
 hipError_t cc_launch(const CcPlan& p, const uint32_t* d_bits, uint32_t* d_labels, void* d_scratch, hipStream_t s) {
@@ -337,17 +247,14 @@ hipError_t cc_launch(const CcPlan& p, const uint32_t* d_bits, uint32_t* d_labels
     a.nty = p.nty; a.ntz = p.ntz;
     a.nwords = (p.n + 31) / 32;
     const uint64_t tiles = (uint64_t)p.ntx * (uint64_t)p.nty * (uint64_t)p.ntz;
-    uint32_t* rb = static_cast<uint32_t*>(d_scratch);
-    uint32_t* wr = rb + p.chunks * (kCcChunk / 32);
-    uint32_t* cc = wr + p.chunks * (kCcChunk / 32);
-    uint32_t* co = cc + p.chunks;
+    const RankTables t = rank_tables_at(d_scratch, p.chunks);
     hipLaunchKernelGGL(k_cc_local, dim3((unsigned)tiles), dim3(kLocalThreads), 0, s, a);
     if (tiles > 1) hipLaunchKernelGGL(k_cc_merge, dim3((unsigned)tiles), dim3(kMergeThreads), 0, s, a);
-    hipLaunchKernelGGL(k_cc_flatten, dim3((unsigned)p.chunks), dim3(256), 0, s, d_labels, p.n, rb, wr, cc);
-    hipLaunchKernelGGL(k_cc_scan, dim3(1), dim3(kScanThreads), 0, s, (const uint32_t*)cc, co, p.chunks, cc_count_word(p, d_scratch));
+    hipLaunchKernelGGL(k_cc_flatten, dim3((unsigned)p.chunks), dim3(256), 0, s, d_labels, p.n, t.rb, t.wr, t.cc);
+    hipLaunchKernelGGL(k_cc_scan, dim3(1), dim3(kRankScanThreads), 0, s, (const uint32_t*)t.cc, t.co, p.chunks, cc_count_word(p, d_scratch));
     const uint64_t rblocks = (p.n + 256 * kRelabelPerThread - 1) / (256 * kRelabelPerThread);
-    hipLaunchKernelGGL(k_cc_relabel, dim3((unsigned)rblocks), dim3(256), 0, s, d_labels, p.n, (const uint32_t*)rb,
-                       (const uint32_t*)wr, (const uint32_t*)co);
+    hipLaunchKernelGGL(k_cc_relabel, dim3((unsigned)rblocks), dim3(256), 0, s, d_labels, p.n, (const uint32_t*)t.rb,
+                       (const uint32_t*)t.wr, (const uint32_t*)t.co);
     return hipGetLastError();
 }
 

@@ -7,10 +7,11 @@
 // x -> y -> z scan meets a component first at that voxel).  Four launches plus a one-block scan:
 //   k_cc_local    one workgroup per tile (tx x ty x tz voxels, at most 16384): z runs from the bit words, union-find in LDS on
 //                 the y / x faces inside the tile, provisional label = global index of the tile-local minimum
-//   k_cc_merge    the tile faces: global union-find on the label words (agent-scope loads + atomicMin, larger root under smaller)
+//   k_cc_merge    the tile faces: global union-find on the label words (sdfgpu_unionfind.hpp: larger root under smaller)
 //   k_cc_flatten  every label -> its root (= the component's minimum index); root flags as bits, per-word ranks inside a chunk
 //   k_cc_scan     exclusive scan of the chunk counts (one workgroup) and K
 //   k_cc_relabel  label = rank of its root among the roots + 1
+// (the last three are the root ranking of sdfgpu_unionfind.hpp, which also lays out its tables in the scratch)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -18,25 +19,22 @@
 namespace sdfgpu {
 
 constexpr int kCcTileVoxels = 16384;    // LDS labels of one k_cc_local tile (64 KiB)
-constexpr int kCcChunk = 8192;          // voxels per k_cc_flatten / k_cc_relabel chunk (256 root-flag words)
 
 struct CcPlan {
     int64_t nx = 0, ny = 0, nz = 0;     // the grid with singleton axes moved to the front (same linear layout, same adjacency)
     int tx = 0, ty = 0, tz = 0;         // tile extents; tz a multiple of 32
     int64_t ntx = 0, nty = 0, ntz = 0;  // tiles per axis
     uint64_t n = 0;                     // voxels (< 2^32)
-    uint64_t chunks = 0;                // ceil(n / kCcChunk)
-    size_t scratch_bytes = 0;           // root bits + word ranks (chunks * 256 words each) + chunk counts + offsets + K
+    uint64_t chunks = 0;                // k_cc_flatten's chunks of 8192 voxels (kRankChunk, sdfgpu_unionfind.hpp)
+    size_t scratch_bytes = 0;           // the rank tables of `chunks` chunks (root bits, word ranks, chunk counts, offsets) + K
 };
 
 // nx, ny, nz: positive, nx * ny * nz < 2^32 (checked by the caller)
 CcPlan cc_plan(int64_t nx, int64_t ny, int64_t nz);
 
 // d_bits: ceil(n / 32) words; d_labels: n words; d_scratch: plan.scratch_bytes, 4-byte aligned.  Enqueued on `s`; K lands in
-// the last word of the scratch (cc_count_word).
+// the word behind the rank tables (cc_count_word).
 hipError_t cc_launch(const CcPlan& p, const uint32_t* d_bits, uint32_t* d_labels, void* d_scratch, hipStream_t s);
-inline uint32_t* cc_count_word(const CcPlan& p, void* d_scratch) {
-    return static_cast<uint32_t*>(d_scratch) + 2 * p.chunks * (kCcChunk / 32) + 2 * p.chunks;
-}
+uint32_t* cc_count_word(const CcPlan& p, void* d_scratch);
 
 }  // namespace sdfgpu

@@ -12,6 +12,7 @@
 #include "sdfgpu_kernels.hpp"
 #include "sdfgpu_context.hpp"
 #include "sdfgpu_convex.hpp"
+#include "sdfgpu_unionfind.hpp"
 #include "sdfgpu.h"
 
 #include <algorithm>
@@ -21,7 +22,6 @@ namespace sdfgpu {
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kScanThreads = 1024;
 // The doubling state of an unresolved node is (p_k(v) << 32) | m_k(v), m_k(v) < n <= 2^32 - 3 (check_convex_args): an index must
 // never equal one of the three markers below, or an open state would read as resolved.  A resolved node's low word is
 // a marker, its high word the answer: kResTerm -> the terminal (a fixed point, or kCxOff), kResCycle -> the cycle's minimum index;
@@ -253,34 +253,8 @@ __device__ __forceinline__ bool joined(uint64_t ka, uint64_t kb, const SegGeom& 
     return __dsqrt_rn(s) < g.thr;
 }
 
-// Union-find invariant as in sdfgpu_components.hip: a label only decreases and never exceeds its own index, so every parent chain
-// ends and a segment's root is its minimum index -- the cell at which the reference's scan starts it.
-__device__ __forceinline__ uint32_t ld_agent(uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ uint32_t min_agent(uint32_t* p, uint32_t v) {
-    return __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ uint32_t g_find(uint32_t* L, uint32_t a) {
-    for (;;) {
-        const uint32_t p = ld_agent(&L[a]);
-        if (p == a) return a;
-        const uint32_t gp = ld_agent(&L[p]);
-        if (gp == p) return p;
-        (void)min_agent(&L[a], gp);
-        a = gp;
-    }
-}
-__device__ __forceinline__ void g_union(uint32_t* L, uint32_t a, uint32_t b) {
-    for (;;) {
-        a = g_find(L, a);
-        b = g_find(L, b);
-        if (a == b) return;
-        if (a < b) { const uint32_t t = a; a = b; b = t; }
-        const uint32_t old = min_agent(&L[a], b);
-        if (old == a) return;
-        a = old;
-    }
-}
-
+// The union-find over the label words is sdfgpu_unionfind.hpp's (a root's word is its own index): a segment's root is its minimum
+// index -- the cell at which the reference's scan starts it.
 // L[v] = the first voxel of v's run of joined z neighbours inside v's wave (64 consecutive indices): chains of depth <= 1
 __global__ __launch_bounds__(kThreads) void k_cx_uf_init(const uint64_t* __restrict__ key, uint64_t n, const SegGeom g,
                                                          uint32_t* __restrict__ L) {
@@ -305,13 +279,13 @@ __global__ __launch_bounds__(kThreads) void k_cx_uf_link(const uint64_t* __restr
     const uint64_t nz = (uint64_t)g.nz, plane = (uint64_t)g.ny * nz;
     const uint64_t z = v % nz, y = (v / nz) % (uint64_t)g.ny;
     const bool zj = z > 0 && joined(kv, key[v - 1], g);
-    if (zj && (v & 63) == 0) g_union(L, (uint32_t)v, (uint32_t)(v - 1));
+    if (zj && (v & 63) == 0) uf_union<RootIsSelf>(L, (uint32_t)v, (uint32_t)(v - 1));
     if (y > 0) {
         const uint64_t u = v - nz;
         const uint64_t ku = key[u];
         if (joined(kv, ku, g)) {
             const bool square = zj && joined(ku, key[u - 1], g) && joined(key[v - 1], key[u - 1], g);
-            if (!square) g_union(L, (uint32_t)v, (uint32_t)u);
+            if (!square) uf_union<RootIsSelf>(L, (uint32_t)v, (uint32_t)u);
         }
     }
     if (v >= plane) {
@@ -319,72 +293,20 @@ __global__ __launch_bounds__(kThreads) void k_cx_uf_link(const uint64_t* __restr
         const uint64_t ku = key[u];
         if (joined(kv, ku, g)) {
             const bool square = zj && joined(ku, key[u - 1], g) && joined(key[v - 1], key[u - 1], g);
-            if (!square) g_union(L, (uint32_t)v, (uint32_t)u);
+            if (!square) uf_union<RootIsSelf>(L, (uint32_t)v, (uint32_t)u);
         }
     }
 }
 
-// As k_cc_flatten, with root = a taking-part voxel that is its own label.  rb: root flags; wr: roots in the chunk's words before
-// w; cc: roots in the chunk.
+// The root ranking of sdfgpu_unionfind.hpp, with root = a taking-part voxel that is its own label; 0 for cells that take no part.
 __global__ __launch_bounds__(256) void k_cx_flatten(uint32_t* __restrict__ L, const uint64_t* __restrict__ key, uint64_t n,
                                                     uint32_t* __restrict__ rb, uint32_t* __restrict__ wr, uint32_t* __restrict__ cc) {
-    __shared__ uint32_t wc[kCxChunk / 32];
-    const uint64_t base = (uint64_t)blockIdx.x * kCxChunk;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int j = 0; j < kCxChunk / 256; ++j) {
-        const uint64_t v = base + (uint64_t)j * 256 + threadIdx.x;
-        bool root = false;
-        if (v < n) {
-            const uint32_t r = L[v];
-            if (r == (uint32_t)v) {
-                root = lo32(key[v]) != kCxOff;
-            } else {
-                uint32_t q = r, p = L[q];
-                while (p != q) { q = p; p = L[q]; }
-                if (q != r) L[v] = q;
-            }
-        }
-        const uint64_t m = __ballot(root);
-        if (lane == 0) {
-            const int w = j * 8 + 2 * wave;
-            rb[base / 32 + w] = (uint32_t)m;
-            rb[base / 32 + w + 1] = (uint32_t)(m >> 32);
-            wc[w] = __popc((uint32_t)m);
-            wc[w + 1] = __popc((uint32_t)(m >> 32));
-        }
-    }
-    __syncthreads();
-    const int t = threadIdx.x;
-    const uint32_t own = wc[t];
-    for (int d = 1; d < 256; d <<= 1) {
-        const uint32_t add = t >= d ? wc[t - d] : 0u;
-        __syncthreads();
-        wc[t] += add;
-        __syncthreads();
-    }
-    wr[base / 32 + t] = wc[t] - own;
-    if (t == 255) cc[blockIdx.x] = wc[255];
+    rank_flatten(L, n, RankTables{rb, wr, cc, nullptr}, [key](uint64_t v) { return lo32(key[v]) != kCxOff; });
 }
 
-__global__ __launch_bounds__(kScanThreads) void k_cx_scan(const uint32_t* __restrict__ cc, uint32_t* __restrict__ co, uint64_t chunks,
-                                                          uint32_t* __restrict__ count) {
-    __shared__ uint32_t s[kScanThreads];
-    const int t = threadIdx.x;
-    const uint64_t per = (chunks + kScanThreads - 1) / kScanThreads;
-    const uint64_t lo = std::min<uint64_t>(chunks, per * t), hi = std::min<uint64_t>(chunks, lo + per);
-    uint32_t sum = 0;
-    for (uint64_t i = lo; i < hi; ++i) sum += cc[i];
-    s[t] = sum;
-    __syncthreads();
-    for (int d = 1; d < kScanThreads; d <<= 1) {
-        const uint32_t add = t >= d ? s[t - d] : 0u;
-        __syncthreads();
-        s[t] += add;
-        __syncthreads();
-    }
-    uint32_t run = s[t] - sum;
-    for (uint64_t i = lo; i < hi; ++i) { const uint32_t c = cc[i]; co[i] = run; run += c; }
-    if (t == kScanThreads - 1) *count = s[t];
+__global__ __launch_bounds__(kRankScanThreads) void k_cx_scan(const uint32_t* __restrict__ cc, uint32_t* __restrict__ co,
+                                                              uint64_t chunks, uint32_t* __restrict__ count) {
+    rank_scan(cc, co, chunks, count);
 }
 
 __global__ __launch_bounds__(256) void k_cx_relabel(uint32_t* __restrict__ L, const uint64_t* __restrict__ key, uint64_t n,
@@ -393,8 +315,7 @@ __global__ __launch_bounds__(256) void k_cx_relabel(uint32_t* __restrict__ L, co
     const uint64_t v = lane_index();
     if (v >= n) return;
     if (lo32(key[v]) == kCxOff) { L[v] = 0u; return; }
-    const uint32_t r = L[v], w = r >> 5;
-    L[v] = co[w / (kCxChunk / 32)] + wr[w] + (uint32_t)__popc(rb[w] & ((1u << (r & 31)) - 1u)) + 1u;
+    L[v] = rank_of(L[v], rb, wr, co);
 }
 
 __global__ __launch_bounds__(kThreads) void k_cx_combine(float* __restrict__ fr, const float* __restrict__ nm, uint64_t n) {
@@ -415,15 +336,12 @@ CxPlan cx_plan(int64_t nx, int64_t ny, int64_t nz) {
     CxPlan p;
     p.nx = nx; p.ny = ny; p.nz = nz;
     p.n = (uint64_t)nx * (uint64_t)ny * (uint64_t)nz;
-    p.chunks = (p.n + kCxChunk - 1) / kCxChunk;
+    p.chunks = rank_chunks(p.n);
     p.off_b = p.n * 8;
     p.off_next = 2 * p.n * 8;
     p.off_stats = (p.off_next + p.n * 4 + 7) & ~(size_t)7;
-    p.off_rb = p.off_stats + ((sizeof(CxStats) + 7) & ~(size_t)7);
-    p.off_wr = p.off_rb + p.chunks * (kCxChunk / 32) * 4;
-    p.off_cc = p.off_wr + p.chunks * (kCxChunk / 32) * 4;
-    p.off_co = p.off_cc + p.chunks * 4;
-    p.scratch_bytes = p.off_co + p.chunks * 4;
+    p.off_ranks = p.off_stats + ((sizeof(CxStats) + 7) & ~(size_t)7);
+    p.scratch_bytes = p.off_ranks + rank_tables_bytes(p.chunks);
     return p;
 }
 
@@ -472,20 +390,17 @@ hipError_t cx_segments(const CxPlan& p, const uint32_t* d_ext, const char* d_cel
     char* base = static_cast<char*>(d_scratch);
     uint64_t* key = reinterpret_cast<uint64_t*>(base);
     CxStats* st = reinterpret_cast<CxStats*>(base + p.off_stats);
-    uint32_t* rb = reinterpret_cast<uint32_t*>(base + p.off_rb);
-    uint32_t* wr = reinterpret_cast<uint32_t*>(base + p.off_wr);
-    uint32_t* cc = reinterpret_cast<uint32_t*>(base + p.off_cc);
-    uint32_t* co = reinterpret_cast<uint32_t*>(base + p.off_co);
+    const RankTables t = rank_tables_at(base + p.off_ranks, p.chunks);
     const dim3 nb = lanes(p.n);
     SegGeom g{p.ny, p.nz, res, threshold};
     hipLaunchKernelGGL(k_cx_key, nb, dim3(kThreads), 0, s, d_ext, d_cells, (uint64_t)stride, (uint64_t)occ_off, (uint64_t)obj_off,
                        p.n, key);
     hipLaunchKernelGGL(k_cx_uf_init, nb, dim3(kThreads), 0, s, (const uint64_t*)key, p.n, g, d_labels);
     hipLaunchKernelGGL(k_cx_uf_link, nb, dim3(kThreads), 0, s, (const uint64_t*)key, p.n, g, d_labels);
-    hipLaunchKernelGGL(k_cx_flatten, dim3((unsigned)p.chunks), dim3(256), 0, s, d_labels, (const uint64_t*)key, p.n, rb, wr, cc);
-    hipLaunchKernelGGL(k_cx_scan, dim3(1), dim3(kScanThreads), 0, s, (const uint32_t*)cc, co, p.chunks, st->count);
-    hipLaunchKernelGGL(k_cx_relabel, nb, dim3(256), 0, s, d_labels, (const uint64_t*)key, p.n, (const uint32_t*)rb,
-                       (const uint32_t*)wr, (const uint32_t*)co);
+    hipLaunchKernelGGL(k_cx_flatten, dim3((unsigned)p.chunks), dim3(256), 0, s, d_labels, (const uint64_t*)key, p.n, t.rb, t.wr, t.cc);
+    hipLaunchKernelGGL(k_cx_scan, dim3(1), dim3(kRankScanThreads), 0, s, (const uint32_t*)t.cc, t.co, p.chunks, st->count);
+    hipLaunchKernelGGL(k_cx_relabel, nb, dim3(256), 0, s, d_labels, (const uint64_t*)key, p.n, (const uint32_t*)t.rb,
+                       (const uint32_t*)t.wr, (const uint32_t*)t.co);
     return hipGetLastError();
 }
 

@@ -17,8 +17,9 @@
 // Segments:
 //   k_cx_key      per voxel (object id, extremum or kCxOff when the cell does not take part)
 //   k_cx_uf_init  union-find labels: the start of the voxel's run of joined z neighbours inside its wave
-//   k_cx_uf_link  global union-find over the remaining joined face pairs (agent-scope loads, atomicMin, as k_cc_merge)
-//   k_cx_flatten / k_cx_scan / k_cx_relabel   roots of taking-part cells -> 1..K in scan order, everything else 0
+//   k_cx_uf_link  global union-find over the remaining joined face pairs (sdfgpu_unionfind.hpp, as k_cc_merge)
+//   k_cx_flatten / k_cx_scan / k_cx_relabel   roots of taking-part cells -> 1..K in scan order, everything else 0 (the root
+//                 ranking of sdfgpu_unionfind.hpp)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -26,7 +27,6 @@
 namespace sdfgpu {
 
 constexpr uint32_t kCxOff = 0xFFFFFFFFu;       // "the walk leaves the grid"; also the extremum index of such a voxel
-constexpr int kCxChunk = 8192;                 // voxels per k_cx_flatten / k_cx_relabel chunk (256 root-flag words)
 constexpr int kCxMaxRounds = 40;               // > ceil(log2(2^32)) + 1
 
 struct CxRot {
@@ -55,10 +55,10 @@ inline uint32_t cx_row_sum(const uint32_t* row) {
 struct CxPlan {
     int64_t nx = 0, ny = 0, nz = 0;
     uint64_t n = 0;                            // voxels (<= 2^32 - 3: indices stay below the doubling markers)
-    uint64_t chunks = 0;                       // ceil(n / kCxChunk)
-    // scratch layout (bytes): A u64 [n] | B u64 [n] | next u32 [n] | pad | stats | root bits u32 [chunks * 256] | word ranks
-    // u32 [chunks * 256] | chunk counts u32 [chunks] | chunk offsets u32 [chunks]
-    size_t off_b = 0, off_next = 0, off_stats = 0, off_rb = 0, off_wr = 0, off_cc = 0, off_co = 0;
+    uint64_t chunks = 0;                       // k_cx_flatten's chunks of 8192 voxels (kRankChunk, sdfgpu_unionfind.hpp)
+    // scratch layout (bytes): A u64 [n] | B u64 [n] | next u32 [n] | pad | stats | the rank tables of `chunks` chunks (root bits
+    // u32 [chunks * 256] | word ranks u32 [chunks * 256] | chunk counts u32 [chunks] | chunk offsets u32 [chunks])
+    size_t off_b = 0, off_next = 0, off_stats = 0, off_ranks = 0;
     size_t scratch_bytes = 0;
 };
 

@@ -3,11 +3,11 @@
 // The family's host orchestration and C ABI entry points (sdfgpu_component_topology*) are at the end of this file, over the handle of
 // sdfgpu_context.hpp.
 //
-// Union-find invariant (the same as sdfgpu_components.hip's): a node word holds kRoot (the node is a root) or a node id BELOW
-// its own, and only ever decreases (a link stores a smaller root into a larger one with atomicMin).  Every parent chain is
-// strictly decreasing until it meets a root, so every find ends, and a surface's root is its smallest node id.
+// The union-find over the node words is sdfgpu_unionfind.hpp's, with its invariant and memory scope: a node word holds kRoot (the
+// node is a root) or a node id BELOW its own, so a surface's root is its smallest node id.
 #include "sdfgpu_context.hpp"
 #include "sdfgpu_topology.hpp"
+#include "sdfgpu_unionfind.hpp"
 #include "sdfgpu.h"
 
 #include <algorithm>
@@ -19,9 +19,9 @@ namespace {
 constexpr int kVertexThreads = 256;
 constexpr int kTableSlots = 1024;              // k_tp_vertex's LDS table of per-label counts (open addressing)
 constexpr int kTableProbes = 16;               // (a label that finds no slot goes straight to the global counters)
-constexpr int kScanThreads = 1024;
 constexpr uint32_t kOut = 0xFFFFFFFFu;         // label of an out-of-grid voxel (a real label is <= max_label < 2^32 - 1)
 constexpr uint32_t kRoot = 0xFFFFFFFFu;        // node word of a root (node ids are < 2^32 - 1)
+using NodeRoot = RootIsSentinel<kRoot>;
 
 struct TpArgs {
     const uint32_t* L;                         // labels
@@ -244,58 +244,10 @@ __global__ __launch_bounds__(kVertexThreads) void k_tp_vertex(const TpArgs a) {
 }
 
 // ---- k_tp_scan: one workgroup, exclusive scan of the chunk counts; the node total goes to the status -------------------------
-__global__ __launch_bounds__(kScanThreads) void k_tp_scan(const uint32_t* __restrict__ cc, uint32_t* __restrict__ co, uint64_t chunks,
-                                                          TpStatus* __restrict__ st) {
-    __shared__ uint64_t s[kScanThreads];
-    const int t = threadIdx.x;
-    const uint64_t per = (chunks + kScanThreads - 1) / kScanThreads;
-    const uint64_t lo = std::min<uint64_t>(chunks, per * t), hi = std::min<uint64_t>(chunks, lo + per);
-    uint64_t sum = 0;
-    for (uint64_t i = lo; i < hi; ++i) sum += cc[i];
-    s[t] = sum;
-    __syncthreads();
-    for (int d = 1; d < kScanThreads; d <<= 1) {
-        const uint64_t add = t >= d ? s[t - d] : 0u;
-        __syncthreads();
-        s[t] += add;
-        __syncthreads();
-    }
-    uint64_t r = s[t] - sum;
-    for (uint64_t i = lo; i < hi; ++i) { co[i] = (uint32_t)r; r += cc[i]; }     // (only used when the total fits in 32 bits)
-    if (t == kScanThreads - 1) st->nodes = s[t];
-}
-
-// ---- global union-find over the node words --------------------------------------------------------------------------------------
-// Other workgroups, on other XCDs, link roots while this one walks: every read of a node word is an agent-scope load and every
-// write an agent-scope atomic (sdfgpu_components.hip).
-__device__ __forceinline__ uint32_t ld_agent(uint32_t* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ uint32_t min_agent(uint32_t* p, uint32_t v) {
-    return __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ uint32_t g_find(uint32_t* P, uint32_t a) {
-    for (;;) {
-        const uint32_t p = ld_agent(&P[a]);
-        if (p == kRoot) return a;
-        const uint32_t gp = ld_agent(&P[p]);
-        if (gp == kRoot) return p;
-        (void)min_agent(&P[a], gp);                         // path halving (monotone, stays in the surface)
-        a = gp;
-    }
-}
-
-__device__ __forceinline__ void g_union(uint32_t* P, uint32_t a, uint32_t b) {
-    for (;;) {
-        a = g_find(P, a);
-        b = g_find(P, b);
-        if (a == b) return;
-        if (a < b) { const uint32_t t = a; a = b; b = t; }
-        const uint32_t old = min_agent(&P[a], b);
-        if (old == kRoot) return;
-        a = old;                                            // a had been linked meanwhile (old < a): join its new root instead
-    }
+// (the scan of sdfgpu_unionfind.hpp with a 64-bit sum: co is only used when the total fits in 32 bits)
+__global__ __launch_bounds__(kRankScanThreads) void k_tp_scan(const uint32_t* __restrict__ cc, uint32_t* __restrict__ co,
+                                                              uint64_t chunks, TpStatus* __restrict__ st) {
+    rank_scan(cc, co, chunks, &st->nodes);
 }
 
 // Joins the nodes of vertex v (cube lab, node byte nmv, ids from base) with the nodes of vertex v + step along axis AX
@@ -336,7 +288,7 @@ __device__ __forceinline__ void link_axis(const TpArgs& a, int64_t i, int64_t j,
         // the far vertex's cube shares the exposed edge's 4 voxels, so it holds c; its node exists unless a label is both selected
         // and unselected (refused before this kernel runs) -- checked anyway
         if (t < 0 || !((nmw >> t) & 1u)) continue;
-        g_union(a.P, base + (uint32_t)__popc(nmv & ((1u << s) - 1u)), wbase + (uint32_t)__popc(nmw & ((1u << t) - 1u)));
+        uf_union<NodeRoot>(a.P, base + (uint32_t)__popc(nmv & ((1u << s) - 1u)), wbase + (uint32_t)__popc(nmw & ((1u << t) - 1u)));
     }
 }
 
@@ -424,7 +376,7 @@ hipError_t tp_launch_count(const TpPlan& p, const uint32_t* d_labels, const uint
     hipError_t e = hipMemsetAsync(d_scratch, 0, p.zero_bytes, s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_tp_vertex, dim3((unsigned)p.chunks), dim3(kVertexThreads), 0, s, a);
-    hipLaunchKernelGGL(k_tp_scan, dim3(1), dim3(kScanThreads), 0, s, (const uint32_t*)a.cc, a.co, p.chunks, a.st);
+    hipLaunchKernelGGL(k_tp_scan, dim3(1), dim3(kRankScanThreads), 0, s, (const uint32_t*)a.cc, a.co, p.chunks, a.st);
     return hipGetLastError();
 }
 

@@ -10,10 +10,10 @@
 //                wave, then in a per-workgroup LDS table (one global atomic per label and workgroup: a room's free space or a
 //                percolating Bernoulli component is one label for most of the grid); the label / selection checks; the node
 //                bytes' running counts inside the workgroup's chunk of kTpChunk vertices
-//   k_tp_scan    exclusive scan of the chunk counts (one workgroup) and the node total (uint64)
+//   k_tp_scan    exclusive scan of the chunk counts (one workgroup) and the node total (uint64): sdfgpu_unionfind.hpp's scan
 //   -- the host reads the total and the error words, refuses, sizes the node buffer --
 //   k_tp_link    one lane per vertex: every exposed +x / +y / +z edge of a node joins it with the node of the same label at the
-//                far vertex (global union-find: agent-scope loads, atomicMin, larger root under smaller)
+//                far vertex (the global union-find of sdfgpu_unionfind.hpp, a root's word being 0xFFFFFFFF)
 //   k_tp_roots   per-label count of the union-find roots = surfaces
 // Node id of (v, slot s) = co[chunk] + gb[v / 8] + popcount of the node bits of vertices 8 (v / 8) .. v - 1 and of v's bits below s.
 #pragma once

@@ -88,8 +88,21 @@ def test_odd_shapes(gpu, shape, p):
     _all_entry_points(gpu, occ)
 
 
-@pytest.mark.parametrize("shape", [(64, 64, 64), (200, 130, 97)])
-@pytest.mark.parametrize("p", [0.02, 0.3116, 0.5, 0.98])
+# (129, 256, 255): 8 421 120 voxels in 1028 ranking chunks of 8192, the last one partial.  k_cc_scan's 1024 threads then take two
+# chunk counts each, the threads from 514 on none, and the rank of a root adds up chunk offsets across many chunk boundaries; every
+# other shape of this file has at most 1024 chunks (one count per thread or none) or a whole number of counts per thread.
+BERNOULLI = [
+    ((64, 64, 64), 0.02), ((200, 130, 97), 0.02),
+    ((64, 64, 64), 0.3116), ((200, 130, 97), 0.3116),
+    ((64, 64, 64), 0.5), ((200, 130, 97), 0.5),
+    ((64, 64, 64), 0.98), ((200, 130, 97), 0.98),
+    ((129, 256, 255), 0.5),
+]
+BERNOULLI_IDS = ["0.02-shape0", "0.02-shape1", "0.3116-shape0", "0.3116-shape1", "0.5-shape0", "0.5-shape1", "0.98-shape0", "0.98-shape1",
+                 "0.5-shape2"]       # (the ids the two stacked parametrize marks gave the first eight)
+
+
+@pytest.mark.parametrize("shape, p", BERNOULLI, ids=BERNOULLI_IDS)
 def test_bernoulli(gpu, shape, p):
     m = synth.bernoulli_mask(shape, p, 11)
     _all_entry_points(gpu, m.astype(np.float32))
