@@ -380,6 +380,98 @@ public:
         return std::make_pair(device.first.Host(), device.second);
     }
 
+    // ---- frontier cells (additions; include/sdfgpu.h "Frontier cells") ----------------------------------------------------
+    // Where seen-free space ends in never-seen space: a frontier cell is a cell of a live chunk that is free (occupancy < 0.5) and
+    // has an unknown neighbour (occupancy == 0.5) among its 6 face neighbours, or among all 26 with use_26.  Neighbours are read
+    // wherever they lie (an absent chunk reads as the default); a window or a box only restricts which cells are candidates.
+    // A refusal of the library (a window of more than 2^32 - 1 cells, cell counts below 1) is std::invalid_argument.
+    //
+    // The frontier cells of the whole map as global cell indices (the coordinates of the window extractions' lower_index), chunks in
+    // ascending (c_x, c_y, c_z) order and cells x -> y -> z inside a chunk.
+    std::vector<VoxelGrid::GRID_INDEX> ExtractFrontierCells(const bool use_26 = false) const { return FrontierCells(nullptr, nullptr, use_26); }
+    // ... among the nx x ny x nz cells from global cell lower_index on
+    std::vector<VoxelGrid::GRID_INDEX> ExtractFrontierCells(const VoxelGrid::GRID_INDEX& lower_index, const int64_t nx, const int64_t ny, const int64_t nz,
+                                                            const bool use_26 = false) const {
+        const int64_t lower[3] = {lower_index.x, lower_index.y, lower_index.z}, extent[3] = {nx, ny, nz};
+        return FrontierCells(lower, extent, use_26);
+    }
+    // The frontier cells of a window as the bit field of sdfgpu_build_bits_device: bit (x ny + y) nz + z is set iff global cell
+    // lower_index + (x, y, z) is a frontier cell; ceil(nx ny nz / 32) words.  (A caller that keeps going on the device calls
+    // sdfgpu_dsh_frontier_window_device on DeviceMapHandle() itself, as ExtractFrontierClusters does.)
+    std::vector<uint32_t> ExtractFrontierWindowBits(const VoxelGrid::GRID_INDEX& lower_index, const int64_t nx, const int64_t ny, const int64_t nz,
+                                                    const bool use_26 = false) const {
+        RequireInitialized();
+        const int64_t lower[3] = {lower_index.x, lower_index.y, lower_index.z};
+        if (!WindowCountsOk(nx, ny, nz)) throw std::invalid_argument("ExtractFrontierWindowBits: cell counts must be positive and span at most 2^32 - 1 cells");
+        std::vector<uint32_t> bits((size_t)((nx * ny * nz + 31) / 32));
+        Locked([&](sdfgpu_dsh_map m) { return sdfgpu_dsh_frontier_window(m, lower, nx, ny, nz, FrontierFlags(use_26), bits.data()); });
+        return bits;
+    }
+    // One connected piece of a window's frontier.  Pieces are 6-connected components of the window's frontier cells, which is what
+    // the project's components are (sdfgpu_components_bits_device), whichever rule found the cells: under the 6-rule a frontier
+    // tends to fall apart along the diagonal steps of a surface, which is why use_26 defaults to true here.
+    struct FrontierCluster {
+        uint32_t label;                       // of sdfgpu_components_bits_device on the window's frontier bits
+        int64_t cells;
+        VoxelGrid::GRID_INDEX lower, upper;   // bounding box in global cells, inclusive
+        Eigen::Vector3d centroid;             // the mean of the cells' centres in world coordinates, in double on the host:
+                                              // g_a = ((double)lower_index_a + ((double)sum_a / (double)cells + 0.5)) * resolution, sum_a the sum of the
+                                              // cells' window coordinates along a; centroid = origin_transform * (g_x, g_y, g_z)
+    };
+    // The clusters of at least min_cells cells among the frontier cells of a window, in label order: window bits -> components ->
+    // statistics on the device; nothing but the statistics records leaves it.
+    std::vector<FrontierCluster> ExtractFrontierClusters(const VoxelGrid::GRID_INDEX& lower_index, const int64_t nx, const int64_t ny, const int64_t nz,
+                                                         const int64_t min_cells = 1, const bool use_26 = true) const {
+        RequireInitialized();
+        if (!WindowCountsOk(nx, ny, nz)) throw std::invalid_argument("ExtractFrontierClusters: cell counts must be positive and span at most 2^32 - 1 cells");
+        const int64_t lower[3] = {lower_index.x, lower_index.y, lower_index.z};
+        const size_t n = (size_t)(nx * ny * nz);
+        std::vector<sdfgpu_component_stats> stats;
+        int rc = SDFGPU_OK;
+        std::string message;
+        {
+            const std::lock_guard<std::mutex> lock(collision_field_->ctx->mutex);
+            sdfgpu_handle h = collision_field_->ctx->handle;
+            void *d_bits = nullptr, *d_labels = nullptr, *d_stats = nullptr;
+            uint32_t label_count = 0;
+            int64_t total = 0;
+            rc = sdfgpu_device_malloc(h, (n + 31) / 32 * 4, &d_bits);
+            if (rc == SDFGPU_OK) rc = sdfgpu_device_malloc(h, n * 4, &d_labels);
+            if (rc == SDFGPU_OK) rc = sdfgpu_dsh_frontier_window_device(collision_field_->map, lower, nx, ny, nz, FrontierFlags(use_26), static_cast<uint32_t*>(d_bits), nullptr);
+            if (rc == SDFGPU_OK) rc = sdfgpu_components_bits_device(h, static_cast<const uint32_t*>(d_bits), nx, ny, nz, static_cast<uint32_t*>(d_labels), &label_count, nullptr);
+            // (the number of records first: the labels of the window's other cells take none)
+            if (rc == SDFGPU_OK) rc = sdfgpu_component_stats_device(h, static_cast<const uint32_t*>(d_bits), static_cast<const uint32_t*>(d_labels), nx, ny, nz,
+                                                                    label_count, nullptr, 0, &total, nullptr);
+            if (rc == SDFGPU_OK && total > 0) {
+                stats.resize((size_t)total);
+                rc = sdfgpu_device_malloc(h, stats.size() * sizeof(sdfgpu_component_stats), &d_stats);
+                if (rc == SDFGPU_OK) rc = sdfgpu_component_stats_device(h, static_cast<const uint32_t*>(d_bits), static_cast<const uint32_t*>(d_labels), nx, ny, nz,
+                                                                        label_count, static_cast<sdfgpu_component_stats*>(d_stats), total, &total, nullptr);
+                if (rc == SDFGPU_OK) rc = sdfgpu_copy_to_host(h, stats.data(), d_stats, stats.size() * sizeof(sdfgpu_component_stats), nullptr);
+            }
+            if (rc != SDFGPU_OK) message = sdfgpu_last_error(h);
+            (void)sdfgpu_device_free(h, d_bits);
+            (void)sdfgpu_device_free(h, d_labels);
+            (void)sdfgpu_device_free(h, d_stats);
+        }
+        if (rc == SDFGPU_ERR_INVALID_ARGUMENT) throw std::invalid_argument("sdfgpu: " + message);
+        if (rc != SDFGPU_OK) throw std::runtime_error("sdfgpu: " + message);
+        std::vector<FrontierCluster> clusters;
+        for (const sdfgpu_component_stats& s : stats) {
+            if (s.count < min_cells) continue;
+            FrontierCluster cluster;
+            cluster.label = s.label;
+            cluster.cells = s.count;
+            cluster.lower = VoxelGrid::GRID_INDEX(lower[0] + s.lo[0], lower[1] + s.lo[1], lower[2] + s.lo[2]);
+            cluster.upper = VoxelGrid::GRID_INDEX(lower[0] + s.hi[0], lower[1] + s.hi[1], lower[2] + s.hi[2]);
+            double g[3];
+            for (int a = 0; a < 3; ++a) g[a] = ((double)lower[a] + ((double)s.sum[a] / (double)s.count + 0.5)) * resolution_;
+            cluster.centroid = origin_transform_ * Eigen::Vector3d(g[0], g[1], g[2]);
+            clusters.push_back(cluster);
+        }
+        return clusters;
+    }
+
     // ---- display (reference dynamic_spatial_hashed_collision_map.cpp:85-199) ---------------------------------------------------------------
     // 0, 1 or 2 markers: the chunk-filled chunks as cubes of the chunk's size at their centres, then the cells of the cell-filled
     // chunks as cubes of the cell's size; a marker without a point is left out.  Chunks in ascending (c_x, c_y, c_z) order (the
@@ -447,6 +539,22 @@ public:
     }
 
 private:
+    static uint32_t FrontierFlags(const bool use_26) { return use_26 ? (uint32_t)SDFGPU_DSH_FRONTIER_26 : 0u; }
+    // positive cell counts whose product is at most 2^32 - 1 (what the window calls take)
+    static bool WindowCountsOk(const int64_t nx, const int64_t ny, const int64_t nz) {
+        const int64_t most = 4294967295ll;
+        return nx > 0 && ny > 0 && nz > 0 && nx <= most && ny <= most / nx && nz <= most / (nx * ny);
+    }
+    std::vector<VoxelGrid::GRID_INDEX> FrontierCells(const int64_t* lower, const int64_t* extent, const bool use_26) const {
+        RequireInitialized();
+        int64_t total = 0;
+        Locked([&](sdfgpu_dsh_map m) { return sdfgpu_dsh_frontier_cells(m, lower, extent, FrontierFlags(use_26), nullptr, 0, &total); });
+        std::vector<int64_t> raw((size_t)total * 3);
+        if (total) Locked([&](sdfgpu_dsh_map m) { return sdfgpu_dsh_frontier_cells(m, lower, extent, FrontierFlags(use_26), raw.data(), total, &total); });
+        std::vector<VoxelGrid::GRID_INDEX> cells((size_t)total);
+        for (size_t i = 0; i < cells.size(); ++i) cells[i] = VoxelGrid::GRID_INDEX(raw[3 * i], raw[3 * i + 1], raw[3 * i + 2]);
+        return cells;
+    }
     static uint32_t CastFlags(const bool unknown_is_filled, const bool skip_first, const bool skip_last) {
         return (unknown_is_filled ? (uint32_t)SDFGPU_DSH_CAST_UNKNOWN_IS_FILLED : 0u) | (skip_first ? (uint32_t)SDFGPU_DSH_CAST_SKIP_FIRST : 0u) |
                (skip_last ? (uint32_t)SDFGPU_DSH_CAST_SKIP_LAST : 0u);

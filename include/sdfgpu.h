@@ -419,6 +419,31 @@ int sdfgpu_components(sdfgpu_handle h, const uint8_t* filled, int64_t nx, int64_
 int sdfgpu_components_cells(sdfgpu_handle h, void* cells, size_t cell_stride, size_t occupancy_offset, size_t component_offset,
                             int64_t nx, int64_t ny, int64_t nz, uint32_t* out_count);
 
+/* Component statistics: size, coordinate sums and bounding box of every component of the set class.
+ * Takes any bit field and the labels sdfgpu_components_bits_device made from it, and summarises every label in 1 .. label_count
+ * that has a voxel whose bit is set, over those voxels: one sdfgpu_component_stats record per such label, in ascending label
+ * order.  sum holds the sums of the voxels' x, y and z, lo and hi the bounding box (inclusive).  Everything is integer
+ * arithmetic: the atomics that gather it cannot make the result depend on their order.  A voxel whose label is 0 or above
+ * label_count is left out.  capacity is in records; the total always goes to out_total (required), and a list whose capacity is
+ * too small is not written, which is not an error.  The call synchronises `stream` once, to read the total.  Its scratch (one
+ * record per label in 0 .. label_count) is the handle's own for this call: the SDF scratch, status block and learnt policy are
+ * left as they were; an allocation that fails is an SDFGPU_ERR_* as elsewhere, with nothing written.  Refused with
+ * SDFGPU_ERR_INVALID_ARGUMENT: null d_bits, d_labels or out_total, buffers off their alignment (bits and labels 4, records 8
+ * bytes), a negative capacity or one without a buffer, a grid of more than 2^32 - 1 voxels or with an axis above 2^31 - 1 (lo and
+ * hi are int32). */
+typedef struct sdfgpu_component_stats {   /* 64 bytes */
+    uint32_t label;
+    uint32_t reserved;           /* 0 */
+    int64_t count;               /* voxels of the label whose bit is set */
+    uint64_t sum[3];             /* sums of their x, y and z */
+    int32_t lo[3];               /* bounding box, inclusive */
+    int32_t hi[3];
+} sdfgpu_component_stats;
+
+int sdfgpu_component_stats_device(sdfgpu_handle h, const uint32_t* d_bits, const uint32_t* d_labels, int64_t nx, int64_t ny, int64_t nz,
+                                  uint32_t label_count, sdfgpu_component_stats* d_stats, int64_t capacity, int64_t* out_total,
+                                  void* stream);
+
 /* ---------------------------------------------------------------------------
  * Component topology: CollisionMapGrid / TaggedObjectCollisionMapGrid::ComputeComponentTopology (reference
  * src/sdf_tools/collision_map.cpp:620-671, tagged_object_collision_map.cpp:424-490, topology_computation.hpp:297-672) on the GPU.
@@ -1308,6 +1333,44 @@ int sdfgpu_dsh_export_device(sdfgpu_dsh_map map, sdfgpu_dsh_chunk* d_chunks, int
                              int64_t* out_chunks, int64_t* out_cells, void* stream);
 int sdfgpu_dsh_export(sdfgpu_dsh_map map, sdfgpu_dsh_chunk* chunks, int64_t chunk_capacity, void* cells, int64_t cell_capacity,
                       int64_t* out_chunks, int64_t* out_cells);
+
+/* Frontier cells: where seen-free space ends in never-seen space.  The contract is this project's own;
+ * tests/dsh_frontier_restated.py restates it.
+ *
+ * Classes.  For a global cell i take the record Get returns there (the default for an absent chunk or an out-of-range chunk
+ * coordinate, the chunk's record for a chunk-filled chunk, the cell's own otherwise) and read its low 4 bytes as a float f:
+ *   free iff f < 0.5f; unknown iff f == 0.5f; a NaN is neither.
+ * A cell is a frontier cell iff
+ *   1. its chunk is live (found != SDFGPU_DSH_NOT_FOUND): a cell of an absent chunk never is one, whatever the default,
+ *   2. it is free, and
+ *   3. at least one neighbour is unknown: one of the 6 face neighbours, or of all 26 under SDFGPU_DSH_FRONTIER_26.
+ * Neighbours are read wherever they lie: in the same chunk, in another live chunk, in an absent chunk or beyond +-2^20 chunks
+ * (both: the default).  A window or a box restricts which cells are candidates, never which neighbours are read.  Any flag bit
+ * but SDFGPU_DSH_FRONTIER_26 is refused.
+ *
+ * sdfgpu_dsh_frontier_window*: the bit field of sdfgpu_build_bits_device over the window (bit set iff the voxel's cell is a frontier
+ *   cell).  Limits and layout are sdfgpu_dsh_extract_window's: at most 2^32 - 1 voxels, ceil(n / 32) words, each written whole by
+ *   one owner, bits behind the last voxel 0.  The device form enqueues one kernel and returns with it pending; it allocates
+ *   nothing and is ordered behind the map's last call by the map's event, as the cast and window forms are.
+ * sdfgpu_dsh_frontier_cells*: the frontier cells among the cells of live chunks in the box lower[a] .. lower[a] + extent[a] - 1
+ *   (the coordinates of the window's lower; every extent[a] >= 1, and lower + extent - 1 must not overflow int64), or, with lower
+ *   and extent both null, of the whole map.  int64[3] per cell, in ascending (c_x, c_y, c_z) order of the chunk and ascending cell
+ *   slot (l_x n_y + l_y) n_z + l_z inside it: the list is fully determined.  capacity is in cells; the total always goes to
+ *   out_total (required), and a list whose capacity is too small is not written, which is not an error (as sdfgpu_dsh_export).
+ *   The device form synchronises the stream once, to read the total; its scratch (a count, an offset and a bit mask of
+ *   ceil(n_x n_y n_z / 64) 64-bit words per live chunk) is the map's per-call scratch, which scratch_bytes counts.
+ * Neither changes the map by a byte, and sdfgpu_dsh_info reads the same before and after except scratch_bytes.  Null or misaligned
+ * buffers (bits 4, cells 8 bytes) and bad sizes are refused with SDFGPU_ERR_INVALID_ARGUMENT. */
+enum { SDFGPU_DSH_FRONTIER_26 = 1 };   /* a frontier call's flags */
+
+int sdfgpu_dsh_frontier_window_device(sdfgpu_dsh_map map, const int64_t lower[3], int64_t nx, int64_t ny, int64_t nz, uint32_t flags,
+                                      uint32_t* d_bits, void* stream);
+int sdfgpu_dsh_frontier_window(sdfgpu_dsh_map map, const int64_t lower[3], int64_t nx, int64_t ny, int64_t nz, uint32_t flags,
+                               uint32_t* bits);
+int sdfgpu_dsh_frontier_cells_device(sdfgpu_dsh_map map, const int64_t lower[3], const int64_t extent[3], uint32_t flags,
+                                     int64_t* d_cells, int64_t capacity, int64_t* out_total, void* stream);
+int sdfgpu_dsh_frontier_cells(sdfgpu_dsh_map map, const int64_t lower[3], const int64_t extent[3], uint32_t flags, int64_t* cells,
+                              int64_t capacity, int64_t* out_total);
 
 /* Red zones (round 6).  With SDFGPU_REDZONE=1 in the environment when sdfgpu_create runs -- or after
  * sdfgpu_set_option(h, "redzone", 1) -- every device allocation of the library (scratch fields, status block, extrema slots,

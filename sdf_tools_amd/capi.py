@@ -28,7 +28,7 @@ EXPORTS = [
     "sdfgpu_copy_to_host", "sdfgpu_copy_from_host", "sdfgpu_query_points", "sdfgpu_device_malloc", "sdfgpu_device_free",
     "sdfgpu_build_to_device", "sdfgpu_build_cells_to_device", "sdfgpu_upload_classified",
     "sdfgpu_build_bits_device", "sdfgpu_build_bits", "sdfgpu_voxelize_points_bits_device", "sdfgpu_debug_finish_table", "sdfgpu_redzone_check",
-    "sdfgpu_components_bits_device", "sdfgpu_components", "sdfgpu_components_cells",
+    "sdfgpu_components_bits_device", "sdfgpu_components", "sdfgpu_components_cells", "sdfgpu_component_stats_device",
     "sdfgpu_component_topology_device", "sdfgpu_component_topology", "sdfgpu_component_topology_cells",
     "sdfgpu_component_surfaces_device", "sdfgpu_component_surfaces", "sdfgpu_component_surfaces_cells",
     "sdfgpu_local_extrema_device", "sdfgpu_local_extrema", "sdfgpu_convex_segments_cells", "sdfgpu_convex_last_info",
@@ -50,6 +50,7 @@ EXPORTS = [
     "sdfgpu_dsh_cast_rays_device", "sdfgpu_dsh_cast_rays", "sdfgpu_dsh_cast_segments_device", "sdfgpu_dsh_cast_segments",
     "sdfgpu_dsh_get_device", "sdfgpu_dsh_get",
     "sdfgpu_dsh_extract_window_device", "sdfgpu_dsh_extract_window", "sdfgpu_dsh_export_device", "sdfgpu_dsh_export",
+    "sdfgpu_dsh_frontier_window_device", "sdfgpu_dsh_frontier_window", "sdfgpu_dsh_frontier_cells_device", "sdfgpu_dsh_frontier_cells",
 ]
 
 # include/sdfgpu.h "Projection": modes and per-point statuses
@@ -155,6 +156,7 @@ def load_library():
     L.sdfgpu_components_bits_device.argtypes = [vp, vp, i64, i64, i64, vp, vp, vp]
     L.sdfgpu_components.argtypes = [vp, vp, i64, i64, i64, vp, vp]
     L.sdfgpu_components_cells.argtypes = [vp, vp, sz, sz, sz, i64, i64, i64, vp]
+    L.sdfgpu_component_stats_device.argtypes = [vp, vp, vp, i64, i64, i64, u32, vp, i64, vp, vp]
     L.sdfgpu_component_topology_device.argtypes = [vp, vp, vp, i64, i64, i64, u32, vp, vp]
     L.sdfgpu_component_topology.argtypes = [vp, vp, vp, i64, i64, i64, u32, vp]
     L.sdfgpu_component_topology_cells.argtypes = [vp, vp, sz, sz, sz, i64, i64, i64, ci, u32, vp]
@@ -222,6 +224,10 @@ def load_library():
     L.sdfgpu_dsh_extract_window.argtypes = [vp, vp, i64, i64, i64, ci, vp, vp]
     L.sdfgpu_dsh_export_device.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp]
     L.sdfgpu_dsh_export.argtypes = [vp, vp, i64, vp, i64, vp, vp]
+    L.sdfgpu_dsh_frontier_window_device.argtypes = [vp, vp, i64, i64, i64, u32, vp, vp]
+    L.sdfgpu_dsh_frontier_window.argtypes = [vp, vp, i64, i64, i64, u32, vp]
+    L.sdfgpu_dsh_frontier_cells_device.argtypes = [vp, vp, vp, u32, vp, i64, vp, vp]
+    L.sdfgpu_dsh_frontier_cells.argtypes = [vp, vp, vp, u32, vp, i64, vp]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is ctypes.c_int or name not in ("sdfgpu_version", "sdfgpu_last_error"):
@@ -579,6 +585,14 @@ class SdfGpu:
         k = ctypes.c_uint32(0)
         self._check(self._lib.sdfgpu_components_bits_device(self._h, d_bits, nx, ny, nz, d_labels, ctypes.byref(k), stream or None))
         return int(k.value)
+
+    def component_stats_device(self, d_bits, d_labels, shape, label_count, d_stats=0, capacity=0, stream=0):
+        """sdfgpu_component_stats_device: bit field + the labels made from it (device) -> COMPONENT_STATS_DTYPE records of the labels
+        in 1 .. label_count with a set voxel, in label order, at d_stats iff `capacity` (in records) suffices; returns their number"""
+        total = ctypes.c_int64()
+        self._check(self._lib.sdfgpu_component_stats_device(self._h, d_bits or None, d_labels or None, *(int(s) for s in shape), int(label_count),
+                                                            d_stats or None, int(capacity), ctypes.byref(total), stream or None))
+        return total.value
 
     def components_cells(self, cells, shape, cell_stride=8, occupancy_offset=0, component_offset=4):
         """cells: writable contiguous records (COLLISION_CELL: 8, 0, 4; TAGGED_OBJECT_COLLISION_CELL: 16, 0, 4); the labels are
@@ -1352,6 +1366,7 @@ DSH_RAY_SKIPPED, DSH_RAY_HIT, DSH_RAY_TRUNCATED = 0, 1, 2
 DSH_CHUNK_NOT_REMOVED, DSH_CHUNK_REMOVED = 0, 1
 DSH_CAST_SKIPPED, DSH_CAST_CLEAR, DSH_CAST_CLEAR_IN_RANGE, DSH_CAST_BLOCKED = 0, 1, 2, 3
 DSH_CAST_SKIP_FIRST, DSH_CAST_SKIP_LAST, DSH_CAST_UNKNOWN_IS_FILLED = 1, 2, 4
+DSH_FRONTIER_26 = 1
 DSH_MAX_CHUNK_CELLS = 32768
 DSH_COUNTS_DTYPE = np.dtype([(n, np.uint64) for n in ("chunk_filled", "cell_filled", "capacity_chunks", "table_capacity", "bytes_held",
                                                       "scratch_bytes", "byte_limit")])
@@ -1361,6 +1376,9 @@ DSH_CAST_HIT_DTYPE = np.dtype([("cell", np.int64, (3,)), ("record", np.uint64), 
 DSH_SENSOR_MODEL_DEFAULT = (0.7, 0.4, 0.12, 0.97)                             # octomap's numbers
 DSH_CHUNK_DTYPE = np.dtype([("c", np.int64, (3,)), ("state", np.uint32), ("reserved", np.uint32), ("record", np.uint64),
                             ("first_cell", np.int64)])
+# include/sdfgpu.h "Component statistics": struct sdfgpu_component_stats (64 bytes)
+COMPONENT_STATS_DTYPE = np.dtype([("label", np.uint32), ("reserved", np.uint32), ("count", np.int64), ("sum", np.uint64, (3,)),
+                                  ("lo", np.int32, (3,)), ("hi", np.int32, (3,))])
 
 
 def dsh_record(occupancy, component=0):
@@ -1579,6 +1597,52 @@ class DshMap:
         nx, ny, nz = (int(s) for s in shape)
         self._check(self._lib.sdfgpu_dsh_extract_window_device(self._m, lo.ctypes.data, nx, ny, nz, int(bool(unknown_is_filled)), d_records or None,
                                                                d_bits or None, stream or None))
+
+    def frontier_window(self, lower, shape, flags=0):
+        """The frontier bits of a window (sdfgpu_dsh_frontier_window): a cell is a frontier cell iff its chunk is live, it is free
+        (occupancy < 0.5) and one of its 6 face neighbours (all 26 under DSH_FRONTIER_26) is unknown (== 0.5) -> bits uint32 [ceil(n / 32)]"""
+        lo = np.ascontiguousarray(lower, dtype=np.int64).reshape(3)
+        nx, ny, nz = (int(s) for s in shape)
+        bit = np.zeros(max((nx * ny * nz + 31) // 32, 0), np.uint32)
+        self._check(self._lib.sdfgpu_dsh_frontier_window(self._m, lo.ctypes.data, nx, ny, nz, int(flags), bit.ctypes.data))
+        return bit
+
+    def frontier_window_device(self, lower, shape, flags=0, d_bits=0, stream=0):
+        """sdfgpu_dsh_frontier_window_device: one kernel on `stream`, pending on return; d_bits takes ceil(n / 32) words"""
+        lo = np.ascontiguousarray(lower, dtype=np.int64).reshape(3)
+        nx, ny, nz = (int(s) for s in shape)
+        self._check(self._lib.sdfgpu_dsh_frontier_window_device(self._m, lo.ctypes.data, nx, ny, nz, int(flags), d_bits or None, stream or None))
+
+    @staticmethod
+    def _box(lower, extent):
+        """(lower, extent) as two int64 [3] arrays, or (None, None) for the whole map"""
+        if lower is None and extent is None:
+            return None, None
+        if lower is None or extent is None:
+            raise ValueError("a box is lower and extent, or neither")
+        return np.array([int(v) for v in lower], np.int64).reshape(3), np.array([int(v) for v in extent], np.int64).reshape(3)
+
+    def frontier_cells(self, lower=None, extent=None, flags=0):
+        """The frontier cells among the cells of live chunks in the box lower .. lower + extent - 1 (the whole map without a box), in
+        ascending chunk and cell slot order (sdfgpu_dsh_frontier_cells) -> global cells int64 [total, 3]"""
+        lo, ext = self._box(lower, extent)
+        args = (None if lo is None else lo.ctypes.data, None if ext is None else ext.ctypes.data, int(flags))
+        total = ctypes.c_int64()
+        self._check(self._lib.sdfgpu_dsh_frontier_cells(self._m, *args, None, 0, ctypes.byref(total)))
+        cells = np.zeros((total.value, 3), np.int64)
+        if total.value:
+            self._check(self._lib.sdfgpu_dsh_frontier_cells(self._m, *args, cells.ctypes.data, total.value, ctypes.byref(total)))
+            assert total.value == len(cells)
+        return cells
+
+    def frontier_cells_device(self, lower=None, extent=None, flags=0, d_cells=0, capacity=0, stream=0):
+        """sdfgpu_dsh_frontier_cells_device: the list (int64 [3] per cell) goes to d_cells iff `capacity` (in cells) suffices;
+        returns the total"""
+        lo, ext = self._box(lower, extent)
+        total = ctypes.c_int64()
+        self._check(self._lib.sdfgpu_dsh_frontier_cells_device(self._m, None if lo is None else lo.ctypes.data, None if ext is None else ext.ctypes.data,
+                                                               int(flags), d_cells or None, int(capacity), ctypes.byref(total), stream or None))
+        return total.value
 
     def export(self):
         """(chunks DSH_CHUNK_DTYPE [n] in ascending (c_x, c_y, c_z) order, cells uint64 [cell-filled chunks, n_x, n_y, n_z])"""

@@ -919,6 +919,48 @@ PYBIND11_MODULE(pysdf_tools, m) {
                                         skip_first, skip_last)});
         }, py::arg("origin"), py::arg("end"), py::arg("max_range"), py::arg("unknown_is_filled"), py::arg("skip_first") = false, py::arg("skip_last") = false,
            "one ray: the dict of CastRays with arrays of length 1")
+        .def("ExtractFrontierCells", [](const DshGrid& g, const py::object& lower, int64_t nx, int64_t ny, int64_t nz, bool use_26) {
+            std::vector<VoxelGrid::GRID_INDEX> cells;
+            if (lower.is_none()) {
+                cells = g.ExtractFrontierCells(use_26);
+            } else {
+                const std::array<int64_t, 3> at = lower.cast<std::array<int64_t, 3>>();
+                cells = g.ExtractFrontierCells(VoxelGrid::GRID_INDEX(at[0], at[1], at[2]), nx, ny, nz, use_26);
+            }
+            py::array_t<int64_t> out({(py::ssize_t)cells.size(), (py::ssize_t)3});
+            for (size_t i = 0; i < cells.size(); ++i) {
+                out.mutable_data()[3 * i] = cells[i].x; out.mutable_data()[3 * i + 1] = cells[i].y; out.mutable_data()[3 * i + 2] = cells[i].z;
+            }
+            return out;
+        }, py::arg("lower_index") = py::none(), py::arg("nx") = 0, py::arg("ny") = 0, py::arg("nz") = 0, py::arg("use_26") = false,
+           "the frontier cells (free, with an unknown neighbour) of the whole map, or of the nx x ny x nz cells from lower_index on: int64 [n, 3] global cells")
+        .def("ExtractFrontierWindowBits", [](const DshGrid& g, const std::array<int64_t, 3>& lower, int64_t nx, int64_t ny, int64_t nz, bool use_26) {
+            const std::vector<uint32_t> bits = g.ExtractFrontierWindowBits(VoxelGrid::GRID_INDEX(lower[0], lower[1], lower[2]), nx, ny, nz, use_26);
+            py::array_t<uint32_t> out((py::ssize_t)bits.size());
+            if (!bits.empty()) std::memcpy(out.mutable_data(), bits.data(), bits.size() * 4);
+            return out;
+        }, py::arg("lower_index"), py::arg("nx"), py::arg("ny"), py::arg("nz"), py::arg("use_26") = false,
+           "the window's frontier cells as a bit field: uint32 [ceil(nx ny nz / 32)], bit (x ny + y) nz + z")
+        .def("ExtractFrontierClusters", [](const DshGrid& g, const std::array<int64_t, 3>& lower, int64_t nx, int64_t ny, int64_t nz, int64_t min_cells, bool use_26) {
+            const std::vector<DshGrid::FrontierCluster> clusters =
+                g.ExtractFrontierClusters(VoxelGrid::GRID_INDEX(lower[0], lower[1], lower[2]), nx, ny, nz, min_cells, use_26);
+            const py::ssize_t n = (py::ssize_t)clusters.size();
+            py::array_t<uint32_t> label(n);
+            py::array_t<int64_t> cells(n), lo({n, (py::ssize_t)3}), hi({n, (py::ssize_t)3});
+            py::array_t<double> centroid({n, (py::ssize_t)3});
+            for (py::ssize_t i = 0; i < n; ++i) {
+                const DshGrid::FrontierCluster& c = clusters[(size_t)i];
+                label.mutable_data()[i] = c.label;
+                cells.mutable_data()[i] = c.cells;
+                lo.mutable_data()[3 * i] = c.lower.x; lo.mutable_data()[3 * i + 1] = c.lower.y; lo.mutable_data()[3 * i + 2] = c.lower.z;
+                hi.mutable_data()[3 * i] = c.upper.x; hi.mutable_data()[3 * i + 1] = c.upper.y; hi.mutable_data()[3 * i + 2] = c.upper.z;
+                centroid.mutable_data()[3 * i] = c.centroid.x(); centroid.mutable_data()[3 * i + 1] = c.centroid.y(); centroid.mutable_data()[3 * i + 2] = c.centroid.z();
+            }
+            py::dict d;
+            d["label"] = label; d["cells"] = cells; d["lower"] = lo; d["upper"] = hi; d["centroid"] = centroid;
+            return d;
+        }, py::arg("lower_index"), py::arg("nx"), py::arg("ny"), py::arg("nz"), py::arg("min_cells") = 1, py::arg("use_26") = true,
+           "the 6-connected pieces of the window's frontier with at least min_cells cells: a dict of arrays (label, cells, lower and upper int64 [n, 3], centroid float64 [n, 3])")
         .def("RemoveChunk", [](DshGrid& g, double x, double y, double z) { return g.RemoveChunk(x, y, z); })
         .def("RemoveChunks", [=](DshGrid& g, const py::array_t<double, py::array::c_style | py::array::forcecast>& locations) {
             const std::vector<bool> removed = g.RemoveChunks(dsh_locations(locations));

@@ -208,6 +208,98 @@ __global__ __launch_bounds__(256) void k_cc_relabel(uint32_t* __restrict__ L, ui
     }
 }
 
+// ---- component statistics (include/sdfgpu.h "Component statistics") ------------------------------------------
+// The table is one sdfgpu_component_stats per label in 0 .. label_count: k_cs_init makes every entry the neutral element, k_cs_gather
+// folds the voxels in with integer atomics (sums, minima and maxima: any order gives the same table), k_cs_count counts the labels
+// that took a voxel and k_cs_compact lists them in label order.
+constexpr int kStatsThreads = 256;
+constexpr int kStatsCompactThreads = 1024;
+
+__global__ __launch_bounds__(kStatsThreads) void k_cs_init(sdfgpu_component_stats* __restrict__ table, uint64_t entries) {
+    const uint64_t i = (uint64_t)blockIdx.x * kStatsThreads + threadIdx.x;
+    if (i >= entries) return;
+    sdfgpu_component_stats s;
+    s.label = (uint32_t)i; s.reserved = 0; s.count = 0;
+    for (int a = 0; a < 3; ++a) { s.sum[a] = 0; s.lo[a] = INT32_MAX; s.hi[a] = INT32_MIN; }
+    table[i] = s;
+}
+
+template <class T, class Op>
+__device__ __forceinline__ T cs_wave_fold(T v, Op op) {
+    for (int d = 32; d >= 1; d >>= 1) v = op(v, __shfl_xor(v, d));
+    return v;
+}
+
+// One thread per voxel.  The lanes of a wave that share a label fold their voxels first (neighbouring voxels mostly do: a wave is
+// 64 voxels of a few z rows), and the first of them adds the sum to the label's entry: one round per distinct label in the wave.
+__global__ __launch_bounds__(kStatsThreads) void k_cs_gather(const uint32_t* __restrict__ bits, const uint32_t* __restrict__ labels, uint64_t n,
+                                                             uint32_t ny, uint32_t nz, uint32_t label_count,
+                                                             sdfgpu_component_stats* __restrict__ table) {
+    const uint64_t v = (uint64_t)blockIdx.x * kStatsThreads + threadIdx.x;
+    uint32_t label = 0;
+    if (v < n && bit_at(bits, v)) label = labels[v];
+    if (label > label_count) label = 0;                                        // (not a label of this call: no entry to add to)
+    const uint64_t q = v / nz;
+    const uint32_t z = (uint32_t)(v - q * nz), x = (uint32_t)(q / ny), y = (uint32_t)(q - (uint64_t)x * ny);
+    const int lane = threadIdx.x & 63;
+    unsigned long long todo = __ballot(label != 0);
+    while (todo) {                                                             // (uniform over the wave)
+        const uint32_t current = (uint32_t)__shfl((int)label, __ffsll(todo) - 1);
+        const bool same = label == current;
+        const unsigned long long members = __ballot(same);
+        const auto add = [](unsigned long long a, unsigned long long b) { return a + b; };
+        const auto lower = [](int a, int b) { return a < b ? a : b; };
+        const auto upper = [](int a, int b) { return a > b ? a : b; };
+        const unsigned long long sx = cs_wave_fold<unsigned long long>(same ? x : 0, add), sy = cs_wave_fold<unsigned long long>(same ? y : 0, add),
+                                 sz = cs_wave_fold<unsigned long long>(same ? z : 0, add);
+        const int lx = cs_wave_fold<int>(same ? (int)x : INT32_MAX, lower), ly = cs_wave_fold<int>(same ? (int)y : INT32_MAX, lower),
+                  lz = cs_wave_fold<int>(same ? (int)z : INT32_MAX, lower);
+        const int hx = cs_wave_fold<int>(same ? (int)x : INT32_MIN, upper), hy = cs_wave_fold<int>(same ? (int)y : INT32_MIN, upper),
+                  hz = cs_wave_fold<int>(same ? (int)z : INT32_MIN, upper);
+        if (lane == __ffsll(members) - 1) {
+            sdfgpu_component_stats* const s = table + current;
+            atomicAdd(reinterpret_cast<unsigned long long*>(&s->count), (unsigned long long)__popcll(members));
+            atomicAdd(reinterpret_cast<unsigned long long*>(&s->sum[0]), sx);
+            atomicAdd(reinterpret_cast<unsigned long long*>(&s->sum[1]), sy);
+            atomicAdd(reinterpret_cast<unsigned long long*>(&s->sum[2]), sz);
+            atomicMin(&s->lo[0], lx); atomicMin(&s->lo[1], ly); atomicMin(&s->lo[2], lz);
+            atomicMax(&s->hi[0], hx); atomicMax(&s->hi[1], hy); atomicMax(&s->hi[2], hz);
+        }
+        todo &= ~members;
+    }
+}
+
+// *total = labels in 1 .. label_count with a voxel, one atomic per wave
+__global__ __launch_bounds__(kStatsThreads) void k_cs_count(const sdfgpu_component_stats* __restrict__ table, uint32_t label_count,
+                                                            unsigned long long* total) {
+    const uint64_t label = (uint64_t)blockIdx.x * kStatsThreads + threadIdx.x + 1;
+    const unsigned long long used = __ballot(label <= label_count && table[label].count > 0);
+    if ((threadIdx.x & 63) == 0 && used) atomicAdd(total, (unsigned long long)__popcll(used));
+}
+
+// One workgroup walks the labels, kStatsCompactThreads at a time, and writes the entries that took a voxel in label order.
+__global__ __launch_bounds__(kStatsCompactThreads) void k_cs_compact(const sdfgpu_component_stats* __restrict__ table, uint32_t label_count,
+                                                                     sdfgpu_component_stats* __restrict__ out) {
+    __shared__ uint32_t wave_sum[kStatsCompactThreads / 64];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint64_t written = 0;
+    for (uint64_t base = 1; base <= label_count; base += kStatsCompactThreads) {
+        const uint64_t label = base + threadIdx.x;
+        const bool used = label <= label_count && table[label].count > 0;
+        const unsigned long long b = __ballot(used);
+        __syncthreads();                                                       // (wave_sum may still be read from the round before)
+        if (lane == 0) wave_sum[wave] = (uint32_t)__popcll(b);
+        __syncthreads();
+        uint32_t before = 0, total = 0;
+        for (uint32_t w = 0; w < kStatsCompactThreads / 64; ++w) {
+            if (w < wave) before += wave_sum[w];
+            total += wave_sum[w];
+        }
+        if (used) out[written + before + (uint32_t)__popcll(b & ((1ull << lane) - 1))] = table[label];
+        written += total;
+    }
+}
+
 }  // namespace
 
 CcPlan cc_plan(int64_t nx, int64_t ny, int64_t nz) {
@@ -290,9 +382,54 @@ int components_host(sdfgpu_handle h, const Occupancy& occ, int64_t nx, int64_t n
     return components_impl(h, (const uint32_t*)h->stage_bits.ptr, nx, ny, nz, (uint32_t*)h->stage_out.ptr, out_count, nullptr);
 }
 
+// bits + labels (device) -> the records of the labels with a set voxel, in label order; synchronises `st` (the total is read back)
+int component_stats_impl(sdfgpu_handle h, const uint32_t* d_bits, const uint32_t* d_labels, int64_t nx, int64_t ny, int64_t nz, uint32_t label_count,
+                         sdfgpu_component_stats* d_stats, int64_t capacity, int64_t* out_total, hipStream_t st) {
+    *out_total = 0;
+    if (label_count == 0) return SDFGPU_OK;
+    const uint64_t n = (uint64_t)nx * (uint64_t)ny * (uint64_t)nz, entries = (uint64_t)label_count + 1;
+    constexpr size_t kCounterBytes = 256;                                      // the total, in front of the table
+    HIP_TRY(h, h->cs_order.create());
+    HIP_TRY(h, h->cs_order.wait(st));
+    if (int rc = ensure(h, h->cs_scratch, kCounterBytes + (size_t)entries * sizeof(sdfgpu_component_stats), "component statistics scratch")) return rc;
+    StreamOrder::RecordAtExit record{h->cs_order, st};
+    unsigned long long* const d_total = static_cast<unsigned long long*>(h->cs_scratch.ptr);
+    sdfgpu_component_stats* const table = reinterpret_cast<sdfgpu_component_stats*>(static_cast<char*>(h->cs_scratch.ptr) + kCounterBytes);
+    const auto blocks = [](uint64_t items) { return dim3((unsigned)((items + kStatsThreads - 1) / kStatsThreads)); };
+    HIP_TRY(h, hipMemsetAsync(d_total, 0, kCounterBytes, st));
+    hipLaunchKernelGGL(k_cs_init, blocks(entries), dim3(kStatsThreads), 0, st, table, entries);
+    hipLaunchKernelGGL(k_cs_gather, blocks(n), dim3(kStatsThreads), 0, st, d_bits, d_labels, n, (uint32_t)ny, (uint32_t)nz, label_count, table);
+    hipLaunchKernelGGL(k_cs_count, blocks(label_count), dim3(kStatsThreads), 0, st, (const sdfgpu_component_stats*)table, label_count, d_total);
+    HIP_TRY(h, hipGetLastError());
+    unsigned long long total = 0;
+    HIP_TRY(h, hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    *out_total = (int64_t)total;
+    if (total == 0 || (uint64_t)capacity < total) return SDFGPU_OK;
+    hipLaunchKernelGGL(k_cs_compact, dim3(1), dim3(kStatsCompactThreads), 0, st, (const sdfgpu_component_stats*)table, label_count, d_stats);
+    HIP_TRY(h, hipGetLastError());
+    return SDFGPU_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int sdfgpu_component_stats_device(sdfgpu_handle h, const uint32_t* d_bits, const uint32_t* d_labels, int64_t nx, int64_t ny, int64_t nz,
+                                  uint32_t label_count, sdfgpu_component_stats* d_stats, int64_t capacity, int64_t* out_total, void* stream) {
+    return rz_wrap(h, stream, [&]() -> int {
+        if (!d_bits || !d_labels || !out_total) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "null pointer");
+        if ((reinterpret_cast<uintptr_t>(d_bits) | reinterpret_cast<uintptr_t>(d_labels)) & 3)
+            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "d_bits and d_labels must be 4-byte aligned");
+        if (reinterpret_cast<uintptr_t>(d_stats) & 7) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "d_stats must be 8-byte aligned");
+        if (capacity < 0 || (capacity > 0 && !d_stats)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "component statistics: a capacity without a buffer");
+        if (int rc = check_dims_u32(h, nx, ny, nz, kLabelsTail)) return rc;
+        if (std::max({nx, ny, nz}) > (int64_t)INT32_MAX)
+            return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "component statistics: an axis above 2^31 - 1 voxels (the bounding box is int32)");
+        HIP_TRY(h, hipSetDevice(h->device));
+        return component_stats_impl(h, d_bits, d_labels, nx, ny, nz, label_count, d_stats, capacity, out_total, (hipStream_t)stream);
+    });
+}
 
 int sdfgpu_components_bits_device(sdfgpu_handle h, const uint32_t* d_bits, int64_t nx, int64_t ny, int64_t nz, uint32_t* d_labels,
                                   uint32_t* out_count, void* stream) {

@@ -460,7 +460,7 @@ int sdfgpu_destroy(sdfgpu_handle h) {
     if (h->batch_pin) (void)hipHostFree(h->batch_pin);
     if (h->h_flags) { (void)hipHostFree(h->h_flags); (void)hipEventDestroy(h->flags_ev); }
     if (h->far_ev) (void)hipEventDestroy(h->far_ev);
-    for (StreamOrder* o : {&h->build_order, &h->cx_order, &h->rs_order, &h->sc_order, &h->mr_order}) o->destroy();
+    for (StreamOrder* o : {&h->build_order, &h->cx_order, &h->rs_order, &h->sc_order, &h->mr_order, &h->cs_order}) o->destroy();
     for (hipEvent_t e : h->rs_time_ev) if (e) (void)hipEventDestroy(e);
     for (int i = 0; i < 2; ++i) { if (h->pin[i]) (void)hipHostFree(h->pin[i]); if (h->pin_ev[i]) (void)hipEventDestroy(h->pin_ev[i]); }
     for (size_t i = 0; i < h->events.size(); ++i)

@@ -90,10 +90,11 @@ struct ContextBuffers {
     DeviceBuffer sc_scratch; // sdfgpu_rasterize_shapes*: status, world bounds per shape, candidate bits per coarse region (sdfgpu_scene.hpp)
     DeviceBuffer mr_scratch; // sdfgpu_rasterize_meshes*: status, first slot per mesh, tile scan, world vertices and id per triangle (sdfgpu_mesh.hpp)
     DeviceBuffer ms_toggle;  // sdfgpu_rasterize_solid_meshes*: one toggle bit per cell, columns padded to words; all zero between calls (sdfgpu_mesh_solid.hpp)
+    DeviceBuffer cs_scratch; // sdfgpu_component_stats_device: the counter, one record per label in 0 .. label_count (sdfgpu_components.hip)
     DeviceBuffer* begin() { return &zfield; }
     DeviceBuffer* end() { return begin() + sizeof(ContextBuffers) / sizeof(DeviceBuffer); }
 };
-static_assert(sizeof(ContextBuffers) == 35 * sizeof(DeviceBuffer), "ContextBuffers holds DeviceBuffer members only");
+static_assert(sizeof(ContextBuffers) == 36 * sizeof(DeviceBuffer), "ContextBuffers holds DeviceBuffer members only");
 
 // What the sdfgpu_last_* and sdfgpu_debug_* calls report about the most recent build or stage call.
 struct LastBuild {
@@ -206,6 +207,7 @@ struct sdfgpu_context : sdfgpu::ContextBuffers {
                                           // stream: one on another stream waits for it before it clears the winner words
     sdfgpu::StreamOrder sc_order;         // recorded behind every shape rasterisation (the same rule, for sc_scratch)
     sdfgpu::StreamOrder mr_order;         // recorded behind every mesh rasterisation (the same rule, for mr_scratch)
+    sdfgpu::StreamOrder cs_order;         // recorded behind every component statistics call (the same rule, for cs_scratch)
     bool ms_dirty = false;                // a solid mesh call failed between a scatter and its merge: ms_toggle is cleared before its next use
     hipEvent_t rs_time_ev[3] = {nullptr, nullptr, nullptr};   // "resample_timing"
     bool rs_timed = false;

@@ -846,6 +846,217 @@ __global__ __launch_bounds__(kDshThreads) void k_dsh_remove_move(const DshPool p
     }
 }
 
+// ---- frontier cells (include/sdfgpu.h "Frontier cells") ---------------------------------------------------------------
+// A frontier cell is a free cell of a live chunk with an unknown neighbour.  The stencil is stated once (dsh_unknown_neighbour) and
+// walks the neighbouring CHUNKS, not the neighbours: for each of the up to 27 chunk offsets it asks `lookup` once what that chunk
+// shows, then reads the neighbours that lie there.  The window form answers a lookup with a dsh_find, the list form out of LDS.
+// The loops index l[] and g.n[] by constants only: nothing is kept in scratch.
+__device__ __forceinline__ bool dsh_record_free(uint64_t record) { return __uint_as_float((uint32_t)record) < 0.5f; }
+__device__ __forceinline__ bool dsh_record_unknown(uint64_t record) { return __uint_as_float((uint32_t)record) == 0.5f; }
+
+// What a chunk shows to a reader: its cells (cell-filled), else one record for every cell (the chunk's own when chunk-filled, the
+// default when it is absent or its coordinate is out of range).
+struct DshChunkView {
+    const uint64_t* cells;
+    uint64_t record;
+};
+
+__device__ __forceinline__ DshChunkView dsh_view_slot(const DshPool& p, uint64_t cells_per_chunk, uint64_t slot, uint64_t default_record) {
+    const uint32_t state = p.heads[slot].state & kDshStateMask;
+    DshChunkView v{nullptr, default_record};
+    if (state == kDshChunkFilled) v.record = p.heads[slot].record;
+    else if (state == kDshCellFilled) v.cells = p.cells + slot * cells_per_chunk;
+    return v;
+}
+
+__device__ __forceinline__ DshChunkView dsh_view_chunk(const DshGeometry& g, const DshTable& t, const DshPool& p, int64_t cx, int64_t cy, int64_t cz) {
+    if (!(dsh_chunk_in_range(cx) && dsh_chunk_in_range(cy) && dsh_chunk_in_range(cz))) return DshChunkView{nullptr, g.default_record};
+    const uint32_t pos = dsh_find(t, dsh_pack_key(cx, cy, cz));
+    if (pos == kDshNoPos) return DshChunkView{nullptr, g.default_record};
+    return dsh_view_slot(p, (uint64_t)g.cells_per_chunk, t.slots[pos], g.default_record);
+}
+
+// whether a neighbour (6 face neighbours, or all 26) of the cell at l[] of a chunk is unknown; lookup(ox, oy, oz) -> DshChunkView of
+// the chunk at that offset from the cell's own ((0, 0, 0) is its own chunk)
+template <class Lookup>
+__device__ __forceinline__ bool dsh_unknown_neighbour(const DshGeometry& g, const int64_t l[3], bool use_26, Lookup&& lookup) {
+    for (int ox = -1; ox <= 1; ++ox) {
+        int x0, x1;
+        dsh_axis_steps(l[0], g.n[0], ox, x0, x1);
+        if (x0 > x1) continue;
+        for (int oy = -1; oy <= 1; ++oy) {
+            int y0, y1;
+            dsh_axis_steps(l[1], g.n[1], oy, y0, y1);
+            if (y0 > y1) continue;
+            for (int oz = -1; oz <= 1; ++oz) {
+                int z0, z1;
+                dsh_axis_steps(l[2], g.n[2], oz, z0, z1);
+                if (z0 > z1) continue;
+                if (!use_26 && (ox != 0) + (oy != 0) + (oz != 0) > 1) continue;       // a face neighbour crosses at most one chunk face
+                const DshChunkView view = lookup(ox, oy, oz);
+                if (!view.cells && !dsh_record_unknown(view.record)) continue;         // one record for all its cells, and not unknown
+                for (int dx = x0; dx <= x1; ++dx)
+                    for (int dy = y0; dy <= y1; ++dy)
+                        for (int dz = z0; dz <= z1; ++dz) {
+                            const int steps = (dx != 0) + (dy != 0) + (dz != 0);
+                            if (steps == 0 || (!use_26 && steps != 1)) continue;
+                            if (!view.cells) return true;
+                            const int64_t m[3] = {l[0] + dx - ox * g.n[0], l[1] + dy - oy * g.n[1], l[2] + dz - oz * g.n[2]};
+                            if (dsh_record_unknown(view.cells[dsh_cell_index(m, g.n)])) return true;
+                        }
+            }
+        }
+    }
+    return false;
+}
+
+struct DshFrontierWindow {
+    int64_t lower[3];
+    uint32_t ny, nz;
+    uint64_t n;             // voxels (< 2^32)
+    uint32_t use_26;
+    uint32_t* bits;
+};
+
+// k_dsh_window's shape: one thread per voxel, the words out of a ballot.  A lane decides its own cell first; only a free cell of a
+// live chunk reads neighbours, those of its own chunk from the slot it has found.
+__global__ __launch_bounds__(kDshThreads) void k_dsh_frontier_window(const DshGeometry g, const DshTable t, const DshPool p, const DshFrontierWindow w) {
+    const uint64_t v = (uint64_t)dsh_item();
+    if (v - threadIdx.x >= w.n) return;                                        // (the last row of a two-dimensional launch)
+    bool frontier = false;
+    if (v < w.n) {
+        const uint32_t u = (uint32_t)v, q = u / w.nz;
+        const uint32_t z = u - q * w.nz, x = q / w.ny, y = q - x * w.ny;
+        const int64_t i[3] = {w.lower[0] + (int64_t)x, w.lower[1] + (int64_t)y, w.lower[2] + (int64_t)z};
+        int64_t c[3], l[3];
+        bool valid = true;
+        for (int a = 0; a < 3; ++a) {
+            dsh_split_cell(i[a], g.n[a], c[a], l[a]);
+            valid = valid && dsh_chunk_in_range(c[a]);
+        }
+        const uint32_t pos = valid ? dsh_find(t, dsh_pack_key(c[0], c[1], c[2])) : kDshNoPos;
+        if (pos != kDshNoPos) {
+            const DshChunkView own = dsh_view_slot(p, (uint64_t)g.cells_per_chunk, t.slots[pos], g.default_record);
+            if (dsh_record_free(own.cells ? own.cells[dsh_cell_index(l, g.n)] : own.record))
+                frontier = dsh_unknown_neighbour(g, l, w.use_26 != 0, [&](int ox, int oy, int oz) {
+                    return (ox | oy | oz) ? dsh_view_chunk(g, t, p, c[0] + ox, c[1] + oy, c[2] + oz) : own;
+                });
+        }
+    }
+    const unsigned long long b = __ballot(frontier);
+    const int lane = threadIdx.x & 63;
+    if (v < w.n && (lane == 0 || lane == 32)) w.bits[v >> 5] = (uint32_t)(b >> lane);
+}
+
+// The list form, first pass: one workgroup per live chunk.  A chunk that holds no cell of the box counts 0 and writes no mask.
+// Lanes 0 .. 26 look the 27 chunks around (and including) it up once; then a thread per cell slot, 256 slots a round: each wave's
+// ballot is one 64-bit word of the chunk's mask (bit k of word j: cell slot 64 j + k), written whole.  counts[slot] = the chunk's
+// frontier cells, *total += them.
+__global__ __launch_bounds__(kDshThreads) void k_dsh_frontier_count(const DshGeometry g, const DshTable t, const DshPool p, uint64_t n_live,
+                                                                    const DshFrontierBox box, uint32_t use_26, uint32_t* __restrict__ counts,
+                                                                    unsigned long long* __restrict__ masks, unsigned long long* total) {
+    __shared__ DshChunkView around[27];
+    __shared__ uint32_t wave_count[kDshThreads / 64];
+    const uint64_t slot = (uint64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    if (slot >= n_live) return;                                                // (the last row of a two-dimensional launch)
+    const uint64_t key = p.heads[slot].key;
+    if (!dsh_key_in_range(key, box.chunks)) {                                  // (uniform over the workgroup)
+        if (threadIdx.x == 0) counts[slot] = 0;
+        return;
+    }
+    int64_t c[3];
+    dsh_unpack_key(key, c[0], c[1], c[2]);
+    const uint64_t cpc = (uint64_t)g.cells_per_chunk, words = dsh_frontier_mask_words(cpc);
+    if (threadIdx.x < 27) {
+        const int k = (int)threadIdx.x, ox = k / 9 - 1, oy = (k / 3) % 3 - 1, oz = k % 3 - 1;
+        around[k] = k == 13 ? dsh_view_slot(p, cpc, slot, g.default_record) : dsh_view_chunk(g, t, p, c[0] + ox, c[1] + oy, c[2] + oz);
+    }
+    __syncthreads();
+    const DshChunkView own = around[13];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t mine = 0;
+    for (uint64_t base = 0; base < cpc; base += kDshThreads) {                 // (every thread runs every round: the ballots are whole)
+        const uint64_t k = base + threadIdx.x;
+        bool frontier = false;
+        if (k < cpc) {
+            const uint64_t q = k / (uint64_t)g.n[2];
+            const int64_t l[3] = {(int64_t)(q / (uint64_t)g.n[1]), (int64_t)(q % (uint64_t)g.n[1]), (int64_t)(k % (uint64_t)g.n[2])};
+            bool in = true;
+            for (int a = 0; a < 3; ++a) {
+                const int64_t i = c[a] * g.n[a] + l[a];
+                in = in && i >= box.lo[a] && i <= box.hi[a];
+            }
+            if (in && dsh_record_free(own.cells ? own.cells[k] : own.record))
+                frontier = dsh_unknown_neighbour(g, l, use_26 != 0, [&](int ox, int oy, int oz) { return around[(ox + 1) * 9 + (oy + 1) * 3 + (oz + 1)]; });
+        }
+        const unsigned long long b = __ballot(frontier);
+        const uint64_t first = base + 64 * (uint64_t)wave;                     // the wave's first cell slot of this round
+        if (lane == 0 && first < cpc) {
+            masks[slot * words + (first >> 6)] = b;
+            mine += (uint32_t)__popcll(b);
+        }
+    }
+    if (lane == 0) wave_count[wave] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t sum = 0;
+        for (int k = 0; k < kDshThreads / 64; ++k) sum += wave_count[k];
+        counts[slot] = sum;
+        if (sum) atomicAdd(total, (unsigned long long)sum);
+    }
+}
+
+// Where a chunk's cells start in the list: the frontier cells of the live chunks with a smaller key.  k_dsh_rank's counting (every
+// thread over all chunks, a tile of heads at a time through LDS) with the counts as weights: the rank and the scan over the chunks
+// in key order in one pass, free of scratch, atomics and order effects.
+__global__ __launch_bounds__(kDshThreads) void k_dsh_frontier_offsets(const DshChunkHead* __restrict__ heads, uint32_t n_live,
+                                                                      const uint32_t* __restrict__ counts, uint64_t* __restrict__ offsets) {
+    __shared__ uint64_t tile_key[kDshThreads];
+    __shared__ uint32_t tile_count[kDshThreads];
+    const int64_t s = dsh_item();
+    const bool live = s < n_live;
+    const uint64_t mine = live ? heads[s].key : kDshEmptyKey;
+    uint64_t before = 0;
+    for (uint32_t base = 0; base < n_live; base += kDshThreads) {
+        const uint32_t j = base + threadIdx.x;
+        tile_key[threadIdx.x] = j < n_live ? heads[j].key : kDshEmptyKey;      // (no key is above the empty key's value)
+        tile_count[threadIdx.x] = j < n_live ? counts[j] : 0;
+        __syncthreads();
+        for (int k = 0; k < kDshThreads; ++k) before += tile_key[k] < mine ? tile_count[k] : 0u;
+        __syncthreads();
+    }
+    if (live) offsets[s] = before;
+}
+
+// The list form, second pass: one workgroup per live chunk with frontier cells writes them, in cell slot order, from offsets[slot]
+// on.  A thread per mask word: the words' popcounts are scanned over the workgroup, and a thread writes the cells of its word.
+__global__ __launch_bounds__(kDshThreads) void k_dsh_frontier_write(const DshGeometry g, const DshChunkHead* __restrict__ heads, uint64_t n_live,
+                                                                    const uint32_t* __restrict__ counts, const uint64_t* __restrict__ offsets,
+                                                                    const unsigned long long* __restrict__ masks, int64_t* __restrict__ out) {
+    __shared__ uint32_t wave_sum[kDshThreads / 64];
+    const uint64_t slot = (uint64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    if (slot >= n_live || counts[slot] == 0) return;                           // (uniform over the workgroup)
+    int64_t c[3];
+    dsh_unpack_key(heads[slot].key, c[0], c[1], c[2]);
+    const uint64_t words = dsh_frontier_mask_words((uint64_t)g.cells_per_chunk);
+    uint64_t at = offsets[slot];
+    for (uint64_t base = 0; base < words; base += kDshThreads) {
+        const uint64_t j = base + threadIdx.x;
+        unsigned long long word = j < words ? masks[slot * words + j] : 0ull;
+        uint32_t total = 0;
+        uint64_t o = at + dsh_block_exclusive((uint32_t)__popcll(word), wave_sum, total);
+        while (word) {
+            const uint64_t k = 64 * j + (uint64_t)(__ffsll(word) - 1), q = k / (uint64_t)g.n[2];
+            word &= word - 1;
+            out[3 * o] = c[0] * g.n[0] + (int64_t)(q / (uint64_t)g.n[1]);
+            out[3 * o + 1] = c[1] * g.n[1] + (int64_t)(q % (uint64_t)g.n[1]);
+            out[3 * o + 2] = c[2] * g.n[2] + (int64_t)(k % (uint64_t)g.n[2]);
+            ++o;
+        }
+        at += total;
+    }
+}
+
 size_t dsh_fuse_lds_bytes(uint64_t cells_per_chunk) { return (size_t)((cells_per_chunk + 15) / 16 * 16); }   // at most 32 KiB
 
 dim3 dsh_chunk_grid(uint64_t chunks) {                                        // one workgroup per chunk
@@ -1359,6 +1570,77 @@ int dsh_window_impl(sdfgpu_dsh_map_object* m, const int64_t* lower, int64_t nx, 
     return SDFGPU_OK;
 }
 
+int dsh_check_frontier_flags(sdfgpu_handle h, uint32_t flags) {
+    if (flags & ~(uint32_t)SDFGPU_DSH_FRONTIER_26) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: a frontier call knows the flag FRONTIER_26 (got 0x%x)", flags);
+    return SDFGPU_OK;
+}
+
+// The frontier bits of a window on `st` (checked by dsh_check_window and dsh_check_frontier_flags): one kernel, nothing allocated.
+int dsh_frontier_window_impl(sdfgpu_dsh_map_object* m, const int64_t* lower, int64_t nx, int64_t ny, int64_t nz, uint32_t flags, uint32_t* d_bits,
+                             hipStream_t st) {
+    sdfgpu_handle h = m->h;
+    if (reinterpret_cast<uintptr_t>(d_bits) & 3) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: the bit field must be 4-byte aligned");
+    DshCall call{m, st};
+    if (int rc = call.open()) return rc;
+    DshFrontierWindow w{};
+    for (int a = 0; a < 3; ++a) w.lower[a] = lower[a];
+    w.ny = (uint32_t)ny; w.nz = (uint32_t)nz;
+    w.n = (uint64_t)nx * (uint64_t)ny * (uint64_t)nz;
+    w.use_26 = (flags & SDFGPU_DSH_FRONTIER_26) != 0;
+    w.bits = d_bits;
+    hipLaunchKernelGGL(k_dsh_frontier_window, dsh_grid((int64_t)w.n), dim3(kDshThreads), 0, st, m->g, m->table, m->pool, w);
+    HIP_TRY(h, hipGetLastError());
+    return SDFGPU_OK;
+}
+
+// What a frontier list is refused for before anything is enqueued, and its box.
+int dsh_frontier_cells_check(sdfgpu_dsh_map_object* m, const int64_t* lower, const int64_t* extent, uint32_t flags, const void* cells, int64_t capacity,
+                             const int64_t* out_total, DshFrontierBox& box) {
+    sdfgpu_handle h = m->h;
+    if (int rc = dsh_check_frontier_flags(h, flags)) return rc;
+    if (!out_total) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: frontier_cells needs out_total");
+    if (capacity < 0 || (capacity > 0 && !cells)) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: frontier_cells: a capacity without a buffer");
+    if (!lower != !extent) return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: frontier_cells takes lower and extent, or neither (the whole map)");
+    if (lower && !dsh_frontier_box_ok(lower, extent))
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: a frontier box has extent >= 1 on every axis and lower + extent - 1 within int64");
+    box = dsh_frontier_box(lower, extent, m->g.n);
+    return SDFGPU_OK;
+}
+
+// The frontier cells of the box on `st` (checked by dsh_frontier_cells_check): count and mask per chunk | the total read back | offsets
+// in key order | write.  The list is written iff capacity suffices.
+int dsh_frontier_cells_impl(sdfgpu_dsh_map_object* m, const DshFrontierBox& box, uint32_t flags, int64_t* d_cells, int64_t capacity, int64_t* out_total,
+                            hipStream_t st) {
+    sdfgpu_handle h = m->h;
+    if (int rc = dsh_aligned8(h, d_cells, "the cell list")) return rc;
+    DshCall call{m, st};
+    if (int rc = call.open()) return rc;
+    *out_total = 0;
+    if (!m->n_live || box.chunks.empty) return SDFGPU_OK;
+    const size_t live = (size_t)m->n_live, words = (size_t)dsh_frontier_mask_words((uint64_t)m->g.cells_per_chunk);
+    uint32_t* counts = nullptr;
+    uint64_t* offsets = nullptr;
+    unsigned long long* masks = nullptr;
+    if (int rc = dsh_scratch(m, [&](DshCut& c) {
+            counts = c.take<uint32_t>(live * 4); offsets = c.take<uint64_t>(live * 8); masks = c.take<unsigned long long>(live * words * 8);
+        })) return rc;
+    unsigned long long* const d_total = static_cast<unsigned long long*>(m->scratch.ptr);
+    const uint32_t use_26 = (flags & SDFGPU_DSH_FRONTIER_26) != 0;
+    HIP_TRY(h, hipMemsetAsync(d_total, 0, kDshCounterBytes, st));
+    hipLaunchKernelGGL(k_dsh_frontier_count, dsh_chunk_grid(m->n_live), dim3(kDshThreads), 0, st, m->g, m->table, m->pool, m->n_live, box, use_26, counts, masks,
+                       d_total);
+    HIP_TRY(h, hipGetLastError());
+    unsigned long long total = 0;
+    HIP_TRY(h, hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));                                       // the call's one synchronisation
+    *out_total = (int64_t)total;
+    if (total == 0 || (uint64_t)capacity < total) return SDFGPU_OK;
+    hipLaunchKernelGGL(k_dsh_frontier_offsets, dsh_grid((int64_t)live), dim3(kDshThreads), 0, st, m->pool.heads, (uint32_t)m->n_live, counts, offsets);
+    hipLaunchKernelGGL(k_dsh_frontier_write, dsh_chunk_grid(m->n_live), dim3(kDshThreads), 0, st, m->g, m->pool.heads, m->n_live, counts, offsets, masks, d_cells);
+    HIP_TRY(h, hipGetLastError());
+    return SDFGPU_OK;
+}
+
 // live chunks by state (synchronises st)
 int dsh_count(sdfgpu_dsh_map_object* m, uint64_t* chunk_filled, uint64_t* cell_filled, hipStream_t st) {
     sdfgpu_handle h = m->h;
@@ -1834,6 +2116,50 @@ int sdfgpu_dsh_extract_window(sdfgpu_dsh_map map, const int64_t lower[3], int64_
         uint32_t* d_bits = nullptr;
         return dsh_staged(map, [&](DshStaging& s) { d_records = s.out(records, n * 8); d_bits = s.out(bits, words * 4); },
                           [&] { return dsh_window_impl(map, lower, nx, ny, nz, unknown_is_filled, d_records, d_bits, nullptr); });
+    });
+}
+
+int sdfgpu_dsh_frontier_window_device(sdfgpu_dsh_map map, const int64_t lower[3], int64_t nx, int64_t ny, int64_t nz, uint32_t flags, uint32_t* d_bits,
+                                      void* stream) {
+    return dsh_entry(map, stream, [&]() -> int {
+        if (int rc = dsh_check_window(map->h, lower, nx, ny, nz, nullptr, d_bits)) return rc;
+        if (int rc = dsh_check_frontier_flags(map->h, flags)) return rc;
+        return dsh_frontier_window_impl(map, lower, nx, ny, nz, flags, d_bits, (hipStream_t)stream);
+    });
+}
+
+int sdfgpu_dsh_frontier_window(sdfgpu_dsh_map map, const int64_t lower[3], int64_t nx, int64_t ny, int64_t nz, uint32_t flags, uint32_t* bits) {
+    return dsh_entry(map, nullptr, [&]() -> int {
+        if (int rc = dsh_check_window(map->h, lower, nx, ny, nz, nullptr, bits)) return rc;
+        if (int rc = dsh_check_frontier_flags(map->h, flags)) return rc;
+        const size_t words = ((size_t)nx * (size_t)ny * (size_t)nz + 31) / 32;
+        uint32_t* d_bits = nullptr;
+        return dsh_staged(map, [&](DshStaging& s) { d_bits = s.out(bits, words * 4); },
+                          [&] { return dsh_frontier_window_impl(map, lower, nx, ny, nz, flags, d_bits, nullptr); });
+    });
+}
+
+int sdfgpu_dsh_frontier_cells_device(sdfgpu_dsh_map map, const int64_t lower[3], const int64_t extent[3], uint32_t flags, int64_t* d_cells,
+                                     int64_t capacity, int64_t* out_total, void* stream) {
+    return dsh_entry(map, stream, [&]() -> int {
+        DshFrontierBox box{};
+        if (int rc = dsh_frontier_cells_check(map, lower, extent, flags, d_cells, capacity, out_total, box)) return rc;
+        return dsh_frontier_cells_impl(map, box, flags, d_cells, capacity, out_total, (hipStream_t)stream);
+    });
+}
+
+int sdfgpu_dsh_frontier_cells(sdfgpu_dsh_map map, const int64_t lower[3], const int64_t extent[3], uint32_t flags, int64_t* cells, int64_t capacity,
+                              int64_t* out_total) {
+    return dsh_entry(map, nullptr, [&]() -> int {
+        DshFrontierBox box{};
+        if (int rc = dsh_frontier_cells_check(map, lower, extent, flags, cells, capacity, out_total, box)) return rc;
+        if (int rc = dsh_wait(map, nullptr)) return rc;
+        if (int rc = dsh_frontier_cells_impl(map, box, flags, nullptr, 0, out_total, nullptr)) return rc;
+        const int64_t total = *out_total;
+        if (total == 0 || capacity < total) return SDFGPU_OK;
+        int64_t* d_cells = nullptr;
+        return dsh_staged(map, [&](DshStaging& s) { d_cells = s.out(cells, (size_t)total * 24); },
+                          [&] { return dsh_frontier_cells_impl(map, box, flags, d_cells, total, out_total, nullptr); });
     });
 }
 

@@ -147,6 +147,49 @@ inline void dsh_plan_shrink(uint64_t live, uint64_t spare, uint64_t pool_cap, ui
     *out_table = table < table_cap ? table : table_cap;
 }
 
+// ---- frontier cells ---------------------------------------------------------------------------------------------
+constexpr uint32_t kDshFrontier26 = 1;                     // SDFGPU_DSH_FRONTIER_26
+
+// The candidates of a frontier list: a closed range of global cells per axis, clamped to the cells of the chunks in [-2^20, 2^20)
+// (no cell outside them belongs to a live chunk), and the chunks that hold them.  `chunks.empty` when the box holds no such cell.
+struct DshFrontierBox {
+    DshChunkRange chunks;
+    int64_t lo[3], hi[3];
+};
+
+// extent >= 1 on every axis and lower + extent - 1 is an int64
+inline bool dsh_frontier_box_ok(const int64_t lower[3], const int64_t extent[3]) {
+    for (int a = 0; a < 3; ++a)
+        if (extent[a] < 1 || lower[a] > INT64_MAX - (extent[a] - 1)) return false;
+    return true;
+}
+
+// The box lower .. lower + extent - 1 (dsh_frontier_box_ok holds), or with both null every cell a chunk can hold.
+inline DshFrontierBox dsh_frontier_box(const int64_t* lower, const int64_t* extent, const int64_t n[3]) {
+    DshFrontierBox b{};
+    for (int a = 0; a < 3; ++a) {
+        const int64_t first = -kDshChunkBias * n[a], last = kDshChunkBias * n[a] - 1;      // |.| <= 2^35
+        const int64_t lo = lower ? lower[a] : first, hi = lower ? lower[a] + (extent[a] - 1) : last;
+        b.lo[a] = lo < first ? first : lo;
+        b.hi[a] = hi > last ? last : hi;
+        if (b.lo[a] > b.hi[a]) { b.chunks.empty = 1; b.chunks.lo[a] = 0; b.chunks.hi[a] = -1; continue; }
+        b.chunks.lo[a] = dsh_floor_div(b.lo[a], n[a]);
+        b.chunks.hi[a] = dsh_floor_div(b.hi[a], n[a]);
+    }
+    return b;
+}
+
+// 64-bit words of a chunk's frontier mask (one bit per cell slot) in the list form's scratch
+SDFGPU_DSH_HD uint64_t dsh_frontier_mask_words(uint64_t cells_per_chunk) { return (cells_per_chunk + 63) / 64; }
+
+// The steps d in {-1, 0, 1} along one axis that lead from the cell at `l` of a chunk of n cells into the chunk `o` chunks further
+// (o in {-1, 0, 1}): the closed range lo .. hi, empty (lo > hi) where no step does.
+SDFGPU_DSH_HD void dsh_axis_steps(int64_t l, int64_t n, int o, int& lo, int& hi) {
+    if (o < 0) { lo = -1; hi = l == 0 ? -1 : -2; }
+    else if (o > 0) { lo = 1; hi = l == n - 1 ? 1 : 0; }
+    else { lo = l > 0 ? -1 : 0; hi = l < n - 1 ? 1 : 0; }
+}
+
 // ---- a frame of sensor rays ------------------------------------------------------------------------------------------
 constexpr double kDshMaxRangeCells = 65536.0;              // R = max_range / cell_size lies in (0, 65536]
 constexpr uint64_t kDshRayBoundCap = (uint64_t)1 << 62;    // where the bound below saturates
