@@ -96,7 +96,11 @@ public:
     DynamicSpatialHashedCollisionMapGrid() : number_of_components_(0), initialized_(false), components_valid_(false) {}
 
     bool IsInitialized() const { return initialized_; }
-    bool AreComponentsValid() const { return components_valid_; }     // never true: no method of the reference computes them
+    // Whether the component words of the map's records are those of the last UpdateConnectedComponents (an addition: no method of
+    // the reference computes them).  The MAP keeps that, not this object: two copies of a grid are two names for one map and agree.
+    // False before any update, after any call that set or removed something, and on an uninitialised map.  (number_of_components_
+    // and components_valid_ keep the reference's layout; the setters still clear the flag, but the map's answer is the truth.)
+    bool AreComponentsValid() const { return ComponentsInfo().valid; }
     std::string GetFrame() const { return frame_; }
     double GetResolution() const { return resolution_; }
     std::vector<double> GetCellSizes() const { return {resolution_, resolution_, resolution_}; }
@@ -272,6 +276,31 @@ public:
     void ShrinkToFit(const int64_t spare_chunks = 0) {
         RequireInitialized();
         Locked([&](sdfgpu_dsh_map m) { return sdfgpu_dsh_shrink(m, spare_chunks, nullptr); });
+    }
+
+    // ---- connected components (additions; include/sdfgpu.h "Dynamic spatial hashed map: connected components") -------
+    // Labels the connected components of the WHOLE map in place: every cell of a cell-filled chunk and every chunk-filled chunk (one
+    // node) gets its component's number in 1..K in the component word of its record, which Get, GetBatch, ExtractCollisionMapGrid
+    // and Export then hand out.  Nodes are joined iff they are of the same class and 6-face neighbours in global cell coordinates,
+    // across chunk borders too; cells of absent chunks connect nothing.  Classes: filled (occupancy > 0.5) and everything else, as
+    // CollisionMapGrid::UpdateConnectedComponents; with unknown_apart filled, free (< 0.5) and the rest (0.5 and NaN), so that known-free
+    // space is not joined with never-seen cells of live chunks.  Components are numbered by their first node in Export's order.
+    // Returns K; the stored K, without any launch, when the map says it is still valid under the same rule; 0 on an uninitialised
+    // map.  A map of 2^32 - 1 nodes or more is refused (std::runtime_error).  The contract is this project's own, UNVERIFIED.
+    uint32_t UpdateConnectedComponents(const bool unknown_apart = false) {
+        if (!initialized_) return 0;
+        const uint32_t flags = unknown_apart ? (uint32_t)SDFGPU_DSH_COMPONENTS_UNKNOWN_APART : 0u;
+        const Components now = ComponentsInfo();
+        uint32_t count = now.count;
+        if (!(now.valid && now.flags == flags)) Locked([&](sdfgpu_dsh_map m) { return sdfgpu_dsh_update_components(m, flags, &count, nullptr); });
+        number_of_components_ = count;
+        components_valid_ = true;
+        return count;
+    }
+    // (K of the last update, whether it still holds): (0, false) before any update and on an uninitialised map
+    std::pair<uint32_t, bool> GetNumConnectedComponents() const {
+        const Components now = ComponentsInfo();
+        return std::make_pair(now.count, now.valid);
     }
 
     // ---- ray casts (additions; include/sdfgpu.h "Ray casts") -----------------------------------------------------------
@@ -539,6 +568,17 @@ public:
     }
 
 private:
+    struct Components { uint32_t count, flags; bool valid; };
+    // what the map says about its components (host-only: no GPU call)
+    Components ComponentsInfo() const {
+        Components now = {0u, 0u, false};
+        if (!initialized_ || !collision_field_ || !collision_field_->map) return now;
+        int valid = 0;
+        const std::lock_guard<std::mutex> lock(collision_field_->ctx->mutex);
+        if (sdfgpu_dsh_components_info(collision_field_->map, &now.count, &now.flags, &valid) != SDFGPU_OK) return Components{0u, 0u, false};
+        now.valid = valid != 0;
+        return now;
+    }
     static uint32_t FrontierFlags(const bool use_26) { return use_26 ? (uint32_t)SDFGPU_DSH_FRONTIER_26 : 0u; }
     // positive cell counts whose product is at most 2^32 - 1 (what the window calls take)
     static bool WindowCountsOk(const int64_t nx, const int64_t ny, const int64_t nz) {

@@ -1372,6 +1372,46 @@ int sdfgpu_dsh_frontier_cells_device(sdfgpu_dsh_map map, const int64_t lower[3],
 int sdfgpu_dsh_frontier_cells(sdfgpu_dsh_map map, const int64_t lower[3], const int64_t extent[3], uint32_t flags, int64_t* cells,
                               int64_t capacity, int64_t* out_total);
 
+/* Dynamic spatial hashed map: connected components.  The labels of the whole map, written in place into
+ * the component word (the high 4 bytes) of its records.  The contract is this project's own -- the reference has no such method on
+ * this class -- and UNVERIFIED against it; tests/dsh_components_restated.py restates it.
+ *
+ * Nodes.  Every cell of a cell-filled chunk is a node; every chunk-filled chunk is ONE node (its cells share one record, are of one
+ *   class and connected to each other).  Cells of absent chunks are no nodes and connect nothing, as space outside a dense grid
+ *   connects nothing.
+ * Classes, from the record's low 4 bytes read as a float f.  With flags == 0 the dense rule of sdfgpu_components*: filled iff
+ *   f > 0.5f, everything else (unknown and NaN included) free.  With SDFGPU_DSH_COMPONENTS_UNKNOWN_APART three classes: f > 0.5f,
+ *   f < 0.5f, and the rest (f == 0.5f and NaN), so that known-free space is not joined with never-seen cells of live chunks.
+ * Connectivity.  Two nodes are joined iff they are of the same class and some cell of one is a 6-face neighbour, in global cell
+ *   coordinates (across chunk borders too), of some cell of the other.
+ * Numbering.  1..K in the order of each component's first node in export order: chunks in ascending (c_x, c_y, c_z), cells in
+ *   ascending slot (l_x n_y + l_y) n_z + l_z inside a chunk, a chunk-filled chunk at its chunk's place.  The labels do not depend on
+ *   the pool's slot order and are fully determined.
+ * Result.  The component word of every cell record of a cell-filled chunk, and of a chunk-filled chunk's record, becomes its
+ *   node's label.  No occupancy byte changes; table, pool layout, live counts and bytes_held stay, and Get, the windows, the export
+ *   and the casts return what they returned apart from that word -- and hand the labels out as part of the records.
+ * Size.  N = cell_filled * cells_per_chunk + chunk_filled must be below 2^32 - 1: otherwise SDFGPU_ERR_UNSUPPORTED_SIZE, and
+ *   nothing is written.  An empty map gives K = 0.
+ * Validity.  The map keeps K, the flags K was computed under, and whether both still hold.  sdfgpu_dsh_update_components sets all
+ *   three.  Every call that changes the map's content clears the validity: the setters and insert_points when at least one location
+ *   was valid, insert_rays / fuse_rays when at least one ray was hit or truncated, the removals and retain_box when they removed a
+ *   chunk.  A call that is refused, or sets or removes nothing, leaves it; sdfgpu_dsh_shrink moves records byte for byte and keeps
+ *   it (and the labels).  K and the validity are the MAP's: every holder of the handle sees the same.
+ *
+ * sdfgpu_dsh_update_components always recomputes (skipping a valid map is the caller's business).  It runs on `stream`, ordered
+ *   like every other call by the map's event, and synchronises the stream twice: behind the count of the chunks by state (N sizes
+ *   the scratch and is checked before anything is written) and at its end, to read K back.  out_count may be null.  Any flag bit
+ *   but SDFGPU_DSH_COMPONENTS_UNKNOWN_APART is SDFGPU_ERR_INVALID_ARGUMENT.  A call that fails after its first kernel leaves the
+ *   validity cleared.
+ *   Scratch: 4 bytes per live chunk, 4 bytes per node and the rank tables (a little over 1 bit per node), from the library's
+ *   allocator (red zones cover it).  It is the map's per-call scratch: kept between calls, counted in scratch_bytes and NOT
+ *   bounded by byte_limit.
+ * sdfgpu_dsh_components_info is host-only: it makes no GPU call and waits for nothing.  Any output may be null. */
+enum { SDFGPU_DSH_COMPONENTS_UNKNOWN_APART = 1 };   /* sdfgpu_dsh_update_components' flags */
+
+int sdfgpu_dsh_update_components(sdfgpu_dsh_map map, uint32_t flags, uint32_t* out_count, void* stream);
+int sdfgpu_dsh_components_info(sdfgpu_dsh_map map, uint32_t* out_count, uint32_t* out_flags, int* out_valid);
+
 /* Red zones (round 6).  With SDFGPU_REDZONE=1 in the environment when sdfgpu_create runs -- or after
  * sdfgpu_set_option(h, "redzone", 1) -- every device allocation of the library (scratch fields, status block, extrema slots,
  * staging buffers, sdfgpu_device_malloc memory) carries 4 KiB of canary bytes in front and behind, and every entry point that

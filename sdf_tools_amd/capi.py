@@ -51,6 +51,7 @@ EXPORTS = [
     "sdfgpu_dsh_get_device", "sdfgpu_dsh_get",
     "sdfgpu_dsh_extract_window_device", "sdfgpu_dsh_extract_window", "sdfgpu_dsh_export_device", "sdfgpu_dsh_export",
     "sdfgpu_dsh_frontier_window_device", "sdfgpu_dsh_frontier_window", "sdfgpu_dsh_frontier_cells_device", "sdfgpu_dsh_frontier_cells",
+    "sdfgpu_dsh_update_components", "sdfgpu_dsh_components_info",
 ]
 
 # include/sdfgpu.h "Projection": modes and per-point statuses
@@ -228,6 +229,8 @@ def load_library():
     L.sdfgpu_dsh_frontier_window.argtypes = [vp, vp, i64, i64, i64, u32, vp]
     L.sdfgpu_dsh_frontier_cells_device.argtypes = [vp, vp, vp, u32, vp, i64, vp, vp]
     L.sdfgpu_dsh_frontier_cells.argtypes = [vp, vp, vp, u32, vp, i64, vp]
+    L.sdfgpu_dsh_update_components.argtypes = [vp, u32, vp, vp]
+    L.sdfgpu_dsh_components_info.argtypes = [vp, vp, vp, vp]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is ctypes.c_int or name not in ("sdfgpu_version", "sdfgpu_last_error"):
@@ -1367,6 +1370,7 @@ DSH_CHUNK_NOT_REMOVED, DSH_CHUNK_REMOVED = 0, 1
 DSH_CAST_SKIPPED, DSH_CAST_CLEAR, DSH_CAST_CLEAR_IN_RANGE, DSH_CAST_BLOCKED = 0, 1, 2, 3
 DSH_CAST_SKIP_FIRST, DSH_CAST_SKIP_LAST, DSH_CAST_UNKNOWN_IS_FILLED = 1, 2, 4
 DSH_FRONTIER_26 = 1
+DSH_COMPONENTS_UNKNOWN_APART = 1
 DSH_MAX_CHUNK_CELLS = 32768
 DSH_COUNTS_DTYPE = np.dtype([(n, np.uint64) for n in ("chunk_filled", "cell_filled", "capacity_chunks", "table_capacity", "bytes_held",
                                                       "scratch_bytes", "byte_limit")])
@@ -1643,6 +1647,20 @@ class DshMap:
         self._check(self._lib.sdfgpu_dsh_frontier_cells_device(self._m, None if lo is None else lo.ctypes.data, None if ext is None else ext.ctypes.data,
                                                                int(flags), d_cells or None, int(capacity), ctypes.byref(total), stream or None))
         return total.value
+
+    def update_components(self, flags=0, stream=0):
+        """Label the connected components of the whole map in place (sdfgpu_dsh_update_components): the component word of every
+        cell record, and of every chunk-filled chunk's record, becomes its node's label in 1..K; flags 0 (filled / everything
+        else) or DSH_COMPONENTS_UNKNOWN_APART (filled / free / unknown and NaN).  Always recomputes.  Returns K."""
+        count = ctypes.c_uint32()
+        self._check(self._lib.sdfgpu_dsh_update_components(self._m, int(flags), ctypes.byref(count), stream or None))
+        return count.value
+
+    def components_info(self):
+        """(K of the last update, the flags it ran under, whether nothing has changed the map's content since): host-only"""
+        count, flags, valid = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_int()
+        self._check(self._lib.sdfgpu_dsh_components_info(self._m, ctypes.byref(count), ctypes.byref(flags), ctypes.byref(valid)))
+        return count.value, flags.value, bool(valid.value)
 
     def export(self):
         """(chunks DSH_CHUNK_DTYPE [n] in ascending (c_x, c_y, c_z) order, cells uint64 [cell-filled chunks, n_x, n_y, n_z])"""

@@ -961,6 +961,23 @@ PYBIND11_MODULE(pysdf_tools, m) {
             return d;
         }, py::arg("lower_index"), py::arg("nx"), py::arg("ny"), py::arg("nz"), py::arg("min_cells") = 1, py::arg("use_26") = true,
            "the 6-connected pieces of the window's frontier with at least min_cells cells: a dict of arrays (label, cells, lower and upper int64 [n, 3], centroid float64 [n, 3])")
+        .def("__copy__", [](const DshGrid& g) { return DshGrid(g); }, "the C++ copy: another name for the SAME device map (what one copy sets, the other reads)")
+        .def("UpdateConnectedComponents", &DshGrid::UpdateConnectedComponents, py::arg("unknown_apart") = false,
+             "labels the connected components of the whole map in place (the component word of every record); returns K, without a launch while the map is valid under the same rule")
+        .def("GetNumConnectedComponents", &DshGrid::GetNumConnectedComponents, "(K of the last update, whether it still holds)")
+        .def("update_components", [](DshGrid& g, uint32_t flags) {
+            if (flags & ~(uint32_t)SDFGPU_DSH_COMPONENTS_UNKNOWN_APART) throw std::invalid_argument("update_components knows the flag DSH_COMPONENTS_UNKNOWN_APART");
+            return g.UpdateConnectedComponents((flags & SDFGPU_DSH_COMPONENTS_UNKNOWN_APART) != 0);
+        }, py::arg("flags") = 0, "UpdateConnectedComponents under the C ABI's flags (0, or DSH_COMPONENTS_UNKNOWN_APART = 1); returns K")
+        .def("components_info", [](const DshGrid& g) {
+            uint32_t count = 0, flags = 0;
+            int valid = 0;
+            if (g.IsInitialized()) {
+                const std::lock_guard<std::mutex> lock(g.Context()->mutex);
+                if (sdfgpu_dsh_components_info(g.DeviceMapHandle(), &count, &flags, &valid) != SDFGPU_OK) throw std::runtime_error("sdfgpu_dsh_components_info failed");
+            }
+            return py::make_tuple(count, flags, valid != 0);
+        }, "(K of the last update, the flags it ran under, whether nothing has changed the map's content since): what the map keeps, host-only")
         .def("RemoveChunk", [](DshGrid& g, double x, double y, double z) { return g.RemoveChunk(x, y, z); })
         .def("RemoveChunks", [=](DshGrid& g, const py::array_t<double, py::array::c_style | py::array::forcecast>& locations) {
             const std::vector<bool> removed = g.RemoveChunks(dsh_locations(locations));

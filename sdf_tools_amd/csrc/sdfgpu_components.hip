@@ -24,25 +24,6 @@ __device__ __forceinline__ uint32_t bit_at(const uint32_t* __restrict__ bits, ui
     return (bits[g >> 5] >> (g & 31)) & 1u;
 }
 
-// ---- LDS union-find (one workgroup) ------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t lds_find(volatile uint32_t* l, uint32_t a) {
-    uint32_t p = l[a];
-    while (p != a) { a = p; p = l[a]; }
-    return a;
-}
-
-__device__ __forceinline__ void lds_union(uint32_t* l, uint32_t a, uint32_t b) {
-    for (;;) {
-        a = lds_find(l, a);
-        b = lds_find(l, b);
-        if (a == b) return;
-        if (a < b) { const uint32_t t = a; a = b; b = t; }
-        const uint32_t old = atomicMin(&l[a], b);    // a was a root: it now hangs under b; else retry from what a had become
-        if (old == a) return;
-        a = old;
-    }
-}
-
 struct CcArgs {
     const uint32_t* bits;
     uint32_t* L;

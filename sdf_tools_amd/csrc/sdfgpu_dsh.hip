@@ -25,6 +25,7 @@
 #pragma clang fp contract(off)
 #include "sdfgpu_context.hpp"
 #include "sdfgpu_dsh.hpp"
+#include "sdfgpu_unionfind.hpp"
 #include "sdfgpu.h"
 
 namespace sdfgpu {
@@ -96,7 +97,8 @@ __device__ __forceinline__ uint32_t dsh_find(const DshTable& t, uint64_t key) {
 }
 
 // ---- a batch: insert keys ------------------------------------------------------------------------------------------------------------
-// counters[0] = new chunks of this batch, counters[1] = operations that found no entry (cannot happen in a table sized for the batch)
+// counters[0] = new chunks of this batch, counters[1] = operations that found no entry (cannot happen in a table sized for the batch),
+// counters[2] = 1 once an operation of a batch named a valid location (every writer stores the same value)
 // The position of `key` in a table this launch inserts into: the thread that makes the entry numbers the chunk and lists it.
 __device__ __forceinline__ uint32_t dsh_claim(const DshTable& t, uint64_t key, uint32_t n_live, uint32_t* __restrict__ newlist, uint32_t* counters) {
     uint64_t pos = dsh_hash(key) & t.mask;
@@ -132,6 +134,7 @@ __global__ __launch_bounds__(kDshThreads) void k_dsh_insert(const DshGeometry g,
         found = dsh_claim(t, key, n_live, newlist, counters);
     op_pos[i] = found;
     op_cell[i] = cell;
+    if (found != kDshNoPos) counters[2] = 1u;
     if (statuses) statuses[i] = found != kDshNoPos ? set_status : (uint8_t)SDFGPU_DSH_NOT_SET;
 }
 
@@ -1009,22 +1012,28 @@ __global__ __launch_bounds__(kDshThreads) void k_dsh_frontier_count(const DshGeo
 // Where a chunk's cells start in the list: the frontier cells of the live chunks with a smaller key.  k_dsh_rank's counting (every
 // thread over all chunks, a tile of heads at a time through LDS) with the counts as weights: the rank and the scan over the chunks
 // in key order in one pass, free of scratch, atomics and order effects.
-__global__ __launch_bounds__(kDshThreads) void k_dsh_frontier_offsets(const DshChunkHead* __restrict__ heads, uint32_t n_live,
-                                                                      const uint32_t* __restrict__ counts, uint64_t* __restrict__ offsets) {
+// The counting itself, for every thread of the workgroup: the sum of weight(j) over the live chunks j with a key below `mine`.
+template <class Weight>
+__device__ __forceinline__ uint64_t dsh_weight_below(const DshChunkHead* __restrict__ heads, uint32_t n_live, uint64_t mine, Weight&& weight) {
     __shared__ uint64_t tile_key[kDshThreads];
-    __shared__ uint32_t tile_count[kDshThreads];
-    const int64_t s = dsh_item();
-    const bool live = s < n_live;
-    const uint64_t mine = live ? heads[s].key : kDshEmptyKey;
+    __shared__ uint32_t tile_weight[kDshThreads];
     uint64_t before = 0;
     for (uint32_t base = 0; base < n_live; base += kDshThreads) {
         const uint32_t j = base + threadIdx.x;
         tile_key[threadIdx.x] = j < n_live ? heads[j].key : kDshEmptyKey;      // (no key is above the empty key's value)
-        tile_count[threadIdx.x] = j < n_live ? counts[j] : 0;
+        tile_weight[threadIdx.x] = j < n_live ? weight(j) : 0u;
         __syncthreads();
-        for (int k = 0; k < kDshThreads; ++k) before += tile_key[k] < mine ? tile_count[k] : 0u;
+        for (int k = 0; k < kDshThreads; ++k) before += tile_key[k] < mine ? tile_weight[k] : 0u;
         __syncthreads();
     }
+    return before;
+}
+
+__global__ __launch_bounds__(kDshThreads) void k_dsh_frontier_offsets(const DshChunkHead* __restrict__ heads, uint32_t n_live,
+                                                                      const uint32_t* __restrict__ counts, uint64_t* __restrict__ offsets) {
+    const int64_t s = dsh_item();
+    const bool live = s < n_live;
+    const uint64_t before = dsh_weight_below(heads, n_live, live ? heads[s].key : kDshEmptyKey, [&](uint32_t j) { return counts[j]; });
     if (live) offsets[s] = before;
 }
 
@@ -1057,6 +1066,168 @@ __global__ __launch_bounds__(kDshThreads) void k_dsh_frontier_write(const DshGeo
     }
 }
 
+// ---- connected components (include/sdfgpu.h "Dynamic spatial hashed map: connected components") ---------------------
+// Nodes are numbered in export order (k_dsh_cc_bases: the weighted counting above), so a set's minimum node index is its first node
+// in that order and the union-find and the root ranking of sdfgpu_unionfind.hpp give 1..K directly.  One label word per node in the
+// scratch: k_dsh_cc_local writes every word once (plain stores), k_dsh_cc_merge joins across tiles and chunks with the agent-scope
+// union-find only, the flatten, the scan and the relabel follow behind kernel boundaries.  Nothing but the relabel writes the map.
+static_assert(kDshCcRankChunk == kRankChunk && kRankWords == kDshThreads, "the rank tables' layout as sdfgpu_dsh.hpp sizes it");
+
+__device__ __forceinline__ uint32_t dsh_cc_record_class(uint64_t record, bool apart) { return dsh_cc_class(__uint_as_float((uint32_t)record), apart); }
+__device__ __forceinline__ uint32_t dsh_cc_view_class(const DshChunkView& v, uint32_t k, bool apart) {
+    return dsh_cc_record_class(v.cells ? v.cells[k] : v.record, apart);
+}
+
+__global__ __launch_bounds__(kDshThreads) void k_dsh_cc_bases(const DshChunkHead* __restrict__ heads, uint32_t n_live, uint32_t cells_per_chunk,
+                                                              uint32_t* __restrict__ bases) {
+    const int64_t s = dsh_item();
+    const bool live = s < n_live;
+    const uint64_t before = dsh_weight_below(heads, n_live, live ? heads[s].key : kDshEmptyKey,
+                                             [&](uint32_t j) { return (uint32_t)dsh_cc_weight(heads[j].state, cells_per_chunk); });
+    if (live) bases[s] = (uint32_t)before;                                     // (N < 2^32 - 1: the host has seen to it)
+}
+
+// One workgroup per tile of kDshCcTile consecutive cell slots of a cell-filled chunk (a chunk-filled chunk: its one word).  Slots
+// ascend with the node index, so the tile-local minimum is the minimum of the tile's part of a component.  Class codes go into LDS,
+// a cell starts under the first cell of its z run inside the tile (run-start bits out of ballots, then the highest start bit at or
+// below the cell), y and x neighbours inside the tile are joined by union-find in LDS, and every cell's word becomes
+// node base + tile start + local root.  Pairs that straddle a tile are k_dsh_cc_merge's.
+__global__ __launch_bounds__(kDshThreads) void k_dsh_cc_local(const DshPool p, uint64_t n_live, uint32_t cells_per_chunk, uint32_t ny, uint32_t nz,
+                                                              uint32_t tiles, uint32_t apart, const uint32_t* __restrict__ bases, uint32_t* __restrict__ L) {
+    __shared__ uint32_t lab[kDshCcTile];
+    __shared__ uint32_t starts[kDshCcTile / 32];
+    __shared__ uint8_t cls[kDshCcTile];
+    const uint64_t w = (uint64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    if (w >= n_live * tiles) return;                                           // (the last row of a two-dimensional launch)
+    const uint64_t slot = w / tiles;
+    const uint32_t tile = (uint32_t)(w - slot * tiles), base = bases[slot];
+    if ((p.heads[slot].state & kDshStateMask) != kDshCellFilled) {             // (uniform over the workgroup)
+        if (tile == 0 && threadIdx.x == 0) L[base] = base;
+        return;
+    }
+    const uint32_t k0 = tile * kDshCcTile, nv = min(kDshCcTile, cells_per_chunk - k0), plane = ny * nz;
+    const uint64_t* const cells = p.cells + slot * (uint64_t)cells_per_chunk + k0;
+    for (uint32_t i = threadIdx.x; i < nv; i += kDshThreads) cls[i] = (uint8_t)dsh_cc_record_class(cells[i], apart != 0);
+    __syncthreads();
+    for (uint32_t b = 0; b < nv; b += kDshThreads) {                           // (every thread runs every round: the ballots are whole)
+        const uint32_t i = b + threadIdx.x;
+        const bool start = i < nv && (i == 0 || (k0 + i) % nz == 0 || cls[i - 1] != cls[i]);
+        const unsigned long long m = __ballot(start);
+        if ((threadIdx.x & 63) == 0) { starts[i >> 5] = (uint32_t)m; starts[(i >> 5) + 1] = (uint32_t)(m >> 32); }
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < nv; i += kDshThreads) {
+        uint32_t word = i >> 5, d = starts[word] & (0xFFFFFFFFu >> (31 - (i & 31)));
+        while (!d) d = starts[--word];                                         // (bit 0 of word 0 is set: the tile's first cell starts a run)
+        lab[i] = 32 * word + (31 - (uint32_t)__clz(d));
+    }
+    __syncthreads();
+    // y and x faces inside the tile.  A pair whose z predecessors are a same-class pair too is already joined through them.
+    for (uint32_t i = threadIdx.x; i < nv; i += kDshThreads) {
+        const uint32_t k = k0 + i, row = k / nz, iz = k - row * nz, ix = row / ny, iy = row - ix * ny, c = cls[i];
+        const bool zp = iz > 0 && i > 0 && cls[i - 1] == c;
+        if (iy > 0 && i >= nz && cls[i - nz] == c && !(zp && i > nz && cls[i - nz - 1] == c)) lds_union(lab, i, i - nz);
+        if (ix > 0 && i >= plane && cls[i - plane] == c && !(zp && i > plane && cls[i - plane - 1] == c)) lds_union(lab, i, i - plane);
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < nv; i += kDshThreads) L[base + k0 + i] = base + k0 + lds_find(lab, i);
+}
+
+// One workgroup per live chunk joins what k_dsh_cc_local could not: the pairs of the chunk's own cells that straddle a tile, and the
+// chunk's low x, y and z faces with the chunk beyond each -- three table lookups per chunk (lanes 0 .. 2), all four state pairs by
+// one loop over a face's pairs (dsh_cc_face_pair), two chunk-filled chunks by one link.  A pair is skipped where its predecessor
+// pair is of its class on both sides: that pair is linked (or skipped in turn), and each side's two cells are joined inside their
+// chunk by the end of this launch.  Every label word is read and written through uf_union alone.
+__global__ __launch_bounds__(kDshThreads) void k_dsh_cc_merge(const DshGeometry g, const DshTable t, const DshPool p, uint64_t n_live, uint32_t apart_flag,
+                                                              const uint32_t* __restrict__ bases, uint32_t* L) {
+    __shared__ DshChunkView beyond[3];
+    __shared__ uint32_t beyond_base[3];
+    __shared__ uint32_t beyond_live[3];
+    const uint64_t slot = (uint64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    if (slot >= n_live) return;                                                // (the last row of a two-dimensional launch)
+    const bool apart = apart_flag != 0;
+    const uint32_t cpc = (uint32_t)g.cells_per_chunk, ny = (uint32_t)g.n[1], nz = (uint32_t)g.n[2], plane = ny * nz;
+    if (threadIdx.x < 3) {
+        const int a = (int)threadIdx.x;
+        int64_t c[3];
+        dsh_unpack_key(p.heads[slot].key, c[0], c[1], c[2]);
+        const int64_t cx = c[0] - (a == 0), cy = c[1] - (a == 1), cz = c[2] - (a == 2);
+        uint32_t live = 0;
+        if (dsh_chunk_in_range(cx) && dsh_chunk_in_range(cy) && dsh_chunk_in_range(cz)) {
+            const uint32_t pos = dsh_find(t, dsh_pack_key(cx, cy, cz));
+            if (pos != kDshNoPos) {
+                const uint64_t other = t.slots[pos];
+                beyond[a] = dsh_view_slot(p, cpc, other, g.default_record);
+                beyond_base[a] = bases[other];
+                live = 1;
+            }
+        }
+        beyond_live[a] = live;
+    }
+    __syncthreads();
+    const DshChunkView own = dsh_view_slot(p, cpc, slot, g.default_record);
+    const uint32_t base = bases[slot];
+
+    if (own.cells)                                                             // (uniform over the workgroup)
+        for (uint32_t k = kDshCcTile + threadIdx.x; k < cpc; k += kDshThreads) {
+            const uint32_t first = k - k % kDshCcTile, row = k / nz, iz = k - row * nz, ix = row / ny, iy = row - ix * ny;
+            const uint32_t c = dsh_cc_record_class(own.cells[k], apart);
+            const bool zp = iz > 0 && dsh_cc_record_class(own.cells[k - 1], apart) == c;
+            if (zp && k == first) uf_union<RootIsSelf>(L, base + k, base + k - 1);
+            if (iy > 0 && k - nz < first && dsh_cc_record_class(own.cells[k - nz], apart) == c &&
+                !(zp && dsh_cc_record_class(own.cells[k - nz - 1], apart) == c))
+                uf_union<RootIsSelf>(L, base + k, base + k - nz);
+            if (ix > 0 && k - plane < first && dsh_cc_record_class(own.cells[k - plane], apart) == c &&
+                !(zp && dsh_cc_record_class(own.cells[k - plane - 1], apart) == c))
+                uf_union<RootIsSelf>(L, base + k, base + k - plane);
+        }
+
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        if (!beyond_live[a]) continue;                                         // (uniform over the workgroup)
+        const DshChunkView other = beyond[a];
+        const uint32_t other_base = beyond_base[a];
+        const uint32_t pairs = (uint32_t)dsh_cc_face_pairs(own.cells != nullptr, other.cells != nullptr, cpc / (uint32_t)g.n[a]);
+        for (uint32_t idx = threadIdx.x; idx < pairs; idx += kDshThreads) {
+            uint32_t k, k2, back;
+            dsh_cc_face_pair(a, idx, g.n, k, k2, back);
+            const uint32_t c = dsh_cc_view_class(own, k, apart);
+            if (dsh_cc_view_class(other, k2, apart) != c) continue;
+            if (back && dsh_cc_view_class(own, k - back, apart) == c && dsh_cc_view_class(other, k2 - back, apart) == c) continue;
+            uf_union<RootIsSelf>(L, (uint32_t)dsh_cc_node(base, own.cells != nullptr, k), (uint32_t)dsh_cc_node(other_base, other.cells != nullptr, k2));
+        }
+    }
+}
+
+// The root ranking of sdfgpu_unionfind.hpp over the N label words; every self-labelled node is a root.
+__global__ __launch_bounds__(kRankWords) void k_dsh_cc_flatten(uint32_t* __restrict__ L, uint64_t n, uint32_t* __restrict__ rb, uint32_t* __restrict__ wr,
+                                                               uint32_t* __restrict__ cc) {
+    rank_flatten(L, n, RankTables{rb, wr, cc, nullptr}, [](uint64_t) { return true; });
+}
+
+__global__ __launch_bounds__(kRankScanThreads) void k_dsh_cc_scan(const uint32_t* __restrict__ cc, uint32_t* __restrict__ co, uint64_t chunks,
+                                                                  uint32_t* __restrict__ count) {
+    rank_scan(cc, co, chunks, count);
+}
+
+// k_dsh_cc_local's grid again: a node's rank goes into the component word of its record, the high 4 bytes of the 8 (COLLISION_CELL:
+// occupancy | component), and of a chunk-filled chunk's head record.  Reads the node's own label word and the tables only.
+__global__ __launch_bounds__(kDshThreads) void k_dsh_cc_relabel(const DshPool p, uint64_t n_live, uint32_t cells_per_chunk, uint32_t tiles,
+                                                                const uint32_t* __restrict__ bases, const uint32_t* __restrict__ L,
+                                                                const uint32_t* __restrict__ rb, const uint32_t* __restrict__ wr, const uint32_t* __restrict__ co) {
+    const uint64_t w = (uint64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    if (w >= n_live * tiles) return;                                           // (the last row of a two-dimensional launch)
+    const uint64_t slot = w / tiles;
+    const uint32_t tile = (uint32_t)(w - slot * tiles), base = bases[slot];
+    if ((p.heads[slot].state & kDshStateMask) != kDshCellFilled) {             // (uniform over the workgroup)
+        if (tile == 0 && threadIdx.x == 0) reinterpret_cast<uint32_t*>(&p.heads[slot].record)[1] = rank_of(L[base], rb, wr, co);
+        return;
+    }
+    const uint32_t k0 = tile * kDshCcTile, nv = min(kDshCcTile, cells_per_chunk - k0);
+    uint32_t* const words = reinterpret_cast<uint32_t*>(p.cells + slot * (uint64_t)cells_per_chunk + k0);
+    for (uint32_t i = threadIdx.x; i < nv; i += kDshThreads) words[2 * i + 1] = rank_of(L[base + k0 + i], rb, wr, co);
+}
+
 size_t dsh_fuse_lds_bytes(uint64_t cells_per_chunk) { return (size_t)((cells_per_chunk + 15) / 16 * 16); }   // at most 32 KiB
 
 dim3 dsh_chunk_grid(uint64_t chunks) {                                        // one workgroup per chunk
@@ -1085,6 +1256,9 @@ struct sdfgpu_dsh_map_object {
     uint8_t* marks = nullptr;       // the mark plane of fused frames (null until the first): all zero between frames
     uint64_t marks_cap = 0;         // chunks it covers: at least pool_cap while a fused frame runs
     StreamOrder order;             // recorded behind every call: one on another stream waits for it first
+    uint32_t cc_count = 0;          // connected components: K of the last update, the flags it ran under, and whether nothing has
+    uint32_t cc_flags = 0;          // changed the map's content since
+    bool cc_valid = false;
 };
 
 namespace {
@@ -1343,11 +1517,12 @@ int dsh_batch(sdfgpu_dsh_map_object* m, bool chunk_sets, const LOC* d_loc, int64
     hipLaunchKernelGGL((k_dsh_insert<LOC>), grid, block, 0, st, m->g, m->table, d_loc, n, (uint32_t)m->n_live, op_pos, op_cell, newlist, counters, d_statuses,
                        (uint8_t)(chunk_sets ? SDFGPU_DSH_SET_CHUNK : SDFGPU_DSH_SET_CELL));
     HIP_TRY(h, hipGetLastError());
-    uint32_t back[2] = {0, 0};                                                  // new chunks, lost operations
+    uint32_t back[3] = {0, 0, 0};                                               // new chunks, lost operations, whether any operation was valid
     HIP_TRY(h, hipMemcpyAsync(back, counters, sizeof back, hipMemcpyDeviceToHost, st));
     HIP_TRY(h, hipStreamSynchronize(st));
     const int lost = back[1] ? fail(h, SDFGPU_ERR_HIP, "dsh: %u operations found no table entry (internal error)", back[1]) : SDFGPU_OK;
     if (int rc = dsh_commit_new(m, lost, back[0], newlist, false, nullptr, 0, st)) return rc;
+    if (back[2]) m->cc_valid = false;                                           // (a batch of invalid locations alone sets nothing)
     if (!chunk_sets) {
         hipLaunchKernelGGL(k_dsh_touch, grid, block, 0, st, m->table, m->pool.heads, op_pos, n);
         hipLaunchKernelGGL(k_dsh_expand, dsh_chunk_grid(m->n_live), block, 0, st, m->pool, m->n_live, (uint64_t)m->g.cells_per_chunk, m->g.default_record);
@@ -1461,6 +1636,7 @@ int dsh_rays_impl(sdfgpu_dsh_map_object* m, const DshRayFrame& f, const float* d
         return SDFGPU_OK;
     }();
     if (int rc = dsh_commit_new(m, walked, back.n_new, newlist, fuse != nullptr, &old_table, old_cap, st)) return rc;
+    if (back.counts[0] + back.counts[1]) m->cc_valid = false;                   // (a ray that is hit or truncated writes at least its first cell)
     hipLaunchKernelGGL(k_dsh_ray_touch, dsh_grid((int64_t)m->table_cap), block, 0, st, m->table, m->pool.heads, marks);
     hipLaunchKernelGGL(k_dsh_expand, dsh_chunk_grid(m->n_live), block, 0, st, m->pool, m->n_live, cpc, m->g.default_record);
     if (!fuse) {
@@ -1659,6 +1835,62 @@ int dsh_count(sdfgpu_dsh_map_object* m, uint64_t* chunk_filled, uint64_t* cell_f
     return SDFGPU_OK;
 }
 
+// The components of the whole map on `st`: the chunks counted by state and read back (N sizes the scratch, and a map of 2^32 - 1
+// nodes or more is refused before anything is written) | node bases | labels inside tiles | joins across tiles and chunks | flatten |
+// scan | relabel into the records | K read back.  Two synchronisations: behind the count and at the end.
+int dsh_components_impl(sdfgpu_dsh_map_object* m, uint32_t flags, uint32_t* out_count, hipStream_t st) {
+    sdfgpu_handle h = m->h;
+    static_assert(kDshComponentsUnknownApart == SDFGPU_DSH_COMPONENTS_UNKNOWN_APART, "the flag as sdfgpu_dsh.hpp states it");
+    if (flags & ~kDshComponentsUnknownApart)
+        return fail(h, SDFGPU_ERR_INVALID_ARGUMENT, "dsh: update_components knows the flag COMPONENTS_UNKNOWN_APART (got 0x%x)", flags);
+    DshCall call{m, st};
+    if (int rc = call.open()) return rc;
+    const uint64_t cpc = (uint64_t)m->g.cells_per_chunk;
+    uint64_t chunk_filled = 0, cell_filled = 0;
+    if (int rc = dsh_count(m, &chunk_filled, &cell_filled, st)) return rc;
+    const uint64_t nodes = dsh_cc_nodes(cell_filled, chunk_filled, cpc);
+    if (!dsh_cc_nodes_ok(nodes))
+        return fail(h, SDFGPU_ERR_UNSUPPORTED_SIZE, "dsh: update_components numbers fewer than 2^32 - 1 nodes (the map has %llu)", (unsigned long long)nodes);
+    uint32_t count = 0;
+    if (m->n_live) {
+        const size_t live = (size_t)m->n_live;
+        const uint64_t rank = rank_chunks(nodes);
+        const uint32_t tiles = (uint32_t)dsh_cc_tiles(cpc), apart = (flags & kDshComponentsUnknownApart) != 0;
+        uint32_t *bases = nullptr, *labels = nullptr;
+        void* tables = nullptr;
+        size_t cut_bytes = 0;
+        if (int rc = dsh_scratch(m, [&](DshCut& c) {
+                bases = c.take<uint32_t>((size_t)dsh_cc_bases_bytes(live)); labels = c.take<uint32_t>((size_t)dsh_cc_label_bytes(nodes));
+                tables = c.take<char>((size_t)dsh_cc_rank_bytes(nodes));
+                cut_bytes = c.total - kDshCounterBytes;
+            })) return rc;
+        if (cut_bytes != dsh_cc_scratch_bytes(live, nodes) || rank_tables_bytes(rank) != dsh_cc_rank_bytes(nodes))
+            return fail(h, SDFGPU_ERR_HIP, "dsh: the components' scratch is not laid out as sdfgpu_dsh.hpp sizes it (internal error)");
+        const RankTables t = rank_tables_at(tables, rank);
+        uint32_t* const d_count = dsh_counters(m);                              // K
+        const dim3 block(kDshThreads), live_grid = dsh_grid((int64_t)live), chunk_grid = dsh_chunk_grid(m->n_live), tile_grid = dsh_chunk_grid(m->n_live * tiles);
+        m->cc_valid = false;                                                    // (until K is back: a call that fails half way leaves no claim)
+        hipLaunchKernelGGL(k_dsh_cc_bases, live_grid, block, 0, st, m->pool.heads, (uint32_t)m->n_live, (uint32_t)cpc, bases);
+        hipLaunchKernelGGL(k_dsh_cc_local, tile_grid, block, 0, st, m->pool, m->n_live, (uint32_t)cpc, (uint32_t)m->g.n[1], (uint32_t)m->g.n[2], tiles, apart, bases,
+                           labels);
+        hipLaunchKernelGGL(k_dsh_cc_merge, chunk_grid, block, 0, st, m->g, m->table, m->pool, m->n_live, apart, bases, labels);
+        hipLaunchKernelGGL(k_dsh_cc_flatten, dim3((unsigned)rank), dim3(kRankWords), 0, st, labels, nodes, t.rb, t.wr, t.cc);
+        hipLaunchKernelGGL(k_dsh_cc_scan, dim3(1), dim3(kRankScanThreads), 0, st, (const uint32_t*)t.cc, t.co, rank, d_count);
+        hipLaunchKernelGGL(k_dsh_cc_relabel, tile_grid, block, 0, st, m->pool, m->n_live, (uint32_t)cpc, tiles, bases, (const uint32_t*)labels, (const uint32_t*)t.rb,
+                           (const uint32_t*)t.wr, (const uint32_t*)t.co);
+        HIP_TRY(h, hipGetLastError());
+        const hipError_t copied = hipMemcpyAsync(&count, d_count, 4, hipMemcpyDeviceToHost, st);
+        const hipError_t waited = hipStreamSynchronize(st);                     // (whatever the copy said: `count` is not left to a pending copy)
+        HIP_TRY(h, copied);
+        HIP_TRY(h, waited);
+    }
+    m->cc_count = count;
+    m->cc_flags = flags;
+    m->cc_valid = true;
+    if (out_count) *out_count = count;
+    return SDFGPU_OK;
+}
+
 int dsh_export_impl(sdfgpu_dsh_map_object* m, sdfgpu_dsh_chunk* d_chunks, int64_t chunk_capacity, void* d_cells, int64_t cell_capacity,
                     int64_t* out_chunks, int64_t* out_cells, hipStream_t st) {
     sdfgpu_handle h = m->h;
@@ -1723,6 +1955,7 @@ int dsh_remove_impl(sdfgpu_dsh_map_object* m, const double* d_loc, int64_t n, co
     if (removed == 0) return SDFGPU_OK;
     if (removed > n_live) return fail(h, SDFGPU_ERR_HIP, "dsh: %u of %u chunks flagged (internal error)", removed, n_live);
     const uint32_t keep = n_live - removed;
+    m->cc_valid = false;
     if (keep) {
         hipLaunchKernelGGL(k_dsh_pair_count, dim3((unsigned)tiles), block, 0, st, flags, n_live, keep, tile_counts);
         hipLaunchKernelGGL(k_dsh_pair_scan, dim3(1), block, 0, st, tile_counts, (uint32_t)tiles, counters);
@@ -2161,6 +2394,18 @@ int sdfgpu_dsh_frontier_cells(sdfgpu_dsh_map map, const int64_t lower[3], const 
         return dsh_staged(map, [&](DshStaging& s) { d_cells = s.out(cells, (size_t)total * 24); },
                           [&] { return dsh_frontier_cells_impl(map, box, flags, d_cells, total, out_total, nullptr); });
     });
+}
+
+int sdfgpu_dsh_update_components(sdfgpu_dsh_map map, uint32_t flags, uint32_t* out_count, void* stream) {
+    return dsh_entry(map, stream, [&]() -> int { return dsh_components_impl(map, flags, out_count, (hipStream_t)stream); });
+}
+
+int sdfgpu_dsh_components_info(sdfgpu_dsh_map map, uint32_t* out_count, uint32_t* out_flags, int* out_valid) {
+    if (dsh_check_map(map)) return SDFGPU_ERR_INVALID_ARGUMENT;                // (the host's record of the map: no GPU call)
+    if (out_count) *out_count = map->cc_count;
+    if (out_flags) *out_flags = map->cc_flags;
+    if (out_valid) *out_valid = map->cc_valid ? 1 : 0;
+    return SDFGPU_OK;
 }
 
 int sdfgpu_dsh_export_device(sdfgpu_dsh_map map, sdfgpu_dsh_chunk* d_chunks, int64_t chunk_capacity, void* d_cells, int64_t cell_capacity,

@@ -2,7 +2,7 @@
 // constants, the packing of a chunk coordinate into a table key, the hash, and the planning of the table's and the pool's sizes.
 // Plain C++ without a HIP header, as sdfgpu_plan.hpp and sdfgpu_policy.hpp are: sdfgpu_dsh.hip includes it for its kernels and its host
 // code, and tests/dsh_plan_harness.cpp, tests/dsh_rays_plan_harness.cpp, tests/dsh_fusion_plan_harness.cpp and
-// tests/dsh_remove_plan_harness.cpp drive the arithmetic on the CPU under -fsanitize=address,undefined.
+// tests/dsh_remove_plan_harness.cpp (and the later dsh_*_plan_harness.cpp) drive the arithmetic on the CPU under -fsanitize=address,undefined.
 #pragma once
 #include <stdint.h>
 
@@ -188,6 +188,52 @@ SDFGPU_DSH_HD void dsh_axis_steps(int64_t l, int64_t n, int o, int& lo, int& hi)
     if (o < 0) { lo = -1; hi = l == 0 ? -1 : -2; }
     else if (o > 0) { lo = 1; hi = l == n - 1 ? 1 : 0; }
     else { lo = l > 0 ? -1 : 0; hi = l < n - 1 ? 1 : 0; }
+}
+
+// ---- connected components ----------------------------------------------------------------------------------------
+// A node is a cell of a cell-filled chunk or a whole chunk-filled chunk.  Nodes are numbered in export order: a chunk's node base is
+// the number of nodes of the live chunks with a smaller key, its cells follow in slot order.  N nodes must stay below 2^32 - 1.
+constexpr uint32_t kDshComponentsUnknownApart = 1;         // SDFGPU_DSH_COMPONENTS_UNKNOWN_APART
+constexpr uint32_t kDshCcTile = 8192;                      // cell slots one workgroup of k_dsh_cc_local labels in LDS
+constexpr uint32_t kDshCcRankChunk = 8192;                 // kRankChunk of sdfgpu_unionfind.hpp (a device header this one cannot include)
+constexpr uint64_t kDshCcMaxNodes = 0xFFFFFFFFull;         // N < this
+
+// weight of a live chunk in the node numbering, and N from the counts by state (64-bit: 2^31 chunks of 2^15 cells stay below 2^47)
+SDFGPU_DSH_HD uint64_t dsh_cc_weight(uint32_t state, uint64_t cells_per_chunk) { return (state & kDshStateMask) == kDshCellFilled ? cells_per_chunk : 1; }
+SDFGPU_DSH_HD uint64_t dsh_cc_nodes(uint64_t cell_filled, uint64_t chunk_filled, uint64_t cells_per_chunk) { return cell_filled * cells_per_chunk + chunk_filled; }
+SDFGPU_DSH_HD bool dsh_cc_nodes_ok(uint64_t nodes) { return nodes < kDshCcMaxNodes; }
+SDFGPU_DSH_HD uint64_t dsh_cc_tiles(uint64_t cells_per_chunk) { return (cells_per_chunk + kDshCcTile - 1) / kDshCcTile; }
+// the node of cell slot k of a chunk with node base `base` (a chunk-filled chunk is its base alone)
+SDFGPU_DSH_HD uint64_t dsh_cc_node(uint64_t base, bool has_cells, uint32_t k) { return base + (has_cells ? (uint64_t)k : 0); }
+
+// The class of an occupancy: filled (1) is > 0.5; everything else is free (0), or with `apart` free is < 0.5 and the rest -- 0.5 and
+// NaN -- is unknown (2).
+SDFGPU_DSH_HD uint32_t dsh_cc_class(float occupancy, bool apart) { return occupancy > 0.5f ? 1u : (apart && !(occupancy < 0.5f)) ? 2u : 0u; }
+
+// The idx-th pair of cells across a chunk's low face along `axis`: cell slot k of the chunk, slot k2 of the chunk one lower along the
+// axis, and `back`, the step to the pair before it along z (x and y faces) or y (z faces), 0 where there is none.  A pair whose
+// predecessor pair is of its own class on both sides is joined through that pair and needs no link.
+SDFGPU_DSH_HD void dsh_cc_face_pair(int axis, uint32_t idx, const int64_t n[3], uint32_t& k, uint32_t& k2, uint32_t& back) {
+    const uint32_t nx = (uint32_t)n[0], ny = (uint32_t)n[1], nz = (uint32_t)n[2];
+    if (axis == 0) { k = idx; k2 = idx + (nx - 1) * ny * nz; back = idx % nz ? 1u : 0u; }
+    else if (axis == 1) { const uint32_t ix = idx / nz, iz = idx - ix * nz; k = ix * ny * nz + iz; k2 = k + (ny - 1) * nz; back = iz ? 1u : 0u; }
+    else { k = idx * nz; k2 = k + nz - 1; back = idx % ny ? nz : 0u; }
+}
+// candidate pairs of one face: its cells, but ONE where both chunks are chunk-filled (two nodes, one link)
+SDFGPU_DSH_HD uint64_t dsh_cc_face_pairs(bool own_cells, bool other_cells, uint64_t face_cells) { return own_cells || other_cells ? face_cells : 1; }
+
+// the update's scratch behind the counters: per-chunk node bases | one label word per node | the rank tables (rb | wr | cc | co of
+// sdfgpu_unionfind.hpp), each section rounded up to 256 bytes
+inline uint64_t dsh_cc_rank_bytes(uint64_t nodes) {
+    const uint64_t chunks = (nodes + kDshCcRankChunk - 1) / kDshCcRankChunk;
+    return (2 * chunks * (kDshCcRankChunk / 32) + 2 * chunks) * 4;
+}
+inline uint64_t dsh_cc_bases_bytes(uint64_t live) { return live * 4; }
+inline uint64_t dsh_cc_label_bytes(uint64_t nodes) { return nodes * 4; }
+// (dsh_components_impl cuts its sections by the three functions above and refuses to run where its cut's total is not this)
+inline uint64_t dsh_cc_scratch_bytes(uint64_t live, uint64_t nodes) {
+    const auto up = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };
+    return up(dsh_cc_bases_bytes(live)) + up(dsh_cc_label_bytes(nodes)) + up(dsh_cc_rank_bytes(nodes));
 }
 
 // ---- a frame of sensor rays ------------------------------------------------------------------------------------------

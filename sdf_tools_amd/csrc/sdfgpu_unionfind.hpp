@@ -1,6 +1,6 @@
 // sdfgpu_unionfind.hpp -- what the analysis families share on the device: the lock-free union-find over uint32 words in HBM, the
 // root ranking that turns roots into 1..K in scan order, and the layout of the ranking's tables.  Device code: included by
-// sdfgpu_components.hip, sdfgpu_convex.hip and sdfgpu_topology.hip and by nothing else (sdfgpu_context.hpp pulls in no kernels).
+// sdfgpu_components.hip, sdfgpu_convex.hip, sdfgpu_topology.hip and sdfgpu_dsh.hip and by nothing else (sdfgpu_context.hpp pulls in no kernels).
 // Every __global__ kernel stays in its unit, under its own name, as a thin kernel around a body defined here.
 //
 // Union-find invariant, relied on by every find: a word only ever DECREASES, and a word that names a parent names an index BELOW
@@ -62,6 +62,25 @@ __device__ __forceinline__ void uf_union(uint32_t* L, uint32_t a, uint32_t b) {
         const uint32_t old = min_agent(&L[a], b);     // a was a root: it now hangs under b
         if (Root::is_root(old, a)) return;
         a = old;                                      // a had been linked meanwhile (old < a): join its new root instead
+    }
+}
+
+// ---- the same over LDS words of one workgroup (k_cc_local, k_dsh_cc_local): a root holds its own index ------------------------
+__device__ __forceinline__ uint32_t lds_find(volatile uint32_t* l, uint32_t a) {
+    uint32_t p = l[a];
+    while (p != a) { a = p; p = l[a]; }
+    return a;
+}
+
+__device__ __forceinline__ void lds_union(uint32_t* l, uint32_t a, uint32_t b) {
+    for (;;) {
+        a = lds_find(l, a);
+        b = lds_find(l, b);
+        if (a == b) return;
+        if (a < b) { const uint32_t t = a; a = b; b = t; }
+        const uint32_t old = atomicMin(&l[a], b);    // a was a root: it now hangs under b; else retry from what a had become
+        if (old == a) return;
+        a = old;
     }
 }
 
